@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- molecules/s of the hierarchical encoder training step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 0..4] [--rnn GRU|LSTM]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 0..4] [--rnn GRU|LSTM] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 ``--gpus N`` (N > 1) without WORLD_SIZE in the environment starts the N rank processes itself (ggpm_amd/launcher.py: the
@@ -37,7 +37,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-import ggpm_amd          # noqa: E402  (sets GPU_MAX_HW_QUEUES=8 before the HIP runtime starts; see ggpm_amd/__init__.py)
+import ggpm_amd          # noqa: E402  (sets HSA_ENABLE_IPC_MODE_LEGACY before the HIP runtime starts; see ggpm_amd/__init__.py)
 import numpy as np       # noqa: E402
 import torch             # noqa: E402
 
@@ -248,7 +248,7 @@ def _sum_outputs(*outs):
 class Workload:
     """One (config, message function) pair on this rank: model, optimizer, device-resident batches."""
 
-    def __init__(self, cfg, rnn, a, rank, world, dev, gate_dtype="f32"):
+    def __init__(self, cfg, rnn, a, rank, world, dev, gate_dtype="f32", keep_outputs=False):
         from ggpm_amd.nnutils import make_cuda
         from ggpm_amd.parallel import FlatGradSync, broadcast_parameters
         from ggpm_amd.property_vae import HierEncoderVAE
@@ -281,6 +281,34 @@ class Workload:
             import itertools
             from ggpm_amd.dataloader import DevicePrefetcher
             self.host_iter = iter(DevicePrefetcher(itertools.cycle(self.pool), device=dev, depth=2))
+        # --dump-outputs: the warm-up runs for a wall-time budget, so the state the timed region starts from differs from run to
+        # run.  Every attempt at the headline region starts instead from the seeded initial state kept here, on batches 0, 1, ...
+        # of the pool, and its last step is recorded (`outputs`): the same inputs on every run and every build.
+        self.keep_outputs, self.outputs = keep_outputs, None
+        self._start_state = self._train_state() if keep_outputs else None
+
+    def _train_state(self):
+        """Parameters and optimizer state (FlatAdam on the device: one flat parameter buffer, its moments, the step count)."""
+        o = self.opt
+        return {"flat": o.flat.detach().clone(), "m": o._m.clone(), "v": o._v.clone(), "t": o._t}
+
+    def _restore_train_state(self, st):
+        o = self.opt
+        with torch.no_grad():
+            o.flat.copy_(st["flat"])
+            o._m.copy_(st["m"])
+            o._v.copy_(st["v"])
+        o._t = st["t"]
+
+    def _collect_outputs(self, last):
+        """What the step hands its caller, as host arrays: the loss, the KL term and the four encoder outputs of the last
+        step, then the gradient it produced and the parameters after its Adam update (both in ``model.parameters()`` order)."""
+        out = {k: v.cpu().numpy() for k, v in last.items()}
+        spans = list(zip(self.sync.offsets, self.sync.params))
+        # (slice by slice to the host: no device allocation, so the caching allocator's pool is what the timing left it)
+        out["grads"] = np.concatenate([self.sync.flat[o:o + p.numel()].cpu().numpy() for o, p in spans])
+        out["params"] = np.concatenate([self.opt.flat.detach()[o:o + p.numel()].cpu().numpy() for o, p in spans])
+        return out
 
     # steps the host may be ahead of the GPU.  This loop reads nothing back, so without a bound the host (2.0 ms of enqueue
     # per 2.8 ms step) gets 8-10 steps ahead inside a 30-step region, every step in flight holds its own ~1 GB arena of saved
@@ -289,7 +317,7 @@ class Workload:
     # loop is bounded by its own metrics read (vae_train.py:86-94 reads them every step); here: step i waits for step i - 2.
     MAX_LEAD = 2
 
-    def step(self, i):
+    def step(self, i, keep=False):
         from ggpm_amd.property_vae import rsample
         m = self.model
         tree, graph = next(self.host_iter) if self.host_iter is not None else self.dev_batches[i % len(self.dev_batches)]
@@ -310,6 +338,9 @@ class Workload:
         self.sync.all_reduce()
         self.opt.step()
         ev.record()
+        if keep:
+            self._last_step = {"loss": loss.detach(), "kl": kl.detach(), "hroot": hroot.detach(), "hnode": hnode.detach(),
+                               "hinter": hinter.detach(), "hatom": hatom.detach()}
         return loss
 
     def _any_rank(self, flag: bool) -> bool:
@@ -339,18 +370,24 @@ class Workload:
         world size: the ranks decide together (`_any_rank`), since each attempt holds collectives."""
         import torch.distributed as dist
         readings = []
+        keep = self.keep_outputs and what == "value"
         for attempt in range(4):
+            if keep:
+                self._restore_train_state(self._start_state)
             _settle_gc()
             self.fence()
             allocs0 = torch.cuda.memory_stats(self.dev).get("num_device_alloc", 0)
             self._lead_wait = 0.0
             t0 = time.perf_counter()
             for i in range(steps):
-                self.step(first + i)
+                self.step(first + i, keep and i == steps - 1)
             host = time.perf_counter() - t0 - self._lead_wait      # (enqueue time proper: without the waits of MAX_LEAD)
             self.fence()
             elapsed = time.perf_counter() - t0
             grew = torch.cuda.memory_stats(self.dev).get("num_device_alloc", 0) - allocs0
+            if keep:
+                self.outputs = self._collect_outputs(self._last_step)
+                self._last_step = None
             if self.world > 1:
                 t = torch.tensor([elapsed], dtype=torch.float64, device=self.dev)
                 dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -425,7 +462,7 @@ class Workload:
         warm = i
         self.warmup_run = warm
         log("warm-up done (%d steps); timing %d steps" % (warm, a.steps))
-        elapsed, host_enqueue = self.timed(a.steps, warm, "value")
+        elapsed, host_enqueue = self.timed(a.steps, 0 if self.keep_outputs else warm, "value")
         log("timed region done: %.3f ms/step (host enqueue %.3f ms/step)" % (1e3 * elapsed / a.steps,
                                                                              1e3 * host_enqueue / a.steps))
         chains = [int(getattr(t[0][3], "ggpm_chain", 0)) for t in self.dev_batches]
@@ -996,6 +1033,30 @@ def _emit(obj):
         os.write(_REAL_STDOUT, line)
 
 
+DUMP_BUDGET_BYTES = 60 << 20       # array data of --dump-outputs: with the .npy headers, under 64 MB however it is counted
+DUMP_WHOLE_BYTES = 1 << 20         # arrays up to this size are always written whole
+
+
+def write_outputs(path, arrays, budget=DUMP_BUDGET_BYTES):
+    """arrays -> path/<name>.npy, float32 (float64 stays float64).  Past `budget` bytes in all, every array larger than
+    DUMP_WHOLE_BYTES is cut to the same fraction of its elements: a seeded sample of flat positions, in ascending order, so
+    that two runs with the same arguments write the same positions."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32).reshape(v.shape)
+              for k, v in arrays.items()}
+    big = [k for k, v in arrays.items() if v.nbytes > DUMP_WHOLE_BYTES]
+    room = budget - sum(v.nbytes for k, v in arrays.items() if k not in big)
+    big_bytes = sum(arrays[k].nbytes for k in big)
+    if big_bytes > room:
+        for k in big:
+            flat = arrays[k].reshape(-1)
+            n = int(flat.size * room / big_bytes)
+            arrays[k] = flat[np.sort(np.random.default_rng(0).choice(flat.size, n, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    return {k: list(v.shape) for k, v in arrays.items()}
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1029,7 +1090,17 @@ def parse_args(argv=None):
     ap.add_argument("--no-configs4", action="store_true", help="skip the configs[4] leg of the default line (\"configs4\": fp32 + bf16)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline step computed in its last timed step as DIR/<name>.npy "
+                         "(loss, kl, hroot, hnode, hinter, hatom, grads, params; float32, at most 64 MB in all).  The timed "
+                         "region then starts from the seeded initial state on batches 0, 1, ... of the pool, so the same "
+                         "arguments give the same inputs on every run")
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs is not None and (a.host_input or a.only_vae):
+        ap.error("--dump-outputs records the headline step on device-resident batches: not with --host-input / --only-vae")
+    return a
 
 
 def launch_ranks(a, argv):
@@ -1094,8 +1165,12 @@ def main():
             dist.barrier()
             dist.destroy_process_group()
         return
-    main_wl = Workload(cfg, rnn, a, rank, world, dev, gate_dtype=a.dtype)
+    main_wl = Workload(cfg, rnn, a, rank, world, dev, gate_dtype=a.dtype, keep_outputs=a.dump_outputs is not None)
     m = main_wl.measure(lib, rank)
+    if a.dump_outputs is not None and rank == 0:
+        shapes = write_outputs(a.dump_outputs, main_wl.outputs)
+        log("outputs of the last timed step written to %s: %s" % (a.dump_outputs, shapes))
+    main_wl.outputs = None
     n_motif, n_attach = cfg["vocab"]
     result = {
         "metric": "HierMPNEncoder fwd+bwd target row (SURVEY 8(d): encoder + KL heads + optimizer, tree fixed-point hint on; "

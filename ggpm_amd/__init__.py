@@ -5,14 +5,12 @@ device side: hand-written HIP kernels behind the C ABI in include/ggpm_hip.h (gg
 """
 import os as _os
 
-# One process uses up to five HIP streams (main, the high-priority atom-level stream, the second stream for transposes and
-# weight gradients, a copy stream, the collective's own) and RCCL brings its own; with the default of 4 hardware queues
-# streams share a queue and the encoder's second stream ends up behind the main one (measured: 5.94 instead of
-# 5.45 ms/step).  Read by the HIP runtime when it starts, so it is set HERE -- importing the package comes before the
-# first HIP call of any program that uses it -- and never overrides a value the user chose.
-_os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# GPU_MAX_HW_QUEUES is left to the HIP runtime (default 4) or the user: the hardware queues are shared by every process on
+# the device, so a library does not raise their count for its own streams ("Hardware queues").
 # multi-process GPU work (RCCL, tensors shared between rank processes): this pool's host driver supports dmabuf IPC only; with
-# the legacy mode hipIpcGetMemHandle fails with "invalid argument".  Same rule: before the runtime starts, never overriding.
+# the legacy mode hipIpcGetMemHandle fails with "invalid argument".  Read by the HIP runtime when it starts, so it is set
+# HERE -- importing the package comes before the first HIP call of any program that uses it -- and never overrides a value
+# the user chose.
 _os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 __all__ = ["GRU", "LSTM", "MPNEncoder", "HierMPNEncoder", "MotifEncoder", "IncMPNEncoder", "IncHierMPNEncoder",

@@ -71,8 +71,7 @@ def rank_env(rank: int, world: int, port: int, base: Optional[Dict[str, str]] = 
                GROUP_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), GGPM_LAUNCHED_BY="ggpm_amd.launcher")
     # the host driver of this pool only supports dmabuf IPC (RCCL / tensor sharing across processes)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    # main + high-priority atom stream + second stream + copy stream + the collective's own: more than the default 4
-    env.setdefault("GPU_MAX_HW_QUEUES", "8")
+    # (GPU_MAX_HW_QUEUES: inherited as it is -- the hardware queues are shared with every other process on the device)
     return env
 
 

@@ -270,3 +270,37 @@ def test_bench_harness_term_equals_the_plain_sum_of_the_outputs():
         assert abs(float(a) - float(b)) <= 1e-12 * abs(float(b)) and torch.equal(ga, gb), views
     ragged = (torch.ones(2, 3, requires_grad=True), torch.ones(2, 4, requires_grad=True))
     assert float(bench._sum_outputs(*ragged)) == 14.0
+
+
+def test_bench_dump_outputs_are_float_bounded_and_reproducible(tmp_path):
+    """``bench.py --dump-outputs DIR``: one DIR/<name>.npy per array, float32 (float64 kept), at most 64 MB in all; past the
+    budget the large arrays are cut to a seeded sample, the same positions on every run, and small ones stay whole."""
+    import glob
+    import os
+    import numpy as np
+    import pytest
+    import bench
+    rng = np.random.default_rng(3)
+    arrays = {"loss": np.array(1.25, dtype=np.float32), "hatom": rng.standard_normal((1000, 300)).astype(np.float32),
+              "params": rng.standard_normal(10_000_000), "grads": rng.standard_normal(10_000_000).astype(np.float32),
+              "index": np.arange(7, dtype=np.int64)}
+    for d in ("a", "b"):
+        bench.write_outputs(str(tmp_path / d), arrays)
+    files = sorted(glob.glob(str(tmp_path / "a" / "*.npy")))
+    assert [os.path.basename(f) for f in files] == ["grads.npy", "hatom.npy", "index.npy", "loss.npy", "params.npy"]
+    assert sum(os.path.getsize(f) for f in files) <= 64e6
+    for f in files:
+        x, y = np.load(f), np.load(f.replace(os.sep + "a" + os.sep, os.sep + "b" + os.sep))
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), f
+    assert np.load(files[3]).shape == () and float(np.load(files[3])) == 1.25
+    assert np.load(files[2]).dtype == np.float32 and np.array_equal(np.load(files[2]), np.arange(7))
+    params = np.load(files[4])
+    assert params.dtype == np.float64 and 0 < params.size < 10_000_000 and np.isin(params[:1000], arrays["params"]).all()
+    # under the budget nothing is cut
+    small = {"hatom": arrays["hatom"]}
+    bench.write_outputs(str(tmp_path / "c"), small)
+    assert np.array_equal(np.load(str(tmp_path / "c" / "hatom.npy")), arrays["hatom"])
+    # --steps is the number of timed steps: it has to be one at least
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+    assert bench.parse_args(["--steps", "7", "--dump-outputs", "d"]).steps == 7

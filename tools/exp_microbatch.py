@@ -1,6 +1,5 @@
 """Experiment: one batch of 32 as two concurrent 16-molecule halves on two streams vs as one batch (dev tool)."""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, bench
 from ggpm_amd import synth

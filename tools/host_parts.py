@@ -1,7 +1,6 @@
 """Host enqueue time of each part of the bench step (dev tool; no profiler, no synchronisation inside the step)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 import bench
 from ggpm_amd import _dev
