@@ -14,7 +14,7 @@ from . import build as _build
 
 _LIB = None
 
-# name -> (restype, [argtypes]); mirrors include/ggpm_hip.h one to one
+# name -> (restype, [argtypes]); mirrors include/ggpm_hip.h one to one (the level calls' last two: opts, stream)
 P = c_void_p
 I = c_int
 SIGNATURES = {
@@ -40,26 +40,19 @@ SIGNATURES = {
     "ggpm_adam_step": (I, [P, P, P, P, c_size_t, c_float, c_float, c_float, c_float, c_float, I, P]),
     "ggpm_onehot": (I, [P, I, I, P, I, I, I, P]),
     "ggpm_embed_graph": (I, [P, I, P, I, I, I, I, P, I, P, I, P]),
-    "ggpm_level_gate_dtype": (I, [I]),
     "ggpm_level_bf16_storage": (I, [I, I]),
-    "ggpm_backward_skip_x_sums": (None, [I]),
     "ggpm_gru_backward_stashes": (I, [P, I, I, I, POINTER(c_void_p), POINTER(c_void_p)]),
     "ggpm_lstm_backward_stashes": (I, [P, I, I, I, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p)]),
     "ggpm_sum_slots": (I, [P, I, c_size_t, P, P]),
     "ggpm_gru_pack_floats": (c_size_t, [I]),
-    "ggpm_gru_forward": (I, [I, I, I, P, P, P, P, I, P, I, P, P, I, P, P, P, P, P, P, P, P, P, P, I, P]),
+    "ggpm_gru_forward": (I, [I, I, I, P, P, P, P, I, P, I, P, P, I, P, P, P, P, P, P, P, P, P, P, I, P, P]),
     "ggpm_gru_backward_workspace_bytes": (c_size_t, [I, I, I]),
     "ggpm_gru_backward": (I, [I, I, I, P, P, I, P, I, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P,
-                              P, I, P, I, P, P, I, P, c_size_t, I, P]),
-    "ggpm_gru_weight_grads": (I, [I, I, I, P, P, P, P, c_size_t, P, I, P, I, P, P, I, P]),
-    "ggpm_gru_sparse_forward": (I, [I, I, I, P, P, P, P, P, P, I, P, I, P, P, I, P, P, P, P, P, P, P, P, P, P, I, P]),
+                              P, I, P, I, P, P, I, P, c_size_t, I, P, P]),
+    "ggpm_gru_weight_grads": (I, [I, I, I, P, P, P, P, c_size_t, P, I, P, I, P, P, I, P, P]),
+    "ggpm_gru_sparse_forward": (I, [I, I, I, P, P, P, P, P, P, I, P, I, P, P, I, P, P, P, P, P, P, P, P, P, P, I, P, P]),
     "ggpm_gru_sparse_backward": (I, [I, I, I, P, P, P, I, P, I, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P,
-                                     P, I, P, I, P, P, I, P, c_size_t, P]),
-    "ggpm_backward_defer_stash": (None, [P, P, P, P]),
-    "ggpm_level_prefer_narrow": (None, [I]),
-    "ggpm_forward_gather_state": (None, [P, P, P]),
-    "ggpm_backward_scatter_state": (None, [P, P, P]),
-    "ggpm_weights_packed": (None, [I]),
+                                     P, I, P, I, P, P, I, P, c_size_t, P, P]),
     "ggpm_weight_grads_stacked_workspace_bytes": (c_size_t, [I, I]),
     "ggpm_gru_weight_grads_stacked": (I, [I, I, I, P, P, P, P, P, P, P, I, P, I, P, P, I, P, c_size_t, P]),
     "ggpm_lstm_weight_grads_stacked": (I, [I, I, I, P, P, P, P, P, P, P, I, P, I, P, I, P, I, P, c_size_t, P]),
@@ -69,15 +62,15 @@ SIGNATURES = {
     "ggpm_decode_steps_backward_async": (I, [P, P, P, P, P, P, P, P, c_size_t, P, P, P, P, c_size_t, P, P, P, c_size_t, P, P]),
     "ggpm_decode_join": (I, []),
     "ggpm_lstm_pack_floats": (c_size_t, [I]),
-    "ggpm_lstm_forward": (I, [I, I, I, P, P, P, P, P, I, P, I, P, I, P, I, P, P, P, P, P, P, P, P, P, P, P, I, P]),
+    "ggpm_lstm_forward": (I, [I, I, I, P, P, P, P, P, I, P, I, P, I, P, I, P, P, P, P, P, P, P, P, P, P, P, I, P, P]),
     "ggpm_lstm_backward_workspace_bytes": (c_size_t, [I, I, I]),
     "ggpm_lstm_backward": (I, [I, I, I, P, P, I, P, I, P, I, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P,
-                               P, P, P, P, P, I, P, I, P, I, P, I, P, c_size_t, I, P]),
-    "ggpm_lstm_weight_grads": (I, [I, I, I, P, P, P, c_size_t, P, I, P, I, P, I, P, I, P]),
+                               P, P, P, P, P, I, P, I, P, I, P, I, P, c_size_t, I, P, P]),
+    "ggpm_lstm_weight_grads": (I, [I, I, I, P, P, P, c_size_t, P, I, P, I, P, I, P, I, P, P]),
     "ggpm_lstm_sparse_forward": (I, [I, I, I, P, P, P, P, P, P, P, P, I, P, I, P, I, P, I, P, P, P, P, P, P, P, P, P, P,
-                                     P, I, P]),
+                                     P, I, P, P]),
     "ggpm_lstm_sparse_backward": (I, [I, I, I, P, P, P, I, P, I, P, I, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P,
-                                      P, P, P, P, P, P, P, I, P, I, P, I, P, I, P, c_size_t, P]),
+                                      P, P, P, P, P, P, P, I, P, I, P, I, P, I, P, c_size_t, P, P]),
     "ggpm_rsample_forward": (I, [P, P, P, I, I, P, P, P]),
     "ggpm_rsample_backward": (I, [P, P, P, P, P, I, I, P, P, P]),
     "ggpm_softmax_ce": (I, [P, I, I, I, P, I, P, P, P, P, I, P, P, P]),

@@ -510,13 +510,13 @@ class _AtomDecode(torch.autograd.Function):
                     E1, H, depth, P(h_prev), P(c_prev), P(frz[t]), P(X[0]), P(X[1]), P(X[2]), P(X[3]), P(Wi[:, I:]),
                     Wi.stride(0), P(Wo_g[:, I:]), Wo_g.stride(0), P(Wu[:, I:]), Wu.stride(0), P(Wf[:, I:]), Wf.stride(0),
                     _vp(ptr[("pred_rp", t)]), _vp(ptr[("pred_col", t)]), P(Hs[t]), P(Cs[t]), P(Qs[t]), P(st[0]), P(st[1]),
-                    P(st[2]), P(st[3]), P(st[4]), P(wpack), 1, s), "lstm_sparse_forward")
+                    P(st[2]), P(st[3]), P(st[4]), P(wpack), 1, None, s), "lstm_sparse_forward")
                 c_prev = Cs[t, depth]
             else:
                 _lib.check(lib.ggpm_gru_sparse_forward(
                     E1, H, depth, P(h_prev), P(frz[t]), P(X[0]), P(X[1]), P(X[2]), P(Wz[:, I:]), Wz.stride(0), P(Ur),
                     Ur.stride(0), P(bu), P(Wh[:, I:]), Wh.stride(0), _vp(ptr[("pred_rp", t)]), _vp(ptr[("pred_col", t)]),
-                    P(Hs[t]), P(Qs[t]), P(st[0]), P(st[1]), P(st[2]), P(st[3]), P(st[4]), P(wpack), 1, s),
+                    P(Hs[t]), P(Qs[t]), P(st[0]), P(st[1]), P(st[2]), P(st[3]), P(st[4]), P(wpack), 1, None, s),
                     "gru_sparse_forward")
             h_prev = Hs[t, depth]
             nei, node = NEI[a0:a1], NODE[a0:a1]
@@ -598,7 +598,7 @@ class _AtomDecode(torch.autograd.Function):
                     _vp(ptr[("pred_col", t)]), _vp(ptr[("succ_rp", t)]), _vp(ptr[("succ_col", t)]), P(Hs[t]), P(Cs[t]),
                     P(Qs[t]), P(st[0]), P(st[1]), P(st[2]), P(st[3]), P(st[4]), P(dH), P(dC), P(dH2), P(dC2), P(dX[0]),
                     P(dX[1]), P(dX[2]), P(dX[3]), P(tmp[0]), H, P(tmp[1]), H, P(tmp[2]), H, P(tmp[3]), H, P(work),
-                    work.numel() * 4, s), "lstm_sparse_backward")
+                    work.numel() * 4, None, s), "lstm_sparse_backward")
                 dC, dC2 = dC2, dC
             else:
                 _lib.check(lib.ggpm_gru_sparse_backward(
@@ -606,7 +606,7 @@ class _AtomDecode(torch.autograd.Function):
                     Wh.stride(0), _vp(ptr[("pred_rp", t)]), _vp(ptr[("pred_col", t)]), _vp(ptr[("succ_rp", t)]),
                     _vp(ptr[("succ_col", t)]), P(Hs[t]), P(Qs[t]), P(st[0]), P(st[1]), P(st[2]), P(st[3]), P(st[4]), P(dH),
                     P(dH2), P(dX[0]), P(dX[1]), P(dX[2]), P(tmp[0]), H, P(tmp[1]), H, P(tmp[3]), P(tmp[2]), H, P(work),
-                    work.numel() * 4, s), "gru_sparse_backward")
+                    work.numel() * 4, None, s), "gru_sparse_backward")
             dH, dH2 = dH2, dH
             torch._foreach_add_([dX_tot] + acc, [dX] + tmp)
         # ---- parameter gradients, once
@@ -673,6 +673,7 @@ class _AtomDecodeCompact(torch.autograd.Function):
             if _dev.ATOM_ASYNC:
                 deferred = True
                 _INFLIGHT.append((desc, _keep, X_all, Hs_all, Cs_all, Qs_all, St_all, wpack, tmp, params))
+        packed = ctypes.byref(F_.LevelOpts(weights_packed=1)) if _dev.PACK_ONCE else None
         for t in (() if _dev.DECODE_DRIVER else range(T)):
             n = plan.nloc[t]
             src = _vp(cp[("srcH", t)])
@@ -682,8 +683,7 @@ class _AtomDecodeCompact(torch.autograd.Function):
             hs, qs = Hs_all[qoff[t]:qoff[t + 1]], Qs_all[roff[t]:roff[t + 1]]
             st = St_all[:, roff[t]:roff[t + 1]]
             fz, rp, col = _vp(frz_loc + plan.floc_off[t]), _vp(ptr[("lpred_rp", t)]), _vp(ptr[("lpred_col", t)])
-            if t > 0 and _dev.PACK_ONCE:
-                lib.ggpm_weights_packed(1)          # same weights, same `wpack`: packed by the first step
+            opts = packed if t > 0 else None        # same weights, same `wpack`: packed by the first step
             if lstm:
                 c_in = torch.empty(n, Hp, **f32)
                 _lib.check(lib.ggpm_gather_rows(P(Cs_all), Hp, src, n, Hp, P(c_in), Hp, 0, 0, s), "gather_rows")
@@ -691,12 +691,12 @@ class _AtomDecodeCompact(torch.autograd.Function):
                     n, H, depth, P(h_in), P(c_in), fz, P(x[0]), P(x[1]), P(x[2]), P(x[3]), P(Wi[:, I:]),
                     Wi.stride(0), P(Wo_g[:, I:]), Wo_g.stride(0), P(Wu[:, I:]), Wu.stride(0), P(Wf[:, I:]), Wf.stride(0),
                     rp, col, P(hs), P(Cs_all[qoff[t]:qoff[t + 1]]), P(qs), P(st[0]), P(st[1]), P(st[2]), P(st[3]), P(st[4]),
-                    P(wpack), 1, s), "lstm_sparse_forward")
+                    P(wpack), 1, opts, s), "lstm_sparse_forward")
             else:
                 _lib.check(lib.ggpm_gru_sparse_forward(
                     n, H, depth, P(h_in), fz, P(x[0]), P(x[1]), P(x[2]), P(Wz[:, I:]), Wz.stride(0), P(Ur),
                     Ur.stride(0), P(bu), P(Wh[:, I:]), Wh.stride(0), rp, col, P(hs), P(qs), P(st[0]), P(st[1]), P(st[2]),
-                    P(st[3]), P(st[4]), P(wpack), 1, s), "gru_sparse_forward")
+                    P(st[3]), P(st[4]), P(wpack), 1, opts, s), "gru_sparse_forward")
         # ---- read-out of all steps at once: incoming messages (at their step's time) -> atoms -> clusters / candidates
         ns_tot, n_inst = plan.aoff[-1], plan.ioff[-1]
         NEI = torch.empty(ns_tot, Hp, **f32)
@@ -842,26 +842,27 @@ class _AtomDecodeCompact(torch.autograd.Function):
             fz = _vp(frz_loc + plan.floc_off[t])
             csr = (_vp(ptr[("lpred_rp", t)]), _vp(ptr[("lpred_col", t)]), _vp(ptr[("lsucc_rp", t)]), _vp(ptr[("lsucc_col", t)]))
             srcF = _vp(cp[("srcF", t)])
-            if t < T - 1 and _dev.PACK_ONCE:
-                lib.ggpm_weights_packed(1)          # same weights, same `work`: the transposes were packed by the first call
+            # the stashes go to the stacked buffers, contracted once in tail(); same weights, same `work`: the transposes were
+            # packed by the first call
+            dq = DQ_all[qoff[t]:].data_ptr()
+            stash = (DG_all[0, roff[t]:].data_ptr(), DG_all[1, roff[t]:].data_ptr()) + \
+                ((DG_all[2, roff[t]:].data_ptr(), dq) if lstm else (dq, None))
+            opts = F_.LevelOpts(weights_packed=int(t < T - 1 and _dev.PACK_ONCE), defer_stash=stash)
             if lstm:
                 dcin = torch.empty(n, Hp, **f32)
-                lib.ggpm_backward_defer_stash(P(DG_all[0, roff[t]:]), P(DG_all[1, roff[t]:]), P(DG_all[2, roff[t]:]),
-                                              P(DQ_all[qoff[t]:]))
                 _lib.check(lib.ggpm_lstm_sparse_backward(
                     n, H, depth, fz, P(xg), P(Wi[:, I:]), Wi.stride(0), P(Wo_g[:, I:]), Wo_g.stride(0), P(Wu[:, I:]),
                     Wu.stride(0), P(Wf[:, I:]), Wf.stride(0), *csr, P(hs), P(Cs_all[qoff[t]:qoff[t + 1]]), P(qs), P(st[0]),
                     P(st[1]), P(st[2]), P(st[3]), P(st[4]), P(dhd), P(dCF[foff[t]:foff[t + 1]]), P(dhin), P(dcin), P(dx[0]),
                     P(dx[1]), P(dx[2]), P(dx[3]), P(acc[0]), H, P(acc[1]), H, P(acc[2]), H, P(acc[3]), H, P(work),
-                    work.numel() * 4, s), "lstm_sparse_backward")
+                    work.numel() * 4, ctypes.byref(opts), s), "lstm_sparse_backward")
                 _lib.check(lib.ggpm_scatter_rows(P(dcin), Hp, srcF, n, Hp, P(dCF), Hp, 1, s), "scatter_rows")
             else:
-                lib.ggpm_backward_defer_stash(P(DG_all[0, roff[t]:]), P(DG_all[1, roff[t]:]), P(DQ_all[qoff[t]:]), None)
                 _lib.check(lib.ggpm_gru_sparse_backward(
                     n, H, depth, fz, P(xg), P(Wz[:, I:]), Wz.stride(0), P(Ur), Ur.stride(0), P(Wh[:, I:]), Wh.stride(0),
                     *csr, P(hs), P(qs), P(st[0]), P(st[1]), P(st[2]), P(st[3]), P(st[4]), P(dhd), P(dhin), P(dx[0]),
-                    P(dx[1]), P(dx[2]), P(acc[0]), H, P(acc[1]), H, P(acc[3]), P(acc[2]), H, P(work), work.numel() * 4, s),
-                    "gru_sparse_backward")
+                    P(dx[1]), P(dx[2]), P(acc[0]), H, P(acc[1]), H, P(acc[3]), P(acc[2]), H, P(work), work.numel() * 4,
+                    ctypes.byref(opts), s), "gru_sparse_backward")
             # the frozen rows' gradient goes to the step that produced their state (rows recomputed here: none)
             _lib.check(lib.ggpm_scatter_rows(P(dhin), Hp, srcF, n, Hp, P(dF), Hp, 1, s), "scatter_rows")
         # ---- parameter gradients, once

@@ -159,55 +159,25 @@ int ggpm_gemm_tall_grouped(int M, int N, int count, const ggpm_gemm_problem* p, 
 #define GGPM_GEMM_MAX_GROUP 4          // members of ggpm_gemm_grouped / segments of ggpm_gemm_ksegments
 typedef ggpm_gemm_problem GgpmGemmProblem;
 
-// Message passing on a tree reaches a fixed point after as many steps as the longest dependency chain: the next dense
-// level forward of this thread (GRU or LSTM) issues only `run_depth` of its `depth` steps (0 / >= depth: all of them);
-// the caller then replicates the last computed slot of every stash array (encoder.hip).  Consumed by one call.
-void ggpm_forward_run_depth(int run_depth);
-int ggpm_take_run_depth();
-// The same acyclic structure makes the Jacobian of a tree level's recurrence nilpotent: with a longest dependency chain
-// of C messages, d(h^{D-k}) is exactly zero for k >= C, so the backward of such a level only has to run its steps
-// t = D .. lo with lo = max(1, D - C + 1); every skipped launch would compute exact zeros and every skipped stash slot
-// would add exact zeros to the weight-gradient contractions.  The next dense level backward / weight-gradient call of
-// this thread stops at step `lo` (<= 1: all steps).  Consumed by one call each.
-void ggpm_backward_lo_depth(int lo);
-int ggpm_take_backward_lo();
-void ggpm_wgrad_lo_depth(int lo);
-int ggpm_take_wgrad_lo();
-// The next ggpm_gru_weight_grads of this thread leaves db_u alone: the caller forms it with ggpm_gru_bias_u_grad on another
-// stream (the encoder driver's atom level: the column sum over all dq stash rows, 52 us, runs on the main stream beside the
-// tall contractions instead of behind them).  `lo` as ggpm_wgrad_lo_depth; `csws`: 256 * Hp floats.
-void ggpm_wgrad_skip_bias_u(int yes);
-int ggpm_gru_bias_u_grad(int E1, int H, int depth, int lo, float* work, float* dbu, float* csws, ggpm_stream_t stream);
-// ggpm_backward_defer_stash (include/ggpm_hip.h): caller-owned gate-gradient stashes for the next sparse backward of this
-// thread.  -> true (and the pointers) once.
-bool ggpm_take_defer_stash(float* (&out)[4]);
-// The next SPARSE backward of this thread (GRU or LSTM) leaves the hidden-half weight gradients to a later call of
-// ggpm_gru_sparse_weight_grads / ggpm_lstm_sparse_weight_grads with the same arguments -- the same launches, on whatever stream
-// that call names (tree_level.hip: beside the rest of the level's backward instead of in front of it).  Consumed by one call.
-void ggpm_sparse_backward_skip_wgrads(int yes);
-bool ggpm_take_sparse_skip_wgrads();
+// ggpm_level_opts (include/ggpm_hip.h) of a call that passed NULL: all defaults
+inline const ggpm_level_opts& ggpm_opts_or_default(const ggpm_level_opts* opts) {
+    static const ggpm_level_opts none = {};
+    return opts ? *opts : none;
+}
+// db_u of a dense GRU level by itself, for a ggpm_gru_weight_grads call with opts->skip_bias_u (the encoder driver's atom
+// level: the column sum over all dq stash rows, 52 us, runs on the main stream beside the tall contractions instead of behind
+// them).  `lo` as ggpm_level_opts.lo; `csws`: 256 * Hp floats.  Reads opts->gate_dtype.
+int ggpm_gru_bias_u_grad(int E1, int H, int depth, int lo, float* work, float* dbu, float* csws, const ggpm_level_opts* opts,
+                         ggpm_stream_t stream);
+// The hidden-half weight gradients a sparse backward with opts->skip_sparse_wgrads left out: call with the same arguments
+// (tree_level.hip: beside the rest of the level's backward instead of in front of it).  Both read opts->gate_dtype.
 int ggpm_gru_sparse_weight_grads(int E1, int H, int depth, const float* Hs, const float* Ss, const float* Gs, float* work,
                                  size_t work_bytes, float* dWz_h, int ld_dwz, float* dUr, int ld_dur, float* dbu, float* dWh_h,
-                                 int ld_dwh, ggpm_stream_t stream);
+                                 int ld_dwh, const ggpm_level_opts* opts, ggpm_stream_t stream);
 int ggpm_lstm_sparse_weight_grads(int E1, int H, int depth, const float* Hs, const float* Ss, float* work, size_t work_bytes,
                                   float* dWi_h, int ld_dwi, float* dWo_h, int ld_dwo, float* dWu_h, int ld_dwu, float* dWf_h,
-                                  int ld_dwf, ggpm_stream_t stream);
+                                  int ld_dwf, const ggpm_level_opts* opts, ggpm_stream_t stream);
 hipEvent_t ggpm_wgrad_event(int i);          // small pool of re-recordable events, per thread (mpn_gru.hip)
-// ggpm_backward_skip_x_sums (include/ggpm_hip.h): consumed by the next dense level backward of this thread.
-bool ggpm_take_skip_x_sums();
-// ggpm_level_prefer_narrow (include/ggpm_hip.h): state of this thread's switch (mpn_gru.hip).
-bool ggpm_prefer_narrow();
-// ggpm_weights_packed (include/ggpm_hip.h): the next level / sparse call of this thread finds its packed weights in place.
-bool ggpm_take_weights_packed();
-// ggpm_forward_gather_state / ggpm_backward_scatter_state (include/ggpm_hip.h): consumed by the next sparse forward /
-// backward of this thread.  -> true (and the pointers) once.
-bool ggpm_take_gather_state(const float** src_h, const float** src_c, const int32_t** idx);
-bool ggpm_take_scatter_state(float** dst_h, float** dst_c, const int32_t** idx);
-
-// Gate-product dtype of the level calls issued by this thread: 0 fp32 (default), 1 bf16 operands.  Set by the encoder
-// drivers from ggpm_enc_dims.gate_dtype for the duration of their call (mpn_gru.hip).
-void ggpm_set_gate_dtype(int dtype);
-int ggpm_gate_dtype();
 
 // Levels whose depth-loop arrays are kept in bf16 under gate mode 1 (tile_mma.h: "bf16 STORAGE"): dense training levels large
 // enough that every weight-gradient contraction over their stashes runs on the bf16 tall kernel, which then reads the

@@ -60,15 +60,16 @@ extern "C" int ggpm_decode_steps_forward(const ggpm_decode_steps* d, const float
         // the step's start state goes straight into slot 0 of its block: frozen rows from the blocks of the steps that
         // produced them, zero for the rows the step recomputes (srcH = -1) -- exactly the masked state sparse_forward would
         // build.  The step's first launch (q^0 = U_r h^0 / qf^0 = Wf_h h^0) fetches the rows through srcH and writes slot 0
-        // on the way (ggpm_forward_gather_state); GGPM_DECODE_FOLD=0: a gather launch of its own, as before.
+        // on the way (ggpm_level_opts.gather_*); GGPM_DECODE_FOLD=0: a gather launch of its own, as before.
+        ggpm_level_opts opts = {};
+        opts.weights_packed = t > 0;      // same weights, same `wpack`: packed by the first step
         int rc = GGPM_OK;
         if (fold) {
-            ggpm_forward_gather_state(Hs_all, d->lstm ? Cs_all : nullptr, d->srcH[t]);
+            opts.gather_h = Hs_all; opts.gather_c = d->lstm ? Cs_all : nullptr; opts.gather_idx = d->srcH[t];
         } else {
             rc = ggpm_gather_rows(Hs_all, Hp, d->srcH[t], n, Hp, hs, Hp, 0, 0, stream);
             if (rc) return rc;
         }
-        if (t > 0) ggpm_weights_packed(1);      // same weights, same `wpack`: packed by the first step
         if (d->lstm) {
             float* cs = Cs_all + o.q0 * Hp;
             if (!fold) {
@@ -77,11 +78,11 @@ extern "C" int ggpm_decode_steps_forward(const ggpm_decode_steps* d, const float
             }
             rc = ggpm_lstm_sparse_forward(n, H, d->depth, hs, cs, d->frozen[t], x, x + xs, x + 2 * xs, x + 3 * xs, W[0],
                                           ldw[0], W[1], ldw[1], W[2], ldw[2], W[3], ldw[3], d->pred_rowptr[t], d->pred_col[t],
-                                          hs, cs, qs, st[0], st[1], st[2], st[3], st[4], wpack, 1, stream);
+                                          hs, cs, qs, st[0], st[1], st[2], st[3], st[4], wpack, 1, &opts, stream);
         } else {
             rc = ggpm_gru_sparse_forward(n, H, d->depth, hs, d->frozen[t], x, x + xs, x + 2 * xs, W[0], ldw[0], W[1], ldw[1],
                                          bu, W[2], ldw[2], d->pred_rowptr[t], d->pred_col[t], hs, qs, st[0], st[1], st[2],
-                                         st[3], st[4], wpack, 1, stream);
+                                         st[3], st[4], wpack, 1, &opts, stream);
         }
         if (rc) return rc;
     }
@@ -117,26 +118,30 @@ extern "C" int ggpm_decode_steps_backward(const ggpm_decode_steps* d, const floa
         float* dg[3];
         for (int k = 0; k < 3; ++k) dg[k] = DG_all + (size_t)k * dg_stride + o.r0 * Hp;
         float* dhd = dF + o.f0 * Hp;
-        if (t < d->T - 1) ggpm_weights_packed(1);      // same weights, same `work`: the transposes were packed by the first call
-        int rc;
+        ggpm_level_opts opts = {};
+        opts.weights_packed = t < d->T - 1;      // same weights, same `work`: the transposes were packed by the first call
         // the frozen rows' gradient goes to the step that produced their state (rows recomputed here: none): added there by
-        // the step's last launch (ggpm_backward_scatter_state), or by scatter launches of their own
-        if (fold) ggpm_backward_scatter_state(dF, d->lstm ? dCF : nullptr, d->srcF[t]);
+        // the step's last launch (ggpm_level_opts.scatter_*), or by scatter launches of their own
+        if (fold) { opts.scatter_h = dF; opts.scatter_c = d->lstm ? dCF : nullptr; opts.scatter_idx = d->srcF[t]; }
+        // the stashes go to the stacked buffers, contracted once after the loop (ggpm_*_weight_grads_stacked)
+        float* const dq = DQ_all + o.q0 * Hp;
+        opts.defer_stash[0] = dg[0]; opts.defer_stash[1] = dg[1];
+        opts.defer_stash[2] = d->lstm ? dg[2] : dq; opts.defer_stash[3] = d->lstm ? dq : nullptr;
+        int rc;
         if (d->lstm) {
-            ggpm_backward_defer_stash(dg[0], dg[1], dg[2], DQ_all + o.q0 * Hp);
             rc = ggpm_lstm_sparse_backward(n, H, d->depth, d->frozen[t], x + 3 * xs, W[0], ldw[0], W[1], ldw[1], W[2], ldw[2],
                                            W[3], ldw[3], d->pred_rowptr[t], d->pred_col[t], d->succ_rowptr[t],
                                            d->succ_col[t], hs, Cs_all + o.q0 * Hp, qs, st[0], st[1], st[2], st[3], st[4], dhd,
                                            dCF + o.f0 * Hp, dhin, dcin, dx, dx + xs, dx + 2 * xs, dx + 3 * xs, dW_unused[0],
-                                           H, dW_unused[1], H, dW_unused[2], H, dW_unused[3], H, work, work_bytes, stream);
+                                           H, dW_unused[1], H, dW_unused[2], H, dW_unused[3], H, work, work_bytes, &opts,
+                                           stream);
             if (rc) return rc;
             if (!fold) rc = ggpm_scatter_rows(dcin, Hp, d->srcF[t], n, Hp, dCF, Hp, 1, stream);
         } else {
-            ggpm_backward_defer_stash(dg[0], dg[1], DQ_all + o.q0 * Hp, nullptr);
             rc = ggpm_gru_sparse_backward(n, H, d->depth, d->frozen[t], x + xs, W[0], ldw[0], W[1], ldw[1], W[2], ldw[2],
                                           d->pred_rowptr[t], d->pred_col[t], d->succ_rowptr[t], d->succ_col[t], hs, qs, st[0],
                                           st[1], st[2], st[3], st[4], dhd, dhin, dx, dx + xs, dx + 2 * xs, dW_unused[0], H,
-                                          dW_unused[1], H, dW_unused[3], dW_unused[2], H, work, work_bytes, stream);
+                                          dW_unused[1], H, dW_unused[3], dW_unused[2], H, work, work_bytes, &opts, stream);
         }
         if (rc) return rc;
         if (!fold) rc = ggpm_scatter_rows(dhin, Hp, d->srcF[t], n, Hp, dF, Hp, 1, stream);

@@ -63,14 +63,16 @@ struct Dims {
     float dropout;                 // training-mode drop probability (0: none)
     unsigned int seed_lo, seed_hi;
     int gate_dtype;                // 0 fp32, 1 bf16 operands for the gate products of the depth loops, 2 fp32 on fp32 MFMA only
+    int prefer_narrow;             // two row tiles per workgroup on every level (ggpm_level_opts.prefer_narrow)
 };
 
-// the level calls of this thread take the gate-product dtype from a thread-local (tile_mma.h) for the driver's duration
-struct GateDtypeScope {
-    int prev;
-    explicit GateDtypeScope(int dtype) : prev(ggpm_gate_dtype()) { ggpm_set_gate_dtype(dtype); }
-    ~GateDtypeScope() { ggpm_set_gate_dtype(prev); }      // (nests: the side-stream bodies may run on the caller's thread)
-};
+// the options every level call of this driver call starts from (include/ggpm_hip.h)
+inline ggpm_level_opts level_opts(const Dims& d) {
+    ggpm_level_opts o = {};
+    o.gate_dtype = d.gate_dtype;
+    o.prefer_narrow = d.prefer_narrow;
+    return o;
+}
 
 // dropout sites (include/ggpm_hip.h)
 enum { DS_EI = 0, DS_EC, DS_WO_ATOM, DS_WI, DS_WO_INTER, DS_WC, DS_WO_TREE };
@@ -92,6 +94,7 @@ Dims make_dims(const ggpm_enc_dims* d) {
     x.tree_chain = d->tree_chain;
     x.dropout = d->dropout; x.seed_lo = d->seed_lo; x.seed_hi = d->seed_hi;
     x.gate_dtype = (d->gate_dtype >= 1 && d->gate_dtype <= 3) ? d->gate_dtype : 0;
+    x.prefer_narrow = d->prefer_narrow != 0;
     return x;
 }
 
@@ -323,6 +326,8 @@ int level_forward(const Dims& d, int E1, int N1, int I, int depth, const float* 
     const size_t slot = (size_t)E1 * Hp;
     const int run = run_steps(d, level, depth, E1);
     struct Tag { Tag(int level) { ggpm_timing_tag(3 - level); } ~Tag() { ggpm_timing_tag(0); } } tag(level);
+    ggpm_level_opts o = level_opts(d);
+    o.run_depth = run;
     if (d.lstm) {
         const float* W[4] = {P[lq(level, Q_WI)], P[lq(level, Q_WOG)], P[lq(level, Q_WU)], P[lq(level, Q_WF)]};
         const float* b[4] = {P[lq(level, Q_BI)], P[lq(level, Q_BOG)], P[lq(level, Q_BU)], P[lq(level, Q_BF)]};
@@ -330,10 +335,9 @@ int level_forward(const Dims& d, int E1, int N1, int I, int depth, const float* 
         for (int k = 0; k < 4; ++k) gp[k] = {x, ldx, W[k], I + H, L.X + k * slot, Hp, Hp, b[k], 0, GGPM_ACT_NONE, 0};
         CK(ggpm_gemm_grouped(0, 1, E1, H, I, 4, gp, s));      // the four input projections in one launch
         const size_t dsl = (size_t)depth * slot;
-        ggpm_forward_run_depth(run);
         CK(ggpm_lstm_forward(E1, H, depth, L.X, L.X + slot, L.X + 2 * slot, L.X + 3 * slot, W[0] + I, I + H, W[1] + I, I + H,
                              W[2] + I, I + H, W[3] + I, I + H, pred.rowptr, pred.col, L.Hs, L.Cs, L.Qs, L.St, L.St + dsl,
-                             L.St + 2 * dsl, L.St + 3 * dsl, L.St + 4 * dsl, L.wpack, 1, s));
+                             L.St + 2 * dsl, L.St + 3 * dsl, L.St + 4 * dsl, L.wpack, 1, &o, s));
         CK(replicate_tail(d, E1, depth, run, level, L, s));
         CK(ggpm_segment_sum(L.Hs + (size_t)depth * slot, Hp, agr.rowptr, agr.col, N1, H, L.nei, Hp, 0, Hp, s));
         return GGPM_OK;
@@ -344,10 +348,9 @@ int level_forward(const Dims& d, int E1, int N1, int I, int depth, const float* 
                                    {x, ldx, Wh, I + H, L.X + 2 * slot, Hp, Hp, P[lp(level, L_BH)], 0, GGPM_ACT_NONE, 0}};
     CK(ggpm_gemm_grouped(0, 1, E1, H, I, 3, gp, s));          // the three input projections in one launch
     const size_t ds = (size_t)depth * slot;
-    ggpm_forward_run_depth(run);
     CK(ggpm_gru_forward(E1, H, depth, L.X, L.X + slot, L.X + 2 * slot, Wz + I, I + H, P[lp(level, L_UR)], H,
                             P[lp(level, L_BU)], Wh + I, I + H, pred.rowptr, pred.col,
-                            L.Hs, L.Qs, L.St, L.St + ds, L.St + 2 * ds, L.St + 3 * ds, L.St + 4 * ds, L.wpack, 1, s));
+                            L.Hs, L.Qs, L.St, L.St + ds, L.St + 2 * ds, L.St + 3 * ds, L.St + 4 * ds, L.wpack, 1, &o, s));
     CK(replicate_tail(d, E1, depth, run, level, L, s));
     CK(ggpm_segment_sum(L.Hs + (size_t)depth * slot, Hp, agr.rowptr, agr.col, N1, H, L.nei, Hp, 0, Hp, s));
     return GGPM_OK;
@@ -379,7 +382,6 @@ extern "C" int ggpm_encoder_forward(const ggpm_enc_dims* dims, float* const* par
         !gbgraph || !roots || !saved || !hroot || !hnode || !hinter || !hatom)
         return GGPM_ERR_ARG;
     const Dims d = make_dims(dims);
-    GateDtypeScope gate_scope(d.gate_dtype);
     Arena A = {reinterpret_cast<char*>(saved), 0, false, saved_bytes};
     Saved S;
     layout_saved(A, d, S);
@@ -611,24 +613,24 @@ int level_backward(const Dims& d, int E1, int I, int depth, const float* x, int 
     const int H = d.H, Hp = d.Hp;
     const size_t slot = (size_t)E1 * Hp, ds = (size_t)depth * slot;
     const int blo = backward_lo(d, level, depth, E1);
-    const int gate_dtype = d.gate_dtype;
     struct Tag { Tag(int level) { ggpm_timing_tag(3 - level); } ~Tag() { ggpm_timing_tag(0); } } tag(level);
     // no input gradient wanted (the atom level: one-hot inputs): the summed gate-input gradients are not needed on this
     // stream at all -- the depth launches skip their read-modify-write and the second stream sums the stashed gate
     // gradients before it contracts them (GGPM_SKIP_XSUM=0: per-depth accumulation everywhere)
     static const bool xsum_env = !(ggpm_dev_env("GGPM_SKIP_XSUM") && atoi(ggpm_dev_env("GGPM_SKIP_XSUM")) == 0);
     const bool skip_xsum = xsum_env && dx == nullptr && depth > 1;
+    ggpm_level_opts o = level_opts(d);
+    o.lo = blo;                   // (the backward and its weight-gradient call alike)
+    o.skip_x_sums = skip_xsum;
     if (d.lstm) {
         const float* W[4] = {P[lq(level, Q_WI)], P[lq(level, Q_WOG)], P[lq(level, Q_WU)], P[lq(level, Q_WF)]};
         float* dW[4] = {G[lq(level, Q_WI)], G[lq(level, Q_WOG)], G[lq(level, Q_WU)], G[lq(level, Q_WF)]};
         float* db[4] = {G[lq(level, Q_BI)], G[lq(level, Q_BOG)], G[lq(level, Q_BU)], G[lq(level, Q_BF)]};
-        ggpm_backward_lo_depth(blo);
-        if (skip_xsum) ggpm_backward_skip_x_sums(1);
         CK(ggpm_lstm_backward(E1, H, depth, L.X + 3 * slot, W[0] + I, I + H, W[1] + I, I + H, W[2] + I, I + H, W[3] + I, I + H,
                               pred.rowptr, pred.col, pred.rowptrT, pred.colT, L.Hs, L.Cs, L.Qs, L.St, L.St + ds,
                               L.St + 2 * ds, L.St + 3 * ds, L.St + 4 * ds, dHD, dX, dX + slot, dX + 2 * slot, dX + 3 * slot,
                               dW[0] + I, I + H, dW[1] + I, I + H, dW[2] + I, I + H, dW[3] + I, I + H, level_work,
-                              w.level_work_bytes, 0, st.main));
+                              w.level_work_bytes, 0, &o, st.main));
         if (dx) {       // dx = sum over the gates of dX_k W_k[:, :I]: one launch over four K segments
             const float* A[4] = {dX, dX + slot, dX + 2 * slot, dX + 3 * slot};
             const int lda[4] = {Hp, Hp, Hp, Hp}, ldb[4] = {I + H, I + H, I + H, I + H}, K[4] = {H, H, H, H};
@@ -673,12 +675,8 @@ int level_backward(const Dims& d, int E1, int I, int depth, const float* x, int 
         const int rc_side = st.on_side([=]() -> int {
             float* const dWk[4] = {dW0, dW1, dW2, dW3};
             if (!x_on_main) CK(x_part(sw));
-            ggpm_wgrad_lo_depth(blo);
-            {       // (thread-local like the hint above: this body may run on the side worker's thread)
-                GateDtypeScope tall_dtype(gate_dtype);
-                CK(ggpm_lstm_weight_grads(E1, H, depth, Hs, St, level_work, wc.level_work_bytes, dWk[0] + I, I + H, dWk[1] + I,
-                                          I + H, dWk[2] + I, I + H, dWk[3] + I, I + H, sw));
-            }
+            CK(ggpm_lstm_weight_grads(E1, H, depth, Hs, St, level_work, wc.level_work_bytes, dWk[0] + I, I + H, dWk[1] + I,
+                                      I + H, dWk[2] + I, I + H, dWk[3] + I, I + H, &o, sw));
             return GGPM_OK;
         });
         if (rc_side) return rc_side;
@@ -686,13 +684,11 @@ int level_backward(const Dims& d, int E1, int I, int depth, const float* x, int 
     }
     const float *Wz = P[lp(level, L_WZ)], *Wr = P[lp(level, L_WR)], *Wh = P[lp(level, L_WH)];
     float *dWz = G[lp(level, L_WZ)], *dWr = G[lp(level, L_WR)], *dWh = G[lp(level, L_WH)], *dUr = G[lp(level, L_UR)];
-    ggpm_backward_lo_depth(blo);
-    if (skip_xsum) ggpm_backward_skip_x_sums(1);
     CK(ggpm_gru_backward(E1, H, depth, L.X + slot, Wz + I, I + H, P[lp(level, L_UR)], H, Wh + I, I + H,
                              pred.rowptr, pred.col, pred.rowptrT, pred.colT, L.Hs,
                              L.Qs, L.St, L.St + ds, L.St + 2 * ds, L.St + 3 * ds, L.St + 4 * ds, dHD, dX, dX + slot,
                              dX + 2 * slot, dWz + I, I + H, dUr, H, G[lp(level, L_BU)], dWh + I, I + H, level_work,
-                             w.level_work_bytes, 0, st.main));
+                             w.level_work_bytes, 0, &o, st.main));
     if (dx) {       // needed upstream right away: main stream
         // dx = dX_z W_z[:, :I] + dX_r W_r + dX_h W_h[:, :I]: one launch over three K segments
         const float* A[3] = {dX, dX + slot, dX + 2 * slot};
@@ -724,7 +720,7 @@ int level_backward(const Dims& d, int E1, int I, int depth, const float* x, int 
         CK(ggpm_colsum(dX, Hp, E1, H, dbz, wc.xcs[level], sx));
         CK(ggpm_colsum(dX + 2 * slot, Hp, E1, H, dbh, wc.xcs[level], sx));
         // db_u here too when this part has the main stream to itself: the second stream then ends with the tall contraction
-        if (bu_here) CK(ggpm_gru_bias_u_grad(E1, H, depth, blo, level_work, dbu, wc.xcs[level], sx));
+        if (bu_here) CK(ggpm_gru_bias_u_grad(E1, H, depth, blo, level_work, dbu, wc.xcs[level], &o, sx));
         if (ggpm_gemm_prefers_grouped(H, I, E1, 3)) {      // the three in one launch
             const GgpmGemmProblem gp[3] = {{dX, Hp, x, ldx, dWz, I + H, I, nullptr, 0, GGPM_ACT_NONE, 0},
                                            {dX + slot, Hp, x, ldx, dWr, I, I, nullptr, 0, GGPM_ACT_NONE, 0},
@@ -739,13 +735,12 @@ int level_backward(const Dims& d, int E1, int I, int depth, const float* x, int 
         }
         return GGPM_OK;
     };
+    ggpm_level_opts wo = o;
+    wo.skip_bias_u = bu_here;
     const int rc_side = st.on_side([=]() -> int {
         if (!x_on_main) CK(x_part(sw));
-        ggpm_wgrad_lo_depth(blo);
-        ggpm_wgrad_skip_bias_u(bu_here ? 1 : 0);
-        GateDtypeScope tall_dtype(gate_dtype);      // (thread-local: this body may run on the side worker's thread)
         CK(ggpm_gru_weight_grads(E1, H, depth, Hs, St, St + ds, level_work, wc.level_work_bytes, dWz + I, I + H, dUr, H,
-                                 dbu, dWh + I, I + H, sw));
+                                 dbu, dWh + I, I + H, &wo, sw));
         return GGPM_OK;
     });
     if (rc_side) return rc_side;
@@ -778,7 +773,6 @@ extern "C" int ggpm_encoder_backward(const ggpm_enc_dims* dims, float* const* pa
         phase > 2)
         return GGPM_ERR_ARG;
     const Dims d = make_dims(dims);
-    GateDtypeScope gate_scope(d.gate_dtype);
     Arena A = {reinterpret_cast<char*>(saved), 0, false, saved_bytes};
     Saved S;
     layout_saved(A, d, S);

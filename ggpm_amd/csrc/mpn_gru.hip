@@ -90,18 +90,6 @@ void ggpm_launch_pack(const GgpmPackArgs& a, int nmat, hipStream_t s) {
     ggpm_pack_weight_kernel<<<grid, 64, 0, s>>>(a);
 }
 
-namespace { thread_local int g_gate_dtype = 0; }
-// 0: fp32 (gate products on split operands where the level's shape allows, see gate_mode below); 1: bf16 operands;
-// 2: fp32 on v_mfma_f32_16x16x4_f32 only, 3: fp32 on split operands wherever they fit the LDS (the two forms every fp32
-// call chooses between, selectable so that they can be compared on one shape)
-void ggpm_set_gate_dtype(int dtype) { g_gate_dtype = (dtype >= 1 && dtype <= 3) ? dtype : 0; }
-int ggpm_gate_dtype() { return g_gate_dtype; }
-extern "C" int ggpm_level_gate_dtype(int dtype) {
-    const int prev = g_gate_dtype;
-    if (dtype >= 0 && dtype <= 3) g_gate_dtype = dtype;
-    return prev;
-}
-
 namespace {
 
 #ifndef GGPM_GATHER_U
@@ -135,7 +123,7 @@ struct GruFwdArgs {
     int h0_zero;                   // first depth of a dense level: h^0 = 0, so s = g = 0 without a gather and the gate
                                    // products vanish (h^1 = sigmoid(x_z) tanh(x_h)); H^0 / Q^0 are neither built nor read
     float* Hout;                   // bf16 storage only: where the LAST depth also writes h' in fp32 (the level's result)
-    const float* src_h;            // kernel B of a sparse forward's q^0 launch (ggpm_forward_gather_state): row r of the
+    const float* src_h;            // kernel B of a sparse forward's q^0 launch (ggpm_level_opts.gather_*): row r of the
     const int32_t* src_idx;        // start state is src_h[src_idx[r]] (zero when < 0); the launch writes it to Hnew itself
 };
 
@@ -426,7 +414,7 @@ struct GruBwdArgs {
     float* carry;                  // [E1,Hp] running dh of frozen rows (started by the first backward depth)
     int final_pass;                // t == 0: P1 + dq.U_r only, result to dHin
     float* dHin;                   // [E1,Hp]
-    float* scat_h;                 // ggpm_backward_scatter_state: the final pass ADDS row r's result to
+    float* scat_h;                 // ggpm_level_opts.scatter_*: the final pass ADDS row r's result to
     const int32_t* scat_idx;       // scat_h[scat_idx[r]] (unique ids; < 0: dropped) instead of writing dHin
     int fuse_b;                    // single column group: kernel A also forms dS, dG for depth t-1 (no B launch)
     unsigned long long* dbg;       // optional phase stamps (GGPM_ADEBUG; dev only)
@@ -773,12 +761,12 @@ inline int pick_tg(int E1, int NT) {
 }
 
 // two row tiles per workgroup where the level is large enough to be bound by the weight stream (see GGPM_RT2_MIN_ROW_TILES)
-thread_local bool g_prefer_narrow = false;       // ggpm_level_prefer_narrow
-inline bool use_rt2(int E1, int Hp, bool sparse) {
+// or the caller asks for it (ggpm_level_opts.prefer_narrow)
+inline bool use_rt2(const ggpm_level_opts& o, int E1, int Hp, bool sparse) {
     static const int mode = [] { const char* e = ggpm_dev_env("GGPM_RT2"); return e ? atoi(e) : 1; }();     // 0 off, 2 always
     if (mode == 0 || sparse) return false;
     if ((size_t)2 * 32 * (Hp + 4) * sizeof(float) > 160 * 1024) return false;
-    return mode == 2 || g_prefer_narrow || ggpm_ceil_div(E1, 16) >= GGPM_RT2_MIN_ROW_TILES;
+    return mode == 2 || o.prefer_narrow || ggpm_ceil_div(E1, 16) >= GGPM_RT2_MIN_ROW_TILES;
 }
 
 // Gate mode of a level call (GruFwdArgs.bf16): the caller's dtype 1 (bf16 operands) stays; an fp32 call runs its gate products
@@ -788,9 +776,10 @@ inline bool use_rt2(int E1, int Hp, bool sparse) {
 // 49.7 -> 42.0) and whose fp32 tile + two bf16 images fit the LDS -- and on fp32 MFMA (mode 0) otherwise: with column groups
 // (the tree-side levels, the decode steps) ONE wave per SIMD streams three weight planes with nothing to hide their latency
 // behind and the launch gets slower (attachment level gru_bwd_a 11.7 -> 16.7 us).  Sparse calls are always mode 0, so a
-// sequence of them sharing one packed weight set (ggpm_weights_packed) agrees on it.  dtype 3 forces mode 2 wherever it
+// sequence of them sharing one packed weight set (ggpm_level_opts.weights_packed) agrees on it.  dtype 3 forces mode 2 wherever it
 // fits (tests); GGPM_GATE_SPLIT=0: mode 0 everywhere (A/B runs).
-inline int gate_mode(int dtype, int Hp, bool rt2, bool single_group, bool sparse) {
+inline int gate_mode(const ggpm_level_opts& o, int Hp, bool rt2, bool single_group, bool sparse) {
+    const int dtype = o.gate_dtype;
     if (dtype == 1) return 1;
     if (dtype == 2) return 0;
     static const bool on = [] { const char* e = ggpm_dev_env("GGPM_GATE_SPLIT"); return !e || atoi(e) != 0; }();
@@ -801,9 +790,8 @@ inline int gate_mode(int dtype, int Hp, bool rt2, bool single_group, bool sparse
 }
 inline bool single_group(int E1, int Hp) { return pick_tg(E1, Hp / 16) >= Hp / 16; }
 
-void launch_fwd(GruFwdArgs a, bool stash, bool with_b, double flops1, hipStream_t s) {
+void launch_fwd(GruFwdArgs a, bool rt2, bool stash, bool with_b, double flops1, hipStream_t s) {
     const int Hp = a.Hp, NT = Hp / 16;
-    const bool rt2 = use_rt2(a.E1, Hp, a.frozen != nullptr);
     const int rows = rt2 ? 32 : 16;
     dim3 grid_a(ggpm_ceil_div(a.E1, rows), ggpm_ceil_div(NT, a.tg));
     const bool split = a.bf16 == 2;
@@ -857,9 +845,8 @@ void launch_fwd(GruFwdArgs a, bool stash, bool with_b, double flops1, hipStream_
     }
 }
 
-void launch_bwd(GruBwdArgs a, bool with_b, double flops1, hipStream_t s) {
+void launch_bwd(GruBwdArgs a, bool rt2, bool with_b, double flops1, hipStream_t s) {
     const int Hp = a.Hp, NT = Hp / 16;
-    const bool rt2 = use_rt2(a.E1, Hp, a.frozen != nullptr);
     const int rows = rt2 ? 32 : 16;
     dim3 grid_a(ggpm_ceil_div(a.E1, rows), ggpm_ceil_div(NT, a.tg));
     const bool split = a.bf16 == 2;
@@ -925,68 +912,13 @@ __global__ void sparse_init_state(const float* __restrict__ h_in, const unsigned
 }
 }  // namespace
 
-namespace { thread_local int g_run_depth = 0, g_bwd_lo = 0, g_wgrad_lo = 0; }
-void ggpm_forward_run_depth(int run_depth) { g_run_depth = run_depth; }
-int ggpm_take_run_depth() { const int v = g_run_depth; g_run_depth = 0; return v; }
-void ggpm_backward_lo_depth(int lo) { g_bwd_lo = lo; }
-int ggpm_take_backward_lo() { const int v = g_bwd_lo; g_bwd_lo = 0; return v; }
-void ggpm_wgrad_lo_depth(int lo) { g_wgrad_lo = lo; }
-int ggpm_take_wgrad_lo() { const int v = g_wgrad_lo; g_wgrad_lo = 0; return v; }
-namespace { thread_local bool g_wgrad_skip_bu = false; }
-void ggpm_wgrad_skip_bias_u(int yes) { g_wgrad_skip_bu = yes != 0; }
-namespace { thread_local float* g_defer[4] = {nullptr, nullptr, nullptr, nullptr}; thread_local bool g_defer_set = false; }
-extern "C" void ggpm_backward_defer_stash(float* s0, float* s1, float* s2, float* s3) {
-    g_defer[0] = s0; g_defer[1] = s1; g_defer[2] = s2; g_defer[3] = s3;
-    g_defer_set = s0 != nullptr;
-}
-namespace { thread_local bool g_sparse_skip_wgrads = false; }
-void ggpm_sparse_backward_skip_wgrads(int yes) { g_sparse_skip_wgrads = yes != 0; }
-bool ggpm_take_sparse_skip_wgrads() { const bool v = g_sparse_skip_wgrads; g_sparse_skip_wgrads = false; return v; }
-namespace { thread_local bool g_skip_xsum = false; }
-extern "C" void ggpm_backward_skip_x_sums(int yes) { g_skip_xsum = yes != 0; }
-bool ggpm_take_skip_x_sums() { const bool v = g_skip_xsum; g_skip_xsum = false; return v; }
-namespace {
-thread_local const float* g_gs_h = nullptr; thread_local const float* g_gs_c = nullptr; thread_local const int32_t* g_gs_idx = nullptr;
-thread_local float* g_ss_h = nullptr; thread_local float* g_ss_c = nullptr; thread_local const int32_t* g_ss_idx = nullptr;
-}
-extern "C" void ggpm_forward_gather_state(const float* src_h, const float* src_c, const int32_t* idx) {
-    g_gs_h = src_h; g_gs_c = src_c; g_gs_idx = idx;
-}
-bool ggpm_take_gather_state(const float** src_h, const float** src_c, const int32_t** idx) {
-    *src_h = g_gs_h; *src_c = g_gs_c; *idx = g_gs_idx;
-    const bool v = g_gs_idx != nullptr && g_gs_h != nullptr;
-    g_gs_h = g_gs_c = nullptr; g_gs_idx = nullptr;
-    return v;
-}
-extern "C" void ggpm_backward_scatter_state(float* dst_h, float* dst_c, const int32_t* idx) {
-    g_ss_h = dst_h; g_ss_c = dst_c; g_ss_idx = idx;
-}
-bool ggpm_take_scatter_state(float** dst_h, float** dst_c, const int32_t** idx) {
-    *dst_h = g_ss_h; *dst_c = g_ss_c; *idx = g_ss_idx;
-    const bool v = g_ss_idx != nullptr && g_ss_h != nullptr;
-    g_ss_h = g_ss_c = nullptr; g_ss_idx = nullptr;
-    return v;
-}
-extern "C" void ggpm_level_prefer_narrow(int yes) { g_prefer_narrow = yes != 0; }
-bool ggpm_prefer_narrow() { return g_prefer_narrow; }
-namespace { thread_local bool g_packed = false; }
-extern "C" void ggpm_weights_packed(int yes) { g_packed = yes != 0; }
-bool ggpm_take_weights_packed() { const bool v = g_packed; g_packed = false; return v; }
-bool ggpm_take_defer_stash(float* (&out)[4]) {
-    const bool v = g_defer_set;
-    for (int i = 0; i < 4; ++i) { out[i] = g_defer[i]; g_defer[i] = nullptr; }
-    g_defer_set = false;
-    return v;
-}
-
 static int gru_forward_impl(int E1, int H, int depth, const float* Xz, const float* Xr, const float* Xh,
                             const float* Wz_h, int ld_wz, const float* Ur, int ld_ur, const float* bu,
                             const float* Wh_h, int ld_wh, const int32_t* pred_rowptr, const int32_t* pred_col,
                             float* Hs, float* Qs, float* Ss, float* Gs, float* Zs, float* Ms, float* Rs,
                             float* wpack, int save_for_backward, const float* h_in, const unsigned char* frozen,
-                            ggpm_stream_t stream) {
+                            const ggpm_level_opts& o, ggpm_stream_t stream) {
     GGPM_CLEAR_STALE_ERROR();
-    const bool weights_packed = ggpm_take_weights_packed();      // (consumed on every path)
     if (E1 <= 0 || H <= 0 || depth <= 0 || !Xz || !Xr || !Xh || !Wz_h || !Ur || !bu || !Wh_h || !pred_rowptr ||
         !pred_col || !Hs || !Qs || !wpack)
         return GGPM_ERR_ARG;
@@ -995,7 +927,8 @@ static int gru_forward_impl(int E1, int H, int depth, const float* Xz, const flo
     if (!gru_shape_ok(Hp)) return GGPM_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     const size_t HH = (size_t)Hp * Hp, slot = (size_t)E1 * Hp;
-    const int bf16 = gate_mode(ggpm_gate_dtype(), Hp, use_rt2(E1, Hp, frozen != nullptr), single_group(E1, Hp), frozen != nullptr);      // gate mode 0 / 1 / 2
+    const bool rt2 = use_rt2(o, E1, Hp, frozen != nullptr);
+    const int bf16 = gate_mode(o, Hp, rt2, single_group(E1, Hp), frozen != nullptr);      // gate mode 0 / 1 / 2
     const size_t mstep = ggpm_packed_matrix_floats(Hp, bf16);
     float* pWz = wpack; float* pWh = wpack + mstep; float* pUr = wpack + 2 * mstep;
     float* pbu = wpack + 3 * ggpm_packed_matrix_slot(Hp);
@@ -1003,20 +936,18 @@ static int gru_forward_impl(int E1, int H, int depth, const float* Xz, const flo
         GgpmPackArgs pk = {};
         pk.W[0] = Wz_h; pk.ldw[0] = ld_wz; pk.W[1] = Wh_h; pk.ldw[1] = ld_wh; pk.W[2] = Ur; pk.ldw[2] = ld_ur;
         pk.H = H; pk.Hp = Hp; pk.transpose = 0; pk.dst = wpack; pk.bias = bu; pk.bias_out = pbu; pk.bf16 = bf16;
-        if (!weights_packed) ggpm_launch_pack(pk, 3, s);
+        if (!o.weights_packed) ggpm_launch_pack(pk, 3, s);
     }
     dim3 ig(ggpm_ceil_div(Hp, 256), E1);
     const int tg0 = pick_tg(E1, Hp / 16);
-    const float *gs_h = nullptr, *gs_c = nullptr;
-    const int32_t* gs_idx = nullptr;
-    const bool gathered = ggpm_take_gather_state(&gs_h, &gs_c, &gs_idx) && frozen;      // (consumed on every path)
+    const bool gathered = o.gather_h && o.gather_idx && frozen;
     if (frozen) {      // sparse_forward: start from the caller's state, q^0 = U_r h^0 + b_u by one B launch
         // (h_in == Hs: the caller put the masked start state -- frozen rows' states, zero elsewhere -- into slot 0 itself;
-        // ggpm_forward_gather_state: the q^0 launch fetches it through the index and writes slot 0 on the way)
+        // ggpm_level_opts.gather_*: the q^0 launch fetches it through the index and writes slot 0 on the way)
         if (h_in != Hs && !gathered) sparse_init_state<<<ig, 256, 0, s>>>(h_in, frozen, Hs, Hp);
         GruFwdArgs a0 = {};
         a0.E1 = E1; a0.Hp = Hp; a0.tg = tg0; a0.Hnew = Hs; a0.Qnew = Qs; a0.Ur = pUr; a0.bu = pbu; a0.bf16 = bf16;
-        if (gathered) { a0.src_h = gs_h; a0.src_idx = gs_idx; }
+        if (gathered) { a0.src_h = o.gather_h; a0.src_idx = o.gather_idx; }
         const size_t lds_b = bf16 == 2 ? ggpm_split_image_bytes(ROWS, Hp) : (size_t)ROWS * (Hp + 4) * sizeof(float);
         dim3 grid_a(ggpm_ceil_div(E1, ROWS), ggpm_ceil_div(Hp / 16, tg0));
         if (bf16 == 2) { set_lds(gru_fwd_b<2, 1>, lds_b); gru_fwd_b<2, 1><<<grid_a, GGPM_NWA * 64, lds_b, s>>>(a0); }
@@ -1030,7 +961,7 @@ static int gru_forward_impl(int E1, int H, int depth, const float* Xz, const flo
     static const char* const abl = ggpm_dev_env("GGPM_ABLATE");
     // bf16 storage (tile_mma.h): bf16 gate products, dense, training, every stash contraction on the bf16 tall kernel
     const bool st16 = bf16 == 1 && !frozen && save_for_backward && ggpm_bf16_storage_applies(E1, H);
-    int run_depth = ggpm_take_run_depth();
+    int run_depth = o.run_depth;
     if (run_depth <= 0 || run_depth > depth || frozen || !save_for_backward) run_depth = depth;
     for (int t = 1; t <= run_depth; ++t) {
         GruFwdArgs a = {};
@@ -1054,7 +985,7 @@ static int gru_forward_impl(int E1, int H, int depth, const float* Xz, const flo
             a.Qprev = Qs + (size_t)((t - 1) & 1) * slot; a.Qnew = Qs + (size_t)(t & 1) * slot;
             a.S = a.G = a.Z = a.M = a.R = nullptr;
         }
-        launch_fwd(a, save_for_backward != 0, t < depth, flops1, s);
+        launch_fwd(a, rt2, save_for_backward != 0, t < depth, flops1, s);
     }
     GGPM_CHECK_LAUNCH();
     return GGPM_OK;
@@ -1065,9 +996,10 @@ extern "C" int ggpm_gru_forward(int E1, int H, int depth, const float* Xz, const
                                 const float* Wh_h, int ld_wh, const int32_t* pred_rowptr,
                                 const int32_t* pred_col, float* Hs, float* Qs, float* Ss, float* Gs, float* Zs,
                                 float* Ms, float* Rs, float* wpack, int save_for_backward,
-                                ggpm_stream_t stream) {
+                                const ggpm_level_opts* opts, ggpm_stream_t stream) {
     return gru_forward_impl(E1, H, depth, Xz, Xr, Xh, Wz_h, ld_wz, Ur, ld_ur, bu, Wh_h, ld_wh, pred_rowptr, pred_col,
-                            Hs, Qs, Ss, Gs, Zs, Ms, Rs, wpack, save_for_backward, nullptr, nullptr, stream);
+                            Hs, Qs, Ss, Gs, Zs, Ms, Rs, wpack, save_for_backward, nullptr, nullptr, ggpm_opts_or_default(opts),
+                            stream);
 }
 
 extern "C" int ggpm_gru_sparse_forward(int E1, int H, int depth, const float* h_in, const unsigned char* frozen,
@@ -1075,10 +1007,12 @@ extern "C" int ggpm_gru_sparse_forward(int E1, int H, int depth, const float* h_
                                        int ld_wz, const float* Ur, int ld_ur, const float* bu, const float* Wh_h,
                                        int ld_wh, const int32_t* pred_rowptr, const int32_t* pred_col, float* Hs,
                                        float* Qs, float* Ss, float* Gs, float* Zs, float* Ms, float* Rs,
-                                       float* wpack, int save_for_backward, ggpm_stream_t stream) {
+                                       float* wpack, int save_for_backward, const ggpm_level_opts* opts,
+                                       ggpm_stream_t stream) {
     if (!h_in || !frozen) return GGPM_ERR_ARG;
     return gru_forward_impl(E1, H, depth, Xz, Xr, Xh, Wz_h, ld_wz, Ur, ld_ur, bu, Wh_h, ld_wh, pred_rowptr, pred_col,
-                            Hs, Qs, Ss, Gs, Zs, Ms, Rs, wpack, save_for_backward, h_in, frozen, stream);
+                            Hs, Qs, Ss, Gs, Zs, Ms, Rs, wpack, save_for_backward, h_in, frozen, ggpm_opts_or_default(opts),
+                            stream);
 }
 
 extern "C" size_t ggpm_gru_backward_workspace_bytes(int E1, int H, int depth) {
@@ -1097,7 +1031,8 @@ extern "C" size_t ggpm_gru_backward_workspace_bytes(int E1, int H, int depth) {
 
 static int gru_weight_grads_impl(int E1, int H, int depth, const float* Hs, const float* Ss, const float* Gs,
                                  float* work, size_t work_bytes, float* dWz_h, int ld_dwz, float* dUr, int ld_dur,
-                                 float* dbu, float* dWh_h, int ld_dwh, bool with_slot0, int lo, ggpm_stream_t stream);
+                                 float* dbu, float* dWh_h, int ld_dwh, bool with_slot0, int lo, const ggpm_level_opts& o,
+                                 ggpm_stream_t stream);
 
 // a small pool of re-recordable events (the encoder drivers' stream ordering, encoder.hip)
 hipEvent_t ggpm_wgrad_event(int i) {
@@ -1115,14 +1050,11 @@ static int gru_backward_impl(int E1, int H, int depth, const float* Xr, const fl
                                  const float* Ms, const float* Rs, const float* dHD, float* dXz, float* dXr, float* dXh,
                                  float* dWz_h, int ld_dwz, float* dUr, int ld_dur, float* dbu, float* dWh_h,
                                  int ld_dwh, float* work, size_t work_bytes, int weight_grads,
-                                 const unsigned char* frozen, float* dHin, ggpm_stream_t stream) {
+                                 const unsigned char* frozen, float* dHin, const ggpm_level_opts& o, ggpm_stream_t stream) {
     GGPM_CLEAR_STALE_ERROR();
-    const bool weights_packed = ggpm_take_weights_packed();      // (consumed on every path)
-    if (ggpm_take_sparse_skip_wgrads() && frozen) weight_grads = 0;      // (ggpm_gru_sparse_weight_grads follows, on the caller's choice of stream)
-    const bool skip_xsum = ggpm_take_skip_x_sums() && !frozen;
-    float *ss_h = nullptr, *ss_c = nullptr;
-    const int32_t* ss_idx = nullptr;
-    const bool scattered = ggpm_take_scatter_state(&ss_h, &ss_c, &ss_idx) && frozen;      // (consumed on every path)
+    if (o.skip_sparse_wgrads && frozen) weight_grads = 0;      // (ggpm_gru_sparse_weight_grads follows, on the caller's choice of stream)
+    const bool skip_xsum = o.skip_x_sums && !frozen;
+    const bool scattered = o.scatter_h && o.scatter_idx && frozen;
     if (E1 <= 0 || H <= 0 || depth <= 0 || !Xr || !Wz_h || !Ur || !Wh_h || !pred_rowptr || !pred_col ||
         !succ_rowptr || !succ_col || !Hs || !Qs || !Ss || !Gs || !Zs || !Ms || !Rs || !dHD || !dXz || !dXr || !dXh ||
         !dWz_h || !dUr || !dbu || !dWh_h || !work)
@@ -1134,9 +1066,10 @@ static int gru_backward_impl(int E1, int H, int depth, const float* Xr, const fl
     const size_t HH = (size_t)Hp * Hp, slot = (size_t)E1 * Hp;
 
     // (the packed transposes come first: their place does not depend on E1, so a sequence of calls that shares one
-    // `work` buffer and one set of weights packs them once -- ggpm_weights_packed)
+    // `work` buffer and one set of weights packs them once -- ggpm_level_opts.weights_packed)
     float* w = work;
-    const int bf16 = gate_mode(ggpm_gate_dtype(), Hp, use_rt2(E1, Hp, frozen != nullptr), single_group(E1, Hp), frozen != nullptr);      // gate mode 0 / 1 / 2
+    const bool rt2 = use_rt2(o, E1, Hp, frozen != nullptr);
+    const int bf16 = gate_mode(o, Hp, rt2, single_group(E1, Hp), frozen != nullptr);      // gate mode 0 / 1 / 2
     const size_t mstep = ggpm_packed_matrix_floats(Hp, bf16);
     float* pWzT = w; float* pWhT = w + mstep; float* pUrT = w + 2 * mstep; w += 3 * ggpm_packed_matrix_slot(Hp);
     float* DMP = w; w += (size_t)depth * slot;
@@ -1149,20 +1082,17 @@ static int gru_backward_impl(int E1, int H, int depth, const float* Xr, const fl
     float* csws = w; w += (size_t)256 * Hp;
     float* skws = w;
     const size_t skbytes = work_bytes - (size_t)((char*)skws - (char*)work);
-    {       // deferred weight gradients (ggpm_backward_defer_stash): the stashes go to the caller's stacked buffers
-        float* ext[4];
-        if (ggpm_take_defer_stash(ext)) {
-            if (!frozen || !ext[1] || !ext[2]) return GGPM_ERR_ARG;
-            DMP = ext[0]; DZP = ext[1]; DQ = ext[2];
-            weight_grads = 0;
-        }
+    if (o.defer_stash[0]) {       // deferred weight gradients: the stashes go to the caller's stacked buffers
+        if (!frozen || !o.defer_stash[1] || !o.defer_stash[2]) return GGPM_ERR_ARG;
+        DMP = o.defer_stash[0]; DZP = o.defer_stash[1]; DQ = o.defer_stash[2];
+        weight_grads = 0;
     }
 
     {
         GgpmPackArgs pk = {};
         pk.W[0] = Wz_h; pk.ldw[0] = ld_wz; pk.W[1] = Wh_h; pk.ldw[1] = ld_wh; pk.W[2] = Ur; pk.ldw[2] = ld_ur;
         pk.H = H; pk.Hp = Hp; pk.transpose = 1; pk.dst = pWzT; pk.bias = nullptr; pk.bias_out = nullptr; pk.bf16 = bf16;
-        if (!weights_packed) ggpm_launch_pack(pk, 3, s);
+        if (!o.weights_packed) ggpm_launch_pack(pk, 3, s);
     }
     // dXz / dXh are started (not accumulated) by the first backward depth; so is dXr when that depth has a dS/dG product
     if (depth == 1 && !frozen) (void)hipMemsetAsync(dXr, 0, slot * sizeof(float), s);
@@ -1171,7 +1101,7 @@ static int gru_backward_impl(int E1, int H, int depth, const float* Xr, const fl
     const double flops1 = 2.0 * (double)(E1 - 1) * H * H;   // algorithmic flops of ONE gate product
     const bool st16 = bf16 == 1 && !frozen && ggpm_bf16_storage_applies(E1, H);      // (as the forward decided)
     // tree-side levels: d(h^t) vanishes below step `lo` (nilpotent Jacobian, common.h); sparse runs go all the way
-    int lo = ggpm_take_backward_lo();
+    int lo = o.lo;
     if (lo < 1 || lo > depth || frozen) lo = 1;
     for (int t = depth; t >= lo; --t) {
         GruBwdArgs a = {};
@@ -1193,7 +1123,7 @@ static int gru_backward_impl(int E1, int H, int depth, const float* Xr, const fl
         a.WzT = pWzT; a.WhT = pWhT; a.UrT = pUrT; a.bf16 = bf16;
         a.srowptr = succ_rowptr; a.scol = succ_col;
         a.skip_xsum = skip_xsum ? 1 : 0;
-        launch_bwd(a, t > 1 || frozen != nullptr, flops1, s);     // (the dS/dG launch of step lo > 1 still forms dXr)
+        launch_bwd(a, rt2, t > 1 || frozen != nullptr, flops1, s);     // (the dS/dG launch of step lo > 1 still forms dXr)
     }
     GGPM_CHECK_LAUNCH();
 
@@ -1204,13 +1134,13 @@ static int gru_backward_impl(int E1, int H, int depth, const float* Xr, const fl
         a.dSin = dSb[1]; a.dGin = dGb[1];          // written by the B launch of depth 1
         a.DQ = DQ; a.UrT = pUrT; a.srowptr = succ_rowptr; a.scol = succ_col; a.bf16 = bf16;
         a.frozen = frozen; a.carry = carry; a.dHin = dHin;
-        if (scattered) { a.scat_h = ss_h; a.scat_idx = ss_idx; }
-        launch_bwd(a, false, flops1, s);
+        if (scattered) { a.scat_h = o.scatter_h; a.scat_idx = o.scatter_idx; }
+        launch_bwd(a, rt2, false, flops1, s);
         GGPM_CHECK_LAUNCH();
     }
     if (!weight_grads) return GGPM_OK;
     return gru_weight_grads_impl(E1, H, depth, Hs, Ss, Gs, work, work_bytes, dWz_h, ld_dwz, dUr, ld_dur, dbu, dWh_h,
-                                 ld_dwh, frozen != nullptr, lo, stream);
+                                 ld_dwh, frozen != nullptr, lo, o, stream);
 }
 
 extern "C" int ggpm_gru_backward(int E1, int H, int depth, const float* Xr, const float* Wz_h, int ld_wz,
@@ -1221,10 +1151,10 @@ extern "C" int ggpm_gru_backward(int E1, int H, int depth, const float* Xr, cons
                                  const float* Ms, const float* Rs, const float* dHD, float* dXz, float* dXr,
                                  float* dXh, float* dWz_h, int ld_dwz, float* dUr, int ld_dur, float* dbu,
                                  float* dWh_h, int ld_dwh, float* work, size_t work_bytes, int weight_grads,
-                                 ggpm_stream_t stream) {
+                                 const ggpm_level_opts* opts, ggpm_stream_t stream) {
     return gru_backward_impl(E1, H, depth, Xr, Wz_h, ld_wz, Ur, ld_ur, Wh_h, ld_wh, pred_rowptr, pred_col, succ_rowptr,
                              succ_col, Hs, Qs, Ss, Gs, Zs, Ms, Rs, dHD, dXz, dXr, dXh, dWz_h, ld_dwz, dUr, ld_dur, dbu,
-                             dWh_h, ld_dwh, work, work_bytes, weight_grads, nullptr, nullptr, stream);
+                             dWh_h, ld_dwh, work, work_bytes, weight_grads, nullptr, nullptr, ggpm_opts_or_default(opts), stream);
 }
 
 // sparse_forward backward: additionally returns dHin (gradient of the incoming state; zero on the recomputed rows)
@@ -1236,11 +1166,12 @@ extern "C" int ggpm_gru_sparse_backward(int E1, int H, int depth, const unsigned
                                         const float* Gs, const float* Zs, const float* Ms, const float* Rs,
                                         const float* dHD, float* dHin, float* dXz, float* dXr, float* dXh,
                                         float* dWz_h, int ld_dwz, float* dUr, int ld_dur, float* dbu, float* dWh_h,
-                                        int ld_dwh, float* work, size_t work_bytes, ggpm_stream_t stream) {
+                                        int ld_dwh, float* work, size_t work_bytes, const ggpm_level_opts* opts,
+                                        ggpm_stream_t stream) {
     if (!frozen || !dHin) return GGPM_ERR_ARG;
     return gru_backward_impl(E1, H, depth, Xr, Wz_h, ld_wz, Ur, ld_ur, Wh_h, ld_wh, pred_rowptr, pred_col, succ_rowptr,
                              succ_col, Hs, Qs, Ss, Gs, Zs, Ms, Rs, dHD, dXz, dXr, dXh, dWz_h, ld_dwz, dUr, ld_dur, dbu,
-                             dWh_h, ld_dwh, work, work_bytes, 1, frozen, dHin, stream);
+                             dWh_h, ld_dwh, work, work_bytes, 1, frozen, dHin, ggpm_opts_or_default(opts), stream);
 }
 
 // Weight gradients of the GRU message function: tall contractions over every (depth, message) row of the
@@ -1248,12 +1179,12 @@ extern "C" int ggpm_gru_sparse_backward(int E1, int H, int depth, const unsigned
 // stream while the next level's (latency-bound) depth loop occupies the main one.
 static int gru_weight_grads_impl(int E1, int H, int depth, const float* Hs, const float* Ss, const float* Gs,
                                  float* work, size_t work_bytes, float* dWz_h, int ld_dwz, float* dUr, int ld_dur,
-                                 float* dbu, float* dWh_h, int ld_dwh, bool with_slot0, int lo, ggpm_stream_t stream) {
+                                 float* dbu, float* dWh_h, int ld_dwh, bool with_slot0, int lo, const ggpm_level_opts& o,
+                                 ggpm_stream_t stream) {
     GGPM_CLEAR_STALE_ERROR();
     if (E1 <= 0 || H <= 0 || depth <= 0 || !Hs || !Ss || !Gs || !work || !dWz_h || !dUr || !dbu || !dWh_h)
         return GGPM_ERR_ARG;
-    const bool skip_bu = g_wgrad_skip_bu;                 // (consumed: ggpm_gru_bias_u_grad forms db_u elsewhere)
-    g_wgrad_skip_bu = false;
+    const bool skip_bu = o.skip_bias_u;                   // (ggpm_gru_bias_u_grad forms db_u elsewhere)
     if (lo < 1 || lo > depth || with_slot0) lo = 1;       // backward steps depth .. lo ran (stash slots lo-1 .. depth-1)
     if (work_bytes < ggpm_gru_backward_workspace_bytes(E1, H, depth)) return GGPM_ERR_WORKSPACE;
     const int Hp = ggpm_padded_hidden(H);
@@ -1270,8 +1201,8 @@ static int gru_weight_grads_impl(int E1, int H, int depth, const float* Hs, cons
     const int KD = (depth - lo + 1) * E1;
     // bf16 storage (as gru_forward_impl / gru_backward_impl decided): the stashes are bf16 in the first half of their buffers
     // and the bf16 tall kernel reads them as they are
-    const bool st16 = ggpm_gate_dtype() == 1 && !with_slot0 && ggpm_bf16_storage_applies(E1, H);
-    const int tall_mode = st16 ? 2 : (ggpm_gate_dtype() == 1 ? 1 : 0);
+    const bool st16 = o.gate_dtype == 1 && !with_slot0 && ggpm_bf16_storage_applies(E1, H);
+    const int tall_mode = st16 ? 2 : (o.gate_dtype == 1 ? 1 : 0);
     int rc;
     // the two or three contractions in ONE launch and one reduce (they share the split-K workspace)
     ggpm_gemm_problem gp[3] = {{ggpm_slot_ptr(DMP, lo - 1, slot, st16), Hp, ggpm_slot_ptr(Gs, lo - 1, slot, st16), Hp, dWh_h, ld_dwh, H,
@@ -1304,9 +1235,10 @@ static int gru_weight_grads_impl(int E1, int H, int depth, const float* Hs, cons
     return GGPM_OK;
 }
 
-// db_u of a dense level by itself (what gru_weight_grads_impl does last unless ggpm_wgrad_skip_bias_u was set): the column
-// sum of the dq stash slots lo .. depth-1 (dq^t pairs with h^t; the dense level never produces dq^0).
-int ggpm_gru_bias_u_grad(int E1, int H, int depth, int lo, float* work, float* dbu, float* csws, ggpm_stream_t stream) {
+// db_u of a dense level by itself (what gru_weight_grads_impl does last unless ggpm_level_opts.skip_bias_u is set): the
+// column sum of the dq stash slots lo .. depth-1 (dq^t pairs with h^t; the dense level never produces dq^0).
+int ggpm_gru_bias_u_grad(int E1, int H, int depth, int lo, float* work, float* dbu, float* csws, const ggpm_level_opts* opts,
+                         ggpm_stream_t stream) {
     GGPM_CLEAR_STALE_ERROR();
     if (E1 <= 0 || H <= 0 || depth <= 0 || !work || !dbu || !csws) return GGPM_ERR_ARG;
     if (lo < 1 || lo > depth) lo = 1;
@@ -1317,7 +1249,7 @@ int ggpm_gru_bias_u_grad(int E1, int H, int depth, int lo, float* work, float* d
         (void)hipMemsetAsync(dbu, 0, H * sizeof(float), (hipStream_t)stream);
         return GGPM_OK;
     }
-    const bool st16 = ggpm_gate_dtype() == 1 && ggpm_bf16_storage_applies(E1, H);
+    const bool st16 = ggpm_opts_or_default(opts).gate_dtype == 1 && ggpm_bf16_storage_applies(E1, H);
     return ggpm_colsum_any(ggpm_slot_ptr(DQ, lo, slot, st16), Hp, (depth - lo) * E1, H, dbu, csws, st16, stream);
 }
 
@@ -1361,7 +1293,7 @@ extern "C" size_t ggpm_weight_grads_stacked_workspace_bytes(int H, int rows) {
 }
 
 // The hidden-half weight gradients of MANY sparse backward calls at once: their stashes stacked row-wise (one block per
-// call, the same block order in every buffer), see ggpm_backward_defer_stash.
+// call, the same block order in every buffer), see ggpm_level_opts.defer_stash.
 extern "C" int ggpm_gru_weight_grads_stacked(int rows, int rows_q, int H, const float* DMP, const float* Gs,
                                              const float* DZP, const float* Ss, const float* DQ, const float* Hs,
                                              float* dWz_h, int ld_dwz, float* dUr, int ld_dur, float* dbu, float* dWh_h,
@@ -1390,14 +1322,16 @@ extern "C" int ggpm_gru_weight_grads_stacked(int rows, int rows_q, int H, const 
 
 int ggpm_gru_sparse_weight_grads(int E1, int H, int depth, const float* Hs, const float* Ss, const float* Gs, float* work,
                                  size_t work_bytes, float* dWz_h, int ld_dwz, float* dUr, int ld_dur, float* dbu, float* dWh_h,
-                                 int ld_dwh, ggpm_stream_t stream) {
+                                 int ld_dwh, const ggpm_level_opts* opts, ggpm_stream_t stream) {
     return gru_weight_grads_impl(E1, H, depth, Hs, Ss, Gs, work, work_bytes, dWz_h, ld_dwz, dUr, ld_dur, dbu, dWh_h, ld_dwh,
-                                 true, 1, stream);
+                                 true, 1, ggpm_opts_or_default(opts), stream);
 }
 
 extern "C" int ggpm_gru_weight_grads(int E1, int H, int depth, const float* Hs, const float* Ss, const float* Gs,
                                      float* work, size_t work_bytes, float* dWz_h, int ld_dwz, float* dUr,
-                                     int ld_dur, float* dbu, float* dWh_h, int ld_dwh, ggpm_stream_t stream) {
+                                     int ld_dur, float* dbu, float* dWh_h, int ld_dwh, const ggpm_level_opts* opts,
+                                     ggpm_stream_t stream) {
+    const ggpm_level_opts& o = ggpm_opts_or_default(opts);
     return gru_weight_grads_impl(E1, H, depth, Hs, Ss, Gs, work, work_bytes, dWz_h, ld_dwz, dUr, ld_dur, dbu, dWh_h,
-                                 ld_dwh, false, ggpm_take_wgrad_lo(), stream);
+                                 ld_dwh, false, o.lo, o, stream);
 }

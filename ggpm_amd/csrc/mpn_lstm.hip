@@ -30,7 +30,7 @@ struct LstmFwdArgs {
     int bf16;                        // gate products on bf16 operands (packed weights are bf16 fragments then)
     int st16;                        // bf16 storage of Hs / Qs / S / I / O / U (gate mode 1, large dense training levels; tile_mma.h)
     float* Hout;                     // ... then the LAST depth also writes h' in fp32 here (the level's result)
-    const float *src_h, *src_c;      // kernel B of a sparse forward's qf^0 launch (ggpm_forward_gather_state): the start
+    const float *src_h, *src_c;      // kernel B of a sparse forward's qf^0 launch (ggpm_level_opts.gather_*): the start
     const int32_t* src_idx;          // (h, c) of row r is (src_h, src_c)[src_idx[r]] (zero when < 0), written to Hnew / Cnew
 };
 
@@ -43,7 +43,7 @@ __device__ __forceinline__ float4 one_minus(float4 r) { return make_float4(1.f -
 template <bool STASH, int GM, int RTT, bool ST16 = false>
 __global__ void GGPM_A_BOUNDS lstm_fwd_a(LstmFwdArgs a) {
     static_assert(!ST16 || GM == 1, "bf16 storage goes with bf16 gate products");      // the cell state c and F stay fp32
-    constexpr int ROWS = RTT * 16;      // RTT = 2: two row tiles per workgroup (ggpm_level_prefer_narrow), no fused P3
+    constexpr int ROWS = RTT * 16;      // RTT = 2: two row tiles per workgroup (ggpm_level_opts.prefer_narrow), no fused P3
     constexpr bool BF16 = GM == 1, SPLIT = GM == 2;      // gate mode (LstmFwdArgs.bf16): 0 fp32 MFMA, 1 bf16, 2 split operands
     static_assert(!SPLIT || RTT == 1, "split operands: one row tile per workgroup");
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -315,7 +315,7 @@ struct LstmBwdArgs {
     float *carry_h, *carry_c;        // [E1,Hp] each, started by the first backward depth
     int final_pass;
     float *dHin, *dCin;
-    float *scat_h, *scat_c;          // ggpm_backward_scatter_state: the final pass ADDS row r's results to
+    float *scat_h, *scat_c;          // ggpm_level_opts.scatter_*: the final pass ADDS row r's results to
     const int32_t* scat_idx;         // (scat_h, scat_c)[scat_idx[r]] (unique ids; < 0: dropped) instead of writing dHin / dCin
     int fuse_b;                      // single column group: kernel A also forms dS for depth t-1 (no B launch)
     int bf16;                        // gate products on bf16 operands
@@ -327,7 +327,7 @@ struct LstmBwdArgs {
 // gate derivatives; dXf += dFC * F.
 template <int GM, int RTT, bool ST16 = false>
 __global__ void GGPM_A_BOUNDS lstm_bwd_a(LstmBwdArgs a) {
-    constexpr int ROWS = RTT * 16;      // RTT = 2: two row tiles per workgroup (ggpm_level_prefer_narrow), no fused P3
+    constexpr int ROWS = RTT * 16;      // RTT = 2: two row tiles per workgroup (ggpm_level_opts.prefer_narrow), no fused P3
     constexpr bool BF16 = GM == 1, SPLIT = GM == 2;
     static_assert(!SPLIT || RTT == 1, "split operands: one row tile per workgroup");
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -653,9 +653,9 @@ template <typename K>
 inline void set_lds(K kernel, size_t bytes) { ggpm_set_lds(kernel, bytes); }      // (common.h)
 
 inline size_t lds_tiles(int n, int Hp, int rows = ROWS) { return (size_t)n * rows * (Hp + 4) * sizeof(float); }
-// ggpm_level_prefer_narrow (mpn_gru.hip, common.h): two row tiles per workgroup for the dense fp32 level calls of this thread
-inline bool use_rt2(int Hp, bool sparse, int bf16) {
-    return ggpm_prefer_narrow() && !sparse && !bf16 && lds_tiles(3, Hp, 32) <= 160 * 1024;
+// ggpm_level_opts.prefer_narrow: two row tiles per workgroup for a dense fp32 level call
+inline bool use_rt2(const ggpm_level_opts& o, int Hp, bool sparse) {
+    return o.prefer_narrow && !sparse && o.gate_dtype != 1 && lds_tiles(3, Hp, 32) <= 160 * 1024;
 }
 
 // Environment switches are read once: getenv walks the whole environment (~0.5 us) and the launch helpers below run
@@ -676,7 +676,8 @@ inline int pick_tg(int E1, int NT) {
 
 // Gate mode of a level call (mpn_gru.hip: gate_mode): fp32 calls run their gate products on split operands (mode 2) where
 // one 16-row tile per workgroup applies and the backward's two fp32 tiles + the dqf image fit the LDS.
-inline int gate_mode(int dtype, int Hp, bool rt2, bool single_group, bool sparse) {
+inline int gate_mode(const ggpm_level_opts& o, int Hp, bool rt2, bool single_group, bool sparse) {
+    const int dtype = o.gate_dtype;
     if (dtype == 1) return 1;
     if (dtype == 2) return 0;
     static const bool on = [] { const char* e = ggpm_dev_env("GGPM_GATE_SPLIT"); return !e || atoi(e) != 0; }();
@@ -687,9 +688,8 @@ inline int gate_mode(int dtype, int Hp, bool rt2, bool single_group, bool sparse
     return (lds_tiles(2, Hp) + img <= 160 * 1024 && 3 * img <= 160 * 1024) ? 2 : 0;
 }
 
-void launch_fwd(LstmFwdArgs a, bool stash, bool with_b, double flops1, hipStream_t s) {
+void launch_fwd(LstmFwdArgs a, bool rt2, bool stash, bool with_b, double flops1, hipStream_t s) {
     const int Hp = a.Hp, NT = Hp / 16;
-    const bool rt2 = use_rt2(Hp, a.frozen != nullptr, a.bf16);
     const int rows = rt2 ? 32 : 16;
     dim3 grid_a(ggpm_ceil_div(a.E1, rows), ggpm_ceil_div(NT, a.tg));
     const bool split = a.bf16 == 2;
@@ -721,9 +721,8 @@ void launch_fwd(LstmFwdArgs a, bool stash, bool with_b, double flops1, hipStream
     }
 }
 
-void launch_bwd(LstmBwdArgs a, bool with_b, double flops1, hipStream_t s) {
+void launch_bwd(LstmBwdArgs a, bool rt2, bool with_b, double flops1, hipStream_t s) {
     const int Hp = a.Hp, NT = Hp / 16;
-    const bool rt2 = use_rt2(Hp, a.frozen != nullptr, a.bf16);
     const int rows = rt2 ? 32 : 16;
     dim3 grid_a(ggpm_ceil_div(a.E1, rows), ggpm_ceil_div(NT, a.tg));
     const bool split = a.bf16 == 2;
@@ -778,9 +777,8 @@ static int lstm_forward_impl(int E1, int H, int depth, const float* Xi, const fl
                              const int32_t* pred_rowptr, const int32_t* pred_col, float* Hs, float* Cs, float* Qs,
                              float* Ss, float* Is, float* Os, float* Us, float* Fs, float* wpack,
                              int save_for_backward, const float* h_in, const float* c_in,
-                             const unsigned char* frozen, ggpm_stream_t stream) {
+                             const unsigned char* frozen, const ggpm_level_opts& o, ggpm_stream_t stream) {
     GGPM_CLEAR_STALE_ERROR();
-    const bool weights_packed = ggpm_take_weights_packed();      // (consumed on every path)
     if (E1 <= 0 || H <= 0 || depth <= 0 || !Xi || !Xo || !Xu || !Xf || !Wi_h || !Wo_h || !Wu_h || !Wf_h ||
         !pred_rowptr || !pred_col || !Hs || !Cs || !Qs || !wpack)
         return GGPM_ERR_ARG;
@@ -789,8 +787,8 @@ static int lstm_forward_impl(int E1, int H, int depth, const float* Xi, const fl
     if (!lstm_shape_ok(Hp) || (size_t)E1 * Hp >= ((size_t)1 << 30)) return GGPM_ERR_UNSUPPORTED;      // (32-bit byte offsets inside a slot)
     hipStream_t s = (hipStream_t)stream;
     const size_t HH = (size_t)Hp * Hp, slot = (size_t)E1 * Hp;
-    const int bf16 = gate_mode(ggpm_gate_dtype(), Hp, use_rt2(Hp, frozen != nullptr, ggpm_gate_dtype() == 1),
-                               pick_tg(E1, Hp / 16) >= Hp / 16, frozen != nullptr);      // gate mode 0 / 1 / 2
+    const bool rt2 = use_rt2(o, Hp, frozen != nullptr);
+    const int bf16 = gate_mode(o, Hp, rt2, pick_tg(E1, Hp / 16) >= Hp / 16, frozen != nullptr);      // gate mode 0 / 1 / 2
     const size_t mstep = ggpm_packed_matrix_floats(Hp, bf16);
     float* pWi = wpack; float* pWo = wpack + mstep; float* pWu = wpack + 2 * mstep; float* pWf = wpack + 3 * mstep;
     {
@@ -798,20 +796,18 @@ static int lstm_forward_impl(int E1, int H, int depth, const float* Xi, const fl
         pk.W[0] = Wi_h; pk.ldw[0] = ld_wi; pk.W[1] = Wo_h; pk.ldw[1] = ld_wo; pk.W[2] = Wu_h; pk.ldw[2] = ld_wu;
         pk.W[3] = Wf_h; pk.ldw[3] = ld_wf;
         pk.H = H; pk.Hp = Hp; pk.transpose = 0; pk.dst = wpack; pk.bias = nullptr; pk.bias_out = nullptr; pk.bf16 = bf16;
-        if (!weights_packed) ggpm_launch_pack(pk, 4, s);
+        if (!o.weights_packed) ggpm_launch_pack(pk, 4, s);
     }
     const int tg = pick_tg(E1, Hp / 16);
-    const float *gs_h = nullptr, *gs_c = nullptr;
-    const int32_t* gs_idx = nullptr;
-    const bool gathered = ggpm_take_gather_state(&gs_h, &gs_c, &gs_idx) && frozen && gs_c;      // (consumed on every path)
+    const bool gathered = o.gather_h && o.gather_idx && frozen && o.gather_c;
     if (frozen) {      // sparse_forward: start from the caller's (h, c); qf^0 = Wf_h h^0 by one B launch
         dim3 ig(ggpm_ceil_div(Hp, 256), E1);
-        // (h_in == Hs and c_in == Cs: the caller put the masked start state into slot 0 itself; ggpm_forward_gather_state:
+        // (h_in == Hs and c_in == Cs: the caller put the masked start state into slot 0 itself; ggpm_level_opts.gather_*:
         // the qf^0 launch fetches it through the index and writes slot 0 of both on the way)
         if ((h_in != Hs || c_in != Cs) && !gathered) lstm_sparse_init_state<<<ig, 256, 0, s>>>(h_in, c_in, frozen, Hs, Cs, Hp);
         LstmFwdArgs a0 = {};
         a0.E1 = E1; a0.Hp = Hp; a0.tg = tg; a0.Hnew = Hs; a0.Qnew = Qs; a0.Wf = pWf; a0.bf16 = bf16;
-        if (gathered) { a0.src_h = gs_h; a0.src_c = gs_c; a0.src_idx = gs_idx; a0.Cnew = Cs; }
+        if (gathered) { a0.src_h = o.gather_h; a0.src_c = o.gather_c; a0.src_idx = o.gather_idx; a0.Cnew = Cs; }
         const size_t lb = bf16 == 2 ? ggpm_split_image_bytes(ROWS, Hp) : lds_tiles(1, Hp);
         dim3 grid_a(ggpm_ceil_div(E1, ROWS), ggpm_ceil_div(Hp / 16, tg));
         if (bf16 == 2) { set_lds(lstm_fwd_b<2, 1>, lb); lstm_fwd_b<2, 1><<<grid_a, GGPM_NWA * 64, lb, s>>>(a0); }
@@ -824,7 +820,7 @@ static int lstm_forward_impl(int E1, int H, int depth, const float* Xi, const fl
     }
 
     const double flops1 = 2.0 * (double)(E1 - 1) * H * H;   // algorithmic flops of ONE gate product
-    int run_depth = ggpm_take_run_depth();
+    int run_depth = o.run_depth;
     if (run_depth <= 0 || run_depth > depth || frozen || !save_for_backward) run_depth = depth;
     // bf16 storage (tile_mma.h): bf16 gate products, dense, training, every stash contraction on the bf16 tall kernel
     const bool st16 = bf16 == 1 && !frozen && save_for_backward && ggpm_bf16_storage_applies(E1, H);
@@ -850,7 +846,7 @@ static int lstm_forward_impl(int E1, int H, int depth, const float* Xi, const fl
             a.Qprev = Qs + (size_t)((t - 1) & 1) * slot; a.Qnew = Qs + (size_t)(t & 1) * slot;
             a.S = a.I = a.O = a.U = a.F = nullptr;
         }
-        launch_fwd(a, save_for_backward != 0, t < depth, flops1, s);
+        launch_fwd(a, rt2, save_for_backward != 0, t < depth, flops1, s);
     }
     GGPM_CHECK_LAUNCH();
     return GGPM_OK;
@@ -861,10 +857,10 @@ extern "C" int ggpm_lstm_forward(int E1, int H, int depth, const float* Xi, cons
                                  const float* Wu_h, int ld_wu, const float* Wf_h, int ld_wf,
                                  const int32_t* pred_rowptr, const int32_t* pred_col, float* Hs, float* Cs,
                                  float* Qs, float* Ss, float* Is, float* Os, float* Us, float* Fs,
-                                 float* wpack, int save_for_backward, ggpm_stream_t stream) {
+                                 float* wpack, int save_for_backward, const ggpm_level_opts* opts, ggpm_stream_t stream) {
     return lstm_forward_impl(E1, H, depth, Xi, Xo, Xu, Xf, Wi_h, ld_wi, Wo_h, ld_wo, Wu_h, ld_wu, Wf_h, ld_wf, pred_rowptr,
                              pred_col, Hs, Cs, Qs, Ss, Is, Os, Us, Fs, wpack, save_for_backward, nullptr, nullptr,
-                             nullptr, stream);
+                             nullptr, ggpm_opts_or_default(opts), stream);
 }
 
 extern "C" int ggpm_lstm_sparse_forward(int E1, int H, int depth, const float* h_in, const float* c_in,
@@ -874,11 +870,11 @@ extern "C" int ggpm_lstm_sparse_forward(int E1, int H, int depth, const float* h
                                         const float* Wf_h, int ld_wf, const int32_t* pred_rowptr,
                                         const int32_t* pred_col, float* Hs, float* Cs, float* Qs, float* Ss,
                                         float* Is, float* Os, float* Us, float* Fs, float* wpack,
-                                        int save_for_backward, ggpm_stream_t stream) {
+                                        int save_for_backward, const ggpm_level_opts* opts, ggpm_stream_t stream) {
     if (!h_in || !c_in || !frozen) return GGPM_ERR_ARG;
     return lstm_forward_impl(E1, H, depth, Xi, Xo, Xu, Xf, Wi_h, ld_wi, Wo_h, ld_wo, Wu_h, ld_wu, Wf_h, ld_wf, pred_rowptr,
                              pred_col, Hs, Cs, Qs, Ss, Is, Os, Us, Fs, wpack, save_for_backward, h_in, c_in, frozen,
-                             stream);
+                             ggpm_opts_or_default(opts), stream);
 }
 
 extern "C" size_t ggpm_lstm_backward_workspace_bytes(int E1, int H, int depth) {
@@ -896,7 +892,8 @@ extern "C" size_t ggpm_lstm_backward_workspace_bytes(int E1, int H, int depth) {
 
 static int lstm_weight_grads_impl(int E1, int H, int depth, const float* Hs, const float* Ss, float* work,
                                   size_t work_bytes, float* dWi_h, int ld_dwi, float* dWo_h, int ld_dwo, float* dWu_h,
-                                  int ld_dwu, float* dWf_h, int ld_dwf, bool with_slot0, int lo, ggpm_stream_t stream);
+                                  int ld_dwu, float* dWf_h, int ld_dwf, bool with_slot0, int lo, const ggpm_level_opts& o,
+                                  ggpm_stream_t stream);
 
 static int lstm_backward_impl(int E1, int H, int depth, const float* Xf, const float* Wi_h, int ld_wi,
                                   const float* Wo_h, int ld_wo, const float* Wu_h, int ld_wu, const float* Wf_h,
@@ -908,13 +905,11 @@ static int lstm_backward_impl(int E1, int H, int depth, const float* Xf, const f
                                   float* dXu, float* dXf, float* dWi_h, int ld_dwi, float* dWo_h, int ld_dwo,
                                   float* dWu_h, int ld_dwu, float* dWf_h, int ld_dwf, float* work,
                                   size_t work_bytes, int weight_grads, const unsigned char* frozen,
-                                  const float* dCD, float* dHin, float* dCin, ggpm_stream_t stream) {
+                                  const float* dCD, float* dHin, float* dCin, const ggpm_level_opts& o,
+                                  ggpm_stream_t stream) {
     GGPM_CLEAR_STALE_ERROR();
-    if (ggpm_take_sparse_skip_wgrads() && frozen) weight_grads = 0;      // (ggpm_lstm_sparse_weight_grads follows)
-    const bool weights_packed = ggpm_take_weights_packed();      // (consumed on every path)
-    float *ss_h = nullptr, *ss_c = nullptr;
-    const int32_t* ss_idx = nullptr;
-    const bool scattered = ggpm_take_scatter_state(&ss_h, &ss_c, &ss_idx) && frozen && ss_c;      // (consumed on every path)
+    if (o.skip_sparse_wgrads && frozen) weight_grads = 0;      // (ggpm_lstm_sparse_weight_grads follows)
+    const bool scattered = o.scatter_h && o.scatter_idx && frozen && o.scatter_c;
     if (E1 <= 0 || H <= 0 || depth <= 0 || !Xf || !Wi_h || !Wo_h || !Wu_h || !Wf_h || !pred_rowptr || !pred_col ||
         !succ_rowptr || !succ_col || !Hs || !Cs || !Qs || !Ss || !Is || !Os || !Us || !Fs || !dHD || !dXi || !dXo || !dXu ||
         !dXf || !dWi_h || !dWo_h || !dWu_h || !dWf_h || !work)
@@ -925,11 +920,11 @@ static int lstm_backward_impl(int E1, int H, int depth, const float* Xf, const f
     hipStream_t s = (hipStream_t)stream;
     const size_t HH = (size_t)Hp * Hp, slot = (size_t)E1 * Hp;
 
-    const bool skip_xsum = ggpm_take_skip_x_sums() && !frozen;
-    // (the packed transposes come first: their place does not depend on E1 -- ggpm_weights_packed)
+    const bool skip_xsum = o.skip_x_sums && !frozen;
+    // (the packed transposes come first: their place does not depend on E1 -- ggpm_level_opts.weights_packed)
     float* w = work;
-    const int bf16 = gate_mode(ggpm_gate_dtype(), Hp, use_rt2(Hp, frozen != nullptr, ggpm_gate_dtype() == 1),
-                               pick_tg(E1, Hp / 16) >= Hp / 16, frozen != nullptr);      // gate mode 0 / 1 / 2
+    const bool rt2 = use_rt2(o, Hp, frozen != nullptr);
+    const int bf16 = gate_mode(o, Hp, rt2, pick_tg(E1, Hp / 16) >= Hp / 16, frozen != nullptr);      // gate mode 0 / 1 / 2
     const size_t mstep = ggpm_packed_matrix_floats(Hp, bf16);
     float* pWiT = w; float* pWoT = w + mstep; float* pWuT = w + 2 * mstep; float* pWfT = w + 3 * mstep;
     w += 4 * ggpm_packed_matrix_slot(Hp);
@@ -942,13 +937,10 @@ static int lstm_backward_impl(int E1, int H, int depth, const float* Xf, const f
     float* carry_h = w; w += slot; float* carry_c = w; w += slot;
     float* skws = w;
     const size_t skbytes = work_bytes - (size_t)((char*)skws - (char*)work);
-    {       // deferred weight gradients (ggpm_backward_defer_stash): the stashes go to the caller's stacked buffers
-        float* ext[4];
-        if (ggpm_take_defer_stash(ext)) {
-            if (!frozen || !ext[1] || !ext[2] || !ext[3]) return GGPM_ERR_ARG;
-            DI = ext[0]; DO = ext[1]; DU = ext[2]; DQ = ext[3];
-            weight_grads = 0;
-        }
+    if (o.defer_stash[0]) {       // deferred weight gradients: the stashes go to the caller's stacked buffers
+        if (!frozen || !o.defer_stash[1] || !o.defer_stash[2] || !o.defer_stash[3]) return GGPM_ERR_ARG;
+        DI = o.defer_stash[0]; DO = o.defer_stash[1]; DU = o.defer_stash[2]; DQ = o.defer_stash[3];
+        weight_grads = 0;
     }
     (void)skws; (void)skbytes;
 
@@ -957,14 +949,14 @@ static int lstm_backward_impl(int E1, int H, int depth, const float* Xf, const f
         pk.W[0] = Wi_h; pk.ldw[0] = ld_wi; pk.W[1] = Wo_h; pk.ldw[1] = ld_wo; pk.W[2] = Wu_h; pk.ldw[2] = ld_wu;
         pk.W[3] = Wf_h; pk.ldw[3] = ld_wf;
         pk.H = H; pk.Hp = Hp; pk.transpose = 1; pk.dst = pWiT; pk.bias = nullptr; pk.bias_out = nullptr; pk.bf16 = bf16;
-        if (!weights_packed) ggpm_launch_pack(pk, 4, s);
+        if (!o.weights_packed) ggpm_launch_pack(pk, 4, s);
     }
     // dXi / dXo / dXu / dXf are started (not accumulated) by the first backward depth
 
     const int tg = pick_tg(E1, Hp / 16);
     const double flops1 = 2.0 * (double)(E1 - 1) * H * H;   // algorithmic flops of ONE gate product
     // tree-side levels: d(h^t), d(c^t) vanish below step `lo` (nilpotent Jacobian, common.h)
-    int lo = ggpm_take_backward_lo();
+    int lo = o.lo;
     if (lo < 1 || lo > depth || frozen) lo = 1;
     const bool st16 = bf16 == 1 && !frozen && ggpm_bf16_storage_applies(E1, H);      // (as the forward decided)
     for (int t = depth; t >= lo; --t) {
@@ -989,7 +981,7 @@ static int lstm_backward_impl(int E1, int H, int depth, const float* Xf, const f
         a.WiT = pWiT; a.WoT = pWoT; a.WuT = pWuT; a.WfT = pWfT; a.bf16 = bf16;
         a.srowptr = succ_rowptr; a.scol = succ_col;
         a.skip_xsum = skip_xsum ? 1 : 0;
-        launch_bwd(a, t > 1 || frozen != nullptr, flops1, s);
+        launch_bwd(a, rt2, t > 1 || frozen != nullptr, flops1, s);
     }
     GGPM_CHECK_LAUNCH();
     if (frozen) {      // gradient of the incoming (h, c): one more gather + dqf.Wf_h launch at t = 0
@@ -999,14 +991,14 @@ static int lstm_backward_impl(int E1, int H, int depth, const float* Xf, const f
         a.dSin = dSb[1]; a.dFCin = dFb[1];          // written by the launches of depth 1
         a.DQ = DQ; a.WfT = pWfT; a.srowptr = succ_rowptr; a.scol = succ_col; a.bf16 = bf16;
         a.frozen = frozen; a.carry_h = carry_h; a.carry_c = carry_c; a.dHin = dHin; a.dCin = dCin;
-        if (scattered) { a.scat_h = ss_h; a.scat_c = ss_c; a.scat_idx = ss_idx; }
-        launch_bwd(a, false, flops1, s);
+        if (scattered) { a.scat_h = o.scatter_h; a.scat_c = o.scatter_c; a.scat_idx = o.scatter_idx; }
+        launch_bwd(a, rt2, false, flops1, s);
         GGPM_CHECK_LAUNCH();
     }
 
     if (!weight_grads) return GGPM_OK;
     return lstm_weight_grads_impl(E1, H, depth, Hs, Ss, work, work_bytes, dWi_h, ld_dwi, dWo_h, ld_dwo, dWu_h, ld_dwu,
-                                  dWf_h, ld_dwf, frozen != nullptr, lo, stream);
+                                  dWf_h, ld_dwf, frozen != nullptr, lo, o, stream);
 }
 
 // where ggpm_lstm_backward left its di_pre / do_pre / du_pre stashes inside `work` (slot t-1 of each = backward step t)
@@ -1027,11 +1019,11 @@ extern "C" int ggpm_lstm_backward(int E1, int H, int depth, const float* Xf, con
                                   const float* Os, const float* Us, const float* Fs, const float* dHD, float* dXi,
                                   float* dXo, float* dXu, float* dXf, float* dWi_h, int ld_dwi, float* dWo_h,
                                   int ld_dwo, float* dWu_h, int ld_dwu, float* dWf_h, int ld_dwf, float* work,
-                                  size_t work_bytes, int weight_grads, ggpm_stream_t stream) {
+                                  size_t work_bytes, int weight_grads, const ggpm_level_opts* opts, ggpm_stream_t stream) {
     return lstm_backward_impl(E1, H, depth, Xf, Wi_h, ld_wi, Wo_h, ld_wo, Wu_h, ld_wu, Wf_h, ld_wf, pred_rowptr, pred_col,
                               succ_rowptr, succ_col, Hs, Cs, Qs, Ss, Is, Os, Us, Fs, dHD, dXi, dXo, dXu, dXf, dWi_h, ld_dwi,
                               dWo_h, ld_dwo, dWu_h, ld_dwu, dWf_h, ld_dwf, work, work_bytes, weight_grads, nullptr, nullptr,
-                              nullptr, nullptr, stream);
+                              nullptr, nullptr, ggpm_opts_or_default(opts), stream);
 }
 
 // sparse_forward backward: takes dL/dh_D and dL/dc_D, additionally returns dHin / dCin (zero on the recomputed rows)
@@ -1045,18 +1037,19 @@ extern "C" int ggpm_lstm_sparse_backward(int E1, int H, int depth, const unsigne
                                          const float* dCD, float* dHin, float* dCin, float* dXi, float* dXo,
                                          float* dXu, float* dXf, float* dWi_h, int ld_dwi, float* dWo_h, int ld_dwo,
                                          float* dWu_h, int ld_dwu, float* dWf_h, int ld_dwf, float* work,
-                                         size_t work_bytes, ggpm_stream_t stream) {
+                                         size_t work_bytes, const ggpm_level_opts* opts, ggpm_stream_t stream) {
     if (!frozen || !dHin || !dCin) return GGPM_ERR_ARG;
     return lstm_backward_impl(E1, H, depth, Xf, Wi_h, ld_wi, Wo_h, ld_wo, Wu_h, ld_wu, Wf_h, ld_wf, pred_rowptr, pred_col,
                               succ_rowptr, succ_col, Hs, Cs, Qs, Ss, Is, Os, Us, Fs, dHD, dXi, dXo, dXu, dXf, dWi_h, ld_dwi,
                               dWo_h, ld_dwo, dWu_h, ld_dwu, dWf_h, ld_dwf, work, work_bytes, 1, frozen, dCD, dHin, dCin,
-                              stream);
+                              ggpm_opts_or_default(opts), stream);
 }
 
 // Weight gradients of the LSTM message function from the stashes ggpm_lstm_backward left in `work`.
 static int lstm_weight_grads_impl(int E1, int H, int depth, const float* Hs, const float* Ss, float* work,
                                   size_t work_bytes, float* dWi_h, int ld_dwi, float* dWo_h, int ld_dwo, float* dWu_h,
-                                  int ld_dwu, float* dWf_h, int ld_dwf, bool with_slot0, int lo, ggpm_stream_t stream) {
+                                  int ld_dwu, float* dWf_h, int ld_dwf, bool with_slot0, int lo, const ggpm_level_opts& o,
+                                  ggpm_stream_t stream) {
     GGPM_CLEAR_STALE_ERROR();
     if (E1 <= 0 || H <= 0 || depth <= 0 || !Hs || !Ss || !work || !dWi_h || !dWo_h || !dWu_h || !dWf_h)
         return GGPM_ERR_ARG;
@@ -1075,8 +1068,8 @@ static int lstm_weight_grads_impl(int E1, int H, int depth, const float* Hs, con
     const size_t skbytes = work_bytes - (size_t)((char*)skws - (char*)work);
     const int KD = (depth - lo + 1) * E1;
     // bf16 storage (as the forward / backward decided): bf16 stashes in the first half of their buffers, read as they are
-    const bool st16 = ggpm_gate_dtype() == 1 && !with_slot0 && ggpm_bf16_storage_applies(E1, H);
-    const int tall_mode = st16 ? 2 : (ggpm_gate_dtype() == 1 ? 1 : 0);
+    const bool st16 = o.gate_dtype == 1 && !with_slot0 && ggpm_bf16_storage_applies(E1, H);
+    const int tall_mode = st16 ? 2 : (o.gate_dtype == 1 ? 1 : 0);
     const float* Sl = ggpm_slot_ptr(Ss, lo - 1, slot, st16);
     int rc;
     // the three or four contractions in ONE launch and one reduce (they share the split-K workspace)
@@ -1128,14 +1121,16 @@ extern "C" int ggpm_lstm_weight_grads_stacked(int rows, int rows_q, int H, const
 
 int ggpm_lstm_sparse_weight_grads(int E1, int H, int depth, const float* Hs, const float* Ss, float* work, size_t work_bytes,
                                   float* dWi_h, int ld_dwi, float* dWo_h, int ld_dwo, float* dWu_h, int ld_dwu, float* dWf_h,
-                                  int ld_dwf, ggpm_stream_t stream) {
+                                  int ld_dwf, const ggpm_level_opts* opts, ggpm_stream_t stream) {
     return lstm_weight_grads_impl(E1, H, depth, Hs, Ss, work, work_bytes, dWi_h, ld_dwi, dWo_h, ld_dwo, dWu_h, ld_dwu, dWf_h,
-                                  ld_dwf, true, 1, stream);
+                                  ld_dwf, true, 1, ggpm_opts_or_default(opts), stream);
 }
 
 extern "C" int ggpm_lstm_weight_grads(int E1, int H, int depth, const float* Hs, const float* Ss, float* work,
                                       size_t work_bytes, float* dWi_h, int ld_dwi, float* dWo_h, int ld_dwo,
-                                      float* dWu_h, int ld_dwu, float* dWf_h, int ld_dwf, ggpm_stream_t stream) {
+                                      float* dWu_h, int ld_dwu, float* dWf_h, int ld_dwf, const ggpm_level_opts* opts,
+                                      ggpm_stream_t stream) {
+    const ggpm_level_opts& o = ggpm_opts_or_default(opts);
     return lstm_weight_grads_impl(E1, H, depth, Hs, Ss, work, work_bytes, dWi_h, ld_dwi, dWo_h, ld_dwo, dWu_h, ld_dwu,
-                                  dWf_h, ld_dwf, false, ggpm_take_wgrad_lo(), stream);
+                                  dWf_h, ld_dwf, false, o.lo, o, stream);
 }

@@ -145,12 +145,12 @@ extern "C" int ggpm_tree_level_forward(const ggpm_tree_level* L, float* saved, s
                                     v.X + 3 * d.slot, L->gate_w[0] + I, L->ld_gate[0], L->gate_w[1] + I, L->ld_gate[1],
                                     L->gate_w[2] + I, L->ld_gate[2], L->gate_w[3] + I, L->ld_gate[3], L->pred_rowptr,
                                     L->pred_col, v.Hs, v.Cs, v.Qs, v.St, v.St + ds, v.St + 2 * ds, v.St + 3 * ds,
-                                    v.St + 4 * ds, v.wpack, 1, stream));
+                                    v.St + 4 * ds, v.wpack, 1, nullptr, stream));
     } else {
         CK(ggpm_gru_sparse_forward(d.Etot, H, d.depth, v.hp, L->frozen, v.X, v.X + d.slot, v.X + 2 * d.slot,
                                    L->gate_w[0] + I, L->ld_gate[0], L->Ur, L->ld_ur, L->bu, L->gate_w[2] + I, L->ld_gate[2],
                                    L->pred_rowptr, L->pred_col, v.Hs, v.Qs, v.St, v.St + ds, v.St + 2 * ds, v.St + 3 * ds,
-                                   v.St + 4 * ds, v.wpack, 1, stream));
+                                   v.St + 4 * ds, v.wpack, 1, nullptr, stream));
     }
     // 6. read-out of every visit
     const float* hid = v.Hs + (size_t)d.depth * d.slot;
@@ -223,7 +223,8 @@ extern "C" int ggpm_tree_level_backward(const ggpm_tree_level* L, const ggpm_tre
     // ---- the level
     const size_t ds = (size_t)d.depth * d.slot;
     hipStream_t ws = side_stream ? (hipStream_t)side_stream : s;       // where the parameter gradients are formed
-    if (side_stream) ggpm_sparse_backward_skip_wgrads(1);
+    ggpm_level_opts opts = {};
+    opts.skip_sparse_wgrads = side_stream != nullptr;      // (the sparse weight-gradient call below forms them on `ws`)
     if (d.lstm) {
         if (hipMemsetAsync(dCD, 0, d.slot * sizeof(float), s) != hipSuccess) return GGPM_ERR_LAUNCH;
         CK(ggpm_lstm_sparse_backward(d.Etot, H, d.depth, L->frozen, v.X + 3 * d.slot, L->gate_w[0] + I, L->ld_gate[0],
@@ -232,13 +233,13 @@ extern "C" int ggpm_tree_level_backward(const ggpm_tree_level* L, const ggpm_tre
                                      v.St, v.St + ds, v.St + 2 * ds, v.St + 3 * ds, v.St + 4 * ds, dHD, dCD, g->dHin, dCin, dX,
                                      dX + d.slot, dX + 2 * d.slot, dX + 3 * d.slot, g->dgate_w[0] + I, g->ld_dgate[0],
                                      g->dgate_w[1] + I, g->ld_dgate[1], g->dgate_w[2] + I, g->ld_dgate[2], g->dgate_w[3] + I,
-                                     g->ld_dgate[3], lwork, lwb, stream));
+                                     g->ld_dgate[3], lwork, lwb, &opts, stream));
     } else {
         CK(ggpm_gru_sparse_backward(d.Etot, H, d.depth, L->frozen, v.X + d.slot, L->gate_w[0] + I, L->ld_gate[0], L->Ur,
                                     L->ld_ur, L->gate_w[2] + I, L->ld_gate[2], L->pred_rowptr, L->pred_col, L->succ_rowptr,
                                     L->succ_col, v.Hs, v.Qs, v.St, v.St + ds, v.St + 2 * ds, v.St + 3 * ds, v.St + 4 * ds, dHD,
                                     g->dHin, dX, dX + d.slot, dX + 2 * d.slot, g->dgate_w[0] + I, g->ld_dgate[0], g->dUr, H,
-                                    g->dbu, g->dgate_w[2] + I, g->ld_dgate[2], lwork, lwb, stream));
+                                    g->dbu, g->dgate_w[2] + I, g->ld_dgate[2], lwork, lwb, &opts, stream));
     }
     if (side_stream) {      // the stashes and dX are complete: hidden halves on the second stream, in the order the level call had them
         hipEvent_t ev = ggpm_wgrad_event(41);
@@ -246,10 +247,10 @@ extern "C" int ggpm_tree_level_backward(const ggpm_tree_level* L, const ggpm_tre
         if (d.lstm)
             CK(ggpm_lstm_sparse_weight_grads(d.Etot, H, d.depth, v.Hs, v.St, lwork, lwb, g->dgate_w[0] + I, g->ld_dgate[0],
                                              g->dgate_w[1] + I, g->ld_dgate[1], g->dgate_w[2] + I, g->ld_dgate[2],
-                                             g->dgate_w[3] + I, g->ld_dgate[3], (ggpm_stream_t)ws));
+                                             g->dgate_w[3] + I, g->ld_dgate[3], nullptr, (ggpm_stream_t)ws));
         else
             CK(ggpm_gru_sparse_weight_grads(d.Etot, H, d.depth, v.Hs, v.St, v.St + ds, lwork, lwb, g->dgate_w[0] + I,
-                                            g->ld_dgate[0], g->dUr, H, g->dbu, g->dgate_w[2] + I, g->ld_dgate[2],
+                                            g->ld_dgate[0], g->dUr, H, g->dbu, g->dgate_w[2] + I, g->ld_dgate[2], nullptr,
                                             (ggpm_stream_t)ws));
     }
     // input halves of the gate weights, gate biases (the rows of the real messages, 1 .. E1-1, are contiguous)

@@ -248,6 +248,24 @@ class GemmProblem(ctypes.Structure):
                 ("accumulate", ctypes.c_int), ("act", ctypes.c_int), ("zero_row0", ctypes.c_int)]
 
 
+class LevelOpts(ctypes.Structure):
+    """include/ggpm_hip.h: ggpm_level_opts -- the options of ONE level call (None: all defaults)"""
+    _fields_ = [("gate_dtype", ctypes.c_int), ("prefer_narrow", ctypes.c_int), ("weights_packed", ctypes.c_int),
+                ("defer_stash", ctypes.c_void_p * 4), ("gather_h", ctypes.c_void_p), ("gather_c", ctypes.c_void_p),
+                ("gather_idx", ctypes.c_void_p), ("scatter_h", ctypes.c_void_p), ("scatter_c", ctypes.c_void_p),
+                ("scatter_idx", ctypes.c_void_p), ("skip_x_sums", ctypes.c_int), ("run_depth", ctypes.c_int),
+                ("lo", ctypes.c_int), ("skip_bias_u", ctypes.c_int), ("skip_sparse_wgrads", ctypes.c_int)]
+
+
+_GATE_OPTS = {dt: LevelOpts(gate_dtype=dt) for dt in (1, 2, 3)}
+
+
+def _gate_opts(gate_dtype: int):
+    """The options of a dense level call on gate-product dtype ``gate_dtype`` (0: None, the defaults)."""
+    o = _GATE_OPTS.get(gate_dtype)
+    return None if o is None else ctypes.byref(o)
+
+
 def gemm_grouped(ta: int, tb: int, M: int, N: int, K: int, problems, splitk: bool = False) -> None:
     """problems: list of dicts(A, lda, B, ldb, C, ldc, n_pad, bias=None, accumulate=False, act=ACT_NONE, zero_row0=False);
     up to four independent products of one shape in one launch.  ``splitk``: the K range in chunks where the group has few
@@ -827,11 +845,10 @@ class _GruLevel(torch.autograd.Function):
             Hs = torch.empty(2, E1, Hp, **f32)
             Qs = torch.empty(2, E1, Hp, **f32)
             Ss = Gs = Zs = Ms = Rs = None
-        with _gate_dtype(gate_dtype):
-            _lib.check(lib.ggpm_gru_forward(E1, H, depth, _p(X[0]), _p(X[1]), _p(X[2]), _p(Wz_h), W_z.stride(0),
-                                            _p(U_r), U_r.stride(0), _p(b_u), _p(Wh_h), W_h.stride(0), _p(pred.rowptr),
-                                            _p(pred.col), _p(Hs), _p(Qs), _p(Ss), _p(Gs), _p(Zs), _p(Ms), _p(Rs),
-                                            _p(wpack), int(save), _stream()), "gru_forward")
+        _lib.check(lib.ggpm_gru_forward(E1, H, depth, _p(X[0]), _p(X[1]), _p(X[2]), _p(Wz_h), W_z.stride(0),
+                                        _p(U_r), U_r.stride(0), _p(b_u), _p(Wh_h), W_h.stride(0), _p(pred.rowptr),
+                                        _p(pred.col), _p(Hs), _p(Qs), _p(Ss), _p(Gs), _p(Zs), _p(Ms), _p(Rs),
+                                        _p(wpack), int(save), _gate_opts(gate_dtype), _stream()), "gru_forward")
         if save:
             ctx.save_for_backward(x, W_z, W_r, U_r, W_h)
             ctx.stash = (X[1], Hs, Qs, Ss, Gs, Zs, Ms, Rs)
@@ -861,13 +878,13 @@ class _GruLevel(torch.autograd.Function):
         wb = int(lib.ggpm_gru_backward_workspace_bytes(E1, H, depth))
         work = torch.empty((wb + 3) // 4, **f32)
         use_side = side_stream_enabled() and can_publish(*ctx.params)
-        with _gate_dtype(ctx.gate_dtype):
-            _lib.check(lib.ggpm_gru_backward(E1, H, depth, _p(Xr), _p(Wz_h), W_z.stride(0), _p(U_r), U_r.stride(0),
-                                             _p(Wh_h), W_h.stride(0), _p(pred.rowptr), _p(pred.col), _p(succ.rowptr),
-                                             _p(succ.col), _p(Hs), _p(Qs), _p(Ss), _p(Gs), _p(Zs), _p(Ms), _p(Rs),
-                                             _p(dHD), _p(dX[0]), _p(dX[1]), _p(dX[2]), _p(dWz_h), dW_z.stride(0),
-                                             _p(dU_r), H, _p(db_u), _p(dWh_h), dW_h.stride(0), _p(work),
-                                             work.numel() * 4, 0 if use_side else 1, _stream()), "gru_backward")
+        _lib.check(lib.ggpm_gru_backward(E1, H, depth, _p(Xr), _p(Wz_h), W_z.stride(0), _p(U_r), U_r.stride(0),
+                                         _p(Wh_h), W_h.stride(0), _p(pred.rowptr), _p(pred.col), _p(succ.rowptr),
+                                         _p(succ.col), _p(Hs), _p(Qs), _p(Ss), _p(Gs), _p(Zs), _p(Ms), _p(Rs),
+                                         _p(dHD), _p(dX[0]), _p(dX[1]), _p(dX[2]), _p(dWz_h), dW_z.stride(0),
+                                         _p(dU_r), H, _p(db_u), _p(dWh_h), dW_h.stride(0), _p(work),
+                                         work.numel() * 4, 0 if use_side else 1, _gate_opts(ctx.gate_dtype), _stream()),
+                   "gru_backward")
         ctx.stash = None
         ldx = _ld(x)
         dx = None
@@ -879,10 +896,9 @@ class _GruLevel(torch.autograd.Function):
 
         def weight_grads():
             if use_side:
-                with _gate_dtype(ctx.gate_dtype):
-                    _lib.check(lib.ggpm_gru_weight_grads(E1, H, depth, _p(Hs), _p(Ss), _p(Gs), _p(work), work.numel() * 4,
-                                                         _p(dWz_h), dW_z.stride(0), _p(dU_r), H, _p(db_u), _p(dWh_h),
-                                                         dW_h.stride(0), _stream()), "gru_weight_grads")
+                _lib.check(lib.ggpm_gru_weight_grads(E1, H, depth, _p(Hs), _p(Ss), _p(Gs), _p(work), work.numel() * 4,
+                                                     _p(dWz_h), dW_z.stride(0), _p(dU_r), H, _p(db_u), _p(dWh_h),
+                                                     dW_h.stride(0), _gate_opts(ctx.gate_dtype), _stream()), "gru_weight_grads")
             # x-halves of the gate weights and the gate biases
             gemm(1, 0, H, I, E1, dX[0], Hp, x, ldx, dWz_x, dW_z.stride(0), I, splitk=True)
             gemm(1, 0, H, I, E1, dX[1], Hp, x, ldx, dW_r, dW_r.stride(0), I, splitk=True)
@@ -908,23 +924,6 @@ class _GruLevel(torch.autograd.Function):
 
 
 GATE_DTYPES = {"f32": 0, "fp32": 0, "bf16": 1, "f32_mfma": 2, "f32_split": 3, None: 0, 0: 0, 1: 1, 2: 2, 3: 3}
-
-
-class _gate_dtype:
-    """``with _gate_dtype(1):`` -- the level calls issued inside run their hidden x hidden products on bf16 operands
-    (ggpm_level_gate_dtype is per thread, so this holds for exactly the calls made here, on whichever thread autograd
-    runs the function)."""
-
-    def __init__(self, dt):
-        self.dt = dt
-
-    def __enter__(self):
-        self.prev = _lib.load().ggpm_level_gate_dtype(self.dt) if self.dt else 0
-
-    def __exit__(self, *exc):
-        if self.dt:
-            _lib.load().ggpm_level_gate_dtype(self.prev)
-        return False
 
 
 def gru_level(x, W_z, b_z, W_r, U_r, b_u, W_h, b_h, pred: CSR, depth: int, I: int, H: int, gate_dtype=None) -> torch.Tensor:
@@ -996,7 +995,7 @@ class _GruSparse(torch.autograd.Function):
         _lib.check(lib.ggpm_gru_sparse_forward(E1, H, depth, _p(hp), _p(frozen), _p(X[0]), _p(X[1]), _p(X[2]), _p(Wz_h),
                                                W_z.stride(0), _p(U_r), U_r.stride(0), _p(b_u), _p(Wh_h), W_h.stride(0),
                                                _p(pred.rowptr), _p(pred.col), _p(Hs), _p(Qs), _p(Ss), _p(Gs), _p(Zs),
-                                               _p(Ms), _p(Rs), _p(wpack), int(save), _stream()), "gru_sparse_forward")
+                                               _p(Ms), _p(Rs), _p(wpack), int(save), None, _stream()), "gru_sparse_forward")
         out = Hs[depth] if save else Hs[depth & 1]
         if save:
             ctx.save_for_backward(x_sub, submess, W_z, W_r, U_r, W_h)
@@ -1032,7 +1031,7 @@ class _GruSparse(torch.autograd.Function):
                                                 _p(succ.rowptr), _p(succ.col), _p(Hs), _p(Qs), _p(Ss), _p(Gs), _p(Zs),
                                                 _p(Ms), _p(Rs), _p(dHD), _p(dHin), _p(dX[0]), _p(dX[1]), _p(dX[2]),
                                                 _p(dWz_h), dW_z.stride(0), _p(dU_r), H, _p(db_u), _p(dWh_h),
-                                                dW_h.stride(0), _p(work), work.numel() * 4, _stream()),
+                                                dW_h.stride(0), _p(work), work.numel() * 4, None, _stream()),
                    "gru_sparse_backward")
         ctx.stash = None
         dXs = dX.index_select(1, submess)             # [3, ms, Hp]: only the recomputed rows carry input gradients
@@ -1095,7 +1094,7 @@ class _LstmSparse(torch.autograd.Function):
                                                 _p(X[3]), _p(Wh[0]), W_i.stride(0), _p(Wh[1]), W_o.stride(0), _p(Wh[2]),
                                                 W_u.stride(0), _p(Wh[3]), W_f.stride(0), _p(pred.rowptr), _p(pred.col),
                                                 _p(Hs), _p(Cs), _p(Qs), _p(Ss), _p(Is), _p(Os), _p(Us), _p(Fs), _p(wpack),
-                                                int(save), _stream()), "lstm_sparse_forward")
+                                                int(save), None, _stream()), "lstm_sparse_forward")
         k = depth if save else depth & 1
         if save:
             ctx.save_for_backward(x_sub, submess, W_i, W_o, W_u, W_f)
@@ -1134,7 +1133,7 @@ class _LstmSparse(torch.autograd.Function):
                                                  _p(dCD), _p(dHin), _p(dCin), _p(dX[0]), _p(dX[1]), _p(dX[2]), _p(dX[3]),
                                                  _p(dWh[0]), dWs[0].stride(0), _p(dWh[1]), dWs[1].stride(0), _p(dWh[2]),
                                                  dWs[2].stride(0), _p(dWh[3]), dWs[3].stride(0), _p(work),
-                                                 work.numel() * 4, _stream()), "lstm_sparse_backward")
+                                                 work.numel() * 4, None, _stream()), "lstm_sparse_backward")
         ctx.stash = None
         dXs = dX.index_select(1, submess)
         ldx = _ld(x_sub)
@@ -1189,11 +1188,10 @@ class _LstmLevel(torch.autograd.Function):
             Qs = torch.empty(2, E1, Hp, **f32)
             Ss = Is = Os = Us = Fs = None
         Wh = [w[:, I:] for w in Ws]
-        with _gate_dtype(gate_dtype):
-            _lib.check(lib.ggpm_lstm_forward(E1, H, depth, _p(X[0]), _p(X[1]), _p(X[2]), _p(X[3]), _p(Wh[0]), W_i.stride(0),
-                                             _p(Wh[1]), W_o.stride(0), _p(Wh[2]), W_u.stride(0), _p(Wh[3]), W_f.stride(0),
-                                             _p(pred.rowptr), _p(pred.col), _p(Hs), _p(Cs), _p(Qs), _p(Ss), _p(Is), _p(Os),
-                                             _p(Us), _p(Fs), _p(wpack), int(save), _stream()), "lstm_forward")
+        _lib.check(lib.ggpm_lstm_forward(E1, H, depth, _p(X[0]), _p(X[1]), _p(X[2]), _p(X[3]), _p(Wh[0]), W_i.stride(0),
+                                         _p(Wh[1]), W_o.stride(0), _p(Wh[2]), W_u.stride(0), _p(Wh[3]), W_f.stride(0),
+                                         _p(pred.rowptr), _p(pred.col), _p(Hs), _p(Cs), _p(Qs), _p(Ss), _p(Is), _p(Os),
+                                         _p(Us), _p(Fs), _p(wpack), int(save), _gate_opts(gate_dtype), _stream()), "lstm_forward")
         k = depth if save else depth & 1
         if save:
             ctx.save_for_backward(x, W_i, W_o, W_u, W_f)
@@ -1222,14 +1220,14 @@ class _LstmLevel(torch.autograd.Function):
         wb = int(lib.ggpm_lstm_backward_workspace_bytes(E1, H, depth))
         work = torch.empty((wb + 3) // 4, **f32)
         use_side = side_stream_enabled() and can_publish(*ctx.params)
-        with _gate_dtype(ctx.gate_dtype):
-            _lib.check(lib.ggpm_lstm_backward(E1, H, depth, _p(Xf), _p(Wh[0]), W_i.stride(0), _p(Wh[1]), W_o.stride(0),
-                                              _p(Wh[2]), W_u.stride(0), _p(Wh[3]), W_f.stride(0), _p(pred.rowptr),
-                                              _p(pred.col), _p(succ.rowptr), _p(succ.col), _p(Hs), _p(Cs), _p(Qs), _p(Ss),
-                                              _p(Is), _p(Os), _p(Us), _p(Fs), _p(dHD), _p(dX[0]), _p(dX[1]), _p(dX[2]),
-                                              _p(dX[3]), _p(dWh[0]), dWs[0].stride(0), _p(dWh[1]), dWs[1].stride(0),
-                                              _p(dWh[2]), dWs[2].stride(0), _p(dWh[3]), dWs[3].stride(0), _p(work),
-                                              work.numel() * 4, 0 if use_side else 1, _stream()), "lstm_backward")
+        _lib.check(lib.ggpm_lstm_backward(E1, H, depth, _p(Xf), _p(Wh[0]), W_i.stride(0), _p(Wh[1]), W_o.stride(0),
+                                          _p(Wh[2]), W_u.stride(0), _p(Wh[3]), W_f.stride(0), _p(pred.rowptr),
+                                          _p(pred.col), _p(succ.rowptr), _p(succ.col), _p(Hs), _p(Cs), _p(Qs), _p(Ss),
+                                          _p(Is), _p(Os), _p(Us), _p(Fs), _p(dHD), _p(dX[0]), _p(dX[1]), _p(dX[2]),
+                                          _p(dX[3]), _p(dWh[0]), dWs[0].stride(0), _p(dWh[1]), dWs[1].stride(0),
+                                          _p(dWh[2]), dWs[2].stride(0), _p(dWh[3]), dWs[3].stride(0), _p(work),
+                                          work.numel() * 4, 0 if use_side else 1, _gate_opts(ctx.gate_dtype), _stream()),
+                   "lstm_backward")
         ctx.stash = None
         ldx = _ld(x)
         dx = None
@@ -1241,11 +1239,10 @@ class _LstmLevel(torch.autograd.Function):
 
         def weight_grads():
             if use_side:
-                with _gate_dtype(ctx.gate_dtype):
-                    _lib.check(lib.ggpm_lstm_weight_grads(E1, H, depth, _p(Hs), _p(Ss), _p(work), work.numel() * 4,
-                                                          _p(dWh[0]), dWs[0].stride(0), _p(dWh[1]), dWs[1].stride(0),
-                                                          _p(dWh[2]), dWs[2].stride(0), _p(dWh[3]), dWs[3].stride(0),
-                                                          _stream()), "lstm_weight_grads")
+                _lib.check(lib.ggpm_lstm_weight_grads(E1, H, depth, _p(Hs), _p(Ss), _p(work), work.numel() * 4,
+                                                      _p(dWh[0]), dWs[0].stride(0), _p(dWh[1]), dWs[1].stride(0),
+                                                      _p(dWh[2]), dWs[2].stride(0), _p(dWh[3]), dWs[3].stride(0),
+                                                      _gate_opts(ctx.gate_dtype), _stream()), "lstm_weight_grads")
             out = []
             for k in range(4):
                 gemm(1, 0, H, I, E1, dX[k], Hp, x, ldx, dWs[k][:, :I], dWs[k].stride(0), I, splitk=True)

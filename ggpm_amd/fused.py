@@ -39,7 +39,7 @@ class EncDims(ctypes.Structure):
                                             "E1g", "Kg_a", "Kg_b", "N1t", "E1t", "Kt_a", "Kt_b", "Kt_c", "B", "rnn_type",
                                             "tree_chain")] + \
                [("dropout", ctypes.c_float), ("seed_lo", ctypes.c_uint), ("seed_hi", ctypes.c_uint),
-                ("gate_dtype", ctypes.c_int)]
+                ("gate_dtype", ctypes.c_int), ("prefer_narrow", ctypes.c_int)]
 
 GATE_DTYPES = F_.GATE_DTYPES      # "f32" (default: split operands where they pay) | "bf16" | "f32_mfma" | "f32_split" (A/B forms)
 
@@ -77,7 +77,7 @@ def _side_ptr(device):
 
 
 # True while the caller runs the encoder beside another chain of launches (property_vae: the decoder's atom level): the
-# level kernels then take half as many workgroups (ggpm_level_prefer_narrow), forwards and backwards.
+# level kernels then take half as many workgroups (ggpm_enc_dims.prefer_narrow), forwards and backwards.
 NARROW = [False]
 
 
@@ -101,17 +101,11 @@ class _HierEncoder(torch.autograd.Function):
             roots.record_stream(side)
         P = F_._p
         beside = bool(NARROW[0])
-        narrow = beside and _dev.ENC_NARROW in (True, "fwd")
-        if narrow:
-            lib.ggpm_level_prefer_narrow(1)
-        try:
-            _lib.check(lib.ggpm_encoder_forward(ctypes.byref(dims), _ptr_array(params), P(tfnode), P(tfmess), P(tagraph),
-                                                P(tbgraph), P(tcgraph), P(gfnode), P(gfmess), P(gagraph), P(gbgraph),
-                                                P(roots), P(saved), saved_bytes, P(hroot), P(hnode), P(hinter), P(hatom),
-                                                F_._stream(), side_p), "encoder_forward")
-        finally:
-            if narrow:
-                lib.ggpm_level_prefer_narrow(0)
+        dims.prefer_narrow = int(beside and _dev.ENC_NARROW in (True, "fwd"))
+        _lib.check(lib.ggpm_encoder_forward(ctypes.byref(dims), _ptr_array(params), P(tfnode), P(tfmess), P(tagraph),
+                                            P(tbgraph), P(tcgraph), P(gfnode), P(gfmess), P(gagraph), P(gbgraph),
+                                            P(roots), P(saved), saved_bytes, P(hroot), P(hnode), P(hinter), P(hatom),
+                                            F_._stream(), side_p), "encoder_forward")
         if any(ctx.needs_input_grad):
             # everything the backward reads goes through save_for_backward: autograd then owns the arena and the
             # outputs (no ctx -> output -> grad_fn -> ctx cycle that would keep a 128 MiB-rounded arena alive after a
@@ -158,18 +152,13 @@ class _HierEncoder(torch.autograd.Function):
         douts = [None if g is None else g.contiguous() for g in (d_hroot, d_hnode, d_hinter, d_hatom)]
         P = F_._p
         parr, garr = _ptr_array(params), _ptr_array(grads)
+        dims.prefer_narrow = int(ctx.narrow)
 
         def run(phase):
-            if getattr(ctx, "narrow", False):
-                lib.ggpm_level_prefer_narrow(1)
-            try:
-                _lib.check(lib.ggpm_encoder_backward(ctypes.byref(dims), parr, garr, P(roots), P(saved), saved.numel(),
-                                                     P(hroot), P(hnode), P(hinter), P(hatom), P(douts[0]), P(douts[1]),
-                                                     P(douts[2]), P(douts[3]), P(work), work_bytes, phase, F_._stream(),
-                                                     side_p), "encoder_backward")
-            finally:
-                if getattr(ctx, "narrow", False):
-                    lib.ggpm_level_prefer_narrow(0)
+            _lib.check(lib.ggpm_encoder_backward(ctypes.byref(dims), parr, garr, P(roots), P(saved), saved.numel(),
+                                                 P(hroot), P(hnode), P(hinter), P(hatom), P(douts[0]), P(douts[1]),
+                                                 P(douts[2]), P(douts[3]), P(work), work_bytes, phase, F_._stream(),
+                                                 side_p), "encoder_backward")
 
         if sink is not None and side is not None and sink.wants_early_bucket():
             run(1)                      # everything but the atom level; its gradients complete on the second stream

@@ -108,14 +108,14 @@ class _TreeLevel(torch.autograd.Function):
             _lib.check(lib.ggpm_lstm_sparse_forward(
                 Etot, H, depth, P(hp), P(cp), P(frozen), P(X[0]), P(X[1]), P(X[2]), P(X[3]), P(Wh[0]), Wi.stride(0), P(Wh[1]),
                 Wog.stride(0), P(Wh[2]), Wu.stride(0), P(Wh[3]), Wf.stride(0), P(pred.rowptr), P(pred.col), P(Hs), P(Cs), P(Qs),
-                P(St[0]), P(St[1]), P(St[2]), P(St[3]), P(St[4]), P(wpack), int(save), s), "lstm_sparse_forward")
+                P(St[0]), P(St[1]), P(St[2]), P(St[3]), P(St[4]), P(wpack), int(save), None, s), "lstm_sparse_forward")
         else:
             Cs = None
             wpack = torch.empty(int(lib.ggpm_gru_pack_floats(H)), **f32)
             _lib.check(lib.ggpm_gru_sparse_forward(
                 Etot, H, depth, P(hp), P(frozen), P(X[0]), P(X[1]), P(X[2]), P(Wz[:, I:]), Wz.stride(0), P(Ur), Ur.stride(0),
                 P(bu), P(Wh[:, I:]), Wh.stride(0), P(pred.rowptr), P(pred.col), P(Hs), P(Qs), P(St[0]), P(St[1]), P(St[2]),
-                P(St[3]), P(St[4]), P(wpack), int(save), s), "gru_sparse_forward")
+                P(St[3]), P(St[4]), P(wpack), int(save), None, s), "gru_sparse_forward")
         hid = Hs[depth]
         # 6. read-out of every visit
         nei = torch.empty(n_inst, Hp, **f32)
@@ -192,7 +192,7 @@ class _TreeLevel(torch.autograd.Function):
                 P(Wh[3]), Wf.stride(0), P(pred.rowptr), P(pred.col), P(succ.rowptr), P(succ.col), P(Hs), P(Cs), P(Qs), P(St[0]),
                 P(St[1]), P(St[2]), P(St[3]), P(St[4]), P(dHD), P(dCD), P(dHin), P(dCin), P(dX[0]), P(dX[1]), P(dX[2]), P(dX[3]),
                 P(dWh[0]), dWs[0].stride(0), P(dWh[1]), dWs[1].stride(0), P(dWh[2]), dWs[2].stride(0), P(dWh[3]),
-                dWs[3].stride(0), P(work), work.numel() * 4, s), "lstm_sparse_backward")
+                dWs[3].stride(0), P(work), work.numel() * 4, None, s), "lstm_sparse_backward")
             xw = [(Ws[k], dWs[k]) for k in range(4)]
         else:
             Wz, bz, Wr, Ur, bu, Wh, bh = rp
@@ -205,7 +205,7 @@ class _TreeLevel(torch.autograd.Function):
                 Etot, H, depth, P(frozen), P(Xg), P(Wz[:, I:]), Wz.stride(0), P(Ur), Ur.stride(0), P(Wh[:, I:]), Wh.stride(0),
                 P(pred.rowptr), P(pred.col), P(succ.rowptr), P(succ.col), P(Hs), P(Qs), P(St[0]), P(St[1]), P(St[2]), P(St[3]),
                 P(St[4]), P(dHD), P(dHin), P(dX[0]), P(dX[1]), P(dX[2]), P(dWz[:, I:]), dWz.stride(0), P(dUr), H, P(dbu),
-                P(dWh_[:, I:]), dWh_.stride(0), P(work), work.numel() * 4, s), "gru_sparse_backward")
+                P(dWh_[:, I:]), dWh_.stride(0), P(work), work.numel() * 4, None, s), "gru_sparse_backward")
             xw = [(Wz, dWz), (Wr, dWr), (Wh, dWh_)]
         dXs = [dX[k][1:E1] for k in range(G)]          # the rows of the real messages: contiguous
         # input halves of the gate weights, gate biases

@@ -179,28 +179,12 @@ int ggpm_embed_graph(const int64_t* fnode, int N1, const int64_t* fmess, int E1,
                      int bond_types, int max_pos, float* hnode, int ld_n, float* hmess, int ld_m,
                      ggpm_stream_t stream);
 
-/* One-shot hint for the NEXT dense ggpm_gru_backward / ggpm_lstm_backward of the calling thread: do not accumulate dXz / dXh per depth (their
- * outputs are then undefined).  The per-depth gate gradients are stashed anyway (for the weight-gradient contractions), so
- * a caller that does not need the sums on the critical path -- the atom level has no input gradient: its inputs are one-hot
- * constants, ggpm/encoder.py:119-126 -- forms dXz = sum_t DZP_t, dXh = sum_t DMP_t afterwards with ggpm_sum_slots over
- * the slots ggpm_gru_backward_stashes names, e.g. on a second stream: 13 MB less HBM traffic and four memory operations
- * fewer per element in every depth launch.  ggpm_sum_slots: out[i] = sum_t src[t * slot_floats + i], fixed order. */
-void ggpm_backward_skip_x_sums(int yes);
+/* Where a dense backward (e.g. one called with ggpm_level_opts.skip_x_sums) left its per-depth gate gradients inside `work`
+ * (slot t-1 of each = backward step t).  ggpm_sum_slots sums slots in fixed order: out[i] = sum_t src[t * slot_floats + i]. */
 int ggpm_gru_backward_stashes(float* work, int E1, int H, int depth, float** DMP, float** DZP);
 /* ... and for ggpm_lstm_backward: dXi, dXo, dXu = sums of the DI / DO / DU stash slots (dXf still accumulates per depth) */
 int ggpm_lstm_backward_stashes(float* work, int E1, int H, int depth, float** DI, float** DO, float** DU);
 int ggpm_sum_slots(const float* src, int slots, size_t slot_floats, float* out, ggpm_stream_t stream);
-/* Gate-product dtype of the level calls (ggpm_gru_/ggpm_lstm_ forward, backward, weight_grads) issued by the CALLING
- * THREAD from now on: 0 = fp32 operands (default, the 1e-4 parity mode: on dense levels large enough for one column group
- * the H x H products run at fp32 accuracy on the bf16 matrix pipe, every operand split exactly into three bf16 values
- * and six of the nine partial products kept; on v_mfma_f32_16x16x4_f32 otherwise),
- * 1 = bf16 operands with fp32 accumulate for the hidden x hidden products of the depth loops and the tall
- * weight-gradient contractions (BASELINE configs[4]; the reference's cells are ggpm/rnn.py:27-36, 88-91), 2 = fp32 on
- * v_mfma_f32_16x16x4_f32 only, 3 = fp32 on split operands wherever their images fit the LDS (0 chooses between 2 and 3
- * per level: split operands for dense levels of one column group).  Returns the previous value; any other argument only
- * queries.  The
- * whole-encoder drivers set it from ggpm_enc_dims.gate_dtype for the duration of their call. */
-int ggpm_level_gate_dtype(int dtype);
 /* 1 when a DENSE TRAINING level (GRU or LSTM) of E1 message rows (pad row included) and hidden size H keeps the arrays of
  * its depth loop in bf16 under gate dtype 1 (BASELINE configs[4]: "bf16 storage"): the state h and the per-message product
  * q, the stashes S / G / Z / M (LSTM: S / I / O / U), the backward's dS / dG and its DQ / DZP / DMP (DQ / DI / DO / DU)
@@ -210,6 +194,77 @@ int ggpm_level_gate_dtype(int dtype);
  * bf16 tall kernel, which then reads the stashes as they are.  Kept fp32: gate inputs X and their gradients, R / F, the
  * LSTM cell state c and dFC, every weight and weight gradient.  oracle/ref_encoder.py restates the roundings as gate_dtype "bf16s" (ggpm/rnn.py:25-50). */
 int ggpm_level_bf16_storage(int E1, int H);
+/* ------------------------------------------------------------------ level-call options
+ * Options of ONE call of the GRU / LSTM level entry points below (forward, backward, weight_grads, sparse_forward,
+ * sparse_backward): each takes `const ggpm_level_opts* opts` before its stream and reads it during that call only.
+ * NULL (or a zero-initialised struct) = all defaults.  Fields a call does not use are ignored. */
+typedef struct ggpm_level_opts {
+    /* Gate-product dtype: 0 = fp32 operands (default, the 1e-4 parity mode: on dense levels large enough for one column
+     * group the H x H products run at fp32 accuracy on the bf16 matrix pipe, every operand split exactly into three bf16
+     * values and six of the nine partial products kept; on v_mfma_f32_16x16x4_f32 otherwise), 1 = bf16 operands with fp32
+     * accumulate for the hidden x hidden products of the depth loops and the tall weight-gradient contractions (BASELINE
+     * configs[4]; the reference's cells are ggpm/rnn.py:27-36, 88-91), 2 = fp32 on v_mfma_f32_16x16x4_f32 only, 3 = fp32
+     * on split operands wherever their images fit the LDS (0 chooses between 2 and 3 per level: split operands for dense
+     * levels of one column group).  A level's forward, backward and weight_grads must agree on it. */
+    int gate_dtype;
+    /* Nonzero: a dense fp32 call uses two row tiles per workgroup whatever the level's size, i.e. half as many workgroups
+     * (the same products in the same order per row; results agree with the default form to rounding, 5e-6 norm-wise after
+     * 20 depth steps -- the two instantiations contract the gate expressions differently).  For a level that runs BESIDE a
+     * latency-bound chain on another stream -- the encoder next to the decoder's atom level in the full VAE step
+     * (ggpm/property_vae.py:47-58 runs them one after the other) -- this leaves the chain's launches free CUs. */
+    int prefer_narrow;
+    /* Nonzero: the call skips packing its gate weights: `wpack` (forward) resp. the head of `work` (backward) still holds
+     * the fragments an earlier call with the SAME weights and the same buffer left there -- the decode steps share one set
+     * of weights. */
+    int weights_packed;
+    /* Sparse backward, non-NULL defer_stash[0]: the call writes its gate-gradient stashes to caller memory and leaves
+     * dW*_h / dUr / dbu untouched (see ggpm_*_weight_grads_stacked).  GRU: [0] = DMP, [1] = DZP ([depth][E1][Hp] each,
+     * pairing with the forward's Gs / Ss), [2] = DQ ([depth][E1][Hp], slot t pairs with Hs slot t; give the block depth+1
+     * slots, the last one zero, so that it lines up with Hs), [3] unused.  LSTM: [0..2] = DI, DO, DU (pair with Ss),
+     * [3] = DQ (pairs with Hs, as above). */
+    float* defer_stash[4];
+    /* Start state / incoming-state gradient of a sparse call through an index (the decode steps keep every step's rows in
+     * stacked blocks; a step's frozen rows are the final states of rows of earlier blocks, ggpm/encoder.py:165-179 reads
+     * them out of the level-wide `hmess` instead).  Rows are [Hp] floats.
+     * gather_*: with gather_h and gather_idx non-NULL (LSTM: gather_c too) a sparse forward takes the start state of row r
+     * from gather_h[gather_idx[r]] (gather_c likewise; zero where the index is < 0) and writes it to slot 0 of Hs (Cs)
+     * itself, inside its first launch; `h_in` / `c_in` are not read. */
+    const float* gather_h;
+    const float* gather_c;
+    const int32_t* gather_idx;
+    /* scatter_*: with scatter_h and scatter_idx non-NULL (LSTM: scatter_c too) a sparse backward ADDS the gradient of the
+     * incoming state of row r to scatter_h[scatter_idx[r]] (scatter_c likewise; indices unique, rows with index < 0
+     * dropped) inside its last launch; dHin / dCin are not written. */
+    float* scatter_h;
+    float* scatter_c;
+    const int32_t* scatter_idx;
+    /* Dense backward, nonzero: do not accumulate the gate-input gradients dXz / dXh (LSTM: dXi, dXo, dXu) per depth (those
+     * outputs are then undefined).  The per-depth gate gradients are stashed anyway (for the weight-gradient
+     * contractions), so a caller that does not need the sums on the critical path -- the atom level has no input gradient:
+     * its inputs are one-hot constants, ggpm/encoder.py:119-126 -- forms them afterwards with ggpm_sum_slots over the slots
+     * ggpm_gru_backward_stashes / ggpm_lstm_backward_stashes name, e.g. on a second stream: 13 MB less HBM traffic and four
+     * memory operations fewer per element in every depth launch. */
+    int skip_x_sums;
+    /* Driver-internal shortcuts (the whole-encoder and tree-level drivers set them; exact only under the conditions
+     * stated, which the caller vouches for):
+     * run_depth -- dense training forward: issue only steps 1 .. run_depth of `depth` (0 / >= depth: all of them).  Message
+     *   passing on a tree reaches a fixed point after as many steps as the longest dependency chain; the caller then
+     *   replicates the last computed slot of every stash array.
+     * lo -- dense backward / weight_grads: stop at step `lo` (<= 1: all steps).  The same acyclic structure makes the
+     *   Jacobian of a tree level's recurrence nilpotent: with a longest dependency chain of C messages, d(h^{D-k}) is
+     *   exactly zero for k >= C, so the backward of such a level only has to run its steps t = D .. lo with
+     *   lo = max(1, D - C + 1); every skipped launch would compute exact zeros and every skipped stash slot would add exact
+     *   zeros to the weight-gradient contractions.  A backward and its separate weight_grads call pass the same value.
+     * skip_bias_u -- GRU weight_grads: leave db_u alone; the caller forms it with its own column sum of the same dq stash
+     *   rows on another stream.
+     * skip_sparse_wgrads -- sparse backward: leave the hidden-half weight gradients to a later sparse weight-gradient call
+     *   with the same arguments (the same launches, on whatever stream that call names). */
+    int run_depth;
+    int lo;
+    int skip_bias_u;
+    int skip_sparse_wgrads;
+} ggpm_level_opts;
+
 /* ------------------------------------------------------------------ GRU message function
  * GRU.forward (ggpm/rnn.py:41-50) with GRU.GRU (ggpm/rnn.py:25-39) restated over CSR predecessors with
  * the depth-invariant input halves hoisted:  Xz = x W_z[:, :I]^T + b_z, Xr = x W_r^T, Xh = x W_h[:, :I]^T + b_h
@@ -228,7 +283,7 @@ int ggpm_gru_forward(int E1, int H, int depth, const float* Xz, const float* Xr,
                      const float* Wz_h, int ld_wz, const float* Ur, int ld_ur, const float* bu,
                      const float* Wh_h, int ld_wh, const int32_t* pred_rowptr, const int32_t* pred_col,
                      float* Hs, float* Qs, float* Ss, float* Gs, float* Zs, float* Ms, float* Rs,
-                     float* wpack, int save_for_backward, ggpm_stream_t stream);
+                     float* wpack, int save_for_backward, const ggpm_level_opts* opts, ggpm_stream_t stream);
 /* Backward of the above (replaces autograd's replay of ggpm/rnn.py:41-50): given dHD = dL/dh_D it
  * overwrites dXz/dXr/dXh [E1][Hp] and the weight gradients (written as [H,H] blocks with the given
  * leading dimension so they can land inside the full W_z/W_h gradient tensors), dbu[H].
@@ -241,12 +296,12 @@ int ggpm_gru_backward(int E1, int H, int depth, const float* Xr, const float* Wz
                       const float* Gs, const float* Zs, const float* Ms, const float* Rs, const float* dHD, float* dXz,
                       float* dXr, float* dXh, float* dWz_h, int ld_dwz, float* dUr, int ld_dur,
                       float* dbu, float* dWh_h, int ld_dwh, float* work, size_t work_bytes,
-                      int weight_grads, ggpm_stream_t stream);
+                      int weight_grads, const ggpm_level_opts* opts, ggpm_stream_t stream);
 /* The weight-gradient tail of ggpm_gru_backward (called with weight_grads = 0) as its own entry point, so the
  * host may enqueue it on a second stream beside the next level's depth loop. Same `work` buffer. */
 int ggpm_gru_weight_grads(int E1, int H, int depth, const float* Hs, const float* Ss, const float* Gs, float* work,
                           size_t work_bytes, float* dWz_h, int ld_dwz, float* dUr, int ld_dur, float* dbu,
-                          float* dWh_h, int ld_dwh, ggpm_stream_t stream);
+                          float* dWh_h, int ld_dwh, const ggpm_level_opts* opts, ggpm_stream_t stream);
 
 /* GRU.sparse_forward (ggpm/rnn.py:52-59) -- the incremental form the decoder uses (IncMPNEncoder, ggpm/encoder.py:160-179):
  * rows with frozen[row] != 0 keep their state for the whole loop, the other rows (the `submess` subset) start from 0 and
@@ -257,14 +312,15 @@ int ggpm_gru_sparse_forward(int E1, int H, int depth, const float* h_in, const u
                             const float* Xr, const float* Xh, const float* Wz_h, int ld_wz, const float* Ur, int ld_ur,
                             const float* bu, const float* Wh_h, int ld_wh, const int32_t* pred_rowptr,
                             const int32_t* pred_col, float* Hs, float* Qs, float* Ss, float* Gs, float* Zs, float* Ms,
-                            float* Rs, float* wpack, int save_for_backward, ggpm_stream_t stream);
+                            float* Rs, float* wpack, int save_for_backward, const ggpm_level_opts* opts, ggpm_stream_t stream);
 int ggpm_gru_sparse_backward(int E1, int H, int depth, const unsigned char* frozen, const float* Xr, const float* Wz_h,
                              int ld_wz, const float* Ur, int ld_ur, const float* Wh_h, int ld_wh,
                              const int32_t* pred_rowptr, const int32_t* pred_col, const int32_t* succ_rowptr,
                              const int32_t* succ_col, const float* Hs, const float* Qs, const float* Ss, const float* Gs,
                              const float* Zs, const float* Ms, const float* Rs, const float* dHD, float* dHin,
                              float* dXz, float* dXr, float* dXh, float* dWz_h, int ld_dwz, float* dUr, int ld_dur,
-                             float* dbu, float* dWh_h, int ld_dwh, float* work, size_t work_bytes, ggpm_stream_t stream);
+                             float* dbu, float* dWh_h, int ld_dwh, float* work, size_t work_bytes,
+                             const ggpm_level_opts* opts, ggpm_stream_t stream);
 
 /* ------------------------------------------------------------------ LSTM message function
  * LSTM.forward (ggpm/rnn.py:96-108) with LSTM.LSTM (ggpm/rnn.py:85-94), same restatement:
@@ -280,7 +336,7 @@ int ggpm_lstm_forward(int E1, int H, int depth, const float* Xi, const float* Xo
                       const float* Wu_h, int ld_wu, const float* Wf_h, int ld_wf,
                       const int32_t* pred_rowptr, const int32_t* pred_col, float* Hs, float* Cs,
                       float* Qs, float* Ss, float* Is, float* Os, float* Us, float* Fs, float* wpack,
-                      int save_for_backward, ggpm_stream_t stream);
+                      int save_for_backward, const ggpm_level_opts* opts, ggpm_stream_t stream);
 size_t ggpm_lstm_backward_workspace_bytes(int E1, int H, int depth);
 int ggpm_lstm_backward(int E1, int H, int depth, const float* Xf, const float* Wi_h, int ld_wi,
                        const float* Wo_h, int ld_wo, const float* Wu_h, int ld_wu, const float* Wf_h,
@@ -290,10 +346,10 @@ int ggpm_lstm_backward(int E1, int H, int depth, const float* Xf, const float* W
                        const float* Os, const float* Us, const float* Fs, const float* dHD, float* dXi,
                        float* dXo, float* dXu, float* dXf, float* dWi_h, int ld_dwi, float* dWo_h, int ld_dwo,
                        float* dWu_h, int ld_dwu, float* dWf_h, int ld_dwf, float* work,
-                       size_t work_bytes, int weight_grads, ggpm_stream_t stream);
+                       size_t work_bytes, int weight_grads, const ggpm_level_opts* opts, ggpm_stream_t stream);
 int ggpm_lstm_weight_grads(int E1, int H, int depth, const float* Hs, const float* Ss, float* work, size_t work_bytes,
                            float* dWi_h, int ld_dwi, float* dWo_h, int ld_dwo, float* dWu_h, int ld_dwu,
-                           float* dWf_h, int ld_dwf, ggpm_stream_t stream);
+                           float* dWf_h, int ld_dwf, const ggpm_level_opts* opts, ggpm_stream_t stream);
 
 /* LSTM.sparse_forward (ggpm/rnn.py:110-121): as ggpm_gru_sparse_forward, with the cell state carried too.  The backward
  * takes dL/dh_D and dL/dc_D (the decoder keeps both) and returns dHin / dCin. */
@@ -302,7 +358,7 @@ int ggpm_lstm_sparse_forward(int E1, int H, int depth, const float* h_in, const 
                              int ld_wi, const float* Wo_h, int ld_wo, const float* Wu_h, int ld_wu, const float* Wf_h,
                              int ld_wf, const int32_t* pred_rowptr, const int32_t* pred_col, float* Hs, float* Cs,
                              float* Qs, float* Ss, float* Is, float* Os, float* Us, float* Fs, float* wpack,
-                             int save_for_backward, ggpm_stream_t stream);
+                             int save_for_backward, const ggpm_level_opts* opts, ggpm_stream_t stream);
 int ggpm_lstm_sparse_backward(int E1, int H, int depth, const unsigned char* frozen, const float* Xf, const float* Wi_h,
                               int ld_wi, const float* Wo_h, int ld_wo, const float* Wu_h, int ld_wu, const float* Wf_h,
                               int ld_wf, const int32_t* pred_rowptr, const int32_t* pred_col,
@@ -311,43 +367,15 @@ int ggpm_lstm_sparse_backward(int E1, int H, int depth, const unsigned char* fro
                               const float* Fs, const float* dHD, const float* dCD, float* dHin, float* dCin, float* dXi,
                               float* dXo, float* dXu, float* dXf, float* dWi_h, int ld_dwi, float* dWo_h, int ld_dwo,
                               float* dWu_h, int ld_dwu, float* dWf_h, int ld_dwf, float* work, size_t work_bytes,
-                              ggpm_stream_t stream);
+                              const ggpm_level_opts* opts, ggpm_stream_t stream);
 
 /* Deferred hidden-half weight gradients for a SEQUENCE of sparse backward calls (the decode steps of one batch,
  * ggpm/decoder.py:201-222 -> ggpm/encoder.py:165-179 once per step; ggpm_amd/atom_decode.py): every step contracts a few
  * hundred rows against the same four H x H matrices, so instead of three or four small contractions per step the
- * gate-gradient stashes of all steps are kept, stacked row-wise, and contracted ONCE.
- *   ggpm_backward_defer_stash(s0, s1, s2, s3): the NEXT ggpm_gru_sparse_backward / ggpm_lstm_sparse_backward call of this
- *   thread writes its stashes to caller memory and leaves dW*_h / dUr / dbu untouched.  GRU: s0 = DMP, s1 = DZP
- *   ([depth][E1][Hp] each, pairing with the forward's Gs / Ss), s2 = DQ ([depth][E1][Hp], slot t pairs with Hs slot t; give
- *   the block depth+1 slots, the last one zero, so that it lines up with Hs), s3 unused.  LSTM: s0..s2 = DI, DO, DU (pair with
- *   Ss), s3 = DQ (pairs with Hs, as above).  One call consumes the setting.
+ * gate-gradient stashes of all steps are kept, stacked row-wise (ggpm_level_opts.defer_stash), and contracted ONCE.
  *   ggpm_*_weight_grads_stacked: rows = total stash rows (sum over the calls of depth*E1), rows_q = total rows of the
  *   DQ / Hs stacks (sum of (depth+1)*E1); every buffer holds the calls' blocks in the same order.  Outputs are
- *   overwritten.  work: ggpm_weight_grads_stacked_workspace_bytes(H, max(rows, rows_q)).
- *   ggpm_weights_packed(1): the NEXT forward / backward / sparse call of this thread skips packing its gate weights: `wpack`
- *   (forward) resp. the head of `work` (backward) still holds the fragments an earlier call with the SAME weights and
- *   the same buffer left there -- the decode steps share one set of weights.  One call consumes the setting. */
-void ggpm_weights_packed(int yes);
-void ggpm_backward_defer_stash(float* s0, float* s1, float* s2, float* s3);
-/* Start state / incoming-state gradient of a sparse call through an index (the decode steps keep every step's rows in
- * stacked blocks; a step's frozen rows are the final states of rows of earlier blocks, ggpm/encoder.py:165-179 reads them
- * out of the level-wide `hmess` instead):
- *   ggpm_forward_gather_state(src_h, src_c, idx): the NEXT ggpm_gru_sparse_forward / ggpm_lstm_sparse_forward of this thread
- *   takes the start state of row r from src_h[idx[r]] (src_c likewise, LSTM; zero where idx[r] < 0) and writes it to slot 0
- *   of Hs (Cs) itself, inside its first launch; `h_in` / `c_in` are not read.
- *   ggpm_backward_scatter_state(dst_h, dst_c, idx): the NEXT ggpm_*_sparse_backward of this thread ADDS the gradient of the
- *   incoming state of row r to dst_h[idx[r]] (dst_c likewise; idx unique, rows with idx[r] < 0 dropped) inside its last
- *   launch; dHin / dCin are not written.  Rows are [Hp] floats.  One call consumes the setting. */
-/* ggpm_level_prefer_narrow(1): until switched off again, the dense fp32 level calls of this thread (GRU and LSTM) use two row tiles per
- * workgroup whatever the level's size, i.e. half as many workgroups (the same products in the same order per row; results
- * agree with the default form to rounding, 5e-6 norm-wise after 20 depth steps -- the two instantiations contract the gate
- * expressions differently).  For a
- * level that runs BESIDE a latency-bound chain on another stream -- the encoder next to the decoder's atom level in the
- * full VAE step (ggpm/property_vae.py:47-58 runs them one after the other) -- this leaves the chain's launches free CUs. */
-void ggpm_level_prefer_narrow(int yes);
-void ggpm_forward_gather_state(const float* src_h, const float* src_c, const int32_t* idx);
-void ggpm_backward_scatter_state(float* dst_h, float* dst_c, const int32_t* idx);
+ *   overwritten.  work: ggpm_weight_grads_stacked_workspace_bytes(H, max(rows, rows_q)). */
 size_t ggpm_weight_grads_stacked_workspace_bytes(int H, int rows);
 int ggpm_gru_weight_grads_stacked(int rows, int rows_q, int H, const float* DMP, const float* Gs, const float* DZP,
                                   const float* Ss, const float* DQ, const float* Hs, float* dWz_h, int ld_dwz, float* dUr,
@@ -519,11 +547,12 @@ typedef struct ggpm_enc_dims {
                                             (ggpm/rnn.py:41-50 iterates a fixed depth regardless). */
     float dropout;                       /* drop probability of the training forward (0: none / eval) */
     unsigned int seed_lo, seed_hi;       /* mask stream of this forward/backward pair */
-    int gate_dtype;                      /* as ggpm_level_gate_dtype.  0: fp32 gate products (the 1e-4 parity configurations);
+    int gate_dtype;                      /* as ggpm_level_opts.gate_dtype.  0: fp32 gate products (the 1e-4 parity configurations);
                                             2: fp32 on v_mfma_f32_16x16x4_f32 only;
                                             1: bf16 operands, fp32 accumulate (v_mfma_f32_16x16x32_bf16) for the H x H gate
                                             products of the depth loops -- BASELINE configs[4].  State, stashes, gate math,
                                             input projections and weight-gradient contractions stay fp32. */
+    int prefer_narrow;                   /* as ggpm_level_opts.prefer_narrow, for every level call of this driver call */
 } ggpm_enc_dims;
 size_t ggpm_encoder_saved_bytes(const ggpm_enc_dims* dims);
 size_t ggpm_encoder_work_bytes(const ggpm_enc_dims* dims);

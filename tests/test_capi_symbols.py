@@ -32,8 +32,8 @@ def test_library_builds_and_exports_every_symbol():
 
 
 def test_ctypes_structs_match_the_header_layout(tmp_path):
-    """The structs that cross the C ABI (ggpm_enc_dims, ggpm_decode_steps, ggpm_sched_in): a C program compiled against
-    include/ggpm_hip.h prints sizeof and every field offset; the ctypes mirrors must agree."""
+    """The structs that cross the C ABI (ggpm_enc_dims, ggpm_level_opts, ggpm_decode_steps, ggpm_sched_in, ...): a C
+    program compiled against include/ggpm_hip.h prints sizeof and every field offset; the ctypes mirrors must agree."""
     import ctypes
     import subprocess
     import pytest
@@ -44,10 +44,11 @@ def test_ctypes_structs_match_the_header_layout(tmp_path):
         # GPU process is what is refused -- but a fork of a process with live HIP state buys nothing here)
         pytest.skip("the ABI probe runs gcc in child processes: kept to processes that have not initialised the GPU")
     from ggpm_amd.atom_decode import DecodeSteps
+    from ggpm_amd.functional import LevelOpts
     from ggpm_amd.fused import EncDims
     from ggpm_amd.schedule_native import SchedIn
     from ggpm_amd.tree_decode import TreeLevelC, TreeLevelGrads, TreeLevelViews
-    structs = {"ggpm_enc_dims": EncDims, "ggpm_decode_steps": DecodeSteps, "ggpm_sched_in": SchedIn,
+    structs = {"ggpm_enc_dims": EncDims, "ggpm_level_opts": LevelOpts, "ggpm_decode_steps": DecodeSteps, "ggpm_sched_in": SchedIn,
                "ggpm_tree_level": TreeLevelC, "ggpm_tree_level_views": TreeLevelViews, "ggpm_tree_level_grads": TreeLevelGrads}
     lines = []
     for cname, cls in structs.items():
