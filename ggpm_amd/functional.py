@@ -17,6 +17,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import _dev, _lib
+from .parallel import grad_view
 
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3
 
@@ -581,6 +582,13 @@ def hand_to(g: torch.Tensor, main: torch.cuda.Stream) -> None:
         g.record_stream(main)
 
 
+def second_backward(node: str) -> RuntimeError:
+    """The error of a node whose first backward has released the state it saved (to free it early): a second backward
+    through the same graph -- loss.backward(retain_graph=True), then backward again -- is not supported."""
+    return RuntimeError("%s: a retained graph is not supported: backward through the same graph a second time "
+                        "(retain_graph=True) finds the state released by the first backward; run the forward again" % node)
+
+
 def _accumulate_grad(param: torch.Tensor, g: torch.Tensor, main: torch.cuda.Stream) -> None:
     """param.grad (+)= g on the CURRENT (side) stream."""
     if param.grad is None:
@@ -743,8 +751,8 @@ def _defer_flush(side: Optional[torch.cuda.Stream] = None) -> None:
         and nothing has been written there in this pass -- the optimizer / all-reduce side then finds it in place (no pack copy:
         one multi-tensor launch right in front of the optimizer, and ~35 `.grad` re-pointings, less per step) -- else a fresh
         tensor.  The first contribution of a pass writes, later ones are added (`_add_to_grad`)."""
-        v = getattr(param, "_ggpm_grad_view", None)
-        if v is not None and param.grad is None and id(param) not in taken:
+        v = grad_view(param)
+        if v is not None and id(param) not in taken:
             taken.add(id(param))
             return v
         return torch.empty_like(param)
@@ -753,7 +761,7 @@ def _defer_flush(side: Optional[torch.cuda.Stream] = None) -> None:
     with torch.cuda.stream(stream):
         # every Linear's weight gradient (one contraction per K segment) and bias gradient in ONE library call
         # (ggpm_linear_wgrads_batch: the same launches in the same order as ~60 separate gemm / colsum calls)
-        items, keep, n_max, ws_max = [], [], 0, 0
+        items, keep, out, n_max, ws_max = [], [], [], 0, 0
         lib = _lib.load()
         for weight, bias, Ks, visits in lin.values():
             N = weight.shape[0]
@@ -773,9 +781,9 @@ def _defer_flush(side: Optional[torch.cuda.Stream] = None) -> None:
                 o += K
             n_max = max(n_max, N)
             keep.append((dpre, xs, dW, db))
-            publish(weight, dW)
+            out.append((weight, dW))
             if db is not None:
-                publish(bias, db)
+                out.append((bias, db))
         if items:
             arr = _lib.array_type(WgradItem, len(items))(*[WgradItem(*it) for it in items])
             dev = keep[0][0].device
@@ -783,6 +791,10 @@ def _defer_flush(side: Optional[torch.cuda.Stream] = None) -> None:
             csws = torch.empty(256 * n_max, dtype=torch.float32, device=dev)
             _lib.check(lib.ggpm_linear_wgrads_batch(len(items), ctypes.addressof(arr), _p(ws), ws_max, _p(csws),
                                                     _stream()), "linear_wgrads_batch")
+        # published only now, behind the launch that writes them: an add into an existing .grad (gradient accumulation,
+        # zero_grad(set_to_none=False), a Linear queued under two K splits) is enqueued after dW / db hold their values
+        for param, g in out:
+            publish(param, g)
         for param, grads in sums.values():
             publish(param, use(grads[0]) if len(grads) == 1 else torch.stack([use(g) for g in grads], dim=0).sum(dim=0))
         for table, width, visits in gath.values():       # embedding tables: d(table)[id] = sum of the rows that used id
@@ -860,6 +872,8 @@ class _GruLevel(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dHD):
         x, W_z, W_r, U_r, W_h = ctx.saved_tensors
+        if ctx.stash is None:
+            raise second_backward("gru_level")
         Xr, Hs, Qs, Ss, Gs, Zs, Ms, Rs = ctx.stash
         pred, depth, I, H = ctx.meta
         lib = _lib.load()
@@ -1007,6 +1021,8 @@ class _GruSparse(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dH):
         x_sub, submess, W_z, W_r, U_r, W_h = ctx.saved_tensors
+        if ctx.stash is None:
+            raise second_backward("gru_sparse")
         Xr, frozen, pred, Hs, Qs, Ss, Gs, Zs, Ms, Rs = ctx.stash
         depth, I, H = ctx.meta
         lib = _lib.load()
@@ -1106,6 +1122,8 @@ class _LstmSparse(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dH, dC):
         x_sub, submess, W_i, W_o, W_u, W_f = ctx.saved_tensors
+        if ctx.stash is None:
+            raise second_backward("lstm_sparse")
         Xf, frozen, pred, Hs, Cs, Qs, Ss, Is, Os, Us, Fs = ctx.stash
         depth, I, H = ctx.meta
         lib = _lib.load()
@@ -1205,6 +1223,8 @@ class _LstmLevel(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dHD, _dC):
         x, W_i, W_o, W_u, W_f = ctx.saved_tensors
+        if ctx.stash is None:
+            raise second_backward("lstm_level")
         Xf, Hs, Cs, Qs, Ss, Is, Os, Us, Fs = ctx.stash
         pred, depth, I, H = ctx.meta
         lib = _lib.load()

@@ -184,6 +184,8 @@ class _Heads(torch.autograd.Function):
         lib = _lib.load()
         heads, spec, S = ctx.heads, ctx.spec, ctx.saved_
         H, L, B, P, C = ctx.dims
+        if S is None:       # released below: the loss gradients are also scaled in place, a second pass would scale them again
+            raise F_.second_backward("score heads")
         ctx.saved_ = None
         if dloss is None:
             return (None,) * len(ctx.needs_input_grad)

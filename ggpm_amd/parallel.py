@@ -12,6 +12,7 @@ Works with any torch.distributed backend ("nccl" = RCCL on ROCm, "gloo" for the 
 """
 from __future__ import annotations
 
+import weakref
 from typing import Iterable, List, Sequence
 
 import torch
@@ -23,6 +24,31 @@ from . import _dev
 def shard_indices(n_items: int, rank: int, world_size: int) -> List[int]:
     """Round-robin shard of item (batch) indices: rank r takes r, r+W, r+2W, ..."""
     return list(range(rank, n_items, world_size))
+
+
+# id(parameter) -> (weakref to the parameter, weakref to the FlatGradSync that owns its slot, slot index).  A side table,
+# not an attribute of the parameter: copy.deepcopy / torch.save of a model then carry no pointer into a flat buffer, and a
+# discarded sync's buffer is neither written nor kept alive.
+_GRAD_SLOTS = {}
+
+
+def slot_view(param, sync, slot: int):
+    """The slice of ``sync``'s flat buffer the backward may form ``param``'s gradient in, or None: the sync is alive and
+    active(), its slot ``slot`` holds this very parameter (not a copy of it), and ``param.grad`` is None (a gradient that is
+    already there is added to, never overwritten)."""
+    if sync is None or not sync.active() or param.grad is not None:
+        return None
+    if not 0 <= slot < len(sync.params) or sync.params[slot] is not param:
+        return None
+    return sync.views[slot]
+
+
+def grad_view(param):
+    """slot_view() for the sync that registered ``param`` last (None if there is none, or it is gone)."""
+    e = _GRAD_SLOTS.get(id(param))
+    if e is None or e[0]() is not param:
+        return None
+    return slot_view(param, e[1](), e[2])
 
 
 class FlatGradSync:
@@ -45,7 +71,6 @@ class FlatGradSync:
 
     def __init__(self, params: Iterable[torch.nn.Parameter], process_group=None, encoder=None, keep_flat: bool = False):
         import os
-        import weakref
         seen, uniq = set(), []
         for p in params:                         # tied embeddings appear once
             if p.requires_grad and id(p) not in seen:
@@ -93,15 +118,17 @@ class FlatGradSync:
         # there and ggpm_amd.optim.FlatAdam reads it as the gradient of its single flat parameter
         self.keep_flat = keep_flat
         self._early_work = None
-        if self.active():
-            # gradients this package forms itself (functional._defer_flush) are written straight into their slice of the
-            # buffer: pack() then has nothing to copy for them
-            # (not the encoder's: the C++ backward driver OVERWRITES its slices -- a tied embedding's decoder-side contribution
-            # must be ADDED behind it, which the fresh-tensor path does)
-            enc = set(id(p) for p in self.encoder_params)
-            for p, v in zip(self.params, self.views):
-                if id(p) not in enc:
-                    p._ggpm_grad_view = v
+        # gradients this package forms itself (functional._defer_flush) are written straight into their slice of the
+        # buffer: pack() then has nothing to copy for them
+        # (not the encoder's: the C++ backward driver OVERWRITES its slices -- a tied embedding's decoder-side contribution
+        # must be ADDED behind it, which the fresh-tensor path does).  A sync built later over the same parameters replaces
+        # this one's slots, an inactive one clears them.
+        enc = set(id(p) for p in self.encoder_params)
+        for i, p in enumerate(self.params):
+            if self.active() and id(p) not in enc:
+                _GRAD_SLOTS[id(p)] = (weakref.ref(p, lambda _, k=id(p): _GRAD_SLOTS.pop(k, None)), weakref.ref(self), i)
+            else:
+                _GRAD_SLOTS.pop(id(p), None)
         backend = dist.get_backend(process_group) if dist.is_initialized() else ""
         self._avg = backend == "nccl"             # RCCL averages in the collective; gloo sums, then one division
 

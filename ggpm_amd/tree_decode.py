@@ -137,6 +137,8 @@ class _TreeLevel(torch.autograd.Function):
         lib = _lib.load()
         S = ctx.S
         lstm, H, He, has_extra = ctx.meta
+        if ctx.stash is None:
+            raise F_.second_backward("tree-side decoder level")
         finput, hnode, hmess, Xg, Hs, Cs, Qs, St, nei = ctx.stash
         lower, node = ctx.saved_tensors
         ctx.stash = None
@@ -334,6 +336,8 @@ class _TreeLevelNative(torch.autograd.Function):
         S = ctx.S
         lstm, H, He, has_extra = ctx.meta
         lower, saved = ctx.saved_tensors
+        if ctx.keep is None:
+            raise F_.second_backward("tree-side decoder level")
         L, V, extra, _tables = ctx.keep
         finput, hnode, nei = ctx.views
         emb, W, b, Wo, bo = ctx.prm[:5]

@@ -484,3 +484,22 @@ class OracleRuns:
         if failed:
             raise RuntimeError(failed)
         return out
+
+
+def vae_model(name, dev):
+    """The VaeGolden fixture ``name`` as the GPU tests run it: (golden, HierPropertyVAE with the fixture's weights on
+    ``dev``, device tensors, DecodeSchedule).  One step is
+    ``model(None, None, tensors, [None] * g.B, None, None, beta=g.beta, perturb_z=False, schedule=sch)``."""
+    import torch
+    from ggpm_amd import synth
+    from ggpm_amd.decoder import DecodeSchedule
+    from ggpm_amd.property_vae import HierPropertyVAE
+    from ggpm_amd.vocab import IndexPairVocab
+    g = VaeGolden(name)
+    specs = g.specs()
+    tensors = synth.tensorize(specs)
+    model = HierPropertyVAE(g.args(IndexPairVocab(g.n_motif, g.n_attach))).to(dev)
+    res = model.load_state_dict({k: torch.from_numpy(v) for k, v in g.state_dict().items()}, strict=False)
+    assert not res.unexpected_keys
+    assert all(k.startswith(("decoder.rnn_cell.", "decoder.E_assm.")) for k in res.missing_keys), res.missing_keys
+    return g, model, tensors, DecodeSchedule.from_specs(specs, tensors)

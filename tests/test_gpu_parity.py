@@ -1389,19 +1389,8 @@ def test_vae_step_matches_reference_golden(name, mode, monkeypatch):
         monkeypatch.setattr(dev_settings, "DECODE_DRIVER", False)
     if mode == "batched_opheads":       # the score heads op by op (~30 autograd nodes) instead of heads_fused's one node
         monkeypatch.setattr(dev_settings, "HEADS_COMPOSITE", False)
-    from golden_utils import VaeGolden
-    from ggpm_amd import synth
-    from ggpm_amd.decoder import DecodeSchedule
-    from ggpm_amd.property_vae import HierPropertyVAE
-    from ggpm_amd.vocab import IndexPairVocab
-    g = VaeGolden(name)
-    specs = g.specs()
-    tensors = synth.tensorize(specs)
-    model = HierPropertyVAE(g.args(IndexPairVocab(g.n_motif, g.n_attach))).to(_dev())
-    res = model.load_state_dict({k: torch.from_numpy(v) for k, v in g.state_dict().items()}, strict=False)
-    assert not res.unexpected_keys
-    assert all(k.startswith(("decoder.rnn_cell.", "decoder.E_assm.")) for k in res.missing_keys), res.missing_keys
-    sch = DecodeSchedule.from_specs(specs, tensors)
+    from golden_utils import vae_model
+    g, model, tensors, sch = vae_model(name, _dev())
     loss, metrics = model(None, None, tensors, [None] * g.B, None, None, beta=g.beta, perturb_z=False, schedule=sch)
     loss.backward()
     assert abs(float(loss.detach()) - float(g.z["loss"])) <= TOL * abs(float(g.z["loss"]))

@@ -153,3 +153,41 @@ def test_flat_buffers_keep_every_parameter_on_a_256_byte_boundary():
     for o, p in zip(sync.offsets, sync.params):
         pad[o:o + p.numel()] = False
     assert float(opt.flat.data[pad].abs().max()) == 0.0 and float(sync.flat[pad].abs().max()) == 0.0      # the padding stays zero
+
+
+def test_flat_buffer_slots_follow_the_sync_that_owns_them():
+    """parallel.slot_view / grad_view: a parameter's gradient may be formed in its slice of a FlatGradSync's flat buffer only
+    while that sync is alive and active(), the slot holds this very parameter, and .grad is None.  A later sync over the same
+    parameters takes the slots over (an inactive one clears them); a deep copy of the model has none."""
+    import copy
+    import gc
+    from ggpm_amd.parallel import grad_view, slot_view
+    model = _model(seed=5)
+    params = list(model.parameters())
+    assert all(grad_view(p) is None for p in params)
+    a = FlatGradSync(params, keep_flat=True)
+    assert a.active()
+    for i, p in enumerate(params):
+        assert grad_view(p) is a.views[i] and slot_view(p, a, i) is a.views[i]
+        assert slot_view(p, a, (i + 1) % len(params)) is None          # another parameter's slot
+        assert slot_view(p, None, i) is None                           # no sync
+    p0 = params[0]
+    p0.grad = torch.zeros_like(p0)
+    assert grad_view(p0) is None and slot_view(p0, a, 0) is None      # a gradient that is there is added to
+    p0.grad = None
+
+    twin = copy.deepcopy(model)
+    assert all(grad_view(q) is None for q in twin.parameters())
+    assert not any(isinstance(v, torch.Tensor) for q in twin.parameters() for v in vars(q).values())
+
+    b = FlatGradSync(params, keep_flat=True)
+    assert all(grad_view(p) is b.views[i] for i, p in enumerate(params))
+    del b
+    gc.collect()
+    assert all(grad_view(p) is None for p in params)                  # the owner is gone: its buffer is not written
+
+    a2 = FlatGradSync(params, keep_flat=True)
+    c = FlatGradSync(params)                                           # one rank, no keep_flat: not active()
+    assert not c.active() and all(slot_view(p, c, i) is None for i, p in enumerate(params))
+    assert all(grad_view(p) is None for p in params)                  # ... and a2's slots are cleared
+    assert all(slot_view(p, a2, i) is a2.views[i] for i, p in enumerate(params))
