@@ -78,6 +78,11 @@ SIGNATURES = {
     "ggpm_scale_rows": (I, [P, I, I, I, P, P]),
     "ggpm_head_accuracies": (I, [P, P, P, P, I, P, I, P, I, P, I, I, I, I, P, P]),
     "ggpm_dropout": (I, [P, I, I, I, ctypes.c_float, ctypes.c_uint, ctypes.c_uint, I, P]),
+    # property heads / latent search (csrc/property.hip): heads are ggpm_prop_head*, grads ggpm_prop_head_grads*
+    "ggpm_property_heads_workspace_bytes": (c_size_t, [I, I, P, P]),
+    "ggpm_property_heads_forward": (I, [I, P, I, I, P, P, P, P, c_float, ctypes.c_uint, ctypes.c_uint, P, P, P, c_size_t, P]),
+    "ggpm_property_heads_backward": (I, [I, P, I, I, P, P, P, P, c_float, P, P, P, c_size_t, P, I, I, P, P, P]),
+    "ggpm_property_latent_search": (I, [I, I, P, I, I, P, P, P, P, c_float, I, c_float, c_float, c_float, I, P, P, P, P, P]),
     "ggpm_encoder_saved_bytes": (c_size_t, [P]),
     "ggpm_encoder_work_bytes": (c_size_t, [P]),
     "ggpm_encoder_forward": (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, c_size_t, P, P, P, P, P, P]),

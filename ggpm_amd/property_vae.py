@@ -272,3 +272,141 @@ class HierPropertyVAE(nn.Module):
             return loss, StepMetrics((loss, kl_div, wacc, iacc, tacc, sacc))
         return loss, {'Loss': loss.item(), 'KL:': kl_div.item(), 'Word': float(wacc), 'I-Word': float(iacc),
                       'Topo': float(tacc), 'Assm': float(sacc)}
+
+
+class PropStepMetrics(StepMetrics):
+    """The metrics dictionary of ``HierPropOptVAE.forward`` (ggpm/property_vae.py:249-252), read lazily like StepMetrics
+    (values are taken as fp32 on the device, python floats when read)."""
+
+    _KEYS = ('Loss', 'KL', 'Recs_Loss', 'HOMO_MSE', 'LUMO_MSE', 'Word', 'I-Word', 'Topo', 'Assm')
+
+
+class LossClipped:
+    """The third value of ``HierPropOptVAE.forward``: whether ``clip_negative_loss`` replaced the loss.  The decision
+    stays on the device; ``bool()`` reads it (vae_fine_tune.py reads it after ``optimizer.step()``)."""
+
+    def __init__(self, flag):
+        self._flag = flag
+
+    def __bool__(self):
+        if isinstance(self._flag, torch.Tensor):
+            self._flag = bool(self._flag.item())
+        return bool(self._flag)
+
+    def __repr__(self):
+        return repr(bool(self))
+
+
+class HierPropOptVAE(nn.Module):
+    """reference ggpm/property_vae.py:130-254 -- HierPropertyVAE's encoder, rsample and teacher-forced decoder plus the
+    HOMO / LUMO heads on the two latent halves (``property_optim``, ggpm_amd.property) and optionally ``LossWeigh``; the
+    class ``OPVNet.get_model('hier-prop-opt')`` returns and ``vae_fine_tune.py`` trains.  Same argument bag (plus
+    ``linear_hidden_size``, ``property_optim_step``, optional ``loss_scaling``), sub-module names and ``state_dict`` keys.
+
+    ``forward(mols, graphs, tensors, orders, homos, lumos, beta, perturb_z=True, schedule=None)`` ->
+    ``(total_loss, metrics, clipped)`` with the reference's arithmetic:
+      * total = recon + homo_mse + lumo_mse.  There is NO KL term (the reference's ``loss += beta * kl_div`` sits in a
+        string literal): ``beta`` is unused and KL is a metric only.  With ``perturb_z=False`` R_var then receives no
+        gradient at all (``.grad`` stays None, as in the reference).
+      * ``loss_scaling``: LossWeigh's fp64 weights, as in the reference (the total is then fp64 of shape [1]).
+      * ``clip_negative_loss``: a total that is not > 0 is replaced by a draw of N(0.5, 0.5) (gradients then zero).  The
+        draw comes from a generator owned by the model (``clip_generator``), so the forward never advances torch's
+        global random streams.  By default the decision stays on the device (``torch.where``) and ``clipped`` is a
+        ``LossClipped`` whose ``bool()`` reads it; ``GGPM_LAZY_METRICS=0`` uses the reference's host-side form.
+    """
+
+    def __init__(self, args):
+        super().__init__()
+        from .decoder import HierMPNDecoder
+        from .property import PropertyOptimizer, LossWeigh
+        if args.latent_size % 2 != 0:
+            raise ValueError("HierPropOptVAE: latent_size must be even (the HOMO and LUMO heads read one half each), got %d"
+                             % args.latent_size)
+        self.encoder = HierMPNEncoder(args.vocab, args.atom_vocab, args.rnn_type, args.embed_size, args.hidden_size,
+                                      args.depthT, args.depthG, args.dropout)
+        self.decoder = HierMPNDecoder(args.vocab, args.atom_vocab, args.rnn_type, args.embed_size, args.hidden_size,
+                                      args.latent_size, args.diterT, args.diterG, args.dropout)
+        self.latent_size = args.latent_size // 2
+        self.property_optim = PropertyOptimizer(input_size=self.latent_size, hidden_size=args.linear_hidden_size,
+                                                dropout=args.dropout)
+        if getattr(args, "tie_embedding", False):
+            self.encoder.tie_embedding(self.decoder.hmpn)
+        self.property_optim_step = args.property_optim_step
+        self.R_mean = nn.Linear(args.hidden_size, args.latent_size)
+        self.R_var = nn.Linear(args.hidden_size, args.latent_size)
+        self.loss_scaling = bool(getattr(args, "loss_scaling", False))
+        if self.loss_scaling:
+            self.loss_weigh = LossWeigh()
+        self._clip_gen = None
+
+    @property
+    def clip_generator(self) -> torch.Generator:
+        """The generator of clip_negative_loss's replacement draws (created on the model's device, seeded with
+        ``torch.initial_seed()``; reseed it with ``manual_seed`` for a repeatable run)."""
+        dev = self.R_mean.weight.device
+        if self._clip_gen is None or self._clip_gen.device != dev:
+            self._clip_gen = torch.Generator(device=dev)
+            self._clip_gen.manual_seed(torch.initial_seed())
+        return self._clip_gen
+
+    def rsample(self, z_vecs, perturb=True):
+        return rsample(z_vecs, self.R_mean, self.R_var, perturb)
+
+    def encode_latent(self, tensors, perturb=False):
+        """Encoder + rsample of the reference's search (ggpm/property_control.py:194-200): -> (latent [B, 2 half], kl)."""
+        tree_tensors, graph_tensors = make_cuda(tensors)
+        root_vecs = self.encoder.forward_padded(tree_tensors, graph_tensors)[0]
+        return rsample(root_vecs, self.R_mean, self.R_var, perturb)
+
+    def reconstruct(self, batch, args=None):
+        raise NotImplementedError("HierPropOptVAE.reconstruct needs HierMPNDecoder.decode(), which needs rdkit "
+                                  "chemistry and is not part of this build")
+
+    def clip_negative_loss(self, loss):
+        noise = lambda: torch.normal(mean=0.5, std=0.5, size=loss.size(), dtype=loss.dtype, device=loss.device,  # noqa
+                                     generator=self.clip_generator)
+        if os.environ.get("GGPM_LAZY_METRICS", "1") == "0":
+            if loss > 0:
+                return False, loss
+            return True, loss * 0 + noise()
+        clipped = torch.logical_not(loss > 0)            # NaN counts as clipped, as `if loss > 0` does
+        return LossClipped(clipped.reshape(-1)[0]), torch.where(clipped, loss * 0 + noise(), loss)
+
+    def forward(self, mols, graphs, tensors, orders, homos, lumos, beta=0.0, perturb_z=True, schedule=None):
+        from . import fused
+        from .decoder import DecodeSchedule
+        if schedule is None:
+            schedule = getattr(graphs, "ggpm_schedule", None)
+        if schedule is None and graphs is not None:
+            schedule = DecodeSchedule.from_graphs(graphs, tensors, orders, self.decoder.vocab, **self.decoder.schedule_hints())
+        tree_tensors, graph_tensors = tensors = make_cuda(tensors)
+        self.decoder.start_atom_level(schedule, tensors)       # independent of the latent vector: issued beside the encoder
+        beside = getattr(self.decoder, "_atom_ahead", None) is not None and _dev.ENC_NARROW
+        fused.NARROW[0] = beside
+        try:
+            root_vecs = self.encoder.forward_padded(tree_tensors, graph_tensors)[0]
+        finally:
+            fused.NARROW[0] = False
+        if perturb_z:
+            root_vecs, kl_div = rsample(root_vecs, self.R_mean, self.R_var, True)
+        else:
+            # z = mean: KL is a metric only, so R_var stays out of the graph (its .grad stays None, as in the reference)
+            root_vecs, kl_div = _KLHead.apply(root_vecs, self.R_mean.weight, self.R_mean.bias,
+                                              self.R_var.weight.detach(), self.R_var.bias.detach(), None)
+        dev = root_vecs.device
+        t_homo = torch.as_tensor(homos, dtype=torch.float32).to(dev, non_blocking=True)
+        t_lumo = torch.as_tensor(lumos, dtype=torch.float32).to(dev, non_blocking=True)
+        homo_loss, lumo_loss, _, _ = self.property_optim.forward_latent(root_vecs, (t_homo, t_lumo))
+        loss, wacc, iacc, tacc, sacc = self.decoder(mols, (root_vecs, root_vecs, root_vecs), graphs, tensors, orders,
+                                                    schedule=schedule)
+        if self.loss_scaling:
+            loss = self.loss_weigh.compute_recon_loss(loss)
+            homo_loss, lumo_loss = self.loss_weigh.compute_prop_loss(homo_loss, lumo_loss)
+        total_loss = loss + homo_loss + lumo_loss
+        clipped, total_loss = self.clip_negative_loss(total_loss)
+        if os.environ.get("GGPM_LAZY_METRICS", "1") != "0":
+            return total_loss, PropStepMetrics((total_loss, kl_div, loss, homo_loss, lumo_loss, wacc, iacc, tacc, sacc)), \
+                clipped
+        return total_loss, {'Loss': total_loss.item(), 'KL': kl_div.item(), 'Recs_Loss': loss.item(),
+                            'HOMO_MSE': homo_loss.item(), 'LUMO_MSE': lumo_loss.item(), 'Word': float(wacc),
+                            'I-Word': float(iacc), 'Topo': float(tacc), 'Assm': float(sacc)}, bool(clipped)

@@ -166,6 +166,67 @@ int ggpm_scatter_rows(const float* src, int ld_src, const int32_t* idx, int rows
  * inject the same mask into the oracle. */
 int ggpm_dropout(float* x, int rows, int cols, int ld, float p, unsigned int seed_lo, unsigned int seed_hi, int site,
                  ggpm_stream_t stream);
+/* ------------------------------------------------------------------ property heads and latent search (property.hip)
+ * HierPropOptVAE's HOMO / LUMO heads (ggpm/property_optimizer.py: PropertyOptimizer = two PropertyRegressor) and the
+ * latent property search of ggpm/property_control.py:65-180.  One head is
+ *     Linear(width[0], width[1]) -> ReLU -> Dropout -> ... -> Linear(width[n_linear - 1], 1)
+ * with nn.Linear's row-major weights W[l] [width[l + 1], width[l]] and biases b[l] [width[l + 1]].  The homo head reads
+ * columns [0, half) of the latent z [B, ld], the lumo head columns [half, 2 half).
+ * Supported: 2 <= n_linear <= GGPM_PROP_MAX_LINEAR (1 to 4 hidden layers), 1 <= half <= 256, hidden widths <= 512,
+ * B <= 1024 for the heads forward / backward; anything else returns GGPM_ERR_UNSUPPORTED.
+ * Dropout (training forward, p > 0): the masks of ggpm_dropout() over the [B, width[l + 1]] output of hidden layer l at
+ * site GGPM_SITE_PROP_HOMO + l (homo head) or GGPM_SITE_PROP_LUMO + l (lumo head); p == 0 generates none. */
+#define GGPM_PROP_MAX_LINEAR 5
+#define GGPM_SITE_PROP_HOMO 16     /* dropout sites 16..19: homo head hidden layers 0..3 */
+#define GGPM_SITE_PROP_LUMO 20     /* dropout sites 20..23: lumo head hidden layers 0..3 */
+typedef struct ggpm_prop_head {
+    int n_linear;
+    int width[GGPM_PROP_MAX_LINEAR + 1];  /* width[0] = half, width[n_linear] = 1 */
+    const float* W[GGPM_PROP_MAX_LINEAR];
+    const float* b[GGPM_PROP_MAX_LINEAR];
+} ggpm_prop_head;
+typedef struct ggpm_prop_head_grads {
+    float* dW[GGPM_PROP_MAX_LINEAR];      /* same shapes as W / b; a null pointer skips that gradient */
+    float* db[GGPM_PROP_MAX_LINEAR];
+    int accumulate;                       /* 0: write, 1: add into what is there */
+} ggpm_prop_head_grads;
+/* Bytes of the workspace the forward fills and the backward reads (0: bad arguments). */
+size_t ggpm_property_heads_workspace_bytes(int B, int half, const ggpm_prop_head* homo, const ggpm_prop_head* lumo);
+/* Both heads in one launch: pred[2][B] (homo row, then lumo row) and, when `loss` is given, the two batch-mean MSEs
+ * loss[0] = mean (pred[0] - t_homo)^2, loss[1] = mean (pred[1] - t_lumo)^2 (each summed in a fixed order).  p: dropout
+ * probability of a training forward (0 in eval mode), seed_lo / seed_hi its mask stream.  `ws` is kept for the backward. */
+int ggpm_property_heads_forward(int B, const float* z, int ld, int half, const ggpm_prop_head* homo,
+                                const ggpm_prop_head* lumo, const float* t_homo, const float* t_lumo, float p,
+                                unsigned int seed_lo, unsigned int seed_hi, float* pred, float* loss, void* ws,
+                                size_t ws_bytes, ggpm_stream_t stream);
+/* The backward of that forward (same z, heads, targets, p, pred and ws) from dloss[2] (device), in one launch:
+ * dz[:, head columns] written (accumulate_dz = 0) or added into (1), every weight and bias gradient per
+ * ggpm_prop_head_grads (a null struct skips that head's parameter gradients).  Batch reductions in a fixed order. */
+int ggpm_property_heads_backward(int B, const float* z, int ld, int half, const ggpm_prop_head* homo,
+                                 const ggpm_prop_head* lumo, const float* t_homo, const float* t_lumo, float p,
+                                 const float* pred, const float* dloss, void* ws, size_t ws_bytes, float* dz, int ld_dz,
+                                 int accumulate_dz, const ggpm_prop_head_grads* g_homo, const ggpm_prop_head_grads* g_lumo,
+                                 ggpm_stream_t stream);
+/* The latent search of ggpm/property_control.py:65-180, ONE launch for the whole batch and every step (one workgroup per
+ * molecule; heads in eval form, no dropout).  Per molecule, fp32, v_h / v_l the two halves of its row of z:
+ *   soft / patience:  pat = patience; prev = 0; n = 0
+ *     while pat > 0 and n < max_steps:
+ *       o_x = f_x(v_x); loss = (o_h - t_h)^2 + (o_l - t_l)^2; n += 1
+ *       soft: if loss <= delta: stop (no update)
+ *       if loss > prev or |loss - prev| / prev <= threshold: pat -= 1 else pat = patience     (IEEE: prev = 0 gives inf / NaN)
+ *       prev = loss
+ *       v_x -= s_x lr 2 (o_x - t_x) df_x/dv_x,  s_x = -1 if o_x < t_x else +1                   (both heads, every body)
+ *   fixed:  min(steps, max_steps) bodies, the same update with the batch-mean factor 2 / B, no stopping rule.
+ * Outputs: z_out [B, ld] (columns past 2 half copied), pred_out[2][B] = the heads on the final latent, steps_taken[B]
+ * (loop bodies executed) and status[B]: GGPM_PROP_DONE, or GGPM_PROP_CAPPED when max_steps ended the loop (fixed: steps >
+ * max_steps).  max_steps >= 1 is required: the reference's loop need not end (a loss of exactly 0 resets the patience
+ * forever). */
+enum { GGPM_PROP_SEARCH_FIXED = 0, GGPM_PROP_SEARCH_SOFT = 1, GGPM_PROP_SEARCH_PATIENCE = 2 };
+enum { GGPM_PROP_DONE = 0, GGPM_PROP_CAPPED = 1 };
+int ggpm_property_latent_search(int mode, int B, const float* z, int ld, int half, const ggpm_prop_head* homo,
+                                const ggpm_prop_head* lumo, const float* t_homo, const float* t_lumo, float lr, int steps,
+                                float delta, float patience, float threshold, int max_steps, float* z_out, float* pred_out,
+                                int32_t* steps_taken, int32_t* status, ggpm_stream_t stream);
 /* One Adam step (torch.optim.Adam's arithmetic; ggpm/../vae_train.py:60,83 `optimizer.step()`) over ONE flat fp32 buffer that
  * all parameters are views of; p, g, m, v 16-byte aligned, n elements; step counts from 1.
  *   m += (1-b1)(g' - m); v = b2 v + (1-b2) g'^2; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps),  g' = g + wd p */
