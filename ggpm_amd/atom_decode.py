@@ -972,7 +972,9 @@ def atom_decode(plan: AtomPlan, graph_encoder, hnode_a: torch.Tensor, hmess_a: t
         params = (rnn.W_z.weight, rnn.W_z.bias, rnn.W_r.weight, rnn.U_r.weight, rnn.U_r.bias, rnn.W_h.weight, rnn.W_h.bias)
     drop = None
     if graph_encoder.training and wo[2].p > 0:
-        seed = torch.randint(0, 2 ** 31 - 1, (2,), dtype=torch.int64)
+        seed = getattr(graph_encoder, "_dropout_seed", None)           # (tests pin the seed)
+        if not seed:
+            seed = torch.randint(0, 2 ** 31 - 1, (2,), dtype=torch.int64)
         drop = (float(wo[2].p), int(seed[0]), int(seed[1]))
     fn = _AtomDecodeCompact if compact_enabled() else _AtomDecode
     if fn is _AtomDecode and not plan.full:

@@ -427,8 +427,10 @@ def init_decoder_tensors(tree_tensors, batch: int):
     return list(tree_tensors[:2]) + [agraph, bgraph] + list(tree_tensors[4:])
 
 
-def inc_mpn_forward(p: Params, pre: str, rnn_type: str, depth: int, tensors, h, num_nodes: int, subset):
-    """IncMPNEncoder.forward -- ggpm/encoder.py:165-179 (no pad-row mask on this path)."""
+def inc_mpn_forward(p: Params, pre: str, rnn_type: str, depth: int, tensors, h, num_nodes: int, subset, drop=None,
+                    step=None):
+    """IncMPNEncoder.forward -- ggpm/encoder.py:165-179 (no pad-row mask on this path).  ``drop``: see ``inc_hier_forward``;
+    W_o's Dropout acts on the ``subnode`` rows of this call, site ``<pre>W_o``."""
     fnode, fmess, agraph, bgraph = tensors
     subnode, submess = subset
     if len(submess) > 0:
@@ -438,6 +440,8 @@ def inc_mpn_forward(p: Params, pre: str, rnn_type: str, depth: int, tensors, h, 
             h = lstm_sparse_forward(p, pre + "rnn.", h[0], h[1], fmess, submess, bgraph, depth)
     nei = gather_rows(_hidden(rnn_type, h), agraph).sum(dim=1)
     node = torch.relu(_affine(p, pre + "W_o.0", torch.cat([fnode, nei], dim=1)))
+    if drop is not None:
+        node = drop(pre + "W_o", node, step)
     buf = torch.zeros(num_nodes, node.shape[1], dtype=node.dtype, device=node.device)
     return index_scatter(node, buf, subnode), h
 
@@ -458,35 +462,42 @@ def _sub_messages(hnode: Tensor, subnode: Tensor, fmess: Tensor, num_nodes: int)
     return torch.cat([buf.index_select(0, fmess[:, 0]), _eye(MAX_POS, hnode).index_select(0, fmess[:, 2])], dim=-1)
 
 
-def embed_sub_tree(p: Params, tree_tensors, hinput: Tensor, subtree, is_inter_layer: bool):
-    """IncHierMPNEncoder.embed_sub_tree -- ggpm/encoder.py:208-230."""
+def embed_sub_tree(p: Params, tree_tensors, hinput: Tensor, subtree, is_inter_layer: bool, drop=None, step=None):
+    """IncHierMPNEncoder.embed_sub_tree -- ggpm/encoder.py:208-230 (``drop``: the Dropout of E_i, W_i resp. E_c, W_c)."""
     subnode, submess = subtree
     fnode, fmess, agraph, bgraph, cgraph = _sub_tensor(tree_tensors, subtree)
+    dr = (lambda site, x: x) if drop is None else (lambda site, x: drop(site, x, step))
     if is_inter_layer:
-        finput = p["E_i.0.weight"].index_select(0, fnode[:, 1])
+        finput = dr("E_i", p["E_i.0.weight"].index_select(0, fnode[:, 1]))
         pooled = gather_rows(hinput, cgraph).sum(dim=1)
-        hnode = torch.relu(_affine(p, "W_i.0", torch.cat([finput, pooled], dim=-1)))
+        hnode = dr("W_i", torch.relu(_affine(p, "W_i.0", torch.cat([finput, pooled], dim=-1))))
     else:
-        finput = p["E_c.0.weight"].index_select(0, fnode[:, 0])
-        hnode = torch.relu(_affine(p, "W_c.0", torch.cat([finput, hinput.index_select(0, subnode)], dim=-1)))
+        finput = dr("E_c", p["E_c.0.weight"].index_select(0, fnode[:, 0]))
+        hnode = dr("W_c", torch.relu(_affine(p, "W_c.0", torch.cat([finput, hinput.index_select(0, subnode)], dim=-1))))
     hmess = fmess if len(submess) == 0 else _sub_messages(hnode, subnode, fmess, tree_tensors[0].shape[0])
     return hnode, hmess, agraph, bgraph
 
 
 def inc_hier_forward(p: Params, rnn_type: str, depthT: int, depthG: int, tree_tensors, inter_tensors, graph_tensors,
-                     htree: IncState, hinter: IncState, hgraph: IncState, subtree, subgraph):
-    """IncHierMPNEncoder.forward -- ggpm/encoder.py:232-249 (``graph_tensors`` already embedded)."""
+                     htree: IncState, hinter: IncState, hgraph: IncState, subtree, subgraph, drop=None, step=None):
+    """IncHierMPNEncoder.forward -- ggpm/encoder.py:232-249 (``graph_tensors`` already embedded).
+
+    ``drop``: training-mode dropout, None = inactive.  Called as ``drop(site, x, step)`` -> x with its mask applied (scaled
+    by 1 / (1 - p)) at each active nn.Dropout of the reference: sites "graph_encoder.W_o", "inter_encoder.W_o",
+    "tree_encoder.W_o" (once per call, over the call's ``subnode`` rows), "E_i", "W_i", "E_c", "W_c" (embed_sub_tree);
+    ``step`` is passed through (the decode step of the call)."""
     n_tree, n_graph = tree_tensors[0].shape[0], graph_tensors[0].shape[0]
     if len(subgraph[0]) + len(subgraph[1]) > 0:
         sub = _sub_tensor(graph_tensors[:4], subgraph)
         hgraph.node, hgraph.mess = inc_mpn_forward(p, "graph_encoder.", rnn_type, depthG, sub, hgraph.mess, n_graph,
-                                                   subgraph)
+                                                   subgraph, drop, step)
     if len(subtree[0]) + len(subtree[1]) > 0:
-        sub = embed_sub_tree(p, inter_tensors, hgraph.node, subtree, True)
+        sub = embed_sub_tree(p, inter_tensors, hgraph.node, subtree, True, drop, step)
         hinter.node, hinter.mess = inc_mpn_forward(p, "inter_encoder.", rnn_type, depthT, sub, hinter.mess, n_tree,
-                                                   subtree)
-        sub = embed_sub_tree(p, tree_tensors, hinter.node, subtree, False)
-        htree.node, htree.mess = inc_mpn_forward(p, "tree_encoder.", rnn_type, depthT, sub, htree.mess, n_tree, subtree)
+                                                   subtree, drop, step)
+        sub = embed_sub_tree(p, tree_tensors, hinter.node, subtree, False, drop, step)
+        htree.node, htree.mess = inc_mpn_forward(p, "tree_encoder.", rnn_type, depthT, sub, htree.mess, n_tree, subtree,
+                                                 drop, step)
     return htree, hinter, hgraph
 
 
@@ -546,9 +557,13 @@ def inc_teacher_forced(p: Params, kind: str, rnn_type: str, depthT: int, depthG:
 
 
 # ---------------------------------------------------------------- decoder score heads + losses (ggpm/decoder.py:35-69, 136-164, 262-283)
-def _head(p: Params, name: str, x: Tensor) -> Tensor:
-    """Sequential(Linear, ReLU, Dropout(inactive), Linear) -- ggpm/decoder.py:35-52."""
-    return _affine(p, name + ".3", torch.relu(_affine(p, name + ".0", x)))
+def _head(p: Params, name: str, x: Tensor, drop=None) -> Tensor:
+    """Sequential(Linear, ReLU, Dropout, Linear) -- ggpm/decoder.py:35-52; ``drop`` None = Dropout inactive, else called
+    as ``drop("<name>.2", hidden, None)``."""
+    h = torch.relu(_affine(p, name + ".0", x))
+    if drop is not None:
+        h = drop(name + ".2", h, None)
+    return _affine(p, name + ".3", h)
 
 
 def vocab_mask(n_motif: int, n_attach: int, owner: Tensor, dtype) -> Tensor:
