@@ -77,6 +77,9 @@ SIGNATURES = {
     "ggpm_bce_logits": (I, [P, P, I, P, P, P, P]),
     "ggpm_scale_rows": (I, [P, I, I, I, P, P]),
     "ggpm_head_accuracies": (I, [P, P, P, P, I, P, I, P, I, P, I, I, I, I, P, P]),
+    # attachment head of the tree-only decoder (csrc/motif_assm.hip)
+    "ggpm_motif_assm_forward": (I, [P, I, P, I, I, I, I, P, I, P, P, P, P, I, P, P, P, P, P, P]),
+    "ggpm_motif_assm_backward": (I, [P, P, I, P, I, I, I, I, I, P, I, P, P, P, I, P, P, P, P, P, P, P, P, P, P]),
     "ggpm_dropout": (I, [P, I, I, I, ctypes.c_float, ctypes.c_uint, ctypes.c_uint, I, P]),
     # property heads / latent search (csrc/property.hip): heads are ggpm_prop_head*, grads ggpm_prop_head_grads*
     "ggpm_property_heads_workspace_bytes": (c_size_t, [I, I, P, P]),

@@ -100,8 +100,10 @@ extern "C" int ggpm_tree_level_forward(const ggpm_tree_level* L, float* saved, s
     GGPM_CLEAR_STALE_ERROR();
     Dims d;
     if (!dims_of(L, d) || !saved || !out || !L->ids || !L->mess_inst || !L->mess_pos || !L->frozen || !L->pred_rowptr ||
-        !L->pred_col || !L->in_rowptr || !L->in_col || !L->emb || !L->W || !L->b || !L->Wo || !L->bo || !L->lower)
+        !L->pred_col || !L->in_rowptr || !L->in_col || !L->emb || !L->Wo || !L->bo)
         return GGPM_ERR_ARG;
+    const bool emb_input = L->W == nullptr;          // embedding-input mode: hnode = E[ids] (no W, b, lower; He == H)
+    if (emb_input ? (L->b || L->lower || L->He != L->H) : (!L->b || !L->lower)) return GGPM_ERR_ARG;
     for (int k = 0; k < d.G; ++k)
         if (!L->gate_w[k]) return GGPM_ERR_ARG;
     if (!d.lstm && (!L->Ur || !L->bu)) return GGPM_ERR_ARG;
@@ -111,9 +113,11 @@ extern "C" int ggpm_tree_level_forward(const ggpm_tree_level* L, float* saved, s
     if (saved_floats < total) return GGPM_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const int H = d.H, Hp = d.Hp, I = d.I;
-    // 1-2. visit vectors: relu([E[ids] | lower] W^T + b)
-    CK(ggpm_gather_rows(L->emb, L->ld_emb, L->ids, d.n_inst, d.He, v.finput, d.Hep, 0, d.Hep, stream));
-    {
+    // 1-2. visit vectors: relu([E[ids] | lower] W^T + b), or E[ids] itself in embedding-input mode
+    if (emb_input) {
+        CK(ggpm_gather_rows(L->emb, L->ld_emb, L->ids, d.n_inst, d.He, v.hnode, Hp, 0, Hp, stream));
+    } else {
+        CK(ggpm_gather_rows(L->emb, L->ld_emb, L->ids, d.n_inst, d.He, v.finput, d.Hep, 0, d.Hep, stream));
         const float* A[2] = {v.finput, L->lower};
         const int lda[2] = {d.Hep, L->ld_lower};
         const float* B[2] = {L->W, L->W + d.He};
@@ -179,8 +183,10 @@ extern "C" int ggpm_tree_level_backward(const ggpm_tree_level* L, const ggpm_tre
     GGPM_CLEAR_STALE_ERROR();
     Dims d;
     if (!dims_of(L, d) || !vin || !g || !work || !L->succ_rowptr || !L->succ_col || !L->inT_rowptr || !L->inT_col ||
-        !L->srcT_rowptr || !L->srcT_col || !g->dpre_w || !g->dpre_o || !g->d_finput || !g->dHin)
+        !L->srcT_rowptr || !L->srcT_col || !g->dpre_o || !g->d_finput || !g->dHin)
         return GGPM_ERR_ARG;
+    const bool emb_input = L->W == nullptr;
+    if (emb_input ? (g->d_lower || L->He != L->H) : !g->dpre_w) return GGPM_ERR_ARG;
     for (int k = 0; k < d.G; ++k)
         if (!g->dgate_w[k]) return GGPM_ERR_ARG;
     if (!d.lstm && (!g->dUr || !g->dbu)) return GGPM_ERR_ARG;
@@ -269,6 +275,13 @@ extern "C" int ggpm_tree_level_backward(const ggpm_tree_level* L, const ggpm_tre
         CK(ggpm_gemm_ksegments(0, d.ms, I, G, dXs, lda, B, ldb, K, dhmess, d.ldm, d.ldm, nullptr, 0, GGPM_ACT_NONE, 0, stream));
     }
     CK(ggpm_segment_sum(dhmess, d.ldm, L->srcT_rowptr, L->srcT_col, d.n_inst, H, d_hnode, Hp, 1, 0, stream));
+    if (emb_input) {        // d(E[ids]) = d(hnode) (He == H: the same padded width)
+        if (hipMemcpyAsync(g->d_finput, d_hnode, (size_t)d.n_inst * Hp * sizeof(float), hipMemcpyDeviceToDevice, s) !=
+            hipSuccess)
+            return GGPM_ERR_LAUNCH;
+        GGPM_CHECK_LAUNCH();
+        return GGPM_OK;
+    }
     CK(ggpm_act_backward(d_hnode, v.hnode, d.n_inst, H, Hp, GGPM_ACT_RELU, 0, g->dpre_w, stream));
     CK(ggpm_gemm(0, 0, d.n_inst, d.He, H, g->dpre_w, Hp, L->W, L->ld_w, g->d_finput, d.Hep, d.Hep, nullptr, 0, GGPM_ACT_NONE, 0,
                  nullptr, 0, stream));

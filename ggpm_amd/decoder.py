@@ -512,6 +512,26 @@ def _accuracy(pred: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     return (pred.long() == labels).float().sum() / labels.numel()
 
 
+def level_states(rnn, h0, hmess, dag, depth):
+    """All messages of one tree-side level at once: ``sparse_forward`` over every real message row with the
+    time-ordered predecessor table, iterated ``depth`` = longest chain times (see DecodeSchedule._level_plan)."""
+    E1 = dag.shape[0] + 1
+    rows = getattr(dag, "_ggpm_rows", None)            # (the same object every step: F_._sparse_structure's key)
+    if rows is None:
+        rows = torch.arange(1, E1, dtype=torch.long, device=hmess.device)
+        try:
+            dag._ggpm_rows = rows
+        except AttributeError:
+            pass
+    I, H = rnn.input_size, rnn.hidden_size
+    if isinstance(h0, tuple):
+        i, o, u, f = rnn.W_i[0], rnn.W_o[0], rnn.W[0], rnn.W_f[0]
+        return F_.lstm_sparse(h0[0], h0[1], hmess, rows, dag, i.weight, i.bias, o.weight, o.bias, u.weight, u.bias,
+                              f.weight, f.bias, depth, I, H)
+    return F_.gru_sparse(h0, hmess, rows, dag, rnn.W_z.weight, rnn.W_z.bias, rnn.W_r.weight, rnn.U_r.weight,
+                         rnn.U_r.bias, rnn.W_h.weight, rnn.W_h.bias, depth, I, H)
+
+
 class HierMPNDecoder(ScoreHeads):
     """reference ggpm/decoder.py:19-301 (training forward)"""
 
@@ -649,23 +669,7 @@ class HierMPNDecoder(ScoreHeads):
         return torch.cat(topo_vecs, dim=0), torch.cat(cls_vecs, dim=0), assm_vecs, assm_dest
 
     def _level_states(self, rnn, h0, hmess, dag, depth):
-        """All messages of one tree-side level at once: ``sparse_forward`` over every real message row with the
-        time-ordered predecessor table, iterated ``depth`` = longest chain times (see DecodeSchedule._level_plan)."""
-        E1 = dag.shape[0] + 1
-        rows = getattr(dag, "_ggpm_rows", None)            # (the same object every step: F_._sparse_structure's key)
-        if rows is None:
-            rows = torch.arange(1, E1, dtype=torch.long, device=hmess.device)
-            try:
-                dag._ggpm_rows = rows
-            except AttributeError:
-                pass
-        I, H = rnn.input_size, rnn.hidden_size
-        if isinstance(h0, tuple):
-            i, o, u, f = rnn.W_i[0], rnn.W_o[0], rnn.W[0], rnn.W_f[0]
-            return F_.lstm_sparse(h0[0], h0[1], hmess, rows, dag, i.weight, i.bias, o.weight, o.bias, u.weight, u.bias,
-                                  f.weight, f.bias, depth, I, H)
-        return F_.gru_sparse(h0, hmess, rows, dag, rnn.W_z.weight, rnn.W_z.bias, rnn.W_r.weight, rnn.U_r.weight,
-                             rnn.U_r.bias, rnn.W_h.weight, rnn.W_h.bias, depth, I, H)
+        return level_states(rnn, h0, hmess, dag, depth)
 
     # ---- the atom level ahead of the encoder ---------------------------------------------------------------------------
     # Teacher forcing makes the decoder's atom level (and its backward) independent of the latent vector: it reads the

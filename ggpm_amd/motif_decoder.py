@@ -1,0 +1,230 @@
+"""MotifDecoder -- the teacher-forced training forward of the tree-only decoder, reference ggpm/decoder.py:475-899
+(``sum_forward``; ``decode`` needs rdkit and stays out of scope, ``mean_forward`` is called nowhere in the reference).
+
+Same constructor, sub-module names and ``state_dict`` keys as the reference (``hmpn.*`` -- an ``IncEncoder`` --,
+``topoNN``, ``clsNN``, ``iclsNN``, ``matchNN``, ``W_assm``, ``W_root`` when latent != hidden, the aliases ``rnn_cell`` and
+``E_assm``), same ``forward(mols, src_mol_vecs, graphs, tensors, orders) -> (loss, cls_acc, icls_acc, topo_acc, assm_acc)``.
+
+The loop's bookkeeping is the hierarchical decoder's minus its atom level, so :class:`ggpm_amd.decoder.DecodeSchedule`
+derives it (its atom plan is simply not used).  Device work:
+  * the decoder's one level (``IncEncoder``: node input ``E_c[motif]``, message input ``[node of the source visit |
+    onehot(pos)]``, the root vectors as B frozen pseudo messages) over the decode-time DAG of ``DecodeSchedule._level_plan``
+    as one call per direction into the tree-level driver (csrc/tree_level.hip, embedding-input mode; the default while
+    dropout is inactive), or op by op (one sparse-level call, one read-out; dropout active or ``_dev.TREE_DRIVER`` off),
+    or the reference's step loop through ``IncEncoder`` (``_dev.DECODER_BATCHED`` off, kept as the checker);
+  * topology and cluster heads through ``ScoreHeads`` on the library GEMM, their losses in csrc/losses.hip;
+  * ``enum_attach`` + ``get_assm_score`` + the padded cross entropy as ONE launch each way (csrc/motif_assm.hip).
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import _dev
+from . import functional as F_
+from . import inc_encoder as IE
+from .decoder import DecodeSchedule, MAX_POS, _accuracy, _memo, level_states
+from .decoder_heads import ScoreHeads, bce_with_logits_sum
+
+
+class _MotifAssm(torch.autograd.Function):
+    """(attachment loss sum, accuracy) of all predictions: ggpm_motif_assm_forward / _backward."""
+
+    @staticmethod
+    def forward(ctx, rows, z, W1, b1, Wa, ba, meta, P: int, C: int, n_cand: int):
+        from . import _lib
+        H, L, B = W1.shape[0], Wa.shape[0], z.shape[0]
+        dev = rows.device
+        z = z.contiguous()            # (dz is allocated like z and written at row stride z.stride(0))
+        act = torch.empty(rows.shape[0], H, dtype=torch.float32, device=dev)
+        score = torch.empty(max(n_cand, 1), dtype=torch.float32, device=dev)
+        stat = torch.empty(P, 4, dtype=torch.float32, device=dev)
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+        counter = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.check(_lib.load().ggpm_motif_assm_forward(
+            F_._p(rows), rows.stride(0), F_._p(meta), P, C, H, L, F_._p(W1), W1.stride(0), F_._p(b1), F_._p(Wa), F_._p(ba),
+            F_._p(z), z.stride(0), F_._p(act), F_._p(score), F_._p(stat), F_._p(out), F_._p(counter), F_._stream()),
+            "motif_assm_forward")
+        ctx.save_for_backward(rows, z, W1, Wa, ba, meta, act, score, stat)
+        ctx.dims = (P, C, B)
+        acc = out[1]
+        ctx.mark_non_differentiable(acc)
+        return out[0], acc
+
+    @staticmethod
+    def backward(ctx, dloss, _dacc):
+        from . import _lib
+        rows, z, W1, Wa, ba, meta, act, score, stat = ctx.saved_tensors
+        P, C, B = ctx.dims
+        H, L = W1.shape[0], Wa.shape[0]
+        dloss = dloss.reshape(1).contiguous().float()
+        drows = torch.zeros_like(rows)
+        dW1 = torch.empty(H, H + MAX_POS, dtype=torch.float32, device=rows.device)
+        db1 = torch.empty(H, dtype=torch.float32, device=rows.device)
+        dWa, dba = torch.empty_like(Wa), torch.empty_like(ba)
+        dz = torch.zeros_like(z)
+        _lib.check(_lib.load().ggpm_motif_assm_backward(
+            F_._p(dloss), F_._p(rows), rows.stride(0), F_._p(meta), P, C, H, L, B, F_._p(W1), W1.stride(0), F_._p(Wa),
+            F_._p(ba), F_._p(z), z.stride(0), F_._p(act), F_._p(score), F_._p(stat), F_._p(drows), F_._p(dW1), F_._p(db1),
+            F_._p(dWa), F_._p(dba), F_._p(dz), F_._stream()), "motif_assm_backward")
+        return drows, dz, dW1, db1, dWa, dba, None, None, None, None
+
+
+class AssmPlan:
+    """The attachment predictions of one schedule in the reference's order (step major): per prediction one meta row
+    {n candidates, k rows per candidate, nth_child, molecule, first candidate, first row}, and the E_assm id of every row
+    (``icls * len(cands)``, ggpm/decoder.py:624-626)."""
+
+    def __init__(self, schedule: DecodeSchedule):
+        meta, ids, n_cand, n_row = [], [], 0, 0
+        for st in schedule.steps:
+            for cands, icls, nth, i in st["assm"]:
+                n, k = len(cands), len(icls)
+                if k not in (1, 2):
+                    raise NotImplementedError("MotifDecoder: an attachment of %d atoms (the reference sums pairs only)" % k)
+                meta.append((n, k, int(nth), int(i), n_cand, n_row))
+                ids.extend(list(icls) * n)
+                n_cand += n
+                n_row += n * k
+        self.P, self.n_cand, self.n_row = len(meta), n_cand, n_row
+        self.meta = np.asarray(meta, dtype=np.int32).reshape(-1, 6)
+        self.ids = np.asarray(ids, dtype=np.int32)        # (int32: what the gather kernel reads)
+        self._dev = None
+
+    def to_device(self, device):
+        if self._dev is None or self._dev[0] != device:
+            self._dev = (device, torch.as_tensor(self.meta).to(device), torch.as_tensor(self.ids).to(device))
+        return self._dev[1], self._dev[2]
+
+
+def assm_plan(schedule: DecodeSchedule) -> AssmPlan:
+    ap = getattr(schedule, "_motif_assm", None)
+    if ap is None:
+        ap = schedule._motif_assm = AssmPlan(schedule)
+    return ap
+
+
+class MotifDecoder(ScoreHeads):
+    """reference ggpm/decoder.py:475-899 (training forward, ``attention=False``)"""
+
+    def __init__(self, vocab, avocab, rnn_type, embed_size, hidden_size, latent_size, depthT, depthG, dropout,
+                 attention=False):
+        super().__init__(vocab, embed_size, hidden_size, latent_size, dropout)
+        if attention:
+            raise NotImplementedError("attention is off in every shipped configuration")
+        if embed_size != hidden_size:
+            raise ValueError("MotifDecoder: embed_size must equal hidden_size (the reference's IncEncoder and enum_attach "
+                             "feed embedding rows where hidden vectors go), got %d and %d" % (embed_size, hidden_size))
+        self.avocab = avocab
+        self.use_attention = False
+        self.hmpn = IE.IncEncoder(vocab, avocab, rnn_type, embed_size, hidden_size, depthT, depthG, dropout)
+        self.rnn_cell = self.hmpn.tree_encoder.rnn          # aliases, as the reference registers them
+        self.E_assm = self.hmpn.E_i
+        self.matchNN = nn.Sequential(nn.Linear(hidden_size + MAX_POS, hidden_size), nn.ReLU())
+        if latent_size != hidden_size:
+            self.W_root = nn.Linear(latent_size, hidden_size)
+
+    def schedule_hints(self) -> dict:
+        return {}
+
+    # ------------------------------------------------------------------ forward
+    def forward(self, mols, src_mol_vecs, graphs, tensors, orders, avg_loss=False, schedule: Optional[DecodeSchedule] = None):
+        if avg_loss:
+            raise NotImplementedError("MotifDecoder.mean_forward (avg_loss=True) is not part of this build: nothing in the "
+                                      "reference calls it")
+        tree_tensors, graph_tensors = tensors
+        B, H, L = len(orders), self.hidden_size, self.latent_size
+        dev = tree_tensors[0].device
+        if schedule is None:
+            schedule = DecodeSchedule.from_graphs(graphs, tensors, orders, self.vocab)
+        D = schedule.to_device(dev)._dev
+        src_root_vecs, src_tree_vecs, src_graph_vecs = src_mol_vecs
+        if L == H:
+            init_vecs = src_root_vecs
+        else:
+            init_vecs = F_.linear([src_root_vecs.contiguous()], [L], self.W_root.weight, self.W_root.bias)[:, :H]
+        if _dev.DECODER_BATCHED and schedule.plan["all_live"] and schedule.plan["E1"] > 1:
+            topo_vecs, cls_vecs = self._states_batched(schedule, D, tree_tensors, init_vecs)
+        else:
+            topo_vecs, cls_vecs = self._states_stepwise(schedule, tree_tensors, graph_tensors, init_vecs)
+
+        topo_scores = self.get_topo_score(src_tree_vecs, D["topo_batch32"], topo_vecs)
+        topo_loss = bce_with_logits_sum(topo_scores, _memo(D, "topo_label_f32", lambda: D["topo_label"].to(torch.float32)))
+        cls_loss, cls_pred, icls_pred = self.cls_losses(
+            src_tree_vecs, D["cls_batch32"], cls_vecs, _memo(D, "cls_clab32", lambda: D["cls_clab"].to(torch.int32).contiguous()),
+            _memo(D, "cls_ilab32", lambda: D["cls_ilab"].to(torch.int32).contiguous()))
+        topo_acc = ((topo_scores.detach() >= 0).long() == D["topo_label"]).float().sum() / D["topo_label"].numel()
+        cls_acc, icls_acc = _accuracy(cls_pred, D["cls_clab"]), _accuracy(icls_pred, D["cls_ilab"])
+        assm_loss, assm_acc = self.assm_head(schedule, src_graph_vecs)
+        loss = (topo_loss + cls_loss + assm_loss) / B
+        return loss, cls_acc, icls_acc, topo_acc, assm_acc
+
+    def assm_head(self, schedule: DecodeSchedule, src_graph_vecs):
+        """(attachment loss sum, accuracy) -- enum_attach, get_assm_score, the cross entropy over max_cls_size rows and
+        get_accuracy_sym of ggpm/decoder.py:620-637, 867-892 in one launch (csrc/motif_assm.hip); 0 and 1 without
+        attachment predictions, as the reference."""
+        ap = assm_plan(schedule)
+        if ap.P == 0:
+            return 0, 1
+        dev = src_graph_vecs.device
+        meta, ids = ap.to_device(dev)
+        # E_assm rows with the embedding's Dropout applied by torch's module (the masks the tests inject reach the kernel)
+        rows = IE._embedding_rows(self.E_assm, ids)
+        l1 = self.matchNN[0]
+        return _MotifAssm.apply(rows, src_graph_vecs, l1.weight, l1.bias, self.W_assm.weight, self.W_assm.bias, meta, ap.P,
+                                schedule.max_cls_size, ap.n_cand)
+
+    def _states_stepwise(self, schedule, tree_tensors, graph_tensors, init_vecs):
+        """The reference's loop, step by step (ggpm/decoder.py:790-860): one IncEncoder call per step."""
+        dev, H = tree_tensors[0].device, self.hidden_size
+        rnn_cell = self.rnn_cell
+        htree, tree_tensors = IE.init_decoder_state(rnn_cell, tree_tensors, init_vecs)
+        prev = IE.HTuple(vmask=torch.zeros(graph_tensors[0].size(0), dtype=torch.long, device=dev))
+        lt = lambda v: torch.as_tensor(np.asarray(v, dtype=np.int64), device=dev)   # noqa: E731
+        topo_vecs, cls_vecs = [], [init_vecs]
+        for st in schedule.steps:
+            subnode, submess = lt(st["subnode"]), lt(st["submess"])
+            if submess.numel():
+                htree.emask[submess] = 1
+            cur = IE.apply_tree_mask(tree_tensors, htree, prev)
+            htree = self.hmpn(cur, htree, (subnode, submess))
+            topo_vecs.append(htree.node.index_select(0, subnode))
+            if len(st["cls_mess"]):
+                cls_vecs.append(rnn_cell.get_hidden_state(htree.mess)[:, :H].index_select(0, lt(st["cls_mess"])))
+        return torch.cat(topo_vecs, dim=0), torch.cat(cls_vecs, dim=0)
+
+    def _states_batched(self, schedule, D, tree_tensors, init_vecs):
+        """Same vectors as ``_states_stepwise`` with the level de-sequentialised (DecodeSchedule._level_plan): every message
+        once, over the decode-time DAG.  With dropout inactive the level is ONE driver call per direction
+        (csrc/tree_level.hip in its embedding-input mode, ``_dev.TREE_COMPOSITE`` / ``TREE_DRIVER``); otherwise op by op:
+        one sparse-level call and ONE read-out over all visits, the Dropout modules applied by torch."""
+        hmpn, te, H = self.hmpn, self.hmpn.tree_encoder, self.hidden_size
+        P, T = schedule.plan, D["plan"]
+        n_inst, depth = P["n_inst"], max(P["chain"], 1)
+        from . import tree_decode as TD
+        prms = [q for m in (hmpn.E_c, te.W_o, te.rnn) for q in m.parameters()]
+        if _dev.TREE_DRIVER and TD.usable((hmpn.E_c[1], te.W_o[2]), prms):
+            spec = D.get("motif_level_spec")
+            if spec is None:
+                B_, E1 = init_vecs.shape[0], P["E1"]
+                pre = (D.get("level_structs") or {}).get("tree")
+                spec = D["motif_level_spec"] = TD.LevelSpec(
+                    T["inst_motif"], T["mess_inst"], T["mess_pos"], T["dag_tree"], T["in_tree"], E1, B_, depth,
+                    prebuilt=pre if pre is not None and pre[1].rows == E1 + B_ else None)
+            node, hid = TD.tree_level(spec, te.rnn, hmpn.E_c, None, te.W_o, None, init_vecs.contiguous())
+            return node[:, :H], torch.cat([init_vecs, hid[:, :H].index_select(0, T["cls_mess"])], dim=0)
+        hnode = IE._embedding_rows(hmpn.E_c, T["inst_motif"])                   # E_c's Dropout included
+        ld = (H + MAX_POS + 3) // 4 * 4
+        src_csr = F_.csr_from_index(T["mess_inst"], ncols=n_inst)
+        hmess = F_.tree_message_input(hnode, T["mess_inst"], src_csr, T["mess_pos"], H, MAX_POS, ld)[:, :H + MAX_POS]
+        fm = tree_tensors[1]
+        h_t = level_states(te.rnn, self.rnn_cell.get_init_state(fm, init_vecs), hmess, T["dag_tree"], depth)
+        hid = te.rnn.get_hidden_state(h_t)
+        nei = F_.segment_sum(hid, F_.csr_from_padded(T["in_tree"], ncols=hid.shape[0]), H)
+        node = F_.linear([hnode, nei], [H, H], te.W_o[0].weight, te.W_o[0].bias, act=F_.ACT_RELU)
+        node = te.W_o[2](node)
+        cls_vecs = torch.cat([init_vecs, hid[:, :H].index_select(0, T["cls_mess"])], dim=0)
+        return node[:, :H], cls_vecs

@@ -297,7 +297,32 @@ class LossClipped:
         return repr(bool(self))
 
 
-class HierPropOptVAE(nn.Module):
+class _ClipNegativeLoss:
+    """``clip_negative_loss`` of the reference's two property-optimising models (HierPropOptVAE, PropOptVAE): a total that
+    is not > 0 is replaced by a draw of N(0.5, 0.5) from ``clip_generator`` (see HierPropOptVAE)."""
+
+    @property
+    def clip_generator(self) -> torch.Generator:
+        """The generator of clip_negative_loss's replacement draws (created on the model's device, seeded with
+        ``torch.initial_seed()``; reseed it with ``manual_seed`` for a repeatable run)."""
+        dev = self.R_mean.weight.device
+        if self._clip_gen is None or self._clip_gen.device != dev:
+            self._clip_gen = torch.Generator(device=dev)
+            self._clip_gen.manual_seed(torch.initial_seed())
+        return self._clip_gen
+
+    def clip_negative_loss(self, loss):
+        noise = lambda: torch.normal(mean=0.5, std=0.5, size=loss.size(), dtype=loss.dtype, device=loss.device,  # noqa
+                                     generator=self.clip_generator)
+        if os.environ.get("GGPM_LAZY_METRICS", "1") == "0":
+            if loss > 0:
+                return False, loss
+            return True, loss * 0 + noise()
+        clipped = torch.logical_not(loss > 0)            # NaN counts as clipped, as `if loss > 0` does
+        return LossClipped(clipped.reshape(-1)[0]), torch.where(clipped, loss * 0 + noise(), loss)
+
+
+class HierPropOptVAE(_ClipNegativeLoss, nn.Module):
     """reference ggpm/property_vae.py:130-254 -- HierPropertyVAE's encoder, rsample and teacher-forced decoder plus the
     HOMO / LUMO heads on the two latent halves (``property_optim``, ggpm_amd.property) and optionally ``LossWeigh``; the
     class ``OPVNet.get_model('hier-prop-opt')`` returns and ``vae_fine_tune.py`` trains.  Same argument bag (plus
@@ -339,16 +364,6 @@ class HierPropOptVAE(nn.Module):
             self.loss_weigh = LossWeigh()
         self._clip_gen = None
 
-    @property
-    def clip_generator(self) -> torch.Generator:
-        """The generator of clip_negative_loss's replacement draws (created on the model's device, seeded with
-        ``torch.initial_seed()``; reseed it with ``manual_seed`` for a repeatable run)."""
-        dev = self.R_mean.weight.device
-        if self._clip_gen is None or self._clip_gen.device != dev:
-            self._clip_gen = torch.Generator(device=dev)
-            self._clip_gen.manual_seed(torch.initial_seed())
-        return self._clip_gen
-
     def rsample(self, z_vecs, perturb=True):
         return rsample(z_vecs, self.R_mean, self.R_var, perturb)
 
@@ -361,16 +376,6 @@ class HierPropOptVAE(nn.Module):
     def reconstruct(self, batch, args=None):
         raise NotImplementedError("HierPropOptVAE.reconstruct needs HierMPNDecoder.decode(), which needs rdkit "
                                   "chemistry and is not part of this build")
-
-    def clip_negative_loss(self, loss):
-        noise = lambda: torch.normal(mean=0.5, std=0.5, size=loss.size(), dtype=loss.dtype, device=loss.device,  # noqa
-                                     generator=self.clip_generator)
-        if os.environ.get("GGPM_LAZY_METRICS", "1") == "0":
-            if loss > 0:
-                return False, loss
-            return True, loss * 0 + noise()
-        clipped = torch.logical_not(loss > 0)            # NaN counts as clipped, as `if loss > 0` does
-        return LossClipped(clipped.reshape(-1)[0]), torch.where(clipped, loss * 0 + noise(), loss)
 
     def forward(self, mols, graphs, tensors, orders, homos, lumos, beta=0.0, perturb_z=True, schedule=None):
         from . import fused
@@ -399,6 +404,135 @@ class HierPropOptVAE(nn.Module):
         homo_loss, lumo_loss, _, _ = self.property_optim.forward_latent(root_vecs, (t_homo, t_lumo))
         loss, wacc, iacc, tacc, sacc = self.decoder(mols, (root_vecs, root_vecs, root_vecs), graphs, tensors, orders,
                                                     schedule=schedule)
+        if self.loss_scaling:
+            loss = self.loss_weigh.compute_recon_loss(loss)
+            homo_loss, lumo_loss = self.loss_weigh.compute_prop_loss(homo_loss, lumo_loss)
+        total_loss = loss + homo_loss + lumo_loss
+        clipped, total_loss = self.clip_negative_loss(total_loss)
+        if os.environ.get("GGPM_LAZY_METRICS", "1") != "0":
+            return total_loss, PropStepMetrics((total_loss, kl_div, loss, homo_loss, lumo_loss, wacc, iacc, tacc, sacc)), \
+                clipped
+        return total_loss, {'Loss': total_loss.item(), 'KL': kl_div.item(), 'Recs_Loss': loss.item(),
+                            'HOMO_MSE': homo_loss.item(), 'LUMO_MSE': lumo_loss.item(), 'Word': float(wacc),
+                            'I-Word': float(iacc), 'Topo': float(tacc), 'Assm': float(sacc)}, bool(clipped)
+
+
+def _motif_schedule(model, graphs, tensors, orders, schedule):
+    """The decoder's bookkeeping: the one passed, the one ScheduleAhead attached to ``graphs``, or derived here."""
+    from .decoder import DecodeSchedule
+    if schedule is None:
+        schedule = getattr(graphs, "ggpm_schedule", None)
+    if schedule is None and graphs is not None:
+        schedule = DecodeSchedule.from_graphs(graphs, tensors, orders, model.decoder.vocab, **model.decoder.schedule_hints())
+    return schedule
+
+
+class PropertyVAE(nn.Module):
+    """reference ggpm/property_vae.py:64-127 -- the tree-only model ``OPVNet.get_model('prop')`` returns (vae_train.py
+    --model-type prop): ``MotifEncoder``, the latent heads, the teacher-forced ``MotifDecoder``.  Same constructor argument
+    bag, sub-module names and ``state_dict`` keys.
+
+    ``forward(mols, graphs, tensors, orders, homos, lumos, beta, perturb_z=True, schedule=None) -> (loss, metrics)``:
+    loss = (topo + cls + icls + assm) / B + beta * KL; metrics under the reference's keys ('KL:' with its colon).
+    """
+
+    def __init__(self, args):
+        super().__init__()
+        from .encoder import MotifEncoder
+        from .motif_decoder import MotifDecoder
+        self.latent_size = args.latent_size
+        self.encoder = MotifEncoder(args.vocab, args.atom_vocab, args.rnn_type, args.embed_size, args.hidden_size,
+                                    args.depthT, args.depthG, args.dropout)
+        self.decoder = MotifDecoder(args.vocab, args.atom_vocab, args.rnn_type, args.embed_size, args.hidden_size,
+                                    args.latent_size, args.diterT, args.diterG, args.dropout)
+        if getattr(args, "tie_embedding", False):
+            self.encoder.tie_embedding(self.decoder.hmpn)
+        self.R_mean = nn.Linear(args.hidden_size, args.latent_size)
+        self.R_var = nn.Linear(args.hidden_size, args.latent_size)
+
+    def rsample(self, z_vecs, perturb=True):
+        return rsample(z_vecs, self.R_mean, self.R_var, perturb)
+
+    def reconstruct(self, batch, args=None):
+        raise NotImplementedError("PropertyVAE.reconstruct needs MotifDecoder.decode(), which needs rdkit chemistry and is "
+                                  "not part of this build")
+
+    def forward(self, mols, graphs, tensors, orders, homos=None, lumos=None, beta=0.0, perturb_z=True, schedule=None):
+        schedule = _motif_schedule(self, graphs, tensors, orders, schedule)
+        tree_tensors, graph_tensors = tensors = make_cuda(tensors)
+        root_vecs = self.encoder.forward_padded(tree_tensors)[0]
+        root_vecs, kl_div = rsample(root_vecs, self.R_mean, self.R_var, perturb_z)
+        loss, wacc, iacc, tacc, sacc = self.decoder(mols, (root_vecs, root_vecs, root_vecs), graphs, tensors, orders,
+                                                    schedule=schedule)
+        loss = loss + beta * kl_div
+        if os.environ.get("GGPM_LAZY_METRICS", "1") != "0":
+            return loss, StepMetrics((loss, kl_div, wacc, iacc, tacc, sacc))
+        return loss, {'Loss': loss.item(), 'KL:': kl_div.item(), 'Word': float(wacc), 'I-Word': float(iacc),
+                      'Topo': float(tacc), 'Assm': float(sacc)}
+
+
+class PropOptVAE(_ClipNegativeLoss, nn.Module):
+    """reference ggpm/property_vae.py:257-397 -- the tree-only model ``OPVNet.get_model('prop-opt')`` returns
+    (vae_fine_tune_indv_opt.py): PropertyVAE's encoder, rsample and decoder plus the HOMO / LUMO heads and optionally
+    ``LossWeigh``, as HierPropOptVAE, with the reference's two differences:
+      * the embeddings are ALWAYS tied (the reference's first ``tie_embedding`` call is unconditional);
+      * ``beta * KL`` IS added to the reconstruction loss (before ``loss_scaling``), so R_var receives a gradient even
+        with ``perturb_z=False``.
+    ``forward(...) -> (total_loss, metrics, clipped)`` with HierPropOptVAE's keys, ``clip_negative_loss`` and conventions.
+    """
+
+    def __init__(self, args):
+        super().__init__()
+        from .encoder import MotifEncoder
+        from .motif_decoder import MotifDecoder
+        from .property import PropertyOptimizer, LossWeigh
+        if args.latent_size % 2 != 0:
+            raise ValueError("PropOptVAE: latent_size must be even (the HOMO and LUMO heads read one half each), got %d"
+                             % args.latent_size)
+        self.encoder = MotifEncoder(args.vocab, args.atom_vocab, args.rnn_type, args.embed_size, args.hidden_size,
+                                    args.depthT, args.depthG, args.dropout)
+        self.decoder = MotifDecoder(args.vocab, args.atom_vocab, args.rnn_type, args.embed_size, args.hidden_size,
+                                    args.latent_size, args.diterT, args.diterG, args.dropout)
+        self.encoder.tie_embedding(self.decoder.hmpn)
+        self.latent_size = args.latent_size // 2
+        self.property_optim = PropertyOptimizer(input_size=self.latent_size, hidden_size=args.linear_hidden_size,
+                                                dropout=args.dropout)
+        self.property_optim_step = args.property_optim_step
+        self.R_mean = nn.Linear(args.hidden_size, args.latent_size)
+        self.R_var = nn.Linear(args.hidden_size, args.latent_size)
+        self.loss_scaling = bool(getattr(args, "loss_scaling", False))
+        if self.loss_scaling:
+            self.loss_weigh = LossWeigh()
+        self._clip_gen = None
+
+    def rsample(self, z_vecs, perturb=True):
+        return rsample(z_vecs, self.R_mean, self.R_var, perturb)
+
+    def encode_latent(self, tensors, perturb=False):
+        """MotifEncoder + rsample: -> (latent [B, 2 half], kl)."""
+        tree_tensors, _ = make_cuda(tensors)
+        return rsample(self.encoder.forward_padded(tree_tensors)[0], self.R_mean, self.R_var, perturb)
+
+    def reconstruct(self, batch, args=None):
+        raise NotImplementedError("PropOptVAE.reconstruct needs MotifDecoder.decode(), which needs rdkit chemistry and is "
+                                  "not part of this build")
+
+    def optimize_recs(self, batch, args=None):
+        raise NotImplementedError("PropOptVAE.optimize_recs needs MotifDecoder.decode(), which needs rdkit chemistry and "
+                                  "is not part of this build")
+
+    def forward(self, mols, graphs, tensors, orders, homos, lumos, beta=0.0, perturb_z=True, schedule=None):
+        schedule = _motif_schedule(self, graphs, tensors, orders, schedule)
+        tree_tensors, graph_tensors = tensors = make_cuda(tensors)
+        root_vecs = self.encoder.forward_padded(tree_tensors)[0]
+        root_vecs, kl_div = rsample(root_vecs, self.R_mean, self.R_var, perturb_z)
+        dev = root_vecs.device
+        t_homo = torch.as_tensor(homos, dtype=torch.float32).to(dev, non_blocking=True)
+        t_lumo = torch.as_tensor(lumos, dtype=torch.float32).to(dev, non_blocking=True)
+        homo_loss, lumo_loss, _, _ = self.property_optim.forward_latent(root_vecs, (t_homo, t_lumo))
+        loss, wacc, iacc, tacc, sacc = self.decoder(mols, (root_vecs, root_vecs, root_vecs), graphs, tensors, orders,
+                                                    schedule=schedule)
+        loss = loss + beta * kl_div
         if self.loss_scaling:
             loss = self.loss_weigh.compute_recon_loss(loss)
             homo_loss, lumo_loss = self.loss_weigh.compute_prop_loss(homo_loss, lumo_loss)

@@ -282,7 +282,7 @@ class _TreeLevelNative(torch.autograd.Function):
     @staticmethod
     def forward(ctx, S: LevelSpec, lstm: bool, H: int, He: int, lower, extra, emb, W, b, Wo, bo, *rp):
         lib = _lib.load()
-        dev = lower.device
+        dev = emb.device
         Hp = F_.padded_hidden(H)
         frozen, pred, in_csr, src_csr = S.structures()
         succ, in_T, src_T = pred.T, in_csr.T, src_csr.T
@@ -301,12 +301,12 @@ class _TreeLevelNative(torch.autograd.Function):
                      ("srcT_rowptr", src_T.rowptr), ("srcT_col", src_T.col)):
             setattr(L, k, _addr(t))
         L.emb, L.ld_emb = _addr(emb), F_._ld(emb)
-        L.W, L.b, L.ld_w = _addr(W), _addr(b), W.stride(0)
+        L.W, L.b, L.ld_w = _addr(W), _addr(b), (W.stride(0) if W is not None else 0)   # (W None: embedding-input mode)
         L.Wo, L.bo, L.ld_wo = _addr(Wo), _addr(bo), Wo.stride(0)
         for k, (w, bb) in enumerate(zip(gw, gb)):
             L.gate_w[k], L.ld_gate[k], L.gate_b[k] = _addr(w), w.stride(0), _addr(bb)
         L.Ur, L.bu, L.ld_ur = _addr(Ur), _addr(bu), (Ur.stride(0) if Ur is not None else 0)
-        L.lower, L.ld_lower = _addr(lower), F_._ld(lower)
+        L.lower, L.ld_lower = _addr(lower), (F_._ld(lower) if lower is not None else 0)
         L.extra, L.ld_extra = _addr(extra), (F_._ld(extra) if extra is not None else 0)
         n_saved = int(lib.ggpm_tree_level_saved_floats(ctypes.byref(L)))
         saved = torch.empty(n_saved, dtype=torch.float32, device=dev)
@@ -395,7 +395,8 @@ class _TreeLevelNative(torch.autograd.Function):
             F_._defer_sum(q, gr)
         if side is not None:
             F_._DEFER["early"] = side      # the end-of-pass flush waits for the second stream before it reads what was queued
-        F_._defer_linear(W, b, dpre_w, [finput, lower], (He, H))
+        if W is not None:
+            F_._defer_linear(W, b, dpre_w, [finput, lower], (He, H))
         F_._defer_linear(Wo, bo, dpre_o, [hnode, nei], (H, H))
         F_._defer_gather(emb, He, d_finput, S.ids)
         d_extra = dHin[E1:, :H] if (has_extra and ctx.needs_input_grad[5]) else None
@@ -413,7 +414,8 @@ def usable(modules, params) -> bool:
 
 
 def tree_level(S: LevelSpec, rnn, emb_seq, lin_seq, wo_seq, lower, extra: Optional[torch.Tensor]):
-    """-> (node [n_inst, Hp], hidden state [E1 + extra rows, Hp]) of one tree-side decoder level."""
+    """-> (node [n_inst, Hp], hidden state [E1 + extra rows, Hp]) of one tree-side decoder level.  ``lin_seq`` and
+    ``lower`` None: the embedding-input mode of the tree-only decoder's level (node input E[ids] itself; driver only)."""
     from .rnn import LSTM
     lstm = isinstance(rnn, LSTM)
     if lstm:
@@ -422,6 +424,11 @@ def tree_level(S: LevelSpec, rnn, emb_seq, lin_seq, wo_seq, lower, extra: Option
     else:
         rp = (rnn.W_z.weight, rnn.W_z.bias, rnn.W_r.weight, rnn.U_r.weight, rnn.U_r.bias, rnn.W_h.weight, rnn.W_h.bias)
     emb = emb_seq[0].weight
+    if lin_seq is None:
+        if lower is not None or not _dev.TREE_DRIVER:
+            raise ValueError("tree_level: the embedding-input mode takes no lower level and runs through the driver only")
+        return _TreeLevelNative.apply(S, lstm, rnn.hidden_size, emb.shape[1], None, extra, emb, None, None,
+                                      wo_seq[0].weight, wo_seq[0].bias, *rp)
     lower = lower if lower.stride(1) == 1 else lower.contiguous()
     node_fn = _TreeLevelNative if _dev.TREE_DRIVER else _TreeLevel      # (the Python composite stays as the checker)
     return node_fn.apply(S, lstm, rnn.hidden_size, emb.shape[1], lower, extra, emb, lin_seq[0].weight, lin_seq[0].bias,

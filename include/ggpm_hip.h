@@ -503,6 +503,8 @@ int ggpm_decode_join(void);
  * (n_inst rows) and inT_* its transpose (E1+n_extra rows), srcT_* the transpose of the message -> visit index (n_inst rows).
  * gate_w / gate_b: GRU {W_z, W_r, W_h} ([H, H+20+H]; W_r [H, H+20], gate_b[1] = null) + Ur, bu; LSTM {W_i, W_o, W, W_f}.
  * Dropout must be inactive (the caller falls back to the per-op entry points otherwise).
+ * Embedding-input mode (the tree-only decoder's level, IncEncoder): W, b and lower null, He == H -- hnode = E[ids] with no
+ * linear and no ReLU; the backward then writes d_finput = d(hnode) and leaves dpre_w (may be null) and d_lower (must be null).
  * forward: `saved` = ggpm_tree_level_saved_floats floats; on return `views` names the intermediates inside it (node
  * [n_inst, Hp] and slot `depth` of Hs [E1+n_extra, Hp] are the level's two results).  backward: d_node / d_hid nullable;
  * `grads` names caller-owned outputs -- full-shape gate weight gradients (both halves written), gate bias gradients
@@ -574,6 +576,24 @@ int ggpm_rsample_forward(const float* mean, const float* pv, const float* eps, i
                          ggpm_stream_t stream);
 int ggpm_rsample_backward(const float* mean, const float* pv, const float* eps, const float* dz, const float* dkl,
                           int B, int L, float* dmean, float* dpv, ggpm_stream_t stream);
+
+/* Attachment head of the tree-only decoder (MotifDecoder, ggpm/decoder.py:475-899: enum_attach, get_assm_score and the
+ * cross entropy over max_cls_size rows), one launch per direction.  rows: [R x H] E_assm rows (row stride ld_rows), every
+ * candidate's k rows consecutive; meta: [P x 6] int32 per prediction {n candidates, k rows per candidate (1 or 2),
+ * nth_child, molecule, first candidate, first row}; W1: matchNN.0.weight [H x (H + 20)] (row stride ldw), b1 its bias;
+ * Wa / ba: W_assm [L x H] / [L]; z: [B x L] latent (row stride ldz).  The C - n pad rows of a prediction score ba . z.
+ * Forward writes act [R x H] (matchNN output per row), score [candidates], stat [P x 4] (for the backward), out[0] = loss
+ * sum, out[1] = accuracy (get_accuracy_sym); counter: one int32, zero on entry, zero again on return.
+ * Backward (dloss: device scalar) writes drows [R x ld_rows], dW1 [H x (H + 20)] contiguous, db1, dWa [L x H], dba, dz
+ * [B x ldz]: plain stores, fixed-order sums, no atomics.  H <= 1024, L <= 1024. */
+int ggpm_motif_assm_forward(const float* rows, int ld_rows, const int32_t* meta, int P, int C, int H, int L,
+                            const float* W1, int ldw, const float* b1, const float* Wa, const float* ba, const float* z,
+                            int ldz, float* act, float* score, float* stat, float* out, int32_t* counter,
+                            ggpm_stream_t stream);
+int ggpm_motif_assm_backward(const float* dloss, const float* rows, int ld_rows, const int32_t* meta, int P, int C, int H,
+                             int L, int B, const float* W1, int ldw, const float* Wa, const float* ba, const float* z,
+                             int ldz, const float* act, const float* score, const float* stat, float* drows, float* dW1,
+                             float* db1, float* dWa, float* dba, float* dz, ggpm_stream_t stream);
 
 /* ------------------------------------------------------------------ whole-encoder drivers
  * HierMPNEncoder.forward (ggpm/encoder.py:140-157, with embed_graph/inter/tree/root :96-138) and its backward as ONE

@@ -1,0 +1,143 @@
+"""Loading of the tree-only model fixtures (tests/golden/make_golden_motif_vae.py) for the CPU and GPU tests, and a
+torch restatement of the tree-only decoder's attachment head (reference ggpm/decoder.py:620-637, 867-892) used as the
+oracle of the head kernel."""
+import glob
+import os
+from collections import OrderedDict
+
+import numpy as np
+import torch
+
+GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "motif_vae")
+
+
+def names(prefix=""):
+    return sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN_DIR, prefix + "*.npz")))
+
+
+class MotifGolden:
+    def __init__(self, name):
+        self.name, self.z = name, np.load(os.path.join(GOLDEN_DIR, name + ".npz"))
+        (self.H, self.latent, self.depthT, self.diterT, self.B, self.n_motif, self.n_attach, self.seed, self.bseed, m0, m1,
+         tie, scaling, full) = [int(v) for v in self.z["meta"]]
+        self.motifs, self.tie, self.scaling, self.full = (m0, m1), bool(tie), bool(scaling), bool(full)
+        self.kind, self.rnn, self.beta = str(self.z["kind"]), str(self.z["rnn"]), float(self.z["beta"])
+        lh = [int(v) for v in self.z["linear_hidden"]]
+        self.linear_hidden = lh[0] if bool(self.z["linear_hidden_is_int"]) else lh
+
+    def specs(self):
+        from ggpm_amd import synth
+        return synth.random_batch(self.bseed, self.B, motifs=self.motifs, n_motif_vocab=self.n_motif,
+                                  n_attach_vocab=self.n_attach)
+
+    def args(self, dropout=0.0):
+        from ggpm_amd.vocab import IndexPairVocab
+
+        class A:
+            pass
+        a = A()
+        a.vocab, a.rnn_type, a.embed_size, a.hidden_size = IndexPairVocab(self.n_motif, self.n_attach), self.rnn, self.H, self.H
+        a.atom_vocab = type("V", (), {"size": lambda s: 38})()
+        a.depthT, a.depthG, a.diterT, a.diterG = self.depthT, 2, self.diterT, 1
+        a.dropout, a.latent_size, a.tie_embedding = dropout, self.latent, self.tie
+        if self.kind == "prop-opt":
+            a.linear_hidden_size, a.property_optim_step, a.loss_scaling = self.linear_hidden, 20, self.scaling
+        return a
+
+    def model(self, dropout=0.0):
+        from ggpm_amd.opvnet import OPVNet
+        m = OPVNet.get_model(self.kind)(self.args(dropout))
+        m.load_state_dict(self.state_dict(m), strict=True)
+        return m
+
+    def state_dict(self, model):
+        """The reference's seeded parameters (in its own parameter order) under every state_dict key, aliases included."""
+        from ggpm_amd.params import seeded_state_dict
+        shapes = dict((k, tuple(v.shape)) for k, v in model.state_dict().items())
+        w64 = {k[4:]: v for k, v in self.z.items() if k.startswith("w64/")}
+        order = [str(k) for k in self.z["param_names"] if str(k) not in w64]
+        sd = dict(seeded_state_dict(OrderedDict((k, shapes[k]) for k in order), self.seed))
+        sd.update(w64)
+        return OrderedDict((str(k), torch.from_numpy(np.array(sd[str(s)]))) for k, s in zip(self.z["sd_keys"], self.z["sd_src"]))
+
+    def batch(self):
+        """(tensors, schedule, orders, homos, lumos) of the fixture's batch as ggpm_amd.synth builds it."""
+        from ggpm_amd import synth
+        from ggpm_amd.decoder import DecodeSchedule, synth_orders
+        specs = self.specs()
+        tensors = synth.tensorize(specs)
+        return (tensors, DecodeSchedule.from_specs(specs, tensors), synth_orders(specs, tensors[0][-1]),
+                self.z["t_homo"].tolist(), self.z["t_lumo"].tolist())
+
+    def ref_steps(self):
+        cols = []
+        for k in ("subnode", "submess"):
+            flat, off = self.z["ref_" + k], self.z["ref_" + k + "_off"]
+            cols.append([flat[off[i]:off[i + 1]].tolist() for i in range(len(off) - 1)])
+        return list(zip(*cols))
+
+    def check_step(self, model, loss, metrics, rel=1e-4):
+        """loss, metrics and every gradient of ``model``'s step against the reference's."""
+        params = model.state_dict(keep_vars=True)
+        grads = {k: (None if v.grad is None else v.grad.detach().double().cpu().numpy()) for k, v in params.items()}
+        self.check_step_values(float(loss), metrics, grads, rel)
+
+    def check_step_values(self, loss, metrics, grads, rel=1e-4):
+        """loss, metrics and {state_dict name: gradient array or None} against the reference's."""
+        z = self.z
+        want = float(z["loss"])
+        assert abs(float(loss) - want) <= rel * max(abs(want), 1.0), (self.name, float(loss), want)
+        names_ = [str(k) for k in z["metric_names"]]
+        assert list(metrics.keys()) == names_
+        for k, w in zip(names_, z["metric_values"]):
+            assert abs(float(metrics[k]) - w) <= rel * max(abs(w), 1.0), (self.name, k, float(metrics[k]), w)
+        none = set(str(k) for k in z["none_grads"])
+        for k in z["param_names"]:
+            k = str(k)
+            g = grads[k]
+            if k in none:
+                assert g is None or float(np.abs(g).max()) == 0.0, (self.name, k)
+                continue
+            assert g is not None, (self.name, k)
+            g = np.asarray(g, dtype=np.float64)
+            if "grad/" + k in z.files:
+                w = z["grad/" + k].astype(np.float64)
+                scale = np.abs(w).max()
+                if scale < 1e-6 or k.endswith("W_assm.bias"):
+                    # analytically zero (the softmax gradients of a prediction sum to 0): rounding noise on both sides
+                    assert np.abs(g).max() < 1e-4, (self.name, k)
+                    continue
+                err = np.abs(g - w).max() / scale
+                assert err <= rel, "%s grad %s: rel err %.3e" % (self.name, k, err)
+            else:
+                from golden_utils import Golden
+                idx = Golden.probe_indices(self, k, g.size)
+                stat = z["gstat/" + k]
+                scale = max(stat[2], 1e-12)
+                err = np.abs(g.reshape(-1)[idx] - z["gprobe/" + k]).max() / scale
+                assert err <= rel, "%s grad probe %s: rel err %.3e" % (self.name, k, err)
+                l2 = np.sqrt((g ** 2).sum())
+                assert abs(l2 - stat[1]) <= 4 * rel * max(stat[1], 1e-12), (self.name, k, l2, stat[1])
+
+
+def assm_head_reference(rows, meta, C, W1, b1, Wa, ba, z):
+    """(loss sum, accuracy): matchNN on [row | onehot(nth)], pair rows summed, zero-padded to C rows, W_assm, dot with
+    the molecule's latent, cross entropy with label 0 over all C rows, get_accuracy_sym.  Differentiable torch."""
+    H = W1.shape[0]
+    scores = []
+    for n, k, nth, b, coff, roff in meta.tolist():
+        x = rows[roff:roff + n * k, :H]
+        onehot = torch.zeros(n * k, W1.shape[1] - H, dtype=rows.dtype)
+        onehot[:, nth] = 1
+        a = torch.relu(torch.cat([x, onehot], dim=1) @ W1.t() + b1)
+        v = a.view(n, k, H).sum(dim=1)
+        v = torch.cat([v, torch.zeros(C - n, H, dtype=rows.dtype)], dim=0)
+        scores.append(((v @ Wa.t() + ba) * z[b]).sum(dim=-1))
+    s = torch.stack(scores)
+    lab = torch.zeros(len(scores), dtype=torch.long)
+    loss = torch.nn.functional.cross_entropy(s, lab, reduction="sum")
+    # get_accuracy_sym; the real rows of a prediction are equal without dropout, which a matmul need not reproduce
+    # bitwise in its last bits: ties within 1e-9 relative count as ties
+    mx = s.max(dim=-1)[0]
+    acc = (s[:, 0] >= mx - 1e-9 * mx.abs()).float().sum() / len(scores)
+    return loss, acc
