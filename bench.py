@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- molecules/s of the hierarchical encoder training step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 0..4] [--rnn GRU|LSTM] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 0..4] [--rnn GRU|LSTM] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 ``--gpus N`` (N > 1) without WORLD_SIZE in the environment starts the N rank processes itself (ggpm_amd/launcher.py: the
@@ -9,14 +9,18 @@ parent makes no HIP call, every rank is a fresh process with RANK / LOCAL_RANK /
 torch.distributed.run the ranks exist already and this file is one of them.
 
 Default workload = BASELINE.json configs[1]: synthetic random-motif molecules (~40 atoms, motif vocab 500),
-hidden = embed = 300, depthT = depthG = 20, batch 32 per GPU, fp32, GRU message function (the LSTM run of the same
-workload is reported in the same line under "lstm").  ``--config N`` selects configs[N] of BASELINE.json (CONFIGS
-below).  One "step" = zero_grad + HierMPNEncoder forward + KL heads + backward (+ gradient all-reduce over RCCL for
+hidden = embed = 300, depthT = depthG = 20, batch 32 per GPU, fp32, GRU message function (with ``--full`` the LSTM run
+of the same workload is reported in the same line under "lstm").  ``--config N`` selects configs[N] of BASELINE.json
+(CONFIGS below).  One "step" = zero_grad + HierMPNEncoder forward + KL heads + backward (+ gradient all-reduce over RCCL for
 N > 1) + Adam update on one batch whose tensorized index tensors are already resident in HBM.  Rank r consumes its own
 stream of batches (weak scaling: per-GPU work fixed); value = all molecules processed by all ranks / max-over-ranks
 time.
 
-Prints ONE JSON line on rank 0 with the contract's keys plus
+A plain run sets up, warms up, times the K steps, writes ``--dump-outputs`` and prints ONE JSON line on rank 0 with the
+contract's keys.  ``--full`` also measures everything else, after the headline steps, into the same line: the steps
+without the tree fixed-point hint ("full_depth_loops"), the other message function ("lstm", configs[1]) or the bf16
+gate products ("bf16", configs[4]), the full VAE training step ("vae_step", configs[1]), the configs[4] leg
+("configs4", configs[1], N = 1) and
   "roofline"     -- the dominant kernel (the fused depth step of the ATOM level: one 16-wave workgroup per CU) timed with
                     HIP events on its own stream, ALGORITHMIC flops per launch / mean launch time vs the fp32 MFMA
                     peak; the same kernel's launches on the two small tree-side levels are reported beside it
@@ -966,7 +970,7 @@ class VaeWorkload:
 
 
 def configs4_leg(a, lib, dev, budget_s=90.0):
-    """BASELINE configs[4] as a leg of the default line: {"fp32": ..., "bf16": ...}, <= 6 timed steps each."""
+    """BASELINE configs[4] as a leg of the --full line: {"fp32": ..., "bf16": ...}, <= 6 timed steps each."""
     import copy
     import gc
     if time.time() - _T0 > budget_s:
@@ -1087,9 +1091,14 @@ def parse_args(argv=None):
     ap.add_argument("--vae-profile", default=None, choices=["resident", "in_loop", "gc"],
                     help="with --only-vae under rocprofv3: stop after the resident steps / after the vae_train.py-shaped steps, so "
                          "that the trace ends with the steps to be cut out (tools/prof_summary.py --steps)")
-    ap.add_argument("--no-configs4", action="store_true", help="skip the configs[4] leg of the default line (\"configs4\": fp32 + bf16)")
+    ap.add_argument("--no-configs4", action="store_true", help="skip the configs[4] leg of the --full line (\"configs4\": fp32 + bf16)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline row: the pass without the tree fixed-point hint, the "
+                         "roofline pass, the other message function (configs[1]) or the bf16 leg (configs[4]), the full VAE "
+                         "step row, the configs[4] leg and the CPU baselines (each still skipped by its --no-* option).  "
+                         "Without it a run sets up, warms up, times the headline steps and prints their line")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the headline step computed in its last timed step as DIR/<name>.npy "
                          "(loss, kl, hroot, hnode, hinter, hatom, grads, params; float32, at most 64 MB in all).  The timed "
@@ -1100,6 +1109,8 @@ def parse_args(argv=None):
         ap.error("--steps must be at least 1")
     if a.dump_outputs is not None and (a.host_input or a.only_vae):
         ap.error("--dump-outputs records the headline step on device-resident batches: not with --host-input / --only-vae")
+    if not a.full:
+        a.no_full_depth = a.no_roofline = a.no_second_cell = a.no_vae = a.no_configs4 = a.no_cpu_baseline = True
     return a
 
 
@@ -1259,7 +1270,7 @@ def main():
             vae = None
 
     # configs[4] (polymers, H = 600, depth 30) next to the headline row, so that its numbers are timed by whoever runs the
-    # default command: fp32 and the bf16 leg, a few steps each on a pool of two batches; skipped, with the reason in the
+    # --full command: fp32 and the bf16 leg, a few steps each on a pool of two batches; skipped, with the reason in the
     # line, once the run is past its time budget
     if a.config == 1 and world == 1 and not a.no_configs4 and not a.host_input and a.rnn is None:
         result["configs4"] = configs4_leg(a, lib, dev)

@@ -24,7 +24,7 @@ def test_bench_with_two_ranks_prints_one_line_through_its_own_launcher(tmp_path)
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "6",
-           "--no-cpu-baseline", "--no-configs4"]
+           "--full", "--no-cpu-baseline", "--no-configs4"]
     err = tmp_path / "bench_two_ranks.log"
     with open(err, "w") as ef:
         p = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=ef, timeout=480)

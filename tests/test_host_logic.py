@@ -304,3 +304,18 @@ def test_bench_dump_outputs_are_float_bounded_and_reproducible(tmp_path):
     with pytest.raises(SystemExit):
         bench.parse_args(["--steps", "0"])
     assert bench.parse_args(["--steps", "7", "--dump-outputs", "d"]).steps == 7
+
+
+def test_bench_plain_run_measures_the_headline_row_alone():
+    """``bench.py`` without ``--full`` skips every leg beside the headline row (the pass without the fixed-point hint, the
+    roofline pass, the other message function / the bf16 leg, the VAE row, the configs[4] leg, the CPU baselines);
+    ``--full`` runs them, and each of its ``--no-*`` options still skips its own leg."""
+    import bench
+    legs = ("no_full_depth", "no_roofline", "no_second_cell", "no_vae", "no_configs4", "no_cpu_baseline")
+    plain = bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "3"])
+    assert not plain.full and all(getattr(plain, k) for k in legs)
+    assert (plain.steps, plain.warmup, plain.gpus) == (5, 3, 1)
+    full = bench.parse_args(["--full"])
+    assert full.full and not any(getattr(full, k) for k in legs)
+    some = bench.parse_args(["--full", "--no-vae", "--no-configs4"])
+    assert some.no_vae and some.no_configs4 and not some.no_second_cell and not some.no_cpu_baseline

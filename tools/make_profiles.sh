@@ -11,8 +11,8 @@ cd /tmp && export TMPDIR=/tmp
 B="$ROOT/bench.py"
 QUICK="--no-vae --no-cpu-baseline --no-second-cell --no-full-depth --no-roofline --no-configs4 --steps 20"
 
-python3 $B > $OUT/bench_default.json 2> $OUT/bench_default.log
-python3 $B --config 4 --no-cpu-baseline > $OUT/bench_config4.json 2> $OUT/bench_config4.log
+python3 $B --full > $OUT/bench_default.json 2> $OUT/bench_default.log
+python3 $B --config 4 --full --no-cpu-baseline > $OUT/bench_config4.json 2> $OUT/bench_config4.log
 
 for C in GRU LSTM; do
   rm -rf /tmp/prof_enc_$C

@@ -1,7 +1,7 @@
 #!/bin/bash
 # rehearsal of bench.py's N > 1 code path on a ONE-GPU box through bench.py's own launcher: two ranks, both on cuda:0,
 # gloo collectives (dev probe; the command VERDICT r3 names)
-ARGS="--gpus 2 --backend gloo --steps 6 --warmup 3 --no-cpu-baseline --no-roofline --no-full-depth --no-second-cell"
+ARGS="--gpus 2 --backend gloo --steps 6 --warmup 3 --full --no-cpu-baseline --no-roofline --no-full-depth --no-second-cell"
 GGPM_BENCH_ONE_DEVICE=1 GGPM_LAUNCH_TIMEOUT=280 python -u bench.py $ARGS > gpurun_out/b2_r0.json 2> gpurun_out/b2_r0.log
 echo "launcher exit $?"
 tail -3 gpurun_out/b2_r0.log
