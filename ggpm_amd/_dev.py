@@ -24,6 +24,10 @@ TREE_WGRADS_ASIDE = True   # ... and whose parameter gradients are formed on the
 ENC_NARROW = True          # the encoder's levels take two row tiles per workgroup while they run beside the atom-level chain
                            # ("fwd" / "bwd": in that direction only)
 
+# ---- forward-only forms (fused.py)
+FORWARD_ONLY = True        # a call autograd will not record (grad mode off, or nothing it reads requires grad) runs the
+                           # forward-only form: no stashes, no backward-only layout (False: the training forward, for A/B)
+
 # ---- gradients (functional.py, parallel.py, optim.py)
 DEFER_EARLY = True         # deferred weight-gradient contractions start beside the atom level's backward (second stream)
 INDEX_MEMO = True          # CSRs / transposes / masks derived from RESIDENT index tensors are remembered on them

@@ -61,6 +61,8 @@ SIGNATURES = {
     "ggpm_decode_steps_forward_async": (I, [P, P, P, P, P, P, P, P, P, c_size_t, P, P, P]),
     "ggpm_decode_steps_backward_async": (I, [P, P, P, P, P, P, P, P, c_size_t, P, P, P, P, c_size_t, P, P, P, c_size_t, P, P]),
     "ggpm_decode_join": (I, []),
+    "ggpm_decode_steps_infer": (I, [P, P, P, P, P, P, P, P, P, P, P, P]),
+    "ggpm_decode_steps_infer_async": (I, [P, P, P, P, P, P, P, P, P, P, P, P]),
     "ggpm_lstm_pack_floats": (c_size_t, [I]),
     "ggpm_lstm_forward": (I, [I, I, I, P, P, P, P, P, I, P, I, P, I, P, I, P, P, P, P, P, P, P, P, P, P, P, I, P, P]),
     "ggpm_lstm_backward_workspace_bytes": (c_size_t, [I, I, I]),
@@ -89,10 +91,14 @@ SIGNATURES = {
     "ggpm_encoder_saved_bytes": (c_size_t, [P]),
     "ggpm_encoder_work_bytes": (c_size_t, [P]),
     "ggpm_encoder_forward": (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, c_size_t, P, P, P, P, P, P]),
+    "ggpm_encoder_infer_bytes": (c_size_t, [P]),
+    "ggpm_encoder_infer": (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, c_size_t, P, P, P, P, P, P]),
     "ggpm_encoder_backward": (I, [P, P, P, P, P, c_size_t, P, P, P, P, P, P, P, P, P, c_size_t, I, P, P]),
     "ggpm_tree_level_saved_floats": (c_size_t, [P]),
     "ggpm_tree_level_work_bytes": (c_size_t, [P]),
     "ggpm_tree_level_forward": (I, [P, P, c_size_t, P, P]),
+    "ggpm_tree_level_infer_floats": (c_size_t, [P]),
+    "ggpm_tree_level_infer": (I, [P, P, c_size_t, P, P]),
     "ggpm_tree_level_backward": (I, [P, P, P, P, P, P, c_size_t, P, P]),
     "ggpm_linear_wgrads_batch": (I, [I, P, P, c_size_t, P, P]),
     "ggpm_timing_enable": (I, [I]),

@@ -34,7 +34,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from . import _dev, _lib
+from . import _dev, _lib, fused
 from . import functional as F_
 
 
@@ -461,78 +461,99 @@ def _vp(addr: int) -> ctypes.c_void_p:
     return ctypes.c_void_p(addr)
 
 
+def _full_level(plan: AtomPlan, cell: str, depth: int, H: int, Fdim: int, I: int, fn_all, hmess, drop, params, infer: bool):
+    """The forward of _AtomDecode -> (pooled, cand, what the backward reads or None, device tables).  ``infer``: the
+    forward-only form -- every step's depth loop in two ping-pong slots, its final state written to one of two level-wide
+    buffers (ggpm_level_opts.h_out), no stashes; the same launches otherwise, so the same outputs bit for bit."""
+    lib = _lib.load()
+    dev = hmess.device
+    D = plan.to_device(dev)
+    ptr, P = D["ptr"], F_._p
+    Hp = F_.padded_hidden(H)
+    E1, T = plan.E1, plan.T
+    f32 = dict(dtype=torch.float32, device=dev)
+    lstm = cell == "LSTM"
+    G = 4 if lstm else 3
+    if lstm:
+        Wi, bi, Wo_g, bo_g, Wu, bu_g, Wf, bf, Wout, bout = params
+        gates = ((Wi, bi), (Wo_g, bo_g), (Wu, bu_g), (Wf, bf))
+    else:
+        Wz, bz, Wr, Ur, bu, Wh, bh, Wout, bout = params
+        gates = ((Wz, bz), (Wr, None), (Wh, bh))
+    # hoisted gate input projections of ALL bond messages (step and depth invariant)
+    X = torch.empty(G, E1, Hp, **f32)
+    for k, (W, b) in enumerate(gates):
+        F_.gemm(0, 1, E1, H, I, hmess, F_._ld(hmess), W, W.stride(0), X[k], Hp, Hp, bias=b)
+    if infer:
+        Hs, Qs = torch.empty(2, E1, Hp, **f32), torch.empty(2, E1, Hp, **f32)
+        Cs = torch.empty(2, E1, Hp, **f32) if lstm else None
+        hbuf = torch.empty(2, E1, Hp, **f32)
+        cbuf = torch.empty(2, E1, Hp, **f32) if lstm else None
+    else:
+        Hs = torch.empty(T, depth + 1, E1, Hp, **f32)
+        Cs = torch.empty(T, depth + 1, E1, Hp, **f32) if lstm else None
+        Qs = torch.empty(T, depth, E1, Hp, **f32)
+        St = torch.empty(T, 5, depth, E1, Hp, **f32)
+    zero = torch.zeros(E1, Hp, **f32)
+    ns_tot, n_inst = plan.aoff[-1], plan.ioff[-1]
+    NODE = torch.empty(ns_tot, Hp, **f32)
+    NEI = torch.empty(ns_tot, Hp, **f32)
+    pooled = torch.empty(n_inst, Hp, **f32)
+    cand = torch.zeros(max(plan.n_cand, 1), Hp, **f32)
+    wpack = torch.empty(int(lib.ggpm_lstm_pack_floats(H) if lstm else lib.ggpm_gru_pack_floats(H)), **f32)
+    s = F_._stream()
+    frz = D["frozen"]
+    ldF, ldwo = F_._ld(fn_all), Wout.stride(0)
+    h_prev, c_prev = zero, zero
+    for t in range(T):
+        a0, a1, i0, i1 = plan.aoff[t], plan.aoff[t + 1], plan.ioff[t], plan.ioff[t + 1]
+        ns, ni = a1 - a0, i1 - i0
+        if infer:
+            Hs_t, Qs_t, Cs_t, st = Hs, Qs, Cs, (None,) * 5
+            opts = ctypes.byref(F_.LevelOpts(h_out=hbuf[t & 1].data_ptr(),
+                                             c_out=cbuf[t & 1].data_ptr() if lstm else None))
+        else:
+            Hs_t, Qs_t, Cs_t, st, opts = Hs[t], Qs[t], Cs[t] if lstm else None, St[t], None
+        if lstm:
+            _lib.check(lib.ggpm_lstm_sparse_forward(
+                E1, H, depth, P(h_prev), P(c_prev), P(frz[t]), P(X[0]), P(X[1]), P(X[2]), P(X[3]), P(Wi[:, I:]),
+                Wi.stride(0), P(Wo_g[:, I:]), Wo_g.stride(0), P(Wu[:, I:]), Wu.stride(0), P(Wf[:, I:]), Wf.stride(0),
+                _vp(ptr[("pred_rp", t)]), _vp(ptr[("pred_col", t)]), P(Hs_t), P(Cs_t), P(Qs_t), P(st[0]), P(st[1]),
+                P(st[2]), P(st[3]), P(st[4]), P(wpack), int(not infer), opts, s), "lstm_sparse_forward")
+            c_prev = cbuf[t & 1] if infer else Cs[t, depth]
+        else:
+            _lib.check(lib.ggpm_gru_sparse_forward(
+                E1, H, depth, P(h_prev), P(frz[t]), P(X[0]), P(X[1]), P(X[2]), P(Wz[:, I:]), Wz.stride(0), P(Ur),
+                Ur.stride(0), P(bu), P(Wh[:, I:]), Wh.stride(0), _vp(ptr[("pred_rp", t)]), _vp(ptr[("pred_col", t)]),
+                P(Hs_t), P(Qs_t), P(st[0]), P(st[1]), P(st[2]), P(st[3]), P(st[4]), P(wpack), int(not infer), opts, s),
+                "gru_sparse_forward")
+        h_prev = hbuf[t & 1] if infer else Hs[t, depth]
+        nei, node = NEI[a0:a1], NODE[a0:a1]
+        _lib.check(lib.ggpm_segment_sum(P(h_prev), Hp, _vp(ptr[("agr_rp", t)]), _vp(ptr[("agr_col", t)]), ns, H,
+                                        P(nei), Hp, 0, Hp, s), "segment_sum")
+        F_.gemm_ksegments(1, ns, H, [fn_all[a0:a1], nei], [ldF, Hp], [Wout, Wout[:, Fdim:]], [ldwo, ldwo], [Fdim, H],
+                          node, Hp, Hp, bias=bout, act=F_.ACT_RELU)
+        if drop is not None:
+            _lib.check(lib.ggpm_dropout(P(node), ns, H, Hp, drop[0], drop[1], drop[2], t, s), "dropout")
+        _lib.check(lib.ggpm_segment_sum(P(node), Hp, _vp(ptr[("pool_rp", t)]), _vp(ptr[("pool_col", t)]), ni, H,
+                                        P(pooled[i0:i1]), Hp, 0, Hp, s), "segment_sum")
+        for j, (row0, n) in enumerate(plan.step_cands[t]):
+            _lib.check(lib.ggpm_gather_rows(P(node), Hp, _vp(ptr[("cand_pos", t, j)]), n, H, P(cand[row0:row0 + n]),
+                                            Hp, 0, Hp, s), "gather_rows")
+    if infer:
+        return pooled, cand, None, D
+    return pooled, cand, (fn_all, hmess, X, Hs, Qs, St, NODE, NEI, *([Cs] if lstm else [])), D
+
+
 class _AtomDecode(torch.autograd.Function):
     """(pooled cluster vectors of all visits [n_inst, Hp], attachment-candidate atom vectors [n_cand, Hp]) -- the
     full-level form: every step runs over all E1 rows of the level with a frozen mask (_dev.ATOM_COMPACT = False)."""
 
     @staticmethod
     def forward(ctx, plan: AtomPlan, cell: str, depth: int, H: int, Fdim: int, I: int, fn_all, hmess, drop, *params):
-        lib = _lib.load()
-        dev = hmess.device
-        D = plan.to_device(dev)
-        ptr, P = D["ptr"], F_._p
-        Hp = F_.padded_hidden(H)
-        E1, T = plan.E1, plan.T
-        f32 = dict(dtype=torch.float32, device=dev)
-        lstm = cell == "LSTM"
-        G = 4 if lstm else 3
-        if lstm:
-            Wi, bi, Wo_g, bo_g, Wu, bu_g, Wf, bf, Wout, bout = params
-            gates = ((Wi, bi), (Wo_g, bo_g), (Wu, bu_g), (Wf, bf))
-        else:
-            Wz, bz, Wr, Ur, bu, Wh, bh, Wout, bout = params
-            gates = ((Wz, bz), (Wr, None), (Wh, bh))
-        # hoisted gate input projections of ALL bond messages (step and depth invariant)
-        X = torch.empty(G, E1, Hp, **f32)
-        for k, (W, b) in enumerate(gates):
-            F_.gemm(0, 1, E1, H, I, hmess, F_._ld(hmess), W, W.stride(0), X[k], Hp, Hp, bias=b)
-        Hs = torch.empty(T, depth + 1, E1, Hp, **f32)
-        Cs = torch.empty(T, depth + 1, E1, Hp, **f32) if lstm else None
-        Qs = torch.empty(T, depth, E1, Hp, **f32)
-        St = torch.empty(T, 5, depth, E1, Hp, **f32)
-        zero = torch.zeros(E1, Hp, **f32)
-        ns_tot, n_inst = plan.aoff[-1], plan.ioff[-1]
-        NODE = torch.empty(ns_tot, Hp, **f32)
-        NEI = torch.empty(ns_tot, Hp, **f32)
-        pooled = torch.empty(n_inst, Hp, **f32)
-        cand = torch.zeros(max(plan.n_cand, 1), Hp, **f32)
-        wpack = torch.empty(int(lib.ggpm_lstm_pack_floats(H) if lstm else lib.ggpm_gru_pack_floats(H)), **f32)
-        s = F_._stream()
-        frz = D["frozen"]
-        ldF, ldwo = F_._ld(fn_all), Wout.stride(0)
-        h_prev, c_prev = zero, zero
-        for t in range(T):
-            a0, a1, i0, i1 = plan.aoff[t], plan.aoff[t + 1], plan.ioff[t], plan.ioff[t + 1]
-            ns, ni = a1 - a0, i1 - i0
-            st = St[t]
-            if lstm:
-                _lib.check(lib.ggpm_lstm_sparse_forward(
-                    E1, H, depth, P(h_prev), P(c_prev), P(frz[t]), P(X[0]), P(X[1]), P(X[2]), P(X[3]), P(Wi[:, I:]),
-                    Wi.stride(0), P(Wo_g[:, I:]), Wo_g.stride(0), P(Wu[:, I:]), Wu.stride(0), P(Wf[:, I:]), Wf.stride(0),
-                    _vp(ptr[("pred_rp", t)]), _vp(ptr[("pred_col", t)]), P(Hs[t]), P(Cs[t]), P(Qs[t]), P(st[0]), P(st[1]),
-                    P(st[2]), P(st[3]), P(st[4]), P(wpack), 1, None, s), "lstm_sparse_forward")
-                c_prev = Cs[t, depth]
-            else:
-                _lib.check(lib.ggpm_gru_sparse_forward(
-                    E1, H, depth, P(h_prev), P(frz[t]), P(X[0]), P(X[1]), P(X[2]), P(Wz[:, I:]), Wz.stride(0), P(Ur),
-                    Ur.stride(0), P(bu), P(Wh[:, I:]), Wh.stride(0), _vp(ptr[("pred_rp", t)]), _vp(ptr[("pred_col", t)]),
-                    P(Hs[t]), P(Qs[t]), P(st[0]), P(st[1]), P(st[2]), P(st[3]), P(st[4]), P(wpack), 1, None, s),
-                    "gru_sparse_forward")
-            h_prev = Hs[t, depth]
-            nei, node = NEI[a0:a1], NODE[a0:a1]
-            _lib.check(lib.ggpm_segment_sum(P(h_prev), Hp, _vp(ptr[("agr_rp", t)]), _vp(ptr[("agr_col", t)]), ns, H,
-                                            P(nei), Hp, 0, Hp, s), "segment_sum")
-            F_.gemm_ksegments(1, ns, H, [fn_all[a0:a1], nei], [ldF, Hp], [Wout, Wout[:, Fdim:]], [ldwo, ldwo], [Fdim, H],
-                              node, Hp, Hp, bias=bout, act=F_.ACT_RELU)
-            if drop is not None:
-                _lib.check(lib.ggpm_dropout(P(node), ns, H, Hp, drop[0], drop[1], drop[2], t, s), "dropout")
-            _lib.check(lib.ggpm_segment_sum(P(node), Hp, _vp(ptr[("pool_rp", t)]), _vp(ptr[("pool_col", t)]), ni, H,
-                                            P(pooled[i0:i1]), Hp, 0, Hp, s), "segment_sum")
-            for j, (row0, n) in enumerate(plan.step_cands[t]):
-                _lib.check(lib.ggpm_gather_rows(P(node), Hp, _vp(ptr[("cand_pos", t, j)]), n, H, P(cand[row0:row0 + n]),
-                                                Hp, 0, Hp, s), "gather_rows")
+        pooled, cand, saved, D = _full_level(plan, cell, depth, H, Fdim, I, fn_all, hmess, drop, params, infer=False)
         ctx.plan, ctx.meta, ctx.drop = plan, (cell, depth, H, Fdim, I), drop
-        ctx.save_for_backward(fn_all, hmess, X, Hs, Qs, St, NODE, NEI, *([Cs] if lstm else []), *params)
+        ctx.save_for_backward(*saved, *params)
         ctx.keep = D
         return pooled, cand
 
@@ -620,11 +641,17 @@ class _AtomDecodeCompact(torch.autograd.Function):
     once over the stacked stashes."""
 
     @staticmethod
-    def launch(plan: AtomPlan, cell: str, depth: int, H: int, Fdim: int, I: int, fn_all, hmess, drop, params) -> dict:
+    def launch(plan: AtomPlan, cell: str, depth: int, H: int, Fdim: int, I: int, fn_all, hmess, drop, params,
+               infer: bool = False) -> dict:
         """Everything the forward computes, issued now (no autograd node): -> state for ``forward(..., state, *params)``.
         ``HierMPNDecoder.start_atom_level`` calls this BEFORE the encoder runs and creates the node later, behind the
         encoder's: the engine then reaches this node first in the backward pass and -- its loop being issued by the worker
-        thread -- goes straight on to the encoder's backward, so that the longer chain starts first."""
+        thread -- goes straight on to the encoder's backward, so that the longer chain starts first.
+        ``infer``: the forward-only form (no backward follows; no autograd node is made): every step's depth loop runs in
+        ping-pong scratch and only the final state of its rows is kept, at its F ids (ggpm_decode_steps_infer) -- no
+        Hs_all / Qs_all / St_all; the read-out reads those rows (``_agr_f_col``).  Same launches, same outputs."""
+        if infer:
+            return _launch_infer(plan, cell, depth, H, Fdim, I, fn_all, hmess, drop, params)
         lib = _lib.load()
         dev = hmess.device
         D = plan.to_device(dev)
@@ -908,6 +935,125 @@ class _AtomDecodeCompact(torch.autograd.Function):
         return (None,) * 10 + tail()
 
 
+def _agr_f_col(plan: AtomPlan, ct: dict, depth: int, device) -> torch.Tensor:
+    """The read-out CSR's columns (``agr_col``: rows of the stacked [(depth + 1) * n_t] state blocks) as F ids, i.e. rows
+    of the forward-only form's final-state buffer, in the same order (cached per device)."""
+    key = ("agrF", torch.device(device))
+    hit = ct.get(key)
+    if hit is not None:
+        return hit
+    n = np.asarray(plan.nloc, dtype=np.int64)
+    foff = np.asarray(ct["foff"], dtype=np.int64)
+    qoff = np.concatenate([[0], np.cumsum((depth + 1) * n)])
+    h2f = np.full(int(qoff[-1]), -1, dtype=np.int64)
+    for t in range(plan.T):
+        base = qoff[t] + depth * n[t]
+        h2f[base:base + n[t]] = foff[t] + np.arange(n[t])
+    d = ct["dev"][torch.device(device)][0]
+    off, ln = ct["where"]["agr_col"]
+    col = torch.from_numpy(h2f).to(device)[d[off:off + ln].long()].to(torch.int32).contiguous()
+    ct[key] = col
+    return col
+
+
+def _launch_infer(plan: AtomPlan, cell: str, depth: int, H: int, Fdim: int, I: int, fn_all, hmess, drop, params) -> dict:
+    lib = _lib.load()
+    dev = hmess.device
+    D = plan.to_device(dev)
+    ptr, P = D["ptr"], F_._p
+    Hp = F_.padded_hidden(H)
+    E1, T = plan.E1, plan.T
+    f32 = dict(dtype=torch.float32, device=dev)
+    lstm = cell == "LSTM"
+    G = 4 if lstm else 3
+    ct, cp = plan.compact_device(depth, G, dev)
+    params = tuple(p.detach() for p in params)
+    if lstm:
+        Wi, bi, Wo_g, bo_g, Wu, bu_g, Wf, bf, Wout, bout = params
+        gates = ((Wi, bi), (Wo_g, bo_g), (Wu, bu_g), (Wf, bf))
+    else:
+        Wz, bz, Wr, Ur, bu, Wh, bh, Wout, bout = params
+        gates = ((Wz, bz), (Wr, None), (Wh, bh))
+    s = F_._stream()
+    X = torch.empty(G, E1, Hp, **f32)
+    for k, (W, b) in enumerate(gates):
+        F_.gemm(0, 1, E1, H, I, hmess, F_._ld(hmess), W, W.stride(0), X[k], Hp, Hp, bias=b)
+    foff, Ftot = ct["foff"], ct["Ftot"]
+    X_all = torch.empty(G * Ftot, Hp, **f32)
+    _lib.check(lib.ggpm_gather_rows(P(X), Hp, _vp(cp["xrows"]), G * Ftot, Hp, P(X_all), Hp, 0, 0, s), "gather_rows")
+    agr_col = _agr_f_col(plan, ct, depth, dev)
+    nmax = max(plan.nloc)
+    F_h = torch.empty(max(Ftot, 1), Hp, **f32)              # final state of every step's rows, by F id
+    F_c = torch.empty(max(Ftot, 1), Hp, **f32) if lstm else None
+    Hs, Qs = torch.empty(2 * nmax, Hp, **f32), torch.empty(2 * nmax, Hp, **f32)
+    Cs = torch.empty(2 * nmax, Hp, **f32) if lstm else None
+    wpack = torch.empty(int(lib.ggpm_lstm_pack_floats(H) if lstm else lib.ggpm_gru_pack_floats(H)), **f32)
+    hw = ((Wi, I), (Wo_g, I), (Wu, I), (Wf, I)) if lstm else ((Wz, I), (Ur, 0), (Wh, I))
+    W_arr = _lib.array_type(ctypes.c_void_p, 4)(*[w[:, c:].data_ptr() for w, c in hw])
+    ld_arr = _lib.array_type(ctypes.c_int, 4)(*[w.stride(0) for w, _ in hw])
+    deferred = False
+    if _dev.DECODE_DRIVER:
+        desc, _keep = _decode_steps(plan, D, ct, cp, H, depth, lstm)
+        fn = lib.ggpm_decode_steps_infer_async if _dev.ATOM_ASYNC else lib.ggpm_decode_steps_infer
+        _lib.check(fn(ctypes.byref(desc), W_arr, ld_arr, None if lstm else P(bu), P(X_all), P(F_h), P(F_c) if lstm else None,
+                      P(Hs), P(Cs) if lstm else None, P(Qs), P(wpack), s), "decode_steps_infer")
+        if _dev.ATOM_ASYNC:
+            deferred = True
+            _INFLIGHT.append((desc, _keep, X_all, F_h, F_c, Hs, Cs, Qs, wpack, params))
+    frz_loc = D["frozen_loc"].data_ptr()
+    for t in (() if _dev.DECODE_DRIVER else range(T)):
+        n = plan.nloc[t]
+        src = _vp(cp[("srcF", t)])
+        h_in = torch.empty(n, Hp, **f32)
+        _lib.check(lib.ggpm_gather_rows(P(F_h), Hp, src, n, Hp, P(h_in), Hp, 0, 0, s), "gather_rows")
+        x = X_all[G * foff[t]:G * foff[t + 1]].view(G, n, Hp)
+        fz, rp, col = _vp(frz_loc + plan.floc_off[t]), _vp(ptr[("lpred_rp", t)]), _vp(ptr[("lpred_col", t)])
+        opts = ctypes.byref(F_.LevelOpts(weights_packed=int(t > 0 and _dev.PACK_ONCE), h_out=F_h[foff[t]].data_ptr(),
+                                         c_out=F_c[foff[t]].data_ptr() if lstm else None))
+        if lstm:
+            c_in = torch.empty(n, Hp, **f32)
+            _lib.check(lib.ggpm_gather_rows(P(F_c), Hp, src, n, Hp, P(c_in), Hp, 0, 0, s), "gather_rows")
+            _lib.check(lib.ggpm_lstm_sparse_forward(
+                n, H, depth, P(h_in), P(c_in), fz, P(x[0]), P(x[1]), P(x[2]), P(x[3]), P(Wi[:, I:]),
+                Wi.stride(0), P(Wo_g[:, I:]), Wo_g.stride(0), P(Wu[:, I:]), Wu.stride(0), P(Wf[:, I:]), Wf.stride(0),
+                rp, col, P(Hs), P(Cs), P(Qs), None, None, None, None, None, P(wpack), 0, opts, s), "lstm_sparse_forward")
+        else:
+            _lib.check(lib.ggpm_gru_sparse_forward(
+                n, H, depth, P(h_in), fz, P(x[0]), P(x[1]), P(x[2]), P(Wz[:, I:]), Wz.stride(0), P(Ur),
+                Ur.stride(0), P(bu), P(Wh[:, I:]), Wh.stride(0), rp, col, P(Hs), P(Qs), None, None, None, None, None,
+                P(wpack), 0, opts, s), "gru_sparse_forward")
+    ns_tot, n_inst = plan.aoff[-1], plan.ioff[-1]
+    NEI = torch.empty(ns_tot, Hp, **f32)
+    NODE = torch.empty(ns_tot, Hp, **f32)
+    pooled = torch.empty(n_inst, Hp, **f32)
+    cand = torch.empty(max(plan.n_cand, 1), Hp, **f32)
+    ldF, ldwo = F_._ld(fn_all), Wout.stride(0)
+    stream_obj = torch.cuda.current_stream(dev)
+
+    def readout():
+        s_ = F_._stream()
+        _lib.check(lib.ggpm_segment_sum(P(F_h), Hp, _vp(cp["agr_rp"]), P(agr_col), ns_tot, H, P(NEI), Hp, 0, Hp, s_),
+                   "segment_sum")
+        F_.gemm_ksegments(1, ns_tot, H, [fn_all, NEI], [ldF, Hp], [Wout, Wout[:, Fdim:]], [ldwo, ldwo], [Fdim, H], NODE, Hp,
+                          Hp, bias=bout, act=F_.ACT_RELU)
+        if drop is not None:
+            _lib.check(lib.ggpm_dropout(P(NODE), ns_tot, H, Hp, drop[0], drop[1], drop[2], 0, s_), "dropout")
+        _lib.check(lib.ggpm_segment_sum(P(NODE), Hp, _vp(cp["pool_rp"]), _vp(cp["pool_col"]), n_inst, H, P(pooled), Hp, 0, Hp,
+                                        s_), "segment_sum")
+        _lib.check(lib.ggpm_gather_rows(P(NODE), Hp, _vp(cp["cand_idx"]), max(plan.n_cand, 1), H, P(cand), Hp, 0, Hp, s_),
+                   "gather_rows")
+
+    finish = None
+    if deferred:
+        def finish():
+            _join_worker("decode_join (forward-only)")
+            with torch.cuda.stream(stream_obj):
+                readout()
+    else:
+        readout()
+    return dict(pooled=pooled, cand=cand, finish=finish, keep=(D, ct, cp), lstm=lstm, saved=None, infer=True)
+
+
 def _param_grads(lstm, params, acc, dX_tot, hmess, DPRE, NEI, fn_all, H, Hp, I, Fdim, E1, ns_tot, bufs=None):
     """Parameter gradients of the atom-level decode from the summed gate-input gradients, the accumulated hidden halves
     and the stacked read-out rows (shared by both forms)."""
@@ -953,6 +1099,8 @@ def atom_decode_node(pre: dict):
     if fin is not None:
         fin()
         pre["state"]["finish"] = None
+    if pre["state"].get("infer"):          # forward-only: no node (the worker is joined above)
+        return pre["state"]["pooled"], pre["state"]["cand"]
     return _AtomDecodeCompact.apply(*pre["args"], pre["state"], *pre["params"])
 
 
@@ -983,10 +1131,25 @@ def atom_decode(plan: AtomPlan, graph_encoder, hnode_a: torch.Tensor, hmess_a: t
     args = (plan, "LSTM" if lstm else "GRU", rnn.depth, rnn.hidden_size, graph_encoder.node_fdim, rnn.input_size, fn_all,
             hmess_a, drop)
     params = params + (wo[0].weight, wo[0].bias)
+    # a call autograd will not record runs the forward-only form, which makes no node and joins the worker before the
+    # caller reads its results (``finish``): nothing is left in _PENDING / _INFLIGHT for a backward to collect
+    infer = not fused.records_grad(params + (fn_all, hmess_a))
     if prelaunch:           # issue now, create the autograd node later (atom_decode_node)
         assert fn is _AtomDecodeCompact
         with torch.no_grad():
-            return dict(args=args, params=params, state=fn.launch(*args, params))
+            return dict(args=args, params=params, state=fn.launch(*args, params, infer=infer))
+    if infer:
+        if fn is _AtomDecode:
+            pooled, cand, _, _ = _full_level(*args, params, infer=True)
+            finish = None
+        else:
+            st = fn.launch(*args, params, infer=True)
+            pooled, cand, finish = st["pooled"], st["cand"], st["finish"]
+        if defer_finish:
+            return pooled, cand, (finish or (lambda: None))
+        if finish is not None:
+            finish()
+        return pooled, cand
     pooled, cand = fn.apply(*args, *params) if fn is _AtomDecode else fn.apply(*args, None, *params)
     finish = _PENDING.pop(id(plan), None)        # set when the step loop was handed to the library's worker thread
     if defer_finish:

@@ -90,6 +90,50 @@ extern "C" int ggpm_decode_steps_forward(const ggpm_decode_steps* d, const float
     return GGPM_OK;
 }
 
+// Forward-only form: the same sparse_forward calls in the same order without stashes.  Every step runs its depth loop in
+// the ping-pong scratch Hs / Qs (/ Cs) and writes its rows' final states to F_h / F_c at its F ids (ggpm_level_opts.h_out);
+// the frozen rows of later steps are gathered from there through srcF.
+extern "C" int ggpm_decode_steps_infer(const ggpm_decode_steps* d, const float* const* W, const int* ldw, const float* bu,
+                                       const float* X_all, float* F_h, float* F_c, float* Hs, float* Cs, float* Qs,
+                                       float* wpack, ggpm_stream_t stream) {
+    GGPM_CLEAR_STALE_ERROR();
+    if (!steps_ok(d) || !W || !ldw || !X_all || !F_h || !Hs || !Qs || !wpack || (d->lstm && (!F_c || !Cs)) ||
+        (!d->lstm && !bu))
+        return GGPM_ERR_ARG;
+    const int H = d->H, Hp = ggpm_padded_hidden(H), G = d->lstm ? 4 : 3;
+    const bool fold = decode_fold();
+    for (int t = 0; t < d->T; ++t) {
+        const int n = d->n[t];
+        const Offs o = offs(d, t);
+        const float* x = X_all + (size_t)G * o.f0 * Hp;
+        const size_t xs = (size_t)n * Hp;
+        ggpm_level_opts opts = {};
+        opts.weights_packed = t > 0;
+        opts.h_out = F_h + o.f0 * Hp;
+        opts.c_out = d->lstm ? F_c + o.f0 * Hp : nullptr;
+        int rc = GGPM_OK;
+        if (fold) {
+            opts.gather_h = F_h; opts.gather_c = d->lstm ? F_c : nullptr; opts.gather_idx = d->srcF[t];
+        } else {
+            rc = ggpm_gather_rows(F_h, Hp, d->srcF[t], n, Hp, Hs, Hp, 0, 0, stream);
+            if (!rc && d->lstm) rc = ggpm_gather_rows(F_c, Hp, d->srcF[t], n, Hp, Cs, Hp, 0, 0, stream);
+            if (rc) return rc;
+        }
+        if (d->lstm) {
+            rc = ggpm_lstm_sparse_forward(n, H, d->depth, Hs, Cs, d->frozen[t], x, x + xs, x + 2 * xs, x + 3 * xs, W[0], ldw[0],
+                                          W[1], ldw[1], W[2], ldw[2], W[3], ldw[3], d->pred_rowptr[t], d->pred_col[t], Hs, Cs,
+                                          Qs, nullptr, nullptr, nullptr, nullptr, nullptr, wpack, 0, &opts, stream);
+        } else {
+            rc = ggpm_gru_sparse_forward(n, H, d->depth, Hs, d->frozen[t], x, x + xs, x + 2 * xs, W[0], ldw[0], W[1], ldw[1],
+                                         bu, W[2], ldw[2], d->pred_rowptr[t], d->pred_col[t], Hs, Qs, nullptr, nullptr,
+                                         nullptr, nullptr, nullptr, wpack, 0, &opts, stream);
+        }
+        if (rc) return rc;
+    }
+    GGPM_CHECK_LAUNCH();
+    return GGPM_OK;
+}
+
 extern "C" int ggpm_decode_steps_backward(const ggpm_decode_steps* d, const float* const* W, const int* ldw,
                                           const float* X_all, const float* Hs_all, const float* Cs_all, const float* Qs_all,
                                           const float* St_all, size_t st_stride, float* dF, float* dCF, float* dX_all,
@@ -244,6 +288,18 @@ extern "C" int ggpm_decode_steps_backward_async(const ggpm_decode_steps* d, cons
     DecodeWorker::get().post(current_device(), [=]() -> int {
         return ggpm_decode_steps_backward(d, Wc, lc, X_all, Hs_all, Cs_all, Qs_all, St_all, st_stride, dF, dCF, dX_all, DG_all,
                                           dg_stride, DQ_all, dWc, work, work_bytes, tmp, stream);
+    });
+    return GGPM_OK;
+}
+
+extern "C" int ggpm_decode_steps_infer_async(const ggpm_decode_steps* d, const float* const* W, const int* ldw, const float* bu,
+                                             const float* X_all, float* F_h, float* F_c, float* Hs, float* Cs, float* Qs,
+                                             float* wpack, ggpm_stream_t stream) {
+    if (!d || !W || !ldw) return GGPM_ERR_ARG;
+    const float* Wc[4] = {W[0], W[1], W[2], W[3]};
+    const int lc[4] = {ldw[0], ldw[1], ldw[2], ldw[3]};
+    DecodeWorker::get().post(current_device(), [=]() -> int {
+        return ggpm_decode_steps_infer(d, Wc, lc, bu, X_all, F_h, F_c, Hs, Cs, Qs, wpack, stream);
     });
     return GGPM_OK;
 }

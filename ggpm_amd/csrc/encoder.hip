@@ -44,6 +44,7 @@ struct Csr {
 
 struct LevelSaved {
     float *X, *Hs, *Cs, *Qs, *St, *wpack, *nei;
+    float* hout;          // forward-only layout: the level's result (its depth loop ping-pongs in Hs / Qs / Cs); else null
 };
 
 struct Saved {          // layout of the `saved` arena (pointers are re-derived by replaying the same takes)
@@ -119,6 +120,7 @@ void take_level(Arena& A, LevelSaved& L, int E1, int N1, int Hp, int H, int dept
 }
 
 void layout_saved(Arena& A, const Dims& d, Saved& s) {
+    s.lv[0].hout = s.lv[1].hout = s.lv[2].hout = nullptr;
     take_csr(A, s.gpred, d.E1g, d.E1g, d.E1g * d.Kgb);
     take_csr(A, s.gagr, d.N1g, d.E1g, d.N1g * d.Kga);
     take_csr(A, s.tpred, d.E1t, d.E1t, d.E1t * d.Ktb);
@@ -143,6 +145,47 @@ void layout_saved(Arena& A, const Dims& d, Saved& s) {
     take_level(A, s.lv[0], d.E1t, d.N1t, d.Hp, d.H, d.depthT, d.lstm);
     take_level(A, s.lv[1], d.E1t, d.N1t, d.Hp, d.H, d.depthT, d.lstm);
     take_level(A, s.lv[2], d.E1g, d.N1g, d.Hp, d.H, d.depthG, d.lstm);
+    s.finput_i = A.take<float>((size_t)d.N1t * d.Hep); s.pooled = A.take<float>((size_t)d.N1t * d.Hp);
+    s.hnode_i = A.take<float>((size_t)d.N1t * d.Hp); s.hmess_i = A.take<float>((size_t)d.E1t * d.ld_t);
+    s.finput_t = A.take<float>((size_t)d.N1t * d.Hep);
+    s.hnode_t = A.take<float>((size_t)d.N1t * d.Hp); s.hmess_t = A.take<float>((size_t)d.E1t * d.ld_t);
+    s.f = A.take<float>((size_t)d.B * d.Hp); s.n = A.take<float>((size_t)d.B * d.Hp);
+}
+
+// The forward-only arena (ggpm_encoder_infer): what the forward reads and nothing the backward needs -- the forward CSRs
+// without transposes or cursors, the index columns, the tree-side inputs and ONE set of depth-loop scratch (hoisted inputs,
+// ping-pong H / Q (/ C) slots, the level's result, packed weights) that the three levels use one after another on the
+// main stream; every level keeps its own aggregated `nei`.
+void take_csr_fwd(Arena& A, Csr& c, int rows, int ncols, int cap) {
+    c.rows = rows; c.ncols = ncols; c.cap = cap < 1 ? 1 : cap;
+    c.rowptr = A.take<int32_t>(rows + 1);
+    c.col = A.take<int32_t>(c.cap);
+    c.rowptrT = c.colT = c.cursor = nullptr;
+}
+
+void layout_infer(Arena& A, const Dims& d, Saved& s) {
+    s = Saved{};
+    take_csr_fwd(A, s.gpred, d.E1g, d.E1g, d.E1g * d.Kgb);
+    take_csr_fwd(A, s.gagr, d.N1g, d.E1g, d.N1g * d.Kga);
+    take_csr_fwd(A, s.tpred, d.E1t, d.E1t, d.E1t * d.Ktb);
+    take_csr_fwd(A, s.tagr, d.N1t, d.E1t, d.N1t * d.Kta);
+    take_csr_fwd(A, s.tcgr, d.N1t, d.N1g, d.N1t * d.Ktc);
+    s.src = A.take<int32_t>(d.E1t); s.attr0 = A.take<int32_t>(d.E1t);
+    s.motif_id = A.take<int32_t>(d.N1t); s.attach_id = A.take<int32_t>(d.N1t);
+    s.hnode_a = A.take<float>((size_t)d.N1g * d.ld_n);
+    s.hmess_a = A.take<float>((size_t)d.E1g * d.ld_m);
+    const size_t slot = (size_t)(d.E1g > d.E1t ? d.E1g : d.E1t) * d.Hp;
+    LevelSaved L = {};
+    L.X = A.take<float>((size_t)d.nX * slot);
+    L.Hs = A.take<float>(2 * slot);
+    L.Qs = A.take<float>(2 * slot);
+    L.Cs = d.lstm ? A.take<float>(2 * slot) : nullptr;
+    L.hout = A.take<float>(slot);
+    L.wpack = A.take<float>(d.lstm ? ggpm_lstm_pack_floats(d.H) : ggpm_gru_pack_floats(d.H));
+    for (int l = 0; l < 3; ++l) {
+        s.lv[l] = L;
+        s.lv[l].nei = A.take<float>((size_t)(l == 2 ? d.N1g : d.N1t) * d.Hp);
+    }
     s.finput_i = A.take<float>((size_t)d.N1t * d.Hep); s.pooled = A.take<float>((size_t)d.N1t * d.Hp);
     s.hnode_i = A.take<float>((size_t)d.N1t * d.Hp); s.hmess_i = A.take<float>((size_t)d.E1t * d.ld_t);
     s.finput_t = A.take<float>((size_t)d.N1t * d.Hep);
@@ -328,6 +371,9 @@ int level_forward(const Dims& d, int E1, int N1, int I, int depth, const float* 
     struct Tag { Tag(int level) { ggpm_timing_tag(3 - level); } ~Tag() { ggpm_timing_tag(0); } } tag(level);
     ggpm_level_opts o = level_opts(d);
     o.run_depth = run;
+    const bool infer = L.hout != nullptr;          // forward-only layout: no stashes, the result lands in L.hout
+    o.h_out = L.hout;
+    const float* result = infer ? L.hout : L.Hs + (size_t)depth * slot;
     if (d.lstm) {
         const float* W[4] = {P[lq(level, Q_WI)], P[lq(level, Q_WOG)], P[lq(level, Q_WU)], P[lq(level, Q_WF)]};
         const float* b[4] = {P[lq(level, Q_BI)], P[lq(level, Q_BOG)], P[lq(level, Q_BU)], P[lq(level, Q_BF)]};
@@ -336,10 +382,11 @@ int level_forward(const Dims& d, int E1, int N1, int I, int depth, const float* 
         CK(ggpm_gemm_grouped(0, 1, E1, H, I, 4, gp, s));      // the four input projections in one launch
         const size_t dsl = (size_t)depth * slot;
         CK(ggpm_lstm_forward(E1, H, depth, L.X, L.X + slot, L.X + 2 * slot, L.X + 3 * slot, W[0] + I, I + H, W[1] + I, I + H,
-                             W[2] + I, I + H, W[3] + I, I + H, pred.rowptr, pred.col, L.Hs, L.Cs, L.Qs, L.St, L.St + dsl,
-                             L.St + 2 * dsl, L.St + 3 * dsl, L.St + 4 * dsl, L.wpack, 1, &o, s));
-        CK(replicate_tail(d, E1, depth, run, level, L, s));
-        CK(ggpm_segment_sum(L.Hs + (size_t)depth * slot, Hp, agr.rowptr, agr.col, N1, H, L.nei, Hp, 0, Hp, s));
+                             W[2] + I, I + H, W[3] + I, I + H, pred.rowptr, pred.col, L.Hs, L.Cs, L.Qs,
+                             infer ? nullptr : L.St, infer ? nullptr : L.St + dsl, infer ? nullptr : L.St + 2 * dsl,
+                             infer ? nullptr : L.St + 3 * dsl, infer ? nullptr : L.St + 4 * dsl, L.wpack, infer ? 0 : 1, &o, s));
+        if (!infer) CK(replicate_tail(d, E1, depth, run, level, L, s));
+        CK(ggpm_segment_sum(result, Hp, agr.rowptr, agr.col, N1, H, L.nei, Hp, 0, Hp, s));
         return GGPM_OK;
     }
     const float *Wz = P[lp(level, L_WZ)], *Wr = P[lp(level, L_WR)], *Wh = P[lp(level, L_WH)];
@@ -350,9 +397,10 @@ int level_forward(const Dims& d, int E1, int N1, int I, int depth, const float* 
     const size_t ds = (size_t)depth * slot;
     CK(ggpm_gru_forward(E1, H, depth, L.X, L.X + slot, L.X + 2 * slot, Wz + I, I + H, P[lp(level, L_UR)], H,
                             P[lp(level, L_BU)], Wh + I, I + H, pred.rowptr, pred.col,
-                            L.Hs, L.Qs, L.St, L.St + ds, L.St + 2 * ds, L.St + 3 * ds, L.St + 4 * ds, L.wpack, 1, &o, s));
-    CK(replicate_tail(d, E1, depth, run, level, L, s));
-    CK(ggpm_segment_sum(L.Hs + (size_t)depth * slot, Hp, agr.rowptr, agr.col, N1, H, L.nei, Hp, 0, Hp, s));
+                            L.Hs, L.Qs, infer ? nullptr : L.St, infer ? nullptr : L.St + ds, infer ? nullptr : L.St + 2 * ds,
+                            infer ? nullptr : L.St + 3 * ds, infer ? nullptr : L.St + 4 * ds, L.wpack, infer ? 0 : 1, &o, s));
+    if (!infer) CK(replicate_tail(d, E1, depth, run, level, L, s));
+    CK(ggpm_segment_sum(result, Hp, agr.rowptr, agr.col, N1, H, L.nei, Hp, 0, Hp, s));
     return GGPM_OK;
 }
 
@@ -371,12 +419,23 @@ extern "C" size_t ggpm_encoder_saved_bytes(const ggpm_enc_dims* dims) {
     return A.off;
 }
 
-extern "C" int ggpm_encoder_forward(const ggpm_enc_dims* dims, float* const* params, const int64_t* tfnode,
-                                    const int64_t* tfmess, const int64_t* tagraph, const int64_t* tbgraph,
-                                    const int64_t* tcgraph, const int64_t* gfnode, const int64_t* gfmess,
-                                    const int64_t* gagraph, const int64_t* gbgraph, const int32_t* roots, void* saved,
-                                    size_t saved_bytes, float* hroot, float* hnode, float* hinter, float* hatom,
-                                    ggpm_stream_t stream, ggpm_stream_t side_stream) {
+extern "C" size_t ggpm_encoder_infer_bytes(const ggpm_enc_dims* dims) {
+    if (!dims) return 0;
+    const Dims d = make_dims(dims);
+    Arena A = {nullptr, 0, false, 0};
+    Saved s;
+    layout_infer(A, d, s);
+    return A.off;
+}
+
+// The forward of both drivers: `infer` = the forward-only form (layout_infer, no stashes, no transposes).  Every launch
+// that computes a value is the same in both forms, in the same order, so their outputs are bit-identical.
+static int encoder_forward_impl(const ggpm_enc_dims* dims, float* const* params, const int64_t* tfnode,
+                                const int64_t* tfmess, const int64_t* tagraph, const int64_t* tbgraph,
+                                const int64_t* tcgraph, const int64_t* gfnode, const int64_t* gfmess,
+                                const int64_t* gagraph, const int64_t* gbgraph, const int32_t* roots, void* saved,
+                                size_t saved_bytes, float* hroot, float* hnode, float* hinter, float* hatom,
+                                ggpm_stream_t stream, ggpm_stream_t side_stream, bool infer) {
     GGPM_CLEAR_STALE_ERROR();
     if (!dims || !params || !tfnode || !tfmess || !tagraph || !tbgraph || !tcgraph || !gfnode || !gfmess || !gagraph ||
         !gbgraph || !roots || !saved || !hroot || !hnode || !hinter || !hatom)
@@ -384,7 +443,8 @@ extern "C" int ggpm_encoder_forward(const ggpm_enc_dims* dims, float* const* par
     const Dims d = make_dims(dims);
     Arena A = {reinterpret_cast<char*>(saved), 0, false, saved_bytes};
     Saved S;
-    layout_saved(A, d, S);
+    if (infer) layout_infer(A, d, S);
+    else layout_saved(A, d, S);
     if (A.overflow) return GGPM_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     float* const* P = params;
@@ -421,7 +481,7 @@ extern "C" int ggpm_encoder_forward(const ggpm_enc_dims* dims, float* const* par
         CK(ggpm_extract_column(tfmess, d.E1t, 4, 2, S.attr0, ts));
         CK(ggpm_extract_column(tfnode, d.N1t, 2, 0, S.motif_id, ts));
         CK(ggpm_extract_column(tfnode, d.N1t, 2, 1, S.attach_id, ts));
-        {
+        if (!infer) {
             const int nio = (d.E1t > d.N1t ? d.E1t : d.N1t) + 1;
             const int n = nio > d.B + 1 ? nio : d.B + 1;
             iota_k<<<ggpm_ceil_div(n, 256), 256, 0, (hipStream_t)ts>>>(S.iota, n);
@@ -433,10 +493,9 @@ extern "C" int ggpm_encoder_forward(const ggpm_enc_dims* dims, float* const* par
         CK(drop(d, S.finput_t, d.N1t, He, d.Hep, DS_EC, ts));
         CK(ggpm_onehot(S.attr0, d.E1t, 20, S.hmess_i, d.ld_t, H, d.ld_t, ts));
         CK(ggpm_onehot(S.attr0, d.E1t, 20, S.hmess_t, d.ld_t, H, d.ld_t, ts));
-        if (side_stream) {
-            (void)hipEventRecord(ev_tree, (hipStream_t)side_stream);
-            (void)hipStreamWaitEvent((hipStream_t)side_stream, ev_atom, 0);     // the atom CSRs, for their transposes
-        }
+        if (side_stream) (void)hipEventRecord(ev_tree, (hipStream_t)side_stream);
+        if (infer) return GGPM_OK;                                              // (the transposes serve the backward only)
+        if (side_stream) (void)hipStreamWaitEvent((hipStream_t)side_stream, ev_atom, 0);     // the atom CSRs, for their transposes
         CK(transpose(S.gpred, nullptr, ts));
         CK(transpose(S.gagr, nullptr, ts));
         CK(transpose(S.tpred, nullptr, ts));
@@ -492,6 +551,26 @@ extern "C" int ggpm_encoder_forward(const ggpm_enc_dims* dims, float* const* par
     CK(linear2(d.B, H, S.f, Hp, H, S.n, Hp, H, P[P_WROOT], P[P_BROOT], GGPM_ACT_TANH, 0, hroot, Hp, stream));
     GGPM_CHECK_LAUNCH();
     return GGPM_OK;
+}
+
+extern "C" int ggpm_encoder_forward(const ggpm_enc_dims* dims, float* const* params, const int64_t* tfnode,
+                                    const int64_t* tfmess, const int64_t* tagraph, const int64_t* tbgraph,
+                                    const int64_t* tcgraph, const int64_t* gfnode, const int64_t* gfmess,
+                                    const int64_t* gagraph, const int64_t* gbgraph, const int32_t* roots, void* saved,
+                                    size_t saved_bytes, float* hroot, float* hnode, float* hinter, float* hatom,
+                                    ggpm_stream_t stream, ggpm_stream_t side_stream) {
+    return encoder_forward_impl(dims, params, tfnode, tfmess, tagraph, tbgraph, tcgraph, gfnode, gfmess, gagraph, gbgraph,
+                                roots, saved, saved_bytes, hroot, hnode, hinter, hatom, stream, side_stream, false);
+}
+
+extern "C" int ggpm_encoder_infer(const ggpm_enc_dims* dims, float* const* params, const int64_t* tfnode,
+                                  const int64_t* tfmess, const int64_t* tagraph, const int64_t* tbgraph,
+                                  const int64_t* tcgraph, const int64_t* gfnode, const int64_t* gfmess,
+                                  const int64_t* gagraph, const int64_t* gbgraph, const int32_t* roots, void* arena,
+                                  size_t arena_bytes, float* hroot, float* hnode, float* hinter, float* hatom,
+                                  ggpm_stream_t stream, ggpm_stream_t side_stream) {
+    return encoder_forward_impl(dims, params, tfnode, tfmess, tagraph, tbgraph, tcgraph, gfnode, gfmess, gagraph, gbgraph,
+                                roots, arena, arena_bytes, hroot, hnode, hinter, hatom, stream, side_stream, true);
 }
 
 namespace {

@@ -813,8 +813,9 @@ void launch_fwd(GruFwdArgs a, bool rt2, bool stash, bool with_b, double flops1, 
         set_lds(kernel, lds_a);
         kernel<<<grid_a, GGPM_NWA * 64, lds_a, s>>>(a);
     };
-    if (a.st16) {      // (training levels only: always with stashes)
-        if (rt2) go(gru_fwd_a<true, 1, 2, true>); else go(gru_fwd_a<true, 1, 1, true>);
+    if (a.st16) {      // (training levels, and the forward-only form of such a level: ggpm_level_opts.h_out)
+        if (stash) { if (rt2) go(gru_fwd_a<true, 1, 2, true>); else go(gru_fwd_a<true, 1, 1, true>); }
+        else { if (rt2) go(gru_fwd_a<false, 1, 2, true>); else go(gru_fwd_a<false, 1, 1, true>); }
     } else if (rt2) {
         if (a.bf16 == 1) { if (stash) go(gru_fwd_a<true, 1, 2>); else go(gru_fwd_a<false, 1, 2>); }
         else { if (stash) go(gru_fwd_a<true, 0, 2>); else go(gru_fwd_a<false, 0, 2>); }
@@ -959,10 +960,12 @@ static int gru_forward_impl(int E1, int H, int depth, const float* Xz, const flo
     const int tg = pick_tg(E1, Hp / 16);
     const double flops1 = 2.0 * (double)(E1 - 1) * H * H;   // algorithmic flops of ONE gate product
     static const char* const abl = ggpm_dev_env("GGPM_ABLATE");
+    // forward-only form (ggpm_level_opts.h_out): the training forward's steps and roundings, without stashes
+    const bool infer = !save_for_backward && o.h_out;
     // bf16 storage (tile_mma.h): bf16 gate products, dense, training, every stash contraction on the bf16 tall kernel
-    const bool st16 = bf16 == 1 && !frozen && save_for_backward && ggpm_bf16_storage_applies(E1, H);
+    const bool st16 = bf16 == 1 && !frozen && (save_for_backward || infer) && ggpm_bf16_storage_applies(E1, H);
     int run_depth = o.run_depth;
-    if (run_depth <= 0 || run_depth > depth || frozen || !save_for_backward) run_depth = depth;
+    if (run_depth <= 0 || run_depth > depth || frozen || !(save_for_backward || infer)) run_depth = depth;
     for (int t = 1; t <= run_depth; ++t) {
         GruFwdArgs a = {};
         a.E1 = E1; a.Hp = Hp; a.tg = tg; a.Xz = Xz; a.Xr = Xr; a.Xh = Xh;
@@ -980,6 +983,14 @@ static int gru_forward_impl(int E1, int H, int depth, const float* Xz, const flo
             a.S = ggpm_slot_ptr(Ss, t - 1, slot, st16); a.G = ggpm_slot_ptr(Gs, t - 1, slot, st16);
             a.Z = ggpm_slot_ptr(Zs, t - 1, slot, st16); a.M = ggpm_slot_ptr(Ms, t - 1, slot, st16);
             a.R = Rs + (size_t)(t - 1) * slot;
+        } else if (infer) {
+            a.Hprev = ggpm_slot_ptr(Hs, (t - 1) & 1, slot, st16); a.Hnew = ggpm_slot_ptr(Hs, t & 1, slot, st16);
+            a.Qprev = ggpm_slot_ptr(Qs, (t - 1) & 1, slot, st16); a.Qnew = ggpm_slot_ptr(Qs, t & 1, slot, st16);
+            if (t == run_depth) {          // the level's result, fp32, where the caller wants it
+                if (st16) a.Hout = o.h_out;
+                else a.Hnew = o.h_out;
+            }
+            a.S = a.G = a.Z = a.M = a.R = nullptr;
         } else {
             a.Hprev = Hs + (size_t)((t - 1) & 1) * slot; a.Hnew = Hs + (size_t)(t & 1) * slot;
             a.Qprev = Qs + (size_t)((t - 1) & 1) * slot; a.Qnew = Qs + (size_t)(t & 1) * slot;

@@ -704,7 +704,9 @@ void launch_fwd(LstmFwdArgs a, bool rt2, bool stash, bool with_b, double flops1,
         set_lds(kernel, la);
         kernel<<<grid_a, GGPM_NWA * 64, la, s>>>(a);
     };
-    if (a.st16) go(lstm_fwd_a<true, 1, 1, true>);      // (training levels only: always with stashes; bf16 mode has no two-row-tile form)
+    if (a.st16) {      // (training levels and their forward-only form, ggpm_level_opts.h_out; bf16 mode has no two-row-tile form)
+        if (stash) go(lstm_fwd_a<true, 1, 1, true>); else go(lstm_fwd_a<false, 1, 1, true>);
+    }
     else if (rt2) { if (stash) go(lstm_fwd_a<true, 0, 2>); else go(lstm_fwd_a<false, 0, 2>); }
     else if (a.bf16 == 2) { if (stash) go(lstm_fwd_a<true, 2, 1>); else go(lstm_fwd_a<false, 2, 1>); }
     else if (a.bf16 == 1) { if (stash) go(lstm_fwd_a<true, 1, 1>); else go(lstm_fwd_a<false, 1, 1>); }
@@ -820,10 +822,12 @@ static int lstm_forward_impl(int E1, int H, int depth, const float* Xi, const fl
     }
 
     const double flops1 = 2.0 * (double)(E1 - 1) * H * H;   // algorithmic flops of ONE gate product
+    // forward-only form (ggpm_level_opts.h_out): the training forward's steps and roundings, without stashes
+    const bool infer = !save_for_backward && o.h_out;
     int run_depth = o.run_depth;
-    if (run_depth <= 0 || run_depth > depth || frozen || !save_for_backward) run_depth = depth;
+    if (run_depth <= 0 || run_depth > depth || frozen || !(save_for_backward || infer)) run_depth = depth;
     // bf16 storage (tile_mma.h): bf16 gate products, dense, training, every stash contraction on the bf16 tall kernel
-    const bool st16 = bf16 == 1 && !frozen && save_for_backward && ggpm_bf16_storage_applies(E1, H);
+    const bool st16 = bf16 == 1 && !frozen && (save_for_backward || infer) && ggpm_bf16_storage_applies(E1, H);
     for (int t = 1; t <= run_depth; ++t) {
         LstmFwdArgs a = {};
         a.E1 = E1; a.Hp = Hp; a.tg = tg; a.Xi = Xi; a.Xo = Xo; a.Xu = Xu; a.Xf = Xf;
@@ -840,6 +844,16 @@ static int lstm_forward_impl(int E1, int H, int depth, const float* Xi, const fl
             a.S = ggpm_slot_ptr(Ss, t - 1, slot, st16); a.I = ggpm_slot_ptr(Is, t - 1, slot, st16);
             a.O = ggpm_slot_ptr(Os, t - 1, slot, st16); a.U = ggpm_slot_ptr(Us, t - 1, slot, st16);
             a.F = Fs + (size_t)(t - 1) * slot;
+        } else if (infer) {
+            a.Hprev = ggpm_slot_ptr(Hs, (t - 1) & 1, slot, st16); a.Hnew = ggpm_slot_ptr(Hs, t & 1, slot, st16);
+            a.Cprev = Cs + (size_t)((t - 1) & 1) * slot; a.Cnew = Cs + (size_t)(t & 1) * slot;
+            a.Qprev = ggpm_slot_ptr(Qs, (t - 1) & 1, slot, st16); a.Qnew = ggpm_slot_ptr(Qs, t & 1, slot, st16);
+            if (t == run_depth) {          // the level's result, fp32, where the caller wants it
+                if (st16) a.Hout = o.h_out;
+                else a.Hnew = o.h_out;
+                if (o.c_out) a.Cnew = o.c_out;
+            }
+            a.S = a.I = a.O = a.U = a.F = nullptr;
         } else {
             a.Hprev = Hs + (size_t)((t - 1) & 1) * slot; a.Hnew = Hs + (size_t)(t & 1) * slot;
             a.Cprev = Cs + (size_t)((t - 1) & 1) * slot; a.Cnew = Cs + (size_t)(t & 1) * slot;

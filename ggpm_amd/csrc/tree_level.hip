@@ -47,7 +47,9 @@ struct Carve {
     }
 };
 
-void views_of(const Dims& d, float* saved, ggpm_tree_level_views& v, size_t& total) {
+// infer: the forward-only arena (ggpm_tree_level_infer) -- the depth loop in two ping-pong slots of Hs / Qs (/ Cs), no
+// stashes (St = null)
+void views_of(const Dims& d, float* saved, ggpm_tree_level_views& v, size_t& total, bool infer = false) {
     Carve c = {saved, 0, 0};
     v.finput = c.take((size_t)d.n_inst * d.Hep);
     v.hnode = c.take((size_t)d.n_inst * d.Hp);
@@ -55,10 +57,11 @@ void views_of(const Dims& d, float* saved, ggpm_tree_level_views& v, size_t& tot
     v.X = c.take((size_t)d.G * d.slot);
     v.hp = c.take(d.slot);
     v.cp = d.lstm ? c.take(d.slot) : nullptr;
-    v.Hs = c.take((size_t)(d.depth + 1) * d.slot);
-    v.Cs = d.lstm ? c.take((size_t)(d.depth + 1) * d.slot) : nullptr;
-    v.Qs = c.take((size_t)d.depth * d.slot);
-    v.St = c.take((size_t)5 * d.depth * d.slot);
+    const size_t states = infer ? 2 : d.depth + 1, qs = infer ? 2 : d.depth;
+    v.Hs = c.take(states * d.slot);
+    v.Cs = d.lstm ? c.take(states * d.slot) : nullptr;
+    v.Qs = c.take(qs * d.slot);
+    v.St = infer ? nullptr : c.take((size_t)5 * d.depth * d.slot);
     v.wpack = c.take(d.lstm ? ggpm_lstm_pack_floats(d.H) : ggpm_gru_pack_floats(d.H));
     v.nei = c.take((size_t)d.n_inst * d.Hp);
     v.node = c.take((size_t)d.n_inst * d.Hp);
@@ -95,8 +98,18 @@ extern "C" size_t ggpm_tree_level_work_bytes(const ggpm_tree_level* L) {
     return bytes + 1024;
 }
 
-extern "C" int ggpm_tree_level_forward(const ggpm_tree_level* L, float* saved, size_t saved_floats,
-                                       ggpm_tree_level_views* out, ggpm_stream_t stream) {
+extern "C" size_t ggpm_tree_level_infer_floats(const ggpm_tree_level* L) {
+    Dims d;
+    if (!dims_of(L, d)) return 0;
+    ggpm_tree_level_views v;
+    size_t total = 0;
+    views_of(d, nullptr, v, total, true);
+    return total;
+}
+
+// The forward of both drivers; `infer`: the forward-only form (same launches without the stash writes, same results).
+static int tree_level_forward_impl(const ggpm_tree_level* L, float* saved, size_t saved_floats, ggpm_tree_level_views* out,
+                                   ggpm_stream_t stream, bool infer) {
     GGPM_CLEAR_STALE_ERROR();
     Dims d;
     if (!dims_of(L, d) || !saved || !out || !L->ids || !L->mess_inst || !L->mess_pos || !L->frozen || !L->pred_rowptr ||
@@ -109,7 +122,7 @@ extern "C" int ggpm_tree_level_forward(const ggpm_tree_level* L, float* saved, s
     if (!d.lstm && (!L->Ur || !L->bu)) return GGPM_ERR_ARG;
     ggpm_tree_level_views v;
     size_t total = 0;
-    views_of(d, saved, v, total);
+    views_of(d, saved, v, total, infer);
     if (saved_floats < total) return GGPM_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const int H = d.H, Hp = d.Hp, I = d.I;
@@ -143,21 +156,23 @@ extern "C" int ggpm_tree_level_forward(const ggpm_tree_level* L, float* saved, s
                          (size_t)H * sizeof(float), (size_t)L->n_extra, hipMemcpyDeviceToDevice, s) != hipSuccess)
         return GGPM_ERR_LAUNCH;
     const size_t ds = (size_t)d.depth * d.slot;
+    float* St[5];
+    for (int k = 0; k < 5; ++k) St[k] = infer ? nullptr : v.St + k * ds;
     if (d.lstm) {
         if (hipMemsetAsync(v.cp, 0, d.slot * sizeof(float), s) != hipSuccess) return GGPM_ERR_LAUNCH;
         CK(ggpm_lstm_sparse_forward(d.Etot, H, d.depth, v.hp, v.cp, L->frozen, v.X, v.X + d.slot, v.X + 2 * d.slot,
                                     v.X + 3 * d.slot, L->gate_w[0] + I, L->ld_gate[0], L->gate_w[1] + I, L->ld_gate[1],
                                     L->gate_w[2] + I, L->ld_gate[2], L->gate_w[3] + I, L->ld_gate[3], L->pred_rowptr,
-                                    L->pred_col, v.Hs, v.Cs, v.Qs, v.St, v.St + ds, v.St + 2 * ds, v.St + 3 * ds,
-                                    v.St + 4 * ds, v.wpack, 1, nullptr, stream));
+                                    L->pred_col, v.Hs, v.Cs, v.Qs, St[0], St[1], St[2], St[3], St[4], v.wpack, infer ? 0 : 1,
+                                    nullptr, stream));
     } else {
         CK(ggpm_gru_sparse_forward(d.Etot, H, d.depth, v.hp, L->frozen, v.X, v.X + d.slot, v.X + 2 * d.slot,
                                    L->gate_w[0] + I, L->ld_gate[0], L->Ur, L->ld_ur, L->bu, L->gate_w[2] + I, L->ld_gate[2],
-                                   L->pred_rowptr, L->pred_col, v.Hs, v.Qs, v.St, v.St + ds, v.St + 2 * ds, v.St + 3 * ds,
-                                   v.St + 4 * ds, v.wpack, 1, nullptr, stream));
+                                   L->pred_rowptr, L->pred_col, v.Hs, v.Qs, St[0], St[1], St[2], St[3], St[4], v.wpack,
+                                   infer ? 0 : 1, nullptr, stream));
     }
-    // 6. read-out of every visit
-    const float* hid = v.Hs + (size_t)d.depth * d.slot;
+    // 6. read-out of every visit (forward-only form: the final state sits in ping-pong slot depth & 1)
+    const float* hid = v.Hs + (size_t)(infer ? (d.depth & 1) : d.depth) * d.slot;
     CK(ggpm_segment_sum(hid, Hp, L->in_rowptr, L->in_col, d.n_inst, H, v.nei, Hp, 0, Hp, stream));
     {
         const float* A[2] = {v.hnode, v.nei};
@@ -169,6 +184,16 @@ extern "C" int ggpm_tree_level_forward(const ggpm_tree_level* L, float* saved, s
     *out = v;
     GGPM_CHECK_LAUNCH();
     return GGPM_OK;
+}
+
+extern "C" int ggpm_tree_level_forward(const ggpm_tree_level* L, float* saved, size_t saved_floats,
+                                       ggpm_tree_level_views* out, ggpm_stream_t stream) {
+    return tree_level_forward_impl(L, saved, saved_floats, out, stream, false);
+}
+
+extern "C" int ggpm_tree_level_infer(const ggpm_tree_level* L, float* arena, size_t arena_floats, ggpm_tree_level_views* out,
+                                     ggpm_stream_t stream) {
+    return tree_level_forward_impl(L, arena, arena_floats, out, stream, true);
 }
 
 // `side_stream` (nullable): the level's PARAMETER gradients -- the hidden-half contractions over the stashes, the input

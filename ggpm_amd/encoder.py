@@ -49,7 +49,8 @@ class _PinnedRing:
         if self.events[k] is not None:
             self.events[k].synchronize()          # slot reuse: its previous copy must have been consumed
         if self.bufs[k] is None or self.bufs[k].numel() < n:
-            self.bufs[k] = torch.empty(max(n, 64), dtype=torch.int32).pin_memory()
+            with torch.inference_mode(False):          # (a buffer made under inference_mode could not be refilled outside it)
+                self.bufs[k] = torch.empty(max(n, 64), dtype=torch.int32).pin_memory()
         self.bufs[k][:n] = torch.as_tensor(values, dtype=torch.int32)
         out = torch.empty(n, dtype=torch.int32, device=device)
         out.copy_(self.bufs[k][:n], non_blocking=True)

@@ -17,6 +17,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import _dev, _lib
+from .nnutils import version_of
 from .parallel import grad_view
 
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3
@@ -170,12 +171,14 @@ def _memo_get(t: torch.Tensor, slot: str, key):
     m = getattr(t, slot, None)
     # `_version` counts in-place writes: a resident index tensor that is refilled (``t.copy_(next_batch)``) must not
     # be served the structures of its old contents
-    return m[2] if m is not None and m[0] == key and m[1] == t._version else None
+    return m[2] if m is not None and m[0] == key and m[1] == version_of(t) else None
 
 
 def _memo_put(t: torch.Tensor, slot: str, key, value):
+    if torch.is_inference_mode_enabled() and not t.is_inference():
+        return value        # (structures made under inference_mode must not outlive it on a tensor that training reuses)
     try:
-        setattr(t, slot, (key, t._version, value))
+        setattr(t, slot, (key, version_of(t), value))
     except AttributeError:
         pass
     return value
@@ -255,7 +258,8 @@ class LevelOpts(ctypes.Structure):
                 ("defer_stash", ctypes.c_void_p * 4), ("gather_h", ctypes.c_void_p), ("gather_c", ctypes.c_void_p),
                 ("gather_idx", ctypes.c_void_p), ("scatter_h", ctypes.c_void_p), ("scatter_c", ctypes.c_void_p),
                 ("scatter_idx", ctypes.c_void_p), ("skip_x_sums", ctypes.c_int), ("run_depth", ctypes.c_int),
-                ("lo", ctypes.c_int), ("skip_bias_u", ctypes.c_int), ("skip_sparse_wgrads", ctypes.c_int)]
+                ("lo", ctypes.c_int), ("skip_bias_u", ctypes.c_int), ("skip_sparse_wgrads", ctypes.c_int),
+                ("h_out", ctypes.c_void_p), ("c_out", ctypes.c_void_p)]
 
 
 _GATE_OPTS = {dt: LevelOpts(gate_dtype=dt) for dt in (1, 2, 3)}
@@ -965,7 +969,7 @@ def _scatter_rows(full_rows: int, sub: torch.Tensor, index: torch.Tensor) -> tor
 
 def _sparse_structure(E1: int, submess: torch.Tensor, bgraph_sub: torch.Tensor):
     """(frozen mask [E1] uint8, predecessor CSR over all E1 rows) of a sparse_forward call, remembered on ``bgraph_sub``."""
-    key = (E1, submess.data_ptr(), submess.numel(), submess._version)
+    key = (E1, submess.data_ptr(), submess.numel(), version_of(submess))
     hit = _memo_get(bgraph_sub, "_ggpm_sparse", key)
     if hit is not None:
         return hit

@@ -181,8 +181,42 @@ class _HierEncoder(torch.autograd.Function):
         return (None, None, None, None, None, *grads)
 
 
+def _encoder_infer(dims: EncDims, tree_tensors, graph_tensors, roots, params):
+    """The forward-only form (ggpm_encoder_infer): the same outputs as _HierEncoder.forward, bit for bit, from an arena of
+    ggpm_encoder_infer_bytes -- no stashes, no transposed CSRs -- that is free again as soon as the call returns."""
+    lib = _lib.load()
+    dev = params[0].device
+    tfnode, tfmess, tagraph, tbgraph, tcgraph = [t.contiguous() for t in tree_tensors[:5]]
+    gfnode, gfmess, gagraph, gbgraph = [t.contiguous() for t in graph_tensors[:4]]
+    Hp = F_.padded_hidden(dims.H)
+    arena_bytes = int(lib.ggpm_encoder_infer_bytes(ctypes.byref(dims)))
+    step = 1 << 24            # (a twentieth of the training arena: 16 MiB steps keep the cached-block reuse of _arena_size)
+    arena = torch.empty((arena_bytes + step - 1) // step * step, dtype=torch.uint8, device=dev)
+    out = torch.empty(dims.B + 2 * dims.N1t + dims.N1g, Hp, dtype=torch.float32, device=dev)
+    hroot, hnode, hinter, hatom = out.split([dims.B, dims.N1t, dims.N1t, dims.N1g])
+    params = [p.detach() if p.is_contiguous() else p.detach().contiguous() for p in params]
+    side, side_p = _side_ptr(dev)
+    if side is not None:
+        arena.record_stream(side)
+        roots.record_stream(side)
+    dims.prefer_narrow = int(bool(NARROW[0]) and _dev.ENC_NARROW in (True, "fwd"))
+    P = F_._p
+    _lib.check(lib.ggpm_encoder_infer(ctypes.byref(dims), _ptr_array(params), P(tfnode), P(tfmess), P(tagraph), P(tbgraph),
+                                      P(tcgraph), P(gfnode), P(gfmess), P(gagraph), P(gbgraph), P(roots), P(arena),
+                                      arena_bytes, P(hroot), P(hnode), P(hinter), P(hatom), F_._stream(), side_p),
+               "encoder_infer")
+    return hroot, hnode, hinter, hatom
+
+
+def records_grad(params) -> bool:
+    """True when autograd will record a call that reads ``params`` (its other inputs are index tensors): grad mode on
+    and some parameter requires grad.  False selects the forward-only forms, unless _dev.FORWARD_ONLY is off."""
+    return not _dev.FORWARD_ONLY or (torch.is_grad_enabled() and any(p.requires_grad for p in params))
+
+
 def hier_encoder(encoder, tree_tensors, graph_tensors, roots):
-    """-> (hroot, hnode, hinter, hatom) as [rows, Hp] tensors; ``encoder`` is a HierMPNEncoder with GRU levels."""
+    """-> (hroot, hnode, hinter, hatom) as [rows, Hp] tensors; ``encoder`` is a HierMPNEncoder with GRU levels.  A call
+    autograd will not record runs the forward-only driver (``records_grad``)."""
     from .rnn import LSTM
     lstm = isinstance(encoder.graph_encoder.rnn, LSTM)
     params = getattr(encoder, "_fused_params", None)
@@ -200,4 +234,6 @@ def hier_encoder(encoder, tree_tensors, graph_tensors, roots):
     if encoder.training and encoder.dropout > 0:      # nn.Dropout semantics: active in training mode only
         seed = getattr(encoder, "_dropout_seed", None) or _dropout_seed()      # (tests pin the seed)
         dims.dropout, dims.seed_lo, dims.seed_hi = float(encoder.dropout), seed[0], seed[1]
+    if not records_grad(params):
+        return _encoder_infer(dims, tree_tensors, graph_tensors, roots, params)
     return _HierEncoder.apply(dims, tree_tensors, graph_tensors, roots, getattr(encoder, "_grad_sink", None), *params)

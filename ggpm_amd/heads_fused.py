@@ -22,7 +22,7 @@ from typing import List, Optional
 import torch
 import torch.nn.functional as TF
 
-from . import _lib
+from . import _lib, fused
 from . import functional as F_
 
 MAX_POS = 20
@@ -97,87 +97,98 @@ class AssmBlock:
         self.k, self.base, self.n, self.icls32, self.nth, self.dest = k, base, n, icls32, nth, dest
 
 
+def _heads_forward(heads, spec: dict, z, topo_x, cls_x, cand, infer: bool):
+    """The forward of _Heads -> (loss, accuracies, saved dict, dims); ``infer``: its forward-only form -> (loss,
+    accuracies): the same launches without the loss gradients (the loss kernels' gradient outputs are nullable) and
+    nothing kept."""
+    lib = _lib.load()
+    H, L, B = heads.hidden_size, heads.latent_size, z.shape[0]
+    dev = z.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    Lp = (L + 3) // 4 * 4
+    zc = z if z.stride(1) == 1 else z.contiguous()
+    saved = {}
+    # ---- topology head: BCE over every (step, node) visit
+    cxt_t = _gather(zc, spec["topo_idx"], L, Lp)
+    h_t, s_t = _mlp_forward(heads.topoNN, topo_x, cxt_t, H, L)
+    x_t = s_t[:, 0].contiguous()
+    loss_t = torch.empty(1, **f32)
+    dx_t = None if infer else torch.empty_like(x_t)       # (forward-only: losses and accuracies, no gradients)
+    _lib.check(lib.ggpm_bce_logits(F_._p(x_t), F_._p(spec["topo_y"]), x_t.numel(), F_._p(loss_t), F_._p(dx_t),
+                                   F_._p(torch.empty_like(x_t)), F_._stream()), "bce_logits")
+    # ---- motif-class and attachment-class heads: cross entropy over every cluster prediction (the roots first)
+    n_c = cls_x.shape[0]
+    cxt_c = _gather(zc, spec["cls_idx"], L, Lp)
+    h_c, s_c = _mlp_forward(heads.clsNN, cls_x, cxt_c, H, L)
+    h_i, s_i = _mlp_forward(heads.iclsNN, cls_x, cxt_c, H, L)
+
+    def ce(s, N, labels, mask=None, mask_row=None):
+        M = s.shape[0]
+        loss, arg = torch.empty(1, **f32), torch.empty(M, dtype=torch.int32, device=dev)
+        d = None if infer else torch.empty(M, F_._ld(s), **f32)
+        if d is not None and d.shape[1] > N:
+            d[:, N:].zero_()
+        _lib.check(lib.ggpm_softmax_ce(F_._p(s), F_._ld(s), M, N, F_._p(mask), 0 if mask is None else F_._ld(mask),
+                                       F_._p(mask_row), F_._p(labels), F_._p(loss), F_._p(d), 0 if d is None else d.shape[1], F_._p(arg),
+                                       F_._p(torch.empty(M, **f32)), F_._stream()), "softmax_ce")
+        return loss, d, arg
+
+    loss_c, d_c, arg_c = ce(s_c, heads.clsNN[3].weight.shape[0], spec["cls_lab"])
+    vocab = heads.vocab
+    mask = vocab.mask_on(dev) if hasattr(vocab, "mask_on") else vocab.mask.to(dev)
+    loss_i, d_i, arg_i = ce(s_i, heads.iclsNN[3].weight.shape[0], spec["icls_lab"], mask, spec["cls_lab"])
+    loss = loss_t + (loss_c + loss_i)
+    # ---- attachment head: enum_attach over all candidates, W_assm, dot with the latent vector, cross entropy (label 0)
+    blocks: List[AssmBlock] = spec["assm_blocks"]
+    P, C = spec["n_assm"], spec["max_cls_size"]
+    scores = None
+    if P > 0:
+        Hp, He = F_.padded_hidden(H), heads.embed_size
+        l1 = heads.matchNN[0]
+        ldw = l1.weight.stride(0)
+        buf = torch.zeros(P * C, Hp, **f32)
+        keep = []
+        for b in blocks:
+            rows = cand[b.base:b.base + b.n]
+            emb = _gather(heads.E_assm[0].weight, b.icls32, He, F_.padded_hidden(He))
+            order = TF.one_hot(b.nth, MAX_POS).to(torch.float32)
+            v = torch.empty(b.n, Hp, **f32)
+            F_.gemm_ksegments(1, b.n, H, [rows, emb, order], [F_._ld(rows), F_._ld(emb), MAX_POS],
+                              [l1.weight, l1.weight[:, H:], l1.weight[:, H + He:]], [ldw] * 3, [H, He, MAX_POS], v, Hp, Hp,
+                              bias=l1.bias, act=RELU)
+            vs = v if b.k == 1 else v.view(-1, b.k, Hp).sum(dim=1)
+            buf.index_copy_(0, b.dest, vs)
+            keep.append((rows, emb, order, v))
+        wa = heads.W_assm
+        ldp = F_.padded_hidden(L)
+        proj = torch.empty(P * C, ldp, **f32)
+        F_.gemm(0, 1, P * C, L, H, buf, Hp, wa.weight, wa.weight.stride(0), proj, ldp, ldp, bias=wa.bias)
+        cxt_a = _gather(zc, spec["assm_idx"], L, Lp)
+        scores = (proj[:, :L] * cxt_a[:, :L]).sum(dim=-1).view(P, C).contiguous()
+        loss_a, d_a, _ = ce(scores, C, spec["assm_lab"])
+        loss = loss + loss_a
+        if not infer:
+            saved.update(buf=buf, keep=keep, proj=proj, cxt_a=cxt_a, d_a=d_a)
+    acc = F_.head_accuracies(arg_c, spec["cls_lab_raw"], arg_i, spec["icls_lab_raw"], x_t, spec["topo_lab_raw"], scores)
+    if infer:
+        return loss.reshape(()), acc
+    saved.update(cxt_t=cxt_t, h_t=h_t, dx_t=dx_t, ld_st=s_t.shape[1], cxt_c=cxt_c, h_c=h_c, h_i=h_i, d_c=d_c, d_i=d_i,
+                 topo_x=topo_x, cls_x=cls_x, cand=cand)
+    return loss.reshape(()), acc, saved, (H, L, B, P, C)
+
+
 class _Heads(torch.autograd.Function):
     @staticmethod
     def forward(ctx, heads, spec: dict, z, topo_x, cls_x, cand, *params):
         """heads: the ScoreHeads module (topoNN, clsNN, iclsNN, matchNN, W_assm, E_assm); spec: index tensors of the batch;
         `params`: the same parameters once more, so that autograd knows the node depends on them (their gradients go
         through the deferred queue, never through the return value)."""
-        lib = _lib.load()
-        H, L, B = heads.hidden_size, heads.latent_size, z.shape[0]
-        dev = z.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        Lp = (L + 3) // 4 * 4
-        zc = z if z.stride(1) == 1 else z.contiguous()
-        saved = {}
-        # ---- topology head: BCE over every (step, node) visit
-        cxt_t = _gather(zc, spec["topo_idx"], L, Lp)
-        h_t, s_t = _mlp_forward(heads.topoNN, topo_x, cxt_t, H, L)
-        x_t = s_t[:, 0].contiguous()
-        loss_t = torch.empty(1, **f32)
-        dx_t = torch.empty_like(x_t)
-        _lib.check(lib.ggpm_bce_logits(F_._p(x_t), F_._p(spec["topo_y"]), x_t.numel(), F_._p(loss_t), F_._p(dx_t),
-                                       F_._p(torch.empty_like(x_t)), F_._stream()), "bce_logits")
-        # ---- motif-class and attachment-class heads: cross entropy over every cluster prediction (the roots first)
-        n_c = cls_x.shape[0]
-        cxt_c = _gather(zc, spec["cls_idx"], L, Lp)
-        h_c, s_c = _mlp_forward(heads.clsNN, cls_x, cxt_c, H, L)
-        h_i, s_i = _mlp_forward(heads.iclsNN, cls_x, cxt_c, H, L)
-
-        def ce(s, N, labels, mask=None, mask_row=None):
-            M = s.shape[0]
-            loss, arg = torch.empty(1, **f32), torch.empty(M, dtype=torch.int32, device=dev)
-            d = torch.empty(M, F_._ld(s), **f32)
-            if d.shape[1] > N:
-                d[:, N:].zero_()
-            _lib.check(lib.ggpm_softmax_ce(F_._p(s), F_._ld(s), M, N, F_._p(mask), 0 if mask is None else F_._ld(mask),
-                                           F_._p(mask_row), F_._p(labels), F_._p(loss), F_._p(d), d.shape[1], F_._p(arg),
-                                           F_._p(torch.empty(M, **f32)), F_._stream()), "softmax_ce")
-            return loss, d, arg
-
-        loss_c, d_c, arg_c = ce(s_c, heads.clsNN[3].weight.shape[0], spec["cls_lab"])
-        vocab = heads.vocab
-        mask = vocab.mask_on(dev) if hasattr(vocab, "mask_on") else vocab.mask.to(dev)
-        loss_i, d_i, arg_i = ce(s_i, heads.iclsNN[3].weight.shape[0], spec["icls_lab"], mask, spec["cls_lab"])
-        loss = loss_t + (loss_c + loss_i)
-        # ---- attachment head: enum_attach over all candidates, W_assm, dot with the latent vector, cross entropy (label 0)
-        blocks: List[AssmBlock] = spec["assm_blocks"]
-        P, C = spec["n_assm"], spec["max_cls_size"]
-        scores = None
-        if P > 0:
-            Hp, He = F_.padded_hidden(H), heads.embed_size
-            l1 = heads.matchNN[0]
-            ldw = l1.weight.stride(0)
-            buf = torch.zeros(P * C, Hp, **f32)
-            keep = []
-            for b in blocks:
-                rows = cand[b.base:b.base + b.n]
-                emb = _gather(heads.E_assm[0].weight, b.icls32, He, F_.padded_hidden(He))
-                order = TF.one_hot(b.nth, MAX_POS).to(torch.float32)
-                v = torch.empty(b.n, Hp, **f32)
-                F_.gemm_ksegments(1, b.n, H, [rows, emb, order], [F_._ld(rows), F_._ld(emb), MAX_POS],
-                                  [l1.weight, l1.weight[:, H:], l1.weight[:, H + He:]], [ldw] * 3, [H, He, MAX_POS], v, Hp, Hp,
-                                  bias=l1.bias, act=RELU)
-                vs = v if b.k == 1 else v.view(-1, b.k, Hp).sum(dim=1)
-                buf.index_copy_(0, b.dest, vs)
-                keep.append((rows, emb, order, v))
-            wa = heads.W_assm
-            ldp = F_.padded_hidden(L)
-            proj = torch.empty(P * C, ldp, **f32)
-            F_.gemm(0, 1, P * C, L, H, buf, Hp, wa.weight, wa.weight.stride(0), proj, ldp, ldp, bias=wa.bias)
-            cxt_a = _gather(zc, spec["assm_idx"], L, Lp)
-            scores = (proj[:, :L] * cxt_a[:, :L]).sum(dim=-1).view(P, C).contiguous()
-            loss_a, d_a, _ = ce(scores, C, spec["assm_lab"])
-            loss = loss + loss_a
-            saved.update(buf=buf, keep=keep, proj=proj, cxt_a=cxt_a, d_a=d_a)
-        acc = F_.head_accuracies(arg_c, spec["cls_lab_raw"], arg_i, spec["icls_lab_raw"], x_t, spec["topo_lab_raw"], scores)
-        saved.update(cxt_t=cxt_t, h_t=h_t, dx_t=dx_t, ld_st=s_t.shape[1], cxt_c=cxt_c, h_c=h_c, h_i=h_i, d_c=d_c, d_i=d_i,
-                     topo_x=topo_x, cls_x=cls_x, cand=cand)
+        loss, acc, saved, dims = _heads_forward(heads, spec, z, topo_x, cls_x, cand, infer=False)
         ctx.heads, ctx.spec, ctx.saved_ = heads, spec, saved
-        ctx.dims = (H, L, B, P, C)
+        ctx.dims = dims
         ctx.mark_non_differentiable(acc)
         ctx.set_materialize_grads(False)
-        return loss.reshape(()), acc
+        return loss, acc
 
     @staticmethod
     def backward(ctx, dloss, _dacc):
@@ -269,4 +280,8 @@ def heads_parameters(heads):
 
 def heads_losses(heads, spec: dict, z, topo_x, cls_x, cand):
     """-> (topo_loss + cls_loss + icls_loss + assm_loss  [sum, not yet divided by the batch size], accuracies [4])"""
-    return _Heads.apply(heads, spec, z, topo_x, cls_x, cand, *heads_parameters(heads))
+    params = heads_parameters(heads)
+    if not fused.records_grad(list(params) + [t for t in (z, topo_x, cls_x, cand) if t is not None]):
+        with torch.no_grad():
+            return _heads_forward(heads, spec, z, topo_x, cls_x, cand, infer=True)
+    return _Heads.apply(heads, spec, z, topo_x, cls_x, cand, *params)

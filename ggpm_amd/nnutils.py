@@ -56,17 +56,25 @@ def tree_chain_length(bgraph) -> int:
     return 0            # never settled: a cycle
 
 
+def version_of(t):
+    """``t._version`` (its in-place version counter), or -1 for a tensor made under torch.inference_mode(), which tracks
+    none (and which nothing outside inference mode may write in place)."""
+    if isinstance(t, torch.Tensor) and t.is_inference():
+        return -1
+    return getattr(t, "_version", None)
+
+
 def attach_hint(t: torch.Tensor, name: str, value) -> None:
     """Leave a value derived from ``t``'s CONTENTS on the tensor object, stamped with its in-place version counter."""
     setattr(t, name, value)
-    setattr(t, name + "_version", t._version)
+    setattr(t, name + "_version", version_of(t))
 
 
 def read_hint(t, name: str, default=None):
     """The value ``attach_hint`` left, unless the tensor was written in place since (a resident index tensor refilled
     with the next batch must not carry the previous batch's chain length / root ids)."""
     v = getattr(t, name, None)
-    if v is None or getattr(t, name + "_version", None) != getattr(t, "_version", None):
+    if v is None or getattr(t, name + "_version", None) != version_of(t):
         return default
     return v
 

@@ -103,14 +103,11 @@ class PropertyVAEOptimizer(nn.Module):
     def hard_optimize(self, homo_vecs, lumo_vecs, homo_targets, lumo_targets):
         return self._search("fixed", homo_vecs, lumo_vecs, homo_targets, lumo_targets)
 
-
-class HierPropertyVAEOptimizer(PropertyVAEOptimizer):
-    """The search over HierPropOptVAE's latent (reference ggpm/property_control.py:183-213)."""
-
     def optimize(self, batch):
-        """Everything the reference's ``forward`` does before ``decode``: encode, rsample without noise, the search
-        (``optimize_type``), the heads on the final latent.  -> (latent [B, 2 half], (homo_pred [B], lumo_pred [B]));
-        ``steps_taken`` / ``status`` hold the per-molecule step counts and outcomes."""
+        """Everything the reference's ``forward`` does before ``decode`` (ggpm/property_control.py:33-60 for the tree-only
+        PropOptVAE, :183-213 for HierPropOptVAE): encode, rsample without noise, the search (``optimize_type``), the heads
+        on the final latent.  -> (latent [B, 2 half], (homo_pred [B], lumo_pred [B])); ``steps_taken`` / ``status`` hold
+        the per-molecule step counts and outcomes."""
         _, _, tensors, _, homos, lumos = batch
         with torch.no_grad():
             root_vecs, _ = self.model.encode_latent(tensors, perturb=False)
@@ -118,3 +115,7 @@ class HierPropertyVAEOptimizer(PropertyVAEOptimizer):
         latent = self._get_optimize_func()(homo_vecs=root_vecs[:, :half], lumo_vecs=root_vecs[:, half:],
                                            homo_targets=homos, lumo_targets=lumos)
         return latent, self.predictions
+
+
+class HierPropertyVAEOptimizer(PropertyVAEOptimizer):
+    """The search over HierPropOptVAE's latent (reference ggpm/property_control.py:183-213)."""

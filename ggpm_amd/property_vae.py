@@ -373,6 +373,12 @@ class HierPropOptVAE(_ClipNegativeLoss, nn.Module):
         root_vecs = self.encoder.forward_padded(tree_tensors, graph_tensors)[0]
         return rsample(root_vecs, self.R_mean, self.R_var, perturb)
 
+    def predict_properties(self, batch):
+        """The property predictions the reference's ``reconstruct`` forms before it decodes (ggpm/property_vae.py:169-186):
+        encoder, the mean latent (no noise), both heads -- under no-grad, so every stage runs its forward-only form.
+        ``batch`` is a reference batch (mols, graphs, tensors, orders, homos, lumos).  -> (homo [B], lumo [B])."""
+        return _predict_properties(self, batch)
+
     def reconstruct(self, batch, args=None):
         raise NotImplementedError("HierPropOptVAE.reconstruct needs HierMPNDecoder.decode(), which needs rdkit "
                                   "chemistry and is not part of this build")
@@ -415,6 +421,14 @@ class HierPropOptVAE(_ClipNegativeLoss, nn.Module):
         return total_loss, {'Loss': total_loss.item(), 'KL': kl_div.item(), 'Recs_Loss': loss.item(),
                             'HOMO_MSE': homo_loss.item(), 'LUMO_MSE': lumo_loss.item(), 'Word': float(wacc),
                             'I-Word': float(iacc), 'Topo': float(tacc), 'Assm': float(sacc)}, bool(clipped)
+
+
+def _predict_properties(model, batch):
+    tensors = batch[2]
+    with torch.no_grad():
+        z, _ = model.encode_latent(tensors, perturb=False)
+        half = model.latent_size
+        return model.property_optim.predict(homo_vecs=z[:, :half], lumo_vecs=z[:, half:])
 
 
 def _motif_schedule(model, graphs, tensors, orders, schedule):
@@ -512,6 +526,10 @@ class PropOptVAE(_ClipNegativeLoss, nn.Module):
         """MotifEncoder + rsample: -> (latent [B, 2 half], kl)."""
         tree_tensors, _ = make_cuda(tensors)
         return rsample(self.encoder.forward_padded(tree_tensors)[0], self.R_mean, self.R_var, perturb)
+
+    def predict_properties(self, batch):
+        """As HierPropOptVAE.predict_properties, on MotifEncoder's latent: -> (homo [B], lumo [B])."""
+        return _predict_properties(self, batch)
 
     def reconstruct(self, batch, args=None):
         raise NotImplementedError("PropOptVAE.reconstruct needs MotifDecoder.decode(), which needs rdkit chemistry and is "

@@ -27,7 +27,7 @@ from typing import Optional
 
 import torch
 
-from . import _dev, _lib
+from . import _dev, _lib, fused
 from . import functional as F_
 
 MAX_POS = 20
@@ -57,80 +57,87 @@ class LevelSpec:
                 F_.csr_from_index(self.mess_inst, ncols=self.ids.numel()))
 
 
+def _composite_forward(ctx, S: LevelSpec, lstm: bool, H: int, He: int, lower, extra, emb, W, b, Wo, bo, rp, infer: bool):
+    """The forward of _TreeLevel; ``infer`` (ctx None): its forward-only form, the same launches without stashes."""
+    lib = _lib.load()
+    P, dev = F_._p, lower.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    Hp, Hep = F_.padded_hidden(H), F_.padded_hidden(He)
+    I = H + MAX_POS
+    ldm = (I + 3) // 4 * 4
+    E1, depth = S.E1, S.depth
+    Etot, ms, n_inst = E1 + S.n_extra, E1 - 1, S.ids.numel()
+    G = 4 if lstm else 3
+    s = F_._stream()
+    frozen, pred, in_csr, src_csr = S.structures()
+    # 1-2. visit vectors: relu([E[ids] | lower] W^T + b)
+    finput = torch.empty(n_inst, Hep, **f32)
+    _lib.check(lib.ggpm_gather_rows(P(emb), F_._ld(emb), P(S.ids), n_inst, He, P(finput), Hep, 0, Hep, s), "gather_rows")
+    hnode = torch.empty(n_inst, Hp, **f32)
+    ldw = W.stride(0)
+    F_.gemm_ksegments(1, n_inst, H, [finput, lower], [Hep, F_._ld(lower)], [W, W[:, He:]], [ldw, ldw], [He, H], hnode, Hp, Hp,
+                      bias=b, act=F_.ACT_RELU)
+    # 3. message inputs
+    hmess = torch.empty(ms, ldm, **f32)
+    _lib.check(lib.ggpm_gather_rows(P(hnode), Hp, P(S.mess_inst), ms, H, P(hmess), ldm, 0, 0, s), "gather_rows")
+    _lib.check(lib.ggpm_onehot(P(S.mess_pos), ms, MAX_POS, P(hmess), ldm, H, ldm, s), "onehot")
+    # 4. hoisted gate inputs, straight into the rows 1 .. E1-1 they belong to (row 0 / the extra rows: zero)
+    if lstm:
+        Wi, bi, Wog, bog, Wu, bu_, Wf, bf = rp
+        gates = ((Wi, bi), (Wog, bog), (Wu, bu_), (Wf, bf))
+    else:
+        Wz, bz, Wr, Ur, bu, Wh, bh = rp
+        gates = ((Wz, bz), (Wr, None), (Wh, bh))
+    X = torch.zeros(G, Etot, Hp, **f32)
+    for k, (Wk, bk) in enumerate(gates):
+        F_.gemm(0, 1, ms, H, I, hmess, ldm, Wk, Wk.stride(0), X[k][1:], Hp, Hp, bias=bk)
+    # 5. start state: zero, the extra (frozen) rows carry `extra`
+    hp = torch.zeros(Etot, Hp, **f32)
+    if extra is not None:
+        hp[E1:, :H] = extra
+    save = not infer            # forward-only: the depth loop in two ping-pong slots, no stashes
+    Hs = torch.empty(depth + 1 if save else 2, Etot, Hp, **f32)
+    Qs = torch.empty(depth if save else 2, Etot, Hp, **f32)
+    St = torch.empty(5, depth, Etot, Hp, **f32) if save else (None,) * 5
+    if lstm:
+        cp = torch.zeros(Etot, Hp, **f32)
+        Cs = torch.empty(depth + 1 if save else 2, Etot, Hp, **f32)
+        wpack = torch.empty(int(lib.ggpm_lstm_pack_floats(H)), **f32)
+        Wh = [w[:, I:] for w, _ in gates]
+        _lib.check(lib.ggpm_lstm_sparse_forward(
+            Etot, H, depth, P(hp), P(cp), P(frozen), P(X[0]), P(X[1]), P(X[2]), P(X[3]), P(Wh[0]), Wi.stride(0), P(Wh[1]),
+            Wog.stride(0), P(Wh[2]), Wu.stride(0), P(Wh[3]), Wf.stride(0), P(pred.rowptr), P(pred.col), P(Hs), P(Cs), P(Qs),
+            P(St[0]), P(St[1]), P(St[2]), P(St[3]), P(St[4]), P(wpack), int(save), None, s), "lstm_sparse_forward")
+    else:
+        Cs = None
+        wpack = torch.empty(int(lib.ggpm_gru_pack_floats(H)), **f32)
+        _lib.check(lib.ggpm_gru_sparse_forward(
+            Etot, H, depth, P(hp), P(frozen), P(X[0]), P(X[1]), P(X[2]), P(Wz[:, I:]), Wz.stride(0), P(Ur), Ur.stride(0),
+            P(bu), P(Wh[:, I:]), Wh.stride(0), P(pred.rowptr), P(pred.col), P(Hs), P(Qs), P(St[0]), P(St[1]), P(St[2]),
+            P(St[3]), P(St[4]), P(wpack), int(save), None, s), "gru_sparse_forward")
+    hid = Hs[depth] if save else Hs[depth & 1]
+    # 6. read-out of every visit
+    nei = torch.empty(n_inst, Hp, **f32)
+    F_._segment_sum_raw(hid, in_csr, H, nei)
+    node = torch.empty(n_inst, Hp, **f32)
+    ldo = Wo.stride(0)
+    F_.gemm_ksegments(1, n_inst, H, [hnode, nei], [Hp, Hp], [Wo, Wo[:, H:]], [ldo, ldo], [H, H], node, Hp, Hp, bias=bo,
+                      act=F_.ACT_RELU)
+    if infer:
+        return node, hid
+    ctx.S, ctx.meta = S, (lstm, H, He, extra is not None)
+    ctx.save_for_backward(lower, node)          # (an input and an output: through autograd, so that no ctx -> output cycle forms)
+    ctx.stash = (finput, hnode, hmess, X[G - 1] if lstm else X[1], Hs, Cs, Qs, St, nei)
+    ctx.prm = (emb, W, b, Wo, bo) + tuple(rp)
+    ctx.structs = (frozen, pred, in_csr, src_csr)
+    ctx.set_materialize_grads(False)            # (an unused output arrives as None, not as a zero tensor to be added)
+    return node, hid
+
+
 class _TreeLevel(torch.autograd.Function):
     @staticmethod
     def forward(ctx, S: LevelSpec, lstm: bool, H: int, He: int, lower, extra, emb, W, b, Wo, bo, *rp):
-        lib = _lib.load()
-        P, dev = F_._p, lower.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        Hp, Hep = F_.padded_hidden(H), F_.padded_hidden(He)
-        I = H + MAX_POS
-        ldm = (I + 3) // 4 * 4
-        E1, depth = S.E1, S.depth
-        Etot, ms, n_inst = E1 + S.n_extra, E1 - 1, S.ids.numel()
-        G = 4 if lstm else 3
-        s = F_._stream()
-        frozen, pred, in_csr, src_csr = S.structures()
-        # 1-2. visit vectors: relu([E[ids] | lower] W^T + b)
-        finput = torch.empty(n_inst, Hep, **f32)
-        _lib.check(lib.ggpm_gather_rows(P(emb), F_._ld(emb), P(S.ids), n_inst, He, P(finput), Hep, 0, Hep, s), "gather_rows")
-        hnode = torch.empty(n_inst, Hp, **f32)
-        ldw = W.stride(0)
-        F_.gemm_ksegments(1, n_inst, H, [finput, lower], [Hep, F_._ld(lower)], [W, W[:, He:]], [ldw, ldw], [He, H], hnode, Hp, Hp,
-                          bias=b, act=F_.ACT_RELU)
-        # 3. message inputs
-        hmess = torch.empty(ms, ldm, **f32)
-        _lib.check(lib.ggpm_gather_rows(P(hnode), Hp, P(S.mess_inst), ms, H, P(hmess), ldm, 0, 0, s), "gather_rows")
-        _lib.check(lib.ggpm_onehot(P(S.mess_pos), ms, MAX_POS, P(hmess), ldm, H, ldm, s), "onehot")
-        # 4. hoisted gate inputs, straight into the rows 1 .. E1-1 they belong to (row 0 / the extra rows: zero)
-        if lstm:
-            Wi, bi, Wog, bog, Wu, bu_, Wf, bf = rp
-            gates = ((Wi, bi), (Wog, bog), (Wu, bu_), (Wf, bf))
-        else:
-            Wz, bz, Wr, Ur, bu, Wh, bh = rp
-            gates = ((Wz, bz), (Wr, None), (Wh, bh))
-        X = torch.zeros(G, Etot, Hp, **f32)
-        for k, (Wk, bk) in enumerate(gates):
-            F_.gemm(0, 1, ms, H, I, hmess, ldm, Wk, Wk.stride(0), X[k][1:], Hp, Hp, bias=bk)
-        # 5. start state: zero, the extra (frozen) rows carry `extra`
-        hp = torch.zeros(Etot, Hp, **f32)
-        if extra is not None:
-            hp[E1:, :H] = extra
-        save = True
-        Hs = torch.empty(depth + 1, Etot, Hp, **f32)
-        Qs = torch.empty(depth, Etot, Hp, **f32)
-        St = torch.empty(5, depth, Etot, Hp, **f32)
-        if lstm:
-            cp = torch.zeros(Etot, Hp, **f32)
-            Cs = torch.empty(depth + 1, Etot, Hp, **f32)
-            wpack = torch.empty(int(lib.ggpm_lstm_pack_floats(H)), **f32)
-            Wh = [w[:, I:] for w, _ in gates]
-            _lib.check(lib.ggpm_lstm_sparse_forward(
-                Etot, H, depth, P(hp), P(cp), P(frozen), P(X[0]), P(X[1]), P(X[2]), P(X[3]), P(Wh[0]), Wi.stride(0), P(Wh[1]),
-                Wog.stride(0), P(Wh[2]), Wu.stride(0), P(Wh[3]), Wf.stride(0), P(pred.rowptr), P(pred.col), P(Hs), P(Cs), P(Qs),
-                P(St[0]), P(St[1]), P(St[2]), P(St[3]), P(St[4]), P(wpack), int(save), None, s), "lstm_sparse_forward")
-        else:
-            Cs = None
-            wpack = torch.empty(int(lib.ggpm_gru_pack_floats(H)), **f32)
-            _lib.check(lib.ggpm_gru_sparse_forward(
-                Etot, H, depth, P(hp), P(frozen), P(X[0]), P(X[1]), P(X[2]), P(Wz[:, I:]), Wz.stride(0), P(Ur), Ur.stride(0),
-                P(bu), P(Wh[:, I:]), Wh.stride(0), P(pred.rowptr), P(pred.col), P(Hs), P(Qs), P(St[0]), P(St[1]), P(St[2]),
-                P(St[3]), P(St[4]), P(wpack), int(save), None, s), "gru_sparse_forward")
-        hid = Hs[depth]
-        # 6. read-out of every visit
-        nei = torch.empty(n_inst, Hp, **f32)
-        F_._segment_sum_raw(hid, in_csr, H, nei)
-        node = torch.empty(n_inst, Hp, **f32)
-        ldo = Wo.stride(0)
-        F_.gemm_ksegments(1, n_inst, H, [hnode, nei], [Hp, Hp], [Wo, Wo[:, H:]], [ldo, ldo], [H, H], node, Hp, Hp, bias=bo,
-                          act=F_.ACT_RELU)
-        ctx.S, ctx.meta = S, (lstm, H, He, extra is not None)
-        ctx.save_for_backward(lower, node)          # (an input and an output: through autograd, so that no ctx -> output cycle forms)
-        ctx.stash = (finput, hnode, hmess, X[G - 1] if lstm else X[1], Hs, Cs, Qs, St, nei)
-        ctx.prm = (emb, W, b, Wo, bo) + tuple(rp)
-        ctx.structs = (frozen, pred, in_csr, src_csr)
-        ctx.set_materialize_grads(False)            # (an unused output arrives as None, not as a zero tensor to be added)
-        return node, hid
+        return _composite_forward(ctx, S, lstm, H, He, lower, extra, emb, W, b, Wo, bo, rp, infer=False)
 
     @staticmethod
     def backward(ctx, d_node, d_hid):
@@ -275,6 +282,57 @@ def _addr(t) -> int:
     return 0 if t is None else t.data_ptr()
 
 
+def _descriptor(S: LevelSpec, lstm: bool, H: int, He: int, lower, extra, emb, W, b, Wo, bo, rp, backward: bool = True):
+    """-> (ggpm_tree_level, the index tables it names).  ``backward`` False: the transposed tables (read by the backward
+    only) are neither built nor named."""
+    frozen, pred, in_csr, src_csr = S.structures()
+    succ, in_T, src_T = (pred.T, in_csr.T, src_csr.T) if backward else (None, None, None)
+    n_inst = S.ids.numel()
+    if lstm:
+        Wi, bi, Wog, bog, Wu, bu_, Wf, bf = rp
+        gw, gb, Ur, bu = (Wi, Wog, Wu, Wf), (bi, bog, bu_, bf), None, None
+    else:
+        Wz, bz, Wr, Ur, bu, Wh, bh = rp
+        gw, gb = (Wz, Wr, Wh), (bz, None, bh)
+    L = TreeLevelC()
+    L.lstm, L.H, L.He, L.E1, L.n_extra, L.depth, L.n_inst = int(lstm), H, He, S.E1, S.n_extra, S.depth, n_inst
+    for k, t in (("ids", S.ids), ("mess_inst", S.mess_inst), ("mess_pos", S.mess_pos), ("frozen", frozen),
+                 ("pred_rowptr", pred.rowptr), ("pred_col", pred.col), ("in_rowptr", in_csr.rowptr), ("in_col", in_csr.col)):
+        setattr(L, k, _addr(t))
+    if backward:
+        for k, t in (("succ_rowptr", succ.rowptr), ("succ_col", succ.col), ("inT_rowptr", in_T.rowptr),
+                     ("inT_col", in_T.col), ("srcT_rowptr", src_T.rowptr), ("srcT_col", src_T.col)):
+            setattr(L, k, _addr(t))
+    L.emb, L.ld_emb = _addr(emb), F_._ld(emb)
+    L.W, L.b, L.ld_w = _addr(W), _addr(b), (W.stride(0) if W is not None else 0)   # (W None: embedding-input mode)
+    L.Wo, L.bo, L.ld_wo = _addr(Wo), _addr(bo), Wo.stride(0)
+    for k, (w, bb) in enumerate(zip(gw, gb)):
+        L.gate_w[k], L.ld_gate[k], L.gate_b[k] = _addr(w), w.stride(0), _addr(bb)
+    L.Ur, L.bu, L.ld_ur = _addr(Ur), _addr(bu), (Ur.stride(0) if Ur is not None else 0)
+    L.lower, L.ld_lower = _addr(lower), (F_._ld(lower) if lower is not None else 0)
+    L.extra, L.ld_extra = _addr(extra), (F_._ld(extra) if extra is not None else 0)
+    return L, (frozen, pred, succ, in_csr, in_T, src_csr, src_T)
+
+
+def _tree_level_infer(S: LevelSpec, lstm: bool, H: int, He: int, lower, extra, emb, W, b, Wo, bo, *rp):
+    """The forward-only form of _TreeLevelNative (ggpm_tree_level_infer): the same (node, hidden state), bit for bit, with
+    no stashes and no transposed tables; the hidden state is a view of the arena, which it keeps alive."""
+    lib = _lib.load()
+    dev = emb.device
+    Hp = F_.padded_hidden(H)
+    detach = lambda t: None if t is None else t.detach()
+    L, _tables = _descriptor(S, lstm, H, He, detach(lower), detach(extra), emb.detach(), detach(W), detach(b), Wo.detach(),
+                            bo.detach(), [detach(t) for t in rp], backward=False)
+    n_arena = int(lib.ggpm_tree_level_infer_floats(ctypes.byref(L)))
+    arena = torch.empty(n_arena, dtype=torch.float32, device=dev)
+    V = TreeLevelViews()
+    _lib.check(lib.ggpm_tree_level_infer(ctypes.byref(L), F_._p(arena), n_arena, ctypes.byref(V), F_._stream()),
+               "tree_level_infer")
+    base, Etot, n_inst = arena.data_ptr(), S.E1 + S.n_extra, S.ids.numel()
+    node_off, hs_off = (V.node - base) // 4, (V.Hs - base) // 4 + (S.depth & 1) * Etot * Hp
+    return arena[node_off:node_off + n_inst * Hp].view(n_inst, Hp), arena[hs_off:hs_off + Etot * Hp].view(Etot, Hp)
+
+
 class _TreeLevelNative(torch.autograd.Function):
     """``_TreeLevel`` with each direction as ONE call into csrc/tree_level.hip (ggpm_tree_level_forward / _backward): the same
     launches in the same order (bit-identical results), no per-launch ctypes marshalling and two allocations per direction."""
@@ -284,30 +342,8 @@ class _TreeLevelNative(torch.autograd.Function):
         lib = _lib.load()
         dev = emb.device
         Hp = F_.padded_hidden(H)
-        frozen, pred, in_csr, src_csr = S.structures()
-        succ, in_T, src_T = pred.T, in_csr.T, src_csr.T
         n_inst, Etot = S.ids.numel(), S.E1 + S.n_extra
-        if lstm:
-            Wi, bi, Wog, bog, Wu, bu_, Wf, bf = rp
-            gw, gb, Ur, bu = (Wi, Wog, Wu, Wf), (bi, bog, bu_, bf), None, None
-        else:
-            Wz, bz, Wr, Ur, bu, Wh, bh = rp
-            gw, gb = (Wz, Wr, Wh), (bz, None, bh)
-        L = TreeLevelC()
-        L.lstm, L.H, L.He, L.E1, L.n_extra, L.depth, L.n_inst = int(lstm), H, He, S.E1, S.n_extra, S.depth, n_inst
-        for k, t in (("ids", S.ids), ("mess_inst", S.mess_inst), ("mess_pos", S.mess_pos), ("frozen", frozen),
-                     ("pred_rowptr", pred.rowptr), ("pred_col", pred.col), ("succ_rowptr", succ.rowptr), ("succ_col", succ.col),
-                     ("in_rowptr", in_csr.rowptr), ("in_col", in_csr.col), ("inT_rowptr", in_T.rowptr), ("inT_col", in_T.col),
-                     ("srcT_rowptr", src_T.rowptr), ("srcT_col", src_T.col)):
-            setattr(L, k, _addr(t))
-        L.emb, L.ld_emb = _addr(emb), F_._ld(emb)
-        L.W, L.b, L.ld_w = _addr(W), _addr(b), (W.stride(0) if W is not None else 0)   # (W None: embedding-input mode)
-        L.Wo, L.bo, L.ld_wo = _addr(Wo), _addr(bo), Wo.stride(0)
-        for k, (w, bb) in enumerate(zip(gw, gb)):
-            L.gate_w[k], L.ld_gate[k], L.gate_b[k] = _addr(w), w.stride(0), _addr(bb)
-        L.Ur, L.bu, L.ld_ur = _addr(Ur), _addr(bu), (Ur.stride(0) if Ur is not None else 0)
-        L.lower, L.ld_lower = _addr(lower), (F_._ld(lower) if lower is not None else 0)
-        L.extra, L.ld_extra = _addr(extra), (F_._ld(extra) if extra is not None else 0)
+        L, tables = _descriptor(S, lstm, H, He, lower, extra, emb, W, b, Wo, bo, rp)
         n_saved = int(lib.ggpm_tree_level_saved_floats(ctypes.byref(L)))
         saved = torch.empty(n_saved, dtype=torch.float32, device=dev)
         V = TreeLevelViews()
@@ -324,7 +360,7 @@ class _TreeLevelNative(torch.autograd.Function):
         hid = view(V.Hs, (S.depth + 1) * Etot, Hp)[S.depth * Etot:]
         ctx.S, ctx.meta = S, (lstm, H, He, extra is not None)
         ctx.save_for_backward(lower, saved)
-        ctx.keep = (L, V, extra, (frozen, pred, succ, in_csr, in_T, src_csr, src_T))      # (the tables the descriptor names)
+        ctx.keep = (L, V, extra, tables)      # (the tables the descriptor names)
         ctx.views = (view(V.finput, n_inst, Hep), view(V.hnode, n_inst, Hp), view(V.nei, n_inst, Hp))
         ctx.prm = (emb, W, b, Wo, bo) + tuple(rp)
         ctx.set_materialize_grads(False)
@@ -427,9 +463,22 @@ def tree_level(S: LevelSpec, rnn, emb_seq, lin_seq, wo_seq, lower, extra: Option
     if lin_seq is None:
         if lower is not None or not _dev.TREE_DRIVER:
             raise ValueError("tree_level: the embedding-input mode takes no lower level and runs through the driver only")
+        if not fused.records_grad([t for t in (extra, emb, wo_seq[0].weight, wo_seq[0].bias) + rp if t is not None]):
+            return _tree_level_infer(S, lstm, rnn.hidden_size, emb.shape[1], None, extra, emb, None, None,
+                                     wo_seq[0].weight, wo_seq[0].bias, *rp)
         return _TreeLevelNative.apply(S, lstm, rnn.hidden_size, emb.shape[1], None, extra, emb, None, None,
                                       wo_seq[0].weight, wo_seq[0].bias, *rp)
     lower = lower if lower.stride(1) == 1 else lower.contiguous()
+    if _dev.TREE_DRIVER and not fused.records_grad([t for t in (lower, extra, emb, lin_seq[0].weight, lin_seq[0].bias,
+                                                               wo_seq[0].weight, wo_seq[0].bias) + rp if t is not None]):
+        return _tree_level_infer(S, lstm, rnn.hidden_size, emb.shape[1], lower, extra, emb, lin_seq[0].weight,
+                                 lin_seq[0].bias, wo_seq[0].weight, wo_seq[0].bias, *rp)
+    if not _dev.TREE_DRIVER and not fused.records_grad([t for t in (lower, extra, emb, lin_seq[0].weight, lin_seq[0].bias,
+                                                                   wo_seq[0].weight, wo_seq[0].bias) + rp if t is not None]):
+        dt = lambda t: None if t is None else t.detach()
+        return _composite_forward(None, S, lstm, rnn.hidden_size, emb.shape[1], dt(lower), dt(extra), emb.detach(),
+                                  lin_seq[0].weight.detach(), lin_seq[0].bias.detach(), wo_seq[0].weight.detach(),
+                                  wo_seq[0].bias.detach(), [t.detach() for t in rp], infer=True)
     node_fn = _TreeLevelNative if _dev.TREE_DRIVER else _TreeLevel      # (the Python composite stays as the checker)
     return node_fn.apply(S, lstm, rnn.hidden_size, emb.shape[1], lower, extra, emb, lin_seq[0].weight, lin_seq[0].bias,
                          wo_seq[0].weight, wo_seq[0].bias, *rp)

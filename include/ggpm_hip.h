@@ -324,6 +324,14 @@ typedef struct ggpm_level_opts {
     int lo;
     int skip_bias_u;
     int skip_sparse_wgrads;
+    /* Forward without stashes (save_for_backward = 0), h_out non-NULL: the forward-only form of a level, dense or sparse.
+     * The call honours run_depth as the dense training forward does, keeps the depth loop in the two ping-pong slots of Hs / Qs (LSTM:
+     * and Cs), writes the last computed step's h [E1][Hp] to h_out (LSTM: c to c_out when that is non-NULL) and applies
+     * bf16 storage (ggpm_level_bf16_storage) exactly as the training forward of the same level does, so h_out is
+     * bit-identical to slot `depth` of the training forward's Hs.  NULL (default): the result is Hs[depth & 1] as
+     * documented at ggpm_gru_forward, all `depth` steps run and the depth loop stays fp32. */
+    float* h_out;
+    float* c_out;
 } ggpm_level_opts;
 
 /* ------------------------------------------------------------------ GRU message function
@@ -490,6 +498,17 @@ int ggpm_decode_steps_backward_async(const ggpm_decode_steps* steps, const float
                                      float* DQ_all, float* const* dW_unused, float* work, size_t work_bytes, float* tmp,
                                      ggpm_stream_t stream);
 int ggpm_decode_join(void);
+/* Forward-only form of ggpm_decode_steps_forward (no backward follows), and its worker-thread form (join as above): the
+ * same sparse_forward calls in the same order without stashes.  Each step runs its depth loop in the scratch Hs / Qs (LSTM:
+ * Cs), 2 * max(n) * Hp floats each, and writes the final states of its n rows to F_h (LSTM: F_c) [sum of n][Hp] at rows
+ * foff[t] ..; later steps gather their frozen rows from there through srcF.  F_h holds exactly the rows that slot `depth`
+ * of every block of the training forward's Hs_all holds, bit for bit.  No Qs_all / St_all. */
+int ggpm_decode_steps_infer(const ggpm_decode_steps* steps, const float* const* W, const int* ldw, const float* bu,
+                            const float* X_all, float* F_h, float* F_c, float* Hs, float* Cs, float* Qs, float* wpack,
+                            ggpm_stream_t stream);
+int ggpm_decode_steps_infer_async(const ggpm_decode_steps* steps, const float* const* W, const int* ldw, const float* bu,
+                                  const float* X_all, float* F_h, float* F_c, float* Hs, float* Cs, float* Qs, float* wpack,
+                                  ggpm_stream_t stream);
 
 /* ------------------------------------------------------------------ one tree-side level of the teacher-forced decoder
  * IncHierMPNEncoder.embed_sub_tree + IncMPNEncoder.forward (ggpm/encoder.py:208-245, 165-179), which
@@ -540,6 +559,13 @@ size_t ggpm_tree_level_saved_floats(const ggpm_tree_level* level);
 size_t ggpm_tree_level_work_bytes(const ggpm_tree_level* level);
 int ggpm_tree_level_forward(const ggpm_tree_level* level, float* saved, size_t saved_floats, ggpm_tree_level_views* views,
                             ggpm_stream_t stream);
+/* Forward-only form of ggpm_tree_level_forward (no backward follows): the same launches in the same order without the
+ * depth loop's stashes -- the loop runs in two ping-pong state slots, so `views->Hs` holds 2 slots (LSTM: Cs too) and the
+ * final state h^depth is slot depth & 1; views->St is NULL.  node and that final state are bit-identical to the training
+ * forward's.  arena: ggpm_tree_level_infer_floats floats. */
+size_t ggpm_tree_level_infer_floats(const ggpm_tree_level* level);
+int ggpm_tree_level_infer(const ggpm_tree_level* level, float* arena, size_t arena_floats, ggpm_tree_level_views* views,
+                          ggpm_stream_t stream);
 /* side_stream (nullable): where the level's PARAMETER gradients (grads->dgate_w / dgate_b / dUr / dbu) are formed, behind an
  * event the main stream records after the depth loop -- the gradients that flow on (d_lower, dHin, dpre_*, d_finput) are
  * then not queued behind ~145 us of contractions.  Same launches, same results.  The caller joins that stream before it
@@ -642,6 +668,19 @@ int ggpm_encoder_forward(const ggpm_enc_dims* dims, float* const* params, const 
                          const int64_t* gfmess, const int64_t* gagraph, const int64_t* gbgraph, const int32_t* roots,
                          void* saved, size_t saved_bytes, float* hroot, float* hnode, float* hinter, float* hatom,
                          ggpm_stream_t stream, ggpm_stream_t side_stream);
+/* Forward-only form of ggpm_encoder_forward, for calls no backward follows (no-grad evaluation, latent encoding): the
+ * same launches that compute values, in the same order, with the same dropout masks (dims->dropout as above), so the four
+ * outputs are bit-identical to ggpm_encoder_forward's (fp32 and gate dtype 1 alike).  `arena`:
+ * ggpm_encoder_infer_bytes() bytes of scratch, free again when the call's work on `stream` has run: the forward CSRs and
+ * index columns, the tree-side inputs, per-level neighbour sums and ONE depth-loop scratch shared by the three levels (hoisted
+ * inputs, two ping-pong state slots, the level's result: ggpm_level_opts.h_out) -- no per-depth stashes, no transposed CSRs.
+ * side_stream (may be 0): the tree-side layout runs there beside the atom level, as in the training forward. */
+size_t ggpm_encoder_infer_bytes(const ggpm_enc_dims* dims);
+int ggpm_encoder_infer(const ggpm_enc_dims* dims, float* const* params, const int64_t* tfnode, const int64_t* tfmess,
+                       const int64_t* tagraph, const int64_t* tbgraph, const int64_t* tcgraph, const int64_t* gfnode,
+                       const int64_t* gfmess, const int64_t* gagraph, const int64_t* gbgraph, const int32_t* roots,
+                       void* arena, size_t arena_bytes, float* hroot, float* hnode, float* hinter, float* hatom,
+                       ggpm_stream_t stream, ggpm_stream_t side_stream);
 int ggpm_encoder_backward(const ggpm_enc_dims* dims, float* const* params, float* const* grads, const int32_t* roots,
                           void* saved, size_t saved_bytes, const float* hroot, const float* hnode, const float* hinter,
                           const float* hatom, const float* d_hroot, const float* d_hnode, const float* d_hinter,
