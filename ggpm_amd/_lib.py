@@ -82,6 +82,12 @@ SIGNATURES = {
     # attachment head of the tree-only decoder (csrc/motif_assm.hip)
     "ggpm_motif_assm_forward": (I, [P, I, P, I, I, I, I, P, I, P, P, P, P, I, P, P, P, P, P, P]),
     "ggpm_motif_assm_backward": (I, [P, P, I, P, I, I, I, I, I, P, I, P, P, P, I, P, P, P, P, P, P, P, P, P, P]),
+    # greedy decode of the tree-only decoder (csrc/motif_decode.hip)
+    "ggpm_motif_decode_tree_step": (I, [I, I, I, I, POINTER(c_void_p), P, P, P, P, I, I, P, P, P, I, I, P, I, P, I, P, I,
+                                        P, I, P]),
+    "ggpm_motif_decode_mlp": (I, [P, I, P, P, I, I, I, I, P, P, P, P, I, I, P, I, P, I, P]),
+    "ggpm_hier_topk": (I, [P, I, I, P, I, I, P, I, I, I, P, P]),
+    "ggpm_motif_decode_assm_score": (I, [P, I, I, I, P, P, I, P, I, P, P, P, P, I, P, P]),
     "ggpm_dropout": (I, [P, I, I, I, ctypes.c_float, ctypes.c_uint, ctypes.c_uint, I, P]),
     # property heads / latent search (csrc/property.hip): heads are ggpm_prop_head*, grads ggpm_prop_head_grads*
     "ggpm_property_heads_workspace_bytes": (c_size_t, [I, I, P, P]),

@@ -1,5 +1,6 @@
-"""MotifDecoder -- the teacher-forced training forward of the tree-only decoder, reference ggpm/decoder.py:475-899
-(``sum_forward``; ``decode`` needs rdkit and stays out of scope, ``mean_forward`` is called nowhere in the reference).
+"""MotifDecoder -- the tree-only decoder, reference ggpm/decoder.py:475-1095: the teacher-forced training forward
+(``sum_forward``; ``mean_forward`` is called nowhere in the reference) and the greedy ``decode`` (ggpm_amd.motif_decode,
+which assembles molecules through a graph batch the caller supplies).
 
 Same constructor, sub-module names and ``state_dict`` keys as the reference (``hmpn.*`` -- an ``IncEncoder`` --,
 ``topoNN``, ``clsNN``, ``iclsNN``, ``matchNN``, ``W_assm``, ``W_root`` when latent != hidden, the aliases ``rnn_cell`` and
@@ -126,9 +127,16 @@ class MotifDecoder(ScoreHeads):
         self.matchNN = nn.Sequential(nn.Linear(hidden_size + MAX_POS, hidden_size), nn.ReLU())
         if latent_size != hidden_size:
             self.W_root = nn.Linear(latent_size, hidden_size)
+        self.graph_batch_factory = None     # decode's graph batch when the call names none (ggpm_amd.motif_decode)
 
     def schedule_hints(self) -> dict:
         return {}
+
+    def decode(self, mols, src_mol_vecs, greedy=True, max_decode_step=100, beam=5, graph_batch_factory=None):
+        """reference ggpm/decoder.py:901-1095 -> (results, graph_batch.get_mol()) on the library's kernels; the graph batch
+        is ``graph_batch_factory`` or else ``self.graph_batch_factory`` (ggpm_amd.motif_decode)."""
+        from .motif_decode import decode
+        return decode(self, mols, src_mol_vecs, greedy, max_decode_step, beam, graph_batch_factory)
 
     # ------------------------------------------------------------------ forward
     def forward(self, mols, src_mol_vecs, graphs, tensors, orders, avg_loss=False, schedule: Optional[DecodeSchedule] = None):

@@ -431,6 +431,18 @@ def _predict_properties(model, batch):
         return model.property_optim.predict(homo_vecs=z[:, :half], lumo_vecs=z[:, half:])
 
 
+def _graph_batch_factory(model, args):
+    """decode's graph batch for reconstruct: ``args.graph_batch_factory``, else the decoder's; neither raises before the
+    batch is touched."""
+    from .motif_decode import NO_FACTORY
+    factory = getattr(args, "graph_batch_factory", None)
+    if factory is None:
+        factory = getattr(model.decoder, "graph_batch_factory", None)
+    if factory is None:
+        raise NotImplementedError(NO_FACTORY)
+    return factory
+
+
 def _motif_schedule(model, graphs, tensors, orders, schedule):
     """The decoder's bookkeeping: the one passed, the one ScheduleAhead attached to ``graphs``, or derived here."""
     from .decoder import DecodeSchedule
@@ -468,8 +480,14 @@ class PropertyVAE(nn.Module):
         return rsample(z_vecs, self.R_mean, self.R_var, perturb)
 
     def reconstruct(self, batch, args=None):
-        raise NotImplementedError("PropertyVAE.reconstruct needs MotifDecoder.decode(), which needs rdkit chemistry and is "
-                                  "not part of this build")
+        """reference ggpm/property_vae.py:101-109: the no-grad encoder, the mean latent, greedy decode of 150 steps ->
+        (results, molecules).  The graph batch: ``args.graph_batch_factory``, else the decoder's."""
+        factory = _graph_batch_factory(self, args)
+        with torch.no_grad():
+            tree_tensors, _ = make_cuda(batch[2])
+            root_vecs, _ = rsample(self.encoder.forward_padded(tree_tensors)[0], self.R_mean, self.R_var, perturb=False)
+        return self.decoder.decode(batch[0], (root_vecs, root_vecs, root_vecs), greedy=True, max_decode_step=150,
+                                   graph_batch_factory=factory)
 
     def forward(self, mols, graphs, tensors, orders, homos=None, lumos=None, beta=0.0, perturb_z=True, schedule=None):
         schedule = _motif_schedule(self, graphs, tensors, orders, schedule)
@@ -532,12 +550,20 @@ class PropOptVAE(_ClipNegativeLoss, nn.Module):
         return _predict_properties(self, batch)
 
     def reconstruct(self, batch, args=None):
-        raise NotImplementedError("PropOptVAE.reconstruct needs MotifDecoder.decode(), which needs rdkit chemistry and is "
-                                  "not part of this build")
+        """reference ggpm/property_vae.py:299-318: the no-grad encoder, the mean latent, the property heads on it, greedy
+        decode of 150 steps -> ((homo [B], lumo [B]), (results, molecules)).  The graph batch: ``args.graph_batch_factory``,
+        else the decoder's."""
+        factory = _graph_batch_factory(self, args)
+        with torch.no_grad():
+            root_vecs, _ = self.encode_latent(batch[2], perturb=False)
+            half = self.latent_size
+            props = self.property_optim.predict(homo_vecs=root_vecs[:, :half], lumo_vecs=root_vecs[:, half:])
+        return props, self.decoder.decode(batch[0], (root_vecs, root_vecs, root_vecs), greedy=True, max_decode_step=150,
+                                          graph_batch_factory=factory)
 
     def optimize_recs(self, batch, args=None):
-        raise NotImplementedError("PropOptVAE.optimize_recs needs MotifDecoder.decode(), which needs rdkit chemistry and "
-                                  "is not part of this build")
+        raise NotImplementedError("PropOptVAE.optimize_recs: the reference's version calls PropertyOptimizer.optimize, "
+                                  "which ggpm/property_optimizer.py does not define")
 
     def forward(self, mols, graphs, tensors, orders, homos, lumos, beta=0.0, perturb_z=True, schedule=None):
         schedule = _motif_schedule(self, graphs, tensors, orders, schedule)

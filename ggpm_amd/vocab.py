@@ -29,6 +29,14 @@ class IndexPairVocab:
         f = lambda v: int(v[1:]) if isinstance(v, str) else int(v)
         return f(label[0]), f(label[1])
 
+    def get_smiles(self, i) -> str:
+        """'m<i>': the label of motif i that ``__getitem__`` parses back (the reference's PairVocab returns its SMILES)."""
+        return "m%d" % int(i)
+
+    def get_ismiles(self, j) -> str:
+        """'a<j>': the label of attachment j that ``__getitem__`` parses back."""
+        return "a%d" % int(j)
+
     @property
     def mask(self) -> torch.Tensor:
         return self._mask["cpu"]

@@ -621,6 +621,39 @@ int ggpm_motif_assm_backward(const float* dloss, const float* rows, int ld_rows,
                              int ldz, const float* act, const float* score, const float* stat, float* drows, float* dW1,
                              float* db1, float* dWa, float* dba, float* dz, ggpm_stream_t stream);
 
+/* Greedy decode of the tree-only decoder (MotifDecoder.decode, ggpm/decoder.py:901-1095; csrc/motif_decode.hip).
+ * ggpm_motif_decode_tree_step (two launches): applies the edits -- n_node_edits pairs {node, motif} to fnode [N], then
+ * n_tab_edits quads {table 0 agraph [N x 12] / 1 bgraph [E x 12] / 2 fmess [E x 2] (source node, position), row, slot,
+ * value} -- then EITHER the read-outs of the n_read nodes (node_out row r = relu(W_o [E_c[fnode[n]] | sum of h over
+ * agraph[n]] + b)) OR the n_mess new messages (pairs {message, output row or -1}: reset, input [E_c[fnode[source]] |
+ * onehot(position)], `depth` GRU / LSTM iterations over bgraph; h (and c) rows written, the hidden row copied to mess_out
+ * row when given).  No new message may appear in another new message's bgraph row.  params: host array of device pointers
+ * {E_c [n_motif x H], W_o.0.weight [H x 2H], W_o.0.bias} then GRU {W_z, b_z, W_r, U_r, b_Ur, W_h, b_h} or LSTM {W_i, b_i,
+ * W_o, b_o, W_f, b_f, W, b} (contiguous, input width H + max_pos).  h, c: [E x H].  H <= 1024.
+ * ggpm_motif_decode_mlp (two launches): out[r] = W2 relu(W1 [vecs[r] | ctx[bidx[r]]] + b1) + b2 (sigmoid if asked);
+ * W1 [H x (H + L)], W2 [n_out x H] contiguous; hid: [M x ld_hid] scratch.
+ * ggpm_hier_topk (one launch, one workgroup per row): nnutils.hier_topk of (cls [M x n_cls], icls [M x n_icls]) with the
+ * mask 0 / -1000 from owner[n_icls] (the motif each attachment belongs to); root != 0: the arg-max motif of the raw cls
+ * row and the top k of its masked icls row.  out [M x 3k] int32: k scores (fp32 bits), k motifs, k attachments.  Ties: the
+ * lower index.  k <= 16.
+ * ggpm_motif_decode_assm_score (one launch, one workgroup per meta row {n candidates, k (1 or 2), nth_child, molecule,
+ * first candidate, first id}): (W_assm sum_{j<k} relu(matchNN [E_assm[id_j] | onehot(nth)]) + b) . z[molecule], written
+ * to score[first candidate .. + n) (enum_attach reads no candidate atom: the n candidates score the same).  E_assm:
+ * [n_ids x H]; a row with k, nth or an id out of range scores NaN. */
+int ggpm_motif_decode_tree_step(int rnn_type, int H, int max_pos, int depth, const void* const* params, int32_t* fnode,
+                                int32_t* fmess, int32_t* agraph, int32_t* bgraph, int N, int E, float* h, float* c,
+                                const int32_t* edits, int n_node_edits, int n_tab_edits, const int32_t* nodes, int n_read,
+                                float* node_out, int ld_node, const int32_t* mess, int n_mess, float* mess_out,
+                                int ld_mess, ggpm_stream_t stream);
+int ggpm_motif_decode_mlp(const float* vecs, int ld_v, const int32_t* bidx, const float* ctx, int ld_ctx, int M, int H,
+                          int L, const float* W1, const float* b1, const float* W2, const float* b2, int n_out,
+                          int sigmoid, float* hid, int ld_hid, float* out, int ld_out, ggpm_stream_t stream);
+int ggpm_hier_topk(const float* cls, int ld_cls, int n_cls, const float* icls, int ld_icls, int n_icls,
+                   const int32_t* owner, int M, int k, int root, int32_t* out, ggpm_stream_t stream);
+int ggpm_motif_decode_assm_score(const float* E_assm, int n_ids, int H, int L, const int32_t* meta, const int32_t* ids,
+                                 int P, const float* W1, int ldw, const float* b1, const float* Wa, const float* ba,
+                                 const float* z, int ldz, float* score, ggpm_stream_t stream);
+
 /* ------------------------------------------------------------------ whole-encoder drivers
  * HierMPNEncoder.forward (ggpm/encoder.py:140-157, with embed_graph/inter/tree/root :96-138) and its backward as ONE
  * call each: the same kernels the op-by-op host path issues, sequenced from C++ (GRU or LSTM message function).
