@@ -185,6 +185,15 @@ hipEvent_t ggpm_wgrad_event(int i);          // small pool of re-recordable even
 bool ggpm_bf16_storage_applies(int E1, int H);       // (gemm.hip: one stash slot alone must qualify for the bf16 tall kernel)
 // out[i] = sum_t src[t][i] over `slots` slots of `slot_floats` elements, src fp32 or bf16 (first half of its buffer); fixed order
 int ggpm_sum_slots_any(const float* src, int slots, size_t slot_floats, float* out, bool src_bf16, ggpm_stream_t stream);
+// Fixed-point levels (ggpm_level_opts.fixed_slot).  ggpm_sum_slots_pair_grouped: hi[i] + lo[i] = sum_t src[t][i] over `slots`
+// fp32 slots, the sum kept as an unevaluated pair -- hi the running fp32 sum, lo the sum of its rounding errors (two-sum per
+// term, fixed order); up to 4 arrays of one slot size in one launch; hi / lo may be slots of the same array below the ones read.
+// ggpm_gemm_tn_pair_grouped: C_i = [hi_i; lo_i]^T [B_i; B_i] for up to GGPM_GEMM_MAX_GROUP such pairs (operands [rows, ld],
+// C_i [M, ldc] overwritten) in one launch.
+int ggpm_sum_slots_pair_grouped(int count, const float* const* src, const int* slots, size_t slot_floats, float* const* hi,
+                                float* const* lo, ggpm_stream_t stream);
+struct ggpm_pair_problem { const float *hi, *lo, *B; float* C; int ldc; };
+int ggpm_gemm_tn_pair_grouped(int M, int N, int rows, int ld, int count, const ggpm_pair_problem* p, ggpm_stream_t stream);
 // column sums of a [rows, ld] fp32 or bf16 matrix (losses.hip / gemm.hip: ggpm_colsum is the fp32 entry point)
 int ggpm_colsum_any(const float* A, int lda, int rows, int cols, float* out, float* scratch, bool a_bf16, ggpm_stream_t stream);
 

@@ -344,8 +344,19 @@ inline int backward_lo(const Dims& d, int level, int depth, int E1) {
     return lo < 1 ? 1 : lo;
 }
 
+// The level's fixed slot (ggpm_level_opts.fixed_slot; 0: none): when the first backward step lies at or above the last
+// forward step (D >= 2C), every state / stash slot an executed backward step reads is the settled one.  The level calls then
+// read it in place, stash only it, and contract the summed gate gradients against it: nothing is replicated.  Otherwise
+// (C + 1 < D < 2C) the backward walks original and replicated slots and replicate_tail fills the latter.
+inline int fixed_slot(const Dims& d, int level, int depth, int E1) {
+    const int run = run_steps(d, level, depth, E1);
+    if (run >= depth || d.gate_dtype == 1) return 0;
+    const int blo = backward_lo(d, level, depth, E1);
+    return (blo >= run && blo >= 3) ? run : 0;          // (blo >= 3: slots 0 and 1 of the gate-gradient stashes are free)
+}
+
 int replicate_tail(const Dims& d, int E1, int depth, int run, int level, const LevelSaved& L, ggpm_stream_t s) {
-    if (run >= depth) return GGPM_OK;
+    if (run >= depth || fixed_slot(d, level, depth, E1)) return GGPM_OK;
     const size_t slot = (size_t)E1 * d.Hp, ds = (size_t)depth * slot;
     const int blo = backward_lo(d, level, depth, E1);     // the backward only reads state slots >= blo, stash slots >= blo - 1
     ReplicateArgs r = {};
@@ -373,7 +384,9 @@ int level_forward(const Dims& d, int E1, int N1, int I, int depth, const float* 
     o.run_depth = run;
     const bool infer = L.hout != nullptr;          // forward-only layout: no stashes, the result lands in L.hout
     o.h_out = L.hout;
-    const float* result = infer ? L.hout : L.Hs + (size_t)depth * slot;
+    const int fs = infer ? 0 : fixed_slot(d, level, depth, E1);
+    o.fixed_slot = fs;
+    const float* result = infer ? L.hout : L.Hs + (size_t)(fs ? fs : depth) * slot;
     if (d.lstm) {
         const float* W[4] = {P[lq(level, Q_WI)], P[lq(level, Q_WOG)], P[lq(level, Q_WU)], P[lq(level, Q_WF)]};
         const float* b[4] = {P[lq(level, Q_BI)], P[lq(level, Q_BOG)], P[lq(level, Q_BU)], P[lq(level, Q_BF)]};
@@ -700,6 +713,7 @@ int level_backward(const Dims& d, int E1, int I, int depth, const float* x, int 
     const bool skip_xsum = xsum_env && dx == nullptr && depth > 1;
     ggpm_level_opts o = level_opts(d);
     o.lo = blo;                   // (the backward and its weight-gradient call alike)
+    o.fixed_slot = fixed_slot(d, level, depth, E1);
     o.skip_x_sums = skip_xsum;
     if (d.lstm) {
         const float* W[4] = {P[lq(level, Q_WI)], P[lq(level, Q_WOG)], P[lq(level, Q_WU)], P[lq(level, Q_WF)]};

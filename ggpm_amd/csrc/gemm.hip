@@ -1378,6 +1378,43 @@ int ggpm_gemm_tall_grouped(int M, int N, int count, const GgpmGemmProblem* p, co
     return GGPM_OK;
 }
 
+// C_i = hi_i^T B_i + lo_i^T B_i = [hi_i; lo_i]^T [B_i; B_i] for `count` members in ONE launch of the small-product kernel:
+// each member is one accumulator chain over two K segments of `rows` rows (no split-K, no reduce launch).  Shapes with
+// more output tiles than that kernel is for run as two products per member, the second one accumulating.
+int ggpm_gemm_tn_pair_grouped(int M, int N, int rows, int ld, int count, const ggpm_pair_problem* p, ggpm_stream_t stream) {
+    GGPM_CLEAR_STALE_ERROR();
+    if (count <= 0 || count > GGPM_GEMM_MAX_GROUP || !p || M <= 0 || N <= 0 || rows <= 0 || ld < M || ld < N) return GGPM_ERR_ARG;
+    bool ok = small_launch(M, N, count);
+    for (int i = 0; i < count; ++i) {
+        if (!p[i].hi || !p[i].lo || !p[i].B || !p[i].C || p[i].ldc < N) return GGPM_ERR_ARG;
+        ok = ok && v2_operands_ok(p[i].hi, ld, rows, p[i].B, ld, rows) && v2_operands_ok(p[i].lo, ld, rows, p[i].B, ld, rows);
+    }
+    if (!ok) {
+        for (int i = 0; i < count; ++i) {
+            int rc = ggpm_gemm(1, 0, M, N, rows, p[i].hi, ld, p[i].B, ld, p[i].C, p[i].ldc, N, nullptr, 0, GGPM_ACT_NONE, 0,
+                               nullptr, 0, stream);
+            if (rc) return rc;
+            rc = ggpm_gemm(1, 0, M, N, rows, p[i].lo, ld, p[i].B, ld, p[i].C, p[i].ldc, N, nullptr, 1, GGPM_ACT_NONE, 0,
+                           nullptr, 0, stream);
+            if (rc) return rc;
+        }
+        return GGPM_OK;
+    }
+    GemmGroupArgs gg;
+    for (int i = 0; i < count; ++i) {
+        const GgpmGemmProblem q = {p[i].hi, ld, p[i].B, ld, p[i].C, p[i].ldc, N, nullptr, 0, GGPM_ACT_NONE, 0};
+        GemmArgs& g = gg.p[i];
+        fill_args(g, M, N, rows, q);
+        g.nseg = 2;
+        g.segA[0] = p[i].hi; g.segA[1] = p[i].lo;
+        for (int sg = 0; sg < 2; ++sg) { g.segB[sg] = p[i].B; g.seg_lda[sg] = g.seg_ldb[sg] = ld; g.segK[sg] = rows; }
+    }
+    for (int i = count; i < GGPM_GEMM_MAX_GROUP; ++i) gg.p[i] = gg.p[0];
+    launch_small(1, 0, gg, count, M, N, (hipStream_t)stream);
+    GGPM_CHECK_LAUNCH();
+    return GGPM_OK;
+}
+
 bool ggpm_bf16_storage_applies(int E1, int H) {
     static const int use_tall = [] { const char* e = ggpm_dev_env("GGPM_GEMM_TALL"); return e ? atoi(e) : 1; }();
     return use_tall && E1 >= 6144 && tall_shape(H, H, E1);

@@ -966,7 +966,11 @@ static int gru_forward_impl(int E1, int H, int depth, const float* Xz, const flo
     const bool st16 = bf16 == 1 && !frozen && (save_for_backward || infer) && ggpm_bf16_storage_applies(E1, H);
     int run_depth = o.run_depth;
     if (run_depth <= 0 || run_depth > depth || frozen || !(save_for_backward || infer)) run_depth = depth;
+    // fixed-point level (ggpm_level_opts.fixed_slot): only the last step's stash slot is ever read
+    const int fs = (o.fixed_slot > 0 && save_for_backward && !frozen && !st16) ? o.fixed_slot : 0;
+    if (fs && fs != run_depth) return GGPM_ERR_ARG;
     for (int t = 1; t <= run_depth; ++t) {
+        const bool stash = save_for_backward && (!fs || t == fs);
         GruFwdArgs a = {};
         a.E1 = E1; a.Hp = Hp; a.tg = tg; a.Xz = Xz; a.Xr = Xr; a.Xh = Xh;
         a.Wz = pWz; a.Wh = pWh; a.Ur = pUr; a.bu = pbu; a.rowptr = pred_rowptr; a.col = pred_col;
@@ -983,6 +987,7 @@ static int gru_forward_impl(int E1, int H, int depth, const float* Xz, const flo
             a.S = ggpm_slot_ptr(Ss, t - 1, slot, st16); a.G = ggpm_slot_ptr(Gs, t - 1, slot, st16);
             a.Z = ggpm_slot_ptr(Zs, t - 1, slot, st16); a.M = ggpm_slot_ptr(Ms, t - 1, slot, st16);
             a.R = Rs + (size_t)(t - 1) * slot;
+            if (!stash) a.S = a.G = a.Z = a.M = a.R = nullptr;
         } else if (infer) {
             a.Hprev = ggpm_slot_ptr(Hs, (t - 1) & 1, slot, st16); a.Hnew = ggpm_slot_ptr(Hs, t & 1, slot, st16);
             a.Qprev = ggpm_slot_ptr(Qs, (t - 1) & 1, slot, st16); a.Qnew = ggpm_slot_ptr(Qs, t & 1, slot, st16);
@@ -996,7 +1001,7 @@ static int gru_forward_impl(int E1, int H, int depth, const float* Xz, const flo
             a.Qprev = Qs + (size_t)((t - 1) & 1) * slot; a.Qnew = Qs + (size_t)(t & 1) * slot;
             a.S = a.G = a.Z = a.M = a.R = nullptr;
         }
-        launch_fwd(a, rt2, save_for_backward != 0, t < depth, flops1, s);
+        launch_fwd(a, rt2, stash, t < depth, flops1, s);
     }
     GGPM_CHECK_LAUNCH();
     return GGPM_OK;
@@ -1114,16 +1119,21 @@ static int gru_backward_impl(int E1, int H, int depth, const float* Xr, const fl
     // tree-side levels: d(h^t) vanishes below step `lo` (nilpotent Jacobian, common.h); sparse runs go all the way
     int lo = o.lo;
     if (lo < 1 || lo > depth || frozen) lo = 1;
+    // fixed-point level (ggpm_level_opts.fixed_slot): state slots above fs and stash slots above fs - 1 alias those
+    const int fs = (o.fixed_slot > 0 && !frozen && !st16) ? o.fixed_slot : 0;
+    if (fs && (fs >= depth || lo < fs)) return GGPM_ERR_ARG;      // (every slot a step >= lo reads must be the settled one)
+    auto state_slot = [fs](int t) { return fs && t > fs ? fs : t; };
+    auto stash_slot = [fs](int t) { return fs && t > fs ? fs - 1 : t - 1; };
     for (int t = depth; t >= lo; --t) {
         GruBwdArgs a = {};
         a.E1 = E1; a.Hp = Hp; a.tg = tg; a.first = (t == depth);
         a.Xr = Xr;
         a.st16 = st16 ? 1 : 0;
-        a.Hcur = ggpm_slot_ptr(Hs, t, slot, st16);
-        a.Qcur = (t < depth) ? ggpm_slot_ptr(Qs, t, slot, st16) : nullptr;
-        a.S = ggpm_slot_ptr(Ss, t - 1, slot, st16); a.Z = ggpm_slot_ptr(Zs, t - 1, slot, st16);
-        a.M = ggpm_slot_ptr(Ms, t - 1, slot, st16);
-        a.R = Rs + (size_t)(t - 1) * slot;
+        a.Hcur = ggpm_slot_ptr(Hs, state_slot(t), slot, st16);
+        a.Qcur = (t < depth) ? ggpm_slot_ptr(Qs, state_slot(t), slot, st16) : nullptr;
+        a.S = ggpm_slot_ptr(Ss, stash_slot(t), slot, st16); a.Z = ggpm_slot_ptr(Zs, stash_slot(t), slot, st16);
+        a.M = ggpm_slot_ptr(Ms, stash_slot(t), slot, st16);
+        a.R = Rs + (size_t)stash_slot(t) * slot;
         a.dHD = dHD;
         a.dSin = dSb[(t + 1) & 1]; a.dGin = dGb[(t + 1) & 1];      // (bf16 storage: bf16 in the first half of each buffer)
         a.dSout = dSb[t & 1]; a.dGout = dGb[t & 1];
@@ -1215,6 +1225,36 @@ static int gru_weight_grads_impl(int E1, int H, int depth, const float* Hs, cons
     const bool st16 = o.gate_dtype == 1 && !with_slot0 && ggpm_bf16_storage_applies(E1, H);
     const int tall_mode = st16 ? 2 : (o.gate_dtype == 1 ? 1 : 0);
     int rc;
+    if (o.fixed_slot > 0 && !with_slot0) {
+        // fixed-point level (ggpm_level_opts.fixed_slot): every G / S / h block a step >= lo pairs with is the settled slot,
+        // so dWh_h = (sum_t DMP_t)^T G*, dWz_h = (sum_t DZP_t)^T S*, dUr = (sum_t DQ_t)^T h*, db_u = colsum(sum_t DQ_t).  The
+        // slot sums do not round on their own: hi + lo pairs in slots 0 / 1 of each stash (free: lo - 1 >= 2), K = 2 E1.
+        const int fs = o.fixed_slot;
+        if (fs >= depth || lo < fs || lo < 3 || o.gate_dtype == 1) return GGPM_ERR_ARG;
+        const int nq = depth - lo;                         // dq^t exists for t = lo .. depth - 1
+        const float* src[3] = {DMP + (size_t)(lo - 1) * slot, DZP + (size_t)(lo - 1) * slot, DQ + (size_t)lo * slot};
+        const int slots[3] = {depth - lo + 1, depth - lo + 1, nq};
+        float* const hi[3] = {DMP, DZP, DQ};
+        float* const lw[3] = {DMP + slot, DZP + slot, DQ + slot};
+        rc = ggpm_sum_slots_pair_grouped(nq > 0 ? 3 : 2, src, slots, slot, hi, lw, stream);
+        if (rc) return rc;
+        const ggpm_pair_problem pp[3] = {{DMP, DMP + slot, Gs + (size_t)(fs - 1) * slot, dWh_h, ld_dwh},
+                                         {DZP, DZP + slot, Ss + (size_t)(fs - 1) * slot, dWz_h, ld_dwz},
+                                         {DQ, DQ + slot, Hs + (size_t)fs * slot, dUr, ld_dur}};
+        if (nq > 0) {
+            if (!skip_bu) {      // hi and lo are adjacent slots: one column sum over both
+                rc = ggpm_colsum(DQ, Hp, 2 * E1, H, dbu, csws, stream);
+                if (rc) return rc;
+            }
+        } else {
+            for (int r = 0; r < H; ++r) (void)hipMemsetAsync(dUr + (size_t)r * ld_dur, 0, H * sizeof(float), s);
+            if (!skip_bu) (void)hipMemsetAsync(dbu, 0, H * sizeof(float), s);
+        }
+        rc = ggpm_gemm_tn_pair_grouped(H, H, E1, Hp, nq > 0 ? 3 : 2, pp, stream);
+        if (rc) return rc;
+        GGPM_CHECK_LAUNCH();
+        return GGPM_OK;
+    }
     // the two or three contractions in ONE launch and one reduce (they share the split-K workspace)
     ggpm_gemm_problem gp[3] = {{ggpm_slot_ptr(DMP, lo - 1, slot, st16), Hp, ggpm_slot_ptr(Gs, lo - 1, slot, st16), Hp, dWh_h, ld_dwh, H,
                                 nullptr, 0, GGPM_ACT_NONE, 0},
@@ -1274,6 +1314,50 @@ __global__ void __launch_bounds__(256) sum_slots_k(const float* __restrict__ src
     reinterpret_cast<float4*>(out)[i] = acc;
 }
 }  // namespace
+
+namespace {
+struct SumPairArgs {
+    const float* src[4];
+    float *hi[4], *lo[4];
+    int slots[4];
+    size_t slot4;
+};
+// s + e == a + b exactly (Knuth's two-sum: no ordering of |a|, |b| assumed)
+__device__ __forceinline__ void two_sum(float a, float b, float& s, float& e) {
+    s = a + b;
+    const float bb = s - a;
+    e = (a - (s - bb)) + (b - bb);
+}
+__global__ void __launch_bounds__(256) sum_slots_pair_k(SumPairArgs p) {
+    const int m = blockIdx.y;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= p.slot4) return;
+    const float4* __restrict__ src = reinterpret_cast<const float4*>(p.src[m]);
+    float4 h = src[i], l = ggpm_zero4(), e;
+    for (int t = 1; t < p.slots[m]; ++t) {          // fixed order
+        const float4 x = src[(size_t)t * p.slot4 + i];
+        two_sum(h.x, x.x, h.x, e.x); two_sum(h.y, x.y, h.y, e.y); two_sum(h.z, x.z, h.z, e.z); two_sum(h.w, x.w, h.w, e.w);
+        l = l + e;
+    }
+    reinterpret_cast<float4*>(p.hi[m])[i] = h;
+    reinterpret_cast<float4*>(p.lo[m])[i] = l;
+}
+}  // namespace
+
+int ggpm_sum_slots_pair_grouped(int count, const float* const* src, const int* slots, size_t slot_floats, float* const* hi,
+                                float* const* lo, ggpm_stream_t stream) {
+    GGPM_CLEAR_STALE_ERROR();
+    if (count <= 0 || count > 4 || !src || !slots || !hi || !lo || slot_floats == 0 || (slot_floats & 3)) return GGPM_ERR_ARG;
+    SumPairArgs p = {};
+    for (int m = 0; m < count; ++m) {
+        if (!src[m] || !hi[m] || !lo[m] || slots[m] <= 0) return GGPM_ERR_ARG;
+        p.src[m] = src[m]; p.hi[m] = hi[m]; p.lo[m] = lo[m]; p.slots[m] = slots[m];
+    }
+    p.slot4 = slot_floats / 4;
+    sum_slots_pair_k<<<dim3((unsigned)((p.slot4 + 255) / 256), count), 256, 0, (hipStream_t)stream>>>(p);
+    GGPM_CHECK_LAUNCH();
+    return GGPM_OK;
+}
 
 extern "C" int ggpm_sum_slots(const float* src, int slots, size_t slot_floats, float* out, ggpm_stream_t stream) {
     return ggpm_sum_slots_any(src, slots, slot_floats, out, false, stream);

@@ -828,7 +828,11 @@ static int lstm_forward_impl(int E1, int H, int depth, const float* Xi, const fl
     if (run_depth <= 0 || run_depth > depth || frozen || !(save_for_backward || infer)) run_depth = depth;
     // bf16 storage (tile_mma.h): bf16 gate products, dense, training, every stash contraction on the bf16 tall kernel
     const bool st16 = bf16 == 1 && !frozen && (save_for_backward || infer) && ggpm_bf16_storage_applies(E1, H);
+    // fixed-point level (ggpm_level_opts.fixed_slot): only the last step's stash slot is ever read
+    const int fs = (o.fixed_slot > 0 && save_for_backward && !frozen && !st16) ? o.fixed_slot : 0;
+    if (fs && fs != run_depth) return GGPM_ERR_ARG;
     for (int t = 1; t <= run_depth; ++t) {
+        const bool stash = save_for_backward && (!fs || t == fs);
         LstmFwdArgs a = {};
         a.E1 = E1; a.Hp = Hp; a.tg = tg; a.Xi = Xi; a.Xo = Xo; a.Xu = Xu; a.Xf = Xf;
         a.Wi = pWi; a.Wo = pWo; a.Wu = pWu; a.Wf = pWf; a.rowptr = pred_rowptr; a.col = pred_col;
@@ -844,6 +848,7 @@ static int lstm_forward_impl(int E1, int H, int depth, const float* Xi, const fl
             a.S = ggpm_slot_ptr(Ss, t - 1, slot, st16); a.I = ggpm_slot_ptr(Is, t - 1, slot, st16);
             a.O = ggpm_slot_ptr(Os, t - 1, slot, st16); a.U = ggpm_slot_ptr(Us, t - 1, slot, st16);
             a.F = Fs + (size_t)(t - 1) * slot;
+            if (!stash) a.S = a.I = a.O = a.U = a.F = nullptr;
         } else if (infer) {
             a.Hprev = ggpm_slot_ptr(Hs, (t - 1) & 1, slot, st16); a.Hnew = ggpm_slot_ptr(Hs, t & 1, slot, st16);
             a.Cprev = Cs + (size_t)((t - 1) & 1) * slot; a.Cnew = Cs + (size_t)(t & 1) * slot;
@@ -860,7 +865,7 @@ static int lstm_forward_impl(int E1, int H, int depth, const float* Xi, const fl
             a.Qprev = Qs + (size_t)((t - 1) & 1) * slot; a.Qnew = Qs + (size_t)(t & 1) * slot;
             a.S = a.I = a.O = a.U = a.F = nullptr;
         }
-        launch_fwd(a, rt2, save_for_backward != 0, t < depth, flops1, s);
+        launch_fwd(a, rt2, stash, t < depth, flops1, s);
     }
     GGPM_CHECK_LAUNCH();
     return GGPM_OK;
@@ -973,16 +978,21 @@ static int lstm_backward_impl(int E1, int H, int depth, const float* Xf, const f
     int lo = o.lo;
     if (lo < 1 || lo > depth || frozen) lo = 1;
     const bool st16 = bf16 == 1 && !frozen && ggpm_bf16_storage_applies(E1, H);      // (as the forward decided)
+    // fixed-point level (ggpm_level_opts.fixed_slot): state slots above fs and stash slots above fs - 1 alias those
+    const int fs = (o.fixed_slot > 0 && !frozen && !st16) ? o.fixed_slot : 0;
+    if (fs && (fs >= depth || lo < fs)) return GGPM_ERR_ARG;      // (every slot a step >= lo reads must be the settled one)
+    auto state_slot = [fs](int t) { return fs && t > fs ? fs : t; };
+    auto stash_slot = [fs](int t) { return fs && t > fs ? fs - 1 : t - 1; };
     for (int t = depth; t >= lo; --t) {
         LstmBwdArgs a = {};
         a.E1 = E1; a.Hp = Hp; a.tg = tg; a.first = (t == depth);
         a.st16 = st16 ? 1 : 0;
         a.Xf = Xf;
-        a.Ccur = Cs + (size_t)t * slot;
-        a.Qcur = (t < depth) ? ggpm_slot_ptr(Qs, t, slot, st16) : nullptr;
-        a.F = Fs + (size_t)(t - 1) * slot;
-        a.I = ggpm_slot_ptr(Is, t - 1, slot, st16); a.O = ggpm_slot_ptr(Os, t - 1, slot, st16);
-        a.U = ggpm_slot_ptr(Us, t - 1, slot, st16);
+        a.Ccur = Cs + (size_t)state_slot(t) * slot;
+        a.Qcur = (t < depth) ? ggpm_slot_ptr(Qs, state_slot(t), slot, st16) : nullptr;
+        a.F = Fs + (size_t)stash_slot(t) * slot;
+        a.I = ggpm_slot_ptr(Is, stash_slot(t), slot, st16); a.O = ggpm_slot_ptr(Os, stash_slot(t), slot, st16);
+        a.U = ggpm_slot_ptr(Us, stash_slot(t), slot, st16);
         a.dHD = dHD;
         a.dSin = dSb[(t + 1) & 1]; a.dFCin = dFb[(t + 1) & 1];
         a.dSout = dSb[t & 1]; a.dFCout = dFb[t & 1];
@@ -1086,6 +1096,29 @@ static int lstm_weight_grads_impl(int E1, int H, int depth, const float* Hs, con
     const int tall_mode = st16 ? 2 : (o.gate_dtype == 1 ? 1 : 0);
     const float* Sl = ggpm_slot_ptr(Ss, lo - 1, slot, st16);
     int rc;
+    if (o.fixed_slot > 0 && !with_slot0) {
+        // fixed-point level (ggpm_level_opts.fixed_slot; mpn_gru.hip: gru_weight_grads_impl): dW*_h = (sum_t D*_t)^T S* for
+        // the i / o / u gates and dWf_h = (sum_t DQ_t)^T h*, the slot sums as hi + lo pairs in slots 0 / 1 of each stash
+        const int fs = o.fixed_slot;
+        if (fs >= depth || lo < fs || lo < 3 || o.gate_dtype == 1) return GGPM_ERR_ARG;
+        const int nq = depth - lo;                         // dqf^t exists for t = lo .. depth - 1
+        const float* src[4] = {DI + (size_t)(lo - 1) * slot, DO + (size_t)(lo - 1) * slot, DU + (size_t)(lo - 1) * slot,
+                               DQ + (size_t)lo * slot};
+        const int slots[4] = {depth - lo + 1, depth - lo + 1, depth - lo + 1, nq};
+        float* const hi[4] = {DI, DO, DU, DQ};
+        float* const lw[4] = {DI + slot, DO + slot, DU + slot, DQ + slot};
+        rc = ggpm_sum_slots_pair_grouped(nq > 0 ? 4 : 3, src, slots, slot, hi, lw, stream);
+        if (rc) return rc;
+        const float* Sf = Ss + (size_t)(fs - 1) * slot;
+        const ggpm_pair_problem pp[4] = {{DI, DI + slot, Sf, dWi_h, ld_dwi}, {DO, DO + slot, Sf, dWo_h, ld_dwo},
+                                         {DU, DU + slot, Sf, dWu_h, ld_dwu}, {DQ, DQ + slot, Hs + (size_t)fs * slot, dWf_h, ld_dwf}};
+        if (nq == 0)
+            for (int r = 0; r < H; ++r) (void)hipMemsetAsync(dWf_h + (size_t)r * ld_dwf, 0, H * sizeof(float), s);
+        rc = ggpm_gemm_tn_pair_grouped(H, H, E1, Hp, nq > 0 ? 4 : 3, pp, stream);
+        if (rc) return rc;
+        GGPM_CHECK_LAUNCH();
+        return GGPM_OK;
+    }
     // the three or four contractions in ONE launch and one reduce (they share the split-K workspace)
     ggpm_gemm_problem gp[4] = {{ggpm_slot_ptr(DI, lo - 1, slot, st16), Hp, Sl, Hp, dWi_h, ld_dwi, H, nullptr, 0, GGPM_ACT_NONE, 0},
                                {ggpm_slot_ptr(DO, lo - 1, slot, st16), Hp, Sl, Hp, dWo_h, ld_dwo, H, nullptr, 0, GGPM_ACT_NONE, 0},

@@ -310,7 +310,7 @@ typedef struct ggpm_level_opts {
      * stated, which the caller vouches for):
      * run_depth -- dense training forward: issue only steps 1 .. run_depth of `depth` (0 / >= depth: all of them).  Message
      *   passing on a tree reaches a fixed point after as many steps as the longest dependency chain; the caller then
-     *   replicates the last computed slot of every stash array.
+     *   replicates the last computed slot of every stash array, or passes fixed_slot (below) and replicates nothing.
      * lo -- dense backward / weight_grads: stop at step `lo` (<= 1: all steps).  The same acyclic structure makes the
      *   Jacobian of a tree level's recurrence nilpotent: with a longest dependency chain of C messages, d(h^{D-k}) is
      *   exactly zero for k >= C, so the backward of such a level only has to run its steps t = D .. lo with
@@ -332,6 +332,17 @@ typedef struct ggpm_level_opts {
      * documented at ggpm_gru_forward, all `depth` steps run and the depth loop stays fp32. */
     float* h_out;
     float* c_out;
+    /* Driver-internal, dense fp32 training calls of a tree-side level that reached its fixed point (run_depth = C + 1 of
+     * `depth` = D steps, D >= 2C, so lo - 1 >= run_depth - 1): fixed_slot = run_depth (0: off) means "state slots above
+     * fixed_slot and stash slots above fixed_slot - 1 alias those" -- nothing replicates them.
+     *   forward: only step fixed_slot writes its stash slot (the only one the backward reads); the state slots as ever.
+     *   backward: reads state slot min(t, fixed_slot) and stash slot min(t - 1, fixed_slot - 1) at step t; the gate
+     *     gradient stashes it writes itself keep their real slots.
+     *   weight_grads: every stash row block a step >= lo pairs with is the one settled slot X*, so the hidden-half gradients
+     *     are (sum_t D_t)^T X* -- the slot sums are kept as unevaluated fp32 pairs hi + lo (slots 0 and 1 of each gate
+     *     gradient stash, free below lo - 1 >= 2) and contracted as [hi; lo]^T [X*; X*], K = 2 E1 instead of C E1.
+     * A level's forward, backward and weight_grads pass the same value. */
+    int fixed_slot;
 } ggpm_level_opts;
 
 /* ------------------------------------------------------------------ GRU message function
