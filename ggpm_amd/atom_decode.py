@@ -461,7 +461,12 @@ def _vp(addr: int) -> ctypes.c_void_p:
     return ctypes.c_void_p(addr)
 
 
-def _full_level(plan: AtomPlan, cell: str, depth: int, H: int, Fdim: int, I: int, fn_all, hmess, drop, params, infer: bool):
+def _cell(kind: str, params, I: int, H: int):
+    """-> (the adapter of the message function, W_out, b_out) from the node's parameter tuple"""
+    return F_.cell_for(kind == "LSTM", params[:-2], I, H), params[-2], params[-1]
+
+
+def _full_level(plan: AtomPlan, kind: str, depth: int, H: int, Fdim: int, I: int, fn_all, hmess, drop, params, infer: bool):
     """The forward of _AtomDecode -> (pooled, cand, what the backward reads or None, device tables).  ``infer``: the
     forward-only form -- every step's depth loop in two ping-pong slots, its final state written to one of two level-wide
     buffers (ggpm_level_opts.h_out), no stashes; the same launches otherwise, so the same outputs bit for bit."""
@@ -472,21 +477,13 @@ def _full_level(plan: AtomPlan, cell: str, depth: int, H: int, Fdim: int, I: int
     Hp = F_.padded_hidden(H)
     E1, T = plan.E1, plan.T
     f32 = dict(dtype=torch.float32, device=dev)
-    lstm = cell == "LSTM"
-    G = 4 if lstm else 3
-    if lstm:
-        Wi, bi, Wo_g, bo_g, Wu, bu_g, Wf, bf, Wout, bout = params
-        gates = ((Wi, bi), (Wo_g, bo_g), (Wu, bu_g), (Wf, bf))
-    else:
-        Wz, bz, Wr, Ur, bu, Wh, bh, Wout, bout = params
-        gates = ((Wz, bz), (Wr, None), (Wh, bh))
+    cell, Wout, bout = _cell(kind, params, I, H)
+    lstm, G = cell.G == 4, cell.G
     # hoisted gate input projections of ALL bond messages (step and depth invariant)
     X = torch.empty(G, E1, Hp, **f32)
-    for k, (W, b) in enumerate(gates):
-        F_.gemm(0, 1, E1, H, I, hmess, F_._ld(hmess), W, W.stride(0), X[k], Hp, Hp, bias=b)
+    cell.project_inputs(hmess, F_._ld(hmess), E1, X)
     if infer:
-        Hs, Qs = torch.empty(2, E1, Hp, **f32), torch.empty(2, E1, Hp, **f32)
-        Cs = torch.empty(2, E1, Hp, **f32) if lstm else None
+        Hs, Cs, Qs, St = cell.alloc_state(E1, depth, save=False)
         hbuf = torch.empty(2, E1, Hp, **f32)
         cbuf = torch.empty(2, E1, Hp, **f32) if lstm else None
     else:
@@ -500,7 +497,7 @@ def _full_level(plan: AtomPlan, cell: str, depth: int, H: int, Fdim: int, I: int
     NEI = torch.empty(ns_tot, Hp, **f32)
     pooled = torch.empty(n_inst, Hp, **f32)
     cand = torch.zeros(max(plan.n_cand, 1), Hp, **f32)
-    wpack = torch.empty(int(lib.ggpm_lstm_pack_floats(H) if lstm else lib.ggpm_gru_pack_floats(H)), **f32)
+    wpack = cell.alloc_pack()
     s = F_._stream()
     frz = D["frozen"]
     ldF, ldwo = F_._ld(fn_all), Wout.stride(0)
@@ -509,24 +506,16 @@ def _full_level(plan: AtomPlan, cell: str, depth: int, H: int, Fdim: int, I: int
         a0, a1, i0, i1 = plan.aoff[t], plan.aoff[t + 1], plan.ioff[t], plan.ioff[t + 1]
         ns, ni = a1 - a0, i1 - i0
         if infer:
-            Hs_t, Qs_t, Cs_t, st = Hs, Qs, Cs, (None,) * 5
+            Hs_t, Cs_t, Qs_t, st = Hs, Cs, Qs, St
             opts = ctypes.byref(F_.LevelOpts(h_out=hbuf[t & 1].data_ptr(),
                                              c_out=cbuf[t & 1].data_ptr() if lstm else None))
         else:
-            Hs_t, Qs_t, Cs_t, st, opts = Hs[t], Qs[t], Cs[t] if lstm else None, St[t], None
+            Hs_t, Cs_t, Qs_t, st, opts = Hs[t], Cs[t] if lstm else None, Qs[t], St[t], None
+        cell.sparse_forward(rows=E1, depth=depth, h_in=h_prev, c_in=c_prev, frozen=frz[t], X=X,
+                            pred=(ptr[("pred_rp", t)], ptr[("pred_col", t)]), Hs=Hs_t, Cs=Cs_t, Qs=Qs_t, St=st, wpack=wpack,
+                            save=not infer, opts=opts, stream=s)
         if lstm:
-            _lib.check(lib.ggpm_lstm_sparse_forward(
-                E1, H, depth, P(h_prev), P(c_prev), P(frz[t]), P(X[0]), P(X[1]), P(X[2]), P(X[3]), P(Wi[:, I:]),
-                Wi.stride(0), P(Wo_g[:, I:]), Wo_g.stride(0), P(Wu[:, I:]), Wu.stride(0), P(Wf[:, I:]), Wf.stride(0),
-                _vp(ptr[("pred_rp", t)]), _vp(ptr[("pred_col", t)]), P(Hs_t), P(Cs_t), P(Qs_t), P(st[0]), P(st[1]),
-                P(st[2]), P(st[3]), P(st[4]), P(wpack), int(not infer), opts, s), "lstm_sparse_forward")
             c_prev = cbuf[t & 1] if infer else Cs[t, depth]
-        else:
-            _lib.check(lib.ggpm_gru_sparse_forward(
-                E1, H, depth, P(h_prev), P(frz[t]), P(X[0]), P(X[1]), P(X[2]), P(Wz[:, I:]), Wz.stride(0), P(Ur),
-                Ur.stride(0), P(bu), P(Wh[:, I:]), Wh.stride(0), _vp(ptr[("pred_rp", t)]), _vp(ptr[("pred_col", t)]),
-                P(Hs_t), P(Qs_t), P(st[0]), P(st[1]), P(st[2]), P(st[3]), P(st[4]), P(wpack), int(not infer), opts, s),
-                "gru_sparse_forward")
         h_prev = hbuf[t & 1] if infer else Hs[t, depth]
         nei, node = NEI[a0:a1], NODE[a0:a1]
         _lib.check(lib.ggpm_segment_sum(P(h_prev), Hp, _vp(ptr[("agr_rp", t)]), _vp(ptr[("agr_col", t)]), ns, H,
@@ -560,23 +549,18 @@ class _AtomDecode(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_pooled, d_cand):
         lib = _lib.load()
-        plan, (cell, depth, H, Fdim, I), drop = ctx.plan, ctx.meta, ctx.drop
-        lstm = cell == "LSTM"
+        plan, (kind, depth, H, Fdim, I), drop = ctx.plan, ctx.meta, ctx.drop
+        lstm = kind == "LSTM"
         sv = list(ctx.saved_tensors)
         fn_all, hmess, X, Hs, Qs, St, NODE, NEI = sv[:8]
         Cs = sv[8] if lstm else None
-        params = sv[9:] if lstm else sv[8:]
+        cell, Wout, _ = _cell(kind, sv[9:] if lstm else sv[8:], I, H)
         D = ctx.keep
         ptr, P = D["ptr"], F_._p
         dev = hmess.device
         Hp = F_.padded_hidden(H)
-        E1, T = plan.E1, plan.T
+        E1, T, G = plan.E1, plan.T, cell.G
         f32 = dict(dtype=torch.float32, device=dev)
-        G = 4 if lstm else 3
-        if lstm:
-            Wi, bi, Wo_g, bo_g, Wu, bu_g, Wf, bf, Wout, bout = params
-        else:
-            Wz, bz, Wr, Ur, bu, Wh, bh, Wout, bout = params
         d_pooled = d_pooled.contiguous()
         d_cand = d_cand.contiguous()
         s = F_._stream()
@@ -587,11 +571,10 @@ class _AtomDecode(torch.autograd.Function):
         dX = torch.empty(G, E1, Hp, **f32)
         dH, dH2 = torch.zeros(E1, Hp, **f32), torch.empty(E1, Hp, **f32)
         dC, dC2 = (torch.zeros(E1, Hp, **f32), torch.empty(E1, Hp, **f32)) if lstm else (None, None)
-        nh = 4 if lstm else 3                                   # hidden-half weight gradients (+ GRU: b_u)
-        acc = [torch.zeros(H, H, **f32) for _ in range(nh)] + ([] if lstm else [torch.zeros(H, **f32)])
-        tmp = [torch.empty(H, H, **f32) for _ in range(nh)] + ([] if lstm else [torch.empty(H, **f32)])
-        wb = int((lib.ggpm_lstm_backward_workspace_bytes if lstm else lib.ggpm_gru_backward_workspace_bytes)(E1, H, depth))
-        work = torch.empty((wb + 3) // 4, **f32)
+        # hidden-half weight gradients, summed over the steps (GRU: Wz_h, U_r, Wh_h, b_u)
+        acc = [torch.zeros(H, H, **f32) for _ in range(G)] + ([] if lstm else [torch.zeros(H, **f32)])
+        tmp = [torch.empty(H, H, **f32) for _ in range(G)] + ([] if lstm else [torch.empty(H, **f32)])
+        work = cell.backward_workspace(E1, depth)
         ldwo = Wout.stride(0)
         for t in range(T - 1, -1, -1):
             a0, a1, i0, i1 = plan.aoff[t], plan.aoff[t + 1], plan.ioff[t], plan.ioff[t + 1]
@@ -611,27 +594,78 @@ class _AtomDecode(torch.autograd.Function):
             # d(state after step t) = what step t+1 passed back + the read-out's share
             _lib.check(lib.ggpm_segment_sum(P(d_nei), Hp, _vp(ptr[("agrT_rp", t)]), _vp(ptr[("agrT_col", t)]), E1, H,
                                             P(dH), Hp, 1, 0, s), "segment_sum")
-            st = St[t]
-            if lstm:
-                _lib.check(lib.ggpm_lstm_sparse_backward(
-                    E1, H, depth, P(frz[t]), P(X[3]), P(Wi[:, I:]), Wi.stride(0), P(Wo_g[:, I:]), Wo_g.stride(0),
-                    P(Wu[:, I:]), Wu.stride(0), P(Wf[:, I:]), Wf.stride(0), _vp(ptr[("pred_rp", t)]),
-                    _vp(ptr[("pred_col", t)]), _vp(ptr[("succ_rp", t)]), _vp(ptr[("succ_col", t)]), P(Hs[t]), P(Cs[t]),
-                    P(Qs[t]), P(st[0]), P(st[1]), P(st[2]), P(st[3]), P(st[4]), P(dH), P(dC), P(dH2), P(dC2), P(dX[0]),
-                    P(dX[1]), P(dX[2]), P(dX[3]), P(tmp[0]), H, P(tmp[1]), H, P(tmp[2]), H, P(tmp[3]), H, P(work),
-                    work.numel() * 4, None, s), "lstm_sparse_backward")
-                dC, dC2 = dC2, dC
-            else:
-                _lib.check(lib.ggpm_gru_sparse_backward(
-                    E1, H, depth, P(frz[t]), P(X[1]), P(Wz[:, I:]), Wz.stride(0), P(Ur), Ur.stride(0), P(Wh[:, I:]),
-                    Wh.stride(0), _vp(ptr[("pred_rp", t)]), _vp(ptr[("pred_col", t)]), _vp(ptr[("succ_rp", t)]),
-                    _vp(ptr[("succ_col", t)]), P(Hs[t]), P(Qs[t]), P(st[0]), P(st[1]), P(st[2]), P(st[3]), P(st[4]), P(dH),
-                    P(dH2), P(dX[0]), P(dX[1]), P(dX[2]), P(tmp[0]), H, P(tmp[1]), H, P(tmp[3]), P(tmp[2]), H, P(work),
-                    work.numel() * 4, None, s), "gru_sparse_backward")
+            cell.sparse_backward(rows=E1, depth=depth, frozen=frz[t], Xg=X[cell.reread],
+                                 pred=(ptr[("pred_rp", t)], ptr[("pred_col", t)]),
+                                 succ=(ptr[("succ_rp", t)], ptr[("succ_col", t)]), Hs=Hs[t], Cs=Cs[t] if lstm else None,
+                                 Qs=Qs[t], St=St[t], d_out=dH, dc_out=dC, d_in=dH2, dc_in=dC2, dX=dX, dW_hidden=tmp, work=work,
+                                 stream=s)
+            dC, dC2 = dC2, dC
             dH, dH2 = dH2, dH
             torch._foreach_add_([dX_tot] + acc, [dX] + tmp)
         # ---- parameter gradients, once
-        return (None,) * 9 + _param_grads(lstm, params, acc, dX_tot, hmess, DPRE, NEI, fn_all, H, Hp, I, Fdim, E1, ns_tot)
+        return (None,) * 9 + _param_grads(cell, Wout, acc, dX_tot, hmess, DPRE, NEI, fn_all, Fdim, E1, ns_tot)
+
+
+def _compact_prelude(plan: AtomPlan, kind: str, depth: int, H: int, I: int, hmess, params):
+    """What both compact forms do in front of their step loop: the hoisted gate input projections of ALL bond messages and
+    the rows every step needs of them (gathered step by step into ``X_all``), the weight pack, the weight arrays and the
+    descriptor of the decode driver (None with _dev.DECODE_DRIVER off).
+    -> (device tables, cell, W_out, b_out, ct, cp, X_all, wpack, W_arr, ld_arr, desc, what desc names)"""
+    dev = hmess.device
+    D = plan.to_device(dev)
+    cell, Wout, bout = _cell(kind, params, I, H)
+    G, Hp, E1 = cell.G, cell.Hp, plan.E1
+    ct, cp = plan.compact_device(depth, G, dev)
+    f32 = dict(dtype=torch.float32, device=dev)
+    X = torch.empty(G, E1, Hp, **f32)
+    cell.project_inputs(hmess, F_._ld(hmess), E1, X)
+    X_all = torch.empty(G * ct["Ftot"], Hp, **f32)
+    _lib.check(_lib.load().ggpm_gather_rows(F_._p(X), Hp, _vp(cp["xrows"]), G * ct["Ftot"], Hp, F_._p(X_all), Hp, 0, 0,
+                                            F_._stream()), "gather_rows")
+    W_arr, ld_arr = cell.hidden_weight_arrays()
+    desc, keep = _decode_steps(plan, D, ct, cp, H, depth, G == 4) if _dev.DECODE_DRIVER else (None, None)
+    return D, cell, Wout, bout, ct, cp, X_all, cell.alloc_pack(), W_arr, ld_arr, desc, keep
+
+
+def _readout_stage(plan: AtomPlan, cp, state_src, agr_col, fn_all, Wout, bout, Fdim: int, H: int, drop, deferred: bool,
+                   what: str):
+    """Read-out of all steps at once: incoming messages (at their step's time) -> atoms -> clusters / candidates.
+    ``state_src``: the buffer that holds every step's final states; ``agr_col``: the column array of the read-out CSR in that
+    buffer's row numbering.  ``deferred``: the step loop is still being issued by the worker, so the read-out follows it
+    after the join, in ``finish``.  -> (pooled, cand, NODE, NEI, finish or None)"""
+    lib, P = _lib.load(), F_._p
+    dev = fn_all.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    Hp = F_.padded_hidden(H)
+    ns_tot, n_inst = plan.aoff[-1], plan.ioff[-1]
+    NEI = torch.empty(ns_tot, Hp, **f32)
+    NODE = torch.empty(ns_tot, Hp, **f32)
+    pooled = torch.empty(n_inst, Hp, **f32)
+    cand = torch.empty(max(plan.n_cand, 1), Hp, **f32)
+    ldF, ldwo = F_._ld(fn_all), Wout.stride(0)
+    stream_obj = torch.cuda.current_stream(dev)
+
+    def readout():
+        s_ = F_._stream()
+        _lib.check(lib.ggpm_segment_sum(P(state_src), Hp, _vp(cp["agr_rp"]), agr_col, ns_tot, H, P(NEI), Hp, 0, Hp, s_),
+                   "segment_sum")
+        F_.gemm_ksegments(1, ns_tot, H, [fn_all, NEI], [ldF, Hp], [Wout, Wout[:, Fdim:]], [ldwo, ldwo], [Fdim, H], NODE, Hp,
+                          Hp, bias=bout, act=F_.ACT_RELU)
+        if drop is not None:
+            _lib.check(lib.ggpm_dropout(P(NODE), ns_tot, H, Hp, drop[0], drop[1], drop[2], 0, s_), "dropout")
+        _lib.check(lib.ggpm_segment_sum(P(NODE), Hp, _vp(cp["pool_rp"]), _vp(cp["pool_col"]), n_inst, H, P(pooled), Hp, 0, Hp,
+                                        s_), "segment_sum")
+        _lib.check(lib.ggpm_gather_rows(P(NODE), Hp, _vp(cp["cand_idx"]), max(plan.n_cand, 1), H, P(cand), Hp, 0, Hp, s_),
+                   "gather_rows")
+
+    def finish():
+        _join_worker(what)
+        with torch.cuda.stream(stream_obj):
+            readout()
+
+    if not deferred:
+        readout()
+    return pooled, cand, NODE, NEI, (finish if deferred else None)
 
 
 class _AtomDecodeCompact(torch.autograd.Function):
@@ -641,7 +675,7 @@ class _AtomDecodeCompact(torch.autograd.Function):
     once over the stacked stashes."""
 
     @staticmethod
-    def launch(plan: AtomPlan, cell: str, depth: int, H: int, Fdim: int, I: int, fn_all, hmess, drop, params,
+    def launch(plan: AtomPlan, kind: str, depth: int, H: int, Fdim: int, I: int, fn_all, hmess, drop, params,
                infer: bool = False) -> dict:
         """Everything the forward computes, issued now (no autograd node): -> state for ``forward(..., state, *params)``.
         ``HierMPNDecoder.start_atom_level`` calls this BEFORE the encoder runs and creates the node later, behind the
@@ -651,109 +685,48 @@ class _AtomDecodeCompact(torch.autograd.Function):
         ping-pong scratch and only the final state of its rows is kept, at its F ids (ggpm_decode_steps_infer) -- no
         Hs_all / Qs_all / St_all; the read-out reads those rows (``_agr_f_col``).  Same launches, same outputs."""
         if infer:
-            return _launch_infer(plan, cell, depth, H, Fdim, I, fn_all, hmess, drop, params)
-        lib = _lib.load()
-        dev = hmess.device
-        D = plan.to_device(dev)
-        ptr, P = D["ptr"], F_._p
-        Hp = F_.padded_hidden(H)
-        E1, T = plan.E1, plan.T
-        f32 = dict(dtype=torch.float32, device=dev)
-        lstm = cell == "LSTM"
-        G = 4 if lstm else 3
-        ct, cp = plan.compact_device(depth, G, dev)
-        if lstm:
-            Wi, bi, Wo_g, bo_g, Wu, bu_g, Wf, bf, Wout, bout = params
-            gates = ((Wi, bi), (Wo_g, bo_g), (Wu, bu_g), (Wf, bf))
-        else:
-            Wz, bz, Wr, Ur, bu, Wh, bh, Wout, bout = params
-            gates = ((Wz, bz), (Wr, None), (Wh, bh))
+            return _launch_infer(plan, kind, depth, H, Fdim, I, fn_all, hmess, drop, params)
+        lib, P = _lib.load(), F_._p
+        D, cell, Wout, bout, ct, cp, X_all, wpack, W_arr, ld_arr, desc, _keep = _compact_prelude(plan, kind, depth, H, I, hmess,
+                                                                                                params)
+        ptr, Hp, G, lstm = D["ptr"], cell.Hp, cell.G, cell.G == 4
+        f32 = dict(dtype=torch.float32, device=hmess.device)
         s = F_._stream()
-        # hoisted gate input projections of ALL bond messages, then the rows every step needs, step by step
-        X = torch.empty(G, E1, Hp, **f32)
-        for k, (W, b) in enumerate(gates):
-            F_.gemm(0, 1, E1, H, I, hmess, F_._ld(hmess), W, W.stride(0), X[k], Hp, Hp, bias=b)
-        foff, Ftot = ct["foff"], ct["Ftot"]
-        X_all = torch.empty(G * Ftot, Hp, **f32)
-        _lib.check(lib.ggpm_gather_rows(P(X), Hp, _vp(cp["xrows"]), G * Ftot, Hp, P(X_all), Hp, 0, 0, s), "gather_rows")
+        foff = ct["foff"]
         roff, qoff = plan.row_offsets(depth)
         Hs_all = torch.empty(qoff[-1], Hp, **f32)
         Cs_all = torch.empty(qoff[-1], Hp, **f32) if lstm else None
         Qs_all = torch.empty(roff[-1], Hp, **f32)
         St_all = torch.empty(5, roff[-1], Hp, **f32)
-        wpack = torch.empty(int(lib.ggpm_lstm_pack_floats(H) if lstm else lib.ggpm_gru_pack_floats(H)), **f32)
         frz_loc = D["frozen_loc"].data_ptr()
-        if lstm:
-            hw = ((Wi, I), (Wo_g, I), (Wu, I), (Wf, I))
-        else:
-            hw = ((Wz, I), (Ur, 0), (Wh, I))
-        W_arr = _lib.array_type(ctypes.c_void_p, 4)(*[w[:, c:].data_ptr() for w, c in hw])
-        ld_arr = _lib.array_type(ctypes.c_int, 4)(*[w.stride(0) for w, _ in hw])
         deferred = False
         if _dev.DECODE_DRIVER:         # the whole step loop as one C call (csrc/decode.hip)
-            desc, _keep = _decode_steps(plan, D, ct, cp, H, depth, lstm)
             tmp = torch.empty(2 * max(plan.nloc), Hp, **f32)
             fn = lib.ggpm_decode_steps_forward_async if _dev.ATOM_ASYNC else lib.ggpm_decode_steps_forward
             _lib.check(fn(
-                ctypes.byref(desc), W_arr, ld_arr, None if lstm else P(bu), P(X_all), P(Hs_all), P(Cs_all) if lstm else None,
-                P(Qs_all), P(St_all), St_all.stride(0), P(wpack), P(tmp), s), "decode_steps_forward")
+                ctypes.byref(desc), W_arr, ld_arr, P(cell.b_u), P(X_all), P(Hs_all), P(Cs_all), P(Qs_all), P(St_all),
+                St_all.stride(0), P(wpack), P(tmp), s), "decode_steps_forward")
             if _dev.ATOM_ASYNC:
                 deferred = True
                 _INFLIGHT.append((desc, _keep, X_all, Hs_all, Cs_all, Qs_all, St_all, wpack, tmp, params))
         packed = ctypes.byref(F_.LevelOpts(weights_packed=1)) if _dev.PACK_ONCE else None
-        for t in (() if _dev.DECODE_DRIVER else range(T)):
+        for t in (() if _dev.DECODE_DRIVER else range(plan.T)):
             n = plan.nloc[t]
             src = _vp(cp[("srcH", t)])
             h_in = torch.empty(n, Hp, **f32)
             _lib.check(lib.ggpm_gather_rows(P(Hs_all), Hp, src, n, Hp, P(h_in), Hp, 0, 0, s), "gather_rows")
-            x = X_all[G * foff[t]:G * foff[t + 1]].view(G, n, Hp)
-            hs, qs = Hs_all[qoff[t]:qoff[t + 1]], Qs_all[roff[t]:roff[t + 1]]
-            st = St_all[:, roff[t]:roff[t + 1]]
-            fz, rp, col = _vp(frz_loc + plan.floc_off[t]), _vp(ptr[("lpred_rp", t)]), _vp(ptr[("lpred_col", t)])
-            opts = packed if t > 0 else None        # same weights, same `wpack`: packed by the first step
+            c_in = torch.empty(n, Hp, **f32) if lstm else None
             if lstm:
-                c_in = torch.empty(n, Hp, **f32)
                 _lib.check(lib.ggpm_gather_rows(P(Cs_all), Hp, src, n, Hp, P(c_in), Hp, 0, 0, s), "gather_rows")
-                _lib.check(lib.ggpm_lstm_sparse_forward(
-                    n, H, depth, P(h_in), P(c_in), fz, P(x[0]), P(x[1]), P(x[2]), P(x[3]), P(Wi[:, I:]),
-                    Wi.stride(0), P(Wo_g[:, I:]), Wo_g.stride(0), P(Wu[:, I:]), Wu.stride(0), P(Wf[:, I:]), Wf.stride(0),
-                    rp, col, P(hs), P(Cs_all[qoff[t]:qoff[t + 1]]), P(qs), P(st[0]), P(st[1]), P(st[2]), P(st[3]), P(st[4]),
-                    P(wpack), 1, opts, s), "lstm_sparse_forward")
-            else:
-                _lib.check(lib.ggpm_gru_sparse_forward(
-                    n, H, depth, P(h_in), fz, P(x[0]), P(x[1]), P(x[2]), P(Wz[:, I:]), Wz.stride(0), P(Ur),
-                    Ur.stride(0), P(bu), P(Wh[:, I:]), Wh.stride(0), rp, col, P(hs), P(qs), P(st[0]), P(st[1]), P(st[2]),
-                    P(st[3]), P(st[4]), P(wpack), 1, opts, s), "gru_sparse_forward")
-        # ---- read-out of all steps at once: incoming messages (at their step's time) -> atoms -> clusters / candidates
-        ns_tot, n_inst = plan.aoff[-1], plan.ioff[-1]
-        NEI = torch.empty(ns_tot, Hp, **f32)
-        NODE = torch.empty(ns_tot, Hp, **f32)
-        pooled = torch.empty(n_inst, Hp, **f32)
-        cand = torch.empty(max(plan.n_cand, 1), Hp, **f32)
-        ldF, ldwo = F_._ld(fn_all), Wout.stride(0)
-        stream_obj = torch.cuda.current_stream(dev)
-
-        def readout():
-            s_ = F_._stream()
-            _lib.check(lib.ggpm_segment_sum(P(Hs_all), Hp, _vp(cp["agr_rp"]), _vp(cp["agr_col"]), ns_tot, H, P(NEI), Hp, 0, Hp, s_),
-                       "segment_sum")
-            F_.gemm_ksegments(1, ns_tot, H, [fn_all, NEI], [ldF, Hp], [Wout, Wout[:, Fdim:]], [ldwo, ldwo], [Fdim, H], NODE, Hp,
-                              Hp, bias=bout, act=F_.ACT_RELU)
-            if drop is not None:
-                _lib.check(lib.ggpm_dropout(P(NODE), ns_tot, H, Hp, drop[0], drop[1], drop[2], 0, s_), "dropout")
-            _lib.check(lib.ggpm_segment_sum(P(NODE), Hp, _vp(cp["pool_rp"]), _vp(cp["pool_col"]), n_inst, H, P(pooled), Hp, 0, Hp,
-                                            s_), "segment_sum")
-            _lib.check(lib.ggpm_gather_rows(P(NODE), Hp, _vp(cp["cand_idx"]), max(plan.n_cand, 1), H, P(cand), Hp, 0, Hp, s_),
-                       "gather_rows")
-
-        finish = None
-        if deferred:        # the loop is still being issued by the worker: the read-out follows it after the join
-            def finish():
-                _join_worker("decode_join (forward)")
-                with torch.cuda.stream(stream_obj):
-                    readout()
-        else:
-            readout()
+            cell.sparse_forward(rows=n, depth=depth, h_in=h_in, c_in=c_in, frozen=frz_loc + plan.floc_off[t],
+                                X=X_all[G * foff[t]:G * foff[t + 1]].view(G, n, Hp),
+                                pred=(ptr[("lpred_rp", t)], ptr[("lpred_col", t)]), Hs=Hs_all[qoff[t]:qoff[t + 1]],
+                                Cs=Cs_all[qoff[t]:qoff[t + 1]] if lstm else None, Qs=Qs_all[roff[t]:roff[t + 1]],
+                                St=St_all[:, roff[t]:roff[t + 1]], wpack=wpack, save=True,
+                                opts=packed if t > 0 else None,       # same weights, same `wpack`: packed by the first step
+                                stream=s)
+        pooled, cand, NODE, NEI, finish = _readout_stage(plan, cp, Hs_all, _vp(cp["agr_col"]), fn_all, Wout, bout, Fdim, H, drop,
+                                                         deferred, "decode_join (forward)")
         return dict(pooled=pooled, cand=cand, finish=finish, keep=(D, ct, cp), lstm=lstm,
                     saved=(fn_all, hmess, NODE, NEI, X_all, Hs_all, Qs_all, St_all) + ((Cs_all,) if lstm else ()))
 
@@ -780,23 +753,19 @@ class _AtomDecodeCompact(torch.autograd.Function):
         flush_after_post = _dev.DECODE_DRIVER and _dev.ATOM_ASYNC
         if not flush_after_post:
             F_.flush_deferred_early()
-        plan, (cell, depth, H, Fdim, I), drop = ctx.plan, ctx.meta, ctx.drop
-        lstm = cell == "LSTM"
+        plan, (kind, depth, H, Fdim, I), drop = ctx.plan, ctx.meta, ctx.drop
+        lstm = kind == "LSTM"
         sv = list(ctx.saved_tensors)
         fn_all, hmess, NODE, NEI, X_all, Hs_all, Qs_all, St_all = sv[:8]
         Cs_all = sv[8] if lstm else None
         params = sv[9:] if lstm else sv[8:]
+        cell, Wout, _ = _cell(kind, params, I, H)
         D, ct, cp = ctx.keep
         ptr, P = D["ptr"], F_._p
         dev = hmess.device
         Hp = F_.padded_hidden(H)
-        E1, T = plan.E1, plan.T
+        E1, T, G = plan.E1, plan.T, cell.G
         f32 = dict(dtype=torch.float32, device=dev)
-        G = 4 if lstm else 3
-        if lstm:
-            Wi, bi, Wo_g, bo_g, Wu, bu_g, Wf, bf, Wout, bout = params
-        else:
-            Wz, bz, Wr, Ur, bu, Wh, bh, Wout, bout = params
         d_pooled, d_cand = d_pooled.contiguous(), d_cand.contiguous()
         s = F_._stream()
         foff, Ftot = ct["foff"], ct["Ftot"]
@@ -824,36 +793,25 @@ class _AtomDecodeCompact(torch.autograd.Function):
         # lines up with the depth + 1 state slots): contracted once behind the loop
         DG_all = torch.empty(3 if lstm else 2, roff[-1], Hp, **f32)
         DQ_all = torch.zeros(qoff[-1], Hp, **f32)
-        nh = 4 if lstm else 3                                   # hidden-half weight gradients (+ GRU: b_u)
         # the [H, I + H] gradient buffers of the gate weights exist from the start: the stacked contractions write their
-        # hidden halves in place (leading dimension I + H), the grouped input-half launch fills the rest -- no copies
-        gate_ws = (Wi, Wo_g, Wu, Wf) if lstm else (Wz, Wr, Wh)
-        bufs = [torch.empty_like(w) for w in gate_ws]
-        if lstm:
-            acc = [b[:, I:] for b in bufs]
-        else:           # acc order of the GRU: Wz_h, U_r, Wh_h, b_u (W_r has no hidden half: U_r is its own matrix)
-            acc = [bufs[0][:, I:], torch.empty(H, H, **f32), bufs[2][:, I:], torch.empty(H, **f32)]
+        # hidden halves (``acc``; GRU: Wz_h, U_r, Wh_h, b_u) in place (leading dimension I + H), the grouped input-half launch
+        # fills the rest -- no copies
+        bufs, acc = cell.dW_buffers()
         nmax = max(plan.nloc)
-        wb = int((lib.ggpm_lstm_backward_workspace_bytes if lstm else lib.ggpm_gru_backward_workspace_bytes)(nmax, H, depth))
-        work = torch.empty((wb + 3) // 4, **f32)
+        work = cell.backward_workspace(nmax, depth)
         frz_loc = D["frozen_loc"].data_ptr()
         params_ref = ctx.params_ref
         go_async = (_dev.DECODE_DRIVER and _dev.ATOM_ASYNC and F_.can_publish(*params_ref) and all(ctx.needs_input_grad[10:]))
         if _dev.DECODE_DRIVER:         # the whole step loop as one C call (csrc/decode.hip)
-            if lstm:
-                hw = ((Wi, I), (Wo_g, I), (Wu, I), (Wf, I))
-            else:
-                hw = ((Wz, I), (Ur, 0), (Wh, I))
-            W_arr = _lib.array_type(ctypes.c_void_p, 4)(*[w[:, c:].data_ptr() for w, c in hw])
-            ld_arr = _lib.array_type(ctypes.c_int, 4)(*[w.stride(0) for w, _ in hw])
+            W_arr, ld_arr = cell.hidden_weight_arrays()
             desc, _keep = _decode_steps(plan, D, ct, cp, H, depth, lstm)
             tmp = torch.empty(2 * nmax, Hp, **f32)
-            dW_arr = _lib.array_type(ctypes.c_void_p, 4)(*([a.data_ptr() for a in acc] + ([] if len(acc) == 4 else [0])))
+            dW_arr = _lib.array_type(ctypes.c_void_p, 4)(*[a.data_ptr() for a in acc])
             fn = lib.ggpm_decode_steps_backward_async if go_async else lib.ggpm_decode_steps_backward
             _lib.check(fn(
-                ctypes.byref(desc), W_arr, ld_arr, P(X_all), P(Hs_all), P(Cs_all) if lstm else None, P(Qs_all), P(St_all),
-                St_all.stride(0), P(dF), P(dCF) if lstm else None, P(dX_all), P(DG_all), DG_all.stride(0), P(DQ_all), dW_arr,
-                P(work), work.numel() * 4, P(tmp), s), "decode_steps_backward")
+                ctypes.byref(desc), W_arr, ld_arr, P(X_all), P(Hs_all), P(Cs_all), P(Qs_all), P(St_all), St_all.stride(0),
+                P(dF), P(dCF), P(dX_all), P(DG_all), DG_all.stride(0), P(DQ_all), dW_arr, P(work), work.numel() * 4, P(tmp),
+                s), "decode_steps_backward")
             if go_async:
                 _INFLIGHT.append((desc, _keep, sv, dF, dCF, dX_all, DG_all, DQ_all, acc, work, tmp))
         F_.mark("bwd: atom loop posted")
@@ -863,11 +821,7 @@ class _AtomDecodeCompact(torch.autograd.Function):
         for t in (() if _dev.DECODE_DRIVER else range(T - 1, -1, -1)):
             n = plan.nloc[t]
             dhd, dhin = dF[foff[t]:foff[t + 1]], torch.empty(n, Hp, **f32)
-            dx = dX_all[G * foff[t]:G * foff[t + 1]].view(G, n, Hp)
-            xg = X_all[G * foff[t]:G * foff[t + 1]].view(G, n, Hp)[3 if lstm else 1]
-            hs, qs, st = Hs_all[qoff[t]:qoff[t + 1]], Qs_all[roff[t]:roff[t + 1]], St_all[:, roff[t]:roff[t + 1]]
-            fz = _vp(frz_loc + plan.floc_off[t])
-            csr = (_vp(ptr[("lpred_rp", t)]), _vp(ptr[("lpred_col", t)]), _vp(ptr[("lsucc_rp", t)]), _vp(ptr[("lsucc_col", t)]))
+            dcin = torch.empty(n, Hp, **f32) if lstm else None
             srcF = _vp(cp[("srcF", t)])
             # the stashes go to the stacked buffers, contracted once in tail(); same weights, same `work`: the transposes were
             # packed by the first call
@@ -875,21 +829,16 @@ class _AtomDecodeCompact(torch.autograd.Function):
             stash = (DG_all[0, roff[t]:].data_ptr(), DG_all[1, roff[t]:].data_ptr()) + \
                 ((DG_all[2, roff[t]:].data_ptr(), dq) if lstm else (dq, None))
             opts = F_.LevelOpts(weights_packed=int(t < T - 1 and _dev.PACK_ONCE), defer_stash=stash)
+            cell.sparse_backward(rows=n, depth=depth, frozen=frz_loc + plan.floc_off[t],
+                                 Xg=X_all[G * foff[t]:G * foff[t + 1]].view(G, n, Hp)[cell.reread],
+                                 pred=(ptr[("lpred_rp", t)], ptr[("lpred_col", t)]),
+                                 succ=(ptr[("lsucc_rp", t)], ptr[("lsucc_col", t)]), Hs=Hs_all[qoff[t]:qoff[t + 1]],
+                                 Cs=Cs_all[qoff[t]:qoff[t + 1]] if lstm else None, Qs=Qs_all[roff[t]:roff[t + 1]],
+                                 St=St_all[:, roff[t]:roff[t + 1]], d_out=dhd, dc_out=dCF[foff[t]:foff[t + 1]] if lstm else None,
+                                 d_in=dhin, dc_in=dcin, dX=dX_all[G * foff[t]:G * foff[t + 1]].view(G, n, Hp), dW_hidden=acc,
+                                 ld_dW=H, work=work, opts=ctypes.byref(opts), stream=s)
             if lstm:
-                dcin = torch.empty(n, Hp, **f32)
-                _lib.check(lib.ggpm_lstm_sparse_backward(
-                    n, H, depth, fz, P(xg), P(Wi[:, I:]), Wi.stride(0), P(Wo_g[:, I:]), Wo_g.stride(0), P(Wu[:, I:]),
-                    Wu.stride(0), P(Wf[:, I:]), Wf.stride(0), *csr, P(hs), P(Cs_all[qoff[t]:qoff[t + 1]]), P(qs), P(st[0]),
-                    P(st[1]), P(st[2]), P(st[3]), P(st[4]), P(dhd), P(dCF[foff[t]:foff[t + 1]]), P(dhin), P(dcin), P(dx[0]),
-                    P(dx[1]), P(dx[2]), P(dx[3]), P(acc[0]), H, P(acc[1]), H, P(acc[2]), H, P(acc[3]), H, P(work),
-                    work.numel() * 4, ctypes.byref(opts), s), "lstm_sparse_backward")
                 _lib.check(lib.ggpm_scatter_rows(P(dcin), Hp, srcF, n, Hp, P(dCF), Hp, 1, s), "scatter_rows")
-            else:
-                _lib.check(lib.ggpm_gru_sparse_backward(
-                    n, H, depth, fz, P(xg), P(Wz[:, I:]), Wz.stride(0), P(Ur), Ur.stride(0), P(Wh[:, I:]), Wh.stride(0),
-                    *csr, P(hs), P(qs), P(st[0]), P(st[1]), P(st[2]), P(st[3]), P(st[4]), P(dhd), P(dhin), P(dx[0]),
-                    P(dx[1]), P(dx[2]), P(acc[0]), H, P(acc[1]), H, P(acc[3]), P(acc[2]), H, P(work), work.numel() * 4,
-                    ctypes.byref(opts), s), "gru_sparse_backward")
             # the frozen rows' gradient goes to the step that produced their state (rows recomputed here: none)
             _lib.check(lib.ggpm_scatter_rows(P(dhin), Hp, srcF, n, Hp, P(dF), Hp, 1, s), "scatter_rows")
         # ---- parameter gradients, once
@@ -901,7 +850,7 @@ class _AtomDecodeCompact(torch.autograd.Function):
             R, RQ = roff[-1], qoff[-1]
             wsb = int(lib.ggpm_weight_grads_stacked_workspace_bytes(H, max(R, RQ)))
             ws = torch.empty((wsb + 3) // 4, **f32)
-            ld = [a.stride(0) for a in acc[:nh]]
+            ld = [a.stride(0) for a in acc[:G]]
             if lstm:        # acc: Wi_h, Wo_h, Wu_h, Wf_h; St_all[0] = S
                 _lib.check(lib.ggpm_lstm_weight_grads_stacked(
                     R, RQ, H, P(DG_all[0]), P(DG_all[1]), P(DG_all[2]), P(St_all[0]), P(DQ_all), P(Hs_all), P(acc[0]), ld[0],
@@ -910,7 +859,7 @@ class _AtomDecodeCompact(torch.autograd.Function):
                 _lib.check(lib.ggpm_gru_weight_grads_stacked(
                     R, RQ, H, P(DG_all[0]), P(St_all[1]), P(DG_all[1]), P(St_all[0]), P(DQ_all), P(Hs_all), P(acc[0]), ld[0],
                     P(acc[1]), ld[1], P(acc[3]), P(acc[2]), ld[2], P(ws), ws.numel() * 4, s_), "gru_weight_grads_stacked")
-            return _param_grads(lstm, params, acc, dX_tot, hmess, DPRE, NEI, fn_all, H, Hp, I, Fdim, E1, ns_tot, bufs=bufs)
+            return _param_grads(cell, Wout, acc, dX_tot, hmess, DPRE, NEI, fn_all, Fdim, E1, ns_tot, bufs=bufs)
 
         if go_async:
             # The loop is being issued by the worker; this node returns now so that the engine can issue the encoder's
@@ -956,140 +905,68 @@ def _agr_f_col(plan: AtomPlan, ct: dict, depth: int, device) -> torch.Tensor:
     return col
 
 
-def _launch_infer(plan: AtomPlan, cell: str, depth: int, H: int, Fdim: int, I: int, fn_all, hmess, drop, params) -> dict:
-    lib = _lib.load()
-    dev = hmess.device
-    D = plan.to_device(dev)
-    ptr, P = D["ptr"], F_._p
-    Hp = F_.padded_hidden(H)
-    E1, T = plan.E1, plan.T
-    f32 = dict(dtype=torch.float32, device=dev)
-    lstm = cell == "LSTM"
-    G = 4 if lstm else 3
-    ct, cp = plan.compact_device(depth, G, dev)
+def _launch_infer(plan: AtomPlan, kind: str, depth: int, H: int, Fdim: int, I: int, fn_all, hmess, drop, params) -> dict:
+    """The forward-only form of ``_AtomDecodeCompact.launch`` (see there)."""
+    lib, P = _lib.load(), F_._p
     params = tuple(p.detach() for p in params)
-    if lstm:
-        Wi, bi, Wo_g, bo_g, Wu, bu_g, Wf, bf, Wout, bout = params
-        gates = ((Wi, bi), (Wo_g, bo_g), (Wu, bu_g), (Wf, bf))
-    else:
-        Wz, bz, Wr, Ur, bu, Wh, bh, Wout, bout = params
-        gates = ((Wz, bz), (Wr, None), (Wh, bh))
+    D, cell, Wout, bout, ct, cp, X_all, wpack, W_arr, ld_arr, desc, _keep = _compact_prelude(plan, kind, depth, H, I, hmess, params)
+    ptr, Hp, G, lstm = D["ptr"], cell.Hp, cell.G, cell.G == 4
+    f32 = dict(dtype=torch.float32, device=hmess.device)
     s = F_._stream()
-    X = torch.empty(G, E1, Hp, **f32)
-    for k, (W, b) in enumerate(gates):
-        F_.gemm(0, 1, E1, H, I, hmess, F_._ld(hmess), W, W.stride(0), X[k], Hp, Hp, bias=b)
     foff, Ftot = ct["foff"], ct["Ftot"]
-    X_all = torch.empty(G * Ftot, Hp, **f32)
-    _lib.check(lib.ggpm_gather_rows(P(X), Hp, _vp(cp["xrows"]), G * Ftot, Hp, P(X_all), Hp, 0, 0, s), "gather_rows")
-    agr_col = _agr_f_col(plan, ct, depth, dev)
-    nmax = max(plan.nloc)
+    agr_col = _agr_f_col(plan, ct, depth, hmess.device)
     F_h = torch.empty(max(Ftot, 1), Hp, **f32)              # final state of every step's rows, by F id
     F_c = torch.empty(max(Ftot, 1), Hp, **f32) if lstm else None
-    Hs, Qs = torch.empty(2 * nmax, Hp, **f32), torch.empty(2 * nmax, Hp, **f32)
-    Cs = torch.empty(2 * nmax, Hp, **f32) if lstm else None
-    wpack = torch.empty(int(lib.ggpm_lstm_pack_floats(H) if lstm else lib.ggpm_gru_pack_floats(H)), **f32)
-    hw = ((Wi, I), (Wo_g, I), (Wu, I), (Wf, I)) if lstm else ((Wz, I), (Ur, 0), (Wh, I))
-    W_arr = _lib.array_type(ctypes.c_void_p, 4)(*[w[:, c:].data_ptr() for w, c in hw])
-    ld_arr = _lib.array_type(ctypes.c_int, 4)(*[w.stride(0) for w, _ in hw])
+    Hs, Cs, Qs, St = cell.alloc_state(max(plan.nloc), depth, save=False)       # ping-pong scratch of the largest step
     deferred = False
     if _dev.DECODE_DRIVER:
-        desc, _keep = _decode_steps(plan, D, ct, cp, H, depth, lstm)
         fn = lib.ggpm_decode_steps_infer_async if _dev.ATOM_ASYNC else lib.ggpm_decode_steps_infer
-        _lib.check(fn(ctypes.byref(desc), W_arr, ld_arr, None if lstm else P(bu), P(X_all), P(F_h), P(F_c) if lstm else None,
-                      P(Hs), P(Cs) if lstm else None, P(Qs), P(wpack), s), "decode_steps_infer")
+        _lib.check(fn(ctypes.byref(desc), W_arr, ld_arr, P(cell.b_u), P(X_all), P(F_h), P(F_c), P(Hs), P(Cs), P(Qs), P(wpack),
+                      s), "decode_steps_infer")
         if _dev.ATOM_ASYNC:
             deferred = True
             _INFLIGHT.append((desc, _keep, X_all, F_h, F_c, Hs, Cs, Qs, wpack, params))
     frz_loc = D["frozen_loc"].data_ptr()
-    for t in (() if _dev.DECODE_DRIVER else range(T)):
+    for t in (() if _dev.DECODE_DRIVER else range(plan.T)):
         n = plan.nloc[t]
         src = _vp(cp[("srcF", t)])
         h_in = torch.empty(n, Hp, **f32)
         _lib.check(lib.ggpm_gather_rows(P(F_h), Hp, src, n, Hp, P(h_in), Hp, 0, 0, s), "gather_rows")
-        x = X_all[G * foff[t]:G * foff[t + 1]].view(G, n, Hp)
-        fz, rp, col = _vp(frz_loc + plan.floc_off[t]), _vp(ptr[("lpred_rp", t)]), _vp(ptr[("lpred_col", t)])
         opts = ctypes.byref(F_.LevelOpts(weights_packed=int(t > 0 and _dev.PACK_ONCE), h_out=F_h[foff[t]].data_ptr(),
                                          c_out=F_c[foff[t]].data_ptr() if lstm else None))
+        c_in = torch.empty(n, Hp, **f32) if lstm else None
         if lstm:
-            c_in = torch.empty(n, Hp, **f32)
             _lib.check(lib.ggpm_gather_rows(P(F_c), Hp, src, n, Hp, P(c_in), Hp, 0, 0, s), "gather_rows")
-            _lib.check(lib.ggpm_lstm_sparse_forward(
-                n, H, depth, P(h_in), P(c_in), fz, P(x[0]), P(x[1]), P(x[2]), P(x[3]), P(Wi[:, I:]),
-                Wi.stride(0), P(Wo_g[:, I:]), Wo_g.stride(0), P(Wu[:, I:]), Wu.stride(0), P(Wf[:, I:]), Wf.stride(0),
-                rp, col, P(Hs), P(Cs), P(Qs), None, None, None, None, None, P(wpack), 0, opts, s), "lstm_sparse_forward")
-        else:
-            _lib.check(lib.ggpm_gru_sparse_forward(
-                n, H, depth, P(h_in), fz, P(x[0]), P(x[1]), P(x[2]), P(Wz[:, I:]), Wz.stride(0), P(Ur),
-                Ur.stride(0), P(bu), P(Wh[:, I:]), Wh.stride(0), rp, col, P(Hs), P(Qs), None, None, None, None, None,
-                P(wpack), 0, opts, s), "gru_sparse_forward")
-    ns_tot, n_inst = plan.aoff[-1], plan.ioff[-1]
-    NEI = torch.empty(ns_tot, Hp, **f32)
-    NODE = torch.empty(ns_tot, Hp, **f32)
-    pooled = torch.empty(n_inst, Hp, **f32)
-    cand = torch.empty(max(plan.n_cand, 1), Hp, **f32)
-    ldF, ldwo = F_._ld(fn_all), Wout.stride(0)
-    stream_obj = torch.cuda.current_stream(dev)
-
-    def readout():
-        s_ = F_._stream()
-        _lib.check(lib.ggpm_segment_sum(P(F_h), Hp, _vp(cp["agr_rp"]), P(agr_col), ns_tot, H, P(NEI), Hp, 0, Hp, s_),
-                   "segment_sum")
-        F_.gemm_ksegments(1, ns_tot, H, [fn_all, NEI], [ldF, Hp], [Wout, Wout[:, Fdim:]], [ldwo, ldwo], [Fdim, H], NODE, Hp,
-                          Hp, bias=bout, act=F_.ACT_RELU)
-        if drop is not None:
-            _lib.check(lib.ggpm_dropout(P(NODE), ns_tot, H, Hp, drop[0], drop[1], drop[2], 0, s_), "dropout")
-        _lib.check(lib.ggpm_segment_sum(P(NODE), Hp, _vp(cp["pool_rp"]), _vp(cp["pool_col"]), n_inst, H, P(pooled), Hp, 0, Hp,
-                                        s_), "segment_sum")
-        _lib.check(lib.ggpm_gather_rows(P(NODE), Hp, _vp(cp["cand_idx"]), max(plan.n_cand, 1), H, P(cand), Hp, 0, Hp, s_),
-                   "gather_rows")
-
-    finish = None
-    if deferred:
-        def finish():
-            _join_worker("decode_join (forward-only)")
-            with torch.cuda.stream(stream_obj):
-                readout()
-    else:
-        readout()
+        cell.sparse_forward(rows=n, depth=depth, h_in=h_in, c_in=c_in, frozen=frz_loc + plan.floc_off[t],
+                            X=X_all[G * foff[t]:G * foff[t + 1]].view(G, n, Hp),
+                            pred=(ptr[("lpred_rp", t)], ptr[("lpred_col", t)]), Hs=Hs, Cs=Cs, Qs=Qs, St=St, wpack=wpack,
+                            save=False, opts=opts, stream=s)
+    pooled, cand, _, _, finish = _readout_stage(plan, cp, F_h, P(agr_col), fn_all, Wout, bout, Fdim, H, drop, deferred,
+                                                "decode_join (forward-only)")
     return dict(pooled=pooled, cand=cand, finish=finish, keep=(D, ct, cp), lstm=lstm, saved=None, infer=True)
 
 
-def _param_grads(lstm, params, acc, dX_tot, hmess, DPRE, NEI, fn_all, H, Hp, I, Fdim, E1, ns_tot, bufs=None):
+def _param_grads(cell, Wout, acc, dX_tot, hmess, DPRE, NEI, fn_all, Fdim, E1, ns_tot, bufs=None):
     """Parameter gradients of the atom-level decode from the summed gate-input gradients, the accumulated hidden halves
-    and the stacked read-out rows (shared by both forms)."""
-    if lstm:
-        Wi, bi, Wo_g, bo_g, Wu, bu_g, Wf, bf, Wout, bout = params
-    else:
-        Wz, bz, Wr, Ur, bu, Wh, bh, Wout, bout = params
-    x_ld = F_._ld(hmess)
-
-    # input halves dW_k[:, :I] = dX_k^T hmess of all gates in ONE grouped launch (as the encoder's drivers form them)
-    gate_ws = (Wi, Wo_g, Wu, Wf) if lstm else (Wz, Wr, Wh)
-    in_place = bufs is not None             # the hidden halves are already there (written by the stacked contractions)
+    ``acc`` and the stacked read-out rows (shared by both forms).  ``bufs``: the gate weights' gradient buffers when
+    ``acc`` already are their hidden halves (written in place by the stacked contractions)."""
+    H, Hp, I = cell.H, cell.Hp, cell.I
+    in_place = bufs is not None
     if bufs is None:
-        bufs = [torch.empty_like(W) for W in gate_ws]
-    F_.gemm_grouped(1, 0, H, I, E1, [dict(A=dX_tot[k], lda=Hp, B=hmess, ldb=x_ld, C=b, ldc=b.stride(0), n_pad=I)
+        bufs = [torch.empty_like(W) for W, _ in cell.gates]
+    # input halves dW_k[:, :I] = dX_k^T hmess of all gates in ONE grouped launch (as the encoder's drivers form them)
+    F_.gemm_grouped(1, 0, H, I, E1, [dict(A=dX_tot[k], lda=Hp, B=hmess, ldb=F_._ld(hmess), C=b, ldc=b.stride(0), n_pad=I)
                                       for k, b in enumerate(bufs)], splitk=True)
-
-    def full(W, k, hidden):                 # [input half from the summed dX | accumulated hidden half]
-        dW = bufs[k]
-        if hidden is not None and not in_place:
-            dW[:, I:] = hidden
-        return dW
-
     dWout = torch.empty_like(Wout)
     F_.gemm(1, 0, H, Fdim, ns_tot, DPRE, Hp, fn_all, F_._ld(fn_all), dWout, dWout.stride(0), Fdim, splitk=True)
     F_.gemm(1, 0, H, H, ns_tot, DPRE, Hp, NEI, Hp, dWout[:, Fdim:], dWout.stride(0), H, splitk=True)
     dbout = F_.colsum(DPRE, ns_tot, H)
-    if lstm:
-        grads = []
-        for k, W in enumerate((Wi, Wo_g, Wu, Wf)):
-            grads += [full(W, k, acc[k]), F_.colsum(dX_tot[k], E1, H)]
-        grads += [dWout, dbout]
-    else:          # acc order of the GRU: Wz_h, U_r, Wh_h, b_u
-        grads = [full(Wz, 0, acc[0]), F_.colsum(dX_tot[0], E1, H), full(Wr, 1, None), acc[1], acc[3],
-                 full(Wh, 2, acc[2]), F_.colsum(dX_tot[2], E1, H), dWout, dbout]
-    return tuple(grads)
+    dbs = []
+    for k, (W, b) in enumerate(cell.gates):     # [input half from the summed dX | accumulated hidden half], gate bias
+        if not in_place and W.shape[1] > I:     # (W_r has no hidden half)
+            bufs[k][:, I:] = acc[k]
+        dbs.append(F_.colsum(dX_tot[k], E1, H) if b is not None else None)
+    return cell.grads(bufs, acc, dbs) + (dWout, dbout)
 
 
 def atom_decode_node(pre: dict):
@@ -1112,12 +989,7 @@ def atom_decode(plan: AtomPlan, graph_encoder, hnode_a: torch.Tensor, hmess_a: t
     when this returns, and the read-out behind it is enqueued by ``finish``)."""
     from .rnn import LSTM
     rnn, wo = graph_encoder.rnn, graph_encoder.W_o
-    lstm = isinstance(rnn, LSTM)
-    if lstm:
-        params = (rnn.W_i[0].weight, rnn.W_i[0].bias, rnn.W_o[0].weight, rnn.W_o[0].bias, rnn.W[0].weight, rnn.W[0].bias,
-                  rnn.W_f[0].weight, rnn.W_f[0].bias)
-    else:
-        params = (rnn.W_z.weight, rnn.W_z.bias, rnn.W_r.weight, rnn.U_r.weight, rnn.U_r.bias, rnn.W_h.weight, rnn.W_h.bias)
+    lstm, params = isinstance(rnn, LSTM), rnn.level_params()
     drop = None
     if graph_encoder.training and wo[2].p > 0:
         seed = getattr(graph_encoder, "_dropout_seed", None)           # (tests pin the seed)

@@ -525,11 +525,8 @@ def level_states(rnn, h0, hmess, dag, depth):
             pass
     I, H = rnn.input_size, rnn.hidden_size
     if isinstance(h0, tuple):
-        i, o, u, f = rnn.W_i[0], rnn.W_o[0], rnn.W[0], rnn.W_f[0]
-        return F_.lstm_sparse(h0[0], h0[1], hmess, rows, dag, i.weight, i.bias, o.weight, o.bias, u.weight, u.bias,
-                              f.weight, f.bias, depth, I, H)
-    return F_.gru_sparse(h0, hmess, rows, dag, rnn.W_z.weight, rnn.W_z.bias, rnn.W_r.weight, rnn.U_r.weight,
-                         rnn.U_r.bias, rnn.W_h.weight, rnn.W_h.bias, depth, I, H)
+        return F_.lstm_sparse(h0[0], h0[1], hmess, rows, dag, *rnn.level_params(), depth, I, H)
+    return F_.gru_sparse(h0, hmess, rows, dag, *rnn.level_params(), depth, I, H)
 
 
 class HierMPNDecoder(ScoreHeads):

@@ -823,131 +823,335 @@ def flush_deferred_early() -> None:
     _defer_flush(side=_side_stream(main.device))       # (the end-of-backward callback stays registered: it publishes)
 
 
-def _split_cols(W: torch.Tensor, I: int):
-    """(x-half view, h-half view) of a [H, I+H] gate weight; both share W's row stride."""
-    return W[:, :I], W[:, I:]
+# ----------------------------------------------------------------------------- GRU / LSTM cell adapters
+# Everything the host side knows about ONE message function: the order of its parameter tuple, its (W, b) gate pairs, the
+# hidden halves of its weights, which gate-input plane its backward re-reads, its stash set, and how the ten level entry
+# points of the C ABI (ggpm_{gru,lstm}_{forward,backward,weight_grads,sparse_forward,sparse_backward}) take all of that.
+# The autograd nodes below, tree_decode.py and atom_decode.py are written once against this surface; the adapters are the
+# only place in the package where those entry points are called.  A node builds one adapter per call (never per decode
+# step); building one is a tuple unpack.
+def _a(v) -> ctypes.c_void_p:
+    """A device argument of a level call: a tensor, None, or a raw address (the atom-level plan hands out addresses into
+    its packed upload)."""
+    return ctypes.c_void_p(v if isinstance(v, int) else 0 if v is None else v.data_ptr())
+
+
+def _csr_args(csr):
+    """(rowptr, col) arguments from a CSR or a (rowptr, col) pair of device arguments"""
+    rowptr, col = (csr.rowptr, csr.col) if isinstance(csr, CSR) else csr
+    return _a(rowptr), _a(col)
+
+
+class _Cell:
+    """What GruCell and LstmCell share.  ``params``: the cell's parameters in the order rnn.GRU / rnn.LSTM hand them to
+    ``gru_level`` / ``lstm_level`` (``level_params()``); ``gates``: the (W [H, I + H], b) pairs in the order of the
+    gate-input planes X[0..G-1].  ``dW_hidden`` of the backward calls is ``dW_buffers()[1]``: the hidden-half gradients."""
+    G = reread = None           # number of gates; index of the gate-input plane the backward re-reads
+    U_r = b_u = None            # GRU only: W_r has no hidden half, U_r [H, H] is its own matrix (with the cell's bias b_u)
+
+    def __init__(self, params, I: int, H: int):
+        self.params, self.I, self.H, self.Hp = tuple(params), I, H, padded_hidden(H)
+
+    lib = property(lambda self: _lib.load())
+
+    @property
+    def weights(self):
+        """the matrices among ``params`` (what a node saves for its backward)"""
+        return tuple(p for p in self.params if p.dim() == 2)
+
+    def _f32(self):
+        return dict(dtype=torch.float32, device=self.params[0].device)
+
+    def hidden(self):
+        """[(hidden-half view or U_r, leading dimension)] in the order the depth kernels take them"""
+        return [(W[:, self.I:], W.stride(0)) for W, _ in self.gates]
+
+    def hidden_weight_arrays(self):
+        """-> (c_void_p * 4, c_int * 4): ``hidden()`` as the decode driver takes it"""
+        hw = self.hidden()
+        return (_lib.array_type(ctypes.c_void_p, 4)(*[w.data_ptr() for w, _ in hw]),
+                _lib.array_type(ctypes.c_int, 4)(*[ld for _, ld in hw]))
+
+    def _weight_args(self, backward: bool):
+        return [v for w, ld in self.hidden() for v in (_a(w), ld)]
+
+    def _lds(self, hid, ld_dW):
+        return [ld_dW if ld_dW is not None else t.stride(0) for t in hid[:self.G]]
+
+    # ---- gate inputs
+    def project_inputs(self, x, ldx: int, rows: int, X) -> None:
+        """X[k][:rows] = x W_k[:, :I]^T + b_k: the hoisted input GEMMs (depth invariant)"""
+        for k, (W, b) in enumerate(self.gates):
+            gemm(0, 1, rows, self.H, self.I, x, ldx, W, W.stride(0), X[k], self.Hp, self.Hp, bias=b)
+
+    def input_grad(self, dX, x, rows: int) -> torch.Tensor:
+        """-> dx = sum_k dX_k W_k[:, :I], in x's layout"""
+        dx = _empty_same_layout(x)
+        for k, (W, _) in enumerate(self.gates):
+            gemm(0, 0, rows, self.I, self.H, dX[k], self.Hp, W, W.stride(0), dx, _ld(x), x.shape[1] if k == 0 else self.I,
+                 accumulate=k > 0)
+        return dx
+
+    def bias_grads(self, dX, rows: int) -> list:
+        """-> [db_k = column sums of dX_k, or None where the gate has no bias (W_r)]"""
+        return [colsum(dX[k], rows, self.H) if b is not None else None for k, (_, b) in enumerate(self.gates)]
+
+    def input_half_grads(self, dX, x, ldx: int, rows: int, bufs, interleaved: Optional[bool] = None) -> list:
+        """bufs[k][:, :I] = dX_k^T x; -> ``bias_grads``.  The launch order is the one every form has always had:
+        ``interleaved`` (each gate's column sum right behind its GEMM) is the LSTM nodes' and the tree level's, all GEMMs
+        first the GRU nodes'."""
+        H, I, Hp = self.H, self.I, self.Hp
+        interleaved = self.G == 4 if interleaved is None else interleaved
+        dbs = []
+        for k, (dW, (_, b)) in enumerate(zip(bufs, self.gates)):
+            gemm(1, 0, H, I, rows, dX[k], Hp, x, ldx, dW, dW.stride(0), I, splitk=True)
+            if interleaved:
+                dbs.append(colsum(dX[k], rows, H) if b is not None else None)
+        return dbs if interleaved else self.bias_grads(dX, rows)
+
+    # ---- buffers
+    def alloc_state(self, rows: int, depth: int, save: bool):
+        """-> Hs, Cs, Qs, St.  ``save``: every depth slot, for a backward; else two ping-pong slots and no stashes."""
+        f32, n = self._f32(), (depth + 1 if save else 2)
+        Hs = torch.empty(n, rows, self.Hp, **f32)
+        Cs = torch.empty(n, rows, self.Hp, **f32) if self.G == 4 else None
+        Qs = torch.empty(depth if save else 2, rows, self.Hp, **f32)
+        return Hs, Cs, Qs, (torch.empty(5, depth, rows, self.Hp, **f32) if save else (None,) * 5)
+
+    def alloc_pack(self) -> torch.Tensor:
+        return torch.empty(self.pack_floats(), **self._f32())
+
+    def dW_buffers(self):
+        """-> (one [H, I + H] gradient buffer per gate weight, the hidden-half gradients the backward calls write: views of
+        those buffers' columns [I, I + H); GruCell: Wz_h, U_r, Wh_h, b_u, with U_r and b_u their own tensors)"""
+        bufs = [torch.empty(W.shape, **self._f32()) for W, _ in self.gates]
+        return bufs, [b[:, self.I:] for b in bufs]
+
+
+class GruCell(_Cell):
+    """GRU (ggpm/rnn.py:5-59); params (W_z, b_z, W_r, U_r, b_u, W_h, b_h); planes X_z, X_r, X_h; stashes S, G, Z, M, R"""
+    G, reread = 3, 1
+
+    def __init__(self, params, I: int, H: int):
+        super().__init__(params, I, H)
+        W_z, b_z, W_r, self.U_r, self.b_u, W_h, b_h = self.params
+        self.gates = ((W_z, b_z), (W_r, None), (W_h, b_h))
+
+    def hidden(self):
+        (W_z, _), _, (W_h, _) = self.gates
+        return [(W_z[:, self.I:], W_z.stride(0)), (self.U_r, self.U_r.stride(0)), (W_h[:, self.I:], W_h.stride(0))]
+
+    def _weight_args(self, backward: bool):
+        (wz, ld_z), (ur, ld_u), (wh, ld_h) = self.hidden()
+        return (_a(wz), ld_z, _a(ur), ld_u) + (() if backward else (_a(self.b_u),)) + (_a(wh), ld_h)
+
+    def _dW_args(self, hid, ld_dW):
+        ld = self._lds(hid, ld_dW)
+        return _a(hid[0]), ld[0], _a(hid[1]), ld[1], _a(hid[3]), _a(hid[2]), ld[2]
+
+    def dW_buffers(self):
+        bufs, hid = super().dW_buffers()
+        f32 = self._f32()
+        return bufs, [hid[0], torch.empty(self.H, self.H, **f32), hid[2], torch.empty(self.H, **f32)]
+
+    def grads(self, bufs, hid, dbs) -> tuple:
+        """-> the gradients in ``params`` order from the gate buffers, the hidden-half list and ``bias_grads``"""
+        return bufs[0], dbs[0], bufs[1], hid[1], hid[3], bufs[2], dbs[2]
+
+    def pack_floats(self) -> int:
+        return int(self.lib.ggpm_gru_pack_floats(self.H))
+
+    def backward_workspace(self, rows: int, depth: int) -> torch.Tensor:
+        wb = int(self.lib.ggpm_gru_backward_workspace_bytes(rows, self.H, depth))
+        return torch.empty((wb + 3) // 4, **self._f32())
+
+    def forward(self, *, rows, depth, X, pred, Hs, Qs, St, wpack, save, Cs=None, opts=None, stream=None):
+        _lib.check(self.lib.ggpm_gru_forward(
+            rows, self.H, depth, *map(_a, X), *self._weight_args(False), *_csr_args(pred), _a(Hs), _a(Qs), *map(_a, St),
+            _a(wpack), int(save), opts, _stream() if stream is None else stream), "gru_forward")
+
+    def sparse_forward(self, *, rows, depth, h_in, frozen, X, pred, Hs, Qs, St, wpack, save, c_in=None, Cs=None, opts=None,
+                       stream=None):
+        _lib.check(self.lib.ggpm_gru_sparse_forward(
+            rows, self.H, depth, _a(h_in), _a(frozen), *map(_a, X), *self._weight_args(False), *_csr_args(pred), _a(Hs),
+            _a(Qs), *map(_a, St), _a(wpack), int(save), opts, _stream() if stream is None else stream), "gru_sparse_forward")
+
+    def backward(self, *, rows, depth, Xg, pred, succ, Hs, Qs, St, d_out, dX, dW_hidden, work, weight_grads, Cs=None,
+                 ld_dW=None, opts=None, stream=None):
+        _lib.check(self.lib.ggpm_gru_backward(
+            rows, self.H, depth, _a(Xg), *self._weight_args(True), *_csr_args(pred), *_csr_args(succ), _a(Hs), _a(Qs),
+            *map(_a, St), _a(d_out), *map(_a, dX), *self._dW_args(dW_hidden, ld_dW), _a(work), work.numel() * 4,
+            int(weight_grads), opts, _stream() if stream is None else stream), "gru_backward")
+
+    def weight_grads(self, *, rows, depth, Hs, St, work, dW_hidden, ld_dW=None, opts=None, stream=None):
+        _lib.check(self.lib.ggpm_gru_weight_grads(
+            rows, self.H, depth, _a(Hs), _a(St[0]), _a(St[1]), _a(work), work.numel() * 4, *self._dW_args(dW_hidden, ld_dW),
+            opts, _stream() if stream is None else stream), "gru_weight_grads")
+
+    def sparse_backward(self, *, rows, depth, frozen, Xg, pred, succ, Hs, Qs, St, d_out, d_in, dX, dW_hidden, work, Cs=None,
+                        dc_out=None, dc_in=None, ld_dW=None, opts=None, stream=None):
+        _lib.check(self.lib.ggpm_gru_sparse_backward(
+            rows, self.H, depth, _a(frozen), _a(Xg), *self._weight_args(True), *_csr_args(pred), *_csr_args(succ), _a(Hs),
+            _a(Qs), *map(_a, St), _a(d_out), _a(d_in), *map(_a, dX), *self._dW_args(dW_hidden, ld_dW), _a(work),
+            work.numel() * 4, opts, _stream() if stream is None else stream), "gru_sparse_backward")
+
+
+class LstmCell(_Cell):
+    """LSTM (ggpm/rnn.py:61-121); params (W_i, b_i, W_o, b_o, W_u, b_u, W_f, b_f); planes X_i, X_o, X_u, X_f; stashes S, I,
+    O, U, F; carries the cell state (Cs, c_in, dc_out, dc_in) beside the hidden state"""
+    G, reread = 4, 3
+
+    def __init__(self, params, I: int, H: int):
+        super().__init__(params, I, H)
+        p = self.params
+        self.gates = ((p[0], p[1]), (p[2], p[3]), (p[4], p[5]), (p[6], p[7]))
+
+    def _dW_args(self, hid, ld_dW):
+        return [v for t, ld in zip(hid, self._lds(hid, ld_dW)) for v in (_a(t), ld)]
+
+    def grads(self, bufs, hid, dbs) -> tuple:
+        """-> the gradients in ``params`` order from the gate buffers and ``bias_grads`` (``hid``: views of ``bufs``)"""
+        return tuple(g for pair in zip(bufs, dbs) for g in pair)
+
+    def pack_floats(self) -> int:
+        return int(self.lib.ggpm_lstm_pack_floats(self.H))
+
+    def backward_workspace(self, rows: int, depth: int) -> torch.Tensor:
+        wb = int(self.lib.ggpm_lstm_backward_workspace_bytes(rows, self.H, depth))
+        return torch.empty((wb + 3) // 4, **self._f32())
+
+    def forward(self, *, rows, depth, X, pred, Hs, Cs, Qs, St, wpack, save, opts=None, stream=None):
+        _lib.check(self.lib.ggpm_lstm_forward(
+            rows, self.H, depth, *map(_a, X), *self._weight_args(False), *_csr_args(pred), _a(Hs), _a(Cs), _a(Qs),
+            *map(_a, St), _a(wpack), int(save), opts, _stream() if stream is None else stream), "lstm_forward")
+
+    def sparse_forward(self, *, rows, depth, h_in, c_in, frozen, X, pred, Hs, Cs, Qs, St, wpack, save, opts=None, stream=None):
+        _lib.check(self.lib.ggpm_lstm_sparse_forward(
+            rows, self.H, depth, _a(h_in), _a(c_in), _a(frozen), *map(_a, X), *self._weight_args(False), *_csr_args(pred),
+            _a(Hs), _a(Cs), _a(Qs), *map(_a, St), _a(wpack), int(save), opts, _stream() if stream is None else stream),
+            "lstm_sparse_forward")
+
+    def backward(self, *, rows, depth, Xg, pred, succ, Hs, Cs, Qs, St, d_out, dX, dW_hidden, work, weight_grads, ld_dW=None,
+                 opts=None, stream=None):
+        _lib.check(self.lib.ggpm_lstm_backward(
+            rows, self.H, depth, _a(Xg), *self._weight_args(True), *_csr_args(pred), *_csr_args(succ), _a(Hs), _a(Cs),
+            _a(Qs), *map(_a, St), _a(d_out), *map(_a, dX), *self._dW_args(dW_hidden, ld_dW), _a(work), work.numel() * 4,
+            int(weight_grads), opts, _stream() if stream is None else stream), "lstm_backward")
+
+    def weight_grads(self, *, rows, depth, Hs, St, work, dW_hidden, ld_dW=None, opts=None, stream=None):
+        _lib.check(self.lib.ggpm_lstm_weight_grads(
+            rows, self.H, depth, _a(Hs), _a(St[0]), _a(work), work.numel() * 4, *self._dW_args(dW_hidden, ld_dW), opts,
+            _stream() if stream is None else stream), "lstm_weight_grads")
+
+    def sparse_backward(self, *, rows, depth, frozen, Xg, pred, succ, Hs, Cs, Qs, St, d_out, dc_out, d_in, dc_in, dX,
+                        dW_hidden, work, ld_dW=None, opts=None, stream=None):
+        _lib.check(self.lib.ggpm_lstm_sparse_backward(
+            rows, self.H, depth, _a(frozen), _a(Xg), *self._weight_args(True), *_csr_args(pred), *_csr_args(succ), _a(Hs),
+            _a(Cs), _a(Qs), *map(_a, St), _a(d_out), _a(dc_out), _a(d_in), _a(dc_in), *map(_a, dX),
+            *self._dW_args(dW_hidden, ld_dW), _a(work), work.numel() * 4, opts, _stream() if stream is None else stream),
+            "lstm_sparse_backward")
+
+
+def cell_for(lstm: bool, params, I: int, H: int) -> _Cell:
+    return (LstmCell if lstm else GruCell)(params, I, H)
+
+
+# ----------------------------------------------------------------------------- dense levels
+def _level_forward(ctx, cell: _Cell, x, pred: CSR, depth: int, gate_dtype: int):
+    """GRU.forward / LSTM.forward (ggpm/rnn.py:41-50, 96-108) for one level: hoisted input GEMMs + fused depth loop.
+    -> (h_D, c_D or None) as [E1, Hp] tensors (pad columns zero)."""
+    _need_gpu(x, *cell.params)
+    E1 = x.shape[0]
+    save = any(ctx.needs_input_grad)
+    X = torch.empty(cell.G, E1, cell.Hp, dtype=torch.float32, device=x.device)
+    cell.project_inputs(x, _ld(x), E1, X)
+    wpack = cell.alloc_pack()
+    Hs, Cs, Qs, St = cell.alloc_state(E1, depth, save)
+    cell.forward(rows=E1, depth=depth, X=X, pred=pred, Hs=Hs, Cs=Cs, Qs=Qs, St=St, wpack=wpack, save=save,
+                 opts=_gate_opts(gate_dtype))
+    k = depth if save else depth & 1
+    if save:
+        ctx.save_for_backward(x, *cell.weights)
+        ctx.stash = (X[cell.reread], Hs, Cs, Qs, St)
+        ctx.meta = (cell, pred, depth, gate_dtype)
+    return Hs[k], (Cs[k] if Cs is not None else None)
+
+
+def _level_backward(ctx, dHD, name: str):
+    """One autograd node per level: the backward writes the x-half and the h-half gradient of every gate weight straight
+    into ONE full-shape gradient tensor (no slice/cat/add kernels from autograd).
+    -> the gradients of (x, pred, depth, I, H, gate_dtype, *params)"""
+    x = ctx.saved_tensors[0]
+    if ctx.stash is None:
+        raise second_backward(name)
+    Xg, Hs, Cs, Qs, St = ctx.stash
+    cell, pred, depth, gate_dtype = ctx.meta
+    E1 = x.shape[0]
+    succ = pred.T
+    dHD = dHD.contiguous()
+    dX = torch.empty(cell.G, E1, cell.Hp, dtype=torch.float32, device=x.device)
+    bufs, hid = cell.dW_buffers()
+    work = cell.backward_workspace(E1, depth)
+    use_side = side_stream_enabled() and can_publish(*cell.params)
+    cell.backward(rows=E1, depth=depth, Xg=Xg, pred=pred, succ=succ, Hs=Hs, Cs=Cs, Qs=Qs, St=St, d_out=dHD, dX=dX,
+                  dW_hidden=hid, work=work, weight_grads=not use_side, opts=_gate_opts(gate_dtype))
+    ctx.stash = None
+    dx = cell.input_grad(dX, x, E1) if ctx.needs_input_grad[0] else None     # needed upstream right away: main stream
+
+    def weight_grads():
+        if use_side:
+            cell.weight_grads(rows=E1, depth=depth, Hs=Hs, St=St, work=work, dW_hidden=hid, opts=_gate_opts(gate_dtype))
+        # x-halves of the gate weights and the gate biases
+        return cell.grads(bufs, hid, cell.input_half_grads(dX, x, _ld(x), E1, bufs))
+
+    if use_side:
+        main = torch.cuda.current_stream()
+        side = _side_stream(x.device)
+        side.wait_stream(main)
+        for tns in (work, dX, Hs, St, x, *bufs, *hid):
+            tns.record_stream(side)
+        with torch.cuda.stream(side):
+            for prm, g in zip(cell.params, weight_grads()):
+                _accumulate_grad(prm, g, main)
+        _join_later(main, side)
+        return (dx,) + (None,) * (5 + len(cell.params))
+    return (dx, None, None, None, None, None, *weight_grads())
 
 
 class _GruLevel(torch.autograd.Function):
-    """GRU.forward (ggpm/rnn.py:41-50) for one level: hoisted input GEMMs + fused depth loop.
-
-    One autograd node per level: the backward writes the x-half and the h-half gradient of every gate weight
-    straight into ONE full-shape gradient tensor (no slice/cat/add kernels from autograd).
-    Returns h_D as [E1, Hp] (pad columns zero).
-    """
-
     @staticmethod
-    def forward(ctx, x, W_z, b_z, W_r, U_r, b_u, W_h, b_h, pred, depth, I, H, gate_dtype=0):
-        _need_gpu(x, W_z, b_z, W_r, U_r, b_u, W_h, b_h)
-        lib = _lib.load()
-        ctx.gate_dtype = gate_dtype
-        E1, Hp = x.shape[0], padded_hidden(H)
-        f32 = dict(dtype=torch.float32, device=x.device)
-        save = any(ctx.needs_input_grad)
-        X = torch.empty(3, E1, Hp, **f32)
-        Wz_x, Wz_h = _split_cols(W_z, I)
-        Wh_x, Wh_h = _split_cols(W_h, I)
-        ldx = _ld(x)
-        gemm(0, 1, E1, H, I, x, ldx, Wz_x, W_z.stride(0), X[0], Hp, Hp, bias=b_z)
-        gemm(0, 1, E1, H, I, x, ldx, W_r, W_r.stride(0), X[1], Hp, Hp)
-        gemm(0, 1, E1, H, I, x, ldx, Wh_x, W_h.stride(0), X[2], Hp, Hp, bias=b_h)
-        wpack = torch.empty(int(lib.ggpm_gru_pack_floats(H)), **f32)
-        if save:
-            Hs = torch.empty(depth + 1, E1, Hp, **f32)
-            Qs = torch.empty(depth, E1, Hp, **f32)
-            St = torch.empty(5, depth, E1, Hp, **f32)
-            Ss, Gs, Zs, Ms, Rs = St[0], St[1], St[2], St[3], St[4]
-        else:
-            Hs = torch.empty(2, E1, Hp, **f32)
-            Qs = torch.empty(2, E1, Hp, **f32)
-            Ss = Gs = Zs = Ms = Rs = None
-        _lib.check(lib.ggpm_gru_forward(E1, H, depth, _p(X[0]), _p(X[1]), _p(X[2]), _p(Wz_h), W_z.stride(0),
-                                        _p(U_r), U_r.stride(0), _p(b_u), _p(Wh_h), W_h.stride(0), _p(pred.rowptr),
-                                        _p(pred.col), _p(Hs), _p(Qs), _p(Ss), _p(Gs), _p(Zs), _p(Ms), _p(Rs),
-                                        _p(wpack), int(save), _gate_opts(gate_dtype), _stream()), "gru_forward")
-        if save:
-            ctx.save_for_backward(x, W_z, W_r, U_r, W_h)
-            ctx.stash = (X[1], Hs, Qs, Ss, Gs, Zs, Ms, Rs)
-            ctx.meta = (pred, depth, I, H)
-            ctx.params = (W_z, b_z, W_r, U_r, b_u, W_h, b_h)
-            return Hs[depth]
-        return Hs[depth & 1]
+    def forward(ctx, x, pred, depth, I, H, gate_dtype, *params):
+        return _level_forward(ctx, GruCell(params, I, H), x, pred, depth, gate_dtype)[0]
 
     @staticmethod
     def backward(ctx, dHD):
-        x, W_z, W_r, U_r, W_h = ctx.saved_tensors
-        if ctx.stash is None:
-            raise second_backward("gru_level")
-        Xr, Hs, Qs, Ss, Gs, Zs, Ms, Rs = ctx.stash
-        pred, depth, I, H = ctx.meta
-        lib = _lib.load()
-        E1, Hp = x.shape[0], padded_hidden(H)
-        succ = pred.T
-        dHD = dHD.contiguous()
-        f32 = dict(dtype=torch.float32, device=x.device)
-        dX = torch.empty(3, E1, Hp, **f32)
-        dW_z, dW_r, dU_r, dW_h = (torch.empty(W_z.shape, **f32), torch.empty(W_r.shape, **f32),
-                                  torch.empty(H, H, **f32), torch.empty(W_h.shape, **f32))
-        db_u = torch.empty(H, **f32)
-        Wz_x, Wz_h = _split_cols(W_z, I)
-        Wh_x, Wh_h = _split_cols(W_h, I)
-        dWz_x, dWz_h = _split_cols(dW_z, I)
-        dWh_x, dWh_h = _split_cols(dW_h, I)
-        wb = int(lib.ggpm_gru_backward_workspace_bytes(E1, H, depth))
-        work = torch.empty((wb + 3) // 4, **f32)
-        use_side = side_stream_enabled() and can_publish(*ctx.params)
-        _lib.check(lib.ggpm_gru_backward(E1, H, depth, _p(Xr), _p(Wz_h), W_z.stride(0), _p(U_r), U_r.stride(0),
-                                         _p(Wh_h), W_h.stride(0), _p(pred.rowptr), _p(pred.col), _p(succ.rowptr),
-                                         _p(succ.col), _p(Hs), _p(Qs), _p(Ss), _p(Gs), _p(Zs), _p(Ms), _p(Rs),
-                                         _p(dHD), _p(dX[0]), _p(dX[1]), _p(dX[2]), _p(dWz_h), dW_z.stride(0),
-                                         _p(dU_r), H, _p(db_u), _p(dWh_h), dW_h.stride(0), _p(work),
-                                         work.numel() * 4, 0 if use_side else 1, _gate_opts(ctx.gate_dtype), _stream()),
-                   "gru_backward")
-        ctx.stash = None
-        ldx = _ld(x)
-        dx = None
-        if ctx.needs_input_grad[0]:      # needed upstream right away: stays on the main stream
-            dx = _empty_same_layout(x)
-            gemm(0, 0, E1, I, H, dX[0], Hp, Wz_x, W_z.stride(0), dx, ldx, x.shape[1])
-            gemm(0, 0, E1, I, H, dX[1], Hp, W_r, W_r.stride(0), dx, ldx, I, accumulate=True)
-            gemm(0, 0, E1, I, H, dX[2], Hp, Wh_x, W_h.stride(0), dx, ldx, I, accumulate=True)
+        return _level_backward(ctx, dHD, "gru_level")
 
-        def weight_grads():
-            if use_side:
-                _lib.check(lib.ggpm_gru_weight_grads(E1, H, depth, _p(Hs), _p(Ss), _p(Gs), _p(work), work.numel() * 4,
-                                                     _p(dWz_h), dW_z.stride(0), _p(dU_r), H, _p(db_u), _p(dWh_h),
-                                                     dW_h.stride(0), _gate_opts(ctx.gate_dtype), _stream()), "gru_weight_grads")
-            # x-halves of the gate weights and the gate biases
-            gemm(1, 0, H, I, E1, dX[0], Hp, x, ldx, dWz_x, dW_z.stride(0), I, splitk=True)
-            gemm(1, 0, H, I, E1, dX[1], Hp, x, ldx, dW_r, dW_r.stride(0), I, splitk=True)
-            gemm(1, 0, H, I, E1, dX[2], Hp, x, ldx, dWh_x, dW_h.stride(0), I, splitk=True)
-            return colsum(dX[0], E1, H), colsum(dX[2], E1, H)
 
-        if use_side:
-            main = torch.cuda.current_stream()
-            side = _side_stream(x.device)
-            side.wait_stream(main)
-            for tns in (work, dX, Hs, Ss, x, dW_z, dW_r, dU_r, dW_h, db_u):
-                tns.record_stream(side)
-            with torch.cuda.stream(side):
-                db_z, db_h = weight_grads()
-                P_z, Pb_z, P_r, P_u, Pb_u, P_h, Pb_h = ctx.params
-                for prm, g in ((P_z, dW_z), (Pb_z, db_z), (P_r, dW_r), (P_u, dU_r), (Pb_u, db_u), (P_h, dW_h),
-                               (Pb_h, db_h)):
-                    _accumulate_grad(prm, g, main)
-            _join_later(main, side)
-            return dx, None, None, None, None, None, None, None, None, None, None, None, None
-        db_z, db_h = weight_grads()
-        return dx, dW_z, db_z, dW_r, dU_r, db_u, dW_h, db_h, None, None, None, None, None
+class _LstmLevel(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, pred, depth, I, H, gate_dtype, *params):
+        h, c = _level_forward(ctx, LstmCell(params, I, H), x, pred, depth, gate_dtype)
+        ctx.mark_non_differentiable(c)
+        return h, c
+
+    @staticmethod
+    def backward(ctx, dHD, _dC):
+        return _level_backward(ctx, dHD, "lstm_level")
 
 
 GATE_DTYPES = {"f32": 0, "fp32": 0, "bf16": 1, "f32_mfma": 2, "f32_split": 3, None: 0, 0: 0, 1: 1, 2: 2, 3: 3}
 
 
 def gru_level(x, W_z, b_z, W_r, U_r, b_u, W_h, b_h, pred: CSR, depth: int, I: int, H: int, gate_dtype=None) -> torch.Tensor:
-    return _GruLevel.apply(x, W_z, b_z, W_r, U_r, b_u, W_h, b_h, pred, depth, I, H, GATE_DTYPES[gate_dtype])
+    return _GruLevel.apply(x, pred, depth, I, H, GATE_DTYPES[gate_dtype], W_z, b_z, W_r, U_r, b_u, W_h, b_h)
 
 
+def lstm_level(x, W_i, b_i, W_o, b_o, W_u, b_u, W_f, b_f, pred: CSR, depth: int, I: int, H: int, gate_dtype=None):
+    return _LstmLevel.apply(x, pred, depth, I, H, GATE_DTYPES[gate_dtype], W_i, b_i, W_o, b_o, W_u, b_u, W_f, b_f)
+
+
+# ----------------------------------------------------------------------------- sparse (incremental) levels
 def _as_padded_state(h: torch.Tensor, H: int, Hp: int) -> torch.Tensor:
     """[E, H] public state -> [E, Hp] buffer with zero pad columns (no copy when it already is a view of one)."""
     if h.dim() == 2 and h.shape[1] == H and h.stride(1) == 1 and h.stride(0) == Hp and Hp != H \
@@ -979,316 +1183,94 @@ def _sparse_structure(E1: int, submess: torch.Tensor, bgraph_sub: torch.Tensor):
     return _memo_put(bgraph_sub, "_ggpm_sparse", key, (frozen, pred, submess))      # (keeps `submess` alive: the key names it)
 
 
-class _GruSparse(torch.autograd.Function):
-    """GRU.sparse_forward (ggpm/rnn.py:52-59): recompute the rows `submess` of the message state `depth` times."""
+def _sparse_forward(ctx, cell: _Cell, h_in, c_in, x_sub, submess, bgraph_sub, depth: int):
+    """GRU.sparse_forward / LSTM.sparse_forward (ggpm/rnn.py:52-59, 110-121): recompute the rows `submess` of the message
+    state `depth` times.  -> (h [E1, H], c [E1, H] or None)"""
+    _need_gpu(h_in, c_in, x_sub, submess, bgraph_sub, cell.params[0])
+    H, Hp = cell.H, cell.Hp
+    E1, ms = h_in.shape[0], submess.numel()
+    f32 = dict(dtype=torch.float32, device=h_in.device)
+    save = any(ctx.needs_input_grad)
+    hp = _as_padded_state(h_in, H, Hp)
+    cp = _as_padded_state(c_in, H, Hp) if c_in is not None else None
+    frozen, pred, _ = _sparse_structure(E1, submess, bgraph_sub)
+    Xs = torch.empty(cell.G, ms, Hp, **f32)
+    cell.project_inputs(x_sub, _ld(x_sub), ms, Xs)
+    X = torch.zeros(cell.G, E1, Hp, **f32)
+    X.index_copy_(1, submess, Xs)
+    wpack = cell.alloc_pack()
+    Hs, Cs, Qs, St = cell.alloc_state(E1, depth, save)
+    cell.sparse_forward(rows=E1, depth=depth, h_in=hp, c_in=cp, frozen=frozen, X=X, pred=pred, Hs=Hs, Cs=Cs, Qs=Qs, St=St,
+                        wpack=wpack, save=save)
+    k = depth if save else depth & 1
+    if save:
+        ctx.save_for_backward(x_sub, submess, *cell.weights)
+        ctx.stash = (X[cell.reread], frozen, pred, Hs, Cs, Qs, St)
+        ctx.meta = (cell, depth)
+    return Hs[k][:, :H], (Cs[k][:, :H] if Cs is not None else None)
 
+
+def _sparse_backward(ctx, dH, dC, want_dx: bool, name: str):
+    """-> (dh_in, dc_in or None, dx_sub or None, the parameter gradients: None where they were queued for the pass's end)"""
+    x_sub, submess = ctx.saved_tensors[:2]
+    if ctx.stash is None:
+        raise second_backward(name)
+    Xg, frozen, pred, Hs, Cs, Qs, St = ctx.stash
+    cell, depth = ctx.meta
+    H, Hp = cell.H, cell.Hp
+    E1, ms = Hs.shape[1], submess.numel()
+    f32 = dict(dtype=torch.float32, device=x_sub.device)
+    lstm = Cs is not None
+    succ = pred.T
+    dHD = torch.zeros(E1, Hp, **f32)
+    dCD = torch.zeros(E1, Hp, **f32) if lstm else None
+    if dH is not None:
+        dHD[:, :H] = dH
+    if dC is not None:
+        dCD[:, :H] = dC
+    dHin = torch.empty(E1, Hp, **f32)
+    dCin = torch.empty(E1, Hp, **f32) if lstm else None
+    dX = torch.empty(cell.G, E1, Hp, **f32)
+    bufs, hid = cell.dW_buffers()
+    work = cell.backward_workspace(E1, depth)
+    cell.sparse_backward(rows=E1, depth=depth, frozen=frozen, Xg=Xg, pred=pred, succ=succ, Hs=Hs, Cs=Cs, Qs=Qs, St=St,
+                         d_out=dHD, dc_out=dCD, d_in=dHin, dc_in=dCin, dX=dX, dW_hidden=hid, work=work)
+    ctx.stash = None
+    dXs = dX.index_select(1, submess)             # [G, ms, Hp]: only the recomputed rows carry input gradients
+    pgrads = cell.grads(bufs, hid, cell.input_half_grads(dXs, x_sub, _ld(x_sub), ms, bufs))
+    dx = cell.input_grad(dXs, x_sub, ms) if want_dx else None
+    if defer_wgrads_enabled() and can_publish(*cell.params):
+        for q, g in zip(cell.params, pgrads):         # summed once per parameter at the end of the pass (see _DEFER)
+            _defer_sum(q, g)
+        pgrads = (None,) * len(pgrads)
+    return dHin[:, :H], (dCin[:, :H] if lstm else None), dx, pgrads
+
+
+class _GruSparse(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, h_in, x_sub, submess, bgraph_sub, W_z, b_z, W_r, U_r, b_u, W_h, b_h, depth, I, H):
-        _need_gpu(h_in, x_sub, submess, bgraph_sub, W_z)
-        lib = _lib.load()
-        E1, Hp, ms = h_in.shape[0], padded_hidden(H), submess.numel()
-        f32 = dict(dtype=torch.float32, device=h_in.device)
-        save = any(ctx.needs_input_grad)
-        hp = _as_padded_state(h_in, H, Hp)
-        frozen, pred, _ = _sparse_structure(E1, submess, bgraph_sub)
-        Wz_x, Wz_h = _split_cols(W_z, I)
-        Wh_x, Wh_h = _split_cols(W_h, I)
-        ldx = _ld(x_sub)
-        Xs = torch.empty(3, ms, Hp, **f32)
-        gemm(0, 1, ms, H, I, x_sub, ldx, Wz_x, W_z.stride(0), Xs[0], Hp, Hp, bias=b_z)
-        gemm(0, 1, ms, H, I, x_sub, ldx, W_r, W_r.stride(0), Xs[1], Hp, Hp)
-        gemm(0, 1, ms, H, I, x_sub, ldx, Wh_x, W_h.stride(0), Xs[2], Hp, Hp, bias=b_h)
-        X = torch.zeros(3, E1, Hp, **f32)
-        X.index_copy_(1, submess, Xs)
-        wpack = torch.empty(int(lib.ggpm_gru_pack_floats(H)), **f32)
-        if save:
-            Hs = torch.empty(depth + 1, E1, Hp, **f32)
-            Qs = torch.empty(depth, E1, Hp, **f32)
-            St = torch.empty(5, depth, E1, Hp, **f32)
-            Ss, Gs, Zs, Ms, Rs = St[0], St[1], St[2], St[3], St[4]
-        else:
-            Hs = torch.empty(2, E1, Hp, **f32)
-            Qs = torch.empty(2, E1, Hp, **f32)
-            Ss = Gs = Zs = Ms = Rs = None
-        _lib.check(lib.ggpm_gru_sparse_forward(E1, H, depth, _p(hp), _p(frozen), _p(X[0]), _p(X[1]), _p(X[2]), _p(Wz_h),
-                                               W_z.stride(0), _p(U_r), U_r.stride(0), _p(b_u), _p(Wh_h), W_h.stride(0),
-                                               _p(pred.rowptr), _p(pred.col), _p(Hs), _p(Qs), _p(Ss), _p(Gs), _p(Zs),
-                                               _p(Ms), _p(Rs), _p(wpack), int(save), None, _stream()), "gru_sparse_forward")
-        out = Hs[depth] if save else Hs[depth & 1]
-        if save:
-            ctx.save_for_backward(x_sub, submess, W_z, W_r, U_r, W_h)
-            ctx.stash = (X[1], frozen, pred, Hs, Qs, Ss, Gs, Zs, Ms, Rs)
-            ctx.meta = (depth, I, H)
-            ctx.param_refs = (W_z, b_z, W_r, U_r, b_u, W_h, b_h)
-        return out[:, :H]
+    def forward(ctx, h_in, x_sub, submess, bgraph_sub, depth, I, H, *params):
+        return _sparse_forward(ctx, GruCell(params, I, H), h_in, None, x_sub, submess, bgraph_sub, depth)[0]
 
     @staticmethod
     def backward(ctx, dH):
-        x_sub, submess, W_z, W_r, U_r, W_h = ctx.saved_tensors
-        if ctx.stash is None:
-            raise second_backward("gru_sparse")
-        Xr, frozen, pred, Hs, Qs, Ss, Gs, Zs, Ms, Rs = ctx.stash
-        depth, I, H = ctx.meta
-        lib = _lib.load()
-        E1, Hp, ms = Hs.shape[1], padded_hidden(H), submess.numel()
-        f32 = dict(dtype=torch.float32, device=x_sub.device)
-        succ = pred.T
-        dHD = torch.zeros(E1, Hp, **f32)
-        dHD[:, :H] = dH
-        dHin = torch.empty(E1, Hp, **f32)
-        dX = torch.empty(3, E1, Hp, **f32)
-        dW_z, dW_r, dU_r, dW_h = (torch.empty(W_z.shape, **f32), torch.empty(W_r.shape, **f32),
-                                  torch.empty(H, H, **f32), torch.empty(W_h.shape, **f32))
-        db_u = torch.empty(H, **f32)
-        Wz_x, Wz_h = _split_cols(W_z, I)
-        Wh_x, Wh_h = _split_cols(W_h, I)
-        dWz_x, dWz_h = _split_cols(dW_z, I)
-        dWh_x, dWh_h = _split_cols(dW_h, I)
-        wb = int(lib.ggpm_gru_backward_workspace_bytes(E1, H, depth))
-        work = torch.empty((wb + 3) // 4, **f32)
-        _lib.check(lib.ggpm_gru_sparse_backward(E1, H, depth, _p(frozen), _p(Xr), _p(Wz_h), W_z.stride(0), _p(U_r),
-                                                U_r.stride(0), _p(Wh_h), W_h.stride(0), _p(pred.rowptr), _p(pred.col),
-                                                _p(succ.rowptr), _p(succ.col), _p(Hs), _p(Qs), _p(Ss), _p(Gs), _p(Zs),
-                                                _p(Ms), _p(Rs), _p(dHD), _p(dHin), _p(dX[0]), _p(dX[1]), _p(dX[2]),
-                                                _p(dWz_h), dW_z.stride(0), _p(dU_r), H, _p(db_u), _p(dWh_h),
-                                                dW_h.stride(0), _p(work), work.numel() * 4, None, _stream()),
-                   "gru_sparse_backward")
-        ctx.stash = None
-        dXs = dX.index_select(1, submess)             # [3, ms, Hp]: only the recomputed rows carry input gradients
-        ldx = _ld(x_sub)
-        gemm(1, 0, H, I, ms, dXs[0], Hp, x_sub, ldx, dWz_x, dW_z.stride(0), I, splitk=True)
-        gemm(1, 0, H, I, ms, dXs[1], Hp, x_sub, ldx, dW_r, dW_r.stride(0), I, splitk=True)
-        gemm(1, 0, H, I, ms, dXs[2], Hp, x_sub, ldx, dWh_x, dW_h.stride(0), I, splitk=True)
-        db_z, db_h = colsum(dXs[0], ms, H), colsum(dXs[2], ms, H)
-        dx = None
-        if ctx.needs_input_grad[1]:
-            dx = _empty_same_layout(x_sub)
-            gemm(0, 0, ms, I, H, dXs[0], Hp, Wz_x, W_z.stride(0), dx, ldx, x_sub.shape[1])
-            gemm(0, 0, ms, I, H, dXs[1], Hp, W_r, W_r.stride(0), dx, ldx, I, accumulate=True)
-            gemm(0, 0, ms, I, H, dXs[2], Hp, Wh_x, W_h.stride(0), dx, ldx, I, accumulate=True)
-        pgrads = (dW_z, db_z, dW_r, dU_r, db_u, dW_h, db_h)
-        if defer_wgrads_enabled() and can_publish(*ctx.param_refs):
-            for q, g in zip(ctx.param_refs, pgrads):      # summed once per parameter at the end of the pass (see _DEFER)
-                _defer_sum(q, g)
-            pgrads = (None,) * 7
-        return (dHin[:, :H], dx, None, None, *pgrads, None, None, None)
-
-
-def gru_sparse(h_in, x_sub, submess, bgraph_sub, W_z, b_z, W_r, U_r, b_u, W_h, b_h, depth: int, I: int, H: int):
-    return _GruSparse.apply(h_in, x_sub, submess, bgraph_sub, W_z, b_z, W_r, U_r, b_u, W_h, b_h, depth, I, H)
+        dh, _, dx, pgrads = _sparse_backward(ctx, dH, None, ctx.needs_input_grad[1], "gru_sparse")
+        return (dh, dx, None, None, None, None, None, *pgrads)
 
 
 class _LstmSparse(torch.autograd.Function):
-    """LSTM.sparse_forward (ggpm/rnn.py:110-121): recompute rows `submess` of the (h, c) state `depth` times."""
-
     @staticmethod
-    def forward(ctx, h_in, c_in, x_sub, submess, bgraph_sub, W_i, b_i, W_o, b_o, W_u, b_u, W_f, b_f, depth, I, H):
-        _need_gpu(h_in, c_in, x_sub, submess, bgraph_sub, W_i)
-        lib = _lib.load()
-        E1, Hp, ms = h_in.shape[0], padded_hidden(H), submess.numel()
-        f32 = dict(dtype=torch.float32, device=h_in.device)
-        save = any(ctx.needs_input_grad)
-        hp, cp = _as_padded_state(h_in, H, Hp), _as_padded_state(c_in, H, Hp)
-        frozen, pred, _ = _sparse_structure(E1, submess, bgraph_sub)
-        Ws, bs = (W_i, W_o, W_u, W_f), (b_i, b_o, b_u, b_f)
-        ldx = _ld(x_sub)
-        Xs = torch.empty(4, ms, Hp, **f32)
-        for k in range(4):
-            gemm(0, 1, ms, H, I, x_sub, ldx, Ws[k][:, :I], Ws[k].stride(0), Xs[k], Hp, Hp, bias=bs[k])
-        X = torch.zeros(4, E1, Hp, **f32)
-        X.index_copy_(1, submess, Xs)
-        wpack = torch.empty(int(lib.ggpm_lstm_pack_floats(H)), **f32)
-        if save:
-            Hs = torch.empty(depth + 1, E1, Hp, **f32)
-            Cs = torch.empty(depth + 1, E1, Hp, **f32)
-            Qs = torch.empty(depth, E1, Hp, **f32)
-            St = torch.empty(5, depth, E1, Hp, **f32)
-            Ss, Is, Os, Us, Fs = St[0], St[1], St[2], St[3], St[4]
-        else:
-            Hs = torch.empty(2, E1, Hp, **f32)
-            Cs = torch.empty(2, E1, Hp, **f32)
-            Qs = torch.empty(2, E1, Hp, **f32)
-            Ss = Is = Os = Us = Fs = None
-        Wh = [w[:, I:] for w in Ws]
-        _lib.check(lib.ggpm_lstm_sparse_forward(E1, H, depth, _p(hp), _p(cp), _p(frozen), _p(X[0]), _p(X[1]), _p(X[2]),
-                                                _p(X[3]), _p(Wh[0]), W_i.stride(0), _p(Wh[1]), W_o.stride(0), _p(Wh[2]),
-                                                W_u.stride(0), _p(Wh[3]), W_f.stride(0), _p(pred.rowptr), _p(pred.col),
-                                                _p(Hs), _p(Cs), _p(Qs), _p(Ss), _p(Is), _p(Os), _p(Us), _p(Fs), _p(wpack),
-                                                int(save), None, _stream()), "lstm_sparse_forward")
-        k = depth if save else depth & 1
-        if save:
-            ctx.save_for_backward(x_sub, submess, W_i, W_o, W_u, W_f)
-            ctx.stash = (X[3], frozen, pred, Hs, Cs, Qs, Ss, Is, Os, Us, Fs)
-            ctx.meta = (depth, I, H)
-            ctx.param_refs = (W_i, b_i, W_o, b_o, W_u, b_u, W_f, b_f)
-        return Hs[k][:, :H], Cs[k][:, :H]
+    def forward(ctx, h_in, c_in, x_sub, submess, bgraph_sub, depth, I, H, *params):
+        return _sparse_forward(ctx, LstmCell(params, I, H), h_in, c_in, x_sub, submess, bgraph_sub, depth)
 
     @staticmethod
     def backward(ctx, dH, dC):
-        x_sub, submess, W_i, W_o, W_u, W_f = ctx.saved_tensors
-        if ctx.stash is None:
-            raise second_backward("lstm_sparse")
-        Xf, frozen, pred, Hs, Cs, Qs, Ss, Is, Os, Us, Fs = ctx.stash
-        depth, I, H = ctx.meta
-        lib = _lib.load()
-        E1, Hp, ms = Hs.shape[1], padded_hidden(H), submess.numel()
-        f32 = dict(dtype=torch.float32, device=x_sub.device)
-        succ = pred.T
-        dHD = torch.zeros(E1, Hp, **f32)
-        dCD = torch.zeros(E1, Hp, **f32)
-        if dH is not None:
-            dHD[:, :H] = dH
-        if dC is not None:
-            dCD[:, :H] = dC
-        dHin, dCin = torch.empty(E1, Hp, **f32), torch.empty(E1, Hp, **f32)
-        Ws = (W_i, W_o, W_u, W_f)
-        dX = torch.empty(4, E1, Hp, **f32)
-        dWs = [torch.empty(w.shape, **f32) for w in Ws]
-        Wh = [w[:, I:] for w in Ws]
-        dWh = [w[:, I:] for w in dWs]
-        wb = int(lib.ggpm_lstm_backward_workspace_bytes(E1, H, depth))
-        work = torch.empty((wb + 3) // 4, **f32)
-        _lib.check(lib.ggpm_lstm_sparse_backward(E1, H, depth, _p(frozen), _p(Xf), _p(Wh[0]), W_i.stride(0), _p(Wh[1]),
-                                                 W_o.stride(0), _p(Wh[2]), W_u.stride(0), _p(Wh[3]), W_f.stride(0),
-                                                 _p(pred.rowptr), _p(pred.col), _p(succ.rowptr), _p(succ.col), _p(Hs),
-                                                 _p(Cs), _p(Qs), _p(Ss), _p(Is), _p(Os), _p(Us), _p(Fs), _p(dHD),
-                                                 _p(dCD), _p(dHin), _p(dCin), _p(dX[0]), _p(dX[1]), _p(dX[2]), _p(dX[3]),
-                                                 _p(dWh[0]), dWs[0].stride(0), _p(dWh[1]), dWs[1].stride(0), _p(dWh[2]),
-                                                 dWs[2].stride(0), _p(dWh[3]), dWs[3].stride(0), _p(work),
-                                                 work.numel() * 4, None, _stream()), "lstm_sparse_backward")
-        ctx.stash = None
-        dXs = dX.index_select(1, submess)
-        ldx = _ld(x_sub)
-        dbs = []
-        for k in range(4):
-            gemm(1, 0, H, I, ms, dXs[k], Hp, x_sub, ldx, dWs[k][:, :I], dWs[k].stride(0), I, splitk=True)
-            dbs.append(colsum(dXs[k], ms, H))
-        dx = None
-        if ctx.needs_input_grad[2]:
-            dx = _empty_same_layout(x_sub)
-            for k in range(4):
-                gemm(0, 0, ms, I, H, dXs[k], Hp, Ws[k][:, :I], Ws[k].stride(0), dx, ldx,
-                     x_sub.shape[1] if k == 0 else I, accumulate=k > 0)
-        pgrads = (dWs[0], dbs[0], dWs[1], dbs[1], dWs[2], dbs[2], dWs[3], dbs[3])
-        if defer_wgrads_enabled() and can_publish(*ctx.param_refs):
-            for q, g in zip(ctx.param_refs, pgrads):      # summed once per parameter at the end of the pass (see _DEFER)
-                _defer_sum(q, g)
-            pgrads = (None,) * 8
-        return (dHin[:, :H], dCin[:, :H], dx, None, None, *pgrads, None, None, None)
+        dh, dc, dx, pgrads = _sparse_backward(ctx, dH, dC, ctx.needs_input_grad[2], "lstm_sparse")
+        return (dh, dc, dx, None, None, None, None, None, *pgrads)
+
+
+def gru_sparse(h_in, x_sub, submess, bgraph_sub, W_z, b_z, W_r, U_r, b_u, W_h, b_h, depth: int, I: int, H: int):
+    return _GruSparse.apply(h_in, x_sub, submess, bgraph_sub, depth, I, H, W_z, b_z, W_r, U_r, b_u, W_h, b_h)
 
 
 def lstm_sparse(h_in, c_in, x_sub, submess, bgraph_sub, W_i, b_i, W_o, b_o, W_u, b_u, W_f, b_f, depth, I, H):
-    return _LstmSparse.apply(h_in, c_in, x_sub, submess, bgraph_sub, W_i, b_i, W_o, b_o, W_u, b_u, W_f, b_f, depth, I, H)
-
-
-class _LstmLevel(torch.autograd.Function):
-    """LSTM.forward (ggpm/rnn.py:96-108) for one level; returns (h_D, c_D) as [E1, Hp] tensors."""
-
-    @staticmethod
-    def forward(ctx, x, W_i, b_i, W_o, b_o, W_u, b_u, W_f, b_f, pred, depth, I, H, gate_dtype=0):
-        _need_gpu(x, W_i, W_o, W_u, W_f)
-        lib = _lib.load()
-        ctx.gate_dtype = gate_dtype
-        E1, Hp = x.shape[0], padded_hidden(H)
-        f32 = dict(dtype=torch.float32, device=x.device)
-        save = any(ctx.needs_input_grad)
-        Ws, bs = (W_i, W_o, W_u, W_f), (b_i, b_o, b_u, b_f)
-        X = torch.empty(4, E1, Hp, **f32)
-        ldx = _ld(x)
-        for k in range(4):
-            gemm(0, 1, E1, H, I, x, ldx, Ws[k][:, :I], Ws[k].stride(0), X[k], Hp, Hp, bias=bs[k])
-        wpack = torch.empty(int(lib.ggpm_lstm_pack_floats(H)), **f32)
-        if save:
-            Hs = torch.empty(depth + 1, E1, Hp, **f32)
-            Cs = torch.empty(depth + 1, E1, Hp, **f32)
-            Qs = torch.empty(depth, E1, Hp, **f32)
-            St = torch.empty(5, depth, E1, Hp, **f32)
-            Ss, Is, Os, Us, Fs = St[0], St[1], St[2], St[3], St[4]
-        else:
-            Hs = torch.empty(2, E1, Hp, **f32)
-            Cs = torch.empty(2, E1, Hp, **f32)
-            Qs = torch.empty(2, E1, Hp, **f32)
-            Ss = Is = Os = Us = Fs = None
-        Wh = [w[:, I:] for w in Ws]
-        _lib.check(lib.ggpm_lstm_forward(E1, H, depth, _p(X[0]), _p(X[1]), _p(X[2]), _p(X[3]), _p(Wh[0]), W_i.stride(0),
-                                         _p(Wh[1]), W_o.stride(0), _p(Wh[2]), W_u.stride(0), _p(Wh[3]), W_f.stride(0),
-                                         _p(pred.rowptr), _p(pred.col), _p(Hs), _p(Cs), _p(Qs), _p(Ss), _p(Is), _p(Os),
-                                         _p(Us), _p(Fs), _p(wpack), int(save), _gate_opts(gate_dtype), _stream()), "lstm_forward")
-        k = depth if save else depth & 1
-        if save:
-            ctx.save_for_backward(x, W_i, W_o, W_u, W_f)
-            ctx.stash = (X[3], Hs, Cs, Qs, Ss, Is, Os, Us, Fs)
-            ctx.meta = (pred, depth, I, H)
-            ctx.params = (W_i, b_i, W_o, b_o, W_u, b_u, W_f, b_f)
-        c_out = Cs[k]
-        ctx.mark_non_differentiable(c_out)
-        return Hs[k], c_out
-
-    @staticmethod
-    def backward(ctx, dHD, _dC):
-        x, W_i, W_o, W_u, W_f = ctx.saved_tensors
-        if ctx.stash is None:
-            raise second_backward("lstm_level")
-        Xf, Hs, Cs, Qs, Ss, Is, Os, Us, Fs = ctx.stash
-        pred, depth, I, H = ctx.meta
-        lib = _lib.load()
-        E1, Hp = x.shape[0], padded_hidden(H)
-        succ = pred.T
-        dHD = dHD.contiguous()
-        f32 = dict(dtype=torch.float32, device=x.device)
-        Ws = (W_i, W_o, W_u, W_f)
-        dX = torch.empty(4, E1, Hp, **f32)
-        dWs = [torch.empty(w.shape, **f32) for w in Ws]
-        Wh = [w[:, I:] for w in Ws]
-        dWh = [w[:, I:] for w in dWs]
-        wb = int(lib.ggpm_lstm_backward_workspace_bytes(E1, H, depth))
-        work = torch.empty((wb + 3) // 4, **f32)
-        use_side = side_stream_enabled() and can_publish(*ctx.params)
-        _lib.check(lib.ggpm_lstm_backward(E1, H, depth, _p(Xf), _p(Wh[0]), W_i.stride(0), _p(Wh[1]), W_o.stride(0),
-                                          _p(Wh[2]), W_u.stride(0), _p(Wh[3]), W_f.stride(0), _p(pred.rowptr),
-                                          _p(pred.col), _p(succ.rowptr), _p(succ.col), _p(Hs), _p(Cs), _p(Qs), _p(Ss),
-                                          _p(Is), _p(Os), _p(Us), _p(Fs), _p(dHD), _p(dX[0]), _p(dX[1]), _p(dX[2]),
-                                          _p(dX[3]), _p(dWh[0]), dWs[0].stride(0), _p(dWh[1]), dWs[1].stride(0),
-                                          _p(dWh[2]), dWs[2].stride(0), _p(dWh[3]), dWs[3].stride(0), _p(work),
-                                          work.numel() * 4, 0 if use_side else 1, _gate_opts(ctx.gate_dtype), _stream()),
-                   "lstm_backward")
-        ctx.stash = None
-        ldx = _ld(x)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = _empty_same_layout(x)
-            for k in range(4):
-                gemm(0, 0, E1, I, H, dX[k], Hp, Ws[k][:, :I], Ws[k].stride(0), dx, ldx, x.shape[1] if k == 0 else I,
-                     accumulate=k > 0)
-
-        def weight_grads():
-            if use_side:
-                _lib.check(lib.ggpm_lstm_weight_grads(E1, H, depth, _p(Hs), _p(Ss), _p(work), work.numel() * 4,
-                                                      _p(dWh[0]), dWs[0].stride(0), _p(dWh[1]), dWs[1].stride(0),
-                                                      _p(dWh[2]), dWs[2].stride(0), _p(dWh[3]), dWs[3].stride(0),
-                                                      _gate_opts(ctx.gate_dtype), _stream()), "lstm_weight_grads")
-            out = []
-            for k in range(4):
-                gemm(1, 0, H, I, E1, dX[k], Hp, x, ldx, dWs[k][:, :I], dWs[k].stride(0), I, splitk=True)
-                out.append(colsum(dX[k], E1, H))
-            return out
-
-        if use_side:
-            main = torch.cuda.current_stream()
-            side = _side_stream(x.device)
-            side.wait_stream(main)
-            for tns in [work, dX, Hs, Ss, x] + dWs:
-                tns.record_stream(side)
-            with torch.cuda.stream(side):
-                dbs = weight_grads()
-                for k in range(4):
-                    _accumulate_grad(ctx.params[2 * k], dWs[k], main)
-                    _accumulate_grad(ctx.params[2 * k + 1], dbs[k], main)
-            _join_later(main, side)
-            return (dx,) + (None,) * 13
-        dbs = weight_grads()
-        return (dx, dWs[0], dbs[0], dWs[1], dbs[1], dWs[2], dbs[2], dWs[3], dbs[3], None, None, None, None, None)
-
-
-def lstm_level(x, W_i, b_i, W_o, b_o, W_u, b_u, W_f, b_f, pred: CSR, depth: int, I: int, H: int, gate_dtype=None):
-    return _LstmLevel.apply(x, W_i, b_i, W_o, b_o, W_u, b_u, W_f, b_f, pred, depth, I, H, GATE_DTYPES[gate_dtype])
+    return _LstmSparse.apply(h_in, c_in, x_sub, submess, bgraph_sub, depth, I, H, W_i, b_i, W_o, b_o, W_u, b_u, W_f, b_f)

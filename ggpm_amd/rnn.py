@@ -41,12 +41,15 @@ class GRU(nn.Module):
     def get_hidden_state(self, h):
         return h
 
+    def level_params(self):
+        """The parameters in the order every level call takes them (functional.GruCell)."""
+        return (self.W_z.weight, self.W_z.bias, self.W_r.weight, self.U_r.weight, self.U_r.bias, self.W_h.weight,
+                self.W_h.bias)
+
     def forward_padded(self, fmess, bgraph):
         """h_D as a [E+1, Hp] tensor (pad columns zero)."""
-        I, H = self.input_size, self.hidden_size
         pred = _as_csr(bgraph, fmess.shape[0])
-        return F_.gru_level(fmess, self.W_z.weight, self.W_z.bias, self.W_r.weight, self.U_r.weight,
-                            self.U_r.bias, self.W_h.weight, self.W_h.bias, pred, self.depth, I, H,
+        return F_.gru_level(fmess, *self.level_params(), pred, self.depth, self.input_size, self.hidden_size,
                             gate_dtype=getattr(self, "gate_dtype", None))
 
     def forward(self, fmess, bgraph):
@@ -55,9 +58,8 @@ class GRU(nn.Module):
     def sparse_forward(self, h, fmess, submess, bgraph):
         """reference ggpm/rnn.py:52-59: recompute rows ``submess`` of the state ``h`` (``fmess``/``bgraph`` are the
         sub-tensors of those rows, ``bgraph`` holding GLOBAL predecessor ids)."""
-        return F_.gru_sparse(h, fmess, submess.long(), bgraph.long(), self.W_z.weight, self.W_z.bias, self.W_r.weight,
-                             self.U_r.weight, self.U_r.bias, self.W_h.weight, self.W_h.bias, self.depth,
-                             self.input_size, self.hidden_size)
+        return F_.gru_sparse(h, fmess, submess.long(), bgraph.long(), *self.level_params(), self.depth, self.input_size,
+                             self.hidden_size)
 
 
 class LSTM(nn.Module):
@@ -84,12 +86,15 @@ class LSTM(nn.Module):
     def get_hidden_state(self, h):
         return h[0]
 
-    def forward_padded(self, fmess, bgraph):
-        I, H = self.input_size, self.hidden_size
-        pred = _as_csr(bgraph, fmess.shape[0])
+    def level_params(self):
+        """The parameters in the order every level call takes them (functional.LstmCell)."""
         i, o, u, f = self.W_i[0], self.W_o[0], self.W[0], self.W_f[0]
-        return F_.lstm_level(fmess, i.weight, i.bias, o.weight, o.bias, u.weight, u.bias, f.weight, f.bias,
-                             pred, self.depth, I, H, gate_dtype=getattr(self, "gate_dtype", None))
+        return (i.weight, i.bias, o.weight, o.bias, u.weight, u.bias, f.weight, f.bias)
+
+    def forward_padded(self, fmess, bgraph):
+        pred = _as_csr(bgraph, fmess.shape[0])
+        return F_.lstm_level(fmess, *self.level_params(), pred, self.depth, self.input_size, self.hidden_size,
+                             gate_dtype=getattr(self, "gate_dtype", None))
 
     def forward(self, fmess, bgraph):
         h, c = self.forward_padded(fmess, bgraph)
@@ -98,6 +103,5 @@ class LSTM(nn.Module):
     def sparse_forward(self, h, fmess, submess, bgraph):
         """reference ggpm/rnn.py:110-121: ``h`` is the (h, c) pair; returns the updated pair."""
         h, c = h
-        i, o, u, f = self.W_i[0], self.W_o[0], self.W[0], self.W_f[0]
-        return F_.lstm_sparse(h, c, fmess, submess.long(), bgraph.long(), i.weight, i.bias, o.weight, o.bias,
-                              u.weight, u.bias, f.weight, f.bias, self.depth, self.input_size, self.hidden_size)
+        return F_.lstm_sparse(h, c, fmess, submess.long(), bgraph.long(), *self.level_params(), self.depth,
+                              self.input_size, self.hidden_size)

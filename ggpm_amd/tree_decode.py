@@ -17,7 +17,7 @@ to run them.  ``tree_level`` is the same arithmetic in the same order on the sam
 the op-by-op path up to the summation order of two fused launches) issued from ONE ``torch.autograd.Function``: the gate
 inputs are written straight into the rows they belong to (the op-by-op form scatters them), the parameter gradients
 go through the same deferred contractions (``functional._defer_*``).  Used when dropout is inactive and the parameters can be published
-(``functional.can_publish``); ``GGPM_TREE_COMPOSITE=0`` keeps the op-by-op path.
+(``functional.can_publish``); ``_dev.TREE_COMPOSITE = False`` keeps the op-by-op path.
 """
 from __future__ import annotations
 
@@ -67,7 +67,8 @@ def _composite_forward(ctx, S: LevelSpec, lstm: bool, H: int, He: int, lower, ex
     ldm = (I + 3) // 4 * 4
     E1, depth = S.E1, S.depth
     Etot, ms, n_inst = E1 + S.n_extra, E1 - 1, S.ids.numel()
-    G = 4 if lstm else 3
+    cell = F_.cell_for(lstm, rp, I, H)
+    G = cell.G
     s = F_._stream()
     frozen, pred, in_csr, src_csr = S.structures()
     # 1-2. visit vectors: relu([E[ids] | lower] W^T + b)
@@ -82,39 +83,17 @@ def _composite_forward(ctx, S: LevelSpec, lstm: bool, H: int, He: int, lower, ex
     _lib.check(lib.ggpm_gather_rows(P(hnode), Hp, P(S.mess_inst), ms, H, P(hmess), ldm, 0, 0, s), "gather_rows")
     _lib.check(lib.ggpm_onehot(P(S.mess_pos), ms, MAX_POS, P(hmess), ldm, H, ldm, s), "onehot")
     # 4. hoisted gate inputs, straight into the rows 1 .. E1-1 they belong to (row 0 / the extra rows: zero)
-    if lstm:
-        Wi, bi, Wog, bog, Wu, bu_, Wf, bf = rp
-        gates = ((Wi, bi), (Wog, bog), (Wu, bu_), (Wf, bf))
-    else:
-        Wz, bz, Wr, Ur, bu, Wh, bh = rp
-        gates = ((Wz, bz), (Wr, None), (Wh, bh))
     X = torch.zeros(G, Etot, Hp, **f32)
-    for k, (Wk, bk) in enumerate(gates):
-        F_.gemm(0, 1, ms, H, I, hmess, ldm, Wk, Wk.stride(0), X[k][1:], Hp, Hp, bias=bk)
+    cell.project_inputs(hmess, ldm, ms, [X[k][1:] for k in range(G)])
     # 5. start state: zero, the extra (frozen) rows carry `extra`
     hp = torch.zeros(Etot, Hp, **f32)
     if extra is not None:
         hp[E1:, :H] = extra
+    cp = torch.zeros(Etot, Hp, **f32) if lstm else None
     save = not infer            # forward-only: the depth loop in two ping-pong slots, no stashes
-    Hs = torch.empty(depth + 1 if save else 2, Etot, Hp, **f32)
-    Qs = torch.empty(depth if save else 2, Etot, Hp, **f32)
-    St = torch.empty(5, depth, Etot, Hp, **f32) if save else (None,) * 5
-    if lstm:
-        cp = torch.zeros(Etot, Hp, **f32)
-        Cs = torch.empty(depth + 1 if save else 2, Etot, Hp, **f32)
-        wpack = torch.empty(int(lib.ggpm_lstm_pack_floats(H)), **f32)
-        Wh = [w[:, I:] for w, _ in gates]
-        _lib.check(lib.ggpm_lstm_sparse_forward(
-            Etot, H, depth, P(hp), P(cp), P(frozen), P(X[0]), P(X[1]), P(X[2]), P(X[3]), P(Wh[0]), Wi.stride(0), P(Wh[1]),
-            Wog.stride(0), P(Wh[2]), Wu.stride(0), P(Wh[3]), Wf.stride(0), P(pred.rowptr), P(pred.col), P(Hs), P(Cs), P(Qs),
-            P(St[0]), P(St[1]), P(St[2]), P(St[3]), P(St[4]), P(wpack), int(save), None, s), "lstm_sparse_forward")
-    else:
-        Cs = None
-        wpack = torch.empty(int(lib.ggpm_gru_pack_floats(H)), **f32)
-        _lib.check(lib.ggpm_gru_sparse_forward(
-            Etot, H, depth, P(hp), P(frozen), P(X[0]), P(X[1]), P(X[2]), P(Wz[:, I:]), Wz.stride(0), P(Ur), Ur.stride(0),
-            P(bu), P(Wh[:, I:]), Wh.stride(0), P(pred.rowptr), P(pred.col), P(Hs), P(Qs), P(St[0]), P(St[1]), P(St[2]),
-            P(St[3]), P(St[4]), P(wpack), int(save), None, s), "gru_sparse_forward")
+    Hs, Cs, Qs, St = cell.alloc_state(Etot, depth, save)
+    cell.sparse_forward(rows=Etot, depth=depth, h_in=hp, c_in=cp, frozen=frozen, X=X, pred=pred, Hs=Hs, Cs=Cs, Qs=Qs, St=St,
+                        wpack=cell.alloc_pack(), save=save, stream=s)
     hid = Hs[depth] if save else Hs[depth & 1]
     # 6. read-out of every visit
     nei = torch.empty(n_inst, Hp, **f32)
@@ -127,7 +106,7 @@ def _composite_forward(ctx, S: LevelSpec, lstm: bool, H: int, He: int, lower, ex
         return node, hid
     ctx.S, ctx.meta = S, (lstm, H, He, extra is not None)
     ctx.save_for_backward(lower, node)          # (an input and an output: through autograd, so that no ctx -> output cycle forms)
-    ctx.stash = (finput, hnode, hmess, X[G - 1] if lstm else X[1], Hs, Cs, Qs, St, nei)
+    ctx.stash = (finput, hnode, hmess, X[cell.reread], Hs, Cs, Qs, St, nei)
     ctx.prm = (emb, W, b, Wo, bo) + tuple(rp)
     ctx.structs = (frozen, pred, in_csr, src_csr)
     ctx.set_materialize_grads(False)            # (an unused output arrives as None, not as a zero tensor to be added)
@@ -159,7 +138,8 @@ class _TreeLevel(torch.autograd.Function):
         ldm = hmess.shape[1]
         E1, depth = S.E1, S.depth
         Etot, ms, n_inst = E1 + S.n_extra, E1 - 1, S.ids.numel()
-        G = 4 if lstm else 3
+        cell = F_.cell_for(lstm, rp, I, H)
+        G = cell.G
         s = F_._stream()
         succ = pred.T
         # ---- read-out: dpre_o -> d(hnode), d(nei) -> d(final state)
@@ -186,51 +166,21 @@ class _TreeLevel(torch.autograd.Function):
         # ---- the level
         dHin = torch.empty(Etot, Hp, **f32)
         dX = torch.empty(G, Etot, Hp, **f32)
-        if lstm:
-            Wi, bi, Wog, bog, Wu, bu_, Wf, bf = rp
-            Ws = (Wi, Wog, Wu, Wf)
-            dWs = [torch.empty(w.shape, **f32) for w in Ws]
-            Wh = [w[:, I:] for w in Ws]
-            dWh = [w[:, I:] for w in dWs]
-            dCD = torch.zeros(Etot, Hp, **f32)
-            dCin = torch.empty(Etot, Hp, **f32)
-            wb = int(lib.ggpm_lstm_backward_workspace_bytes(Etot, H, depth))
-            work = torch.empty((wb + 3) // 4, **f32)
-            _lib.check(lib.ggpm_lstm_sparse_backward(
-                Etot, H, depth, P(frozen), P(Xg), P(Wh[0]), Wi.stride(0), P(Wh[1]), Wog.stride(0), P(Wh[2]), Wu.stride(0),
-                P(Wh[3]), Wf.stride(0), P(pred.rowptr), P(pred.col), P(succ.rowptr), P(succ.col), P(Hs), P(Cs), P(Qs), P(St[0]),
-                P(St[1]), P(St[2]), P(St[3]), P(St[4]), P(dHD), P(dCD), P(dHin), P(dCin), P(dX[0]), P(dX[1]), P(dX[2]), P(dX[3]),
-                P(dWh[0]), dWs[0].stride(0), P(dWh[1]), dWs[1].stride(0), P(dWh[2]), dWs[2].stride(0), P(dWh[3]),
-                dWs[3].stride(0), P(work), work.numel() * 4, None, s), "lstm_sparse_backward")
-            xw = [(Ws[k], dWs[k]) for k in range(4)]
-        else:
-            Wz, bz, Wr, Ur, bu, Wh, bh = rp
-            dWz, dWr, dUr, dWh_ = (torch.empty(Wz.shape, **f32), torch.empty(Wr.shape, **f32), torch.empty(H, H, **f32),
-                                   torch.empty(Wh.shape, **f32))
-            dbu = torch.empty(H, **f32)
-            wb = int(lib.ggpm_gru_backward_workspace_bytes(Etot, H, depth))
-            work = torch.empty((wb + 3) // 4, **f32)
-            _lib.check(lib.ggpm_gru_sparse_backward(
-                Etot, H, depth, P(frozen), P(Xg), P(Wz[:, I:]), Wz.stride(0), P(Ur), Ur.stride(0), P(Wh[:, I:]), Wh.stride(0),
-                P(pred.rowptr), P(pred.col), P(succ.rowptr), P(succ.col), P(Hs), P(Qs), P(St[0]), P(St[1]), P(St[2]), P(St[3]),
-                P(St[4]), P(dHD), P(dHin), P(dX[0]), P(dX[1]), P(dX[2]), P(dWz[:, I:]), dWz.stride(0), P(dUr), H, P(dbu),
-                P(dWh_[:, I:]), dWh_.stride(0), P(work), work.numel() * 4, None, s), "gru_sparse_backward")
-            xw = [(Wz, dWz), (Wr, dWr), (Wh, dWh_)]
+        bufs, hid = cell.dW_buffers()
+        dCD = torch.zeros(Etot, Hp, **f32) if lstm else None
+        dCin = torch.empty(Etot, Hp, **f32) if lstm else None
+        cell.sparse_backward(rows=Etot, depth=depth, frozen=frozen, Xg=Xg, pred=pred, succ=succ, Hs=Hs, Cs=Cs, Qs=Qs, St=St,
+                             d_out=dHD, dc_out=dCD, d_in=dHin, dc_in=dCin, dX=dX, dW_hidden=hid,
+                             work=cell.backward_workspace(Etot, depth), stream=s)
         dXs = [dX[k][1:E1] for k in range(G)]          # the rows of the real messages: contiguous
         # input halves of the gate weights, gate biases
-        dbs = []
-        for k, (Wk, dWk) in enumerate(xw):
-            F_.gemm(1, 0, H, I, ms, dXs[k], Hp, hmess, ldm, dWk, dWk.stride(0), I, splitk=True)
-            dbs.append(F_.colsum(dXs[k], ms, H) if (lstm or k != 1) else None)       # (W_r has no bias)
-        if lstm:
-            pg = (dWs[0], dbs[0], dWs[1], dbs[1], dWs[2], dbs[2], dWs[3], dbs[3])
-        else:
-            pg = (dWz, dbs[0], dWr, dUr, dbu, dWh_, dbs[2])
-        for q, g in zip(rp, pg):
+        dbs = cell.input_half_grads(dXs, hmess, ldm, ms, bufs, interleaved=True)
+        for q, g in zip(rp, cell.grads(bufs, hid, dbs)):
             F_._defer_sum(q, g)
         # ---- message inputs -> visit vectors
         dhmess = torch.empty(ms, ldm, **f32)
-        F_.gemm_ksegments(0, ms, I, dXs, [Hp] * G, [w for w, _ in xw], [w.stride(0) for w, _ in xw], [H] * G, dhmess, ldm, ldm)
+        F_.gemm_ksegments(0, ms, I, dXs, [Hp] * G, [w for w, _ in cell.gates], [w.stride(0) for w, _ in cell.gates], [H] * G, dhmess,
+                          ldm, ldm)
         src_T = src_csr.T
         _lib.check(lib.ggpm_segment_sum(P(dhmess), ldm, P(src_T.rowptr), P(src_T.col), n_inst, H, P(d_hnode), Hp, 1, 0, s),
                    "segment_sum")
@@ -288,12 +238,8 @@ def _descriptor(S: LevelSpec, lstm: bool, H: int, He: int, lower, extra, emb, W,
     frozen, pred, in_csr, src_csr = S.structures()
     succ, in_T, src_T = (pred.T, in_csr.T, src_csr.T) if backward else (None, None, None)
     n_inst = S.ids.numel()
-    if lstm:
-        Wi, bi, Wog, bog, Wu, bu_, Wf, bf = rp
-        gw, gb, Ur, bu = (Wi, Wog, Wu, Wf), (bi, bog, bu_, bf), None, None
-    else:
-        Wz, bz, Wr, Ur, bu, Wh, bh = rp
-        gw, gb = (Wz, Wr, Wh), (bz, None, bh)
+    cell = F_.cell_for(lstm, rp, H + MAX_POS, H)
+    Ur, bu = cell.U_r, cell.b_u
     L = TreeLevelC()
     L.lstm, L.H, L.He, L.E1, L.n_extra, L.depth, L.n_inst = int(lstm), H, He, S.E1, S.n_extra, S.depth, n_inst
     for k, t in (("ids", S.ids), ("mess_inst", S.mess_inst), ("mess_pos", S.mess_pos), ("frozen", frozen),
@@ -306,7 +252,7 @@ def _descriptor(S: LevelSpec, lstm: bool, H: int, He: int, lower, extra, emb, W,
     L.emb, L.ld_emb = _addr(emb), F_._ld(emb)
     L.W, L.b, L.ld_w = _addr(W), _addr(b), (W.stride(0) if W is not None else 0)   # (W None: embedding-input mode)
     L.Wo, L.bo, L.ld_wo = _addr(Wo), _addr(bo), Wo.stride(0)
-    for k, (w, bb) in enumerate(zip(gw, gb)):
+    for k, (w, bb) in enumerate(cell.gates):
         L.gate_w[k], L.ld_gate[k], L.gate_b[k] = _addr(w), w.stride(0), _addr(bb)
     L.Ur, L.bu, L.ld_ur = _addr(Ur), _addr(bu), (Ur.stride(0) if Ur is not None else 0)
     L.lower, L.ld_lower = _addr(lower), (F_._ld(lower) if lower is not None else 0)
@@ -382,14 +328,9 @@ class _TreeLevelNative(torch.autograd.Function):
         f32 = dict(dtype=torch.float32, device=dev)
         Hp, Hep = F_.padded_hidden(H), F_.padded_hidden(He)
         n_inst, Etot, E1 = S.ids.numel(), S.E1 + S.n_extra, S.E1
-        if lstm:
-            Wi, bi, Wog, bog, Wu, bu_, Wf, bf = rp
-            gw, gb = (Wi, Wog, Wu, Wf), (bi, bog, bu_, bf)
-        else:
-            Wz, bz, Wr, Ur, bu, Wh, bh = rp
-            gw, gb = (Wz, Wr, Wh), (bz, None, bh)
-        dgw = [torch.empty(w.shape, **f32) for w in gw]
-        dgb = [torch.empty(H, **f32) if bb is not None else None for bb in gb]
+        cell = F_.cell_for(lstm, rp, H + MAX_POS, H)
+        dgw = [torch.empty(w.shape, **f32) for w, _ in cell.gates]
+        dgb = [torch.empty(H, **f32) if bb is not None else None for _, bb in cell.gates]
         dUr = torch.empty(H, H, **f32) if not lstm else None
         dbu = torch.empty(H, **f32) if not lstm else None
         rows = torch.empty(2, n_inst, Hp, **f32)
@@ -398,7 +339,7 @@ class _TreeLevelNative(torch.autograd.Function):
         dHin = torch.empty(Etot, Hp, **f32)
         d_lower = F_._empty_same_layout(lower) if ctx.needs_input_grad[4] else None
         g = TreeLevelGrads()
-        for k in range(len(gw)):
+        for k in range(cell.G):
             g.dgate_w[k], g.ld_dgate[k], g.dgate_b[k] = _addr(dgw[k]), dgw[k].stride(0), _addr(dgb[k])
         g.dUr, g.dbu = _addr(dUr), _addr(dbu)
         g.dpre_w, g.dpre_o, g.d_finput = _addr(dpre_w), _addr(dpre_o), _addr(d_finput)
@@ -423,11 +364,7 @@ class _TreeLevelNative(torch.autograd.Function):
         if side is not None:
             for t in (work, saved):        # read there after this node has returned
                 t.record_stream(side)
-        if lstm:
-            pg = (dgw[0], dgb[0], dgw[1], dgb[1], dgw[2], dgb[2], dgw[3], dgb[3])
-        else:
-            pg = (dgw[0], dgb[0], dgw[1], dUr, dbu, dgw[2], dgb[2])
-        for q, gr in zip(rp, pg):
+        for q, gr in zip(rp, cell.grads(dgw, (None, dUr, None, dbu), dgb)):
             F_._defer_sum(q, gr)
         if side is not None:
             F_._DEFER["early"] = side      # the end-of-pass flush waits for the second stream before it reads what was queued
@@ -453,12 +390,7 @@ def tree_level(S: LevelSpec, rnn, emb_seq, lin_seq, wo_seq, lower, extra: Option
     """-> (node [n_inst, Hp], hidden state [E1 + extra rows, Hp]) of one tree-side decoder level.  ``lin_seq`` and
     ``lower`` None: the embedding-input mode of the tree-only decoder's level (node input E[ids] itself; driver only)."""
     from .rnn import LSTM
-    lstm = isinstance(rnn, LSTM)
-    if lstm:
-        rp = (rnn.W_i[0].weight, rnn.W_i[0].bias, rnn.W_o[0].weight, rnn.W_o[0].bias, rnn.W[0].weight, rnn.W[0].bias,
-              rnn.W_f[0].weight, rnn.W_f[0].bias)
-    else:
-        rp = (rnn.W_z.weight, rnn.W_z.bias, rnn.W_r.weight, rnn.U_r.weight, rnn.U_r.bias, rnn.W_h.weight, rnn.W_h.bias)
+    lstm, rp = isinstance(rnn, LSTM), rnn.level_params()
     emb = emb_seq[0].weight
     if lin_seq is None:
         if lower is not None or not _dev.TREE_DRIVER:
