@@ -136,14 +136,12 @@ __global__ void __launch_bounds__(ASSM_THREADS) motif_assm_fwd_k(AssmFwd a) {
     }
 }
 
-// d(score_c) of candidate c (< n) and d(s0) of prediction p (all C rows carry s0)
+// d(score_c) of candidate c (< n).  d(s0) of a prediction is sum_c softmax_c - 1 = 0: all C rows carry s0 and the cross
+// entropy does not change under a shift of every score.  Evaluated in fp32 that sum is one rounding of lse away from 1
+// (about ulp(lse) / 2, 1e-6 at lse = 16), with a sign of its own per prediction; summed over 700 predictions into dba that is
+// 2e-5.  So dba is written as the zero it is, and dz gets no ba term.
 __device__ __forceinline__ float dscore(const AssmBwd& a, float g, const float* st, int coff, int c) {
     return g * (expf(a.score[coff + c] - st[0]) - (c == 0 ? 1.f : 0.f));
-}
-__device__ float ds0_of(const AssmBwd& a, float g, const float* st, int n, int coff) {
-    float s = n < a.C ? (float)(a.C - n) * expf(st[1] - st[0]) : 0.f;
-    for (int c = 0; c < n; ++c) s += expf(a.score[coff + c] - st[0]);
-    return g * (s - 1.f);
 }
 
 __device__ void bwd_w1(const AssmBwd& a, int blk) {
@@ -237,13 +235,12 @@ __device__ __forceinline__ float du_of(const AssmBwd& a, float g, const int32_t*
 }
 
 __device__ void bwd_wa(const AssmBwd& a, int blk) {
-    // dWa[:, h] for ASSM_HS hidden units (and, in workgroup 0, dba), summed over the predictions in order
+    // dWa[:, h] for ASSM_HS hidden units, summed over the predictions in order (and, in workgroup 0, dba = 0)
     const int t = threadIdx.x, H = a.H, L = a.L;
     const int h0 = blk * ASSM_HS;
     const float g = a.dloss[0];
     for (int l = t; l < L; l += ASSM_THREADS) {
         float acc[ASSM_HS];
-        float accb = 0.f;
         for (int s = 0; s < ASSM_HS; ++s) acc[s] = 0.f;
         for (int p = 0; p < a.P; ++p) {
             const int32_t* m = a.meta + (size_t)p * META;
@@ -251,16 +248,15 @@ __device__ void bwd_wa(const AssmBwd& a, int blk) {
             const float zl = a.z[(size_t)m[3] * a.ldz + l];
             for (int s = 0; s < ASSM_HS; ++s)
                 if (h0 + s < H) acc[s] += du_of(a, g, m, st, h0 + s) * zl;
-            if (blk == 0) accb += ds0_of(a, g, st, m[0], m[4]) * zl;
         }
         for (int s = 0; s < ASSM_HS; ++s)
             if (h0 + s < H) a.dWa[(size_t)l * H + h0 + s] = acc[s];
-        if (blk == 0) a.dba[l] = accb;
+        if (blk == 0) a.dba[l] = 0.f;
     }
 }
 
 __device__ void bwd_z(const AssmBwd& a, int b) {
-    // dz[b] = sum over the predictions of molecule b (in order) of Wa du_p + ds0_p ba
+    // dz[b] = sum over the predictions of molecule b (in order) of Wa du_p  (ds0_p = 0: no ba term)
     __shared__ float du[ASSM_MAX_H];
     const int t = threadIdx.x, H = a.H, L = a.L;
     const float g = a.dloss[0];
@@ -272,11 +268,10 @@ __device__ void bwd_z(const AssmBwd& a, int b) {
         __syncthreads();
         for (int h = t; h < H; h += ASSM_THREADS) du[h] = du_of(a, g, m, st, h);
         __syncthreads();
-        const float d0 = ds0_of(a, g, st, m[0], m[4]);
         for (int q = 0, l = t; l < L && q < 4; ++q, l += ASSM_THREADS) {
             float s = 0.f;
             for (int h = 0; h < H; ++h) s += a.Wa[(size_t)l * H + h] * du[h];
-            acc[q] += s + d0 * a.ba[l];
+            acc[q] += s;
         }
     }
     for (int q = 0, l = t; l < L && q < 4; ++q, l += ASSM_THREADS) a.dz[(size_t)b * a.ldz + l] = acc[q];

@@ -40,6 +40,7 @@ class _MotifAssm(torch.autograd.Function):
         H, L, B = W1.shape[0], Wa.shape[0], z.shape[0]
         dev = rows.device
         z = z.contiguous()            # (dz is allocated like z and written at row stride z.stride(0))
+        rows = rows.contiguous()      # (likewise drows: zeros_like of a column view of a wider buffer is dense)
         act = torch.empty(rows.shape[0], H, dtype=torch.float32, device=dev)
         score = torch.empty(max(n_cand, 1), dtype=torch.float32, device=dev)
         stat = torch.empty(P, 4, dtype=torch.float32, device=dev)

@@ -120,9 +120,31 @@ class MotifGolden:
                 assert abs(l2 - stat[1]) <= 4 * rel * max(stat[1], 1e-12), (self.name, k, l2, stat[1])
 
 
-def assm_head_reference(rows, meta, C, W1, b1, Wa, ba, z):
+def head_case(seed, H, L, C, preds, B, distinct):
+    """Inputs of one attachment-head call: rows / meta of predictions given as (n, k, nth, b); ``distinct``: the rows of a
+    prediction differ (as under E_assm's Dropout), else every candidate repeats the prediction's one or two rows.
+    -> (rows, meta, W1, b1, Wa, ba, z, number of candidates), fp32 on the CPU."""
+    gen = torch.Generator().manual_seed(seed)
+    meta, rows, coff, roff = [], [], 0, 0
+    for n, k, nth, b in preds:
+        meta.append((n, k, nth, b, coff, roff))
+        if distinct:
+            rows.append(torch.randn(n * k, H, generator=gen))
+        else:
+            rows.append(torch.randn(k, H, generator=gen).repeat(n, 1))
+        coff, roff = coff + n, roff + n * k
+    W1 = torch.randn(H, H + 20, generator=gen) / H ** 0.5
+    b1 = torch.randn(H, generator=gen) * 0.1
+    Wa = torch.randn(L, H, generator=gen) / H ** 0.5
+    ba = torch.randn(L, generator=gen) * 0.3
+    z = torch.randn(B, L, generator=gen)
+    return torch.cat(rows), torch.tensor(meta, dtype=torch.int32), W1, b1, Wa, ba, z, coff
+
+
+def assm_head_reference(rows, meta, C, W1, b1, Wa, ba, z, scores_out=None):
     """(loss sum, accuracy): matchNN on [row | onehot(nth)], pair rows summed, zero-padded to C rows, W_assm, dot with
-    the molecule's latent, cross entropy with label 0 over all C rows, get_accuracy_sym.  Differentiable torch."""
+    the molecule's latent, cross entropy with label 0 over all C rows, get_accuracy_sym.  Differentiable torch.
+    ``scores_out``: a list that receives the [P, C] score matrix (detached)."""
     H = W1.shape[0]
     scores = []
     for n, k, nth, b, coff, roff in meta.tolist():
@@ -134,6 +156,8 @@ def assm_head_reference(rows, meta, C, W1, b1, Wa, ba, z):
         v = torch.cat([v, torch.zeros(C - n, H, dtype=rows.dtype)], dim=0)
         scores.append(((v @ Wa.t() + ba) * z[b]).sum(dim=-1))
     s = torch.stack(scores)
+    if scores_out is not None:
+        scores_out.append(s.detach())
     lab = torch.zeros(len(scores), dtype=torch.long)
     loss = torch.nn.functional.cross_entropy(s, lab, reduction="sum")
     # get_accuracy_sym; the real rows of a prediction are equal without dropout, which a matmul need not reproduce

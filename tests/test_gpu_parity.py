@@ -1643,7 +1643,10 @@ def test_rsample_with_perturbation_matches_torch_formula():
         assert float((a - b).abs().max()) <= 2e-5 * max(float(b.abs().max()), 1e-6)
 
 
-@pytest.mark.parametrize("M,N,masked", [(1, 7, False), (5, 64, True), (130, 721, True), (33, 1000, False)])
+@pytest.mark.parametrize("M,N,masked", [(1, 7, False), (5, 64, True), (130, 721, True), (33, 1000, False),
+                                        # the fixed-order loss sum past one trip of its 256-stride loop (two and five
+                                        # trips), and 33 trips of the class loop
+                                        (257, 33, True), (1030, 70, False), (4, 2100, True)])
 def test_softmax_ce_and_bce_kernels_against_torch(M, N, masked):
     """ggpm_softmax_ce (optional additive mask rows, arg-max, gradient) and ggpm_bce_logits vs torch, odd shapes."""
     from ggpm_amd.decoder_heads import bce_with_logits_sum, cross_entropy_sum

@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 import torch
 
-from motif_fixtures import MotifGolden, assm_head_reference, names
+from motif_fixtures import MotifGolden, assm_head_reference, head_case as _head_case, names
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -91,26 +91,6 @@ def test_backward_adds_into_existing_grad():
     for k, p in model.named_parameters():
         if k in first:
             assert torch.allclose(p.grad, 2 * first[k], rtol=1e-5, atol=1e-7), k
-
-
-def _head_case(seed, H, L, C, preds, B, distinct):
-    """rows / meta of predictions given as (n, k, nth, b); ``distinct``: the rows of a prediction differ (as under
-    E_assm's Dropout), else every candidate repeats the prediction's one or two rows."""
-    gen = torch.Generator().manual_seed(seed)
-    meta, rows, coff, roff = [], [], 0, 0
-    for n, k, nth, b in preds:
-        meta.append((n, k, nth, b, coff, roff))
-        if distinct:
-            rows.append(torch.randn(n * k, H, generator=gen))
-        else:
-            rows.append(torch.randn(k, H, generator=gen).repeat(n, 1))
-        coff, roff = coff + n, roff + n * k
-    W1 = torch.randn(H, H + 20, generator=gen) / H ** 0.5
-    b1 = torch.randn(H, generator=gen) * 0.1
-    Wa = torch.randn(L, H, generator=gen) / H ** 0.5
-    ba = torch.randn(L, generator=gen) * 0.3
-    z = torch.randn(B, L, generator=gen)
-    return torch.cat(rows), torch.tensor(meta, dtype=torch.int32), W1, b1, Wa, ba, z, coff
 
 
 @pytest.mark.parametrize("distinct", [False, True])
