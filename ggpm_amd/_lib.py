@@ -38,6 +38,11 @@ SIGNATURES = {
     "ggpm_gather_rows": (I, [P, I, P, I, I, P, I, I, I, P]),
     "ggpm_scatter_rows": (I, [P, I, P, I, I, P, I, I, P]),
     "ggpm_adam_step": (I, [P, P, P, P, c_size_t, c_float, c_float, c_float, c_float, c_float, I, P]),
+    # clipping and parameter groups of FlatAdam (csrc/gather.hip): groups are ggpm_adam_group[n_groups]
+    "ggpm_flat_sqnorm_workspace_bytes": (c_size_t, [c_size_t]),
+    "ggpm_flat_sqnorm_partials": (I, [P, c_size_t, P, c_size_t, P]),
+    "ggpm_flat_norm_finish": (I, [P, I, c_float, P, P]),
+    "ggpm_adam_step_groups": (I, [P, P, P, P, c_size_t, P, I, P, I, P, I, c_float, P, I, P]),
     "ggpm_onehot": (I, [P, I, I, P, I, I, I, P]),
     "ggpm_embed_graph": (I, [P, I, P, I, I, I, I, P, I, P, I, P]),
     "ggpm_level_bf16_storage": (I, [I, I]),

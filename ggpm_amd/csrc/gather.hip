@@ -221,6 +221,176 @@ extern "C" int ggpm_adam_step(float* p, const float* g, float* m, float* v, size
     return GGPM_OK;
 }
 
+// ---------------------------------------------------------------- gradient-norm clipping and parameter groups (FlatAdam)
+// clip_grad_norm_ (vae_train.py:82) and the four optimizers of vae_fine_tune_indv_opt.py:61-70 on the flat buffers.  The sum
+// of squares crosses workgroups through KERNEL BOUNDARIES only: one launch writes a double per workgroup, the next launch
+// (the Adam step, or the one-workgroup finish behind grad_norm() / param_norm()) adds them up in index order -- every
+// workgroup for itself, from the same values in the same order, so all of them hold the same bits.  No counters, no atomics.
+namespace {
+constexpr int NORM_THREADS = 1024;                       // 16 waves: one workgroup per CU keeps 64 KB of loads in flight
+constexpr int NORM_MAX_PARTIALS = GGPM_NORM_MAX_PARTIALS;
+
+__host__ __device__ inline unsigned norm_grid(size_t n) {
+    size_t blocks = ((n >> 2) + NORM_THREADS - 1) / NORM_THREADS;
+    return (unsigned)(blocks < 1 ? 1 : blocks > (size_t)NORM_MAX_PARTIALS ? (size_t)NORM_MAX_PARTIALS : blocks);
+}
+
+__device__ __forceinline__ void sq_acc4(double (&acc)[4], float4 x) {
+    acc[0] += (double)x.x * (double)x.x; acc[1] += (double)x.y * (double)x.y;
+    acc[2] += (double)x.z * (double)x.z; acc[3] += (double)x.w * (double)x.w;
+}
+
+// partials[blockIdx.x] = sum of squares of this workgroup's grid-stride share, fp64 throughout.  The order of every addition
+// is a function of n alone: four accumulators per thread (one per float4 component), lanes by shuffle, waves in index order.
+__global__ void __launch_bounds__(NORM_THREADS) flat_sqnorm_partials_k(const float* __restrict__ x, size_t n,
+                                                                       double* __restrict__ partials) {
+    __shared__ double wave_sum[NORM_THREADS / 64];
+    const size_t n4 = n >> 2, stride = (size_t)gridDim.x * NORM_THREADS;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    size_t i = (size_t)blockIdx.x * NORM_THREADS + threadIdx.x;
+    for (; i + 3 * stride < n4; i += 4 * stride) {         // four independent 16-byte loads in flight per lane
+        const float4 a = ggpm_ld4(x + 4 * i), b = ggpm_ld4(x + 4 * (i + stride)), c = ggpm_ld4(x + 4 * (i + 2 * stride)),
+                     d = ggpm_ld4(x + 4 * (i + 3 * stride));
+        sq_acc4(acc, a); sq_acc4(acc, b); sq_acc4(acc, c); sq_acc4(acc, d);
+    }
+    for (; i < n4; i += stride) sq_acc4(acc, ggpm_ld4(x + 4 * i));
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {         // tail of up to three elements
+        const double t = (double)x[(n4 << 2) + threadIdx.x];
+        acc[0] += t * t;
+    }
+    double s = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+#pragma unroll
+        for (int w = 0; w < NORM_THREADS / 64; ++w) t += wave_sum[w];
+        partials[blockIdx.x] = t;
+    }
+}
+
+// The partials, staged in LDS by the caller (a barrier behind the staging), summed in index order; the norm and
+// clip_grad_norm_'s coefficient max_norm / (norm + 1e-6) clamped to 1 as torch.clamp does (a NaN stays a NaN).
+__device__ __forceinline__ void norm_and_coef(const double* staged, int n_partials, float max_norm, float& norm, float& coef) {
+    double s = 0.0;
+    for (int i = 0; i < n_partials; ++i) s += staged[i];
+    norm = (float)sqrt(s);
+    const float c = max_norm / (norm + 1e-6f);
+    coef = c > 1.0f ? 1.0f : c;
+}
+
+__global__ void __launch_bounds__(NORM_MAX_PARTIALS) flat_norm_finish_k(const double* __restrict__ partials, int n_partials,
+                                                                        float max_norm, float* __restrict__ out) {
+    __shared__ double staged[NORM_MAX_PARTIALS];
+    if ((int)threadIdx.x < n_partials) staged[threadIdx.x] = partials[threadIdx.x];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float norm, coef;
+        norm_and_coef(staged, n_partials, max_norm, norm, coef);
+        out[0] = norm;
+        if (max_norm > 0.f) out[1] = coef;
+    }
+}
+
+struct AdamGroupsArgs {                                    // by value: row k of `hp` is group k
+    float hp[GGPM_ADAM_MAX_GROUPS][8];                     // b1, b2, eps, wd, step_size, inv_bc2_sqrt, 0, 0
+};
+
+// adam_flat_k's arithmetic with the hyper-parameters looked up per 64-float tile (tile_group; null: group 0 everywhere)
+// and the gradient scaled by the clip coefficient formed from `partials` (null: no clip).  n % 64 == 0.
+__global__ void __launch_bounds__(256) adam_groups_k(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                     float* __restrict__ v, size_t n, const uint8_t* __restrict__ tile_group,
+                                                     AdamGroupsArgs args, const double* __restrict__ partials,
+                                                     int n_partials, float max_norm, float* __restrict__ clip_out,
+                                                     int write_clipped) {
+    __shared__ double staged[NORM_MAX_PARTIALS];
+    __shared__ __attribute__((aligned(16))) float hp[GGPM_ADAM_MAX_GROUPS][8];
+    if (threadIdx.x < GGPM_ADAM_MAX_GROUPS * 8) (&hp[0][0])[threadIdx.x] = (&args.hp[0][0])[threadIdx.x];
+    if (partials && (int)threadIdx.x < n_partials) staged[threadIdx.x] = partials[threadIdx.x];
+    __syncthreads();
+    float coef = 1.0f;
+    if (partials) {
+        float norm;
+        norm_and_coef(staged, n_partials, max_norm, norm, coef);
+        if (clip_out && blockIdx.x == 0 && threadIdx.x == 0) { clip_out[0] = norm; clip_out[1] = coef; }
+    }
+    const bool scale = partials != nullptr, store_g = scale && write_clipped != 0;
+    const size_t n4 = n >> 2;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+        const int grp = tile_group ? (tile_group[i >> 4] & (GGPM_ADAM_MAX_GROUPS - 1)) : 0;
+        const float4 h0 = *reinterpret_cast<const float4*>(&hp[grp][0]);
+        const float b1 = h0.x, b2 = h0.y, eps = h0.z, wd = h0.w, step_size = hp[grp][4], inv_bc2_sqrt = hp[grp][5];
+        float4 pp = ggpm_ld4(p + 4 * i), gg = ggpm_ld4(g + 4 * i), mm = ggpm_ld4(m + 4 * i), vv = ggpm_ld4(v + 4 * i);
+        float* P = &pp.x; float* G = &gg.x; float* M = &mm.x; float* V = &vv.x;
+        if (scale) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) G[k] *= coef;
+            if (store_g) ggpm_st4(g + 4 * i, gg);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float gr = wd != 0.f ? G[k] + wd * P[k] : G[k];
+            M[k] = M[k] + (1.f - b1) * (gr - M[k]);
+            V[k] = b2 * V[k] + (1.f - b2) * gr * gr;
+            P[k] -= step_size * M[k] / (sqrtf(V[k]) * inv_bc2_sqrt + eps);
+        }
+        ggpm_st4(p + 4 * i, pp); ggpm_st4(m + 4 * i, mm); ggpm_st4(v + 4 * i, vv);
+    }
+}
+}  // namespace
+
+extern "C" size_t ggpm_flat_sqnorm_workspace_bytes(size_t n) { return (size_t)norm_grid(n) * sizeof(double); }
+
+extern "C" int ggpm_flat_sqnorm_partials(const float* x, size_t n, double* partials, size_t partials_bytes,
+                                         ggpm_stream_t stream) {
+    GGPM_CLEAR_STALE_ERROR();
+    if (!x || !partials || n == 0 || (((uintptr_t)x & 15) != 0) || (((uintptr_t)partials & 7) != 0)) return GGPM_ERR_ARG;
+    const unsigned grid = norm_grid(n);
+    if (partials_bytes < (size_t)grid * sizeof(double)) return GGPM_ERR_ARG;
+    flat_sqnorm_partials_k<<<grid, NORM_THREADS, 0, (hipStream_t)stream>>>(x, n, partials);
+    GGPM_CHECK_LAUNCH();
+    return GGPM_OK;
+}
+
+extern "C" int ggpm_flat_norm_finish(const double* partials, int n_partials, float max_norm, float* out,
+                                     ggpm_stream_t stream) {
+    GGPM_CLEAR_STALE_ERROR();
+    if (!partials || !out || n_partials < 1 || n_partials > NORM_MAX_PARTIALS) return GGPM_ERR_ARG;
+    if ((((uintptr_t)partials & 7) != 0) || (((uintptr_t)out & 3) != 0)) return GGPM_ERR_ARG;
+    flat_norm_finish_k<<<1, NORM_MAX_PARTIALS, 0, (hipStream_t)stream>>>(partials, n_partials, max_norm, out);
+    GGPM_CHECK_LAUNCH();
+    return GGPM_OK;
+}
+
+extern "C" int ggpm_adam_step_groups(float* p, float* g, float* m, float* v, size_t n, const uint8_t* tile_group,
+                                     int n_groups, const ggpm_adam_group* groups, int step, const double* partials,
+                                     int n_partials, float max_norm, float* clip_out, int write_clipped,
+                                     ggpm_stream_t stream) {
+    GGPM_CLEAR_STALE_ERROR();
+    if (!p || !g || !m || !v || !groups || n == 0 || n % 64 != 0 || step < 1) return GGPM_ERR_ARG;
+    if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) != 0) return GGPM_ERR_ARG;
+    if (n_groups < 1 || n_groups > GGPM_ADAM_MAX_GROUPS || (!tile_group && n_groups > 1)) return GGPM_ERR_ARG;
+    if (partials && (!(max_norm > 0.f) || n_partials < 1 || n_partials > NORM_MAX_PARTIALS || ((uintptr_t)partials & 7) != 0))
+        return GGPM_ERR_ARG;
+    if (((uintptr_t)clip_out & 3) != 0) return GGPM_ERR_ARG;
+    AdamGroupsArgs args = {};
+    for (int k = 0; k < n_groups; ++k) {
+        const ggpm_adam_group& q = groups[k];
+        const double bc1 = 1.0 - pow((double)q.beta1, step), bc2 = 1.0 - pow((double)q.beta2, step);
+        float* h = args.hp[k];
+        h[0] = q.beta1; h[1] = q.beta2; h[2] = q.eps; h[3] = q.weight_decay;
+        h[4] = (float)((double)q.lr / bc1); h[5] = (float)(1.0 / sqrt(bc2));
+    }
+    size_t blocks = ((n >> 2) + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    adam_groups_k<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(p, g, m, v, n, tile_group, args, partials, n_partials,
+                                                                   max_norm, clip_out, write_clipped);
+    GGPM_CHECK_LAUNCH();
+    return GGPM_OK;
+}
+
 extern "C" int ggpm_dropout(float* x, int rows, int cols, int ld, float p, unsigned int seed_lo, unsigned int seed_hi,
                             int site, ggpm_stream_t stream) {
     GGPM_CLEAR_STALE_ERROR();

@@ -232,6 +232,31 @@ int ggpm_property_latent_search(int mode, int B, const float* z, int ld, int hal
  *   m += (1-b1)(g' - m); v = b2 v + (1-b2) g'^2; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps),  g' = g + wd p */
 int ggpm_adam_step(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
                    float weight_decay, int step, ggpm_stream_t stream);
+/* Gradient-norm clipping (torch.nn.utils.clip_grad_norm_, vae_train.py:82) and per-group Adam (the four optimizers of
+ * vae_fine_tune_indv_opt.py:61-70) over the same flat buffers.  The sum of squares is combined ACROSS KERNEL BOUNDARIES:
+ * the partials launch writes one fp64 sum per workgroup into a caller-owned workspace; the launch behind it (the grouped Adam
+ * step, or the one-workgroup finish) adds the partials in index order.  Nothing is allocated, copied to the host or
+ * synchronised, and the result is the same bits on every call and in every workgroup.
+ *   partials:  x 16-byte aligned, any n >= 1; `partials` holds the workspace query's bytes (a function of n alone, at
+ *              most GGPM_NORM_MAX_PARTIALS doubles); n_partials of the calls below = those bytes / 8.
+ *   finish:    out[0] = (float)sqrt(sum); with max_norm > 0 also out[1] = min(max_norm / (out[0] + 1e-6f), 1), a NaN kept
+ *              (torch's clip coefficient).  max_norm <= 0 leaves out[1] alone. */
+#define GGPM_NORM_MAX_PARTIALS 256
+size_t ggpm_flat_sqnorm_workspace_bytes(size_t n);
+int ggpm_flat_sqnorm_partials(const float* x, size_t n, double* partials, size_t partials_bytes, ggpm_stream_t stream);
+int ggpm_flat_norm_finish(const double* partials, int n_partials, float max_norm, float* out, ggpm_stream_t stream);
+/* ggpm_adam_step's arithmetic with up to GGPM_ADAM_MAX_GROUPS hyper-parameter sets and an optional clip.  n % 64 == 0:
+ * tile_group[n / 64] (device, values < n_groups) names the group of every 64-float tile (FlatGradSync.ALIGN puts every
+ * parameter on such a boundary; padding may carry any group: zeros stay zeros); NULL with one group.  One step count
+ * serves all groups.  partials != NULL (n_partials, max_norm > 0): the gradient is used as g * coef, coef as in the
+ * finish above, formed by every workgroup for itself; clip_out (device float[2], may be NULL) receives {norm, coef};
+ * write_clipped != 0 also stores g * coef back to g.  A non-finite gradient propagates as under clip_grad_norm_ with
+ * error_if_nonfinite=False. */
+#define GGPM_ADAM_MAX_GROUPS 8
+typedef struct ggpm_adam_group { float lr, beta1, beta2, eps, weight_decay; } ggpm_adam_group;
+int ggpm_adam_step_groups(float* p, float* g, float* m, float* v, size_t n, const uint8_t* tile_group, int n_groups,
+                          const ggpm_adam_group* groups, int step, const double* partials, int n_partials, float max_norm,
+                          float* clip_out, int write_clipped, ggpm_stream_t stream);
 int ggpm_onehot(const int32_t* idx, int rows, int classes, float* out, int ld_out, int col_off, int zero_to,
                 ggpm_stream_t stream);
 /* embed_graph (ggpm/encoder.py:119-126) in one launch: hnode[N1, ld_n] = onehot(fnode), hmess[E1, ld_m] =
