@@ -93,6 +93,10 @@ SIGNATURES = {
     "ggpm_motif_decode_mlp": (I, [P, I, P, P, I, I, I, I, P, P, P, P, I, I, P, I, P, I, P]),
     "ggpm_hier_topk": (I, [P, I, I, P, I, I, P, I, I, I, P, P]),
     "ggpm_motif_decode_assm_score": (I, [P, I, I, I, P, P, I, P, I, P, P, P, P, I, P, P]),
+    # greedy decode of the hierarchical decoder (csrc/hier_decode.hip): dims int[14], state void*[21], params void*[36]
+    "ggpm_hier_decode_atom_step": (I, [P, P, P, P, P, P, I, P]),
+    "ggpm_hier_decode_tree_step": (I, [P, P, P, P, I, P, I, P, I, I, P, I, P, I, P]),
+    "ggpm_hier_decode_assm_score": (I, [P, P, P, P, P, P, I, I, I, I, P, I, P, P, P, I, P, I, I, P, P]),
     "ggpm_dropout": (I, [P, I, I, I, ctypes.c_float, ctypes.c_uint, ctypes.c_uint, I, P]),
     # property heads / latent search (csrc/property.hip): heads are ggpm_prop_head*, grads ggpm_prop_head_grads*
     "ggpm_property_heads_workspace_bytes": (c_size_t, [I, I, P, P]),

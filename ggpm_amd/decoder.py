@@ -544,6 +544,13 @@ class HierMPNDecoder(ScoreHeads):
         self.E_assm = self.hmpn.E_i
         if latent_size != hidden_size:
             self.W_root = nn.Linear(latent_size, hidden_size)
+        self.graph_batch_factory = None     # decode's graph batch when the call names none (ggpm_amd.hier_decode)
+
+    def decode(self, mols, src_mol_vecs, greedy=True, max_decode_step=100, beam=5, graph_batch_factory=None):
+        """reference ggpm/decoder.py:303-472 -> (results, graph_batch.get_mol()) on the library's kernels; the graph batch
+        is ``graph_batch_factory`` or else ``self.graph_batch_factory`` (ggpm_amd.hier_decode)."""
+        from .hier_decode import decode
+        return decode(self, mols, src_mol_vecs, greedy, max_decode_step, beam, graph_batch_factory)
 
     def schedule_hints(self) -> dict:
         """What ``DecodeSchedule.from_*`` can use of this decoder: diterG and the number of gates of its message function,

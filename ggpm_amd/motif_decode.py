@@ -36,6 +36,7 @@ from . import functional as F_
 from .decoder_heads import MAX_POS
 
 MAX_NB = 12                                     # IncBase's max_nb
+MAX_SUB_NODES = 30                              # IncTree's max_sub_nodes: the width of a cgraph row
 L_TREE, L_MLP, L_TOPK, L_ASSM = 2, 2, 1, 1      # launches per library call
 NO_FACTORY = ("MotifDecoder.decode needs a graph batch (the molecule-assembly object, the reference's IncGraph): pass "
               "graph_batch_factory= (ggpm_amd.synth_graph.SynthGraphBatch, or the reference's IncGraph wrapped as "
@@ -47,13 +48,16 @@ class DecodeTree:
     """IncBase / IncTree of reference ggpm/inc_graph.py:10-92 with lists and numpy.  Node 0 and message 0 are the pads;
     predecessors and successors are kept in insertion order, as networkx keeps them; the tables are written slot for
     slot as IncBase.add_edge writes them.  Every table write is also queued for the device copy (``take_edits``).
-    ``cgraph`` is not kept: the tree-only decode never reads it."""
+    ``cgraph`` (IncTree's cluster atoms per node, ``MAX_SUB_NODES`` wide) is kept only when asked for: the tree-only
+    decode never reads it.  With it, the second node column and the cgraph slots are queued as table edits 3 and 4."""
 
-    def __init__(self, max_nodes: int, max_edges: int):
+    def __init__(self, max_nodes: int, max_edges: int, max_nb: int = MAX_NB, cgraph: bool = False):
+        self.max_nb = max_nb
         self.fnode = np.zeros((max_nodes, 2), np.int64)
         self.fmess = np.zeros((max_edges, 3), np.int64)
-        self.agraph = np.zeros((max_nodes, MAX_NB), np.int64)
-        self.bgraph = np.zeros((max_edges, MAX_NB), np.int64)
+        self.agraph = np.zeros((max_nodes, max_nb), np.int64)
+        self.bgraph = np.zeros((max_edges, max_nb), np.int64)
+        self.cgraph = np.zeros((max_nodes, MAX_SUB_NODES), np.int64) if cgraph else None
         self.preds, self.succs = [[]], [[]]
         self.edge = {}
         self.n_edges = 1
@@ -74,16 +78,18 @@ class DecodeTree:
         return len(self.preds[i])
 
     def can_expand(self, i):
-        return len(self.preds[i]) < MAX_NB
+        return len(self.preds[i]) < self.max_nb
 
     def set_node_feature(self, i, clab, ilab):
         self.fnode[i] = (clab, ilab)
         self._node_edits[i] = clab
+        if self.cgraph is not None:
+            self._tab_edits[(3, i, 1)] = ilab
 
     def _write(self, tab, table, row, slot, value):
-        if not -MAX_NB <= slot < MAX_NB:
-            raise IndexError("decode tree: slot %d of a %d-slot row" % (slot, MAX_NB))
-        slot %= MAX_NB                  # slot -1 is the last one, as the reference's tensor indexing has it
+        if not -self.max_nb <= slot < self.max_nb:
+            raise IndexError("decode tree: slot %d of a %d-slot row" % (slot, self.max_nb))
+        slot %= self.max_nb             # slot -1 is the last one, as the reference's tensor indexing has it
         table[row, slot] = value
         self._tab_edits[(tab, row, slot)] = value
 
@@ -106,6 +112,10 @@ class DecodeTree:
         return idx
 
     def register_cgraph(self, i, nodes, edges, attached):
+        if self.cgraph is not None:
+            self.cgraph[i, :len(nodes)] = nodes         # (more atoms than the row holds raise, as the reference's write)
+            for s, a in enumerate(nodes):
+                self._tab_edits[(4, i, s)] = int(a)
         self.cluster[i], self.cluster_edges[i], self.attached[i] = nodes, edges, attached
 
     def update_attached(self, i, inter_label):
@@ -116,8 +126,9 @@ class DecodeTree:
         return self.cluster[i], self.cluster_edges[i], self.attached[i]
 
     def take_edits(self):
-        """-> (node edits [(node, motif)], table edits [(0 agraph / 1 bgraph / 2 fmess, row, slot, value)]) queued since
-        the last call: one per node / slot, its last value (the device applies the edits in parallel)"""
+        """-> (node edits [(node, motif)], table edits [(0 agraph / 1 bgraph / 2 fmess / with cgraph: 3 fnode column 1,
+        4 cgraph; row, slot, value)]) queued since the last call: one per node / slot, its last value (the device applies
+        the edits in parallel)"""
         out = list(self._node_edits.items()), [k + (v,) for k, v in self._tab_edits.items()]
         self._node_edits, self._tab_edits = {}, {}
         return out

@@ -13,10 +13,9 @@ Differences from the reference, on purpose:
     parameter gradient of the model as a side effect) is not reproduced;
   * the heads must be in eval form (``model.eval()``, as optimize.py runs) or have dropout 0: the search applies no
     dropout, so heads in training mode with dropout > 0 raise.
-``forward`` for the tree-only PropOptVAE ends, as the reference's does, in the greedy ``MotifDecoder.decode`` through the
-graph batch ``args.graph_batch_factory`` (else the decoder's); for HierPropOptVAE it raises NotImplementedError (the
-atom level of HierMPNDecoder.decode needs atom features from real chemistry).  ``optimize(batch)`` returns everything
-before the decode.
+``forward`` ends, as the reference's does, in the decoder's greedy ``decode`` (``MotifDecoder.decode`` for the tree-only
+PropOptVAE, ``HierMPNDecoder.decode`` for HierPropOptVAE) through the graph batch ``args.graph_batch_factory`` (else the
+decoder's).  ``optimize(batch)`` returns everything before the decode.
 """
 from __future__ import annotations
 
@@ -57,20 +56,12 @@ class PropertyVAEOptimizer(nn.Module):
         return self.func_dict[self.optimize_type]
 
     def forward(self, batch, args=None):
-        """reference ggpm/property_control.py:33-63 for the tree-only PropOptVAE: ``optimize(batch)``, the heads on the
-        optimised latent, greedy decode of 150 steps -> ((homo [B], lumo [B]), (results, molecules))."""
-        from .motif_decoder import MotifDecoder
-        from .motif_decode import NO_FACTORY
-        dec = getattr(self.model, "decoder", None)
-        if not isinstance(dec, MotifDecoder):
-            raise NotImplementedError("the reference's forward ends in HierMPNDecoder.decode(), whose atom level needs atom "
-                                      "features from rdkit chemistry and is not part of this build; optimize(batch) "
-                                      "returns the optimised latents and predictions")
-        factory = getattr(args, "graph_batch_factory", None)
-        if factory is None:
-            factory = getattr(dec, "graph_batch_factory", None)
-        if factory is None:
-            raise NotImplementedError(NO_FACTORY)
+        """reference ggpm/property_control.py:33-63 (the tree-only PropOptVAE) and :186-216 (HierPropOptVAE):
+        ``optimize(batch)``, the heads on the optimised latent, greedy decode of 150 steps -> ((homo [B], lumo [B]),
+        (results, molecules))."""
+        from .property_vae import _graph_batch_factory
+        dec = self.model.decoder
+        factory = _graph_batch_factory(self.model, args)
         latent, _ = self.optimize(batch)
         half = self.model.latent_size
         with torch.no_grad():

@@ -240,6 +240,17 @@ class HierPropertyVAE(nn.Module):
     def rsample(self, z_vecs, W_mean, W_var, perturb=True):
         return rsample(z_vecs, W_mean, W_var, perturb)
 
+    def reconstruct(self, batch, args=None):
+        """reference ggpm/property_vae.py:39-45: the no-grad encoder, the mean latent, greedy decode of 150 steps ->
+        (results, molecules).  The graph batch: ``args.graph_batch_factory``, else the decoder's."""
+        factory = _graph_batch_factory(self, args)
+        with torch.no_grad():
+            tree_tensors, graph_tensors = make_cuda(batch[2])
+            root_vecs = self.encoder.forward_padded(tree_tensors, graph_tensors)[0]
+            root_vecs, _ = rsample(root_vecs, self.R_mean, self.R_var, perturb=False)
+        return self.decoder.decode(batch[0], (root_vecs, root_vecs, root_vecs), greedy=True, max_decode_step=150,
+                                   graph_batch_factory=factory)
+
     def forward(self, mols, graphs, tensors, orders, homos=None, lumos=None, beta=0.0, perturb_z=True, schedule=None):
         if schedule is None:
             schedule = getattr(graphs, "ggpm_schedule", None)       # dataloader.ScheduleAhead: built one batch ahead
@@ -380,8 +391,16 @@ class HierPropOptVAE(_ClipNegativeLoss, nn.Module):
         return _predict_properties(self, batch)
 
     def reconstruct(self, batch, args=None):
-        raise NotImplementedError("HierPropOptVAE.reconstruct needs HierMPNDecoder.decode(), which needs rdkit "
-                                  "chemistry and is not part of this build")
+        """reference ggpm/property_vae.py:169-188: the no-grad encoder, the mean latent, the property heads on it, greedy
+        decode of 150 steps -> ((homo [B], lumo [B]), (results, molecules)).  The graph batch: ``args.graph_batch_factory``,
+        else the decoder's."""
+        factory = _graph_batch_factory(self, args)
+        with torch.no_grad():
+            root_vecs, _ = self.encode_latent(batch[2], perturb=False)
+            half = self.latent_size
+            props = self.property_optim.predict(homo_vecs=root_vecs[:, :half], lumo_vecs=root_vecs[:, half:])
+        return props, self.decoder.decode(batch[0], (root_vecs, root_vecs, root_vecs), greedy=True, max_decode_step=150,
+                                          graph_batch_factory=factory)
 
     def forward(self, mols, graphs, tensors, orders, homos, lumos, beta=0.0, perturb_z=True, schedule=None):
         from . import fused
@@ -434,11 +453,15 @@ def _predict_properties(model, batch):
 def _graph_batch_factory(model, args):
     """decode's graph batch for reconstruct: ``args.graph_batch_factory``, else the decoder's; neither raises before the
     batch is touched."""
-    from .motif_decode import NO_FACTORY
     factory = getattr(args, "graph_batch_factory", None)
     if factory is None:
         factory = getattr(model.decoder, "graph_batch_factory", None)
     if factory is None:
+        from .motif_decoder import MotifDecoder
+        if isinstance(model.decoder, MotifDecoder):
+            from .motif_decode import NO_FACTORY
+        else:
+            from .hier_decode import NO_FACTORY
         raise NotImplementedError(NO_FACTORY)
     return factory
 

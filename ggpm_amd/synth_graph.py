@@ -20,11 +20,26 @@ against the reference, anywhere:
 Together the rules give one candidate (bond parents), several (ring parents), none (exhausted parents) and refusals (N,
 O and S atoms), so decode meets every branch of the reference's loop: the fall-through to the next candidate and beam
 entry, and the forced backtrack.  Atom ids are global over the batch and start at 1, as IncGraph's do.
+
+``SynthHierGraphBatch`` adds what ``HierMPNDecoder.decode`` (reference ggpm/decoder.py:303-472) reads besides: the atom-level
+tables ``fnode``, ``fmess``, ``agraph`` and ``bgraph`` of ``IncBase`` (reference ggpm/inc_graph.py:10-57), written in place
+by ``add_mol`` slot for slot as ``IncGraph.add_mol`` (:136-187) writes them, and returned by ``get_tensors()`` as host
+tensors:
+  * an atom's feature is the one-hot of ``avocab[(symbol, 0)]`` (an unknown symbol is the vocabulary's ``KeyError``).  It is
+    handed to ``add_node(feature)``, which -- as ``IncBase.add_node`` (:23-29) -- does not store it: the ``fnode`` rows stay
+    zero in the reference's decode, and so they do here;
+  * a message row is ``[one-hot source atom | one-hot bond type | one-hot(nth_child if the destination atom is attached,
+    else 0)]``; the source symbol is the fragment's own label of that atom, as the reference reads it from the fragment;
+  * bond types: the bond of a two-atom fragment is type 0, every ring bond type 1;
+  * both directions of a new bond are added, (a1, a2) then (a2, a1), in the fragment's bond order (ring order, the closing
+    bond last); a bond that exists already (the shared bond of a fused ring) is not added again;
+  * ``add_mol`` returns *directed* message ids, two per bond of the fragment, existing bonds included.
 """
 from __future__ import annotations
 
 from collections import defaultdict
 
+import numpy as np
 import torch
 
 ATOMS = ("C", "N", "O", "S")
@@ -119,3 +134,109 @@ class SynthGraphBatch:
         """IncGraph's (fnode, fmess, agraph, bgraph, scope) as far as the tree-only decode reads them: the row count of
         fmess (the reference sizes a message state it never uses from it)."""
         return None, torch.zeros(self.max_edges * self.batch_size, max(self.edge_fdim, 1)), None, None, None
+
+
+NUM_BOND_TYPES = 4      # len(MolGraph.BOND_LIST)
+MAX_POS = 20            # MolGraph.MAX_POS
+
+
+class SynthAtomVocab:
+    """The reference's ``common_atom_vocab`` as far as the synthetic fragments need it: 38 entries, the neutral C, N, O
+    and S at their places in that table."""
+
+    IDS = {("C", 0): 5, ("N", 0): 21, ("O", 0): 24, ("S", 0): 30}
+
+    def size(self):
+        return 38
+
+    def __getitem__(self, key):
+        return self.IDS[key]
+
+
+class SynthHierGraphBatch(SynthGraphBatch):
+    """``SynthGraphBatch`` with IncGraph's atom-level tables (see the module docstring).  ``get_assm_cands``,
+    ``try_add_mol``, ``get_mol``, ``anchor_label`` and the fragment rules are SynthGraphBatch's."""
+
+    def __init__(self, vocab, avocab, batch_size, node_fdim=0, edge_fdim=0, max_nodes=100, max_edges=300, max_nb=10):
+        super().__init__(vocab, avocab, batch_size, max_nodes, max_edges, node_fdim, edge_fdim, max_nb)
+        self.max_nb = max_nb
+        # numpy tables (scalar writes cost a tenth of a tensor's); get_tensors() hands out tensors over the same memory
+        self._fnode = np.zeros((max_nodes * batch_size, node_fdim), np.float32)
+        self._fmess = np.zeros((max_edges * batch_size, edge_fdim), np.float32)
+        self._agraph = np.zeros((max_edges * batch_size, max_nb), np.int64)      # sized by edges, as IncBase's
+        self._bgraph = np.zeros((max_edges * batch_size, max_nb), np.int64)
+        self.fnode, self.fmess = torch.from_numpy(self._fnode), torch.from_numpy(self._fmess)
+        self.agraph, self.bgraph = torch.from_numpy(self._agraph), torch.from_numpy(self._bgraph)
+        self.preds, self.succs = [[]], [[]]
+        self.edge_dict = {None: 0}
+
+    def get_tensors(self):
+        """IncGraph's (fnode, fmess, agraph, bgraph, scope): host tensors that ``add_mol`` writes in place"""
+        return self.fnode, self.fmess, self.agraph, self.bgraph, None
+
+    def get_atom_feature(self, symbol):
+        f = np.zeros(self.avocab.size(), np.float32)
+        f[self.avocab[(symbol, 0)]] = 1
+        return f
+
+    def get_mess_feature(self, symbol, bond_type, nth_child):
+        n = self.avocab.size()
+        f = np.zeros(n + NUM_BOND_TYPES + MAX_POS, np.float32)
+        f[:n][self.avocab[(symbol, 0)]] = 1
+        f[n:n + NUM_BOND_TYPES][bond_type] = 1
+        f[n + NUM_BOND_TYPES:][nth_child] = 1
+        return f
+
+    def add_node(self, feature=None):
+        """IncBase.add_node: the feature is not stored"""
+        self.preds.append([])
+        self.succs.append([])
+        return len(self.preds) - 1
+
+    def add_edge(self, i, j, feature=None):
+        """IncBase.add_edge"""
+        if (i, j) in self.edge_dict:
+            return self.edge_dict[(i, j)]
+        self.preds[j].append(i)
+        self.succs[i].append(j)
+        self.edge_dict[(i, j)] = idx = len(self.edge_dict)
+        self._agraph[j, len(self.preds[j]) - 1] = idx
+        if feature is not None:
+            self._fmess[idx, :len(feature)] = feature
+        in_edges = [self.edge_dict[(k, i)] for k in self.preds[i] if k != j]
+        self._bgraph[idx, :len(in_edges)] = in_edges
+        for k in self.succs[j]:
+            if k != i:
+                self._bgraph[self.edge_dict[(j, k)], len(self.preds[j]) - 2] = idx
+        return idx
+
+    def add_mol(self, bid, ismiles, inter_label, nth_child):
+        """-> (the fragment's atoms, its directed message ids, the parent atoms it shares in attach-point order)"""
+        size, labels, _ = fragment(ismiles)
+        shared = {int(p): int(a) for a, p in inter_label}
+        atoms, attached = [], []
+        for i in range(size):
+            if i in shared:
+                atoms.append(shared[i])
+                attached.append(shared[i])
+                continue
+            feature = self.get_atom_feature(labels[i])
+            self.label.append(labels[i])
+            self.degree.append(0)
+            self.owner.append(bid)
+            idx = len(self.label) - 1
+            assert idx == self.add_node(feature)
+            atoms.append(idx)
+            self.batch[bid].append(idx)
+        ring = [(i, i + 1) for i in range(size - 1)] + ([(size - 1, 0)] if size > 2 else [])
+        bond_type = 0 if size == 2 else 1
+        bonds = []
+        for p, q in ring:
+            a1, a2 = atoms[p], atoms[q]
+            if ((a1, a2) if a1 < a2 else (a2, a1)) not in self.bonds:
+                self._bond(a1, a2)
+                self.add_edge(a1, a2, self.get_mess_feature(labels[p], bond_type, nth_child if a2 in attached else 0))
+                self.add_edge(a2, a1, self.get_mess_feature(labels[q], bond_type, nth_child if a1 in attached else 0))
+            bonds.extend([self.edge_dict[(a1, a2)], self.edge_dict[(a2, a1)]])
+        self._mol.pop(bid, None)
+        return atoms, bonds, [shared[p] for p in sorted(shared)]

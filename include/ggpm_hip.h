@@ -690,6 +690,44 @@ int ggpm_motif_decode_assm_score(const float* E_assm, int n_ids, int H, int L, c
                                  int P, const float* W1, int ldw, const float* b1, const float* Wa, const float* ba,
                                  const float* z, int ldz, float* score, ggpm_stream_t stream);
 
+/* Greedy decode of the hierarchical decoder (HierMPNDecoder.decode, ggpm/decoder.py:303-472; csrc/hier_decode.hip).
+ * dims: host int[14] {rnn_type, H, max_pos, N, E, NA, EA, atom_size, edge_fdim, diterT, diterG, n_motif, n_attach, B}.
+ * state: host array of 21 device pointers, resident for the decode -- the tree tables fnode [N x 2], fmess [E x 2] (source
+ * node, position), agraph [N x 12], bgraph [E x 12], cgraph [N x 30] (int32); the atom tables fnode [NA x atom_size], fmess
+ * [EA x edge_fdim] (fp32), agraph [EA x 10], bgraph [EA x 10] (int32); the atom level's states h0, h1, c0, c1 [EA x H] (two
+ * buffers: a Jacobi iteration reads one and writes the other; both agree between calls); the atom read-outs [NA x H] and
+ * the step that wrote each [NA] (int32); the inter level's h, c and the tree level's h, c [E x H]; the inter and tree node
+ * inputs of the current call [B x H].  The c pointers may be null for GRU.
+ * params: host array of 36 device pointers (contiguous fp32) -- the atom, inter and tree cells, 8 slots each (GRU {W_z, b_z,
+ * W_r, U_r, b_Ur, W_h, b_h, unused}, LSTM {W_i, b_i, W_o, b_o, W_f, b_f, W, b}; input widths edge_fdim, H + max_pos,
+ * H + max_pos), then graph_encoder.W_o.0 {weight [H x (atom_size + H)], bias}, inter_encoder.W_o.0, tree_encoder.W_o.0
+ * {weight [H x 2H], bias}, E_i [n_attach x H], E_c [n_motif x H], W_i.0 {weight [H x 2H], bias}, W_c.0 {weight, bias}.
+ * ggpm_hier_decode_atom_step (2 + diterG launches): `up` holds, at the int32 offsets offs[0..10], the tree edits (counts[0]
+ * quads {table 0 agraph / 1 bgraph / 2 fmess / 3 fnode / 4 cgraph, row, slot, value}), then for the atom tables fnode,
+ * fmess, agraph, bgraph the ids of counts[1..4] changed rows and those rows (fp32 bits for the first two), then counts[5]
+ * cluster messages and counts[6] cluster atoms.  Applies the edits, resets the listed messages, runs diterG Jacobi
+ * iterations of the GRU / LSTM over them (input row fmess, neighbours bgraph), writes relu(W_o [fnode | sum of h over
+ * agraph]) of the listed atoms to the read-out rows and stamps them with `stamp`.
+ * ggpm_hier_decode_tree_step: per node of `nodes` (n_nodes <= B) the inter input relu(W_i [E_i[fnode[.,1]] | sum over
+ * cgraph of the read-out rows stamped `stamp`]) and the tree input relu(W_c [E_c[fnode[.,0]] | inter read-out]).  n_mess
+ * == 0 (1 launch; n_edits must be 0): both levels' read-outs, the tree's to node_out row r.  n_mess > 0 (5 launches): the
+ * tree edits, then per level the new messages (pairs {message, mess_out row or -1}: reset, input [node input of the source
+ * node, zero when it is not among `nodes` | onehot(position)], diterT sparse iterations over bgraph), inter before tree;
+ * the tree level's hidden rows go to mess_out.  No new message may appear in another new message's bgraph row.
+ * ggpm_hier_decode_assm_score (1 launch, one workgroup per candidate): meta rows {n candidates, k (1 or 2), nth_child,
+ * molecule, first candidate, first id, first atom}; candidate c of a row reads k atoms from `atoms` and scores
+ * (W_assm sum_{j<k} relu(matchNN [read-out[atom_j] | E_assm[id_j] | onehot(nth)]) + b) . z[molecule]; a read-out row not
+ * stamped `stamp` reads as zero.  W1 [H x ldw], ldw >= 2H + max_pos.  A candidate whose row is out of range scores NaN. */
+int ggpm_hier_decode_atom_step(const int* dims, void* const* state, const void* const* params, const int32_t* up,
+                               const int* offs, const int* counts, int stamp, ggpm_stream_t stream);
+int ggpm_hier_decode_tree_step(const int* dims, void* const* state, const void* const* params, const int32_t* edits,
+                               int n_edits, const int32_t* nodes, int n_nodes, const int32_t* mess, int n_mess, int stamp,
+                               float* node_out, int ld_node, float* mess_out, int ld_mess, ggpm_stream_t stream);
+int ggpm_hier_decode_assm_score(const int* dims, void* const* state, const float* E_assm, const int32_t* meta,
+                                const int32_t* ids, const int32_t* atoms, int P, int n_cand, int n_ids, int n_atoms,
+                                const float* W1, int ldw, const float* b1, const float* Wa, const float* ba, int L,
+                                const float* z, int ldz, int stamp, float* score, ggpm_stream_t stream);
+
 /* ------------------------------------------------------------------ whole-encoder drivers
  * HierMPNEncoder.forward (ggpm/encoder.py:140-157, with embed_graph/inter/tree/root :96-138) and its backward as ONE
  * call each: the same kernels the op-by-op host path issues, sequenced from C++ (GRU or LSTM message function).
