@@ -1,5 +1,6 @@
 """fp64 restatements of what the greedy-decode kernels (csrc/motif_decode.hip) compute, one call at a time, and the
-seeded inputs the kernel tests share with tests/golden/make_golden_topk.py.  CPU only (numpy / torch fp64).
+seeded inputs the kernel tests share with tests/golden/make_golden_topk.py, and a decode backend made of them
+(``OracleBackend``: ``ggpm_amd.motif_decode``'s host loop runs on it without a GPU).  CPU only (numpy / torch fp64).
 
 Anchors outside the code under test:
   * the message update and the read-out go through ``oracle.ref_encoder`` (``gru_sparse_forward`` / ``lstm_sparse_forward``,
@@ -143,6 +144,75 @@ def root_topk(cls, icls, owner, k, ties=False):
         top = _select(v, k, gaps)
         S[r], C[r], A[r] = v[top], c, top
     return S, C, A, _min_gap(gaps, ties)
+
+
+def heads_topk(p, vecs, ctx, owner, k, root):
+    """clsNN and iclsNN on [vecs | ctx], then the root selection or hier_topk -> (scores, motifs, attachments) [M, k]"""
+    w = lambda seq: [p[seq + n] for n in (".0.weight", ".0.bias", ".3.weight", ".3.bias")]     # noqa: E731
+    cls, icls = mlp(vecs, ctx, *w("clsNN"))[1].numpy(), mlp(vecs, ctx, *w("iclsNN"))[1].numpy()
+    return (root_topk if root else hier_topk)(cls, icls, owner, k)[:3]
+
+
+# ---------------------------------------------------------------------------------------------- a decode backend
+class OracleBackend:
+    """``ggpm_amd.motif_decode.HipBackend``'s interface in fp64 on the CPU.  It keeps its own mirrors of the tables and
+    brings them up to date from the edits alone, as the device does."""
+
+    def __init__(self, dec, src_mol_vecs, B, N, E, beam):
+        self.B, self.H, self.L = B, dec.hidden_size, dec.latent_size
+        self.p = f64({k: v.detach().cpu().numpy() for k, v in dec.state_dict().items()})
+        self.rnn = "LSTM" if hasattr(dec.hmpn.tree_encoder.rnn, "W_f") else "GRU"
+        self.depth = dec.hmpn.tree_encoder.rnn.depth
+        self.src = [torch.as_tensor(v.detach().cpu().numpy()).double() for v in src_mol_vecs]
+        self.fnode = np.zeros(N, np.int64)
+        self.tabs = {0: np.zeros((N, MAX_NB), np.int64), 1: np.zeros((E, MAX_NB), np.int64), 2: np.zeros((E, 2), np.int64)}
+        self.h, self.c = torch.zeros(E, self.H, dtype=torch.float64), torch.zeros(E, self.H, dtype=torch.float64)
+        owner = getattr(dec.vocab, "owner", None)
+        self.owner = np.asarray(owner if owner is not None else torch.as_tensor(dec.vocab.mask).argmax(dim=0).numpy())
+        self.new_counts()
+
+    def new_counts(self):
+        self.cur = {"launches": 0, "d2h": 0, "h2d": 0, "mess": 0, "expand": 0, "scored": 0, "wait_s": 0.0}
+        return self.cur
+
+    def _edits(self, tedits):
+        for tab, row, slot, v in np.asarray(tedits).reshape(-1, 4):
+            if tab == 3:
+                assert slot == 0        # (a tree without cgraph queues the motif only)
+                self.fnode[row] = v
+            else:
+                self.tabs[int(tab)][row, slot] = v
+
+    def root(self, k0):
+        init = self.src[0] if self.L == self.H else R._affine(self.p, "W_root", self.src[0])
+        self.h[1:self.B + 1] = init
+        return heads_topk(self.p, init, self.src[1], self.owner, k0, True)
+
+    def phase1(self, tedits, aedits, edges, atoms, nodes, bidx):
+        self._edits(tedits)
+        read = torch.stack([tree_readout(self.p, self.h, self.fnode, self.tabs[0], int(n)) for n in nodes])
+        w = [self.p["topoNN" + n] for n in (".0.weight", ".0.bias", ".3.weight", ".3.bias")]
+        return mlp(read, self.src[1][_lt(bidx)], *w, sigmoid=True)[1].reshape(-1).numpy()
+
+    def phase2(self, tedits, nodes, mess, expanding, k):
+        self._edits(tedits)
+        mess = np.asarray(mess, np.int64).reshape(-1, 2)
+        if len(mess):
+            self.h, c = tree_messages(self.p, self.rnn, self.depth, self.h, self.c, self.fnode, self.tabs[2], self.tabs[1],
+                                      mess[:, 0])
+            self.c = self.c if c is None else c
+        if not len(expanding):
+            return None
+        rows = mess[mess[:, 1] >= 0]
+        vecs = torch.zeros(len(expanding), self.H, dtype=torch.float64)
+        vecs[_lt(rows[:, 1])] = self.h[_lt(rows[:, 0])]
+        return heads_topk(self.p, vecs, self.src[1][_lt(expanding)], self.owner, k, False)
+
+    def phase3(self, meta, ids, atoms, n_cand):
+        out = np.zeros(n_cand)
+        for n, k, nth, b, coff, roff, _ in np.asarray(meta).reshape(-1, 7):
+            out[coff:coff + n] = assm_score(self.p, n, ids[roff:roff + k], nth, self.src[2][b]).numpy()
+        return out
 
 
 # ---------------------------------------------------------------------------------------------- seeded inputs

@@ -1,5 +1,6 @@
 """fp64 restatements of what the kernels of csrc/hier_decode.hip compute, one call at a time, and a decode backend made of
-them (``OracleBackend``: ``ggpm_amd.hier_decode``'s host loop runs on it without a GPU).  CPU only (torch fp64).
+them (``OracleBackend``: the host loop of ``ggpm_amd.hier_decode.decode`` runs on it without a GPU).  CPU only (torch
+fp64).
 
 Anchors outside the code under test: every level goes through ``oracle.ref_encoder`` (``inc_mpn_forward``,
 ``embed_sub_tree``, ``inc_hier_forward``: the restatement of IncHierMPNEncoder that tests/test_oracle_golden.py pins to the
@@ -130,12 +131,7 @@ class OracleBackend:
         return self.cur
 
     def _heads(self, vecs, bidx, k, root):
-        ctx = self.src[1][_lt(bidx)]
-        w = lambda seq: [self.p[seq + n] for n in (".0.weight", ".0.bias", ".3.weight", ".3.bias")]     # noqa: E731
-        cls = O.mlp(vecs, ctx, *w("clsNN"))[1].numpy()
-        icls = O.mlp(vecs, ctx, *w("iclsNN"))[1].numpy()
-        s, c, a, _ = (O.root_topk if root else O.hier_topk)(cls, icls, self.owner, k)
-        return s, c, a
+        return O.heads_topk(self.p, vecs, self.src[1][_lt(bidx)], self.owner, k, root)
 
     def root(self, k0):
         init = self.src[0] if self.L == self.H else R._affine(self.p, "W_root", self.src[0])
@@ -160,6 +156,8 @@ class OracleBackend:
         return O.mlp(out["tnode"], self.src[1][_lt(bidx)], *w, sigmoid=True)[1].reshape(-1).numpy()
 
     def phase2(self, tedits, nodes, mess, expanding, k):
+        if not len(mess):
+            return None
         self._tree_edits(tedits)
         mess = np.asarray(mess).reshape(-1, 2)
         out = tree_step(self.p, self.rnn, self.dT, self.tt, self.anode, self.ih, self.ic, self.th, self.tc, nodes,

@@ -88,7 +88,7 @@ def test_node_edits_across_a_wave_boundary():
     with torch.no_grad():
         results, _ = run.run()
     # the device's motif table, read back once after the loop, against the host's
-    got = run.fnode[:run.tree.n_nodes].cpu().numpy()
+    got = run.be.fnode[:run.tree.n_nodes].cpu().numpy()
     want = run.tree.fnode[:run.tree.n_nodes, 0]
     pending = dict(run.tree.take_edits()[0])     # the last step's assembly edits are not uploaded (no step reads them)
     for n, v in pending.items():
