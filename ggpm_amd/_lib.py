@@ -97,6 +97,10 @@ SIGNATURES = {
     "ggpm_hier_decode_atom_step": (I, [P, P, P, P, P, P, I, P]),
     "ggpm_hier_decode_tree_step": (I, [P, P, P, P, I, P, I, P, I, I, P, I, P, I, P]),
     "ggpm_hier_decode_assm_score": (I, [P, P, P, P, P, P, I, I, I, I, P, I, P, P, P, I, P, I, I, P, P]),
+    # seeded draws of the sampled decode and of the prior (csrc/sample.hip)
+    "ggpm_sample_topo": (I, [P, P, P, I, I, ctypes.c_uint, ctypes.c_uint, P, P]),
+    "ggpm_sample_beam_order": (I, [P, P, P, I, I, I, ctypes.c_uint, ctypes.c_uint, P, P]),
+    "ggpm_sample_normal": (I, [P, I, I, I, P, ctypes.c_uint, ctypes.c_uint, P]),
     "ggpm_dropout": (I, [P, I, I, I, ctypes.c_float, ctypes.c_uint, ctypes.c_uint, I, P]),
     # property heads / latent search (csrc/property.hip): heads are ggpm_prop_head*, grads ggpm_prop_head_grads*
     "ggpm_property_heads_workspace_bytes": (c_size_t, [I, I, P, P]),

@@ -552,6 +552,16 @@ class HierMPNDecoder(ScoreHeads):
         from .hier_decode import decode
         return decode(self, mols, src_mol_vecs, greedy, max_decode_step, beam, graph_batch_factory)
 
+    def decode_sampled(self, mols, src_mol_vecs, seed=None, sample_ids=None, max_decode_step=100, beam=5,
+                       graph_batch_factory=None):
+        """The reference's ``decode(..., greedy=False)`` (ggpm/decoder.py:371-374, 409-416) -> what ``decode`` returns.  The topology
+        decision is a Bernoulli draw and the beam entries are tried in an order drawn without replacement; the draws come
+        from a counter-based stream keyed by ``seed`` (an int, 64 bits used; ``None`` takes them from torch's default CPU
+        generator) and by ``sample_ids`` (one int per molecule, default ``arange``), so a molecule's draws do not depend
+        on its batch (*Sampled decoding and the prior*)."""
+        from .hier_decode import decode_sampled
+        return decode_sampled(self, mols, src_mol_vecs, seed, sample_ids, max_decode_step, beam, graph_batch_factory)
+
     def schedule_hints(self) -> dict:
         """What ``DecodeSchedule.from_*`` can use of this decoder: diterG and the number of gates of its message function,
         so that the native builder prepares the tables that depend on them in the same call."""

@@ -40,6 +40,23 @@ def _need_gpu(*ts: torch.Tensor) -> None:
                                % t.device.type)
 
 
+def sample_normal(rows: int, cols: int, seed_lo: int, seed_hi: int, ids=None, device=None, ld: Optional[int] = None):
+    """[rows, cols] standard normals of the seeded stream (csrc/sample.hip, site PRIOR), row r keyed by ``ids[r]``
+    (default ``arange``): a row's values depend on its id, the column and the seed only"""
+    dev = torch.device("cuda") if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("ggpm_amd: sample_normal runs on the MI355X (got device %s); there is no CPU path" % dev)
+    ids = torch.arange(rows, dtype=torch.int32) if ids is None else torch.as_tensor(ids).to(torch.int64).bitwise_and(
+        0xFFFFFFFF).to(torch.int32)
+    if ids.shape != (rows,):
+        raise ValueError("sample_normal: %d ids for %d rows" % (ids.numel(), rows))
+    out = torch.zeros(rows, cols if ld is None else ld, device=dev)
+    ids = ids.to(dev)
+    _lib.check(_lib.load().ggpm_sample_normal(_p(out), rows, cols, out.stride(0), _p(ids), seed_lo & 0xFFFFFFFF,
+                                              seed_hi & 0xFFFFFFFF, _stream()), "sample_normal")
+    return out[:, :cols]
+
+
 def padded_hidden(H: int) -> int:
     return (H + 15) // 16 * 16
 

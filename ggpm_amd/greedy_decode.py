@@ -24,6 +24,13 @@ and the tables, resident for the whole decode and edited from uploads.  One step
      nothing.  An entry that kept an exception raises it here, or is the failed expansion (``CAUGHT``).
 At most 3 uploads and 3 device-to-host copies per step, and a number of launches that depends on the phases run only,
 whatever the batch size or the beam (``last_decode_stats`` of the decoder holds the counts of every step).
+
+Sampled mode (``decode_sampled``, the reference's ``greedy=False``): with a :class:`Sampling` the loop
+takes the topology decision from a Bernoulli draw and tries the beam entries in an order drawn without replacement.  The
+draws come from a seeded counter-based stream keyed by the molecules' sample ids: the device backend launches one draw
+behind the sigmoid head and one behind ``hier_topk`` and each comes back in the copy of the values it was drawn from
+(``topo_draws``, ``beam_order``), or a host ``sampler`` (a test seam) makes them from those values.  The greedy path and
+its calls to the backend are the same with and without this mode.
 """
 from __future__ import annotations
 
@@ -41,7 +48,7 @@ from .decoder_heads import MAX_POS
 
 MAX_NB = 12                                     # IncBase's max_nb
 MAX_SUB_NODES = 30                              # IncTree's max_sub_nodes: the width of a cgraph row
-L_MLP, L_TOPK, L_ASSM = 2, 1, 1                 # launches per library call
+L_MLP, L_TOPK, L_ASSM, L_DRAW = 2, 1, 1, 1       # launches per library call
 
 
 def no_factory(name, synth, optimizer):
@@ -156,22 +163,70 @@ def check_beam(name, dec, beam):
                          % (name, beam, n_cls, n_icls))
 
 
-def decode(run_cls, dec, src_mol_vecs, greedy, max_decode_step, beam, graph_batch_factory, backend):
-    """the ``decode`` of ``run_cls``'s decoder -> (results, graph_batch.get_mol())"""
-    name = run_cls.NAME
-    factory = graph_batch_factory if graph_batch_factory is not None else getattr(dec, "graph_batch_factory", None)
-    if factory is None:
-        raise NotImplementedError(run_cls.NO_FACTORY)
-    if not greedy:
-        raise NotImplementedError("%s.decode: greedy=False (sampled decoding) is not part of this build; every caller in "
-                                  "the reference decodes greedily" % name)
+def _check_eval(run_cls, dec, what):
     if dec.training and any(isinstance(m, nn.Dropout) and m.p > 0 for m in dec.modules()):
-        raise NotImplementedError("%s.decode runs without dropout: call model.eval() first (reconstruct.py does)" % name)
+        raise NotImplementedError("%s.%s runs without dropout: call model.eval() first (reconstruct.py does)"
+                                  % (run_cls.NAME, what))
+
+
+def _run(run_cls, dec, src_mol_vecs, max_decode_step, beam, factory, backend, sampling):
     with torch.no_grad():
-        run = run_cls(dec, factory, src_mol_vecs, int(max_decode_step), int(beam), backend)
+        run = run_cls(dec, factory, src_mol_vecs, int(max_decode_step), int(beam), backend, sampling)
         out = run.run()
     dec.last_decode_stats, dec.last_decode_tree, dec.last_decode_trace = run.stats, run.tree, run.trace
     return out
+
+
+def _factory(run_cls, dec, graph_batch_factory):
+    factory = graph_batch_factory if graph_batch_factory is not None else getattr(dec, "graph_batch_factory", None)
+    if factory is None:
+        raise NotImplementedError(run_cls.NO_FACTORY)
+    return factory
+
+
+def decode(run_cls, dec, src_mol_vecs, greedy, max_decode_step, beam, graph_batch_factory, backend):
+    """the ``decode`` of ``run_cls``'s decoder -> (results, graph_batch.get_mol())"""
+    name = run_cls.NAME
+    factory = _factory(run_cls, dec, graph_batch_factory)
+    if not greedy:
+        raise NotImplementedError("%s.decode: greedy=False (sampled decoding) draws from a seeded stream here, not from "
+                                  "torch's global generator, and has its own entry point: call %s.decode_sampled(mols, "
+                                  "src_mol_vecs, seed=...)" % (name, name))
+    _check_eval(run_cls, dec, "decode")
+    return _run(run_cls, dec, src_mol_vecs, max_decode_step, beam, factory, backend, None)
+
+
+def decode_sampled(run_cls, dec, src_mol_vecs, seed, sample_ids, max_decode_step, beam, graph_batch_factory, backend,
+                   sampler):
+    """the ``decode_sampled`` of ``run_cls``'s decoder -> (results, graph_batch.get_mol())"""
+    factory = _factory(run_cls, dec, graph_batch_factory)
+    _check_eval(run_cls, dec, "decode_sampled")
+    sampling = Sampling(seed, sample_ids, src_mol_vecs[0].shape[0], sampler)
+    return _run(run_cls, dec, src_mol_vecs, max_decode_step, beam, factory, backend, sampling)
+
+
+def split_seed(seed):
+    """``seed`` -> (seed_lo, seed_hi), the two 32-bit halves of its low 64 bits; ``None`` takes 64 bits from torch's default
+    CPU generator (``torch.manual_seed`` makes the run reproducible)"""
+    if seed is None:
+        lo, hi = (int(v) for v in torch.randint(0, 1 << 32, (2,), dtype=torch.int64))
+        return lo, hi
+    seed = int(seed) & ((1 << 64) - 1)
+    return seed & 0xFFFFFFFF, seed >> 32
+
+
+class Sampling:
+    """What makes a decode a sampled one: the seed halves, the molecules' sample ids (the stream keys, their low 32 bits)
+    and the host ``sampler`` of the test seam (``None``: the backend draws on the device)."""
+
+    def __init__(self, seed, sample_ids, B, sampler=None):
+        self.seed_lo, self.seed_hi = split_seed(seed)
+        ids = np.arange(B) if sample_ids is None else np.asarray(
+            sample_ids.cpu() if isinstance(sample_ids, torch.Tensor) else sample_ids)
+        if ids.shape != (B,) or ids.dtype.kind not in "iu":
+            raise ValueError("decode_sampled: sample_ids must be %d integers, one per molecule" % B)
+        self.ids = (ids.astype(np.int64) & 0xFFFFFFFF).astype(np.uint32)
+        self.sampler = sampler
 
 
 class GreedyDecode:
@@ -183,8 +238,9 @@ class GreedyDecode:
     #                                 it has one (decoder.py:1037); the entry that raised is then the failed expansion
     ROOT_ATTACHMENT_POINTS = False  # the root entry of the results carries 'attachment-points'
 
-    def __init__(self, dec, factory, src_mol_vecs, max_steps, beam, backend=None):
+    def __init__(self, dec, factory, src_mol_vecs, max_steps, beam, backend=None, sampling=None):
         self.dec, self.max_steps, self.beam = dec, max_steps, beam
+        self.sampling = sampling        # None: greedy
         self.B = src_mol_vecs[0].shape[0]
         self.vocab = dec.vocab
         self.n_cls, self.n_icls = (int(v) for v in dec.vocab.size())
@@ -220,7 +276,12 @@ class GreedyDecode:
         B, vocab, gb, tree = self.B, self.vocab, self.gb, self.tree
         results = [[] for _ in range(B)]
         stack = [[] for _ in range(B)]
-        # the root (decoder.py:916-949, :313-350)
+        # the root (decoder.py:916-949, :313-350): the arg-max in both modes
+        device_draws = self.sampling is not None and self.sampling.sampler is None
+        if device_draws:
+            if not hasattr(self.be, "start_sampling"):
+                raise TypeError("%s.decode_sampled: this backend draws nothing itself: pass sampler=" % self.NAME)
+            self.be.start_sampling(self.sampling)
         k0 = min(5, self.n_icls)
         sc, rc, ri = self.be.root(k0)
         for b in range(B):
@@ -249,6 +310,8 @@ class GreedyDecode:
             if not batch_list:
                 break
             self.cur = self.be.new_counts()
+            if device_draws:
+                self.be.step = t
             self._step(t, batch_list, stack, results)
             for mol, r in zip(gb.get_mol(), results):
                 r[-1]['partial-graph'] = mol
@@ -261,6 +324,8 @@ class GreedyDecode:
         nodes = [stack[b][-1] for b in batch_list]
         aedits, edges, atoms = self._atom_inputs(nodes)
         topo = self.be.phase1(self._tree_edits(), aedits, edges, atoms, nodes, batch_list)
+        if self.sampling is not None:       # torch.bernoulli (decoder.py:374, :987): the entry records the draw
+            topo = self._topo_draws(t, batch_list, topo)
         # 2. expand or pop (:978-998, :376-394), the new messages, the cluster heads of the expanding molecules
         new_mess, expand = [], []
         for i, bid in enumerate(batch_list):
@@ -286,6 +351,11 @@ class GreedyDecode:
             return
         self.cur["expand"] = 1
         scores, cls_topk, icls_topk = top
+        order = None
+        if self.sampling is not None:       # torch.multinomial over exp(scores) (decoder.py:409-416, :1024-1033)
+            log_scores = np.asarray(scores, np.float64)
+            scores = np.exp(log_scores)
+            order = self._beam_orders(t, expanding, scores, log_scores)
         # 3. every beam entry's candidates; the entries with several scored in one launch
         plans, meta, ids, cand_atoms = [], [], [], []
         n_cand = 0
@@ -295,16 +365,16 @@ class GreedyDecode:
             results[bid][-1]['top-5-inter-cands'] = [(vocab.get_smiles(int(x)), vocab.get_ismiles(int(y)), float(s))
                                                      for x, y, s in zip(cls_topk[i], icls_topk[i], scores[i])]
             entries = []
-            for kk in range(self.beam):
+            for kk in (range(self.beam) if order is None else order[i]):
                 clab, ilab = int(cls_topk[i][kk]), int(icls_topk[i][kk])
                 try:
                     ent = self._plan(bid, clab, ilab, fa_node, fa_cluster, fa_used, meta, ids, cand_atoms, n_cand)
                 except Exception as e:      # noqa: BLE001  (met again in the assembly, if it gets there)
-                    entries.append((clab, ilab, e))
+                    entries.append((kk, clab, ilab, e))
                     break
                 if ent[4] is not None:
                     n_cand += len(ent[1])
-                entries.append((clab, ilab, ent))
+                entries.append((kk, clab, ilab, ent))
             plans.append(entries)
         assm = None
         if meta:
@@ -316,7 +386,7 @@ class GreedyDecode:
         for i, bid in enumerate(expanding):
             new_node, fa_node = stack[bid][-1], stack[bid][-2]
             success = False
-            for kk, (clab, ilab, ent) in enumerate(plans[i]):
+            for kk, clab, ilab, ent in plans[i]:     # (kk: the entry's place in the top k, whatever order it is tried in)
                 tree.set_node_feature(new_node, clab, ilab)       # (kept when the entry fails, as the reference's is)
                 if isinstance(ent, Exception):
                     if not isinstance(ent, self.CAUGHT):
@@ -344,6 +414,33 @@ class GreedyDecode:
                 if stack[bid]:
                     nth = tree.in_degree(stack[bid][-1])
                     tree.add_edge(child, stack[bid][-1], (child, stack[bid][-1], nth))
+
+    def _topo_draws(self, t, batch_list, topo):
+        """the topology draws (0.0 / 1.0) of the live molecules: the host sampler's from the probabilities, or the ones
+        the backend drew on the device and brought back with them"""
+        sampler = self.sampling.sampler
+        if sampler is None:
+            draws = self.be.topo_draws
+        else:
+            draws = sampler.topo(t, [int(self.sampling.ids[b]) for b in batch_list], np.asarray(topo, np.float64))
+        draws = np.asarray(draws, np.float64).reshape(-1)
+        if draws.shape != (len(batch_list),) or not np.isin(draws, (0.0, 1.0)).all():
+            raise RuntimeError("%s.decode_sampled: topology draws %r for %d molecules" % (self.NAME, draws, len(batch_list)))
+        return draws
+
+    def _beam_orders(self, t, expanding, probs, scores):
+        """the order in which every expanding molecule tries its beam entries: one permutation of 0..beam-1 each.  A host
+        sampler gets the probabilities, as ``torch.multinomial`` does, and the scores they are the exponentials of: a
+        masked entry's probability is 0 in any format, its score is what the device ranks it by"""
+        sampler = self.sampling.sampler
+        if sampler is None:
+            order = self.be.beam_order
+        else:
+            order = sampler.order(t, [int(self.sampling.ids[b]) for b in expanding], probs, scores)
+        order = np.asarray(order, np.int64).reshape(len(expanding), -1)
+        if not np.array_equal(np.sort(order, axis=1), np.tile(np.arange(self.beam), (len(expanding), 1))):
+            raise RuntimeError("%s.decode_sampled: a drawn beam order is no permutation: %r" % (self.NAME, order))
+        return order.tolist()
 
     def _plan(self, bid, clab, ilab, fa_node, fa_cluster, fa_used, meta, ids, cand_atoms, n_cand):
         """one beam entry: its candidates, and for several the row of the scoring launch (candidates, labels, child
@@ -425,7 +522,9 @@ class DeviceBackend:
         self.lstm = hasattr(dec.hmpn.tree_encoder.rnn, "W_f")
         ld = (H + 3) // 4 * 4
         self.node_out, self.mess_out, self.hid = (torch.empty(B, ld, device=dev) for _ in range(3))
-        self.topo = torch.empty(B, device=dev)
+        self.topo = torch.empty(2 * B, device=dev)      # (the probabilities, then in a sampled decode their draws)
+        self.sample = None                              # a sampled decode: (seed_lo, seed_hi)
+        self.step = 0
         self.cls_out, self.icls_out = torch.empty(B, self.n_cls, device=dev), torch.empty(B, self.n_icls, device=dev)
         owner = getattr(dec.vocab, "owner", None)
         if owner is None:       # a PairVocab: the motif whose mask row is 0 at the attachment
@@ -457,6 +556,30 @@ class DeviceBackend:
         self.cur["wait_s"] += time.perf_counter() - t0
         return out
 
+    def start_sampling(self, sampling):
+        """the draws of this decode are made on the device; ``root`` takes the sample ids up"""
+        self.sample = (sampling.seed_lo, sampling.seed_hi)
+        self.sample_ids = sampling.ids.view(np.int32)
+
+    def _topo_head(self, bidx, n):
+        """the topology head with its sigmoid on the ``n`` read-out rows; in a sampled decode the draws are launched
+        behind it, into the second half of the probabilities' buffer"""
+        self._mlp(self.dec.topoNN, self.node_out, self.node_out.stride(0), bidx, n, self.topo, 1, sigmoid=True)
+        if self.sample is not None:
+            _lib.check(self.lib.ggpm_sample_topo(F_._p(self.topo), bidx, F_._p(self.ids_dev), n, self.step,
+                                                 self.sample[0], self.sample[1], _ptr(self.topo, n), F_._stream()),
+                       "sample_topo")
+            self.cur["launches"] += L_DRAW
+
+    def _read_topo(self, n):
+        """the ``n`` topology probabilities copied back; in a sampled decode their draws come in the same copy
+        (``topo_draws``)"""
+        if self.sample is None:
+            return self._copy_back(self.topo[:n])
+        out = self._copy_back(self.topo[:2 * n])
+        self.topo_draws = out[n:]
+        return out[:n]
+
     def _mlp(self, seq, vecs, ld_v, bidx, M, out, ld_out, sigmoid=False):
         l1, l2 = seq[0], seq[3]
         _lib.check(self.lib.ggpm_motif_decode_mlp(
@@ -467,19 +590,31 @@ class DeviceBackend:
 
     def _heads_topk(self, vecs, ld_v, bidx, M, k, root):
         """clsNN, iclsNN and hier_topk (root: the arg-max motif and its sorted masked attachments) of M rows, launched ->
-        the device buffer ``_read_topk`` copies back"""
+        what ``_read_topk`` copies back.  In a sampled decode the order draw is launched behind ``hier_topk`` and writes behind
+        its output, so one copy brings both"""
         self._mlp(self.dec.clsNN, vecs, ld_v, bidx, M, self.cls_out, self.n_cls)
         self._mlp(self.dec.iclsNN, vecs, ld_v, bidx, M, self.icls_out, self.n_icls)
-        out = torch.empty(M, 3 * k, dtype=torch.int32, device=self.dev)
+        draw = self.sample is not None and not root     # (the drawn order [M, k] behind the [M, 3k] it is drawn from)
+        out = torch.empty(M * (4 if draw else 3) * k, dtype=torch.int32, device=self.dev)
         _lib.check(self.lib.ggpm_hier_topk(F_._p(self.cls_out), self.n_cls, self.n_cls, F_._p(self.icls_out), self.n_icls,
                                            self.n_icls, F_._p(self.owner), M, k, int(root), F_._p(out), F_._stream()),
                    "hier_topk")
         self.cur["launches"] += L_TOPK
-        return out
+        if draw:
+            _lib.check(self.lib.ggpm_sample_beam_order(F_._p(out), bidx, F_._p(self.ids_dev), M, k, self.step,
+                                                       self.sample[0], self.sample[1], _ptr(out, M * 3 * k),
+                                                       F_._stream()), "sample_beam_order")
+            self.cur["launches"] += L_DRAW
+        return out, M, draw
 
-    def _read_topk(self, out, k):
-        """-> (scores [M, k], motifs [M, k], attachments [M, k])"""
+    def _read_topk(self, launched, k):
+        """``_heads_topk``'s buffer, copied back -> (scores [M, k], motifs [M, k], attachments [M, k]); the drawn order that
+        came with them is ``beam_order``"""
+        out, M, draw = launched
         out = self._copy_back(out)
+        if draw:
+            self.beam_order = out[3 * k * M:].reshape(M, k)
+        out = out[:3 * k * M].reshape(M, 3 * k)
         return out[:, :k].view(np.float32), out[:, k:2 * k], out[:, 2 * k:]
 
     def _root_state(self):
@@ -493,7 +628,10 @@ class DeviceBackend:
             init = self.src_root
         else:
             init = F_.linear([self.src_root], [self.L], dec.W_root.weight, dec.W_root.bias)[:, :H]
-        buf, offs = self._upload([np.arange(B)])
+        parts = [np.arange(B)] + ([] if self.sample is None else [self.sample_ids])
+        buf, offs = self._upload(parts)
+        if self.sample is not None:
+            self.ids_dev = buf[offs[1]:offs[1] + B]         # resident for the decode
         out = self._read_topk(self._heads_topk(init, F_._ld(init), _ptr(buf, offs[0]), B, k0, root=True), k0)
         self._root_state().copy_(init[:, :H])
         return out

@@ -22,7 +22,8 @@ and one copy back:
      messages; inter read-outs and tree inputs; tree messages.  clsNN [2], iclsNN [2], ``hier_topk`` [1].  (No new message
      -- every live molecule popped its root: nothing is run.)
   3. the candidates' rows, labels and atoms; all scored in one launch [1] (the atom rows are those phase 1 wrote).
-``LAUNCHES`` derives the counts.
+``LAUNCHES`` derives the counts.  A sampled decode (``decode_sampled``) adds the topology draw [1] to phase 1 and the order
+draw [1] to phase 2, into the buffers those phases copy back anyway.
 """
 from __future__ import annotations
 
@@ -88,6 +89,14 @@ class AtomTables:
 def decode(dec, mols, src_mol_vecs, greedy=True, max_decode_step=100, beam=5, graph_batch_factory=None, backend=None):
     """``HierMPNDecoder.decode`` -> (results, graph_batch.get_mol())"""
     return G.decode(_Decode, dec, src_mol_vecs, greedy, max_decode_step, beam, graph_batch_factory, backend)
+
+
+def decode_sampled(dec, mols, src_mol_vecs, seed=None, sample_ids=None, max_decode_step=100, beam=5,
+                   graph_batch_factory=None, backend=None, sampler=None):
+    """``HierMPNDecoder.decode_sampled``: the reference's ``decode(greedy=False)`` on a seeded stream ->
+    (results, graph_batch.get_mol())"""
+    return G.decode_sampled(_Decode, dec, src_mol_vecs, seed, sample_ids, max_decode_step, beam, graph_batch_factory,
+                            backend, sampler)
 
 
 def check_limits(dec, beam, B):
@@ -184,11 +193,10 @@ class HipBackend(G.DeviceBackend):
         t1 = self._mark()
         n = len(nodes)
         self._tree_step(buf, 0, 0, offs[11], n, 0, 0)
-        self._mlp(self.dec.topoNN, self.node_out, self.node_out.stride(0), _ptr(buf, offs[12]), n, self.topo, 1,
-                  sigmoid=True)
+        self._topo_head(_ptr(buf, offs[12]), n)
         if t0 is not None:
             self.spans += [("atom", t0, t1), ("rest", t1, self._mark())]
-        return self._copy_back(self.topo[:n])
+        return self._read_topo(n)
 
     def phase2(self, tedits, nodes, mess, expanding, k):
         """the new messages on the inter and tree levels (none: nothing is run) -> (scores, motifs, attachments) of the

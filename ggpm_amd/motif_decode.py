@@ -10,7 +10,8 @@ does; nothing else is caught.
 Device, resident for the whole decode: the message states (h, and c for LSTM) and the tree's tables (motif ids, fmess,
 agraph, bgraph).  Every phase is one upload, its launches and one copy back: the tree step with the read-outs and the
 topology head [2 + 2]; the tree step with the new messages [2], then for the expanding molecules the cluster heads and
-``hier_topk`` [2 + 2 + 1]; the attachment scores [1].  At most 12 launches per step.
+``hier_topk`` [2 + 2 + 1]; the attachment scores [1].  At most 12 launches per step; a sampled decode
+(``decode_sampled``) adds the topology draw [1] behind the sigmoid head and the order draw [1] behind ``hier_topk``.
 """
 from __future__ import annotations
 
@@ -32,6 +33,14 @@ NO_FACTORY = G.no_factory("MotifDecoder", "SynthGraphBatch", "PropertyVAEOptimiz
 def decode(dec, mols, src_mol_vecs, greedy=True, max_decode_step=100, beam=5, graph_batch_factory=None, backend=None):
     """``MotifDecoder.decode`` -> (results, graph_batch.get_mol())"""
     return G.decode(_Decode, dec, src_mol_vecs, greedy, max_decode_step, beam, graph_batch_factory, backend)
+
+
+def decode_sampled(dec, mols, src_mol_vecs, seed=None, sample_ids=None, max_decode_step=100, beam=5,
+                   graph_batch_factory=None, backend=None, sampler=None):
+    """``MotifDecoder.decode_sampled``: the reference's ``decode(greedy=False)`` on a seeded stream ->
+    (results, graph_batch.get_mol())"""
+    return G.decode_sampled(_Decode, dec, src_mol_vecs, seed, sample_ids, max_decode_step, beam, graph_batch_factory,
+                            backend, sampler)
 
 
 class HipBackend(G.DeviceBackend):
@@ -78,9 +87,8 @@ class HipBackend(G.DeviceBackend):
         n = len(nodes)
         buf, n_ne, n_te, offs = self._upload_edits(tedits, [nodes, bidx])
         self._tree_step(buf, n_ne, n_te, nodes_off=offs[0], n_read=n)
-        self._mlp(self.dec.topoNN, self.node_out, self.node_out.stride(0), _ptr(buf, offs[1]), n, self.topo, 1,
-                  sigmoid=True)
-        return self._copy_back(self.topo[:n])
+        self._topo_head(_ptr(buf, offs[1]), n)
+        return self._read_topo(n)
 
     def phase2(self, tedits, nodes, mess, expanding, k):
         """the new messages (none: the upload and the tree step are still issued, for the edits) -> (scores, motifs,

@@ -139,6 +139,16 @@ class MotifDecoder(ScoreHeads):
         from .motif_decode import decode
         return decode(self, mols, src_mol_vecs, greedy, max_decode_step, beam, graph_batch_factory)
 
+    def decode_sampled(self, mols, src_mol_vecs, seed=None, sample_ids=None, max_decode_step=100, beam=5,
+                       graph_batch_factory=None):
+        """The reference's ``decode(..., greedy=False)`` (ggpm/decoder.py:984-987, 1024-1033) -> what ``decode`` returns.  The topology
+        decision is a Bernoulli draw and the beam entries are tried in an order drawn without replacement; the draws come
+        from a counter-based stream keyed by ``seed`` (an int, 64 bits used; ``None`` takes them from torch's default CPU
+        generator) and by ``sample_ids`` (one int per molecule, default ``arange``), so a molecule's draws do not depend
+        on its batch (*Sampled decoding and the prior*)."""
+        from .motif_decode import decode_sampled
+        return decode_sampled(self, mols, src_mol_vecs, seed, sample_ids, max_decode_step, beam, graph_batch_factory)
+
     # ------------------------------------------------------------------ forward
     def forward(self, mols, src_mol_vecs, graphs, tensors, orders, avg_loss=False, schedule: Optional[DecodeSchedule] = None):
         if avg_loss:

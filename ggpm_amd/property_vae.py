@@ -240,6 +240,12 @@ class HierPropertyVAE(nn.Module):
     def rsample(self, z_vecs, W_mean, W_var, perturb=True):
         return rsample(z_vecs, W_mean, W_var, perturb)
 
+    def sample(self, batch_size, greedy=True, seed=None, max_decode_step=150, beam=5, graph_batch_factory=None):
+        """New molecules from the prior (what reference ggpm/property_vae.py:35-37 intends): seeded standard-normal latents
+        drawn on the device, then ``decode`` or, with ``greedy=False``, ``decode_sampled`` at the same seed ->
+        (results, molecules)."""
+        return _sample(self, batch_size, greedy, seed, max_decode_step, beam, graph_batch_factory)
+
     def reconstruct(self, batch, args=None):
         """reference ggpm/property_vae.py:39-45: the no-grad encoder, the mean latent, greedy decode of 150 steps ->
         (results, molecules).  The graph batch: ``args.graph_batch_factory``, else the decoder's."""
@@ -390,6 +396,12 @@ class HierPropOptVAE(_ClipNegativeLoss, nn.Module):
         ``batch`` is a reference batch (mols, graphs, tensors, orders, homos, lumos).  -> (homo [B], lumo [B])."""
         return _predict_properties(self, batch)
 
+    def sample(self, batch_size, greedy=True, seed=None, max_decode_step=150, beam=5, graph_batch_factory=None):
+        """New molecules from the prior (what reference ggpm/property_vae.py:35-37 intends): seeded standard-normal latents
+        drawn on the device, then ``decode`` or, with ``greedy=False``, ``decode_sampled`` at the same seed ->
+        (results, molecules)."""
+        return _sample(self, batch_size, greedy, seed, max_decode_step, beam, graph_batch_factory)
+
     def reconstruct(self, batch, args=None):
         """reference ggpm/property_vae.py:169-188: the no-grad encoder, the mean latent, the property heads on it, greedy
         decode of 150 steps -> ((homo [B], lumo [B]), (results, molecules)).  The graph batch: ``args.graph_batch_factory``,
@@ -450,6 +462,28 @@ def _predict_properties(model, batch):
         return model.property_optim.predict(homo_vecs=z[:, :half], lumo_vecs=z[:, half:])
 
 
+def _sample(model, batch_size, greedy, seed, max_decode_step, beam, graph_batch_factory):
+    """``sample`` of the four VAEs: [batch_size, decoder.latent_size] latents -- the width ``reconstruct`` hands to
+    ``decode`` -- from ``functional.sample_normal`` (sample ids ``arange``), used as all three source vectors."""
+    from .greedy_decode import split_seed
+    dec = model.decoder
+    factory = graph_batch_factory
+    if factory is None:
+        factory = _graph_batch_factory(model, getattr(model, "args", None))
+    if dec.training and any(isinstance(m, nn.Dropout) and m.p > 0 for m in dec.modules()):
+        raise NotImplementedError("%s.sample runs without dropout: call model.eval() first" % type(model).__name__)
+    if int(batch_size) < 1:
+        raise ValueError("%s.sample: batch_size %d" % (type(model).__name__, batch_size))
+    lo, hi = split_seed(seed)
+    with torch.no_grad():
+        z = F_.sample_normal(int(batch_size), dec.latent_size, lo, hi, device=next(dec.parameters()).device)
+        if greedy:
+            return dec.decode(None, (z, z, z), greedy=True, max_decode_step=max_decode_step, beam=beam,
+                              graph_batch_factory=factory)
+        return dec.decode_sampled(None, (z, z, z), seed=lo | hi << 32, max_decode_step=max_decode_step, beam=beam,
+                                  graph_batch_factory=factory)
+
+
 def _graph_batch_factory(model, args):
     """decode's graph batch for reconstruct: ``args.graph_batch_factory``, else the decoder's; neither raises before the
     batch is touched."""
@@ -501,6 +535,12 @@ class PropertyVAE(nn.Module):
 
     def rsample(self, z_vecs, perturb=True):
         return rsample(z_vecs, self.R_mean, self.R_var, perturb)
+
+    def sample(self, batch_size, greedy=True, seed=None, max_decode_step=150, beam=5, graph_batch_factory=None):
+        """New molecules from the prior (what reference ggpm/property_vae.py:35-37 intends): seeded standard-normal latents
+        drawn on the device, then ``decode`` or, with ``greedy=False``, ``decode_sampled`` at the same seed ->
+        (results, molecules)."""
+        return _sample(self, batch_size, greedy, seed, max_decode_step, beam, graph_batch_factory)
 
     def reconstruct(self, batch, args=None):
         """reference ggpm/property_vae.py:101-109: the no-grad encoder, the mean latent, greedy decode of 150 steps ->
@@ -571,6 +611,12 @@ class PropOptVAE(_ClipNegativeLoss, nn.Module):
     def predict_properties(self, batch):
         """As HierPropOptVAE.predict_properties, on MotifEncoder's latent: -> (homo [B], lumo [B])."""
         return _predict_properties(self, batch)
+
+    def sample(self, batch_size, greedy=True, seed=None, max_decode_step=150, beam=5, graph_batch_factory=None):
+        """New molecules from the prior (what reference ggpm/property_vae.py:35-37 intends): seeded standard-normal latents
+        drawn on the device, then ``decode`` or, with ``greedy=False``, ``decode_sampled`` at the same seed ->
+        (results, molecules)."""
+        return _sample(self, batch_size, greedy, seed, max_decode_step, beam, graph_batch_factory)
 
     def reconstruct(self, batch, args=None):
         """reference ggpm/property_vae.py:299-318: the no-grad encoder, the mean latent, the property heads on it, greedy

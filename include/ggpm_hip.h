@@ -728,6 +728,32 @@ int ggpm_hier_decode_assm_score(const int* dims, void* const* state, const float
                                 const float* W1, int ldw, const float* b1, const float* Wa, const float* ba, int L,
                                 const float* z, int ldz, int stamp, float* score, ggpm_stream_t stream);
 
+/* Seeded draws of the sampled decode (decode_sampled; the reference's greedy=False, ggpm/decoder.py:371-374, 409-416) and of
+ * the prior (HierPropertyVAE.sample, ggpm/property_vae.py:35-37); csrc/sample.hip.  Stateless and counter-based:
+ *     base = mix(mix(id * 0x9E3779B1 + seed_lo) ^ (seed_hi + site * 0x7F4A7C15))
+ *     m(site, id, step, slot) = mix(base + (step * 64 + slot) * 0x9E3779B1) >> 8          (24 bits)
+ * in 32-bit arithmetic, mix = the murmur3 32-bit finaliser of ggpm_dropout().  `ids` [B] holds the sample id (the stream
+ * key) of every molecule, `bidx` the molecule of every row; nothing else about the launch enters a draw.
+ * ggpm_sample_topo (one launch): draw[i] = m(TOPO, ids[bidx[i]], step, 0) * 2^-24 < p[i] ? 1.f : 0.f, i < n.
+ * ggpm_sample_beam_order (one launch, one wave per row): topk is ggpm_hier_topk's out [M x 3k]; with key_q = score_q -
+ * log(e_q), e_q = max(-log((m(BEAM, ids[bidx[r]], step, q) + 1) * 2^-24), 2^-24), order [M x k] lists the entries q by
+ * descending key, ties to the lower q: a draw without replacement with probabilities proportional to exp(score_q).
+ * 1 <= k <= GGPM_SAMPLE_MAX_K.
+ * ggpm_sample_normal (one launch): out[r, c] = sqrt(-2 log((m0 + 1) * 2^-24)) * cos(2 pi m1 * 2^-24) with m0 / m1 =
+ * m(PRIOR, ids[r], c, 0 / 1), for c < cols; columns cols..ld of a row are left alone.  rows * cols < 2^31.
+ * A null pointer, n / M / rows / cols <= 0, step < 0, ld < cols or k outside its range returns GGPM_ERR_ARG; nothing is
+ * launched then. */
+#define GGPM_SITE_SAMPLE_TOPO 256   /* sites no dropout mask uses */
+#define GGPM_SITE_SAMPLE_BEAM 257
+#define GGPM_SITE_SAMPLE_PRIOR 258
+#define GGPM_SAMPLE_MAX_K 16
+int ggpm_sample_topo(const float* p, const int32_t* bidx, const int32_t* ids, int n, int step, unsigned int seed_lo,
+                     unsigned int seed_hi, float* draw, ggpm_stream_t stream);
+int ggpm_sample_beam_order(const int32_t* topk, const int32_t* bidx, const int32_t* ids, int M, int k, int step,
+                           unsigned int seed_lo, unsigned int seed_hi, int32_t* order, ggpm_stream_t stream);
+int ggpm_sample_normal(float* out, int rows, int cols, int ld, const int32_t* ids, unsigned int seed_lo,
+                       unsigned int seed_hi, ggpm_stream_t stream);
+
 /* ------------------------------------------------------------------ whole-encoder drivers
  * HierMPNEncoder.forward (ggpm/encoder.py:140-157, with embed_graph/inter/tree/root :96-138) and its backward as ONE
  * call each: the same kernels the op-by-op host path issues, sequenced from C++ (GRU or LSTM message function).
