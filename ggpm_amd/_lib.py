@@ -101,6 +101,11 @@ SIGNATURES = {
     "ggpm_sample_topo": (I, [P, P, P, I, I, ctypes.c_uint, ctypes.c_uint, P, P]),
     "ggpm_sample_beam_order": (I, [P, P, P, I, I, I, ctypes.c_uint, ctypes.c_uint, P, P]),
     "ggpm_sample_normal": (I, [P, I, I, I, P, ctypes.c_uint, ctypes.c_uint, P]),
+    "ggpm_sample_latent_normal": (I, [P, I, I, I, P, ctypes.c_uint, ctypes.c_uint, P]),
+    # per-molecule likelihood terms (csrc/mol_loss.hip): terms: ggpm_mol_loss_term[4]
+    "ggpm_mol_loss_parts": (I, [P, I, P, P]),
+    "ggpm_latent_terms": (I, [P, P, P, I, I, I, P, P, P, P]),
+    "ggpm_iwae_finish": (I, [P, P, P, I, I, P, P, P]),
     "ggpm_dropout": (I, [P, I, I, I, ctypes.c_float, ctypes.c_uint, ctypes.c_uint, I, P]),
     # property heads / latent search (csrc/property.hip): heads are ggpm_prop_head*, grads ggpm_prop_head_grads*
     "ggpm_property_heads_workspace_bytes": (c_size_t, [I, I, P, P]),

@@ -1,0 +1,135 @@
+// Per-molecule likelihood terms ("Per-molecule ELBO and the importance-weighted bound"; include/ggpm_hip.h):
+//   ggpm_mol_loss_parts : the row losses the loss kernels leave in `work`, summed per (molecule, term)
+//   ggpm_latent_terms   : z_k = mean + exp(lv / 2) eps_k, the analytic KL, log p(z_k) - log q(z_k | x)
+//   ggpm_iwae_finish    : ELBO and the K-sample importance-weighted bound (max-subtracted logsumexp over k)
+// One wave owns one output element and walks its addends in a fixed order: no atomics, bitwise reproducible.  Sums are
+// carried in fp64 and rounded to fp32 once, where they are stored.
+#include "common.h"
+
+namespace {
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+__device__ __forceinline__ double wave_max_f64(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+    return v;
+}
+
+struct LossTerms {
+    const float* row_loss[GGPM_MOL_LOSS_TERMS];
+    const int32_t* mol[GGPM_MOL_LOSS_TERMS];
+    int stride[GGPM_MOL_LOSS_TERMS];
+    int n_rows[GGPM_MOL_LOSS_TERMS];
+};
+
+// block = (molecule b, term t): the rows of a molecule are scattered (predictions are step-major), so the wave strides all
+// rows of the term and keeps its own.  A row whose molecule is outside [0, B) belongs to no block.
+__global__ void __launch_bounds__(64) mol_loss_parts_k(LossTerms a, float* __restrict__ parts) {
+    const int b = blockIdx.x / GGPM_MOL_LOSS_TERMS, t = blockIdx.x % GGPM_MOL_LOSS_TERMS;
+    const int lane = threadIdx.x;
+    const float* __restrict__ v = a.row_loss[t];
+    const int32_t* __restrict__ mol = a.mol[t];
+    const int n = a.n_rows[t], st = a.stride[t];
+    double acc = 0.0;
+    for (int r = lane; r < n; r += 64)
+        if (mol[r] == b) acc += (double)v[(size_t)r * st];
+    acc = wave_sum_f64(acc);
+    if (lane == 0) parts[blockIdx.x] = (float)acc;
+}
+
+// block = (sample k, molecule b).  z and the KL addends are formed in fp32 with rsample's own expressions (csrc/losses.hip:
+// eps = 0 gives mean itself, and kl sums the values the training KL sums); logpq reads that stored z in fp64.
+__global__ void __launch_bounds__(64) latent_terms_k(const float* __restrict__ mean, const float* __restrict__ pv,
+                                                     const float* __restrict__ eps, int B, int L, float* __restrict__ z,
+                                                     float* __restrict__ kl, float* __restrict__ logpq) {
+    const int k = blockIdx.x / B, b = blockIdx.x - k * B;
+    const int lane = threadIdx.x;
+    const float* m = mean + (size_t)b * L;
+    const float* p = pv + (size_t)b * L;
+    const float* e = eps + (size_t)blockIdx.x * L;
+    float* zo = z + (size_t)blockIdx.x * L;
+    double s_kl = 0.0, s_pq = 0.0;
+    for (int j = lane; j < L; j += 64) {
+        const float mj = m[j], lv = -fabsf(p[j]), ej = e[j];
+        const float zj = mj + expf(0.5f * lv) * ej;
+        zo[j] = zj;
+        s_pq += -0.5 * (double)zj * (double)zj + 0.5 * ((double)ej * (double)ej + (double)lv);
+        s_kl += (double)(1.f + lv - mj * mj - expf(lv));      // rsample's fp32 addend: the KL of training adds the same values
+    }
+    s_pq = wave_sum_f64(s_pq);
+    s_kl = wave_sum_f64(s_kl);
+    if (lane == 0) {
+        logpq[blockIdx.x] = (float)s_pq;
+        if (k == 0) kl[b] = (float)(-0.5 * s_kl);
+    }
+}
+
+// block = molecule b; the lanes stride the samples.
+__global__ void __launch_bounds__(64) iwae_finish_k(const float* __restrict__ parts, const float* __restrict__ logpq,
+                                                    const float* __restrict__ kl, int K, int B, float* __restrict__ elbo,
+                                                    float* __restrict__ iwae) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    double s_nll = 0.0, mx = -INFINITY;
+    for (int k = lane; k < K; k += 64) {
+        const float* q = parts + ((size_t)k * B + b) * GGPM_MOL_LOSS_TERMS;
+        const double nll = ((double)q[0] + (double)q[1]) + ((double)q[2] + (double)q[3]);
+        s_nll += nll;
+        mx = fmax(mx, (double)logpq[(size_t)k * B + b] - nll);
+    }
+    s_nll = wave_sum_f64(s_nll);
+    mx = wave_max_f64(mx);
+    double se = 0.0;
+    for (int k = lane; k < K; k += 64) {
+        const float* q = parts + ((size_t)k * B + b) * GGPM_MOL_LOSS_TERMS;
+        const double nll = ((double)q[0] + (double)q[1]) + ((double)q[2] + (double)q[3]);
+        se += exp((double)logpq[(size_t)k * B + b] - nll - mx);
+    }
+    se = wave_sum_f64(se);
+    if (lane == 0) {
+        elbo[b] = (float)(-s_nll / (double)K - (double)kl[b]);
+        iwae[b] = (float)(mx + log(se) - log((double)K));
+    }
+}
+
+}  // namespace
+
+extern "C" int ggpm_mol_loss_parts(const ggpm_mol_loss_term* terms, int B, float* parts, ggpm_stream_t stream) {
+    GGPM_CLEAR_STALE_ERROR();
+    if (!terms || !parts || B <= 0 || (size_t)B * GGPM_MOL_LOSS_TERMS >= ((size_t)1 << 31)) return GGPM_ERR_ARG;
+    LossTerms a;
+    for (int t = 0; t < GGPM_MOL_LOSS_TERMS; ++t) {
+        const ggpm_mol_loss_term& s = terms[t];
+        if (s.n_rows < 0 || (s.n_rows > 0 && (!s.row_loss || !s.mol || s.stride < 1))) return GGPM_ERR_ARG;
+        a.row_loss[t] = s.row_loss;
+        a.mol[t] = s.mol;
+        a.stride[t] = s.stride;
+        a.n_rows[t] = s.n_rows;
+    }
+    mol_loss_parts_k<<<B * GGPM_MOL_LOSS_TERMS, 64, 0, (hipStream_t)stream>>>(a, parts);
+    GGPM_CHECK_LAUNCH();
+    return GGPM_OK;
+}
+
+extern "C" int ggpm_latent_terms(const float* mean, const float* pre_var, const float* eps, int K, int B, int L, float* z,
+                                 float* kl, float* logpq, ggpm_stream_t stream) {
+    GGPM_CLEAR_STALE_ERROR();
+    if (!mean || !pre_var || !eps || !z || !kl || !logpq || K < 1 || K > GGPM_LIKELIHOOD_MAX_K || B <= 0 || L <= 0 ||
+        (size_t)K * (size_t)B >= ((size_t)1 << 31))
+        return GGPM_ERR_ARG;
+    latent_terms_k<<<K * B, 64, 0, (hipStream_t)stream>>>(mean, pre_var, eps, B, L, z, kl, logpq);
+    GGPM_CHECK_LAUNCH();
+    return GGPM_OK;
+}
+
+extern "C" int ggpm_iwae_finish(const float* parts, const float* logpq, const float* kl, int K, int B, float* elbo,
+                                float* iwae, ggpm_stream_t stream) {
+    GGPM_CLEAR_STALE_ERROR();
+    if (!parts || !logpq || !kl || !elbo || !iwae || K < 1 || K > GGPM_LIKELIHOOD_MAX_K || B <= 0) return GGPM_ERR_ARG;
+    iwae_finish_k<<<B, 64, 0, (hipStream_t)stream>>>(parts, logpq, kl, K, B, elbo, iwae);
+    GGPM_CHECK_LAUNCH();
+    return GGPM_OK;
+}

@@ -54,17 +54,33 @@ __global__ void __launch_bounds__(64) sample_order_k(const int32_t* __restrict__
 }
 
 // Box-Muller from two words per element: sqrt(-2 log u1) cos(2 pi u2), u1 = (m0 + 1) 2^-24 in (0, 1], u2 = m1 2^-24
+__device__ __forceinline__ float sample_gauss(unsigned int seed_lo, unsigned int seed_hi, unsigned int site,
+                                              unsigned int id, unsigned int counter) {
+    const unsigned int m0 = sample_m(seed_lo, seed_hi, site, id, counter, 0u);
+    const unsigned int m1 = sample_m(seed_lo, seed_hi, site, id, counter, 1u);
+    const float u1 = (float)(m0 + 1u) * TWO_M24, u2 = (float)m1 * TWO_M24;
+    return sqrtf(-2.f * logf(u1)) * cospif(2.f * u2);
+}
+
 __global__ void __launch_bounds__(256) sample_normal_k(float* __restrict__ out, int rows, int cols, int ld,
                                                        const int32_t* __restrict__ ids, unsigned int seed_lo,
                                                        unsigned int seed_hi) {
     const int total = rows * cols;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
         const int r = i / cols, c = i - r * cols;
-        const unsigned int id = (unsigned int)ids[r];
-        const unsigned int m0 = sample_m(seed_lo, seed_hi, GGPM_SITE_SAMPLE_PRIOR, id, (unsigned int)c, 0u);
-        const unsigned int m1 = sample_m(seed_lo, seed_hi, GGPM_SITE_SAMPLE_PRIOR, id, (unsigned int)c, 1u);
-        const float u1 = (float)(m0 + 1u) * TWO_M24, u2 = (float)m1 * TWO_M24;
-        out[(size_t)r * ld + c] = sqrtf(-2.f * logf(u1)) * cospif(2.f * u2);
+        out[(size_t)r * ld + c] = sample_gauss(seed_lo, seed_hi, GGPM_SITE_SAMPLE_PRIOR, (unsigned int)ids[r], (unsigned int)c);
+    }
+}
+
+// eps[k, b, c] of the likelihood estimate: site LATENT, the molecule's id, counter k * L + c
+__global__ void __launch_bounds__(256) sample_latent_normal_k(float* __restrict__ out, int K, int B, int L,
+                                                              const int32_t* __restrict__ ids, unsigned int seed_lo,
+                                                              unsigned int seed_hi) {
+    const int total = K * B * L;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const int c = i % L, kb = i / L;
+        const int b = kb % B, k = kb / B;
+        out[i] = sample_gauss(seed_lo, seed_hi, GGPM_SITE_SAMPLE_LATENT, (unsigned int)ids[b], (unsigned int)(k * L + c));
     }
 }
 
@@ -99,6 +115,17 @@ extern "C" int ggpm_sample_normal(float* out, int rows, int cols, int ld, const 
     if (!out || !ids || rows <= 0 || cols <= 0 || ld < cols || (size_t)rows * (size_t)cols >= ((size_t)1 << 31))
         return GGPM_ERR_ARG;
     sample_normal_k<<<stride_grid(rows * cols), 256, 0, (hipStream_t)stream>>>(out, rows, cols, ld, ids, seed_lo, seed_hi);
+    GGPM_CHECK_LAUNCH();
+    return GGPM_OK;
+}
+
+extern "C" int ggpm_sample_latent_normal(float* out, int K, int B, int L, const int32_t* ids, unsigned int seed_lo,
+                                         unsigned int seed_hi, ggpm_stream_t stream) {
+    GGPM_CLEAR_STALE_ERROR();
+    if (!out || !ids || K < 1 || K > GGPM_LIKELIHOOD_MAX_K || B <= 0 || L <= 0 ||
+        (size_t)K * (size_t)L >= ((size_t)1 << 26) || (size_t)K * (size_t)B * (size_t)L >= ((size_t)1 << 31))
+        return GGPM_ERR_ARG;
+    sample_latent_normal_k<<<stride_grid(K * B * L), 256, 0, (hipStream_t)stream>>>(out, K, B, L, ids, seed_lo, seed_hi);
     GGPM_CHECK_LAUNCH();
     return GGPM_OK;
 }

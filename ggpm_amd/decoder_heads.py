@@ -84,6 +84,31 @@ def bce_with_logits_sum(scores: torch.Tensor, labels: torch.Tensor) -> torch.Ten
     return _BCELogits.apply(scores, labels)
 
 
+def bce_rows(scores: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    """The addends of ``bce_with_logits_sum``, one per row: what ggpm_bce_logits leaves in its ``work`` buffer.  Forward only."""
+    F_._need_gpu(scores, labels)
+    x, y = scores.detach().contiguous(), labels.to(torch.float32).contiguous()
+    loss, rows = torch.empty(1, dtype=torch.float32, device=x.device), torch.empty_like(x)
+    _lib.check(_lib.load().ggpm_bce_logits(F_._p(x), F_._p(y), x.numel(), F_._p(loss), None, F_._p(rows), F_._stream()),
+               "bce_logits")
+    return rows
+
+
+def cross_entropy_rows(scores: torch.Tensor, labels: torch.Tensor, mask: torch.Tensor = None,
+                       mask_row: torch.Tensor = None) -> torch.Tensor:
+    """The addends of ``cross_entropy_sum``, one per row: what ggpm_softmax_ce leaves in its ``work`` buffer.  Forward only."""
+    F_._need_gpu(scores, labels)
+    M, N = scores.shape
+    s = scores.detach()
+    loss, rows = torch.empty(1, dtype=torch.float32, device=s.device), torch.empty(M, dtype=torch.float32, device=s.device)
+    lab = labels.to(torch.int32).contiguous()
+    mrow = mask_row.to(torch.int32).contiguous() if mask_row is not None else None
+    _lib.check(_lib.load().ggpm_softmax_ce(F_._p(s), F_._ld(s), M, N, F_._p(mask), 0 if mask is None else F_._ld(mask),
+                                           F_._p(mrow), F_._p(lab), F_._p(loss), None, 0, None, F_._p(rows), F_._stream()),
+               "softmax_ce")
+    return rows
+
+
 def _mlp(seq: nn.Sequential, parts, widths):
     """Sequential(Linear, ReLU, Dropout, Linear) on the concatenation of `parts` (never materialised)."""
     l1, l2 = seq[0], seq[3]

@@ -57,6 +57,90 @@ def sample_normal(rows: int, cols: int, seed_lo: int, seed_hi: int, ids=None, de
     return out[:, :cols]
 
 
+LIKELIHOOD_MAX_K = 1024         # include/ggpm_hip.h GGPM_LIKELIHOOD_MAX_K
+
+
+def sample_latent_normal(K: int, B: int, L: int, seed_lo: int, seed_hi: int, ids=None, device=None):
+    """[K, B, L] standard normals of the seeded stream (csrc/sample.hip, site LATENT): element (k, b, c) is keyed by the
+    seed, ``ids[b]`` (default ``arange``) and the counter ``k * L + c`` -- not by B, K or the molecule's place in the batch"""
+    dev = torch.device("cuda") if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("ggpm_amd: sample_latent_normal runs on the MI355X (got device %s); there is no CPU path" % dev)
+    ids = torch.arange(B, dtype=torch.int32) if ids is None else torch.as_tensor(ids).to(torch.int64).bitwise_and(
+        0xFFFFFFFF).to(torch.int32)
+    if ids.shape != (B,):
+        raise ValueError("sample_latent_normal: %d ids for %d molecules" % (ids.numel(), B))
+    out = torch.empty(K, B, L, dtype=torch.float32, device=dev)
+    ids = ids.to(dev)
+    _lib.check(_lib.load().ggpm_sample_latent_normal(_p(out), K, B, L, _p(ids), seed_lo & 0xFFFFFFFF, seed_hi & 0xFFFFFFFF,
+                                                     _stream()), "sample_latent_normal")
+    return out
+
+
+class MolLossTerm(ctypes.Structure):
+    """ggpm_mol_loss_term (include/ggpm_hip.h)"""
+    _fields_ = [("row_loss", ctypes.c_void_p), ("mol", ctypes.c_void_p), ("stride", ctypes.c_int), ("n_rows", ctypes.c_int)]
+
+
+def mol_loss_parts(terms, B: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``terms``: four entries ``(row_loss, mol, n_rows[, stride])`` or None (an absent term) -> parts [B, 4]: per molecule
+    the sum of the row losses of each term (csrc/mol_loss.hip).  ``row_loss`` fp32, ``mol`` int32, both on the device."""
+    if len(terms) != 4:
+        raise ValueError("mol_loss_parts: four terms (topology, motif class, attachment class, attachment), got %d" % len(terms))
+    arr = (MolLossTerm * 4)()
+    dev = None
+    for t, term in enumerate(terms):
+        if term is None or term[2] == 0:
+            continue
+        v, mol, n = term[0], term[1], int(term[2])
+        _need_gpu(v, mol)
+        stride = int(term[3]) if len(term) > 3 else 1
+        if v.dtype != torch.float32 or mol.dtype != torch.int32 or not mol.is_contiguous() or not v.is_contiguous():
+            raise ValueError("mol_loss_parts: term %d needs contiguous fp32 row losses and a contiguous int32 row -> molecule "
+                             "table" % t)
+        if stride < 1 or mol.numel() < n or v.numel() < (n - 1) * stride + 1:
+            raise ValueError("mol_loss_parts: term %d lists %d rows %d floats apart but holds %d losses and %d molecules"
+                             % (t, n, stride, v.numel(), mol.numel()))
+        arr[t] = MolLossTerm(v.data_ptr(), mol.data_ptr(), stride, n)
+        dev = v.device
+    if out is None:
+        if dev is None:
+            raise ValueError("mol_loss_parts: every term is absent and no output tensor names the device")
+        out = torch.empty(B, 4, dtype=torch.float32, device=dev)
+    elif out.shape != (B, 4) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("mol_loss_parts: out must be a contiguous fp32 [B, 4] tensor")
+    _need_gpu(out)
+    _lib.check(_lib.load().ggpm_mol_loss_parts(ctypes.byref(arr), B, _p(out), _stream()), "mol_loss_parts")
+    return out
+
+
+def latent_terms(mean: torch.Tensor, pre_var: torch.Tensor, eps: torch.Tensor):
+    """mean, pre_var [B, L], eps [K, B, L] -> (z [K, B, L], kl [B], logpq [K, B]) (csrc/mol_loss.hip)"""
+    _need_gpu(mean, pre_var, eps)
+    K, B, L = eps.shape
+    mean, pre_var, eps = mean.contiguous(), pre_var.contiguous(), eps.contiguous()
+    if mean.shape != (B, L) or pre_var.shape != (B, L):
+        raise ValueError("latent_terms: mean %s / pre_var %s for eps %s" % (tuple(mean.shape), tuple(pre_var.shape), (K, B, L)))
+    f32 = dict(dtype=torch.float32, device=mean.device)
+    z, kl, logpq = torch.empty(K, B, L, **f32), torch.empty(B, **f32), torch.empty(K, B, **f32)
+    _lib.check(_lib.load().ggpm_latent_terms(_p(mean), _p(pre_var), _p(eps), K, B, L, _p(z), _p(kl), _p(logpq), _stream()),
+               "latent_terms")
+    return z, kl, logpq
+
+
+def iwae_finish(parts: torch.Tensor, logpq: torch.Tensor, kl: torch.Tensor):
+    """parts [K, B, 4], logpq [K, B], kl [B] -> (elbo [B], iwae [B]) (csrc/mol_loss.hip)"""
+    _need_gpu(parts, logpq, kl)
+    K, B = logpq.shape
+    if parts.shape != (K, B, 4) or kl.shape != (B,):
+        raise ValueError("iwae_finish: parts %s / kl %s for logpq %s" % (tuple(parts.shape), tuple(kl.shape), (K, B)))
+    parts, logpq, kl = parts.contiguous(), logpq.contiguous(), kl.contiguous()
+    f32 = dict(dtype=torch.float32, device=parts.device)
+    elbo, iwae = torch.empty(B, **f32), torch.empty(B, **f32)
+    _lib.check(_lib.load().ggpm_iwae_finish(_p(parts), _p(logpq), _p(kl), K, B, _p(elbo), _p(iwae), _stream()), "iwae_finish")
+    return elbo, iwae
+
+
 def padded_hidden(H: int) -> int:
     return (H + 15) // 16 * 16
 

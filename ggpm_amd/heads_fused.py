@@ -97,10 +97,11 @@ class AssmBlock:
         self.k, self.base, self.n, self.icls32, self.nth, self.dest = k, base, n, icls32, nth, dest
 
 
-def _heads_forward(heads, spec: dict, z, topo_x, cls_x, cand, infer: bool):
+def _heads_forward(heads, spec: dict, z, topo_x, cls_x, cand, infer: bool, rows_out: Optional[dict] = None):
     """The forward of _Heads -> (loss, accuracies, saved dict, dims); ``infer``: its forward-only form -> (loss,
     accuracies): the same launches without the loss gradients (the loss kernels' gradient outputs are nullable) and
-    nothing kept."""
+    nothing kept.  ``rows_out``: a dict that receives the loss kernels' per-row losses (their ``work`` buffers) under
+    'topo', 'cls', 'icls' and, with attachment predictions, 'assm'."""
     lib = _lib.load()
     H, L, B = heads.hidden_size, heads.latent_size, z.shape[0]
     dev = z.device
@@ -114,29 +115,35 @@ def _heads_forward(heads, spec: dict, z, topo_x, cls_x, cand, infer: bool):
     x_t = s_t[:, 0].contiguous()
     loss_t = torch.empty(1, **f32)
     dx_t = None if infer else torch.empty_like(x_t)       # (forward-only: losses and accuracies, no gradients)
+    rows_t = torch.empty_like(x_t)
     _lib.check(lib.ggpm_bce_logits(F_._p(x_t), F_._p(spec["topo_y"]), x_t.numel(), F_._p(loss_t), F_._p(dx_t),
-                                   F_._p(torch.empty_like(x_t)), F_._stream()), "bce_logits")
+                                   F_._p(rows_t), F_._stream()), "bce_logits")
+    if rows_out is not None:
+        rows_out["topo"] = rows_t
     # ---- motif-class and attachment-class heads: cross entropy over every cluster prediction (the roots first)
     n_c = cls_x.shape[0]
     cxt_c = _gather(zc, spec["cls_idx"], L, Lp)
     h_c, s_c = _mlp_forward(heads.clsNN, cls_x, cxt_c, H, L)
     h_i, s_i = _mlp_forward(heads.iclsNN, cls_x, cxt_c, H, L)
 
-    def ce(s, N, labels, mask=None, mask_row=None):
+    def ce(s, N, labels, mask=None, mask_row=None, name=None):
         M = s.shape[0]
+        rows = torch.empty(M, **f32)
         loss, arg = torch.empty(1, **f32), torch.empty(M, dtype=torch.int32, device=dev)
         d = None if infer else torch.empty(M, F_._ld(s), **f32)
         if d is not None and d.shape[1] > N:
             d[:, N:].zero_()
         _lib.check(lib.ggpm_softmax_ce(F_._p(s), F_._ld(s), M, N, F_._p(mask), 0 if mask is None else F_._ld(mask),
                                        F_._p(mask_row), F_._p(labels), F_._p(loss), F_._p(d), 0 if d is None else d.shape[1], F_._p(arg),
-                                       F_._p(torch.empty(M, **f32)), F_._stream()), "softmax_ce")
+                                       F_._p(rows), F_._stream()), "softmax_ce")
+        if rows_out is not None:
+            rows_out[name] = rows
         return loss, d, arg
 
-    loss_c, d_c, arg_c = ce(s_c, heads.clsNN[3].weight.shape[0], spec["cls_lab"])
+    loss_c, d_c, arg_c = ce(s_c, heads.clsNN[3].weight.shape[0], spec["cls_lab"], name="cls")
     vocab = heads.vocab
     mask = vocab.mask_on(dev) if hasattr(vocab, "mask_on") else vocab.mask.to(dev)
-    loss_i, d_i, arg_i = ce(s_i, heads.iclsNN[3].weight.shape[0], spec["icls_lab"], mask, spec["cls_lab"])
+    loss_i, d_i, arg_i = ce(s_i, heads.iclsNN[3].weight.shape[0], spec["icls_lab"], mask, spec["cls_lab"], name="icls")
     loss = loss_t + (loss_c + loss_i)
     # ---- attachment head: enum_attach over all candidates, W_assm, dot with the latent vector, cross entropy (label 0)
     blocks: List[AssmBlock] = spec["assm_blocks"]
@@ -165,7 +172,7 @@ def _heads_forward(heads, spec: dict, z, topo_x, cls_x, cand, infer: bool):
         F_.gemm(0, 1, P * C, L, H, buf, Hp, wa.weight, wa.weight.stride(0), proj, ldp, ldp, bias=wa.bias)
         cxt_a = _gather(zc, spec["assm_idx"], L, Lp)
         scores = (proj[:, :L] * cxt_a[:, :L]).sum(dim=-1).view(P, C).contiguous()
-        loss_a, d_a, _ = ce(scores, C, spec["assm_lab"])
+        loss_a, d_a, _ = ce(scores, C, spec["assm_lab"], name="assm")
         loss = loss + loss_a
         if not infer:
             saved.update(buf=buf, keep=keep, proj=proj, cxt_a=cxt_a, d_a=d_a)

@@ -27,8 +27,8 @@ import torch.nn as nn
 from . import _dev
 from . import functional as F_
 from . import inc_encoder as IE
-from .decoder import DecodeSchedule, MAX_POS, _accuracy, _memo, level_states
-from .decoder_heads import ScoreHeads, bce_with_logits_sum
+from .decoder import DecodeSchedule, MAX_POS, _accuracy, _memo, _pinned_cls_size, level_states
+from .decoder_heads import ScoreHeads, bce_rows, bce_with_logits_sum, cross_entropy_rows, _mlp
 
 
 class _MotifAssm(torch.autograd.Function):
@@ -180,6 +180,65 @@ class MotifDecoder(ScoreHeads):
         assm_loss, assm_acc = self.assm_head(schedule, src_graph_vecs)
         loss = (topo_loss + cls_loss + assm_loss) / B
         return loss, cls_acc, icls_acc, topo_acc, assm_acc
+
+    def molecule_losses(self, mols, src_mol_vecs, graphs, tensors, orders, schedule: Optional[DecodeSchedule] = None,
+                        max_cls_size: Optional[int] = None, atom=None, out: Optional[torch.Tensor] = None):
+        """The per-molecule form of what ``forward`` sums, forward only -> [B, 4]: per molecule the sum of its rows'
+        topology BCE, motif-class CE, attachment-class CE and attachment CE (``forward``'s loss is their total / B).
+        ``max_cls_size``: the number of rows every attachment prediction is padded to (the reference pads to the batch's
+        largest cluster x 2 with zero candidates, which score ``b_assm . z``): None takes the batch's own, an int pins it.
+        ``atom`` is HierMPNDecoder's argument (this decoder has no atom level: None); ``out``: a contiguous fp32 [B, 4]
+        tensor to write."""
+        from . import _lib
+        if self.training and any(isinstance(m, nn.Dropout) and m.p > 0 for m in self.modules()):
+            raise NotImplementedError("MotifDecoder.molecule_losses runs without dropout: call model.eval() first")
+        tree_tensors, graph_tensors = tensors
+        B, H, L = len(orders), self.hidden_size, self.latent_size
+        dev = tree_tensors[0].device
+        if schedule is None:
+            schedule = DecodeSchedule.from_graphs(graphs, tensors, orders, self.vocab)
+        C = _pinned_cls_size(schedule, max_cls_size)
+        src_root_vecs, src_tree_vecs, src_graph_vecs = src_mol_vecs
+        with torch.no_grad():
+            D = schedule.to_device(dev)._dev
+            if L == H:
+                init_vecs = src_root_vecs
+            else:
+                init_vecs = F_.linear([src_root_vecs.contiguous()], [L], self.W_root.weight, self.W_root.bias)[:, :H]
+            if _dev.DECODER_BATCHED and schedule.plan["all_live"] and schedule.plan["E1"] > 1:
+                topo_vecs, cls_vecs = self._states_batched(schedule, D, tree_tensors, init_vecs)
+            else:
+                topo_vecs, cls_vecs = self._states_stepwise(schedule, tree_tensors, graph_tensors, init_vecs)
+            topo_scores = self.get_topo_score(src_tree_vecs, D["topo_batch32"], topo_vecs)
+            topo_rows = bce_rows(topo_scores, _memo(D, "topo_label_f32", lambda: D["topo_label"].to(torch.float32)))
+            clab = _memo(D, "cls_clab32", lambda: D["cls_clab"].to(torch.int32).contiguous())
+            ilab = _memo(D, "cls_ilab32", lambda: D["cls_ilab"].to(torch.int32).contiguous())
+            parts = self._parts(src_tree_vecs, D["cls_batch32"], cls_vecs)
+            cls_rows = cross_entropy_rows(_mlp(self.clsNN, *parts), clab)
+            vocab = self.vocab
+            mask = vocab.mask_on(dev) if hasattr(vocab, "mask_on") else vocab.mask.to(dev)
+            icls_rows = cross_entropy_rows(_mlp(self.iclsNN, *parts), ilab, mask=mask, mask_row=clab)
+            assm = None
+            ap = assm_plan(schedule)
+            if ap.P > 0:
+                # the head's own launch (csrc/motif_assm.hip): stat[p] = {lse, s0, loss, hit}, so the losses sit 4 floats apart
+                meta, ids = ap.to_device(dev)
+                rows = IE._embedding_rows(self.E_assm, ids).contiguous()
+                z = src_graph_vecs.contiguous()
+                l1, wa = self.matchNN[0], self.W_assm
+                f32 = dict(dtype=torch.float32, device=dev)
+                act, score = torch.empty(rows.shape[0], H, **f32), torch.empty(max(ap.n_cand, 1), **f32)
+                stat, res = torch.empty(ap.P, 4, **f32), torch.empty(2, **f32)
+                counter = torch.zeros(1, dtype=torch.int32, device=dev)
+                _lib.check(_lib.load().ggpm_motif_assm_forward(
+                    F_._p(rows), rows.stride(0), F_._p(meta), ap.P, C, H, L, F_._p(l1.weight), l1.weight.stride(0),
+                    F_._p(l1.bias), F_._p(wa.weight), F_._p(wa.bias), F_._p(z), z.stride(0), F_._p(act), F_._p(score),
+                    F_._p(stat), F_._p(res), F_._p(counter), F_._stream()), "motif_assm_forward")
+                pred_mol = _memo(D, "motif_assm_mol32", lambda: meta[:, 3].contiguous())
+                assm = (stat.view(-1)[2:], pred_mol, ap.P, 4)
+            n_c = cls_rows.numel()
+            return F_.mol_loss_parts([(topo_rows, D["topo_batch32"], topo_rows.numel()), (cls_rows, D["cls_batch32"], n_c),
+                                      (icls_rows, D["cls_batch32"], n_c), assm], B, out=out)
 
     def assm_head(self, schedule: DecodeSchedule, src_graph_vecs):
         """(attachment loss sum, accuracy) -- enum_attach, get_assm_score, the cross entropy over max_cls_size rows and

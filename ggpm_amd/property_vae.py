@@ -7,6 +7,7 @@ ggpm/property_vae.py:26-33; the two [B,H]x[H,latent] products run through the li
 from __future__ import annotations
 
 import os
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
@@ -47,6 +48,17 @@ class _RsampleTail(torch.autograd.Function):
         return dmean, dpv, None
 
 
+def _latent_heads(z_vecs, Wm, bm, Wv, bv):
+    """(mean, pre_var) = (R_mean(h), R_var(h)): both [B,H]x[H,latent] products in one grouped launch"""
+    B, (L, H) = z_vecs.shape[0], Wm.shape
+    mean = torch.empty(B, L, dtype=torch.float32, device=z_vecs.device)
+    pv = torch.empty(B, L, dtype=torch.float32, device=z_vecs.device)
+    F_.gemm_grouped(0, 1, B, L, H, [
+        dict(A=z_vecs, lda=F_._ld(z_vecs), B=Wm, ldb=Wm.stride(0), C=mean, ldc=L, n_pad=L, bias=bm),
+        dict(A=z_vecs, lda=F_._ld(z_vecs), B=Wv, ldb=Wv.stride(0), C=pv, ldc=L, n_pad=L, bias=bv)])
+    return mean, pv
+
+
 class _KLHead(torch.autograd.Function):
     """The whole of rsample as ONE autograd node: both [B,H]x[H,latent] products in one grouped launch, the elementwise
     tail in one launch, and on the way back one launch for d(z_vecs) (two K segments), one grouped launch for the two
@@ -57,11 +69,7 @@ class _KLHead(torch.autograd.Function):
         from . import _lib
         B, (L, H) = z_vecs.shape[0], Wm.shape
         dev = z_vecs.device
-        mean = torch.empty(B, L, dtype=torch.float32, device=dev)
-        pv = torch.empty(B, L, dtype=torch.float32, device=dev)
-        F_.gemm_grouped(0, 1, B, L, H, [
-            dict(A=z_vecs, lda=F_._ld(z_vecs), B=Wm, ldb=Wm.stride(0), C=mean, ldc=L, n_pad=L, bias=bm),
-            dict(A=z_vecs, lda=F_._ld(z_vecs), B=Wv, ldb=Wv.stride(0), C=pv, ldc=L, n_pad=L, bias=bv)])
+        mean, pv = _latent_heads(z_vecs, Wm, bm, Wv, bv)
         z = torch.empty_like(mean)
         kl = torch.empty(1, dtype=torch.float32, device=dev)
         _lib.check(_lib.load().ggpm_rsample_forward(F_._p(mean), F_._p(pv), F_._p(eps), B, L, F_._p(z), F_._p(kl),
@@ -246,6 +254,11 @@ class HierPropertyVAE(nn.Module):
         (results, molecules)."""
         return _sample(self, batch_size, greedy, seed, max_decode_step, beam, graph_batch_factory)
 
+    def log_likelihood(self, batch, n_samples=1, seed=None, sample_ids=None, eps=None, max_cls_size=None, schedule=None):
+        """Per-molecule reconstruction terms, KL, ELBO and the ``n_samples``-sample importance-weighted bound of ``batch``
+        (the tuple ``self(*batch)`` takes) -> :class:`MolLikelihood`; forward only, see :func:`log_likelihood`."""
+        return log_likelihood(self, batch, n_samples, seed, sample_ids, eps, max_cls_size, schedule)
+
     def reconstruct(self, batch, args=None):
         """reference ggpm/property_vae.py:39-45: the no-grad encoder, the mean latent, greedy decode of 150 steps ->
         (results, molecules).  The graph batch: ``args.graph_batch_factory``, else the decoder's."""
@@ -402,6 +415,11 @@ class HierPropOptVAE(_ClipNegativeLoss, nn.Module):
         (results, molecules)."""
         return _sample(self, batch_size, greedy, seed, max_decode_step, beam, graph_batch_factory)
 
+    def log_likelihood(self, batch, n_samples=1, seed=None, sample_ids=None, eps=None, max_cls_size=None, schedule=None):
+        """Per-molecule reconstruction terms, KL, ELBO and the ``n_samples``-sample importance-weighted bound of ``batch``
+        (the tuple ``self(*batch)`` takes) -> :class:`MolLikelihood`; forward only, see :func:`log_likelihood`."""
+        return log_likelihood(self, batch, n_samples, seed, sample_ids, eps, max_cls_size, schedule)
+
     def reconstruct(self, batch, args=None):
         """reference ggpm/property_vae.py:169-188: the no-grad encoder, the mean latent, the property heads on it, greedy
         decode of 150 steps -> ((homo [B], lumo [B]), (results, molecules)).  The graph batch: ``args.graph_batch_factory``,
@@ -484,6 +502,86 @@ def _sample(model, batch_size, greedy, seed, max_decode_step, beam, graph_batch_
                                   graph_batch_factory=factory)
 
 
+MolLikelihood = namedtuple("MolLikelihood", ["parts", "kl", "elbo", "iwae", "z", "stats"])
+MolLikelihood.__doc__ = """What ``log_likelihood`` returns: fp32 device tensors (none requires grad, nothing is synchronised)
+for K samples, B molecules and latent width L.
+  parts [K, B, 4]  per sample and molecule the summed row losses of the topology BCE, the motif-class CE, the attachment-class
+                   CE (vocabulary mask as in training) and the attachment CE (label 0); 0 where a molecule has no such row
+  kl    [B]        -0.5 * sum_j(1 + lv - mean^2 - exp(lv)), lv = -|R_var(h)|: the reference's rsample before its / B
+  elbo  [B]        -mean_k(sum of parts[k, i, :]) - kl[i]
+  iwae  [B]        logsumexp_k(-nll[k, i] + log p(z_k) - log q(z_k | x_i)) - log K; the single-sample ELBO estimate for K = 1
+  z     [K, B, L]  the latents used
+  stats            {'encoder_calls', 'atom_level_calls', 'decoder_passes'}: python ints, what the call issued"""
+
+
+def log_likelihood(model, batch, n_samples=1, seed=None, sample_ids=None, eps=None, max_cls_size=None, schedule=None):
+    """``log_likelihood`` of the four VAEs (*Per-molecule ELBO and the importance-weighted bound*).
+
+    The encoder, ``R_mean`` / ``R_var`` and -- for the hierarchical decoder -- the atom level run once: under teacher
+    forcing none of them depends on the latent draw.  Per sample only ``z_k``, ``W_root``, the tree-side levels and the
+    heads run.  ``eps[k, i, :]`` comes from the seeded stream of csrc/sample.hip at site LATENT, keyed by ``seed`` (an int,
+    64 bits used; None takes them from torch's default CPU generator), ``sample_ids[i]`` (default ``arange``) and the counter
+    ``k * L + column``: a molecule's draws do not depend on its batch, and the first K draws of a larger call are the
+    K-sample call's.  ``eps=`` (a fp32 [K, B, L] tensor on the model's device, ``n_samples`` = K) replaces the stream; all
+    zeros with K = 1 is the ``perturb_z=False`` latent.  ``max_cls_size``: see ``molecule_losses`` -- None is the training
+    convention (the parts then add up to the training loss x B), an int makes numbers comparable across batches."""
+    from .decoder import HierMPNDecoder, _pinned_cls_size
+    from .greedy_decode import split_seed
+    name, dec = type(model).__name__, model.decoder
+    if any(m.training and isinstance(m, nn.Dropout) and m.p > 0 for m in model.modules()):
+        raise NotImplementedError("%s.log_likelihood runs without dropout: call model.eval() first" % name)
+    mols, graphs, tensors, orders = batch[0], batch[1], batch[2], batch[3]
+    B, L = len(orders), model.R_mean.weight.shape[0]
+    dev = model.R_mean.weight.device
+    K = n_samples
+    if isinstance(K, bool) or int(K) != K or not 1 <= int(K) <= F_.LIKELIHOOD_MAX_K:
+        raise ValueError("%s.log_likelihood: n_samples %r (1 .. %d)" % (name, n_samples, F_.LIKELIHOOD_MAX_K))
+    K = int(K)
+    if eps is not None:
+        if not isinstance(eps, torch.Tensor) or eps.dtype != torch.float32 or eps.device != dev:
+            raise ValueError("%s.log_likelihood: eps must be a float32 tensor on %s" % (name, dev))
+        if tuple(eps.shape) != (K, B, L):
+            raise ValueError("%s.log_likelihood: eps of shape %s for n_samples %d, %d molecules and latent width %d"
+                             % (name, tuple(eps.shape), K, B, L))
+    if sample_ids is not None and len(sample_ids) != B:
+        raise ValueError("%s.log_likelihood: %d sample_ids for %d molecules" % (name, len(sample_ids), B))
+    schedule = _motif_schedule(model, graphs, tensors, orders, schedule)
+    if schedule is None:
+        raise ValueError("%s.log_likelihood: the batch carries no graphs (batch[1]) and no schedule= was given: nothing to "
+                         "derive the decoder's bookkeeping from" % name)
+    C = _pinned_cls_size(schedule, max_cls_size)
+    hier = isinstance(dec, HierMPNDecoder)
+    stats = dict(encoder_calls=0, atom_level_calls=0, decoder_passes=0)
+    with torch.no_grad():
+        tree_tensors, graph_tensors = tensors = make_cuda(tensors)
+        atom = None
+        if hier:
+            atom = dec.atom_level(schedule, tensors)
+            if atom is None:
+                raise NotImplementedError("%s.log_likelihood: this batch runs the decoder's step loop (no tree message at all, "
+                                          "no AtomPlan, or a batched form switched off in ggpm_amd._dev), which has no "
+                                          "per-molecule form" % name)
+            stats["atom_level_calls"] = 1
+            root_vecs = model.encoder.forward_padded(tree_tensors, graph_tensors)[0]
+        else:
+            root_vecs = model.encoder.forward_padded(tree_tensors)[0]
+        stats["encoder_calls"] = 1
+        Rm, Rv = model.R_mean, model.R_var
+        mean, pre_var = _latent_heads(root_vecs, Rm.weight, Rm.bias, Rv.weight, Rv.bias)
+        if eps is None:
+            lo, hi = split_seed(seed)
+            eps = F_.sample_latent_normal(K, B, L, lo, hi, ids=sample_ids, device=dev)
+        z, kl, logpq = F_.latent_terms(mean, pre_var, eps)
+        parts = torch.empty(K, B, 4, dtype=torch.float32, device=dev)
+        for k in range(K):
+            zk = z[k]
+            dec.molecule_losses(mols, (zk, zk, zk), graphs, tensors, orders, schedule=schedule, max_cls_size=C, atom=atom,
+                                out=parts[k])
+            stats["decoder_passes"] += 1
+        elbo, iwae = F_.iwae_finish(parts, logpq, kl)
+    return MolLikelihood(parts, kl, elbo, iwae, z, stats)
+
+
 def _graph_batch_factory(model, args):
     """decode's graph batch for reconstruct: ``args.graph_batch_factory``, else the decoder's; neither raises before the
     batch is touched."""
@@ -541,6 +639,11 @@ class PropertyVAE(nn.Module):
         drawn on the device, then ``decode`` or, with ``greedy=False``, ``decode_sampled`` at the same seed ->
         (results, molecules)."""
         return _sample(self, batch_size, greedy, seed, max_decode_step, beam, graph_batch_factory)
+
+    def log_likelihood(self, batch, n_samples=1, seed=None, sample_ids=None, eps=None, max_cls_size=None, schedule=None):
+        """Per-molecule reconstruction terms, KL, ELBO and the ``n_samples``-sample importance-weighted bound of ``batch``
+        (the tuple ``self(*batch)`` takes) -> :class:`MolLikelihood`; forward only, see :func:`log_likelihood`."""
+        return log_likelihood(self, batch, n_samples, seed, sample_ids, eps, max_cls_size, schedule)
 
     def reconstruct(self, batch, args=None):
         """reference ggpm/property_vae.py:101-109: the no-grad encoder, the mean latent, greedy decode of 150 steps ->
@@ -617,6 +720,11 @@ class PropOptVAE(_ClipNegativeLoss, nn.Module):
         drawn on the device, then ``decode`` or, with ``greedy=False``, ``decode_sampled`` at the same seed ->
         (results, molecules)."""
         return _sample(self, batch_size, greedy, seed, max_decode_step, beam, graph_batch_factory)
+
+    def log_likelihood(self, batch, n_samples=1, seed=None, sample_ids=None, eps=None, max_cls_size=None, schedule=None):
+        """Per-molecule reconstruction terms, KL, ELBO and the ``n_samples``-sample importance-weighted bound of ``batch``
+        (the tuple ``self(*batch)`` takes) -> :class:`MolLikelihood`; forward only, see :func:`log_likelihood`."""
+        return log_likelihood(self, batch, n_samples, seed, sample_ids, eps, max_cls_size, schedule)
 
     def reconstruct(self, batch, args=None):
         """reference ggpm/property_vae.py:299-318: the no-grad encoder, the mean latent, the property heads on it, greedy

@@ -754,6 +754,44 @@ int ggpm_sample_beam_order(const int32_t* topk, const int32_t* bidx, const int32
 int ggpm_sample_normal(float* out, int rows, int cols, int ld, const int32_t* ids, unsigned int seed_lo,
                        unsigned int seed_hi, ggpm_stream_t stream);
 
+/* Per-molecule likelihood terms of the teacher-forced decoder (log_likelihood of the four VAEs; csrc/mol_loss.hip and, for
+ * the draw, csrc/sample.hip).  One wave owns one output element and adds in a fixed order: no atomics, bitwise reproducible;
+ * sums are carried in fp64 and rounded to fp32 once.  1 <= K <= GGPM_LIKELIHOOD_MAX_K samples, B molecules, L latent columns.
+ * ggpm_sample_latent_normal (one launch): out[k, b, c] = the Box-Muller normal of ggpm_sample_normal from the words
+ * m(LATENT, ids[b], k * L + c, 0 / 1): a molecule's draws depend on its id, k, c and the seed only, and the first K samples of
+ * a larger call are the K-sample call's.  K * L < 2^26, K * B * L < 2^31.
+ * ggpm_mol_loss_parts (one launch): parts[b, t] = sum over the rows r < n_rows of term t with mol[r] == b of
+ * row_loss[r * stride], t < GGPM_MOL_LOSS_TERMS (topology BCE, motif-class CE, attachment-class CE, attachment CE): what
+ * ggpm_softmax_ce / ggpm_bce_logits leave in `work` (stride 1) or ggpm_motif_assm_forward in `stat` (stride 4, from
+ * stat + 2).  `terms` is a host array of GGPM_MOL_LOSS_TERMS entries; an absent term has n_rows 0 (its pointers may be
+ * null) and a molecule without rows in a term gets 0.  A row whose molecule is outside [0, B) is counted nowhere.
+ * ggpm_latent_terms (one launch): with lv = -|pre_var|,
+ *     z[k, b, j] = mean[b, j] + exp(lv[b, j] / 2) * eps[k, b, j]          (fp32, ggpm_rsample_forward's expression)
+ *     kl[b] = -0.5 * sum_j (1 + lv - mean^2 - exp(lv))                     (ggpm/property_vae.py:26-33 before its / B;
+ *                                                                           fp32 addends, ggpm_rsample_forward's)
+ *     logpq[k, b] = log p(z_k) - log q(z_k | x_b) = -0.5 * sum_j z^2 + 0.5 * sum_j (eps^2 + lv)     (the 2 pi terms cancel)
+ * mean, pre_var [B x L], eps and z [K x B x L], all dense.
+ * ggpm_iwae_finish (one launch): with nll[k, b] = sum_t parts[k, b, t],
+ *     elbo[b] = -mean_k nll[k, b] - kl[b]
+ *     iwae[b] = logsumexp_k (logpq[k, b] - nll[k, b]) - log K               (maximum subtracted before the exponentials)
+ * A null pointer, a size <= 0, K outside its range, a negative n_rows or a stride < 1 returns GGPM_ERR_ARG; nothing is
+ * launched then. */
+#define GGPM_SITE_SAMPLE_LATENT 259
+#define GGPM_LIKELIHOOD_MAX_K 1024
+#define GGPM_MOL_LOSS_TERMS 4
+typedef struct ggpm_mol_loss_term {
+    const float* row_loss;      /* device, n_rows values `stride` floats apart */
+    const int32_t* mol;         /* device, the molecule of every row */
+    int stride, n_rows;
+} ggpm_mol_loss_term;
+int ggpm_sample_latent_normal(float* out, int K, int B, int L, const int32_t* ids, unsigned int seed_lo,
+                              unsigned int seed_hi, ggpm_stream_t stream);
+int ggpm_mol_loss_parts(const ggpm_mol_loss_term* terms, int B, float* parts, ggpm_stream_t stream);
+int ggpm_latent_terms(const float* mean, const float* pre_var, const float* eps, int K, int B, int L, float* z, float* kl,
+                      float* logpq, ggpm_stream_t stream);
+int ggpm_iwae_finish(const float* parts, const float* logpq, const float* kl, int K, int B, float* elbo, float* iwae,
+                     ggpm_stream_t stream);
+
 /* ------------------------------------------------------------------ whole-encoder drivers
  * HierMPNEncoder.forward (ggpm/encoder.py:140-157, with embed_graph/inter/tree/root :96-138) and its backward as ONE
  * call each: the same kernels the op-by-op host path issues, sequenced from C++ (GRU or LSTM message function).
