@@ -87,6 +87,7 @@ SIGNATURES = {
     # attachment head of the tree-only decoder (csrc/motif_assm.hip)
     "ggpm_motif_assm_forward": (I, [P, I, P, I, I, I, I, P, I, P, P, P, P, I, P, P, P, P, P, P]),
     "ggpm_motif_assm_backward": (I, [P, P, I, P, I, I, I, I, I, P, I, P, P, P, I, P, P, P, P, P, P, P, P, P, P]),
+    "ggpm_motif_assm_backward_weighted": (I, [P, P, I, P, I, P, I, I, I, I, I, P, I, P, P, P, I, P, P, P, P, P, P, P, P, P, P]),
     # greedy decode of the tree-only decoder (csrc/motif_decode.hip)
     "ggpm_motif_decode_tree_step": (I, [I, I, I, I, POINTER(c_void_p), P, P, P, P, I, I, P, P, P, I, I, P, I, P, I, P, I,
                                         P, I, P]),
@@ -106,6 +107,10 @@ SIGNATURES = {
     "ggpm_mol_loss_parts": (I, [P, I, P, P]),
     "ggpm_latent_terms": (I, [P, P, P, I, I, I, P, P, P, P]),
     "ggpm_iwae_finish": (I, [P, P, P, I, I, P, P, P]),
+    # training on the bound (csrc/mol_loss.hip)
+    "ggpm_bound_objective": (I, [P, P, P, P, I, I, I, ctypes.c_float, P, P, P, P, P, P]),
+    "ggpm_scale_rows_by_mol": (I, [P, I, I, I, P, P, I, I, P, P]),
+    "ggpm_latent_terms_backward": (I, [P, P, P, P, P, P, P, I, I, I, P, P, P]),
     "ggpm_dropout": (I, [P, I, I, I, ctypes.c_float, ctypes.c_uint, ctypes.c_uint, I, P]),
     # property heads / latent search (csrc/property.hip): heads are ggpm_prop_head*, grads ggpm_prop_head_grads*
     "ggpm_property_heads_workspace_bytes": (c_size_t, [I, I, P, P]),

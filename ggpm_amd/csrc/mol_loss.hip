@@ -2,6 +2,10 @@
 //   ggpm_mol_loss_parts : the row losses the loss kernels leave in `work`, summed per (molecule, term)
 //   ggpm_latent_terms   : z_k = mean + exp(lv / 2) eps_k, the analytic KL, log p(z_k) - log q(z_k | x)
 //   ggpm_iwae_finish    : ELBO and the K-sample importance-weighted bound (max-subtracted logsumexp over k)
+// and what training on them needs ("Training on the bound"):
+//   ggpm_bound_objective       : the weighted K-sample ELBO / IWAE loss and its partial derivatives c_nll, c_logpq, c_kl
+//   ggpm_scale_rows_by_mol     : d[m, 0:N] *= g * coef[mol[m]], the chain rule of a per-molecule upstream gradient
+//   ggpm_latent_terms_backward : the backward of ggpm_latent_terms, summed over k in a fixed order
 // One wave owns one output element and walks its addends in a fixed order: no atomics, bitwise reproducible.  Sums are
 // carried in fp64 and rounded to fp32 once, where they are stored.
 #include "common.h"
@@ -95,6 +99,108 @@ __global__ void __launch_bounds__(64) iwae_finish_k(const float* __restrict__ pa
     }
 }
 
+// block = molecule b; the lanes stride the samples.  Writes the molecule's coefficients and its (unrounded) addend of the loss.
+__global__ void __launch_bounds__(64) bound_objective_k(const float* __restrict__ parts, const float* __restrict__ logpq,
+                                                        const float* __restrict__ kl, const float* __restrict__ w, int K, int B,
+                                                        int objective, float beta, double* __restrict__ addend,
+                                                        float* __restrict__ c_nll, float* __restrict__ c_logpq,
+                                                        float* __restrict__ c_kl) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const double wb = w ? (double)w[b] : 1.0;
+    if (objective == GGPM_BOUND_ELBO) {
+        double s_nll = 0.0;
+        for (int k = lane; k < K; k += 64) {
+            const float* q = parts + ((size_t)k * B + b) * GGPM_MOL_LOSS_TERMS;
+            s_nll += ((double)q[0] + (double)q[1]) + ((double)q[2] + (double)q[3]);
+            c_nll[(size_t)k * B + b] = (float)(wb / ((double)K * (double)B));
+            c_logpq[(size_t)k * B + b] = 0.f;
+        }
+        s_nll = wave_sum_f64(s_nll);
+        if (lane == 0) {
+            c_kl[b] = (float)((double)beta * wb / (double)B);
+            addend[b] = wb * (s_nll / (double)K + (double)beta * (double)kl[b]);
+        }
+        return;
+    }
+    double mx = -INFINITY;
+    for (int k = lane; k < K; k += 64) {
+        const float* q = parts + ((size_t)k * B + b) * GGPM_MOL_LOSS_TERMS;
+        const double nll = ((double)q[0] + (double)q[1]) + ((double)q[2] + (double)q[3]);
+        mx = fmax(mx, (double)logpq[(size_t)k * B + b] - nll);
+    }
+    mx = wave_max_f64(mx);
+    double se = 0.0;
+    for (int k = lane; k < K; k += 64) {
+        const float* q = parts + ((size_t)k * B + b) * GGPM_MOL_LOSS_TERMS;
+        const double nll = ((double)q[0] + (double)q[1]) + ((double)q[2] + (double)q[3]);
+        se += exp((double)logpq[(size_t)k * B + b] - nll - mx);
+    }
+    se = wave_sum_f64(se);
+    for (int k = lane; k < K; k += 64) {
+        const float* q = parts + ((size_t)k * B + b) * GGPM_MOL_LOSS_TERMS;
+        const double nll = ((double)q[0] + (double)q[1]) + ((double)q[2] + (double)q[3]);
+        const double c = wb * (exp((double)logpq[(size_t)k * B + b] - nll - mx) / se) / (double)B;
+        c_nll[(size_t)k * B + b] = (float)c;
+        c_logpq[(size_t)k * B + b] = (float)-c;
+    }
+    if (lane == 0) {
+        c_kl[b] = 0.f;
+        addend[b] = -wb * (mx + log(se) - log((double)K));
+    }
+}
+
+// one wave: the molecules' addends in a fixed order, rounded once.
+__global__ void __launch_bounds__(64) bound_loss_sum_k(const double* __restrict__ addend, int B, float* __restrict__ loss) {
+    double acc = 0.0;
+    for (int b = threadIdx.x; b < B; b += 64) acc += addend[b];
+    acc = wave_sum_f64(acc);
+    if (threadIdx.x == 0) loss[0] = (float)(acc / (double)B);
+}
+
+// wave = row m (four per block); the lanes stride its N columns.
+__global__ void __launch_bounds__(256) scale_rows_by_mol_k(float* __restrict__ d, int ld, int M, int N,
+                                                           const int32_t* __restrict__ mol, const float* __restrict__ coef,
+                                                           int coef_stride, int B, const float* __restrict__ g) {
+    const int m = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (m >= M) return;
+    const int b = mol[m];
+    float s = 0.f;                                           // a row of no molecule counts nowhere: its gradient is 0
+    if (b >= 0 && b < B) s = (g ? g[0] : 1.f) * coef[(size_t)b * coef_stride];
+    float* row = d + (size_t)m * ld;
+    for (int n = lane; n < N; n += 64) row[n] = (b >= 0 && b < B) ? row[n] * s : 0.f;
+}
+
+// block = (molecule b, column j); the lanes stride the samples.  z is re-formed with ggpm_latent_terms' fp32 expression.
+__global__ void __launch_bounds__(64) latent_terms_bwd_k(const float* __restrict__ dz, const float* __restrict__ mean,
+                                                         const float* __restrict__ pv, const float* __restrict__ eps,
+                                                         const float* __restrict__ c_logpq, const float* __restrict__ c_kl,
+                                                         const float* __restrict__ g, int K, int B, int L,
+                                                         float* __restrict__ dmean, float* __restrict__ dpv) {
+    const int b = blockIdx.x / L, j = blockIdx.x - b * L, lane = threadIdx.x;
+    const size_t i = (size_t)b * L + j;
+    const float m = mean[i], p = pv[i], lv = -fabsf(p);
+    const float sd = expf(0.5f * lv);
+    const double gs = g ? (double)g[0] : 1.0;
+    double s_m = 0.0, s_lv = 0.0;
+    for (int k = lane; k < K; k += 64) {
+        const size_t kb = (size_t)k * B + b;
+        const float e = eps[kb * L + j];
+        const float z = m + sd * e;
+        const double G = c_logpq ? gs * (double)c_logpq[kb] : 0.0;
+        const double a = (dz ? (double)dz[kb * L + j] : 0.0) - G * (double)z;      // d/dz: the decoder's and logpq's -z
+        s_m += a;
+        s_lv += a * (0.5 * (double)sd * (double)e) + 0.5 * G;                      // z's exp(lv / 2) eps and logpq's + lv / 2
+    }
+    s_m = wave_sum_f64(s_m);
+    s_lv = wave_sum_f64(s_lv);
+    if (lane == 0) {
+        const double gk = c_kl ? gs * (double)c_kl[b] : 0.0;
+        dmean[i] = (float)(s_m + gk * (double)m);
+        const double dlv = s_lv - 0.5 * gk * (1.0 - (double)expf(lv));
+        dpv[i] = (float)((p > 0.f ? -1.0 : (p < 0.f ? 1.0 : 0.0)) * dlv);          // d(-|p|)/dp = -sign(p)  (0 at p = 0)
+    }
+}
+
 }  // namespace
 
 extern "C" int ggpm_mol_loss_parts(const ggpm_mol_loss_term* terms, int B, float* parts, ggpm_stream_t stream) {
@@ -130,6 +236,42 @@ extern "C" int ggpm_iwae_finish(const float* parts, const float* logpq, const fl
     GGPM_CLEAR_STALE_ERROR();
     if (!parts || !logpq || !kl || !elbo || !iwae || K < 1 || K > GGPM_LIKELIHOOD_MAX_K || B <= 0) return GGPM_ERR_ARG;
     iwae_finish_k<<<B, 64, 0, (hipStream_t)stream>>>(parts, logpq, kl, K, B, elbo, iwae);
+    GGPM_CHECK_LAUNCH();
+    return GGPM_OK;
+}
+
+extern "C" int ggpm_bound_objective(const float* parts, const float* logpq, const float* kl, const float* w, int K, int B,
+                                    int objective, float beta, double* work, float* loss, float* c_nll, float* c_logpq,
+                                    float* c_kl, ggpm_stream_t stream) {
+    GGPM_CLEAR_STALE_ERROR();
+    if (!parts || !logpq || !kl || !work || !loss || !c_nll || !c_logpq || !c_kl || K < 1 || K > GGPM_LIKELIHOOD_MAX_K ||
+        B <= 0 || (size_t)K * (size_t)B >= ((size_t)1 << 31) || (objective != GGPM_BOUND_ELBO && objective != GGPM_BOUND_IWAE) ||
+        !(beta == beta) || (objective == GGPM_BOUND_IWAE && beta != 1.f))
+        return GGPM_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    bound_objective_k<<<B, 64, 0, s>>>(parts, logpq, kl, w, K, B, objective, beta, work, c_nll, c_logpq, c_kl);
+    bound_loss_sum_k<<<1, 64, 0, s>>>(work, B, loss);
+    GGPM_CHECK_LAUNCH();
+    return GGPM_OK;
+}
+
+extern "C" int ggpm_scale_rows_by_mol(float* d, int ld, int M, int N, const int32_t* mol, const float* coef, int coef_stride,
+                                      int B, const float* g, ggpm_stream_t stream) {
+    GGPM_CLEAR_STALE_ERROR();
+    if (!d || !mol || !coef || M <= 0 || N <= 0 || ld < N || B <= 0 || coef_stride < 1) return GGPM_ERR_ARG;
+    scale_rows_by_mol_k<<<ggpm_ceil_div(M, 4), 256, 0, (hipStream_t)stream>>>(d, ld, M, N, mol, coef, coef_stride, B, g);
+    GGPM_CHECK_LAUNCH();
+    return GGPM_OK;
+}
+
+extern "C" int ggpm_latent_terms_backward(const float* dz, const float* mean, const float* pre_var, const float* eps,
+                                          const float* c_logpq, const float* c_kl, const float* g, int K, int B, int L,
+                                          float* dmean, float* dpre_var, ggpm_stream_t stream) {
+    GGPM_CLEAR_STALE_ERROR();
+    if (!mean || !pre_var || !eps || !dmean || !dpre_var || K < 1 || K > GGPM_LIKELIHOOD_MAX_K || B <= 0 || L <= 0 ||
+        (size_t)B * (size_t)L >= ((size_t)1 << 31) || (size_t)K * (size_t)B >= ((size_t)1 << 31))
+        return GGPM_ERR_ARG;
+    latent_terms_bwd_k<<<B * L, 64, 0, (hipStream_t)stream>>>(dz, mean, pre_var, eps, c_logpq, c_kl, g, K, B, L, dmean, dpre_var);
     GGPM_CHECK_LAUNCH();
     return GGPM_OK;
 }

@@ -34,6 +34,7 @@ struct AssmBwd {
     const float* act; const float* score; const float* stat;
     float* drows; float* dW1; float* db1; float* dWa; float* dba; float* dz;
     int nb_w1, nb_wa;
+    const float* coef; int coef_stride;         // per-molecule upstream gradient (ggpm_motif_assm_backward_weighted), else null
 };
 
 // fixed-order block sum (every thread gets the result)
@@ -140,6 +141,13 @@ __global__ void __launch_bounds__(ASSM_THREADS) motif_assm_fwd_k(AssmFwd a) {
 // entropy does not change under a shift of every score.  Evaluated in fp32 that sum is one rounding of lse away from 1
 // (about ulp(lse) / 2, 1e-6 at lse = 16), with a sign of its own per prediction; summed over 700 predictions into dba that is
 // 2e-5.  So dba is written as the zero it is, and dz gets no ba term.
+// the upstream gradient of a prediction of molecule b: dloss[0] (1 when absent), times the molecule's coefficient when given
+__device__ __forceinline__ float base_g(const AssmBwd& a) { return a.dloss ? a.dloss[0] : 1.f; }
+__device__ __forceinline__ float pred_g(const AssmBwd& a, float g, int b) {
+    if (!a.coef) return g;
+    return (b >= 0 && b < a.B) ? g * a.coef[(size_t)b * a.coef_stride] : 0.f;
+}
+
 __device__ __forceinline__ float dscore(const AssmBwd& a, float g, const float* st, int coff, int c) {
     return g * (expf(a.score[coff + c] - st[0]) - (c == 0 ? 1.f : 0.f));
 }
@@ -149,7 +157,7 @@ __device__ void bwd_w1(const AssmBwd& a, int blk) {
     __shared__ float us[ASSM_HS];
     const int t = threadIdx.x, H = a.H, L = a.L, W = H + 20;
     const int h0 = blk * ASSM_HS;
-    const float g = a.dloss[0];
+    const float g = base_g(a);
     float acc[ASSM_HS][4];
     float accb[ASSM_HS];
     for (int s = 0; s < ASSM_HS; ++s) {
@@ -169,7 +177,7 @@ __device__ void bwd_w1(const AssmBwd& a, int blk) {
         }
         __syncthreads();
         for (int c = 0; c < n; ++c) {
-            const float dsc = dscore(a, g, st, coff, c);
+            const float dsc = dscore(a, pred_g(a, g, b), st, coff, c);
             for (int j = 0; j < k; ++j) {
                 const int r = roff + c * k + j;
                 float d[ASSM_HS];
@@ -199,7 +207,7 @@ __device__ void bwd_rows(const AssmBwd& a, int p) {
     const int32_t* m = a.meta + (size_t)p * META;
     const int n = m[0], k = m[1], b = m[3], coff = m[4], roff = m[5];
     const float* st = a.stat + (size_t)p * 4;
-    const float g = a.dloss[0];
+    const float g = pred_g(a, base_g(a), b);
     const float* zb = a.z + (size_t)b * a.ldz;
     for (int h = t; h < H; h += ASSM_THREADS) {
         float u = 0.f;
@@ -238,7 +246,7 @@ __device__ void bwd_wa(const AssmBwd& a, int blk) {
     // dWa[:, h] for ASSM_HS hidden units, summed over the predictions in order (and, in workgroup 0, dba = 0)
     const int t = threadIdx.x, H = a.H, L = a.L;
     const int h0 = blk * ASSM_HS;
-    const float g = a.dloss[0];
+    const float g = base_g(a);
     for (int l = t; l < L; l += ASSM_THREADS) {
         float acc[ASSM_HS];
         for (int s = 0; s < ASSM_HS; ++s) acc[s] = 0.f;
@@ -247,7 +255,7 @@ __device__ void bwd_wa(const AssmBwd& a, int blk) {
             const float* st = a.stat + (size_t)p * 4;
             const float zl = a.z[(size_t)m[3] * a.ldz + l];
             for (int s = 0; s < ASSM_HS; ++s)
-                if (h0 + s < H) acc[s] += du_of(a, g, m, st, h0 + s) * zl;
+                if (h0 + s < H) acc[s] += du_of(a, pred_g(a, g, m[3]), m, st, h0 + s) * zl;
         }
         for (int s = 0; s < ASSM_HS; ++s)
             if (h0 + s < H) a.dWa[(size_t)l * H + h0 + s] = acc[s];
@@ -259,7 +267,7 @@ __device__ void bwd_z(const AssmBwd& a, int b) {
     // dz[b] = sum over the predictions of molecule b (in order) of Wa du_p  (ds0_p = 0: no ba term)
     __shared__ float du[ASSM_MAX_H];
     const int t = threadIdx.x, H = a.H, L = a.L;
-    const float g = a.dloss[0];
+    const float g = pred_g(a, base_g(a), b);
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     for (int p = 0; p < a.P; ++p) {
         const int32_t* m = a.meta + (size_t)p * META;
@@ -319,7 +327,27 @@ extern "C" int ggpm_motif_assm_backward(const float* dloss, const float* rows, i
         return GGPM_ERR_ARG;
     const int nb = ggpm_ceil_div(H, ASSM_HS);
     AssmBwd a{dloss, rows, ld_rows, meta, P, C, H, L, B, W1, ldw, Wa, ba, z, ldz, act, score, stat,
-              drows, dW1, db1, dWa, dba, dz, nb, nb};
+              drows, dW1, db1, dWa, dba, dz, nb, nb, nullptr, 0};
+    hipLaunchKernelGGL(motif_assm_bwd_k, dim3(2 * nb + P + B), dim3(ASSM_THREADS), 0, (hipStream_t)stream, a);
+    GGPM_CHECK_LAUNCH();
+    return GGPM_OK;
+}
+
+// ggpm_motif_assm_backward with a per-molecule upstream gradient: a prediction of molecule b = meta[p][3] is weighted by
+// dloss[0] * coef[b * coef_stride] (dloss nullable: 1).  Same device code; coef = null is not accepted here.
+extern "C" int ggpm_motif_assm_backward_weighted(const float* dloss, const float* coef, int coef_stride, const float* rows,
+                                                 int ld_rows, const int32_t* meta, int P, int C, int H, int L, int B,
+                                                 const float* W1, int ldw, const float* Wa, const float* ba, const float* z,
+                                                 int ldz, const float* act, const float* score, const float* stat,
+                                                 float* drows, float* dW1, float* db1, float* dWa, float* dba, float* dz,
+                                                 ggpm_stream_t stream) {
+    GGPM_CLEAR_STALE_ERROR();
+    if (!dims_ok(P, C, H, L, ldw) || B <= 0 || ld_rows < H || ldz < L || !coef || coef_stride < 1 || !rows || !meta || !W1 ||
+        !Wa || !ba || !z || !act || !score || !stat || !drows || !dW1 || !db1 || !dWa || !dba || !dz)
+        return GGPM_ERR_ARG;
+    const int nb = ggpm_ceil_div(H, ASSM_HS);
+    AssmBwd a{dloss, rows, ld_rows, meta, P, C, H, L, B, W1, ldw, Wa, ba, z, ldz, act, score, stat,
+              drows, dW1, db1, dWa, dba, dz, nb, nb, coef, coef_stride};
     hipLaunchKernelGGL(motif_assm_bwd_k, dim3(2 * nb + P + B), dim3(ASSM_THREADS), 0, (hipStream_t)stream, a);
     GGPM_CHECK_LAUNCH();
     return GGPM_OK;

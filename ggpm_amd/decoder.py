@@ -16,6 +16,7 @@ from __future__ import annotations
 
 from typing import Dict, List, Optional, Sequence, Tuple
 
+import contextlib
 import os
 import weakref
 
@@ -668,33 +669,45 @@ class HierMPNDecoder(ScoreHeads):
     def _batched_schedule(self, schedule) -> bool:
         return bool(_dev.DECODER_BATCHED and schedule.plan["all_live"] and schedule.plan["E1"] > 1)
 
-    def atom_level(self, schedule, tensors):
-        """The atom level of one teacher-forced pass, forward only -> (pooled cluster vectors, candidate atom vectors), or
-        None where this schedule's atom level runs inside the step loop.  Teacher forcing makes it independent of the
-        latent vectors (``start_atom_level``), so ``molecule_losses(..., atom=)`` takes it for any number of latent draws
-        of the same batch.  Nothing is kept on the decoder."""
+    def atom_level(self, schedule, tensors, record_grad: bool = False):
+        """The atom level of one teacher-forced pass -> (pooled cluster vectors, candidate atom vectors), or None where this
+        schedule's atom level runs inside the step loop.  Teacher forcing makes it independent of the latent vectors
+        (``start_atom_level``), so ``molecule_losses(..., atom=)`` takes it for any number of latent draws of the same
+        batch.  Forward only, or with ``record_grad`` as the autograd node ``forward`` makes (under the caller's grad mode):
+        autograd then adds the gradients of every pass that read the pair before the level's backward runs, once.  Nothing
+        is kept on the decoder."""
         tree_tensors, graph_tensors = tensors
         if not (self._batched_schedule(schedule) and _dev.ATOM_DECODE):
             return None
         if not schedule.atom_plan(graph_tensors[0].size(0), graph_tensors[1].size(0)).ok:
             return None
-        with torch.no_grad():
+        with contextlib.nullcontext() if record_grad else torch.no_grad():
             D = schedule.to_device(tree_tensors[0].device)._dev
             pooled_all, cand, _ = self._atom_level(schedule, D, graph_tensors)
         return pooled_all, cand
 
     def molecule_losses(self, mols, src_mol_vecs, graphs, tensors, orders, schedule: Optional[DecodeSchedule] = None,
                         max_cls_size: Optional[int] = None, atom=None, out: Optional[torch.Tensor] = None):
-        """The per-molecule form of what ``forward`` sums, forward only -> [B, 4]: per molecule the sum of its rows'
-        topology BCE, motif-class CE, attachment-class CE and attachment CE (``forward``'s loss is their total / B).
+        """The per-molecule form of what ``forward`` sums -> [B, 4]: per molecule the sum of its rows' topology BCE,
+        motif-class CE, attachment-class CE and attachment CE (``forward``'s loss is their total / B).
         ``max_cls_size``: the number of rows every attachment prediction is padded to (the reference pads to the batch's
         largest cluster x 2 with zero candidates, which score ``b_assm . z``): None takes the batch's own, an int pins it.
-        ``atom``: the result of ``atom_level`` for this schedule; ``out``: a contiguous fp32 [B, 4] tensor to write."""
+        ``atom``: the result of ``atom_level`` for this schedule; ``out``: a contiguous fp32 [B, 4] tensor to write.
+        Forward only unless autograd records -- gradients enabled and a latent vector or ``atom`` requiring them: then the
+        same values are the output of ONE node (heads_fused._HeadsParts) whose backward takes ``dparts [B, 4]``, behind the
+        nodes of ``W_root`` and the two tree-side levels (``out`` is not taken then)."""
         from . import heads_fused
         src_root_vecs, src_tree_vecs, src_graph_vecs = src_mol_vecs
         if src_tree_vecs is not src_graph_vecs:
             raise NotImplementedError("HierMPNDecoder.molecule_losses: one context vector per molecule for all four heads "
                                       "(src_tree_vecs is src_graph_vecs), as the VAEs pass it")
+        record = torch.is_grad_enabled() and any(v is not None and v.requires_grad for v in tuple(src_mol_vecs) + tuple(atom or ()))
+        if record and out is not None:
+            raise ValueError("HierMPNDecoder.molecule_losses: out= is for the forward-only form (autograd records this call)")
+        if record and not heads_fused.usable(self):
+            raise NotImplementedError("HierMPNDecoder.molecule_losses: the differentiable form runs the heads as one node, which "
+                                      "needs deferred, publishable parameter gradients (GGPM_DEFER_WGRADS on, every head "
+                                      "parameter a hook-free leaf that requires grad, ggpm_amd._dev.HEADS_COMPOSITE on)")
         if self.training and any(isinstance(m, nn.Dropout) and m.p > 0 for m in self.modules()):
             raise NotImplementedError("HierMPNDecoder.molecule_losses runs without dropout: call model.eval() first")
         tree_tensors, graph_tensors = tensors
@@ -709,7 +722,7 @@ class HierMPNDecoder(ScoreHeads):
         if not (_dev.ATOM_DECODE and schedule.atom_plan(graph_tensors[0].size(0), graph_tensors[1].size(0)).ok):
             raise NotImplementedError("HierMPNDecoder.molecule_losses: this batch's atom level runs step by step (no "
                                       "AtomPlan, or ggpm_amd._dev.ATOM_DECODE off), which has no per-molecule form")
-        with torch.no_grad():
+        with contextlib.nullcontext() if record else torch.no_grad():
             D = schedule.to_device(dev)._dev
             if L == H:
                 init_vecs = src_root_vecs
@@ -731,6 +744,8 @@ class HierMPNDecoder(ScoreHeads):
             ok = lambda v: v.dim() == 2 and v.stride(1) == 1 and v.stride(0) % 4 == 0
             tv = topo_vecs if ok(topo_vecs) else topo_vecs.contiguous()
             cv = cls_vecs if ok(cls_vecs) else cls_vecs.contiguous()
+            if record:
+                return heads_fused.heads_parts(self, dict(spec, assm_pred_mol=pred_mol), src_tree_vecs, tv, cv, cand)
             rows = {}
             heads_fused._heads_forward(self, spec, src_tree_vecs, tv, cv, cand, infer=True, rows_out=rows)
             n_c = rows["cls"].numel()

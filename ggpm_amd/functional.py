@@ -141,6 +141,65 @@ def iwae_finish(parts: torch.Tensor, logpq: torch.Tensor, kl: torch.Tensor):
     return elbo, iwae
 
 
+BOUND_OBJECTIVES = {"elbo": 0, "iwae": 1}       # include/ggpm_hip.h GGPM_BOUND_ELBO / GGPM_BOUND_IWAE
+
+
+def bound_objective(parts: torch.Tensor, logpq: torch.Tensor, kl: torch.Tensor, w: Optional[torch.Tensor], objective: str,
+                    beta: float):
+    """parts [K, B, 4], logpq [K, B], kl [B], w [B] or None -> (loss [1], c_nll [K, B], c_logpq [K, B], c_kl [B]): the
+    weighted K-sample ELBO / IWAE loss and its partial derivatives by nll, logpq and kl (csrc/mol_loss.hip)"""
+    _need_gpu(parts, logpq, kl)
+    K, B = logpq.shape
+    if parts.shape != (K, B, 4) or kl.shape != (B,) or (w is not None and (w.shape != (B,) or w.dtype != torch.float32)):
+        raise ValueError("bound_objective: parts %s / kl %s / w %s for logpq %s"
+                         % (tuple(parts.shape), tuple(kl.shape), None if w is None else tuple(w.shape), (K, B)))
+    if objective not in BOUND_OBJECTIVES:
+        raise ValueError("bound_objective: objective %r (one of %s)" % (objective, sorted(BOUND_OBJECTIVES)))
+    parts, logpq, kl = parts.contiguous(), logpq.contiguous(), kl.contiguous()
+    w = w.contiguous() if w is not None else None
+    f32 = dict(dtype=torch.float32, device=parts.device)
+    loss, c_nll, c_logpq, c_kl = torch.empty(1, **f32), torch.empty(K, B, **f32), torch.empty(K, B, **f32), torch.empty(B, **f32)
+    work = torch.empty(B, dtype=torch.float64, device=parts.device)
+    _lib.check(_lib.load().ggpm_bound_objective(_p(parts), _p(logpq), _p(kl), _p(w), K, B, BOUND_OBJECTIVES[objective],
+                                                float(beta), _p(work), _p(loss), _p(c_nll), _p(c_logpq), _p(c_kl), _stream()),
+               "bound_objective")
+    return loss, c_nll, c_logpq, c_kl
+
+
+def scale_rows_by_mol(d: torch.Tensor, N: int, mol: torch.Tensor, coef: torch.Tensor, B: int,
+                      g: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """d[m, 0:N] *= g[0] * coef[mol[m]] in place (csrc/mol_loss.hip); a row of no molecule in [0, B) becomes 0.  ``d`` fp32
+    [M, ld >= N] or [M] with unit column stride, ``mol`` int32 [M], ``coef`` fp32 [B] (any stride, e.g. a column of [B, 4])."""
+    _need_gpu(d, mol, coef)
+    M = d.shape[0]
+    ld = 1 if d.dim() == 1 else d.stride(0)
+    if d.dtype != torch.float32 or (d.dim() == 2 and d.stride(1) != 1 and d.shape[1] > 1) or (d.dim() == 1 and M > 1 and d.stride(0) != 1):
+        raise ValueError("scale_rows_by_mol: d must be fp32 rows with unit column stride")
+    if mol.dtype != torch.int32 or not mol.is_contiguous() or mol.numel() < M or coef.dtype != torch.float32 or coef.shape != (B,):
+        raise ValueError("scale_rows_by_mol: a contiguous int32 molecule per row and %d fp32 coefficients" % B)
+    _lib.check(_lib.load().ggpm_scale_rows_by_mol(_p(d), ld, M, N, _p(mol), _p(coef), max(coef.stride(0), 1), B, _p(g),
+                                                  _stream()), "scale_rows_by_mol")
+    return d
+
+
+def latent_terms_backward(dz: Optional[torch.Tensor], mean: torch.Tensor, pre_var: torch.Tensor, eps: torch.Tensor,
+                          c_logpq: Optional[torch.Tensor], c_kl: Optional[torch.Tensor], g: Optional[torch.Tensor] = None):
+    """The backward of ``latent_terms``: dz [K, B, L], the gradients that reached logpq [K, B] and kl [B] (each None for
+    zeros) -> (dmean [B, L], dpre_var [B, L]) (csrc/mol_loss.hip)"""
+    _need_gpu(mean, pre_var, eps)
+    K, B, L = eps.shape
+    cont = lambda t: t.contiguous() if t is not None else None
+    dz, c_logpq, c_kl = cont(dz), cont(c_logpq), cont(c_kl)
+    if mean.shape != (B, L) or pre_var.shape != (B, L) or (dz is not None and dz.shape != (K, B, L)) or \
+            (c_logpq is not None and c_logpq.shape != (K, B)) or (c_kl is not None and c_kl.shape != (B,)):
+        raise ValueError("latent_terms_backward: shapes do not fit eps %s" % ((K, B, L),))
+    mean, pre_var, eps = mean.contiguous(), pre_var.contiguous(), eps.contiguous()
+    dmean, dpv = torch.empty_like(mean), torch.empty_like(pre_var)
+    _lib.check(_lib.load().ggpm_latent_terms_backward(_p(dz), _p(mean), _p(pre_var), _p(eps), _p(c_logpq), _p(c_kl), _p(g), K, B,
+                                                      L, _p(dmean), _p(dpv), _stream()), "latent_terms_backward")
+    return dmean, dpv
+
+
 def padded_hidden(H: int) -> int:
     return (H + 15) // 16 * 16
 

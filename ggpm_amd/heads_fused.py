@@ -200,67 +200,118 @@ class _Heads(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dloss, _dacc):
         lib = _lib.load()
-        heads, spec, S = ctx.heads, ctx.spec, ctx.saved_
-        H, L, B, P, C = ctx.dims
+        S = ctx.saved_
         if S is None:       # released below: the loss gradients are also scaled in place, a second pass would scale them again
             raise F_.second_backward("score heads")
         ctx.saved_ = None
         if dloss is None:
             return (None,) * len(ctx.needs_input_grad)
-        dev = dloss.device
-        f32 = dict(dtype=torch.float32, device=dev)
         g = dloss.reshape(1).to(torch.float32).contiguous()
 
-        def scale(d, N):
+        def scale(d, N, term):
             _lib.check(lib.ggpm_scale_rows(F_._p(d), d.shape[1], d.shape[0], N, F_._p(g), F_._stream()), "scale_rows")
             return d
 
-        # ---- topology head
-        n_t = S["dx_t"].numel()
-        ds_t = torch.zeros(n_t, S["ld_st"], **f32)
-        ds_t[:, 0] = S["dx_t"] * g
-        dtopo_x, dcxt_t = _mlp_backward(heads.topoNN, S["topo_x"], S["cxt_t"], S["h_t"], ds_t, H, L, None, False)
-        dz = _scatter_context(dcxt_t, spec["topo_idx"], B, L, spec.get("idx_csr", {}).get("topo"))
-        # ---- class heads (both read the same rows: one input gradient, two scatters into the same context rows)
-        dcls_x, dcxt_c = _mlp_backward(heads.clsNN, S["cls_x"], S["cxt_c"], S["h_c"],
-                                       scale(S["d_c"], heads.clsNN[3].weight.shape[0]), H, L, None, False)
-        dcls_x, dcxt_i = _mlp_backward(heads.iclsNN, S["cls_x"], S["cxt_c"], S["h_i"],
-                                       scale(S["d_i"], heads.iclsNN[3].weight.shape[0]), H, L, dcls_x, True)
-        dz = dz + _scatter_context(dcxt_c.add_(dcxt_i), spec["cls_idx"], B, L, spec.get("idx_csr", {}).get("cls"))
-        # ---- attachment head
-        dcand = None
-        if P > 0:
-            Hp, He = F_.padded_hidden(H), heads.embed_size
-            d_a = scale(S["d_a"], C).reshape(P * C, 1)
-            proj, cxt_a, buf = S["proj"], S["cxt_a"], S["buf"]
-            dproj = torch.zeros_like(proj)
-            dproj[:, :L] = d_a * cxt_a[:, :L]
-            dcxt_a = torch.zeros_like(cxt_a)
-            dcxt_a[:, :L] = d_a * proj[:, :L]
-            dz = dz + _scatter_context(dcxt_a, spec["assm_idx"], B, L, spec.get("idx_csr", {}).get("assm"))
-            wa = heads.W_assm
-            dbuf = torch.empty(P * C, Hp, **f32)
-            F_.gemm(0, 0, P * C, H, L, dproj, F_._ld(dproj), wa.weight, wa.weight.stride(0), dbuf, Hp, Hp)
-            F_._defer_linear(wa.weight, wa.bias, dproj, [buf], (H,))
-            l1 = heads.matchNN[0]
-            ldw = l1.weight.stride(0)
-            cand = S["cand"]
-            dcand = torch.zeros(cand.shape[0], F_._ld(cand), **f32)[:, :cand.shape[1]] if ctx.needs_input_grad[5] else None
-            for b, (rows, emb, order, v) in zip(spec["assm_blocks"], S["keep"]):
-                dvs = dbuf.index_select(0, b.dest)
-                dv = dvs if b.k == 1 else dvs.unsqueeze(1).expand(-1, b.k, -1).reshape(-1, Hp)
-                dpre = torch.empty(b.n, Hp, **f32)
-                _lib.check(lib.ggpm_act_backward(F_._p(dv), F_._p(v), b.n, H, Hp, RELU, 0, F_._p(dpre), F_._stream()), "act_backward")
-                if dcand is not None:
-                    drows = dcand[b.base:b.base + b.n]
-                    F_.gemm(0, 0, b.n, H, H, dpre, Hp, l1.weight, ldw, drows, F_._ld(drows), drows.shape[1])
-                demb = torch.empty_like(emb)
-                F_.gemm(0, 0, b.n, He, H, dpre, Hp, l1.weight[:, H:], ldw, demb, F_._ld(demb), emb.shape[1])
-                F_._defer_gather(heads.E_assm[0].weight, He, demb, b.icls32)
-                F_._defer_linear(l1.weight, l1.bias, dpre, [rows, emb, order], (H, He, MAX_POS))
-        n_params = len(ctx.needs_input_grad) - 6
-        return (None, None, dz if ctx.needs_input_grad[2] else None, dtopo_x if ctx.needs_input_grad[3] else None,
-                dcls_x if ctx.needs_input_grad[4] else None, dcand) + (None,) * n_params
+        return _heads_backward(ctx.heads, ctx.spec, S, ctx.dims, ctx.needs_input_grad, scale, S["dx_t"] * g)
+
+
+def _heads_backward(heads, spec, S, dims, needs, scale, dx_t):
+    """The backward of the heads' one node behind the chain rule of its loss gradients: ``scale(d, N, term)`` -> the
+    gradient by the scores of 'cls' / 'icls' / 'assm' from the one the loss kernel left for an upstream gradient of 1 (in
+    place), ``dx_t`` the same for the topology scores.  -> the gradients of (heads, spec, z, topo_x, cls_x, cand, *params)."""
+    lib = _lib.load()
+    H, L, B, P, C = dims
+    f32 = dict(dtype=torch.float32, device=dx_t.device)
+    # ---- topology head
+    n_t = S["dx_t"].numel()
+    ds_t = torch.zeros(n_t, S["ld_st"], **f32)
+    ds_t[:, 0] = dx_t
+    dtopo_x, dcxt_t = _mlp_backward(heads.topoNN, S["topo_x"], S["cxt_t"], S["h_t"], ds_t, H, L, None, False)
+    dz = _scatter_context(dcxt_t, spec["topo_idx"], B, L, spec.get("idx_csr", {}).get("topo"))
+    # ---- class heads (both read the same rows: one input gradient, two scatters into the same context rows)
+    dcls_x, dcxt_c = _mlp_backward(heads.clsNN, S["cls_x"], S["cxt_c"], S["h_c"],
+                                   scale(S["d_c"], heads.clsNN[3].weight.shape[0], "cls"), H, L, None, False)
+    dcls_x, dcxt_i = _mlp_backward(heads.iclsNN, S["cls_x"], S["cxt_c"], S["h_i"],
+                                   scale(S["d_i"], heads.iclsNN[3].weight.shape[0], "icls"), H, L, dcls_x, True)
+    dz = dz + _scatter_context(dcxt_c.add_(dcxt_i), spec["cls_idx"], B, L, spec.get("idx_csr", {}).get("cls"))
+    # ---- attachment head
+    dcand = None
+    if P > 0:
+        Hp, He = F_.padded_hidden(H), heads.embed_size
+        d_a = scale(S["d_a"], C, "assm").reshape(P * C, 1)
+        proj, cxt_a, buf = S["proj"], S["cxt_a"], S["buf"]
+        dproj = torch.zeros_like(proj)
+        dproj[:, :L] = d_a * cxt_a[:, :L]
+        dcxt_a = torch.zeros_like(cxt_a)
+        dcxt_a[:, :L] = d_a * proj[:, :L]
+        dz = dz + _scatter_context(dcxt_a, spec["assm_idx"], B, L, spec.get("idx_csr", {}).get("assm"))
+        wa = heads.W_assm
+        dbuf = torch.empty(P * C, Hp, **f32)
+        F_.gemm(0, 0, P * C, H, L, dproj, F_._ld(dproj), wa.weight, wa.weight.stride(0), dbuf, Hp, Hp)
+        F_._defer_linear(wa.weight, wa.bias, dproj, [buf], (H,))
+        l1 = heads.matchNN[0]
+        ldw = l1.weight.stride(0)
+        cand = S["cand"]
+        dcand = torch.zeros(cand.shape[0], F_._ld(cand), **f32)[:, :cand.shape[1]] if needs[5] else None
+        for b, (rows, emb, order, v) in zip(spec["assm_blocks"], S["keep"]):
+            dvs = dbuf.index_select(0, b.dest)
+            dv = dvs if b.k == 1 else dvs.unsqueeze(1).expand(-1, b.k, -1).reshape(-1, Hp)
+            dpre = torch.empty(b.n, Hp, **f32)
+            _lib.check(lib.ggpm_act_backward(F_._p(dv), F_._p(v), b.n, H, Hp, RELU, 0, F_._p(dpre), F_._stream()), "act_backward")
+            if dcand is not None:
+                drows = dcand[b.base:b.base + b.n]
+                F_.gemm(0, 0, b.n, H, H, dpre, Hp, l1.weight, ldw, drows, F_._ld(drows), drows.shape[1])
+            demb = torch.empty_like(emb)
+            F_.gemm(0, 0, b.n, He, H, dpre, Hp, l1.weight[:, H:], ldw, demb, F_._ld(demb), emb.shape[1])
+            F_._defer_gather(heads.E_assm[0].weight, He, demb, b.icls32)
+            F_._defer_linear(l1.weight, l1.bias, dpre, [rows, emb, order], (H, He, MAX_POS))
+    n_params = len(needs) - 6
+    return (None, None, dz if needs[2] else None, dtopo_x if needs[3] else None,
+            dcls_x if needs[4] else None, dcand) + (None,) * n_params
+
+
+class _HeadsParts(torch.autograd.Function):
+    """``_Heads`` with the per-molecule sums of the row losses as its output (``molecule_losses`` where autograd records):
+    the same forward launches, then ggpm_mol_loss_parts; the backward takes ``dparts [B, 4]`` and weighs every row's loss
+    gradient with its molecule's entry (ggpm_scale_rows_by_mol) where ``_Heads`` multiplies by one scalar."""
+
+    @staticmethod
+    def forward(ctx, heads, spec: dict, z, topo_x, cls_x, cand, *params):
+        """``spec`` as for _Heads plus 'assm_pred_mol' (the molecule of every attachment prediction)"""
+        rows = {}
+        _, _, saved, dims = _heads_forward(heads, spec, z, topo_x, cls_x, cand, infer=False, rows_out=rows)
+        B, P = dims[2], dims[3]
+        n_c = rows["cls"].numel()
+        parts = F_.mol_loss_parts([(rows["topo"], spec["topo_idx"], rows["topo"].numel()),
+                                   (rows["cls"], spec["cls_idx"], n_c), (rows["icls"], spec["cls_idx"], n_c),
+                                   (rows["assm"], spec["assm_pred_mol"], P) if P > 0 else None], B)
+        ctx.heads, ctx.spec, ctx.saved_, ctx.dims = heads, spec, saved, dims
+        ctx.set_materialize_grads(False)
+        return parts
+
+    @staticmethod
+    def backward(ctx, dparts):
+        S, spec = ctx.saved_, ctx.spec
+        if S is None:
+            raise F_.second_backward("score heads (per molecule)")
+        ctx.saved_ = None
+        if dparts is None:
+            return (None,) * len(ctx.needs_input_grad)
+        B = ctx.dims[2]
+        dparts = dparts.to(torch.float32).contiguous()
+        mol = {"cls": spec["cls_idx"], "icls": spec["cls_idx"], "assm": spec["assm_pred_mol"]}
+        col = {"topo": 0, "cls": 1, "icls": 2, "assm": 3}
+
+        def scale(d, N, term):
+            return F_.scale_rows_by_mol(d, N, mol[term], dparts[:, col[term]], B)
+
+        dx_t = F_.scale_rows_by_mol(S["dx_t"], 1, spec["topo_idx"], dparts[:, 0], B)
+        return _heads_backward(ctx.heads, spec, S, ctx.dims, ctx.needs_input_grad, scale, dx_t)
+
+
+def heads_parts(heads, spec: dict, z, topo_x, cls_x, cand):
+    """-> parts [B, 4], differentiable: the per-molecule sums of the four heads' row losses as the output of one node"""
+    return _HeadsParts.apply(heads, spec, z, topo_x, cls_x, cand, *heads_parameters(heads))
 
 
 def usable(heads) -> bool:

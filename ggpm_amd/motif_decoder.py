@@ -18,6 +18,7 @@ derives it (its atom plan is simply not used).  Device work:
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Optional
 
 import numpy as np
@@ -73,6 +74,93 @@ class _MotifAssm(torch.autograd.Function):
             F_._p(ba), F_._p(z), z.stride(0), F_._p(act), F_._p(score), F_._p(stat), F_._p(drows), F_._p(dW1), F_._p(db1),
             F_._p(dWa), F_._p(dba), F_._p(dz), F_._stream()), "motif_assm_backward")
         return drows, dz, dW1, db1, dWa, dba, None, None, None, None
+
+
+class _MotifParts(torch.autograd.Function):
+    """The four losses of one teacher-forced pass per molecule, parts [B, 4], as ONE node over the heads' scores
+    (``molecule_losses`` where autograd records): the loss kernels of ``forward`` with their row losses kept, the attachment
+    head's launch and ggpm_mol_loss_parts.  The backward takes ``dparts [B, 4]``: every row's loss gradient is weighed with
+    its molecule's entry (ggpm_scale_rows_by_mol, ggpm_motif_assm_backward_weighted)."""
+
+    @staticmethod
+    def forward(ctx, topo_scores, cls_scores, icls_scores, rows, z, W1, b1, Wa, ba, spec: dict):
+        """``spec``: topo_y fp32, topo_mol / cls_mol int32, clab / ilab int32, mask, B, and with attachment predictions
+        meta, pred_mol, P, C, n_cand (``rows`` .. ``ba`` are None without)."""
+        from . import _lib
+        lib = _lib.load()
+        dev, B = topo_scores.device, spec["B"]
+        f32 = dict(dtype=torch.float32, device=dev)
+        x = topo_scores.contiguous()
+        loss = torch.empty(1, **f32)
+        topo_rows, dx = torch.empty_like(x), torch.empty_like(x)
+        _lib.check(lib.ggpm_bce_logits(F_._p(x), F_._p(spec["topo_y"]), x.numel(), F_._p(loss), F_._p(dx), F_._p(topo_rows),
+                                       F_._stream()), "bce_logits")
+
+        def ce(s, labels, mask=None, mask_row=None):
+            M, N = s.shape
+            r, d = torch.empty(M, **f32), torch.empty(M, F_._ld(s), **f32)
+            if d.shape[1] > N:
+                d[:, N:].zero_()
+            _lib.check(lib.ggpm_softmax_ce(F_._p(s), F_._ld(s), M, N, F_._p(mask), 0 if mask is None else F_._ld(mask),
+                                           F_._p(mask_row), F_._p(labels), F_._p(loss), F_._p(d), d.shape[1], None, F_._p(r),
+                                           F_._stream()), "softmax_ce")
+            return r, d
+
+        cls_rows, d_c = ce(cls_scores, spec["clab"])
+        icls_rows, d_i = ce(icls_scores, spec["ilab"], spec["mask"], spec["clab"])
+        assm, P = None, spec.get("P", 0)
+        ctx.assm = None
+        if P > 0:
+            H = W1.shape[0]
+            z, rows = z.contiguous(), rows.contiguous()
+            act, score = torch.empty(rows.shape[0], H, **f32), torch.empty(max(spec["n_cand"], 1), **f32)
+            stat, res = torch.empty(P, 4, **f32), torch.empty(2, **f32)
+            counter = torch.zeros(1, dtype=torch.int32, device=dev)
+            _lib.check(lib.ggpm_motif_assm_forward(
+                F_._p(rows), rows.stride(0), F_._p(spec["meta"]), P, spec["C"], H, Wa.shape[0], F_._p(W1), W1.stride(0),
+                F_._p(b1), F_._p(Wa), F_._p(ba), F_._p(z), z.stride(0), F_._p(act), F_._p(score), F_._p(stat), F_._p(res),
+                F_._p(counter), F_._stream()), "motif_assm_forward")
+            assm = (stat.view(-1)[2:], spec["pred_mol"], P, 4)
+            ctx.assm = (rows, z, W1, Wa, ba, act, score, stat)
+        n_c = cls_rows.numel()
+        parts = F_.mol_loss_parts([(topo_rows, spec["topo_mol"], topo_rows.numel()), (cls_rows, spec["cls_mol"], n_c),
+                                   (icls_rows, spec["cls_mol"], n_c), assm], B)
+        ctx.spec, ctx.grads = spec, (dx, d_c, d_i)
+        ctx.widths = (cls_scores.shape[1], icls_scores.shape[1])
+        ctx.set_materialize_grads(False)
+        return parts
+
+    @staticmethod
+    def backward(ctx, dparts):
+        from . import _lib
+        if ctx.grads is None:       # released below: the loss gradients are scaled in place
+            raise F_.second_backward("tree-only decoder losses (per molecule)")
+        (dx, d_c, d_i), ctx.grads = ctx.grads, None
+        assm, ctx.assm = ctx.assm, None
+        if dparts is None:
+            return (None,) * 10
+        spec = ctx.spec
+        B = spec["B"]
+        dparts = dparts.to(torch.float32).contiguous()
+        F_.scale_rows_by_mol(dx, 1, spec["topo_mol"], dparts[:, 0], B)
+        F_.scale_rows_by_mol(d_c, ctx.widths[0], spec["cls_mol"], dparts[:, 1], B)
+        F_.scale_rows_by_mol(d_i, ctx.widths[1], spec["cls_mol"], dparts[:, 2], B)
+        out = [dx, d_c[:, :ctx.widths[0]], d_i[:, :ctx.widths[1]]] + [None] * 7
+        if assm is not None:
+            rows, z, W1, Wa, ba, act, score, stat = assm
+            H, L, P = W1.shape[0], Wa.shape[0], spec["P"]
+            drows, dz = torch.zeros_like(rows), torch.zeros_like(z)
+            dW1 = torch.empty(H, H + MAX_POS, dtype=torch.float32, device=rows.device)
+            db1 = torch.empty(H, dtype=torch.float32, device=rows.device)
+            dWa, dba = torch.empty_like(Wa), torch.empty_like(ba)
+            coef = dparts[:, 3]
+            _lib.check(_lib.load().ggpm_motif_assm_backward_weighted(
+                None, F_._p(coef), max(coef.stride(0), 1), F_._p(rows), rows.stride(0), F_._p(spec["meta"]), P, spec["C"], H, L,
+                B, F_._p(W1), W1.stride(0), F_._p(Wa), F_._p(ba), F_._p(z), z.stride(0), F_._p(act), F_._p(score), F_._p(stat),
+                F_._p(drows), F_._p(dW1), F_._p(db1), F_._p(dWa), F_._p(dba), F_._p(dz), F_._stream()),
+                "motif_assm_backward_weighted")
+            out[3:9] = [drows, dz, dW1, db1, dWa, dba]
+        return tuple(out)
 
 
 class AssmPlan:
@@ -183,13 +271,18 @@ class MotifDecoder(ScoreHeads):
 
     def molecule_losses(self, mols, src_mol_vecs, graphs, tensors, orders, schedule: Optional[DecodeSchedule] = None,
                         max_cls_size: Optional[int] = None, atom=None, out: Optional[torch.Tensor] = None):
-        """The per-molecule form of what ``forward`` sums, forward only -> [B, 4]: per molecule the sum of its rows'
-        topology BCE, motif-class CE, attachment-class CE and attachment CE (``forward``'s loss is their total / B).
+        """The per-molecule form of what ``forward`` sums -> [B, 4]: per molecule the sum of its rows' topology BCE,
+        motif-class CE, attachment-class CE and attachment CE (``forward``'s loss is their total / B).
         ``max_cls_size``: the number of rows every attachment prediction is padded to (the reference pads to the batch's
         largest cluster x 2 with zero candidates, which score ``b_assm . z``): None takes the batch's own, an int pins it.
         ``atom`` is HierMPNDecoder's argument (this decoder has no atom level: None); ``out``: a contiguous fp32 [B, 4]
-        tensor to write."""
+        tensor to write.  Forward only unless autograd records -- gradients enabled and a latent vector requiring them:
+        then the same values are the output of ONE node over the heads' scores (_MotifParts) whose backward takes
+        ``dparts [B, 4]`` (``out`` is not taken then)."""
         from . import _lib
+        record = torch.is_grad_enabled() and any(v is not None and v.requires_grad for v in src_mol_vecs)
+        if record and out is not None:
+            raise ValueError("MotifDecoder.molecule_losses: out= is for the forward-only form (autograd records this call)")
         if self.training and any(isinstance(m, nn.Dropout) and m.p > 0 for m in self.modules()):
             raise NotImplementedError("MotifDecoder.molecule_losses runs without dropout: call model.eval() first")
         tree_tensors, graph_tensors = tensors
@@ -199,7 +292,7 @@ class MotifDecoder(ScoreHeads):
             schedule = DecodeSchedule.from_graphs(graphs, tensors, orders, self.vocab)
         C = _pinned_cls_size(schedule, max_cls_size)
         src_root_vecs, src_tree_vecs, src_graph_vecs = src_mol_vecs
-        with torch.no_grad():
+        with contextlib.nullcontext() if record else torch.no_grad():
             D = schedule.to_device(dev)._dev
             if L == H:
                 init_vecs = src_root_vecs
@@ -210,6 +303,8 @@ class MotifDecoder(ScoreHeads):
             else:
                 topo_vecs, cls_vecs = self._states_stepwise(schedule, tree_tensors, graph_tensors, init_vecs)
             topo_scores = self.get_topo_score(src_tree_vecs, D["topo_batch32"], topo_vecs)
+            if record:
+                return self._parts_node(schedule, D, C, B, src_tree_vecs, src_graph_vecs, topo_scores, cls_vecs)
             topo_rows = bce_rows(topo_scores, _memo(D, "topo_label_f32", lambda: D["topo_label"].to(torch.float32)))
             clab = _memo(D, "cls_clab32", lambda: D["cls_clab"].to(torch.int32).contiguous())
             ilab = _memo(D, "cls_ilab32", lambda: D["cls_ilab"].to(torch.int32).contiguous())
@@ -239,6 +334,28 @@ class MotifDecoder(ScoreHeads):
             n_c = cls_rows.numel()
             return F_.mol_loss_parts([(topo_rows, D["topo_batch32"], topo_rows.numel()), (cls_rows, D["cls_batch32"], n_c),
                                       (icls_rows, D["cls_batch32"], n_c), assm], B, out=out)
+
+    def _parts_node(self, schedule, D, C, B, src_tree_vecs, src_graph_vecs, topo_scores, cls_vecs):
+        """The differentiable tail of ``molecule_losses``: the class heads' scores, the attachment head's inputs, _MotifParts"""
+        dev = topo_scores.device
+        clab = _memo(D, "cls_clab32", lambda: D["cls_clab"].to(torch.int32).contiguous())
+        ilab = _memo(D, "cls_ilab32", lambda: D["cls_ilab"].to(torch.int32).contiguous())
+        parts = self._parts(src_tree_vecs, D["cls_batch32"], cls_vecs)
+        cls_scores, icls_scores = _mlp(self.clsNN, *parts), _mlp(self.iclsNN, *parts)
+        vocab = self.vocab
+        i32 = lambda t: t if (t.dtype == torch.int32 and t.is_contiguous()) else t.to(torch.int32).contiguous()
+        spec = dict(B=B, topo_y=_memo(D, "topo_label_f32", lambda: D["topo_label"].to(torch.float32)),
+                    topo_mol=i32(D["topo_batch32"]), cls_mol=i32(D["cls_batch32"]), clab=clab, ilab=ilab,
+                    mask=vocab.mask_on(dev) if hasattr(vocab, "mask_on") else vocab.mask.to(dev))
+        ap = assm_plan(schedule)
+        if ap.P == 0:
+            return _MotifParts.apply(topo_scores, cls_scores, icls_scores, None, None, None, None, None, None, spec)
+        meta, ids = ap.to_device(dev)
+        spec.update(meta=meta, pred_mol=_memo(D, "motif_assm_mol32", lambda: meta[:, 3].contiguous()), P=ap.P, C=C,
+                    n_cand=ap.n_cand)
+        l1, wa = self.matchNN[0], self.W_assm
+        return _MotifParts.apply(topo_scores, cls_scores, icls_scores, IE._embedding_rows(self.E_assm, ids), src_graph_vecs,
+                                 l1.weight, l1.bias, wa.weight, wa.bias, spec)
 
     def assm_head(self, schedule: DecodeSchedule, src_graph_vecs):
         """(attachment loss sum, accuracy) -- enum_attach, get_assm_score, the cross entropy over max_cls_size rows and

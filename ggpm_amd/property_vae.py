@@ -89,34 +89,124 @@ class _KLHead(torch.autograd.Function):
         dmean, dpv = torch.empty_like(mean), torch.empty_like(pv)
         _lib.check(_lib.load().ggpm_rsample_backward(F_._p(mean), F_._p(pv), F_._p(ctx.eps), F_._p(dz), F_._p(dkl), B, L,
                                                      F_._p(dmean), F_._p(dpv), F_._stream()), "rsample_backward")
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(z_vecs)
-            F_.gemm_ksegments(0, B, H, [dmean, dpv], [L, L], [Wm, Wv], [Wm.stride(0), Wv.stride(0)], [L, L], dx,
-                              F_._ld(dx), z_vecs.shape[1])
+        return _latent_heads_backward(ctx, z_vecs, Wm, Wv, dmean, dpv) + (None,)
 
-        pWm, pbm, pWv, pbv = ctx.params
 
-        def param_grads():
-            dWm, dWv = torch.empty_like(Wm), torch.empty_like(Wv)
-            F_.gemm_grouped(1, 0, L, H, B, [
-                dict(A=dmean, lda=L, B=z_vecs, ldb=F_._ld(z_vecs), C=dWm, ldc=dWm.stride(0), n_pad=H),
-                dict(A=dpv, lda=L, B=z_vecs, ldb=F_._ld(z_vecs), C=dWv, ldc=dWv.stride(0), n_pad=H)])
-            return dWm, F_.colsum(dmean, B, L), dWv, F_.colsum(dpv, B, L)
+def _latent_heads_backward(ctx, z_vecs, Wm, Wv, dmean, dpv):
+    """(dmean, dpre_var) -> the gradients of (z_vecs, Wm, bm, Wv, bv): one launch for d(z_vecs) (two K segments), one grouped
+    launch for the two weight gradients (second stream, straight into ``.grad``, where they can be published).
+    ``ctx.params``: the four Parameter objects."""
+    B, (L, H) = z_vecs.shape[0], Wm.shape
+    dx = None
+    if ctx.needs_input_grad[0]:
+        dx = torch.empty_like(z_vecs)
+        F_.gemm_ksegments(0, B, H, [dmean, dpv], [L, L], [Wm, Wv], [Wm.stride(0), Wv.stride(0)], [L, L], dx,
+                          F_._ld(dx), z_vecs.shape[1])
 
-        if F_.side_stream_enabled() and F_.can_publish(*ctx.params) and all(ctx.needs_input_grad[1:5]):
-            main = torch.cuda.current_stream()
-            side = F_._side_stream(z_vecs.device)
-            side.wait_stream(main)
-            for t in (dmean, dpv, z_vecs):
-                t.record_stream(side)
-            with torch.cuda.stream(side):
-                for q, g in zip(ctx.params, param_grads()):
-                    F_._accumulate_grad(q, g, main)
-            F_._join_later(main, side)
-            return dx, None, None, None, None, None
-        dWm, dbm, dWv, dbv = param_grads()
-        return dx, dWm, dbm, dWv, dbv, None
+    def param_grads():
+        dWm, dWv = torch.empty_like(Wm), torch.empty_like(Wv)
+        F_.gemm_grouped(1, 0, L, H, B, [
+            dict(A=dmean, lda=L, B=z_vecs, ldb=F_._ld(z_vecs), C=dWm, ldc=dWm.stride(0), n_pad=H),
+            dict(A=dpv, lda=L, B=z_vecs, ldb=F_._ld(z_vecs), C=dWv, ldc=dWv.stride(0), n_pad=H)])
+        return dWm, F_.colsum(dmean, B, L), dWv, F_.colsum(dpv, B, L)
+
+    if F_.side_stream_enabled() and F_.can_publish(*ctx.params) and all(ctx.needs_input_grad[1:5]):
+        main = torch.cuda.current_stream()
+        side = F_._side_stream(z_vecs.device)
+        side.wait_stream(main)
+        for t in (dmean, dpv, z_vecs):
+            t.record_stream(side)
+        with torch.cuda.stream(side):
+            for q, g in zip(ctx.params, param_grads()):
+                F_._accumulate_grad(q, g, main)
+        F_._join_later(main, side)
+        return dx, None, None, None, None
+    dWm, dbm, dWv, dbv = param_grads()
+    return dx, dWm, dbm, dWv, dbv
+
+
+class _LatentTerms(torch.autograd.Function):
+    """_KLHead for K draws per molecule: (z_vecs, R_mean, R_var, eps [K, B, L]) -> (z [K, B, L], kl [B], logpq [K, B]) --
+    ``_latent_heads`` and ggpm_latent_terms, the launches of ``log_likelihood`` -- and on the way back
+    ggpm_latent_terms_backward (the K gradients of z, of logpq and of kl summed in a fixed order), then _KLHead's tail."""
+
+    @staticmethod
+    def forward(ctx, z_vecs, Wm, bm, Wv, bv, eps):
+        mean, pv = _latent_heads(z_vecs, Wm, bm, Wv, bv)
+        z, kl, logpq = F_.latent_terms(mean, pv, eps)
+        ctx.save_for_backward(z_vecs, Wm, Wv, mean, pv, eps)
+        ctx.params = (Wm, bm, Wv, bv)
+        ctx.set_materialize_grads(False)
+        return z, kl, logpq
+
+    @staticmethod
+    def backward(ctx, dz, dkl, dlogpq):
+        z_vecs, Wm, Wv, mean, pv, eps = ctx.saved_tensors
+        dmean, dpv = F_.latent_terms_backward(dz, mean, pv, eps, dlogpq, dkl)
+        return _latent_heads_backward(ctx, z_vecs, Wm, Wv, dmean, dpv) + (None,)
+
+
+class _BoundObjective(torch.autograd.Function):
+    """(parts [K, B, 4], logpq [K, B], kl [B]) -> the weighted K-sample ELBO / IWAE loss (ggpm_bound_objective, which also
+    leaves the loss's partial derivatives); the backward hands them on, times the upstream gradient.  It is the first node
+    of the pass, so it also arranges that the pass adds into gradients that are already there ONCE (_add_pass_once)."""
+
+    @staticmethod
+    def forward(ctx, parts, logpq, kl, w, objective, beta, params):
+        loss, c_nll, c_logpq, c_kl = F_.bound_objective(parts, logpq, kl, w, objective, beta)
+        ctx.coef = (c_nll, c_logpq, c_kl)
+        ctx.params = params
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        if ctx.coef is None:
+            raise F_.second_backward("bound objective")
+        (c_nll, c_logpq, c_kl), ctx.coef = ctx.coef, None
+        _add_pass_once(ctx.params)
+        g = dloss.reshape(()).to(torch.float32)
+        return (c_nll * g).unsqueeze(-1).expand(-1, -1, 4), c_logpq * g, c_kl * g, None, None, None, None
+
+
+_SET_ASIDE = []         # (parameter, the gradient it held) of the pass in flight
+
+
+def _add_pass_once(params) -> None:
+    """Called from the first node of a backward pass.  A parameter used in several places (tied embeddings; the encoder's
+    gradient through autograd, the decoder's through the deferred queue) receives one addition into ``.grad`` per use, so a
+    gradient that is already there would be rounded once per use.  Here the gradients that are there are set aside, the pass
+    forms its own total exactly as a pass on fresh gradients does, and the last callback of the pass -- behind the deferred
+    flush, the atom level's tail and the stream joins -- adds that total to what was there, once: accumulation costs one
+    fp32 rounding per element, and ``.grad`` stays the tensor it was.  Not where gradients are formed inside a flat buffer
+    (parallel.FlatGradSync, the encoder's gradient sink): setting ``.grad`` aside would let the pass overwrite it there, so
+    those keep the one-addition-per-use form."""
+    from . import parallel
+    main = torch.cuda.current_stream()
+
+    def add_once():
+        held, _SET_ASIDE[:] = list(_SET_ASIDE), []
+        base, new = [], []
+        for p, b in held:
+            if p.grad is not None:
+                base.append(b)
+                new.append(p.grad)
+            p.grad = b
+        if base:
+            with torch.cuda.stream(main):
+                torch._foreach_add_(base, new)
+
+    if _SET_ASIDE:          # a pass that raised never ran its callbacks: what it set aside goes back first
+        add_once()
+    held = [(p, p.grad) for p in params if p.grad is not None]
+    if not held or any(id(p) in parallel._GRAD_SLOTS for p, _ in held):
+        return
+    for p, _ in held:
+        p.grad = None
+    _SET_ASIDE.extend(held)
+    engine = torch.autograd.Variable._execution_engine
+
+    # queued from inside a callback: behind every callback the nodes of this pass queue
+    engine.queue_callback(lambda: engine.queue_callback(add_once))
 
 
 def rsample(z_vecs, W_mean: nn.Linear, W_var: nn.Linear, perturb: bool = True, z_width=None):
@@ -258,6 +348,12 @@ class HierPropertyVAE(nn.Module):
         """Per-molecule reconstruction terms, KL, ELBO and the ``n_samples``-sample importance-weighted bound of ``batch``
         (the tuple ``self(*batch)`` takes) -> :class:`MolLikelihood`; forward only, see :func:`log_likelihood`."""
         return log_likelihood(self, batch, n_samples, seed, sample_ids, eps, max_cls_size, schedule)
+
+    def bound_loss(self, batch, n_samples=1, objective="elbo", beta=1.0, mol_weights=None, seed=None, sample_ids=None,
+                   eps=None, max_cls_size=None, schedule=None):
+        """The ``n_samples``-sample ELBO (``objective="elbo"``) or importance-weighted bound (``"iwae"``) of ``batch`` as a
+        loss to train on, with optional per-molecule weights -> (loss, :class:`MolObjective`); see :func:`bound_loss`."""
+        return bound_loss(self, batch, n_samples, objective, beta, mol_weights, seed, sample_ids, eps, max_cls_size, schedule)
 
     def reconstruct(self, batch, args=None):
         """reference ggpm/property_vae.py:39-45: the no-grad encoder, the mean latent, greedy decode of 150 steps ->
@@ -420,6 +516,12 @@ class HierPropOptVAE(_ClipNegativeLoss, nn.Module):
         (the tuple ``self(*batch)`` takes) -> :class:`MolLikelihood`; forward only, see :func:`log_likelihood`."""
         return log_likelihood(self, batch, n_samples, seed, sample_ids, eps, max_cls_size, schedule)
 
+    def bound_loss(self, batch, n_samples=1, objective="elbo", beta=1.0, mol_weights=None, seed=None, sample_ids=None,
+                   eps=None, max_cls_size=None, schedule=None):
+        """The ``n_samples``-sample ELBO (``objective="elbo"``) or importance-weighted bound (``"iwae"``) of ``batch`` as a
+        loss to train on, with optional per-molecule weights -> (loss, :class:`MolObjective`); see :func:`bound_loss`."""
+        return bound_loss(self, batch, n_samples, objective, beta, mol_weights, seed, sample_ids, eps, max_cls_size, schedule)
+
     def reconstruct(self, batch, args=None):
         """reference ggpm/property_vae.py:169-188: the no-grad encoder, the mean latent, the property heads on it, greedy
         decode of 150 steps -> ((homo [B], lumo [B]), (results, molecules)).  The graph batch: ``args.graph_batch_factory``,
@@ -502,6 +604,36 @@ def _sample(model, batch_size, greedy, seed, max_decode_step, beam, graph_batch_
                                   graph_batch_factory=factory)
 
 
+def _likelihood_args(model, what, batch, n_samples, sample_ids, eps, max_cls_size, schedule):
+    """The argument checks ``log_likelihood`` and ``bound_loss`` share (``what``: the method's name in the messages) ->
+    (class name, decoder, device, K, B, L, schedule, pinned max_cls_size, hierarchical decoder?)"""
+    from .decoder import HierMPNDecoder, _pinned_cls_size
+    name, dec = type(model).__name__, model.decoder
+    if any(m.training and isinstance(m, nn.Dropout) and m.p > 0 for m in model.modules()):
+        raise NotImplementedError("%s.%s runs without dropout: call model.eval() first" % (name, what))
+    graphs, tensors, orders = batch[1], batch[2], batch[3]
+    B, L = len(orders), model.R_mean.weight.shape[0]
+    dev = model.R_mean.weight.device
+    K = n_samples
+    if isinstance(K, bool) or int(K) != K or not 1 <= int(K) <= F_.LIKELIHOOD_MAX_K:
+        raise ValueError("%s.%s: n_samples %r (1 .. %d)" % (name, what, n_samples, F_.LIKELIHOOD_MAX_K))
+    K = int(K)
+    if eps is not None:
+        if not isinstance(eps, torch.Tensor) or eps.dtype != torch.float32 or eps.device != dev:
+            raise ValueError("%s.%s: eps must be a float32 tensor on %s" % (name, what, dev))
+        if tuple(eps.shape) != (K, B, L):
+            raise ValueError("%s.%s: eps of shape %s for n_samples %d, %d molecules and latent width %d"
+                             % (name, what, tuple(eps.shape), K, B, L))
+    if sample_ids is not None and len(sample_ids) != B:
+        raise ValueError("%s.%s: %d sample_ids for %d molecules" % (name, what, len(sample_ids), B))
+    schedule = _motif_schedule(model, graphs, tensors, orders, schedule)
+    if schedule is None:
+        raise ValueError("%s.%s: the batch carries no graphs (batch[1]) and no schedule= was given: nothing to "
+                         "derive the decoder's bookkeeping from" % (name, what))
+    C = _pinned_cls_size(schedule, max_cls_size)
+    return name, dec, dev, K, B, L, schedule, C, isinstance(dec, HierMPNDecoder)
+
+
 MolLikelihood = namedtuple("MolLikelihood", ["parts", "kl", "elbo", "iwae", "z", "stats"])
 MolLikelihood.__doc__ = """What ``log_likelihood`` returns: fp32 device tensors (none requires grad, nothing is synchronised)
 for K samples, B molecules and latent width L.
@@ -525,32 +657,10 @@ def log_likelihood(model, batch, n_samples=1, seed=None, sample_ids=None, eps=No
     K-sample call's.  ``eps=`` (a fp32 [K, B, L] tensor on the model's device, ``n_samples`` = K) replaces the stream; all
     zeros with K = 1 is the ``perturb_z=False`` latent.  ``max_cls_size``: see ``molecule_losses`` -- None is the training
     convention (the parts then add up to the training loss x B), an int makes numbers comparable across batches."""
-    from .decoder import HierMPNDecoder, _pinned_cls_size
     from .greedy_decode import split_seed
-    name, dec = type(model).__name__, model.decoder
-    if any(m.training and isinstance(m, nn.Dropout) and m.p > 0 for m in model.modules()):
-        raise NotImplementedError("%s.log_likelihood runs without dropout: call model.eval() first" % name)
+    name, dec, dev, K, B, L, schedule, C, hier = _likelihood_args(model, "log_likelihood", batch, n_samples, sample_ids, eps,
+                                                                  max_cls_size, schedule)
     mols, graphs, tensors, orders = batch[0], batch[1], batch[2], batch[3]
-    B, L = len(orders), model.R_mean.weight.shape[0]
-    dev = model.R_mean.weight.device
-    K = n_samples
-    if isinstance(K, bool) or int(K) != K or not 1 <= int(K) <= F_.LIKELIHOOD_MAX_K:
-        raise ValueError("%s.log_likelihood: n_samples %r (1 .. %d)" % (name, n_samples, F_.LIKELIHOOD_MAX_K))
-    K = int(K)
-    if eps is not None:
-        if not isinstance(eps, torch.Tensor) or eps.dtype != torch.float32 or eps.device != dev:
-            raise ValueError("%s.log_likelihood: eps must be a float32 tensor on %s" % (name, dev))
-        if tuple(eps.shape) != (K, B, L):
-            raise ValueError("%s.log_likelihood: eps of shape %s for n_samples %d, %d molecules and latent width %d"
-                             % (name, tuple(eps.shape), K, B, L))
-    if sample_ids is not None and len(sample_ids) != B:
-        raise ValueError("%s.log_likelihood: %d sample_ids for %d molecules" % (name, len(sample_ids), B))
-    schedule = _motif_schedule(model, graphs, tensors, orders, schedule)
-    if schedule is None:
-        raise ValueError("%s.log_likelihood: the batch carries no graphs (batch[1]) and no schedule= was given: nothing to "
-                         "derive the decoder's bookkeeping from" % name)
-    C = _pinned_cls_size(schedule, max_cls_size)
-    hier = isinstance(dec, HierMPNDecoder)
     stats = dict(encoder_calls=0, atom_level_calls=0, decoder_passes=0)
     with torch.no_grad():
         tree_tensors, graph_tensors = tensors = make_cuda(tensors)
@@ -580,6 +690,76 @@ def log_likelihood(model, batch, n_samples=1, seed=None, sample_ids=None, eps=No
             stats["decoder_passes"] += 1
         elbo, iwae = F_.iwae_finish(parts, logpq, kl)
     return MolLikelihood(parts, kl, elbo, iwae, z, stats)
+
+
+MolObjective = namedtuple("MolObjective", ["parts", "kl", "elbo", "iwae", "z", "weights", "stats"])
+MolObjective.__doc__ = """The second value of ``bound_loss``: detached fp32 device tensors, the fields of :class:`MolLikelihood` (bit for
+bit what ``log_likelihood`` returns for the same draws) plus ``weights [B]``, the molecule weights used (ones for None)."""
+
+
+def bound_loss(model, batch, n_samples=1, objective="elbo", beta=1.0, mol_weights=None, seed=None, sample_ids=None, eps=None,
+               max_cls_size=None, schedule=None):
+    """``bound_loss`` of the four VAEs (*Training on the bound*) -> (loss, :class:`MolObjective`).
+
+    With ``nll``, ``kl``, ``logpq`` and ``iwae`` as ``log_likelihood`` forms them, w the molecule weights and K = n_samples:
+      objective="elbo":  loss = (1/B) sum_i w_i ((1/K) sum_k nll[k, i] + beta kl[i])
+      objective="iwae":  loss = -(1/B) sum_i w_i iwae[i]                                    (beta must be 1.0)
+    ``loss`` is a 0-dim tensor autograd differentiates: the reparameterised gradient through the decoder, through
+    z_k = mean + exp(lv / 2) eps_k, through the lv and z terms of logpq and through kl, to every encoder, latent-head and
+    decoder parameter (the property heads and LossWeigh of the -opt models take no part).  ``mol_weights``: None or B
+    floats (a host sequence or a float32 tensor on the model's device), a constant.  Every other argument is
+    ``log_likelihood``'s.  One encoder pass and one atom-level pass serve the K decoder passes, forward and backward."""
+    from .greedy_decode import split_seed
+    name, dec, dev, K, B, L, schedule, C, hier = _likelihood_args(model, "bound_loss", batch, n_samples, sample_ids, eps,
+                                                                  max_cls_size, schedule)
+    if objective not in F_.BOUND_OBJECTIVES:
+        raise ValueError("%s.bound_loss: objective %r (one of %s)" % (name, objective, sorted(F_.BOUND_OBJECTIVES)))
+    beta = float(beta)
+    if objective == "iwae" and beta != 1.0:
+        raise ValueError("%s.bound_loss: the importance-weighted bound has no beta (got %r): pass beta=1.0" % (name, beta))
+    w = None
+    if mol_weights is not None:
+        if isinstance(mol_weights, torch.Tensor):
+            if mol_weights.dtype != torch.float32 or mol_weights.device != dev:
+                raise ValueError("%s.bound_loss: mol_weights must be a float32 tensor on %s (or a host sequence)" % (name, dev))
+            w = mol_weights.detach()
+        else:
+            w = torch.as_tensor([float(v) for v in mol_weights], dtype=torch.float32).to(dev)
+        if tuple(w.shape) != (B,):
+            raise ValueError("%s.bound_loss: %d mol_weights for %d molecules" % (name, w.numel(), B))
+    mols, graphs, tensors, orders = batch[0], batch[1], batch[2], batch[3]
+    stats = dict(encoder_calls=0, atom_level_calls=0, decoder_passes=0)
+    with torch.enable_grad():
+        tree_tensors, graph_tensors = tensors = make_cuda(tensors)
+        atom = None
+        if hier:
+            atom = dec.atom_level(schedule, tensors, record_grad=True)
+            if atom is None:
+                raise NotImplementedError("%s.bound_loss: this batch runs the decoder's step loop (no tree message at all, "
+                                          "no AtomPlan, or a batched form switched off in ggpm_amd._dev), which has no "
+                                          "per-molecule form" % name)
+            stats["atom_level_calls"] = 1
+            root_vecs = model.encoder.forward_padded(tree_tensors, graph_tensors)[0]
+        else:
+            root_vecs = model.encoder.forward_padded(tree_tensors)[0]
+        stats["encoder_calls"] = 1
+        if eps is None:
+            lo, hi = split_seed(seed)
+            eps = F_.sample_latent_normal(K, B, L, lo, hi, ids=sample_ids, device=dev)
+        Rm, Rv = model.R_mean, model.R_var
+        z, kl, logpq = _LatentTerms.apply(root_vecs, Rm.weight, Rm.bias, Rv.weight, Rv.bias, eps.detach())
+        parts = []
+        for k in range(K):
+            zk = z[k]
+            parts.append(dec.molecule_losses(mols, (zk, zk, zk), graphs, tensors, orders, schedule=schedule, max_cls_size=C,
+                                             atom=atom))
+            stats["decoder_passes"] += 1
+        parts = torch.stack(parts, dim=0)
+        loss = _BoundObjective.apply(parts, logpq, kl, w, objective, beta, tuple(model.parameters()))
+    with torch.no_grad():
+        elbo, iwae = F_.iwae_finish(parts.detach(), logpq.detach(), kl.detach())
+    ones = w if w is not None else torch.ones(B, dtype=torch.float32, device=dev)
+    return loss, MolObjective(parts.detach(), kl.detach(), elbo, iwae, z.detach(), ones, stats)
 
 
 def _graph_batch_factory(model, args):
@@ -644,6 +824,12 @@ class PropertyVAE(nn.Module):
         """Per-molecule reconstruction terms, KL, ELBO and the ``n_samples``-sample importance-weighted bound of ``batch``
         (the tuple ``self(*batch)`` takes) -> :class:`MolLikelihood`; forward only, see :func:`log_likelihood`."""
         return log_likelihood(self, batch, n_samples, seed, sample_ids, eps, max_cls_size, schedule)
+
+    def bound_loss(self, batch, n_samples=1, objective="elbo", beta=1.0, mol_weights=None, seed=None, sample_ids=None,
+                   eps=None, max_cls_size=None, schedule=None):
+        """The ``n_samples``-sample ELBO (``objective="elbo"``) or importance-weighted bound (``"iwae"``) of ``batch`` as a
+        loss to train on, with optional per-molecule weights -> (loss, :class:`MolObjective`); see :func:`bound_loss`."""
+        return bound_loss(self, batch, n_samples, objective, beta, mol_weights, seed, sample_ids, eps, max_cls_size, schedule)
 
     def reconstruct(self, batch, args=None):
         """reference ggpm/property_vae.py:101-109: the no-grad encoder, the mean latent, greedy decode of 150 steps ->
@@ -725,6 +911,12 @@ class PropOptVAE(_ClipNegativeLoss, nn.Module):
         """Per-molecule reconstruction terms, KL, ELBO and the ``n_samples``-sample importance-weighted bound of ``batch``
         (the tuple ``self(*batch)`` takes) -> :class:`MolLikelihood`; forward only, see :func:`log_likelihood`."""
         return log_likelihood(self, batch, n_samples, seed, sample_ids, eps, max_cls_size, schedule)
+
+    def bound_loss(self, batch, n_samples=1, objective="elbo", beta=1.0, mol_weights=None, seed=None, sample_ids=None,
+                   eps=None, max_cls_size=None, schedule=None):
+        """The ``n_samples``-sample ELBO (``objective="elbo"``) or importance-weighted bound (``"iwae"``) of ``batch`` as a
+        loss to train on, with optional per-molecule weights -> (loss, :class:`MolObjective`); see :func:`bound_loss`."""
+        return bound_loss(self, batch, n_samples, objective, beta, mol_weights, seed, sample_ids, eps, max_cls_size, schedule)
 
     def reconstruct(self, batch, args=None):
         """reference ggpm/property_vae.py:299-318: the no-grad encoder, the mean latent, the property heads on it, greedy

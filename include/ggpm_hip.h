@@ -656,6 +656,14 @@ int ggpm_motif_assm_backward(const float* dloss, const float* rows, int ld_rows,
                              int L, int B, const float* W1, int ldw, const float* Wa, const float* ba, const float* z,
                              int ldz, const float* act, const float* score, const float* stat, float* drows, float* dW1,
                              float* db1, float* dWa, float* dba, float* dz, ggpm_stream_t stream);
+/* ggpm_motif_assm_backward for a per-molecule upstream gradient (bound_loss): prediction p counts with
+ * dloss[0] * coef[meta[p][3] * coef_stride] (dloss nullable: 1; a molecule outside [0, B): 0).  Same device code and the same
+ * outputs; coef must not be null, coef_stride >= 1. */
+int ggpm_motif_assm_backward_weighted(const float* dloss, const float* coef, int coef_stride, const float* rows, int ld_rows,
+                                      const int32_t* meta, int P, int C, int H, int L, int B, const float* W1, int ldw,
+                                      const float* Wa, const float* ba, const float* z, int ldz, const float* act,
+                                      const float* score, const float* stat, float* drows, float* dW1, float* db1, float* dWa,
+                                      float* dba, float* dz, ggpm_stream_t stream);
 
 /* Greedy decode of the tree-only decoder (MotifDecoder.decode, ggpm/decoder.py:901-1095; csrc/motif_decode.hip).
  * ggpm_motif_decode_tree_step (two launches): applies the edits -- n_node_edits pairs {node, motif} to fnode [N], then
@@ -791,6 +799,35 @@ int ggpm_latent_terms(const float* mean, const float* pre_var, const float* eps,
                       float* logpq, ggpm_stream_t stream);
 int ggpm_iwae_finish(const float* parts, const float* logpq, const float* kl, int K, int B, float* elbo, float* iwae,
                      ggpm_stream_t stream);
+
+/* Training on the bound (bound_loss of the four VAEs; csrc/mol_loss.hip): the same conventions as the entries above.
+ * ggpm_bound_objective (two launches): with nll, kl, logpq as above and w (nullable: all ones) the molecules' weights,
+ *     GGPM_BOUND_ELBO: loss = (1/B) sum_b w_b ((1/K) sum_k nll[k, b] + beta kl[b])
+ *                      c_nll[k, b] = w_b / (K B), c_logpq = 0, c_kl[b] = beta w_b / B
+ *     GGPM_BOUND_IWAE: loss = -(1/B) sum_b w_b (logsumexp_k (logpq - nll)[k, b] - log K)            (beta must be 1)
+ *                      c_nll[k, b] = w_b softmax_k(logpq - nll)[k, b] / B, c_logpq = -c_nll, c_kl = 0
+ * c_* are the partial derivatives of loss by nll, logpq and kl; the softmax is formed in fp64 with the maximum subtracted.
+ * work: B doubles (the molecules' addends, summed in molecule order by one wave and rounded once).
+ * ggpm_scale_rows_by_mol (one launch): d[m, 0:N] *= g[0] * coef[mol[m] * coef_stride] for the M rows of d (row stride
+ * ld >= N; g nullable: 1); a row whose molecule is outside [0, B) becomes 0, as ggpm_mol_loss_parts counts it nowhere.
+ * ggpm_latent_terms_backward (one launch): with G[k, b] = g[0] c_logpq[k, b], a = dz[k, b, j] - G z[k, b, j], gk = g[0] c_kl[b],
+ *     dmean[b, j] = sum_k a + gk mean
+ *     dlv[b, j]   = sum_k (a exp(lv / 2) eps[k, b, j] / 2 + G / 2) - gk (1 - exp(lv)) / 2
+ *     dpre_var    = -sign(pre_var) dlv                                     (0 at pre_var = 0, as ggpm_rsample_backward)
+ * dz is the gradient that reached z (not scaled by g); dz, c_logpq, c_kl and g are nullable (zeros, zeros, zeros, 1).  The
+ * sum over k is formed in fp64 in a fixed order.
+ * A null required pointer, a size <= 0, K outside its range, ld < N, a stride < 1, an unknown objective or beta != 1 with
+ * GGPM_BOUND_IWAE returns GGPM_ERR_ARG; nothing is launched then. */
+#define GGPM_BOUND_ELBO 0
+#define GGPM_BOUND_IWAE 1
+int ggpm_bound_objective(const float* parts, const float* logpq, const float* kl, const float* w, int K, int B, int objective,
+                         float beta, double* work, float* loss, float* c_nll, float* c_logpq, float* c_kl,
+                         ggpm_stream_t stream);
+int ggpm_scale_rows_by_mol(float* d, int ld, int M, int N, const int32_t* mol, const float* coef, int coef_stride, int B,
+                           const float* g, ggpm_stream_t stream);
+int ggpm_latent_terms_backward(const float* dz, const float* mean, const float* pre_var, const float* eps,
+                               const float* c_logpq, const float* c_kl, const float* g, int K, int B, int L, float* dmean,
+                               float* dpre_var, ggpm_stream_t stream);
 
 /* ------------------------------------------------------------------ whole-encoder drivers
  * HierMPNEncoder.forward (ggpm/encoder.py:140-157, with embed_graph/inter/tree/root :96-138) and its backward as ONE
