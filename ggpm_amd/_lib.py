@@ -22,11 +22,13 @@ SIGNATURES = {
     "ggpm_error_string": (c_char_p, [I]),
     "ggpm_padded_hidden": (I, [I]),
     "ggpm_padded_to_csr": (I, [P, I, I, P, P, P]),
+    "ggpm_padded_to_csr_pair": (I, [P, I, I, P, P, P, I, I, P, P, P]),
     "ggpm_csr_transpose": (I, [P, P, I, I, P, P, P, P]),
     "ggpm_extract_column": (I, [P, I, I, I, P, P]),
     "ggpm_gemm_workspace_bytes": (c_size_t, [I, I, I]),
     "ggpm_gemm": (I, [I, I, I, I, I, P, I, P, I, P, I, I, P, I, I, I, P, c_size_t, P]),
     "ggpm_gemm_grouped": (I, [I, I, I, I, I, I, P, P]),                   # problems: ggpm_gemm_problem[count]
+    "ggpm_gemm_grouped_masked": (I, [I, I, I, I, I, I, P, P, P]),         # + epilogues: ggpm_gemm_epilogue[count]
     "ggpm_gemm_grouped_splitk_workspace_bytes": (c_size_t, [I, I, I, I]),
     "ggpm_gemm_grouped_splitk": (I, [I, I, I, I, I, I, P, P, c_size_t, P]),
     "ggpm_gemm_ksegments": (I, [I, I, I, I, P, P, P, P, P, P, I, I, P, I, I, I, P]),
@@ -35,6 +37,7 @@ SIGNATURES = {
     "ggpm_colsum": (I, [P, I, I, I, P, P, P]),
     "ggpm_act_backward": (I, [P, P, I, I, I, I, I, P, P]),
     "ggpm_segment_sum": (I, [P, I, P, P, I, I, P, I, I, I, P]),
+    "ggpm_segment_sum_masked": (I, [I, P, I, P, P, I, I, P, I, P, I, I, P, P, I, I, I, P]),
     "ggpm_gather_rows": (I, [P, I, P, I, I, P, I, I, I, P]),
     "ggpm_scatter_rows": (I, [P, I, P, I, I, P, I, I, P]),
     "ggpm_adam_step": (I, [P, P, P, P, c_size_t, c_float, c_float, c_float, c_float, c_float, I, P]),

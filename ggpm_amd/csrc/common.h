@@ -93,6 +93,16 @@ __device__ __forceinline__ float4 operator+(float4 a, float4 b) {
 __device__ __forceinline__ float4 operator*(float4 a, float4 b) {
     return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w);
 }
+// g * act'(y) from the activation OUTPUT o (ggpm_act_backward and every epilogue that fuses it: one expression, one rounding)
+__device__ __forceinline__ float ggpm_act_grad(float g, float o, int act) {
+    switch (act) {
+        case GGPM_ACT_RELU: g = o > 0.f ? g : 0.f; break;
+        case GGPM_ACT_TANH: g = g * (1.f - o * o); break;
+        case GGPM_ACT_SIGMOID: g = g * o * (1.f - o); break;
+        default: break;
+    }
+    return g;
+}
 __device__ __forceinline__ float4 ggpm_sigmoid4(float4 a) {
     return make_float4(ggpm_sigmoid(a.x), ggpm_sigmoid(a.y), ggpm_sigmoid(a.z), ggpm_sigmoid(a.w));
 }

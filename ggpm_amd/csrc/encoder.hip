@@ -475,8 +475,8 @@ static int encoder_forward_impl(const ggpm_enc_dims* dims, float* const* params,
         if (!ev_in) return GGPM_ERR_LAUNCH;
         (void)hipEventRecord(ev_in, s);              // the caller's index tensors are ready from here on
     }
-    CK(ggpm_padded_to_csr(gbgraph, d.E1g, d.Kgb, S.gpred.rowptr, S.gpred.col, stream));
-    CK(ggpm_padded_to_csr(gagraph, d.N1g, d.Kga, S.gagr.rowptr, S.gagr.col, stream));
+    CK(ggpm_padded_to_csr_pair(gbgraph, d.E1g, d.Kgb, S.gpred.rowptr, S.gpred.col, gagraph, d.N1g, d.Kga, S.gagr.rowptr,
+                               S.gagr.col, stream));
     hipEvent_t ev_atom = nullptr, ev_tree = nullptr;
     if (side_stream) {
         ev_atom = ggpm_wgrad_event(54);
@@ -590,7 +590,7 @@ namespace {
 
 struct BwdWork {
     float *dpre_root, *df, *dn, *d_hnode_t, *d_nei_t, *dpre, *d_h, *dX, *dx_mess, *d_finput, *d_hinter, *d_hnode_i,
-        *d_nei_i, *d_pooled, *d_hatom, *d_nei_g, *level_work, *skws, *csws;
+        *d_nei_i, *d_pooled, *d_nei_g, *level_work, *skws, *csws;
     size_t level_work_bytes, skws_bytes;
     // per level: split-K slabs and column-sum scratch of its input-half weight gradients (level_backward's x_part runs on
     // either stream, beside the other levels' parts: nothing shared)
@@ -614,7 +614,7 @@ void layout_work(Arena& A, const Dims& d, BwdWork& w) {
     w.d_hinter = A.take<float>((size_t)d.N1t * Hp);
     w.d_hnode_i = A.take<float>((size_t)d.N1t * Hp); w.d_nei_i = A.take<float>((size_t)d.N1t * Hp);
     w.d_pooled = A.take<float>((size_t)d.N1t * Hp);
-    w.d_hatom = A.take<float>((size_t)d.N1g * Hp); w.d_nei_g = A.take<float>((size_t)d.N1g * Hp);
+    w.d_nei_g = A.take<float>((size_t)d.N1g * Hp);
     size_t lw = d.lstm ? ggpm_lstm_backward_workspace_bytes(d.E1g, d.H, d.depthG)
                        : ggpm_gru_backward_workspace_bytes(d.E1g, d.H, d.depthG);
     const size_t lwt = d.lstm ? ggpm_lstm_backward_workspace_bytes(d.E1t, d.H, d.depthT)
@@ -679,6 +679,33 @@ int linear2_dx(int M, int H, int K1, const float* dpre, int ldp, const float* W,
     CK(ggpm_gemm(0, 0, M, K1, H, dpre, ldp, W, ldw, d1, ld1, ld1, nullptr, acc1, GGPM_ACT_NONE, 0, nullptr, 0, s));
     CK(ggpm_gemm(0, 0, M, H, H, dpre, ldp, W + K1, ldw, d2, ld2, ld2, nullptr, acc2, GGPM_ACT_NONE, 0, nullptr, 0, s));
     return GGPM_OK;
+}
+
+// linear2_dx with d2 finished in the same launch: d2 = dpre W2 + add2 (add2 null: the product alone) and, on the way out,
+// dmask = act'(ymask) d2 with row 0 zeroed (ggpm_act_backward(d2, ymask, ..., act, 1)).  Same values as copying add2 into
+// d2, linear2_dx(..., acc2 = 1) and the mask launch: the epilogue adds add2[m, n] where it would add d2[m, n].  Where the
+// small-tile kernel does not take the group (unaligned operands, K1 != H), exactly those launches are issued.
+int linear2_dx_masked(int M, int H, int K1, const float* dpre, int ldp, const float* W, float* d1, int ld1, float* d2,
+                      int ld2, const float* add2, const float* ymask, int act, float* dmask, ggpm_stream_t s) {
+    const int ldw = K1 + H;
+    if (K1 == H) {
+        const GgpmGemmProblem gp[2] = {{dpre, ldp, W, ldw, d1, ld1, ld1, nullptr, 0, GGPM_ACT_NONE, 0},
+                                       {dpre, ldp, W + K1, ldw, d2, ld2, ld2, nullptr, add2 ? 1 : 0, GGPM_ACT_NONE, 0}};
+        const ggpm_gemm_epilogue ep[2] = {{nullptr, 0, nullptr, nullptr, 0, 0, 0}, {add2, ld2, ymask, dmask, ld2, act, 1}};
+        const int rc = ggpm_gemm_grouped_masked(0, 0, M, H, H, 2, gp, ep, s);
+        if (rc != GGPM_ERR_UNSUPPORTED) return rc;
+    }
+    if (add2) (void)hipMemcpyAsync(d2, add2, (size_t)M * ld2 * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)s);
+    CK(linear2_dx(M, H, K1, dpre, ldp, W, d1, ld1, 0, d2, ld2, add2 ? 1 : 0, s));
+    return ggpm_act_backward(d2, ymask, M, H, ld2, act, 1, dmask, s);
+}
+
+// out (+)= segmented sum of src and dmask = act'(ymask) out in one launch (ggpm_segment_sum_masked): `add` is what the sum
+// starts from (null: zero; out itself: accumulate in place); out may be null when only the masked gradient is read later
+int segment_sum_act(const float* src, int ld_src, const int32_t* rowptr, const int32_t* col, int rows, int H, int Hp,
+                    const float* add, float* out, const float* ymask, int zero_row0, float* dmask, ggpm_stream_t s) {
+    return ggpm_segment_sum_masked(1, &src, ld_src, rowptr, col, rows, H, &add, Hp, &out, Hp, 0, &ymask, &dmask, Hp,
+                                   GGPM_ACT_RELU, zero_row0, s);
 }
 
 // weight / bias gradients of y = act(x1 W1^T + x2 W2^T + b): dW[:, :K1] = dpre^T x1, dW[:, K1:] = dpre^T x2, db = colsum
@@ -891,7 +918,7 @@ extern "C" int ggpm_encoder_backward(const ggpm_enc_dims* dims, float* const* pa
     for (int i = 0; i < 3; ++i) dXl[i] = w.dX + (size_t)i * 4 * Emax * Hp;
     float* lwork[3];
     for (int i = 0; i < 3; ++i) lwork[i] = w.level_work + (size_t)i * (w.level_work_bytes / 4 + 64);
-    const size_t nt = (size_t)d.N1t * Hp * sizeof(float), ng = (size_t)d.N1g * Hp * sizeof(float);
+    const size_t nt = (size_t)d.N1t * Hp * sizeof(float);
 
     if (side_stream && phase != 2) {      // the transposed CSRs were built on the second stream during the forward
         hipEvent_t ev = ggpm_wgrad_event(61);
@@ -904,8 +931,12 @@ extern "C" int ggpm_encoder_backward(const ggpm_enc_dims* dims, float* const* pa
     if (d_hroot) {
         CK(ggpm_act_backward(d_hroot, hroot, d.B, H, Hp, GGPM_ACT_TANH, 0, w.dpre_root, stream));
         CK(linear2_dx(d.B, H, H, w.dpre_root, Hp, P[P_WROOT], w.df, Hp, 0, w.dn, Hp, 0, stream));
-        CK(ggpm_segment_sum(w.df, Hp, S.root.rowptrT, S.root.colT, d.N1t, H, w.d_hnode_t, Hp, 0, Hp, stream));
-        CK(ggpm_segment_sum(w.dn, Hp, S.root.rowptrT, S.root.colT, d.N1t, H, w.d_nei_t, Hp, 0, Hp, stream));
+        {       // the two scatters over the root index in one launch
+            const float* src2[2] = {w.df, w.dn};
+            float* out2[2] = {w.d_hnode_t, w.d_nei_t};
+            CK(ggpm_segment_sum_masked(2, src2, Hp, S.root.rowptrT, S.root.colT, d.N1t, H, nullptr, 0, out2, Hp, Hp, nullptr,
+                                       nullptr, 0, GGPM_ACT_NONE, 0, stream));
+        }
         CK(linear2_wgrad(d.B, H, w.dpre_root, Hp, S.f, Hp, H, S.n, Hp, H, G[P_WROOT], G[P_BROOT], w, st));
     } else {
         (void)hipMemsetAsync(w.d_hnode_t, 0, nt, s);
@@ -937,11 +968,13 @@ extern "C" int ggpm_encoder_backward(const ggpm_enc_dims* dims, float* const* pa
     CK(ggpm_segment_sum(w.d_nei_t, Hp, S.tagr.rowptrT, S.tagr.colT, d.E1t, H, w.d_h, Hp, 0, Hp, stream));
     CK(level_backward(d, d.E1t, d.It, d.depthT, S.hmess_t, d.ld_t, P, G, 0, S.tpred, S.lv[0], w.d_h, dXl[0], lwork[0],
                       w.dx_mess, d.ld_t, w, st));
-    CK(ggpm_segment_sum(w.dx_mess, d.ld_t, S.tsrc.rowptrT, S.tsrc.colT, d.N1t, H, w.d_hnode_t, Hp, 1, 0, stream));
-    CK(ggpm_act_backward(w.d_hnode_t, S.hnode_t, d.N1t, H, Hp, GGPM_ACT_RELU, 0, dpre[1], stream));
+    // d(hnode_t) is complete with this sum: the ReLU mask of W_c rides on it (nothing reads the unmasked sum afterwards)
+    CK(segment_sum_act(w.dx_mess, d.ld_t, S.tsrc.rowptrT, S.tsrc.colT, d.N1t, H, Hp, w.d_hnode_t, nullptr, S.hnode_t, 0,
+                       dpre[1], stream));
     CK(drop(d, dpre[1], d.N1t, H, Hp, DS_WC, stream));
-    if (d_hinter) (void)hipMemcpyAsync(w.d_hinter, d_hinter, nt, hipMemcpyDeviceToDevice, s);
-    CK(linear2_dx(d.N1t, H, He, dpre[1], Hp, P[P_WC], w.d_finput, d.Hep, 0, w.d_hinter, Hp, d_hinter ? 1 : 0, stream));
+    // d(hinter) = the caller's gradient + dpre W_c[:, He:]; the ReLU mask of the attachment level's W_o rides on the product
+    CK(linear2_dx_masked(d.N1t, H, He, dpre[1], Hp, P[P_WC], w.d_finput, d.Hep, w.d_hinter, Hp, d_hinter, hinter,
+                         GGPM_ACT_RELU, dpre[2], stream));
     CK(drop(d, w.d_finput, d.N1t, He, d.Hep, DS_EC, stream));
     CK(linear2_wgrad(d.N1t, H, dpre[1], Hp, S.finput_t, d.Hep, He, hinter, Hp, H, G[P_WC], G[P_BC], w, st));
     {
@@ -951,15 +984,14 @@ extern "C" int ggpm_encoder_backward(const ggpm_enc_dims* dims, float* const* pa
     }
 
     // ---- attachment level: W_o, message function, W_i / E_i, pooling over atoms
-    CK(ggpm_act_backward(w.d_hinter, hinter, d.N1t, H, Hp, GGPM_ACT_RELU, 1, dpre[2], stream));
     CK(drop(d, dpre[2], d.N1t, H, Hp, DS_WO_INTER, stream));
     CK(linear2_dx(d.N1t, H, H, dpre[2], Hp, P[lwo(d.lstm, 1)], w.d_hnode_i, Hp, 0, w.d_nei_i, Hp, 0, stream));
     CK(linear2_wgrad(d.N1t, H, dpre[2], Hp, S.hnode_i, Hp, H, S.lv[1].nei, Hp, H, G[lwo(d.lstm, 1)], G[lbo(d.lstm, 1)], w, st));
     CK(ggpm_segment_sum(w.d_nei_i, Hp, S.tagr.rowptrT, S.tagr.colT, d.E1t, H, w.d_h, Hp, 0, Hp, stream));
     CK(level_backward(d, d.E1t, d.It, d.depthT, S.hmess_i, d.ld_t, P, G, 1, S.tpred, S.lv[1], w.d_h, dXl[1], lwork[1],
                       w.dx_mess, d.ld_t, w, st));
-    CK(ggpm_segment_sum(w.dx_mess, d.ld_t, S.tsrc.rowptrT, S.tsrc.colT, d.N1t, H, w.d_hnode_i, Hp, 1, 0, stream));
-    CK(ggpm_act_backward(w.d_hnode_i, S.hnode_i, d.N1t, H, Hp, GGPM_ACT_RELU, 0, dpre[3], stream));
+    CK(segment_sum_act(w.dx_mess, d.ld_t, S.tsrc.rowptrT, S.tsrc.colT, d.N1t, H, Hp, w.d_hnode_i, nullptr, S.hnode_i, 0,
+                       dpre[3], stream));
     CK(drop(d, dpre[3], d.N1t, H, Hp, DS_WI, stream));
     float* d_finput_i = w.d_finput + (size_t)d.N1t * d.Hep;
     CK(linear2_dx(d.N1t, H, He, dpre[3], Hp, P[P_WI], d_finput_i, d.Hep, 0, w.d_pooled, Hp, 0, stream));
@@ -970,9 +1002,9 @@ extern "C" int ggpm_encoder_backward(const ggpm_enc_dims* dims, float* const* pa
         float* const g = G[P_EI]; const ggpm_stream_t sw = st.w(); const int Hep = d.Hep, rows = d.n_attach;
         CK(st.on_side([=]() -> int { return ggpm_segment_sum(d_finput_i, Hep, rp, cl, rows, He, g, He, 0, He, sw); }));
     }
-    if (d_hatom) (void)hipMemcpyAsync(w.d_hatom, d_hatom, ng, hipMemcpyDeviceToDevice, s);
-    CK(ggpm_segment_sum(w.d_pooled, Hp, S.tcgr.rowptrT, S.tcgr.colT, d.N1g, H, w.d_hatom, Hp, d_hatom ? 1 : 0,
-                        d_hatom ? 0 : Hp, stream));
+    // d(hatom) = the caller's gradient + the pooled gradient scattered back; the ReLU mask of the atom level's W_o rides on
+    // the sum (dpre[4] lives in `work`, so it is there for a phase-2 call)
+    CK(segment_sum_act(w.d_pooled, Hp, S.tcgr.rowptrT, S.tcgr.colT, d.N1g, H, Hp, d_hatom, nullptr, hatom, 1, dpre[4], stream));
 
     }   // phase != 2
     if (phase == 1) {      // everything but the atom level's parameter gradients is issued (second stream: in flight)
@@ -982,7 +1014,6 @@ extern "C" int ggpm_encoder_backward(const ggpm_enc_dims* dims, float* const* pa
     }
 
     // ---- atom level: W_o, message function (its inputs are constants)
-    CK(ggpm_act_backward(w.d_hatom, hatom, d.N1g, H, Hp, GGPM_ACT_RELU, 1, dpre[4], stream));
     CK(drop(d, dpre[4], d.N1g, H, Hp, DS_WO_ATOM, stream));
     CK(ggpm_gemm(0, 0, d.N1g, H, H, dpre[4], Hp, P[lwo(d.lstm, 2)] + d.atom, d.atom + H, w.d_nei_g, Hp, Hp, nullptr, 0,
                  GGPM_ACT_NONE, 0, nullptr, 0, stream));

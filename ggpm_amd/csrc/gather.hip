@@ -6,28 +6,55 @@
 
 namespace {
 
+// The segmented sum (every entry point's): one wave per destination row walks the row's list in order.  Two options let the
+// backward drivers drop the launches around it (same sums, same order):
+//   addend  the value a row starts from (null: zero; `out` itself: plain accumulation; a matrix of its own: what accumulating
+//           onto a copy of it gives),
+//   dpre    a second, masked output dpre = act'(y) applied to the finished sum, by ggpm_act_grad (what act_backward_k does
+//           to `out` in a launch of its own); `out` may then be left out.
+// blockIdx.y picks one of up to two problems over the same CSR (the root read-out's two gradients).
+struct SegmentSumX {
+    const float* src[2];
+    const float* addend[2];
+    float* out[2];
+    const float* y[2];
+    float* dpre[2];
+    int ld_src, ld_addend, ld_out, ld_mask, act, zero_row0, zero_to;
+};
 template <bool VEC>
-__global__ void __launch_bounds__(256) segment_sum_k(const float* __restrict__ src, int ld_src,
-                                                     const int32_t* __restrict__ rowptr,
-                                                     const int32_t* __restrict__ col, int rows, int width,
-                                                     float* __restrict__ out, int ld_out, int accumulate, int zero_to) {
-    const int lane = threadIdx.x & 63;
+__global__ void __launch_bounds__(256) segment_sum_x_k(SegmentSumX a, const int32_t* __restrict__ rowptr,
+                                                       const int32_t* __restrict__ col, int rows, int width) {
+    const int lane = threadIdx.x & 63, p = blockIdx.y;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= rows) return;
     const int lo = rowptr[r], hi = rowptr[r + 1];
-    float* dst = out + (size_t)r * ld_out;
-    for (int c = width + lane; c < zero_to; c += 64) dst[c] = 0.f;      // pad columns of the row
+    const float* __restrict__ src = a.src[p];
+    const float* add = a.addend[p] ? a.addend[p] + (size_t)r * a.ld_addend : nullptr;
+    float* dst = a.out[p] ? a.out[p] + (size_t)r * a.ld_out : nullptr;
+    const float* y = a.dpre[p] ? a.y[p] + (size_t)r * a.ld_mask : nullptr;
+    float* dp = a.dpre[p] ? a.dpre[p] + (size_t)r * a.ld_mask : nullptr;
+    const bool zero_row = a.zero_row0 && r == 0;
+    if (dst) for (int c = width + lane; c < a.zero_to; c += 64) dst[c] = 0.f;      // pad columns of the row
     if (VEC) {
         for (int c = lane * 4; c < width; c += 256) {
-            float4 acc = accumulate ? ggpm_ld4(dst + c) : ggpm_zero4();
-            for (int j = lo; j < hi; ++j) acc = acc + ggpm_ld4(src + (size_t)col[j] * ld_src + c);
-            ggpm_st4(dst + c, acc);
+            float4 acc = add ? ggpm_ld4(add + c) : ggpm_zero4();
+            for (int j = lo; j < hi; ++j) acc = acc + ggpm_ld4(src + (size_t)col[j] * a.ld_src + c);
+            if (dst) ggpm_st4(dst + c, acc);
+            if (dp) {
+                const float4 o = ggpm_ld4(y + c);
+                float4 g;
+                g.x = ggpm_act_grad(acc.x, o.x, a.act); g.y = ggpm_act_grad(acc.y, o.y, a.act);
+                g.z = ggpm_act_grad(acc.z, o.z, a.act); g.w = ggpm_act_grad(acc.w, o.w, a.act);
+                if (zero_row) g = ggpm_zero4();
+                ggpm_st4(dp + c, g);
+            }
         }
     } else {
         for (int c = lane; c < width; c += 64) {
-            float acc = accumulate ? dst[c] : 0.f;
-            for (int j = lo; j < hi; ++j) acc += src[(size_t)col[j] * ld_src + c];
-            dst[c] = acc;
+            float acc = add ? add[c] : 0.f;
+            for (int j = lo; j < hi; ++j) acc += src[(size_t)col[j] * a.ld_src + c];
+            if (dst) dst[c] = acc;
+            if (dp) dp[c] = zero_row ? 0.f : ggpm_act_grad(acc, y[c], a.act);
         }
     }
 }
@@ -103,10 +130,43 @@ extern "C" int ggpm_segment_sum(const float* src, int ld_src, const int32_t* row
     hipStream_t s = (hipStream_t)stream;
     const bool vec = (width % 4 == 0) && (ld_src % 4 == 0) && (ld_out % 4 == 0) &&
                      (((uintptr_t)src & 15) == 0) && (((uintptr_t)out & 15) == 0);
-    const int grid = ggpm_ceil_div(rows, 4);
-    if (vec) segment_sum_k<true><<<grid, 256, 0, s>>>(src, ld_src, rowptr, col, rows, width, out, ld_out, accumulate,
-                                                           zero_to);
-    else segment_sum_k<false><<<grid, 256, 0, s>>>(src, ld_src, rowptr, col, rows, width, out, ld_out, accumulate, zero_to);
+    SegmentSumX a = {};
+    a.src[0] = src; a.out[0] = out; a.addend[0] = accumulate ? out : nullptr;
+    a.ld_src = ld_src; a.ld_out = a.ld_addend = ld_out; a.zero_to = zero_to;
+    const dim3 grid(ggpm_ceil_div(rows, 4), 1);
+    if (vec) segment_sum_x_k<true><<<grid, 256, 0, s>>>(a, rowptr, col, rows, width);
+    else segment_sum_x_k<false><<<grid, 256, 0, s>>>(a, rowptr, col, rows, width);
+    GGPM_CHECK_LAUNCH();
+    return GGPM_OK;
+}
+
+extern "C" int ggpm_segment_sum_masked(int count, const float* const* src, int ld_src, const int32_t* rowptr, const int32_t* col,
+                                       int rows, int width, const float* const* addend, int ld_addend, float* const* out,
+                                       int ld_out, int zero_to, const float* const* y, float* const* dpre, int ld_mask, int act,
+                                       int zero_row0, ggpm_stream_t stream) {
+    GGPM_CLEAR_STALE_ERROR();
+    if (count < 1 || count > 2 || !src || !rowptr || !col || rows <= 0 || width <= 0) return GGPM_ERR_ARG;
+    SegmentSumX a = {};
+    bool vec = (width % 4 == 0) && (ld_src % 4 == 0);
+    bool any_add = false, any_out = false, any_mask = false;
+    for (int i = 0; i < count; ++i) {
+        a.src[i] = src[i];
+        a.addend[i] = addend ? addend[i] : nullptr;
+        a.out[i] = out ? out[i] : nullptr;
+        a.dpre[i] = dpre ? dpre[i] : nullptr;
+        a.y[i] = y ? y[i] : nullptr;
+        if (!a.src[i] || (!a.out[i] && !a.dpre[i]) || (a.dpre[i] && !a.y[i])) return GGPM_ERR_ARG;
+        any_add = any_add || a.addend[i]; any_out = any_out || a.out[i]; any_mask = any_mask || a.dpre[i];
+        vec = vec && (((uintptr_t)a.src[i] | (uintptr_t)a.addend[i] | (uintptr_t)a.out[i] | (uintptr_t)a.y[i] |
+                       (uintptr_t)a.dpre[i]) & 15) == 0;
+    }
+    if ((any_add && ld_addend < width) || (any_out && ld_out < width) || (any_mask && ld_mask < width)) return GGPM_ERR_ARG;
+    vec = vec && (!any_add || ld_addend % 4 == 0) && (!any_out || ld_out % 4 == 0) && (!any_mask || ld_mask % 4 == 0);
+    a.ld_src = ld_src; a.ld_addend = ld_addend; a.ld_out = ld_out; a.ld_mask = ld_mask; a.act = act; a.zero_row0 = zero_row0;
+    a.zero_to = zero_to;
+    dim3 grid(ggpm_ceil_div(rows, 4), count);
+    if (vec) segment_sum_x_k<true><<<grid, 256, 0, (hipStream_t)stream>>>(a, rowptr, col, rows, width);
+    else segment_sum_x_k<false><<<grid, 256, 0, (hipStream_t)stream>>>(a, rowptr, col, rows, width);
     GGPM_CHECK_LAUNCH();
     return GGPM_OK;
 }

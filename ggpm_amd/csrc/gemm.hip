@@ -39,6 +39,11 @@ struct GemmArgs {
     const float* segA[GGPM_GEMM_MAX_GROUP];
     const float* segB[GGPM_GEMM_MAX_GROUP];
     int seg_lda[GGPM_GEMM_MAX_GROUP], seg_ldb[GGPM_GEMM_MAX_GROUP], segK[GGPM_GEMM_MAX_GROUP];
+    int seg_vec;             // gemm_kernel's K segments: bit 2s / 2s + 1 = 16-byte loads legal for A_s / B_s
+    // epilogue options of gemm_small_v3 (ggpm_gemm_epilogue, common.h): `accumulate` adds addend[m, n] instead of C[m, n];
+    // mask_out[m, n] = act'(mask_y[m, n]) applied to the value stored to C (what act_backward_k would do in its own launch)
+    const float* addend; int ld_addend;
+    const float* mask_y; float* mask_out; int ld_mask, mask_act, mask_zero_row0;
 };
 
 struct GemmGroupArgs {       // independent problems of one shape in one launch (blockIdx.z picks the problem)
@@ -108,12 +113,12 @@ __device__ __forceinline__ void stash_tile(const float4 (&v)[2], float (*T)[LDT]
     }
 }
 
-template <bool TA, bool TB>
-__global__ void __launch_bounds__(256) gemm_kernel(GemmArgs g) {
-    __shared__ __attribute__((aligned(16))) float As[BK][LDT];
-    __shared__ __attribute__((aligned(16))) float Bs[BK][LDT];
+// `chunk`: the K chunk of a split-K launch (blockIdx.z there), 0 otherwise.  SEGS: the K-segment form (gemm_kernel_segs; its
+// carry registers and second product stay out of the plain kernels, whose register count is what it was: 52)
+template <bool TA, bool TB, bool SEGS>
+__device__ __forceinline__ void gemm_tile_64(const GemmArgs& g, int chunk, float (&As)[BK][LDT], float (&Bs)[BK][LDT]) {
     const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
-    const int kbeg = blockIdx.z * g.k_chunk;
+    const int kbeg = chunk * g.k_chunk;
     const int kend = min(g.K, kbeg + g.k_chunk);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave >> 1, wn = wave & 1;
@@ -121,18 +126,20 @@ __global__ void __launch_bounds__(256) gemm_kernel(GemmArgs g) {
     f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    const int n = n0 + wn * 32 + (lane & 31);
 
-    if (n0 < g.N) {
+    // one product A[:, kb:ke] B[kb:ke, :] added into acc
+    auto product = [&](const float* A, int lda, bool vecA, const float* B, int ldb, bool vecB, int kb, int ke) {
         float4 ra[2], rb[2];
-        fetch_tile<!TA>(g.A, g.lda, m0, g.M, kbeg, kend, g.vecA != 0, ra);
-        fetch_tile<TB>(g.B, g.ldb, n0, g.N, kbeg, kend, g.vecB != 0, rb);
-        for (int k0 = kbeg; k0 < kend; k0 += BK) {
+        fetch_tile<!TA>(A, lda, m0, g.M, kb, ke, vecA, ra);
+        fetch_tile<TB>(B, ldb, n0, g.N, kb, ke, vecB, rb);
+        for (int k0 = kb; k0 < ke; k0 += BK) {
             stash_tile<!TA>(ra, As);
             stash_tile<TB>(rb, Bs);
             __syncthreads();
-            if (k0 + BK < kend) {       // next k-step's operands fly under this step's MFMAs
-                fetch_tile<!TA>(g.A, g.lda, m0, g.M, k0 + BK, kend, g.vecA != 0, ra);
-                fetch_tile<TB>(g.B, g.ldb, n0, g.N, k0 + BK, kend, g.vecB != 0, rb);
+            if (k0 + BK < ke) {       // next k-step's operands fly under this step's MFMAs
+                fetch_tile<!TA>(A, lda, m0, g.M, k0 + BK, ke, vecA, ra);
+                fetch_tile<TB>(B, ldb, n0, g.N, k0 + BK, ke, vecB, rb);
             }
 #pragma unroll
             for (int kk = 0; kk < BK; kk += 2) {
@@ -142,15 +149,60 @@ __global__ void __launch_bounds__(256) gemm_kernel(GemmArgs g) {
             }
             __syncthreads();
         }
+    };
+
+    // K segments (ggpm_gemm_ksegments on operands without 16-byte loads): the chain of launches it replaces, rounding for
+    // rounding -- segment s starts from a FRESH accumulator and its finished value v_s = acc_s + v_(s-1) (v_0 = acc_0 + bias
+    // (+ C)) is what the next launch of the chain read back from C; activation and row mask with the last.
+    if constexpr (SEGS) {
+        float carry[16];
+        for (int sg = 0; sg + 1 < g.nseg; ++sg) {
+            if (n0 < g.N)
+                product(g.segA[sg], g.seg_lda[sg], (g.seg_vec >> (2 * sg)) & 1, g.segB[sg], g.seg_ldb[sg],
+                        (g.seg_vec >> (2 * sg + 1)) & 1, 0, g.segK[sg]);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                float v = acc[r];
+                if (sg == 0) {
+                    if (g.bias && n < g.N) v += g.bias[n];
+                    if (g.accumulate && m < g.M && n < g.N) v += g.C[(size_t)m * g.ldc + n];
+                } else {
+                    v += carry[r];
+                }
+                carry[r] = v;
+                acc[r] = 0.f;
+            }
+        }
+        const int sg = g.nseg - 1;
+        if (n0 < g.N)
+            product(g.segA[sg], g.seg_lda[sg], (g.seg_vec >> (2 * sg)) & 1, g.segB[sg], g.seg_ldb[sg],
+                    (g.seg_vec >> (2 * sg + 1)) & 1, 0, g.segK[sg]);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            if (m >= g.M) continue;
+            if (n < g.N) {
+                float v = acc[r];
+                v += carry[r];
+                v = apply_act(v, g.act);
+                if (g.zero_row0 && m == 0) v = 0.f;
+                g.C[(size_t)m * g.ldc + n] = v;
+            } else if (n < g.n_pad) {
+                g.C[(size_t)m * g.ldc + n] = 0.f;
+            }
+        }
+        return;
     }
 
-    const int n = n0 + wn * 32 + (lane & 31);
+    if (n0 < g.N) product(g.A, g.lda, g.vecA != 0, g.B, g.ldb, g.vecB != 0, kbeg, kend);
+
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
         if (m >= g.M) continue;
         if (g.ws) {
-            if (n < g.N) g.ws[((size_t)blockIdx.z * g.M + m) * g.N + n] = acc[r];
+            if (n < g.N) g.ws[((size_t)chunk * g.M + m) * g.N + n] = acc[r];
             continue;
         }
         if (n < g.N) {
@@ -165,6 +217,30 @@ __global__ void __launch_bounds__(256) gemm_kernel(GemmArgs g) {
             g.C[(size_t)m * g.ldc + n] = 0.f;
         }
     }
+}
+
+template <bool TA, bool TB>
+__global__ void __launch_bounds__(256) gemm_kernel(GemmArgs g) {
+    __shared__ __attribute__((aligned(16))) float As[BK][LDT];
+    __shared__ __attribute__((aligned(16))) float Bs[BK][LDT];
+    gemm_tile_64<TA, TB, false>(g, blockIdx.z, As, Bs);
+}
+
+// ggpm_gemm_ksegments on operands without 16-byte loads: the chain of gemm_kernel launches in one (A not transposed)
+template <bool TB>
+__global__ void __launch_bounds__(256) gemm_kernel_segs(GemmArgs g) {
+    __shared__ __attribute__((aligned(16))) float As[BK][LDT];
+    __shared__ __attribute__((aligned(16))) float Bs[BK][LDT];
+    gemm_tile_64<false, TB, true>(g, 0, As, Bs);
+}
+
+// independent unsplit problems of one shape on the scalar-load tile above, one launch: blockIdx.z picks the problem (the
+// members of a group whose operands do not allow 16-byte loads -- the atom level's gate-input projections, W rows of 62 + H)
+template <bool TA, bool TB>
+__global__ void __launch_bounds__(256) gemm_kernel_group(GemmGroupArgs gg) {
+    __shared__ __attribute__((aligned(16))) float As[BK][LDT];
+    __shared__ __attribute__((aligned(16))) float Bs[BK][LDT];
+    gemm_tile_64<TA, TB, false>(gg.p[blockIdx.z], 0, As, Bs);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -365,7 +441,6 @@ struct SmallStage {
     __amdgpu_buffer_rsrc_t rs;
     unsigned voff[2], vstep;
     int loff[2], kq[2];
-
     __device__ __forceinline__ void init(const float* P, int ld, int r0, int R, int K, int total_rows) {
         const size_t last = CONTIG_K ? (size_t)(total_rows - 1) * ld + K : (size_t)(K - 1) * ld + R;
         rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P), 0, (unsigned)(last * 4), 0x00020000);
@@ -534,10 +609,15 @@ __device__ __forceinline__ void gemm_v3_tile(const GemmArgs& g, int bx, int by, 
                       (part[(2 * 16 + r) * 64 + l] + part[(3 * 16 + r) * 64 + l]);
             if (g.bias) v += g.bias[n];
             float* dst = g.C + (size_t)m * g.ldc + n;
-            if (g.accumulate) v += *dst;
+            if (g.accumulate) v += g.addend ? g.addend[(size_t)m * g.ld_addend + n] : *dst;
             v = apply_act(v, g.act);
             if (g.zero_row0 && m == 0) v = 0.f;
             *dst = v;
+            if (g.mask_out) {
+                const size_t i = (size_t)m * g.ld_mask + n;
+                const float gm = ggpm_act_grad(v, g.mask_y[i], g.mask_act);
+                g.mask_out[i] = (g.mask_zero_row0 && m == 0) ? 0.f : gm;
+            }
         } else if (n < g.n_pad) {
             g.C[(size_t)m * g.ldc + n] = 0.f;
         }
@@ -1156,13 +1236,7 @@ __global__ void act_backward_k(const float* __restrict__ dy, const float* __rest
     const int r = blockIdx.y;
     if (c >= cols) return;
     const size_t i = (size_t)r * ld + c;
-    float g = dy[i], o = y[i];
-    switch (act) {
-        case GGPM_ACT_RELU: g = o > 0.f ? g : 0.f; break;
-        case GGPM_ACT_TANH: g = g * (1.f - o * o); break;
-        case GGPM_ACT_SIGMOID: g = g * o * (1.f - o); break;
-        default: break;
-    }
+    float g = ggpm_act_grad(dy[i], y[i], act);
     if (zero_row0 && r == 0) g = 0.f;
     dpre[i] = g;
 }
@@ -1449,6 +1523,31 @@ extern "C" int ggpm_gemm_grouped(int trans_a, int trans_b, int M, int N, int K, 
         n_pad_max = max(n_pad_max, p[i].n_pad);
     }
     if (!ok) {
+        // every member on the scalar-load kernel (ggpm_gemm sends a product there, unsplit, whenever one of its operands
+        // does not allow 16-byte loads): the same tiles in one launch
+        bool scalar = count > 1;
+        for (int i = 0; i < count; ++i) {
+            const bool vecA = ((p[i].lda & 3) == 0) && (((uintptr_t)p[i].A & 15) == 0);
+            const bool vecB = ((p[i].ldb & 3) == 0) && (((uintptr_t)p[i].B & 15) == 0);
+            scalar = scalar && !(vecA && vecB);
+        }
+        if (scalar) {
+            GemmGroupArgs gg;
+            for (int i = 0; i < count; ++i) {
+                fill_args(gg.p[i], M, N, K, p[i]);
+                gg.p[i].vecA = ((p[i].lda & 3) == 0) && (((uintptr_t)p[i].A & 15) == 0);
+                gg.p[i].vecB = ((p[i].ldb & 3) == 0) && (((uintptr_t)p[i].B & 15) == 0);
+            }
+            for (int i = count; i < GGPM_GEMM_MAX_GROUP; ++i) gg.p[i] = gg.p[0];
+            hipStream_t s = (hipStream_t)stream;
+            dim3 grid(ggpm_ceil_div(n_pad_max, BN), ggpm_ceil_div(M, BM), count);
+            if (!trans_a && !trans_b) gemm_kernel_group<false, false><<<grid, 256, 0, s>>>(gg);
+            else if (!trans_a && trans_b) gemm_kernel_group<false, true><<<grid, 256, 0, s>>>(gg);
+            else if (trans_a && !trans_b) gemm_kernel_group<true, false><<<grid, 256, 0, s>>>(gg);
+            else gemm_kernel_group<true, true><<<grid, 256, 0, s>>>(gg);
+            GGPM_CHECK_LAUNCH();
+            return GGPM_OK;
+        }
         for (int i = 0; i < count; ++i) {
             const int rc = ggpm_gemm(trans_a, trans_b, M, N, K, p[i].A, p[i].lda, p[i].B, p[i].ldb, p[i].C, p[i].ldc,
                                      p[i].n_pad, p[i].bias, p[i].accumulate, p[i].act, p[i].zero_row0, nullptr, 0, stream);
@@ -1470,6 +1569,34 @@ extern "C" int ggpm_gemm_grouped(int trans_a, int trans_b, int M, int N, int K, 
     else if (!trans_a && trans_b) gemm_group_v2<false, true><<<grid, 256, 0, s>>>(gg);
     else if (trans_a && !trans_b) gemm_group_v2<true, false><<<grid, 256, 0, s>>>(gg);
     else gemm_group_v2<true, true><<<grid, 256, 0, s>>>(gg);
+    GGPM_CHECK_LAUNCH();
+    return GGPM_OK;
+}
+
+// ggpm_gemm_grouped on gemm_small_v3 with per-problem epilogue options (`e[i]`; common.h).  GGPM_ERR_UNSUPPORTED when the
+// group would not run on that kernel (operands not 16-byte aligned, too many tiles): the caller then composes the plain calls.
+extern "C" int ggpm_gemm_grouped_masked(int trans_a, int trans_b, int M, int N, int K, int count, const ggpm_gemm_problem* p,
+                                        const ggpm_gemm_epilogue* e, ggpm_stream_t stream) {
+    GGPM_CLEAR_STALE_ERROR();
+    if (count <= 0 || count > GGPM_GEMM_MAX_GROUP || !p || !e || M <= 0 || N <= 0 || K <= 0) return GGPM_ERR_ARG;
+    int n_pad_max = 0;
+    for (int i = 0; i < count; ++i) {
+        if (!p[i].A || !p[i].B || !p[i].C || p[i].n_pad < N || p[i].n_pad > p[i].ldc) return GGPM_ERR_ARG;
+        if (e[i].addend && e[i].ld_addend < N) return GGPM_ERR_ARG;
+        if (e[i].mask_out && (!e[i].mask_y || e[i].ld_mask < N)) return GGPM_ERR_ARG;
+        if (!v2_operands_ok(p[i].A, p[i].lda, trans_a ? K : M, p[i].B, p[i].ldb, trans_b ? N : K)) return GGPM_ERR_UNSUPPORTED;
+        n_pad_max = max(n_pad_max, p[i].n_pad);
+    }
+    if (!small_launch(M, N, count)) return GGPM_ERR_UNSUPPORTED;
+    GemmGroupArgs gg;
+    for (int i = 0; i < count; ++i) {
+        fill_args(gg.p[i], M, N, K, p[i]);
+        gg.p[i].addend = e[i].addend; gg.p[i].ld_addend = e[i].ld_addend;
+        gg.p[i].mask_y = e[i].mask_y; gg.p[i].mask_out = e[i].mask_out; gg.p[i].ld_mask = e[i].ld_mask;
+        gg.p[i].mask_act = e[i].mask_act; gg.p[i].mask_zero_row0 = e[i].mask_zero_row0;
+    }
+    for (int i = count; i < GGPM_GEMM_MAX_GROUP; ++i) gg.p[i] = gg.p[0];
+    launch_small(trans_a, trans_b, gg, count, M, n_pad_max, (hipStream_t)stream);
     GGPM_CHECK_LAUNCH();
     return GGPM_OK;
 }
@@ -1521,6 +1648,32 @@ extern "C" int ggpm_gemm_ksegments(int trans_b, int M, int N, int nseg, const fl
     for (int i = 0; i < nseg; ++i) {
         if (!A[i] || !B[i] || K[i] <= 0) return GGPM_ERR_ARG;
         ok = ok && v2_operands_ok(A[i], lda[i], M, B[i], ldb[i], trans_b ? N : K[i]);
+    }
+    if (!ok && nseg > 1) {
+        // every segment on the scalar-load kernel (where ggpm_gemm sends a product, unsplit, whenever one of its operands
+        // does not allow 16-byte loads): the chain below in ONE launch that rounds where the chain rounds (gemm_tile_64)
+        bool scalar = true;
+        int seg_vec = 0;
+        for (int i = 0; i < nseg; ++i) {
+            const bool vecA = ((lda[i] & 3) == 0) && (((uintptr_t)A[i] & 15) == 0);
+            const bool vecB = ((ldb[i] & 3) == 0) && (((uintptr_t)B[i] & 15) == 0);
+            scalar = scalar && !(vecA && vecB);
+            seg_vec |= (vecA ? 1 : 0) << (2 * i) | (vecB ? 1 : 0) << (2 * i + 1);
+        }
+        if (scalar) {
+            GemmArgs g{};
+            g.M = M; g.N = N; g.K = K[0]; g.C = C; g.ldc = ldc; g.n_pad = n_pad;
+            g.bias = bias; g.accumulate = accumulate; g.act = act; g.zero_row0 = zero_row0;
+            g.k_chunk = ggpm_round_up(K[0], BK);
+            g.nseg = nseg; g.seg_vec = seg_vec;
+            for (int i = 0; i < nseg; ++i) { g.segA[i] = A[i]; g.segB[i] = B[i]; g.seg_lda[i] = lda[i]; g.seg_ldb[i] = ldb[i]; g.segK[i] = K[i]; }
+            hipStream_t s = (hipStream_t)stream;
+            dim3 grid(ggpm_ceil_div(n_pad, BN), ggpm_ceil_div(M, BM), 1);
+            if (trans_b) gemm_kernel_segs<true><<<grid, 256, 0, s>>>(g);
+            else gemm_kernel_segs<false><<<grid, 256, 0, s>>>(g);
+            GGPM_CHECK_LAUNCH();
+            return GGPM_OK;
+        }
     }
     if (!ok) {      // bias with the first product, activation / row mask with the last
         for (int i = 0; i < nseg; ++i) {

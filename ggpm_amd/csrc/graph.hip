@@ -132,10 +132,9 @@ __device__ __forceinline__ void block_exclusive_scan_inplace(int32_t* data, int 
     __syncthreads();
 }
 
-__global__ void __launch_bounds__(SCAN_THREADS) padded_to_csr_small(const int64_t* __restrict__ padded, int rows,
-                                                                     int width, int32_t* __restrict__ rowptr,
-                                                                     int32_t* __restrict__ col) {
-    __shared__ int32_t partial[SCAN_THREADS];
+__device__ __forceinline__ void padded_to_csr_block(const int64_t* __restrict__ padded, int rows, int width,
+                                                    int32_t* __restrict__ rowptr, int32_t* __restrict__ col,
+                                                    int32_t* partial) {
     for (int r = threadIdx.x; r < rows; r += SCAN_THREADS) {
         const int64_t* p = padded + (size_t)r * width;
         int c = 0;
@@ -152,6 +151,25 @@ __global__ void __launch_bounds__(SCAN_THREADS) padded_to_csr_small(const int64_
             if (v != 0) col[o++] = (int32_t)v;
         }
     }
+}
+
+__global__ void __launch_bounds__(SCAN_THREADS) padded_to_csr_small(const int64_t* __restrict__ padded, int rows,
+                                                                     int width, int32_t* __restrict__ rowptr,
+                                                                     int32_t* __restrict__ col) {
+    __shared__ int32_t partial[SCAN_THREADS];
+    padded_to_csr_block(padded, rows, width, rowptr, col, partial);
+}
+
+// two independent small lists in one launch: workgroup b builds list b
+struct PaddedPair {
+    const int64_t* padded[2];
+    int rows[2], width[2];
+    int32_t *rowptr[2], *col[2];
+};
+__global__ void __launch_bounds__(SCAN_THREADS) padded_to_csr_small_pair(PaddedPair a) {
+    __shared__ int32_t partial[SCAN_THREADS];
+    const int b = blockIdx.x;
+    padded_to_csr_block(a.padded[b], a.rows[b], a.width[b], a.rowptr[b], a.col[b], partial);
 }
 
 // Ascending order inside every transposed row makes the backward sums deterministic.  Rows of up to SORT_SERIAL entries are
@@ -270,6 +288,23 @@ extern "C" int ggpm_padded_to_csr(const int64_t* padded, int rows, int width, in
     count_nonzero_rows<<<B, T, 0, s>>>(padded, rows, width, rowptr);
     exclusive_scan_1block<<<1, SCAN_THREADS, 0, s>>>(rowptr, rows, rowptr);
     fill_csr_from_padded<<<B, T, 0, s>>>(padded, rows, width, rowptr, col);
+    GGPM_CHECK_LAUNCH();
+    return GGPM_OK;
+}
+
+extern "C" int ggpm_padded_to_csr_pair(const int64_t* padded_a, int rows_a, int width_a, int32_t* rowptr_a, int32_t* col_a,
+                                       const int64_t* padded_b, int rows_b, int width_b, int32_t* rowptr_b, int32_t* col_b,
+                                       ggpm_stream_t stream) {
+    GGPM_CLEAR_STALE_ERROR();
+    if (!padded_a || !rowptr_a || !col_a || rows_a <= 0 || width_a <= 0 || !padded_b || !rowptr_b || !col_b || rows_b <= 0 ||
+        width_b <= 0)
+        return GGPM_ERR_ARG;
+    if (rows_a > SMALL_ROWS || rows_b > SMALL_ROWS) {      // the multi-launch forms, one list after the other
+        const int rc = ggpm_padded_to_csr(padded_a, rows_a, width_a, rowptr_a, col_a, stream);
+        return rc ? rc : ggpm_padded_to_csr(padded_b, rows_b, width_b, rowptr_b, col_b, stream);
+    }
+    PaddedPair a = {{padded_a, padded_b}, {rows_a, rows_b}, {width_a, width_b}, {rowptr_a, rowptr_b}, {col_a, col_b}};
+    padded_to_csr_small_pair<<<2, SCAN_THREADS, 0, (hipStream_t)stream>>>(a);
     GGPM_CHECK_LAUNCH();
     return GGPM_OK;
 }

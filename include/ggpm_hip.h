@@ -56,6 +56,10 @@ int ggpm_padded_hidden(int H);
 /* rowptr[rows+1], col[>= rows*width]; entries keep their in-row order. */
 int ggpm_padded_to_csr(const int64_t* padded, int rows, int width, int32_t* rowptr, int32_t* col,
                        ggpm_stream_t stream);
+/* Two ggpm_padded_to_csr in one launch (one workgroup per list when both are small; the plain calls otherwise). */
+int ggpm_padded_to_csr_pair(const int64_t* padded_a, int rows_a, int width_a, int32_t* rowptr_a, int32_t* col_a,
+                            const int64_t* padded_b, int rows_b, int width_b, int32_t* rowptr_b, int32_t* col_b,
+                            ggpm_stream_t stream);
 /* Transpose of a CSR whose column ids lie in [0, ncols): rowptrT[ncols+1], colT[>= nnz capacity]
  * hold, for every column id, the ascending list of rows that reference it (deterministic order);
  * `cursor` is int32 scratch of ncols entries. Used for the atomics-free backward gathers. */
@@ -106,6 +110,19 @@ int ggpm_gemm_grouped(int trans_a, int trans_b, int M, int N, int K, int count, 
 size_t ggpm_gemm_grouped_splitk_workspace_bytes(int M, int N, int K, int count);
 int ggpm_gemm_grouped_splitk(int trans_a, int trans_b, int M, int N, int K, int count, const ggpm_gemm_problem* problems,
                              float* ws, size_t ws_bytes, ggpm_stream_t stream);
+/* ggpm_gemm_grouped (count >= 1) with two epilogue options per problem, so that the launches around a product can go:
+ *   addend   -- with problems[i].accumulate != 0 the product is added to addend[m, n] (leading dimension ld_addend) instead
+ *               of to C[m, n]: the same value in the same place of the same sum as accumulating onto a copy of `addend`;
+ *   mask_out -- mask_out[m, n] = ggpm_act_backward(C, mask_y, ..., mask_act, mask_zero_row0) of the value just stored to
+ *               C (both with leading dimension ld_mask; NULL: no second output).
+ * Runs on the small-tile kernel only: GGPM_ERR_UNSUPPORTED (nothing launched) when an operand does not allow 16-byte
+ * loads or the group has too many tiles for it; the caller then issues copy, product and ggpm_act_backward itself. */
+typedef struct ggpm_gemm_epilogue {
+    const float* addend; int ld_addend;
+    const float* mask_y; float* mask_out; int ld_mask, mask_act, mask_zero_row0;
+} ggpm_gemm_epilogue;
+int ggpm_gemm_grouped_masked(int trans_a, int trans_b, int M, int N, int K, int count, const ggpm_gemm_problem* problems,
+                             const ggpm_gemm_epilogue* epilogues, ggpm_stream_t stream);
 int ggpm_gemm_ksegments(int trans_b, int M, int N, int nseg, const float* const* A, const int* lda,
                         const float* const* B, const int* ldb, const int* K, float* C, int ldc, int n_pad,
                         const float* bias, int accumulate, int act, int zero_row0, ggpm_stream_t stream);
@@ -148,6 +165,16 @@ int ggpm_act_backward(const float* dy, const float* y, int rows, int cols, int l
  * columns of the Hp-strided matrices), 0 = leave them alone. */
 int ggpm_segment_sum(const float* src, int ld_src, const int32_t* rowptr, const int32_t* col, int rows,
                      int width, float* out, int ld_out, int accumulate, int zero_to, ggpm_stream_t stream);
+/* `count` (1 or 2) segmented sums over ONE CSR in one launch, each with two options:
+ *   addend[i] -- row r starts from addend[i][r, :] (leading dimension ld_addend) instead of from zero: what accumulate != 0
+ *                does with a copy of `addend` in `out`, same order of additions (NULL array / entry: start from zero);
+ *   dpre[i]   -- a second output dpre[i] = ggpm_act_backward(sum, y[i], ..., act, zero_row0), y / dpre with leading
+ *                dimension ld_mask (NULL: none).  out[i] may be NULL when dpre[i] is given: the plain sum is not stored.
+ * zero_to as above (applies to out). */
+int ggpm_segment_sum_masked(int count, const float* const* src, int ld_src, const int32_t* rowptr, const int32_t* col,
+                            int rows, int width, const float* const* addend, int ld_addend, float* const* out, int ld_out,
+                            int zero_to, const float* const* y, float* const* dpre, int ld_mask, int act, int zero_row0,
+                            ggpm_stream_t stream);
 /* out[r, col_off : col_off+width] = table[idx[r], 0:width]; rows with idx<0 give zeros.
  * = nn.Embedding / index_select of ggpm/encoder.py:98,103,111,114 */
 int ggpm_gather_rows(const float* table, int ld_table, const int32_t* idx, int rows, int width,
