@@ -28,7 +28,7 @@ import torch.nn.functional as TF
 from . import _dev
 from . import functional as F_
 from . import inc_encoder as IE
-from .decoder_heads import ScoreHeads, bce_with_logits_sum, cross_entropy_sum
+from .decoder_heads import ScoreHeads, _gemm_rows, _i32, _memo, bce_with_logits_sum, check_no_dropout, cross_entropy_sum
 
 MAX_POS = 20
 
@@ -511,14 +511,6 @@ def _pinned_cls_size(schedule, max_cls_size) -> int:
     return int(max_cls_size)
 
 
-def _memo(D: dict, key: str, make):
-    """``D[key]``, made on first use: tensors derived from a decode schedule's device tables live as long as the tables."""
-    v = D.get(key)
-    if v is None:
-        v = D[key] = make()
-    return v
-
-
 def _accuracy(pred: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     """get_accuracy (ggpm/nnutils.py:84-87) from the arg-max the loss kernel already produced."""
     return (pred.long() == labels).float().sum() / labels.numel()
@@ -544,6 +536,8 @@ def level_states(rnn, h0, hmess, dag, depth):
 class HierMPNDecoder(ScoreHeads):
     """reference ggpm/decoder.py:19-301 (training forward)"""
 
+    DECODE_MODULE = "hier_decode"
+
     def __init__(self, vocab, avocab, rnn_type, embed_size, hidden_size, latent_size, depthT, depthG, dropout,
                  attention=False):
         super().__init__(vocab, embed_size, hidden_size, latent_size, dropout)
@@ -557,22 +551,6 @@ class HierMPNDecoder(ScoreHeads):
         if latent_size != hidden_size:
             self.W_root = nn.Linear(latent_size, hidden_size)
         self.graph_batch_factory = None     # decode's graph batch when the call names none (ggpm_amd.hier_decode)
-
-    def decode(self, mols, src_mol_vecs, greedy=True, max_decode_step=100, beam=5, graph_batch_factory=None):
-        """reference ggpm/decoder.py:303-472 -> (results, graph_batch.get_mol()) on the library's kernels; the graph batch
-        is ``graph_batch_factory`` or else ``self.graph_batch_factory`` (ggpm_amd.hier_decode)."""
-        from .hier_decode import decode
-        return decode(self, mols, src_mol_vecs, greedy, max_decode_step, beam, graph_batch_factory)
-
-    def decode_sampled(self, mols, src_mol_vecs, seed=None, sample_ids=None, max_decode_step=100, beam=5,
-                       graph_batch_factory=None):
-        """The reference's ``decode(..., greedy=False)`` (ggpm/decoder.py:371-374, 409-416) -> what ``decode`` returns.  The topology
-        decision is a Bernoulli draw and the beam entries are tried in an order drawn without replacement; the draws come
-        from a counter-based stream keyed by ``seed`` (an int, 64 bits used; ``None`` takes them from torch's default CPU
-        generator) and by ``sample_ids`` (one int per molecule, default ``arange``), so a molecule's draws do not depend
-        on its batch (*Sampled decoding and the prior*)."""
-        from .hier_decode import decode_sampled
-        return decode_sampled(self, mols, src_mol_vecs, seed, sample_ids, max_decode_step, beam, graph_batch_factory)
 
     def schedule_hints(self) -> dict:
         """What ``DecodeSchedule.from_*`` can use of this decoder: diterG and the number of gates of its message function,
@@ -610,18 +588,15 @@ class HierMPNDecoder(ScoreHeads):
     # ------------------------------------------------------------------ forward
     def forward(self, mols, src_mol_vecs, graphs, tensors, orders, schedule: Optional[DecodeSchedule] = None):
         tree_tensors, graph_tensors = tensors
-        B, H, L = len(orders), self.hidden_size, self.latent_size
+        B = len(orders)
         dev = tree_tensors[0].device
         if schedule is None:
             schedule = DecodeSchedule.from_graphs(graphs, tensors, orders, self.vocab, **self.schedule_hints())
         D = schedule.to_device(dev)._dev
         src_root_vecs, src_tree_vecs, src_graph_vecs = src_mol_vecs
-        if L == H:
-            init_vecs = src_root_vecs
-        else:
-            init_vecs = F_.linear([src_root_vecs.contiguous()], [L], self.W_root.weight, self.W_root.bias)[:, :H]
+        init_vecs = self._init_vecs(src_root_vecs)
         self._heads_in = None
-        if _dev.DECODER_BATCHED and schedule.plan["all_live"] and schedule.plan["E1"] > 1:
+        if self._batched_schedule(schedule):
             topo_vecs, cls_vecs, assm_vecs, assm_dest = self._states_batched(schedule, D, tree_tensors, graph_tensors,
                                                                             init_vecs)
         else:
@@ -642,9 +617,7 @@ class HierMPNDecoder(ScoreHeads):
         from . import heads_fused
         cand, blocks = heads_in
         spec = dict(self._heads_spec(schedule, D, dev), assm_blocks=blocks)
-        tv = topo_vecs if (topo_vecs.dim() == 2 and topo_vecs.stride(1) == 1 and topo_vecs.stride(0) % 4 == 0) else topo_vecs.contiguous()
-        cv = cls_vecs if (cls_vecs.dim() == 2 and cls_vecs.stride(1) == 1 and cls_vecs.stride(0) % 4 == 0) else cls_vecs.contiguous()
-        loss_sum, acc = heads_fused.heads_losses(self, spec, z, tv, cv, cand)
+        loss_sum, acc = heads_fused.heads_losses(self, spec, z, _gemm_rows(topo_vecs), _gemm_rows(cls_vecs), cand)
         return loss_sum / B, acc[0], acc[1], acc[2], acc[3]
 
     @staticmethod
@@ -652,23 +625,17 @@ class HierMPNDecoder(ScoreHeads):
         """The index tensors of the batch as heads_fused reads them, kept with the resident schedule."""
         spec = D.get("heads_spec")
         if spec is None:
-            i32 = lambda t: t if (t.dtype == torch.int32 and t.is_contiguous()) else t.to(torch.int32).contiguous()
+            topo_y, clab, ilab = ScoreHeads._labels(D)
             spec = D["heads_spec"] = dict(
-                topo_idx=i32(D["topo_batch32"]), topo_y=_memo(D, "topo_label_f32", lambda: D["topo_label"].to(torch.float32)),
-                cls_idx=i32(D["cls_batch32"]),
-                cls_lab=_memo(D, "cls_clab32", lambda: D["cls_clab"].to(torch.int32).contiguous()),
-                icls_lab=_memo(D, "cls_ilab32", lambda: D["cls_ilab"].to(torch.int32).contiguous()),
+                topo_idx=_i32(D["topo_batch32"]), topo_y=topo_y, cls_idx=_i32(D["cls_batch32"]), cls_lab=clab, icls_lab=ilab,
                 cls_lab_raw=D["cls_clab"], icls_lab_raw=D["cls_ilab"], topo_lab_raw=D["topo_label"],
                 n_assm=D["n_assm"], max_cls_size=schedule.max_cls_size,
-                assm_idx=i32(D["assm_batch32"]) if D["n_assm"] > 0 else None,
+                assm_idx=_i32(D["assm_batch32"]) if D["n_assm"] > 0 else None,
                 assm_lab=_memo(D, "assm_labels32", lambda: torch.zeros(max(D["n_assm"], 1), dtype=torch.int32, device=dev)),
                 idx_csr=D.get("head_csr") or {})          # molecule -> its prediction rows, when the schedule's builder made them
         return spec
 
     # ------------------------------------------------------------------ per-molecule losses (forward only)
-    def _batched_schedule(self, schedule) -> bool:
-        return bool(_dev.DECODER_BATCHED and schedule.plan["all_live"] and schedule.plan["E1"] > 1)
-
     def atom_level(self, schedule, tensors, record_grad: bool = False):
         """The atom level of one teacher-forced pass -> (pooled cluster vectors, candidate atom vectors), or None where this
         schedule's atom level runs inside the step loop.  Teacher forcing makes it independent of the latent vectors
@@ -708,10 +675,9 @@ class HierMPNDecoder(ScoreHeads):
             raise NotImplementedError("HierMPNDecoder.molecule_losses: the differentiable form runs the heads as one node, which "
                                       "needs deferred, publishable parameter gradients (GGPM_DEFER_WGRADS on, every head "
                                       "parameter a hook-free leaf that requires grad, ggpm_amd._dev.HEADS_COMPOSITE on)")
-        if self.training and any(isinstance(m, nn.Dropout) and m.p > 0 for m in self.modules()):
-            raise NotImplementedError("HierMPNDecoder.molecule_losses runs without dropout: call model.eval() first")
+        check_no_dropout(self, "HierMPNDecoder.molecule_losses runs without dropout: call model.eval() first")
         tree_tensors, graph_tensors = tensors
-        B, H, L = len(orders), self.hidden_size, self.latent_size
+        B = len(orders)
         dev = tree_tensors[0].device
         if schedule is None:
             schedule = DecodeSchedule.from_graphs(graphs, tensors, orders, self.vocab, **self.schedule_hints())
@@ -724,10 +690,7 @@ class HierMPNDecoder(ScoreHeads):
                                       "AtomPlan, or ggpm_amd._dev.ATOM_DECODE off), which has no per-molecule form")
         with contextlib.nullcontext() if record else torch.no_grad():
             D = schedule.to_device(dev)._dev
-            if L == H:
-                init_vecs = src_root_vecs
-            else:
-                init_vecs = F_.linear([src_root_vecs.contiguous()], [L], self.W_root.weight, self.W_root.bias)[:, :H]
+            init_vecs = self._init_vecs(src_root_vecs)
             self._heads_in = None
             topo_vecs, cls_vecs, _, _ = self._states_batched(schedule, D, tree_tensors, graph_tensors, init_vecs, atom=atom,
                                                              heads_in_always=True)
@@ -741,9 +704,7 @@ class HierMPNDecoder(ScoreHeads):
                                                 torch.div(b.dest, C0, rounding_mode="floor") * C + b.dest % C0) for b in blocks]
                 spec = dict(spec, max_cls_size=C, assm_idx=pred_mol.repeat_interleave(C))
             spec = dict(spec, assm_blocks=blocks)
-            ok = lambda v: v.dim() == 2 and v.stride(1) == 1 and v.stride(0) % 4 == 0
-            tv = topo_vecs if ok(topo_vecs) else topo_vecs.contiguous()
-            cv = cls_vecs if ok(cls_vecs) else cls_vecs.contiguous()
+            tv, cv = _gemm_rows(topo_vecs), _gemm_rows(cls_vecs)
             if record:
                 return heads_fused.heads_parts(self, dict(spec, assm_pred_mol=pred_mol), src_tree_vecs, tv, cv, cand)
             rows = {}
@@ -794,7 +755,7 @@ class HierMPNDecoder(ScoreHeads):
     # ---- the atom level ahead of the encoder ---------------------------------------------------------------------------
     # Teacher forcing makes the decoder's atom level (and its backward) independent of the latent vector: it reads the
     # molecule's own bonds and the decoder's parameters only.  ``start_atom_level`` therefore issues it on its own stream
-    # BEFORE the encoder runs (HierPropertyVAE.forward), so that two chains of small latency-bound launches share the GPU
+    # BEFORE the encoder runs (property_vae._VAE._encode), so that two chains of small latency-bound launches share the GPU
     # instead of queueing behind each other; autograd runs a node's backward on the stream of its forward, so the backward
     # overlaps the encoder's backward the same way.  _dev.ATOM_AHEAD = False switches it off.
     _ATOM_STREAMS = {}
@@ -993,10 +954,9 @@ class HierMPNDecoder(ScoreHeads):
         H = self.hidden_size
         topo_scores = self.get_topo_score(src_tree_vecs, D["topo_batch32"], topo_vecs)
         # the loss kernels read float targets / int32 labels: converted once per schedule, not once per step
-        topo_loss = bce_with_logits_sum(topo_scores, _memo(D, "topo_label_f32", lambda: D["topo_label"].to(torch.float32)))
-        cls_loss, cls_pred, icls_pred = self.cls_losses(
-            src_tree_vecs, D["cls_batch32"], cls_vecs, _memo(D, "cls_clab32", lambda: D["cls_clab"].to(torch.int32).contiguous()),
-            _memo(D, "cls_ilab32", lambda: D["cls_ilab"].to(torch.int32).contiguous()))
+        topo_y, clab, ilab = self._labels(D)
+        topo_loss = bce_with_logits_sum(topo_scores, topo_y)
+        cls_loss, cls_pred, icls_pred = self.cls_losses(src_tree_vecs, D["cls_batch32"], cls_vecs, clab, ilab)
         labs = (D["topo_label"], D["cls_clab"], D["cls_ilab"])
         if topo_scores.is_cuda and len({t.dtype for t in labs}) == 1 and labs[0].dtype in (torch.int64, torch.int32):
             # the four accuracies in ONE launch (ggpm_head_accuracies) instead of ~19 elementwise / reduction launches

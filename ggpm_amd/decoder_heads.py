@@ -9,13 +9,46 @@ with the additive vocabulary mask of ``PairVocab.get_mask`` fused into the cross
 """
 from __future__ import annotations
 
+import importlib
+
 import torch
 import torch.nn as nn
 
+from . import _dev
 from . import _lib
 from . import functional as F_
 
 MAX_POS = 20
+
+
+def _memo(D: dict, key: str, make):
+    """``D[key]``, made on first use: tensors derived from a decode schedule's device tables live as long as the tables."""
+    v = D.get(key)
+    if v is None:
+        v = D[key] = make()
+    return v
+
+
+def _i32(t: torch.Tensor) -> torch.Tensor:
+    """``t`` as the kernels read an index: contiguous int32 (``t`` itself where it is that already)."""
+    return t if (t.dtype == torch.int32 and t.is_contiguous()) else t.to(torch.int32).contiguous()
+
+
+def _gemm_rows(v: torch.Tensor) -> torch.Tensor:
+    """``v`` as the GEMM takes its rows.  A [rows, H] view of a row-padded buffer (unit column stride, row stride % 4 == 0)
+    goes as it is: its leading dimension is the buffer's.  Anything else is copied."""
+    return v if v.dim() == 2 and v.stride(1) == 1 and v.stride(0) % 4 == 0 else v.contiguous()
+
+
+def check_no_dropout(module: nn.Module, message: str, each_dropout: bool = False) -> None:
+    """NotImplementedError(``message``) where a forward-only path would run with dropout active.  There are two meanings
+    of "active", both as the callers always had them: the decoders and ``sample`` go by ``module``'s own ``training``
+    flag, which is what ``.eval()`` on the decoder or on the model sets; ``log_likelihood`` and ``bound_loss``
+    (``each_dropout``) run the encoder too and go by every Dropout's own flag, so a model that is only partly in eval mode
+    (``model.train(); model.decoder.eval()``) is refused there and accepted by the decoder on its own."""
+    drops = [m for m in module.modules() if isinstance(m, nn.Dropout) and m.p > 0]
+    if any(m.training for m in drops) if each_dropout else (module.training and bool(drops)):
+        raise NotImplementedError(message)
 
 
 class _SoftmaxCE(torch.autograd.Function):
@@ -122,6 +155,8 @@ def _mlp(seq: nn.Sequential, parts, widths):
 class ScoreHeads(nn.Module):
     """topoNN / clsNN / iclsNN / matchNN / W_assm of reference ggpm/decoder.py:35-58 with their score functions."""
 
+    DECODE_MODULE = None    # "hier_decode" / "motif_decode": the module behind decode / decode_sampled, imported on first use
+
     def __init__(self, vocab, embed_size, hidden_size, latent_size, dropout):
         super().__init__()
         self.vocab, self.hidden_size, self.latent_size, self.embed_size = vocab, hidden_size, latent_size, embed_size
@@ -133,6 +168,45 @@ class ScoreHeads(nn.Module):
         self.topoNN, self.clsNN, self.iclsNN = head(1), head(n_cls), head(n_icls)
         self.matchNN = nn.Sequential(nn.Linear(hidden_size + embed_size + MAX_POS, hidden_size), nn.ReLU())
         self.W_assm = nn.Linear(hidden_size, latent_size)
+
+    def decode_backend(self):
+        return importlib.import_module("." + self.DECODE_MODULE, __package__)
+
+    def decode(self, mols, src_mol_vecs, greedy=True, max_decode_step=100, beam=5, graph_batch_factory=None):
+        """reference ggpm/decoder.py:303-472 (HierMPNDecoder) / 901-1095 (MotifDecoder) -> (results, graph_batch.get_mol())
+        on the library's kernels; the graph batch is ``graph_batch_factory`` or else ``self.graph_batch_factory``
+        (ggpm_amd.hier_decode / ggpm_amd.motif_decode)."""
+        return self.decode_backend().decode(self, mols, src_mol_vecs, greedy, max_decode_step, beam, graph_batch_factory)
+
+    def decode_sampled(self, mols, src_mol_vecs, seed=None, sample_ids=None, max_decode_step=100, beam=5,
+                       graph_batch_factory=None):
+        """The reference's ``decode(..., greedy=False)`` (ggpm/decoder.py:371-374, 409-416 / 984-987, 1024-1033) -> what
+        ``decode`` returns.  The topology decision is a Bernoulli draw and the beam entries are tried in an order drawn
+        without replacement; the draws come from a counter-based stream keyed by ``seed`` (an int, 64 bits used; ``None``
+        takes them from torch's default CPU generator) and by ``sample_ids`` (one int per molecule, default ``arange``), so
+        a molecule's draws do not depend on its batch (*Sampled decoding and the prior*)."""
+        return self.decode_backend().decode_sampled(self, mols, src_mol_vecs, seed, sample_ids, max_decode_step, beam,
+                                                    graph_batch_factory)
+
+    def _init_vecs(self, src_root_vecs):
+        """The root vectors as the tree level's initial state: themselves, or through ``W_root`` where latent != hidden."""
+        H, L = self.hidden_size, self.latent_size
+        if L == H:
+            return src_root_vecs
+        return F_.linear([src_root_vecs.contiguous()], [L], self.W_root.weight, self.W_root.bias)[:, :H]
+
+    @staticmethod
+    def _batched_schedule(schedule) -> bool:
+        """Whether this schedule runs the de-sequentialised tree-side levels (else the reference's step loop)."""
+        return bool(_dev.DECODER_BATCHED and schedule.plan["all_live"] and schedule.plan["E1"] > 1)
+
+    @staticmethod
+    def _labels(D):
+        """(topology targets as float, motif-class labels, attachment-class labels as int32): the loss kernels' forms of the
+        schedule's label tables, converted once per resident schedule."""
+        return (_memo(D, "topo_label_f32", lambda: D["topo_label"].to(torch.float32)),
+                _memo(D, "cls_clab32", lambda: D["cls_clab"].to(torch.int32).contiguous()),
+                _memo(D, "cls_ilab32", lambda: D["cls_ilab"].to(torch.int32).contiguous()))
 
     def _context(self, src_vecs, batch_idx):
         """``src_vecs.index_select(0, batch_idx)`` (ggpm/decoder.py:138,146,161) through the library's gather: its
@@ -147,9 +221,7 @@ class ScoreHeads(nn.Module):
         return F_.gather_rows(src, idx, F_.csr_from_index(idx, ncols=src.shape[0]), L, (L + 3) // 4 * 4)
 
     def _parts(self, src_vecs, batch_idx, vecs):
-        # (a [rows, H] view of a row-padded buffer goes to the GEMM as it is: its leading dimension is the buffer's)
-        v = vecs if vecs.dim() == 2 and vecs.stride(1) == 1 and vecs.stride(0) % 4 == 0 else vecs.contiguous()
-        return [v, self._context(src_vecs, batch_idx)], [self.hidden_size, self.latent_size]
+        return [_gemm_rows(vecs), self._context(src_vecs, batch_idx)], [self.hidden_size, self.latent_size]
 
     def get_topo_score(self, src_tree_vecs, batch_idx, topo_vecs):
         """reference ggpm/decoder.py:136-141"""

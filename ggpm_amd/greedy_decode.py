@@ -40,11 +40,10 @@ from itertools import chain
 
 import numpy as np
 import torch
-import torch.nn as nn
 
 from . import _lib
 from . import functional as F_
-from .decoder_heads import MAX_POS
+from .decoder_heads import MAX_POS, check_no_dropout
 
 MAX_NB = 12                                     # IncBase's max_nb
 MAX_SUB_NODES = 30                              # IncTree's max_sub_nodes: the width of a cgraph row
@@ -164,9 +163,7 @@ def check_beam(name, dec, beam):
 
 
 def _check_eval(run_cls, dec, what):
-    if dec.training and any(isinstance(m, nn.Dropout) and m.p > 0 for m in dec.modules()):
-        raise NotImplementedError("%s.%s runs without dropout: call model.eval() first (reconstruct.py does)"
-                                  % (run_cls.NAME, what))
+    check_no_dropout(dec, "%s.%s runs without dropout: call model.eval() first (reconstruct.py does)" % (run_cls.NAME, what))
 
 
 def _run(run_cls, dec, src_mol_vecs, max_decode_step, beam, factory, backend, sampling):
@@ -624,10 +621,7 @@ class DeviceBackend:
     def root(self, k0):
         """the root's heads on init_vecs -> (scores, motifs, attachments) [B, k0]"""
         dec, B, H = self.dec, self.B, self.H
-        if self.L == H:
-            init = self.src_root
-        else:
-            init = F_.linear([self.src_root], [self.L], dec.W_root.weight, dec.W_root.bias)[:, :H]
+        init = dec._init_vecs(self.src_root)
         parts = [np.arange(B)] + ([] if self.sample is None else [self.sample_ids])
         buf, offs = self._upload(parts)
         if self.sample is not None:

@@ -28,8 +28,9 @@ import torch.nn as nn
 from . import _dev
 from . import functional as F_
 from . import inc_encoder as IE
-from .decoder import DecodeSchedule, MAX_POS, _accuracy, _memo, _pinned_cls_size, level_states
-from .decoder_heads import ScoreHeads, bce_rows, bce_with_logits_sum, cross_entropy_rows, _mlp
+from .decoder import DecodeSchedule, MAX_POS, _accuracy, _pinned_cls_size, level_states
+from .decoder_heads import (ScoreHeads, _i32, _memo, _mlp, bce_rows, bce_with_logits_sum, check_no_dropout,
+                            cross_entropy_rows)
 
 
 class _MotifAssm(torch.autograd.Function):
@@ -200,6 +201,8 @@ def assm_plan(schedule: DecodeSchedule) -> AssmPlan:
 class MotifDecoder(ScoreHeads):
     """reference ggpm/decoder.py:475-899 (training forward, ``attention=False``)"""
 
+    DECODE_MODULE = "motif_decode"
+
     def __init__(self, vocab, avocab, rnn_type, embed_size, hidden_size, latent_size, depthT, depthG, dropout,
                  attention=False):
         super().__init__(vocab, embed_size, hidden_size, latent_size, dropout)
@@ -221,48 +224,28 @@ class MotifDecoder(ScoreHeads):
     def schedule_hints(self) -> dict:
         return {}
 
-    def decode(self, mols, src_mol_vecs, greedy=True, max_decode_step=100, beam=5, graph_batch_factory=None):
-        """reference ggpm/decoder.py:901-1095 -> (results, graph_batch.get_mol()) on the library's kernels; the graph batch
-        is ``graph_batch_factory`` or else ``self.graph_batch_factory`` (ggpm_amd.motif_decode)."""
-        from .motif_decode import decode
-        return decode(self, mols, src_mol_vecs, greedy, max_decode_step, beam, graph_batch_factory)
-
-    def decode_sampled(self, mols, src_mol_vecs, seed=None, sample_ids=None, max_decode_step=100, beam=5,
-                       graph_batch_factory=None):
-        """The reference's ``decode(..., greedy=False)`` (ggpm/decoder.py:984-987, 1024-1033) -> what ``decode`` returns.  The topology
-        decision is a Bernoulli draw and the beam entries are tried in an order drawn without replacement; the draws come
-        from a counter-based stream keyed by ``seed`` (an int, 64 bits used; ``None`` takes them from torch's default CPU
-        generator) and by ``sample_ids`` (one int per molecule, default ``arange``), so a molecule's draws do not depend
-        on its batch (*Sampled decoding and the prior*)."""
-        from .motif_decode import decode_sampled
-        return decode_sampled(self, mols, src_mol_vecs, seed, sample_ids, max_decode_step, beam, graph_batch_factory)
-
     # ------------------------------------------------------------------ forward
     def forward(self, mols, src_mol_vecs, graphs, tensors, orders, avg_loss=False, schedule: Optional[DecodeSchedule] = None):
         if avg_loss:
             raise NotImplementedError("MotifDecoder.mean_forward (avg_loss=True) is not part of this build: nothing in the "
                                       "reference calls it")
         tree_tensors, graph_tensors = tensors
-        B, H, L = len(orders), self.hidden_size, self.latent_size
+        B = len(orders)
         dev = tree_tensors[0].device
         if schedule is None:
             schedule = DecodeSchedule.from_graphs(graphs, tensors, orders, self.vocab)
         D = schedule.to_device(dev)._dev
         src_root_vecs, src_tree_vecs, src_graph_vecs = src_mol_vecs
-        if L == H:
-            init_vecs = src_root_vecs
-        else:
-            init_vecs = F_.linear([src_root_vecs.contiguous()], [L], self.W_root.weight, self.W_root.bias)[:, :H]
-        if _dev.DECODER_BATCHED and schedule.plan["all_live"] and schedule.plan["E1"] > 1:
+        init_vecs = self._init_vecs(src_root_vecs)
+        if self._batched_schedule(schedule):
             topo_vecs, cls_vecs = self._states_batched(schedule, D, tree_tensors, init_vecs)
         else:
             topo_vecs, cls_vecs = self._states_stepwise(schedule, tree_tensors, graph_tensors, init_vecs)
 
         topo_scores = self.get_topo_score(src_tree_vecs, D["topo_batch32"], topo_vecs)
-        topo_loss = bce_with_logits_sum(topo_scores, _memo(D, "topo_label_f32", lambda: D["topo_label"].to(torch.float32)))
-        cls_loss, cls_pred, icls_pred = self.cls_losses(
-            src_tree_vecs, D["cls_batch32"], cls_vecs, _memo(D, "cls_clab32", lambda: D["cls_clab"].to(torch.int32).contiguous()),
-            _memo(D, "cls_ilab32", lambda: D["cls_ilab"].to(torch.int32).contiguous()))
+        topo_y, clab, ilab = self._labels(D)
+        topo_loss = bce_with_logits_sum(topo_scores, topo_y)
+        cls_loss, cls_pred, icls_pred = self.cls_losses(src_tree_vecs, D["cls_batch32"], cls_vecs, clab, ilab)
         topo_acc = ((topo_scores.detach() >= 0).long() == D["topo_label"]).float().sum() / D["topo_label"].numel()
         cls_acc, icls_acc = _accuracy(cls_pred, D["cls_clab"]), _accuracy(icls_pred, D["cls_ilab"])
         assm_loss, assm_acc = self.assm_head(schedule, src_graph_vecs)
@@ -283,8 +266,7 @@ class MotifDecoder(ScoreHeads):
         record = torch.is_grad_enabled() and any(v is not None and v.requires_grad for v in src_mol_vecs)
         if record and out is not None:
             raise ValueError("MotifDecoder.molecule_losses: out= is for the forward-only form (autograd records this call)")
-        if self.training and any(isinstance(m, nn.Dropout) and m.p > 0 for m in self.modules()):
-            raise NotImplementedError("MotifDecoder.molecule_losses runs without dropout: call model.eval() first")
+        check_no_dropout(self, "MotifDecoder.molecule_losses runs without dropout: call model.eval() first")
         tree_tensors, graph_tensors = tensors
         B, H, L = len(orders), self.hidden_size, self.latent_size
         dev = tree_tensors[0].device
@@ -294,20 +276,16 @@ class MotifDecoder(ScoreHeads):
         src_root_vecs, src_tree_vecs, src_graph_vecs = src_mol_vecs
         with contextlib.nullcontext() if record else torch.no_grad():
             D = schedule.to_device(dev)._dev
-            if L == H:
-                init_vecs = src_root_vecs
-            else:
-                init_vecs = F_.linear([src_root_vecs.contiguous()], [L], self.W_root.weight, self.W_root.bias)[:, :H]
-            if _dev.DECODER_BATCHED and schedule.plan["all_live"] and schedule.plan["E1"] > 1:
+            init_vecs = self._init_vecs(src_root_vecs)
+            if self._batched_schedule(schedule):
                 topo_vecs, cls_vecs = self._states_batched(schedule, D, tree_tensors, init_vecs)
             else:
                 topo_vecs, cls_vecs = self._states_stepwise(schedule, tree_tensors, graph_tensors, init_vecs)
             topo_scores = self.get_topo_score(src_tree_vecs, D["topo_batch32"], topo_vecs)
             if record:
                 return self._parts_node(schedule, D, C, B, src_tree_vecs, src_graph_vecs, topo_scores, cls_vecs)
-            topo_rows = bce_rows(topo_scores, _memo(D, "topo_label_f32", lambda: D["topo_label"].to(torch.float32)))
-            clab = _memo(D, "cls_clab32", lambda: D["cls_clab"].to(torch.int32).contiguous())
-            ilab = _memo(D, "cls_ilab32", lambda: D["cls_ilab"].to(torch.int32).contiguous())
+            topo_y, clab, ilab = self._labels(D)
+            topo_rows = bce_rows(topo_scores, topo_y)
             parts = self._parts(src_tree_vecs, D["cls_batch32"], cls_vecs)
             cls_rows = cross_entropy_rows(_mlp(self.clsNN, *parts), clab)
             vocab = self.vocab
@@ -338,14 +316,11 @@ class MotifDecoder(ScoreHeads):
     def _parts_node(self, schedule, D, C, B, src_tree_vecs, src_graph_vecs, topo_scores, cls_vecs):
         """The differentiable tail of ``molecule_losses``: the class heads' scores, the attachment head's inputs, _MotifParts"""
         dev = topo_scores.device
-        clab = _memo(D, "cls_clab32", lambda: D["cls_clab"].to(torch.int32).contiguous())
-        ilab = _memo(D, "cls_ilab32", lambda: D["cls_ilab"].to(torch.int32).contiguous())
+        topo_y, clab, ilab = self._labels(D)
         parts = self._parts(src_tree_vecs, D["cls_batch32"], cls_vecs)
         cls_scores, icls_scores = _mlp(self.clsNN, *parts), _mlp(self.iclsNN, *parts)
         vocab = self.vocab
-        i32 = lambda t: t if (t.dtype == torch.int32 and t.is_contiguous()) else t.to(torch.int32).contiguous()
-        spec = dict(B=B, topo_y=_memo(D, "topo_label_f32", lambda: D["topo_label"].to(torch.float32)),
-                    topo_mol=i32(D["topo_batch32"]), cls_mol=i32(D["cls_batch32"]), clab=clab, ilab=ilab,
+        spec = dict(B=B, topo_y=topo_y, topo_mol=_i32(D["topo_batch32"]), cls_mol=_i32(D["cls_batch32"]), clab=clab, ilab=ilab,
                     mask=vocab.mask_on(dev) if hasattr(vocab, "mask_on") else vocab.mask.to(dev))
         ap = assm_plan(schedule)
         if ap.P == 0:

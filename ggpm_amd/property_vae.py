@@ -14,6 +14,7 @@ import torch.nn as nn
 
 from . import _dev
 from . import functional as F_
+from .decoder_heads import check_no_dropout
 from .encoder import HierMPNEncoder
 from .nnutils import make_cuda
 
@@ -312,99 +313,24 @@ class StepMetrics(dict):
         return dict.__repr__(self)
 
 
-class HierPropertyVAE(nn.Module):
-    """reference ggpm/property_vae.py:11-62 -- encoder, latent heads, teacher-forced decoder; the class
-    ``OPVNet.get_model('hier-prop')`` returns (ggpm/opvnet.py:4-9) and ``vae_train.py:78`` calls as
-    ``model(*batch, beta=beta)``.  Same constructor argument bag, sub-module names and ``state_dict`` keys.
-
-    ``forward(mols, graphs, tensors, orders, homos, lumos, beta, perturb_z=True)`` returns ``(loss, metrics)`` like the
-    reference; ``schedule=`` optionally passes a prepared :class:`ggpm_amd.decoder.DecodeSchedule` (the decoder's
-    integer bookkeeping, otherwise derived from ``graphs`` on every call).
-    """
-
-    def __init__(self, args):
-        super().__init__()
-        from .decoder import HierMPNDecoder
-        self.encoder = HierMPNEncoder(args.vocab, args.atom_vocab, args.rnn_type, args.embed_size, args.hidden_size,
-                                      args.depthT, args.depthG, args.dropout)
-        self.decoder = HierMPNDecoder(args.vocab, args.atom_vocab, args.rnn_type, args.embed_size, args.hidden_size,
-                                      args.latent_size, args.diterT, args.diterG, args.dropout)
-        if getattr(args, "tie_embedding", False):
-            self.encoder.tie_embedding(self.decoder.hmpn)
-        self.latent_size = args.latent_size
-        self.R_mean = nn.Linear(args.hidden_size, args.latent_size)
-        self.R_var = nn.Linear(args.hidden_size, args.latent_size)
-
-    def rsample(self, z_vecs, W_mean, W_var, perturb=True):
-        return rsample(z_vecs, W_mean, W_var, perturb)
-
-    def sample(self, batch_size, greedy=True, seed=None, max_decode_step=150, beam=5, graph_batch_factory=None):
-        """New molecules from the prior (what reference ggpm/property_vae.py:35-37 intends): seeded standard-normal latents
-        drawn on the device, then ``decode`` or, with ``greedy=False``, ``decode_sampled`` at the same seed ->
-        (results, molecules)."""
-        return _sample(self, batch_size, greedy, seed, max_decode_step, beam, graph_batch_factory)
-
-    def log_likelihood(self, batch, n_samples=1, seed=None, sample_ids=None, eps=None, max_cls_size=None, schedule=None):
-        """Per-molecule reconstruction terms, KL, ELBO and the ``n_samples``-sample importance-weighted bound of ``batch``
-        (the tuple ``self(*batch)`` takes) -> :class:`MolLikelihood`; forward only, see :func:`log_likelihood`."""
-        return log_likelihood(self, batch, n_samples, seed, sample_ids, eps, max_cls_size, schedule)
-
-    def bound_loss(self, batch, n_samples=1, objective="elbo", beta=1.0, mol_weights=None, seed=None, sample_ids=None,
-                   eps=None, max_cls_size=None, schedule=None):
-        """The ``n_samples``-sample ELBO (``objective="elbo"``) or importance-weighted bound (``"iwae"``) of ``batch`` as a
-        loss to train on, with optional per-molecule weights -> (loss, :class:`MolObjective`); see :func:`bound_loss`."""
-        return bound_loss(self, batch, n_samples, objective, beta, mol_weights, seed, sample_ids, eps, max_cls_size, schedule)
-
-    def reconstruct(self, batch, args=None):
-        """reference ggpm/property_vae.py:39-45: the no-grad encoder, the mean latent, greedy decode of 150 steps ->
-        (results, molecules).  The graph batch: ``args.graph_batch_factory``, else the decoder's."""
-        factory = _graph_batch_factory(self, args)
-        with torch.no_grad():
-            tree_tensors, graph_tensors = make_cuda(batch[2])
-            root_vecs = self.encoder.forward_padded(tree_tensors, graph_tensors)[0]
-            root_vecs, _ = rsample(root_vecs, self.R_mean, self.R_var, perturb=False)
-        return self.decoder.decode(batch[0], (root_vecs, root_vecs, root_vecs), greedy=True, max_decode_step=150,
-                                   graph_batch_factory=factory)
-
-    def forward(self, mols, graphs, tensors, orders, homos=None, lumos=None, beta=0.0, perturb_z=True, schedule=None):
-        if schedule is None:
-            schedule = getattr(graphs, "ggpm_schedule", None)       # dataloader.ScheduleAhead: built one batch ahead
-        if schedule is None and graphs is not None:
-            # the reference's call shape, ``model(*batch, beta=beta)`` (vae_train.py:78): derive the decoder's integer
-            # bookkeeping HERE, from the batch as it arrives (host arrays: no read-back), so that the atom level can be
-            # issued beside the encoder exactly as with a prepared schedule
-            from .decoder import DecodeSchedule
-            schedule = DecodeSchedule.from_graphs(graphs, tensors, orders, self.decoder.vocab, **self.decoder.schedule_hints())
-        tree_tensors, graph_tensors = tensors = make_cuda(tensors)
-        F_.mark("fwd: inputs on the device")
-        self.decoder.start_atom_level(schedule, tensors)       # independent of the latent vector: issued beside the encoder
-        F_.mark("fwd: atom level posted")
-        # beside the atom level's chain of small launches the encoder's levels take half as many (twice as large)
-        # workgroups: the chain's launches then find free compute units instead of waiting for the encoder's to drain
-        from . import fused
-        beside = getattr(self.decoder, "_atom_ahead", None) is not None and _dev.ENC_NARROW
-        fused.NARROW[0] = beside
-        try:
-            root_vecs = self.encoder.forward_padded(tree_tensors, graph_tensors)[0]
-        finally:
-            fused.NARROW[0] = False
-        root_vecs, kl_div = rsample(root_vecs, self.R_mean, self.R_var, perturb_z)
-        F_.mark("fwd: encoder + rsample issued")
-        loss, wacc, iacc, tacc, sacc = self.decoder(mols, (root_vecs, root_vecs, root_vecs), graphs, tensors, orders,
-                                                    schedule=schedule)
-        loss = loss + beta * kl_div
-        F_.mark("fwd: heads and losses issued")
-        if os.environ.get("GGPM_LAZY_METRICS", "1") != "0":
-            return loss, StepMetrics((loss, kl_div, wacc, iacc, tacc, sacc))
-        return loss, {'Loss': loss.item(), 'KL:': kl_div.item(), 'Word': float(wacc), 'I-Word': float(iacc),
-                      'Topo': float(tacc), 'Assm': float(sacc)}
-
-
 class PropStepMetrics(StepMetrics):
     """The metrics dictionary of ``HierPropOptVAE.forward`` (ggpm/property_vae.py:249-252), read lazily like StepMetrics
     (values are taken as fp32 on the device, python floats when read)."""
 
     _KEYS = ('Loss', 'KL', 'Recs_Loss', 'HOMO_MSE', 'LUMO_MSE', 'Word', 'I-Word', 'Topo', 'Assm')
+
+
+def _eager_metrics() -> bool:
+    """Whether this call reads its metrics inside the forward, as the reference does (read at call time)."""
+    return os.environ.get("GGPM_LAZY_METRICS", "1") == "0"
+
+
+def _metrics(cls, values):
+    """The metrics of one step under ``cls._KEYS``: ``cls(values)``, read on first access (StepMetrics), or in the eager form
+    the reference's dictionary of python floats (``.item()`` inside the forward)."""
+    if _eager_metrics():
+        return {k: v.item() if isinstance(v, torch.Tensor) else float(v) for k, v in zip(cls._KEYS, values)}
+    return cls(values)
 
 
 class LossClipped:
@@ -440,7 +366,7 @@ class _ClipNegativeLoss:
     def clip_negative_loss(self, loss):
         noise = lambda: torch.normal(mean=0.5, std=0.5, size=loss.size(), dtype=loss.dtype, device=loss.device,  # noqa
                                      generator=self.clip_generator)
-        if os.environ.get("GGPM_LAZY_METRICS", "1") == "0":
+        if _eager_metrics():
             if loss > 0:
                 return False, loss
             return True, loss * 0 + noise()
@@ -448,7 +374,189 @@ class _ClipNegativeLoss:
         return LossClipped(clipped.reshape(-1)[0]), torch.where(clipped, loss * 0 + noise(), loss)
 
 
-class HierPropOptVAE(_ClipNegativeLoss, nn.Module):
+class _VAE(nn.Module):
+    """What the four models share: the sub-modules, the encode step, the decoder's bookkeeping, the forward of the two
+    models without property heads, and the methods that differ in nothing but the model they are called on."""
+
+    HIER = True                 # encoder(tree_tensors, graph_tensors) and a decoder with an atom level; False: tree-only
+    PROPERTY_HEADS = False      # the HOMO / LUMO heads on the two latent halves (the -opt models)
+
+    def _build(self, args, encoder_cls, decoder_cls, tie_always=False):
+        """The sub-modules, in the order that fixes the state_dict, ``parameters()`` (FlatAdam's flat buffer, bound_loss's
+        parameter tuple) and the draws of the initial weights: encoder, decoder, [property_optim], R_mean, R_var,
+        [loss_weigh].  Tying draws nothing and registers nothing on the model, so where it stands among them shows nowhere."""
+        heads = self.PROPERTY_HEADS
+        if heads and args.latent_size % 2 != 0:
+            raise ValueError("%s: latent_size must be even (the HOMO and LUMO heads read one half each), got %d"
+                             % (type(self).__name__, args.latent_size))
+        self.encoder = encoder_cls(args.vocab, args.atom_vocab, args.rnn_type, args.embed_size, args.hidden_size,
+                                   args.depthT, args.depthG, args.dropout)
+        self.decoder = decoder_cls(args.vocab, args.atom_vocab, args.rnn_type, args.embed_size, args.hidden_size,
+                                   args.latent_size, args.diterT, args.diterG, args.dropout)
+        if tie_always or getattr(args, "tie_embedding", False):
+            self.encoder.tie_embedding(self.decoder.hmpn)
+        self.latent_size = args.latent_size // 2 if heads else args.latent_size
+        if heads:
+            from .property import LossWeigh, PropertyOptimizer
+            self.property_optim = PropertyOptimizer(input_size=self.latent_size, hidden_size=args.linear_hidden_size,
+                                                    dropout=args.dropout)
+            self.property_optim_step = args.property_optim_step
+        self.R_mean = nn.Linear(args.hidden_size, args.latent_size)
+        self.R_var = nn.Linear(args.hidden_size, args.latent_size)
+        if heads:
+            self.loss_scaling = bool(getattr(args, "loss_scaling", False))
+            if self.loss_scaling:
+                self.loss_weigh = LossWeigh()
+            self._clip_gen = None
+
+    def _decode_schedule(self, graphs, tensors, orders, schedule):
+        """The decoder's bookkeeping: the one passed, the one ScheduleAhead attached to ``graphs`` (built one batch ahead),
+        or derived here."""
+        if schedule is None:
+            schedule = getattr(graphs, "ggpm_schedule", None)
+        if schedule is None and graphs is not None:
+            # the reference's call shape, ``model(*batch, beta=beta)`` (vae_train.py:78): derive the decoder's integer
+            # bookkeeping HERE, from the batch as it arrives (host arrays: no read-back), so that the atom level can be
+            # issued beside the encoder exactly as with a prepared schedule
+            from .decoder import DecodeSchedule
+            schedule = DecodeSchedule.from_graphs(graphs, tensors, orders, self.decoder.vocab, **self.decoder.schedule_hints())
+        return schedule
+
+    def _encode(self, tensors, schedule=None, atom_ahead=False):
+        """The encoder's root vectors of ``tensors`` (on the device).  ``atom_ahead`` (the hierarchical pair's training
+        forward): the decoder's atom level of ``schedule`` is posted first -- it does not depend on the latent vector, so it
+        is issued beside the encoder."""
+        tree_tensors, graph_tensors = tensors
+        if not self.HIER:
+            return self.encoder.forward_padded(tree_tensors)[0]
+        if not atom_ahead:
+            return self.encoder.forward_padded(tree_tensors, graph_tensors)[0]
+        from . import fused
+        F_.mark("fwd: inputs on the device")
+        self.decoder.start_atom_level(schedule, tensors)
+        F_.mark("fwd: atom level posted")
+        # beside the atom level's chain of small launches the encoder's levels take half as many (twice as large)
+        # workgroups: the chain's launches then find free compute units instead of waiting for the encoder's to drain
+        fused.NARROW[0] = getattr(self.decoder, "_atom_ahead", None) is not None and _dev.ENC_NARROW
+        try:
+            return self.encoder.forward_padded(tree_tensors, graph_tensors)[0]
+        finally:
+            fused.NARROW[0] = False
+
+    def forward(self, mols, graphs, tensors, orders, homos=None, lumos=None, beta=0.0, perturb_z=True, schedule=None):
+        schedule = self._decode_schedule(graphs, tensors, orders, schedule)
+        tensors = make_cuda(tensors)
+        root_vecs = self._encode(tensors, schedule, atom_ahead=True)
+        root_vecs, kl_div = rsample(root_vecs, self.R_mean, self.R_var, perturb_z)
+        F_.mark("fwd: encoder + rsample issued")
+        loss, wacc, iacc, tacc, sacc = self.decoder(mols, (root_vecs, root_vecs, root_vecs), graphs, tensors, orders,
+                                                    schedule=schedule)
+        loss = loss + beta * kl_div
+        F_.mark("fwd: heads and losses issued")
+        return loss, _metrics(StepMetrics, (loss, kl_div, wacc, iacc, tacc, sacc))
+
+    def rsample(self, z_vecs, perturb=True):
+        return rsample(z_vecs, self.R_mean, self.R_var, perturb)
+
+    def sample(self, batch_size, greedy=True, seed=None, max_decode_step=150, beam=5, graph_batch_factory=None):
+        """New molecules from the prior (what reference ggpm/property_vae.py:35-37 intends): seeded standard-normal latents
+        drawn on the device, then ``decode`` or, with ``greedy=False``, ``decode_sampled`` at the same seed ->
+        (results, molecules)."""
+        return _sample(self, batch_size, greedy, seed, max_decode_step, beam, graph_batch_factory)
+
+    def log_likelihood(self, batch, n_samples=1, seed=None, sample_ids=None, eps=None, max_cls_size=None, schedule=None):
+        """Per-molecule reconstruction terms, KL, ELBO and the ``n_samples``-sample importance-weighted bound of ``batch``
+        (the tuple ``self(*batch)`` takes) -> :class:`MolLikelihood`; forward only, see :func:`log_likelihood`."""
+        return log_likelihood(self, batch, n_samples, seed, sample_ids, eps, max_cls_size, schedule)
+
+    def bound_loss(self, batch, n_samples=1, objective="elbo", beta=1.0, mol_weights=None, seed=None, sample_ids=None,
+                   eps=None, max_cls_size=None, schedule=None):
+        """The ``n_samples``-sample ELBO (``objective="elbo"``) or importance-weighted bound (``"iwae"``) of ``batch`` as a
+        loss to train on, with optional per-molecule weights -> (loss, :class:`MolObjective`); see :func:`bound_loss`."""
+        return bound_loss(self, batch, n_samples, objective, beta, mol_weights, seed, sample_ids, eps, max_cls_size, schedule)
+
+    def reconstruct(self, batch, args=None):
+        """reference ggpm/property_vae.py:39-45 (101-109, 169-188, 299-318 for the other three): the no-grad encoder, the
+        mean latent, for the -opt models the property heads on it, greedy decode of 150 steps -> (results, molecules), for
+        the -opt models ((homo [B], lumo [B]), (results, molecules)).  The graph batch: ``args.graph_batch_factory``, else
+        the decoder's."""
+        factory = _graph_batch_factory(self, args)
+        with torch.no_grad():
+            root_vecs, _ = rsample(self._encode(make_cuda(batch[2])), self.R_mean, self.R_var, perturb=False)
+            props = self._property_heads(root_vecs) if self.PROPERTY_HEADS else None
+        decoded = self.decoder.decode(batch[0], (root_vecs, root_vecs, root_vecs), greedy=True, max_decode_step=150,
+                                      graph_batch_factory=factory)
+        return (props, decoded) if self.PROPERTY_HEADS else decoded
+
+
+class _PropOptVAE(_ClipNegativeLoss, _VAE):
+    """The two property-optimising models: the heads on the two latent halves and the forward with their losses."""
+
+    PROPERTY_HEADS = True
+    KL_IN_LOSS = False          # whether ``beta * KL`` joins the reconstruction loss (before ``loss_scaling``)
+
+    def _property_heads(self, z):
+        half = self.latent_size
+        return self.property_optim.predict(homo_vecs=z[:, :half], lumo_vecs=z[:, half:])
+
+    def encode_latent(self, tensors, perturb=False):
+        """Encoder + rsample of the reference's search (ggpm/property_control.py:194-200): -> (latent [B, 2 half], kl)."""
+        return rsample(self._encode(make_cuda(tensors)), self.R_mean, self.R_var, perturb)
+
+    def predict_properties(self, batch):
+        """The property predictions the reference's ``reconstruct`` forms before it decodes (ggpm/property_vae.py:169-186):
+        encoder, the mean latent (no noise), both heads -- under no-grad, so every stage runs its forward-only form.
+        ``batch`` is a reference batch (mols, graphs, tensors, orders, homos, lumos).  -> (homo [B], lumo [B])."""
+        with torch.no_grad():
+            return self._property_heads(self.encode_latent(batch[2], perturb=False)[0])
+
+    def forward(self, mols, graphs, tensors, orders, homos, lumos, beta=0.0, perturb_z=True, schedule=None):
+        schedule = self._decode_schedule(graphs, tensors, orders, schedule)
+        tensors = make_cuda(tensors)
+        root_vecs = self._encode(tensors, schedule, atom_ahead=True)
+        if perturb_z or self.KL_IN_LOSS:
+            root_vecs, kl_div = rsample(root_vecs, self.R_mean, self.R_var, perturb_z)
+        else:
+            # z = mean: KL is a metric only, so R_var stays out of the graph (its .grad stays None, as in the reference)
+            root_vecs, kl_div = _KLHead.apply(root_vecs, self.R_mean.weight, self.R_mean.bias,
+                                              self.R_var.weight.detach(), self.R_var.bias.detach(), None)
+        dev = root_vecs.device
+        t_homo = torch.as_tensor(homos, dtype=torch.float32).to(dev, non_blocking=True)
+        t_lumo = torch.as_tensor(lumos, dtype=torch.float32).to(dev, non_blocking=True)
+        homo_loss, lumo_loss, _, _ = self.property_optim.forward_latent(root_vecs, (t_homo, t_lumo))
+        loss, wacc, iacc, tacc, sacc = self.decoder(mols, (root_vecs, root_vecs, root_vecs), graphs, tensors, orders,
+                                                    schedule=schedule)
+        if self.KL_IN_LOSS:
+            loss = loss + beta * kl_div
+        if self.loss_scaling:
+            loss = self.loss_weigh.compute_recon_loss(loss)
+            homo_loss, lumo_loss = self.loss_weigh.compute_prop_loss(homo_loss, lumo_loss)
+        total_loss = loss + homo_loss + lumo_loss
+        clipped, total_loss = self.clip_negative_loss(total_loss)
+        return total_loss, _metrics(PropStepMetrics, (total_loss, kl_div, loss, homo_loss, lumo_loss, wacc, iacc, tacc, sacc)), \
+            clipped
+
+
+class HierPropertyVAE(_VAE):
+    """reference ggpm/property_vae.py:11-62 -- encoder, latent heads, teacher-forced decoder; the class
+    ``OPVNet.get_model('hier-prop')`` returns (ggpm/opvnet.py:4-9) and ``vae_train.py:78`` calls as
+    ``model(*batch, beta=beta)``.  Same constructor argument bag, sub-module names and ``state_dict`` keys.
+
+    ``forward(mols, graphs, tensors, orders, homos, lumos, beta, perturb_z=True)`` returns ``(loss, metrics)`` like the
+    reference; ``schedule=`` optionally passes a prepared :class:`ggpm_amd.decoder.DecodeSchedule` (the decoder's
+    integer bookkeeping, otherwise derived from ``graphs`` on every call).
+    """
+
+    def __init__(self, args):
+        super().__init__()
+        from .decoder import HierMPNDecoder
+        self._build(args, HierMPNEncoder, HierMPNDecoder)
+
+    def rsample(self, z_vecs, W_mean, W_var, perturb=True):
+        return rsample(z_vecs, W_mean, W_var, perturb)
+
+
+class HierPropOptVAE(_PropOptVAE):
     """reference ggpm/property_vae.py:130-254 -- HierPropertyVAE's encoder, rsample and teacher-forced decoder plus the
     HOMO / LUMO heads on the two latent halves (``property_optim``, ggpm_amd.property) and optionally ``LossWeigh``; the
     class ``OPVNet.get_model('hier-prop-opt')`` returns and ``vae_fine_tune.py`` trains.  Same argument bag (plus
@@ -469,117 +577,7 @@ class HierPropOptVAE(_ClipNegativeLoss, nn.Module):
     def __init__(self, args):
         super().__init__()
         from .decoder import HierMPNDecoder
-        from .property import PropertyOptimizer, LossWeigh
-        if args.latent_size % 2 != 0:
-            raise ValueError("HierPropOptVAE: latent_size must be even (the HOMO and LUMO heads read one half each), got %d"
-                             % args.latent_size)
-        self.encoder = HierMPNEncoder(args.vocab, args.atom_vocab, args.rnn_type, args.embed_size, args.hidden_size,
-                                      args.depthT, args.depthG, args.dropout)
-        self.decoder = HierMPNDecoder(args.vocab, args.atom_vocab, args.rnn_type, args.embed_size, args.hidden_size,
-                                      args.latent_size, args.diterT, args.diterG, args.dropout)
-        self.latent_size = args.latent_size // 2
-        self.property_optim = PropertyOptimizer(input_size=self.latent_size, hidden_size=args.linear_hidden_size,
-                                                dropout=args.dropout)
-        if getattr(args, "tie_embedding", False):
-            self.encoder.tie_embedding(self.decoder.hmpn)
-        self.property_optim_step = args.property_optim_step
-        self.R_mean = nn.Linear(args.hidden_size, args.latent_size)
-        self.R_var = nn.Linear(args.hidden_size, args.latent_size)
-        self.loss_scaling = bool(getattr(args, "loss_scaling", False))
-        if self.loss_scaling:
-            self.loss_weigh = LossWeigh()
-        self._clip_gen = None
-
-    def rsample(self, z_vecs, perturb=True):
-        return rsample(z_vecs, self.R_mean, self.R_var, perturb)
-
-    def encode_latent(self, tensors, perturb=False):
-        """Encoder + rsample of the reference's search (ggpm/property_control.py:194-200): -> (latent [B, 2 half], kl)."""
-        tree_tensors, graph_tensors = make_cuda(tensors)
-        root_vecs = self.encoder.forward_padded(tree_tensors, graph_tensors)[0]
-        return rsample(root_vecs, self.R_mean, self.R_var, perturb)
-
-    def predict_properties(self, batch):
-        """The property predictions the reference's ``reconstruct`` forms before it decodes (ggpm/property_vae.py:169-186):
-        encoder, the mean latent (no noise), both heads -- under no-grad, so every stage runs its forward-only form.
-        ``batch`` is a reference batch (mols, graphs, tensors, orders, homos, lumos).  -> (homo [B], lumo [B])."""
-        return _predict_properties(self, batch)
-
-    def sample(self, batch_size, greedy=True, seed=None, max_decode_step=150, beam=5, graph_batch_factory=None):
-        """New molecules from the prior (what reference ggpm/property_vae.py:35-37 intends): seeded standard-normal latents
-        drawn on the device, then ``decode`` or, with ``greedy=False``, ``decode_sampled`` at the same seed ->
-        (results, molecules)."""
-        return _sample(self, batch_size, greedy, seed, max_decode_step, beam, graph_batch_factory)
-
-    def log_likelihood(self, batch, n_samples=1, seed=None, sample_ids=None, eps=None, max_cls_size=None, schedule=None):
-        """Per-molecule reconstruction terms, KL, ELBO and the ``n_samples``-sample importance-weighted bound of ``batch``
-        (the tuple ``self(*batch)`` takes) -> :class:`MolLikelihood`; forward only, see :func:`log_likelihood`."""
-        return log_likelihood(self, batch, n_samples, seed, sample_ids, eps, max_cls_size, schedule)
-
-    def bound_loss(self, batch, n_samples=1, objective="elbo", beta=1.0, mol_weights=None, seed=None, sample_ids=None,
-                   eps=None, max_cls_size=None, schedule=None):
-        """The ``n_samples``-sample ELBO (``objective="elbo"``) or importance-weighted bound (``"iwae"``) of ``batch`` as a
-        loss to train on, with optional per-molecule weights -> (loss, :class:`MolObjective`); see :func:`bound_loss`."""
-        return bound_loss(self, batch, n_samples, objective, beta, mol_weights, seed, sample_ids, eps, max_cls_size, schedule)
-
-    def reconstruct(self, batch, args=None):
-        """reference ggpm/property_vae.py:169-188: the no-grad encoder, the mean latent, the property heads on it, greedy
-        decode of 150 steps -> ((homo [B], lumo [B]), (results, molecules)).  The graph batch: ``args.graph_batch_factory``,
-        else the decoder's."""
-        factory = _graph_batch_factory(self, args)
-        with torch.no_grad():
-            root_vecs, _ = self.encode_latent(batch[2], perturb=False)
-            half = self.latent_size
-            props = self.property_optim.predict(homo_vecs=root_vecs[:, :half], lumo_vecs=root_vecs[:, half:])
-        return props, self.decoder.decode(batch[0], (root_vecs, root_vecs, root_vecs), greedy=True, max_decode_step=150,
-                                          graph_batch_factory=factory)
-
-    def forward(self, mols, graphs, tensors, orders, homos, lumos, beta=0.0, perturb_z=True, schedule=None):
-        from . import fused
-        from .decoder import DecodeSchedule
-        if schedule is None:
-            schedule = getattr(graphs, "ggpm_schedule", None)
-        if schedule is None and graphs is not None:
-            schedule = DecodeSchedule.from_graphs(graphs, tensors, orders, self.decoder.vocab, **self.decoder.schedule_hints())
-        tree_tensors, graph_tensors = tensors = make_cuda(tensors)
-        self.decoder.start_atom_level(schedule, tensors)       # independent of the latent vector: issued beside the encoder
-        beside = getattr(self.decoder, "_atom_ahead", None) is not None and _dev.ENC_NARROW
-        fused.NARROW[0] = beside
-        try:
-            root_vecs = self.encoder.forward_padded(tree_tensors, graph_tensors)[0]
-        finally:
-            fused.NARROW[0] = False
-        if perturb_z:
-            root_vecs, kl_div = rsample(root_vecs, self.R_mean, self.R_var, True)
-        else:
-            # z = mean: KL is a metric only, so R_var stays out of the graph (its .grad stays None, as in the reference)
-            root_vecs, kl_div = _KLHead.apply(root_vecs, self.R_mean.weight, self.R_mean.bias,
-                                              self.R_var.weight.detach(), self.R_var.bias.detach(), None)
-        dev = root_vecs.device
-        t_homo = torch.as_tensor(homos, dtype=torch.float32).to(dev, non_blocking=True)
-        t_lumo = torch.as_tensor(lumos, dtype=torch.float32).to(dev, non_blocking=True)
-        homo_loss, lumo_loss, _, _ = self.property_optim.forward_latent(root_vecs, (t_homo, t_lumo))
-        loss, wacc, iacc, tacc, sacc = self.decoder(mols, (root_vecs, root_vecs, root_vecs), graphs, tensors, orders,
-                                                    schedule=schedule)
-        if self.loss_scaling:
-            loss = self.loss_weigh.compute_recon_loss(loss)
-            homo_loss, lumo_loss = self.loss_weigh.compute_prop_loss(homo_loss, lumo_loss)
-        total_loss = loss + homo_loss + lumo_loss
-        clipped, total_loss = self.clip_negative_loss(total_loss)
-        if os.environ.get("GGPM_LAZY_METRICS", "1") != "0":
-            return total_loss, PropStepMetrics((total_loss, kl_div, loss, homo_loss, lumo_loss, wacc, iacc, tacc, sacc)), \
-                clipped
-        return total_loss, {'Loss': total_loss.item(), 'KL': kl_div.item(), 'Recs_Loss': loss.item(),
-                            'HOMO_MSE': homo_loss.item(), 'LUMO_MSE': lumo_loss.item(), 'Word': float(wacc),
-                            'I-Word': float(iacc), 'Topo': float(tacc), 'Assm': float(sacc)}, bool(clipped)
-
-
-def _predict_properties(model, batch):
-    tensors = batch[2]
-    with torch.no_grad():
-        z, _ = model.encode_latent(tensors, perturb=False)
-        half = model.latent_size
-        return model.property_optim.predict(homo_vecs=z[:, :half], lumo_vecs=z[:, half:])
+        self._build(args, HierMPNEncoder, HierMPNDecoder)
 
 
 def _sample(model, batch_size, greedy, seed, max_decode_step, beam, graph_batch_factory):
@@ -590,8 +588,7 @@ def _sample(model, batch_size, greedy, seed, max_decode_step, beam, graph_batch_
     factory = graph_batch_factory
     if factory is None:
         factory = _graph_batch_factory(model, getattr(model, "args", None))
-    if dec.training and any(isinstance(m, nn.Dropout) and m.p > 0 for m in dec.modules()):
-        raise NotImplementedError("%s.sample runs without dropout: call model.eval() first" % type(model).__name__)
+    check_no_dropout(dec, "%s.sample runs without dropout: call model.eval() first" % type(model).__name__)
     if int(batch_size) < 1:
         raise ValueError("%s.sample: batch_size %d" % (type(model).__name__, batch_size))
     lo, hi = split_seed(seed)
@@ -606,11 +603,10 @@ def _sample(model, batch_size, greedy, seed, max_decode_step, beam, graph_batch_
 
 def _likelihood_args(model, what, batch, n_samples, sample_ids, eps, max_cls_size, schedule):
     """The argument checks ``log_likelihood`` and ``bound_loss`` share (``what``: the method's name in the messages) ->
-    (class name, decoder, device, K, B, L, schedule, pinned max_cls_size, hierarchical decoder?)"""
-    from .decoder import HierMPNDecoder, _pinned_cls_size
+    (class name, decoder, device, K, B, L, schedule, pinned max_cls_size)"""
+    from .decoder import _pinned_cls_size
     name, dec = type(model).__name__, model.decoder
-    if any(m.training and isinstance(m, nn.Dropout) and m.p > 0 for m in model.modules()):
-        raise NotImplementedError("%s.%s runs without dropout: call model.eval() first" % (name, what))
+    check_no_dropout(model, "%s.%s runs without dropout: call model.eval() first" % (name, what), each_dropout=True)
     graphs, tensors, orders = batch[1], batch[2], batch[3]
     B, L = len(orders), model.R_mean.weight.shape[0]
     dev = model.R_mean.weight.device
@@ -626,12 +622,30 @@ def _likelihood_args(model, what, batch, n_samples, sample_ids, eps, max_cls_siz
                              % (name, what, tuple(eps.shape), K, B, L))
     if sample_ids is not None and len(sample_ids) != B:
         raise ValueError("%s.%s: %d sample_ids for %d molecules" % (name, what, len(sample_ids), B))
-    schedule = _motif_schedule(model, graphs, tensors, orders, schedule)
+    schedule = model._decode_schedule(graphs, tensors, orders, schedule)
     if schedule is None:
         raise ValueError("%s.%s: the batch carries no graphs (batch[1]) and no schedule= was given: nothing to "
                          "derive the decoder's bookkeeping from" % (name, what))
-    C = _pinned_cls_size(schedule, max_cls_size)
-    return name, dec, dev, K, B, L, schedule, C, isinstance(dec, HierMPNDecoder)
+    return name, dec, dev, K, B, L, schedule, _pinned_cls_size(schedule, max_cls_size)
+
+
+def _likelihood_encode(model, what, tensors, schedule, record_grad):
+    """What ``log_likelihood`` and ``bound_loss`` run once for all K draws, under the caller's grad mode: the atom level
+    of the hierarchical decoder (``atom_level``, not the one posted beside the encoder) and the encoder ->
+    (tensors on the device, atom, root vectors, stats)"""
+    stats = dict(encoder_calls=0, atom_level_calls=0, decoder_passes=0)
+    tensors = make_cuda(tensors)
+    atom = None
+    if model.HIER:
+        atom = model.decoder.atom_level(schedule, tensors, record_grad=record_grad)
+        if atom is None:
+            raise NotImplementedError("%s.%s: this batch runs the decoder's step loop (no tree message at all, "
+                                      "no AtomPlan, or a batched form switched off in ggpm_amd._dev), which has no "
+                                      "per-molecule form" % (type(model).__name__, what))
+        stats["atom_level_calls"] = 1
+    root_vecs = model._encode(tensors)
+    stats["encoder_calls"] = 1
+    return tensors, atom, root_vecs, stats
 
 
 MolLikelihood = namedtuple("MolLikelihood", ["parts", "kl", "elbo", "iwae", "z", "stats"])
@@ -658,24 +672,11 @@ def log_likelihood(model, batch, n_samples=1, seed=None, sample_ids=None, eps=No
     zeros with K = 1 is the ``perturb_z=False`` latent.  ``max_cls_size``: see ``molecule_losses`` -- None is the training
     convention (the parts then add up to the training loss x B), an int makes numbers comparable across batches."""
     from .greedy_decode import split_seed
-    name, dec, dev, K, B, L, schedule, C, hier = _likelihood_args(model, "log_likelihood", batch, n_samples, sample_ids, eps,
-                                                                  max_cls_size, schedule)
+    name, dec, dev, K, B, L, schedule, C = _likelihood_args(model, "log_likelihood", batch, n_samples, sample_ids, eps,
+                                                            max_cls_size, schedule)
     mols, graphs, tensors, orders = batch[0], batch[1], batch[2], batch[3]
-    stats = dict(encoder_calls=0, atom_level_calls=0, decoder_passes=0)
     with torch.no_grad():
-        tree_tensors, graph_tensors = tensors = make_cuda(tensors)
-        atom = None
-        if hier:
-            atom = dec.atom_level(schedule, tensors)
-            if atom is None:
-                raise NotImplementedError("%s.log_likelihood: this batch runs the decoder's step loop (no tree message at all, "
-                                          "no AtomPlan, or a batched form switched off in ggpm_amd._dev), which has no "
-                                          "per-molecule form" % name)
-            stats["atom_level_calls"] = 1
-            root_vecs = model.encoder.forward_padded(tree_tensors, graph_tensors)[0]
-        else:
-            root_vecs = model.encoder.forward_padded(tree_tensors)[0]
-        stats["encoder_calls"] = 1
+        tensors, atom, root_vecs, stats = _likelihood_encode(model, "log_likelihood", tensors, schedule, record_grad=False)
         Rm, Rv = model.R_mean, model.R_var
         mean, pre_var = _latent_heads(root_vecs, Rm.weight, Rm.bias, Rv.weight, Rv.bias)
         if eps is None:
@@ -710,8 +711,8 @@ def bound_loss(model, batch, n_samples=1, objective="elbo", beta=1.0, mol_weight
     floats (a host sequence or a float32 tensor on the model's device), a constant.  Every other argument is
     ``log_likelihood``'s.  One encoder pass and one atom-level pass serve the K decoder passes, forward and backward."""
     from .greedy_decode import split_seed
-    name, dec, dev, K, B, L, schedule, C, hier = _likelihood_args(model, "bound_loss", batch, n_samples, sample_ids, eps,
-                                                                  max_cls_size, schedule)
+    name, dec, dev, K, B, L, schedule, C = _likelihood_args(model, "bound_loss", batch, n_samples, sample_ids, eps,
+                                                            max_cls_size, schedule)
     if objective not in F_.BOUND_OBJECTIVES:
         raise ValueError("%s.bound_loss: objective %r (one of %s)" % (name, objective, sorted(F_.BOUND_OBJECTIVES)))
     beta = float(beta)
@@ -728,21 +729,8 @@ def bound_loss(model, batch, n_samples=1, objective="elbo", beta=1.0, mol_weight
         if tuple(w.shape) != (B,):
             raise ValueError("%s.bound_loss: %d mol_weights for %d molecules" % (name, w.numel(), B))
     mols, graphs, tensors, orders = batch[0], batch[1], batch[2], batch[3]
-    stats = dict(encoder_calls=0, atom_level_calls=0, decoder_passes=0)
     with torch.enable_grad():
-        tree_tensors, graph_tensors = tensors = make_cuda(tensors)
-        atom = None
-        if hier:
-            atom = dec.atom_level(schedule, tensors, record_grad=True)
-            if atom is None:
-                raise NotImplementedError("%s.bound_loss: this batch runs the decoder's step loop (no tree message at all, "
-                                          "no AtomPlan, or a batched form switched off in ggpm_amd._dev), which has no "
-                                          "per-molecule form" % name)
-            stats["atom_level_calls"] = 1
-            root_vecs = model.encoder.forward_padded(tree_tensors, graph_tensors)[0]
-        else:
-            root_vecs = model.encoder.forward_padded(tree_tensors)[0]
-        stats["encoder_calls"] = 1
+        tensors, atom, root_vecs, stats = _likelihood_encode(model, "bound_loss", tensors, schedule, record_grad=True)
         if eps is None:
             lo, hi = split_seed(seed)
             eps = F_.sample_latent_normal(K, B, L, lo, hi, ids=sample_ids, device=dev)
@@ -769,26 +757,11 @@ def _graph_batch_factory(model, args):
     if factory is None:
         factory = getattr(model.decoder, "graph_batch_factory", None)
     if factory is None:
-        from .motif_decoder import MotifDecoder
-        if isinstance(model.decoder, MotifDecoder):
-            from .motif_decode import NO_FACTORY
-        else:
-            from .hier_decode import NO_FACTORY
-        raise NotImplementedError(NO_FACTORY)
+        raise NotImplementedError(model.decoder.decode_backend().NO_FACTORY)
     return factory
 
 
-def _motif_schedule(model, graphs, tensors, orders, schedule):
-    """The decoder's bookkeeping: the one passed, the one ScheduleAhead attached to ``graphs``, or derived here."""
-    from .decoder import DecodeSchedule
-    if schedule is None:
-        schedule = getattr(graphs, "ggpm_schedule", None)
-    if schedule is None and graphs is not None:
-        schedule = DecodeSchedule.from_graphs(graphs, tensors, orders, model.decoder.vocab, **model.decoder.schedule_hints())
-    return schedule
-
-
-class PropertyVAE(nn.Module):
+class PropertyVAE(_VAE):
     """reference ggpm/property_vae.py:64-127 -- the tree-only model ``OPVNet.get_model('prop')`` returns (vae_train.py
     --model-type prop): ``MotifEncoder``, the latent heads, the teacher-forced ``MotifDecoder``.  Same constructor argument
     bag, sub-module names and ``state_dict`` keys.
@@ -797,65 +770,16 @@ class PropertyVAE(nn.Module):
     loss = (topo + cls + icls + assm) / B + beta * KL; metrics under the reference's keys ('KL:' with its colon).
     """
 
+    HIER = False
+
     def __init__(self, args):
         super().__init__()
         from .encoder import MotifEncoder
         from .motif_decoder import MotifDecoder
-        self.latent_size = args.latent_size
-        self.encoder = MotifEncoder(args.vocab, args.atom_vocab, args.rnn_type, args.embed_size, args.hidden_size,
-                                    args.depthT, args.depthG, args.dropout)
-        self.decoder = MotifDecoder(args.vocab, args.atom_vocab, args.rnn_type, args.embed_size, args.hidden_size,
-                                    args.latent_size, args.diterT, args.diterG, args.dropout)
-        if getattr(args, "tie_embedding", False):
-            self.encoder.tie_embedding(self.decoder.hmpn)
-        self.R_mean = nn.Linear(args.hidden_size, args.latent_size)
-        self.R_var = nn.Linear(args.hidden_size, args.latent_size)
-
-    def rsample(self, z_vecs, perturb=True):
-        return rsample(z_vecs, self.R_mean, self.R_var, perturb)
-
-    def sample(self, batch_size, greedy=True, seed=None, max_decode_step=150, beam=5, graph_batch_factory=None):
-        """New molecules from the prior (what reference ggpm/property_vae.py:35-37 intends): seeded standard-normal latents
-        drawn on the device, then ``decode`` or, with ``greedy=False``, ``decode_sampled`` at the same seed ->
-        (results, molecules)."""
-        return _sample(self, batch_size, greedy, seed, max_decode_step, beam, graph_batch_factory)
-
-    def log_likelihood(self, batch, n_samples=1, seed=None, sample_ids=None, eps=None, max_cls_size=None, schedule=None):
-        """Per-molecule reconstruction terms, KL, ELBO and the ``n_samples``-sample importance-weighted bound of ``batch``
-        (the tuple ``self(*batch)`` takes) -> :class:`MolLikelihood`; forward only, see :func:`log_likelihood`."""
-        return log_likelihood(self, batch, n_samples, seed, sample_ids, eps, max_cls_size, schedule)
-
-    def bound_loss(self, batch, n_samples=1, objective="elbo", beta=1.0, mol_weights=None, seed=None, sample_ids=None,
-                   eps=None, max_cls_size=None, schedule=None):
-        """The ``n_samples``-sample ELBO (``objective="elbo"``) or importance-weighted bound (``"iwae"``) of ``batch`` as a
-        loss to train on, with optional per-molecule weights -> (loss, :class:`MolObjective`); see :func:`bound_loss`."""
-        return bound_loss(self, batch, n_samples, objective, beta, mol_weights, seed, sample_ids, eps, max_cls_size, schedule)
-
-    def reconstruct(self, batch, args=None):
-        """reference ggpm/property_vae.py:101-109: the no-grad encoder, the mean latent, greedy decode of 150 steps ->
-        (results, molecules).  The graph batch: ``args.graph_batch_factory``, else the decoder's."""
-        factory = _graph_batch_factory(self, args)
-        with torch.no_grad():
-            tree_tensors, _ = make_cuda(batch[2])
-            root_vecs, _ = rsample(self.encoder.forward_padded(tree_tensors)[0], self.R_mean, self.R_var, perturb=False)
-        return self.decoder.decode(batch[0], (root_vecs, root_vecs, root_vecs), greedy=True, max_decode_step=150,
-                                   graph_batch_factory=factory)
-
-    def forward(self, mols, graphs, tensors, orders, homos=None, lumos=None, beta=0.0, perturb_z=True, schedule=None):
-        schedule = _motif_schedule(self, graphs, tensors, orders, schedule)
-        tree_tensors, graph_tensors = tensors = make_cuda(tensors)
-        root_vecs = self.encoder.forward_padded(tree_tensors)[0]
-        root_vecs, kl_div = rsample(root_vecs, self.R_mean, self.R_var, perturb_z)
-        loss, wacc, iacc, tacc, sacc = self.decoder(mols, (root_vecs, root_vecs, root_vecs), graphs, tensors, orders,
-                                                    schedule=schedule)
-        loss = loss + beta * kl_div
-        if os.environ.get("GGPM_LAZY_METRICS", "1") != "0":
-            return loss, StepMetrics((loss, kl_div, wacc, iacc, tacc, sacc))
-        return loss, {'Loss': loss.item(), 'KL:': kl_div.item(), 'Word': float(wacc), 'I-Word': float(iacc),
-                      'Topo': float(tacc), 'Assm': float(sacc)}
+        self._build(args, MotifEncoder, MotifDecoder)
 
 
-class PropOptVAE(_ClipNegativeLoss, nn.Module):
+class PropOptVAE(_PropOptVAE):
     """reference ggpm/property_vae.py:257-397 -- the tree-only model ``OPVNet.get_model('prop-opt')`` returns
     (vae_fine_tune_indv_opt.py): PropertyVAE's encoder, rsample and decoder plus the HOMO / LUMO heads and optionally
     ``LossWeigh``, as HierPropOptVAE, with the reference's two differences:
@@ -865,95 +789,15 @@ class PropOptVAE(_ClipNegativeLoss, nn.Module):
     ``forward(...) -> (total_loss, metrics, clipped)`` with HierPropOptVAE's keys, ``clip_negative_loss`` and conventions.
     """
 
+    HIER = False
+    KL_IN_LOSS = True
+
     def __init__(self, args):
         super().__init__()
         from .encoder import MotifEncoder
         from .motif_decoder import MotifDecoder
-        from .property import PropertyOptimizer, LossWeigh
-        if args.latent_size % 2 != 0:
-            raise ValueError("PropOptVAE: latent_size must be even (the HOMO and LUMO heads read one half each), got %d"
-                             % args.latent_size)
-        self.encoder = MotifEncoder(args.vocab, args.atom_vocab, args.rnn_type, args.embed_size, args.hidden_size,
-                                    args.depthT, args.depthG, args.dropout)
-        self.decoder = MotifDecoder(args.vocab, args.atom_vocab, args.rnn_type, args.embed_size, args.hidden_size,
-                                    args.latent_size, args.diterT, args.diterG, args.dropout)
-        self.encoder.tie_embedding(self.decoder.hmpn)
-        self.latent_size = args.latent_size // 2
-        self.property_optim = PropertyOptimizer(input_size=self.latent_size, hidden_size=args.linear_hidden_size,
-                                                dropout=args.dropout)
-        self.property_optim_step = args.property_optim_step
-        self.R_mean = nn.Linear(args.hidden_size, args.latent_size)
-        self.R_var = nn.Linear(args.hidden_size, args.latent_size)
-        self.loss_scaling = bool(getattr(args, "loss_scaling", False))
-        if self.loss_scaling:
-            self.loss_weigh = LossWeigh()
-        self._clip_gen = None
-
-    def rsample(self, z_vecs, perturb=True):
-        return rsample(z_vecs, self.R_mean, self.R_var, perturb)
-
-    def encode_latent(self, tensors, perturb=False):
-        """MotifEncoder + rsample: -> (latent [B, 2 half], kl)."""
-        tree_tensors, _ = make_cuda(tensors)
-        return rsample(self.encoder.forward_padded(tree_tensors)[0], self.R_mean, self.R_var, perturb)
-
-    def predict_properties(self, batch):
-        """As HierPropOptVAE.predict_properties, on MotifEncoder's latent: -> (homo [B], lumo [B])."""
-        return _predict_properties(self, batch)
-
-    def sample(self, batch_size, greedy=True, seed=None, max_decode_step=150, beam=5, graph_batch_factory=None):
-        """New molecules from the prior (what reference ggpm/property_vae.py:35-37 intends): seeded standard-normal latents
-        drawn on the device, then ``decode`` or, with ``greedy=False``, ``decode_sampled`` at the same seed ->
-        (results, molecules)."""
-        return _sample(self, batch_size, greedy, seed, max_decode_step, beam, graph_batch_factory)
-
-    def log_likelihood(self, batch, n_samples=1, seed=None, sample_ids=None, eps=None, max_cls_size=None, schedule=None):
-        """Per-molecule reconstruction terms, KL, ELBO and the ``n_samples``-sample importance-weighted bound of ``batch``
-        (the tuple ``self(*batch)`` takes) -> :class:`MolLikelihood`; forward only, see :func:`log_likelihood`."""
-        return log_likelihood(self, batch, n_samples, seed, sample_ids, eps, max_cls_size, schedule)
-
-    def bound_loss(self, batch, n_samples=1, objective="elbo", beta=1.0, mol_weights=None, seed=None, sample_ids=None,
-                   eps=None, max_cls_size=None, schedule=None):
-        """The ``n_samples``-sample ELBO (``objective="elbo"``) or importance-weighted bound (``"iwae"``) of ``batch`` as a
-        loss to train on, with optional per-molecule weights -> (loss, :class:`MolObjective`); see :func:`bound_loss`."""
-        return bound_loss(self, batch, n_samples, objective, beta, mol_weights, seed, sample_ids, eps, max_cls_size, schedule)
-
-    def reconstruct(self, batch, args=None):
-        """reference ggpm/property_vae.py:299-318: the no-grad encoder, the mean latent, the property heads on it, greedy
-        decode of 150 steps -> ((homo [B], lumo [B]), (results, molecules)).  The graph batch: ``args.graph_batch_factory``,
-        else the decoder's."""
-        factory = _graph_batch_factory(self, args)
-        with torch.no_grad():
-            root_vecs, _ = self.encode_latent(batch[2], perturb=False)
-            half = self.latent_size
-            props = self.property_optim.predict(homo_vecs=root_vecs[:, :half], lumo_vecs=root_vecs[:, half:])
-        return props, self.decoder.decode(batch[0], (root_vecs, root_vecs, root_vecs), greedy=True, max_decode_step=150,
-                                          graph_batch_factory=factory)
+        self._build(args, MotifEncoder, MotifDecoder, tie_always=True)
 
     def optimize_recs(self, batch, args=None):
         raise NotImplementedError("PropOptVAE.optimize_recs: the reference's version calls PropertyOptimizer.optimize, "
                                   "which ggpm/property_optimizer.py does not define")
-
-    def forward(self, mols, graphs, tensors, orders, homos, lumos, beta=0.0, perturb_z=True, schedule=None):
-        schedule = _motif_schedule(self, graphs, tensors, orders, schedule)
-        tree_tensors, graph_tensors = tensors = make_cuda(tensors)
-        root_vecs = self.encoder.forward_padded(tree_tensors)[0]
-        root_vecs, kl_div = rsample(root_vecs, self.R_mean, self.R_var, perturb_z)
-        dev = root_vecs.device
-        t_homo = torch.as_tensor(homos, dtype=torch.float32).to(dev, non_blocking=True)
-        t_lumo = torch.as_tensor(lumos, dtype=torch.float32).to(dev, non_blocking=True)
-        homo_loss, lumo_loss, _, _ = self.property_optim.forward_latent(root_vecs, (t_homo, t_lumo))
-        loss, wacc, iacc, tacc, sacc = self.decoder(mols, (root_vecs, root_vecs, root_vecs), graphs, tensors, orders,
-                                                    schedule=schedule)
-        loss = loss + beta * kl_div
-        if self.loss_scaling:
-            loss = self.loss_weigh.compute_recon_loss(loss)
-            homo_loss, lumo_loss = self.loss_weigh.compute_prop_loss(homo_loss, lumo_loss)
-        total_loss = loss + homo_loss + lumo_loss
-        clipped, total_loss = self.clip_negative_loss(total_loss)
-        if os.environ.get("GGPM_LAZY_METRICS", "1") != "0":
-            return total_loss, PropStepMetrics((total_loss, kl_div, loss, homo_loss, lumo_loss, wacc, iacc, tacc, sacc)), \
-                clipped
-        return total_loss, {'Loss': total_loss.item(), 'KL': kl_div.item(), 'Recs_Loss': loss.item(),
-                            'HOMO_MSE': homo_loss.item(), 'LUMO_MSE': lumo_loss.item(), 'Word': float(wacc),
-                            'I-Word': float(iacc), 'Topo': float(tacc), 'Assm': float(sacc)}, bool(clipped)
