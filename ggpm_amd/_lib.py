@@ -14,6 +14,9 @@ from . import build as _build
 
 _LIB = None
 
+# include/ggpm_hip.h: the GGPM_ERR_* codes every entry point returns
+GGPM_OK, GGPM_ERR_ARG, GGPM_ERR_LAUNCH, GGPM_ERR_UNSUPPORTED, GGPM_ERR_WORKSPACE = range(5)
+
 # name -> (restype, [argtypes]); mirrors include/ggpm_hip.h one to one (the level calls' last two: opts, stream)
 P = c_void_p
 I = c_int
@@ -49,6 +52,7 @@ SIGNATURES = {
     "ggpm_onehot": (I, [P, I, I, P, I, I, I, P]),
     "ggpm_embed_graph": (I, [P, I, P, I, I, I, I, P, I, P, I, P]),
     "ggpm_level_bf16_storage": (I, [I, I]),
+    "ggpm_level_form_query": (I, [I, I, I, I, I, P, P]),                  # opts: ggpm_level_opts* or NULL, out: ggpm_level_form*
     "ggpm_gru_backward_stashes": (I, [P, I, I, I, POINTER(c_void_p), POINTER(c_void_p)]),
     "ggpm_lstm_backward_stashes": (I, [P, I, I, I, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p)]),
     "ggpm_sum_slots": (I, [P, I, c_size_t, P, P]),

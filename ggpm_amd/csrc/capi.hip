@@ -18,6 +18,14 @@ extern "C" const char* ggpm_error_string(int code) {
 
 extern "C" int ggpm_padded_hidden(int H) { return ggpm_round_up(H, 16); }
 
+// The form a GRU / LSTM level call takes (include/ggpm_hip.h): host only, decided by the launchers' own functions
+extern "C" int ggpm_level_form_query(int lstm, int E1, int H, int sparse, int training, const ggpm_level_opts* opts,
+                                     ggpm_level_form* out) {
+    if (E1 <= 0 || H <= 0 || !out) return GGPM_ERR_ARG;
+    const ggpm_level_opts& o = ggpm_opts_or_default(opts);
+    return lstm ? ggpm_lstm_level_form(E1, H, sparse, training, o, out) : ggpm_gru_level_form(E1, H, sparse, training, o, out);
+}
+
 // ---------------------------------------------------------------- timing sink (debug/bench only)
 namespace {
 struct Span { hipEvent_t a, b; double flops; };

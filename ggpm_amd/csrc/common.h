@@ -193,6 +193,13 @@ hipEvent_t ggpm_wgrad_event(int i);          // small pool of re-recordable even
 // enough that every weight-gradient contraction over their stashes runs on the bf16 tall kernel, which then reads the
 // stashes as they are.  (GRU levels; exported as ggpm_level_bf16_storage for the tests' choice of oracle mode.)
 bool ggpm_bf16_storage_applies(int E1, int H);       // (gemm.hip: one stash slot alone must qualify for the bf16 tall kernel)
+// ... as a level call decides it from its gate mode; keeps_arrays: a training forward, its forward-only form (h_out), a backward
+inline bool ggpm_level_st16(int gate_mode, bool sparse, bool keeps_arrays, int E1, int H) {
+    return gate_mode == 1 && !sparse && keeps_arrays && ggpm_bf16_storage_applies(E1, H);
+}
+// ggpm_level_form_query per cell (mpn_gru.hip / mpn_lstm.hip, beside the launchers whose decisions they report); E1, H > 0
+int ggpm_gru_level_form(int E1, int H, int sparse, int training, const ggpm_level_opts& o, ggpm_level_form* out);
+int ggpm_lstm_level_form(int E1, int H, int sparse, int training, const ggpm_level_opts& o, ggpm_level_form* out);
 // out[i] = sum_t src[t][i] over `slots` slots of `slot_floats` elements, src fp32 or bf16 (first half of its buffer); fixed order
 int ggpm_sum_slots_any(const float* src, int slots, size_t slot_floats, float* out, bool src_bf16, ggpm_stream_t stream);
 // Fixed-point levels (ggpm_level_opts.fixed_slot).  ggpm_sum_slots_pair_grouped: hi[i] + lo[i] = sum_t src[t][i] over `slots`

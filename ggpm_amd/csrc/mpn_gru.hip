@@ -788,17 +788,52 @@ inline int gate_mode(const ggpm_level_opts& o, int Hp, bool rt2, bool single_gro
     const size_t need = (size_t)16 * (Hp + 4) * sizeof(float) + 2 * ggpm_split_image_bytes(16, Hp);
     return need <= 160 * 1024 ? 2 : 0;
 }
-inline bool single_group(int E1, int Hp) { return pick_tg(E1, Hp / 16) >= Hp / 16; }
+
+// The form of a level call -- what the impl functions, the launchers below and ggpm_level_form_query (include/ggpm_hip.h) all
+// decide through: the call's geometry (LevelPlan) and, per depth step, whether kernel A takes the B launch's product with it
+// and the dynamic LDS of the two launches (StepLds).
+struct LevelPlan { int tg; bool rt2; int gm; };      // tiles per column group, two row tiles per workgroup, gate mode 0 / 1 / 2
+inline LevelPlan level_plan(const ggpm_level_opts& o, int E1, int Hp, bool sparse) {
+    LevelPlan p;
+    p.tg = pick_tg(E1, Hp / 16);
+    p.rt2 = use_rt2(o, E1, Hp, sparse);
+    p.gm = gate_mode(o, Hp, p.rt2, p.tg >= Hp / 16, sparse);
+    return p;
+}
+struct StepLds { int fuse; size_t a, b; };      // b: what the B launch takes when there is one
+// a forward depth step; with_b: the step forms q' (every step but the level's last)
+inline StepLds fwd_step(int Hp, int tg, bool rt2, int gm, bool with_b) {
+    const int rows = rt2 ? 32 : 16;
+    const bool split = gm == 2;
+    const size_t tile_b = (size_t)rows * (Hp + 4) * sizeof(float), img_b = ggpm_split_image_bytes(rows, Hp);
+    const size_t lds_fused = split ? tile_b + 3 * img_b : 3 * tile_b;
+    StepLds p;
+    p.fuse = (!rt2 && with_b && ggpm_ceil_div(Hp / 16, tg) == 1 && lds_fused <= 160 * 1024 && !env_no_fuse_b()) ? 1 : 0;
+    p.a = p.fuse ? lds_fused : split ? tile_b + 2 * img_b : 2 * tile_b;
+    p.b = split ? img_b : tile_b;
+    return p;
+}
+// a backward depth step; with_b: the step forms dS / dG for the one below it; final_pass: the sparse backward's t = 0 launch
+inline StepLds bwd_step(int Hp, int tg, bool rt2, int gm, bool with_b, bool final_pass) {
+    const int rows = rt2 ? 32 : 16, NT = Hp / 16;
+    const bool split = gm == 2;
+    const size_t tile_b = (size_t)rows * (Hp + 4) * sizeof(float), img_b = ggpm_split_image_bytes(rows, Hp);
+    const size_t lds_fused = split ? tile_b + 3 * img_b : 4 * tile_b;
+    StepLds p;
+    p.fuse = (!rt2 && with_b && !final_pass && ggpm_ceil_div(NT, tg) == 1 && NT <= 2 * GGPM_NWA && lds_fused <= 160 * 1024 &&
+              !env_no_fuse_b()) ? 1 : 0;
+    p.a = p.fuse ? lds_fused : split ? tile_b + img_b : 2 * tile_b;
+    p.b = split ? 2 * img_b : 2 * tile_b;                        // kernel B: the dz_pre and dm_pre rows
+    return p;
+}
 
 void launch_fwd(GruFwdArgs a, bool rt2, bool stash, bool with_b, double flops1, hipStream_t s) {
     const int Hp = a.Hp, NT = Hp / 16;
     const int rows = rt2 ? 32 : 16;
     dim3 grid_a(ggpm_ceil_div(a.E1, rows), ggpm_ceil_div(NT, a.tg));
-    const bool split = a.bf16 == 2;
-    const size_t tile_b = (size_t)rows * (Hp + 4) * sizeof(float), img_b = ggpm_split_image_bytes(rows, Hp);
-    const size_t lds_b = split ? img_b : tile_b;
-    const size_t lds_fused = split ? tile_b + 3 * img_b : 3 * tile_b;
-    a.fuse_b = (!rt2 && with_b && grid_a.y == 1 && lds_fused <= 160 * 1024 && !env_no_fuse_b()) ? 1 : 0;
+    const StepLds step = fwd_step(Hp, a.tg, rt2, a.bf16, with_b);
+    const size_t lds_a = step.a, lds_b = step.b;
+    a.fuse_b = step.fuse;
     static unsigned long long* dbg_buf = nullptr;
     static int dbg_count = 0;
     a.dbg = nullptr;
@@ -807,7 +842,6 @@ void launch_fwd(GruFwdArgs a, bool rt2, bool stash, bool with_b, double flops1, 
         a.dbg = dbg_buf;
     }
     if (a.fuse_b) with_b = false;
-    const size_t lds_a = a.fuse_b ? lds_fused : split ? tile_b + 2 * img_b : 2 * tile_b;
     ggpm_timing_begin(0, s, ((a.fuse_b ? 1 : 0) + (a.h0_zero ? 0 : 2)) * flops1);     // the first depth has no gate products
     auto go = [&](auto kernel) {
         set_lds(kernel, lds_a);
@@ -850,14 +884,10 @@ void launch_bwd(GruBwdArgs a, bool rt2, bool with_b, double flops1, hipStream_t 
     const int Hp = a.Hp, NT = Hp / 16;
     const int rows = rt2 ? 32 : 16;
     dim3 grid_a(ggpm_ceil_div(a.E1, rows), ggpm_ceil_div(NT, a.tg));
-    const bool split = a.bf16 == 2;
-    const size_t tile_b = (size_t)rows * (Hp + 4) * sizeof(float), img_b = ggpm_split_image_bytes(rows, Hp);
-    const size_t lds = split ? 2 * img_b : 2 * tile_b;                        // kernel B: the dz_pre and dm_pre rows
-    const size_t lds_fused = split ? tile_b + 3 * img_b : 4 * tile_b;
-    a.fuse_b = (!rt2 && with_b && !a.final_pass && grid_a.y == 1 && NT <= 2 * GGPM_NWA && lds_fused <= 160 * 1024 &&
-                !env_no_fuse_b()) ? 1 : 0;
+    const StepLds step = bwd_step(Hp, a.tg, rt2, a.bf16, with_b, a.final_pass != 0);
+    const size_t lds_a = step.a, lds = step.b;
+    a.fuse_b = step.fuse;
     if (a.fuse_b) with_b = false;
-    const size_t lds_a = a.fuse_b ? lds_fused : split ? tile_b + img_b : 2 * tile_b;
     static unsigned long long* dbg_buf = nullptr;
     static int dbg_count = 0;
     a.dbg = nullptr;
@@ -903,6 +933,23 @@ static int gru_shape_ok(int Hp) {
     return (size_t)2 * 16 * (Hp + 4) * sizeof(float) <= 160 * 1024;
 }
 
+// ggpm_level_form_query (capi.hip) for a GRU level: the decisions above, nothing launched
+int ggpm_gru_level_form(int E1, int H, int sparse, int training, const ggpm_level_opts& o, ggpm_level_form* out) {
+    const int Hp = ggpm_padded_hidden(H);
+    if (!gru_shape_ok(Hp)) return GGPM_ERR_UNSUPPORTED;
+    const LevelPlan plan = level_plan(o, E1, Hp, sparse != 0);
+    const StepLds f = fwd_step(Hp, plan.tg, plan.rt2, plan.gm, true);
+    const StepLds b = bwd_step(Hp, plan.tg, plan.rt2, plan.gm, true, false);
+    *out = ggpm_level_form{};
+    out->Hp = Hp; out->tiles = Hp / 16; out->tg = plan.tg; out->groups = ggpm_ceil_div(Hp / 16, plan.tg);
+    out->rt2 = plan.rt2 ? 1 : 0; out->gate_mode = plan.gm;
+    out->st16 = ggpm_level_st16(plan.gm, sparse != 0, training || o.h_out, E1, H) ? 1 : 0;
+    out->fuse_fwd = f.fuse;
+    out->lds_fwd_a = f.a; out->lds_fwd_b = (f.fuse && !sparse) ? 0 : f.b;      // (a sparse forward forms q^0 by a B launch)
+    if (training) { out->fuse_bwd = b.fuse; out->lds_bwd_a = b.a; out->lds_bwd_b = b.fuse ? 0 : b.b; }
+    return GGPM_OK;
+}
+
 namespace {
 __global__ void sparse_init_state(const float* __restrict__ h_in, const unsigned char* __restrict__ frozen,
                                   float* __restrict__ H0, int Hp) {
@@ -928,8 +975,9 @@ static int gru_forward_impl(int E1, int H, int depth, const float* Xz, const flo
     if (!gru_shape_ok(Hp)) return GGPM_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     const size_t HH = (size_t)Hp * Hp, slot = (size_t)E1 * Hp;
-    const bool rt2 = use_rt2(o, E1, Hp, frozen != nullptr);
-    const int bf16 = gate_mode(o, Hp, rt2, single_group(E1, Hp), frozen != nullptr);      // gate mode 0 / 1 / 2
+    const LevelPlan plan = level_plan(o, E1, Hp, frozen != nullptr);
+    const bool rt2 = plan.rt2;
+    const int bf16 = plan.gm;      // gate mode 0 / 1 / 2
     const size_t mstep = ggpm_packed_matrix_floats(Hp, bf16);
     float* pWz = wpack; float* pWh = wpack + mstep; float* pUr = wpack + 2 * mstep;
     float* pbu = wpack + 3 * ggpm_packed_matrix_slot(Hp);
@@ -940,7 +988,7 @@ static int gru_forward_impl(int E1, int H, int depth, const float* Xz, const flo
         if (!o.weights_packed) ggpm_launch_pack(pk, 3, s);
     }
     dim3 ig(ggpm_ceil_div(Hp, 256), E1);
-    const int tg0 = pick_tg(E1, Hp / 16);
+    const int tg0 = plan.tg;
     const bool gathered = o.gather_h && o.gather_idx && frozen;
     if (frozen) {      // sparse_forward: start from the caller's state, q^0 = U_r h^0 + b_u by one B launch
         // (h_in == Hs: the caller put the masked start state -- frozen rows' states, zero elsewhere -- into slot 0 itself;
@@ -949,7 +997,7 @@ static int gru_forward_impl(int E1, int H, int depth, const float* Xz, const flo
         GruFwdArgs a0 = {};
         a0.E1 = E1; a0.Hp = Hp; a0.tg = tg0; a0.Hnew = Hs; a0.Qnew = Qs; a0.Ur = pUr; a0.bu = pbu; a0.bf16 = bf16;
         if (gathered) { a0.src_h = o.gather_h; a0.src_idx = o.gather_idx; }
-        const size_t lds_b = bf16 == 2 ? ggpm_split_image_bytes(ROWS, Hp) : (size_t)ROWS * (Hp + 4) * sizeof(float);
+        const size_t lds_b = fwd_step(Hp, tg0, false, bf16, true).b;
         dim3 grid_a(ggpm_ceil_div(E1, ROWS), ggpm_ceil_div(Hp / 16, tg0));
         if (bf16 == 2) { set_lds(gru_fwd_b<2, 1>, lds_b); gru_fwd_b<2, 1><<<grid_a, GGPM_NWA * 64, lds_b, s>>>(a0); }
         else if (bf16 == 1) { set_lds(gru_fwd_b<1, 1>, lds_b); gru_fwd_b<1, 1><<<grid_a, GGPM_NWA * 64, lds_b, s>>>(a0); }
@@ -957,13 +1005,13 @@ static int gru_forward_impl(int E1, int H, int depth, const float* Xz, const flo
     }
     // dense levels start from h^0 = 0: the first depth launch knows that (h0_zero), so H^0 / Q^0 are never materialised
 
-    const int tg = pick_tg(E1, Hp / 16);
+    const int tg = plan.tg;
     const double flops1 = 2.0 * (double)(E1 - 1) * H * H;   // algorithmic flops of ONE gate product
     static const char* const abl = ggpm_dev_env("GGPM_ABLATE");
     // forward-only form (ggpm_level_opts.h_out): the training forward's steps and roundings, without stashes
     const bool infer = !save_for_backward && o.h_out;
     // bf16 storage (tile_mma.h): bf16 gate products, dense, training, every stash contraction on the bf16 tall kernel
-    const bool st16 = bf16 == 1 && !frozen && (save_for_backward || infer) && ggpm_bf16_storage_applies(E1, H);
+    const bool st16 = ggpm_level_st16(bf16, frozen != nullptr, save_for_backward || infer, E1, H);
     int run_depth = o.run_depth;
     if (run_depth <= 0 || run_depth > depth || frozen || !(save_for_backward || infer)) run_depth = depth;
     // fixed-point level (ggpm_level_opts.fixed_slot): only the last step's stash slot is ever read
@@ -1084,8 +1132,9 @@ static int gru_backward_impl(int E1, int H, int depth, const float* Xr, const fl
     // (the packed transposes come first: their place does not depend on E1, so a sequence of calls that shares one
     // `work` buffer and one set of weights packs them once -- ggpm_level_opts.weights_packed)
     float* w = work;
-    const bool rt2 = use_rt2(o, E1, Hp, frozen != nullptr);
-    const int bf16 = gate_mode(o, Hp, rt2, single_group(E1, Hp), frozen != nullptr);      // gate mode 0 / 1 / 2
+    const LevelPlan plan = level_plan(o, E1, Hp, frozen != nullptr);
+    const bool rt2 = plan.rt2;
+    const int bf16 = plan.gm;      // gate mode 0 / 1 / 2
     const size_t mstep = ggpm_packed_matrix_floats(Hp, bf16);
     float* pWzT = w; float* pWhT = w + mstep; float* pUrT = w + 2 * mstep; w += 3 * ggpm_packed_matrix_slot(Hp);
     float* DMP = w; w += (size_t)depth * slot;
@@ -1113,9 +1162,9 @@ static int gru_backward_impl(int E1, int H, int depth, const float* Xr, const fl
     // dXz / dXh are started (not accumulated) by the first backward depth; so is dXr when that depth has a dS/dG product
     if (depth == 1 && !frozen) (void)hipMemsetAsync(dXr, 0, slot * sizeof(float), s);
 
-    const int tg = pick_tg(E1, Hp / 16);
+    const int tg = plan.tg;
     const double flops1 = 2.0 * (double)(E1 - 1) * H * H;   // algorithmic flops of ONE gate product
-    const bool st16 = bf16 == 1 && !frozen && ggpm_bf16_storage_applies(E1, H);      // (as the forward decided)
+    const bool st16 = ggpm_level_st16(bf16, frozen != nullptr, true, E1, H);      // (as the forward decided)
     // tree-side levels: d(h^t) vanishes below step `lo` (nilpotent Jacobian, common.h); sparse runs go all the way
     int lo = o.lo;
     if (lo < 1 || lo > depth || frozen) lo = 1;

@@ -688,17 +688,50 @@ inline int gate_mode(const ggpm_level_opts& o, int Hp, bool rt2, bool single_gro
     return (lds_tiles(2, Hp) + img <= 160 * 1024 && 3 * img <= 160 * 1024) ? 2 : 0;
 }
 
+// The form of a level call (mpn_gru.hip has the same three for the GRU): what the impl functions, the launchers below and
+// ggpm_level_form_query (include/ggpm_hip.h) all decide through.
+struct LevelPlan { int tg; bool rt2; int gm; };      // tiles per column group, two row tiles per workgroup, gate mode 0 / 1 / 2
+inline LevelPlan level_plan(const ggpm_level_opts& o, int E1, int Hp, bool sparse) {
+    LevelPlan p;
+    p.tg = pick_tg(E1, Hp / 16);
+    p.rt2 = use_rt2(o, Hp, sparse);
+    p.gm = gate_mode(o, Hp, p.rt2, p.tg >= Hp / 16, sparse);
+    return p;
+}
+struct StepLds { int fuse; size_t a, b; };      // b: what the B launch takes when there is one
+// a forward depth step; with_b: the step forms qf' (every step but the level's last)
+inline StepLds fwd_step(int Hp, int tg, bool rt2, int gm, bool with_b) {
+    const int rows = rt2 ? 32 : 16;
+    const bool split = gm == 2;
+    const size_t img_b = ggpm_split_image_bytes(rows, Hp);
+    const size_t l_fused = split ? lds_tiles(1, Hp) + 2 * img_b : lds_tiles(3, Hp);
+    StepLds p;
+    p.fuse = (!rt2 && with_b && ggpm_ceil_div(Hp / 16, tg) == 1 && l_fused <= 160 * 1024 && !env_no_fuse_b()) ? 1 : 0;
+    p.a = p.fuse ? l_fused : split ? lds_tiles(1, Hp) + img_b : lds_tiles(2, Hp, rows);
+    p.b = split ? img_b : lds_tiles(1, Hp, rows);
+    return p;
+}
+// a backward depth step; with_b: the step forms dS for the one below it; final_pass: the sparse backward's t = 0 launch
+inline StepLds bwd_step(int Hp, int tg, bool rt2, int gm, bool with_b, bool final_pass) {
+    const int rows = rt2 ? 32 : 16;
+    const bool split = gm == 2;
+    const size_t img_b = ggpm_split_image_bytes(rows, Hp);
+    const size_t l_fused = split ? lds_tiles(2, Hp) + 4 * img_b : lds_tiles(6, Hp);
+    StepLds p;
+    p.fuse = (!rt2 && with_b && !final_pass && ggpm_ceil_div(Hp / 16, tg) == 1 && l_fused <= 160 * 1024 && !env_no_fuse_b()) ? 1 : 0;
+    p.a = p.fuse ? l_fused : split ? lds_tiles(2, Hp) + img_b : lds_tiles(3, Hp, rows);
+    p.b = split ? 3 * img_b : lds_tiles(3, Hp, rows);                  // kernel B: the three gate-gradient row sets
+    return p;
+}
+
 void launch_fwd(LstmFwdArgs a, bool rt2, bool stash, bool with_b, double flops1, hipStream_t s) {
     const int Hp = a.Hp, NT = Hp / 16;
     const int rows = rt2 ? 32 : 16;
     dim3 grid_a(ggpm_ceil_div(a.E1, rows), ggpm_ceil_div(NT, a.tg));
-    const bool split = a.bf16 == 2;
-    const size_t img_b = ggpm_split_image_bytes(rows, Hp);
-    const size_t l_fused = split ? lds_tiles(1, Hp) + 2 * img_b : lds_tiles(3, Hp);
-    a.fuse_b = (!rt2 && with_b && grid_a.y == 1 && l_fused <= 160 * 1024 && !env_no_fuse_b()) ? 1 : 0;
+    const StepLds step = fwd_step(Hp, a.tg, rt2, a.bf16, with_b);
+    const size_t la = step.a, lb = step.b;
+    a.fuse_b = step.fuse;
     if (a.fuse_b) with_b = false;
-    const size_t la = a.fuse_b ? l_fused : split ? lds_tiles(1, Hp) + img_b : lds_tiles(2, Hp, rows);
-    const size_t lb = split ? img_b : lds_tiles(1, Hp, rows);
     ggpm_timing_begin(2, s, ((a.fuse_b ? 1 : 0) + (a.h0_zero ? 0 : 3)) * flops1);     // the first depth has no gate products
     auto go = [&](auto kernel) {
         set_lds(kernel, la);
@@ -727,13 +760,10 @@ void launch_bwd(LstmBwdArgs a, bool rt2, bool with_b, double flops1, hipStream_t
     const int Hp = a.Hp, NT = Hp / 16;
     const int rows = rt2 ? 32 : 16;
     dim3 grid_a(ggpm_ceil_div(a.E1, rows), ggpm_ceil_div(NT, a.tg));
-    const bool split = a.bf16 == 2;
-    const size_t img_b = ggpm_split_image_bytes(rows, Hp);
-    const size_t l3 = split ? 3 * img_b : lds_tiles(3, Hp, rows);                  // kernel B: the three gate-gradient row sets
-    const size_t l_fused = split ? lds_tiles(2, Hp) + 4 * img_b : lds_tiles(6, Hp);
-    a.fuse_b = (!rt2 && with_b && !a.final_pass && grid_a.y == 1 && l_fused <= 160 * 1024 && !env_no_fuse_b()) ? 1 : 0;
+    const StepLds step = bwd_step(Hp, a.tg, rt2, a.bf16, with_b, a.final_pass != 0);
+    const size_t la = step.a, l3 = step.b;
+    a.fuse_b = step.fuse;
     if (a.fuse_b) with_b = false;
-    const size_t la = a.fuse_b ? l_fused : split ? lds_tiles(2, Hp) + img_b : lds_tiles(3, Hp, rows);
     ggpm_timing_begin(3, s, (a.fuse_b ? 4 : 1) * flops1);
     if (a.st16) { set_lds(lstm_bwd_a<1, 1, true>, la); lstm_bwd_a<1, 1, true><<<grid_a, GGPM_NWA * 64, la, s>>>(a); }
     else if (rt2) { set_lds(lstm_bwd_a<0, 2>, la); lstm_bwd_a<0, 2><<<grid_a, GGPM_NWA * 64, la, s>>>(a); }
@@ -758,7 +788,25 @@ extern "C" size_t ggpm_lstm_pack_floats(int H) {
     return 4 * ggpm_packed_matrix_slot(ggpm_padded_hidden(H));
 }
 
-static int lstm_shape_ok(int Hp) { return lds_tiles(3, Hp) <= 160 * 1024; }
+// three LDS tiles of 16 rows must fit a CU; 32-bit byte offsets inside a slot
+static int lstm_shape_ok(int E1, int Hp) { return lds_tiles(3, Hp) <= 160 * 1024 && (size_t)E1 * Hp < ((size_t)1 << 30); }
+
+// ggpm_level_form_query (capi.hip) for an LSTM level: the decisions above, nothing launched
+int ggpm_lstm_level_form(int E1, int H, int sparse, int training, const ggpm_level_opts& o, ggpm_level_form* out) {
+    const int Hp = ggpm_padded_hidden(H);
+    if (!lstm_shape_ok(E1, Hp)) return GGPM_ERR_UNSUPPORTED;
+    const LevelPlan plan = level_plan(o, E1, Hp, sparse != 0);
+    const StepLds f = fwd_step(Hp, plan.tg, plan.rt2, plan.gm, true);
+    const StepLds b = bwd_step(Hp, plan.tg, plan.rt2, plan.gm, true, false);
+    *out = ggpm_level_form{};
+    out->Hp = Hp; out->tiles = Hp / 16; out->tg = plan.tg; out->groups = ggpm_ceil_div(Hp / 16, plan.tg);
+    out->rt2 = plan.rt2 ? 1 : 0; out->gate_mode = plan.gm;
+    out->st16 = ggpm_level_st16(plan.gm, sparse != 0, training || o.h_out, E1, H) ? 1 : 0;
+    out->fuse_fwd = f.fuse;
+    out->lds_fwd_a = f.a; out->lds_fwd_b = (f.fuse && !sparse) ? 0 : f.b;      // (a sparse forward forms qf^0 by a B launch)
+    if (training) { out->fuse_bwd = b.fuse; out->lds_bwd_a = b.a; out->lds_bwd_b = b.fuse ? 0 : b.b; }
+    return GGPM_OK;
+}
 
 namespace {
 __global__ void lstm_sparse_init_state(const float* __restrict__ h_in, const float* __restrict__ c_in,
@@ -786,11 +834,12 @@ static int lstm_forward_impl(int E1, int H, int depth, const float* Xi, const fl
         return GGPM_ERR_ARG;
     if (save_for_backward && (!Ss || !Is || !Os || !Us || !Fs)) return GGPM_ERR_ARG;
     const int Hp = ggpm_padded_hidden(H);
-    if (!lstm_shape_ok(Hp) || (size_t)E1 * Hp >= ((size_t)1 << 30)) return GGPM_ERR_UNSUPPORTED;      // (32-bit byte offsets inside a slot)
+    if (!lstm_shape_ok(E1, Hp)) return GGPM_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     const size_t HH = (size_t)Hp * Hp, slot = (size_t)E1 * Hp;
-    const bool rt2 = use_rt2(o, Hp, frozen != nullptr);
-    const int bf16 = gate_mode(o, Hp, rt2, pick_tg(E1, Hp / 16) >= Hp / 16, frozen != nullptr);      // gate mode 0 / 1 / 2
+    const LevelPlan plan = level_plan(o, E1, Hp, frozen != nullptr);
+    const bool rt2 = plan.rt2;
+    const int bf16 = plan.gm;      // gate mode 0 / 1 / 2
     const size_t mstep = ggpm_packed_matrix_floats(Hp, bf16);
     float* pWi = wpack; float* pWo = wpack + mstep; float* pWu = wpack + 2 * mstep; float* pWf = wpack + 3 * mstep;
     {
@@ -800,7 +849,7 @@ static int lstm_forward_impl(int E1, int H, int depth, const float* Xi, const fl
         pk.H = H; pk.Hp = Hp; pk.transpose = 0; pk.dst = wpack; pk.bias = nullptr; pk.bias_out = nullptr; pk.bf16 = bf16;
         if (!o.weights_packed) ggpm_launch_pack(pk, 4, s);
     }
-    const int tg = pick_tg(E1, Hp / 16);
+    const int tg = plan.tg;
     const bool gathered = o.gather_h && o.gather_idx && frozen && o.gather_c;
     if (frozen) {      // sparse_forward: start from the caller's (h, c); qf^0 = Wf_h h^0 by one B launch
         dim3 ig(ggpm_ceil_div(Hp, 256), E1);
@@ -810,7 +859,7 @@ static int lstm_forward_impl(int E1, int H, int depth, const float* Xi, const fl
         LstmFwdArgs a0 = {};
         a0.E1 = E1; a0.Hp = Hp; a0.tg = tg; a0.Hnew = Hs; a0.Qnew = Qs; a0.Wf = pWf; a0.bf16 = bf16;
         if (gathered) { a0.src_h = o.gather_h; a0.src_c = o.gather_c; a0.src_idx = o.gather_idx; a0.Cnew = Cs; }
-        const size_t lb = bf16 == 2 ? ggpm_split_image_bytes(ROWS, Hp) : lds_tiles(1, Hp);
+        const size_t lb = fwd_step(Hp, tg, false, bf16, true).b;
         dim3 grid_a(ggpm_ceil_div(E1, ROWS), ggpm_ceil_div(Hp / 16, tg));
         if (bf16 == 2) { set_lds(lstm_fwd_b<2, 1>, lb); lstm_fwd_b<2, 1><<<grid_a, GGPM_NWA * 64, lb, s>>>(a0); }
         else if (bf16 == 1) { set_lds(lstm_fwd_b<1, 1>, lb); lstm_fwd_b<1, 1><<<grid_a, GGPM_NWA * 64, lb, s>>>(a0); }
@@ -827,7 +876,7 @@ static int lstm_forward_impl(int E1, int H, int depth, const float* Xi, const fl
     int run_depth = o.run_depth;
     if (run_depth <= 0 || run_depth > depth || frozen || !(save_for_backward || infer)) run_depth = depth;
     // bf16 storage (tile_mma.h): bf16 gate products, dense, training, every stash contraction on the bf16 tall kernel
-    const bool st16 = bf16 == 1 && !frozen && (save_for_backward || infer) && ggpm_bf16_storage_applies(E1, H);
+    const bool st16 = ggpm_level_st16(bf16, frozen != nullptr, save_for_backward || infer, E1, H);
     // fixed-point level (ggpm_level_opts.fixed_slot): only the last step's stash slot is ever read
     const int fs = (o.fixed_slot > 0 && save_for_backward && !frozen && !st16) ? o.fixed_slot : 0;
     if (fs && fs != run_depth) return GGPM_ERR_ARG;
@@ -935,15 +984,16 @@ static int lstm_backward_impl(int E1, int H, int depth, const float* Xf, const f
         return GGPM_ERR_ARG;
     if (work_bytes < ggpm_lstm_backward_workspace_bytes(E1, H, depth)) return GGPM_ERR_WORKSPACE;
     const int Hp = ggpm_padded_hidden(H);
-    if (!lstm_shape_ok(Hp) || (size_t)E1 * Hp >= ((size_t)1 << 30)) return GGPM_ERR_UNSUPPORTED;      // (32-bit byte offsets inside a slot)
+    if (!lstm_shape_ok(E1, Hp)) return GGPM_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     const size_t HH = (size_t)Hp * Hp, slot = (size_t)E1 * Hp;
 
     const bool skip_xsum = o.skip_x_sums && !frozen;
     // (the packed transposes come first: their place does not depend on E1 -- ggpm_level_opts.weights_packed)
     float* w = work;
-    const bool rt2 = use_rt2(o, Hp, frozen != nullptr);
-    const int bf16 = gate_mode(o, Hp, rt2, pick_tg(E1, Hp / 16) >= Hp / 16, frozen != nullptr);      // gate mode 0 / 1 / 2
+    const LevelPlan plan = level_plan(o, E1, Hp, frozen != nullptr);
+    const bool rt2 = plan.rt2;
+    const int bf16 = plan.gm;      // gate mode 0 / 1 / 2
     const size_t mstep = ggpm_packed_matrix_floats(Hp, bf16);
     float* pWiT = w; float* pWoT = w + mstep; float* pWuT = w + 2 * mstep; float* pWfT = w + 3 * mstep;
     w += 4 * ggpm_packed_matrix_slot(Hp);
@@ -972,12 +1022,12 @@ static int lstm_backward_impl(int E1, int H, int depth, const float* Xf, const f
     }
     // dXi / dXo / dXu / dXf are started (not accumulated) by the first backward depth
 
-    const int tg = pick_tg(E1, Hp / 16);
+    const int tg = plan.tg;
     const double flops1 = 2.0 * (double)(E1 - 1) * H * H;   // algorithmic flops of ONE gate product
     // tree-side levels: d(h^t), d(c^t) vanish below step `lo` (nilpotent Jacobian, common.h)
     int lo = o.lo;
     if (lo < 1 || lo > depth || frozen) lo = 1;
-    const bool st16 = bf16 == 1 && !frozen && ggpm_bf16_storage_applies(E1, H);      // (as the forward decided)
+    const bool st16 = ggpm_level_st16(bf16, frozen != nullptr, true, E1, H);      // (as the forward decided)
     // fixed-point level (ggpm_level_opts.fixed_slot): state slots above fs and stash slots above fs - 1 alias those
     const int fs = (o.fixed_slot > 0 && !frozen && !st16) ? o.fixed_slot : 0;
     if (fs && (fs >= depth || lo < fs)) return GGPM_ERR_ARG;      // (every slot a step >= lo reads must be the settled one)

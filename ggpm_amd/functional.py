@@ -422,6 +422,26 @@ class LevelOpts(ctypes.Structure):
                 ("h_out", ctypes.c_void_p), ("c_out", ctypes.c_void_p), ("fixed_slot", ctypes.c_int)]
 
 
+class LevelForm(ctypes.Structure):
+    """include/ggpm_hip.h: ggpm_level_form -- the launch geometry, gate mode and LDS sizes a level call takes"""
+    _fields_ = [("Hp", ctypes.c_int), ("tiles", ctypes.c_int), ("tg", ctypes.c_int), ("groups", ctypes.c_int),
+                ("rt2", ctypes.c_int), ("gate_mode", ctypes.c_int), ("st16", ctypes.c_int), ("fuse_fwd", ctypes.c_int),
+                ("fuse_bwd", ctypes.c_int), ("lds_fwd_a", ctypes.c_size_t), ("lds_fwd_b", ctypes.c_size_t),
+                ("lds_bwd_a", ctypes.c_size_t), ("lds_bwd_b", ctypes.c_size_t)]
+
+
+def level_form(lstm: bool, E1: int, H: int, sparse: bool = False, training: bool = True, opts: Optional[LevelOpts] = None):
+    """ggpm_level_form_query: the form a GRU / LSTM level call of ``E1`` rows and hidden size ``H`` takes -> LevelForm, or
+    None for a shape the level entry points refuse (GGPM_ERR_UNSUPPORTED).  Host only: needs no GPU."""
+    out = LevelForm()
+    rc = _lib.load().ggpm_level_form_query(int(lstm), E1, H, int(sparse), int(training),
+                                           None if opts is None else ctypes.byref(opts), ctypes.byref(out))
+    if rc == _lib.GGPM_ERR_UNSUPPORTED:
+        return None
+    _lib.check(rc, "level_form_query")
+    return out
+
+
 _GATE_OPTS = {dt: LevelOpts(gate_dtype=dt) for dt in (1, 2, 3)}
 
 

@@ -397,6 +397,33 @@ typedef struct ggpm_level_opts {
     int fixed_slot;
 } ggpm_level_opts;
 
+/* The form a level call takes: which of the depth kernels' launch geometries, gate modes and LDS layouts a GRU (lstm = 0) or
+ * LSTM level of E1 message rows (pad row included) and hidden size H runs on -- dense (sparse = 0: ggpm_*_forward / _backward)
+ * or sparse (ggpm_*_sparse_forward / _sparse_backward), with stashes (training != 0: save_for_backward, and the backward) or
+ * without, under `opts` (NULL: defaults; gate_dtype, prefer_narrow and h_out are read).  Host only: no HIP call, nothing
+ * launched.  The level entry points and this query decide through the same functions (csrc/mpn_gru.hip, csrc/mpn_lstm.hip:
+ * level_plan, fwd_step, bwd_step), so what it reports is what a call does; DESIGN.md ("The lattice of level forms") lists
+ * the forms the configured hidden sizes reach.
+ *   tiles = Hp / 16 output tiles are cut into `groups` = ceil(tiles / tg) column groups (grid.y) of tg tiles, the last one
+ *   ragged when tg does not divide tiles; each of the 16 waves of a workgroup owns ceil(tg / 16) tiles of its group at most.
+ *   rt2: two row tiles (32 message rows) per workgroup.  gate_mode: 0 fp32 MFMA, 1 bf16 operands, 2 fp32 on split operands.
+ *   st16: bf16 storage (ggpm_level_bf16_storage).  fuse_fwd / fuse_bwd: a depth step that needs q' (LSTM: qf') resp.
+ *   dS, dG (dS) forms it inside kernel A instead of by a B launch.  lds_*: dynamic LDS bytes of such a step's A and B
+ *   launches, 0 = not launched (a sparse forward always has its q^0 B launch; the level's last forward step and the first
+ *   backward step of a dense level need no B product and take the unfused A size, which is never the larger one;
+ *   training = 0 leaves the backward fields 0).
+ * Returns GGPM_OK, GGPM_ERR_UNSUPPORTED for a shape the level entry points refuse (see the accepted hidden sizes below), or
+ * GGPM_ERR_ARG (E1 <= 0, H <= 0, out == NULL). */
+typedef struct ggpm_level_form {
+    int Hp, tiles;            /* padded hidden size, NT = Hp / 16 */
+    int tg, groups;           /* tiles per column group, grid.y */
+    int rt2, gate_mode, st16; /* as the launchers decide them */
+    int fuse_fwd, fuse_bwd;   /* q' resp. dS/dG inside kernel A */
+    size_t lds_fwd_a, lds_fwd_b, lds_bwd_a, lds_bwd_b;   /* dynamic LDS bytes per launch, 0 = not launched */
+} ggpm_level_form;
+int ggpm_level_form_query(int lstm, int E1, int H, int sparse, int training, const ggpm_level_opts* opts,
+                          ggpm_level_form* out);
+
 /* ------------------------------------------------------------------ GRU message function
  * GRU.forward (ggpm/rnn.py:41-50) with GRU.GRU (ggpm/rnn.py:25-39) restated over CSR predecessors with
  * the depth-invariant input halves hoisted:  Xz = x W_z[:, :I]^T + b_z, Xr = x W_r^T, Xh = x W_h[:, :I]^T + b_h
@@ -409,6 +436,12 @@ typedef struct ggpm_level_opts {
  * [depth][E1][Hp] (Rs = sum_p h_p r(1-r), which lets the backward form dXr without a gather).  With
  * save_for_backward = 0 only Hs[2][E1][Hp] and Qs[2][E1][Hp] are needed and the result is Hs[depth & 1].
  * wpack: ggpm_gru_pack_floats(H) floats of scratch.
+ * Accepted hidden sizes: Hp = ggpm_padded_hidden(H) <= 1264, i.e. H <= 1264 (two fp32 LDS tiles of 16 rows x (Hp + 4) columns
+ * must fit the 160 KiB of a workgroup); every GRU level entry point (forward, backward, sparse_*) returns
+ * GGPM_ERR_UNSUPPORTED beyond that and launches nothing.  Inside the range the form changes with H (ggpm_level_form_query); a
+ * dense fp32 level of one column group runs on split gate operands with q' and dS / dG fused up to Hp = 448, on split
+ * operands with B launches up to Hp = 624 (also the last size with two row tiles per workgroup), on fp32 MFMA with q'
+ * fused up to Hp = 848, and on fp32 MFMA with B launches in both directions above that, a wave owning up to five tiles.
  */
 size_t ggpm_gru_pack_floats(int H);
 int ggpm_gru_forward(int E1, int H, int depth, const float* Xz, const float* Xr, const float* Xh,
@@ -461,6 +494,10 @@ int ggpm_gru_sparse_backward(int E1, int H, int depth, const unsigned char* froz
  *     i = sigmoid(Xi + Wi_h s), o = sigmoid(Xo + Wo_h s), u = tanh(Xu + Wu_h s),
  *     c' = i u + fc,  h' = o tanh(c'),  rows 0 := 0.
  * Stash: Hs, Cs [depth+1][E1][Hp]; Qs (qf), Ss, Is, Os, Us, Fs [depth][E1][Hp] (Fs = sum_p c_p f(1-f)).
+ * Accepted hidden sizes: Hp = ggpm_padded_hidden(H) <= 848, i.e. H <= 848 (three fp32 LDS tiles of 16 rows x (Hp + 4) columns
+ * must fit the 160 KiB of a workgroup), and E1 * Hp < 2^30 (32-bit byte offsets inside a slot); every LSTM level entry point
+ * returns GGPM_ERR_UNSUPPORTED beyond either and launches nothing.  ggpm_level_form_query reports the form inside the range
+ * (a dense fp32 level of one column group: split operands up to Hp = 560, dS fused up to Hp = 304, qf' fused throughout).
  */
 size_t ggpm_lstm_pack_floats(int H);
 int ggpm_lstm_forward(int E1, int H, int depth, const float* Xi, const float* Xo, const float* Xu,

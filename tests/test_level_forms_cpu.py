@@ -1,0 +1,118 @@
+"""CPU: ggpm_level_form_query (host only) against the case table of tests/level_form_cases.py -- every form a level call
+can take at the configured hidden sizes has a case that tests/test_gpu_level_forms.py runs against fp64, no form asks for
+more LDS than a workgroup has, and the accepted hidden sizes are the documented ones."""
+import itertools
+
+import pytest
+
+import level_form_cases as C
+from ggpm_amd import functional as F_
+
+LDS_BYTES = 160 * 1024          # MI355X LDS per workgroup: what the dispatch budgets against
+
+
+def _table(cases):
+    forms = {}
+    for c in cases:
+        forms.setdefault((c.cell, c.H), set()).add(c.form)
+    return forms
+
+
+def test_every_case_takes_the_form_the_table_states():
+    for c in C.DENSE + C.SPARSE + C.LIMIT_DENSE + C.LIMIT_SPARSE:
+        f = C.query(c)
+        assert f is not None and C.reduced(f) == c.form, (C.case_id(c), f and C.reduced(f), c.form)
+
+
+def test_the_table_keeps_the_cases_the_lattice_alone_does_not_ask_for():
+    """The coverage tests hold every form to SOME case; these are named on top of that: the upper end (last row tile full)
+    of the two-group classes, depth 3 on the H = 600 two-group class (two full gate-product steps with two tiles per
+    wave), the natural two-row-tile GRU level, the three sparse classes, and the cases at the accepted limits."""
+    dense = {(c.cell, c.H, c.E1): c for c in C.DENSE}
+    assert len(dense) == len(C.DENSE)
+    for cell in ("GRU", "LSTM"):
+        for H, cls in ((250, (8, 2)), (300, (10, 2)), (600, (19, 2))):
+            lo, hi = dense[cell, H, 1361], dense[cell, H, 2048]
+            assert lo.form[:2] == hi.form[:2] == cls and hi.E1 % 16 == 0
+            assert C.reduced(C.query(hi._replace(E1=hi.E1 + 1)))[:2] != cls        # 2048 is the class's last E1
+            assert lo.depth == hi.depth == (3 if H == 600 else 2), (cell, H, lo.depth, hi.depth)
+        for H in C.HIDDEN:
+            assert dense[cell, H, 40].depth >= 2 and dense[cell, H, 2049].form[1] == 1
+    assert dense["GRU", 300, 8177].form == (19, 1, 0, 1, 0, 0)
+    assert all(c.depth >= 2 and not c.sparse for c in C.DENSE + C.LIMIT_DENSE)
+    sparse = {(c.cell, c.H, c.E1): c for c in C.SPARSE}
+    assert sorted(sparse) == sorted((cell, H, E1) for cell in ("GRU", "LSTM") for H in C.HIDDEN for E1 in C.SPARSE_E1)
+    assert all(c.sparse and c.depth >= 2 and abs(4 * c.ms - c.E1) < 4 for c in C.SPARSE + C.LIMIT_SPARSE)
+    assert sorted((c.cell, c.H, c.E1) for c in C.LIMIT_DENSE) == sorted(
+        [("GRU", 1264, E1) for E1 in (40, 673, 1361, 2049)] + [("GRU", 840, 2049), ("GRU", 850, 2049)]
+        + [("LSTM", 848, E1) for E1 in (40, 1025, 2049)])
+    assert [(c.cell, c.H, c.E1) for c in C.LIMIT_SPARSE] == [("LSTM", 848, 450)]
+
+
+def test_every_reachable_dense_form_has_a_case():
+    """cell x H in {250, 300, 600} x E1 = 2 .. 4096, dense training call, default options"""
+    table = _table(C.DENSE)
+    for cell, H in itertools.product(("GRU", "LSTM"), C.HIDDEN):
+        for E1 in range(2, 4097):
+            form = C.reduced(F_.level_form(cell == "LSTM", E1, H))
+            assert form in table[cell, H], "no dense case covers (cell, H, E1, form) = %r" % ((cell, H, E1, form),)
+
+
+def test_every_sparse_form_of_the_tested_classes_has_a_case():
+    """... and sparse calls, over the E1 of the three (tg, groups) classes the sparse cases stand in"""
+    table = _table(C.SPARSE)
+    for cell, H in itertools.product(("GRU", "LSTM"), C.HIDDEN):
+        classes = {C.reduced(F_.level_form(cell == "LSTM", E1, H, sparse=True))[:2] for E1 in C.SPARSE_E1}
+        assert len(classes) == 3, (cell, H, classes)
+        for E1 in range(2, 4097):
+            form = C.reduced(F_.level_form(cell == "LSTM", E1, H, sparse=True))
+            if form[:2] in classes:
+                assert form in table[cell, H], "no sparse case covers (cell, H, E1, form) = %r" % ((cell, H, E1, form),)
+
+
+def _accepted_hp(lstm):
+    return [hp for hp in range(16, 2049, 16) if F_.level_form(lstm, 40, hp) is not None]
+
+
+@pytest.mark.parametrize("cell", ["GRU", "LSTM"])
+def test_no_form_exceeds_the_lds_of_a_workgroup(cell):
+    """Every accepted Hp x the lower end of every group count x sparse x training x gate dtype x prefer_narrow: each
+    launch's dynamic LDS fits, and the geometry is consistent (groups = ceil(tiles / tg), a non-empty last group)."""
+    lstm = cell == "LSTM"
+    hps = _accepted_hp(lstm)
+    assert hps == list(range(16, (C.LSTM_MAX_H if lstm else C.GRU_MAX_H) + 1, 16))
+    rows = sorted({2} | {16 * (256 // g) + 1 for g in range(1, 65)})
+    opts = [F_.LevelOpts(gate_dtype=dt, prefer_narrow=pn) for dt in range(4) for pn in (0, 1)]
+    for hp, E1, o, sparse, training in itertools.product(hps, rows, opts, (False, True), (False, True)):
+        f = F_.level_form(lstm, E1, hp, sparse=sparse, training=training, opts=o)
+        what = (cell, hp, E1, o.gate_dtype, o.prefer_narrow, sparse, training)
+        assert f is not None, what
+        assert max(f.lds_fwd_a, f.lds_fwd_b, f.lds_bwd_a, f.lds_bwd_b) <= LDS_BYTES, \
+            (what, f.lds_fwd_a, f.lds_fwd_b, f.lds_bwd_a, f.lds_bwd_b)
+        assert f.Hp == hp and f.tiles * 16 == hp and 1 <= f.tg <= f.tiles, (what, f.tiles, f.tg)
+        assert f.groups == -(-f.tiles // f.tg) and 0 < f.tiles - (f.groups - 1) * f.tg <= f.tg, (what, f.tiles, f.tg, f.groups)
+        assert f.lds_fwd_a > 0 and (f.lds_fwd_b > 0) == (sparse or not f.fuse_fwd), what
+        if training:
+            assert f.lds_bwd_a > 0 and (f.lds_bwd_b > 0) == (not f.fuse_bwd), what
+        else:
+            assert (f.fuse_bwd, f.lds_bwd_a, f.lds_bwd_b) == (0, 0, 0), what
+
+
+def test_accepted_hidden_sizes_are_the_documented_ones():
+    """include/ggpm_hip.h, "Accepted hidden sizes": GRU H <= 1264, LSTM H <= 848; beyond: GGPM_ERR_UNSUPPORTED"""
+    import ctypes
+    from ggpm_amd import _lib
+    lib, out = _lib.load(), F_.LevelForm()
+    ok, bad_arg, refused = _lib.GGPM_OK, _lib.GGPM_ERR_ARG, _lib.GGPM_ERR_UNSUPPORTED
+    for lstm, H, want in ((0, C.GRU_MAX_H, ok), (0, C.GRU_MAX_H + 1, refused), (1, C.LSTM_MAX_H, ok),
+                          (1, C.LSTM_MAX_H + 1, refused)):
+        for sparse, training, E1 in itertools.product((0, 1), (0, 1), (2, 40, 2049)):
+            assert lib.ggpm_level_form_query(lstm, E1, H, sparse, training, None, ctypes.byref(out)) == want, (lstm, H, E1)
+    assert lib.ggpm_level_form_query(0, 0, 300, 0, 1, None, ctypes.byref(out)) == bad_arg
+    assert lib.ggpm_level_form_query(0, 40, 0, 0, 1, None, ctypes.byref(out)) == bad_arg
+    assert lib.ggpm_level_form_query(1, 40, 300, 0, 1, None, None) == bad_arg
+    # the LSTM's second limit: 32-bit byte offsets inside a slot
+    edge = -(-(1 << 30) // 304)          # the first E1 with E1 * Hp >= 2^30 at H = 300
+    assert F_.level_form(True, edge, 300) is None and F_.level_form(True, edge - 1, 300) is not None
+    # the fused single-group GRU forward ends between Hp = 848 and Hp = 864
+    assert F_.level_form(False, 2049, 840).fuse_fwd == 1 and F_.level_form(False, 2049, 850).fuse_fwd == 0
