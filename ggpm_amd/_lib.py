@@ -38,6 +38,11 @@ SIGNATURES = {
     "ggpm_gemm_tn_bf16": (I, [I, I, I, P, I, P, I, P, I, P, c_size_t, P]),
     "ggpm_gemm_tn_bf16_applies": (I, [I, I, I]),
     "ggpm_colsum": (I, [P, I, I, I, P, P, P]),
+    # the level weight gradients' products by themselves, and the host-only form query (call: ggpm_gemm_call*, out: ggpm_gemm_form*)
+    "ggpm_gemm_tn_tall_grouped": (I, [I, I, I, P, P, P, c_size_t, I, P]),  # problems: ggpm_gemm_problem[count], K: int[count]
+    "ggpm_gemm_tn_pair_grouped_c": (I, [I, I, I, I, I, P, P]),            # problems: ggpm_pair_problem[count]
+    "ggpm_colsum_dtype": (I, [P, I, I, I, P, P, I, P]),
+    "ggpm_gemm_form_query": (I, [P, P]),
     "ggpm_act_backward": (I, [P, P, I, I, I, I, I, P, P]),
     "ggpm_segment_sum": (I, [P, I, P, P, I, I, P, I, I, I, P]),
     "ggpm_segment_sum_masked": (I, [I, P, I, P, P, I, I, P, I, P, I, I, P, P, I, I, I, P]),

@@ -209,7 +209,6 @@ int ggpm_sum_slots_any(const float* src, int slots, size_t slot_floats, float* o
 // C_i [M, ldc] overwritten) in one launch.
 int ggpm_sum_slots_pair_grouped(int count, const float* const* src, const int* slots, size_t slot_floats, float* const* hi,
                                 float* const* lo, ggpm_stream_t stream);
-struct ggpm_pair_problem { const float *hi, *lo, *B; float* C; int ldc; };
 int ggpm_gemm_tn_pair_grouped(int M, int N, int rows, int ld, int count, const ggpm_pair_problem* p, ggpm_stream_t stream);
 // column sums of a [rows, ld] fp32 or bf16 matrix (losses.hip / gemm.hip: ggpm_colsum is the fp32 entry point)
 int ggpm_colsum_any(const float* A, int lda, int rows, int cols, float* out, float* scratch, bool a_bf16, ggpm_stream_t stream);

@@ -839,8 +839,12 @@ __global__ void __launch_bounds__(256, 2) gemm_tn_tall_bf16(GemmGroupArgs gg, in
     const float* P = isb ? g.B : g.A;
     const int ld = isb ? g.ldb : g.lda, c0 = isb ? n0 : m0, climit = isb ? g.N : g.M;
     constexpr unsigned ES = IN16 ? 2 : 4;       // bytes per operand element in memory
+    // the range check works on whole dwords: with bf16 in memory and an odd column count the record must end after the pad
+    // element that shares a dword with column climit - 1 (inside the row: ld >= round_up(climit, 4)), or the chunk's last
+    // row would lose that column
+    const int cend = IN16 ? (climit + 1) & ~1 : climit;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(P), 0, kend > kbeg ? (unsigned)(((size_t)(kend - 1) * ld + climit) * ES) : 0u, 0x00020000);
+        const_cast<float*>(P), 0, kend > kbeg ? (unsigned)(((size_t)(kend - 1) * ld + cend) * ES) : 0u, 0x00020000);
     unsigned voff[10];
     int loff[10];
 #pragma unroll
@@ -1251,9 +1255,7 @@ inline bool small_launch(int M, int N, int count) {
     static const int max_tiles = [] { const char* e = ggpm_dev_env("GGPM_GEMM_V3_TILES"); return e ? atoi(e) : 300; }();
     return use_v3 && (size_t)ggpm_ceil_div(M, BM) * ggpm_ceil_div(N, BN) * count <= (size_t)max_tiles;
 }
-inline void launch_small(int trans_a, int trans_b, const GemmGroupArgs& gg, int count, int M, int n_pad_max, hipStream_t s,
-                         int splits = 1) {
-    dim3 grid(ggpm_ceil_div(n_pad_max, SN), ggpm_ceil_div(M, SM), count * splits);
+inline void launch_small(int trans_a, int trans_b, const GemmGroupArgs& gg, dim3 grid, int splits, hipStream_t s) {
     if (!trans_a && !trans_b) gemm_small_v3<false, false><<<grid, 256, 0, s>>>(gg, splits);
     else if (!trans_a && trans_b) gemm_small_v3<false, true><<<grid, 256, 0, s>>>(gg, splits);
     else if (trans_a && !trans_b) gemm_small_v3<true, false><<<grid, 256, 0, s>>>(gg, splits);
@@ -1272,6 +1274,324 @@ inline int small_splits(int M, int N, int K, int count, int* k_chunk) {
 }
 }  // namespace
 
+// ---- which kernel a call runs on --------------------------------------------------------------------------------------
+// Every dispatch decision of this file as a function of what ggpm_gemm_call (include/ggpm_hip.h) describes: shapes, leading
+// dimensions, the low four bits of each operand's address, the workspace passed.  The entry points below build such a
+// description from their arguments, call the plan_* function and launch what it says; ggpm_gemm_form_query calls the same
+// functions and launches nothing.
+namespace {
+inline int gemm_use_tall() { static const int v = [] { const char* e = ggpm_dev_env("GGPM_GEMM_TALL"); return e ? atoi(e) : 1; }(); return v; }
+inline int gemm_use_v2() { static const int v = [] { const char* e = ggpm_dev_env("GGPM_GEMM_V2"); return e ? atoi(e) : 1; }(); return v; }
+inline int low4(const void* p) { return (int)((uintptr_t)p & 15); }
+inline bool vec_legal(int ld, int base) { return (ld & 3) == 0 && (base & 15) == 0; }      // 16-byte loads of every row
+inline bool fits_buffer(size_t rows, int ld, size_t es = 4) { return rows * ld * es < 0xffffff00ull; }   // 32-bit buffer offsets
+// The tall kernels step their 32-bit buffer offsets whole k-steps at a time and prefetch two steps ahead: past the last chunk's
+// end they reach row K + 3 * BTK - 1 at most.  Those rows must stay beyond the record (they read zeros); an offset that
+// wrapped past 2^32 would land inside it again and read rows from the operand's start into the K tail.
+constexpr int TALL_K_OVERSHOOT = 3 * BTK;
+inline bool v2_operands_ok(int lda, int base_a, size_t rows_a, int ldb, int base_b, size_t rows_b) {
+    return gemm_use_v2() && vec_legal(lda, base_a) && vec_legal(ldb, base_b) && fits_buffer(rows_a, lda) && fits_buffer(rows_b, ldb);
+}
+inline void small_grid(int n_pad_max, int M, int count, int splits, int* grid) {
+    grid[0] = ggpm_ceil_div(n_pad_max, SN); grid[1] = ggpm_ceil_div(M, SM); grid[2] = count * splits;
+}
+constexpr size_t LDS_SCALAR = 2 * BK * LDT * sizeof(float), LDS_V2 = 4 * BK2 * LDT * sizeof(float),
+                 LDS_SMALL = 4 * SK * SLD * sizeof(float), LDS_TALL = 4 * TK * TLD * sizeof(float),
+                 LDS_TALL_BF16 = 2 * BTK * BLD * sizeof(__bf16);
+
+struct GemmPlan {
+    int rc = GGPM_OK, kernel = GGPM_GEMM_KERNEL_NONE, vec_a = 0, vec_b = 0, reduce = GGPM_GEMM_REDUCE_NONE, splits = 1;
+    int k_chunk[GGPM_GEMM_MAX_GROUP] = {0, 0, 0, 0};
+    int grid[3] = {0, 0, 0};
+    size_t lds = 0, ws_used = 0;
+};
+inline GemmPlan plan_refuse(int rc) { GemmPlan pl; pl.rc = rc; return pl; }
+inline void plan_small(GemmPlan& pl, int n_pad_max, int M, int count, int splits) {
+    pl.kernel = GGPM_GEMM_KERNEL_SMALL_V3; pl.lds = LDS_SMALL; pl.splits = splits;
+    small_grid(n_pad_max, M, count, splits, pl.grid);
+}
+
+// ggpm_gemm
+inline GemmPlan plan_gemm(int trans_a, int trans_b, int M, int N, int K, int lda, int base_a, int ldb, int base_b, int ldc,
+                          int n_pad, bool has_ws, size_t ws_bytes) {
+    if (M <= 0 || N <= 0 || K <= 0 || n_pad < N || n_pad > ldc) return plan_refuse(GGPM_ERR_ARG);
+    GemmPlan pl;
+    const bool vecA = vec_legal(lda, base_a), vecB = vec_legal(ldb, base_b);
+    pl.vec_a = vecA; pl.vec_b = vecB;
+    if (gemm_use_tall() && trans_a && !trans_b && vecA && vecB && lda >= ggpm_round_up(M, 4) && ldb >= ggpm_round_up(N, 4) &&
+        tall_shape(M, N, K) && n_pad <= ggpm_round_up(N, TN) && fits_buffer(K + TALL_K_OVERSHOOT, lda) && fits_buffer(K + TALL_K_OVERSHOOT, ldb)) {
+        const size_t slab = tall_slab_bytes(M, N);
+        pl.grid[0] = ggpm_ceil_div(N, TN); pl.grid[1] = ggpm_ceil_div(M, TM);
+        if (tall_split_mode() && has_ws && ws_bytes >= slab) {
+            // split operands on the bf16 pipe (fp32 accuracy, operand-stream bound): always through slabs + tall_reduce
+            // (which applies bias / accumulate / activation)
+            int sp = tall_splits(M, N, K, tall_split_wgs());
+            if ((size_t)sp * slab > ws_bytes) sp = (int)(ws_bytes / slab);
+            if (sp < 1) sp = 1;
+            pl.k_chunk[0] = ggpm_round_up(ggpm_ceil_div(K, sp), BTK);
+            pl.splits = ggpm_ceil_div(K, pl.k_chunk[0]);
+            pl.kernel = GGPM_GEMM_KERNEL_TALL_SPLIT; pl.lds = GGPM_TALL_SPLIT_LDS;
+            pl.reduce = GGPM_GEMM_REDUCE_TALL; pl.ws_used = pl.splits * slab;
+            pl.grid[2] = pl.splits;
+            return pl;
+        }
+        int splits = has_ws ? tall_splits(M, N, K) : 1;
+        if (splits > 1 && (size_t)splits * slab > ws_bytes) splits = (int)(ws_bytes / slab);
+        if (splits < 1) splits = 1;
+        pl.k_chunk[0] = ggpm_round_up(ggpm_ceil_div(K, splits), TK);
+        pl.splits = ggpm_ceil_div(K, pl.k_chunk[0]);
+        pl.kernel = GGPM_GEMM_KERNEL_TALL; pl.lds = LDS_TALL;
+        if (pl.splits > 1) { pl.reduce = GGPM_GEMM_REDUCE_TALL; pl.ws_used = pl.splits * slab; }
+        pl.grid[2] = pl.splits;
+        return pl;
+    }
+    int splits = 1;
+    if (has_ws) {
+        splits = choose_splits(M, N, K);
+        if (splits > 1 && (size_t)splits * M * N * sizeof(float) > ws_bytes) splits = 1;
+    }
+    if (splits > 1) {
+        pl.k_chunk[0] = ggpm_round_up(ggpm_ceil_div(K, splits), BK);
+        splits = ggpm_ceil_div(K, pl.k_chunk[0]);
+    }
+    if (splits <= 1) { splits = 1; pl.k_chunk[0] = ggpm_round_up(K, BK); }
+    pl.splits = splits;
+    const size_t rows_a = trans_a ? K : M, rows_b = trans_b ? N : K;
+    const bool v2ok = v2_operands_ok(lda, base_a, rows_a, ldb, base_b, rows_b);
+    if (splits == 1 && small_launch(M, N, 1) && v2ok) {
+        plan_small(pl, n_pad, M, 1, 1);
+        return pl;
+    }
+    pl.grid[0] = ggpm_ceil_div(splits > 1 ? N : n_pad, BN); pl.grid[1] = ggpm_ceil_div(M, BM); pl.grid[2] = splits;
+    // v2 keeps 70 KB of LDS per workgroup (two resident per CU): it wins while the whole grid is resident at once
+    // (latency-bound launches: 573 x 600 x 912 35 -> 25 us) and loses beyond (2843 x 912 x 340: 33 -> 37 us)
+    const bool resident = (size_t)pl.grid[0] * pl.grid[1] * pl.grid[2] <= 512 || gemm_use_v2() == 2;
+    if (resident && v2ok) { pl.kernel = GGPM_GEMM_KERNEL_V2; pl.lds = LDS_V2; }
+    else { pl.kernel = GGPM_GEMM_KERNEL_SCALAR; pl.lds = LDS_SCALAR; }
+    if (splits > 1) { pl.reduce = GGPM_GEMM_REDUCE_SPLITK; pl.ws_used = (size_t)splits * M * N * sizeof(float); }
+    return pl;
+}
+
+// ggpm_gemm_tall_grouped (c.mode: its bf16 argument; c.K, lda, ldb, ldc, n_pad, base_a, base_b per member)
+inline GemmPlan plan_tall_group(const ggpm_gemm_call& c) {
+    const int M = c.M, N = c.N, count = c.count, bf16 = c.mode;
+    if (count <= 0 || count > GGPM_GEMM_MAX_GROUP || M <= 0 || N <= 0) return plan_refuse(GGPM_ERR_ARG);
+    GemmPlan pl;
+    const size_t slab = tall_slab_bytes(M, N);
+    // (bf16 operands exist in the tall kernel only: a group that does not qualify falls back to fp32 products, which is
+    // the more accurate side of the stated tolerance)
+    const bool in16 = bf16 == 2;
+    const size_t es = in16 ? 2 : 4;
+    bool ok = gemm_use_tall() && (count > 1 || bf16) && c.has_ws;
+    const bool split = !bf16 && tall_split_mode() != 0;      // fp32 accuracy on the bf16 pipe (gemm_tn_tall_split)
+    int splits = 1 << 30;
+    for (int i = 0; i < count && ok; ++i) {
+        ok = vec_legal(c.lda[i], c.base_a[i]) && vec_legal(c.ldb[i], c.base_b[i]) &&
+             c.lda[i] >= ggpm_round_up(M, 4) && c.ldb[i] >= ggpm_round_up(N, 4) && tall_shape(M, N, c.K[i]) &&
+             c.n_pad[i] <= ggpm_round_up(N, TN) && c.n_pad[i] >= N && c.n_pad[i] <= c.ldc[i] &&
+             fits_buffer(c.K[i] + TALL_K_OVERSHOOT, c.lda[i], es) && fits_buffer(c.K[i] + TALL_K_OVERSHOOT, c.ldb[i], es);
+        splits = min(splits, tall_splits(M, N, c.K[i], bf16 ? GGPM_TALL_BF16_WGS / count : (split ? tall_split_wgs() / count : 0)));
+    }
+    if (ok) splits = min(splits, (int)(c.ws_bytes / (count * slab)));      // the group shares the workspace
+    if (!ok || splits < ((bf16 || split) ? 1 : 2)) {
+        if (in16) return plan_refuse(GGPM_ERR_UNSUPPORTED);      // (bf16 operands in memory exist for the tall kernel only)
+        pl.kernel = GGPM_GEMM_KERNEL_SEQUENCE;
+        return pl;
+    }
+    // one launch: the K chunks of all members share the grid (same number of chunks, chunk length per member), the
+    // slabs of member i start at ws + i * splits * slab, one reduce launch sums them all
+    pl.vec_a = pl.vec_b = (1 << count) - 1;
+    pl.splits = splits;
+    for (int i = 0; i < count; ++i) pl.k_chunk[i] = ggpm_round_up(ggpm_ceil_div(c.K[i], splits), (bf16 || split) ? BTK : TK);
+    pl.grid[0] = ggpm_ceil_div(N, TN); pl.grid[1] = ggpm_ceil_div(M, TM); pl.grid[2] = splits * count;
+    if (in16) { pl.kernel = GGPM_GEMM_KERNEL_TALL_BF16_IN16; pl.lds = LDS_TALL_BF16; }
+    else if (bf16) { pl.kernel = GGPM_GEMM_KERNEL_TALL_BF16; pl.lds = LDS_TALL_BF16; }
+    else if (split) { pl.kernel = GGPM_GEMM_KERNEL_TALL_SPLIT; pl.lds = GGPM_TALL_SPLIT_LDS; }
+    else { pl.kernel = GGPM_GEMM_KERNEL_TALL; pl.lds = LDS_TALL; }
+    pl.reduce = GGPM_GEMM_REDUCE_TALL;
+    pl.ws_used = (size_t)count * splits * slab;
+    return pl;
+}
+
+// ggpm_gemm_tn_pair_grouped (c.K[0]: rows, c.lda[0]: ld, base_a: hi, base_lo: lo, base_b: B)
+inline GemmPlan plan_pairs(const ggpm_gemm_call& c) {
+    const int rows = c.K[0], ld = c.lda[0];
+    if (c.count <= 0 || c.count > GGPM_GEMM_MAX_GROUP || c.M <= 0 || c.N <= 0 || rows <= 0 || ld < c.M || ld < c.N)
+        return plan_refuse(GGPM_ERR_ARG);
+    GemmPlan pl;
+    bool ok = small_launch(c.M, c.N, c.count);
+    for (int i = 0; i < c.count; ++i) {
+        if (c.ldc[i] < c.N) return plan_refuse(GGPM_ERR_ARG);
+        ok = ok && v2_operands_ok(ld, c.base_a[i], rows, ld, c.base_b[i], rows) && v2_operands_ok(ld, c.base_lo[i], rows, ld, c.base_b[i], rows);
+    }
+    if (!ok) { pl.kernel = GGPM_GEMM_KERNEL_SEQUENCE; return pl; }
+    pl.vec_a = pl.vec_b = (1 << c.count) - 1;
+    pl.k_chunk[0] = ggpm_round_up(rows, BK);
+    plan_small(pl, c.N, c.M, c.count, 1);
+    return pl;
+}
+
+inline int group_vec_bits(const ggpm_gemm_call& c, bool b_side) {
+    int bits = 0;
+    for (int i = 0; i < c.count; ++i) bits |= (int)(b_side ? vec_legal(c.ldb[i], c.base_b[i]) : vec_legal(c.lda[i], c.base_a[i])) << i;
+    return bits;
+}
+
+// ggpm_gemm_grouped
+inline GemmPlan plan_group(const ggpm_gemm_call& c) {
+    const int M = c.M, N = c.N, K = c.K[0], count = c.count;
+    if (count <= 0 || count > GGPM_GEMM_MAX_GROUP || M <= 0 || N <= 0 || K <= 0) return plan_refuse(GGPM_ERR_ARG);
+    GemmPlan pl;
+    bool ok = count > 1;
+    int n_pad_max = 0;
+    for (int i = 0; i < count; ++i) {
+        if (c.n_pad[i] < N || c.n_pad[i] > c.ldc[i]) return plan_refuse(GGPM_ERR_ARG);
+        ok = ok && v2_operands_ok(c.lda[i], c.base_a[i], c.trans_a ? K : M, c.ldb[i], c.base_b[i], c.trans_b ? N : K);
+        n_pad_max = max(n_pad_max, c.n_pad[i]);
+    }
+    pl.vec_a = group_vec_bits(c, false); pl.vec_b = group_vec_bits(c, true);
+    pl.k_chunk[0] = ggpm_round_up(K, BK);
+    if (!ok) {
+        // every member on the scalar-load kernel (ggpm_gemm sends a product there, unsplit, whenever one of its operands
+        // does not allow 16-byte loads): the same tiles in one launch
+        bool scalar = count > 1;
+        for (int i = 0; i < count; ++i) scalar = scalar && !((pl.vec_a >> i & 1) && (pl.vec_b >> i & 1));
+        if (!scalar) { pl.kernel = GGPM_GEMM_KERNEL_SEQUENCE; return pl; }
+        pl.kernel = GGPM_GEMM_KERNEL_GROUP; pl.lds = LDS_SCALAR;
+        pl.grid[0] = ggpm_ceil_div(n_pad_max, BN); pl.grid[1] = ggpm_ceil_div(M, BM); pl.grid[2] = count;
+        return pl;
+    }
+    if (small_launch(M, N, count)) { plan_small(pl, n_pad_max, M, count, 1); return pl; }
+    pl.kernel = GGPM_GEMM_KERNEL_GROUP_V2; pl.lds = LDS_V2;
+    pl.grid[0] = ggpm_ceil_div(n_pad_max, BN); pl.grid[1] = ggpm_ceil_div(M, BM); pl.grid[2] = count;
+    return pl;
+}
+
+// ggpm_gemm_grouped_masked
+inline GemmPlan plan_group_masked(const ggpm_gemm_call& c) {
+    const int M = c.M, N = c.N, K = c.K[0], count = c.count;
+    if (count <= 0 || count > GGPM_GEMM_MAX_GROUP || M <= 0 || N <= 0 || K <= 0) return plan_refuse(GGPM_ERR_ARG);
+    int n_pad_max = 0;
+    for (int i = 0; i < count; ++i) {
+        if (c.n_pad[i] < N || c.n_pad[i] > c.ldc[i]) return plan_refuse(GGPM_ERR_ARG);
+        if (!v2_operands_ok(c.lda[i], c.base_a[i], c.trans_a ? K : M, c.ldb[i], c.base_b[i], c.trans_b ? N : K))
+            return plan_refuse(GGPM_ERR_UNSUPPORTED);
+        n_pad_max = max(n_pad_max, c.n_pad[i]);
+    }
+    if (!small_launch(M, N, count)) return plan_refuse(GGPM_ERR_UNSUPPORTED);
+    GemmPlan pl;
+    pl.vec_a = pl.vec_b = (1 << count) - 1;
+    pl.k_chunk[0] = ggpm_round_up(K, BK);
+    plan_small(pl, n_pad_max, M, count, 1);
+    return pl;
+}
+
+inline size_t group_splitk_bytes(int M, int N, int K, int count) {
+    if (M <= 0 || N <= 0 || K <= 0 || count <= 0 || count > GGPM_GEMM_MAX_GROUP || !small_launch(M, N, count)) return 0;
+    int kc;
+    const int sp = small_splits(M, N, K, count, &kc);
+    return sp > 1 ? (size_t)sp * count * M * N * sizeof(float) : 0;
+}
+
+// ggpm_gemm_grouped_splitk
+inline GemmPlan plan_group_splitk(const ggpm_gemm_call& c) {
+    const int M = c.M, N = c.N, K = c.K[0], count = c.count;
+    if (count <= 0 || count > GGPM_GEMM_MAX_GROUP || M <= 0 || N <= 0 || K <= 0) return plan_refuse(GGPM_ERR_ARG);
+    const size_t need = group_splitk_bytes(M, N, K, count);
+    bool ok = need > 0 && c.has_ws && c.ws_bytes >= need;
+    int n_pad_max = 0;
+    for (int i = 0; i < count && ok; ++i) {
+        if (c.n_pad[i] < N || c.n_pad[i] > c.ldc[i]) return plan_refuse(GGPM_ERR_ARG);
+        ok = v2_operands_ok(c.lda[i], c.base_a[i], c.trans_a ? K : M, c.ldb[i], c.base_b[i], c.trans_b ? N : K);
+        n_pad_max = max(n_pad_max, c.n_pad[i]);
+    }
+    if (!ok) return plan_group(c);
+    GemmPlan pl;
+    pl.vec_a = pl.vec_b = (1 << count) - 1;
+    const int sp = small_splits(M, N, K, count, &pl.k_chunk[0]);
+    plan_small(pl, N, M, count, sp);
+    pl.reduce = GGPM_GEMM_REDUCE_SPLITK_GROUP;
+    pl.ws_used = need;
+    return pl;
+}
+
+// ggpm_gemm_ksegments (c.count: nseg; K, lda, ldb, base_a, base_b per segment; ldc[0], n_pad[0])
+inline GemmPlan plan_segments(const ggpm_gemm_call& c) {
+    const int M = c.M, N = c.N, nseg = c.count;
+    if (nseg <= 0 || nseg > GGPM_GEMM_MAX_GROUP || M <= 0 || N <= 0 || c.n_pad[0] < N || c.n_pad[0] > c.ldc[0])
+        return plan_refuse(GGPM_ERR_ARG);
+    GemmPlan pl;
+    bool ok = nseg > 1;
+    for (int i = 0; i < nseg; ++i) {
+        if (c.K[i] <= 0) return plan_refuse(GGPM_ERR_ARG);
+        ok = ok && v2_operands_ok(c.lda[i], c.base_a[i], M, c.ldb[i], c.base_b[i], c.trans_b ? N : c.K[i]);
+    }
+    pl.vec_a = group_vec_bits(c, false); pl.vec_b = group_vec_bits(c, true);
+    pl.k_chunk[0] = ggpm_round_up(c.K[0], BK);
+    if (!ok) {
+        // every segment on the scalar-load kernel (where ggpm_gemm sends a product, unsplit, whenever one of its operands
+        // does not allow 16-byte loads): the chain of calls in ONE launch that rounds where the chain rounds (gemm_tile_64)
+        bool scalar = nseg > 1;
+        for (int i = 0; i < nseg; ++i) scalar = scalar && !((pl.vec_a >> i & 1) && (pl.vec_b >> i & 1));
+        if (!scalar) { pl.kernel = GGPM_GEMM_KERNEL_SEQUENCE; return pl; }
+        pl.kernel = GGPM_GEMM_KERNEL_SEGS; pl.lds = LDS_SCALAR;
+        pl.grid[0] = ggpm_ceil_div(c.n_pad[0], BN); pl.grid[1] = ggpm_ceil_div(M, BM); pl.grid[2] = 1;
+        return pl;
+    }
+    if (small_launch(M, N, 1)) { plan_small(pl, c.n_pad[0], M, 1, 1); return pl; }
+    pl.kernel = GGPM_GEMM_KERNEL_V2; pl.lds = LDS_V2;
+    pl.grid[0] = ggpm_ceil_div(c.n_pad[0], BN); pl.grid[1] = ggpm_ceil_div(M, BM); pl.grid[2] = 1;
+    return pl;
+}
+
+inline void call_set_member(ggpm_gemm_call& c, int i, const GgpmGemmProblem& p) {
+    c.lda[i] = p.lda; c.ldb[i] = p.ldb; c.ldc[i] = p.ldc; c.n_pad[i] = p.n_pad; c.base_a[i] = low4(p.A); c.base_b[i] = low4(p.B);
+}
+inline ggpm_gemm_call call_of_group(int entry, int trans_a, int trans_b, int M, int N, int K, int count, const GgpmGemmProblem* p,
+                                    bool has_ws, size_t ws_bytes) {
+    ggpm_gemm_call c{};
+    c.entry = entry; c.trans_a = trans_a; c.trans_b = trans_b; c.M = M; c.N = N; c.count = count; c.K[0] = K;
+    c.has_ws = has_ws; c.ws_bytes = ws_bytes;
+    for (int i = 0; i < count && i < GGPM_GEMM_MAX_GROUP; ++i) call_set_member(c, i, p[i]);
+    return c;
+}
+inline dim3 plan_grid(const GemmPlan& pl) { return dim3(pl.grid[0], pl.grid[1], pl.grid[2]); }
+}  // namespace
+
+extern "C" int ggpm_gemm_form_query(const ggpm_gemm_call* call, ggpm_gemm_form* out) {
+    if (!call || !out) return GGPM_ERR_ARG;
+    const ggpm_gemm_call& c = *call;
+    GemmPlan pl;
+    switch (c.entry) {
+        case GGPM_GEMM_ENTRY_GEMM:
+            pl = plan_gemm(c.trans_a, c.trans_b, c.M, c.N, c.K[0], c.lda[0], c.base_a[0], c.ldb[0], c.base_b[0], c.ldc[0], c.n_pad[0],
+                           c.has_ws != 0, c.ws_bytes);
+            break;
+        case GGPM_GEMM_ENTRY_GROUPED: pl = plan_group(c); break;
+        case GGPM_GEMM_ENTRY_GROUPED_SPLITK: pl = plan_group_splitk(c); break;
+        case GGPM_GEMM_ENTRY_GROUPED_MASKED: pl = plan_group_masked(c); break;
+        case GGPM_GEMM_ENTRY_KSEGMENTS: pl = plan_segments(c); break;
+        case GGPM_GEMM_ENTRY_TALL_GROUPED: pl = plan_tall_group(c); break;
+        case GGPM_GEMM_ENTRY_PAIR_GROUPED: pl = plan_pairs(c); break;
+        case GGPM_GEMM_ENTRY_TN_BF16: {      // ggpm_gemm_tn_bf16: one member, n_pad = N, operands rounded to bf16
+            if (!c.has_ws || c.M <= 0 || c.N <= 0 || c.K[0] <= 0 || c.ldc[0] < c.N) { pl = plan_refuse(GGPM_ERR_ARG); break; }
+            ggpm_gemm_call t = c;
+            t.count = 1; t.mode = 1; t.n_pad[0] = c.N;
+            pl = plan_tall_group(t);
+            break;
+        }
+        default: return GGPM_ERR_ARG;
+    }
+    *out = ggpm_gemm_form{};
+    out->rc = pl.rc;
+    if (pl.rc) return GGPM_OK;
+    out->kernel = pl.kernel; out->vec_a = pl.vec_a; out->vec_b = pl.vec_b; out->reduce = pl.reduce; out->splits = pl.splits;
+    for (int i = 0; i < GGPM_GEMM_MAX_GROUP; ++i) out->k_chunk[i] = pl.k_chunk[i];
+    for (int i = 0; i < 3; ++i) out->grid[i] = pl.grid[i];
+    out->lds_bytes = pl.lds; out->ws_used = pl.ws_used;
+    return GGPM_OK;
+}
+
 extern "C" size_t ggpm_gemm_workspace_bytes(int M, int N, int K) {
     const int s = choose_splits(M, N, K);
     size_t bytes = s > 1 ? (size_t)s * M * N * sizeof(float) : 0;
@@ -1287,42 +1607,29 @@ extern "C" int ggpm_gemm(int trans_a, int trans_b, int M, int N, int K, const fl
                          int accumulate, int act, int zero_row0, float* splitk_ws, size_t splitk_ws_bytes,
                          ggpm_stream_t stream) {
     GGPM_CLEAR_STALE_ERROR();
-    if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0 || n_pad < N || n_pad > ldc) return GGPM_ERR_ARG;
+    if (!A || !B || !C) return GGPM_ERR_ARG;
+    const GemmPlan pl = plan_gemm(trans_a, trans_b, M, N, K, lda, low4(A), ldb, low4(B), ldc, n_pad, splitk_ws != nullptr, splitk_ws_bytes);
+    if (pl.rc) return pl.rc;
     hipStream_t s = (hipStream_t)stream;
     GemmArgs g{};
     g.M = M; g.N = N; g.K = K; g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc;
     g.n_pad = n_pad; g.bias = bias; g.accumulate = accumulate; g.act = act; g.zero_row0 = zero_row0;
-    g.vecA = ((lda & 3) == 0) && (((uintptr_t)A & 15) == 0);
-    g.vecB = ((ldb & 3) == 0) && (((uintptr_t)B & 15) == 0);
-    static const int use_tall = [] { const char* e = ggpm_dev_env("GGPM_GEMM_TALL"); return e ? atoi(e) : 1; }();
-    if (use_tall && trans_a && !trans_b && g.vecA && g.vecB && lda >= ggpm_round_up(M, 4) && ldb >= ggpm_round_up(N, 4) &&
-        tall_shape(M, N, K) && n_pad <= ggpm_round_up(N, TN) && (size_t)K * lda * 4 < 0xffffff00ull && (size_t)K * ldb * 4 < 0xffffff00ull) {
-        const size_t slab = tall_slab_bytes(M, N);
-        if (tall_split_mode() && splitk_ws && splitk_ws_bytes >= slab) {
-            // split operands on the bf16 pipe (fp32 accuracy, operand-stream bound): always through slabs + tall_reduce
-            // (which applies bias / accumulate / activation)
-            int sp = tall_splits(M, N, K, tall_split_wgs());
-            if ((size_t)sp * slab > splitk_ws_bytes) sp = (int)(splitk_ws_bytes / slab);
-            if (sp < 1) sp = 1;
-            g.k_chunk = ggpm_round_up(ggpm_ceil_div(K, sp), BTK);
-            sp = ggpm_ceil_div(K, g.k_chunk);
-            g.ws = splitk_ws;
-            const int tiles_n = ggpm_ceil_div(N, TN), tiles_m = ggpm_ceil_div(M, TM);
-            GemmGroupArgs gg;
-            for (int i = 0; i < GGPM_GEMM_MAX_GROUP; ++i) gg.p[i] = g;
-            launch_tall_split(gg, dim3(tiles_n, tiles_m, sp), sp, s);
-            tall_reduce<<<tiles_n * tiles_m * 100, 256, 0, s>>>(gg, sp, tiles_n, tiles_n * tiles_m);
-            GGPM_CHECK_LAUNCH();
-            return GGPM_OK;
-        }
-        int splits = splitk_ws ? tall_splits(M, N, K) : 1;
-        if (splits > 1 && (size_t)splits * slab > splitk_ws_bytes) splits = (int)(splitk_ws_bytes / slab);
-        if (splits < 1) splits = 1;
-        g.k_chunk = ggpm_round_up(ggpm_ceil_div(K, splits), TK);
-        splits = ggpm_ceil_div(K, g.k_chunk);
-        g.ws = splits > 1 ? splitk_ws : nullptr;
-        const int tiles_n = ggpm_ceil_div(N, TN), tiles_m = ggpm_ceil_div(M, TM);
-        dim3 grid(tiles_n, tiles_m, splits);
+    g.vecA = pl.vec_a; g.vecB = pl.vec_b;
+    g.k_chunk = pl.k_chunk[0];
+    g.ws = pl.ws_used ? splitk_ws : nullptr;
+    const int splits = pl.splits;
+    const dim3 grid = plan_grid(pl);
+    if (pl.kernel == GGPM_GEMM_KERNEL_TALL_SPLIT) {
+        const int tiles_n = grid.x, tiles_m = grid.y;
+        GemmGroupArgs gg;
+        for (int i = 0; i < GGPM_GEMM_MAX_GROUP; ++i) gg.p[i] = g;
+        launch_tall_split(gg, grid, splits, s);
+        tall_reduce<<<tiles_n * tiles_m * 100, 256, 0, s>>>(gg, splits, tiles_n, tiles_n * tiles_m);
+        GGPM_CHECK_LAUNCH();
+        return GGPM_OK;
+    }
+    if (pl.kernel == GGPM_GEMM_KERNEL_TALL) {
+        const int tiles_n = grid.x, tiles_m = grid.y;
         static unsigned long long* dbg = [] {
             unsigned long long* p = nullptr;
             if (ggpm_dev_env("GGPM_GEMM_DEBUG")) (void)hipMalloc(&p, 64);
@@ -1345,31 +1652,14 @@ extern "C" int ggpm_gemm(int trans_a, int trans_b, int M, int N, int K, const fl
         GGPM_CHECK_LAUNCH();
         return GGPM_OK;
     }
-    int splits = 1;
-    if (splitk_ws) {
-        splits = choose_splits(M, N, K);
-        if (splits > 1 && (size_t)splits * M * N * sizeof(float) > splitk_ws_bytes) splits = 1;
-    }
-    if (splits > 1) {
-        g.k_chunk = ggpm_round_up(ggpm_ceil_div(K, splits), BK);
-        splits = ggpm_ceil_div(K, g.k_chunk);
-    }
-    if (splits <= 1) { splits = 1; g.k_chunk = ggpm_round_up(K, BK); g.ws = nullptr; } else { g.ws = splitk_ws; }
-    dim3 grid(ggpm_ceil_div(splits > 1 ? N : n_pad, BN), ggpm_ceil_div(M, BM), splits);
-    static const int use_v2 = [] { const char* e = ggpm_dev_env("GGPM_GEMM_V2"); return e ? atoi(e) : 1; }();
-    const size_t rows_a = trans_a ? K : M, rows_b = trans_b ? N : K;
-    if (use_v2 && splits == 1 && small_launch(M, N, 1) && g.vecA && g.vecB && rows_a * lda * 4 < 0xffffff00ull &&
-        rows_b * ldb * 4 < 0xffffff00ull) {
+    if (pl.kernel == GGPM_GEMM_KERNEL_SMALL_V3) {
         GemmGroupArgs gg;
         for (int i = 0; i < GGPM_GEMM_MAX_GROUP; ++i) gg.p[i] = g;
-        launch_small(trans_a, trans_b, gg, 1, M, n_pad, s);
+        launch_small(trans_a, trans_b, gg, grid, 1, s);
         GGPM_CHECK_LAUNCH();
         return GGPM_OK;
     }
-    // v2 keeps 70 KB of LDS per workgroup (two resident per CU): it wins while the whole grid is resident at once
-    // (latency-bound launches: 573 x 600 x 912 35 -> 25 us) and loses beyond (2843 x 912 x 340: 33 -> 37 us)
-    const bool resident = (size_t)grid.x * grid.y * grid.z <= 512 || use_v2 == 2;
-    if (use_v2 && resident && g.vecA && g.vecB && rows_a * lda * 4 < 0xffffff00ull && rows_b * ldb * 4 < 0xffffff00ull) {
+    if (pl.kernel == GGPM_GEMM_KERNEL_V2) {
         if (!trans_a && !trans_b) gemm_kernel_v2<false, false><<<grid, 256, 0, s>>>(g);
         else if (!trans_a && trans_b) gemm_kernel_v2<false, true><<<grid, 256, 0, s>>>(g);
         else if (trans_a && !trans_b) gemm_kernel_v2<true, false><<<grid, 256, 0, s>>>(g);
@@ -1387,11 +1677,6 @@ extern "C" int ggpm_gemm(int trans_a, int trans_b, int M, int N, int K, const fl
 }
 
 namespace {
-inline bool v2_operands_ok(const float* A, int lda, size_t rows_a, const float* B, int ldb, size_t rows_b) {
-    static const int use_v2 = [] { const char* e = ggpm_dev_env("GGPM_GEMM_V2"); return e ? atoi(e) : 1; }();
-    return use_v2 && (lda & 3) == 0 && (ldb & 3) == 0 && ((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0 &&
-           rows_a * lda * 4 < 0xffffff00ull && rows_b * ldb * 4 < 0xffffff00ull;
-}
 inline void fill_args(GemmArgs& g, int M, int N, int K, const GgpmGemmProblem& p) {
     g = GemmArgs{};
     g.M = M; g.N = N; g.K = K; g.A = p.A; g.lda = p.lda; g.B = p.B; g.ldb = p.ldb; g.C = p.C; g.ldc = p.ldc;
@@ -1405,26 +1690,12 @@ int ggpm_gemm_tall_grouped(int M, int N, int count, const GgpmGemmProblem* p, co
                            ggpm_stream_t stream, int bf16) {
     GGPM_CLEAR_STALE_ERROR();
     if (count <= 0 || count > GGPM_GEMM_MAX_GROUP || !p || !K || M <= 0 || N <= 0) return GGPM_ERR_ARG;
-    static const int use_tall = [] { const char* e = ggpm_dev_env("GGPM_GEMM_TALL"); return e ? atoi(e) : 1; }();
-    const size_t slab = tall_slab_bytes(M, N);
-    // (bf16 operands exist in the tall kernel only: a group that does not qualify falls back to fp32 products, which is
-    // the more accurate side of the stated tolerance)
-    const bool in16 = bf16 == 2;
-    const size_t es = in16 ? 2 : 4;
-    bool ok = use_tall && (count > 1 || bf16) && ws != nullptr;
-    const bool split = !bf16 && tall_split_mode() != 0;      // fp32 accuracy on the bf16 pipe (gemm_tn_tall_split)
-    int splits = 1 << 30;
-    for (int i = 0; i < count && ok; ++i) {
-        ok = (p[i].lda & 3) == 0 && (p[i].ldb & 3) == 0 && ((uintptr_t)p[i].A & 15) == 0 && ((uintptr_t)p[i].B & 15) == 0 &&
-             p[i].lda >= ggpm_round_up(M, 4) && p[i].ldb >= ggpm_round_up(N, 4) && tall_shape(M, N, K[i]) &&
-             p[i].n_pad <= ggpm_round_up(N, TN) && p[i].n_pad >= N && p[i].n_pad <= p[i].ldc &&
-             (size_t)K[i] * p[i].lda * es < 0xffffff00ull && (size_t)K[i] * p[i].ldb * es < 0xffffff00ull;
-        splits = min(splits, tall_splits(M, N, K[i], bf16 ? GGPM_TALL_BF16_WGS / count : (split ? tall_split_wgs() / count : 0)));
-    }
-    const int slabs_per_chunk = 1;
-    if (ok) splits = min(splits, (int)(ws_bytes / (count * slab * slabs_per_chunk)));      // the group shares the workspace
-    if (!ok || splits < ((bf16 || split) ? 1 : 2)) {
-        if (in16) return GGPM_ERR_UNSUPPORTED;      // (bf16 operands in memory exist for the tall kernel only)
+    ggpm_gemm_call c = call_of_group(GGPM_GEMM_ENTRY_TALL_GROUPED, 1, 0, M, N, 0, count, p, ws != nullptr, ws_bytes);
+    for (int i = 0; i < count; ++i) c.K[i] = K[i];
+    c.mode = bf16;
+    const GemmPlan pl = plan_tall_group(c);
+    if (pl.rc) return pl.rc;
+    if (pl.kernel == GGPM_GEMM_KERNEL_SEQUENCE) {
         for (int i = 0; i < count; ++i) {
             const int rc = ggpm_gemm(1, 0, M, N, K[i], p[i].A, p[i].lda, p[i].B, p[i].ldb, p[i].C, p[i].ldc, p[i].n_pad,
                                      p[i].bias, p[i].accumulate, p[i].act, p[i].zero_row0, ws, ws_bytes, stream);
@@ -1432,22 +1703,23 @@ int ggpm_gemm_tall_grouped(int M, int N, int count, const GgpmGemmProblem* p, co
         }
         return GGPM_OK;
     }
-    // one launch: the K chunks of all members share the grid (same number of chunks, chunk length per member), the
-    // slabs of member i start at ws + i * splits * slab, one reduce launch sums them all
+    const int splits = pl.splits;
+    const size_t slab = tall_slab_bytes(M, N);
     GemmGroupArgs gg;
     for (int i = 0; i < count; ++i) {
         fill_args(gg.p[i], M, N, K[i], p[i]);
-        gg.p[i].k_chunk = ggpm_round_up(ggpm_ceil_div(K[i], splits), (bf16 || split) ? BTK : TK);
-        gg.p[i].ws = ws + (size_t)i * splits * slabs_per_chunk * (slab / sizeof(float));
+        gg.p[i].k_chunk = pl.k_chunk[i];
+        gg.p[i].ws = ws + (size_t)i * splits * (slab / sizeof(float));
     }
     for (int i = count; i < GGPM_GEMM_MAX_GROUP; ++i) gg.p[i] = gg.p[0];
     hipStream_t s = (hipStream_t)stream;
-    const int tiles_n = ggpm_ceil_div(N, TN), tiles_m = ggpm_ceil_div(M, TM);
-    if (in16) gemm_tn_tall_bf16<true><<<dim3(tiles_n, tiles_m, splits * count), 256, 0, s>>>(gg, splits);
-    else if (bf16) gemm_tn_tall_bf16<false><<<dim3(tiles_n, tiles_m, splits * count), 256, 0, s>>>(gg, splits);
-    else if (split) launch_tall_split(gg, dim3(tiles_n, tiles_m, splits * count), splits, s);
-    else gemm_tn_tall<<<dim3(tiles_n, tiles_m, splits * count), 256, 0, s>>>(gg, splits);
-    tall_reduce<<<dim3(tiles_n * tiles_m * 100, count), 256, 0, s>>>(gg, splits * slabs_per_chunk, tiles_n, tiles_n * tiles_m);
+    const dim3 grid = plan_grid(pl);
+    const int tiles_n = grid.x, tiles_m = grid.y;
+    if (pl.kernel == GGPM_GEMM_KERNEL_TALL_BF16_IN16) gemm_tn_tall_bf16<true><<<grid, 256, 0, s>>>(gg, splits);
+    else if (pl.kernel == GGPM_GEMM_KERNEL_TALL_BF16) gemm_tn_tall_bf16<false><<<grid, 256, 0, s>>>(gg, splits);
+    else if (pl.kernel == GGPM_GEMM_KERNEL_TALL_SPLIT) launch_tall_split(gg, grid, splits, s);
+    else gemm_tn_tall<<<grid, 256, 0, s>>>(gg, splits);
+    tall_reduce<<<dim3(tiles_n * tiles_m * 100, count), 256, 0, s>>>(gg, splits, tiles_n, tiles_n * tiles_m);
     GGPM_CHECK_LAUNCH();
     return GGPM_OK;
 }
@@ -1458,11 +1730,15 @@ int ggpm_gemm_tall_grouped(int M, int N, int count, const GgpmGemmProblem* p, co
 int ggpm_gemm_tn_pair_grouped(int M, int N, int rows, int ld, int count, const ggpm_pair_problem* p, ggpm_stream_t stream) {
     GGPM_CLEAR_STALE_ERROR();
     if (count <= 0 || count > GGPM_GEMM_MAX_GROUP || !p || M <= 0 || N <= 0 || rows <= 0 || ld < M || ld < N) return GGPM_ERR_ARG;
-    bool ok = small_launch(M, N, count);
+    ggpm_gemm_call c{};
+    c.entry = GGPM_GEMM_ENTRY_PAIR_GROUPED; c.trans_a = 1; c.M = M; c.N = N; c.count = count; c.K[0] = rows; c.lda[0] = c.ldb[0] = ld;
     for (int i = 0; i < count; ++i) {
         if (!p[i].hi || !p[i].lo || !p[i].B || !p[i].C || p[i].ldc < N) return GGPM_ERR_ARG;
-        ok = ok && v2_operands_ok(p[i].hi, ld, rows, p[i].B, ld, rows) && v2_operands_ok(p[i].lo, ld, rows, p[i].B, ld, rows);
+        c.ldc[i] = p[i].ldc; c.base_a[i] = low4(p[i].hi); c.base_lo[i] = low4(p[i].lo); c.base_b[i] = low4(p[i].B);
     }
+    const GemmPlan pl = plan_pairs(c);
+    if (pl.rc) return pl.rc;
+    const bool ok = pl.kernel != GGPM_GEMM_KERNEL_SEQUENCE;
     if (!ok) {
         for (int i = 0; i < count; ++i) {
             int rc = ggpm_gemm(1, 0, M, N, rows, p[i].hi, ld, p[i].B, ld, p[i].C, p[i].ldc, N, nullptr, 0, GGPM_ACT_NONE, 0,
@@ -1484,7 +1760,7 @@ int ggpm_gemm_tn_pair_grouped(int M, int N, int rows, int ld, int count, const g
         for (int sg = 0; sg < 2; ++sg) { g.segB[sg] = p[i].B; g.seg_lda[sg] = g.seg_ldb[sg] = ld; g.segK[sg] = rows; }
     }
     for (int i = count; i < GGPM_GEMM_MAX_GROUP; ++i) gg.p[i] = gg.p[0];
-    launch_small(1, 0, gg, count, M, N, (hipStream_t)stream);
+    launch_small(1, 0, gg, plan_grid(pl), 1, (hipStream_t)stream);
     GGPM_CHECK_LAUNCH();
     return GGPM_OK;
 }
@@ -1515,39 +1791,11 @@ extern "C" int ggpm_gemm_grouped(int trans_a, int trans_b, int M, int N, int K, 
                                  ggpm_stream_t stream) {
     GGPM_CLEAR_STALE_ERROR();
     if (count <= 0 || count > GGPM_GEMM_MAX_GROUP || !p || M <= 0 || N <= 0 || K <= 0) return GGPM_ERR_ARG;
-    bool ok = count > 1;
-    int n_pad_max = 0;
-    for (int i = 0; i < count; ++i) {
+    for (int i = 0; i < count; ++i)
         if (!p[i].A || !p[i].B || !p[i].C || p[i].n_pad < N || p[i].n_pad > p[i].ldc) return GGPM_ERR_ARG;
-        ok = ok && v2_operands_ok(p[i].A, p[i].lda, trans_a ? K : M, p[i].B, p[i].ldb, trans_b ? N : K);
-        n_pad_max = max(n_pad_max, p[i].n_pad);
-    }
-    if (!ok) {
-        // every member on the scalar-load kernel (ggpm_gemm sends a product there, unsplit, whenever one of its operands
-        // does not allow 16-byte loads): the same tiles in one launch
-        bool scalar = count > 1;
-        for (int i = 0; i < count; ++i) {
-            const bool vecA = ((p[i].lda & 3) == 0) && (((uintptr_t)p[i].A & 15) == 0);
-            const bool vecB = ((p[i].ldb & 3) == 0) && (((uintptr_t)p[i].B & 15) == 0);
-            scalar = scalar && !(vecA && vecB);
-        }
-        if (scalar) {
-            GemmGroupArgs gg;
-            for (int i = 0; i < count; ++i) {
-                fill_args(gg.p[i], M, N, K, p[i]);
-                gg.p[i].vecA = ((p[i].lda & 3) == 0) && (((uintptr_t)p[i].A & 15) == 0);
-                gg.p[i].vecB = ((p[i].ldb & 3) == 0) && (((uintptr_t)p[i].B & 15) == 0);
-            }
-            for (int i = count; i < GGPM_GEMM_MAX_GROUP; ++i) gg.p[i] = gg.p[0];
-            hipStream_t s = (hipStream_t)stream;
-            dim3 grid(ggpm_ceil_div(n_pad_max, BN), ggpm_ceil_div(M, BM), count);
-            if (!trans_a && !trans_b) gemm_kernel_group<false, false><<<grid, 256, 0, s>>>(gg);
-            else if (!trans_a && trans_b) gemm_kernel_group<false, true><<<grid, 256, 0, s>>>(gg);
-            else if (trans_a && !trans_b) gemm_kernel_group<true, false><<<grid, 256, 0, s>>>(gg);
-            else gemm_kernel_group<true, true><<<grid, 256, 0, s>>>(gg);
-            GGPM_CHECK_LAUNCH();
-            return GGPM_OK;
-        }
+    const GemmPlan pl = plan_group(call_of_group(GGPM_GEMM_ENTRY_GROUPED, trans_a, trans_b, M, N, K, count, p, false, 0));
+    if (pl.rc) return pl.rc;
+    if (pl.kernel == GGPM_GEMM_KERNEL_SEQUENCE) {
         for (int i = 0; i < count; ++i) {
             const int rc = ggpm_gemm(trans_a, trans_b, M, N, K, p[i].A, p[i].lda, p[i].B, p[i].ldb, p[i].C, p[i].ldc,
                                      p[i].n_pad, p[i].bias, p[i].accumulate, p[i].act, p[i].zero_row0, nullptr, 0, stream);
@@ -1556,16 +1804,22 @@ extern "C" int ggpm_gemm_grouped(int trans_a, int trans_b, int M, int N, int K, 
         return GGPM_OK;
     }
     GemmGroupArgs gg;
-    for (int i = 0; i < count; ++i) fill_args(gg.p[i], M, N, K, p[i]);
+    for (int i = 0; i < count; ++i) {
+        fill_args(gg.p[i], M, N, K, p[i]);
+        gg.p[i].vecA = pl.vec_a >> i & 1;
+        gg.p[i].vecB = pl.vec_b >> i & 1;
+    }
     for (int i = count; i < GGPM_GEMM_MAX_GROUP; ++i) gg.p[i] = gg.p[0];
     hipStream_t s = (hipStream_t)stream;
-    if (small_launch(M, N, count)) {
-        launch_small(trans_a, trans_b, gg, count, M, n_pad_max, s);
-        GGPM_CHECK_LAUNCH();
-        return GGPM_OK;
-    }
-    dim3 grid(ggpm_ceil_div(n_pad_max, BN), ggpm_ceil_div(M, BM), count);
-    if (!trans_a && !trans_b) gemm_group_v2<false, false><<<grid, 256, 0, s>>>(gg);
+    const dim3 grid = plan_grid(pl);
+    if (pl.kernel == GGPM_GEMM_KERNEL_GROUP) {
+        if (!trans_a && !trans_b) gemm_kernel_group<false, false><<<grid, 256, 0, s>>>(gg);
+        else if (!trans_a && trans_b) gemm_kernel_group<false, true><<<grid, 256, 0, s>>>(gg);
+        else if (trans_a && !trans_b) gemm_kernel_group<true, false><<<grid, 256, 0, s>>>(gg);
+        else gemm_kernel_group<true, true><<<grid, 256, 0, s>>>(gg);
+    } else if (pl.kernel == GGPM_GEMM_KERNEL_SMALL_V3) {
+        launch_small(trans_a, trans_b, gg, grid, 1, s);
+    } else if (!trans_a && !trans_b) gemm_group_v2<false, false><<<grid, 256, 0, s>>>(gg);
     else if (!trans_a && trans_b) gemm_group_v2<false, true><<<grid, 256, 0, s>>>(gg);
     else if (trans_a && !trans_b) gemm_group_v2<true, false><<<grid, 256, 0, s>>>(gg);
     else gemm_group_v2<true, true><<<grid, 256, 0, s>>>(gg);
@@ -1579,15 +1833,14 @@ extern "C" int ggpm_gemm_grouped_masked(int trans_a, int trans_b, int M, int N, 
                                         const ggpm_gemm_epilogue* e, ggpm_stream_t stream) {
     GGPM_CLEAR_STALE_ERROR();
     if (count <= 0 || count > GGPM_GEMM_MAX_GROUP || !p || !e || M <= 0 || N <= 0 || K <= 0) return GGPM_ERR_ARG;
-    int n_pad_max = 0;
     for (int i = 0; i < count; ++i) {
         if (!p[i].A || !p[i].B || !p[i].C || p[i].n_pad < N || p[i].n_pad > p[i].ldc) return GGPM_ERR_ARG;
         if (e[i].addend && e[i].ld_addend < N) return GGPM_ERR_ARG;
         if (e[i].mask_out && (!e[i].mask_y || e[i].ld_mask < N)) return GGPM_ERR_ARG;
-        if (!v2_operands_ok(p[i].A, p[i].lda, trans_a ? K : M, p[i].B, p[i].ldb, trans_b ? N : K)) return GGPM_ERR_UNSUPPORTED;
-        n_pad_max = max(n_pad_max, p[i].n_pad);
+        if (!v2_operands_ok(p[i].lda, low4(p[i].A), trans_a ? K : M, p[i].ldb, low4(p[i].B), trans_b ? N : K)) return GGPM_ERR_UNSUPPORTED;
     }
-    if (!small_launch(M, N, count)) return GGPM_ERR_UNSUPPORTED;
+    const GemmPlan pl = plan_group_masked(call_of_group(GGPM_GEMM_ENTRY_GROUPED_MASKED, trans_a, trans_b, M, N, K, count, p, false, 0));
+    if (pl.rc) return pl.rc;
     GemmGroupArgs gg;
     for (int i = 0; i < count; ++i) {
         fill_args(gg.p[i], M, N, K, p[i]);
@@ -1596,33 +1849,29 @@ extern "C" int ggpm_gemm_grouped_masked(int trans_a, int trans_b, int M, int N, 
         gg.p[i].mask_act = e[i].mask_act; gg.p[i].mask_zero_row0 = e[i].mask_zero_row0;
     }
     for (int i = count; i < GGPM_GEMM_MAX_GROUP; ++i) gg.p[i] = gg.p[0];
-    launch_small(trans_a, trans_b, gg, count, M, n_pad_max, (hipStream_t)stream);
+    launch_small(trans_a, trans_b, gg, plan_grid(pl), 1, (hipStream_t)stream);
     GGPM_CHECK_LAUNCH();
     return GGPM_OK;
 }
 
 extern "C" size_t ggpm_gemm_grouped_splitk_workspace_bytes(int M, int N, int K, int count) {
-    if (M <= 0 || N <= 0 || K <= 0 || count <= 0 || count > GGPM_GEMM_MAX_GROUP || !small_launch(M, N, count)) return 0;
-    int kc;
-    const int sp = small_splits(M, N, K, count, &kc);
-    return sp > 1 ? (size_t)sp * count * M * N * sizeof(float) : 0;
+    return group_splitk_bytes(M, N, K, count);
 }
 
 extern "C" int ggpm_gemm_grouped_splitk(int trans_a, int trans_b, int M, int N, int K, int count, const ggpm_gemm_problem* p,
                                         float* ws, size_t ws_bytes, ggpm_stream_t stream) {
     GGPM_CLEAR_STALE_ERROR();
     if (count <= 0 || count > GGPM_GEMM_MAX_GROUP || !p || M <= 0 || N <= 0 || K <= 0) return GGPM_ERR_ARG;
-    const size_t need = ggpm_gemm_grouped_splitk_workspace_bytes(M, N, K, count);
+    const size_t need = group_splitk_bytes(M, N, K, count);
     bool ok = need > 0 && ws && ws_bytes >= need;
-    int n_pad_max = 0;
-    for (int i = 0; i < count && ok; ++i) {
+    for (int i = 0; i < count && ok; ++i)
         if (!p[i].A || !p[i].B || !p[i].C || p[i].n_pad < N || p[i].n_pad > p[i].ldc) return GGPM_ERR_ARG;
-        ok = v2_operands_ok(p[i].A, p[i].lda, trans_a ? K : M, p[i].B, p[i].ldb, trans_b ? N : K);
-        n_pad_max = max(n_pad_max, p[i].n_pad);
-    }
-    if (!ok) return ggpm_gemm_grouped(trans_a, trans_b, M, N, K, count, p, stream);
-    int kc;
-    const int sp = small_splits(M, N, K, count, &kc);
+    const GemmPlan pl = plan_group_splitk(call_of_group(GGPM_GEMM_ENTRY_GROUPED_SPLITK, trans_a, trans_b, M, N, K, count, p, ws != nullptr, ws_bytes));
+    if (pl.rc) return pl.rc;
+    if (pl.reduce != GGPM_GEMM_REDUCE_SPLITK_GROUP) return ggpm_gemm_grouped(trans_a, trans_b, M, N, K, count, p, stream);
+    const int kc = pl.k_chunk[0], sp = pl.splits;
+    int n_pad_max = 0;
+    for (int i = 0; i < count; ++i) n_pad_max = max(n_pad_max, p[i].n_pad);
     GemmGroupArgs gg;
     for (int i = 0; i < count; ++i) {
         fill_args(gg.p[i], M, N, K, p[i]);
@@ -1631,7 +1880,7 @@ extern "C" int ggpm_gemm_grouped_splitk(int trans_a, int trans_b, int M, int N, 
     }
     for (int i = count; i < GGPM_GEMM_MAX_GROUP; ++i) gg.p[i] = gg.p[0];
     hipStream_t s = (hipStream_t)stream;
-    launch_small(trans_a, trans_b, gg, count, M, N, s, sp);
+    launch_small(trans_a, trans_b, gg, plan_grid(pl), sp, s);
     splitk_reduce_group<<<dim3(ggpm_ceil_div(n_pad_max, 256), M, count), 256, 0, s>>>(gg, sp);
     GGPM_CHECK_LAUNCH();
     return GGPM_OK;
@@ -1644,38 +1893,15 @@ extern "C" int ggpm_gemm_ksegments(int trans_b, int M, int N, int nseg, const fl
     if (nseg <= 0 || nseg > GGPM_GEMM_MAX_GROUP || !A || !lda || !B || !ldb || !K || !C || M <= 0 || N <= 0 || n_pad < N ||
         n_pad > ldc)
         return GGPM_ERR_ARG;
-    bool ok = nseg > 1;
+    ggpm_gemm_call c{};
+    c.entry = GGPM_GEMM_ENTRY_KSEGMENTS; c.trans_b = trans_b; c.M = M; c.N = N; c.count = nseg; c.ldc[0] = ldc; c.n_pad[0] = n_pad;
     for (int i = 0; i < nseg; ++i) {
         if (!A[i] || !B[i] || K[i] <= 0) return GGPM_ERR_ARG;
-        ok = ok && v2_operands_ok(A[i], lda[i], M, B[i], ldb[i], trans_b ? N : K[i]);
+        c.K[i] = K[i]; c.lda[i] = lda[i]; c.ldb[i] = ldb[i]; c.base_a[i] = low4(A[i]); c.base_b[i] = low4(B[i]);
     }
-    if (!ok && nseg > 1) {
-        // every segment on the scalar-load kernel (where ggpm_gemm sends a product, unsplit, whenever one of its operands
-        // does not allow 16-byte loads): the chain below in ONE launch that rounds where the chain rounds (gemm_tile_64)
-        bool scalar = true;
-        int seg_vec = 0;
-        for (int i = 0; i < nseg; ++i) {
-            const bool vecA = ((lda[i] & 3) == 0) && (((uintptr_t)A[i] & 15) == 0);
-            const bool vecB = ((ldb[i] & 3) == 0) && (((uintptr_t)B[i] & 15) == 0);
-            scalar = scalar && !(vecA && vecB);
-            seg_vec |= (vecA ? 1 : 0) << (2 * i) | (vecB ? 1 : 0) << (2 * i + 1);
-        }
-        if (scalar) {
-            GemmArgs g{};
-            g.M = M; g.N = N; g.K = K[0]; g.C = C; g.ldc = ldc; g.n_pad = n_pad;
-            g.bias = bias; g.accumulate = accumulate; g.act = act; g.zero_row0 = zero_row0;
-            g.k_chunk = ggpm_round_up(K[0], BK);
-            g.nseg = nseg; g.seg_vec = seg_vec;
-            for (int i = 0; i < nseg; ++i) { g.segA[i] = A[i]; g.segB[i] = B[i]; g.seg_lda[i] = lda[i]; g.seg_ldb[i] = ldb[i]; g.segK[i] = K[i]; }
-            hipStream_t s = (hipStream_t)stream;
-            dim3 grid(ggpm_ceil_div(n_pad, BN), ggpm_ceil_div(M, BM), 1);
-            if (trans_b) gemm_kernel_segs<true><<<grid, 256, 0, s>>>(g);
-            else gemm_kernel_segs<false><<<grid, 256, 0, s>>>(g);
-            GGPM_CHECK_LAUNCH();
-            return GGPM_OK;
-        }
-    }
-    if (!ok) {      // bias with the first product, activation / row mask with the last
+    const GemmPlan pl = plan_segments(c);
+    if (pl.rc) return pl.rc;
+    if (pl.kernel == GGPM_GEMM_KERNEL_SEQUENCE) {      // bias with the first product, activation / row mask with the last
         for (int i = 0; i < nseg; ++i) {
             const bool last = i == nseg - 1;
             const int rc = ggpm_gemm(0, trans_b, M, N, K[i], A[i], lda[i], B[i], ldb[i], C, ldc, i == 0 ? n_pad : N,
@@ -1686,24 +1912,46 @@ extern "C" int ggpm_gemm_ksegments(int trans_b, int M, int N, int nseg, const fl
         return GGPM_OK;
     }
     GemmArgs g{};
-    g.M = M; g.N = N; g.K = K[0]; g.A = A[0]; g.lda = lda[0]; g.B = B[0]; g.ldb = ldb[0]; g.C = C; g.ldc = ldc; g.n_pad = n_pad;
-    g.bias = bias; g.accumulate = accumulate; g.act = act; g.zero_row0 = zero_row0; g.vecA = g.vecB = 1;
-    g.k_chunk = ggpm_round_up(K[0], BK);
+    g.M = M; g.N = N; g.K = K[0]; g.C = C; g.ldc = ldc; g.n_pad = n_pad;
+    g.bias = bias; g.accumulate = accumulate; g.act = act; g.zero_row0 = zero_row0;
+    g.k_chunk = pl.k_chunk[0];
     g.nseg = nseg;
     for (int i = 0; i < nseg; ++i) { g.segA[i] = A[i]; g.segB[i] = B[i]; g.seg_lda[i] = lda[i]; g.seg_ldb[i] = ldb[i]; g.segK[i] = K[i]; }
     hipStream_t s = (hipStream_t)stream;
-    if (small_launch(M, N, 1)) {
-        GemmGroupArgs gg;
-        for (int i = 0; i < GGPM_GEMM_MAX_GROUP; ++i) gg.p[i] = g;
-        launch_small(0, trans_b, gg, 1, M, n_pad, s);
+    const dim3 grid = plan_grid(pl);
+    if (pl.kernel == GGPM_GEMM_KERNEL_SEGS) {
+        for (int i = 0; i < nseg; ++i) g.seg_vec |= (pl.vec_a >> i & 1) << (2 * i) | (pl.vec_b >> i & 1) << (2 * i + 1);
+        if (trans_b) gemm_kernel_segs<true><<<grid, 256, 0, s>>>(g);
+        else gemm_kernel_segs<false><<<grid, 256, 0, s>>>(g);
         GGPM_CHECK_LAUNCH();
         return GGPM_OK;
     }
-    dim3 grid(ggpm_ceil_div(n_pad, BN), ggpm_ceil_div(M, BM), 1);
+    g.A = A[0]; g.lda = lda[0]; g.B = B[0]; g.ldb = ldb[0]; g.vecA = g.vecB = 1;
+    if (pl.kernel == GGPM_GEMM_KERNEL_SMALL_V3) {
+        GemmGroupArgs gg;
+        for (int i = 0; i < GGPM_GEMM_MAX_GROUP; ++i) gg.p[i] = g;
+        launch_small(0, trans_b, gg, grid, 1, s);
+        GGPM_CHECK_LAUNCH();
+        return GGPM_OK;
+    }
     if (trans_b) gemm_kernel_v2<false, true><<<grid, 256, 0, s>>>(g);
     else gemm_kernel_v2<false, false><<<grid, 256, 0, s>>>(g);
     GGPM_CHECK_LAUNCH();
     return GGPM_OK;
+}
+
+// the internal entry points under C linkage (include/ggpm_hip.h), as the level weight gradients call them
+extern "C" int ggpm_gemm_tn_tall_grouped(int M, int N, int count, const ggpm_gemm_problem* problems, const int* K, float* ws,
+                                         size_t ws_bytes, int mode, ggpm_stream_t stream) {
+    if (mode < 0 || mode > 2) return GGPM_ERR_ARG;
+    return ggpm_gemm_tall_grouped(M, N, count, problems, K, ws, ws_bytes, stream, mode);
+}
+extern "C" int ggpm_gemm_tn_pair_grouped_c(int M, int N, int rows, int ld, int count, const ggpm_pair_problem* problems,
+                                           ggpm_stream_t stream) {
+    return ggpm_gemm_tn_pair_grouped(M, N, rows, ld, count, problems, stream);
+}
+extern "C" int ggpm_colsum_dtype(const float* A, int lda, int M, int N, float* out, float* ws, int a_bf16, ggpm_stream_t stream) {
+    return ggpm_colsum_any(A, lda, M, N, out, ws, a_bf16 != 0, stream);
 }
 
 extern "C" int ggpm_colsum(const float* A, int lda, int M, int N, float* out, float* ws, ggpm_stream_t stream) {

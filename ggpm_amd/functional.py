@@ -412,6 +412,50 @@ class GemmProblem(ctypes.Structure):
                 ("accumulate", ctypes.c_int), ("act", ctypes.c_int), ("zero_row0", ctypes.c_int)]
 
 
+class PairProblem(ctypes.Structure):
+    """include/ggpm_hip.h: ggpm_pair_problem"""
+    _fields_ = [("hi", ctypes.c_void_p), ("lo", ctypes.c_void_p), ("B", ctypes.c_void_p), ("C", ctypes.c_void_p),
+                ("ldc", ctypes.c_int)]
+
+
+_I4 = ctypes.c_int * 4
+GEMM_ENTRIES = ("gemm", "grouped", "grouped_splitk", "grouped_masked", "ksegments", "tall_grouped", "pair_grouped", "tn_bf16")
+GEMM_KERNELS = ("none", "gemm_kernel", "gemm_kernel_segs", "gemm_kernel_group", "gemm_kernel_v2", "gemm_group_v2",
+                "gemm_small_v3", "gemm_tn_tall", "gemm_tn_tall_bf16<false>", "gemm_tn_tall_bf16<true>", "gemm_tn_tall_split",
+                "sequence")
+GEMM_REDUCES = ("none", "splitk_reduce", "splitk_reduce_group", "tall_reduce")
+
+
+class GemmCall(ctypes.Structure):
+    """include/ggpm_hip.h: ggpm_gemm_call -- what the GEMM dispatchers look at"""
+    _fields_ = [("entry", ctypes.c_int), ("trans_a", ctypes.c_int), ("trans_b", ctypes.c_int), ("M", ctypes.c_int),
+                ("N", ctypes.c_int), ("count", ctypes.c_int), ("K", _I4), ("lda", _I4), ("ldb", _I4), ("ldc", _I4),
+                ("n_pad", _I4), ("base_a", _I4), ("base_b", _I4), ("base_lo", _I4), ("has_ws", ctypes.c_int),
+                ("mode", ctypes.c_int), ("ws_bytes", ctypes.c_size_t)]
+
+
+class GemmForm(ctypes.Structure):
+    """include/ggpm_hip.h: ggpm_gemm_form -- the kernel, reduce, split and grid a GEMM call takes"""
+    _fields_ = [("kernel", ctypes.c_int), ("vec_a", ctypes.c_int), ("vec_b", ctypes.c_int), ("reduce", ctypes.c_int),
+                ("splits", ctypes.c_int), ("k_chunk", _I4), ("grid", ctypes.c_int * 3), ("rc", ctypes.c_int),
+                ("lds_bytes", ctypes.c_size_t), ("ws_used", ctypes.c_size_t)]
+
+
+def gemm_form(entry: str, ta: int, tb: int, M: int, N: int, K, lda, ldb, ldc, n_pad, base_a=0, base_b=0, base_lo=0,
+              count: int = 1, ws_bytes: Optional[int] = None, mode: int = 0) -> GemmForm:
+    """ggpm_gemm_form_query: the form the GEMM entry point ``entry`` (GEMM_ENTRIES) takes for this call -> GemmForm, whose
+    ``rc`` is what the call itself would return.  K, the leading dimensions, n_pad and the low address bits are per member
+    (an int stands for every member); ``ws_bytes`` None: no workspace passed.  Host only: needs no GPU."""
+    def four(v):
+        v = list(v) if isinstance(v, (list, tuple)) else [v] * 4
+        return _I4(*(v + [0] * (4 - len(v))))
+    call = GemmCall(GEMM_ENTRIES.index(entry), ta, tb, M, N, count, four(K), four(lda), four(ldb), four(ldc), four(n_pad),
+                    four(base_a), four(base_b), four(base_lo), int(ws_bytes is not None), mode, ws_bytes or 0)
+    out = GemmForm()
+    _lib.check(_lib.load().ggpm_gemm_form_query(ctypes.byref(call), ctypes.byref(out)), "gemm_form_query")
+    return out
+
+
 class LevelOpts(ctypes.Structure):
     """include/ggpm_hip.h: ggpm_level_opts -- the options of ONE level call (None: all defaults)"""
     _fields_ = [("gate_dtype", ctypes.c_int), ("prefer_narrow", ctypes.c_int), ("weights_packed", ctypes.c_int),

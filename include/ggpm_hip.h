@@ -153,6 +153,58 @@ int ggpm_linear_wgrads_batch(int count, const ggpm_wgrad_item* items, float* ws,
                              ggpm_stream_t stream);
 /* out[n] = sum_m A[m*lda+n] (bias gradients), deterministic two-stage; ws >= 256*N floats. */
 int ggpm_colsum(const float* A, int lda, int M, int N, float* out, float* ws, ggpm_stream_t stream);
+/* The three products the level weight gradients are built from (csrc/mpn_gru.hip, csrc/mpn_lstm.hip), callable by themselves:
+ *   ggpm_gemm_tn_tall_grouped -- `count` (<= 4) contractions C_i = A_i^T B_i of one output shape, K[i] rows each, in one launch
+ *       of a 160 x 160 tall kernel plus one reduce; mode 0: fp32 operands at fp32 accuracy, 1: fp32 operands rounded to bf16,
+ *       2: the operands ARE bf16 in memory (lda / ldb in elements).  A group that does not qualify for the tall kernel runs
+ *       as ggpm_gemm(1, 0, ...) per member (modes 0, 1) or returns GGPM_ERR_UNSUPPORTED and launches nothing (mode 2).
+ *   ggpm_gemm_tn_pair_grouped_c -- C_i[M x N] = hi_i^T B_i + lo_i^T B_i, every operand [rows, ld], in one launch of the
+ *       small-tile kernel (one accumulator chain over both); two products per member when the group has too many tiles.
+ *   ggpm_colsum_dtype -- ggpm_colsum of an fp32 (a_bf16 = 0) or bf16 (lda in elements) matrix. */
+typedef struct ggpm_pair_problem { const float *hi, *lo, *B; float* C; int ldc; } ggpm_pair_problem;
+int ggpm_gemm_tn_tall_grouped(int M, int N, int count, const ggpm_gemm_problem* problems, const int* K, float* ws,
+                              size_t ws_bytes, int mode, ggpm_stream_t stream);
+int ggpm_gemm_tn_pair_grouped_c(int M, int N, int rows, int ld, int count, const ggpm_pair_problem* problems,
+                                ggpm_stream_t stream);
+int ggpm_colsum_dtype(const float* A, int lda, int M, int N, float* out, float* ws, int a_bf16, ggpm_stream_t stream);
+
+/* Which kernel a product runs on.  Host only: no HIP call, nothing launched.  The entry points above and this query decide
+ * through the same functions (csrc/gemm.hip: plan_gemm, plan_tall_group, plan_group, plan_group_splitk, plan_segments,
+ * plan_pairs), so what it reports is what a call does; DESIGN.md ("The GEMM forms") lists the thresholds.
+ * `call` describes what the dispatchers look at; pointers appear as the low four bits of their address only.
+ *   entry   -- GGPM_GEMM_ENTRY_*: the entry point; count: members (grouped entries) or segments (ksegments), 1 for gemm
+ *   K[i]    -- per member (tall_grouped) or per segment (ksegments); the other entries read K[0] (pair_grouped: rows)
+ *   lda, ldb, ldc, n_pad, base_a, base_b -- per member / segment (ksegments: ldc[0], n_pad[0]; pair_grouped: lda[0] = ld,
+ *              base_a = hi, base_lo = lo, base_b = B)
+ *   has_ws, ws_bytes -- whether a workspace pointer is passed, and its size
+ *   mode    -- tall_grouped: 0 / 1 / 2 as above
+ * The form: kernel (GGPM_GEMM_KERNEL_*; SEQUENCE: one ggpm_gemm call per member / segment (pair_grouped: two), each with
+ * the form ggpm_gemm reports for it), vec_a / vec_b (bit i: 16-byte loads legal for member i's operand), reduce
+ * (GGPM_GEMM_REDUCE_*), splits (grid.z chunks per member), k_chunk per member, the grid, static + dynamic LDS bytes of the
+ * product kernel, the bytes of workspace the call writes, and `rc`: what the entry point itself would return
+ * (GGPM_ERR_ARG / GGPM_ERR_UNSUPPORTED launch nothing: kernel = NONE).  Returns GGPM_ERR_ARG for a NULL argument or an
+ * unknown entry, GGPM_OK otherwise. */
+enum { GGPM_GEMM_ENTRY_GEMM = 0, GGPM_GEMM_ENTRY_GROUPED, GGPM_GEMM_ENTRY_GROUPED_SPLITK, GGPM_GEMM_ENTRY_GROUPED_MASKED,
+       GGPM_GEMM_ENTRY_KSEGMENTS, GGPM_GEMM_ENTRY_TALL_GROUPED, GGPM_GEMM_ENTRY_PAIR_GROUPED, GGPM_GEMM_ENTRY_TN_BF16 };
+enum { GGPM_GEMM_KERNEL_NONE = 0, GGPM_GEMM_KERNEL_SCALAR, GGPM_GEMM_KERNEL_SEGS, GGPM_GEMM_KERNEL_GROUP, GGPM_GEMM_KERNEL_V2,
+       GGPM_GEMM_KERNEL_GROUP_V2, GGPM_GEMM_KERNEL_SMALL_V3, GGPM_GEMM_KERNEL_TALL, GGPM_GEMM_KERNEL_TALL_BF16,
+       GGPM_GEMM_KERNEL_TALL_BF16_IN16, GGPM_GEMM_KERNEL_TALL_SPLIT, GGPM_GEMM_KERNEL_SEQUENCE };
+enum { GGPM_GEMM_REDUCE_NONE = 0, GGPM_GEMM_REDUCE_SPLITK, GGPM_GEMM_REDUCE_SPLITK_GROUP, GGPM_GEMM_REDUCE_TALL };
+typedef struct ggpm_gemm_call {
+    int entry, trans_a, trans_b, M, N, count;
+    int K[4], lda[4], ldb[4], ldc[4], n_pad[4];
+    int base_a[4], base_b[4], base_lo[4];
+    int has_ws, mode;
+    size_t ws_bytes;
+} ggpm_gemm_call;
+typedef struct ggpm_gemm_form {
+    int kernel, vec_a, vec_b, reduce, splits;
+    int k_chunk[4];
+    int grid[3];
+    int rc;
+    size_t lds_bytes, ws_used;
+} ggpm_gemm_form;
+int ggpm_gemm_form_query(const ggpm_gemm_call* call, ggpm_gemm_form* out);
 /* dpre = dy * act'(y) given the activation OUTPUT y; optional row-0 zeroing. In-place allowed. */
 int ggpm_act_backward(const float* dy, const float* y, int rows, int cols, int ld, int act,
                       int zero_row0, float* dpre, ggpm_stream_t stream);

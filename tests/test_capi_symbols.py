@@ -44,11 +44,12 @@ def test_ctypes_structs_match_the_header_layout(tmp_path):
         # GPU process is what is refused -- but a fork of a process with live HIP state buys nothing here)
         pytest.skip("the ABI probe runs gcc in child processes: kept to processes that have not initialised the GPU")
     from ggpm_amd.atom_decode import DecodeSteps
-    from ggpm_amd.functional import LevelForm, LevelOpts
+    from ggpm_amd.functional import GemmCall, GemmForm, LevelForm, LevelOpts
     from ggpm_amd.fused import EncDims
     from ggpm_amd.schedule_native import SchedIn
     from ggpm_amd.tree_decode import TreeLevelC, TreeLevelGrads, TreeLevelViews
-    structs = {"ggpm_enc_dims": EncDims, "ggpm_level_opts": LevelOpts, "ggpm_level_form": LevelForm, "ggpm_decode_steps": DecodeSteps, "ggpm_sched_in": SchedIn,
+    structs = {"ggpm_enc_dims": EncDims, "ggpm_level_opts": LevelOpts, "ggpm_level_form": LevelForm, "ggpm_gemm_call": GemmCall,
+               "ggpm_gemm_form": GemmForm, "ggpm_decode_steps": DecodeSteps, "ggpm_sched_in": SchedIn,
                "ggpm_tree_level": TreeLevelC, "ggpm_tree_level_views": TreeLevelViews, "ggpm_tree_level_grads": TreeLevelGrads}
     lines = []
     for cname, cls in structs.items():
