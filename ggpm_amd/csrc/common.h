@@ -25,7 +25,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // Tuning / ablation switches (tile splits, kernel selections, phases switched off for timing, ...) are read from the
 // environment only in the DEV variant of the library -- `python -m ggpm_amd.build --variant dev -DGGPM_DEV_SWITCHES`, selected
 // at run time with GGPM_LIB_PATH.  The product build compiles every one of them to its default: it has no environment
-// switches of its own.  tools/README.md lists the names.
+// switches of its own.  tools/README.md lists the names.  (The level launchers read theirs in level_host.h, once for both
+// cells: GGPM_TG_SMALL, formerly a GRU switch, applies to LSTM levels as well; GGPM_RT2 and GGPM_ADEBUG stay with the GRU.)
 #ifdef GGPM_DEV_SWITCHES
 inline const char* ggpm_dev_env(const char* name) { return getenv(name); }
 #else
@@ -197,7 +198,8 @@ bool ggpm_bf16_storage_applies(int E1, int H);       // (gemm.hip: one stash slo
 inline bool ggpm_level_st16(int gate_mode, bool sparse, bool keeps_arrays, int E1, int H) {
     return gate_mode == 1 && !sparse && keeps_arrays && ggpm_bf16_storage_applies(E1, H);
 }
-// ggpm_level_form_query per cell (mpn_gru.hip / mpn_lstm.hip, beside the launchers whose decisions they report); E1, H > 0
+// ggpm_level_form_query per cell (mpn_gru.hip / mpn_lstm.hip: level_host.h's level_form over the cell's description, the
+// same functions the launchers beside them decide through); E1, H > 0
 int ggpm_gru_level_form(int E1, int H, int sparse, int training, const ggpm_level_opts& o, ggpm_level_form* out);
 int ggpm_lstm_level_form(int E1, int H, int sparse, int training, const ggpm_level_opts& o, ggpm_level_form* out);
 // out[i] = sum_t src[t][i] over `slots` slots of `slot_floats` elements, src fp32 or bf16 (first half of its buffer); fixed order

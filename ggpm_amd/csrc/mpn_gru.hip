@@ -20,6 +20,7 @@
 // Weight gradients are three tall split-K GEMMs over the [depth*E1, Hp] stashes (gemm.hip), issued by the caller
 // on a second stream.  sparse_forward (rows with a `frozen` mask) reuses the same kernels.
 #include "tile_mma.h"
+#include "level_host.h"
 #include <cstdlib>
 #include <cstdio>
 
@@ -736,188 +737,92 @@ __global__ void GGPM_A_BOUNDS gru_bwd_b(GruBwdArgs a) {
     }
 }
 
-template <typename K>
-inline void set_lds(K kernel, size_t bytes) { ggpm_set_lds(kernel, bytes); }      // (common.h)
-
-// Environment switches are read once: getenv walks the whole environment (~0.5 us) and the launch helpers below run
-// ~120 times per training step.
-inline bool env_no_fuse_b() { static const bool v = ggpm_dev_env("GGPM_NO_FUSE_B") != nullptr; return v; }
-inline bool env_adebug() { static const bool v = ggpm_dev_env("GGPM_ADEBUG") != nullptr; return v; }
-
-inline int pick_tg(int E1, int NT) {
-    static const char* const tg_env = ggpm_dev_env("GGPM_TG");
-    if (const char* e = tg_env) { int v = atoi(e); if (v >= 1 && v <= 64) return v; }   // tuning override
-    static const char* const tg_small_env = ggpm_dev_env("GGPM_TG_SMALL");
-    if (const char* e = tg_small_env) {      // tuning override for the small (motif / attachment) levels only
-        int v = atoi(e);
-        if (v >= 1 && v <= 64 && (E1 + 15) / 16 <= 64) return v < NT ? v : NT;
+// What level_host.h needs to know about the GRU (each line is a difference from the LSTM; DESIGN.md 5.1 has the table).
+struct GruCell {
+    static constexpr StepNeed fwd = {{3, 1, 3}, {2, 1, 2}, {1, 0, 1}};      // fused: s, g, h' | A: s, g | B: the h' rows
+    static constexpr StepNeed bwd = {{4, 1, 3}, {2, 1, 1}, {2, 0, 2}};      // kernel B: the dz_pre and dm_pre rows
+    static constexpr int bwd_fuse_max_tiles = 2 * GGPM_NWA;                 // the fused dS / dG phase: two output tiles per wave
+    static constexpr bool rt2_bf16 = true;                                  // gru_*<1, 2> and gru_*<1, 2, true> exist
+    static constexpr int gate_products = 2;                                 // forward Wz.s, Wh.g; backward B dG, dS
+    static constexpr int timing_base = 0;                                   // ggpm_timing_begin slots 0 / 1 / 4 / 5
+    static constexpr int n_mat = 3, n_stash = 2;                            // Wz, Wh, Ur; DMP, DZP
+    static constexpr int csws_rows = 256;                                   // column-sum scratch of db_u
+    // two row tiles per workgroup where the level is large enough to be bound by the weight stream (see GGPM_RT2_MIN_ROW_TILES)
+    // or the caller asks for it (ggpm_level_opts.prefer_narrow)
+    static bool use_rt2(const ggpm_level_opts& o, int E1, int Hp, bool sparse) {
+        static const int mode = [] { const char* e = ggpm_dev_env("GGPM_RT2"); return e ? atoi(e) : 1; }();     // 0 off, 2 always
+        if (mode == 0 || sparse) return false;
+        if (lds_tiles(2, Hp, 32) > GGPM_LDS_LIMIT) return false;
+        return mode == 2 || o.prefer_narrow || ggpm_ceil_div(E1, 16) >= GGPM_RT2_MIN_ROW_TILES;
     }
-    static const char* const tg_large_env = ggpm_dev_env("GGPM_TG_LARGE");
-    if (const char* e = tg_large_env) {      // tuning override for the large (atom) levels only
-        int v = atoi(e);
-        if (v >= 1 && v <= 64 && (E1 + 15) / 16 > 64) return v < NT ? v : NT;
-    }
-    return ggpm_tiles_per_group(E1, NT);
-}
+    // mode 2: the fp32 tile + two bf16 images of the forward A launch
+    static bool mode2_fits(int Hp) { return lds_tiles(1, Hp) + 2 * ggpm_split_image_bytes(16, Hp) <= GGPM_LDS_LIMIT; }
+    // one LDS tile pair of 16 rows must fit a CU
+    static bool shape_ok(int, int Hp) { return lds_tiles(2, Hp) <= GGPM_LDS_LIMIT; }
+};
 
-// two row tiles per workgroup where the level is large enough to be bound by the weight stream (see GGPM_RT2_MIN_ROW_TILES)
-// or the caller asks for it (ggpm_level_opts.prefer_narrow)
-inline bool use_rt2(const ggpm_level_opts& o, int E1, int Hp, bool sparse) {
-    static const int mode = [] { const char* e = ggpm_dev_env("GGPM_RT2"); return e ? atoi(e) : 1; }();     // 0 off, 2 always
-    if (mode == 0 || sparse) return false;
-    if ((size_t)2 * 32 * (Hp + 4) * sizeof(float) > 160 * 1024) return false;
-    return mode == 2 || o.prefer_narrow || ggpm_ceil_div(E1, 16) >= GGPM_RT2_MIN_ROW_TILES;
-}
-
-// Gate mode of a level call (GruFwdArgs.bf16): the caller's dtype 1 (bf16 operands) stays; an fp32 call runs its gate products
-// on split operands (mode 2: fp32 accuracy on the bf16 matrix pipe, tile_mma.h) where that form is the faster one -- DENSE
-// levels whose row tiles alone fill the chip (one column group: one 16-wave workgroup per 16 messages owns all gate columns,
-// four waves per SIMD take turns on the pipe; the atom level: 33.9 -> 31.4 / 39.1 -> 35.8 us per launch, LSTM 46.2 -> 36.7 /
-// 49.7 -> 42.0) and whose fp32 tile + two bf16 images fit the LDS -- and on fp32 MFMA (mode 0) otherwise: with column groups
-// (the tree-side levels, the decode steps) ONE wave per SIMD streams three weight planes with nothing to hide their latency
-// behind and the launch gets slower (attachment level gru_bwd_a 11.7 -> 16.7 us).  Sparse calls are always mode 0, so a
-// sequence of them sharing one packed weight set (ggpm_level_opts.weights_packed) agrees on it.  dtype 3 forces mode 2 wherever it
-// fits (tests); GGPM_GATE_SPLIT=0: mode 0 everywhere (A/B runs).
-inline int gate_mode(const ggpm_level_opts& o, int Hp, bool rt2, bool single_group, bool sparse) {
-    const int dtype = o.gate_dtype;
-    if (dtype == 1) return 1;
-    if (dtype == 2) return 0;
-    static const bool on = [] { const char* e = ggpm_dev_env("GGPM_GATE_SPLIT"); return !e || atoi(e) != 0; }();
-    if (!on || rt2) return 0;
-    if (dtype != 3 && (!single_group || sparse)) return 0;
-    const size_t need = (size_t)16 * (Hp + 4) * sizeof(float) + 2 * ggpm_split_image_bytes(16, Hp);
-    return need <= 160 * 1024 ? 2 : 0;
-}
-
-// The form of a level call -- what the impl functions, the launchers below and ggpm_level_form_query (include/ggpm_hip.h) all
-// decide through: the call's geometry (LevelPlan) and, per depth step, whether kernel A takes the B launch's product with it
-// and the dynamic LDS of the two launches (StepLds).
-struct LevelPlan { int tg; bool rt2; int gm; };      // tiles per column group, two row tiles per workgroup, gate mode 0 / 1 / 2
-inline LevelPlan level_plan(const ggpm_level_opts& o, int E1, int Hp, bool sparse) {
-    LevelPlan p;
-    p.tg = pick_tg(E1, Hp / 16);
-    p.rt2 = use_rt2(o, E1, Hp, sparse);
-    p.gm = gate_mode(o, Hp, p.rt2, p.tg >= Hp / 16, sparse);
-    return p;
-}
-struct StepLds { int fuse; size_t a, b; };      // b: what the B launch takes when there is one
-// a forward depth step; with_b: the step forms q' (every step but the level's last)
-inline StepLds fwd_step(int Hp, int tg, bool rt2, int gm, bool with_b) {
-    const int rows = rt2 ? 32 : 16;
-    const bool split = gm == 2;
-    const size_t tile_b = (size_t)rows * (Hp + 4) * sizeof(float), img_b = ggpm_split_image_bytes(rows, Hp);
-    const size_t lds_fused = split ? tile_b + 3 * img_b : 3 * tile_b;
-    StepLds p;
-    p.fuse = (!rt2 && with_b && ggpm_ceil_div(Hp / 16, tg) == 1 && lds_fused <= 160 * 1024 && !env_no_fuse_b()) ? 1 : 0;
-    p.a = p.fuse ? lds_fused : split ? tile_b + 2 * img_b : 2 * tile_b;
-    p.b = split ? img_b : tile_b;
-    return p;
-}
-// a backward depth step; with_b: the step forms dS / dG for the one below it; final_pass: the sparse backward's t = 0 launch
-inline StepLds bwd_step(int Hp, int tg, bool rt2, int gm, bool with_b, bool final_pass) {
-    const int rows = rt2 ? 32 : 16, NT = Hp / 16;
-    const bool split = gm == 2;
-    const size_t tile_b = (size_t)rows * (Hp + 4) * sizeof(float), img_b = ggpm_split_image_bytes(rows, Hp);
-    const size_t lds_fused = split ? tile_b + 3 * img_b : 4 * tile_b;
-    StepLds p;
-    p.fuse = (!rt2 && with_b && !final_pass && ggpm_ceil_div(NT, tg) == 1 && NT <= 2 * GGPM_NWA && lds_fused <= 160 * 1024 &&
-              !env_no_fuse_b()) ? 1 : 0;
-    p.a = p.fuse ? lds_fused : split ? tile_b + img_b : 2 * tile_b;
-    p.b = split ? 2 * img_b : 2 * tile_b;                        // kernel B: the dz_pre and dm_pre rows
-    return p;
+// GGPM_ADEBUG (dev variant; the GRU A kernels only): where workgroup (0,0) leaves its phase stamps
+inline unsigned long long* adebug_stamps(unsigned long long*& buf) {
+    if (!env_adebug()) return nullptr;
+    if (!buf) (void)hipMalloc(&buf, 64);
+    return buf;
 }
 
 void launch_fwd(GruFwdArgs a, bool rt2, bool stash, bool with_b, double flops1, hipStream_t s) {
-    const int Hp = a.Hp, NT = Hp / 16;
-    const int rows = rt2 ? 32 : 16;
-    dim3 grid_a(ggpm_ceil_div(a.E1, rows), ggpm_ceil_div(NT, a.tg));
-    const StepLds step = fwd_step(Hp, a.tg, rt2, a.bf16, with_b);
-    const size_t lds_a = step.a, lds_b = step.b;
+    const StepLds step = fwd_step<GruCell>(a.Hp, a.tg, rt2, a.bf16, with_b);
     a.fuse_b = step.fuse;
     static unsigned long long* dbg_buf = nullptr;
     static int dbg_count = 0;
-    a.dbg = nullptr;
-    if (env_adebug()) {
-        if (!dbg_buf) (void)hipMalloc(&dbg_buf, 64);
-        a.dbg = dbg_buf;
-    }
-    if (a.fuse_b) with_b = false;
-    ggpm_timing_begin(0, s, ((a.fuse_b ? 1 : 0) + (a.h0_zero ? 0 : 2)) * flops1);     // the first depth has no gate products
-    auto go = [&](auto kernel) {
-        set_lds(kernel, lds_a);
-        kernel<<<grid_a, GGPM_NWA * 64, lds_a, s>>>(a);
-    };
-    if (a.st16) {      // (training levels, and the forward-only form of such a level: ggpm_level_opts.h_out)
-        if (stash) { if (rt2) go(gru_fwd_a<true, 1, 2, true>); else go(gru_fwd_a<true, 1, 1, true>); }
-        else { if (rt2) go(gru_fwd_a<false, 1, 2, true>); else go(gru_fwd_a<false, 1, 1, true>); }
-    } else if (rt2) {
-        if (a.bf16 == 1) { if (stash) go(gru_fwd_a<true, 1, 2>); else go(gru_fwd_a<false, 1, 2>); }
-        else { if (stash) go(gru_fwd_a<true, 0, 2>); else go(gru_fwd_a<false, 0, 2>); }
-    } else {
-        if (a.bf16 == 2) { if (stash) go(gru_fwd_a<true, 2, 1>); else go(gru_fwd_a<false, 2, 1>); }
-        else if (a.bf16 == 1) { if (stash) go(gru_fwd_a<true, 1, 1>); else go(gru_fwd_a<false, 1, 1>); }
-        else { if (stash) go(gru_fwd_a<true, 0, 1>); else go(gru_fwd_a<false, 0, 1>); }
-    }
-    ggpm_timing_end(0, s);
+    a.dbg = adebug_stamps(dbg_buf);
+    ggpm_timing_begin(GruCell::timing_base, s, (step.fuse + (a.h0_zero ? 0 : GruCell::gate_products)) * flops1);     // the first depth has no gate products
+    for_variant<GruCell>(a.st16, rt2, a.bf16, [&](auto GM, auto RTT, auto ST16) {
+        launch_step(stash ? gru_fwd_a<true, GM, RTT, ST16> : gru_fwd_a<false, GM, RTT, ST16>, a, rt2, step.a, s);
+    });
+    ggpm_timing_end(GruCell::timing_base, s);
     if (a.dbg && (++dbg_count % 97) == 0) {
         unsigned long long h[7];
+        const dim3 grid = step_grid(a, rt2);
         (void)hipStreamSynchronize(s);
         (void)hipMemcpy(h, a.dbg, sizeof(h), hipMemcpyDeviceToHost);
         fprintf(stderr, "[adebug E1=%d grid=%dx%d fuse=%d] gather %.2f barrier %.2f gemm %.2f epilogue %.2f us; wave 15 starts "
-                "+%.2f, gathers %.2f\n", a.E1, grid_a.x, grid_a.y, a.fuse_b, (h[1] - h[0]) * 0.01, (h[2] - h[1]) * 0.01,
+                "+%.2f, gathers %.2f\n", a.E1, grid.x, grid.y, a.fuse_b, (h[1] - h[0]) * 0.01, (h[2] - h[1]) * 0.01,
                 (h[3] - h[2]) * 0.01, (h[4] - h[3]) * 0.01, ((double)h[5] - (double)h[0]) * 0.01, (h[6] - h[5]) * 0.01);
     }
-    if (with_b) {
-        auto gob = [&](auto kernel) {
-            set_lds(kernel, lds_b);
-            kernel<<<grid_a, GGPM_NWA * 64, lds_b, s>>>(a);
-        };
-        ggpm_timing_begin(4, s, 1 * flops1);
-        if (a.st16) { if (rt2) gob(gru_fwd_b<1, 2, true>); else gob(gru_fwd_b<1, 1, true>); }
-        else if (rt2) { if (a.bf16 == 1) gob(gru_fwd_b<1, 2>); else gob(gru_fwd_b<0, 2>); }
-        else { if (a.bf16 == 2) gob(gru_fwd_b<2, 1>); else if (a.bf16 == 1) gob(gru_fwd_b<1, 1>); else gob(gru_fwd_b<0, 1>); }
-        ggpm_timing_end(4, s);
+    if (with_b && !step.fuse) {
+        ggpm_timing_begin(GruCell::timing_base + 4, s, 1 * flops1);
+        for_variant<GruCell>(a.st16, rt2, a.bf16, [&](auto GM, auto RTT, auto ST16) {
+            launch_step(gru_fwd_b<GM, RTT, ST16>, a, rt2, step.b, s);
+        });
+        ggpm_timing_end(GruCell::timing_base + 4, s);
     }
 }
 
 void launch_bwd(GruBwdArgs a, bool rt2, bool with_b, double flops1, hipStream_t s) {
-    const int Hp = a.Hp, NT = Hp / 16;
-    const int rows = rt2 ? 32 : 16;
-    dim3 grid_a(ggpm_ceil_div(a.E1, rows), ggpm_ceil_div(NT, a.tg));
-    const StepLds step = bwd_step(Hp, a.tg, rt2, a.bf16, with_b, a.final_pass != 0);
-    const size_t lds_a = step.a, lds = step.b;
+    const StepLds step = bwd_step<GruCell>(a.Hp, a.tg, rt2, a.bf16, with_b, a.final_pass != 0);
     a.fuse_b = step.fuse;
-    if (a.fuse_b) with_b = false;
     static unsigned long long* dbg_buf = nullptr;
     static int dbg_count = 0;
-    a.dbg = nullptr;
-    if (env_adebug()) {
-        if (!dbg_buf) (void)hipMalloc(&dbg_buf, 64);
-        a.dbg = dbg_buf;
-    }
-    auto go = [&](auto kernel, size_t bytes) {
-        set_lds(kernel, bytes);
-        kernel<<<grid_a, GGPM_NWA * 64, bytes, s>>>(a);
-    };
-    ggpm_timing_begin(1, s, (a.fuse_b ? 3 : 1) * flops1);
-    if (a.st16) { if (rt2) go(gru_bwd_a<1, 2, true>, lds_a); else go(gru_bwd_a<1, 1, true>, lds_a); }
-    else if (rt2) { if (a.bf16 == 1) go(gru_bwd_a<1, 2>, lds_a); else go(gru_bwd_a<0, 2>, lds_a); }
-    else { if (a.bf16 == 2) go(gru_bwd_a<2, 1>, lds_a); else if (a.bf16 == 1) go(gru_bwd_a<1, 1>, lds_a); else go(gru_bwd_a<0, 1>, lds_a); }
-    ggpm_timing_end(1, s);
+    a.dbg = adebug_stamps(dbg_buf);
+    ggpm_timing_begin(GruCell::timing_base + 1, s, (step.fuse ? 1 + GruCell::gate_products : 1) * flops1);
+    for_variant<GruCell>(a.st16, rt2, a.bf16, [&](auto GM, auto RTT, auto ST16) {
+        launch_step(gru_bwd_a<GM, RTT, ST16>, a, rt2, step.a, s);
+    });
+    ggpm_timing_end(GruCell::timing_base + 1, s);
     if (a.dbg && !a.first && (++dbg_count % 89) == 0) {
         unsigned long long h[5];
+        const dim3 grid = step_grid(a, rt2);
         (void)hipStreamSynchronize(s);
         (void)hipMemcpy(h, a.dbg, sizeof(h), hipMemcpyDeviceToHost);
         fprintf(stderr, "[adebug bwd E1=%d grid=%dx%d fuse=%d] gather %.2f barrier %.2f gemm %.2f epilogue %.2f us\n", a.E1,
-                grid_a.x, grid_a.y, a.fuse_b, (h[1] - h[0]) * 0.01, (h[2] - h[1]) * 0.01, (h[3] - h[2]) * 0.01,
+                grid.x, grid.y, a.fuse_b, (h[1] - h[0]) * 0.01, (h[2] - h[1]) * 0.01, (h[3] - h[2]) * 0.01,
                 (h[4] - h[3]) * 0.01);
     }
-    if (with_b) {
-        ggpm_timing_begin(5, s, 2 * flops1);
-        if (a.st16) { if (rt2) go(gru_bwd_b<1, 2, true>, lds); else go(gru_bwd_b<1, 1, true>, lds); }
-        else if (rt2) { if (a.bf16 == 1) go(gru_bwd_b<1, 2>, lds); else go(gru_bwd_b<0, 2>, lds); }
-        else { if (a.bf16 == 2) go(gru_bwd_b<2, 1>, lds); else if (a.bf16 == 1) go(gru_bwd_b<1, 1>, lds); else go(gru_bwd_b<0, 1>, lds); }
-        ggpm_timing_end(5, s);
+    if (with_b && !step.fuse) {
+        ggpm_timing_begin(GruCell::timing_base + 5, s, GruCell::gate_products * flops1);
+        for_variant<GruCell>(a.st16, rt2, a.bf16, [&](auto GM, auto RTT, auto ST16) {
+            launch_step(gru_bwd_b<GM, RTT, ST16>, a, rt2, step.b, s);
+        });
+        ggpm_timing_end(GruCell::timing_base + 5, s);
     }
 }
 
@@ -928,26 +833,9 @@ extern "C" size_t ggpm_gru_pack_floats(int H) {
     return 3 * ggpm_packed_matrix_slot(Hp) + (size_t)Hp;
 }
 
-static int gru_shape_ok(int Hp) {
-    // one LDS tile pair of 16 rows must fit a CU
-    return (size_t)2 * 16 * (Hp + 4) * sizeof(float) <= 160 * 1024;
-}
-
-// ggpm_level_form_query (capi.hip) for a GRU level: the decisions above, nothing launched
+// ggpm_level_form_query (capi.hip) for a GRU level
 int ggpm_gru_level_form(int E1, int H, int sparse, int training, const ggpm_level_opts& o, ggpm_level_form* out) {
-    const int Hp = ggpm_padded_hidden(H);
-    if (!gru_shape_ok(Hp)) return GGPM_ERR_UNSUPPORTED;
-    const LevelPlan plan = level_plan(o, E1, Hp, sparse != 0);
-    const StepLds f = fwd_step(Hp, plan.tg, plan.rt2, plan.gm, true);
-    const StepLds b = bwd_step(Hp, plan.tg, plan.rt2, plan.gm, true, false);
-    *out = ggpm_level_form{};
-    out->Hp = Hp; out->tiles = Hp / 16; out->tg = plan.tg; out->groups = ggpm_ceil_div(Hp / 16, plan.tg);
-    out->rt2 = plan.rt2 ? 1 : 0; out->gate_mode = plan.gm;
-    out->st16 = ggpm_level_st16(plan.gm, sparse != 0, training || o.h_out, E1, H) ? 1 : 0;
-    out->fuse_fwd = f.fuse;
-    out->lds_fwd_a = f.a; out->lds_fwd_b = (f.fuse && !sparse) ? 0 : f.b;      // (a sparse forward forms q^0 by a B launch)
-    if (training) { out->fuse_bwd = b.fuse; out->lds_bwd_a = b.a; out->lds_bwd_b = b.fuse ? 0 : b.b; }
-    return GGPM_OK;
+    return level_form<GruCell>(E1, H, sparse, training, o, out);
 }
 
 namespace {
@@ -972,10 +860,10 @@ static int gru_forward_impl(int E1, int H, int depth, const float* Xz, const flo
         return GGPM_ERR_ARG;
     if (save_for_backward && (!Ss || !Gs || !Zs || !Ms || !Rs)) return GGPM_ERR_ARG;
     const int Hp = ggpm_padded_hidden(H);
-    if (!gru_shape_ok(Hp)) return GGPM_ERR_UNSUPPORTED;
+    if (!GruCell::shape_ok(E1, Hp)) return GGPM_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     const size_t HH = (size_t)Hp * Hp, slot = (size_t)E1 * Hp;
-    const LevelPlan plan = level_plan(o, E1, Hp, frozen != nullptr);
+    const LevelPlan plan = level_plan<GruCell>(o, E1, Hp, frozen != nullptr);
     const bool rt2 = plan.rt2;
     const int bf16 = plan.gm;      // gate mode 0 / 1 / 2
     const size_t mstep = ggpm_packed_matrix_floats(Hp, bf16);
@@ -997,11 +885,10 @@ static int gru_forward_impl(int E1, int H, int depth, const float* Xz, const flo
         GruFwdArgs a0 = {};
         a0.E1 = E1; a0.Hp = Hp; a0.tg = tg0; a0.Hnew = Hs; a0.Qnew = Qs; a0.Ur = pUr; a0.bu = pbu; a0.bf16 = bf16;
         if (gathered) { a0.src_h = o.gather_h; a0.src_idx = o.gather_idx; }
-        const size_t lds_b = fwd_step(Hp, tg0, false, bf16, true).b;
-        dim3 grid_a(ggpm_ceil_div(E1, ROWS), ggpm_ceil_div(Hp / 16, tg0));
-        if (bf16 == 2) { set_lds(gru_fwd_b<2, 1>, lds_b); gru_fwd_b<2, 1><<<grid_a, GGPM_NWA * 64, lds_b, s>>>(a0); }
-        else if (bf16 == 1) { set_lds(gru_fwd_b<1, 1>, lds_b); gru_fwd_b<1, 1><<<grid_a, GGPM_NWA * 64, lds_b, s>>>(a0); }
-        else { set_lds(gru_fwd_b<0, 1>, lds_b); gru_fwd_b<0, 1><<<grid_a, GGPM_NWA * 64, lds_b, s>>>(a0); }
+        const size_t lds_b = fwd_step<GruCell>(Hp, tg0, false, bf16, true).b;
+        for_variant<GruCell>(false, false, bf16, [&](auto GM, auto RTT, auto ST16) {
+            launch_step(gru_fwd_b<GM, RTT, ST16>, a0, false, lds_b, s);
+        });
     }
     // dense levels start from h^0 = 0: the first depth launch knows that (h0_zero), so H^0 / Q^0 are never materialised
 
@@ -1080,17 +967,7 @@ extern "C" int ggpm_gru_sparse_forward(int E1, int H, int depth, const float* h_
 }
 
 extern "C" size_t ggpm_gru_backward_workspace_bytes(int E1, int H, int depth) {
-    const size_t Hp = (size_t)ggpm_padded_hidden(H);
-    const size_t slot = (size_t)E1 * Hp;
-    size_t f = 0;
-    f += 2 * (size_t)depth * slot;                     // DMP, DZP
-    f += (size_t)depth * slot;                         // DQ (slot t = dq^t; slot 0 only used by sparse_forward)
-    f += 6 * slot;                                     // dS/dG double buffers + ds_dir scratch + carry
-    f += 3 * ggpm_packed_matrix_slot((int)Hp);         // packed transposes (the largest gate mode's)
-    f += 256 * Hp;                                     // colsum scratch
-    size_t bytes = f * sizeof(float);
-    bytes += ggpm_gemm_workspace_bytes(H, H, depth * E1);   // split-K slabs (largest contraction)
-    return bytes + 256;
+    return backward_workspace_bytes<GruCell>(E1, H, depth);      // (level_host.h: carve)
 }
 
 static int gru_weight_grads_impl(int E1, int H, int depth, const float* Hs, const float* Ss, const float* Gs,
@@ -1125,28 +1002,20 @@ static int gru_backward_impl(int E1, int H, int depth, const float* Xr, const fl
         return GGPM_ERR_ARG;
     if (work_bytes < ggpm_gru_backward_workspace_bytes(E1, H, depth)) return GGPM_ERR_WORKSPACE;
     const int Hp = ggpm_padded_hidden(H);
-    if (!gru_shape_ok(Hp)) return GGPM_ERR_UNSUPPORTED;
+    if (!GruCell::shape_ok(E1, Hp)) return GGPM_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     const size_t HH = (size_t)Hp * Hp, slot = (size_t)E1 * Hp;
 
-    // (the packed transposes come first: their place does not depend on E1, so a sequence of calls that shares one
-    // `work` buffer and one set of weights packs them once -- ggpm_level_opts.weights_packed)
-    float* w = work;
-    const LevelPlan plan = level_plan(o, E1, Hp, frozen != nullptr);
+    const LevelPlan plan = level_plan<GruCell>(o, E1, Hp, frozen != nullptr);
     const bool rt2 = plan.rt2;
     const int bf16 = plan.gm;      // gate mode 0 / 1 / 2
     const size_t mstep = ggpm_packed_matrix_floats(Hp, bf16);
-    float* pWzT = w; float* pWhT = w + mstep; float* pUrT = w + 2 * mstep; w += 3 * ggpm_packed_matrix_slot(Hp);
-    float* DMP = w; w += (size_t)depth * slot;
-    float* DZP = w; w += (size_t)depth * slot;
-    float* DQ = w; w += (size_t)depth * slot;
-    float* dSb[2]; float* dGb[2];
-    dSb[0] = w; w += slot; dSb[1] = w; w += slot; dGb[0] = w; w += slot; dGb[1] = w; w += slot;
-    float* DSD = w; w += slot;
-    float* carry = w; w += slot;
-    float* csws = w; w += (size_t)256 * Hp;
-    float* skws = w;
-    const size_t skbytes = work_bytes - (size_t)((char*)skws - (char*)work);
+    const LevelWork<GruCell> wk = carve<GruCell>(work, E1, Hp, depth);
+    float* pWzT = wk.packedT; float* pWhT = pWzT + mstep; float* pUrT = pWzT + 2 * mstep;
+    float* DMP = wk.stash[0]; float* DZP = wk.stash[1]; float* DQ = wk.DQ;
+    float* const dSb[2] = {wk.scratch[0], wk.scratch[1]}; float* const dGb[2] = {wk.scratch[2], wk.scratch[3]};
+    float* DSD = wk.scratch[4];      // ds_dir scratch
+    float* carry = wk.scratch[5];
     if (o.defer_stash[0]) {       // deferred weight gradients: the stashes go to the caller's stacked buffers
         if (!frozen || !o.defer_stash[1] || !o.defer_stash[2]) return GGPM_ERR_ARG;
         DMP = o.defer_stash[0]; DZP = o.defer_stash[1]; DQ = o.defer_stash[2];
@@ -1254,85 +1123,13 @@ static int gru_weight_grads_impl(int E1, int H, int depth, const float* Hs, cons
     GGPM_CLEAR_STALE_ERROR();
     if (E1 <= 0 || H <= 0 || depth <= 0 || !Hs || !Ss || !Gs || !work || !dWz_h || !dUr || !dbu || !dWh_h)
         return GGPM_ERR_ARG;
-    const bool skip_bu = o.skip_bias_u;                   // (ggpm_gru_bias_u_grad forms db_u elsewhere)
     if (lo < 1 || lo > depth || with_slot0) lo = 1;       // backward steps depth .. lo ran (stash slots lo-1 .. depth-1)
     if (work_bytes < ggpm_gru_backward_workspace_bytes(E1, H, depth)) return GGPM_ERR_WORKSPACE;
-    const int Hp = ggpm_padded_hidden(H);
-    hipStream_t s = (hipStream_t)stream;
-    const size_t HH = (size_t)Hp * Hp, slot = (size_t)E1 * Hp;
-    float* w = work + 3 * ggpm_packed_matrix_slot(Hp);             // (layout of gru_backward_impl)
-    float* DMP = w; w += (size_t)depth * slot;
-    float* DZP = w; w += (size_t)depth * slot;
-    float* DQ = w; w += (size_t)depth * slot;
-    w += 6 * slot;
-    float* csws = w; w += (size_t)256 * Hp;
-    float* skws = w;
-    const size_t skbytes = work_bytes - (size_t)((char*)skws - (char*)work);
-    const int KD = (depth - lo + 1) * E1;
-    // bf16 storage (as gru_forward_impl / gru_backward_impl decided): the stashes are bf16 in the first half of their buffers
-    // and the bf16 tall kernel reads them as they are
-    const bool st16 = o.gate_dtype == 1 && !with_slot0 && ggpm_bf16_storage_applies(E1, H);
-    const int tall_mode = st16 ? 2 : (o.gate_dtype == 1 ? 1 : 0);
-    int rc;
-    if (o.fixed_slot > 0 && !with_slot0) {
-        // fixed-point level (ggpm_level_opts.fixed_slot): every G / S / h block a step >= lo pairs with is the settled slot,
-        // so dWh_h = (sum_t DMP_t)^T G*, dWz_h = (sum_t DZP_t)^T S*, dUr = (sum_t DQ_t)^T h*, db_u = colsum(sum_t DQ_t).  The
-        // slot sums do not round on their own: hi + lo pairs in slots 0 / 1 of each stash (free: lo - 1 >= 2), K = 2 E1.
-        const int fs = o.fixed_slot;
-        if (fs >= depth || lo < fs || lo < 3 || o.gate_dtype == 1) return GGPM_ERR_ARG;
-        const int nq = depth - lo;                         // dq^t exists for t = lo .. depth - 1
-        const float* src[3] = {DMP + (size_t)(lo - 1) * slot, DZP + (size_t)(lo - 1) * slot, DQ + (size_t)lo * slot};
-        const int slots[3] = {depth - lo + 1, depth - lo + 1, nq};
-        float* const hi[3] = {DMP, DZP, DQ};
-        float* const lw[3] = {DMP + slot, DZP + slot, DQ + slot};
-        rc = ggpm_sum_slots_pair_grouped(nq > 0 ? 3 : 2, src, slots, slot, hi, lw, stream);
-        if (rc) return rc;
-        const ggpm_pair_problem pp[3] = {{DMP, DMP + slot, Gs + (size_t)(fs - 1) * slot, dWh_h, ld_dwh},
-                                         {DZP, DZP + slot, Ss + (size_t)(fs - 1) * slot, dWz_h, ld_dwz},
-                                         {DQ, DQ + slot, Hs + (size_t)fs * slot, dUr, ld_dur}};
-        if (nq > 0) {
-            if (!skip_bu) {      // hi and lo are adjacent slots: one column sum over both
-                rc = ggpm_colsum(DQ, Hp, 2 * E1, H, dbu, csws, stream);
-                if (rc) return rc;
-            }
-        } else {
-            for (int r = 0; r < H; ++r) (void)hipMemsetAsync(dUr + (size_t)r * ld_dur, 0, H * sizeof(float), s);
-            if (!skip_bu) (void)hipMemsetAsync(dbu, 0, H * sizeof(float), s);
-        }
-        rc = ggpm_gemm_tn_pair_grouped(H, H, E1, Hp, nq > 0 ? 3 : 2, pp, stream);
-        if (rc) return rc;
-        GGPM_CHECK_LAUNCH();
-        return GGPM_OK;
-    }
-    // the two or three contractions in ONE launch and one reduce (they share the split-K workspace)
-    ggpm_gemm_problem gp[3] = {{ggpm_slot_ptr(DMP, lo - 1, slot, st16), Hp, ggpm_slot_ptr(Gs, lo - 1, slot, st16), Hp, dWh_h, ld_dwh, H,
-                                nullptr, 0, GGPM_ACT_NONE, 0},
-                               {ggpm_slot_ptr(DZP, lo - 1, slot, st16), Hp, ggpm_slot_ptr(Ss, lo - 1, slot, st16), Hp, dWz_h, ld_dwz, H,
-                                nullptr, 0, GGPM_ACT_NONE, 0},
-                               {nullptr, Hp, nullptr, Hp, dUr, ld_dur, H, nullptr, 0, GGPM_ACT_NONE, 0}};
-    int Ks[3] = {KD, KD, 0};
-    if (depth > lo || with_slot0) {
-        // dq^t pairs with h^t; the dense level never produces dq^0 (h^0 = 0), sparse_forward does
-        const int first_slot = with_slot0 ? 0 : lo;
-        const int KQ = (depth - first_slot) * E1;
-        const float* dq0 = ggpm_slot_ptr(DQ, first_slot, slot, st16);
-        gp[2].A = dq0;
-        gp[2].B = ggpm_slot_ptr(Hs, first_slot, slot, st16);
-        Ks[2] = KQ;
-        if (!skip_bu) {      // (the light column sum first, the contraction last)
-            rc = ggpm_colsum_any(dq0, Hp, KQ, H, dbu, csws, st16, stream);
-            if (rc) return rc;
-        }
-        rc = ggpm_gemm_tall_grouped(H, H, 3, gp, Ks, skws, skbytes, stream, tall_mode);
-        if (rc) return rc;
-    } else {
-        rc = ggpm_gemm_tall_grouped(H, H, 2, gp, Ks, skws, skbytes, stream, tall_mode);
-        if (rc) return rc;
-        for (int r = 0; r < H; ++r) (void)hipMemsetAsync(dUr + (size_t)r * ld_dur, 0, H * sizeof(float), s);
-        if (!skip_bu) (void)hipMemsetAsync(dbu, 0, H * sizeof(float), s);
-    }
-    GGPM_CHECK_LAUNCH();
-    return GGPM_OK;
+    const LevelWork<GruCell> wk = carve<GruCell>(work, E1, ggpm_padded_hidden(H), depth);
+    // dWh_h = DMP^T G, dWz_h = DZP^T S, dUr = DQ^T h, db_u = colsum(DQ) (skip_bias_u: ggpm_gru_bias_u_grad forms it elsewhere)
+    const WgradTerm gate[2] = {{wk.stash[0], Gs, dWh_h, ld_dwh}, {wk.stash[1], Ss, dWz_h, ld_dwz}};
+    return level_weight_grads(E1, H, depth, lo, with_slot0, o, 2, gate, {wk.DQ, Hs, dUr, ld_dur}, o.skip_bias_u ? nullptr : dbu,
+                              wk.csws, wk.skws, wk.skbytes(work_bytes), stream);
 }
 
 // db_u of a dense level by itself (what gru_weight_grads_impl does last unless ggpm_level_opts.skip_bias_u is set): the
@@ -1344,7 +1141,7 @@ int ggpm_gru_bias_u_grad(int E1, int H, int depth, int lo, float* work, float* d
     if (lo < 1 || lo > depth) lo = 1;
     const int Hp = ggpm_padded_hidden(H);
     const size_t slot = (size_t)E1 * Hp;
-    const float* DQ = work + 3 * ggpm_packed_matrix_slot(Hp) + 2 * (size_t)depth * slot;      // (layout of gru_backward_impl)
+    const float* DQ = carve<GruCell>(work, E1, Hp, depth).DQ;
     if (depth <= lo) {
         (void)hipMemsetAsync(dbu, 0, H * sizeof(float), (hipStream_t)stream);
         return GGPM_OK;
@@ -1425,9 +1222,9 @@ int ggpm_sum_slots_any(const float* src, int slots, size_t slot_floats, float* o
 // where ggpm_gru_backward left its dm_pre / dz_pre stashes inside `work` (slot t-1 of each = backward step t)
 extern "C" int ggpm_gru_backward_stashes(float* work, int E1, int H, int depth, float** DMP, float** DZP) {
     if (!work || !DMP || !DZP || E1 <= 0 || H <= 0 || depth <= 0) return GGPM_ERR_ARG;
-    const size_t Hp = (size_t)ggpm_padded_hidden(H), slot = (size_t)E1 * Hp;
-    *DMP = work + 3 * ggpm_packed_matrix_slot((int)Hp);
-    *DZP = *DMP + (size_t)depth * slot;
+    const LevelWork<GruCell> wk = carve<GruCell>(work, E1, ggpm_padded_hidden(H), depth);
+    *DMP = wk.stash[0];
+    *DZP = wk.stash[1];
     return GGPM_OK;
 }
 
@@ -1451,17 +1248,9 @@ extern "C" int ggpm_gru_weight_grads_stacked(int rows, int rows_q, int H, const 
     float* csws = work;
     float* skws = work + (size_t)256 * Hp;
     const size_t skbytes = work_bytes - (size_t)256 * Hp * sizeof(float);
-    const ggpm_gemm_problem gp[3] = {{DMP, Hp, Gs, Hp, dWh_h, ld_dwh, H, nullptr, 0, GGPM_ACT_NONE, 0},
-                                     {DZP, Hp, Ss, Hp, dWz_h, ld_dwz, H, nullptr, 0, GGPM_ACT_NONE, 0},
-                                     {DQ, Hp, Hs, Hp, dUr, ld_dur, H, nullptr, 0, GGPM_ACT_NONE, 0}};
-    const int Ks[3] = {rows, rows, rows_q};
+    const WgradTerm gate[2] = {{DMP, Gs, dWh_h, ld_dwh}, {DZP, Ss, dWz_h, ld_dwz}};
     // (the light column sum first: whatever else shares the GPU at the end of a pass, the stream ends with the contraction)
-    int rc = ggpm_colsum(DQ, Hp, rows_q, H, dbu, csws, stream);
-    if (rc) return rc;
-    rc = ggpm_gemm_tall_grouped(H, H, 3, gp, Ks, skws, skbytes, stream);
-    if (rc) return rc;
-    GGPM_CHECK_LAUNCH();
-    return GGPM_OK;
+    return tall_weight_grads(H, Hp, 2, gate, rows, {DQ, Hs, dUr, ld_dur}, rows_q, dbu, csws, false, 0, skws, skbytes, stream);
 }
 
 int ggpm_gru_sparse_weight_grads(int E1, int H, int depth, const float* Hs, const float* Ss, const float* Gs, float* work,

@@ -10,6 +10,7 @@
 //   bwd  A: P1 successors -> dh partial, dqf, dc tiles | P2 dh += dqf.Wf_h ; gate derivatives, dXf += dFC * F
 //           P3 (one column group) dS = di_pre.Wi_h + do_pre.Wo_h + du_pre.Wu_h      B: otherwise, from L2
 #include "tile_mma.h"
+#include "level_host.h"
 #include <cstdlib>
 
 namespace {
@@ -649,136 +650,60 @@ __global__ void GGPM_A_BOUNDS lstm_bwd_b(LstmBwdArgs a) {
     }
 }
 
-template <typename K>
-inline void set_lds(K kernel, size_t bytes) { ggpm_set_lds(kernel, bytes); }      // (common.h)
-
-inline size_t lds_tiles(int n, int Hp, int rows = ROWS) { return (size_t)n * rows * (Hp + 4) * sizeof(float); }
-// ggpm_level_opts.prefer_narrow: two row tiles per workgroup for a dense fp32 level call
-inline bool use_rt2(const ggpm_level_opts& o, int Hp, bool sparse) {
-    return o.prefer_narrow && !sparse && o.gate_dtype != 1 && lds_tiles(3, Hp, 32) <= 160 * 1024;
-}
-
-// Environment switches are read once: getenv walks the whole environment (~0.5 us) and the launch helpers below run
-// ~120 times per training step.
-inline bool env_no_fuse_b() { static const bool v = ggpm_dev_env("GGPM_NO_FUSE_B") != nullptr; return v; }
-inline bool env_adebug() { static const bool v = ggpm_dev_env("GGPM_ADEBUG") != nullptr; return v; }
-
-inline int pick_tg(int E1, int NT) {
-    static const char* const tg_env = ggpm_dev_env("GGPM_TG");
-    if (const char* e = tg_env) { int v = atoi(e); if (v >= 1 && v <= 64) return v; }   // tuning override
-    static const char* const tg_large_env = ggpm_dev_env("GGPM_TG_LARGE");
-    if (const char* e = tg_large_env) {      // tuning override for the large (atom) levels only
-        int v = atoi(e);
-        if (v >= 1 && v <= 64 && (E1 + 15) / 16 > 64) return v < NT ? v : NT;
+// What level_host.h needs to know about the LSTM (each line is a difference from the GRU; DESIGN.md 5.1 has the table).
+struct LstmCell {
+    static constexpr StepNeed fwd = {{3, 1, 2}, {2, 1, 1}, {1, 0, 1}};      // fused: s, fc, h' | A: s, fc | B: the h' rows
+    static constexpr StepNeed bwd = {{6, 2, 4}, {3, 2, 1}, {3, 0, 3}};      // kernel B: the three gate-gradient row sets
+    static constexpr int bwd_fuse_max_tiles = 0;                            // no limit beyond the LDS
+    static constexpr bool rt2_bf16 = false;                                 // bf16 mode has no two-row-tile form
+    static constexpr int gate_products = 3;                                 // forward [Wi; Wo; Wu].s; backward B the three dS terms
+    static constexpr int timing_base = 2;                                   // ggpm_timing_begin slots 2 / 3 / 6 / 7
+    static constexpr int n_mat = 4, n_stash = 3;                            // Wi, Wo, Wu, Wf; DI, DO, DU
+    static constexpr int csws_rows = 0;                                     // no bias gradient here
+    // ggpm_level_opts.prefer_narrow: two row tiles per workgroup for a dense fp32 level call
+    static bool use_rt2(const ggpm_level_opts& o, int, int Hp, bool sparse) {
+        return o.prefer_narrow && !sparse && o.gate_dtype != 1 && lds_tiles(3, Hp, 32) <= GGPM_LDS_LIMIT;
     }
-    return ggpm_tiles_per_group(E1, NT);
-}
-
-// Gate mode of a level call (mpn_gru.hip: gate_mode): fp32 calls run their gate products on split operands (mode 2) where
-// one 16-row tile per workgroup applies and the backward's two fp32 tiles + the dqf image fit the LDS.
-inline int gate_mode(const ggpm_level_opts& o, int Hp, bool rt2, bool single_group, bool sparse) {
-    const int dtype = o.gate_dtype;
-    if (dtype == 1) return 1;
-    if (dtype == 2) return 0;
-    static const bool on = [] { const char* e = ggpm_dev_env("GGPM_GATE_SPLIT"); return !e || atoi(e) != 0; }();
-    if (!on || rt2) return 0;
-    if (dtype != 3 && (!single_group || sparse)) return 0;
-    // kernel A of the backward: two fp32 tiles + the dqf image; kernel B of the backward: three gate-gradient images
-    const size_t img = ggpm_split_image_bytes(16, Hp);
-    return (lds_tiles(2, Hp) + img <= 160 * 1024 && 3 * img <= 160 * 1024) ? 2 : 0;
-}
-
-// The form of a level call (mpn_gru.hip has the same three for the GRU): what the impl functions, the launchers below and
-// ggpm_level_form_query (include/ggpm_hip.h) all decide through.
-struct LevelPlan { int tg; bool rt2; int gm; };      // tiles per column group, two row tiles per workgroup, gate mode 0 / 1 / 2
-inline LevelPlan level_plan(const ggpm_level_opts& o, int E1, int Hp, bool sparse) {
-    LevelPlan p;
-    p.tg = pick_tg(E1, Hp / 16);
-    p.rt2 = use_rt2(o, Hp, sparse);
-    p.gm = gate_mode(o, Hp, p.rt2, p.tg >= Hp / 16, sparse);
-    return p;
-}
-struct StepLds { int fuse; size_t a, b; };      // b: what the B launch takes when there is one
-// a forward depth step; with_b: the step forms qf' (every step but the level's last)
-inline StepLds fwd_step(int Hp, int tg, bool rt2, int gm, bool with_b) {
-    const int rows = rt2 ? 32 : 16;
-    const bool split = gm == 2;
-    const size_t img_b = ggpm_split_image_bytes(rows, Hp);
-    const size_t l_fused = split ? lds_tiles(1, Hp) + 2 * img_b : lds_tiles(3, Hp);
-    StepLds p;
-    p.fuse = (!rt2 && with_b && ggpm_ceil_div(Hp / 16, tg) == 1 && l_fused <= 160 * 1024 && !env_no_fuse_b()) ? 1 : 0;
-    p.a = p.fuse ? l_fused : split ? lds_tiles(1, Hp) + img_b : lds_tiles(2, Hp, rows);
-    p.b = split ? img_b : lds_tiles(1, Hp, rows);
-    return p;
-}
-// a backward depth step; with_b: the step forms dS for the one below it; final_pass: the sparse backward's t = 0 launch
-inline StepLds bwd_step(int Hp, int tg, bool rt2, int gm, bool with_b, bool final_pass) {
-    const int rows = rt2 ? 32 : 16;
-    const bool split = gm == 2;
-    const size_t img_b = ggpm_split_image_bytes(rows, Hp);
-    const size_t l_fused = split ? lds_tiles(2, Hp) + 4 * img_b : lds_tiles(6, Hp);
-    StepLds p;
-    p.fuse = (!rt2 && with_b && !final_pass && ggpm_ceil_div(Hp / 16, tg) == 1 && l_fused <= 160 * 1024 && !env_no_fuse_b()) ? 1 : 0;
-    p.a = p.fuse ? l_fused : split ? lds_tiles(2, Hp) + img_b : lds_tiles(3, Hp, rows);
-    p.b = split ? 3 * img_b : lds_tiles(3, Hp, rows);                  // kernel B: the three gate-gradient row sets
-    return p;
-}
+    // mode 2: kernel A of the backward (two fp32 tiles + the dqf image) and kernel B of the backward (three gate-gradient images)
+    static bool mode2_fits(int Hp) {
+        const size_t img = ggpm_split_image_bytes(16, Hp);
+        return lds_tiles(2, Hp) + img <= GGPM_LDS_LIMIT && 3 * img <= GGPM_LDS_LIMIT;
+    }
+    // three LDS tiles of 16 rows must fit a CU; 32-bit byte offsets inside a slot
+    static bool shape_ok(int E1, int Hp) { return lds_tiles(3, Hp) <= GGPM_LDS_LIMIT && (size_t)E1 * Hp < ((size_t)1 << 30); }
+};
 
 void launch_fwd(LstmFwdArgs a, bool rt2, bool stash, bool with_b, double flops1, hipStream_t s) {
-    const int Hp = a.Hp, NT = Hp / 16;
-    const int rows = rt2 ? 32 : 16;
-    dim3 grid_a(ggpm_ceil_div(a.E1, rows), ggpm_ceil_div(NT, a.tg));
-    const StepLds step = fwd_step(Hp, a.tg, rt2, a.bf16, with_b);
-    const size_t la = step.a, lb = step.b;
+    const StepLds step = fwd_step<LstmCell>(a.Hp, a.tg, rt2, a.bf16, with_b);
     a.fuse_b = step.fuse;
-    if (a.fuse_b) with_b = false;
-    ggpm_timing_begin(2, s, ((a.fuse_b ? 1 : 0) + (a.h0_zero ? 0 : 3)) * flops1);     // the first depth has no gate products
-    auto go = [&](auto kernel) {
-        set_lds(kernel, la);
-        kernel<<<grid_a, GGPM_NWA * 64, la, s>>>(a);
-    };
-    if (a.st16) {      // (training levels and their forward-only form, ggpm_level_opts.h_out; bf16 mode has no two-row-tile form)
-        if (stash) go(lstm_fwd_a<true, 1, 1, true>); else go(lstm_fwd_a<false, 1, 1, true>);
-    }
-    else if (rt2) { if (stash) go(lstm_fwd_a<true, 0, 2>); else go(lstm_fwd_a<false, 0, 2>); }
-    else if (a.bf16 == 2) { if (stash) go(lstm_fwd_a<true, 2, 1>); else go(lstm_fwd_a<false, 2, 1>); }
-    else if (a.bf16 == 1) { if (stash) go(lstm_fwd_a<true, 1, 1>); else go(lstm_fwd_a<false, 1, 1>); }
-    else { if (stash) go(lstm_fwd_a<true, 0, 1>); else go(lstm_fwd_a<false, 0, 1>); }
-    ggpm_timing_end(2, s);
-    if (with_b) {
-        ggpm_timing_begin(6, s, 1 * flops1);
-        if (a.st16) { set_lds(lstm_fwd_b<1, 1, true>, lb); lstm_fwd_b<1, 1, true><<<grid_a, GGPM_NWA * 64, lb, s>>>(a); }
-        else if (rt2) { set_lds(lstm_fwd_b<0, 2>, lb); lstm_fwd_b<0, 2><<<grid_a, GGPM_NWA * 64, lb, s>>>(a); }
-        else if (a.bf16 == 2) { set_lds(lstm_fwd_b<2, 1>, lb); lstm_fwd_b<2, 1><<<grid_a, GGPM_NWA * 64, lb, s>>>(a); }
-        else if (a.bf16 == 1) { set_lds(lstm_fwd_b<1, 1>, lb); lstm_fwd_b<1, 1><<<grid_a, GGPM_NWA * 64, lb, s>>>(a); }
-        else { set_lds(lstm_fwd_b<0, 1>, lb); lstm_fwd_b<0, 1><<<grid_a, GGPM_NWA * 64, lb, s>>>(a); }
-        ggpm_timing_end(6, s);
+    ggpm_timing_begin(LstmCell::timing_base, s, (step.fuse + (a.h0_zero ? 0 : LstmCell::gate_products)) * flops1);     // the first depth has no gate products
+    for_variant<LstmCell>(a.st16, rt2, a.bf16, [&](auto GM, auto RTT, auto ST16) {
+        launch_step(stash ? lstm_fwd_a<true, GM, RTT, ST16> : lstm_fwd_a<false, GM, RTT, ST16>, a, rt2, step.a, s);
+    });
+    ggpm_timing_end(LstmCell::timing_base, s);
+    if (with_b && !step.fuse) {
+        ggpm_timing_begin(LstmCell::timing_base + 4, s, 1 * flops1);
+        for_variant<LstmCell>(a.st16, rt2, a.bf16, [&](auto GM, auto RTT, auto ST16) {
+            launch_step(lstm_fwd_b<GM, RTT, ST16>, a, rt2, step.b, s);
+        });
+        ggpm_timing_end(LstmCell::timing_base + 4, s);
     }
 }
 
 void launch_bwd(LstmBwdArgs a, bool rt2, bool with_b, double flops1, hipStream_t s) {
-    const int Hp = a.Hp, NT = Hp / 16;
-    const int rows = rt2 ? 32 : 16;
-    dim3 grid_a(ggpm_ceil_div(a.E1, rows), ggpm_ceil_div(NT, a.tg));
-    const StepLds step = bwd_step(Hp, a.tg, rt2, a.bf16, with_b, a.final_pass != 0);
-    const size_t la = step.a, l3 = step.b;
+    const StepLds step = bwd_step<LstmCell>(a.Hp, a.tg, rt2, a.bf16, with_b, a.final_pass != 0);
     a.fuse_b = step.fuse;
-    if (a.fuse_b) with_b = false;
-    ggpm_timing_begin(3, s, (a.fuse_b ? 4 : 1) * flops1);
-    if (a.st16) { set_lds(lstm_bwd_a<1, 1, true>, la); lstm_bwd_a<1, 1, true><<<grid_a, GGPM_NWA * 64, la, s>>>(a); }
-    else if (rt2) { set_lds(lstm_bwd_a<0, 2>, la); lstm_bwd_a<0, 2><<<grid_a, GGPM_NWA * 64, la, s>>>(a); }
-    else if (a.bf16 == 2) { set_lds(lstm_bwd_a<2, 1>, la); lstm_bwd_a<2, 1><<<grid_a, GGPM_NWA * 64, la, s>>>(a); }
-    else if (a.bf16 == 1) { set_lds(lstm_bwd_a<1, 1>, la); lstm_bwd_a<1, 1><<<grid_a, GGPM_NWA * 64, la, s>>>(a); }
-    else { set_lds(lstm_bwd_a<0, 1>, la); lstm_bwd_a<0, 1><<<grid_a, GGPM_NWA * 64, la, s>>>(a); }
-    ggpm_timing_end(3, s);
-    if (with_b) {
-        ggpm_timing_begin(7, s, 3 * flops1);
-        if (a.st16) { set_lds(lstm_bwd_b<1, 1, true>, l3); lstm_bwd_b<1, 1, true><<<grid_a, GGPM_NWA * 64, l3, s>>>(a); }
-        else if (rt2) { set_lds(lstm_bwd_b<0, 2>, l3); lstm_bwd_b<0, 2><<<grid_a, GGPM_NWA * 64, l3, s>>>(a); }
-        else if (a.bf16 == 2) { set_lds(lstm_bwd_b<2, 1>, l3); lstm_bwd_b<2, 1><<<grid_a, GGPM_NWA * 64, l3, s>>>(a); }
-        else if (a.bf16 == 1) { set_lds(lstm_bwd_b<1, 1>, l3); lstm_bwd_b<1, 1><<<grid_a, GGPM_NWA * 64, l3, s>>>(a); }
-        else { set_lds(lstm_bwd_b<0, 1>, l3); lstm_bwd_b<0, 1><<<grid_a, GGPM_NWA * 64, l3, s>>>(a); }
-        ggpm_timing_end(7, s);
+    ggpm_timing_begin(LstmCell::timing_base + 1, s, (step.fuse ? 1 + LstmCell::gate_products : 1) * flops1);
+    for_variant<LstmCell>(a.st16, rt2, a.bf16, [&](auto GM, auto RTT, auto ST16) {
+        launch_step(lstm_bwd_a<GM, RTT, ST16>, a, rt2, step.a, s);
+    });
+    ggpm_timing_end(LstmCell::timing_base + 1, s);
+    if (with_b && !step.fuse) {
+        ggpm_timing_begin(LstmCell::timing_base + 5, s, LstmCell::gate_products * flops1);
+        for_variant<LstmCell>(a.st16, rt2, a.bf16, [&](auto GM, auto RTT, auto ST16) {
+            launch_step(lstm_bwd_b<GM, RTT, ST16>, a, rt2, step.b, s);
+        });
+        ggpm_timing_end(LstmCell::timing_base + 5, s);
     }
 }
 
@@ -788,24 +713,9 @@ extern "C" size_t ggpm_lstm_pack_floats(int H) {
     return 4 * ggpm_packed_matrix_slot(ggpm_padded_hidden(H));
 }
 
-// three LDS tiles of 16 rows must fit a CU; 32-bit byte offsets inside a slot
-static int lstm_shape_ok(int E1, int Hp) { return lds_tiles(3, Hp) <= 160 * 1024 && (size_t)E1 * Hp < ((size_t)1 << 30); }
-
-// ggpm_level_form_query (capi.hip) for an LSTM level: the decisions above, nothing launched
+// ggpm_level_form_query (capi.hip) for an LSTM level
 int ggpm_lstm_level_form(int E1, int H, int sparse, int training, const ggpm_level_opts& o, ggpm_level_form* out) {
-    const int Hp = ggpm_padded_hidden(H);
-    if (!lstm_shape_ok(E1, Hp)) return GGPM_ERR_UNSUPPORTED;
-    const LevelPlan plan = level_plan(o, E1, Hp, sparse != 0);
-    const StepLds f = fwd_step(Hp, plan.tg, plan.rt2, plan.gm, true);
-    const StepLds b = bwd_step(Hp, plan.tg, plan.rt2, plan.gm, true, false);
-    *out = ggpm_level_form{};
-    out->Hp = Hp; out->tiles = Hp / 16; out->tg = plan.tg; out->groups = ggpm_ceil_div(Hp / 16, plan.tg);
-    out->rt2 = plan.rt2 ? 1 : 0; out->gate_mode = plan.gm;
-    out->st16 = ggpm_level_st16(plan.gm, sparse != 0, training || o.h_out, E1, H) ? 1 : 0;
-    out->fuse_fwd = f.fuse;
-    out->lds_fwd_a = f.a; out->lds_fwd_b = (f.fuse && !sparse) ? 0 : f.b;      // (a sparse forward forms qf^0 by a B launch)
-    if (training) { out->fuse_bwd = b.fuse; out->lds_bwd_a = b.a; out->lds_bwd_b = b.fuse ? 0 : b.b; }
-    return GGPM_OK;
+    return level_form<LstmCell>(E1, H, sparse, training, o, out);
 }
 
 namespace {
@@ -834,10 +744,10 @@ static int lstm_forward_impl(int E1, int H, int depth, const float* Xi, const fl
         return GGPM_ERR_ARG;
     if (save_for_backward && (!Ss || !Is || !Os || !Us || !Fs)) return GGPM_ERR_ARG;
     const int Hp = ggpm_padded_hidden(H);
-    if (!lstm_shape_ok(E1, Hp)) return GGPM_ERR_UNSUPPORTED;
+    if (!LstmCell::shape_ok(E1, Hp)) return GGPM_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     const size_t HH = (size_t)Hp * Hp, slot = (size_t)E1 * Hp;
-    const LevelPlan plan = level_plan(o, E1, Hp, frozen != nullptr);
+    const LevelPlan plan = level_plan<LstmCell>(o, E1, Hp, frozen != nullptr);
     const bool rt2 = plan.rt2;
     const int bf16 = plan.gm;      // gate mode 0 / 1 / 2
     const size_t mstep = ggpm_packed_matrix_floats(Hp, bf16);
@@ -859,11 +769,10 @@ static int lstm_forward_impl(int E1, int H, int depth, const float* Xi, const fl
         LstmFwdArgs a0 = {};
         a0.E1 = E1; a0.Hp = Hp; a0.tg = tg; a0.Hnew = Hs; a0.Qnew = Qs; a0.Wf = pWf; a0.bf16 = bf16;
         if (gathered) { a0.src_h = o.gather_h; a0.src_c = o.gather_c; a0.src_idx = o.gather_idx; a0.Cnew = Cs; }
-        const size_t lb = fwd_step(Hp, tg, false, bf16, true).b;
-        dim3 grid_a(ggpm_ceil_div(E1, ROWS), ggpm_ceil_div(Hp / 16, tg));
-        if (bf16 == 2) { set_lds(lstm_fwd_b<2, 1>, lb); lstm_fwd_b<2, 1><<<grid_a, GGPM_NWA * 64, lb, s>>>(a0); }
-        else if (bf16 == 1) { set_lds(lstm_fwd_b<1, 1>, lb); lstm_fwd_b<1, 1><<<grid_a, GGPM_NWA * 64, lb, s>>>(a0); }
-        else { set_lds(lstm_fwd_b<0, 1>, lb); lstm_fwd_b<0, 1><<<grid_a, GGPM_NWA * 64, lb, s>>>(a0); }
+        const size_t lb = fwd_step<LstmCell>(Hp, tg, false, bf16, true).b;
+        for_variant<LstmCell>(false, false, bf16, [&](auto GM, auto RTT, auto ST16) {
+            launch_step(lstm_fwd_b<GM, RTT, ST16>, a0, false, lb, s);
+        });
     } else {
         (void)hipMemsetAsync(Hs, 0, slot * sizeof(float), s);
         (void)hipMemsetAsync(Cs, 0, slot * sizeof(float), s);
@@ -946,16 +855,7 @@ extern "C" int ggpm_lstm_sparse_forward(int E1, int H, int depth, const float* h
 }
 
 extern "C" size_t ggpm_lstm_backward_workspace_bytes(int E1, int H, int depth) {
-    const size_t Hp = (size_t)ggpm_padded_hidden(H);
-    const size_t slot = (size_t)E1 * Hp;
-    size_t f = 0;
-    f += 3 * (size_t)depth * slot;                     // DI, DO, DU
-    f += (size_t)depth * slot;                         // DQ (slot t = dqf^t; slot 0 only used by sparse_forward)
-    f += 6 * slot;                                     // dS / dFC double buffers + dh / dc carries
-    f += 4 * ggpm_packed_matrix_slot((int)Hp);         // packed transposes (the largest gate mode's)
-    size_t bytes = f * sizeof(float);
-    bytes += ggpm_gemm_workspace_bytes(H, H, depth * E1);
-    return bytes + 256;
+    return backward_workspace_bytes<LstmCell>(E1, H, depth);      // (level_host.h: carve)
 }
 
 static int lstm_weight_grads_impl(int E1, int H, int depth, const float* Hs, const float* Ss, float* work,
@@ -984,34 +884,25 @@ static int lstm_backward_impl(int E1, int H, int depth, const float* Xf, const f
         return GGPM_ERR_ARG;
     if (work_bytes < ggpm_lstm_backward_workspace_bytes(E1, H, depth)) return GGPM_ERR_WORKSPACE;
     const int Hp = ggpm_padded_hidden(H);
-    if (!lstm_shape_ok(E1, Hp)) return GGPM_ERR_UNSUPPORTED;
+    if (!LstmCell::shape_ok(E1, Hp)) return GGPM_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     const size_t HH = (size_t)Hp * Hp, slot = (size_t)E1 * Hp;
 
     const bool skip_xsum = o.skip_x_sums && !frozen;
-    // (the packed transposes come first: their place does not depend on E1 -- ggpm_level_opts.weights_packed)
-    float* w = work;
-    const LevelPlan plan = level_plan(o, E1, Hp, frozen != nullptr);
+    const LevelPlan plan = level_plan<LstmCell>(o, E1, Hp, frozen != nullptr);
     const bool rt2 = plan.rt2;
     const int bf16 = plan.gm;      // gate mode 0 / 1 / 2
     const size_t mstep = ggpm_packed_matrix_floats(Hp, bf16);
-    float* pWiT = w; float* pWoT = w + mstep; float* pWuT = w + 2 * mstep; float* pWfT = w + 3 * mstep;
-    w += 4 * ggpm_packed_matrix_slot(Hp);
-    float* DI = w; w += (size_t)depth * slot;
-    float* DO = w; w += (size_t)depth * slot;
-    float* DU = w; w += (size_t)depth * slot;
-    float* DQ = w; w += (size_t)depth * slot;
-    float* dSb[2]; float* dFb[2];
-    dSb[0] = w; w += slot; dSb[1] = w; w += slot; dFb[0] = w; w += slot; dFb[1] = w; w += slot;
-    float* carry_h = w; w += slot; float* carry_c = w; w += slot;
-    float* skws = w;
-    const size_t skbytes = work_bytes - (size_t)((char*)skws - (char*)work);
+    const LevelWork<LstmCell> wk = carve<LstmCell>(work, E1, Hp, depth);
+    float* pWiT = wk.packedT; float* pWoT = pWiT + mstep; float* pWuT = pWiT + 2 * mstep; float* pWfT = pWiT + 3 * mstep;
+    float* DI = wk.stash[0]; float* DO = wk.stash[1]; float* DU = wk.stash[2]; float* DQ = wk.DQ;
+    float* const dSb[2] = {wk.scratch[0], wk.scratch[1]}; float* const dFb[2] = {wk.scratch[2], wk.scratch[3]};
+    float* carry_h = wk.scratch[4]; float* carry_c = wk.scratch[5];
     if (o.defer_stash[0]) {       // deferred weight gradients: the stashes go to the caller's stacked buffers
         if (!frozen || !o.defer_stash[1] || !o.defer_stash[2] || !o.defer_stash[3]) return GGPM_ERR_ARG;
         DI = o.defer_stash[0]; DO = o.defer_stash[1]; DU = o.defer_stash[2]; DQ = o.defer_stash[3];
         weight_grads = 0;
     }
-    (void)skws; (void)skbytes;
 
     {
         GgpmPackArgs pk = {};
@@ -1078,10 +969,10 @@ static int lstm_backward_impl(int E1, int H, int depth, const float* Xf, const f
 // where ggpm_lstm_backward left its di_pre / do_pre / du_pre stashes inside `work` (slot t-1 of each = backward step t)
 extern "C" int ggpm_lstm_backward_stashes(float* work, int E1, int H, int depth, float** DI, float** DO, float** DU) {
     if (!work || !DI || !DO || !DU || E1 <= 0 || H <= 0 || depth <= 0) return GGPM_ERR_ARG;
-    const size_t Hp = (size_t)ggpm_padded_hidden(H), slot = (size_t)E1 * Hp;
-    *DI = work + 4 * ggpm_packed_matrix_slot((int)Hp);
-    *DO = *DI + (size_t)depth * slot;
-    *DU = *DO + (size_t)depth * slot;
+    const LevelWork<LstmCell> wk = carve<LstmCell>(work, E1, ggpm_padded_hidden(H), depth);
+    *DI = wk.stash[0];
+    *DO = wk.stash[1];
+    *DU = wk.stash[2];
     return GGPM_OK;
 }
 
@@ -1129,66 +1020,11 @@ static int lstm_weight_grads_impl(int E1, int H, int depth, const float* Hs, con
         return GGPM_ERR_ARG;
     if (lo < 1 || lo > depth || with_slot0) lo = 1;       // backward steps depth .. lo ran (stash slots lo-1 .. depth-1)
     if (work_bytes < ggpm_lstm_backward_workspace_bytes(E1, H, depth)) return GGPM_ERR_WORKSPACE;
-    const int Hp = ggpm_padded_hidden(H);
-    hipStream_t s = (hipStream_t)stream;
-    const size_t HH = (size_t)Hp * Hp, slot = (size_t)E1 * Hp;
-    float* w = work + 4 * ggpm_packed_matrix_slot(Hp);             // (layout of lstm_backward_impl)
-    float* DI = w; w += (size_t)depth * slot;
-    float* DO = w; w += (size_t)depth * slot;
-    float* DU = w; w += (size_t)depth * slot;
-    float* DQ = w; w += (size_t)depth * slot;
-    w += 6 * slot;
-    float* skws = w;
-    const size_t skbytes = work_bytes - (size_t)((char*)skws - (char*)work);
-    const int KD = (depth - lo + 1) * E1;
-    // bf16 storage (as the forward / backward decided): bf16 stashes in the first half of their buffers, read as they are
-    const bool st16 = o.gate_dtype == 1 && !with_slot0 && ggpm_bf16_storage_applies(E1, H);
-    const int tall_mode = st16 ? 2 : (o.gate_dtype == 1 ? 1 : 0);
-    const float* Sl = ggpm_slot_ptr(Ss, lo - 1, slot, st16);
-    int rc;
-    if (o.fixed_slot > 0 && !with_slot0) {
-        // fixed-point level (ggpm_level_opts.fixed_slot; mpn_gru.hip: gru_weight_grads_impl): dW*_h = (sum_t D*_t)^T S* for
-        // the i / o / u gates and dWf_h = (sum_t DQ_t)^T h*, the slot sums as hi + lo pairs in slots 0 / 1 of each stash
-        const int fs = o.fixed_slot;
-        if (fs >= depth || lo < fs || lo < 3 || o.gate_dtype == 1) return GGPM_ERR_ARG;
-        const int nq = depth - lo;                         // dqf^t exists for t = lo .. depth - 1
-        const float* src[4] = {DI + (size_t)(lo - 1) * slot, DO + (size_t)(lo - 1) * slot, DU + (size_t)(lo - 1) * slot,
-                               DQ + (size_t)lo * slot};
-        const int slots[4] = {depth - lo + 1, depth - lo + 1, depth - lo + 1, nq};
-        float* const hi[4] = {DI, DO, DU, DQ};
-        float* const lw[4] = {DI + slot, DO + slot, DU + slot, DQ + slot};
-        rc = ggpm_sum_slots_pair_grouped(nq > 0 ? 4 : 3, src, slots, slot, hi, lw, stream);
-        if (rc) return rc;
-        const float* Sf = Ss + (size_t)(fs - 1) * slot;
-        const ggpm_pair_problem pp[4] = {{DI, DI + slot, Sf, dWi_h, ld_dwi}, {DO, DO + slot, Sf, dWo_h, ld_dwo},
-                                         {DU, DU + slot, Sf, dWu_h, ld_dwu}, {DQ, DQ + slot, Hs + (size_t)fs * slot, dWf_h, ld_dwf}};
-        if (nq == 0)
-            for (int r = 0; r < H; ++r) (void)hipMemsetAsync(dWf_h + (size_t)r * ld_dwf, 0, H * sizeof(float), s);
-        rc = ggpm_gemm_tn_pair_grouped(H, H, E1, Hp, nq > 0 ? 4 : 3, pp, stream);
-        if (rc) return rc;
-        GGPM_CHECK_LAUNCH();
-        return GGPM_OK;
-    }
-    // the three or four contractions in ONE launch and one reduce (they share the split-K workspace)
-    ggpm_gemm_problem gp[4] = {{ggpm_slot_ptr(DI, lo - 1, slot, st16), Hp, Sl, Hp, dWi_h, ld_dwi, H, nullptr, 0, GGPM_ACT_NONE, 0},
-                               {ggpm_slot_ptr(DO, lo - 1, slot, st16), Hp, Sl, Hp, dWo_h, ld_dwo, H, nullptr, 0, GGPM_ACT_NONE, 0},
-                               {ggpm_slot_ptr(DU, lo - 1, slot, st16), Hp, Sl, Hp, dWu_h, ld_dwu, H, nullptr, 0, GGPM_ACT_NONE, 0},
-                               {nullptr, Hp, nullptr, Hp, dWf_h, ld_dwf, H, nullptr, 0, GGPM_ACT_NONE, 0}};
-    int Ks[4] = {KD, KD, KD, 0};
-    if (depth > lo || with_slot0) {
-        const int first_slot = with_slot0 ? 0 : lo;    // dqf^t pairs with h^t; slot 0 exists for sparse_forward only
-        gp[3].A = ggpm_slot_ptr(DQ, first_slot, slot, st16);
-        gp[3].B = ggpm_slot_ptr(Hs, first_slot, slot, st16);
-        Ks[3] = (depth - first_slot) * E1;
-        rc = ggpm_gemm_tall_grouped(H, H, 4, gp, Ks, skws, skbytes, stream, tall_mode);
-        if (rc) return rc;
-    } else {
-        rc = ggpm_gemm_tall_grouped(H, H, 3, gp, Ks, skws, skbytes, stream, tall_mode);
-        if (rc) return rc;
-        for (int r = 0; r < H; ++r) (void)hipMemsetAsync(dWf_h + (size_t)r * ld_dwf, 0, H * sizeof(float), s);
-    }
-    GGPM_CHECK_LAUNCH();
-    return GGPM_OK;
+    const LevelWork<LstmCell> wk = carve<LstmCell>(work, E1, ggpm_padded_hidden(H), depth);
+    // dW*_h = D*^T S for the i / o / u gates, dWf_h = DQ^T h (dqf^t pairs with h^t)
+    const WgradTerm gate[3] = {{wk.stash[0], Ss, dWi_h, ld_dwi}, {wk.stash[1], Ss, dWo_h, ld_dwo}, {wk.stash[2], Ss, dWu_h, ld_dwu}};
+    return level_weight_grads(E1, H, depth, lo, with_slot0, o, 3, gate, {wk.DQ, Hs, dWf_h, ld_dwf}, nullptr, nullptr, wk.skws,
+                              wk.skbytes(work_bytes), stream);
 }
 
 // The hidden-half weight gradients of MANY sparse backward calls at once (see ggpm_gru_weight_grads_stacked).
@@ -1205,15 +1041,8 @@ extern "C" int ggpm_lstm_weight_grads_stacked(int rows, int rows_q, int H, const
     const int Hp = ggpm_padded_hidden(H);
     float* skws = work + (size_t)256 * Hp;
     const size_t skbytes = work_bytes - (size_t)256 * Hp * sizeof(float);
-    const ggpm_gemm_problem gp[4] = {{DI, Hp, Ss, Hp, dWi_h, ld_dwi, H, nullptr, 0, GGPM_ACT_NONE, 0},
-                                     {DO, Hp, Ss, Hp, dWo_h, ld_dwo, H, nullptr, 0, GGPM_ACT_NONE, 0},
-                                     {DU, Hp, Ss, Hp, dWu_h, ld_dwu, H, nullptr, 0, GGPM_ACT_NONE, 0},
-                                     {DQ, Hp, Hs, Hp, dWf_h, ld_dwf, H, nullptr, 0, GGPM_ACT_NONE, 0}};
-    const int Ks[4] = {rows, rows, rows, rows_q};
-    const int rc = ggpm_gemm_tall_grouped(H, H, 4, gp, Ks, skws, skbytes, stream);
-    if (rc) return rc;
-    GGPM_CHECK_LAUNCH();
-    return GGPM_OK;
+    const WgradTerm gate[3] = {{DI, Ss, dWi_h, ld_dwi}, {DO, Ss, dWo_h, ld_dwo}, {DU, Ss, dWu_h, ld_dwu}};
+    return tall_weight_grads(H, Hp, 3, gate, rows, {DQ, Hs, dWf_h, ld_dwf}, rows_q, nullptr, nullptr, false, 0, skws, skbytes, stream);
 }
 
 int ggpm_lstm_sparse_weight_grads(int E1, int H, int depth, const float* Hs, const float* Ss, float* work, size_t work_bytes,

@@ -1,7 +1,8 @@
 """The forms a GRU / LSTM level call can take at the configured hidden sizes, as a table of test cases, and their inputs.
 
-A level call's launch geometry is decided per call (csrc/tile_mma.h: ggpm_tiles_per_group; csrc/mpn_gru.hip and
-csrc/mpn_lstm.hip: level_plan, fwd_step, bwd_step) and reported by ``ggpm_level_form_query``.  A case names one call and the
+A level call's launch geometry is decided per call (csrc/tile_mma.h: ggpm_tiles_per_group; csrc/level_host.h: level_plan,
+fwd_step, bwd_step over the cell descriptions of csrc/mpn_gru.hip and csrc/mpn_lstm.hip) and reported by
+``ggpm_level_form_query``.  A case names one call and the
 form the table expects it to take, reduced to ``(tg, groups, gate_mode, rt2, fuse_fwd, fuse_bwd)``:
 tests/test_level_forms_cpu.py holds the table to the lattice the query spans (every reachable form has a case; every case
 has the form it states), tests/test_gpu_level_forms.py runs every case against the fp64 oracle.

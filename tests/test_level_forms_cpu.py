@@ -98,6 +98,36 @@ def test_no_form_exceeds_the_lds_of_a_workgroup(cell):
             assert (f.fuse_bwd, f.lds_bwd_a, f.lds_bwd_b) == (0, 0, 0), what
 
 
+@pytest.mark.parametrize("H", [250, 300, 600])
+def test_backward_workspace_layout_is_the_documented_one(H):
+    """Where a backward leaves its gate stashes inside `work`, and how large `work` is: packed transposes first (3 GRU /
+    4 LSTM slots of the largest gate mode's size), then the stashes of `depth` slots each, the dq stash, six scratch slots,
+    for the GRU 256 * Hp floats of column-sum scratch, and the split-K workspace.  Host-only entry points: `work` is an
+    address that is never read."""
+    import ctypes
+    from ggpm_amd import _lib
+    lib = _lib.load()
+    Hp = int(lib.ggpm_padded_hidden(H))
+    slotW_gru, rem = divmod(int(lib.ggpm_gru_pack_floats(H)) - Hp, 3)
+    slotW_lstm, rem4 = divmod(int(lib.ggpm_lstm_pack_floats(H)), 4)
+    assert rem == 0 and rem4 == 0
+    work = 1 << 20
+    for E1, depth in itertools.product((2, 40, 2049), (1, 2, 20)):
+        slot = E1 * Hp
+        gemm_ws = int(lib.ggpm_gemm_workspace_bytes(H, H, depth * E1))
+        p = [ctypes.c_void_p() for _ in range(3)]
+        assert lib.ggpm_gru_backward_stashes(work, E1, H, depth, ctypes.byref(p[0]), ctypes.byref(p[1])) == _lib.GGPM_OK
+        assert p[0].value == work + 4 * 3 * slotW_gru, (E1, depth)
+        assert p[1].value == p[0].value + 4 * depth * slot, (E1, depth)
+        assert lib.ggpm_lstm_backward_stashes(work, E1, H, depth, *(ctypes.byref(x) for x in p)) == _lib.GGPM_OK
+        assert p[0].value == work + 4 * 4 * slotW_lstm, (E1, depth)
+        assert p[1].value == p[0].value + 4 * depth * slot and p[2].value == p[1].value + 4 * depth * slot, (E1, depth)
+        assert int(lib.ggpm_gru_backward_workspace_bytes(E1, H, depth)) == \
+            4 * (3 * depth * slot + 6 * slot + 3 * slotW_gru + 256 * Hp) + gemm_ws + 256, (E1, depth)
+        assert int(lib.ggpm_lstm_backward_workspace_bytes(E1, H, depth)) == \
+            4 * (4 * depth * slot + 6 * slot + 4 * slotW_lstm) + gemm_ws + 256, (E1, depth)
+
+
 def test_accepted_hidden_sizes_are_the_documented_ones():
     """include/ggpm_hip.h, "Accepted hidden sizes": GRU H <= 1264, LSTM H <= 848; beyond: GGPM_ERR_UNSUPPORTED"""
     import ctypes
