@@ -123,7 +123,12 @@ SIGNATURES = {
     "ggpm_bound_objective": (I, [P, P, P, P, I, I, I, ctypes.c_float, P, P, P, P, P, P]),
     "ggpm_scale_rows_by_mol": (I, [P, I, I, I, P, P, I, I, P, P]),
     "ggpm_latent_terms_backward": (I, [P, P, P, P, P, P, P, I, I, I, P, P, P]),
-    "ggpm_dropout": (I, [P, I, I, I, ctypes.c_float, ctypes.c_uint, ctypes.c_uint, I, P]),
+    # the latent column by column (csrc/latent_dims.hip)
+    "ggpm_latent_dim_accumulate": (I, [P, P, I, I, P, P]),
+    "ggpm_latent_dim_finish": (I, [P, I, c_float, P, P, P]),
+    "ggpm_free_bits_kl": (I, [P, P, P, I, I, c_float, P, P, P]),
+    "ggpm_free_bits_kl_backward": (I, [P, P, P, P, I, I, c_float, P, P, P, P]),
+    "ggpm_dropout": (I, [P, I, I, I, ctypes.c_float,ctypes.c_uint, ctypes.c_uint, I, P]),
     # property heads / latent search (csrc/property.hip): heads are ggpm_prop_head*, grads ggpm_prop_head_grads*
     "ggpm_property_heads_workspace_bytes": (c_size_t, [I, I, P, P]),
     "ggpm_property_heads_forward": (I, [I, P, I, I, P, P, P, P, c_float, ctypes.c_uint, ctypes.c_uint, P, P, P, c_size_t, P]),

@@ -200,6 +200,92 @@ def latent_terms_backward(dz: Optional[torch.Tensor], mean: torch.Tensor, pre_va
     return dmean, dpv
 
 
+LATENT_STAT_ROWS = 5            # include/ggpm_hip.h GGPM_LATENT_STAT_ROWS / GGPM_LATENT_STAT_OUT
+FREE_BITS_MAX_L = 4096          # include/ggpm_hip.h GGPM_FREE_BITS_MAX_L
+
+
+def _latent_pair(what: str, mean: torch.Tensor, pre_var: torch.Tensor, w: Optional[torch.Tensor] = None):
+    """the checks the per-dimension entries share -> (mean, pre_var, w) contiguous, B, L"""
+    _need_gpu(mean, pre_var, w)
+    if mean.dim() != 2 or pre_var.shape != mean.shape or mean.dtype != torch.float32 or pre_var.dtype != torch.float32 or \
+            mean.numel() == 0:
+        raise ValueError("%s: mean %s / pre_var %s must be fp32 [B, L] of one shape" % (what, tuple(mean.shape), tuple(pre_var.shape)))
+    B, L = mean.shape
+    if w is not None and (w.shape != (B,) or w.dtype != torch.float32):
+        raise ValueError("%s: %s weights for %d molecules (fp32 [B])" % (what, tuple(w.shape), B))
+    return mean.contiguous(), pre_var.contiguous(), (w.contiguous() if w is not None else None), B, L
+
+
+def _free_bits_lambda(what: str, lam, L: int) -> float:
+    lam = float(lam)
+    if not (0.0 <= lam < float("inf")):
+        raise ValueError("%s: lambda %r (a finite value >= 0)" % (what, lam))
+    if L > FREE_BITS_MAX_L:
+        raise ValueError("%s: %d latent columns (at most %d)" % (what, L, FREE_BITS_MAX_L))
+    return lam
+
+
+def latent_dim_accumulate(mean: torch.Tensor, pre_var: torch.Tensor, acc: torch.Tensor) -> torch.Tensor:
+    """Adds the per-column sums of mean, pre_var [B, L] to ``acc``, a contiguous fp64 [5, L] device tensor the caller zeroed
+    once (rows: count, sum mean, sum mean^2, sum exp(lv), sum kl_dim) -> acc (csrc/latent_dims.hip)"""
+    mean, pre_var, _, B, L = _latent_pair("latent_dim_accumulate", mean, pre_var)
+    _need_gpu(acc)
+    if acc.shape != (LATENT_STAT_ROWS, L) or acc.dtype != torch.float64 or not acc.is_contiguous():
+        raise ValueError("latent_dim_accumulate: acc must be a contiguous fp64 [%d, %d] tensor, got %s %s"
+                         % (LATENT_STAT_ROWS, L, acc.dtype, tuple(acc.shape)))
+    _lib.check(_lib.load().ggpm_latent_dim_accumulate(_p(mean), _p(pre_var), B, L, _p(acc), _stream()), "latent_dim_accumulate")
+    return acc
+
+
+def latent_dim_finish(acc: torch.Tensor, au_threshold: float = 0.01):
+    """acc fp64 [5, L] -> (out fp32 [5, L]: kl_dims, mu_mean, mu_var, sigma2_mean, agg_var; n_active int32 [1]: the columns
+    with mu_var > au_threshold) (csrc/latent_dims.hip)"""
+    _need_gpu(acc)
+    if acc.dim() != 2 or acc.shape[0] != LATENT_STAT_ROWS or acc.shape[1] < 1 or acc.dtype != torch.float64 or \
+            not acc.is_contiguous():
+        raise ValueError("latent_dim_finish: acc must be a contiguous fp64 [%d, L] tensor, got %s %s"
+                         % (LATENT_STAT_ROWS, acc.dtype, tuple(acc.shape)))
+    au_threshold = float(au_threshold)
+    if au_threshold != au_threshold:
+        raise ValueError("latent_dim_finish: au_threshold is NaN")
+    L = acc.shape[1]
+    out = torch.empty(LATENT_STAT_ROWS, L, dtype=torch.float32, device=acc.device)
+    n_active = torch.empty(1, dtype=torch.int32, device=acc.device)
+    _lib.check(_lib.load().ggpm_latent_dim_finish(_p(acc), L, au_threshold, _p(out), _p(n_active), _stream()), "latent_dim_finish")
+    return out, n_active
+
+
+def free_bits_kl(mean: torch.Tensor, pre_var: torch.Tensor, w: Optional[torch.Tensor], lam: float):
+    """mean, pre_var [B, L], w [B] or None -> (kl_dims [L]: the batch-mean weighted KL of every latent column, term [1]:
+    sum_j max(lam, kl_dims_j) formed in fp64) (csrc/latent_dims.hip)"""
+    mean, pre_var, w, B, L = _latent_pair("free_bits_kl", mean, pre_var, w)
+    lam = _free_bits_lambda("free_bits_kl", lam, L)
+    f32 = dict(dtype=torch.float32, device=mean.device)
+    kl_dims, term = torch.empty(L, **f32), torch.empty(1, **f32)
+    _lib.check(_lib.load().ggpm_free_bits_kl(_p(mean), _p(pre_var), _p(w), B, L, lam, _p(kl_dims), _p(term), _stream()),
+               "free_bits_kl")
+    return kl_dims, term
+
+
+def free_bits_kl_backward(mean: torch.Tensor, pre_var: torch.Tensor, w: Optional[torch.Tensor], lam: float,
+                          g: Optional[torch.Tensor] = None, kl_dims: Optional[torch.Tensor] = None):
+    """The gradient of ``free_bits_kl``'s term times ``g`` (fp32 [1] or None: 1) -> (dmean [B, L], dpre_var [B, L]), zero in
+    the columns that are free.  ``kl_dims``: the forward's, which spares the columns it decides their sum; the result does
+    not depend on it (csrc/latent_dims.hip)"""
+    mean, pre_var, w, B, L = _latent_pair("free_bits_kl_backward", mean, pre_var, w)
+    lam = _free_bits_lambda("free_bits_kl_backward", lam, L)
+    _need_gpu(g, kl_dims)
+    if g is not None and (g.numel() != 1 or g.dtype != torch.float32):
+        raise ValueError("free_bits_kl_backward: g must hold one fp32 value")
+    if kl_dims is not None and (kl_dims.shape != (L,) or kl_dims.dtype != torch.float32):
+        raise ValueError("free_bits_kl_backward: kl_dims %s for %d latent columns (fp32 [L])" % (tuple(kl_dims.shape), L))
+    kl_dims = kl_dims.contiguous() if kl_dims is not None else None
+    dmean, dpv = torch.empty_like(mean), torch.empty_like(pre_var)
+    _lib.check(_lib.load().ggpm_free_bits_kl_backward(_p(mean), _p(pre_var), _p(w), _p(kl_dims), B, L, lam, _p(g), _p(dmean),
+                                                      _p(dpv), _stream()), "free_bits_kl_backward")
+    return dmean, dpv
+
+
 def padded_hidden(H: int) -> int:
     return (H + 15) // 16 * 16
 

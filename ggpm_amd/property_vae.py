@@ -147,6 +147,37 @@ class _LatentTerms(torch.autograd.Function):
         return _latent_heads_backward(ctx, z_vecs, Wm, Wv, dmean, dpv) + (None,)
 
 
+class _FreeBitsLatentTerms(torch.autograd.Function):
+    """_LatentTerms with the free-bits KL beside it: also returns ``term = sum_j max(free_bits, klbar_j)`` and ``kl_dims``
+    (ggpm_free_bits_kl; ``w`` [B] or None weighs the molecules in klbar).  On the way back ggpm_free_bits_kl_backward's
+    dmean / dpre_var are added to ggpm_latent_terms_backward's, so the heads and their deferred weight gradients run once.
+    ``term`` reaches parameters only through this node, which also waits for z, kl and logpq: _BoundObjective stays the first
+    node of the pass."""
+
+    @staticmethod
+    def forward(ctx, z_vecs, Wm, bm, Wv, bv, eps, w, free_bits):
+        mean, pv = _latent_heads(z_vecs, Wm, bm, Wv, bv)
+        z, kl, logpq = F_.latent_terms(mean, pv, eps)
+        kl_dims, term = F_.free_bits_kl(mean, pv, w, free_bits)
+        ctx.save_for_backward(z_vecs, Wm, Wv, mean, pv, eps, kl_dims)
+        ctx.params = (Wm, bm, Wv, bv)
+        ctx.free_bits = (w, free_bits)
+        ctx.mark_non_differentiable(kl_dims)
+        ctx.set_materialize_grads(False)
+        return z, kl, logpq, term.reshape(()), kl_dims
+
+    @staticmethod
+    def backward(ctx, dz, dkl, dlogpq, dterm, _):
+        z_vecs, Wm, Wv, mean, pv, eps, kl_dims = ctx.saved_tensors
+        dmean, dpv = F_.latent_terms_backward(dz, mean, pv, eps, dlogpq, dkl)
+        if dterm is not None:
+            w, free_bits = ctx.free_bits
+            fm, fp = F_.free_bits_kl_backward(mean, pv, w, free_bits, dterm.reshape(1).to(torch.float32), kl_dims)
+            dmean.add_(fm)
+            dpv.add_(fp)
+        return _latent_heads_backward(ctx, z_vecs, Wm, Wv, dmean, dpv) + (None, None, None)
+
+
 class _BoundObjective(torch.autograd.Function):
     """(parts [K, B, 4], logpq [K, B], kl [B]) -> the weighted K-sample ELBO / IWAE loss (ggpm_bound_objective, which also
     leaves the loss's partial derivatives); the backward hands them on, times the upstream gradient.  It is the first node
@@ -470,10 +501,25 @@ class _VAE(nn.Module):
         return log_likelihood(self, batch, n_samples, seed, sample_ids, eps, max_cls_size, schedule)
 
     def bound_loss(self, batch, n_samples=1, objective="elbo", beta=1.0, mol_weights=None, seed=None, sample_ids=None,
-                   eps=None, max_cls_size=None, schedule=None):
+                   eps=None, max_cls_size=None, schedule=None, free_bits=None):
         """The ``n_samples``-sample ELBO (``objective="elbo"``) or importance-weighted bound (``"iwae"``) of ``batch`` as a
-        loss to train on, with optional per-molecule weights -> (loss, :class:`MolObjective`); see :func:`bound_loss`."""
-        return bound_loss(self, batch, n_samples, objective, beta, mol_weights, seed, sample_ids, eps, max_cls_size, schedule)
+        loss to train on, with optional per-molecule weights and, for the ELBO, a free-bits KL -> (loss,
+        :class:`MolObjective`); see :func:`bound_loss`."""
+        return bound_loss(self, batch, n_samples, objective, beta, mol_weights, seed, sample_ids, eps, max_cls_size, schedule,
+                          free_bits)
+
+    def latent_accumulator(self, au_threshold=0.01):
+        """A :class:`LatentAccumulator` of this model: per-dimension statistics of the latent over as many batches as it is
+        given, kept on the device."""
+        return LatentAccumulator(self, au_threshold)
+
+    def latent_stats(self, batches, au_threshold=0.01):
+        """Per-dimension KL, the mean and variance of the posterior means, the mean posterior variance and the number of
+        active units (``Var_x E_q[z_j] > au_threshold``) over the iterable ``batches`` -> :class:`LatentStats`."""
+        acc = self.latent_accumulator(au_threshold)
+        for batch in batches:
+            acc.update(batch)
+        return acc.result()
 
     def reconstruct(self, batch, args=None):
         """reference ggpm/property_vae.py:39-45 (101-109, 169-188, 299-318 for the other three): the no-grad encoder, the
@@ -698,8 +744,67 @@ MolObjective.__doc__ = """The second value of ``bound_loss``: detached fp32 devi
 bit what ``log_likelihood`` returns for the same draws) plus ``weights [B]``, the molecule weights used (ones for None)."""
 
 
+class FreeBitsObjective(MolObjective):
+    """The second value of ``bound_loss(free_bits=...)``: :class:`MolObjective`'s seven fields (so unpacking it is unchanged)
+    and two attributes, ``kl_dims`` (fp32 [L] on the device: klbar_j, the weighted batch mean of every latent column's KL)
+    and ``free_bits`` (the float used)."""
+
+    def __new__(cls, *fields, kl_dims, free_bits):
+        self = super().__new__(cls, *fields)
+        self.kl_dims, self.free_bits = kl_dims, free_bits
+        return self
+
+
+LatentStats = namedtuple("LatentStats", ["kl_dims", "mu_mean", "mu_var", "sigma2_mean", "agg_var", "n_active", "n_molecules"])
+LatentStats.__doc__ = """What ``latent_stats`` and ``LatentAccumulator.result`` return, over the N molecules seen and per latent column j
+(fp32 [L] device tensors; nothing requires grad, nothing is synchronised), with lv = -|R_var(h)| and mean = R_mean(h):
+  kl_dims      mean over molecules of -0.5 (1 + lv - mean^2 - exp(lv)); summed over j it is the mean of ``log_likelihood``'s kl
+  mu_mean      mean over molecules of mean
+  mu_var       population variance over molecules of mean: Var_x E_q[z_j], the quantity behind "active units"
+  sigma2_mean  mean over molecules of exp(lv), the posterior variance
+  agg_var      mu_var + sigma2_mean, the variance of the aggregate posterior (1 where it matches the prior)
+  n_active     0-dim int32 device tensor: the columns with mu_var > au_threshold
+  n_molecules  python int: N, counted on the host"""
+
+
+class LatentAccumulator:
+    """Per-dimension statistics of a model's latent over any number of batches (``model.latent_accumulator()``).  The sums
+    stay on the device in fp64 (ggpm_latent_dim_accumulate adds one batch per launch; nothing is synchronised);
+    ``result()`` may be called at any time and updates may go on after it."""
+
+    def __init__(self, model, au_threshold=0.01):
+        self.model, self.au_threshold = model, float(au_threshold)
+        if self.au_threshold != self.au_threshold:
+            raise ValueError("%s.latent_accumulator: au_threshold is NaN" % type(model).__name__)
+        self._check()
+        Rm = model.R_mean.weight
+        self.acc = torch.zeros(F_.LATENT_STAT_ROWS, Rm.shape[0], dtype=torch.float64, device=Rm.device)
+        self.n_molecules = 0
+
+    def _check(self):
+        check_no_dropout(self.model, "%s.latent_stats runs without dropout: call model.eval() first"
+                         % type(self.model).__name__, each_dropout=True)
+
+    def update(self, batch):
+        """Adds the molecules of ``batch`` (the tuple ``model(*batch)`` takes; only ``batch[2]``, the tensors, is used)."""
+        self._check()
+        model = self.model
+        with torch.no_grad():
+            root_vecs = model._encode(make_cuda(batch[2]))
+            Rm, Rv = model.R_mean, model.R_var
+            mean, pre_var = _latent_heads(root_vecs, Rm.weight, Rm.bias, Rv.weight, Rv.bias)
+            F_.latent_dim_accumulate(mean, pre_var, self.acc)
+        self.n_molecules += mean.shape[0]
+        return self
+
+    def result(self):
+        """-> :class:`LatentStats` of what has been added so far (zeros before the first update)"""
+        out, n_active = F_.latent_dim_finish(self.acc, self.au_threshold)
+        return LatentStats(out[0], out[1], out[2], out[3], out[4], n_active.reshape(()), self.n_molecules)
+
+
 def bound_loss(model, batch, n_samples=1, objective="elbo", beta=1.0, mol_weights=None, seed=None, sample_ids=None, eps=None,
-               max_cls_size=None, schedule=None):
+               max_cls_size=None, schedule=None, free_bits=None):
     """``bound_loss`` of the four VAEs (*Training on the bound*) -> (loss, :class:`MolObjective`).
 
     With ``nll``, ``kl``, ``logpq`` and ``iwae`` as ``log_likelihood`` forms them, w the molecule weights and K = n_samples:
@@ -709,7 +814,14 @@ def bound_loss(model, batch, n_samples=1, objective="elbo", beta=1.0, mol_weight
     z_k = mean + exp(lv / 2) eps_k, through the lv and z terms of logpq and through kl, to every encoder, latent-head and
     decoder parameter (the property heads and LossWeigh of the -opt models take no part).  ``mol_weights``: None or B
     floats (a host sequence or a float32 tensor on the model's device), a constant.  Every other argument is
-    ``log_likelihood``'s.  One encoder pass and one atom-level pass serve the K decoder passes, forward and backward."""
+    ``log_likelihood``'s.  One encoder pass and one atom-level pass serve the K decoder passes, forward and backward.
+
+    ``free_bits`` (None, or a finite float >= 0 with ``objective="elbo"``; DESIGN.md, *Per-dimension KL*): the KL is held
+    per latent column instead of per molecule,
+      loss = (1/B) sum_i w_i (1/K) sum_k nll[k, i] + beta sum_j max(free_bits, klbar_j),  klbar_j = (1/B) sum_i w_i kl_dim[i, j]
+    so a column whose batch-mean KL is at or below ``free_bits`` nats is no longer pushed down (its KL gradient is exactly
+    zero).  ``free_bits=0.0`` is the ELBO above summed in another order.  The second value is then a
+    :class:`FreeBitsObjective`, which adds ``kl_dims`` ([L], klbar) and ``free_bits`` to the same seven fields."""
     from .greedy_decode import split_seed
     name, dec, dev, K, B, L, schedule, C = _likelihood_args(model, "bound_loss", batch, n_samples, sample_ids, eps,
                                                             max_cls_size, schedule)
@@ -718,6 +830,14 @@ def bound_loss(model, batch, n_samples=1, objective="elbo", beta=1.0, mol_weight
     beta = float(beta)
     if objective == "iwae" and beta != 1.0:
         raise ValueError("%s.bound_loss: the importance-weighted bound has no beta (got %r): pass beta=1.0" % (name, beta))
+    if free_bits is not None:
+        if objective != "elbo":
+            raise ValueError("%s.bound_loss: free_bits holds the KL of the ELBO; objective %r has none to hold" % (name, objective))
+        free_bits = float(free_bits)
+        if not (0.0 <= free_bits < float("inf")):
+            raise ValueError("%s.bound_loss: free_bits %r (None, or a finite value >= 0)" % (name, free_bits))
+        if L > F_.FREE_BITS_MAX_L:
+            raise ValueError("%s.bound_loss: free_bits for %d latent columns (at most %d)" % (name, L, F_.FREE_BITS_MAX_L))
     w = None
     if mol_weights is not None:
         if isinstance(mol_weights, torch.Tensor):
@@ -735,7 +855,11 @@ def bound_loss(model, batch, n_samples=1, objective="elbo", beta=1.0, mol_weight
             lo, hi = split_seed(seed)
             eps = F_.sample_latent_normal(K, B, L, lo, hi, ids=sample_ids, device=dev)
         Rm, Rv = model.R_mean, model.R_var
-        z, kl, logpq = _LatentTerms.apply(root_vecs, Rm.weight, Rm.bias, Rv.weight, Rv.bias, eps.detach())
+        if free_bits is None:
+            z, kl, logpq = _LatentTerms.apply(root_vecs, Rm.weight, Rm.bias, Rv.weight, Rv.bias, eps.detach())
+        else:
+            z, kl, logpq, term, kl_dims = _FreeBitsLatentTerms.apply(root_vecs, Rm.weight, Rm.bias, Rv.weight, Rv.bias,
+                                                                     eps.detach(), w, free_bits)
         parts = []
         for k in range(K):
             zk = z[k]
@@ -743,11 +867,18 @@ def bound_loss(model, batch, n_samples=1, objective="elbo", beta=1.0, mol_weight
                                              atom=atom))
             stats["decoder_passes"] += 1
         parts = torch.stack(parts, dim=0)
-        loss = _BoundObjective.apply(parts, logpq, kl, w, objective, beta, tuple(model.parameters()))
+        if free_bits is None:
+            loss = _BoundObjective.apply(parts, logpq, kl, w, objective, beta, tuple(model.parameters()))
+        else:
+            # the reconstruction part is the ELBO without its KL; the held KL joins it as one term
+            loss = _BoundObjective.apply(parts, logpq, kl, w, objective, 0.0, tuple(model.parameters())) + beta * term
     with torch.no_grad():
         elbo, iwae = F_.iwae_finish(parts.detach(), logpq.detach(), kl.detach())
     ones = w if w is not None else torch.ones(B, dtype=torch.float32, device=dev)
-    return loss, MolObjective(parts.detach(), kl.detach(), elbo, iwae, z.detach(), ones, stats)
+    fields = (parts.detach(), kl.detach(), elbo, iwae, z.detach(), ones, stats)
+    if free_bits is None:
+        return loss, MolObjective(*fields)
+    return loss, FreeBitsObjective(*fields, kl_dims=kl_dims.detach(), free_bits=free_bits)
 
 
 def _graph_batch_factory(model, args):

@@ -945,6 +945,46 @@ int ggpm_latent_terms_backward(const float* dz, const float* mean, const float* 
                                const float* c_logpq, const float* c_kl, const float* g, int K, int B, int L, float* dmean,
                                float* dpre_var, ggpm_stream_t stream);
 
+/* The latent column by column (latent_stats and bound_loss(free_bits=) of the four VAEs; csrc/latent_dims.hip): the
+ * conventions of the entries above -- one wave per output with its lanes striding the molecules, fp64 partials through a fixed
+ * shuffle tree, one rounding where a value is stored, no atomics, bitwise reproducible.  With lv = -|pre_var|,
+ *     a[b, j] = 1 + lv - mean^2 - expf(lv)      (fp32: the addend of ggpm_latent_terms' kl and of ggpm_rsample_forward)
+ *     kl_dim[b, j] = -0.5 a[b, j]                (sum_j kl_dim[b, j] is kl[b] of ggpm_latent_terms before its rounding)
+ * mean, pre_var [B x L] dense, B * L < 2^31.
+ * ggpm_latent_dim_accumulate (one launch, one wave per column): acc is double[GGPM_LATENT_STAT_ROWS][L] on the device, zeroed
+ * once by the caller; the call ADDS to it: row 0 += B, row 1 += sum_b mean, row 2 += sum_b mean^2 (the squares exact in fp64),
+ * row 3 += sum_b expf(lv), row 4 += sum_b kl_dim.  Calls on one stream are ordered, so a data set is accumulated batch by
+ * batch without a host synchronisation; calls on different streams into one acc must be ordered by the caller.
+ * ggpm_latent_dim_finish (one launch, one wave): out is float[GGPM_LATENT_STAT_OUT][L]; with N = acc row 0, in fp64,
+ *     row 0 kl_dims     = row 4 / N                      row 3 sigma2_mean = row 3 / N
+ *     row 1 mu_mean     = row 1 / N                      row 4 agg_var     = mu_var + sigma2_mean
+ *     row 2 mu_var      = max(row 2 / N - mu_mean^2, 0)  (the population variance of the posterior means)
+ * each rounded once.  n_active[0] = the number of columns whose STORED (fp32) mu_var > au_threshold.  A column with N = 0
+ * gives zeros and counts as inactive.  acc is only read: accumulation may go on afterwards.
+ * ggpm_free_bits_kl (one launch, one workgroup): with w (nullable: all ones) the molecules' weights, in fp64,
+ *     klbar_j = (1/B) sum_b w_b kl_dim[b, j]             kl_dims[j] = (float)klbar_j
+ *     term[0] = (float) sum_j max((double)lambda, klbar_j)      (one wave, its lanes striding j, then the shuffle tree)
+ * 1 <= L <= GGPM_FREE_BITS_MAX_L: the workgroup keeps the L fp64 column sums in LDS (32 KiB at the limit).  With lambda = 0,
+ * beta * term is the KL part of GGPM_BOUND_ELBO's loss up to the order of summation.
+ * ggpm_free_bits_kl_backward (one launch, one wave per column): with c[b, j] = g[0] w_b / B where klbar_j > lambda, else 0,
+ *     dmean = c mean        dlv = -c (1 - expf(lv)) / 2        dpre_var = -sign(pre_var) dlv     (0 at pre_var = 0)
+ * WRITTEN to dmean / dpre_var (not added); g nullable: 1.  The comparison is strict and made in fp64 on the very klbar_j of the
+ * forward (a column exactly at lambda is free): the backward re-forms the column sum with the forward's own code.
+ * kl_dims_gate (nullable): the forward's kl_dims of the same inputs.  Rounding is monotone and lambda is a fp32 value, so a
+ * kl_dims[j] above (below) lambda already says klbar_j is above (below) it and the sum of that column is not re-formed; a
+ * kl_dims[j] equal to lambda decides nothing and the sum is re-formed.  The result is the same with and without it.
+ * A null required pointer, a size <= 0, L above its limit, a negative or NaN lambda or a NaN au_threshold returns
+ * GGPM_ERR_ARG; nothing is launched then. */
+#define GGPM_LATENT_STAT_ROWS 5
+#define GGPM_LATENT_STAT_OUT 5
+#define GGPM_FREE_BITS_MAX_L 4096
+int ggpm_latent_dim_accumulate(const float* mean, const float* pre_var, int B, int L, double* acc, ggpm_stream_t stream);
+int ggpm_latent_dim_finish(const double* acc, int L, float au_threshold, float* out, int32_t* n_active, ggpm_stream_t stream);
+int ggpm_free_bits_kl(const float* mean, const float* pre_var, const float* w, int B, int L, float lambda, float* kl_dims,
+                      float* term, ggpm_stream_t stream);
+int ggpm_free_bits_kl_backward(const float* mean, const float* pre_var, const float* w, const float* kl_dims_gate, int B, int L,
+                               float lambda, const float* g, float* dmean, float* dpre_var, ggpm_stream_t stream);
+
 /* ------------------------------------------------------------------ whole-encoder drivers
  * HierMPNEncoder.forward (ggpm/encoder.py:140-157, with embed_graph/inter/tree/root :96-138) and its backward as ONE
  * call each: the same kernels the op-by-op host path issues, sequenced from C++ (GRU or LSTM message function).

@@ -1,0 +1,335 @@
+"""GPU: ``latent_stats`` / ``latent_accumulator`` and ``bound_loss(free_bits=...)`` of the four VAEs end to end, on the
+fixtures of tests/mol_likelihood_fixtures.py.  The reference has no per-dimension view and no free bits: the statistics are
+compared with torch fp64 on the CPU over the model's own posterior parameters and with ``log_likelihood``'s KL; the free-bits
+loss and its gradients with ``bound_loss`` itself where the two coincide (free_bits = 0: the ELBO; free_bits above every
+klbar: the beta = 0 loss plus a constant) and, at a midpoint, with a composite of ``bound_loss(beta=0)`` and the free-bits
+term written in torch ops under autograd.  PARITY = 1e-4, norm-wise, as in tests/test_mol_objective_gpu.py; the derived bound of
+``mu_var`` is the one of tests/test_latent_dims_kernels_gpu.py's docstring."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as TF
+
+import mol_likelihood_fixtures as LF
+from golden_utils import rel_err
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+PARITY = 1e-4           # the project's relative parity figure (BASELINE.json)
+U = 2.0 ** -24
+SEED = 0x1234ABCD5678EF01
+BETA = 0.3
+FOUR = [("ll_hier_gru_s40", "hier-prop"), ("ll_hier_lstm_s41", "hier-prop"), ("ll_motif_gru_s60", "prop"),
+        ("ll_motif_lstm_s61", "prop")]
+HEADS = ("R_mean.weight", "R_mean.bias", "R_var.weight", "R_var.bias")
+FIELDS = ("kl_dims", "mu_mean", "mu_var", "sigma2_mean", "agg_var")
+
+
+@functools.lru_cache(maxsize=None)
+def _case(case, kind):
+    g = LF.LLGolden(case)
+    batch, sch = g.batch()
+    return g, g.model(kind).to(DEV), batch, sch
+
+
+def _np(t):
+    return t.detach().cpu().numpy().astype(np.float64)
+
+
+def _step(model, fn):
+    """zero_grad, ``fn() -> loss``, backward -> (loss, {first name: gradient})"""
+    model.zero_grad(set_to_none=True)
+    loss = fn()
+    loss.backward()
+    torch.cuda.synchronize()
+    return loss.detach().clone(), {k: p.grad.clone() for k, p in model.named_parameters() if p.grad is not None}
+
+
+def _check_grads(got, want, what):
+    """Every tensor within PARITY norm-wise of ``want``'s; a tensor whose wanted gradient is below 1e-6 of the largest:
+    max|got| <= PARITY gmax.  The two sets of parameters must be the same."""
+    assert set(got) == set(want), (what, sorted(set(got) ^ set(want)))
+    got, want = {k: _np(v) for k, v in got.items()}, {k: _np(v) for k, v in want.items()}
+    gmax = max(np.abs(v).max() for v in want.values())
+    worst = 0.0
+    for k, w in want.items():
+        a = got[k]
+        if np.abs(w).max() < 1e-6 * gmax:
+            assert np.abs(a).max() <= PARITY * gmax, (what, k, np.abs(a).max(), gmax)
+            continue
+        e = rel_err(a, w)
+        worst = max(worst, e)
+        assert e < PARITY, (what, k, e)
+    print("%s: %d gradients, largest distance %.3e" % (what, len(want), worst))
+    return worst
+
+
+def _weights(g, weighted):
+    return [float(v) for v in np.linspace(0.5, 2.0, g.B)] if weighted else None
+
+
+def _posterior(model, batch, grad=False):
+    """(mean, pre_var) [B, L] of the batch as the model's own launches form them"""
+    from ggpm_amd.nnutils import make_cuda
+    from ggpm_amd.property_vae import _latent_heads
+    with torch.set_grad_enabled(grad):
+        root = model._encode(make_cuda(batch[2]))
+        if not grad:
+            return _latent_heads(root, model.R_mean.weight, model.R_mean.bias, model.R_var.weight, model.R_var.bias)
+        H = model.R_mean.weight.shape[1]
+        return (TF.linear(root[:, :H], model.R_mean.weight, model.R_mean.bias),
+                TF.linear(root[:, :H], model.R_var.weight, model.R_var.bias))
+
+
+def _stats64(mean, pre_var):
+    """torch fp64 on the CPU -> the five per-dimension rows"""
+    m, p = mean.detach().double().cpu(), pre_var.detach().double().cpu()
+    lv = -p.abs()
+    kd = -0.5 * (1.0 + lv - m * m - lv.exp())
+    mu_var = m.var(dim=0, unbiased=False)
+    s2 = lv.exp().mean(dim=0)
+    return [t.numpy() for t in (kd.mean(dim=0), m.mean(dim=0), mu_var, s2, mu_var + s2)], kd
+
+
+def _fb_term(mean, pre_var, w, lam):
+    """sum_j max(lam, klbar_j) in torch ops (any dtype / device), differentiable"""
+    lv = -pre_var.abs()
+    kd = -0.5 * (1.0 + lv - mean * mean - lv.exp())
+    ww = torch.ones(mean.shape[0], dtype=mean.dtype, device=mean.device) if w is None else w
+    klbar = (ww[:, None] * kd).sum(dim=0) / mean.shape[0]
+    return torch.clamp(klbar, min=lam).sum(), klbar
+
+
+def _midpoint(kl_dims):
+    """a float32 midway between the two neighbouring kl_dims that lie farthest apart (relative) -> (lambda, open columns)"""
+    s = np.sort(_np(kl_dims))
+    i = int(np.argmax((s[1:] - s[:-1]) / np.maximum(s[1:], 1e-300)))
+    lam = float(np.float32(0.5 * (s[i] + s[i + 1])))
+    assert lam - s[i] >= 1e-3 * lam and s[i + 1] - lam >= 1e-3 * s[i + 1]
+    return lam, len(s) - 1 - i
+
+
+# ---------------------------------------------------------------------------------------------- latent statistics
+@pytest.mark.parametrize("case,kind", LF.cases())
+def test_latent_stats_are_the_fp64_statistics_of_the_posterior(case, kind):
+    g, model, batch, sch = _case(case, kind)
+    st = model.latent_stats([batch])
+    mean, pv = _posterior(model, batch)
+    want, kd = _stats64(mean, pv)
+    assert st.n_molecules == g.B and type(st.n_molecules) is int
+    assert st.n_active.dim() == 0 and st.n_active.dtype == torch.int32 and st.n_active.is_cuda
+    for what, w in zip(FIELDS, want):
+        a = getattr(st, what)
+        assert a.shape == (g.latent,) and a.dtype == torch.float32 and a.is_cuda and not a.requires_grad
+        e = rel_err(_np(a), w)
+        print("%s %s %s: %.3e" % (case, kind, what, e))
+        assert e < PARITY, (what, e)
+    # active units: thresholds the fp64 variances are clear of
+    v = np.sort(want[2])
+    i = int(np.argmax((v[1:] - v[:-1]) / np.maximum(v[1:], 1e-300)))
+    thr = float(np.float32(0.5 * (v[i] + v[i + 1])))
+    assert (np.abs(want[2] - thr) >= 1e-3 * np.maximum(want[2], thr)).all()
+    assert int(model.latent_stats([batch], au_threshold=thr).n_active) == g.latent - 1 - i
+    if (np.abs(want[2] - 0.01) >= 1e-3 * np.maximum(want[2], 0.01)).all():
+        assert int(st.n_active) == int((want[2] > 0.01).sum())
+    # the per-dimension KL adds up to log_likelihood's per-molecule KL
+    ll = model.log_likelihood(batch, n_samples=1, seed=SEED, schedule=sch)
+    a, b = float(_np(st.kl_dims).sum() * g.B), float(_np(ll.kl).sum())
+    print("%s %s: sum kl_dims * B %.9g, sum kl %.9g" % (case, kind, a, b))
+    assert abs(a - b) <= PARITY * abs(b) and abs(b - float(kd.sum())) <= PARITY * abs(b)
+
+
+@pytest.mark.parametrize("case,kind", FOUR)
+def test_two_passes_over_a_batch_and_an_accumulator_read_in_between(case, kind):
+    g, model, batch, sch = _case(case, kind)
+    one, two = model.latent_stats([batch]), model.latent_stats([batch, batch])
+    assert two.n_molecules == 2 * one.n_molecules == 2 * g.B
+    mean, _ = _posterior(model, batch)
+    m = _np(mean)
+    for what in FIELDS:
+        a, b = _np(getattr(two, what)), _np(getattr(one, what))
+        bound = 2 * U * np.abs(b)
+        if what in ("mu_var", "agg_var"):       # E[m^2] - mu^2 in fp64: relative to E[m^2] (2 B + 16 additions), + the rounding
+            bound = bound + 2 * 4 * (2 * g.B + 16) * 2.0 ** -52 * (m * m).mean(axis=0)
+        print("%s %s %s, two passes against one: %.3e (bound %.3e)" % (case, kind, what, np.abs(a - b).max(), bound.max()))
+        assert (np.abs(a - b) <= bound).all(), what
+    assert int(two.n_active) == int(one.n_active)
+    # update, read, update, read
+    acc = model.latent_accumulator()
+    assert acc.result().n_molecules == 0 and not bool(acc.result().kl_dims.ne(0).any()) and int(acc.result().n_active) == 0
+    first = acc.update(batch).result()
+    second = acc.update(batch).result()
+    for what in FIELDS + ("n_active",):
+        assert torch.equal(getattr(first, what), getattr(one, what)), what
+        assert torch.equal(getattr(second, what), getattr(two, what)), what
+    assert (first.n_molecules, second.n_molecules) == (g.B, 2 * g.B)
+
+
+def test_a_model_with_active_dropout_is_refused():
+    g, model, batch, sch = _case("ll_hier_gru_s40", "hier-prop")
+    m2 = g.model("hier-prop", dropout=0.1).to(DEV)
+    m2.train()
+    with pytest.raises(NotImplementedError, match=r"latent_stats runs without dropout: call model\.eval\(\) first"):
+        m2.latent_stats([batch])
+    with pytest.raises(NotImplementedError, match=r"runs without dropout"):
+        m2.latent_accumulator()
+    acc = m2.eval().latent_accumulator()
+    m2.train()
+    with pytest.raises(NotImplementedError, match=r"runs without dropout"):
+        acc.update(batch)
+    assert acc.n_molecules == 0 and not bool(acc.acc.ne(0).any())
+
+
+# ---------------------------------------------------------------------------------------------- free bits
+@pytest.mark.parametrize("K", [1, 2])
+@pytest.mark.parametrize("case,kind", FOUR)
+def test_free_bits_zero_is_the_elbo(case, kind, K):
+    g, model, batch, sch = _case(case, kind)
+    for weighted in (False, True):
+        kw = dict(n_samples=K, objective="elbo", beta=BETA, mol_weights=_weights(g, weighted), seed=SEED, schedule=sch)
+        want_loss, want = _step(model, lambda: model.bound_loss(batch, **kw)[0])
+        got_loss, got = _step(model, lambda: model.bound_loss(batch, free_bits=0.0, **kw)[0])
+        print("%s %s K %d w %d: loss %.9g, free_bits=None %.9g" % (case, kind, K, weighted, float(got_loss), float(want_loss)))
+        assert abs(float(got_loss) - float(want_loss)) <= PARITY * abs(float(want_loss))
+        _check_grads(got, want, "%s %s K %d w %d free_bits 0 against None" % (case, kind, K, weighted))
+    model.zero_grad(set_to_none=True)
+
+
+@pytest.mark.parametrize("case,kind", FOUR)
+def test_all_dimensions_free_is_the_loss_without_kl_plus_a_constant(case, kind):
+    g, model, batch, sch = _case(case, kind)
+    kw = dict(n_samples=2, objective="elbo", mol_weights=_weights(g, True), seed=SEED, schedule=sch)
+    _, info = model.bound_loss(batch, beta=BETA, free_bits=0.0, **kw)
+    fb = float(np.float32(2 * float(info.kl_dims.max()) + 1))
+    want_loss, want = _step(model, lambda: model.bound_loss(batch, beta=0.0, **kw)[0])
+    got_loss, got = _step(model, lambda: model.bound_loss(batch, beta=BETA, free_bits=fb, **kw)[0])
+    ref = float(want_loss) + BETA * g.latent * fb
+    print("%s %s: loss %.9g, beta=0 loss + beta L free_bits %.9g" % (case, kind, float(got_loss), ref))
+    assert abs(float(got_loss) - ref) <= PARITY * abs(ref)
+    _check_grads(got, want, "%s %s all free against beta 0" % (case, kind))
+    print("%s %s: gradients bitwise equal to the beta=0 run: %s" % (case, kind, all(torch.equal(got[k], want[k]) for k in want)))
+    model.zero_grad(set_to_none=True)
+
+
+@pytest.mark.parametrize("weighted", [False, True])
+@pytest.mark.parametrize("case,kind", FOUR)
+def test_a_midpoint_lambda_against_the_composite_of_existing_pieces(case, kind, weighted):
+    g, model, batch, sch = _case(case, kind)
+    w = _weights(g, weighted)
+    kw = dict(n_samples=2, objective="elbo", mol_weights=w, seed=SEED, schedule=sch)
+    _, info = model.bound_loss(batch, beta=BETA, free_bits=0.0, **kw)
+    lam, n_open = _midpoint(info.kl_dims)
+    assert 0 < n_open < g.latent
+    wt = None if w is None else torch.tensor(w, dtype=torch.float32, device=DEV)
+
+    # the composite: bound_loss(beta=0) and the term in torch ops, as two passes that add into .grad
+    model.zero_grad(set_to_none=True)
+    l0 = model.bound_loss(batch, beta=0.0, **kw)[0]
+    l0.backward()
+    torch.cuda.synchronize()
+    base = {k: p.grad.clone() for k, p in model.named_parameters() if p.grad is not None}
+    term, klbar = _fb_term(*_posterior(model, batch, grad=True), wt, lam)
+    assert int((klbar > lam).sum()) == n_open
+    (BETA * term).backward()
+    torch.cuda.synchronize()
+    want = {k: p.grad.clone() for k, p in model.named_parameters() if p.grad is not None}
+    want_loss = float(l0.detach()) + BETA * float(term.detach())
+
+    got_loss, got = _step(model, lambda: model.bound_loss(batch, beta=BETA, free_bits=lam, **kw)[0])
+    print("%s %s w %d lambda %.6g (%d of %d open): loss %.9g, composite %.9g" % (case, kind, weighted, lam, n_open, g.latent,
+                                                                               float(got_loss), want_loss))
+    assert abs(float(got_loss) - want_loss) <= PARITY * abs(want_loss)
+    _check_grads(got, want, "%s %s w %d midpoint against the composite" % (case, kind, weighted))
+
+    # the latent heads' share of the held KL by itself, against torch fp64 on the CPU
+    from ggpm_amd.nnutils import make_cuda
+    with torch.no_grad():
+        h = model._encode(make_cuda(batch[2]))[:, :model.R_mean.weight.shape[1]].double().cpu()
+    P64 = {k: dict(model.named_parameters())[k].detach().double().cpu().requires_grad_(True) for k in HEADS}
+    t64, _ = _fb_term(TF.linear(h, P64["R_mean.weight"], P64["R_mean.bias"]), TF.linear(h, P64["R_var.weight"], P64["R_var.bias"]),
+                      None if w is None else torch.tensor(w, dtype=torch.float64), lam)
+    (BETA * t64).backward()
+    for k in HEADS:
+        a, r = _np(got[k]) - _np(base[k]), P64[k].grad.numpy()
+        e = rel_err(a, r)
+        print("%s %s w %d d%s, the held KL's share: %.3e" % (case, kind, weighted, k, e))
+        assert e < PARITY, (k, e)
+    model.zero_grad(set_to_none=True)
+
+
+@pytest.mark.parametrize("case,kind", LF.cases())
+def test_info_with_free_bits(case, kind):
+    from ggpm_amd.property_vae import FreeBitsObjective, MolObjective
+    g, model, batch, sch = _case(case, kind)
+    kw = dict(n_samples=g.K, objective="elbo", beta=BETA, seed=SEED, schedule=sch)
+    _, plain = model.bound_loss(batch, **kw)
+    loss, info = model.bound_loss(batch, free_bits=0.25, **kw)
+    assert type(plain) is MolObjective and isinstance(info, MolObjective) and type(info) is FreeBitsObjective and len(info) == 7
+    parts, kl, elbo, iwae, z, weights, stats = info                      # existing unpacking keeps working
+    for what in ("parts", "kl", "elbo", "iwae", "z", "weights"):
+        a = getattr(info, what)
+        assert torch.equal(a, getattr(plain, what)), what
+        assert not a.requires_grad and a.dtype == torch.float32
+    assert info.stats == plain.stats and sorted(info.stats) == ["atom_level_calls", "decoder_passes", "encoder_calls"]
+    assert all(type(v) is int for v in info.stats.values())
+    assert info.free_bits == 0.25 and type(info.free_bits) is float
+    assert info.kl_dims.shape == (g.latent,) and info.kl_dims.dtype == torch.float32 and not info.kl_dims.requires_grad
+    assert loss.dim() == 0 and loss.requires_grad
+    a, b = float(_np(info.kl_dims).sum() * g.B), float(_np(info.kl).sum())
+    assert abs(a - b) <= PARITY * abs(b)
+    # without backward nothing gains a .grad; the same call twice is bitwise the same
+    loss2, info2 = model.bound_loss(batch, free_bits=0.25, **kw)
+    assert torch.equal(loss.detach(), loss2.detach()) and torch.equal(info.kl_dims, info2.kl_dims)
+    assert all(p.grad is None for p in model.parameters())
+
+
+@pytest.mark.parametrize("side", ["0", "1"])
+@pytest.mark.parametrize("case,kind", [("ll_hier_lstm_s41", "hier-prop-opt"), ("ll_motif_lstm_s61", "prop-opt")])
+def test_a_second_step_adds_into_grad(case, kind, side, monkeypatch):
+    """no zero_grad between two bound_loss(free_bits=) + backward: every .grad is the sum of the two single-pass gradients
+    within PARITY (tied embedding tables included), and stays the tensor it was"""
+    monkeypatch.setenv("GGPM_SIDE_STREAM", side)
+    g, model, batch, sch = _case(case, kind)
+    kw = dict(n_samples=2, objective="elbo", beta=BETA, mol_weights=_weights(g, True), seed=SEED, schedule=sch)
+    _, info = model.bound_loss(batch, free_bits=0.0, **kw)
+    lam, _ = _midpoint(info.kl_dims)
+    fn = lambda: model.bound_loss(batch, free_bits=lam, **kw)[0]
+    _, once = _step(model, fn)
+    held = {k: p.grad for k, p in model.named_parameters() if p.grad is not None}
+    fn().backward()
+    torch.cuda.synchronize()
+    twice = {}
+    for k, p in model.named_parameters():
+        if k in once:
+            assert p.grad is held[k], k
+            twice[k] = p.grad.clone()
+    _check_grads(twice, {k: 2 * v for k, v in once.items()}, "%s %s side %s two passes against twice one" % (case, kind, side))
+    model.zero_grad(set_to_none=True)
+
+
+@pytest.mark.parametrize("case,kind", [("ll_hier_gru_s40", "hier-prop"), ("ll_motif_lstm_s61", "prop-opt")])
+def test_second_backward_raises(case, kind):
+    g, model, batch, sch = _case(case, kind)
+    model.zero_grad(set_to_none=True)
+    loss, _ = model.bound_loss(batch, n_samples=2, beta=BETA, free_bits=0.1, seed=SEED, schedule=sch)
+    loss.backward(retain_graph=True)
+    with pytest.raises(RuntimeError, match="a retained graph is not supported"):
+        loss.backward()
+    torch.cuda.synchronize()
+    model.zero_grad(set_to_none=True)
+
+
+def test_argument_errors():
+    g, model, batch, sch = _case("ll_hier_gru_s40", "hier-prop")
+    with pytest.raises(ValueError, match="free_bits"):
+        model.bound_loss(batch, objective="iwae", free_bits=0.1, schedule=sch)
+    for bad in (-0.1, float("nan"), float("inf")):
+        with pytest.raises(ValueError, match="free_bits"):
+            model.bound_loss(batch, free_bits=bad, schedule=sch)
+    with pytest.raises(ValueError, match="objective"):                       # what was refused before still is
+        model.bound_loss(batch, objective="free_bits", schedule=sch)
+    with pytest.raises(ValueError, match="au_threshold"):
+        model.latent_accumulator(au_threshold=float("nan"))
+    assert all(p.grad is None for p in model.parameters())
