@@ -149,6 +149,8 @@ SIGNATURES = {
     "ggpm_linear_wgrads_batch": (I, [I, P, P, c_size_t, P, P]),
     "ggpm_timing_enable": (I, [I]),
     "ggpm_timing_collect": (I, [I, POINTER(c_int), POINTER(c_double), POINTER(c_double)]),
+    # the device gate functions as the level kernels compile them (csrc/capi.hip; tests/test_gate_math_gpu.py)
+    "ggpm_selftest_gate_math": (I, [I, P, I, P, P]),
     # host-only decode schedule (csrc/schedule.hip): in: ggpm_sched_in*
     "ggpm_schedule_build": (P, [P]),
     "ggpm_schedule_get": (I, [P, c_char_p, POINTER(c_void_p), POINTER(ctypes.c_int64), POINTER(c_int), POINTER(c_int),

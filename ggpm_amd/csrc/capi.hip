@@ -26,6 +26,30 @@ extern "C" int ggpm_level_form_query(int lstm, int E1, int H, int sparse, int tr
     return lstm ? ggpm_lstm_level_form(E1, H, sparse, training, o, out) : ggpm_gru_level_form(E1, H, sparse, training, o, out);
 }
 
+// ---------------------------------------------------------------- gate-function self-test (tests only)
+// The device gate functions of common.h AS THE LEVEL KERNELS COMPILE THEM (this header, these flags, any ablation switch
+// of the build), one argument per thread: what tests/test_gate_math_gpu.py measures against fp64.
+namespace {
+template <int WHICH>
+__global__ void __launch_bounds__(256) gate_math_kernel(const float* __restrict__ x, int n, float* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float v = x[i];
+    out[i] = WHICH == 0 ? ggpm_fsigmoid<false>(v) : WHICH == 1 ? ggpm_fsigmoid<true>(v) : ggpm_sigmoid(v);
+}
+}  // namespace
+
+extern "C" int ggpm_selftest_gate_math(int which, const float* x, int n, float* out, ggpm_stream_t stream) {
+    if (which < 0 || which > 2 || n < 0 || n > (1 << 30) || (n > 0 && (!x || !out))) return GGPM_ERR_ARG;
+    if (n == 0) return GGPM_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid(ggpm_ceil_div(n, 256)), block(256);
+    if (which == 0) hipLaunchKernelGGL(gate_math_kernel<0>, grid, block, 0, s, x, n, out);
+    else if (which == 1) hipLaunchKernelGGL(gate_math_kernel<1>, grid, block, 0, s, x, n, out);
+    else hipLaunchKernelGGL(gate_math_kernel<2>, grid, block, 0, s, x, n, out);
+    return hipGetLastError() == hipSuccess ? GGPM_OK : GGPM_ERR_LAUNCH;
+}
+
 // ---------------------------------------------------------------- timing sink (debug/bench only)
 namespace {
 struct Span { hipEvent_t a, b; double flops; };

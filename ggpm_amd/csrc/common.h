@@ -117,15 +117,23 @@ __device__ __forceinline__ float4 ggpm_zero4() { return make_float4(0.f, 0.f, 0.
 // to fp64 on the deciding configs[4] tensors).
 __device__ __forceinline__ float ggpm_fsigmoid_fast(float x) { return __frcp_rn(1.0f + __expf(-x)); }
 // ACCURATE (shipped, every gate mode): measured mean 0.42 ulp, 6.9 % above 1 ulp, worst 3.4 ulp -- at |x| ~ 16.7, where 1 + e itself
-// rounds -- against 0.40 / 5.3 % / 2.5 for libm expf + IEEE division, in 11 instructions instead of ~35 (and FEWER issue
+// rounds -- against 0.40 / 5.3 % / 2.5 for libm expf + IEEE division, in 12 instructions instead of ~35 (and FEWER issue
 // slots than the fast form, whose __expf carries denormal-range handling: 2.57 against 3.82 ms for 2^33 evaluations):
 //   t = -x * log2e as a two-term product t_hi + t_lo (log2e = L_hi + L_lo, the rounding of the leading product recovered by
 //   fma); exp2(t_hi) on v_exp_f32 -- the unit's own range reduction of the ROUNDED argument is exact --, times
 //   2^t_lo = 1 + t_lo ln2 (|t_lo| < 2^-17: first order is exact to 2^-35); then 1 / (1 + e) as v_rcp_f32 + one Newton step.
 //   |x| is clamped to 88 first so that e stays finite (inf * 0 in the correction would be NaN); sigmoid(+-88) is 1 / 6e-39.
+//   The clamp PROPAGATES NaN: IEEE 754-2019 minimum / maximum, one v_minimum3_f32 and one v_maximum3_f32 on gfx950 (12
+//   instructions), and a NaN then runs through every later step.  It was one v_med3_f32, which answers a NaN operand with the
+//   smallest of the three (fminf / fmaxf drop NaN as well, in any order): a NaN argument came out as sigmoid(-88) ~ 0, and a NaN
+//   confined to W_r / U_r / b_u / W_f never reached h.  Every other argument gives the bits it gave before.
+//   The suite measures both forms through ggpm_selftest_gate_math (tests/test_gate_math_gpu.py; its 1.7 M arguments hold every
+//   float of |x| in [16.5, 17], the worst region, so its means are higher than the probe's): accurate 0.49 ulp mean, 8.0 %
+//   above 1 ulp, worst 3.46 at x = -16.654; libm 0.47 / 6.7 % / 2.62 at x = -16.678.  Cost of the second instruction, and of
+//   the v_cmp_u_f32 + v_cndmask_b32 form it was measured against: DESIGN 13.4.
 __device__ __forceinline__ float ggpm_fsigmoid_acc(float x) {
     const float L_hi = 1.44269502162933349609375f, L_lo = 1.925963033500011e-08f, LN2 = 0.693147182464599609375f;
-    const float nx = -__builtin_amdgcn_fmed3f(x, -88.f, 88.f);
+    const float nx = -__builtin_elementwise_maximum(__builtin_elementwise_minimum(x, 88.f), -88.f);
     const float t = nx * L_hi;
     float lo = __builtin_fmaf(nx, L_hi, -t);
     lo = __builtin_fmaf(nx, L_lo, lo);

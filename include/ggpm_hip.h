@@ -1062,6 +1062,12 @@ int ggpm_encoder_backward(const ggpm_enc_dims* dims, float* const* params, float
 int ggpm_timing_enable(int on);
 int ggpm_timing_collect(int which, int* launches, double* total_ms, double* flops);
 
+/* ------------------------------------------------------------------ gate-function self-test (tests only)
+ * out[i] = f(x[i]) for n <= 2^30 device floats, f being a device gate function exactly as the level kernels compile
+ * it: which = 0 the gather sigmoid of the fp32 gate modes, 1 the gather sigmoid of the bf16 gate mode, 2 the libm
+ * sigmoid of the gate epilogues.  NaN arguments give NaN; -inf gives 0 (or a flushed denormal), +inf gives 1. */
+int ggpm_selftest_gate_math(int which, const float* x, int n, float* out, ggpm_stream_t stream);
+
 /* ------------------------------------------------------------------ decode schedule (host only, no GPU work)
  * The integer bookkeeping of the teacher-forced decoder for one tensorized batch, which the reference interleaves
  * with device work on every step of HierMPNDecoder.forward (ggpm/decoder.py:186-259: the per-step subtree / subgraph

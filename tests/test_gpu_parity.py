@@ -1682,6 +1682,64 @@ def test_softmax_ce_and_bce_kernels_against_torch(M, N, masked):
     assert float((s.grad - s2.grad).abs().max()) <= 2e-6
 
 
+def _loss_kernels_ce(x, labels, mask, mask_row):
+    """cross_entropy_sum on numpy inputs -> loss, the gradient of 1.7 x loss with respect to the logits"""
+    from ggpm_amd.decoder_heads import cross_entropy_sum
+    import loss_extreme_cases as L
+    xt = torch.from_numpy(x).to(_dev()).requires_grad_(True)
+    lab, mk, mr = (torch.from_numpy(a).to(_dev()) for a in (labels, mask, mask_row))
+    loss, _ = cross_entropy_sum(xt, lab, mask=mk, mask_row=mr)
+    (L.UPSTREAM * loss).backward()
+    return float(loss.detach()), xt.grad.cpu().numpy()
+
+
+@pytest.mark.parametrize("M,N", [(5, 64), (257, 33), (4, 2100)])
+def test_softmax_ce_and_bce_kernels_at_large_logits(M, N):
+    """The same kernels where logits are large (standard deviation 30 under mask rows of -1000; BCE at +-100) against
+    numpy fp64 at the same bars, 2e-5 relative on the loss and 2e-6 absolute on the gradient; torch's fp32 on the CPU
+    keeps half of them (tests/test_loss_extremes_cpu.py)."""
+    from ggpm_amd.decoder_heads import bce_with_logits_sum
+    import loss_extreme_cases as L
+    assert (M, N) in L.SHAPES
+    inputs = L.ce_inputs(M, N)
+    loss, grad = _loss_kernels_ce(*inputs)
+    ok_l, ok_g, dl, dg = L.within_bars(loss, grad, *L.ce_reference(*inputs))
+    print("softmax CE at large logits (%d, %d): loss off by %.2e of %.4g, gradient by %.2e" % (M, N, dl, loss, dg))
+    assert np.isfinite(loss) and np.isfinite(grad).all()
+    assert ok_l and ok_g
+    s, y = L.bce_inputs(max(M, 8))
+    st = torch.from_numpy(s).to(_dev()).requires_grad_(True)
+    l2 = bce_with_logits_sum(st, torch.from_numpy(y).to(_dev()))
+    l2.backward()
+    ok_l, ok_g, dl, dg = L.within_bars(float(l2.detach()), st.grad.cpu().numpy(), *L.bce_reference(s, y))
+    print("BCE at +-100 (%d rows): loss off by %.2e of %.4g, gradient by %.2e" % (len(s), dl, float(l2.detach()), dg))
+    assert ok_l and ok_g
+
+
+def test_softmax_ce_and_bce_kernels_propagate_nan():
+    """One NaN logit: the loss is NaN, the gradient is NaN in that row and untouched, bit for bit, in every other row
+    (nothing is asserted about that row's arg-max).  BCE likewise, element-wise."""
+    from ggpm_amd.decoder_heads import bce_with_logits_sum
+    import loss_extreme_cases as L
+    x, labels, mask, mask_row = L.ce_inputs(257, 33)
+    _, clean = _loss_kernels_ce(x, labels, mask, mask_row)
+    r = 130
+    bad = x.copy()
+    bad[r, (labels[r] + 5) % 33] = np.nan
+    loss, grad = _loss_kernels_ce(bad, labels, mask, mask_row)
+    assert np.isnan(loss) and np.isnan(grad[r]).all()
+    rest = np.arange(257) != r
+    assert np.isfinite(clean).all() and np.array_equal(grad[rest].view(np.uint32), clean[rest].view(np.uint32))
+    s, y = L.bce_inputs(257)
+    s[r] = np.nan
+    st = torch.from_numpy(s).to(_dev()).requires_grad_(True)
+    l2 = bce_with_logits_sum(st, torch.from_numpy(y).to(_dev()))
+    l2.backward()
+    g = st.grad.cpu().numpy()
+    assert np.isnan(float(l2.detach())) and np.isnan(g[r]) and np.isfinite(g[rest]).all()
+    assert np.abs(g[rest] - L.bce_reference(s, y)[1][rest]).max() <= L.GRAD_ATOL
+
+
 
 
 @pytest.mark.gpu

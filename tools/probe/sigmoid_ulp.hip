@@ -48,6 +48,9 @@ int main() {
     }
     for (float x = 0.25f; x < 16.f; x = nextafterf(x, 100.f) + 3e-6f * x) { xs.push_back(x); xs.push_back(-x); }
     for (float x : {0.f, -0.f, 88.f, -88.f, 100.f, -100.f, 1e30f, -1e30f, 1e-30f}) xs.push_back(x);
+    // NaN in, NaN out (the last column counts them: 2 for the accurate and the libm form; the suite asserts it,
+    // tests/test_gate_math_gpu.py)
+    for (float x : {nanf(""), -nanf("")}) xs.push_back(x);
     const int n = (int)xs.size();
     float *dx, *d0, *d1, *d2;
     hipMalloc(&dx, n * 4); hipMalloc(&d0, n * 4); hipMalloc(&d1, n * 4); hipMalloc(&d2, n * 4);
