@@ -3,7 +3,9 @@
 None of these is an environment switch.  Every default is the measured-fastest form (DESIGN.md sections 6, 8, 9 carry the
 figures); a test or a tool under ``tools/`` changes an attribute here (``monkeypatch.setattr(_dev, "ATOM_COMPACT", False)``)
 to run the other form against the same fixtures; every module reads these attributes at CALL time (none copies one
-into a module global at import), so a change made after the package was imported takes effect.  The runtime switches a user of the package sees are the few in
+into a module global at import), so a change made after the package was imported takes effect.  What a switch selects
+travels by value from there on: the atom level issued ahead is the handle ``start_atom_level`` returns, "beside the atom
+level" is the encoder's ``beside=`` argument.  The runtime switches a user of the package sees are the few in
 README.md; the compile-time tuning switches of the kernels live in the ``dev`` variant of the library
 (``python -m ggpm_amd.build --variant dev -DGGPM_DEV_SWITCHES``, csrc/common.h: ggpm_dev_env).
 """

@@ -442,7 +442,6 @@ def _decode_steps(plan: "AtomPlan", D, ct, cp, H: int, depth: int, lstm: bool):
 # the same time and would otherwise issue one chain only after the other, although they do not depend on each other.
 # What follows a loop on its stream (read-out / parameter gradients) is enqueued after ggpm_decode_join.
 _INFLIGHT: list = []         # buffers named by loops the worker may still be issuing (released by the next join)
-_PENDING: dict = {}          # id(plan) -> the forward's `finish` closure, taken by atom_decode()
 
 
 def _join_worker(what: str) -> None:
@@ -727,15 +726,11 @@ class _AtomDecodeCompact(torch.autograd.Function):
                                 stream=s)
         pooled, cand, NODE, NEI, finish = _readout_stage(plan, cp, Hs_all, _vp(cp["agr_col"]), fn_all, Wout, bout, Fdim, H, drop,
                                                          deferred, "decode_join (forward)")
-        return dict(pooled=pooled, cand=cand, finish=finish, keep=(D, ct, cp), lstm=lstm,
+        return dict(pooled=pooled, cand=cand, finish=finish, keep=(D, ct, cp),
                     saved=(fn_all, hmess, NODE, NEI, X_all, Hs_all, Qs_all, St_all) + ((Cs_all,) if lstm else ()))
 
     @staticmethod
     def forward(ctx, plan: AtomPlan, cell: str, depth: int, H: int, Fdim: int, I: int, fn_all, hmess, drop, state, *params):
-        if state is None:
-            state = _AtomDecodeCompact.launch(plan, cell, depth, H, Fdim, I, fn_all, hmess, drop, params)
-            if state["finish"] is not None:
-                _PENDING[id(plan)] = state["finish"]
         ctx.plan, ctx.meta, ctx.drop = plan, (cell, depth, H, Fdim, I), drop
         ctx.save_for_backward(*state["saved"], *params)
         ctx.keep = state["keep"]
@@ -943,7 +938,7 @@ def _launch_infer(plan: AtomPlan, kind: str, depth: int, H: int, Fdim: int, I: i
                             save=False, opts=opts, stream=s)
     pooled, cand, _, _, finish = _readout_stage(plan, cp, F_h, P(agr_col), fn_all, Wout, bout, Fdim, H, drop, deferred,
                                                 "decode_join (forward-only)")
-    return dict(pooled=pooled, cand=cand, finish=finish, keep=(D, ct, cp), lstm=lstm, saved=None, infer=True)
+    return dict(pooled=pooled, cand=cand, finish=finish)
 
 
 def _param_grads(cell, Wout, acc, dX_tot, hmess, DPRE, NEI, fn_all, Fdim, E1, ns_tot, bufs=None):
@@ -969,24 +964,36 @@ def _param_grads(cell, Wout, acc, dX_tot, hmess, DPRE, NEI, fn_all, Fdim, E1, ns
     return cell.grads(bufs, acc, dbs) + (dWout, dbout)
 
 
-def atom_decode_node(pre: dict):
-    """The autograd node of a prelaunched atom level (``atom_decode(..., prelaunch=True)``), created where the decoder
-    joins it: -> (pooled, cand).  Joins the worker and enqueues the read-out first."""
-    fin = pre["state"]["finish"]
-    if fin is not None:
-        fin()
-        pre["state"]["finish"] = None
-    if pre["state"].get("infer"):          # forward-only: no node (the worker is joined above)
-        return pre["state"]["pooled"], pre["state"]["cand"]
-    return _AtomDecodeCompact.apply(*pre["args"], pre["state"], *pre["params"])
+class AtomRun:
+    """One issued atom level: its launch stream, its two result tensors and what is still owed on them -- ``finish`` (the
+    worker's join and the read-out behind the step loop, or None) and ``node`` = (args, state, params) of the
+    ``_AtomDecodeCompact`` node where autograd records (None for the forward-only form and for ``_AtomDecode``, whose
+    node is made at launch)."""
+
+    def __init__(self, stream, pooled, cand, finish=None, node=None):
+        self.stream, self.pooled, self.cand = stream, pooled, cand
+        self._finish, self._node = finish, node
+
+    def join(self):
+        """-> (pooled, cand), ready for the launch stream's next reader.  The first call pays what is owed, inside the
+        launch stream (the node's backward runs on the stream of its forward), and drops the closure and the state."""
+        finish, node = self._finish, self._node
+        self._finish = self._node = None
+        if finish is not None or node is not None:
+            with torch.cuda.stream(self.stream):
+                if finish is not None:
+                    finish()
+                if node is not None:
+                    args, state, params = node
+                    self.pooled, self.cand = _AtomDecodeCompact.apply(*args, state, *params)
+        return self.pooled, self.cand
 
 
-def atom_decode(plan: AtomPlan, graph_encoder, hnode_a: torch.Tensor, hmess_a: torch.Tensor, fn_all: torch.Tensor,
-                defer_finish: bool = False, prelaunch: bool = False):
-    """-> (pooled [n_inst, Hp], cand [n_cand, Hp]) for ``graph_encoder`` = the decoder's atom-level ``IncMPNEncoder``.
-    ``defer_finish``: -> (pooled, cand, finish); the caller calls ``finish()`` before it reads the two tensors or lets any
-    other stream wait on the current one (with _dev.ATOM_ASYNC the step loop is still being issued by a worker thread
-    when this returns, and the read-out behind it is enqueued by ``finish``)."""
+def atom_decode_launch(plan: AtomPlan, graph_encoder, hnode_a: torch.Tensor, hmess_a: torch.Tensor,
+                       fn_all: torch.Tensor) -> AtomRun:
+    """Issues the atom level of ``graph_encoder`` = the decoder's atom-level ``IncMPNEncoder`` on the current stream.
+    With _dev.ATOM_ASYNC the step loop is still being issued by a worker thread when this returns: ``AtomRun.join``
+    comes before anything reads the two tensors or another stream waits on this one."""
     from .rnn import LSTM
     rnn, wo = graph_encoder.rnn, graph_encoder.W_o
     lstm, params = isinstance(rnn, LSTM), rnn.level_params()
@@ -1003,29 +1010,18 @@ def atom_decode(plan: AtomPlan, graph_encoder, hnode_a: torch.Tensor, hmess_a: t
     args = (plan, "LSTM" if lstm else "GRU", rnn.depth, rnn.hidden_size, graph_encoder.node_fdim, rnn.input_size, fn_all,
             hmess_a, drop)
     params = params + (wo[0].weight, wo[0].bias)
-    # a call autograd will not record runs the forward-only form, which makes no node and joins the worker before the
-    # caller reads its results (``finish``): nothing is left in _PENDING / _INFLIGHT for a backward to collect
+    # a call autograd will not record runs the forward-only form, which makes no node: once joined, nothing of it is left
+    # in _INFLIGHT for a backward to collect
     infer = not fused.records_grad(params + (fn_all, hmess_a))
-    if prelaunch:           # issue now, create the autograd node later (atom_decode_node)
-        assert fn is _AtomDecodeCompact
-        with torch.no_grad():
-            return dict(args=args, params=params, state=fn.launch(*args, params, infer=infer))
-    if infer:
-        if fn is _AtomDecode:
-            pooled, cand, _, _ = _full_level(*args, params, infer=True)
-            finish = None
-        else:
-            st = fn.launch(*args, params, infer=True)
-            pooled, cand, finish = st["pooled"], st["cand"], st["finish"]
-        if defer_finish:
-            return pooled, cand, (finish or (lambda: None))
-        if finish is not None:
-            finish()
-        return pooled, cand
-    pooled, cand = fn.apply(*args, *params) if fn is _AtomDecode else fn.apply(*args, None, *params)
-    finish = _PENDING.pop(id(plan), None)        # set when the step loop was handed to the library's worker thread
-    if defer_finish:
-        return pooled, cand, (finish or (lambda: None))
-    if finish is not None:
-        finish()
-    return pooled, cand
+    stream = torch.cuda.current_stream(hmess_a.device)
+    if fn is _AtomDecode:
+        pooled, cand = _full_level(*args, params, infer=True)[:2] if infer else fn.apply(*args, *params)
+        return AtomRun(stream, pooled, cand)
+    with torch.no_grad():
+        state = fn.launch(*args, params, infer=infer)
+    return AtomRun(stream, state["pooled"], state["cand"], state.pop("finish"), None if infer else (args, state, params))
+
+
+def atom_decode(plan: AtomPlan, graph_encoder, hnode_a: torch.Tensor, hmess_a: torch.Tensor, fn_all: torch.Tensor):
+    """-> (pooled [n_inst, Hp], cand [n_cand, Hp]): ``atom_decode_launch`` joined at once."""
+    return atom_decode_launch(plan, graph_encoder, hnode_a, hmess_a, fn_all).join()

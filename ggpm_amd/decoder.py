@@ -16,6 +16,7 @@ from __future__ import annotations
 
 from typing import Dict, List, Optional, Sequence, Tuple
 
+import collections
 import contextlib
 import os
 import weakref
@@ -31,6 +32,10 @@ from . import inc_encoder as IE
 from .decoder_heads import ScoreHeads, _gemm_rows, _i32, _memo, bce_with_logits_sum, check_no_dropout, cross_entropy_sum
 
 MAX_POS = 20
+
+# what HierMPNDecoder.start_atom_level hands to forward(atom=): the schedule, its issued atom level (atom_decode.AtomRun)
+# and the stream it was issued on
+AtomAhead = collections.namedtuple("AtomAhead", "schedule run side")
 
 
 class DecodeSchedule:
@@ -586,7 +591,8 @@ class HierMPNDecoder(ScoreHeads):
         return self.enum_attach_batched(hgraph.node, k, c.reshape(-1), ic, nth)[:, :self.hidden_size]
 
     # ------------------------------------------------------------------ forward
-    def forward(self, mols, src_mol_vecs, graphs, tensors, orders, schedule: Optional[DecodeSchedule] = None):
+    def forward(self, mols, src_mol_vecs, graphs, tensors, orders, schedule: Optional[DecodeSchedule] = None, atom=None):
+        """``atom``: what ``start_atom_level`` returned for ``schedule`` (None: the atom level is issued here)."""
         tree_tensors, graph_tensors = tensors
         B = len(orders)
         dev = tree_tensors[0].device
@@ -594,14 +600,16 @@ class HierMPNDecoder(ScoreHeads):
             schedule = DecodeSchedule.from_graphs(graphs, tensors, orders, self.vocab, **self.schedule_hints())
         D = schedule.to_device(dev)._dev
         src_root_vecs, src_tree_vecs, src_graph_vecs = src_mol_vecs
+        if atom is not None and atom.schedule is not schedule:
+            atom.run.join()                          # (the worker drains)
+            raise ValueError("HierMPNDecoder.forward: atom= is the handle of another schedule's atom level")
         init_vecs = self._init_vecs(src_root_vecs)
-        self._heads_in = None
-        if self._batched_schedule(schedule):
-            topo_vecs, cls_vecs, assm_vecs, assm_dest = self._states_batched(schedule, D, tree_tensors, graph_tensors,
-                                                                            init_vecs)
+        if self._batched_schedule(schedule):         # (as every schedule start_atom_level posts)
+            topo_vecs, cls_vecs, assm_vecs, assm_dest, heads_in = self._states_batched(schedule, D, tree_tensors, graph_tensors,
+                                                                                      init_vecs, atom=atom)
         else:
             topo_vecs, cls_vecs, assm_vecs, assm_dest = self._states_stepwise(D, tree_tensors, graph_tensors, init_vecs)
-        heads_in, self._heads_in = self._heads_in, None
+            heads_in = None
         if heads_in is not None and src_tree_vecs is src_graph_vecs:
             return self._losses_composite(schedule, D, src_tree_vecs, topo_vecs, cls_vecs, heads_in, B, dev)
         if heads_in is not None:                     # (distinct tree / graph context vectors: the op-by-op heads)
@@ -650,8 +658,7 @@ class HierMPNDecoder(ScoreHeads):
             return None
         with contextlib.nullcontext() if record_grad else torch.no_grad():
             D = schedule.to_device(tree_tensors[0].device)._dev
-            pooled_all, cand, _ = self._atom_level(schedule, D, graph_tensors)
-        return pooled_all, cand
+            return self._atom_level(schedule, D, graph_tensors).join()
 
     def molecule_losses(self, mols, src_mol_vecs, graphs, tensors, orders, schedule: Optional[DecodeSchedule] = None,
                         max_cls_size: Optional[int] = None, atom=None, out: Optional[torch.Tensor] = None):
@@ -691,10 +698,8 @@ class HierMPNDecoder(ScoreHeads):
         with contextlib.nullcontext() if record else torch.no_grad():
             D = schedule.to_device(dev)._dev
             init_vecs = self._init_vecs(src_root_vecs)
-            self._heads_in = None
-            topo_vecs, cls_vecs, _, _ = self._states_batched(schedule, D, tree_tensors, graph_tensors, init_vecs, atom=atom,
-                                                             heads_in_always=True)
-            (cand, blocks), self._heads_in = self._heads_in, None
+            topo_vecs, cls_vecs, _, _, (cand, blocks) = self._states_batched(schedule, D, tree_tensors, graph_tensors, init_vecs,
+                                                                             atom=atom, heads_in_always=True)
             spec = self._heads_spec(schedule, D, dev)
             P, C0 = spec["n_assm"], schedule.max_cls_size
             # the molecule of every attachment prediction (the schedule lists it once per padded row)
@@ -755,22 +760,23 @@ class HierMPNDecoder(ScoreHeads):
     # ---- the atom level ahead of the encoder ---------------------------------------------------------------------------
     # Teacher forcing makes the decoder's atom level (and its backward) independent of the latent vector: it reads the
     # molecule's own bonds and the decoder's parameters only.  ``start_atom_level`` therefore issues it on its own stream
-    # BEFORE the encoder runs (property_vae._VAE._encode), so that two chains of small latency-bound launches share the GPU
-    # instead of queueing behind each other; autograd runs a node's backward on the stream of its forward, so the backward
-    # overlaps the encoder's backward the same way.  _dev.ATOM_AHEAD = False switches it off.
+    # BEFORE the encoder runs (property_vae._VAE._encode_beside_atom_level), so that two chains of small latency-bound
+    # launches share the GPU instead of queueing behind each other; autograd runs a node's backward on the stream of its
+    # forward, so the backward overlaps the encoder's backward the same way.  The caller passes the handle it gets to
+    # ``forward(atom=)``: nothing is kept on the decoder.  _dev.ATOM_AHEAD = False switches it off.
     _ATOM_STREAMS = {}
 
-    def start_atom_level(self, schedule, tensors) -> bool:
-        self._atom_ahead = None
+    def start_atom_level(self, schedule, tensors) -> Optional["AtomAhead"]:
+        """-> the handle ``forward(..., schedule=schedule, atom=)`` joins, or None where the level is not issued ahead."""
         if schedule is None or not (_dev.ATOM_AHEAD and _dev.ATOM_DECODE and _dev.DECODER_BATCHED):
-            return False
+            return None
         tree_tensors, graph_tensors = tensors
         dev = tree_tensors[0].device
         if dev.type != "cuda" or not (schedule.plan["all_live"] and schedule.plan["E1"] > 1):
-            return False
+            return None
         ap = schedule.atom_plan(graph_tensors[0].size(0), graph_tensors[1].size(0))
         if not ap.ok:
-            return False
+            return None
         D = schedule.to_device(dev)._dev
         main = torch.cuda.current_stream(dev)
         side = self._ATOM_STREAMS.get(dev.index)
@@ -780,36 +786,26 @@ class HierMPNDecoder(ScoreHeads):
             prio = -1 if _dev.ATOM_PRIORITY else 0
             side = self._ATOM_STREAMS[dev.index] = torch.cuda.Stream(device=dev, priority=prio)
         side.wait_stream(main)
-        from .atom_decode import compact_enabled
-        with torch.cuda.stream(side):
-            if compact_enabled():       # issued now; its autograd node is created at the join, behind the encoder's
-                pre = self._atom_level(schedule, D, graph_tensors, prelaunch=True)
-                self._atom_ahead = (schedule, None, None, side, None, pre)
-            else:
-                pooled_all, cand, _, finish = self._atom_level(schedule, D, graph_tensors, defer_finish=True)
-                self._atom_ahead = (schedule, pooled_all, cand, side, finish, None)
-        return True
+        with torch.cuda.stream(side):       # issued now; the compact form's autograd node is created at the join, behind the encoder's
+            return AtomAhead(schedule, self._atom_level(schedule, D, graph_tensors), side)
 
-    def _atom_level(self, schedule, D, graph_tensors, defer_finish: bool = False, prelaunch: bool = False):
-        """(pooled cluster vectors of all visits, attachment-candidate atom vectors, plan[, finish]) through atom_decode;
-        ``prelaunch``: -> the state ``atom_decode_node`` turns into the autograd node later."""
-        from .atom_decode import atom_decode
+    def _atom_level(self, schedule, D, graph_tensors):
+        """The atom level of ``schedule``, issued on the current stream -> its ``atom_decode.AtomRun``."""
+        from .atom_decode import atom_decode_launch
         hmpn, T = self.hmpn, D["plan"]
         graph_emb = hmpn.embed_graph(graph_tensors)
         fnode_all = graph_emb[0].index_select(0, T["atoms_all"])
         ap = schedule.atom_plan(graph_tensors[0].size(0), graph_tensors[1].size(0))
-        out = atom_decode(ap, hmpn.graph_encoder, graph_emb[0], graph_emb[1], fnode_all, defer_finish=defer_finish,
-                          prelaunch=prelaunch)
-        if prelaunch:
-            return out
-        return (out[0], out[1], ap) + tuple(out[2:])
+        return atom_decode_launch(ap, hmpn.graph_encoder, graph_emb[0], graph_emb[1], fnode_all)
 
     def _states_batched(self, schedule, D, tree_tensors, graph_tensors, init_vecs, atom=None, heads_in_always=False):
         """Same vectors as ``_states_stepwise`` with the two tree-side levels de-sequentialised: only the atom level
         (diterG interacting iterations per step) keeps the step loop; the attachment and motif levels are ONE call each
         over all their messages (a DAG in decode time, DecodeSchedule._level_plan) and ONE read-out over all visits.
-        ``atom``: the atom level's (pooled, cand) where the caller already has it (``atom_level``); ``heads_in_always``: hand
-        the candidates to the heads' one node whether or not it can record gradients (``molecule_losses``)."""
+        ``atom``: the atom level's (pooled, cand) where the caller already has it (``atom_level``), or the handle of
+        ``start_atom_level``, joined here; ``heads_in_always``: hand the candidates to the heads' one node whether or not it
+        can record gradients (``molecule_losses``).
+        -> (..., what that node takes in place of the attachment vectors: (cand, blocks), or None)"""
         hmpn, rnn_cell = self.hmpn, self.rnn_cell
         H, He, P, T = self.hidden_size, self.embed_size, schedule.plan, D["plan"]
         dev = tree_tensors[0].device
@@ -819,27 +815,17 @@ class HierMPNDecoder(ScoreHeads):
         hgraph = IE.HTuple(mess=rnn_cell.get_init_state(graph_tensors[1]))
         pooled, assm_vecs, assm_dest = [], [], []
         off, aoff, boff = P["inst_off"], P["atom_off"], P["bond_off"]
-        ahead, self._atom_ahead = getattr(self, "_atom_ahead", None), None
         ap = schedule.atom_plan(n_gnodes, graph_tensors[1].size(0)) if _dev.ATOM_DECODE else None
+        heads_in = None
         if ap is not None and ap.ok:                        # ---- atom level as ONE autograd node (atom_decode.py)
-            if atom is None and ahead is not None and ahead[0] is schedule:  # issued before the encoder on its own stream: join it here
-                _, pooled_all, cand, side, finish, pre = ahead
-                if pre is not None:                         # prelaunched: join the worker, read-out, autograd node NOW (on
-                    from .atom_decode import atom_decode_node          # the level's stream: its backward runs there)
-                    with torch.cuda.stream(side):
-                        pooled_all, cand = atom_decode_node(pre)
-                else:
-                    finish()                                # (worker-issued step loop: join it, enqueue the read-out behind it)
+            if isinstance(atom, AtomAhead):                 # issued before the encoder on its own stream: join it here --
+                pooled_all, cand = atom.run.join()          # worker, read-out, autograd node NOW, on the level's stream
                 main = torch.cuda.current_stream(dev)
-                main.wait_stream(side)
+                main.wait_stream(atom.side)
                 pooled_all.record_stream(main); cand.record_stream(main)
                 F_.mark("fwd: atom level joined")
             else:
-                if ahead is not None:                       # (a stale ahead run of another schedule: let its loop drain)
-                    stale = ahead[4] if ahead[5] is None else ahead[5]["state"]["finish"]
-                    if stale is not None:
-                        stale()
-                pooled_all, cand = atom if atom is not None else self._atom_level(schedule, D, graph_tensors)[:2]
+                pooled_all, cand = atom if atom is not None else self._atom_level(schedule, D, graph_tensors).join()
             meta = ap.to_device(dev)["meta"]
 
             def attach_rows():
@@ -848,10 +834,9 @@ class HierMPNDecoder(ScoreHeads):
                     assm_dest.append(meta[k]["dest"])
 
             from . import heads_fused
-            self._heads_in = None
             if heads_in_always or heads_fused.usable(self):       # enum_attach moves into the heads' one autograd node (heads_fused.py)
-                self._heads_in = (cand, [heads_fused.AssmBlock(k, base, n, meta[k]["icls"], meta[k]["nth"], meta[k]["dest"])
-                                         for k, base, n in ap.cand_blocks])
+                heads_in = (cand, [heads_fused.AssmBlock(k, base, n, meta[k]["icls"], meta[k]["nth"], meta[k]["dest"])
+                                    for k, base, n in ap.cand_blocks])
             else:
                 attach_rows()
             steps = []
@@ -906,7 +891,7 @@ class HierMPNDecoder(ScoreHeads):
                                               init_vecs.contiguous())
             cls_vecs = torch.cat([init_vecs, hid_t[:, :H].index_select(0, T["cls_mess"])], dim=0)
             F_.mark("fwd: tree-side levels issued")
-            return htree_node[:, :H], cls_vecs, assm_vecs, assm_dest
+            return htree_node[:, :H], cls_vecs, assm_vecs, assm_dest, heads_in
         # ---- attachment level (embed_sub_tree(is_inter_layer=True) + inter_encoder, ggpm/encoder.py:208-245)
         finput = IE._embedding_rows(hmpn.E_i, T["inst_attach"])
         hnode_i = hmpn.W_i[2](F_.linear([finput, pooled], [He, H], hmpn.W_i[0].weight, hmpn.W_i[0].bias, act=F_.ACT_RELU))
@@ -920,7 +905,7 @@ class HierMPNDecoder(ScoreHeads):
                                  T["dag_tree"], depth)
         htree_node = readout(hmpn.tree_encoder, hnode_t, h_t, T["in_tree"])
         cls_vecs = torch.cat([init_vecs, rnn_cell.get_hidden_state(h_t).index_select(0, T["cls_mess"])], dim=0)
-        return htree_node[:, :H], cls_vecs, assm_vecs, assm_dest
+        return htree_node[:, :H], cls_vecs, assm_vecs, assm_dest, heads_in
 
     def _assm_head(self, schedule, D, src_graph_vecs, assm_vecs, assm_dest, dev, want_scores=False):
         """(attachment loss, accuracy) of the batch -- ggpm/decoder.py:252-254, 276-281"""

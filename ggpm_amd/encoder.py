@@ -218,14 +218,15 @@ class HierMPNEncoder(nn.Module):
         return (self.E_c[0].weight, self.E_i[0].weight)
 
     def forward_padded(self, tree_tensors, graph_tensors, prep: Optional[PreparedBatch] = None,
-                       roots: Optional[torch.Tensor] = None):
+                       roots: Optional[torch.Tensor] = None, beside: bool = False):
+        """``beside``: this call runs beside another chain of launches (``fused.hier_encoder``; the op-by-op path has one form)."""
         if prep is None and self._fused_ok(tree_tensors, graph_tensors):
             from . import fused
             if roots is None:
                 roots = read_hint(tree_tensors[0], "ggpm_roots")         # make_cuda / DevicePrefetcher leave it there
                 if roots is None or roots.numel() != len(tree_tensors[-1]):
                     roots = _RING.upload([st for st, _ in tree_tensors[-1]], tree_tensors[0].device)
-            return fused.hier_encoder(self, tree_tensors, graph_tensors, roots)
+            return fused.hier_encoder(self, tree_tensors, graph_tensors, roots, beside)
         if prep is None:
             prep = PreparedBatch(tree_tensors, graph_tensors, roots)
         if prep.motif_csr is None:

@@ -76,14 +76,9 @@ def _side_ptr(device):
     return side, ctypes.c_void_p(side.cuda_stream)
 
 
-# True while the caller runs the encoder beside another chain of launches (property_vae: the decoder's atom level): the
-# level kernels then take half as many workgroups (ggpm_enc_dims.prefer_narrow), forwards and backwards.
-NARROW = [False]
-
-
 class _HierEncoder(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, dims: EncDims, tree_tensors, graph_tensors, roots, grad_sink, *params):
+    def forward(ctx, dims: EncDims, tree_tensors, graph_tensors, roots, grad_sink, beside, *params):
         lib = _lib.load()
         dev = params[0].device
         tfnode, tfmess, tagraph, tbgraph, tcgraph = [t.contiguous() for t in tree_tensors[:5]]
@@ -100,7 +95,6 @@ class _HierEncoder(torch.autograd.Function):
             saved.record_stream(side)
             roots.record_stream(side)
         P = F_._p
-        beside = bool(NARROW[0])
         dims.prefer_narrow = int(beside and _dev.ENC_NARROW in (True, "fwd"))
         _lib.check(lib.ggpm_encoder_forward(ctypes.byref(dims), _ptr_array(params), P(tfnode), P(tfmess), P(tagraph),
                                             P(tbgraph), P(tcgraph), P(gfnode), P(gfmess), P(gagraph), P(gbgraph),
@@ -169,7 +163,7 @@ class _HierEncoder(torch.autograd.Function):
             run(0)
         if accumulate:
             torch._foreach_add_(list(sink.encoder_views), grads)
-            return (None,) * (5 + len(params))
+            return (None,) * (6 + len(params))
         if sink is not None:
             # hand the gradients over in place: returning the buffer's own views would make autograd clone each one
             for p, v in zip(params, grads):
@@ -177,11 +171,11 @@ class _HierEncoder(torch.autograd.Function):
                     p.grad = v
                 elif p.grad.data_ptr() != v.data_ptr():
                     p.grad.add_(v)
-            return (None,) * (5 + len(params))
-        return (None, None, None, None, None, *grads)
+            return (None,) * (6 + len(params))
+        return (None, None, None, None, None, None, *grads)
 
 
-def _encoder_infer(dims: EncDims, tree_tensors, graph_tensors, roots, params):
+def _encoder_infer(dims: EncDims, tree_tensors, graph_tensors, roots, params, beside):
     """The forward-only form (ggpm_encoder_infer): the same outputs as _HierEncoder.forward, bit for bit, from an arena of
     ggpm_encoder_infer_bytes -- no stashes, no transposed CSRs -- that is free again as soon as the call returns."""
     lib = _lib.load()
@@ -199,7 +193,7 @@ def _encoder_infer(dims: EncDims, tree_tensors, graph_tensors, roots, params):
     if side is not None:
         arena.record_stream(side)
         roots.record_stream(side)
-    dims.prefer_narrow = int(bool(NARROW[0]) and _dev.ENC_NARROW in (True, "fwd"))
+    dims.prefer_narrow = int(beside and _dev.ENC_NARROW in (True, "fwd"))
     P = F_._p
     _lib.check(lib.ggpm_encoder_infer(ctypes.byref(dims), _ptr_array(params), P(tfnode), P(tfmess), P(tagraph), P(tbgraph),
                                       P(tcgraph), P(gfnode), P(gfmess), P(gagraph), P(gbgraph), P(roots), P(arena),
@@ -214,9 +208,11 @@ def records_grad(params) -> bool:
     return not _dev.FORWARD_ONLY or (torch.is_grad_enabled() and any(p.requires_grad for p in params))
 
 
-def hier_encoder(encoder, tree_tensors, graph_tensors, roots):
+def hier_encoder(encoder, tree_tensors, graph_tensors, roots, beside=False):
     """-> (hroot, hnode, hinter, hatom) as [rows, Hp] tensors; ``encoder`` is a HierMPNEncoder with GRU levels.  A call
-    autograd will not record runs the forward-only driver (``records_grad``)."""
+    autograd will not record runs the forward-only driver (``records_grad``).  ``beside``: the caller runs the encoder
+    beside another chain of launches (property_vae: the decoder's atom level) -- the level kernels then take half as many
+    workgroups (ggpm_enc_dims.prefer_narrow, _dev.ENC_NARROW), forwards and backwards."""
     from .rnn import LSTM
     lstm = isinstance(encoder.graph_encoder.rnn, LSTM)
     params = getattr(encoder, "_fused_params", None)
@@ -235,5 +231,5 @@ def hier_encoder(encoder, tree_tensors, graph_tensors, roots):
         seed = getattr(encoder, "_dropout_seed", None) or _dropout_seed()      # (tests pin the seed)
         dims.dropout, dims.seed_lo, dims.seed_hi = float(encoder.dropout), seed[0], seed[1]
     if not records_grad(params):
-        return _encoder_infer(dims, tree_tensors, graph_tensors, roots, params)
-    return _HierEncoder.apply(dims, tree_tensors, graph_tensors, roots, getattr(encoder, "_grad_sink", None), *params)
+        return _encoder_infer(dims, tree_tensors, graph_tensors, roots, params, beside)
+    return _HierEncoder.apply(dims, tree_tensors, graph_tensors, roots, getattr(encoder, "_grad_sink", None), beside, *params)

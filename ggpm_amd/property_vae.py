@@ -265,9 +265,9 @@ class HierEncoderVAE(nn.Module):
         self.R_mean = nn.Linear(args.hidden_size, args.latent_size)
         self.R_var = nn.Linear(args.hidden_size, args.latent_size)
 
-    def forward(self, tensors, beta=0.0, perturb_z=True, prep=None):
+    def forward(self, tensors, beta=0.0, perturb_z=True, prep=None, beside=False):
         tree_tensors, graph_tensors = make_cuda(tensors)
-        hroot, hnode, hinter, hatom = self.encoder.forward_padded(tree_tensors, graph_tensors, prep)
+        hroot, hnode, hinter, hatom = self.encoder.forward_padded(tree_tensors, graph_tensors, prep, beside=beside)
         z, kl = rsample(hroot, self.R_mean, self.R_var, perturb_z)
         H = self.encoder.hidden_size
         return z, kl, (hroot[:, :H], hnode[:, :H], hinter[:, :H], hatom[:, :H])
@@ -453,35 +453,34 @@ class _VAE(nn.Module):
             schedule = DecodeSchedule.from_graphs(graphs, tensors, orders, self.decoder.vocab, **self.decoder.schedule_hints())
         return schedule
 
-    def _encode(self, tensors, schedule=None, atom_ahead=False):
-        """The encoder's root vectors of ``tensors`` (on the device).  ``atom_ahead`` (the hierarchical pair's training
-        forward): the decoder's atom level of ``schedule`` is posted first -- it does not depend on the latent vector, so it
-        is issued beside the encoder."""
+    def _encode(self, tensors):
+        """The encoder's root vectors of ``tensors`` (on the device)."""
         tree_tensors, graph_tensors = tensors
         if not self.HIER:
             return self.encoder.forward_padded(tree_tensors)[0]
-        if not atom_ahead:
-            return self.encoder.forward_padded(tree_tensors, graph_tensors)[0]
-        from . import fused
+        return self.encoder.forward_padded(tree_tensors, graph_tensors)[0]
+
+    def _encode_beside_atom_level(self, tensors, schedule):
+        """The training forwards' encoder call -> (root vectors, what the decoder's call takes besides: ``atom=``, the
+        handle of its atom level).  The hierarchical decoder's atom level of ``schedule`` does not depend on the latent
+        vector: it is posted first and issued beside the encoder.  (A tree-only decoder has no atom level.)"""
+        if not self.HIER:
+            return self._encode(tensors), {}
         F_.mark("fwd: inputs on the device")
-        self.decoder.start_atom_level(schedule, tensors)
+        atom = self.decoder.start_atom_level(schedule, tensors)
         F_.mark("fwd: atom level posted")
         # beside the atom level's chain of small launches the encoder's levels take half as many (twice as large)
         # workgroups: the chain's launches then find free compute units instead of waiting for the encoder's to drain
-        fused.NARROW[0] = getattr(self.decoder, "_atom_ahead", None) is not None and _dev.ENC_NARROW
-        try:
-            return self.encoder.forward_padded(tree_tensors, graph_tensors)[0]
-        finally:
-            fused.NARROW[0] = False
+        return self.encoder.forward_padded(*tensors, beside=atom is not None)[0], dict(atom=atom)
 
     def forward(self, mols, graphs, tensors, orders, homos=None, lumos=None, beta=0.0, perturb_z=True, schedule=None):
         schedule = self._decode_schedule(graphs, tensors, orders, schedule)
         tensors = make_cuda(tensors)
-        root_vecs = self._encode(tensors, schedule, atom_ahead=True)
+        root_vecs, ahead = self._encode_beside_atom_level(tensors, schedule)
         root_vecs, kl_div = rsample(root_vecs, self.R_mean, self.R_var, perturb_z)
         F_.mark("fwd: encoder + rsample issued")
         loss, wacc, iacc, tacc, sacc = self.decoder(mols, (root_vecs, root_vecs, root_vecs), graphs, tensors, orders,
-                                                    schedule=schedule)
+                                                    schedule=schedule, **ahead)
         loss = loss + beta * kl_div
         F_.mark("fwd: heads and losses issued")
         return loss, _metrics(StepMetrics, (loss, kl_div, wacc, iacc, tacc, sacc))
@@ -559,7 +558,7 @@ class _PropOptVAE(_ClipNegativeLoss, _VAE):
     def forward(self, mols, graphs, tensors, orders, homos, lumos, beta=0.0, perturb_z=True, schedule=None):
         schedule = self._decode_schedule(graphs, tensors, orders, schedule)
         tensors = make_cuda(tensors)
-        root_vecs = self._encode(tensors, schedule, atom_ahead=True)
+        root_vecs, ahead = self._encode_beside_atom_level(tensors, schedule)
         if perturb_z or self.KL_IN_LOSS:
             root_vecs, kl_div = rsample(root_vecs, self.R_mean, self.R_var, perturb_z)
         else:
@@ -571,7 +570,7 @@ class _PropOptVAE(_ClipNegativeLoss, _VAE):
         t_lumo = torch.as_tensor(lumos, dtype=torch.float32).to(dev, non_blocking=True)
         homo_loss, lumo_loss, _, _ = self.property_optim.forward_latent(root_vecs, (t_homo, t_lumo))
         loss, wacc, iacc, tacc, sacc = self.decoder(mols, (root_vecs, root_vecs, root_vecs), graphs, tensors, orders,
-                                                    schedule=schedule)
+                                                    schedule=schedule, **ahead)
         if self.KL_IN_LOSS:
             loss = loss + beta * kl_div
         if self.loss_scaling:

@@ -418,17 +418,12 @@ def test_narrow_level_kernels_agree_with_the_default_form(name):
     differ in how the compiler contracts the gate expressions into fused multiply-adds, so the results agree to rounding
     (a few ulp per depth step; 5e-6 norm-wise after 20 steps at H = 300, a twentieth of the parity bar), not bit for bit.
     The golden-vector tests of the full VAE step run WITH the narrow form."""
-    from ggpm_amd import fused
     g = Golden(name)
     model = _build_encoder(g)
     res = []
     for narrow in (False, True):
         model.zero_grad(set_to_none=True)
-        fused.NARROW[0] = narrow
-        try:
-            z, kl, outs = model(g.numpy_tensors(), perturb_z=False)
-        finally:
-            fused.NARROW[0] = False
+        z, kl, outs = model(g.numpy_tensors(), perturb_z=False, beside=narrow)
         (kl + sum((o * o).sum() for o in outs)).backward()
         res.append([o.detach().clone() for o in outs] + [p.grad.clone() for p in model.parameters()])
     for a, b in zip(*res):
@@ -640,12 +635,12 @@ def test_configs4_full_batch_is_invariant_under_batch_composition(dtype):
     The bound is CALIBRATED like the configs[4] GRU parity case, and for the same reason (a sum-aggregating GRU over 30 depths
     amplifies rounding, by how much depends on the molecule): the sub-batches are evaluated a second time in an equivalent
     form that differs in rounding only -- fp32: gate products on split bf16 operands instead of fp32 MFMA (gate dtype "f32_split");
-    bf16: the two-row-tile kernels forced on the halves (``fused.NARROW``) -- and per tensor the full batch may be at most
+    bf16: the two-row-tile kernels forced on the halves (``beside=True``) -- and per tensor the full batch may be at most
     4 x as far from the sub-batches as those two evaluations of the sub-batches are from each other (never asked to be below
     2e-4 / BF16_TOL).  A wrong row-tile mapping, stash slot or storage offset at the 950-tile geometry moves results by O(1).
     Gradients: the full batch's loss is sum_mol ||rows||^2 + KL with KL a MEAN over the batch (ggpm/property_vae.py:30), so
     the sub-batch losses carry their KL with weight sub/32 and the parameter gradients must add up."""
-    from ggpm_amd import _lib, fused, synth
+    from ggpm_amd import _lib, synth
     from ggpm_amd.params import encoder_param_shapes, vae_head_shapes, seeded_state_dict
     from ggpm_amd.property_vae import HierEncoderVAE
     H, depth, B, latent = 600, 30, 32, 32
@@ -667,12 +662,8 @@ def test_configs4_full_batch_is_invariant_under_batch_composition(dtype):
         model = HierEncoderVAE(a).to(_dev())
         model.load_state_dict({(k if k.startswith("R_") else "encoder." + k): torch.from_numpy(v) for k, v in sd.items()})
         model.encoder.gate_dtype = dt
-        fused.NARROW[0] = narrow
-        try:
-            z, kl, outs = model((tree, graph), perturb_z=False)
-            (kl_weight * kl + sum((o * o).sum() for o in outs)).backward()
-        finally:
-            fused.NARROW[0] = False
+        z, kl, outs = model((tree, graph), perturb_z=False, beside=narrow)
+        (kl_weight * kl + sum((o * o).sum() for o in outs)).backward()
         torch.cuda.synchronize()
         grads = {k: (v.grad.double().cpu().numpy() if v.grad is not None else np.zeros(tuple(v.shape))) for k, v in model.named_parameters()}
         rows = [o.detach().cpu().numpy() for o in outs]                     # hroot [B], hnode / hinter [Nt + 1], hatom [Na + 1]

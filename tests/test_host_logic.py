@@ -319,3 +319,34 @@ def test_bench_plain_run_measures_the_headline_row_alone():
     assert full.full and not any(getattr(full, k) for k in legs)
     some = bench.parse_args(["--full", "--no-vae", "--no-configs4"])
     assert some.no_vae and some.no_configs4 and not some.no_second_cell and not some.no_cpu_baseline
+
+
+def test_atom_run_join_pays_what_is_owed_once_and_releases_it():
+    """``atom_decode.AtomRun`` without a GPU (stub tensors, no node state): the first ``join`` runs ``finish``, a second
+    one returns the same two tensors and does nothing else, and the closure is released after the first."""
+    import weakref
+    from ggpm_amd.atom_decode import AtomRun
+    pooled, cand, calls = torch.zeros(3, 4), torch.ones(2, 4), []
+
+    def finish():
+        calls.append(1)
+
+    probe = weakref.ref(finish)
+    run = AtomRun(None, pooled, cand, finish)
+    del finish
+    assert probe() is not None
+    first = run.join()
+    assert calls == [1] and probe() is None
+    second = run.join()
+    assert calls == [1]
+    assert first[0] is pooled and first[1] is cand and second[0] is pooled and second[1] is cand
+
+
+def test_hand_offs_are_arguments_not_module_state():
+    import inspect
+    from ggpm_amd import atom_decode, fused
+    from ggpm_amd.decoder import HierMPNDecoder
+    from ggpm_amd.encoder import HierMPNEncoder
+    assert not hasattr(fused, "NARROW") and not hasattr(atom_decode, "_PENDING")
+    assert "beside" in inspect.signature(HierMPNEncoder.forward_padded).parameters
+    assert "atom" in inspect.signature(HierMPNDecoder.forward).parameters

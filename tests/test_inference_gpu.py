@@ -124,7 +124,7 @@ def test_no_grad_forward_joins_the_decode_worker():
     for mode in MODES:
         with _ctx(mode):
             model(*batch, beta=0.1, perturb_z=False, schedule=sch)
-        assert not atom_decode._PENDING and not atom_decode._INFLIGHT, mode
+        assert not atom_decode._INFLIGHT and not hasattr(atom_decode, "_PENDING"), mode
 
 
 @pytest.mark.parametrize("name", ["vae_gru_s42", "vae_lstm_s41"])
@@ -284,6 +284,41 @@ def test_no_grad_forward_between_training_steps_leaves_no_state(name):
     assert set(plain) == set(after)
     for k in plain:
         assert torch.equal(plain[k], after[k]), k
+
+
+@pytest.mark.parametrize("name", ["vae_gru_s42", "vae_lstm_s41"])
+def test_two_atom_levels_in_flight_travel_with_their_own_handles(name):
+    """Two atom levels issued ahead, of two schedules of the same batch, joined in the other order: each handle carries
+    its own run, so both steps give the bits of an ordinary step, and nothing stays with the decode worker."""
+    from ggpm_amd import _dev, atom_decode
+    from ggpm_amd.decoder import DecodeSchedule
+    from ggpm_amd.property_vae import make_cuda, rsample
+    assert _dev.ATOM_ASYNC and _dev.ATOM_AHEAD
+    model, batch, sch_a, g = _hier("hier-prop", name)
+    sch_b = DecodeSchedule.from_specs(g.specs(), batch[2])
+    model.train()                                               # (dropout 0)
+
+    def grads(loss):
+        model.zero_grad(set_to_none=True)
+        loss.backward()
+        torch.cuda.synchronize()
+        return loss.detach().clone(), {k: p.grad.clone() for k, p in model.named_parameters() if p.grad is not None}
+
+    ref = {id(s): grads(model(*batch, beta=0.1, perturb_z=False, schedule=s)[0]) for s in (sch_a, sch_b)}
+
+    tensors = make_cuda(batch[2])
+    ahead = {id(s): model.decoder.start_atom_level(s, tensors) for s in (sch_a, sch_b)}
+    assert ahead[id(sch_a)] is not None and ahead[id(sch_b)] is not None
+    for s in (sch_b, sch_a):
+        root = model.encoder.forward_padded(*tensors, beside=True)[0]
+        root, kl = rsample(root, model.R_mean, model.R_var, False)
+        loss = model.decoder(None, (root, root, root), None, tensors, batch[3], schedule=s, atom=ahead[id(s)])[0] + 0.1 * kl
+        loss, got = grads(loss)
+        assert torch.equal(loss, ref[id(s)][0])
+        assert set(got) == set(ref[id(s)][1])
+        for k in got:
+            assert torch.equal(got[k], ref[id(s)][1][k]), k
+    assert not atom_decode._INFLIGHT
 
 
 def _layers(opt):

@@ -134,7 +134,7 @@ def test_nothing_is_left_behind(name, kind):
     model.zero_grad(set_to_none=True)
     model.log_likelihood(batch, n_samples=2, seed=SEED, schedule=sch)
     assert all(p.grad is None for p in model.parameters())
-    assert getattr(model.decoder, "_atom_ahead", None) is None and getattr(model.decoder, "_heads_in", None) is None
+    assert not hasattr(model.decoder, "_atom_ahead") and not hasattr(model.decoder, "_heads_in")
     got_loss, got = step(model)
     assert torch.equal(got_loss, want_loss)
     assert set(got) == set(want)
