@@ -188,14 +188,6 @@ inline const ggpm_level_opts& ggpm_opts_or_default(const ggpm_level_opts* opts) 
 // them).  `lo` as ggpm_level_opts.lo; `csws`: 256 * Hp floats.  Reads opts->gate_dtype.
 int ggpm_gru_bias_u_grad(int E1, int H, int depth, int lo, float* work, float* dbu, float* csws, const ggpm_level_opts* opts,
                          ggpm_stream_t stream);
-// The hidden-half weight gradients a sparse backward with opts->skip_sparse_wgrads left out: call with the same arguments
-// (tree_level.hip: beside the rest of the level's backward instead of in front of it).  Both read opts->gate_dtype.
-int ggpm_gru_sparse_weight_grads(int E1, int H, int depth, const float* Hs, const float* Ss, const float* Gs, float* work,
-                                 size_t work_bytes, float* dWz_h, int ld_dwz, float* dUr, int ld_dur, float* dbu, float* dWh_h,
-                                 int ld_dwh, const ggpm_level_opts* opts, ggpm_stream_t stream);
-int ggpm_lstm_sparse_weight_grads(int E1, int H, int depth, const float* Hs, const float* Ss, float* work, size_t work_bytes,
-                                  float* dWi_h, int ld_dwi, float* dWo_h, int ld_dwo, float* dWu_h, int ld_dwu, float* dWf_h,
-                                  int ld_dwf, const ggpm_level_opts* opts, ggpm_stream_t stream);
 hipEvent_t ggpm_wgrad_event(int i);          // small pool of re-recordable events, per thread (mpn_gru.hip)
 
 // Levels whose depth-loop arrays are kept in bf16 under gate mode 1 (tile_mma.h: "bf16 STORAGE"): dense training levels large

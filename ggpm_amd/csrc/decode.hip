@@ -9,6 +9,7 @@
 // order, from C++: ~25 launches per step and direction that Python + ctypes otherwise issue one by one (the full VAE step
 // is as long on the host as on the GPU).
 #include "common.h"
+#include "level_call.h"
 #include <condition_variable>
 #include <deque>
 #include <functional>
@@ -21,12 +22,21 @@ namespace {
 // launches of their own instead of inside the step's first / last launch
 inline bool decode_fold() { static const bool v = [] { const char* e = ggpm_dev_env("GGPM_DECODE_FOLD"); return !e || atoi(e) != 0; }(); return v; }
 
-struct Offs {
-    size_t f0, f1, r0, q0;      // F-id range of the step, first row of its [depth][n] and [depth + 1][n] blocks
-};
+struct Offs { size_t f0, r0, q0; };      // first F id of the step, first row of its [depth][n] and [depth + 1][n] blocks
+inline Offs offs(const ggpm_decode_steps* d, int t) { return {(size_t)d->foff[t], (size_t)d->roff[t], (size_t)d->qoff[t]}; }
 
-inline Offs offs(const ggpm_decode_steps* d, int t) {
-    return {(size_t)d->foff[t], (size_t)d->foff[t + 1], (size_t)d->roff[t], (size_t)d->qoff[t]};
+// what every level call of a step loop shares: shape, cell, hidden matrices (gate order: level_call.h)
+inline LevelCall step_call(const ggpm_decode_steps* d, const float* const* W, const int* ldw, const float* bu) {
+    LevelCall c = {};
+    c.lstm = d->lstm != 0; c.H = d->H; c.depth = d->depth; c.bu = bu;
+    for (int k = 0; k < cell_gates(c.lstm).n; ++k) { c.W[k] = W[k]; c.ldw[k] = ldw[k]; }
+    return c;
+}
+// ... and what step t adds: its rows, CSRs, frozen mask and the X planes of its block
+inline void set_step(LevelCall& c, const ggpm_decode_steps* d, int t, const float* x) {
+    c.rows = d->n[t]; c.frozen = d->frozen[t];
+    c.pred_rowptr = d->pred_rowptr[t]; c.pred_col = d->pred_col[t]; c.succ_rowptr = d->succ_rowptr[t]; c.succ_col = d->succ_col[t];
+    for (int k = 0; k < cell_gates(c.lstm).n; ++k) c.X[k] = x + (size_t)k * c.rows * ggpm_padded_hidden(c.H);
 }
 
 inline bool steps_ok(const ggpm_decode_steps* d) {
@@ -43,20 +53,18 @@ extern "C" int ggpm_decode_steps_forward(const ggpm_decode_steps* d, const float
     if (!steps_ok(d) || !W || !ldw || !X_all || !Hs_all || !Qs_all || !St_all || !wpack || !tmp || (d->lstm && !Cs_all) ||
         (!d->lstm && !bu))
         return GGPM_ERR_ARG;
-    const int H = d->H, Hp = ggpm_padded_hidden(H), G = d->lstm ? 4 : 3;
-    int nmax = 0;
-    for (int t = 0; t < d->T; ++t) nmax = d->n[t] > nmax ? d->n[t] : nmax;
-    (void)tmp;
+    LevelCall c = step_call(d, W, ldw, bu);
+    const int Hp = ggpm_padded_hidden(d->H), G = cell_gates(c.lstm).n;
+    c.wpack = wpack;
     const bool fold = decode_fold();
     for (int t = 0; t < d->T; ++t) {
-        const int n = d->n[t];
         const Offs o = offs(d, t);
-        const float* x = X_all + (size_t)G * o.f0 * Hp;
-        const size_t xs = (size_t)n * Hp;
-        float* hs = Hs_all + o.q0 * Hp;
-        float* qs = Qs_all + o.r0 * Hp;
-        float* st[5];
-        for (int k = 0; k < 5; ++k) st[k] = St_all + (size_t)k * st_stride + o.r0 * Hp;
+        set_step(c, d, t, X_all + (size_t)G * o.f0 * Hp);
+        c.Hs = Hs_all + o.q0 * Hp;
+        c.Cs = c.lstm ? Cs_all + o.q0 * Hp : nullptr;
+        c.Qs = Qs_all + o.r0 * Hp;
+        for (int k = 0; k < 5; ++k) c.St[k] = St_all + (size_t)k * st_stride + o.r0 * Hp;
+        c.h_in = c.Hs; c.c_in = c.Cs;
         // the step's start state goes straight into slot 0 of its block: frozen rows from the blocks of the steps that
         // produced them, zero for the rows the step recomputes (srcH = -1) -- exactly the masked state sparse_forward would
         // build.  The step's first launch (q^0 = U_r h^0 / qf^0 = Wf_h h^0) fetches the rows through srcH and writes slot 0
@@ -65,25 +73,13 @@ extern "C" int ggpm_decode_steps_forward(const ggpm_decode_steps* d, const float
         opts.weights_packed = t > 0;      // same weights, same `wpack`: packed by the first step
         int rc = GGPM_OK;
         if (fold) {
-            opts.gather_h = Hs_all; opts.gather_c = d->lstm ? Cs_all : nullptr; opts.gather_idx = d->srcH[t];
+            opts.gather_h = Hs_all; opts.gather_c = Cs_all; opts.gather_idx = d->srcH[t];
         } else {
-            rc = ggpm_gather_rows(Hs_all, Hp, d->srcH[t], n, Hp, hs, Hp, 0, 0, stream);
+            rc = ggpm_gather_rows(Hs_all, Hp, d->srcH[t], c.rows, Hp, c.Hs, Hp, 0, 0, stream);
+            if (!rc && c.lstm) rc = ggpm_gather_rows(Cs_all, Hp, d->srcH[t], c.rows, Hp, c.Cs, Hp, 0, 0, stream);
             if (rc) return rc;
         }
-        if (d->lstm) {
-            float* cs = Cs_all + o.q0 * Hp;
-            if (!fold) {
-                rc = ggpm_gather_rows(Cs_all, Hp, d->srcH[t], n, Hp, cs, Hp, 0, 0, stream);
-                if (rc) return rc;
-            }
-            rc = ggpm_lstm_sparse_forward(n, H, d->depth, hs, cs, d->frozen[t], x, x + xs, x + 2 * xs, x + 3 * xs, W[0],
-                                          ldw[0], W[1], ldw[1], W[2], ldw[2], W[3], ldw[3], d->pred_rowptr[t], d->pred_col[t],
-                                          hs, cs, qs, st[0], st[1], st[2], st[3], st[4], wpack, 1, &opts, stream);
-        } else {
-            rc = ggpm_gru_sparse_forward(n, H, d->depth, hs, d->frozen[t], x, x + xs, x + 2 * xs, W[0], ldw[0], W[1], ldw[1],
-                                         bu, W[2], ldw[2], d->pred_rowptr[t], d->pred_col[t], hs, qs, st[0], st[1], st[2],
-                                         st[3], st[4], wpack, 1, &opts, stream);
-        }
+        rc = ggpm_level_forward(c, true, &opts, stream);
         if (rc) return rc;
     }
     GGPM_CHECK_LAUNCH();
@@ -100,34 +96,27 @@ extern "C" int ggpm_decode_steps_infer(const ggpm_decode_steps* d, const float* 
     if (!steps_ok(d) || !W || !ldw || !X_all || !F_h || !Hs || !Qs || !wpack || (d->lstm && (!F_c || !Cs)) ||
         (!d->lstm && !bu))
         return GGPM_ERR_ARG;
-    const int H = d->H, Hp = ggpm_padded_hidden(H), G = d->lstm ? 4 : 3;
+    LevelCall c = step_call(d, W, ldw, bu);
+    const int Hp = ggpm_padded_hidden(d->H), G = cell_gates(c.lstm).n;
+    c.Hs = Hs; c.Cs = Cs; c.Qs = Qs; c.wpack = wpack;
+    c.h_in = Hs; c.c_in = Cs;
     const bool fold = decode_fold();
     for (int t = 0; t < d->T; ++t) {
-        const int n = d->n[t];
         const Offs o = offs(d, t);
-        const float* x = X_all + (size_t)G * o.f0 * Hp;
-        const size_t xs = (size_t)n * Hp;
+        set_step(c, d, t, X_all + (size_t)G * o.f0 * Hp);
         ggpm_level_opts opts = {};
         opts.weights_packed = t > 0;
         opts.h_out = F_h + o.f0 * Hp;
-        opts.c_out = d->lstm ? F_c + o.f0 * Hp : nullptr;
+        opts.c_out = c.lstm ? F_c + o.f0 * Hp : nullptr;
         int rc = GGPM_OK;
         if (fold) {
-            opts.gather_h = F_h; opts.gather_c = d->lstm ? F_c : nullptr; opts.gather_idx = d->srcF[t];
+            opts.gather_h = F_h; opts.gather_c = F_c; opts.gather_idx = d->srcF[t];
         } else {
-            rc = ggpm_gather_rows(F_h, Hp, d->srcF[t], n, Hp, Hs, Hp, 0, 0, stream);
-            if (!rc && d->lstm) rc = ggpm_gather_rows(F_c, Hp, d->srcF[t], n, Hp, Cs, Hp, 0, 0, stream);
+            rc = ggpm_gather_rows(F_h, Hp, d->srcF[t], c.rows, Hp, Hs, Hp, 0, 0, stream);
+            if (!rc && c.lstm) rc = ggpm_gather_rows(F_c, Hp, d->srcF[t], c.rows, Hp, Cs, Hp, 0, 0, stream);
             if (rc) return rc;
         }
-        if (d->lstm) {
-            rc = ggpm_lstm_sparse_forward(n, H, d->depth, Hs, Cs, d->frozen[t], x, x + xs, x + 2 * xs, x + 3 * xs, W[0], ldw[0],
-                                          W[1], ldw[1], W[2], ldw[2], W[3], ldw[3], d->pred_rowptr[t], d->pred_col[t], Hs, Cs,
-                                          Qs, nullptr, nullptr, nullptr, nullptr, nullptr, wpack, 0, &opts, stream);
-        } else {
-            rc = ggpm_gru_sparse_forward(n, H, d->depth, Hs, d->frozen[t], x, x + xs, x + 2 * xs, W[0], ldw[0], W[1], ldw[1],
-                                         bu, W[2], ldw[2], d->pred_rowptr[t], d->pred_col[t], Hs, Qs, nullptr, nullptr,
-                                         nullptr, nullptr, nullptr, wpack, 0, &opts, stream);
-        }
+        rc = ggpm_level_forward(c, false, &opts, stream);
         if (rc) return rc;
     }
     GGPM_CHECK_LAUNCH();
@@ -143,58 +132,45 @@ extern "C" int ggpm_decode_steps_backward(const ggpm_decode_steps* d, const floa
     if (!steps_ok(d) || !W || !ldw || !X_all || !Hs_all || !Qs_all || !St_all || !dF || !dX_all || !DG_all || !DQ_all ||
         !dW_unused || !work || !tmp || (d->lstm && (!Cs_all || !dCF)))
         return GGPM_ERR_ARG;
-    const int H = d->H, Hp = ggpm_padded_hidden(H), G = d->lstm ? 4 : 3;
+    LevelCall c = step_call(d, W, ldw, nullptr);
+    const int Hp = ggpm_padded_hidden(d->H), G = cell_gates(c.lstm).n;
     int nmax = 0;
     for (int t = 0; t < d->T; ++t) nmax = d->n[t] > nmax ? d->n[t] : nmax;
-    float* dhin = tmp;
-    float* dcin = tmp + (size_t)nmax * Hp;
+    c.d_in = tmp;                                  // the frozen rows' gradient of one step
+    c.dc_in = tmp + (size_t)nmax * Hp;
+    // the weight gradients are deferred (defer_stash): what a level call would write them to is never written
+    for (int k = 0; k < G; ++k) { c.dW[k] = dW_unused[k]; c.ld_dw[k] = d->H; }
+    c.dbu = dW_unused[3];                          // (GRU)
+    c.work = work; c.work_bytes = work_bytes;
     const bool fold = decode_fold();
     for (int t = d->T - 1; t >= 0; --t) {
-        const int n = d->n[t];
         const Offs o = offs(d, t);
-        const size_t xs = (size_t)n * Hp;
-        const float* x = X_all + (size_t)G * o.f0 * Hp;
-        float* dx = dX_all + (size_t)G * o.f0 * Hp;
-        const float* hs = Hs_all + o.q0 * Hp;
-        const float* qs = Qs_all + o.r0 * Hp;
-        const float* st[5];
-        for (int k = 0; k < 5; ++k) st[k] = St_all + (size_t)k * st_stride + o.r0 * Hp;
-        float* dg[3];
-        for (int k = 0; k < 3; ++k) dg[k] = DG_all + (size_t)k * dg_stride + o.r0 * Hp;
-        float* dhd = dF + o.f0 * Hp;
+        set_step(c, d, t, X_all + (size_t)G * o.f0 * Hp);
+        for (int k = 0; k < G; ++k) c.dX[k] = dX_all + ((size_t)G * o.f0 + (size_t)k * c.rows) * Hp;
+        c.Hs = level_read(Hs_all) + o.q0 * Hp;
+        c.Cs = c.lstm ? level_read(Cs_all) + o.q0 * Hp : nullptr;
+        c.Qs = level_read(Qs_all) + o.r0 * Hp;
+        for (int k = 0; k < 5; ++k) c.St[k] = level_read(St_all) + (size_t)k * st_stride + o.r0 * Hp;
+        c.d_out = dF + o.f0 * Hp;
+        c.dc_out = c.lstm ? dCF + o.f0 * Hp : nullptr;
         ggpm_level_opts opts = {};
         opts.weights_packed = t < d->T - 1;      // same weights, same `work`: the transposes were packed by the first call
         // the frozen rows' gradient goes to the step that produced their state (rows recomputed here: none): added there by
         // the step's last launch (ggpm_level_opts.scatter_*), or by scatter launches of their own
-        if (fold) { opts.scatter_h = dF; opts.scatter_c = d->lstm ? dCF : nullptr; opts.scatter_idx = d->srcF[t]; }
+        if (fold) { opts.scatter_h = dF; opts.scatter_c = dCF; opts.scatter_idx = d->srcF[t]; }
         // the stashes go to the stacked buffers, contracted once after the loop (ggpm_*_weight_grads_stacked)
-        float* const dq = DQ_all + o.q0 * Hp;
-        opts.defer_stash[0] = dg[0]; opts.defer_stash[1] = dg[1];
-        opts.defer_stash[2] = d->lstm ? dg[2] : dq; opts.defer_stash[3] = d->lstm ? dq : nullptr;
-        int rc;
-        if (d->lstm) {
-            rc = ggpm_lstm_sparse_backward(n, H, d->depth, d->frozen[t], x + 3 * xs, W[0], ldw[0], W[1], ldw[1], W[2], ldw[2],
-                                           W[3], ldw[3], d->pred_rowptr[t], d->pred_col[t], d->succ_rowptr[t],
-                                           d->succ_col[t], hs, Cs_all + o.q0 * Hp, qs, st[0], st[1], st[2], st[3], st[4], dhd,
-                                           dCF + o.f0 * Hp, dhin, dcin, dx, dx + xs, dx + 2 * xs, dx + 3 * xs, dW_unused[0],
-                                           H, dW_unused[1], H, dW_unused[2], H, dW_unused[3], H, work, work_bytes, &opts,
-                                           stream);
-            if (rc) return rc;
-            if (!fold) rc = ggpm_scatter_rows(dcin, Hp, d->srcF[t], n, Hp, dCF, Hp, 1, stream);
-        } else {
-            rc = ggpm_gru_sparse_backward(n, H, d->depth, d->frozen[t], x + xs, W[0], ldw[0], W[1], ldw[1], W[2], ldw[2],
-                                          d->pred_rowptr[t], d->pred_col[t], d->succ_rowptr[t], d->succ_col[t], hs, qs, st[0],
-                                          st[1], st[2], st[3], st[4], dhd, dhin, dx, dx + xs, dx + 2 * xs, dW_unused[0], H,
-                                          dW_unused[1], H, dW_unused[3], dW_unused[2], H, work, work_bytes, &opts, stream);
-        }
+        const int ns = cell_gates(c.lstm).n_sum;      // the gate-gradient stashes, then dq
+        for (int k = 0; k < ns; ++k) opts.defer_stash[k] = DG_all + (size_t)k * dg_stride + o.r0 * Hp;
+        opts.defer_stash[ns] = DQ_all + o.q0 * Hp;
+        int rc = ggpm_level_backward(c, 1, &opts, stream);
         if (rc) return rc;
-        if (!fold) rc = ggpm_scatter_rows(dhin, Hp, d->srcF[t], n, Hp, dF, Hp, 1, stream);
+        if (!fold && c.lstm) rc = ggpm_scatter_rows(c.dc_in, Hp, d->srcF[t], c.rows, Hp, dCF, Hp, 1, stream);
+        if (!fold && !rc) rc = ggpm_scatter_rows(c.d_in, Hp, d->srcF[t], c.rows, Hp, dF, Hp, 1, stream);
         if (rc) return rc;
     }
     GGPM_CHECK_LAUNCH();
     return GGPM_OK;
 }
-
 
 // ---- issuing the step loops from a worker thread ------------------------------------------------------------------------
 // A step loop is ~280 launches = 1.5-1.8 ms of host time inside ONE call.  While the calling thread sits in it, nothing else

@@ -9,15 +9,13 @@
 // gradient contractions there, event-ordered.  GRU message function, dropout 0 (the host keeps the op-by-op path
 // for everything else).
 #include "common.h"
+#include "level_call.h"
 #include <condition_variable>
-#include <cstring>
 #include <cstdlib>
 #include <deque>
 #include <functional>
 #include <mutex>
 #include <thread>
-
-hipEvent_t ggpm_wgrad_event(int i);          // small pool of re-recordable events (mpn_gru.hip)
 
 namespace {
 
@@ -59,7 +57,7 @@ struct Dims {
     int H, Hp, He, Hep, depthT, depthG, atom, n_motif, n_attach;
     int N1g, E1g, Kga, Kgb, N1t, E1t, Kta, Ktb, Ktc, B;
     int ld_n, ld_m, ld_t, Ig, It;
-    int lstm, nX, lcount;          // cell type, hoisted-input slots per level (3 / 4), parameter slots per level (9 / 10)
+    int lstm, nX;                  // cell type, hoisted-input slots per level (3 / 4)
     int tree_chain;                // longest dependency chain of the tree messages (0: unknown)
     float dropout;                 // training-mode drop probability (0: none)
     unsigned int seed_lo, seed_hi;
@@ -91,7 +89,7 @@ Dims make_dims(const ggpm_enc_dims* d) {
     x.ld_n = ggpm_round_up(x.atom, 4);
     x.Ig = x.atom + 4 + 20; x.ld_m = ggpm_round_up(x.Ig, 4);
     x.It = x.H + 20; x.ld_t = ggpm_round_up(x.It, 4);
-    x.lstm = d->rnn_type == 1; x.nX = x.lstm ? 4 : 3; x.lcount = x.lstm ? 10 : 9;
+    x.lstm = d->rnn_type == 1; x.nX = cell_gates(x.lstm).n;
     x.tree_chain = d->tree_chain;
     x.dropout = d->dropout; x.seed_lo = d->seed_lo; x.seed_hi = d->seed_hi;
     x.gate_dtype = (d->gate_dtype >= 1 && d->gate_dtype <= 3) ? d->gate_dtype : 0;
@@ -110,12 +108,12 @@ void take_csr(Arena& A, Csr& c, int rows, int ncols, int cap) {
 
 void take_level(Arena& A, LevelSaved& L, int E1, int N1, int Hp, int H, int depth, bool lstm) {
     const size_t slot = (size_t)E1 * Hp;
-    L.X = A.take<float>((lstm ? 4 : 3) * slot);
+    L.X = A.take<float>(cell_gates(lstm).n * slot);
     L.Hs = A.take<float>((size_t)(depth + 1) * slot);
     L.Cs = lstm ? A.take<float>((size_t)(depth + 1) * slot) : nullptr;
     L.Qs = A.take<float>((size_t)depth * slot);
     L.St = A.take<float>((size_t)5 * depth * slot);
-    L.wpack = A.take<float>(lstm ? ggpm_lstm_pack_floats(H) : ggpm_gru_pack_floats(H));
+    L.wpack = A.take<float>(ggpm_level_pack_floats(lstm, H));
     L.nei = A.take<float>((size_t)N1 * Hp);
 }
 
@@ -181,7 +179,7 @@ void layout_infer(Arena& A, const Dims& d, Saved& s) {
     L.Qs = A.take<float>(2 * slot);
     L.Cs = d.lstm ? A.take<float>(2 * slot) : nullptr;
     L.hout = A.take<float>(slot);
-    L.wpack = A.take<float>(d.lstm ? ggpm_lstm_pack_floats(d.H) : ggpm_gru_pack_floats(d.H));
+    L.wpack = A.take<float>(ggpm_level_pack_floats(d.lstm, d.H));
     for (int l = 0; l < 3; ++l) {
         s.lv[l] = L;
         s.lv[l].nei = A.take<float>((size_t)(l == 2 ? d.N1g : d.N1t) * d.Hp);
@@ -200,12 +198,26 @@ __global__ void iota_k(int32_t* out, int n) {
 
 // parameter slots
 enum { P_EC = 0, P_EI, P_WC, P_BC, P_WI, P_BI, P_WROOT, P_BROOT, P_LEVEL0 };
+// A level's block of parameter slots: W_o, b_o, then the message function's.  The ONE place that says which slot is gate k's
+// weight and bias (gate order: level_call.h; -1: none); U_r and b_u stand alone.
 enum { L_WO = 0, L_BO, L_WZ, L_BZ, L_WR, L_UR, L_BU, L_WH, L_BH, L_COUNT };               // GRU level
 enum { Q_WO = 0, Q_BO, Q_WI, Q_BI, Q_WOG, Q_BOG, Q_WU, Q_BU, Q_WF, Q_BF, Q_COUNT };      // LSTM level
-inline int lp(int level, int which) { return P_LEVEL0 + level * L_COUNT + which; }
-inline int lq(int level, int which) { return P_LEVEL0 + level * Q_COUNT + which; }
-inline int lwo(bool lstm, int level) { return lstm ? lq(level, Q_WO) : lp(level, L_WO); }
-inline int lbo(bool lstm, int level) { return lstm ? lq(level, Q_BO) : lp(level, L_BO); }
+struct LevelSlots { int count, w[4], b[4], ur, bu, ld[4]; };
+constexpr LevelSlots GRU_SLOTS = {L_COUNT, {L_WZ, L_WR, L_WH, -1}, {L_BZ, -1, L_BH, -1}, L_UR, L_BU, {}};
+constexpr LevelSlots LSTM_SLOTS = {Q_COUNT, {Q_WI, Q_WOG, Q_WU, Q_WF}, {Q_BI, Q_BOG, Q_BU, Q_BF}, -1, -1, {}};
+inline const LevelSlots& level_slots(bool lstm) { return lstm ? LSTM_SLOTS : GRU_SLOTS; }
+inline int lwo(const Dims& d, int level) { return P_LEVEL0 + level * level_slots(d.lstm).count + L_WO; }      // (W_o, b_o lead both blocks)
+inline int lbo(const Dims& d, int level) { return P_LEVEL0 + level * level_slots(d.lstm).count + L_BO; }
+// ... of level `level` as indices into the driver's parameter / gradient arrays, with the leading dimension of gate k's weight:
+// its I input columns, then (a full gate) its H hidden columns
+inline LevelSlots gate_slots(bool lstm, int level, int I, int H) {
+    LevelSlots g = level_slots(lstm);
+    const int base = P_LEVEL0 + level * g.count;
+    auto at = [base](int slot) { return slot < 0 ? -1 : base + slot; };
+    for (int k = 0; k < 4; ++k) { g.w[k] = at(g.w[k]); g.b[k] = at(g.b[k]); g.ld[k] = cell_gates(lstm).full[k] ? I + H : I; }
+    g.ur = at(g.ur); g.bu = at(g.bu);
+    return g;
+}
 
 // GGPM_SPLIT_TAIL=0: the input-half gradients of the last level behind its tall contractions on the second stream again
 inline bool split_tail_enabled() { static const bool v = !(ggpm_dev_env("GGPM_SPLIT_TAIL") && atoi(ggpm_dev_env("GGPM_SPLIT_TAIL")) == 0); return v; }
@@ -374,12 +386,34 @@ int replicate_tail(const Dims& d, int E1, int depth, int run, int level, const L
     return GGPM_OK;
 }
 
+struct LevelTag { LevelTag(int level) { ggpm_timing_tag(3 - level); } ~LevelTag() { ggpm_timing_tag(0); } };      // (timing rows)
+
+// The message-function call of a level over the driver's arrays: gate k's hidden matrix is the hidden half of its own weight,
+// or U_r where it has none
+LevelCall level_call(const Dims& d, int E1, int I, int depth, float* const* P, const LevelSlots& gs, const Csr& pred,
+                     const LevelSaved& L) {
+    const CellGates& cg = cell_gates(d.lstm);
+    const size_t slot = (size_t)E1 * d.Hp;
+    LevelCall c = {};
+    c.lstm = d.lstm; c.rows = E1; c.H = d.H; c.depth = depth;
+    for (int k = 0; k < cg.n; ++k) {
+        c.X[k] = L.X + k * slot;
+        c.W[k] = cg.full[k] ? P[gs.w[k]] + I : P[gs.ur];
+        c.ldw[k] = cg.full[k] ? gs.ld[k] : d.H;
+    }
+    c.bu = gs.bu < 0 ? nullptr : P[gs.bu];
+    c.pred_rowptr = pred.rowptr; c.pred_col = pred.col; c.succ_rowptr = pred.rowptrT; c.succ_col = pred.colT;
+    c.Hs = L.Hs; c.Cs = L.Cs; c.Qs = L.Qs; c.wpack = L.wpack;
+    for (int k = 0; k < 5; ++k) c.St[k] = L.St ? L.St + k * depth * slot : nullptr;      // (forward-only layout: no stashes)
+    return c;
+}
+
 int level_forward(const Dims& d, int E1, int N1, int I, int depth, const float* x, int ldx, float* const* P, int level,
                   const Csr& pred, const Csr& agr, LevelSaved& L, ggpm_stream_t s) {
     const int H = d.H, Hp = d.Hp;
     const size_t slot = (size_t)E1 * Hp;
     const int run = run_steps(d, level, depth, E1);
-    struct Tag { Tag(int level) { ggpm_timing_tag(3 - level); } ~Tag() { ggpm_timing_tag(0); } } tag(level);
+    const LevelTag tag(level);
     ggpm_level_opts o = level_opts(d);
     o.run_depth = run;
     const bool infer = L.hout != nullptr;          // forward-only layout: no stashes, the result lands in L.hout
@@ -387,31 +421,13 @@ int level_forward(const Dims& d, int E1, int N1, int I, int depth, const float* 
     const int fs = infer ? 0 : fixed_slot(d, level, depth, E1);
     o.fixed_slot = fs;
     const float* result = infer ? L.hout : L.Hs + (size_t)(fs ? fs : depth) * slot;
-    if (d.lstm) {
-        const float* W[4] = {P[lq(level, Q_WI)], P[lq(level, Q_WOG)], P[lq(level, Q_WU)], P[lq(level, Q_WF)]};
-        const float* b[4] = {P[lq(level, Q_BI)], P[lq(level, Q_BOG)], P[lq(level, Q_BU)], P[lq(level, Q_BF)]};
-        GgpmGemmProblem gp[4];
-        for (int k = 0; k < 4; ++k) gp[k] = {x, ldx, W[k], I + H, L.X + k * slot, Hp, Hp, b[k], 0, GGPM_ACT_NONE, 0};
-        CK(ggpm_gemm_grouped(0, 1, E1, H, I, 4, gp, s));      // the four input projections in one launch
-        const size_t dsl = (size_t)depth * slot;
-        CK(ggpm_lstm_forward(E1, H, depth, L.X, L.X + slot, L.X + 2 * slot, L.X + 3 * slot, W[0] + I, I + H, W[1] + I, I + H,
-                             W[2] + I, I + H, W[3] + I, I + H, pred.rowptr, pred.col, L.Hs, L.Cs, L.Qs,
-                             infer ? nullptr : L.St, infer ? nullptr : L.St + dsl, infer ? nullptr : L.St + 2 * dsl,
-                             infer ? nullptr : L.St + 3 * dsl, infer ? nullptr : L.St + 4 * dsl, L.wpack, infer ? 0 : 1, &o, s));
-        if (!infer) CK(replicate_tail(d, E1, depth, run, level, L, s));
-        CK(ggpm_segment_sum(result, Hp, agr.rowptr, agr.col, N1, H, L.nei, Hp, 0, Hp, s));
-        return GGPM_OK;
-    }
-    const float *Wz = P[lp(level, L_WZ)], *Wr = P[lp(level, L_WR)], *Wh = P[lp(level, L_WH)];
-    const GgpmGemmProblem gp[3] = {{x, ldx, Wz, I + H, L.X, Hp, Hp, P[lp(level, L_BZ)], 0, GGPM_ACT_NONE, 0},
-                                   {x, ldx, Wr, I, L.X + slot, Hp, Hp, nullptr, 0, GGPM_ACT_NONE, 0},
-                                   {x, ldx, Wh, I + H, L.X + 2 * slot, Hp, Hp, P[lp(level, L_BH)], 0, GGPM_ACT_NONE, 0}};
-    CK(ggpm_gemm_grouped(0, 1, E1, H, I, 3, gp, s));          // the three input projections in one launch
-    const size_t ds = (size_t)depth * slot;
-    CK(ggpm_gru_forward(E1, H, depth, L.X, L.X + slot, L.X + 2 * slot, Wz + I, I + H, P[lp(level, L_UR)], H,
-                            P[lp(level, L_BU)], Wh + I, I + H, pred.rowptr, pred.col,
-                            L.Hs, L.Qs, infer ? nullptr : L.St, infer ? nullptr : L.St + ds, infer ? nullptr : L.St + 2 * ds,
-                            infer ? nullptr : L.St + 3 * ds, infer ? nullptr : L.St + 4 * ds, L.wpack, infer ? 0 : 1, &o, s));
+    const LevelSlots gs = gate_slots(d.lstm, level, I, H);
+    const LevelCall c = level_call(d, E1, I, depth, P, gs, pred, L);
+    GgpmGemmProblem gp[4];
+    for (int k = 0; k < d.nX; ++k)
+        gp[k] = {x, ldx, P[gs.w[k]], gs.ld[k], L.X + k * slot, Hp, Hp, gs.b[k] < 0 ? nullptr : P[gs.b[k]], 0, GGPM_ACT_NONE, 0};
+    CK(ggpm_gemm_grouped(0, 1, E1, H, I, d.nX, gp, s));      // the input projections in one launch
+    CK(ggpm_level_forward(c, !infer, &o, s));
     if (!infer) CK(replicate_tail(d, E1, depth, run, level, L, s));
     CK(ggpm_segment_sum(result, Hp, agr.rowptr, agr.col, N1, H, L.nei, Hp, 0, Hp, s));
     return GGPM_OK;
@@ -532,7 +548,7 @@ static int encoder_forward_impl(const ggpm_enc_dims* dims, float* const* params,
     // ---- atom level (embed_graph, graph_encoder)
     CK(ggpm_embed_graph(gfnode, d.N1g, gfmess, d.E1g, d.atom, 4, 20, S.hnode_a, d.ld_n, S.hmess_a, d.ld_m, stream));
     CK(level_forward(d, d.E1g, d.N1g, d.Ig, d.depthG, S.hmess_a, d.ld_m, P, 2, S.gpred, S.gagr, S.lv[2], stream));
-    CK(linear2(d.N1g, H, S.hnode_a, d.ld_n, d.atom, S.lv[2].nei, Hp, H, P[lwo(d.lstm, 2)], P[lbo(d.lstm, 2)], GGPM_ACT_RELU, 1,
+    CK(linear2(d.N1g, H, S.hnode_a, d.ld_n, d.atom, S.lv[2].nei, Hp, H, P[lwo(d, 2)], P[lbo(d, 2)], GGPM_ACT_RELU, 1,
                hatom, Hp, stream));
     CK(drop(d, hatom, d.N1g, H, Hp, DS_WO_ATOM, stream));
 
@@ -545,7 +561,7 @@ static int encoder_forward_impl(const ggpm_enc_dims* dims, float* const* params,
     CK(drop(d, S.hnode_i, d.N1t, H, Hp, DS_WI, stream));
     CK(ggpm_gather_rows(S.hnode_i, Hp, S.src, d.E1t, H, S.hmess_i, d.ld_t, 0, 0, stream));
     CK(level_forward(d, d.E1t, d.N1t, d.It, d.depthT, S.hmess_i, d.ld_t, P, 1, S.tpred, S.tagr, S.lv[1], stream));
-    CK(linear2(d.N1t, H, S.hnode_i, Hp, H, S.lv[1].nei, Hp, H, P[lwo(d.lstm, 1)], P[lbo(d.lstm, 1)], GGPM_ACT_RELU, 1, hinter, Hp,
+    CK(linear2(d.N1t, H, S.hnode_i, Hp, H, S.lv[1].nei, Hp, H, P[lwo(d, 1)], P[lbo(d, 1)], GGPM_ACT_RELU, 1, hinter, Hp,
                stream));
     CK(drop(d, hinter, d.N1t, H, Hp, DS_WO_INTER, stream));
 
@@ -554,7 +570,7 @@ static int encoder_forward_impl(const ggpm_enc_dims* dims, float* const* params,
     CK(drop(d, S.hnode_t, d.N1t, H, Hp, DS_WC, stream));
     CK(ggpm_gather_rows(S.hnode_t, Hp, S.src, d.E1t, H, S.hmess_t, d.ld_t, 0, 0, stream));
     CK(level_forward(d, d.E1t, d.N1t, d.It, d.depthT, S.hmess_t, d.ld_t, P, 0, S.tpred, S.tagr, S.lv[0], stream));
-    CK(linear2(d.N1t, H, S.hnode_t, Hp, H, S.lv[0].nei, Hp, H, P[lwo(d.lstm, 0)], P[lbo(d.lstm, 0)], GGPM_ACT_RELU, 1, hnode, Hp,
+    CK(linear2(d.N1t, H, S.hnode_t, Hp, H, S.lv[0].nei, Hp, H, P[lwo(d, 0)], P[lbo(d, 0)], GGPM_ACT_RELU, 1, hnode, Hp,
                stream));
     CK(drop(d, hnode, d.N1t, H, Hp, DS_WO_TREE, stream));
 
@@ -615,10 +631,8 @@ void layout_work(Arena& A, const Dims& d, BwdWork& w) {
     w.d_hnode_i = A.take<float>((size_t)d.N1t * Hp); w.d_nei_i = A.take<float>((size_t)d.N1t * Hp);
     w.d_pooled = A.take<float>((size_t)d.N1t * Hp);
     w.d_nei_g = A.take<float>((size_t)d.N1g * Hp);
-    size_t lw = d.lstm ? ggpm_lstm_backward_workspace_bytes(d.E1g, d.H, d.depthG)
-                       : ggpm_gru_backward_workspace_bytes(d.E1g, d.H, d.depthG);
-    const size_t lwt = d.lstm ? ggpm_lstm_backward_workspace_bytes(d.E1t, d.H, d.depthT)
-                              : ggpm_gru_backward_workspace_bytes(d.E1t, d.H, d.depthT);
+    const size_t lw = ggpm_level_backward_workspace_bytes(d.lstm, d.E1g, d.H, d.depthG);
+    const size_t lwt = ggpm_level_backward_workspace_bytes(d.lstm, d.E1t, d.H, d.depthT);
     w.level_work_bytes = lw > lwt ? lw : lwt;
     w.level_work = A.take<float>(3 * (w.level_work_bytes / 4 + 64));      // one per level (stashes read by stream 2)
     size_t sk = 0;
@@ -629,9 +643,8 @@ void layout_work(Arena& A, const Dims& d, BwdWork& w) {
     w.skws_bytes = sk + 1024;
     w.skws = A.take<float>(w.skws_bytes / 4);
     w.csws = A.take<float>((size_t)256 * (Hp > d.ld_t ? Hp : d.ld_t));
-    const int gates = d.lstm ? 4 : 3;
-    const size_t xa = ggpm_gemm_grouped_splitk_workspace_bytes(d.H, d.It, d.E1t, gates);
-    const size_t xb = ggpm_gemm_grouped_splitk_workspace_bytes(d.H, d.Ig, d.E1g, gates);
+    const size_t xa = ggpm_gemm_grouped_splitk_workspace_bytes(d.H, d.It, d.E1t, d.nX);
+    const size_t xb = ggpm_gemm_grouped_splitk_workspace_bytes(d.H, d.Ig, d.E1g, d.nX);
     w.xws_bytes = (xa > xb ? xa : xb) + 256;
     for (int l = 0; l < 3; ++l) {
         w.xws[l] = A.take<float>(w.xws_bytes / 4);
@@ -730,9 +743,9 @@ int level_backward(const Dims& d, int E1, int I, int depth, const float* x, int 
                    int level, const Csr& pred, const LevelSaved& L, const float* dHD, float* dX, float* level_work,
                    float* dx, int lddx, BwdWork& w, Streams& st) {
     const int H = d.H, Hp = d.Hp;
-    const size_t slot = (size_t)E1 * Hp, ds = (size_t)depth * slot;
+    const size_t slot = (size_t)E1 * Hp;
     const int blo = backward_lo(d, level, depth, E1);
-    struct Tag { Tag(int level) { ggpm_timing_tag(3 - level); } ~Tag() { ggpm_timing_tag(0); } } tag(level);
+    const LevelTag tag(level);
     // no input gradient wanted (the atom level: one-hot inputs): the summed gate-input gradients are not needed on this
     // stream at all -- the depth launches skip their read-modify-write and the second stream sums the stashed gate
     // gradients before it contracts them (GGPM_SKIP_XSUM=0: per-depth accumulation everywhere)
@@ -742,126 +755,67 @@ int level_backward(const Dims& d, int E1, int I, int depth, const float* x, int 
     o.lo = blo;                   // (the backward and its weight-gradient call alike)
     o.fixed_slot = fixed_slot(d, level, depth, E1);
     o.skip_x_sums = skip_xsum;
-    if (d.lstm) {
-        const float* W[4] = {P[lq(level, Q_WI)], P[lq(level, Q_WOG)], P[lq(level, Q_WU)], P[lq(level, Q_WF)]};
-        float* dW[4] = {G[lq(level, Q_WI)], G[lq(level, Q_WOG)], G[lq(level, Q_WU)], G[lq(level, Q_WF)]};
-        float* db[4] = {G[lq(level, Q_BI)], G[lq(level, Q_BOG)], G[lq(level, Q_BU)], G[lq(level, Q_BF)]};
-        CK(ggpm_lstm_backward(E1, H, depth, L.X + 3 * slot, W[0] + I, I + H, W[1] + I, I + H, W[2] + I, I + H, W[3] + I, I + H,
-                              pred.rowptr, pred.col, pred.rowptrT, pred.colT, L.Hs, L.Cs, L.Qs, L.St, L.St + ds,
-                              L.St + 2 * ds, L.St + 3 * ds, L.St + 4 * ds, dHD, dX, dX + slot, dX + 2 * slot, dX + 3 * slot,
-                              dW[0] + I, I + H, dW[1] + I, I + H, dW[2] + I, I + H, dW[3] + I, I + H, level_work,
-                              w.level_work_bytes, 0, &o, st.main));
-        if (dx) {       // dx = sum over the gates of dX_k W_k[:, :I]: one launch over four K segments
-            const float* A[4] = {dX, dX + slot, dX + 2 * slot, dX + 3 * slot};
-            const int lda[4] = {Hp, Hp, Hp, Hp}, ldb[4] = {I + H, I + H, I + H, I + H}, K[4] = {H, H, H, H};
-            CK(ggpm_gemm_ksegments(0, E1, I, 4, A, lda, W, ldb, K, dx, lddx, lddx, nullptr, 0, GGPM_ACT_NONE, 0, st.main));
-        }
-        CK(st.side_after_main());
-        const ggpm_stream_t sw = st.w();
-        const BwdWork wc = w;
-        float* const dW0 = dW[0]; float* const dW1 = dW[1]; float* const dW2 = dW[2]; float* const dW3 = dW[3];
-        float* const db0 = db[0]; float* const db1 = db[1]; float* const db2 = db[2]; float* const db3 = db[3];
-        const float* Hs = L.Hs; const float* St = L.St;
-        // input halves + bias sums from the summed gate-input gradients
-        auto x_part = [=](ggpm_stream_t sx) -> int {
-            float* const dWk[4] = {dW0, dW1, dW2, dW3};
-            float* const dbk[4] = {db0, db1, db2, db3};
-            if (skip_xsum) {
-                float *DI = nullptr, *DO = nullptr, *DU = nullptr;
-                CK(ggpm_lstm_backward_stashes(level_work, E1, H, depth, &DI, &DO, &DU));
-                const int lo_ = blo < 1 ? 1 : blo;      // backward steps depth .. lo ran: stash slots lo-1 .. depth-1
-                float* const src[3] = {DI, DO, DU};
-                const bool b16 = bf16_stored(d, E1);    // (then lo_ == 1 and the stashes are bf16 in the first half of their buffers)
-                for (int k = 0; k < 3; ++k)
-                    CK(ggpm_sum_slots_any(src[k] + (b16 ? 0 : (size_t)(lo_ - 1) * slot), depth - lo_ + 1, slot, dX + (size_t)k * slot,
-                                          b16, sx));
-            }
-            // (the light column sums first, the products last: see the GRU branch)
-            for (int k = 0; k < 4; ++k) CK(ggpm_colsum(dX + k * slot, Hp, E1, H, dbk[k], wc.xcs[level], sx));
-            if (ggpm_gemm_prefers_grouped(H, I, E1, 4)) {      // the four in one launch
-                GgpmGemmProblem gp[4];
-                for (int k = 0; k < 4; ++k) gp[k] = {dX + k * slot, Hp, x, ldx, dWk[k], I + H, I, nullptr, 0, GGPM_ACT_NONE, 0};
-                CK(ggpm_gemm_grouped_splitk(1, 0, H, I, E1, 4, gp, wc.xws[level], wc.xws_bytes, sx));
-            } else {
-                for (int k = 0; k < 4; ++k)
-                    CK(ggpm_gemm(1, 0, H, I, E1, dX + k * slot, Hp, x, ldx, dWk[k], I + H, I, nullptr, 0, GGPM_ACT_NONE, 0,
-                                 wc.skws, wc.skws_bytes, sx));
-            }
-            return GGPM_OK;
-        };
-        // a level with nothing behind it on this stream (the atom level: no input gradient): its input halves run HERE,
-        // beside the tall contractions on the second stream, instead of behind them
-        const bool x_on_main = skip_xsum && st.side != nullptr && split_tail_enabled();
-        const int rc_side = st.on_side([=]() -> int {
-            float* const dWk[4] = {dW0, dW1, dW2, dW3};
-            if (!x_on_main) CK(x_part(sw));
-            CK(ggpm_lstm_weight_grads(E1, H, depth, Hs, St, level_work, wc.level_work_bytes, dWk[0] + I, I + H, dWk[1] + I,
-                                      I + H, dWk[2] + I, I + H, dWk[3] + I, I + H, &o, sw));
-            return GGPM_OK;
-        });
-        if (rc_side) return rc_side;
-        return x_on_main ? x_part(st.main) : GGPM_OK;
+    const CellGates cg = cell_gates(d.lstm);
+    const LevelSlots gs = gate_slots(d.lstm, level, I, H);
+    LevelCall c = level_call(d, E1, I, depth, P, gs, pred, L);
+    float *dWx[4] = {}, *db[4] = {};          // gate k's whole weight gradient (its input half leads it) and bias gradient
+    c.d_out = dHD;
+    for (int k = 0; k < cg.n; ++k) {
+        dWx[k] = G[gs.w[k]];
+        db[k] = gs.b[k] < 0 ? nullptr : G[gs.b[k]];
+        c.dX[k] = dX + k * slot;
+        c.dW[k] = cg.full[k] ? dWx[k] + I : G[gs.ur];
+        c.ld_dw[k] = cg.full[k] ? gs.ld[k] : H;
     }
-    const float *Wz = P[lp(level, L_WZ)], *Wr = P[lp(level, L_WR)], *Wh = P[lp(level, L_WH)];
-    float *dWz = G[lp(level, L_WZ)], *dWr = G[lp(level, L_WR)], *dWh = G[lp(level, L_WH)], *dUr = G[lp(level, L_UR)];
-    CK(ggpm_gru_backward(E1, H, depth, L.X + slot, Wz + I, I + H, P[lp(level, L_UR)], H, Wh + I, I + H,
-                             pred.rowptr, pred.col, pred.rowptrT, pred.colT, L.Hs,
-                             L.Qs, L.St, L.St + ds, L.St + 2 * ds, L.St + 3 * ds, L.St + 4 * ds, dHD, dX, dX + slot,
-                             dX + 2 * slot, dWz + I, I + H, dUr, H, G[lp(level, L_BU)], dWh + I, I + H, level_work,
-                             w.level_work_bytes, 0, &o, st.main));
-    if (dx) {       // needed upstream right away: main stream
-        // dx = dX_z W_z[:, :I] + dX_r W_r + dX_h W_h[:, :I]: one launch over three K segments
-        const float* A[3] = {dX, dX + slot, dX + 2 * slot};
-        const float* B[3] = {Wz, Wr, Wh};
-        const int lda[3] = {Hp, Hp, Hp}, ldb[3] = {I + H, I, I + H}, K[3] = {H, H, H};
-        CK(ggpm_gemm_ksegments(0, E1, I, 3, A, lda, B, ldb, K, dx, lddx, lddx, nullptr, 0, GGPM_ACT_NONE, 0, st.main));
+    c.dbu = gs.bu < 0 ? nullptr : G[gs.bu];
+    c.work = level_work; c.work_bytes = w.level_work_bytes;
+    CK(ggpm_level_backward(c, 0, &o, st.main));
+    if (dx) {       // needed upstream right away: main stream.  dx = sum over the gates of dX_k W_k[:, :I]: one launch, K segments
+        const float *A[4], *B[4];
+        int lda[4], K[4];
+        for (int k = 0; k < cg.n; ++k) { A[k] = c.dX[k]; B[k] = P[gs.w[k]]; lda[k] = Hp; K[k] = H; }
+        CK(ggpm_gemm_ksegments(0, E1, I, cg.n, A, lda, B, gs.ld, K, dx, lddx, lddx, nullptr, 0, GGPM_ACT_NONE, 0, st.main));
     }
     CK(st.side_after_main());
     const ggpm_stream_t sw = st.w();
     const BwdWork wc = w;
-    const float* Hs = L.Hs; const float* St = L.St;
-    float* const dbu = G[lp(level, L_BU)]; float* const dbz = G[lp(level, L_BZ)]; float* const dbh = G[lp(level, L_BH)];
     // a level with nothing behind it on this stream (the atom level: no input gradient): its input halves run HERE, beside
     // the tall contractions on the second stream, instead of behind them
     const bool x_on_main = skip_xsum && st.side != nullptr && split_tail_enabled();
-    const bool bu_here = x_on_main;
     auto x_part = [=](ggpm_stream_t sx) -> int {       // input halves + bias sums from the summed gate-input gradients
         if (skip_xsum) {
-            float *DMP = nullptr, *DZP = nullptr;
-            CK(ggpm_gru_backward_stashes(level_work, E1, H, depth, &DMP, &DZP));
+            float* stash[3] = {};
+            CK(c.lstm ? ggpm_lstm_backward_stashes(c.work, E1, H, depth, &stash[0], &stash[1], &stash[2])
+                      : ggpm_gru_backward_stashes(c.work, E1, H, depth, &stash[0], &stash[1]));
             const int lo_ = blo < 1 ? 1 : blo;          // backward steps depth .. lo ran: stash slots lo-1 .. depth-1
             const bool b16 = bf16_stored(d, E1);        // (then lo_ == 1 and the stashes are bf16 in the first half of their buffers)
-            CK(ggpm_sum_slots_any(DZP + (b16 ? 0 : (size_t)(lo_ - 1) * slot), depth - lo_ + 1, slot, dX, b16, sx));
-            CK(ggpm_sum_slots_any(DMP + (b16 ? 0 : (size_t)(lo_ - 1) * slot), depth - lo_ + 1, slot, dX + 2 * slot, b16, sx));
+            for (int i = 0; i < cg.n_sum; ++i)
+                CK(ggpm_sum_slots_any(stash[cg.sum[i].stash] + (b16 ? 0 : (size_t)(lo_ - 1) * slot), depth - lo_ + 1, slot,
+                                      c.dX[cg.sum[i].plane], b16, sx));
         }
         // the light column sums first, the products last: beside the tall contractions of the second stream (one 129 KB
         // workgroup on every CU) a 600-workgroup product takes 145 us instead of 20, and whatever follows it on this stream
         // ends the step -- so what follows it is nothing
-        CK(ggpm_colsum(dX, Hp, E1, H, dbz, wc.xcs[level], sx));
-        CK(ggpm_colsum(dX + 2 * slot, Hp, E1, H, dbh, wc.xcs[level], sx));
-        // db_u here too when this part has the main stream to itself: the second stream then ends with the tall contraction
-        if (bu_here) CK(ggpm_gru_bias_u_grad(E1, H, depth, blo, level_work, dbu, wc.xcs[level], &o, sx));
-        if (ggpm_gemm_prefers_grouped(H, I, E1, 3)) {      // the three in one launch
-            const GgpmGemmProblem gp[3] = {{dX, Hp, x, ldx, dWz, I + H, I, nullptr, 0, GGPM_ACT_NONE, 0},
-                                           {dX + slot, Hp, x, ldx, dWr, I, I, nullptr, 0, GGPM_ACT_NONE, 0},
-                                           {dX + 2 * slot, Hp, x, ldx, dWh, I + H, I, nullptr, 0, GGPM_ACT_NONE, 0}};
-            CK(ggpm_gemm_grouped_splitk(1, 0, H, I, E1, 3, gp, wc.xws[level], wc.xws_bytes, sx));
+        for (int k = 0; k < cg.n; ++k)
+            if (cg.full[k]) CK(ggpm_colsum(c.dX[k], Hp, E1, H, db[k], wc.xcs[level], sx));
+        // GRU: db_u here too when this part has the main stream to itself: the second stream then ends with the tall contraction
+        if (!c.lstm && x_on_main) CK(ggpm_gru_bias_u_grad(E1, H, depth, blo, c.work, c.dbu, wc.xcs[level], &o, sx));
+        if (ggpm_gemm_prefers_grouped(H, I, E1, cg.n)) {      // the input halves in one launch
+            GgpmGemmProblem gp[4];
+            for (int k = 0; k < cg.n; ++k) gp[k] = {c.dX[k], Hp, x, ldx, dWx[k], gs.ld[k], I, nullptr, 0, GGPM_ACT_NONE, 0};
+            CK(ggpm_gemm_grouped_splitk(1, 0, H, I, E1, cg.n, gp, wc.xws[level], wc.xws_bytes, sx));
         } else {
-            CK(ggpm_gemm(1, 0, H, I, E1, dX, Hp, x, ldx, dWz, I + H, I, nullptr, 0, GGPM_ACT_NONE, 0, wc.skws, wc.skws_bytes, sx));
-            CK(ggpm_gemm(1, 0, H, I, E1, dX + slot, Hp, x, ldx, dWr, I, I, nullptr, 0, GGPM_ACT_NONE, 0, wc.skws, wc.skws_bytes,
-                         sx));
-            CK(ggpm_gemm(1, 0, H, I, E1, dX + 2 * slot, Hp, x, ldx, dWh, I + H, I, nullptr, 0, GGPM_ACT_NONE, 0, wc.skws,
-                         wc.skws_bytes, sx));
+            for (int k = 0; k < cg.n; ++k)
+                CK(ggpm_gemm(1, 0, H, I, E1, c.dX[k], Hp, x, ldx, dWx[k], gs.ld[k], I, nullptr, 0, GGPM_ACT_NONE, 0, wc.skws,
+                             wc.skws_bytes, sx));
         }
         return GGPM_OK;
     };
     ggpm_level_opts wo = o;
-    wo.skip_bias_u = bu_here;
+    wo.skip_bias_u = x_on_main;          // (GRU: formed above)
     const int rc_side = st.on_side([=]() -> int {
         if (!x_on_main) CK(x_part(sw));
-        CK(ggpm_gru_weight_grads(E1, H, depth, Hs, St, St + ds, level_work, wc.level_work_bytes, dWz + I, I + H, dUr, H,
-                                 dbu, dWh + I, I + H, &wo, sw));
-        return GGPM_OK;
+        return ggpm_level_weight_grads(c, &wo, sw);
     });
     if (rc_side) return rc_side;
     return x_on_main ? x_part(st.main) : GGPM_OK;
@@ -954,10 +908,10 @@ extern "C" int ggpm_encoder_backward(const ggpm_enc_dims* dims, float* const* pa
     if (d_hnode) {
         CK(ggpm_act_backward(d_hnode, hnode, d.N1t, H, Hp, GGPM_ACT_RELU, 1, dpre[0], stream));
         CK(drop(d, dpre[0], d.N1t, H, Hp, DS_WO_TREE, stream));     // d(dropout) commutes with the ReLU mask
-        CK(linear2_dx(d.N1t, H, H, dpre[0], Hp, P[lwo(d.lstm, 0)], w.d_hnode_t, Hp, 1, w.d_nei_t, Hp, 1, stream));
-        CK(linear2_wgrad(d.N1t, H, dpre[0], Hp, S.hnode_t, Hp, H, S.lv[0].nei, Hp, H, G[lwo(d.lstm, 0)], G[lbo(d.lstm, 0)], w, st));
+        CK(linear2_dx(d.N1t, H, H, dpre[0], Hp, P[lwo(d, 0)], w.d_hnode_t, Hp, 1, w.d_nei_t, Hp, 1, stream));
+        CK(linear2_wgrad(d.N1t, H, dpre[0], Hp, S.hnode_t, Hp, H, S.lv[0].nei, Hp, H, G[lwo(d, 0)], G[lbo(d, 0)], w, st));
     } else {
-        float* const gw = G[lwo(d.lstm, 0)]; float* const gb = G[lbo(d.lstm, 0)];
+        float* const gw = G[lwo(d, 0)]; float* const gb = G[lbo(d, 0)];
         const ggpm_stream_t sw = st.w();
         CK(st.on_side([=]() -> int {
             (void)hipMemsetAsync(gw, 0, (size_t)H * 2 * H * sizeof(float), (hipStream_t)sw);
@@ -985,8 +939,8 @@ extern "C" int ggpm_encoder_backward(const ggpm_enc_dims* dims, float* const* pa
 
     // ---- attachment level: W_o, message function, W_i / E_i, pooling over atoms
     CK(drop(d, dpre[2], d.N1t, H, Hp, DS_WO_INTER, stream));
-    CK(linear2_dx(d.N1t, H, H, dpre[2], Hp, P[lwo(d.lstm, 1)], w.d_hnode_i, Hp, 0, w.d_nei_i, Hp, 0, stream));
-    CK(linear2_wgrad(d.N1t, H, dpre[2], Hp, S.hnode_i, Hp, H, S.lv[1].nei, Hp, H, G[lwo(d.lstm, 1)], G[lbo(d.lstm, 1)], w, st));
+    CK(linear2_dx(d.N1t, H, H, dpre[2], Hp, P[lwo(d, 1)], w.d_hnode_i, Hp, 0, w.d_nei_i, Hp, 0, stream));
+    CK(linear2_wgrad(d.N1t, H, dpre[2], Hp, S.hnode_i, Hp, H, S.lv[1].nei, Hp, H, G[lwo(d, 1)], G[lbo(d, 1)], w, st));
     CK(ggpm_segment_sum(w.d_nei_i, Hp, S.tagr.rowptrT, S.tagr.colT, d.E1t, H, w.d_h, Hp, 0, Hp, stream));
     CK(level_backward(d, d.E1t, d.It, d.depthT, S.hmess_i, d.ld_t, P, G, 1, S.tpred, S.lv[1], w.d_h, dXl[1], lwork[1],
                       w.dx_mess, d.ld_t, w, st));
@@ -1015,9 +969,9 @@ extern "C" int ggpm_encoder_backward(const ggpm_enc_dims* dims, float* const* pa
 
     // ---- atom level: W_o, message function (its inputs are constants)
     CK(drop(d, dpre[4], d.N1g, H, Hp, DS_WO_ATOM, stream));
-    CK(ggpm_gemm(0, 0, d.N1g, H, H, dpre[4], Hp, P[lwo(d.lstm, 2)] + d.atom, d.atom + H, w.d_nei_g, Hp, Hp, nullptr, 0,
+    CK(ggpm_gemm(0, 0, d.N1g, H, H, dpre[4], Hp, P[lwo(d, 2)] + d.atom, d.atom + H, w.d_nei_g, Hp, Hp, nullptr, 0,
                  GGPM_ACT_NONE, 0, nullptr, 0, stream));
-    CK(linear2_wgrad(d.N1g, H, dpre[4], Hp, S.hnode_a, d.ld_n, d.atom, S.lv[2].nei, Hp, H, G[lwo(d.lstm, 2)], G[lbo(d.lstm, 2)], w,
+    CK(linear2_wgrad(d.N1g, H, dpre[4], Hp, S.hnode_a, d.ld_n, d.atom, S.lv[2].nei, Hp, H, G[lwo(d, 2)], G[lbo(d, 2)], w,
                      st));
     CK(ggpm_segment_sum(w.d_nei_g, Hp, S.gagr.rowptrT, S.gagr.colT, d.E1g, H, w.d_h, Hp, 0, Hp, stream));
     CK(level_backward(d, d.E1g, d.Ig, d.depthG, S.hmess_a, d.ld_m, P, G, 2, S.gpred, S.lv[2], w.d_h, dXl[2], lwork[2],

@@ -21,6 +21,7 @@
 // on a second stream.  sparse_forward (rows with a `frozen` mask) reuses the same kernels.
 #include "tile_mma.h"
 #include "level_host.h"
+#include "level_call.h"
 #include <cstdlib>
 #include <cstdio>
 
@@ -848,21 +849,19 @@ __global__ void sparse_init_state(const float* __restrict__ h_in, const unsigned
 }
 }  // namespace
 
-static int gru_forward_impl(int E1, int H, int depth, const float* Xz, const float* Xr, const float* Xh,
-                            const float* Wz_h, int ld_wz, const float* Ur, int ld_ur, const float* bu,
-                            const float* Wh_h, int ld_wh, const int32_t* pred_rowptr, const int32_t* pred_col,
-                            float* Hs, float* Qs, float* Ss, float* Gs, float* Zs, float* Ms, float* Rs,
-                            float* wpack, int save_for_backward, const float* h_in, const unsigned char* frozen,
-                            const ggpm_level_opts& o, ggpm_stream_t stream) {
+int gru_forward_impl(const LevelCall& c, int save_for_backward, const ggpm_level_opts& o, ggpm_stream_t stream) {
     GGPM_CLEAR_STALE_ERROR();
-    if (E1 <= 0 || H <= 0 || depth <= 0 || !Xz || !Xr || !Xh || !Wz_h || !Ur || !bu || !Wh_h || !pred_rowptr ||
-        !pred_col || !Hs || !Qs || !wpack)
-        return GGPM_ERR_ARG;
-    if (save_for_backward && (!Ss || !Gs || !Zs || !Ms || !Rs)) return GGPM_ERR_ARG;
+    const int E1 = c.rows, H = c.H, depth = c.depth;
+    float *Hs = c.Hs, *Qs = c.Qs, *wpack = c.wpack;
+    const unsigned char* frozen = c.frozen;
+    bool ok = E1 > 0 && H > 0 && depth > 0 && c.bu && c.pred_rowptr && c.pred_col && Hs && Qs && wpack;
+    for (int k = 0; k < 3; ++k) ok = ok && c.X[k] && c.W[k];
+    for (int k = 0; k < 5; ++k) ok = ok && (c.St[k] || !save_for_backward);
+    if (!ok) return GGPM_ERR_ARG;
     const int Hp = ggpm_padded_hidden(H);
     if (!GruCell::shape_ok(E1, Hp)) return GGPM_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
-    const size_t HH = (size_t)Hp * Hp, slot = (size_t)E1 * Hp;
+    const size_t slot = (size_t)E1 * Hp;
     const LevelPlan plan = level_plan<GruCell>(o, E1, Hp, frozen != nullptr);
     const bool rt2 = plan.rt2;
     const int bf16 = plan.gm;      // gate mode 0 / 1 / 2
@@ -871,8 +870,8 @@ static int gru_forward_impl(int E1, int H, int depth, const float* Xz, const flo
     float* pbu = wpack + 3 * ggpm_packed_matrix_slot(Hp);
     {
         GgpmPackArgs pk = {};
-        pk.W[0] = Wz_h; pk.ldw[0] = ld_wz; pk.W[1] = Wh_h; pk.ldw[1] = ld_wh; pk.W[2] = Ur; pk.ldw[2] = ld_ur;
-        pk.H = H; pk.Hp = Hp; pk.transpose = 0; pk.dst = wpack; pk.bias = bu; pk.bias_out = pbu; pk.bf16 = bf16;
+        pk.W[0] = c.W[0]; pk.ldw[0] = c.ldw[0]; pk.W[1] = c.W[2]; pk.ldw[1] = c.ldw[2]; pk.W[2] = c.W[1]; pk.ldw[2] = c.ldw[1];
+        pk.H = H; pk.Hp = Hp; pk.transpose = 0; pk.dst = wpack; pk.bias = c.bu; pk.bias_out = pbu; pk.bf16 = bf16;
         if (!o.weights_packed) ggpm_launch_pack(pk, 3, s);
     }
     dim3 ig(ggpm_ceil_div(Hp, 256), E1);
@@ -881,7 +880,7 @@ static int gru_forward_impl(int E1, int H, int depth, const float* Xz, const flo
     if (frozen) {      // sparse_forward: start from the caller's state, q^0 = U_r h^0 + b_u by one B launch
         // (h_in == Hs: the caller put the masked start state -- frozen rows' states, zero elsewhere -- into slot 0 itself;
         // ggpm_level_opts.gather_*: the q^0 launch fetches it through the index and writes slot 0 on the way)
-        if (h_in != Hs && !gathered) sparse_init_state<<<ig, 256, 0, s>>>(h_in, frozen, Hs, Hp);
+        if (c.h_in != Hs && !gathered) sparse_init_state<<<ig, 256, 0, s>>>(c.h_in, frozen, Hs, Hp);
         GruFwdArgs a0 = {};
         a0.E1 = E1; a0.Hp = Hp; a0.tg = tg0; a0.Hnew = Hs; a0.Qnew = Qs; a0.Ur = pUr; a0.bu = pbu; a0.bf16 = bf16;
         if (gathered) { a0.src_h = o.gather_h; a0.src_idx = o.gather_idx; }
@@ -907,8 +906,8 @@ static int gru_forward_impl(int E1, int H, int depth, const float* Xz, const flo
     for (int t = 1; t <= run_depth; ++t) {
         const bool stash = save_for_backward && (!fs || t == fs);
         GruFwdArgs a = {};
-        a.E1 = E1; a.Hp = Hp; a.tg = tg; a.Xz = Xz; a.Xr = Xr; a.Xh = Xh;
-        a.Wz = pWz; a.Wh = pWh; a.Ur = pUr; a.bu = pbu; a.rowptr = pred_rowptr; a.col = pred_col;
+        a.E1 = E1; a.Hp = Hp; a.tg = tg; a.Xz = c.X[0]; a.Xr = c.X[1]; a.Xh = c.X[2];
+        a.Wz = pWz; a.Wh = pWh; a.Ur = pUr; a.bu = pbu; a.rowptr = c.pred_rowptr; a.col = c.pred_col;
         a.ablate = abl ? atoi(abl) : 0;
         a.frozen = frozen;
         a.bf16 = bf16;
@@ -919,9 +918,9 @@ static int gru_forward_impl(int E1, int H, int depth, const float* Xz, const flo
             a.Hout = (st16 && t == depth) ? Hs + (size_t)depth * slot : nullptr;      // the level's result stays fp32, at its usual place
             a.Qprev = ggpm_slot_ptr(Qs, t - 1, slot, st16);
             a.Qnew = (t < depth) ? ggpm_slot_ptr(Qs, t, slot, st16) : nullptr;   // q^depth is never consumed
-            a.S = ggpm_slot_ptr(Ss, t - 1, slot, st16); a.G = ggpm_slot_ptr(Gs, t - 1, slot, st16);
-            a.Z = ggpm_slot_ptr(Zs, t - 1, slot, st16); a.M = ggpm_slot_ptr(Ms, t - 1, slot, st16);
-            a.R = Rs + (size_t)(t - 1) * slot;
+            a.S = ggpm_slot_ptr(c.St[0], t - 1, slot, st16); a.G = ggpm_slot_ptr(c.St[1], t - 1, slot, st16);
+            a.Z = ggpm_slot_ptr(c.St[2], t - 1, slot, st16); a.M = ggpm_slot_ptr(c.St[3], t - 1, slot, st16);
+            a.R = c.St[4] + (size_t)(t - 1) * slot;
             if (!stash) a.S = a.G = a.Z = a.M = a.R = nullptr;
         } else if (infer) {
             a.Hprev = ggpm_slot_ptr(Hs, (t - 1) & 1, slot, st16); a.Hnew = ggpm_slot_ptr(Hs, t & 1, slot, st16);
@@ -942,15 +941,22 @@ static int gru_forward_impl(int E1, int H, int depth, const float* Xz, const flo
     return GGPM_OK;
 }
 
+// the operands both forward entry points name, by the parameter names they share
+#define GRU_FORWARD_OPERANDS(c) \
+    c.rows = E1; c.H = H; c.depth = depth; \
+    c.X[0] = Xz; c.X[1] = Xr; c.X[2] = Xh; \
+    c.W[0] = Wz_h; c.ldw[0] = ld_wz; c.W[1] = Ur; c.ldw[1] = ld_ur; c.W[2] = Wh_h; c.ldw[2] = ld_wh; c.bu = bu; \
+    c.pred_rowptr = pred_rowptr; c.pred_col = pred_col; \
+    c.Hs = Hs; c.Qs = Qs; c.St[0] = Ss; c.St[1] = Gs; c.St[2] = Zs; c.St[3] = Ms; c.St[4] = Rs; c.wpack = wpack;
 extern "C" int ggpm_gru_forward(int E1, int H, int depth, const float* Xz, const float* Xr, const float* Xh,
                                 const float* Wz_h, int ld_wz, const float* Ur, int ld_ur, const float* bu,
                                 const float* Wh_h, int ld_wh, const int32_t* pred_rowptr,
                                 const int32_t* pred_col, float* Hs, float* Qs, float* Ss, float* Gs, float* Zs,
                                 float* Ms, float* Rs, float* wpack, int save_for_backward,
                                 const ggpm_level_opts* opts, ggpm_stream_t stream) {
-    return gru_forward_impl(E1, H, depth, Xz, Xr, Xh, Wz_h, ld_wz, Ur, ld_ur, bu, Wh_h, ld_wh, pred_rowptr, pred_col,
-                            Hs, Qs, Ss, Gs, Zs, Ms, Rs, wpack, save_for_backward, nullptr, nullptr, ggpm_opts_or_default(opts),
-                            stream);
+    LevelCall c = {};
+    GRU_FORWARD_OPERANDS(c);
+    return gru_forward_impl(c, save_for_backward, ggpm_opts_or_default(opts), stream);
 }
 
 extern "C" int ggpm_gru_sparse_forward(int E1, int H, int depth, const float* h_in, const unsigned char* frozen,
@@ -961,19 +967,16 @@ extern "C" int ggpm_gru_sparse_forward(int E1, int H, int depth, const float* h_
                                        float* wpack, int save_for_backward, const ggpm_level_opts* opts,
                                        ggpm_stream_t stream) {
     if (!h_in || !frozen) return GGPM_ERR_ARG;
-    return gru_forward_impl(E1, H, depth, Xz, Xr, Xh, Wz_h, ld_wz, Ur, ld_ur, bu, Wh_h, ld_wh, pred_rowptr, pred_col,
-                            Hs, Qs, Ss, Gs, Zs, Ms, Rs, wpack, save_for_backward, h_in, frozen, ggpm_opts_or_default(opts),
-                            stream);
+    LevelCall c = {};
+    GRU_FORWARD_OPERANDS(c);
+    c.h_in = h_in; c.frozen = frozen;
+    return gru_forward_impl(c, save_for_backward, ggpm_opts_or_default(opts), stream);
 }
+#undef GRU_FORWARD_OPERANDS
 
 extern "C" size_t ggpm_gru_backward_workspace_bytes(int E1, int H, int depth) {
     return backward_workspace_bytes<GruCell>(E1, H, depth);      // (level_host.h: carve)
 }
-
-static int gru_weight_grads_impl(int E1, int H, int depth, const float* Hs, const float* Ss, const float* Gs,
-                                 float* work, size_t work_bytes, float* dWz_h, int ld_dwz, float* dUr, int ld_dur,
-                                 float* dbu, float* dWh_h, int ld_dwh, bool with_slot0, int lo, const ggpm_level_opts& o,
-                                 ggpm_stream_t stream);
 
 // a small pool of re-recordable events (the encoder drivers' stream ordering, encoder.hip)
 hipEvent_t ggpm_wgrad_event(int i) {
@@ -983,28 +986,25 @@ hipEvent_t ggpm_wgrad_event(int i) {
     return pool[i];
 }
 
-static int gru_backward_impl(int E1, int H, int depth, const float* Xr, const float* Wz_h, int ld_wz,
-                                 const float* Ur, int ld_ur, const float* Wh_h, int ld_wh,
-                                 const int32_t* pred_rowptr, const int32_t* pred_col,
-                                 const int32_t* succ_rowptr, const int32_t* succ_col, const float* Hs,
-                                 const float* Qs, const float* Ss, const float* Gs, const float* Zs,
-                                 const float* Ms, const float* Rs, const float* dHD, float* dXz, float* dXr, float* dXh,
-                                 float* dWz_h, int ld_dwz, float* dUr, int ld_dur, float* dbu, float* dWh_h,
-                                 int ld_dwh, float* work, size_t work_bytes, int weight_grads,
-                                 const unsigned char* frozen, float* dHin, const ggpm_level_opts& o, ggpm_stream_t stream) {
+int gru_backward_impl(const LevelCall& c, int weight_grads, const ggpm_level_opts& o, ggpm_stream_t stream) {
     GGPM_CLEAR_STALE_ERROR();
-    if (o.skip_sparse_wgrads && frozen) weight_grads = 0;      // (ggpm_gru_sparse_weight_grads follows, on the caller's choice of stream)
+    const int E1 = c.rows, H = c.H, depth = c.depth;
+    const float *Xr = c.X[GRU_GATES.reread], *Hs = c.Hs, *Qs = c.Qs;
+    float* work = c.work;
+    const unsigned char* frozen = c.frozen;
+    if (o.skip_sparse_wgrads && frozen) weight_grads = 0;      // (ggpm_level_weight_grads follows, on the caller's choice of stream)
     const bool skip_xsum = o.skip_x_sums && !frozen;
     const bool scattered = o.scatter_h && o.scatter_idx && frozen;
-    if (E1 <= 0 || H <= 0 || depth <= 0 || !Xr || !Wz_h || !Ur || !Wh_h || !pred_rowptr || !pred_col ||
-        !succ_rowptr || !succ_col || !Hs || !Qs || !Ss || !Gs || !Zs || !Ms || !Rs || !dHD || !dXz || !dXr || !dXh ||
-        !dWz_h || !dUr || !dbu || !dWh_h || !work)
-        return GGPM_ERR_ARG;
-    if (work_bytes < ggpm_gru_backward_workspace_bytes(E1, H, depth)) return GGPM_ERR_WORKSPACE;
+    bool ok = E1 > 0 && H > 0 && depth > 0 && Xr && c.pred_rowptr && c.pred_col && c.succ_rowptr && c.succ_col && Hs && Qs &&
+              c.d_out && c.dbu && work;
+    for (int k = 0; k < 3; ++k) ok = ok && c.W[k] && c.dX[k] && c.dW[k];
+    for (int k = 0; k < 5; ++k) ok = ok && c.St[k];
+    if (!ok) return GGPM_ERR_ARG;
+    if (c.work_bytes < ggpm_gru_backward_workspace_bytes(E1, H, depth)) return GGPM_ERR_WORKSPACE;
     const int Hp = ggpm_padded_hidden(H);
     if (!GruCell::shape_ok(E1, Hp)) return GGPM_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
-    const size_t HH = (size_t)Hp * Hp, slot = (size_t)E1 * Hp;
+    const size_t slot = (size_t)E1 * Hp;
 
     const LevelPlan plan = level_plan<GruCell>(o, E1, Hp, frozen != nullptr);
     const bool rt2 = plan.rt2;
@@ -1024,12 +1024,12 @@ static int gru_backward_impl(int E1, int H, int depth, const float* Xr, const fl
 
     {
         GgpmPackArgs pk = {};
-        pk.W[0] = Wz_h; pk.ldw[0] = ld_wz; pk.W[1] = Wh_h; pk.ldw[1] = ld_wh; pk.W[2] = Ur; pk.ldw[2] = ld_ur;
+        pk.W[0] = c.W[0]; pk.ldw[0] = c.ldw[0]; pk.W[1] = c.W[2]; pk.ldw[1] = c.ldw[2]; pk.W[2] = c.W[1]; pk.ldw[2] = c.ldw[1];
         pk.H = H; pk.Hp = Hp; pk.transpose = 1; pk.dst = pWzT; pk.bias = nullptr; pk.bias_out = nullptr; pk.bf16 = bf16;
         if (!o.weights_packed) ggpm_launch_pack(pk, 3, s);
     }
     // dXz / dXh are started (not accumulated) by the first backward depth; so is dXr when that depth has a dS/dG product
-    if (depth == 1 && !frozen) (void)hipMemsetAsync(dXr, 0, slot * sizeof(float), s);
+    if (depth == 1 && !frozen) (void)hipMemsetAsync(c.dX[1], 0, slot * sizeof(float), s);
 
     const int tg = plan.tg;
     const double flops1 = 2.0 * (double)(E1 - 1) * H * H;   // algorithmic flops of ONE gate product
@@ -1049,18 +1049,18 @@ static int gru_backward_impl(int E1, int H, int depth, const float* Xr, const fl
         a.st16 = st16 ? 1 : 0;
         a.Hcur = ggpm_slot_ptr(Hs, state_slot(t), slot, st16);
         a.Qcur = (t < depth) ? ggpm_slot_ptr(Qs, state_slot(t), slot, st16) : nullptr;
-        a.S = ggpm_slot_ptr(Ss, stash_slot(t), slot, st16); a.Z = ggpm_slot_ptr(Zs, stash_slot(t), slot, st16);
-        a.M = ggpm_slot_ptr(Ms, stash_slot(t), slot, st16);
-        a.R = Rs + (size_t)stash_slot(t) * slot;
-        a.dHD = dHD;
+        a.S = ggpm_slot_ptr(c.St[0], stash_slot(t), slot, st16); a.Z = ggpm_slot_ptr(c.St[2], stash_slot(t), slot, st16);
+        a.M = ggpm_slot_ptr(c.St[3], stash_slot(t), slot, st16);
+        a.R = c.St[4] + (size_t)stash_slot(t) * slot;
+        a.dHD = c.d_out;
         a.dSin = dSb[(t + 1) & 1]; a.dGin = dGb[(t + 1) & 1];      // (bf16 storage: bf16 in the first half of each buffer)
         a.dSout = dSb[t & 1]; a.dGout = dGb[t & 1];
         a.DQ = (t < depth) ? ggpm_slot_ptr(DQ, t, slot, st16) : nullptr;
         a.frozen = frozen; a.carry = carry; a.final_pass = 0; a.dHin = nullptr;
         a.DMP = ggpm_slot_ptr(DMP, t - 1, slot, st16); a.DZP = ggpm_slot_ptr(DZP, t - 1, slot, st16); a.DSD = DSD;
-        a.dXz = dXz; a.dXr = dXr; a.dXh = dXh;
+        a.dXz = c.dX[0]; a.dXr = c.dX[1]; a.dXh = c.dX[2];
         a.WzT = pWzT; a.WhT = pWhT; a.UrT = pUrT; a.bf16 = bf16;
-        a.srowptr = succ_rowptr; a.scol = succ_col;
+        a.srowptr = c.succ_rowptr; a.scol = c.succ_col;
         a.skip_xsum = skip_xsum ? 1 : 0;
         launch_bwd(a, rt2, t > 1 || frozen != nullptr, flops1, s);     // (the dS/dG launch of step lo > 1 still forms dXr)
     }
@@ -1071,17 +1071,27 @@ static int gru_backward_impl(int E1, int H, int depth, const float* Xr, const fl
         a.E1 = E1; a.Hp = Hp; a.tg = tg; a.first = 0; a.final_pass = 1;
         a.Xr = Xr; a.Hcur = Hs; a.Qcur = Qs;
         a.dSin = dSb[1]; a.dGin = dGb[1];          // written by the B launch of depth 1
-        a.DQ = DQ; a.UrT = pUrT; a.srowptr = succ_rowptr; a.scol = succ_col; a.bf16 = bf16;
-        a.frozen = frozen; a.carry = carry; a.dHin = dHin;
+        a.DQ = DQ; a.UrT = pUrT; a.srowptr = c.succ_rowptr; a.scol = c.succ_col; a.bf16 = bf16;
+        a.frozen = frozen; a.carry = carry; a.dHin = c.d_in;
         if (scattered) { a.scat_h = o.scatter_h; a.scat_idx = o.scatter_idx; }
         launch_bwd(a, rt2, false, flops1, s);
         GGPM_CHECK_LAUNCH();
     }
     if (!weight_grads) return GGPM_OK;
-    return gru_weight_grads_impl(E1, H, depth, Hs, Ss, Gs, work, work_bytes, dWz_h, ld_dwz, dUr, ld_dur, dbu, dWh_h,
-                                 ld_dwh, frozen != nullptr, lo, o, stream);
+    return gru_weight_grads_impl(c, lo, o, stream);
 }
 
+// the operands both backward entry points name, by the parameter names they share
+#define GRU_BACKWARD_OPERANDS(c) \
+    c.rows = E1; c.H = H; c.depth = depth; \
+    c.X[GRU_GATES.reread] = Xr; \
+    c.W[0] = Wz_h; c.ldw[0] = ld_wz; c.W[1] = Ur; c.ldw[1] = ld_ur; c.W[2] = Wh_h; c.ldw[2] = ld_wh; \
+    c.pred_rowptr = pred_rowptr; c.pred_col = pred_col; c.succ_rowptr = succ_rowptr; c.succ_col = succ_col; \
+    c.Hs = level_read(Hs); c.Qs = level_read(Qs); \
+    c.St[0] = level_read(Ss); c.St[1] = level_read(Gs); c.St[2] = level_read(Zs); c.St[3] = level_read(Ms); c.St[4] = level_read(Rs); \
+    c.d_out = dHD; c.dX[0] = dXz; c.dX[1] = dXr; c.dX[2] = dXh; \
+    c.dW[0] = dWz_h; c.ld_dw[0] = ld_dwz; c.dW[1] = dUr; c.ld_dw[1] = ld_dur; c.dW[2] = dWh_h; c.ld_dw[2] = ld_dwh; c.dbu = dbu; \
+    c.work = work; c.work_bytes = work_bytes;
 extern "C" int ggpm_gru_backward(int E1, int H, int depth, const float* Xr, const float* Wz_h, int ld_wz,
                                  const float* Ur, int ld_ur, const float* Wh_h, int ld_wh,
                                  const int32_t* pred_rowptr, const int32_t* pred_col,
@@ -1091,9 +1101,9 @@ extern "C" int ggpm_gru_backward(int E1, int H, int depth, const float* Xr, cons
                                  float* dXh, float* dWz_h, int ld_dwz, float* dUr, int ld_dur, float* dbu,
                                  float* dWh_h, int ld_dwh, float* work, size_t work_bytes, int weight_grads,
                                  const ggpm_level_opts* opts, ggpm_stream_t stream) {
-    return gru_backward_impl(E1, H, depth, Xr, Wz_h, ld_wz, Ur, ld_ur, Wh_h, ld_wh, pred_rowptr, pred_col, succ_rowptr,
-                             succ_col, Hs, Qs, Ss, Gs, Zs, Ms, Rs, dHD, dXz, dXr, dXh, dWz_h, ld_dwz, dUr, ld_dur, dbu,
-                             dWh_h, ld_dwh, work, work_bytes, weight_grads, nullptr, nullptr, ggpm_opts_or_default(opts), stream);
+    LevelCall c = {};
+    GRU_BACKWARD_OPERANDS(c);
+    return gru_backward_impl(c, weight_grads, ggpm_opts_or_default(opts), stream);
 }
 
 // sparse_forward backward: additionally returns dHin (gradient of the incoming state; zero on the recomputed rows)
@@ -1108,28 +1118,29 @@ extern "C" int ggpm_gru_sparse_backward(int E1, int H, int depth, const unsigned
                                         int ld_dwh, float* work, size_t work_bytes, const ggpm_level_opts* opts,
                                         ggpm_stream_t stream) {
     if (!frozen || !dHin) return GGPM_ERR_ARG;
-    return gru_backward_impl(E1, H, depth, Xr, Wz_h, ld_wz, Ur, ld_ur, Wh_h, ld_wh, pred_rowptr, pred_col, succ_rowptr,
-                             succ_col, Hs, Qs, Ss, Gs, Zs, Ms, Rs, dHD, dXz, dXr, dXh, dWz_h, ld_dwz, dUr, ld_dur, dbu,
-                             dWh_h, ld_dwh, work, work_bytes, 1, frozen, dHin, ggpm_opts_or_default(opts), stream);
+    LevelCall c = {};
+    GRU_BACKWARD_OPERANDS(c);
+    c.frozen = frozen; c.d_in = dHin;
+    return gru_backward_impl(c, 1, ggpm_opts_or_default(opts), stream);
 }
+#undef GRU_BACKWARD_OPERANDS
 
 // Weight gradients of the GRU message function: tall contractions over every (depth, message) row of the
 // stashes ggpm_gru_backward left in `work`.  Separate entry point so that the host can run them on a second
-// stream while the next level's (latency-bound) depth loop occupies the main one.
-static int gru_weight_grads_impl(int E1, int H, int depth, const float* Hs, const float* Ss, const float* Gs,
-                                 float* work, size_t work_bytes, float* dWz_h, int ld_dwz, float* dUr, int ld_dur,
-                                 float* dbu, float* dWh_h, int ld_dwh, bool with_slot0, int lo, const ggpm_level_opts& o,
-                                 ggpm_stream_t stream) {
+// stream while the next level's (latency-bound) depth loop occupies the main one.  A sparse level (c.frozen): dq^0 included.
+int gru_weight_grads_impl(const LevelCall& c, int lo, const ggpm_level_opts& o, ggpm_stream_t stream) {
     GGPM_CLEAR_STALE_ERROR();
-    if (E1 <= 0 || H <= 0 || depth <= 0 || !Hs || !Ss || !Gs || !work || !dWz_h || !dUr || !dbu || !dWh_h)
+    const int E1 = c.rows, H = c.H, depth = c.depth;
+    const bool with_slot0 = c.frozen != nullptr;
+    if (E1 <= 0 || H <= 0 || depth <= 0 || !c.Hs || !c.St[0] || !c.St[1] || !c.work || !c.dW[0] || !c.dW[1] || !c.dbu || !c.dW[2])
         return GGPM_ERR_ARG;
     if (lo < 1 || lo > depth || with_slot0) lo = 1;       // backward steps depth .. lo ran (stash slots lo-1 .. depth-1)
-    if (work_bytes < ggpm_gru_backward_workspace_bytes(E1, H, depth)) return GGPM_ERR_WORKSPACE;
-    const LevelWork<GruCell> wk = carve<GruCell>(work, E1, ggpm_padded_hidden(H), depth);
+    if (c.work_bytes < ggpm_gru_backward_workspace_bytes(E1, H, depth)) return GGPM_ERR_WORKSPACE;
+    const LevelWork<GruCell> wk = carve<GruCell>(c.work, E1, ggpm_padded_hidden(H), depth);
     // dWh_h = DMP^T G, dWz_h = DZP^T S, dUr = DQ^T h, db_u = colsum(DQ) (skip_bias_u: ggpm_gru_bias_u_grad forms it elsewhere)
-    const WgradTerm gate[2] = {{wk.stash[0], Gs, dWh_h, ld_dwh}, {wk.stash[1], Ss, dWz_h, ld_dwz}};
-    return level_weight_grads(E1, H, depth, lo, with_slot0, o, 2, gate, {wk.DQ, Hs, dUr, ld_dur}, o.skip_bias_u ? nullptr : dbu,
-                              wk.csws, wk.skws, wk.skbytes(work_bytes), stream);
+    const WgradTerm gate[2] = {{wk.stash[0], c.St[1], c.dW[2], c.ld_dw[2]}, {wk.stash[1], c.St[0], c.dW[0], c.ld_dw[0]}};
+    return level_weight_grads(E1, H, depth, lo, with_slot0, o, 2, gate, {wk.DQ, c.Hs, c.dW[1], c.ld_dw[1]},
+                              o.skip_bias_u ? nullptr : c.dbu, wk.csws, wk.skws, wk.skbytes(c.work_bytes), stream);
 }
 
 // db_u of a dense level by itself (what gru_weight_grads_impl does last unless ggpm_level_opts.skip_bias_u is set): the
@@ -1253,18 +1264,14 @@ extern "C" int ggpm_gru_weight_grads_stacked(int rows, int rows_q, int H, const 
     return tall_weight_grads(H, Hp, 2, gate, rows, {DQ, Hs, dUr, ld_dur}, rows_q, dbu, csws, false, 0, skws, skbytes, stream);
 }
 
-int ggpm_gru_sparse_weight_grads(int E1, int H, int depth, const float* Hs, const float* Ss, const float* Gs, float* work,
-                                 size_t work_bytes, float* dWz_h, int ld_dwz, float* dUr, int ld_dur, float* dbu, float* dWh_h,
-                                 int ld_dwh, const ggpm_level_opts* opts, ggpm_stream_t stream) {
-    return gru_weight_grads_impl(E1, H, depth, Hs, Ss, Gs, work, work_bytes, dWz_h, ld_dwz, dUr, ld_dur, dbu, dWh_h, ld_dwh,
-                                 true, 1, ggpm_opts_or_default(opts), stream);
-}
-
 extern "C" int ggpm_gru_weight_grads(int E1, int H, int depth, const float* Hs, const float* Ss, const float* Gs,
                                      float* work, size_t work_bytes, float* dWz_h, int ld_dwz, float* dUr,
                                      int ld_dur, float* dbu, float* dWh_h, int ld_dwh, const ggpm_level_opts* opts,
                                      ggpm_stream_t stream) {
-    const ggpm_level_opts& o = ggpm_opts_or_default(opts);
-    return gru_weight_grads_impl(E1, H, depth, Hs, Ss, Gs, work, work_bytes, dWz_h, ld_dwz, dUr, ld_dur, dbu, dWh_h,
-                                 ld_dwh, false, o.lo, o, stream);
+    LevelCall c = {};
+    c.rows = E1; c.H = H; c.depth = depth;
+    c.Hs = level_read(Hs); c.St[0] = level_read(Ss); c.St[1] = level_read(Gs);
+    c.dW[0] = dWz_h; c.ld_dw[0] = ld_dwz; c.dW[1] = dUr; c.ld_dw[1] = ld_dur; c.dW[2] = dWh_h; c.ld_dw[2] = ld_dwh; c.dbu = dbu;
+    c.work = work; c.work_bytes = work_bytes;
+    return ggpm_level_weight_grads(c, opts, stream);
 }

@@ -11,6 +11,7 @@
 //           P3 (one column group) dS = di_pre.Wi_h + do_pre.Wo_h + du_pre.Wu_h      B: otherwise, from L2
 #include "tile_mma.h"
 #include "level_host.h"
+#include "level_call.h"
 #include <cstdlib>
 
 namespace {
@@ -731,22 +732,19 @@ __global__ void lstm_sparse_init_state(const float* __restrict__ h_in, const flo
 }
 }  // namespace
 
-static int lstm_forward_impl(int E1, int H, int depth, const float* Xi, const float* Xo, const float* Xu,
-                             const float* Xf, const float* Wi_h, int ld_wi, const float* Wo_h, int ld_wo,
-                             const float* Wu_h, int ld_wu, const float* Wf_h, int ld_wf,
-                             const int32_t* pred_rowptr, const int32_t* pred_col, float* Hs, float* Cs, float* Qs,
-                             float* Ss, float* Is, float* Os, float* Us, float* Fs, float* wpack,
-                             int save_for_backward, const float* h_in, const float* c_in,
-                             const unsigned char* frozen, const ggpm_level_opts& o, ggpm_stream_t stream) {
+int lstm_forward_impl(const LevelCall& c, int save_for_backward, const ggpm_level_opts& o, ggpm_stream_t stream) {
     GGPM_CLEAR_STALE_ERROR();
-    if (E1 <= 0 || H <= 0 || depth <= 0 || !Xi || !Xo || !Xu || !Xf || !Wi_h || !Wo_h || !Wu_h || !Wf_h ||
-        !pred_rowptr || !pred_col || !Hs || !Cs || !Qs || !wpack)
-        return GGPM_ERR_ARG;
-    if (save_for_backward && (!Ss || !Is || !Os || !Us || !Fs)) return GGPM_ERR_ARG;
+    const int E1 = c.rows, H = c.H, depth = c.depth;
+    float *Hs = c.Hs, *Cs = c.Cs, *Qs = c.Qs, *wpack = c.wpack;
+    const unsigned char* frozen = c.frozen;
+    bool ok = E1 > 0 && H > 0 && depth > 0 && c.pred_rowptr && c.pred_col && Hs && Cs && Qs && wpack;
+    for (int k = 0; k < 4; ++k) ok = ok && c.X[k] && c.W[k];
+    for (int k = 0; k < 5; ++k) ok = ok && (c.St[k] || !save_for_backward);
+    if (!ok) return GGPM_ERR_ARG;
     const int Hp = ggpm_padded_hidden(H);
     if (!LstmCell::shape_ok(E1, Hp)) return GGPM_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
-    const size_t HH = (size_t)Hp * Hp, slot = (size_t)E1 * Hp;
+    const size_t slot = (size_t)E1 * Hp;
     const LevelPlan plan = level_plan<LstmCell>(o, E1, Hp, frozen != nullptr);
     const bool rt2 = plan.rt2;
     const int bf16 = plan.gm;      // gate mode 0 / 1 / 2
@@ -754,8 +752,7 @@ static int lstm_forward_impl(int E1, int H, int depth, const float* Xi, const fl
     float* pWi = wpack; float* pWo = wpack + mstep; float* pWu = wpack + 2 * mstep; float* pWf = wpack + 3 * mstep;
     {
         GgpmPackArgs pk = {};
-        pk.W[0] = Wi_h; pk.ldw[0] = ld_wi; pk.W[1] = Wo_h; pk.ldw[1] = ld_wo; pk.W[2] = Wu_h; pk.ldw[2] = ld_wu;
-        pk.W[3] = Wf_h; pk.ldw[3] = ld_wf;
+        for (int k = 0; k < 4; ++k) { pk.W[k] = c.W[k]; pk.ldw[k] = c.ldw[k]; }
         pk.H = H; pk.Hp = Hp; pk.transpose = 0; pk.dst = wpack; pk.bias = nullptr; pk.bias_out = nullptr; pk.bf16 = bf16;
         if (!o.weights_packed) ggpm_launch_pack(pk, 4, s);
     }
@@ -765,7 +762,7 @@ static int lstm_forward_impl(int E1, int H, int depth, const float* Xi, const fl
         dim3 ig(ggpm_ceil_div(Hp, 256), E1);
         // (h_in == Hs and c_in == Cs: the caller put the masked start state into slot 0 itself; ggpm_level_opts.gather_*:
         // the qf^0 launch fetches it through the index and writes slot 0 of both on the way)
-        if ((h_in != Hs || c_in != Cs) && !gathered) lstm_sparse_init_state<<<ig, 256, 0, s>>>(h_in, c_in, frozen, Hs, Cs, Hp);
+        if ((c.h_in != Hs || c.c_in != Cs) && !gathered) lstm_sparse_init_state<<<ig, 256, 0, s>>>(c.h_in, c.c_in, frozen, Hs, Cs, Hp);
         LstmFwdArgs a0 = {};
         a0.E1 = E1; a0.Hp = Hp; a0.tg = tg; a0.Hnew = Hs; a0.Qnew = Qs; a0.Wf = pWf; a0.bf16 = bf16;
         if (gathered) { a0.src_h = o.gather_h; a0.src_c = o.gather_c; a0.src_idx = o.gather_idx; a0.Cnew = Cs; }
@@ -792,8 +789,8 @@ static int lstm_forward_impl(int E1, int H, int depth, const float* Xi, const fl
     for (int t = 1; t <= run_depth; ++t) {
         const bool stash = save_for_backward && (!fs || t == fs);
         LstmFwdArgs a = {};
-        a.E1 = E1; a.Hp = Hp; a.tg = tg; a.Xi = Xi; a.Xo = Xo; a.Xu = Xu; a.Xf = Xf;
-        a.Wi = pWi; a.Wo = pWo; a.Wu = pWu; a.Wf = pWf; a.rowptr = pred_rowptr; a.col = pred_col;
+        a.E1 = E1; a.Hp = Hp; a.tg = tg; a.Xi = c.X[0]; a.Xo = c.X[1]; a.Xu = c.X[2]; a.Xf = c.X[3];
+        a.Wi = pWi; a.Wo = pWo; a.Wu = pWu; a.Wf = pWf; a.rowptr = c.pred_rowptr; a.col = c.pred_col;
         a.frozen = frozen;
         a.bf16 = bf16;
         a.st16 = st16 ? 1 : 0;
@@ -803,9 +800,9 @@ static int lstm_forward_impl(int E1, int H, int depth, const float* Xi, const fl
             a.Hout = (st16 && t == depth) ? Hs + (size_t)depth * slot : nullptr;      // the level's result stays fp32, at its usual place
             a.Cprev = Cs + (size_t)(t - 1) * slot; a.Cnew = Cs + (size_t)t * slot;
             a.Qprev = ggpm_slot_ptr(Qs, t - 1, slot, st16); a.Qnew = (t < depth) ? ggpm_slot_ptr(Qs, t, slot, st16) : nullptr;
-            a.S = ggpm_slot_ptr(Ss, t - 1, slot, st16); a.I = ggpm_slot_ptr(Is, t - 1, slot, st16);
-            a.O = ggpm_slot_ptr(Os, t - 1, slot, st16); a.U = ggpm_slot_ptr(Us, t - 1, slot, st16);
-            a.F = Fs + (size_t)(t - 1) * slot;
+            a.S = ggpm_slot_ptr(c.St[0], t - 1, slot, st16); a.I = ggpm_slot_ptr(c.St[1], t - 1, slot, st16);
+            a.O = ggpm_slot_ptr(c.St[2], t - 1, slot, st16); a.U = ggpm_slot_ptr(c.St[3], t - 1, slot, st16);
+            a.F = c.St[4] + (size_t)(t - 1) * slot;
             if (!stash) a.S = a.I = a.O = a.U = a.F = nullptr;
         } else if (infer) {
             a.Hprev = ggpm_slot_ptr(Hs, (t - 1) & 1, slot, st16); a.Hnew = ggpm_slot_ptr(Hs, t & 1, slot, st16);
@@ -829,15 +826,22 @@ static int lstm_forward_impl(int E1, int H, int depth, const float* Xi, const fl
     return GGPM_OK;
 }
 
+// the operands both forward entry points name, by the parameter names they share
+#define LSTM_FORWARD_OPERANDS(c) \
+    c.lstm = true; c.rows = E1; c.H = H; c.depth = depth; \
+    c.X[0] = Xi; c.X[1] = Xo; c.X[2] = Xu; c.X[3] = Xf; \
+    c.W[0] = Wi_h; c.ldw[0] = ld_wi; c.W[1] = Wo_h; c.ldw[1] = ld_wo; c.W[2] = Wu_h; c.ldw[2] = ld_wu; c.W[3] = Wf_h; c.ldw[3] = ld_wf; \
+    c.pred_rowptr = pred_rowptr; c.pred_col = pred_col; \
+    c.Hs = Hs; c.Cs = Cs; c.Qs = Qs; c.St[0] = Ss; c.St[1] = Is; c.St[2] = Os; c.St[3] = Us; c.St[4] = Fs; c.wpack = wpack;
 extern "C" int ggpm_lstm_forward(int E1, int H, int depth, const float* Xi, const float* Xo, const float* Xu,
                                  const float* Xf, const float* Wi_h, int ld_wi, const float* Wo_h, int ld_wo,
                                  const float* Wu_h, int ld_wu, const float* Wf_h, int ld_wf,
                                  const int32_t* pred_rowptr, const int32_t* pred_col, float* Hs, float* Cs,
                                  float* Qs, float* Ss, float* Is, float* Os, float* Us, float* Fs,
                                  float* wpack, int save_for_backward, const ggpm_level_opts* opts, ggpm_stream_t stream) {
-    return lstm_forward_impl(E1, H, depth, Xi, Xo, Xu, Xf, Wi_h, ld_wi, Wo_h, ld_wo, Wu_h, ld_wu, Wf_h, ld_wf, pred_rowptr,
-                             pred_col, Hs, Cs, Qs, Ss, Is, Os, Us, Fs, wpack, save_for_backward, nullptr, nullptr,
-                             nullptr, ggpm_opts_or_default(opts), stream);
+    LevelCall c = {};
+    LSTM_FORWARD_OPERANDS(c);
+    return lstm_forward_impl(c, save_for_backward, ggpm_opts_or_default(opts), stream);
 }
 
 extern "C" int ggpm_lstm_sparse_forward(int E1, int H, int depth, const float* h_in, const float* c_in,
@@ -849,44 +853,35 @@ extern "C" int ggpm_lstm_sparse_forward(int E1, int H, int depth, const float* h
                                         float* Is, float* Os, float* Us, float* Fs, float* wpack,
                                         int save_for_backward, const ggpm_level_opts* opts, ggpm_stream_t stream) {
     if (!h_in || !c_in || !frozen) return GGPM_ERR_ARG;
-    return lstm_forward_impl(E1, H, depth, Xi, Xo, Xu, Xf, Wi_h, ld_wi, Wo_h, ld_wo, Wu_h, ld_wu, Wf_h, ld_wf, pred_rowptr,
-                             pred_col, Hs, Cs, Qs, Ss, Is, Os, Us, Fs, wpack, save_for_backward, h_in, c_in, frozen,
-                             ggpm_opts_or_default(opts), stream);
+    LevelCall c = {};
+    LSTM_FORWARD_OPERANDS(c);
+    c.h_in = h_in; c.c_in = c_in; c.frozen = frozen;
+    return lstm_forward_impl(c, save_for_backward, ggpm_opts_or_default(opts), stream);
 }
+#undef LSTM_FORWARD_OPERANDS
 
 extern "C" size_t ggpm_lstm_backward_workspace_bytes(int E1, int H, int depth) {
     return backward_workspace_bytes<LstmCell>(E1, H, depth);      // (level_host.h: carve)
 }
 
-static int lstm_weight_grads_impl(int E1, int H, int depth, const float* Hs, const float* Ss, float* work,
-                                  size_t work_bytes, float* dWi_h, int ld_dwi, float* dWo_h, int ld_dwo, float* dWu_h,
-                                  int ld_dwu, float* dWf_h, int ld_dwf, bool with_slot0, int lo, const ggpm_level_opts& o,
-                                  ggpm_stream_t stream);
-
-static int lstm_backward_impl(int E1, int H, int depth, const float* Xf, const float* Wi_h, int ld_wi,
-                                  const float* Wo_h, int ld_wo, const float* Wu_h, int ld_wu, const float* Wf_h,
-                                  int ld_wf, const int32_t* pred_rowptr, const int32_t* pred_col,
-                                  const int32_t* succ_rowptr, const int32_t* succ_col, const float* Hs,
-                                  const float* Cs, const float* Qs, const float* Ss, const float* Is,
-                                  const float* Os, const float* Us, const float* Fs, const float* dHD, float* dXi,
-                                  float* dXo,
-                                  float* dXu, float* dXf, float* dWi_h, int ld_dwi, float* dWo_h, int ld_dwo,
-                                  float* dWu_h, int ld_dwu, float* dWf_h, int ld_dwf, float* work,
-                                  size_t work_bytes, int weight_grads, const unsigned char* frozen,
-                                  const float* dCD, float* dHin, float* dCin, const ggpm_level_opts& o,
-                                  ggpm_stream_t stream) {
+int lstm_backward_impl(const LevelCall& c, int weight_grads, const ggpm_level_opts& o, ggpm_stream_t stream) {
     GGPM_CLEAR_STALE_ERROR();
-    if (o.skip_sparse_wgrads && frozen) weight_grads = 0;      // (ggpm_lstm_sparse_weight_grads follows)
+    const int E1 = c.rows, H = c.H, depth = c.depth;
+    const float *Xf = c.X[LSTM_GATES.reread], *Cs = c.Cs, *Qs = c.Qs;
+    float* work = c.work;
+    const unsigned char* frozen = c.frozen;
+    if (o.skip_sparse_wgrads && frozen) weight_grads = 0;      // (ggpm_level_weight_grads follows)
     const bool scattered = o.scatter_h && o.scatter_idx && frozen && o.scatter_c;
-    if (E1 <= 0 || H <= 0 || depth <= 0 || !Xf || !Wi_h || !Wo_h || !Wu_h || !Wf_h || !pred_rowptr || !pred_col ||
-        !succ_rowptr || !succ_col || !Hs || !Cs || !Qs || !Ss || !Is || !Os || !Us || !Fs || !dHD || !dXi || !dXo || !dXu ||
-        !dXf || !dWi_h || !dWo_h || !dWu_h || !dWf_h || !work)
-        return GGPM_ERR_ARG;
-    if (work_bytes < ggpm_lstm_backward_workspace_bytes(E1, H, depth)) return GGPM_ERR_WORKSPACE;
+    bool ok = E1 > 0 && H > 0 && depth > 0 && Xf && c.pred_rowptr && c.pred_col && c.succ_rowptr && c.succ_col && c.Hs && Cs &&
+              Qs && c.d_out && work;
+    for (int k = 0; k < 4; ++k) ok = ok && c.W[k] && c.dX[k] && c.dW[k];
+    for (int k = 0; k < 5; ++k) ok = ok && c.St[k];
+    if (!ok) return GGPM_ERR_ARG;
+    if (c.work_bytes < ggpm_lstm_backward_workspace_bytes(E1, H, depth)) return GGPM_ERR_WORKSPACE;
     const int Hp = ggpm_padded_hidden(H);
     if (!LstmCell::shape_ok(E1, Hp)) return GGPM_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
-    const size_t HH = (size_t)Hp * Hp, slot = (size_t)E1 * Hp;
+    const size_t slot = (size_t)E1 * Hp;
 
     const bool skip_xsum = o.skip_x_sums && !frozen;
     const LevelPlan plan = level_plan<LstmCell>(o, E1, Hp, frozen != nullptr);
@@ -906,8 +901,7 @@ static int lstm_backward_impl(int E1, int H, int depth, const float* Xf, const f
 
     {
         GgpmPackArgs pk = {};
-        pk.W[0] = Wi_h; pk.ldw[0] = ld_wi; pk.W[1] = Wo_h; pk.ldw[1] = ld_wo; pk.W[2] = Wu_h; pk.ldw[2] = ld_wu;
-        pk.W[3] = Wf_h; pk.ldw[3] = ld_wf;
+        for (int k = 0; k < 4; ++k) { pk.W[k] = c.W[k]; pk.ldw[k] = c.ldw[k]; }
         pk.H = H; pk.Hp = Hp; pk.transpose = 1; pk.dst = pWiT; pk.bias = nullptr; pk.bias_out = nullptr; pk.bf16 = bf16;
         if (!o.weights_packed) ggpm_launch_pack(pk, 4, s);
     }
@@ -931,20 +925,20 @@ static int lstm_backward_impl(int E1, int H, int depth, const float* Xf, const f
         a.Xf = Xf;
         a.Ccur = Cs + (size_t)state_slot(t) * slot;
         a.Qcur = (t < depth) ? ggpm_slot_ptr(Qs, state_slot(t), slot, st16) : nullptr;
-        a.F = Fs + (size_t)stash_slot(t) * slot;
-        a.I = ggpm_slot_ptr(Is, stash_slot(t), slot, st16); a.O = ggpm_slot_ptr(Os, stash_slot(t), slot, st16);
-        a.U = ggpm_slot_ptr(Us, stash_slot(t), slot, st16);
-        a.dHD = dHD;
+        a.F = c.St[4] + (size_t)stash_slot(t) * slot;
+        a.I = ggpm_slot_ptr(c.St[1], stash_slot(t), slot, st16); a.O = ggpm_slot_ptr(c.St[2], stash_slot(t), slot, st16);
+        a.U = ggpm_slot_ptr(c.St[3], stash_slot(t), slot, st16);
+        a.dHD = c.d_out;
         a.dSin = dSb[(t + 1) & 1]; a.dFCin = dFb[(t + 1) & 1];
         a.dSout = dSb[t & 1]; a.dFCout = dFb[t & 1];
         a.DQ = (t < depth) ? ggpm_slot_ptr(DQ, t, slot, st16) : nullptr;
-        a.frozen = frozen; a.dCD = dCD; a.carry_h = carry_h; a.carry_c = carry_c; a.final_pass = 0;
+        a.frozen = frozen; a.dCD = c.dc_out; a.carry_h = carry_h; a.carry_c = carry_c; a.final_pass = 0;
         a.dHin = nullptr; a.dCin = nullptr;
         a.DI = ggpm_slot_ptr(DI, t - 1, slot, st16); a.DO = ggpm_slot_ptr(DO, t - 1, slot, st16);
         a.DU = ggpm_slot_ptr(DU, t - 1, slot, st16);
-        a.dXi = dXi; a.dXo = dXo; a.dXu = dXu; a.dXf = dXf;
+        a.dXi = c.dX[0]; a.dXo = c.dX[1]; a.dXu = c.dX[2]; a.dXf = c.dX[3];
         a.WiT = pWiT; a.WoT = pWoT; a.WuT = pWuT; a.WfT = pWfT; a.bf16 = bf16;
-        a.srowptr = succ_rowptr; a.scol = succ_col;
+        a.srowptr = c.succ_rowptr; a.scol = c.succ_col;
         a.skip_xsum = skip_xsum ? 1 : 0;
         launch_bwd(a, rt2, t > 1 || frozen != nullptr, flops1, s);
     }
@@ -954,16 +948,15 @@ static int lstm_backward_impl(int E1, int H, int depth, const float* Xf, const f
         a.E1 = E1; a.Hp = Hp; a.tg = tg; a.first = 0; a.final_pass = 1;
         a.Xf = Xf; a.Ccur = Cs; a.Qcur = Qs;
         a.dSin = dSb[1]; a.dFCin = dFb[1];          // written by the launches of depth 1
-        a.DQ = DQ; a.WfT = pWfT; a.srowptr = succ_rowptr; a.scol = succ_col; a.bf16 = bf16;
-        a.frozen = frozen; a.carry_h = carry_h; a.carry_c = carry_c; a.dHin = dHin; a.dCin = dCin;
+        a.DQ = DQ; a.WfT = pWfT; a.srowptr = c.succ_rowptr; a.scol = c.succ_col; a.bf16 = bf16;
+        a.frozen = frozen; a.carry_h = carry_h; a.carry_c = carry_c; a.dHin = c.d_in; a.dCin = c.dc_in;
         if (scattered) { a.scat_h = o.scatter_h; a.scat_c = o.scatter_c; a.scat_idx = o.scatter_idx; }
         launch_bwd(a, rt2, false, flops1, s);
         GGPM_CHECK_LAUNCH();
     }
 
     if (!weight_grads) return GGPM_OK;
-    return lstm_weight_grads_impl(E1, H, depth, Hs, Ss, work, work_bytes, dWi_h, ld_dwi, dWo_h, ld_dwo, dWu_h, ld_dwu,
-                                  dWf_h, ld_dwf, frozen != nullptr, lo, o, stream);
+    return lstm_weight_grads_impl(c, lo, o, stream);
 }
 
 // where ggpm_lstm_backward left its di_pre / do_pre / du_pre stashes inside `work` (slot t-1 of each = backward step t)
@@ -976,6 +969,18 @@ extern "C" int ggpm_lstm_backward_stashes(float* work, int E1, int H, int depth,
     return GGPM_OK;
 }
 
+// the operands both backward entry points name, by the parameter names they share
+#define LSTM_BACKWARD_OPERANDS(c) \
+    c.lstm = true; c.rows = E1; c.H = H; c.depth = depth; \
+    c.X[LSTM_GATES.reread] = Xf; \
+    c.W[0] = Wi_h; c.ldw[0] = ld_wi; c.W[1] = Wo_h; c.ldw[1] = ld_wo; c.W[2] = Wu_h; c.ldw[2] = ld_wu; c.W[3] = Wf_h; c.ldw[3] = ld_wf; \
+    c.pred_rowptr = pred_rowptr; c.pred_col = pred_col; c.succ_rowptr = succ_rowptr; c.succ_col = succ_col; \
+    c.Hs = level_read(Hs); c.Cs = level_read(Cs); c.Qs = level_read(Qs); \
+    c.St[0] = level_read(Ss); c.St[1] = level_read(Is); c.St[2] = level_read(Os); c.St[3] = level_read(Us); c.St[4] = level_read(Fs); \
+    c.d_out = dHD; c.dX[0] = dXi; c.dX[1] = dXo; c.dX[2] = dXu; c.dX[3] = dXf; \
+    c.dW[0] = dWi_h; c.ld_dw[0] = ld_dwi; c.dW[1] = dWo_h; c.ld_dw[1] = ld_dwo; c.dW[2] = dWu_h; c.ld_dw[2] = ld_dwu; \
+    c.dW[3] = dWf_h; c.ld_dw[3] = ld_dwf; \
+    c.work = work; c.work_bytes = work_bytes;
 extern "C" int ggpm_lstm_backward(int E1, int H, int depth, const float* Xf, const float* Wi_h, int ld_wi,
                                   const float* Wo_h, int ld_wo, const float* Wu_h, int ld_wu, const float* Wf_h,
                                   int ld_wf, const int32_t* pred_rowptr, const int32_t* pred_col,
@@ -985,10 +990,9 @@ extern "C" int ggpm_lstm_backward(int E1, int H, int depth, const float* Xf, con
                                   float* dXo, float* dXu, float* dXf, float* dWi_h, int ld_dwi, float* dWo_h,
                                   int ld_dwo, float* dWu_h, int ld_dwu, float* dWf_h, int ld_dwf, float* work,
                                   size_t work_bytes, int weight_grads, const ggpm_level_opts* opts, ggpm_stream_t stream) {
-    return lstm_backward_impl(E1, H, depth, Xf, Wi_h, ld_wi, Wo_h, ld_wo, Wu_h, ld_wu, Wf_h, ld_wf, pred_rowptr, pred_col,
-                              succ_rowptr, succ_col, Hs, Cs, Qs, Ss, Is, Os, Us, Fs, dHD, dXi, dXo, dXu, dXf, dWi_h, ld_dwi,
-                              dWo_h, ld_dwo, dWu_h, ld_dwu, dWf_h, ld_dwf, work, work_bytes, weight_grads, nullptr, nullptr,
-                              nullptr, nullptr, ggpm_opts_or_default(opts), stream);
+    LevelCall c = {};
+    LSTM_BACKWARD_OPERANDS(c);
+    return lstm_backward_impl(c, weight_grads, ggpm_opts_or_default(opts), stream);
 }
 
 // sparse_forward backward: takes dL/dh_D and dL/dc_D, additionally returns dHin / dCin (zero on the recomputed rows)
@@ -1004,27 +1008,28 @@ extern "C" int ggpm_lstm_sparse_backward(int E1, int H, int depth, const unsigne
                                          float* dWu_h, int ld_dwu, float* dWf_h, int ld_dwf, float* work,
                                          size_t work_bytes, const ggpm_level_opts* opts, ggpm_stream_t stream) {
     if (!frozen || !dHin || !dCin) return GGPM_ERR_ARG;
-    return lstm_backward_impl(E1, H, depth, Xf, Wi_h, ld_wi, Wo_h, ld_wo, Wu_h, ld_wu, Wf_h, ld_wf, pred_rowptr, pred_col,
-                              succ_rowptr, succ_col, Hs, Cs, Qs, Ss, Is, Os, Us, Fs, dHD, dXi, dXo, dXu, dXf, dWi_h, ld_dwi,
-                              dWo_h, ld_dwo, dWu_h, ld_dwu, dWf_h, ld_dwf, work, work_bytes, 1, frozen, dCD, dHin, dCin,
-                              ggpm_opts_or_default(opts), stream);
+    LevelCall c = {};
+    LSTM_BACKWARD_OPERANDS(c);
+    c.frozen = frozen; c.dc_out = dCD; c.d_in = dHin; c.dc_in = dCin;
+    return lstm_backward_impl(c, 1, ggpm_opts_or_default(opts), stream);
 }
+#undef LSTM_BACKWARD_OPERANDS
 
-// Weight gradients of the LSTM message function from the stashes ggpm_lstm_backward left in `work`.
-static int lstm_weight_grads_impl(int E1, int H, int depth, const float* Hs, const float* Ss, float* work,
-                                  size_t work_bytes, float* dWi_h, int ld_dwi, float* dWo_h, int ld_dwo, float* dWu_h,
-                                  int ld_dwu, float* dWf_h, int ld_dwf, bool with_slot0, int lo, const ggpm_level_opts& o,
-                                  ggpm_stream_t stream) {
+// Weight gradients of the LSTM message function from the stashes ggpm_lstm_backward left in `work` (sparse: dqf^0 included).
+int lstm_weight_grads_impl(const LevelCall& c, int lo, const ggpm_level_opts& o, ggpm_stream_t stream) {
     GGPM_CLEAR_STALE_ERROR();
-    if (E1 <= 0 || H <= 0 || depth <= 0 || !Hs || !Ss || !work || !dWi_h || !dWo_h || !dWu_h || !dWf_h)
+    const int E1 = c.rows, H = c.H, depth = c.depth;
+    const bool with_slot0 = c.frozen != nullptr;
+    if (E1 <= 0 || H <= 0 || depth <= 0 || !c.Hs || !c.St[0] || !c.work || !c.dW[0] || !c.dW[1] || !c.dW[2] || !c.dW[3])
         return GGPM_ERR_ARG;
     if (lo < 1 || lo > depth || with_slot0) lo = 1;       // backward steps depth .. lo ran (stash slots lo-1 .. depth-1)
-    if (work_bytes < ggpm_lstm_backward_workspace_bytes(E1, H, depth)) return GGPM_ERR_WORKSPACE;
-    const LevelWork<LstmCell> wk = carve<LstmCell>(work, E1, ggpm_padded_hidden(H), depth);
+    if (c.work_bytes < ggpm_lstm_backward_workspace_bytes(E1, H, depth)) return GGPM_ERR_WORKSPACE;
+    const LevelWork<LstmCell> wk = carve<LstmCell>(c.work, E1, ggpm_padded_hidden(H), depth);
     // dW*_h = D*^T S for the i / o / u gates, dWf_h = DQ^T h (dqf^t pairs with h^t)
-    const WgradTerm gate[3] = {{wk.stash[0], Ss, dWi_h, ld_dwi}, {wk.stash[1], Ss, dWo_h, ld_dwo}, {wk.stash[2], Ss, dWu_h, ld_dwu}};
-    return level_weight_grads(E1, H, depth, lo, with_slot0, o, 3, gate, {wk.DQ, Hs, dWf_h, ld_dwf}, nullptr, nullptr, wk.skws,
-                              wk.skbytes(work_bytes), stream);
+    WgradTerm gate[3];
+    for (int k = 0; k < 3; ++k) gate[k] = {wk.stash[k], c.St[0], c.dW[k], c.ld_dw[k]};
+    return level_weight_grads(E1, H, depth, lo, with_slot0, o, 3, gate, {wk.DQ, c.Hs, c.dW[3], c.ld_dw[3]}, nullptr, nullptr,
+                              wk.skws, wk.skbytes(c.work_bytes), stream);
 }
 
 // The hidden-half weight gradients of MANY sparse backward calls at once (see ggpm_gru_weight_grads_stacked).
@@ -1045,18 +1050,15 @@ extern "C" int ggpm_lstm_weight_grads_stacked(int rows, int rows_q, int H, const
     return tall_weight_grads(H, Hp, 3, gate, rows, {DQ, Hs, dWf_h, ld_dwf}, rows_q, nullptr, nullptr, false, 0, skws, skbytes, stream);
 }
 
-int ggpm_lstm_sparse_weight_grads(int E1, int H, int depth, const float* Hs, const float* Ss, float* work, size_t work_bytes,
-                                  float* dWi_h, int ld_dwi, float* dWo_h, int ld_dwo, float* dWu_h, int ld_dwu, float* dWf_h,
-                                  int ld_dwf, const ggpm_level_opts* opts, ggpm_stream_t stream) {
-    return lstm_weight_grads_impl(E1, H, depth, Hs, Ss, work, work_bytes, dWi_h, ld_dwi, dWo_h, ld_dwo, dWu_h, ld_dwu, dWf_h,
-                                  ld_dwf, true, 1, ggpm_opts_or_default(opts), stream);
-}
-
 extern "C" int ggpm_lstm_weight_grads(int E1, int H, int depth, const float* Hs, const float* Ss, float* work,
                                       size_t work_bytes, float* dWi_h, int ld_dwi, float* dWo_h, int ld_dwo,
                                       float* dWu_h, int ld_dwu, float* dWf_h, int ld_dwf, const ggpm_level_opts* opts,
                                       ggpm_stream_t stream) {
-    const ggpm_level_opts& o = ggpm_opts_or_default(opts);
-    return lstm_weight_grads_impl(E1, H, depth, Hs, Ss, work, work_bytes, dWi_h, ld_dwi, dWo_h, ld_dwo, dWu_h, ld_dwu,
-                                  dWf_h, ld_dwf, false, o.lo, o, stream);
+    LevelCall c = {};
+    c.lstm = true; c.rows = E1; c.H = H; c.depth = depth;
+    c.Hs = level_read(Hs); c.St[0] = level_read(Ss);
+    c.dW[0] = dWi_h; c.ld_dw[0] = ld_dwi; c.dW[1] = dWo_h; c.ld_dw[1] = ld_dwo; c.dW[2] = dWu_h; c.ld_dw[2] = ld_dwu;
+    c.dW[3] = dWf_h; c.ld_dw[3] = ld_dwf;
+    c.work = work; c.work_bytes = work_bytes;
+    return ggpm_level_weight_grads(c, opts, stream);
 }

@@ -14,6 +14,7 @@
 // intermediate out of one caller-provided arena per direction.  The Python node keeps the tape and the deferred
 // parameter-gradient queue.
 #include "common.h"
+#include "level_call.h"
 
 namespace {
 
@@ -30,7 +31,7 @@ inline bool dims_of(const ggpm_tree_level* L, Dims& d) {
     d.H = L->H; d.He = L->He; d.Hp = ggpm_padded_hidden(L->H); d.Hep = ggpm_padded_hidden(L->He);
     d.I = L->H + MAX_POS; d.ldm = (d.I + 3) / 4 * 4;
     d.E1 = L->E1; d.Etot = L->E1 + L->n_extra; d.ms = L->E1 - 1; d.n_inst = L->n_inst; d.depth = L->depth;
-    d.lstm = L->lstm != 0; d.G = d.lstm ? 4 : 3;
+    d.lstm = L->lstm != 0; d.G = cell_gates(d.lstm).n;
     d.slot = (size_t)d.Etot * d.Hp;
     return true;
 }
@@ -62,10 +63,29 @@ void views_of(const Dims& d, float* saved, ggpm_tree_level_views& v, size_t& tot
     v.Cs = d.lstm ? c.take(states * d.slot) : nullptr;
     v.Qs = c.take(qs * d.slot);
     v.St = infer ? nullptr : c.take((size_t)5 * d.depth * d.slot);
-    v.wpack = c.take(d.lstm ? ggpm_lstm_pack_floats(d.H) : ggpm_gru_pack_floats(d.H));
+    v.wpack = c.take(ggpm_level_pack_floats(d.lstm, d.H));
     v.nei = c.take((size_t)d.n_inst * d.Hp);
     v.node = c.take((size_t)d.n_inst * d.Hp);
     total = c.used;
+}
+
+// The level's message-function call: every message row (the extra rows frozen), gate k's hidden half inside its own weight
+// behind the I input columns -- or, where the gate has none (W_r), U_r.
+LevelCall level_call(const ggpm_tree_level* L, const Dims& d, const ggpm_tree_level_views& v) {
+    const CellGates& cg = cell_gates(d.lstm);
+    LevelCall c = {};
+    c.lstm = d.lstm; c.rows = d.Etot; c.H = d.H; c.depth = d.depth;
+    for (int k = 0; k < cg.n; ++k) {
+        c.X[k] = v.X + (size_t)k * d.slot;
+        c.W[k] = cg.full[k] ? L->gate_w[k] + d.I : L->Ur;
+        c.ldw[k] = cg.full[k] ? L->ld_gate[k] : L->ld_ur;
+    }
+    c.bu = L->bu;
+    c.pred_rowptr = L->pred_rowptr; c.pred_col = L->pred_col; c.succ_rowptr = L->succ_rowptr; c.succ_col = L->succ_col;
+    c.Hs = v.Hs; c.Cs = v.Cs; c.Qs = v.Qs; c.wpack = v.wpack;
+    for (int k = 0; k < 5; ++k) c.St[k] = v.St ? v.St + (size_t)k * d.depth * d.slot : nullptr;
+    c.frozen = L->frozen; c.h_in = v.hp; c.c_in = v.cp;
+    return c;
 }
 
 #define CK(x) do { const int rc_ = (x); if (rc_ != GGPM_OK) return rc_; } while (0)
@@ -92,8 +112,7 @@ extern "C" size_t ggpm_tree_level_work_bytes(const ggpm_tree_level* L) {
     f += r64((size_t)d.ms * d.ldm);                        // dhmess
     f += r64((size_t)256 * d.H);                           // column-sum scratch
     size_t bytes = f * sizeof(float);
-    bytes += (d.lstm ? ggpm_lstm_backward_workspace_bytes(d.Etot, d.H, d.depth)
-                     : ggpm_gru_backward_workspace_bytes(d.Etot, d.H, d.depth)) + 256;
+    bytes += ggpm_level_backward_workspace_bytes(d.lstm, d.Etot, d.H, d.depth) + 256;
     bytes += ggpm_gemm_workspace_bytes(d.H, d.I, d.ms) + 256;      // split-K slabs of the input-half weight gradients
     return bytes + 1024;
 }
@@ -155,22 +174,8 @@ static int tree_level_forward_impl(const ggpm_tree_level* L, float* saved, size_
         hipMemcpy2DAsync(v.hp + (size_t)d.E1 * Hp, (size_t)Hp * sizeof(float), L->extra, (size_t)L->ld_extra * sizeof(float),
                          (size_t)H * sizeof(float), (size_t)L->n_extra, hipMemcpyDeviceToDevice, s) != hipSuccess)
         return GGPM_ERR_LAUNCH;
-    const size_t ds = (size_t)d.depth * d.slot;
-    float* St[5];
-    for (int k = 0; k < 5; ++k) St[k] = infer ? nullptr : v.St + k * ds;
-    if (d.lstm) {
-        if (hipMemsetAsync(v.cp, 0, d.slot * sizeof(float), s) != hipSuccess) return GGPM_ERR_LAUNCH;
-        CK(ggpm_lstm_sparse_forward(d.Etot, H, d.depth, v.hp, v.cp, L->frozen, v.X, v.X + d.slot, v.X + 2 * d.slot,
-                                    v.X + 3 * d.slot, L->gate_w[0] + I, L->ld_gate[0], L->gate_w[1] + I, L->ld_gate[1],
-                                    L->gate_w[2] + I, L->ld_gate[2], L->gate_w[3] + I, L->ld_gate[3], L->pred_rowptr,
-                                    L->pred_col, v.Hs, v.Cs, v.Qs, St[0], St[1], St[2], St[3], St[4], v.wpack, infer ? 0 : 1,
-                                    nullptr, stream));
-    } else {
-        CK(ggpm_gru_sparse_forward(d.Etot, H, d.depth, v.hp, L->frozen, v.X, v.X + d.slot, v.X + 2 * d.slot,
-                                   L->gate_w[0] + I, L->ld_gate[0], L->Ur, L->ld_ur, L->bu, L->gate_w[2] + I, L->ld_gate[2],
-                                   L->pred_rowptr, L->pred_col, v.Hs, v.Qs, St[0], St[1], St[2], St[3], St[4], v.wpack,
-                                   infer ? 0 : 1, nullptr, stream));
-    }
+    if (d.lstm && hipMemsetAsync(v.cp, 0, d.slot * sizeof(float), s) != hipSuccess) return GGPM_ERR_LAUNCH;      // (the cell state)
+    CK(ggpm_level_forward(level_call(L, d, v), !infer, nullptr, stream));
     // 6. read-out of every visit (forward-only form: the final state sits in ping-pong slot depth & 1)
     const float* hid = v.Hs + (size_t)(infer ? (d.depth & 1) : d.depth) * d.slot;
     CK(ggpm_segment_sum(hid, Hp, L->in_rowptr, L->in_col, d.n_inst, H, v.nei, Hp, 0, Hp, stream));
@@ -229,8 +234,7 @@ extern "C" int ggpm_tree_level_backward(const ggpm_tree_level* L, const ggpm_tre
     float* dCin = d.lstm ? c.take(d.slot) : nullptr;
     float* dhmess = c.take((size_t)d.ms * d.ldm);
     float* csws = c.take((size_t)256 * H);
-    const size_t lwb = d.lstm ? ggpm_lstm_backward_workspace_bytes(d.Etot, H, d.depth)
-                              : ggpm_gru_backward_workspace_bytes(d.Etot, H, d.depth);
+    const size_t lwb = ggpm_level_backward_workspace_bytes(d.lstm, d.Etot, H, d.depth);
     float* lwork = c.take((lwb + 3) / 4);
     const size_t skb = ggpm_gemm_workspace_bytes(H, I, d.ms);
     float* skws = skb ? c.take((skb + 3) / 4) : nullptr;
@@ -252,37 +256,25 @@ extern "C" int ggpm_tree_level_backward(const ggpm_tree_level* L, const ggpm_tre
     }
     CK(ggpm_segment_sum(d_nei, Hp, L->inT_rowptr, L->inT_col, d.Etot, H, dHD, Hp, acc, acc ? 0 : Hp, stream));
     // ---- the level
-    const size_t ds = (size_t)d.depth * d.slot;
     hipStream_t ws = side_stream ? (hipStream_t)side_stream : s;       // where the parameter gradients are formed
     ggpm_level_opts opts = {};
     opts.skip_sparse_wgrads = side_stream != nullptr;      // (the sparse weight-gradient call below forms them on `ws`)
-    if (d.lstm) {
-        if (hipMemsetAsync(dCD, 0, d.slot * sizeof(float), s) != hipSuccess) return GGPM_ERR_LAUNCH;
-        CK(ggpm_lstm_sparse_backward(d.Etot, H, d.depth, L->frozen, v.X + 3 * d.slot, L->gate_w[0] + I, L->ld_gate[0],
-                                     L->gate_w[1] + I, L->ld_gate[1], L->gate_w[2] + I, L->ld_gate[2], L->gate_w[3] + I,
-                                     L->ld_gate[3], L->pred_rowptr, L->pred_col, L->succ_rowptr, L->succ_col, v.Hs, v.Cs, v.Qs,
-                                     v.St, v.St + ds, v.St + 2 * ds, v.St + 3 * ds, v.St + 4 * ds, dHD, dCD, g->dHin, dCin, dX,
-                                     dX + d.slot, dX + 2 * d.slot, dX + 3 * d.slot, g->dgate_w[0] + I, g->ld_dgate[0],
-                                     g->dgate_w[1] + I, g->ld_dgate[1], g->dgate_w[2] + I, g->ld_dgate[2], g->dgate_w[3] + I,
-                                     g->ld_dgate[3], lwork, lwb, &opts, stream));
-    } else {
-        CK(ggpm_gru_sparse_backward(d.Etot, H, d.depth, L->frozen, v.X + d.slot, L->gate_w[0] + I, L->ld_gate[0], L->Ur,
-                                    L->ld_ur, L->gate_w[2] + I, L->ld_gate[2], L->pred_rowptr, L->pred_col, L->succ_rowptr,
-                                    L->succ_col, v.Hs, v.Qs, v.St, v.St + ds, v.St + 2 * ds, v.St + 3 * ds, v.St + 4 * ds, dHD,
-                                    g->dHin, dX, dX + d.slot, dX + 2 * d.slot, g->dgate_w[0] + I, g->ld_dgate[0], g->dUr, H,
-                                    g->dbu, g->dgate_w[2] + I, g->ld_dgate[2], lwork, lwb, &opts, stream));
+    if (d.lstm && hipMemsetAsync(dCD, 0, d.slot * sizeof(float), s) != hipSuccess) return GGPM_ERR_LAUNCH;      // (the cell state)
+    LevelCall lc = level_call(L, d, v);
+    const CellGates& cg = cell_gates(d.lstm);
+    lc.d_out = dHD; lc.dc_out = dCD; lc.d_in = g->dHin; lc.dc_in = dCin;
+    for (int k = 0; k < G; ++k) {
+        lc.dX[k] = dX + (size_t)k * d.slot;
+        lc.dW[k] = cg.full[k] ? g->dgate_w[k] + I : g->dUr;
+        lc.ld_dw[k] = cg.full[k] ? g->ld_dgate[k] : H;
     }
+    lc.dbu = g->dbu;
+    lc.work = lwork; lc.work_bytes = lwb;
+    CK(ggpm_level_backward(lc, 1, &opts, stream));
     if (side_stream) {      // the stashes and dX are complete: hidden halves on the second stream, in the order the level call had them
         hipEvent_t ev = ggpm_wgrad_event(41);
         if (!ev || hipEventRecord(ev, s) != hipSuccess || hipStreamWaitEvent(ws, ev, 0) != hipSuccess) return GGPM_ERR_LAUNCH;
-        if (d.lstm)
-            CK(ggpm_lstm_sparse_weight_grads(d.Etot, H, d.depth, v.Hs, v.St, lwork, lwb, g->dgate_w[0] + I, g->ld_dgate[0],
-                                             g->dgate_w[1] + I, g->ld_dgate[1], g->dgate_w[2] + I, g->ld_dgate[2],
-                                             g->dgate_w[3] + I, g->ld_dgate[3], nullptr, (ggpm_stream_t)ws));
-        else
-            CK(ggpm_gru_sparse_weight_grads(d.Etot, H, d.depth, v.Hs, v.St, v.St + ds, lwork, lwb, g->dgate_w[0] + I,
-                                            g->ld_dgate[0], g->dUr, H, g->dbu, g->dgate_w[2] + I, g->ld_dgate[2], nullptr,
-                                            (ggpm_stream_t)ws));
+        CK(ggpm_level_weight_grads(lc, nullptr, (ggpm_stream_t)ws));
     }
     // input halves of the gate weights, gate biases (the rows of the real messages, 1 .. E1-1, are contiguous)
     const float* dXs[4];
