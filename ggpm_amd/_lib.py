@@ -123,6 +123,9 @@ SIGNATURES = {
     "ggpm_bound_objective": (I, [P, P, P, P, I, I, I, ctypes.c_float, P, P, P, P, P, P]),
     "ggpm_scale_rows_by_mol": (I, [P, I, I, I, P, P, I, I, P, P]),
     "ggpm_latent_terms_backward": (I, [P, P, P, P, P, P, P, I, I, I, P, P, P]),
+    # path-derivative estimators of the importance-weighted bound (csrc/mol_loss.hip)
+    "ggpm_iwae_weights": (I, [P, P, I, I, P, P, P]),
+    "ggpm_latent_terms_backward_path": (I, [P, P, P, P, P, P, P, I, I, I, P, P, P]),
     # the latent column by column (csrc/latent_dims.hip)
     "ggpm_latent_dim_accumulate": (I, [P, P, I, I, P, P]),
     "ggpm_latent_dim_finish": (I, [P, I, c_float, P, P, P]),

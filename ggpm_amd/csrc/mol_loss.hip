@@ -6,6 +6,10 @@
 //   ggpm_bound_objective       : the weighted K-sample ELBO / IWAE loss and its partial derivatives c_nll, c_logpq, c_kl
 //   ggpm_scale_rows_by_mol     : d[m, 0:N] *= g * coef[mol[m]], the chain rule of a per-molecule upstream gradient
 //   ggpm_latent_terms_backward : the backward of ggpm_latent_terms, summed over k in a fixed order
+// and the path-derivative estimators of the importance-weighted bound ("STL and DReG"):
+//   ggpm_iwae_weights               : the normalised importance weights s = softmax_k(logpq - nll) and 1 / sum_k s^2
+//   ggpm_latent_terms_backward_path : ggpm_latent_terms_backward with log q's parameters held fixed (STL), optionally with
+//                                     every sample's addend weighted by s once more (DReG)
 // One wave owns one output element and walks its addends in a fixed order: no atomics, bitwise reproducible.  Sums are
 // carried in fp64 and rounded to fp32 once, where they are stored.
 #include "common.h"
@@ -201,6 +205,77 @@ __global__ void __launch_bounds__(64) latent_terms_bwd_k(const float* __restrict
     }
 }
 
+// block = molecule b; the lanes stride the samples.  nll, the maximum and the sum are bound_objective_k's own expressions, so
+// s is the softmax that kernel's coefficients hold; the effective sample size adds the squares of the unrounded weights.
+__global__ void __launch_bounds__(64) iwae_weights_k(const float* __restrict__ parts, const float* __restrict__ logpq, int K,
+                                                     int B, float* __restrict__ s, float* __restrict__ ess) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    double mx = -INFINITY;
+    for (int k = lane; k < K; k += 64) {
+        const float* q = parts + ((size_t)k * B + b) * GGPM_MOL_LOSS_TERMS;
+        const double nll = ((double)q[0] + (double)q[1]) + ((double)q[2] + (double)q[3]);
+        mx = fmax(mx, (double)logpq[(size_t)k * B + b] - nll);
+    }
+    mx = wave_max_f64(mx);
+    double se = 0.0;
+    for (int k = lane; k < K; k += 64) {
+        const float* q = parts + ((size_t)k * B + b) * GGPM_MOL_LOSS_TERMS;
+        const double nll = ((double)q[0] + (double)q[1]) + ((double)q[2] + (double)q[3]);
+        se += exp((double)logpq[(size_t)k * B + b] - nll - mx);
+    }
+    se = wave_sum_f64(se);
+    double s2 = 0.0;
+    for (int k = lane; k < K; k += 64) {
+        const float* q = parts + ((size_t)k * B + b) * GGPM_MOL_LOSS_TERMS;
+        const double nll = ((double)q[0] + (double)q[1]) + ((double)q[2] + (double)q[3]);
+        const double sk = exp((double)logpq[(size_t)k * B + b] - nll - mx) / se;
+        s[(size_t)k * B + b] = (float)sk;
+        s2 += sk * sk;
+    }
+    s2 = wave_sum_f64(s2);
+    if (ess && lane == 0) ess[b] = (float)(1.0 / s2);
+}
+
+// block = (molecule b, column j); the lanes stride the samples.  z and sd are re-formed with ggpm_latent_terms' fp32
+// expressions, as latent_terms_bwd_k does; r = exp(-lv / 2) is formed in fp64 from the fp32 lv (sd underflows long before r
+// overflows, and the two are no exact reciprocals: the lv addend is written multiplied out, G eps^2 / 2).  A sample whose
+// G eps is 0 -- a molecule of weight 0, a softmax weight that underflowed, eps = 0 -- takes no r product: 0 * inf never appears.
+__global__ void __launch_bounds__(64) latent_terms_bwd_path_k(const float* __restrict__ dz, const float* __restrict__ mean,
+                                                              const float* __restrict__ pv, const float* __restrict__ eps,
+                                                              const float* __restrict__ c_logpq, const float* __restrict__ s,
+                                                              const float* __restrict__ g, int K, int B, int L,
+                                                              float* __restrict__ dmean, float* __restrict__ dpv) {
+    const int b = blockIdx.x / L, j = blockIdx.x - b * L, lane = threadIdx.x;
+    const size_t i = (size_t)b * L + j;
+    const float m = mean[i], p = pv[i], lv = -fabsf(p);
+    const float sd = expf(0.5f * lv);
+    const double r = exp(-0.5 * (double)lv);
+    const double gs = g ? (double)g[0] : 1.0;
+    double s_m = 0.0, s_lv = 0.0;
+    for (int k = lane; k < K; k += 64) {
+        const size_t kb = (size_t)k * B + b;
+        const float e = eps[kb * L + j];
+        const float z = m + sd * e;
+        const double G = c_logpq ? gs * (double)c_logpq[kb] : 0.0;
+        const double t = (dz ? (double)dz[kb * L + j] : 0.0) - G * (double)z;      // d/dz: the decoder's and log p's -z
+        const double Ge = G * (double)e;
+        double a = t, v = t * (0.5 * (double)sd * (double)e);
+        if (Ge != 0.0) {
+            a += Ge * r;                                                           // d(-log q)/dz = eps / sd
+            v += 0.5 * Ge * (double)e;                                             // ... times dz/dlv = sd eps / 2
+        }
+        const double q = s ? (double)s[kb] : 1.0;
+        s_m += q * a;
+        s_lv += q * v;
+    }
+    s_m = wave_sum_f64(s_m);
+    s_lv = wave_sum_f64(s_lv);
+    if (lane == 0) {
+        dmean[i] = (float)s_m;
+        dpv[i] = (float)((p > 0.f ? -1.0 : (p < 0.f ? 1.0 : 0.0)) * s_lv);         // d(-|p|)/dp = -sign(p)  (0 at p = 0)
+    }
+}
+
 }  // namespace
 
 extern "C" int ggpm_mol_loss_parts(const ggpm_mol_loss_term* terms, int B, float* parts, ggpm_stream_t stream) {
@@ -272,6 +347,28 @@ extern "C" int ggpm_latent_terms_backward(const float* dz, const float* mean, co
         (size_t)B * (size_t)L >= ((size_t)1 << 31) || (size_t)K * (size_t)B >= ((size_t)1 << 31))
         return GGPM_ERR_ARG;
     latent_terms_bwd_k<<<B * L, 64, 0, (hipStream_t)stream>>>(dz, mean, pre_var, eps, c_logpq, c_kl, g, K, B, L, dmean, dpre_var);
+    GGPM_CHECK_LAUNCH();
+    return GGPM_OK;
+}
+
+extern "C" int ggpm_iwae_weights(const float* parts, const float* logpq, int K, int B, float* s, float* ess,
+                                 ggpm_stream_t stream) {
+    GGPM_CLEAR_STALE_ERROR();
+    if (!parts || !logpq || !s || K < 1 || K > GGPM_LIKELIHOOD_MAX_K || B <= 0 || (size_t)K * (size_t)B >= ((size_t)1 << 31))
+        return GGPM_ERR_ARG;
+    iwae_weights_k<<<B, 64, 0, (hipStream_t)stream>>>(parts, logpq, K, B, s, ess);
+    GGPM_CHECK_LAUNCH();
+    return GGPM_OK;
+}
+
+extern "C" int ggpm_latent_terms_backward_path(const float* dz, const float* mean, const float* pre_var, const float* eps,
+                                               const float* c_logpq, const float* s, const float* g, int K, int B, int L,
+                                               float* dmean, float* dpre_var, ggpm_stream_t stream) {
+    GGPM_CLEAR_STALE_ERROR();
+    if (!mean || !pre_var || !eps || !dmean || !dpre_var || K < 1 || K > GGPM_LIKELIHOOD_MAX_K || B <= 0 || L <= 0 ||
+        (size_t)B * (size_t)L >= ((size_t)1 << 31) || (size_t)K * (size_t)B >= ((size_t)1 << 31))
+        return GGPM_ERR_ARG;
+    latent_terms_bwd_path_k<<<B * L, 64, 0, (hipStream_t)stream>>>(dz, mean, pre_var, eps, c_logpq, s, g, K, B, L, dmean, dpre_var);
     GGPM_CHECK_LAUNCH();
     return GGPM_OK;
 }

@@ -200,6 +200,54 @@ def latent_terms_backward(dz: Optional[torch.Tensor], mean: torch.Tensor, pre_va
     return dmean, dpv
 
 
+def _fp32(what: str, **named) -> None:
+    for k, t in named.items():
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32):
+            raise ValueError("%s: %s must be a float32 tensor" % (what, k))
+
+
+def iwae_weights(parts: torch.Tensor, logpq: torch.Tensor):
+    """parts [K, B, 4], logpq [K, B] -> (s [K, B]: the normalised importance weights softmax_k(logpq - nll), ess [B]: the
+    effective sample size 1 / sum_k s^2 of every molecule) (csrc/mol_loss.hip)"""
+    _fp32("iwae_weights", parts=parts, logpq=logpq)
+    if logpq.dim() != 2 or logpq.numel() == 0 or parts.shape != (logpq.shape[0], logpq.shape[1], 4):
+        raise ValueError("iwae_weights: parts %s for logpq %s ([K, B, 4] and [K, B])" % (tuple(parts.shape), tuple(logpq.shape)))
+    _need_gpu(parts, logpq)
+    K, B = logpq.shape
+    parts, logpq = parts.contiguous(), logpq.contiguous()
+    f32 = dict(dtype=torch.float32, device=parts.device)
+    s, ess = torch.empty(K, B, **f32), torch.empty(B, **f32)
+    _lib.check(_lib.load().ggpm_iwae_weights(_p(parts), _p(logpq), K, B, _p(s), _p(ess), _stream()), "iwae_weights")
+    return s, ess
+
+
+def latent_terms_backward_path(dz: Optional[torch.Tensor], mean: torch.Tensor, pre_var: torch.Tensor, eps: torch.Tensor,
+                               c_logpq: Optional[torch.Tensor], s: Optional[torch.Tensor] = None,
+                               g: Optional[torch.Tensor] = None):
+    """``latent_terms_backward`` with the parameters of log q held fixed (the path derivative): dz [K, B, L] and the gradient
+    that reached logpq [K, B] (each None for zeros), ``s`` [K, B] the normalised importance weights for the doubly
+    reparameterised estimator or None for "sticking the landing", ``g`` fp32 [1] or None: 1 -> (dmean [B, L],
+    dpre_var [B, L]) (csrc/mol_loss.hip)"""
+    what = "latent_terms_backward_path"
+    _fp32(what, dz=dz, mean=mean, pre_var=pre_var, eps=eps, c_logpq=c_logpq, s=s, g=g)
+    if eps.dim() != 3 or eps.numel() == 0:
+        raise ValueError("%s: eps %s must be [K, B, L]" % (what, tuple(eps.shape)))
+    K, B, L = eps.shape
+    if mean.shape != (B, L) or pre_var.shape != (B, L) or (dz is not None and dz.shape != (K, B, L)) or \
+            (c_logpq is not None and c_logpq.shape != (K, B)) or (s is not None and s.shape != (K, B)):
+        raise ValueError("%s: shapes do not fit eps %s" % (what, (K, B, L)))
+    if g is not None and g.numel() != 1:
+        raise ValueError("%s: g must hold one fp32 value" % what)
+    _need_gpu(dz, mean, pre_var, eps, c_logpq, s, g)
+    cont = lambda t: t.contiguous() if t is not None else None
+    dz, c_logpq, s = cont(dz), cont(c_logpq), cont(s)
+    mean, pre_var, eps = mean.contiguous(), pre_var.contiguous(), eps.contiguous()
+    dmean, dpv = torch.empty_like(mean), torch.empty_like(pre_var)
+    _lib.check(_lib.load().ggpm_latent_terms_backward_path(_p(dz), _p(mean), _p(pre_var), _p(eps), _p(c_logpq), _p(s), _p(g), K,
+                                                           B, L, _p(dmean), _p(dpv), _stream()), what)
+    return dmean, dpv
+
+
 LATENT_STAT_ROWS = 5            # include/ggpm_hip.h GGPM_LATENT_STAT_ROWS / GGPM_LATENT_STAT_OUT
 FREE_BITS_MAX_L = 4096          # include/ggpm_hip.h GGPM_FREE_BITS_MAX_L
 

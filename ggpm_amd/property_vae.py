@@ -178,6 +178,40 @@ class _FreeBitsLatentTerms(torch.autograd.Function):
         return _latent_heads_backward(ctx, z_vecs, Wm, Wv, dmean, dpv) + (None, None, None)
 
 
+class _ImportanceWeights:
+    """What ``bound_loss`` hands to _PathLatentTerms when it applies it and fills in after the K decoder passes: the normalised
+    importance weights ``s`` [K, B] and the effective sample sizes ``ess`` [B] (ggpm_iwae_weights), which exist only once the
+    passes have run; ``dreg``: whether the node's backward weighs every sample by ``s`` once more."""
+
+    def __init__(self, dreg):
+        self.dreg, self.s, self.ess = bool(dreg), None, None
+
+
+class _PathLatentTerms(torch.autograd.Function):
+    """_LatentTerms for the path-derivative estimators of the importance-weighted bound: the same forward, and on the way back
+    ggpm_latent_terms_backward_path -- the parameters of log q held fixed, for DReG every sample weighted by ``weights.s`` --
+    then _KLHead's tail.  The gradient that arrives for kl is c_kl g = 0 for the importance-weighted bound and takes no part."""
+
+    @staticmethod
+    def forward(ctx, z_vecs, Wm, bm, Wv, bv, eps, weights):
+        mean, pv = _latent_heads(z_vecs, Wm, bm, Wv, bv)
+        z, kl, logpq = F_.latent_terms(mean, pv, eps)
+        ctx.save_for_backward(z_vecs, Wm, Wv, mean, pv, eps)
+        ctx.params = (Wm, bm, Wv, bv)
+        ctx.weights = weights
+        ctx.set_materialize_grads(False)
+        return z, kl, logpq
+
+    @staticmethod
+    def backward(ctx, dz, dkl, dlogpq):
+        if ctx.weights is None:
+            raise F_.second_backward("path latent terms")
+        weights, ctx.weights = ctx.weights, None
+        z_vecs, Wm, Wv, mean, pv, eps = ctx.saved_tensors
+        dmean, dpv = F_.latent_terms_backward_path(dz, mean, pv, eps, dlogpq, weights.s if weights.dreg else None)
+        return _latent_heads_backward(ctx, z_vecs, Wm, Wv, dmean, dpv) + (None, None)
+
+
 class _BoundObjective(torch.autograd.Function):
     """(parts [K, B, 4], logpq [K, B], kl [B]) -> the weighted K-sample ELBO / IWAE loss (ggpm_bound_objective, which also
     leaves the loss's partial derivatives); the backward hands them on, times the upstream gradient.  It is the first node
@@ -500,12 +534,12 @@ class _VAE(nn.Module):
         return log_likelihood(self, batch, n_samples, seed, sample_ids, eps, max_cls_size, schedule)
 
     def bound_loss(self, batch, n_samples=1, objective="elbo", beta=1.0, mol_weights=None, seed=None, sample_ids=None,
-                   eps=None, max_cls_size=None, schedule=None, free_bits=None):
+                   eps=None, max_cls_size=None, schedule=None, estimator="reparam", free_bits=None):
         """The ``n_samples``-sample ELBO (``objective="elbo"``) or importance-weighted bound (``"iwae"``) of ``batch`` as a
-        loss to train on, with optional per-molecule weights and, for the ELBO, a free-bits KL -> (loss,
-        :class:`MolObjective`); see :func:`bound_loss`."""
+        loss to train on, with optional per-molecule weights, for the ELBO a free-bits KL and for the importance-weighted
+        bound a choice of gradient estimator -> (loss, :class:`MolObjective`); see :func:`bound_loss`."""
         return bound_loss(self, batch, n_samples, objective, beta, mol_weights, seed, sample_ids, eps, max_cls_size, schedule,
-                          free_bits)
+                          estimator, free_bits)
 
     def latent_accumulator(self, au_threshold=0.01):
         """A :class:`LatentAccumulator` of this model: per-dimension statistics of the latent over as many batches as it is
@@ -754,6 +788,21 @@ class FreeBitsObjective(MolObjective):
         return self
 
 
+class EstimatorObjective(MolObjective):
+    """The second value of ``bound_loss(objective="iwae", estimator="stl" | "dreg")``: :class:`MolObjective`'s seven fields
+    (bit-equal to the ``estimator="reparam"`` call's) and three attributes, ``estimator`` (the name used), ``sample_weights``
+    (fp32 [K, B] on the device: the normalised importance weights of every molecule's K samples) and ``ess`` (fp32 [B]: the
+    effective sample size 1 / sum_k sample_weights^2, between 1 and K); the two tensors are detached."""
+
+    def __new__(cls, *fields, estimator, sample_weights, ess):
+        self = super().__new__(cls, *fields)
+        self.estimator, self.sample_weights, self.ess = estimator, sample_weights, ess
+        return self
+
+
+ESTIMATORS = ("reparam", "stl", "dreg")
+
+
 LatentStats = namedtuple("LatentStats", ["kl_dims", "mu_mean", "mu_var", "sigma2_mean", "agg_var", "n_active", "n_molecules"])
 LatentStats.__doc__ = """What ``latent_stats`` and ``LatentAccumulator.result`` return, over the N molecules seen and per latent column j
 (fp32 [L] device tensors; nothing requires grad, nothing is synchronised), with lv = -|R_var(h)| and mean = R_mean(h):
@@ -803,7 +852,7 @@ class LatentAccumulator:
 
 
 def bound_loss(model, batch, n_samples=1, objective="elbo", beta=1.0, mol_weights=None, seed=None, sample_ids=None, eps=None,
-               max_cls_size=None, schedule=None, free_bits=None):
+               max_cls_size=None, schedule=None, estimator="reparam", free_bits=None):
     """``bound_loss`` of the four VAEs (*Training on the bound*) -> (loss, :class:`MolObjective`).
 
     With ``nll``, ``kl``, ``logpq`` and ``iwae`` as ``log_likelihood`` forms them, w the molecule weights and K = n_samples:
@@ -820,12 +869,26 @@ def bound_loss(model, batch, n_samples=1, objective="elbo", beta=1.0, mol_weight
       loss = (1/B) sum_i w_i (1/K) sum_k nll[k, i] + beta sum_j max(free_bits, klbar_j),  klbar_j = (1/B) sum_i w_i kl_dim[i, j]
     so a column whose batch-mean KL is at or below ``free_bits`` nats is no longer pushed down (its KL gradient is exactly
     zero).  ``free_bits=0.0`` is the ELBO above summed in another order.  The second value is then a
-    :class:`FreeBitsObjective`, which adds ``kl_dims`` ([L], klbar) and ``free_bits`` to the same seven fields."""
+    :class:`FreeBitsObjective`, which adds ``kl_dims`` ([L], klbar) and ``free_bits`` to the same seven fields.
+
+    ``estimator`` (*STL and DReG*): how the gradient of the importance-weighted bound reaches the encoder and
+    ``R_mean`` / ``R_var``.  ``"reparam"``, the default, is the gradient described above.  ``"stl"`` ("sticking the landing")
+    holds the posterior's parameters fixed inside log q(z_k | x), which removes the zero-mean score term whose variance
+    does not shrink with K; it is biased for K > 1.  ``"dreg"`` (doubly reparameterised) weighs every sample of that path
+    gradient by its normalised importance weight once more and is unbiased.  Both need ``objective="iwae"`` (the analytic
+    KL of the ELBO has no score term to remove, so ``free_bits`` is excluded too); loss, ``info``'s seven fields and the
+    decoder's gradients are those of ``"reparam"``, and the second value is an :class:`EstimatorObjective`, which adds
+    ``estimator``, ``sample_weights`` ([K, B]) and ``ess`` ([B])."""
     from .greedy_decode import split_seed
     name, dec, dev, K, B, L, schedule, C = _likelihood_args(model, "bound_loss", batch, n_samples, sample_ids, eps,
                                                             max_cls_size, schedule)
     if objective not in F_.BOUND_OBJECTIVES:
         raise ValueError("%s.bound_loss: objective %r (one of %s)" % (name, objective, sorted(F_.BOUND_OBJECTIVES)))
+    if estimator not in ESTIMATORS:
+        raise ValueError("%s.bound_loss: estimator %r (one of %s)" % (name, estimator, ", ".join(ESTIMATORS)))
+    if estimator != "reparam" and objective != "iwae":
+        raise ValueError("%s.bound_loss: estimator %r changes the gradient of the importance-weighted bound; objective %r has "
+                         "an analytic KL and no score term to remove (free_bits included)" % (name, estimator, objective))
     beta = float(beta)
     if objective == "iwae" and beta != 1.0:
         raise ValueError("%s.bound_loss: the importance-weighted bound has no beta (got %r): pass beta=1.0" % (name, beta))
@@ -854,7 +917,11 @@ def bound_loss(model, batch, n_samples=1, objective="elbo", beta=1.0, mol_weight
             lo, hi = split_seed(seed)
             eps = F_.sample_latent_normal(K, B, L, lo, hi, ids=sample_ids, device=dev)
         Rm, Rv = model.R_mean, model.R_var
-        if free_bits is None:
+        weights = None
+        if estimator != "reparam":
+            weights = _ImportanceWeights(dreg=estimator == "dreg")
+            z, kl, logpq = _PathLatentTerms.apply(root_vecs, Rm.weight, Rm.bias, Rv.weight, Rv.bias, eps.detach(), weights)
+        elif free_bits is None:
             z, kl, logpq = _LatentTerms.apply(root_vecs, Rm.weight, Rm.bias, Rv.weight, Rv.bias, eps.detach())
         else:
             z, kl, logpq, term, kl_dims = _FreeBitsLatentTerms.apply(root_vecs, Rm.weight, Rm.bias, Rv.weight, Rv.bias,
@@ -866,6 +933,9 @@ def bound_loss(model, batch, n_samples=1, objective="elbo", beta=1.0, mol_weight
                                              atom=atom))
             stats["decoder_passes"] += 1
         parts = torch.stack(parts, dim=0)
+        if weights is not None:
+            with torch.no_grad():
+                weights.s, weights.ess = F_.iwae_weights(parts.detach(), logpq.detach())
         if free_bits is None:
             loss = _BoundObjective.apply(parts, logpq, kl, w, objective, beta, tuple(model.parameters()))
         else:
@@ -875,6 +945,8 @@ def bound_loss(model, batch, n_samples=1, objective="elbo", beta=1.0, mol_weight
         elbo, iwae = F_.iwae_finish(parts.detach(), logpq.detach(), kl.detach())
     ones = w if w is not None else torch.ones(B, dtype=torch.float32, device=dev)
     fields = (parts.detach(), kl.detach(), elbo, iwae, z.detach(), ones, stats)
+    if weights is not None:
+        return loss, EstimatorObjective(*fields, estimator=estimator, sample_weights=weights.s, ess=weights.ess)
     if free_bits is None:
         return loss, MolObjective(*fields)
     return loss, FreeBitsObjective(*fields, kl_dims=kl_dims.detach(), free_bits=free_bits)

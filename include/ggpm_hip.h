@@ -945,6 +945,30 @@ int ggpm_latent_terms_backward(const float* dz, const float* mean, const float* 
                                const float* c_logpq, const float* c_kl, const float* g, int K, int B, int L, float* dmean,
                                float* dpre_var, ggpm_stream_t stream);
 
+/* Path-derivative estimators of the importance-weighted bound (bound_loss(objective="iwae", estimator="stl" | "dreg") of the
+ * four VAEs; csrc/mol_loss.hip): the conventions of the entries above.
+ * ggpm_iwae_weights (one launch, one wave per molecule): with nll[k, b] = sum_t parts[k, b, t] as ggpm_bound_objective forms it,
+ *     s[k, b] = softmax_k (logpq - nll)[k, b]          (fp64, the maximum subtracted; GGPM_BOUND_IWAE's c_nll is w_b s / B)
+ *     ess[b]  = 1 / sum_k s[k, b]^2                     (the unrounded weights; between 1 and K)
+ * ess is nullable.
+ * ggpm_latent_terms_backward_path (one launch, one wave per (b, j)): the gradient by mean and pre_var with the parameters of
+ * log q(z | mean, lv) held fixed, so that d(-log q)/dz = eps / sd and lv has no direct term.  With sd = expf(lv / 2) and
+ * z = mean + sd eps (fp32, ggpm_latent_terms' expressions), r = exp(-lv / 2) formed in fp64 from the fp32 lv,
+ * G[k, b] = g[0] c_logpq[k, b] and q[k, b] = s[k, b] (s null: 1),
+ *     t = dz[k, b, j] - G z                          a = t + G eps r
+ *     dmean[b, j] = sum_k q a
+ *     dlv[b, j]   = sum_k q (t sd eps / 2 + G eps^2 / 2)
+ *     dpre_var    = -sign(pre_var) dlv                (0 at pre_var = 0)
+ * s null is the "sticking the landing" estimator, s = ggpm_iwae_weights' the doubly reparameterised one.  A sample with
+ * G eps = 0 adds no r term (r may be inf there).  dz is the gradient that reached z (not scaled by g); dz, c_logpq, s and g
+ * are nullable (zeros, zeros, ones, 1).  The sums over k are formed in fp64 in a fixed order.  The size limits are
+ * ggpm_latent_terms_backward's.
+ * A null required pointer, a size <= 0 or K outside its range returns GGPM_ERR_ARG; nothing is launched then. */
+int ggpm_iwae_weights(const float* parts, const float* logpq, int K, int B, float* s, float* ess, ggpm_stream_t stream);
+int ggpm_latent_terms_backward_path(const float* dz, const float* mean, const float* pre_var, const float* eps,
+                                    const float* c_logpq, const float* s, const float* g, int K, int B, int L, float* dmean,
+                                    float* dpre_var, ggpm_stream_t stream);
+
 /* The latent column by column (latent_stats and bound_loss(free_bits=) of the four VAEs; csrc/latent_dims.hip): the
  * conventions of the entries above -- one wave per output with its lanes striding the molecules, fp64 partials through a fixed
  * shuffle tree, one rounding where a value is stored, no atomics, bitwise reproducible.  With lv = -|pre_var|,
