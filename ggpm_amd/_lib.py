@@ -131,6 +131,10 @@ SIGNATURES = {
     "ggpm_latent_dim_finish": (I, [P, I, c_float, P, P, P]),
     "ggpm_free_bits_kl": (I, [P, P, P, I, I, c_float, P, P, P]),
     "ggpm_free_bits_kl_backward": (I, [P, P, P, P, I, I, c_float, P, P, P, P]),
+    # the KL split across the batch (csrc/latent_decomp.hip)
+    "ggpm_latent_decomp": (I, [P, P, P, I, I, I, c_double, P, P, P, P, P]),
+    "ggpm_latent_decomp_backward": (I, [P, P, P, P, P, P, I, I, I, P, P, P, P]),
+    "ggpm_latent_decomp_accumulate": (I, [P, P, I, I, I, P, P]),
     "ggpm_dropout": (I, [P, I, I, I, ctypes.c_float,ctypes.c_uint, ctypes.c_uint, I, P]),
     # property heads / latent search (csrc/property.hip): heads are ggpm_prop_head*, grads ggpm_prop_head_grads*
     "ggpm_property_heads_workspace_bytes": (c_size_t, [I, I, P, P]),

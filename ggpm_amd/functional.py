@@ -334,6 +334,90 @@ def free_bits_kl_backward(mean: torch.Tensor, pre_var: torch.Tensor, w: Optional
     return dmean, dpv
 
 
+LATENT_DECOMP_ROWS = 4          # include/ggpm_hip.h GGPM_LATENT_DECOMP_ROWS
+LATENT_DECOMP_MAX_B = 4096      # include/ggpm_hip.h GGPM_LATENT_DECOMP_MAX_B
+
+
+def _decomp_args(what: str, z: torch.Tensor, mean: torch.Tensor, pre_var: torch.Tensor):
+    """the checks the entries of the KL split share (no device needed for the ValueErrors) -> K, B, L"""
+    _fp32(what, z=z, mean=mean, pre_var=pre_var)
+    if z.dim() != 3 or z.numel() == 0 or mean.shape != z.shape[1:] or pre_var.shape != z.shape[1:]:
+        raise ValueError("%s: z %s must be [K, B, L] and mean %s / pre_var %s [B, L]"
+                         % (what, tuple(z.shape), tuple(mean.shape), tuple(pre_var.shape)))
+    K, B, L = z.shape
+    if K > LIKELIHOOD_MAX_K or B > LATENT_DECOMP_MAX_B or L > FREE_BITS_MAX_L or K * B * L >= 1 << 31:
+        raise ValueError("%s: %d samples of %d molecules and %d latent columns (at most %d, %d and %d, fewer than 2^31 elements)"
+                         % (what, K, B, L, LIKELIHOOD_MAX_K, LATENT_DECOMP_MAX_B, FREE_BITS_MAX_L))
+    return K, B, L
+
+
+def latent_decomp_log_nb(what: str, dataset_size, B: int) -> float:
+    """log(N B) of minibatch-weighted sampling; ``dataset_size``: an int >= B"""
+    if isinstance(dataset_size, bool) or not isinstance(dataset_size, int) or dataset_size < B:
+        raise ValueError("%s: dataset_size %r (an int, at least the %d molecules of the batch)" % (what, dataset_size, B))
+    import math
+    return math.log(float(dataset_size) * float(B))
+
+
+def latent_decomposition(z: torch.Tensor, mean: torch.Tensor, pre_var: torch.Tensor, dataset_size: int):
+    """z [K, B, L] the draws, mean, pre_var [B, L] the posteriors, ``dataset_size`` N -> (comps fp32 [K, B, 3]: the index-code
+    mutual information, the total correlation and the dimension-wise KL of every draw by minibatch-weighted sampling,
+    dwkl_dim fp32 [K, B, L], lse_joint fp64 [K, B], lse_dim fp64 [K, B, L]: what the backward reads) (csrc/latent_decomp.hip)"""
+    what = "latent_decomposition"
+    K, B, L = _decomp_args(what, z, mean, pre_var)
+    log_nb = latent_decomp_log_nb(what, dataset_size, B)
+    _need_gpu(z, mean, pre_var)
+    z, mean, pre_var = z.contiguous(), mean.contiguous(), pre_var.contiguous()
+    dev = z.device
+    comps = torch.empty(K, B, 3, dtype=torch.float32, device=dev)
+    dwkl_dim = torch.empty(K, B, L, dtype=torch.float32, device=dev)
+    lse_joint = torch.empty(K, B, dtype=torch.float64, device=dev)
+    lse_dim = torch.empty(K, B, L, dtype=torch.float64, device=dev)
+    _lib.check(_lib.load().ggpm_latent_decomp(_p(z), _p(mean), _p(pre_var), K, B, L, log_nb, _p(comps), _p(dwkl_dim),
+                                              _p(lse_joint), _p(lse_dim), _stream()), what)
+    return comps, dwkl_dim, lse_joint, lse_dim
+
+
+def latent_decomposition_backward(z: torch.Tensor, mean: torch.Tensor, pre_var: torch.Tensor, lse_joint: torch.Tensor,
+                                  lse_dim: torch.Tensor, coef: torch.Tensor):
+    """The gradient of sum_{k,i} coef[k, i, :] . (mi, tc, dwkl)[k, i] with z, mean and pre_var held independent; ``lse_joint``
+    / ``lse_dim``: ``latent_decomposition``'s of the same inputs, ``coef`` fp32 [K, B, 3] -> (dz [K, B, L], dmean [B, L],
+    dpre_var [B, L]) (csrc/latent_decomp.hip)"""
+    what = "latent_decomposition_backward"
+    K, B, L = _decomp_args(what, z, mean, pre_var)
+    _fp32(what, coef=coef)
+    if coef.shape != (K, B, 3):
+        raise ValueError("%s: coef %s for z %s (fp32 [K, B, 3])" % (what, tuple(coef.shape), (K, B, L)))
+    for name, t, shape in (("lse_joint", lse_joint, (K, B)), ("lse_dim", lse_dim, (K, B, L))):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.shape != shape or not t.is_contiguous():
+            raise ValueError("%s: %s must be the forward's contiguous fp64 %s tensor" % (what, name, list(shape)))
+    _need_gpu(z, mean, pre_var, lse_joint, lse_dim, coef)
+    z, mean, pre_var, coef = z.contiguous(), mean.contiguous(), pre_var.contiguous(), coef.contiguous()
+    dz, dmean, dpv = torch.empty_like(z), torch.empty_like(mean), torch.empty_like(pre_var)
+    _lib.check(_lib.load().ggpm_latent_decomp_backward(_p(z), _p(mean), _p(pre_var), _p(lse_joint), _p(lse_dim), _p(coef), K, B, L,
+                                                       _p(dz), _p(dmean), _p(dpv), _stream()), what)
+    return dz, dmean, dpv
+
+
+def latent_decomp_accumulate(comps: torch.Tensor, dwkl_dim: torch.Tensor, acc: torch.Tensor) -> torch.Tensor:
+    """Adds the count K B and the sums over the draws of comps [K, B, 3] and of every column of dwkl_dim [K, B, L] to ``acc``,
+    a contiguous fp64 [4 + L] device tensor the caller zeroed once -> acc (csrc/latent_decomp.hip)"""
+    what = "latent_decomp_accumulate"
+    _fp32(what, comps=comps, dwkl_dim=dwkl_dim)
+    if dwkl_dim.dim() != 3 or dwkl_dim.numel() == 0 or comps.shape != tuple(dwkl_dim.shape[:2]) + (3,):
+        raise ValueError("%s: comps %s / dwkl_dim %s must be [K, B, 3] and [K, B, L]" % (what, tuple(comps.shape), tuple(dwkl_dim.shape)))
+    K, B, L = dwkl_dim.shape
+    if K > LIKELIHOOD_MAX_K or B > LATENT_DECOMP_MAX_B or L > FREE_BITS_MAX_L or K * B * L >= 1 << 31:
+        raise ValueError("%s: %d samples of %d molecules and %d latent columns are past the limits" % (what, K, B, L))
+    if not isinstance(acc, torch.Tensor) or acc.shape != (LATENT_DECOMP_ROWS + L,) or acc.dtype != torch.float64 or \
+            not acc.is_contiguous():
+        raise ValueError("%s: acc must be a contiguous fp64 [%d] tensor" % (what, LATENT_DECOMP_ROWS + L))
+    _need_gpu(comps, dwkl_dim, acc)
+    comps, dwkl_dim = comps.contiguous(), dwkl_dim.contiguous()
+    _lib.check(_lib.load().ggpm_latent_decomp_accumulate(_p(comps), _p(dwkl_dim), K, B, L, _p(acc), _stream()), what)
+    return acc
+
+
 def padded_hidden(H: int) -> int:
     return (H + 15) // 16 * 16
 

@@ -178,6 +178,37 @@ class _FreeBitsLatentTerms(torch.autograd.Function):
         return _latent_heads_backward(ctx, z_vecs, Wm, Wv, dmean, dpv) + (None, None, None)
 
 
+class _DecompLatentTerms(torch.autograd.Function):
+    """_LatentTerms with the KL split across the batch beside it: also returns ``comps`` [K, B, 3] -- the index-code mutual
+    information, the total correlation and the dimension-wise KL of every draw (ggpm_latent_decomp on the z, mean and pre_var
+    of this very node; ``dataset_size`` is N of log(N B)).  On the way back ggpm_latent_decomp_backward turns the gradient
+    that reached ``comps`` into dz, dmean and dpre_var with the three held independent; its dz joins the decoder's before
+    ggpm_latent_terms_backward -- the existing rsample chain -- and its dmean / dpre_var are added behind it, so the heads
+    and their deferred weight gradients run once."""
+
+    @staticmethod
+    def forward(ctx, z_vecs, Wm, bm, Wv, bv, eps, dataset_size):
+        mean, pv = _latent_heads(z_vecs, Wm, bm, Wv, bv)
+        z, kl, logpq = F_.latent_terms(mean, pv, eps)
+        comps, _, lse_joint, lse_dim = F_.latent_decomposition(z, mean, pv, dataset_size)
+        ctx.save_for_backward(z_vecs, Wm, Wv, mean, pv, eps, z, lse_joint, lse_dim)
+        ctx.params = (Wm, bm, Wv, bv)
+        ctx.set_materialize_grads(False)
+        return z, kl, logpq, comps
+
+    @staticmethod
+    def backward(ctx, dz, dkl, dlogpq, dcomps):
+        z_vecs, Wm, Wv, mean, pv, eps, z, lse_joint, lse_dim = ctx.saved_tensors
+        if dcomps is not None:
+            cz, cm, cp = F_.latent_decomposition_backward(z, mean, pv, lse_joint, lse_dim, dcomps.to(torch.float32))
+            dz = cz if dz is None else cz.add_(dz)
+        dmean, dpv = F_.latent_terms_backward(dz, mean, pv, eps, dlogpq, dkl)
+        if dcomps is not None:
+            dmean.add_(cm)
+            dpv.add_(cp)
+        return _latent_heads_backward(ctx, z_vecs, Wm, Wv, dmean, dpv) + (None, None)
+
+
 class _ImportanceWeights:
     """What ``bound_loss`` hands to _PathLatentTerms when it applies it and fills in after the K decoder passes: the normalised
     importance weights ``s`` [K, B] and the effective sample sizes ``ess`` [B] (ggpm_iwae_weights), which exist only once the
@@ -534,12 +565,28 @@ class _VAE(nn.Module):
         return log_likelihood(self, batch, n_samples, seed, sample_ids, eps, max_cls_size, schedule)
 
     def bound_loss(self, batch, n_samples=1, objective="elbo", beta=1.0, mol_weights=None, seed=None, sample_ids=None,
-                   eps=None, max_cls_size=None, schedule=None, estimator="reparam", free_bits=None):
-        """The ``n_samples``-sample ELBO (``objective="elbo"``) or importance-weighted bound (``"iwae"``) of ``batch`` as a
-        loss to train on, with optional per-molecule weights, for the ELBO a free-bits KL and for the importance-weighted
-        bound a choice of gradient estimator -> (loss, :class:`MolObjective`); see :func:`bound_loss`."""
+                   eps=None, max_cls_size=None, schedule=None, estimator="reparam", alpha=None, gamma=None, dataset_size=None,
+                   free_bits=None):
+        """The ``n_samples``-sample ELBO (``objective="elbo"``), importance-weighted bound (``"iwae"``) or beta-TCVAE loss
+        (``"tcvae"``, with ``alpha``, ``gamma`` and ``dataset_size``) of ``batch`` as a loss to train on, with optional
+        per-molecule weights, for the ELBO a free-bits KL and for the importance-weighted bound a choice of gradient
+        estimator -> (loss, :class:`MolObjective`); see :func:`bound_loss`."""
         return bound_loss(self, batch, n_samples, objective, beta, mol_weights, seed, sample_ids, eps, max_cls_size, schedule,
-                          estimator, free_bits)
+                          estimator, alpha, gamma, dataset_size, free_bits)
+
+    def latent_decomposition_accumulator(self, dataset_size, n_samples=1, seed=None):
+        """A :class:`LatentDecompositionAccumulator` of this model: the split of the KL into mutual information, total
+        correlation and dimension-wise KL over as many batches as it is given, kept on the device."""
+        return LatentDecompositionAccumulator(self, dataset_size, n_samples, seed)
+
+    def latent_decomposition(self, batches, dataset_size, n_samples=1, seed=None):
+        """The index-code mutual information, the total correlation and the dimension-wise KL (in all and per column) of
+        the latent over the iterable ``batches``, every batch estimating q(z) by minibatch-weighted sampling from its own
+        molecules and ``dataset_size`` -> :class:`LatentDecomposition`."""
+        acc = self.latent_decomposition_accumulator(dataset_size, n_samples, seed)
+        for batch in batches:
+            acc.update(batch)
+        return acc.result()
 
     def latent_accumulator(self, au_threshold=0.01):
         """A :class:`LatentAccumulator` of this model: per-dimension statistics of the latent over as many batches as it is
@@ -800,6 +847,19 @@ class EstimatorObjective(MolObjective):
         return self
 
 
+class DecompositionObjective(MolObjective):
+    """The second value of ``bound_loss(objective="tcvae")``: :class:`MolObjective`'s seven fields (bit-equal to the
+    ``objective="elbo"`` call's on the same draws) and the attributes ``mi``, ``tc``, ``dwkl`` (fp32 [K, B] on the device,
+    detached: the index-code mutual information, the total correlation and the dimension-wise KL of every draw), ``alpha``,
+    ``beta``, ``gamma`` (the floats that weighed them) and ``dataset_size`` (the int used)."""
+
+    def __new__(cls, *fields, mi, tc, dwkl, alpha, beta, gamma, dataset_size):
+        self = super().__new__(cls, *fields)
+        self.mi, self.tc, self.dwkl = mi, tc, dwkl
+        self.alpha, self.beta, self.gamma, self.dataset_size = alpha, beta, gamma, dataset_size
+        return self
+
+
 ESTIMATORS = ("reparam", "stl", "dreg")
 
 
@@ -851,8 +911,75 @@ class LatentAccumulator:
         return LatentStats(out[0], out[1], out[2], out[3], out[4], n_active.reshape(()), self.n_molecules)
 
 
+LatentDecomposition = namedtuple("LatentDecomposition", ["mi", "tc", "dwkl", "dwkl_dims", "kl", "n_molecules"])
+LatentDecomposition.__doc__ = """What ``latent_decomposition`` and ``LatentDecompositionAccumulator.result`` return: means over the
+draws of the N molecules seen (fp32 device tensors; nothing requires grad, nothing is synchronised).
+  mi           0-dim: the index-code mutual information I(x; z), E[log q(z|x) - log q(z)]
+  tc           0-dim: the total correlation KL(q(z) || prod_l q(z_l))
+  dwkl         0-dim: the dimension-wise KL sum_l KL(q(z_l) || p(z_l))
+  dwkl_dims    [L]: the dimension-wise KL column by column (it sums to ``dwkl``)
+  kl           0-dim: the mean over molecules of the analytic KL(q(z|x) || p(z)), which mi + tc + dwkl estimates
+  n_molecules  python int: N, counted on the host
+log q(z) and log q(z_l) are minibatch-weighted estimates from the molecules of the draw's own batch and ``dataset_size``;
+they are biased for small batches (DESIGN.md, *Splitting the KL*)."""
+
+
+class LatentDecompositionAccumulator:
+    """The split of the KL over any number of batches (``model.latent_decomposition_accumulator(dataset_size)``).  Every
+    update draws ``n_samples`` latents per molecule from the seeded stream -- molecule n of the pass has sample id n, so no
+    two batches share draws -- and adds the batch's sums on the device in fp64 (ggpm_latent_decomp, then
+    ggpm_latent_decomp_accumulate and, for the analytic KL, ggpm_latent_dim_accumulate; nothing is synchronised).
+    ``result()`` may be called at any time and updates may go on after it."""
+
+    def __init__(self, model, dataset_size, n_samples=1, seed=None):
+        from .greedy_decode import split_seed
+        name = type(model).__name__
+        self.model = model
+        self._check()
+        F_.latent_decomp_log_nb("%s.latent_decomposition" % name, dataset_size, 1)
+        if isinstance(n_samples, bool) or int(n_samples) != n_samples or not 1 <= int(n_samples) <= F_.LIKELIHOOD_MAX_K:
+            raise ValueError("%s.latent_decomposition: n_samples %r (1 .. %d)" % (name, n_samples, F_.LIKELIHOOD_MAX_K))
+        self.dataset_size, self.n_samples = dataset_size, int(n_samples)
+        self.seed = split_seed(seed)
+        Rm = model.R_mean.weight
+        self.acc = torch.zeros(F_.LATENT_DECOMP_ROWS + Rm.shape[0], dtype=torch.float64, device=Rm.device)
+        self.dims = torch.zeros(F_.LATENT_STAT_ROWS, Rm.shape[0], dtype=torch.float64, device=Rm.device)
+        self.n_molecules = 0
+
+    def _check(self):
+        check_no_dropout(self.model, "%s.latent_decomposition runs without dropout: call model.eval() first"
+                         % type(self.model).__name__, each_dropout=True)
+
+    def update(self, batch):
+        """Adds the molecules of ``batch`` (the tuple ``model(*batch)`` takes; only ``batch[2]``, the tensors, is used)."""
+        self._check()
+        model = self.model
+        with torch.no_grad():
+            root_vecs = model._encode(make_cuda(batch[2]))
+            Rm, Rv = model.R_mean, model.R_var
+            mean, pre_var = _latent_heads(root_vecs, Rm.weight, Rm.bias, Rv.weight, Rv.bias)
+            B, L = mean.shape
+            F_.latent_decomp_log_nb("%s.latent_decomposition" % type(model).__name__, self.dataset_size, B)
+            ids = torch.arange(self.n_molecules, self.n_molecules + B, dtype=torch.int64)
+            eps = F_.sample_latent_normal(self.n_samples, B, L, self.seed[0], self.seed[1], ids=ids, device=mean.device)
+            z, _, _ = F_.latent_terms(mean, pre_var, eps)
+            comps, dwkl_dim, _, _ = F_.latent_decomposition(z, mean, pre_var, self.dataset_size)
+            F_.latent_decomp_accumulate(comps, dwkl_dim, self.acc)
+            F_.latent_dim_accumulate(mean, pre_var, self.dims)
+        self.n_molecules += B
+        return self
+
+    def result(self):
+        """-> :class:`LatentDecomposition` of what has been added so far (zeros before the first update)"""
+        with torch.no_grad():
+            n = self.acc[0]
+            out = torch.where(n > 0, self.acc[1:] / n.clamp(min=1.0), torch.zeros_like(self.acc[1:])).to(torch.float32)
+            kl = F_.latent_dim_finish(self.dims)[0][0].sum()
+        return LatentDecomposition(out[0], out[1], out[2], out[3:], kl, self.n_molecules)
+
+
 def bound_loss(model, batch, n_samples=1, objective="elbo", beta=1.0, mol_weights=None, seed=None, sample_ids=None, eps=None,
-               max_cls_size=None, schedule=None, estimator="reparam", free_bits=None):
+               max_cls_size=None, schedule=None, estimator="reparam", alpha=None, gamma=None, dataset_size=None, free_bits=None):
     """``bound_loss`` of the four VAEs (*Training on the bound*) -> (loss, :class:`MolObjective`).
 
     With ``nll``, ``kl``, ``logpq`` and ``iwae`` as ``log_likelihood`` forms them, w the molecule weights and K = n_samples:
@@ -871,6 +998,18 @@ def bound_loss(model, batch, n_samples=1, objective="elbo", beta=1.0, mol_weight
     zero).  ``free_bits=0.0`` is the ELBO above summed in another order.  The second value is then a
     :class:`FreeBitsObjective`, which adds ``kl_dims`` ([L], klbar) and ``free_bits`` to the same seven fields.
 
+    ``objective="tcvae"`` (*Splitting the KL*): the beta-TCVAE loss, which weighs the three parts of the KL
+    separately,
+      loss = (1/B) sum_i w_i (1/K) sum_k (nll[k, i] + alpha mi[k, i] + beta tc[k, i] + gamma dwkl[k, i])
+    with mi the index-code mutual information, tc the total correlation and dwkl the dimension-wise KL of draw (k, i),
+    estimated by minibatch-weighted sampling from the B posteriors of the batch and ``dataset_size`` (required: an int >= B,
+    the number of molecules of the data set).  ``alpha`` and ``gamma`` default to 1.0 (None); all three weights must be
+    finite.  mi + tc + dwkl = log q(z_k | x_i) - log p(z_k) exactly, so alpha = beta = gamma = 1 is the single-sample
+    estimate of the ELBO.  ``mol_weights`` weigh the outer sum over molecules only: the estimate of q(z) uses every molecule
+    of the batch unweighted.  ``estimator`` must be "reparam" and ``free_bits`` None.  The second value is a
+    :class:`DecompositionObjective`, which adds ``mi``, ``tc``, ``dwkl`` ([K, B]), ``alpha``, ``beta``, ``gamma`` and
+    ``dataset_size`` to the same seven fields.
+
     ``estimator`` (*STL and DReG*): how the gradient of the importance-weighted bound reaches the encoder and
     ``R_mean`` / ``R_var``.  ``"reparam"``, the default, is the gradient described above.  ``"stl"`` ("sticking the landing")
     holds the posterior's parameters fixed inside log q(z_k | x), which removes the zero-mean score term whose variance
@@ -882,13 +1021,34 @@ def bound_loss(model, batch, n_samples=1, objective="elbo", beta=1.0, mol_weight
     from .greedy_decode import split_seed
     name, dec, dev, K, B, L, schedule, C = _likelihood_args(model, "bound_loss", batch, n_samples, sample_ids, eps,
                                                             max_cls_size, schedule)
-    if objective not in F_.BOUND_OBJECTIVES:
-        raise ValueError("%s.bound_loss: objective %r (one of %s)" % (name, objective, sorted(F_.BOUND_OBJECTIVES)))
+    if objective not in F_.BOUND_OBJECTIVES and objective != "tcvae":
+        raise ValueError("%s.bound_loss: objective %r (one of %s)" % (name, objective, sorted(F_.BOUND_OBJECTIVES) + ["tcvae"]))
     if estimator not in ESTIMATORS:
         raise ValueError("%s.bound_loss: estimator %r (one of %s)" % (name, estimator, ", ".join(ESTIMATORS)))
     if estimator != "reparam" and objective != "iwae":
         raise ValueError("%s.bound_loss: estimator %r changes the gradient of the importance-weighted bound; objective %r has "
                          "an analytic KL and no score term to remove (free_bits included)" % (name, estimator, objective))
+    tcvae = objective == "tcvae"
+    if not tcvae and (alpha is not None or gamma is not None or dataset_size is not None):
+        raise ValueError("%s.bound_loss: alpha, gamma and dataset_size weigh the split KL of objective \"tcvae\"; objective %r "
+                         "has none" % (name, objective))
+    if tcvae:
+        if estimator != "reparam":
+            raise ValueError("%s.bound_loss: estimator %r changes the gradient of the importance-weighted bound; objective "
+                             "\"tcvae\" takes \"reparam\"" % (name, estimator))
+        if free_bits is not None:
+            raise ValueError("%s.bound_loss: free_bits holds the KL of the ELBO; objective \"tcvae\" splits it instead" % name)
+        if dataset_size is None:
+            raise ValueError("%s.bound_loss: objective \"tcvae\" needs dataset_size, the number of molecules of the data set"
+                             % name)
+        F_.latent_decomp_log_nb("%s.bound_loss" % name, dataset_size, B)
+        alpha, gamma = 1.0 if alpha is None else float(alpha), 1.0 if gamma is None else float(gamma)
+        for what, v in (("alpha", alpha), ("beta", float(beta)), ("gamma", gamma)):
+            if not (abs(v) < float("inf")):
+                raise ValueError("%s.bound_loss: %s %r (a finite weight)" % (name, what, v))
+        if B > F_.LATENT_DECOMP_MAX_B or L > F_.FREE_BITS_MAX_L:
+            raise ValueError("%s.bound_loss: objective \"tcvae\" for %d molecules and %d latent columns (at most %d and %d)"
+                             % (name, B, L, F_.LATENT_DECOMP_MAX_B, F_.FREE_BITS_MAX_L))
     beta = float(beta)
     if objective == "iwae" and beta != 1.0:
         raise ValueError("%s.bound_loss: the importance-weighted bound has no beta (got %r): pass beta=1.0" % (name, beta))
@@ -921,6 +1081,9 @@ def bound_loss(model, batch, n_samples=1, objective="elbo", beta=1.0, mol_weight
         if estimator != "reparam":
             weights = _ImportanceWeights(dreg=estimator == "dreg")
             z, kl, logpq = _PathLatentTerms.apply(root_vecs, Rm.weight, Rm.bias, Rv.weight, Rv.bias, eps.detach(), weights)
+        elif tcvae:
+            z, kl, logpq, comps = _DecompLatentTerms.apply(root_vecs, Rm.weight, Rm.bias, Rv.weight, Rv.bias, eps.detach(),
+                                                           dataset_size)
         elif free_bits is None:
             z, kl, logpq = _LatentTerms.apply(root_vecs, Rm.weight, Rm.bias, Rv.weight, Rv.bias, eps.detach())
         else:
@@ -936,7 +1099,14 @@ def bound_loss(model, batch, n_samples=1, objective="elbo", beta=1.0, mol_weight
         if weights is not None:
             with torch.no_grad():
                 weights.s, weights.ess = F_.iwae_weights(parts.detach(), logpq.detach())
-        if free_bits is None:
+        if tcvae:
+            # the reconstruction part is the ELBO without its KL; the three components join it as one weighted sum (formed in
+            # fp64: tc and dwkl carry +- L log(N B), which cancels between them)
+            cw = (torch.ones(B, dtype=torch.float64, device=dev) if w is None else w.double()) / float(B * K)
+            cw = cw[None, :, None] * torch.tensor([alpha, beta, gamma], dtype=torch.float64, device=dev)
+            loss = _BoundObjective.apply(parts, logpq, kl, w, "elbo", 0.0, tuple(model.parameters())) + \
+                (comps.double() * cw).sum().to(torch.float32)
+        elif free_bits is None:
             loss = _BoundObjective.apply(parts, logpq, kl, w, objective, beta, tuple(model.parameters()))
         else:
             # the reconstruction part is the ELBO without its KL; the held KL joins it as one term
@@ -945,6 +1115,10 @@ def bound_loss(model, batch, n_samples=1, objective="elbo", beta=1.0, mol_weight
         elbo, iwae = F_.iwae_finish(parts.detach(), logpq.detach(), kl.detach())
     ones = w if w is not None else torch.ones(B, dtype=torch.float32, device=dev)
     fields = (parts.detach(), kl.detach(), elbo, iwae, z.detach(), ones, stats)
+    if tcvae:
+        c = comps.detach()
+        return loss, DecompositionObjective(*fields, mi=c[..., 0], tc=c[..., 1], dwkl=c[..., 2], alpha=alpha, beta=beta,
+                                            gamma=gamma, dataset_size=dataset_size)
     if weights is not None:
         return loss, EstimatorObjective(*fields, estimator=estimator, sample_weights=weights.s, ess=weights.ess)
     if free_bits is None:

@@ -1009,6 +1009,43 @@ int ggpm_free_bits_kl(const float* mean, const float* pre_var, const float* w, i
 int ggpm_free_bits_kl_backward(const float* mean, const float* pre_var, const float* w, const float* kl_dims_gate, int B, int L,
                                float lambda, const float* g, float* dmean, float* dpre_var, ggpm_stream_t stream);
 
+/* The KL split across the batch (latent_decomposition and bound_loss(objective="tcvae") of the four VAEs;
+ * csrc/latent_decomp.hip): Chen et al.'s split of E_x KL(q(z|x) || p(z)) into the index-code mutual information, the total
+ * correlation and the dimension-wise KL, estimated by minibatch-weighted sampling.  z [K x B x L] the draws, mean, pre_var
+ * [B x L] the posteriors, lv = -|pre_var|, log_nb = log(N B) with N the size of the data set.  EVERYTHING below is formed in
+ * fp64 from the fp32 inputs (exp / log on double); fixed reduction orders, no atomics, bitwise reproducible; one rounding where
+ * a fp32 value is stored.
+ *     ell[k,i,j,l] = -0.5 (log 2pi + lv[j,l] + (z[k,i,l] - mean[j,l])^2 exp(-lv[j,l]))
+ *     S[k,i,j] = sum_l ell      A[k,i] = logsumexp_j S      D[k,i,l] = logsumexp_j ell      logp[k,i] = sum_l -0.5 (log 2pi + z^2)
+ * ggpm_latent_decomp (one launch, one workgroup of 4 waves per draw (k, i)):
+ *     comps[k,i,0] = mi   = S[k,i,i] - A + log_nb
+ *     comps[k,i,1] = tc   = A - sum_l D + (L - 1) log_nb
+ *     comps[k,i,2] = dwkl = sum_l D - L log_nb - logp
+ *     dwkl_dim[k,i,l]     = D - log_nb + 0.5 (log 2pi + z^2)                          (nullable)
+ *     lse_joint[k,i] = A,  lse_dim[k,i,l] = D   (double; both nullable for a forward-only call)
+ * mi + tc + dwkl = S[k,i,i] - logp[k,i] whatever log_nb is.
+ * ggpm_latent_decomp_backward (two launches): with (a, b, c3) = coef[k,i,0:3] the gradients that reached mi, tc and dwkl,
+ * p = exp(S - A), r = exp(ell - D), G[k,i,j,l] = a [i == j] + (b - a) p + (c3 - b) r, d = z[k,i,l] - mean[j,l], iv = exp(-lv[j,l]):
+ *     dz[k,i,l]   = sum_j G (-d iv) + c3 z[k,i,l]             (row pass: one workgroup per draw; p[0:B] in LDS)
+ *     dmean[j,l]  = sum_{k,i} G d iv                          (column pass: one workgroup per molecule and 64 columns)
+ *     dlv[j,l]    = sum_{k,i} G (-0.5 + 0.5 d^2 iv)           dpre_var = -sign(pre_var) dlv     (0 at pre_var = 0)
+ * WRITTEN (not added); partial derivatives with z, mean and pre_var held independent.  lse_joint / lse_dim: the forward's, of
+ * the same inputs.
+ * ggpm_latent_decomp_accumulate (one launch, one wave per cell): acc is double[GGPM_LATENT_DECOMP_ROWS + L] on the device,
+ * zeroed once by the caller; the call ADDS to it: acc[0] += K B, acc[1 + t] += sum_{k,i} comps[k,i,t],
+ * acc[GGPM_LATENT_DECOMP_ROWS + l] += sum_{k,i} dwkl_dim[k,i,l].  Ordering as for ggpm_latent_dim_accumulate.
+ * 1 <= K <= GGPM_LIKELIHOOD_MAX_K, 1 <= B <= GGPM_LATENT_DECOMP_MAX_B, 1 <= L <= GGPM_FREE_BITS_MAX_L, K * B * L < 2^31,
+ * log_nb finite.  A null required pointer or a size outside these limits returns GGPM_ERR_ARG; nothing is launched then. */
+#define GGPM_LATENT_DECOMP_ROWS 4
+#define GGPM_LATENT_DECOMP_MAX_B 4096
+int ggpm_latent_decomp(const float* z, const float* mean, const float* pre_var, int K, int B, int L, double log_nb, float* comps,
+                       float* dwkl_dim, double* lse_joint, double* lse_dim, ggpm_stream_t stream);
+int ggpm_latent_decomp_backward(const float* z, const float* mean, const float* pre_var, const double* lse_joint,
+                                const double* lse_dim, const float* coef, int K, int B, int L, float* dz, float* dmean,
+                                float* dpre_var, ggpm_stream_t stream);
+int ggpm_latent_decomp_accumulate(const float* comps, const float* dwkl_dim, int K, int B, int L, double* acc,
+                                  ggpm_stream_t stream);
+
 /* ------------------------------------------------------------------ whole-encoder drivers
  * HierMPNEncoder.forward (ggpm/encoder.py:140-157, with embed_graph/inter/tree/root :96-138) and its backward as ONE
  * call each: the same kernels the op-by-op host path issues, sequenced from C++ (GRU or LSTM message function).

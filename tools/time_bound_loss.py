@@ -1,7 +1,7 @@
 """``bound_loss`` + ``backward`` with K samples beside the training step ``model(*batch)`` + ``backward``: ms per step and peak
 MiB, as one JSON line.
 
-    python tools/time_bound_loss.py [--reps N] [--warmup N]
+    python tools/time_bound_loss.py [--reps N] [--warmup N] [--objective iwae|elbo|tcvae] [--ks 1,4,16]
 
 Rows: the configs[1] HierPropertyVAE (hidden 300, depth 20, diterT 1 / diterG 5, latent 32; B 32; GRU and LSTM; eval mode, no
 dropout), K in {1, 4, 16}.  ``bound_ms`` is one ``model.bound_loss(batch, n_samples=K, objective="iwae", seed=...)`` followed
@@ -10,7 +10,9 @@ by ``loss.backward()`` -- one encoder pass and one atom-level pass each way, K p
 Gradients are dropped (``zero_grad(set_to_none=True)``) before every step.  The two are timed in alternation, `reps` windows
 each after `warmup` untimed rounds; a window is `calls` steps back to back between two device synchronisations, and the
 figures are per step: the median over the windows, with the fastest and the slowest window beside it.  ``*_peak_mib`` is
-``torch.cuda.max_memory_allocated`` over one step after a reset.  No threshold: the tool reports.
+``torch.cuda.max_memory_allocated`` over one step after a reset.  ``--objective elbo`` times the K-sample ELBO instead and
+``--objective tcvae`` the beta-TCVAE loss (alpha 1, beta 4, gamma 1, dataset_size 250000), whose figure is to be read against
+the ``elbo`` one of the same K; ``--ks`` replaces the list of K.  No threshold: the tool reports.
 """
 import argparse
 import json
@@ -59,7 +61,11 @@ def _peak_mib(call):
     return round(torch.cuda.max_memory_allocated(DEV) / 2 ** 20, 1)
 
 
-def row(rnn, K, reps, warmup, calls):
+OBJECTIVES = {"iwae": dict(objective="iwae"), "elbo": dict(objective="elbo"),
+              "tcvae": dict(objective="tcvae", beta=4.0, dataset_size=250000)}
+
+
+def row(rnn, K, reps, warmup, calls, objective="iwae"):
     torch.manual_seed(0)
     model = HierPropertyVAE(_args(rnn)).to(DEV).eval()
     specs = synth.random_batch(1000, B, motifs=(8, 12), n_motif_vocab=500, n_attach_vocab=1500)
@@ -69,7 +75,7 @@ def row(rnn, K, reps, warmup, calls):
 
     def bound():
         model.zero_grad(set_to_none=True)
-        model.bound_loss(batch, n_samples=K, objective="iwae", seed=7, schedule=sch)[0].backward()
+        model.bound_loss(batch, n_samples=K, seed=7, schedule=sch, **OBJECTIVES[objective])[0].backward()
 
     def train():
         model.zero_grad(set_to_none=True)
@@ -92,10 +98,15 @@ def main():
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--calls", type=int, default=0, help="steps per timed window (default: 8 for K = 1, 4 for K = 4, 2 for K = 16)")
+    ap.add_argument("--objective", choices=sorted(OBJECTIVES), default="iwae", help="what bound_loss computes (default: iwae)")
+    ap.add_argument("--ks", default=",".join(str(k) for k in KS), help="comma-separated n_samples (default: %(default)s)")
     a = ap.parse_args()
-    res = {"tool": "time_bound_loss", "batch": B, "reps": a.reps, "warmup": a.warmup, "calls": a.calls or "8/4/2"}
+    ks = [int(k) for k in a.ks.split(",")]
+    res = {"tool": "time_bound_loss", "objective": a.objective, "batch": B, "reps": a.reps, "warmup": a.warmup,
+           "calls": a.calls or "8/4/2"}
     for rnn in ("GRU", "LSTM"):
-        res["configs1_" + rnn.lower()] = [row(rnn, K, a.reps, a.warmup, a.calls or {1: 8, 4: 4, 16: 2}[K]) for K in KS]
+        res["configs1_" + rnn.lower()] = [row(rnn, K, a.reps, a.warmup, a.calls or (8 if K < 4 else 4 if K < 16 else 2), a.objective)
+                                          for K in ks]
     print(json.dumps(res))
 
 
