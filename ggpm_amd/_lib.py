@@ -58,6 +58,8 @@ SIGNATURES = {
     "ggpm_embed_graph": (I, [P, I, P, I, I, I, I, P, I, P, I, P]),
     "ggpm_level_bf16_storage": (I, [I, I]),
     "ggpm_level_form_query": (I, [I, I, I, I, I, P, P]),                  # opts: ggpm_level_opts* or NULL, out: ggpm_level_form*
+    "ggpm_level_q_part_bytes": (c_size_t, [I, I]),
+    "ggpm_level_ksplit_q": (I, [I, I, I, I, P]),                          # opts: ggpm_level_opts* or NULL
     "ggpm_gru_backward_stashes": (I, [P, I, I, I, POINTER(c_void_p), POINTER(c_void_p)]),
     "ggpm_lstm_backward_stashes": (I, [P, I, I, I, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p)]),
     "ggpm_sum_slots": (I, [P, I, c_size_t, P, P]),

@@ -43,6 +43,8 @@ struct Csr {
 struct LevelSaved {
     float *X, *Hs, *Cs, *Qs, *St, *wpack, *nei;
     float* hout;          // forward-only layout: the level's result (its depth loop ping-pongs in Hs / Qs / Cs); else null
+    float* qpart;         // tree-side GRU levels on column groups: ggpm_level_opts.q_part (forward scratch); else null
+    size_t qpart_bytes;
 };
 
 struct Saved {          // layout of the `saved` arena (pointers are re-derived by replaying the same takes)
@@ -117,6 +119,16 @@ void take_level(Arena& A, LevelSaved& L, int E1, int N1, int Hp, int H, int dept
     L.nei = A.take<float>((size_t)N1 * Hp);
 }
 
+// The partial-q' buffer of a tree-side level (ggpm_level_opts.q_part): taken where the level's forward takes the K-split form
+// under this driver's options (a GRU level on column groups; training and forward-only calls then run the same launches)
+void take_q_part(Arena& A, const Dims& d, LevelSaved& L) {
+    const ggpm_level_opts o = level_opts(d);
+    L.qpart = nullptr; L.qpart_bytes = 0;
+    if (!ggpm_level_ksplit_q(d.lstm, d.E1t, d.H, 0, &o)) return;
+    L.qpart_bytes = ggpm_level_q_part_bytes(d.E1t, d.H);
+    L.qpart = A.take<float>(L.qpart_bytes / sizeof(float));
+}
+
 void layout_saved(Arena& A, const Dims& d, Saved& s) {
     s.lv[0].hout = s.lv[1].hout = s.lv[2].hout = nullptr;
     take_csr(A, s.gpred, d.E1g, d.E1g, d.E1g * d.Kgb);
@@ -148,6 +160,8 @@ void layout_saved(Arena& A, const Dims& d, Saved& s) {
     s.finput_t = A.take<float>((size_t)d.N1t * d.Hep);
     s.hnode_t = A.take<float>((size_t)d.N1t * d.Hp); s.hmess_t = A.take<float>((size_t)d.E1t * d.ld_t);
     s.f = A.take<float>((size_t)d.B * d.Hp); s.n = A.take<float>((size_t)d.B * d.Hp);
+    for (int l = 0; l < 2; ++l) take_q_part(A, d, s.lv[l]);      // (last: nothing else moves)
+    s.lv[2].qpart = nullptr; s.lv[2].qpart_bytes = 0;
 }
 
 // The forward-only arena (ggpm_encoder_infer): what the forward reads and nothing the backward needs -- the forward CSRs
@@ -189,6 +203,8 @@ void layout_infer(Arena& A, const Dims& d, Saved& s) {
     s.finput_t = A.take<float>((size_t)d.N1t * d.Hep);
     s.hnode_t = A.take<float>((size_t)d.N1t * d.Hp); s.hmess_t = A.take<float>((size_t)d.E1t * d.ld_t);
     s.f = A.take<float>((size_t)d.B * d.Hp); s.n = A.take<float>((size_t)d.B * d.Hp);
+    take_q_part(A, d, s.lv[0]);      // one buffer for the two tree-side levels, as the rest of their scratch
+    s.lv[1].qpart = s.lv[0].qpart; s.lv[1].qpart_bytes = s.lv[0].qpart_bytes;
 }
 
 __global__ void iota_k(int32_t* out, int n) {
@@ -420,6 +436,7 @@ int level_forward(const Dims& d, int E1, int N1, int I, int depth, const float* 
     o.h_out = L.hout;
     const int fs = infer ? 0 : fixed_slot(d, level, depth, E1);
     o.fixed_slot = fs;
+    o.q_part = L.qpart; o.q_part_bytes = L.qpart_bytes;
     const float* result = infer ? L.hout : L.Hs + (size_t)(fs ? fs : depth) * slot;
     const LevelSlots gs = gate_slots(d.lstm, level, I, H);
     const LevelCall c = level_call(d, E1, I, depth, P, gs, pred, L);

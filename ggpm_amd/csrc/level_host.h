@@ -85,6 +85,19 @@ inline LevelPlan level_plan(const ggpm_level_opts& o, int E1, int Hp, bool spars
     p.gm = gate_mode<Cell>(o, Hp, p.rt2, p.tg >= Hp / 16, sparse);
     return p;
 }
+// K-split q' (ggpm_level_opts.q_part; GRU forward): a column group forms a partial q' over its own K slice of U_r inside kernel A
+// and the next step's gather adds the partials, so only the last executed step keeps its B launch.  The geometry it applies
+// to: fp32 MFMA, one row tile, 2 .. GGPM_KSPLIT_MAX_GROUPS column groups (the gather holds that many partial rows per
+// predecessor in registers), at most two tiles of a group per wave (kernel A keeps their h' fragments in registers across
+// the barrier that frees the LDS tile).  Dense calls only (the caller checks).  GGPM_KSPLIT_Q=0: off (A/B runs).
+constexpr int GGPM_KSPLIT_MAX_GROUPS = 5;
+inline bool ksplit_q_form(const LevelPlan& p, int Hp) {
+    static const bool on = [] { const char* e = ggpm_dev_env("GGPM_KSPLIT_Q"); return !e || atoi(e) != 0; }();
+    const int groups = ggpm_ceil_div(Hp / 16, p.tg);
+    return on && p.gm == 0 && !p.rt2 && groups >= 2 && groups <= GGPM_KSPLIT_MAX_GROUPS && p.tg <= 2 * GGPM_NWA;
+}
+inline size_t q_part_floats(int E1, int Hp, int tg) { return (size_t)2 * ggpm_ceil_div(Hp / 16, tg) * E1 * Hp; }
+
 struct StepLds { int fuse; size_t a, b; };      // b: what the B launch takes when there is one
 // may_fuse: the step has a B product at all; the fused form needs one row tile, one column group and room in the LDS
 inline StepLds step_lds(const StepNeed& need, int max_tiles, int Hp, int tg, bool rt2, int gm, bool may_fuse) {

@@ -127,7 +127,46 @@ struct GruFwdArgs {
     float* Hout;                   // bf16 storage only: where the LAST depth also writes h' in fp32 (the level's result)
     const float* src_h;            // kernel B of a sparse forward's q^0 launch (ggpm_level_opts.gather_*): row r of the
     const int32_t* src_idx;        // start state is src_h[src_idx[r]] (zero when < 0); the launch writes it to Hnew itself
+    // K-split q' (ggpm_level_opts.q_part; gru_fwd_a_ks / gru_fwd_b_ks): blocks of [groups][E1][Hp] partial q rows
+    float* Qpart_out;              // kernel A: where column group `grp` stores U_r[:, its k chunks] h'[its columns] (group 0: + b_u); null: none
+    const float* Qpart_in;         // kernel A: the previous step's partials, which the gather adds in group order in place of Qprev rows
+    float* Qsum;                   // ... and their sums for this workgroup's rows and columns (the Qs slot of the previous step; null: not kept)
+    int groups;                    // column groups (kernel B: q' as the sum of the groups' K slices, bit for bit what the partials add up to)
 };
+
+// ---- K-split q': the product of one K slice [k0, k1) of a packed matrix with the matching columns of an LDS tile.
+constexpr int GGPM_KS_MAXG = GGPM_KSPLIT_MAX_GROUPS;
+// fragments of chunks k0 .. k0 + 3 of tile t (past the slice: its last chunk again, unused)
+__device__ __forceinline__ void ggpm_slice_head(const float* wp, int KC, int t, int k0, int k1, int lane, f32x4 (&r)[4]) {
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+        r[d] = *reinterpret_cast<const f32x4*>(wp + ggpm_pack_index(t, min(k0 + d, k1 - 1), KC, lane));
+}
+// acc += Wp(tile t)[:, chunks k0 .. k1) x tile[:, those columns]^T, chunk by chunk in ascending order (the order is the result:
+// kernel A's partials and kernel B's slices run this same chain).  `head` holds the slice's first four fragments
+// (ggpm_slice_head) and is left holding those of slice [k0n, k1n) of tile tn (tn < 0: nothing), loaded a slice ahead.
+__device__ __forceinline__ void ggpm_wave_gemm_slice(const float* tile, int LD, const float* wp, int KC, int t, int k0, int k1,
+                                                     int tn, int k0n, int k1n, int lane, f32x4& acc, f32x4 (&head)[4]) {
+    const int boff = (lane & 15) * LD + 4 * (lane >> 4);
+    for (int kb = k0; kb < k1; kb += 4) {
+        f32x4 nxt[4];
+        const bool more = kb + 4 < k1;
+        if (more) ggpm_slice_head(wp, KC, t, kb + 4, k1, lane, nxt);
+        else if (tn >= 0) ggpm_slice_head(wp, KC, tn, k0n, k1n, lane, nxt);
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+            if (kb + d < k1) {
+                const f32x4 b = *reinterpret_cast<const f32x4*>(tile + boff + (kb + d) * 16);
+#pragma unroll
+                for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(head[d][s], b[s], acc, 0, 0, 0);
+            }
+        }
+        if (more || tn >= 0) {
+#pragma unroll
+            for (int d = 0; d < 4; ++d) head[d] = nxt[d];
+        }
+    }
+}
 
 __global__ void pad_bias(const float* __restrict__ b, int H, int Hp, float* __restrict__ out) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -339,6 +378,294 @@ __global__ void GGPM_A_BOUNDS gru_fwd_a(GruFwdArgs a) {
             else ggpm_wave_gemm_ring<1, 1>(tiles, LD, wps3, KC, tt, tn, lane, acc, ring3);
             if (row < a.E1) ggpm_stx<ST16>(a.Qnew, (size_t)row * Hp + c, ggpm_f4(acc[0][0]) + b);
         }
+    }
+}
+
+// Kernel A of a level on the K-split form of q' (GruFwdArgs.Qpart_*; dense, fp32 MFMA, one row tile, 2 .. GGPM_KS_MAXG column
+// groups, at most two tiles of the group per wave: level_host.h, ksplit_q_form).  P1 and P2 are gru_fwd_a's, with two
+// differences: the gather adds the previous step's `groups` partial q rows of a predecessor, in ascending group order, where
+// gru_fwd_a reads one q row; and behind P2 the group's h' columns go back to LDS and ALL waves multiply them by the group's
+// K slice of U_r over every output tile: Qpart[grp] = U_r[:, slice] h'[slice] (+ b_u in group 0).  The groups' partials add
+// up to q' = U_r h' + b_u and nothing crosses workgroups inside the launch.  The step also sums the previous step's partials
+// of its own rows and columns into that step's Qs slot, which is what the backward reads.
+template <bool STASH>
+__global__ void GGPM_A_BOUNDS gru_fwd_a_ks(GruFwdArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int Hp = a.Hp, LD = Hp + 4, KC = Hp / 16, NT = Hp / 16;
+    float* Ts = lds;
+    float* Tg = lds + 16 * LD;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // 1-D grid (ks_grid): workgroups go to the 8 XCDs round robin by their id, and the `groups` workgroups of a row tile
+    // gather the same rows -- they get ids that are equal modulo 8, so they share one XCD's L2
+    const int rtile = ((int)(blockIdx.x >> 3) / a.groups) * 8 + (int)(blockIdx.x & 7);
+    if (rtile * 16 >= a.E1) return;
+    const int r0 = rtile * 16;
+    const int grp = (int)(blockIdx.x >> 3) % a.groups;
+    const int t = grp * a.tg + wave;              // this wave's first output tile (if < t_end)
+    const int t_end = min(NT, (grp + 1) * a.tg);
+    const size_t pslot = (size_t)a.E1 * Hp;       // one group's partial rows
+    const bool dbg_on = a.dbg && rtile == 1 && grp == 0 && threadIdx.x == 0;
+    if (dbg_on) a.dbg[0] = wall_clock64();
+
+    // ---- P1: gather.  Groups past the last re-read group 0 and are not added; null slots read row 0, whose h is 0 and whose
+    // partials are finite.
+    for (int lr = wave; lr < 16; lr += GGPM_NWA) {
+        const int row = r0 + lr;
+        GgpmRowList rl;
+        if (a.h0_zero) { rl.lo = 0; rl.n = 0; } else rl = ggpm_row_list(a.rowptr, row, a.E1);
+        const size_t rowo = (size_t)(row < a.E1 ? row : 0) * Hp;
+        if (Hp <= 320) {
+            // H = 250, 300: a lane takes four of the first 256 columns and, as scalars, one of the up to 64 behind them, so
+            // the h row and the partial q rows of a predecessor are 5 * (1 + GGPM_KS_MAXG) = 30 registers of loads and TWO
+            // predecessors per trip fit the 128 registers of a 16-wave workgroup, as in gru_fwd_a
+            const int c = lane * 4, tc = 256 + lane;
+            const bool on = c < Hp, ton = tc < Hp;
+            const int cs = on ? c : 0, tcs = ton ? tc : 0;
+            float4 s = ggpm_zero4(), g = ggpm_zero4(), rc = ggpm_zero4();
+            float s1 = 0.f, g1 = 0.f, rc1 = 0.f;
+            const float4 xr = ggpm_ld4(a.Xr + rowo + cs);
+            const float xr1 = a.Xr[rowo + tcs];
+            for (int base = 0; base < rl.n; base += 64) {
+                const int chunk = ggpm_list_chunk(a.col, rl, base, lane);
+                const int m = min(64, rl.n - base);
+                for (int j = 0; j < m; j += 2) {
+                    float4 h[2], qp[2][GGPM_KS_MAXG];
+                    float h1[2], qp1[2][GGPM_KS_MAXG];
+#pragma unroll
+                    for (int u = 0; u < 2; ++u) {
+                        const size_t p = (size_t)ggpm_list_at(chunk, j + u, m) * Hp;
+                        h[u] = ggpm_ld4(a.Hprev + p + cs);
+                        h1[u] = a.Hprev[p + tcs];
+#pragma unroll
+                        for (int gi = 0; gi < GGPM_KS_MAXG; ++gi) {
+                            const float* part = a.Qpart_in + (gi < a.groups ? gi : 0) * pslot + p;
+                            qp[u][gi] = ggpm_ld4(part + cs);
+                            qp1[u][gi] = part[tcs];
+                        }
+                    }
+#pragma unroll
+                    for (int u = 0; u < 2; ++u) {
+                        float4 q = qp[u][0];
+                        float q1 = qp1[u][0];
+#pragma unroll
+                        for (int gi = 1; gi < GGPM_KS_MAXG; ++gi)
+                            if (gi < a.groups) { q = q + qp[u][gi]; q1 = q1 + qp1[u][gi]; }      // before xr + q
+                        const float4 r = ggpm_fsigmoid4<false>(xr + q);
+                        const float4 rh = r * h[u];
+                        s = s + h[u];
+                        g = g + rh;
+                        rc = rc + rh * one_minus(r);
+                        const float r1 = ggpm_fsigmoid<false>(xr1 + q1), rh1 = r1 * h1[u];
+                        s1 = s1 + h1[u];
+                        g1 = g1 + rh1;
+                        rc1 = rc1 + rh1 * (1.f - r1);
+                    }
+                }
+            }
+            if (on) {
+                ggpm_st4(Ts + lr * LD + c, s);
+                ggpm_st4(Tg + lr * LD + c, g);
+                if (STASH && row < a.E1 && (c >> 4) / a.tg == grp) {
+                    const size_t o = (size_t)row * Hp + c;
+                    ggpm_st4(a.S + o, s); ggpm_st4(a.G + o, g); ggpm_st4(a.R + o, rc);
+                }
+            }
+            if (ton) {
+                Ts[lr * LD + tc] = s1;
+                Tg[lr * LD + tc] = g1;
+                if (STASH && row < a.E1 && (tc >> 4) / a.tg == grp) {
+                    const size_t o = (size_t)row * Hp + tc;
+                    a.S[o] = s1; a.G[o] = g1; a.R[o] = rc1;
+                }
+            }
+        } else {
+            // wider rows: 512 columns per sweep as in gru_fwd_a, ONE predecessor per trip (2 + 2 * GGPM_KS_MAXG loads of 16 bytes)
+            for (int c0 = 0; c0 < Hp; c0 += 512) {
+                int c[2], cs[2];
+                bool on[2];
+                float4 s[2], g[2], rc[2], xr[2];
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    c[k] = c0 + 256 * k + lane * 4;
+                    on[k] = c[k] < Hp;
+                    cs[k] = on[k] ? c[k] : 0;
+                    s[k] = ggpm_zero4(); g[k] = ggpm_zero4(); rc[k] = ggpm_zero4();
+                    xr[k] = ggpm_ld4(a.Xr + rowo + cs[k]);
+                }
+                for (int base = 0; base < rl.n; base += 64) {
+                    const int chunk = ggpm_list_chunk(a.col, rl, base, lane);
+                    const int m = min(64, rl.n - base);
+                    for (int j = 0; j < m; ++j) {
+                        const size_t p = (size_t)ggpm_list_at(chunk, j, m) * Hp;
+                        float4 h[2], qp[2][GGPM_KS_MAXG];
+#pragma unroll
+                        for (int k = 0; k < 2; ++k) {
+                            h[k] = ggpm_ld4(a.Hprev + p + cs[k]);
+#pragma unroll
+                            for (int gi = 0; gi < GGPM_KS_MAXG; ++gi)
+                                qp[k][gi] = ggpm_ld4(a.Qpart_in + (gi < a.groups ? gi : 0) * pslot + p + cs[k]);
+                        }
+#pragma unroll
+                        for (int k = 0; k < 2; ++k) {
+                            float4 q = qp[k][0];
+#pragma unroll
+                            for (int gi = 1; gi < GGPM_KS_MAXG; ++gi)
+                                if (gi < a.groups) q = q + qp[k][gi];
+                            const float4 r = ggpm_fsigmoid4<false>(xr[k] + q);
+                            const float4 rh = r * h[k];
+                            s[k] = s[k] + h[k];
+                            g[k] = g[k] + rh;
+                            rc[k] = rc[k] + rh * one_minus(r);
+                        }
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    if (!on[k]) continue;
+                    ggpm_st4(Ts + lr * LD + c[k], s[k]);
+                    ggpm_st4(Tg + lr * LD + c[k], g[k]);
+                    if (STASH && row < a.E1 && (c[k] >> 4) / a.tg == grp) {
+                        const size_t o = (size_t)row * Hp + c[k];
+                        ggpm_st4(a.S + o, s[k]); ggpm_st4(a.G + o, g[k]); ggpm_st4(a.R + o, rc[k]);
+                    }
+                }
+            }
+        }
+    }
+    if (dbg_on) a.dbg[1] = wall_clock64();
+
+    const bool p2_gemm = !a.h0_zero;
+    const float* const wps2[2] = {a.Wz, a.Wh};
+    GgpmRing<2> ring2;
+    if (p2_gemm && t < t_end) ggpm_ring_prefetch<2>(wps2, KC, t, lane, ring2);
+    ggpm_lds_barrier();      // LDS tiles only: the stash stores above finish under the GEMM
+    if (dbg_on) a.dbg[2] = wall_clock64();
+
+    // ---- P2: gate GEMMs + gate math for this wave's (at most two) tiles, as straight-line code.  What the phase behind it
+    // reads from memory is asked for BEFORE the epilogue's stores (a wave's loads and stores are acknowledged in order:
+    // behind them every load would wait for the stores to land) -- by a wave without a tile right away, by the others behind
+    // their last gate GEMM: the U_r fragments of this group's K slice for the wave's first two output tiles, and the previous
+    // step's partials of the wave's own rows and columns (first tile).
+    const int lr = lane & 15, row = r0 + lr;
+    const int k0 = grp * a.tg, k1 = t_end;
+    f32x4 head[4], head2[4];
+    float4 hkeep[2] = {ggpm_zero4(), ggpm_zero4()};      // the h' fragments of this wave's tiles; rows past E1 stay 0
+    // the previous step's partials of this workgroup's rows and columns, summed (the order of the gather) into that step's Qs
+    // slot: 16 rows x 4 (k1 - k0) float4, spread over the waves [w0, w0 + nw)
+    auto own_sums = [&](int w0, int nw) {
+        const int n4 = 4 * (k1 - k0);
+        for (int i = (wave - w0) * 64 + lane; i < 16 * n4; i += nw * 64) {
+            const int orow = r0 + i / n4;
+            if (orow >= a.E1) continue;
+            const size_t o = (size_t)orow * Hp + 16 * k0 + 4 * (i % n4);
+            float4 qo[GGPM_KS_MAXG];
+#pragma unroll
+            for (int gi = 0; gi < GGPM_KS_MAXG; ++gi) qo[gi] = ggpm_ld4(a.Qpart_in + (gi < a.groups ? gi : 0) * pslot + o);
+            float4 q = qo[0];
+#pragma unroll
+            for (int gi = 1; gi < GGPM_KS_MAXG; ++gi)
+                if (gi < a.groups) q = q + qo[gi];
+            ggpm_st4(a.Qsum + o, q);
+        }
+    };
+    const bool qsum_on = a.Qsum && a.Qpart_in;
+    const int nown = min(k1 - k0, GGPM_NWA);      // waves that own a tile; the others are idle during P2 and take the sums
+    auto prefetch = [&]() {
+        if (a.Qpart_out) {
+            if (wave < NT) ggpm_slice_head(a.Ur, KC, wave, k0, k1, lane, head);
+            if (wave + GGPM_NWA < NT) ggpm_slice_head(a.Ur, KC, wave + GGPM_NWA, k0, k1, lane, head2);
+        }
+    };
+    auto p2_tile = [&](int tt, float4& keep, bool last) {
+        const int c = 16 * tt + 4 * (lane >> 4);
+        const size_t o = (size_t)(row < a.E1 ? row : 0) * Hp + c;
+        const float4 xz = ggpm_ld4(a.Xz + o), xh = ggpm_ld4(a.Xh + o);      // in flight under the GEMM
+        f32x4 acc[2][1];
+        ggpm_zero_acc<2, 1>(acc);
+        if (p2_gemm) {
+            const float* const tiles[2] = {Ts, Tg};
+            ggpm_wave_gemm_ring<2, 1>(tiles, LD, wps2, KC, tt, last ? -1 : tt + GGPM_NWA, lane, acc, ring2);
+        }
+        if (last) prefetch();
+        if (dbg_on) a.dbg[3] = wall_clock64();
+        if (row >= a.E1) return;
+        float4 h = ggpm_zero4(), z = ggpm_zero4(), m = ggpm_zero4();
+        if (row != 0) {
+            const float4 s = ggpm_ld4(Ts + lr * LD + c);
+            const float4 pz = ggpm_f4(acc[0][0]) + xz, pm = ggpm_f4(acc[1][0]) + xh;
+            z = ggpm_sigmoid4(pz);
+            m = make_float4(tanhf(pm.x), tanhf(pm.y), tanhf(pm.z), tanhf(pm.w));
+            h = make_float4((1.f - z.x) * s.x + z.x * m.x, (1.f - z.y) * s.y + z.y * m.y,
+                            (1.f - z.z) * s.z + z.z * m.z, (1.f - z.w) * s.w + z.w * m.w);
+        }
+        ggpm_st4(a.Hnew + o, h);
+        keep = h;
+        if (STASH) {
+            ggpm_st4(a.Z + o, z);
+            ggpm_st4(a.M + o, m);
+        }
+    };
+    if (t >= t_end) {
+        prefetch();
+        if (qsum_on) own_sums(nown, GGPM_NWA - nown);
+    } else if (t + GGPM_NWA >= t_end) p2_tile(t, hkeep[0], true);
+    else { p2_tile(t, hkeep[0], false); p2_tile(t + GGPM_NWA, hkeep[1], true); }
+    if (dbg_on) a.dbg[4] = wall_clock64();
+
+    // ---- partial q' of this group
+    if (a.Qpart_out) {
+        ggpm_lds_barrier();      // every wave is done with g
+        if (t < t_end) ggpm_st4(Tg + lr * LD + 16 * t + 4 * (lane >> 4), hkeep[0]);
+        if (t + GGPM_NWA < t_end) ggpm_st4(Tg + lr * LD + 16 * (t + GGPM_NWA) + 4 * (lane >> 4), hkeep[1]);
+        ggpm_lds_barrier();
+        float* const part = a.Qpart_out + (size_t)grp * pslot;
+        int pi = 0;
+        for (int tt = wave; tt < NT; tt += GGPM_NWA, ++pi) {
+            const int c = 16 * tt + 4 * (lane >> 4);
+            const float4 b = grp == 0 ? ggpm_ld4(a.bu + c) : ggpm_zero4();
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            if (pi == 1) {
+#pragma unroll
+                for (int d = 0; d < 4; ++d) head[d] = head2[d];
+            }
+            // (a third tile and beyond: their fragments come a tile ahead)
+            ggpm_wave_gemm_slice(Tg, LD, a.Ur, KC, tt, k0, k1, pi >= 1 && tt + GGPM_NWA < NT ? tt + GGPM_NWA : -1, k0, k1, lane, acc, head);
+            if (row < a.E1) ggpm_st4(part + (size_t)row * Hp + c, grp == 0 ? ggpm_f4(acc) + b : ggpm_f4(acc));
+        }
+    }
+    if (qsum_on && nown == GGPM_NWA) own_sums(0, GGPM_NWA);      // (no idle wave: everyone, at the end)
+    if (dbg_on) a.dbg[7] = wall_clock64();
+}
+
+// Kernel B of such a level (its last executed step, when that is not the level's last): q' as the sum over the column groups'
+// K slices in group order, each slice the chain gru_fwd_a_ks's partials run, so what the step leaves in Qs has the bits a
+// sum of partials would have (the fixed-point level stops early and must agree bit for bit with the level that does not).
+__global__ void GGPM_A_BOUNDS gru_fwd_b_ks(GruFwdArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int Hp = a.Hp, LD = Hp + 4, KC = Hp / 16, NT = Hp / 16;
+    float* Th = lds;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int r0 = blockIdx.x * 16;
+    const int grp = blockIdx.y;
+    const int t_end = min(NT, (grp + 1) * a.tg);
+    ggpm_load_rows_to_lds<16, false>(a.Hnew, r0, a.E1, Hp, LD, Th);
+    __syncthreads();
+    const int row = r0 + (lane & 15);
+    for (int tt = grp * a.tg + wave; tt < t_end; tt += GGPM_NWA) {
+        const int c = 16 * tt + 4 * (lane >> 4);
+        const float4 b = ggpm_ld4(a.bu + c);
+        f32x4 head[4];
+        ggpm_slice_head(a.Ur, KC, tt, 0, min(NT, a.tg), lane, head);
+        float4 q = ggpm_zero4();
+        for (int gi = 0; gi < a.groups; ++gi) {
+            const int k0 = gi * a.tg, k1 = min(NT, k0 + a.tg);
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            ggpm_wave_gemm_slice(Th, LD, a.Ur, KC, tt, k0, k1, gi + 1 < a.groups ? tt : -1, k1, min(NT, k1 + a.tg), lane, acc, head);
+            q = gi == 0 ? ggpm_f4(acc) + b : q + ggpm_f4(acc);
+        }
+        if (row < a.E1) ggpm_st4(a.Qnew + (size_t)row * Hp + c, q);
     }
 }
 
@@ -769,9 +1096,40 @@ inline unsigned long long* adebug_stamps(unsigned long long*& buf) {
     return buf;
 }
 
-void launch_fwd(GruFwdArgs a, bool rt2, bool stash, bool with_b, double flops1, hipStream_t s) {
+// the 1-D grid of gru_fwd_a_ks: ids i, i + 8, .. i + 8 (groups - 1) are the column groups of one row tile
+inline dim3 ks_grid(const GruFwdArgs& a) { return dim3(8 * ggpm_ceil_div(ggpm_ceil_div(a.E1, 16), 8) * a.groups); }
+
+// ks: the level runs on the K-split form of q' (ksplit_q_form: gate mode 0, one row tile, column groups, so nothing is fused);
+// a step that leaves partials (a.Qpart_out) has no B launch
+void launch_fwd(GruFwdArgs a, bool rt2, bool stash, bool with_b, bool ks, double flops1, hipStream_t s) {
     const StepLds step = fwd_step<GruCell>(a.Hp, a.tg, rt2, a.bf16, with_b);
     a.fuse_b = step.fuse;
+    if (ks) {
+        static unsigned long long* ks_dbg_buf = nullptr;
+        static int ks_dbg_count = 0;
+        a.dbg = adebug_stamps(ks_dbg_buf);
+        ggpm_timing_begin(GruCell::timing_base, s, ((a.Qpart_out ? 1 : 0) + (a.h0_zero ? 0 : GruCell::gate_products)) * flops1);
+        {
+            auto kernel = stash ? gru_fwd_a_ks<true> : gru_fwd_a_ks<false>;
+            set_lds(kernel, step.a);
+            kernel<<<ks_grid(a), GGPM_NWA * 64, step.a, s>>>(a);
+        }
+        ggpm_timing_end(GruCell::timing_base, s);
+        if (a.dbg && a.Qpart_in && a.Qpart_out && (++ks_dbg_count % 97) == 0) {
+            unsigned long long h[8];
+            (void)hipStreamSynchronize(s);
+            (void)hipMemcpy(h, a.dbg, sizeof(h), hipMemcpyDeviceToHost);
+            fprintf(stderr, "[adebug ksplit E1=%d groups=%d] gather %.2f barrier %.2f gemm %.2f epilogue %.2f partial q' %.2f us\n",
+                    a.E1, a.groups, (h[1] - h[0]) * 0.01, (h[2] - h[1]) * 0.01, (h[3] - h[2]) * 0.01, (h[4] - h[3]) * 0.01,
+                    (h[7] - h[4]) * 0.01);
+        }
+        if (with_b && !a.Qpart_out) {
+            ggpm_timing_begin(GruCell::timing_base + 4, s, 1 * flops1);
+            launch_step(gru_fwd_b_ks, a, false, step.b, s);
+            ggpm_timing_end(GruCell::timing_base + 4, s);
+        }
+        return;
+    }
     static unsigned long long* dbg_buf = nullptr;
     static int dbg_count = 0;
     a.dbg = adebug_stamps(dbg_buf);
@@ -839,6 +1197,19 @@ int ggpm_gru_level_form(int E1, int H, int sparse, int training, const ggpm_leve
     return level_form<GruCell>(E1, H, sparse, training, o, out);
 }
 
+// the K-split form of q' (ggpm_level_opts.q_part): the buffer of a level, and whether a forward call would use one
+extern "C" size_t ggpm_level_q_part_bytes(int E1, int H) {
+    if (E1 <= 0 || H <= 0) return 0;
+    const int Hp = ggpm_padded_hidden(H);
+    return q_part_floats(E1, Hp, pick_tg(E1, Hp / 16)) * sizeof(float);
+}
+extern "C" int ggpm_level_ksplit_q(int lstm, int E1, int H, int sparse, const ggpm_level_opts* opts) {
+    if (lstm || sparse || E1 <= 0 || H <= 0) return 0;
+    const int Hp = ggpm_padded_hidden(H);
+    if (!GruCell::shape_ok(E1, Hp)) return 0;
+    return ksplit_q_form(level_plan<GruCell>(ggpm_opts_or_default(opts), E1, Hp, false), Hp) ? 1 : 0;
+}
+
 namespace {
 __global__ void sparse_init_state(const float* __restrict__ h_in, const unsigned char* __restrict__ frozen,
                                   float* __restrict__ H0, int Hp) {
@@ -865,6 +1236,10 @@ int gru_forward_impl(const LevelCall& c, int save_for_backward, const ggpm_level
     const LevelPlan plan = level_plan<GruCell>(o, E1, Hp, frozen != nullptr);
     const bool rt2 = plan.rt2;
     const int bf16 = plan.gm;      // gate mode 0 / 1 / 2
+    // K-split q' (ggpm_level_opts.q_part): every step but the last executed one leaves partials in place of its B launch
+    const bool ks = o.q_part && !frozen && ksplit_q_form(plan, Hp);
+    const size_t qblock = q_part_floats(E1, Hp, plan.tg) / 2;
+    if (ks && o.q_part_bytes < 2 * qblock * sizeof(float)) return GGPM_ERR_WORKSPACE;
     const size_t mstep = ggpm_packed_matrix_floats(Hp, bf16);
     float* pWz = wpack; float* pWh = wpack + mstep; float* pUr = wpack + 2 * mstep;
     float* pbu = wpack + 3 * ggpm_packed_matrix_slot(Hp);
@@ -935,7 +1310,15 @@ int gru_forward_impl(const LevelCall& c, int save_for_backward, const ggpm_level
             a.Qprev = Qs + (size_t)((t - 1) & 1) * slot; a.Qnew = Qs + (size_t)(t & 1) * slot;
             a.S = a.G = a.Z = a.M = a.R = nullptr;
         }
-        launch_fwd(a, rt2, stash, t < depth, flops1, s);
+        if (ks) {
+            a.groups = ggpm_ceil_div(Hp / 16, tg);
+            if (t < run_depth) a.Qpart_out = o.q_part + (size_t)(t & 1) * qblock;
+            if (t > 1) {
+                a.Qpart_in = o.q_part + (size_t)((t - 1) & 1) * qblock;
+                a.Qsum = save_for_backward ? const_cast<float*>(a.Qprev) : nullptr;      // (only the backward reads Qs again)
+            }
+        }
+        launch_fwd(a, rt2, stash, t < depth, ks, flops1, s);
     }
     GGPM_CHECK_LAUNCH();
     return GGPM_OK;

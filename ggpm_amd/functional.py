@@ -681,7 +681,8 @@ class LevelOpts(ctypes.Structure):
                 ("gather_idx", ctypes.c_void_p), ("scatter_h", ctypes.c_void_p), ("scatter_c", ctypes.c_void_p),
                 ("scatter_idx", ctypes.c_void_p), ("skip_x_sums", ctypes.c_int), ("run_depth", ctypes.c_int),
                 ("lo", ctypes.c_int), ("skip_bias_u", ctypes.c_int), ("skip_sparse_wgrads", ctypes.c_int),
-                ("h_out", ctypes.c_void_p), ("c_out", ctypes.c_void_p), ("fixed_slot", ctypes.c_int)]
+                ("h_out", ctypes.c_void_p), ("c_out", ctypes.c_void_p), ("fixed_slot", ctypes.c_int),
+                ("q_part", ctypes.c_void_p), ("q_part_bytes", ctypes.c_size_t)]
 
 
 class LevelForm(ctypes.Structure):

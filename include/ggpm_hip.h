@@ -447,7 +447,26 @@ typedef struct ggpm_level_opts {
      *     gradient stash, free below lo - 1 >= 2) and contracted as [hi; lo]^T [X*; X*], K = 2 E1 instead of C E1.
      * A level's forward, backward and weight_grads pass the same value. */
     int fixed_slot;
+    /* Dense GRU forward on a column-grouped level (ggpm_level_ksplit_q says which calls): q_part non-NULL, of at least
+     * ggpm_level_q_part_bytes(E1, H) bytes, lets every forward step but the last executed one drop its B launch.  A column
+     * group multiplies the h' columns it holds by the matching K slice of U_r inside kernel A and stores a partial q' over
+     * all output columns (group 0 adds b_u); the next step's gather adds the `groups` partial rows of a predecessor in
+     * ascending group order and writes the sums of its own rows to Qs, so Qs holds what it always held.  The buffer is two
+     * blocks of [groups][E1][Hp] floats used alternately by depth parity; its contents before and after the call mean
+     * nothing.  q' is then a sum of `groups` short chains instead of one long one: results agree with the B-launch form to
+     * fp32 summation order and are run-to-run identical.  NULL (default), or a call the form does not apply to: the B
+     * launches as ever.  A buffer that is too small: GGPM_ERR_WORKSPACE. */
+    float* q_part;
+    size_t q_part_bytes;
 } ggpm_level_opts;
+/* Bytes of ggpm_level_opts.q_part for a level of E1 rows and hidden size H: 2 * groups * E1 * Hp * sizeof(float), with
+ * `groups` as ggpm_level_form_query reports it under default options.  Host only. */
+size_t ggpm_level_q_part_bytes(int E1, int H);
+/* 1 when a forward call of this level (arguments as ggpm_level_form_query) takes the K-split form of q' once it is given
+ * ggpm_level_opts.q_part: a dense GRU call on fp32 MFMA (gate mode 0) with one row tile per workgroup, 2 to 5 column groups
+ * and at most two output tiles of a group per wave.  0 otherwise (LSTM, sparse, other geometries), and on bad arguments.
+ * The answer does not depend on q_part itself, nor does ggpm_level_form_query's.  Host only. */
+int ggpm_level_ksplit_q(int lstm, int E1, int H, int sparse, const ggpm_level_opts* opts);
 
 /* The form a level call takes: which of the depth kernels' launch geometries, gate modes and LDS layouts a GRU (lstm = 0) or
  * LSTM level of E1 message rows (pad row included) and hidden size H runs on -- dense (sparse = 0: ggpm_*_forward / _backward)
