@@ -81,11 +81,14 @@ def mlp(vec, ctx, W1, b1, W2, b2, sigmoid=False):
 
 def assm_score(p, n, icls, nth, z_row):
     """enum_attach + get_assm_score of one prediction with ``n`` candidates -> [n] scores.  The tree-only decoder's
-    enum_attach feeds no atom vectors: ref_decoder.enum_attach with zero-width candidate vectors."""
+    enum_attach feeds no atom vectors: ref_decoder.enum_attach with zero-width candidate vectors.  The n rows are then one
+    row n times, and the decode loop ranks them with a stable sort, so the tie has to be exact: the row is evaluated once
+    and repeated (n equal rows of one matrix product need not come out bit-equal -- a BLAS may round its edge rows on
+    another path, and on such a host the replayed decodes attach at another atom)."""
     none = torch.zeros(1, 0, dtype=torch.float64)
-    v = RD.enum_attach(p, none, torch.zeros(n, len(icls), dtype=torch.long), list(icls), int(nth))
+    v = RD.enum_attach(p, none, torch.zeros(1, len(icls), dtype=torch.long), list(icls), int(nth))
     z = torch.as_tensor(np.asarray(z_row)).double()
-    return (R._affine(p, "W_assm", v) * z.unsqueeze(0)).sum(dim=-1)
+    return (R._affine(p, "W_assm", v) * z.unsqueeze(0)).sum(dim=-1).expand(n).clone()
 
 
 # ---------------------------------------------------------------------------------------------- top k
