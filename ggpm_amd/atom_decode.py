@@ -11,25 +11,26 @@ batch: per step the frozen mask, the masked predecessor CSR of the step's bonds 
 incoming-message CSR of the step's atoms and its transpose, and -- composed with the scatter into the zeroed node
 buffer the reference rebuilds at every step -- where each pooled cluster vector (``embed_sub_tree``) and each
 attachment candidate (``enum_attach``) reads the step's atom vectors.  ``atom_decode`` then runs the whole loop as one
-``torch.autograd.Function`` whose forward and backward call the C ABI directly (``ggpm_*_sparse_forward/backward``,
+``torch.autograd.Function`` whose forward and backward call the C ABI directly (``ggpm_decode_steps_*``,
 ``ggpm_segment_sum``, ``ggpm_gemm*``): no per-step autograd graph, no per-step index kernels, the gate input
 projections of ALL bonds computed once (they are depth- and step-invariant one-hot look-ups), and every weight gradient
 formed once per call (the read-out's from the stacked rows of all steps, the input halves from the summed ``dX``).
 
-Compact steps (default, _dev.ATOM_COMPACT = False switches them off): a step recomputes a few hundred of the level's thousands
-of bond messages, so its ``sparse_forward`` runs on the step's COMPACT row set -- the step's bonds plus the frozen
-older bonds they read, renumbered 0..n-1 with host-built local CSRs -- instead of on every row of the level with a
-frozen mask: the rows are gathered from / scattered back into the level-wide state (``ggpm_gather_rows`` /
-``ggpm_scatter_rows``), the depth kernels launch ~1/8 of the row tiles and the hidden-half weight-gradient
-contractions shrink by the same factor.  Same arithmetic per row, so the results are bit-identical to the full-level
-form except for the weight gradients' summation order.
+Compact steps: a step recomputes a few hundred of the level's thousands of bond messages, so its ``sparse_forward`` runs
+on the step's COMPACT row set -- the step's bonds plus the frozen older bonds they read, renumbered 0..n-1 with
+host-built local CSRs -- and not on every row of the level under a frozen mask: a step's frozen rows are gathered from
+the blocks of the earlier steps that produced them, their gradients scatter-added back there (``ggpm_gather_rows`` /
+``ggpm_scatter_rows``, ``AtomPlan.compact_tables``), the depth kernels launch ~1/8 of the row tiles and the hidden-half
+weight-gradient contractions shrink by the same factor.  Same arithmetic per row as a level-wide step.  The step loops
+themselves are csrc/decode.hip's; tests/test_decode_steps_gpu.py checks them against fp64 and, bit for bit, against the
+same steps issued one public call at a time.
 """
 from __future__ import annotations
 
 import ctypes
 import os
 import weakref
-from typing import List, Optional
+from typing import List
 
 import numpy as np
 import torch
@@ -52,14 +53,14 @@ def _transpose(rows: np.ndarray, cols: np.ndarray, ncols: int):
 class AtomPlan:
     """Host-built index tables of the atom-level decode loop (see the module docstring)."""
 
-    def __init__(self, schedule, n_gnodes: int, n_gmess: int, full: Optional[bool] = None):
-        """``full``: also build the level-wide per-step tables of the full-level form (``_AtomDecode``; default: only when
-        _dev.ATOM_COMPACT = False -- the compact form does not read them and they are the larger half of the build and upload)."""
+    def __init__(self, schedule, n_gnodes: int, n_gmess: int, full: bool = False):
+        """``full``: also build the level-wide per-step tables (frozen mask and CSRs over all E1 rows of every step).  They are
+        the reference of tests/test_oracle_golden.py::test_atom_plan_compact_row_sets_match_the_level_wide_tables; nothing on
+        the device reads them (the level-wide mask ``frozen`` is not uploaded), and they are the larger half of the build."""
         P, steps = schedule.plan, schedule.steps
         self._native, self._schedule, self._raw_cache = None, None, None
         self.T, self.N1, self.E1 = len(steps), n_gnodes, n_gmess
-        self.full = (not compact_enabled()) if full is None else bool(full)
-        full = self.full
+        self.full = full = bool(full)
         self.ok = all(len(st["atoms"]) > 0 for st in steps)          # (the reference keeps a stale node buffer otherwise)
         ints: List[np.ndarray] = []
         self.where = {}
@@ -376,26 +377,24 @@ class AtomPlan:
             ptr = {k: base + 4 * off for k, (off, n) in self.where.items()}
             meta = {k: dict(icls=view("meta_icls/%d" % k), nth=view("meta_nth/%d" % k), dest=view("meta_dest/%d" % k))
                     for k, _, _ in self.cand_blocks}
-            D = self._dev[device] = dict(device=device, ints=d32, frozen=None, frozen_loc=dl, ptr=ptr, meta=meta, desc={},
-                                         seen=set(), pack64=d64)
+            D = self._dev[device] = dict(device=device, ints=d32, frozen_loc=dl, ptr=ptr, meta=meta, desc={}, seen=set(),
+                                         pack64=d64)
         if D is None:
             di, dl = F_.upload(self.ints, device), F_.upload(self.frozen_loc, device)
-            df = F_.upload(self.frozen, device) if self.full else None
             base = di.data_ptr()
             ptr = {k: base + 4 * off for k, (off, n) in self.where.items()}
             meta = {k: {n: F_.upload(v, device) for n, v in m.items()} for k, m in self.cand_meta.items()}
             for m in meta.values():
                 m["icls"] = m["icls"].to(torch.int32)
-            D = self._dev[device] = dict(device=device, ints=di, frozen=df, frozen_loc=dl, ptr=ptr, meta=meta, desc={},
-                                         seen=set())
+            D = self._dev[device] = dict(device=device, ints=di, frozen_loc=dl, ptr=ptr, meta=meta, desc={}, seen=set())
         if device.type == "cuda":
             # uploaded on whatever stream was current then (the atom-ahead stream, usually) and read on others: tell the
             # allocator once per reading stream
             cur = torch.cuda.current_stream(device)
             if cur.cuda_stream not in D["seen"]:
                 D["seen"].add(cur.cuda_stream)
-                ts = [D["ints"], D["frozen_loc"]] + ([D["frozen"]] if D["frozen"] is not None else [])
-                ts += [v for m in D["meta"].values() for v in m.values()] + ([D["pack64"]] if "pack64" in D else [])
+                ts = [D["ints"], D["frozen_loc"]]
+                ts +=[v for m in D["meta"].values() for v in m.values()] + ([D["pack64"]] if "pack64" in D else [])
                 for t in ts:
                     t.record_stream(cur)
         return D
@@ -434,26 +433,20 @@ def _decode_steps(plan: "AtomPlan", D, ct, cp, H: int, depth: int, lstm: bool):
     return d, keep
 
 
-# _dev.DECODE_DRIVER (False: the step loops are issued from Python; dev A/B, tests) -- read at CALL time, like every
-# _dev setting: a tool or test that flips the attribute after this module was imported gets the other form.
-# The two step loops are ~280 launches = 1.5-1.8 ms of host time each, inside one C call.  _dev.ATOM_ASYNC (default)
-# hands them to a worker thread of the library (ggpm_decode_steps_*_async): the forward loop is then issued beside the
-# encoder's forward, the backward loop beside the encoder's backward -- the autograd engine reaches the two nodes at about
-# the same time and would otherwise issue one chain only after the other, although they do not depend on each other.
-# What follows a loop on its stream (read-out / parameter gradients) is enqueued after ggpm_decode_join.
+# The two step loops are ~280 launches = 1.5-1.8 ms of host time each, inside one C call (csrc/decode.hip; the weights are
+# packed by the first step and shared by the others).  _dev.ATOM_ASYNC (default; read at CALL time, like every _dev
+# setting) hands them to a worker thread of the library (ggpm_decode_steps_*_async): the forward loop is then issued
+# beside the encoder's forward, the backward loop beside the encoder's backward -- the autograd engine reaches the two
+# nodes at about the same time and would otherwise issue one chain only after the other, although they do not depend on
+# each other.  What follows a loop on its stream (read-out / parameter gradients) is enqueued after ggpm_decode_join.
+# Without it, and in a backward whose gradients cannot be published, the synchronous entry points issue the same launches
+# from the calling thread.
 _INFLIGHT: list = []         # buffers named by loops the worker may still be issuing (released by the next join)
 
 
 def _join_worker(what: str) -> None:
     _lib.check(_lib.load().ggpm_decode_join(), what)
     del _INFLIGHT[:]
-
-
-# _dev.PACK_ONCE = False: every decode step packs its weights again (dev A/B)
-
-
-def compact_enabled() -> bool:
-    return _dev.ATOM_COMPACT
 
 
 def _vp(addr: int) -> ctypes.c_void_p:
@@ -465,150 +458,10 @@ def _cell(kind: str, params, I: int, H: int):
     return F_.cell_for(kind == "LSTM", params[:-2], I, H), params[-2], params[-1]
 
 
-def _full_level(plan: AtomPlan, kind: str, depth: int, H: int, Fdim: int, I: int, fn_all, hmess, drop, params, infer: bool):
-    """The forward of _AtomDecode -> (pooled, cand, what the backward reads or None, device tables).  ``infer``: the
-    forward-only form -- every step's depth loop in two ping-pong slots, its final state written to one of two level-wide
-    buffers (ggpm_level_opts.h_out), no stashes; the same launches otherwise, so the same outputs bit for bit."""
-    lib = _lib.load()
-    dev = hmess.device
-    D = plan.to_device(dev)
-    ptr, P = D["ptr"], F_._p
-    Hp = F_.padded_hidden(H)
-    E1, T = plan.E1, plan.T
-    f32 = dict(dtype=torch.float32, device=dev)
-    cell, Wout, bout = _cell(kind, params, I, H)
-    lstm, G = cell.G == 4, cell.G
-    # hoisted gate input projections of ALL bond messages (step and depth invariant)
-    X = torch.empty(G, E1, Hp, **f32)
-    cell.project_inputs(hmess, F_._ld(hmess), E1, X)
-    if infer:
-        Hs, Cs, Qs, St = cell.alloc_state(E1, depth, save=False)
-        hbuf = torch.empty(2, E1, Hp, **f32)
-        cbuf = torch.empty(2, E1, Hp, **f32) if lstm else None
-    else:
-        Hs = torch.empty(T, depth + 1, E1, Hp, **f32)
-        Cs = torch.empty(T, depth + 1, E1, Hp, **f32) if lstm else None
-        Qs = torch.empty(T, depth, E1, Hp, **f32)
-        St = torch.empty(T, 5, depth, E1, Hp, **f32)
-    zero = torch.zeros(E1, Hp, **f32)
-    ns_tot, n_inst = plan.aoff[-1], plan.ioff[-1]
-    NODE = torch.empty(ns_tot, Hp, **f32)
-    NEI = torch.empty(ns_tot, Hp, **f32)
-    pooled = torch.empty(n_inst, Hp, **f32)
-    cand = torch.zeros(max(plan.n_cand, 1), Hp, **f32)
-    wpack = cell.alloc_pack()
-    s = F_._stream()
-    frz = D["frozen"]
-    ldF, ldwo = F_._ld(fn_all), Wout.stride(0)
-    h_prev, c_prev = zero, zero
-    for t in range(T):
-        a0, a1, i0, i1 = plan.aoff[t], plan.aoff[t + 1], plan.ioff[t], plan.ioff[t + 1]
-        ns, ni = a1 - a0, i1 - i0
-        if infer:
-            Hs_t, Cs_t, Qs_t, st = Hs, Cs, Qs, St
-            opts = ctypes.byref(F_.LevelOpts(h_out=hbuf[t & 1].data_ptr(),
-                                             c_out=cbuf[t & 1].data_ptr() if lstm else None))
-        else:
-            Hs_t, Cs_t, Qs_t, st, opts = Hs[t], Cs[t] if lstm else None, Qs[t], St[t], None
-        cell.sparse_forward(rows=E1, depth=depth, h_in=h_prev, c_in=c_prev, frozen=frz[t], X=X,
-                            pred=(ptr[("pred_rp", t)], ptr[("pred_col", t)]), Hs=Hs_t, Cs=Cs_t, Qs=Qs_t, St=st, wpack=wpack,
-                            save=not infer, opts=opts, stream=s)
-        if lstm:
-            c_prev = cbuf[t & 1] if infer else Cs[t, depth]
-        h_prev = hbuf[t & 1] if infer else Hs[t, depth]
-        nei, node = NEI[a0:a1], NODE[a0:a1]
-        _lib.check(lib.ggpm_segment_sum(P(h_prev), Hp, _vp(ptr[("agr_rp", t)]), _vp(ptr[("agr_col", t)]), ns, H,
-                                        P(nei), Hp, 0, Hp, s), "segment_sum")
-        F_.gemm_ksegments(1, ns, H, [fn_all[a0:a1], nei], [ldF, Hp], [Wout, Wout[:, Fdim:]], [ldwo, ldwo], [Fdim, H],
-                          node, Hp, Hp, bias=bout, act=F_.ACT_RELU)
-        if drop is not None:
-            _lib.check(lib.ggpm_dropout(P(node), ns, H, Hp, drop[0], drop[1], drop[2], t, s), "dropout")
-        _lib.check(lib.ggpm_segment_sum(P(node), Hp, _vp(ptr[("pool_rp", t)]), _vp(ptr[("pool_col", t)]), ni, H,
-                                        P(pooled[i0:i1]), Hp, 0, Hp, s), "segment_sum")
-        for j, (row0, n) in enumerate(plan.step_cands[t]):
-            _lib.check(lib.ggpm_gather_rows(P(node), Hp, _vp(ptr[("cand_pos", t, j)]), n, H, P(cand[row0:row0 + n]),
-                                            Hp, 0, Hp, s), "gather_rows")
-    if infer:
-        return pooled, cand, None, D
-    return pooled, cand, (fn_all, hmess, X, Hs, Qs, St, NODE, NEI, *([Cs] if lstm else [])), D
-
-
-class _AtomDecode(torch.autograd.Function):
-    """(pooled cluster vectors of all visits [n_inst, Hp], attachment-candidate atom vectors [n_cand, Hp]) -- the
-    full-level form: every step runs over all E1 rows of the level with a frozen mask (_dev.ATOM_COMPACT = False)."""
-
-    @staticmethod
-    def forward(ctx, plan: AtomPlan, cell: str, depth: int, H: int, Fdim: int, I: int, fn_all, hmess, drop, *params):
-        pooled, cand, saved, D = _full_level(plan, cell, depth, H, Fdim, I, fn_all, hmess, drop, params, infer=False)
-        ctx.plan, ctx.meta, ctx.drop = plan, (cell, depth, H, Fdim, I), drop
-        ctx.save_for_backward(*saved, *params)
-        ctx.keep = D
-        return pooled, cand
-
-    @staticmethod
-    def backward(ctx, d_pooled, d_cand):
-        lib = _lib.load()
-        plan, (kind, depth, H, Fdim, I), drop = ctx.plan, ctx.meta, ctx.drop
-        lstm = kind == "LSTM"
-        sv = list(ctx.saved_tensors)
-        fn_all, hmess, X, Hs, Qs, St, NODE, NEI = sv[:8]
-        Cs = sv[8] if lstm else None
-        cell, Wout, _ = _cell(kind, sv[9:] if lstm else sv[8:], I, H)
-        D = ctx.keep
-        ptr, P = D["ptr"], F_._p
-        dev = hmess.device
-        Hp = F_.padded_hidden(H)
-        E1, T, G = plan.E1, plan.T, cell.G
-        f32 = dict(dtype=torch.float32, device=dev)
-        d_pooled = d_pooled.contiguous()
-        d_cand = d_cand.contiguous()
-        s = F_._stream()
-        frz = D["frozen"]
-        ns_tot = plan.aoff[-1]
-        DPRE = torch.empty(ns_tot, Hp, **f32)
-        dX_tot = torch.zeros(G, E1, Hp, **f32)
-        dX = torch.empty(G, E1, Hp, **f32)
-        dH, dH2 = torch.zeros(E1, Hp, **f32), torch.empty(E1, Hp, **f32)
-        dC, dC2 = (torch.zeros(E1, Hp, **f32), torch.empty(E1, Hp, **f32)) if lstm else (None, None)
-        # hidden-half weight gradients, summed over the steps (GRU: Wz_h, U_r, Wh_h, b_u)
-        acc = [torch.zeros(H, H, **f32) for _ in range(G)] + ([] if lstm else [torch.zeros(H, **f32)])
-        tmp = [torch.empty(H, H, **f32) for _ in range(G)] + ([] if lstm else [torch.empty(H, **f32)])
-        work = cell.backward_workspace(E1, depth)
-        ldwo = Wout.stride(0)
-        for t in range(T - 1, -1, -1):
-            a0, a1, i0, i1 = plan.aoff[t], plan.aoff[t + 1], plan.ioff[t], plan.ioff[t + 1]
-            ns, ni = a1 - a0, i1 - i0
-            d_node = torch.empty(ns, Hp, **f32)
-            _lib.check(lib.ggpm_segment_sum(P(d_pooled[i0:i1]), Hp, _vp(ptr[("poolT_rp", t)]), _vp(ptr[("poolT_col", t)]),
-                                            ns, H, P(d_node), Hp, 0, Hp, s), "segment_sum")
-            for j, (row0, n) in enumerate(plan.step_cands[t]):
-                _lib.check(lib.ggpm_segment_sum(P(d_cand[row0:row0 + n]), Hp, _vp(ptr[("candT_rp", t, j)]),
-                                                _vp(ptr[("candT_col", t, j)]), ns, H, P(d_node), Hp, 1, 0, s), "segment_sum")
-            dpre = DPRE[a0:a1]
-            _lib.check(lib.ggpm_act_backward(P(d_node), P(NODE[a0:a1]), ns, H, Hp, F_.ACT_RELU, 0, P(dpre), s), "act_backward")
-            if drop is not None:            # d(dropout . relu) = mask * scale * relu' (the saved output is the dropped one)
-                _lib.check(lib.ggpm_dropout(P(dpre), ns, H, Hp, drop[0], drop[1], drop[2], t, s), "dropout")
-            d_nei = torch.empty(ns, Hp, **f32)
-            F_.gemm(0, 0, ns, H, H, dpre, Hp, Wout[:, Fdim:], ldwo, d_nei, Hp, Hp)
-            # d(state after step t) = what step t+1 passed back + the read-out's share
-            _lib.check(lib.ggpm_segment_sum(P(d_nei), Hp, _vp(ptr[("agrT_rp", t)]), _vp(ptr[("agrT_col", t)]), E1, H,
-                                            P(dH), Hp, 1, 0, s), "segment_sum")
-            cell.sparse_backward(rows=E1, depth=depth, frozen=frz[t], Xg=X[cell.reread],
-                                 pred=(ptr[("pred_rp", t)], ptr[("pred_col", t)]),
-                                 succ=(ptr[("succ_rp", t)], ptr[("succ_col", t)]), Hs=Hs[t], Cs=Cs[t] if lstm else None,
-                                 Qs=Qs[t], St=St[t], d_out=dH, dc_out=dC, d_in=dH2, dc_in=dC2, dX=dX, dW_hidden=tmp, work=work,
-                                 stream=s)
-            dC, dC2 = dC2, dC
-            dH, dH2 = dH2, dH
-            torch._foreach_add_([dX_tot] + acc, [dX] + tmp)
-        # ---- parameter gradients, once
-        return (None,) * 9 + _param_grads(cell, Wout, acc, dX_tot, hmess, DPRE, NEI, fn_all, Fdim, E1, ns_tot)
-
-
 def _compact_prelude(plan: AtomPlan, kind: str, depth: int, H: int, I: int, hmess, params):
-    """What both compact forms do in front of their step loop: the hoisted gate input projections of ALL bond messages and
-    the rows every step needs of them (gathered step by step into ``X_all``), the weight pack, the weight arrays and the
-    descriptor of the decode driver (None with _dev.DECODE_DRIVER off).
+    """What the training and the forward-only form do in front of their step loop: the hoisted gate input projections of
+    ALL bond messages and the rows every step needs of them (gathered step by step into ``X_all``), the weight pack, the
+    weight arrays and the descriptor of the decode driver.
     -> (device tables, cell, W_out, b_out, ct, cp, X_all, wpack, W_arr, ld_arr, desc, what desc names)"""
     dev = hmess.device
     D = plan.to_device(dev)
@@ -622,7 +475,7 @@ def _compact_prelude(plan: AtomPlan, kind: str, depth: int, H: int, I: int, hmes
     _lib.check(_lib.load().ggpm_gather_rows(F_._p(X), Hp, _vp(cp["xrows"]), G * ct["Ftot"], Hp, F_._p(X_all), Hp, 0, 0,
                                             F_._stream()), "gather_rows")
     W_arr, ld_arr = cell.hidden_weight_arrays()
-    desc, keep = _decode_steps(plan, D, ct, cp, H, depth, G == 4) if _dev.DECODE_DRIVER else (None, None)
+    desc, keep = _decode_steps(plan, D, ct, cp, H, depth, G == 4)
     return D, cell, Wout, bout, ct, cp, X_all, cell.alloc_pack(), W_arr, ld_arr, desc, keep
 
 
@@ -668,10 +521,10 @@ def _readout_stage(plan: AtomPlan, cp, state_src, agr_col, fn_all, Wout, bout, F
 
 
 class _AtomDecodeCompact(torch.autograd.Function):
-    """Same outputs as ``_AtomDecode`` on compact row sets (module docstring, ``AtomPlan.compact_tables``): inside the step
-    loop only ``gather frozen rows -> sparse_forward`` (backward: ``sparse_backward -> scatter-add to the rows' sources``);
-    gate inputs of all steps gathered once, read-out of all steps batched behind the loop, weight gradients contracted
-    once over the stacked stashes."""
+    """(pooled cluster vectors of all visits [n_inst, Hp], attachment-candidate atom vectors [n_cand, Hp]) from decode steps
+    on compact row sets (module docstring, ``AtomPlan.compact_tables``): inside the step loop only ``gather frozen rows ->
+    sparse_forward`` (backward: ``sparse_backward -> scatter-add to the rows' sources``); gate inputs of all steps gathered
+    once, read-out of all steps batched behind the loop, weight gradients contracted once over the stacked stashes."""
 
     @staticmethod
     def launch(plan: AtomPlan, kind: str, depth: int, H: int, Fdim: int, I: int, fn_all, hmess, drop, params,
@@ -688,42 +541,22 @@ class _AtomDecodeCompact(torch.autograd.Function):
         lib, P = _lib.load(), F_._p
         D, cell, Wout, bout, ct, cp, X_all, wpack, W_arr, ld_arr, desc, _keep = _compact_prelude(plan, kind, depth, H, I, hmess,
                                                                                                 params)
-        ptr, Hp, G, lstm = D["ptr"], cell.Hp, cell.G, cell.G == 4
+        Hp, lstm = cell.Hp, cell.G == 4
         f32 = dict(dtype=torch.float32, device=hmess.device)
-        s = F_._stream()
-        foff = ct["foff"]
         roff, qoff = plan.row_offsets(depth)
         Hs_all = torch.empty(qoff[-1], Hp, **f32)
         Cs_all = torch.empty(qoff[-1], Hp, **f32) if lstm else None
         Qs_all = torch.empty(roff[-1], Hp, **f32)
         St_all = torch.empty(5, roff[-1], Hp, **f32)
-        frz_loc = D["frozen_loc"].data_ptr()
-        deferred = False
-        if _dev.DECODE_DRIVER:         # the whole step loop as one C call (csrc/decode.hip)
-            tmp = torch.empty(2 * max(plan.nloc), Hp, **f32)
-            fn = lib.ggpm_decode_steps_forward_async if _dev.ATOM_ASYNC else lib.ggpm_decode_steps_forward
-            _lib.check(fn(
-                ctypes.byref(desc), W_arr, ld_arr, P(cell.b_u), P(X_all), P(Hs_all), P(Cs_all), P(Qs_all), P(St_all),
-                St_all.stride(0), P(wpack), P(tmp), s), "decode_steps_forward")
-            if _dev.ATOM_ASYNC:
-                deferred = True
-                _INFLIGHT.append((desc, _keep, X_all, Hs_all, Cs_all, Qs_all, St_all, wpack, tmp, params))
-        packed = ctypes.byref(F_.LevelOpts(weights_packed=1)) if _dev.PACK_ONCE else None
-        for t in (() if _dev.DECODE_DRIVER else range(plan.T)):
-            n = plan.nloc[t]
-            src = _vp(cp[("srcH", t)])
-            h_in = torch.empty(n, Hp, **f32)
-            _lib.check(lib.ggpm_gather_rows(P(Hs_all), Hp, src, n, Hp, P(h_in), Hp, 0, 0, s), "gather_rows")
-            c_in = torch.empty(n, Hp, **f32) if lstm else None
-            if lstm:
-                _lib.check(lib.ggpm_gather_rows(P(Cs_all), Hp, src, n, Hp, P(c_in), Hp, 0, 0, s), "gather_rows")
-            cell.sparse_forward(rows=n, depth=depth, h_in=h_in, c_in=c_in, frozen=frz_loc + plan.floc_off[t],
-                                X=X_all[G * foff[t]:G * foff[t + 1]].view(G, n, Hp),
-                                pred=(ptr[("lpred_rp", t)], ptr[("lpred_col", t)]), Hs=Hs_all[qoff[t]:qoff[t + 1]],
-                                Cs=Cs_all[qoff[t]:qoff[t + 1]] if lstm else None, Qs=Qs_all[roff[t]:roff[t + 1]],
-                                St=St_all[:, roff[t]:roff[t + 1]], wpack=wpack, save=True,
-                                opts=packed if t > 0 else None,       # same weights, same `wpack`: packed by the first step
-                                stream=s)
+        # the whole step loop as one C call (csrc/decode.hip)
+        tmp = torch.empty(2 * max(plan.nloc), Hp, **f32)
+        deferred = _dev.ATOM_ASYNC
+        fn = lib.ggpm_decode_steps_forward_async if deferred else lib.ggpm_decode_steps_forward
+        _lib.check(fn(
+            ctypes.byref(desc), W_arr, ld_arr, P(cell.b_u), P(X_all), P(Hs_all), P(Cs_all), P(Qs_all), P(St_all),
+            St_all.stride(0), P(wpack), P(tmp), F_._stream()), "decode_steps_forward")
+        if deferred:
+            _INFLIGHT.append((desc, _keep, X_all, Hs_all, Cs_all, Qs_all, St_all, wpack, tmp, params))
         pooled, cand, NODE, NEI, finish = _readout_stage(plan, cp, Hs_all, _vp(cp["agr_col"]), fn_all, Wout, bout, Fdim, H, drop,
                                                          deferred, "decode_join (forward)")
         return dict(pooled=pooled, cand=cand, finish=finish, keep=(D, ct, cp),
@@ -745,7 +578,7 @@ class _AtomDecodeCompact(torch.autograd.Function):
         # host time: with the step loop handed to the worker thread they are issued AFTER the loop has been posted (below),
         # so that the longest chain of the pass starts first; without the worker, here.
         F_.mark("bwd: atom level's node reached")
-        flush_after_post = _dev.DECODE_DRIVER and _dev.ATOM_ASYNC
+        flush_after_post = _dev.ATOM_ASYNC
         if not flush_after_post:
             F_.flush_deferred_early()
         plan, (kind, depth, H, Fdim, I), drop = ctx.plan, ctx.meta, ctx.drop
@@ -756,14 +589,14 @@ class _AtomDecodeCompact(torch.autograd.Function):
         params = sv[9:] if lstm else sv[8:]
         cell, Wout, _ = _cell(kind, params, I, H)
         D, ct, cp = ctx.keep
-        ptr, P = D["ptr"], F_._p
+        P = F_._p
         dev = hmess.device
         Hp = F_.padded_hidden(H)
-        E1, T, G = plan.E1, plan.T, cell.G
+        E1, G = plan.E1, cell.G
         f32 = dict(dtype=torch.float32, device=dev)
         d_pooled, d_cand = d_pooled.contiguous(), d_cand.contiguous()
         s = F_._stream()
-        foff, Ftot = ct["foff"], ct["Ftot"]
+        Ftot = ct["Ftot"]
         roff, qoff = plan.row_offsets(depth)
         ns_tot, ldwo = plan.aoff[-1], Wout.stride(0)
         # ---- read-out of all steps, backwards: clusters / candidates -> atoms -> the final states they read
@@ -794,48 +627,25 @@ class _AtomDecodeCompact(torch.autograd.Function):
         bufs, acc = cell.dW_buffers()
         nmax = max(plan.nloc)
         work = cell.backward_workspace(nmax, depth)
-        frz_loc = D["frozen_loc"].data_ptr()
         params_ref = ctx.params_ref
-        go_async = (_dev.DECODE_DRIVER and _dev.ATOM_ASYNC and F_.can_publish(*params_ref) and all(ctx.needs_input_grad[10:]))
-        if _dev.DECODE_DRIVER:         # the whole step loop as one C call (csrc/decode.hip)
-            W_arr, ld_arr = cell.hidden_weight_arrays()
-            desc, _keep = _decode_steps(plan, D, ct, cp, H, depth, lstm)
-            tmp = torch.empty(2 * nmax, Hp, **f32)
-            dW_arr = _lib.array_type(ctypes.c_void_p, 4)(*[a.data_ptr() for a in acc])
-            fn = lib.ggpm_decode_steps_backward_async if go_async else lib.ggpm_decode_steps_backward
-            _lib.check(fn(
-                ctypes.byref(desc), W_arr, ld_arr, P(X_all), P(Hs_all), P(Cs_all), P(Qs_all), P(St_all), St_all.stride(0),
-                P(dF), P(dCF), P(dX_all), P(DG_all), DG_all.stride(0), P(DQ_all), dW_arr, P(work), work.numel() * 4, P(tmp),
-                s), "decode_steps_backward")
-            if go_async:
-                _INFLIGHT.append((desc, _keep, sv, dF, dCF, dX_all, DG_all, DQ_all, acc, work, tmp))
+        go_async = _dev.ATOM_ASYNC and F_.can_publish(*params_ref) and all(ctx.needs_input_grad[10:])
+        # the whole step loop as one C call (csrc/decode.hip): per step sparse_backward, its stashes to the stacked buffers
+        # (contracted once in tail()), the frozen rows' gradient scatter-added to the step that produced their state
+        W_arr, ld_arr = cell.hidden_weight_arrays()
+        desc, _keep = _decode_steps(plan, D, ct, cp, H, depth, lstm)
+        tmp = torch.empty(2 * nmax, Hp, **f32)
+        dW_arr = _lib.array_type(ctypes.c_void_p, 4)(*[a.data_ptr() for a in acc])
+        fn = lib.ggpm_decode_steps_backward_async if go_async else lib.ggpm_decode_steps_backward
+        _lib.check(fn(
+            ctypes.byref(desc), W_arr, ld_arr, P(X_all), P(Hs_all), P(Cs_all), P(Qs_all), P(St_all), St_all.stride(0),
+            P(dF), P(dCF), P(dX_all), P(DG_all), DG_all.stride(0), P(DQ_all), dW_arr, P(work), work.numel() * 4, P(tmp),
+            s), "decode_steps_backward")
+        if go_async:
+            _INFLIGHT.append((desc, _keep, sv, dF, dCF, dX_all, DG_all, DQ_all, acc, work, tmp))
         F_.mark("bwd: atom loop posted")
         if flush_after_post:
             F_.flush_deferred_early()
         F_.mark("bwd: atom node returns")
-        for t in (() if _dev.DECODE_DRIVER else range(T - 1, -1, -1)):
-            n = plan.nloc[t]
-            dhd, dhin = dF[foff[t]:foff[t + 1]], torch.empty(n, Hp, **f32)
-            dcin = torch.empty(n, Hp, **f32) if lstm else None
-            srcF = _vp(cp[("srcF", t)])
-            # the stashes go to the stacked buffers, contracted once in tail(); same weights, same `work`: the transposes were
-            # packed by the first call
-            dq = DQ_all[qoff[t]:].data_ptr()
-            stash = (DG_all[0, roff[t]:].data_ptr(), DG_all[1, roff[t]:].data_ptr()) + \
-                ((DG_all[2, roff[t]:].data_ptr(), dq) if lstm else (dq, None))
-            opts = F_.LevelOpts(weights_packed=int(t < T - 1 and _dev.PACK_ONCE), defer_stash=stash)
-            cell.sparse_backward(rows=n, depth=depth, frozen=frz_loc + plan.floc_off[t],
-                                 Xg=X_all[G * foff[t]:G * foff[t + 1]].view(G, n, Hp)[cell.reread],
-                                 pred=(ptr[("lpred_rp", t)], ptr[("lpred_col", t)]),
-                                 succ=(ptr[("lsucc_rp", t)], ptr[("lsucc_col", t)]), Hs=Hs_all[qoff[t]:qoff[t + 1]],
-                                 Cs=Cs_all[qoff[t]:qoff[t + 1]] if lstm else None, Qs=Qs_all[roff[t]:roff[t + 1]],
-                                 St=St_all[:, roff[t]:roff[t + 1]], d_out=dhd, dc_out=dCF[foff[t]:foff[t + 1]] if lstm else None,
-                                 d_in=dhin, dc_in=dcin, dX=dX_all[G * foff[t]:G * foff[t + 1]].view(G, n, Hp), dW_hidden=acc,
-                                 ld_dW=H, work=work, opts=ctypes.byref(opts), stream=s)
-            if lstm:
-                _lib.check(lib.ggpm_scatter_rows(P(dcin), Hp, srcF, n, Hp, P(dCF), Hp, 1, s), "scatter_rows")
-            # the frozen rows' gradient goes to the step that produced their state (rows recomputed here: none)
-            _lib.check(lib.ggpm_scatter_rows(P(dhin), Hp, srcF, n, Hp, P(dF), Hp, 1, s), "scatter_rows")
         # ---- parameter gradients, once
         def tail():
             s_ = F_._stream()
@@ -854,7 +664,7 @@ class _AtomDecodeCompact(torch.autograd.Function):
                 _lib.check(lib.ggpm_gru_weight_grads_stacked(
                     R, RQ, H, P(DG_all[0]), P(St_all[1]), P(DG_all[1]), P(St_all[0]), P(DQ_all), P(Hs_all), P(acc[0]), ld[0],
                     P(acc[1]), ld[1], P(acc[3]), P(acc[2]), ld[2], P(ws), ws.numel() * 4, s_), "gru_weight_grads_stacked")
-            return _param_grads(cell, Wout, acc, dX_tot, hmess, DPRE, NEI, fn_all, Fdim, E1, ns_tot, bufs=bufs)
+            return _param_grads(cell, Wout, acc, dX_tot, hmess, DPRE, NEI, fn_all, Fdim, E1, ns_tot, bufs)
 
         if go_async:
             # The loop is being issued by the worker; this node returns now so that the engine can issue the encoder's
@@ -904,51 +714,29 @@ def _launch_infer(plan: AtomPlan, kind: str, depth: int, H: int, Fdim: int, I: i
     """The forward-only form of ``_AtomDecodeCompact.launch`` (see there)."""
     lib, P = _lib.load(), F_._p
     params = tuple(p.detach() for p in params)
-    D, cell, Wout, bout, ct, cp, X_all, wpack, W_arr, ld_arr, desc, _keep = _compact_prelude(plan, kind, depth, H, I, hmess, params)
-    ptr, Hp, G, lstm = D["ptr"], cell.Hp, cell.G, cell.G == 4
+    _, cell, Wout, bout, ct, cp, X_all, wpack, W_arr, ld_arr, desc, _keep = _compact_prelude(plan, kind, depth, H, I, hmess, params)
+    Hp, lstm, Ftot = cell.Hp, cell.G == 4, ct["Ftot"]
     f32 = dict(dtype=torch.float32, device=hmess.device)
-    s = F_._stream()
-    foff, Ftot = ct["foff"], ct["Ftot"]
     agr_col = _agr_f_col(plan, ct, depth, hmess.device)
     F_h = torch.empty(max(Ftot, 1), Hp, **f32)              # final state of every step's rows, by F id
     F_c = torch.empty(max(Ftot, 1), Hp, **f32) if lstm else None
-    Hs, Cs, Qs, St = cell.alloc_state(max(plan.nloc), depth, save=False)       # ping-pong scratch of the largest step
-    deferred = False
-    if _dev.DECODE_DRIVER:
-        fn = lib.ggpm_decode_steps_infer_async if _dev.ATOM_ASYNC else lib.ggpm_decode_steps_infer
-        _lib.check(fn(ctypes.byref(desc), W_arr, ld_arr, P(cell.b_u), P(X_all), P(F_h), P(F_c), P(Hs), P(Cs), P(Qs), P(wpack),
-                      s), "decode_steps_infer")
-        if _dev.ATOM_ASYNC:
-            deferred = True
-            _INFLIGHT.append((desc, _keep, X_all, F_h, F_c, Hs, Cs, Qs, wpack, params))
-    frz_loc = D["frozen_loc"].data_ptr()
-    for t in (() if _dev.DECODE_DRIVER else range(plan.T)):
-        n = plan.nloc[t]
-        src = _vp(cp[("srcF", t)])
-        h_in = torch.empty(n, Hp, **f32)
-        _lib.check(lib.ggpm_gather_rows(P(F_h), Hp, src, n, Hp, P(h_in), Hp, 0, 0, s), "gather_rows")
-        opts = ctypes.byref(F_.LevelOpts(weights_packed=int(t > 0 and _dev.PACK_ONCE), h_out=F_h[foff[t]].data_ptr(),
-                                         c_out=F_c[foff[t]].data_ptr() if lstm else None))
-        c_in = torch.empty(n, Hp, **f32) if lstm else None
-        if lstm:
-            _lib.check(lib.ggpm_gather_rows(P(F_c), Hp, src, n, Hp, P(c_in), Hp, 0, 0, s), "gather_rows")
-        cell.sparse_forward(rows=n, depth=depth, h_in=h_in, c_in=c_in, frozen=frz_loc + plan.floc_off[t],
-                            X=X_all[G * foff[t]:G * foff[t + 1]].view(G, n, Hp),
-                            pred=(ptr[("lpred_rp", t)], ptr[("lpred_col", t)]), Hs=Hs, Cs=Cs, Qs=Qs, St=St, wpack=wpack,
-                            save=False, opts=opts, stream=s)
+    Hs, Cs, Qs, _ = cell.alloc_state(max(plan.nloc), depth, save=False)        # ping-pong scratch of the largest step
+    deferred = _dev.ATOM_ASYNC
+    fn = lib.ggpm_decode_steps_infer_async if deferred else lib.ggpm_decode_steps_infer
+    _lib.check(fn(ctypes.byref(desc), W_arr, ld_arr, P(cell.b_u), P(X_all), P(F_h), P(F_c), P(Hs), P(Cs), P(Qs), P(wpack),
+                  F_._stream()), "decode_steps_infer")
+    if deferred:
+        _INFLIGHT.append((desc, _keep, X_all, F_h, F_c, Hs, Cs, Qs, wpack, params))
     pooled, cand, _, _, finish = _readout_stage(plan, cp, F_h, P(agr_col), fn_all, Wout, bout, Fdim, H, drop, deferred,
                                                 "decode_join (forward-only)")
     return dict(pooled=pooled, cand=cand, finish=finish)
 
 
-def _param_grads(cell, Wout, acc, dX_tot, hmess, DPRE, NEI, fn_all, Fdim, E1, ns_tot, bufs=None):
-    """Parameter gradients of the atom-level decode from the summed gate-input gradients, the accumulated hidden halves
-    ``acc`` and the stacked read-out rows (shared by both forms).  ``bufs``: the gate weights' gradient buffers when
-    ``acc`` already are their hidden halves (written in place by the stacked contractions)."""
+def _param_grads(cell, Wout, acc, dX_tot, hmess, DPRE, NEI, fn_all, Fdim, E1, ns_tot, bufs):
+    """Parameter gradients of the atom-level decode from the summed gate-input gradients, the hidden halves ``acc`` and the
+    stacked read-out rows.  ``bufs``: the gate weights' gradient buffers, whose hidden halves ``acc`` are (written in
+    place by the stacked contractions)."""
     H, Hp, I = cell.H, cell.Hp, cell.I
-    in_place = bufs is not None
-    if bufs is None:
-        bufs = [torch.empty_like(W) for W, _ in cell.gates]
     # input halves dW_k[:, :I] = dX_k^T hmess of all gates in ONE grouped launch (as the encoder's drivers form them)
     F_.gemm_grouped(1, 0, H, I, E1, [dict(A=dX_tot[k], lda=Hp, B=hmess, ldb=F_._ld(hmess), C=b, ldc=b.stride(0), n_pad=I)
                                       for k, b in enumerate(bufs)], splitk=True)
@@ -956,19 +744,14 @@ def _param_grads(cell, Wout, acc, dX_tot, hmess, DPRE, NEI, fn_all, Fdim, E1, ns
     F_.gemm(1, 0, H, Fdim, ns_tot, DPRE, Hp, fn_all, F_._ld(fn_all), dWout, dWout.stride(0), Fdim, splitk=True)
     F_.gemm(1, 0, H, H, ns_tot, DPRE, Hp, NEI, Hp, dWout[:, Fdim:], dWout.stride(0), H, splitk=True)
     dbout = F_.colsum(DPRE, ns_tot, H)
-    dbs = []
-    for k, (W, b) in enumerate(cell.gates):     # [input half from the summed dX | accumulated hidden half], gate bias
-        if not in_place and W.shape[1] > I:     # (W_r has no hidden half)
-            bufs[k][:, I:] = acc[k]
-        dbs.append(F_.colsum(dX_tot[k], E1, H) if b is not None else None)
+    dbs = [F_.colsum(dX_tot[k], E1, H) if b is not None else None for k, (_, b) in enumerate(cell.gates)]      # gate biases
     return cell.grads(bufs, acc, dbs) + (dWout, dbout)
 
 
 class AtomRun:
     """One issued atom level: its launch stream, its two result tensors and what is still owed on them -- ``finish`` (the
     worker's join and the read-out behind the step loop, or None) and ``node`` = (args, state, params) of the
-    ``_AtomDecodeCompact`` node where autograd records (None for the forward-only form and for ``_AtomDecode``, whose
-    node is made at launch)."""
+    ``_AtomDecodeCompact`` node where autograd records (None for the forward-only form, which makes no node)."""
 
     def __init__(self, stream, pooled, cand, finish=None, node=None):
         self.stream, self.pooled, self.cand = stream, pooled, cand
@@ -1003,22 +786,15 @@ def atom_decode_launch(plan: AtomPlan, graph_encoder, hnode_a: torch.Tensor, hme
         if not seed:
             seed = torch.randint(0, 2 ** 31 - 1, (2,), dtype=torch.int64)
         drop = (float(wo[2].p), int(seed[0]), int(seed[1]))
-    fn = _AtomDecodeCompact if compact_enabled() else _AtomDecode
-    if fn is _AtomDecode and not plan.full:
-        raise RuntimeError("this AtomPlan was built without the level-wide tables (_dev.ATOM_COMPACT changed after the plan "
-                           "was built?); build it with full=True")
-    args = (plan, "LSTM" if lstm else "GRU", rnn.depth, rnn.hidden_size, graph_encoder.node_fdim, rnn.input_size, fn_all,
+    args =(plan, "LSTM" if lstm else "GRU", rnn.depth, rnn.hidden_size, graph_encoder.node_fdim, rnn.input_size, fn_all,
             hmess_a, drop)
     params = params + (wo[0].weight, wo[0].bias)
     # a call autograd will not record runs the forward-only form, which makes no node: once joined, nothing of it is left
     # in _INFLIGHT for a backward to collect
     infer = not fused.records_grad(params + (fn_all, hmess_a))
     stream = torch.cuda.current_stream(hmess_a.device)
-    if fn is _AtomDecode:
-        pooled, cand = _full_level(*args, params, infer=True)[:2] if infer else fn.apply(*args, *params)
-        return AtomRun(stream, pooled, cand)
     with torch.no_grad():
-        state = fn.launch(*args, params, infer=infer)
+        state = _AtomDecodeCompact.launch(*args, params, infer=infer)
     return AtomRun(stream, state["pooled"], state["cand"], state.pop("finish"), None if infer else (args, state, params))
 
 

@@ -125,7 +125,7 @@ class DecodeSchedule:
     @staticmethod
     def _native_wanted() -> bool:
         from . import schedule_native as SN
-        return bool(SN.enabled() and _dev.DECODER_BATCHED and _dev.ATOM_DECODE and _dev.ATOM_COMPACT)
+        return bool(SN.enabled() and _dev.DECODER_BATCHED and _dev.ATOM_DECODE)
 
     @staticmethod
     def _build_native(tensors, orders, labels, depth, gates) -> "Optional[DecodeSchedule]":

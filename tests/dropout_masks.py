@@ -42,15 +42,11 @@ def encoder_masks(n_tree_nodes, n_graph_nodes, H, p, seed):
     return {k: torch.from_numpy(scaled(dropout_keep(rows(k), H, p, seed[0], seed[1], s), p)) for k, s in ENC_SITES.items()}
 
 
-def atom_row_masks(aoff, H, p, seed, compact):
+def atom_row_masks(aoff, H, p, seed):
     """Per decode step t the [atoms of step t, H] scaled mask of the atom level's W_o rows (row j = st["atoms"][j]):
-    compact form, one call at site 0 over the rows of all steps (step t's rows start at aoff[t]); full form, one call per
-    step at site t over that step's rows."""
-    T = len(aoff) - 1
-    if compact:
-        m = dropout_keep(aoff[-1], H, p, seed[0], seed[1], 0)
-        return [scaled(m[aoff[t]:aoff[t + 1]], p) for t in range(T)]
-    return [scaled(dropout_keep(aoff[t + 1] - aoff[t], H, p, seed[0], seed[1], t), p) for t in range(T)]
+    one call at site 0 over the rows of all steps (step t's rows start at aoff[t])."""
+    m = dropout_keep(aoff[-1], H, p, seed[0], seed[1], 0)
+    return [scaled(m[aoff[t]:aoff[t + 1]], p) for t in range(len(aoff) - 1)]
 
 
 def column_masks(H, p):

@@ -33,10 +33,7 @@ def _set_mode(monkeypatch, mode):
     from ggpm_amd import _dev as dev_settings
     monkeypatch.setattr(dev_settings, "DECODER_BATCHED", mode != "stepwise")
     monkeypatch.setattr(dev_settings, "ATOM_DECODE", mode.startswith("batched"))
-    monkeypatch.setattr(dev_settings, "ATOM_COMPACT", mode != "batched_full")
     monkeypatch.setattr(dev_settings, "ATOM_AHEAD", mode == "batched")
-    if mode == "batched_pyloop":
-        monkeypatch.setattr(dev_settings, "DECODE_DRIVER", False)
     if mode == "batched_opheads":
         monkeypatch.setattr(dev_settings, "HEADS_COMPOSITE", False)
 
@@ -44,7 +41,7 @@ def _set_mode(monkeypatch, mode):
 def _mode_cases():
     names = vae_case_names()
     picked = [next((n for n in names if cell in n), None) for cell in ("gru", "lstm")]
-    others = ["batched_inline", "batched_pyloop", "batched_full", "batched_opheads", "levels", "stepwise"]
+    others = ["batched_inline", "batched_opheads", "levels", "stepwise"]
     return [(n, "batched") for n in names] + [(n, m) for n in picked if n for m in others]
 
 
@@ -77,10 +74,10 @@ def _oracle_params(sd, tie, dtype=torch.float32):
 
 def _oracle_drop(H, sch, tt, gt, mode, counts=None):
     """(encoder masks, decoder drop) of the form ``mode``: the atom level's W_o is the HIP hash in the ATOM_DECODE forms
-    (compact: site 0 over all steps' rows; full: site t per step), the injected module in ``levels`` / ``stepwise``."""
+    (site 0 over all steps' rows), the injected module in ``levels`` / ``stepwise``."""
     atom_rows = None
     if mode.startswith("batched"):
-        atom_rows = dm.atom_row_masks(sch.plan["atom_off"], H, P, ATOM_SEED, compact=(mode != "batched_full"))
+        atom_rows = dm.atom_row_masks(sch.plan["atom_off"], H, P, ATOM_SEED)
     return (dm.encoder_masks(tt[0].shape[0], gt[0].shape[0], H, P, ENC_SEED),
             dm.oracle_drop(H, P, atom_rows, counts))
 

@@ -286,9 +286,7 @@ def _set_form(monkeypatch, mode="batched", side="1", defer_early=True, defer_wgr
     from ggpm_amd import _dev as dev_settings
     monkeypatch.setattr(dev_settings, "DECODER_BATCHED", mode != "stepwise")
     monkeypatch.setattr(dev_settings, "ATOM_DECODE", mode.startswith("batched"))
-    monkeypatch.setattr(dev_settings, "ATOM_COMPACT", mode != "batched_full")
     monkeypatch.setattr(dev_settings, "ATOM_AHEAD", mode == "batched")
-    monkeypatch.setattr(dev_settings, "DECODE_DRIVER", mode != "batched_pyloop")
     monkeypatch.setattr(dev_settings, "DEFER_EARLY", defer_early)
     monkeypatch.setenv("GGPM_SIDE_STREAM", side)
     monkeypatch.setenv("GGPM_DEFER_WGRADS", defer_wgrads)
@@ -395,7 +393,7 @@ def test_vae_step_adds_into_existing_grad(name, start, monkeypatch):
 def _form_cases():
     out = []
     for name in ("vae_gru_s40", "vae_lstm_s41"):
-        for mode in ("batched_inline", "batched_pyloop", "levels", "stepwise"):
+        for mode in ("batched_inline", "levels", "stepwise"):
             for side in ("1", "0"):
                 out.append(pytest.param(name, mode, side, True, "1", id="%s-%s-side%s" % (name, mode, side)))
         out.append(pytest.param(name, "batched", "1", False, "1", id="%s-no_early_flush" % name))

@@ -1355,7 +1355,7 @@ def _vae_mode_cases():
     GRU and the first LSTM fixture."""
     names = _vae_names()
     picked = [next((n for n in names if cell in n), None) for cell in ("gru", "lstm")]
-    others = ["batched_inline", "batched_pyloop", "batched_full", "batched_opheads", "levels", "stepwise"]
+    others = ["batched_inline", "batched_opheads", "levels", "stepwise"]
     return [(n, "batched") for n in names] + [(n, m) for n in picked if n for m in others]
 
 
@@ -1368,16 +1368,11 @@ def test_vae_step_matches_reference_golden(name, mode, monkeypatch):
     loop, three incremental-encoder calls per step), ``levels`` (the attachment and motif levels as ONE level call each
     over the decode-time DAG of their messages, the atom level stepping through the incremental encoder) and ``batched``
     (default: additionally the atom level's step loop as one autograd node on host-built index tables, atom_decode.py,
-    issued on its own stream ahead of the encoder; ``batched_inline`` keeps it in program order, ``batched_pyloop``
-    additionally issues the step loops from Python instead of through ggpm_decode_steps_*, ``batched_full`` runs
-    its steps over all rows of the level instead of compact row sets)."""
+    issued on its own stream ahead of the encoder; ``batched_inline`` keeps it in program order)."""
     from ggpm_amd import _dev as dev_settings
     monkeypatch.setattr(dev_settings, "DECODER_BATCHED", mode != "stepwise")
     monkeypatch.setattr(dev_settings, "ATOM_DECODE", mode.startswith("batched"))
-    monkeypatch.setattr(dev_settings, "ATOM_COMPACT", mode != "batched_full")     # compact row sets per decode step
     monkeypatch.setattr(dev_settings, "ATOM_AHEAD", mode == "batched")
-    if mode == "batched_pyloop":        # the decode step loops issued from Python instead of csrc/decode.hip
-        monkeypatch.setattr(dev_settings, "DECODE_DRIVER", False)
     if mode == "batched_opheads":       # the score heads op by op (~30 autograd nodes) instead of heads_fused's one node
         monkeypatch.setattr(dev_settings, "HEADS_COMPOSITE", False)
     from golden_utils import vae_model

@@ -96,10 +96,8 @@ def test_hier_prop_opt_cases_cover_loss_scaling_on_and_off():
     assert {pf.PropOptGolden(n).scaling for n in pf.names("propopt")} == {False, True}
 
 
-# the decoder's other forms (ggpm_amd/_dev.py): full-level atom level, step loops issued from Python, no worker thread,
-# tree-side levels as the Python composite
-FORMS = {"full_level": dict(ATOM_COMPACT=False, ATOM_AHEAD=False), "python_loop": dict(DECODE_DRIVER=False),
-         "no_worker": dict(ATOM_ASYNC=False), "tree_composite": dict(TREE_DRIVER=False)}
+# the decoder's other forms (ggpm_amd/_dev.py): no worker thread, tree-side levels as the Python composite
+FORMS = {"no_worker": dict(ATOM_ASYNC=False), "tree_composite": dict(TREE_DRIVER=False)}
 
 
 @pytest.mark.parametrize("form", sorted(FORMS))

@@ -100,17 +100,14 @@ def test_compact_row_base_maps_to_the_oracle_atom_order(name):
 
 
 def test_row_masks_of_the_two_forms_are_the_hash_at_their_sites():
-    """atom_row_masks against ggpm_dropout's counter layout: compact = one call at site 0 (row aoff[t] + j), full = one
-    call per step at site t (row j); the two forms' masks differ, each keeps about 1 - p."""
+    """atom_row_masks against ggpm_dropout's counter layout: one call at site 0 over the rows of all steps (step t's row j is
+    row aoff[t] + j), keeping about 1 - p.  (The name dates from when a full-level form drew one call per step at site t.)"""
     from dropout_masks import atom_row_masks
     from golden_utils import dropout_keep
     aoff, H, p, seed = [0, 5, 5, 12, 40], 16, 0.1, (11, 22)
-    c = atom_row_masks(aoff, H, p, seed, compact=True)
-    f = atom_row_masks(aoff, H, p, seed, compact=False)
+    c = atom_row_masks(aoff, H, p, seed)
     whole = dropout_keep(40, H, p, 11, 22, 0)
     for t in range(4):
-        assert c[t].shape == f[t].shape == (aoff[t + 1] - aoff[t], H)
+        assert c[t].shape == (aoff[t + 1] - aoff[t], H)
         assert np.array_equal(c[t] > 0, whole[aoff[t]:aoff[t + 1]])
-        assert np.array_equal(f[t] > 0, dropout_keep(aoff[t + 1] - aoff[t], H, p, 11, 22, t))
-    assert not np.array_equal(np.concatenate(c), np.concatenate(f))
     assert abs(float((np.concatenate(c) > 0).mean()) - (1 - p)) < 0.05

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py with development settings changed first (ggpm_amd/_dev.py): python tools/bench_dev.py NAME=VALUE [...] -- <bench.py arguments>
 
-    python tools/bench_dev.py DECODE_TABLES=False -- --only-vae
+    python tools/bench_dev.py ATOM_AHEAD=False -- --only-vae
 """
 import ast
 import os
