@@ -38,7 +38,7 @@ def _np(t):
 
 def _posterior(model, batch):
     from ggpm_amd.nnutils import make_cuda
-    from ggpm_amd.property_vae import _latent_heads
+    from ggpm_amd.latent_heads import _latent_heads
     with torch.no_grad():
         root = model._encode(make_cuda(batch[2]))
         mean, pv = _latent_heads(root, model.R_mean.weight, model.R_mean.bias, model.R_var.weight, model.R_var.bias)
@@ -113,7 +113,7 @@ def _weights(g, weighted):
 @pytest.mark.parametrize("case,kind", THREE)
 def test_equal_weights_against_the_composite_of_existing_pieces(case, kind):
     from ggpm_amd.nnutils import make_cuda
-    from ggpm_amd.property_vae import _LatentTerms
+    from ggpm_amd.latent_heads import _LatentTerms
     g, model, batch, sch = _case(case, kind)
     K = 2
     w = _weights(g, True)

@@ -73,7 +73,7 @@ def _weights(g, weighted):
 def _posterior(model, batch, grad=False):
     """(mean, pre_var) [B, L] of the batch as the model's own launches form them"""
     from ggpm_amd.nnutils import make_cuda
-    from ggpm_amd.property_vae import _latent_heads
+    from ggpm_amd.latent_heads import _latent_heads
     with torch.set_grad_enabled(grad):
         root = model._encode(make_cuda(batch[2]))
         if not grad:
