@@ -169,12 +169,8 @@ __device__ __forceinline__ void ggpm_lds_barrier() {
 // true when `count` products of this shape are better issued as ONE unsplit grouped launch (small output, K short enough
 // for the in-workgroup K split) than as separate split-K launches
 bool ggpm_gemm_prefers_grouped(int M, int N, int K, int count);
-// `count` (<= 4) tall contractions C_i = A_i^T B_i of one output shape (K_i may differ) in one launch + one reduce;
-// falls back to sequential ggpm_gemm calls when a member does not qualify for the tall kernel
-// bf16 == 1: operands rounded to bf16 (RNE) on their way into LDS, fp32 accumulate (gemm_tn_tall_bf16); bf16 == 2: the
-// operands ARE bf16 in memory (lda / ldb in elements; the group must qualify for the tall kernel: GGPM_ERR_UNSUPPORTED if not)
-int ggpm_gemm_tall_grouped(int M, int N, int count, const ggpm_gemm_problem* p, const int* K, float* ws, size_t ws_bytes,
-                           ggpm_stream_t stream, int bf16 = 0);
+// (the level weight gradients' products -- ggpm_gemm_tn_tall_grouped, ggpm_gemm_tn_pair_grouped_c, ggpm_colsum_dtype -- are
+// declared in include/ggpm_hip.h)
 #define GGPM_GEMM_MAX_GROUP 4          // members of ggpm_gemm_grouped / segments of ggpm_gemm_ksegments
 typedef ggpm_gemm_problem GgpmGemmProblem;
 
@@ -207,13 +203,10 @@ int ggpm_sum_slots_any(const float* src, int slots, size_t slot_floats, float* o
 // Fixed-point levels (ggpm_level_opts.fixed_slot).  ggpm_sum_slots_pair_grouped: hi[i] + lo[i] = sum_t src[t][i] over `slots`
 // fp32 slots, the sum kept as an unevaluated pair -- hi the running fp32 sum, lo the sum of its rounding errors (two-sum per
 // term, fixed order); up to 4 arrays of one slot size in one launch; hi / lo may be slots of the same array below the ones read.
-// ggpm_gemm_tn_pair_grouped: C_i = [hi_i; lo_i]^T [B_i; B_i] for up to GGPM_GEMM_MAX_GROUP such pairs (operands [rows, ld],
-// C_i [M, ldc] overwritten) in one launch.
+// ggpm_gemm_tn_pair_grouped_c (include/ggpm_hip.h) then forms C_i = [hi_i; lo_i]^T [B_i; B_i] for up to GGPM_GEMM_MAX_GROUP
+// such pairs (operands [rows, ld], C_i [M, ldc] overwritten) in one launch.
 int ggpm_sum_slots_pair_grouped(int count, const float* const* src, const int* slots, size_t slot_floats, float* const* hi,
                                 float* const* lo, ggpm_stream_t stream);
-int ggpm_gemm_tn_pair_grouped(int M, int N, int rows, int ld, int count, const ggpm_pair_problem* p, ggpm_stream_t stream);
-// column sums of a [rows, ld] fp32 or bf16 matrix (losses.hip / gemm.hip: ggpm_colsum is the fp32 entry point)
-int ggpm_colsum_any(const float* A, int lda, int rows, int cols, float* out, float* scratch, bool a_bf16, ggpm_stream_t stream);
 
 // Optional per-launch timing (bench.py roofline): implemented in capi.hip.
 void ggpm_timing_tag(int tag);       // 1 atom, 2 attachment, 3 motif level, 0 untagged; collected as which + 8 * tag

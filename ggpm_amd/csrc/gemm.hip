@@ -1087,14 +1087,6 @@ __global__ void __launch_bounds__(512, 1) gemm_tn_tall_split(GemmGroupArgs gg, i
 #pragma unroll
         for (int j = 0; j < 5; ++j) slab[(i * 5 + j) * 64] = acc[i][j];
 }
-constexpr size_t GGPM_TALL_SPLIT_LDS = (size_t)2 * 3 * BTK * BLD * sizeof(__bf16);
-// 0: fp32 MFMA for the fp32 tall contractions (the round-1 kernel); 1 (default): split operands on the bf16 pipe
-inline int tall_split_mode() { static const int v = [] { const char* e = ggpm_dev_env("GGPM_TALL_SPLIT"); return e ? atoi(e) : 1; }(); return v; }
-inline int tall_split_wgs() { static const int v = [] { const char* e = ggpm_dev_env("GGPM_TALL_SPLIT_WGS"); return e ? atoi(e) : 256; }(); return v; }
-inline void launch_tall_split(const GemmGroupArgs& gg, dim3 grid, int splits, hipStream_t s) {
-    ggpm_set_lds(gemm_tn_tall_split, GGPM_TALL_SPLIT_LDS);
-    gemm_tn_tall_split<<<grid, 512, GGPM_TALL_SPLIT_LDS, s>>>(gg, splits);
-}
 
 // Sums the fragment-order slabs of gemm_tn_tall over the K chunks (fixed order: four interleaved partial sums per
 // workgroup, combined as (0+1)+(2+3)) and writes C.  One workgroup per (tile, wave, 16 x 16 block).
@@ -1132,25 +1124,6 @@ __global__ void __launch_bounds__(256) tall_reduce(GemmGroupArgs gg, int splits,
     }
 }
 
-// The tall kernel pays when the 160 x 160 tiles cover the output without much padding and K is long.
-inline bool tall_shape(int M, int N, int K) {
-    if (K < 6144 || M < 64 || N < 64) return false;     // measured: 300 x 300 x 2843 is faster on the 64 x 64 kernel
-    const double cover = (double)ggpm_round_up(M, TM) * ggpm_round_up(N, TN);
-    return (double)M * N >= 0.8 * cover;
-}
-inline size_t tall_slab_bytes(int M, int N) {
-    return (size_t)ggpm_ceil_div(M, TM) * ggpm_ceil_div(N, TN) * 4 * 25 * 64 * sizeof(f32x4);
-}
-constexpr int GGPM_TALL_BF16_WGS = 768;      // workgroups of a bf16 tall launch (three per CU: it lives on overlapped loads)
-inline int tall_splits(int M, int N, int K, int target_wgs = 0) {
-    static const int target_env = [] { const char* e = ggpm_dev_env("GGPM_GEMM_TALL_WGS"); return e ? atoi(e) : 256; }();
-    const int target = target_wgs > 0 ? target_wgs : target_env;
-    const int tiles = ggpm_ceil_div(M, TM) * ggpm_ceil_div(N, TN);
-    int s = target / tiles, maxs = K / (8 * TK);
-    if (s > maxs) s = maxs;
-    return s < 1 ? 1 : s;
-}
-
 __global__ void splitk_reduce(GemmArgs g, int splits) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     const int m = blockIdx.y;
@@ -1164,16 +1137,6 @@ __global__ void splitk_reduce(GemmArgs g, int splits) {
     v = apply_act(v, g.act);
     if (g.zero_row0 && m == 0) v = 0.f;
     *dst = v;
-}
-
-// choose the split: enough workgroups to cover the chip a few times over, chunks of >= 256 k.
-inline int choose_splits(int M, int N, int K) {
-    const int tiles = ggpm_ceil_div(M, BM) * ggpm_ceil_div(N, BN);
-    if (K < 2048 || tiles >= 512) return 1;
-    int want = ggpm_ceil_div(1024, tiles);
-    int maxs = K / 256;
-    int s = want < maxs ? want : maxs;
-    return s < 1 ? 1 : s;
 }
 
 constexpr int CS_ROWS = 256;   // max row chunks of the column-sum first stage (workspace = 256*N floats)
@@ -1247,19 +1210,50 @@ __global__ void act_backward_k(const float* __restrict__ dy, const float* __rest
 
 }  // namespace
 
+// ---- host policy: shape predicates, split choosers, dev switches, LDS sizes ------------------------------------------
 namespace {
+// dev switches (read in the dev variant only, common.h): one reader each
+inline int gemm_use_tall() { static const int v = [] { const char* e = ggpm_dev_env("GGPM_GEMM_TALL"); return e ? atoi(e) : 1; }(); return v; }
+inline int gemm_use_v2() { static const int v = [] { const char* e = ggpm_dev_env("GGPM_GEMM_V2"); return e ? atoi(e) : 1; }(); return v; }
+// 0: fp32 MFMA for the fp32 tall contractions (the round-1 kernel); 1 (default): split operands on the bf16 pipe
+inline int tall_split_mode() { static const int v = [] { const char* e = ggpm_dev_env("GGPM_TALL_SPLIT"); return e ? atoi(e) : 1; }(); return v; }
+inline int tall_split_wgs() { static const int v = [] { const char* e = ggpm_dev_env("GGPM_TALL_SPLIT_WGS"); return e ? atoi(e) : 256; }(); return v; }
+
+// The tall kernel pays when the 160 x 160 tiles cover the output without much padding and K is long.
+inline bool tall_shape(int M, int N, int K) {
+    if (K < 6144 || M < 64 || N < 64) return false;     // measured: 300 x 300 x 2843 is faster on the 64 x 64 kernel
+    const double cover = (double)ggpm_round_up(M, TM) * ggpm_round_up(N, TN);
+    return (double)M * N >= 0.8 * cover;
+}
+inline size_t tall_slab_bytes(int M, int N) {
+    return (size_t)ggpm_ceil_div(M, TM) * ggpm_ceil_div(N, TN) * 4 * 25 * 64 * sizeof(f32x4);
+}
+constexpr int GGPM_TALL_BF16_WGS = 768;      // workgroups of a bf16 tall launch (three per CU: it lives on overlapped loads)
+inline int tall_splits(int M, int N, int K, int target_wgs = 0) {
+    static const int target_env = [] { const char* e = ggpm_dev_env("GGPM_GEMM_TALL_WGS"); return e ? atoi(e) : 256; }();
+    const int target = target_wgs > 0 ? target_wgs : target_env;
+    const int tiles = ggpm_ceil_div(M, TM) * ggpm_ceil_div(N, TN);
+    int s = target / tiles, maxs = K / (8 * TK);
+    if (s > maxs) s = maxs;
+    return s < 1 ? 1 : s;
+}
+
+// choose the split: enough workgroups to cover the chip a few times over, chunks of >= 256 k.
+inline int choose_splits(int M, int N, int K) {
+    const int tiles = ggpm_ceil_div(M, BM) * ggpm_ceil_div(N, BN);
+    if (K < 2048 || tiles >= 512) return 1;
+    int want = ggpm_ceil_div(1024, tiles);
+    int maxs = K / 256;
+    int s = want < maxs ? want : maxs;
+    return s < 1 ? 1 : s;
+}
+
 // gemm_small_v3 when the 64 x 64 kernels would launch about one workgroup per CU or fewer (swept: 128 / 300 / 1024
 // tiles -> 4.51 / 4.49 / 4.53 ms per GRU step)
 inline bool small_launch(int M, int N, int count) {
     static const int use_v3 = [] { const char* e = ggpm_dev_env("GGPM_GEMM_V3"); return e ? atoi(e) : 1; }();
     static const int max_tiles = [] { const char* e = ggpm_dev_env("GGPM_GEMM_V3_TILES"); return e ? atoi(e) : 300; }();
     return use_v3 && (size_t)ggpm_ceil_div(M, BM) * ggpm_ceil_div(N, BN) * count <= (size_t)max_tiles;
-}
-inline void launch_small(int trans_a, int trans_b, const GemmGroupArgs& gg, dim3 grid, int splits, hipStream_t s) {
-    if (!trans_a && !trans_b) gemm_small_v3<false, false><<<grid, 256, 0, s>>>(gg, splits);
-    else if (!trans_a && trans_b) gemm_small_v3<false, true><<<grid, 256, 0, s>>>(gg, splits);
-    else if (trans_a && !trans_b) gemm_small_v3<true, false><<<grid, 256, 0, s>>>(gg, splits);
-    else gemm_small_v3<true, true><<<grid, 256, 0, s>>>(gg, splits);
 }
 // K chunks of a grouped small launch whose few 32 x 32 tiles would each walk a long K alone (the input halves of a level's
 // gate weight gradients: 60 tiles x 2848 rows = 45 dependent k-steps, 177 us at the very end of the step): enough chunks
@@ -1272,16 +1266,7 @@ inline int small_splits(int M, int N, int K, int count, int* k_chunk) {
     *k_chunk = ggpm_round_up(ggpm_ceil_div(K, sp), SK);
     return ggpm_ceil_div(K, *k_chunk);
 }
-}  // namespace
 
-// ---- which kernel a call runs on --------------------------------------------------------------------------------------
-// Every dispatch decision of this file as a function of what ggpm_gemm_call (include/ggpm_hip.h) describes: shapes, leading
-// dimensions, the low four bits of each operand's address, the workspace passed.  The entry points below build such a
-// description from their arguments, call the plan_* function and launch what it says; ggpm_gemm_form_query calls the same
-// functions and launches nothing.
-namespace {
-inline int gemm_use_tall() { static const int v = [] { const char* e = ggpm_dev_env("GGPM_GEMM_TALL"); return e ? atoi(e) : 1; }(); return v; }
-inline int gemm_use_v2() { static const int v = [] { const char* e = ggpm_dev_env("GGPM_GEMM_V2"); return e ? atoi(e) : 1; }(); return v; }
 inline int low4(const void* p) { return (int)((uintptr_t)p & 15); }
 inline bool vec_legal(int ld, int base) { return (ld & 3) == 0 && (base & 15) == 0; }      // 16-byte loads of every row
 inline bool fits_buffer(size_t rows, int ld, size_t es = 4) { return rows * ld * es < 0xffffff00ull; }   // 32-bit buffer offsets
@@ -1292,57 +1277,82 @@ constexpr int TALL_K_OVERSHOOT = 3 * BTK;
 inline bool v2_operands_ok(int lda, int base_a, size_t rows_a, int ldb, int base_b, size_t rows_b) {
     return gemm_use_v2() && vec_legal(lda, base_a) && vec_legal(ldb, base_b) && fits_buffer(rows_a, lda) && fits_buffer(rows_b, ldb);
 }
-inline void small_grid(int n_pad_max, int M, int count, int splits, int* grid) {
-    grid[0] = ggpm_ceil_div(n_pad_max, SN); grid[1] = ggpm_ceil_div(M, SM); grid[2] = count * splits;
-}
 constexpr size_t LDS_SCALAR = 2 * BK * LDT * sizeof(float), LDS_V2 = 4 * BK2 * LDT * sizeof(float),
                  LDS_SMALL = 4 * SK * SLD * sizeof(float), LDS_TALL = 4 * TK * TLD * sizeof(float),
-                 LDS_TALL_BF16 = 2 * BTK * BLD * sizeof(__bf16);
+                 LDS_TALL_BF16 = 2 * BTK * BLD * sizeof(__bf16), LDS_TALL_SPLIT = (size_t)2 * 3 * BTK * BLD * sizeof(__bf16);
 
+// ---- which kernel a call runs on --------------------------------------------------------------------------------------
+// Every dispatch decision of this file as a function of what ggpm_gemm_call (include/ggpm_hip.h) describes: shapes, leading
+// dimensions, the low four bits of each operand's address, the workspace passed.  A plan holds everything a launch needs;
+// the entry points below build such a description from their arguments, call their plan_* function, fill the kernel
+// arguments from the plan (fill_group) and launch what it says (run_plan).  ggpm_gemm_form_query calls the same functions
+// and launches nothing.  Shape, n_pad, group-size and alignment checks are made here and nowhere else.
 struct GemmPlan {
     int rc = GGPM_OK, kernel = GGPM_GEMM_KERNEL_NONE, vec_a = 0, vec_b = 0, reduce = GGPM_GEMM_REDUCE_NONE, splits = 1;
-    int k_chunk[GGPM_GEMM_MAX_GROUP] = {0, 0, 0, 0};
+    int k_chunk[GGPM_GEMM_MAX_GROUP] = {0, 0, 0, 0};      // per member; a plan over one K states it once, in k_chunk[0]
     int grid[3] = {0, 0, 0};
     size_t lds = 0, ws_used = 0;
+    // beyond what ggpm_gemm_form reports:
+    int block = 256;                     // workgroup size of the product kernel
+    int reduce_grid[3] = {0, 0, 0};      // grid of the reduce launch (256 threads)
+    size_t ws_stride = 0;                // floats from one member's slabs in the workspace to the next member's
+    int stopped_at = GGPM_GEMM_MAX_GROUP;      // a refusal made while walking the members: the member it was made at
 };
-inline GemmPlan plan_refuse(int rc) { GemmPlan pl; pl.rc = rc; return pl; }
+inline GemmPlan plan_refuse(int rc, int member = GGPM_GEMM_MAX_GROUP) { GemmPlan pl; pl.rc = rc; pl.stopped_at = member; return pl; }
+inline bool group_size_ok(int count) { return count > 0 && count <= GGPM_GEMM_MAX_GROUP; }
+inline void plan_tiles_64(GemmPlan& pl, int kernel, size_t lds, int n_cols, int M, int z) {
+    pl.kernel = kernel; pl.lds = lds;
+    pl.grid[0] = ggpm_ceil_div(n_cols, BN); pl.grid[1] = ggpm_ceil_div(M, BM); pl.grid[2] = z;
+}
 inline void plan_small(GemmPlan& pl, int n_pad_max, int M, int count, int splits) {
     pl.kernel = GGPM_GEMM_KERNEL_SMALL_V3; pl.lds = LDS_SMALL; pl.splits = splits;
-    small_grid(n_pad_max, M, count, splits, pl.grid);
+    pl.grid[0] = ggpm_ceil_div(n_pad_max, SN); pl.grid[1] = ggpm_ceil_div(M, SM); pl.grid[2] = count * splits;
+}
+// a tall kernel over `count` members of pl.splits chunks each (grid.x / .y: the 160 x 160 tiles)
+inline void plan_tall(GemmPlan& pl, int kernel, int M, int N, int count) {
+    pl.kernel = kernel;
+    pl.lds = kernel == GGPM_GEMM_KERNEL_TALL ? LDS_TALL : kernel == GGPM_GEMM_KERNEL_TALL_SPLIT ? LDS_TALL_SPLIT : LDS_TALL_BF16;
+    pl.block = kernel == GGPM_GEMM_KERNEL_TALL_SPLIT ? 512 : 256;
+    pl.grid[0] = ggpm_ceil_div(N, TN); pl.grid[1] = ggpm_ceil_div(M, TM); pl.grid[2] = pl.splits * count;
+}
+// ... through fragment-order slabs: member i's start at ws + i * splits * slab, one tall_reduce launch sums them all
+inline void plan_tall_reduce(GemmPlan& pl, int M, int N, int count) {
+    const size_t slab = tall_slab_bytes(M, N);
+    pl.reduce = GGPM_GEMM_REDUCE_TALL;
+    pl.reduce_grid[0] = pl.grid[0] * pl.grid[1] * 100; pl.reduce_grid[1] = count; pl.reduce_grid[2] = 1;
+    pl.ws_stride = pl.splits * (slab / sizeof(float));
+    pl.ws_used = (size_t)count * pl.splits * slab;
+}
+// row-major slabs [splits][M][N] per member, summed by splitk_reduce (one member) / splitk_reduce_group
+inline void plan_splitk_reduce(GemmPlan& pl, int reduce, int M, int N, int n_pad_max, int count) {
+    pl.reduce = reduce;
+    pl.reduce_grid[0] = ggpm_ceil_div(n_pad_max, 256); pl.reduce_grid[1] = M; pl.reduce_grid[2] = count;
+    pl.ws_stride = (size_t)pl.splits * M * N;
+    pl.ws_used = count * pl.ws_stride * sizeof(float);
 }
 
-// ggpm_gemm
-inline GemmPlan plan_gemm(int trans_a, int trans_b, int M, int N, int K, int lda, int base_a, int ldb, int base_b, int ldc,
-                          int n_pad, bool has_ws, size_t ws_bytes) {
-    if (M <= 0 || N <= 0 || K <= 0 || n_pad < N || n_pad > ldc) return plan_refuse(GGPM_ERR_ARG);
+// ggpm_gemm (member 0 of the call)
+inline GemmPlan plan_gemm(const ggpm_gemm_call& c) {
+    const int trans_a = c.trans_a, trans_b = c.trans_b, M = c.M, N = c.N, K = c.K[0], lda = c.lda[0], ldb = c.ldb[0], n_pad = c.n_pad[0];
+    const bool has_ws = c.has_ws != 0;
+    const size_t ws_bytes = c.ws_bytes;
+    if (M <= 0 || N <= 0 || K <= 0 || n_pad < N || n_pad > c.ldc[0]) return plan_refuse(GGPM_ERR_ARG);
     GemmPlan pl;
-    const bool vecA = vec_legal(lda, base_a), vecB = vec_legal(ldb, base_b);
+    const bool vecA = vec_legal(lda, c.base_a[0]), vecB = vec_legal(ldb, c.base_b[0]);
     pl.vec_a = vecA; pl.vec_b = vecB;
     if (gemm_use_tall() && trans_a && !trans_b && vecA && vecB && lda >= ggpm_round_up(M, 4) && ldb >= ggpm_round_up(N, 4) &&
         tall_shape(M, N, K) && n_pad <= ggpm_round_up(N, TN) && fits_buffer(K + TALL_K_OVERSHOOT, lda) && fits_buffer(K + TALL_K_OVERSHOOT, ldb)) {
         const size_t slab = tall_slab_bytes(M, N);
-        pl.grid[0] = ggpm_ceil_div(N, TN); pl.grid[1] = ggpm_ceil_div(M, TM);
-        if (tall_split_mode() && has_ws && ws_bytes >= slab) {
-            // split operands on the bf16 pipe (fp32 accuracy, operand-stream bound): always through slabs + tall_reduce
-            // (which applies bias / accumulate / activation)
-            int sp = tall_splits(M, N, K, tall_split_wgs());
-            if ((size_t)sp * slab > ws_bytes) sp = (int)(ws_bytes / slab);
-            if (sp < 1) sp = 1;
-            pl.k_chunk[0] = ggpm_round_up(ggpm_ceil_div(K, sp), BTK);
-            pl.splits = ggpm_ceil_div(K, pl.k_chunk[0]);
-            pl.kernel = GGPM_GEMM_KERNEL_TALL_SPLIT; pl.lds = GGPM_TALL_SPLIT_LDS;
-            pl.reduce = GGPM_GEMM_REDUCE_TALL; pl.ws_used = pl.splits * slab;
-            pl.grid[2] = pl.splits;
-            return pl;
-        }
-        int splits = has_ws ? tall_splits(M, N, K) : 1;
-        if (splits > 1 && (size_t)splits * slab > ws_bytes) splits = (int)(ws_bytes / slab);
+        // split operands on the bf16 pipe (fp32 accuracy, operand-stream bound): always through slabs + tall_reduce
+        // (which applies bias / accumulate / activation)
+        const bool split = tall_split_mode() && has_ws && ws_bytes >= slab;
+        int splits = split ? tall_splits(M, N, K, tall_split_wgs()) : has_ws ? tall_splits(M, N, K) : 1;
+        if ((split || splits > 1) && (size_t)splits * slab > ws_bytes) splits = (int)(ws_bytes / slab);
         if (splits < 1) splits = 1;
-        pl.k_chunk[0] = ggpm_round_up(ggpm_ceil_div(K, splits), TK);
+        pl.k_chunk[0] = ggpm_round_up(ggpm_ceil_div(K, splits), split ? BTK : TK);
         pl.splits = ggpm_ceil_div(K, pl.k_chunk[0]);
-        pl.kernel = GGPM_GEMM_KERNEL_TALL; pl.lds = LDS_TALL;
-        if (pl.splits > 1) { pl.reduce = GGPM_GEMM_REDUCE_TALL; pl.ws_used = pl.splits * slab; }
-        pl.grid[2] = pl.splits;
+        plan_tall(pl, split ? GGPM_GEMM_KERNEL_TALL_SPLIT : GGPM_GEMM_KERNEL_TALL, M, N, 1);
+        if (split || pl.splits > 1) plan_tall_reduce(pl, M, N, 1);
         return pl;
     }
     int splits = 1;
@@ -1357,25 +1367,24 @@ inline GemmPlan plan_gemm(int trans_a, int trans_b, int M, int N, int K, int lda
     if (splits <= 1) { splits = 1; pl.k_chunk[0] = ggpm_round_up(K, BK); }
     pl.splits = splits;
     const size_t rows_a = trans_a ? K : M, rows_b = trans_b ? N : K;
-    const bool v2ok = v2_operands_ok(lda, base_a, rows_a, ldb, base_b, rows_b);
+    const bool v2ok = v2_operands_ok(lda, c.base_a[0], rows_a, ldb, c.base_b[0], rows_b);
     if (splits == 1 && small_launch(M, N, 1) && v2ok) {
         plan_small(pl, n_pad, M, 1, 1);
         return pl;
     }
-    pl.grid[0] = ggpm_ceil_div(splits > 1 ? N : n_pad, BN); pl.grid[1] = ggpm_ceil_div(M, BM); pl.grid[2] = splits;
+    plan_tiles_64(pl, GGPM_GEMM_KERNEL_SCALAR, LDS_SCALAR, splits > 1 ? N : n_pad, M, splits);
     // v2 keeps 70 KB of LDS per workgroup (two resident per CU): it wins while the whole grid is resident at once
     // (latency-bound launches: 573 x 600 x 912 35 -> 25 us) and loses beyond (2843 x 912 x 340: 33 -> 37 us)
     const bool resident = (size_t)pl.grid[0] * pl.grid[1] * pl.grid[2] <= 512 || gemm_use_v2() == 2;
     if (resident && v2ok) { pl.kernel = GGPM_GEMM_KERNEL_V2; pl.lds = LDS_V2; }
-    else { pl.kernel = GGPM_GEMM_KERNEL_SCALAR; pl.lds = LDS_SCALAR; }
-    if (splits > 1) { pl.reduce = GGPM_GEMM_REDUCE_SPLITK; pl.ws_used = (size_t)splits * M * N * sizeof(float); }
+    if (splits > 1) plan_splitk_reduce(pl, GGPM_GEMM_REDUCE_SPLITK, M, N, n_pad, 1);
     return pl;
 }
 
-// ggpm_gemm_tall_grouped (c.mode: its bf16 argument; c.K, lda, ldb, ldc, n_pad, base_a, base_b per member)
+// ggpm_gemm_tn_tall_grouped (c.mode: its mode argument; c.K, lda, ldb, ldc, n_pad, base_a, base_b per member)
 inline GemmPlan plan_tall_group(const ggpm_gemm_call& c) {
     const int M = c.M, N = c.N, count = c.count, bf16 = c.mode;
-    if (count <= 0 || count > GGPM_GEMM_MAX_GROUP || M <= 0 || N <= 0) return plan_refuse(GGPM_ERR_ARG);
+    if (!group_size_ok(count) || M <= 0 || N <= 0) return plan_refuse(GGPM_ERR_ARG);
     GemmPlan pl;
     const size_t slab = tall_slab_bytes(M, N);
     // (bf16 operands exist in the tall kernel only: a group that does not qualify falls back to fp32 products, which is
@@ -1398,26 +1407,28 @@ inline GemmPlan plan_tall_group(const ggpm_gemm_call& c) {
         pl.kernel = GGPM_GEMM_KERNEL_SEQUENCE;
         return pl;
     }
-    // one launch: the K chunks of all members share the grid (same number of chunks, chunk length per member), the
-    // slabs of member i start at ws + i * splits * slab, one reduce launch sums them all
+    // one launch: the K chunks of all members share the grid (same number of chunks, chunk length per member)
     pl.vec_a = pl.vec_b = (1 << count) - 1;
     pl.splits = splits;
     for (int i = 0; i < count; ++i) pl.k_chunk[i] = ggpm_round_up(ggpm_ceil_div(c.K[i], splits), (bf16 || split) ? BTK : TK);
-    pl.grid[0] = ggpm_ceil_div(N, TN); pl.grid[1] = ggpm_ceil_div(M, TM); pl.grid[2] = splits * count;
-    if (in16) { pl.kernel = GGPM_GEMM_KERNEL_TALL_BF16_IN16; pl.lds = LDS_TALL_BF16; }
-    else if (bf16) { pl.kernel = GGPM_GEMM_KERNEL_TALL_BF16; pl.lds = LDS_TALL_BF16; }
-    else if (split) { pl.kernel = GGPM_GEMM_KERNEL_TALL_SPLIT; pl.lds = GGPM_TALL_SPLIT_LDS; }
-    else { pl.kernel = GGPM_GEMM_KERNEL_TALL; pl.lds = LDS_TALL; }
-    pl.reduce = GGPM_GEMM_REDUCE_TALL;
-    pl.ws_used = (size_t)count * splits * slab;
+    plan_tall(pl, in16 ? GGPM_GEMM_KERNEL_TALL_BF16_IN16 : bf16 ? GGPM_GEMM_KERNEL_TALL_BF16 :
+                  split ? GGPM_GEMM_KERNEL_TALL_SPLIT : GGPM_GEMM_KERNEL_TALL, M, N, count);
+    plan_tall_reduce(pl, M, N, count);
     return pl;
 }
 
-// ggpm_gemm_tn_pair_grouped (c.K[0]: rows, c.lda[0]: ld, base_a: hi, base_lo: lo, base_b: B)
+// ggpm_gemm_tn_bf16: one member, n_pad = N, operands rounded to bf16
+inline GemmPlan plan_tn_bf16(const ggpm_gemm_call& c) {
+    if (!c.has_ws || c.M <= 0 || c.N <= 0 || c.K[0] <= 0 || c.ldc[0] < c.N) return plan_refuse(GGPM_ERR_ARG);
+    ggpm_gemm_call t = c;
+    t.count = 1; t.mode = 1; t.n_pad[0] = c.N;
+    return plan_tall_group(t);
+}
+
+// ggpm_gemm_tn_pair_grouped_c (c.K[0]: rows, c.lda[0]: ld, base_a: hi, base_lo: lo, base_b: B)
 inline GemmPlan plan_pairs(const ggpm_gemm_call& c) {
     const int rows = c.K[0], ld = c.lda[0];
-    if (c.count <= 0 || c.count > GGPM_GEMM_MAX_GROUP || c.M <= 0 || c.N <= 0 || rows <= 0 || ld < c.M || ld < c.N)
-        return plan_refuse(GGPM_ERR_ARG);
+    if (!group_size_ok(c.count) || c.M <= 0 || c.N <= 0 || rows <= 0 || ld < c.M || ld < c.N) return plan_refuse(GGPM_ERR_ARG);
     GemmPlan pl;
     bool ok = small_launch(c.M, c.N, c.count);
     for (int i = 0; i < c.count; ++i) {
@@ -1436,11 +1447,17 @@ inline int group_vec_bits(const ggpm_gemm_call& c, bool b_side) {
     for (int i = 0; i < c.count; ++i) bits |= (int)(b_side ? vec_legal(c.ldb[i], c.base_b[i]) : vec_legal(c.lda[i], c.base_a[i])) << i;
     return bits;
 }
+// no member / segment allows 16-byte loads of both operands: each is a product ggpm_gemm sends to the scalar-load kernel
+inline bool all_scalar(const GemmPlan& pl, int count) {
+    bool scalar = count > 1;
+    for (int i = 0; i < count; ++i) scalar = scalar && !((pl.vec_a >> i & 1) && (pl.vec_b >> i & 1));
+    return scalar;
+}
 
 // ggpm_gemm_grouped
 inline GemmPlan plan_group(const ggpm_gemm_call& c) {
     const int M = c.M, N = c.N, K = c.K[0], count = c.count;
-    if (count <= 0 || count > GGPM_GEMM_MAX_GROUP || M <= 0 || N <= 0 || K <= 0) return plan_refuse(GGPM_ERR_ARG);
+    if (!group_size_ok(count) || M <= 0 || N <= 0 || K <= 0) return plan_refuse(GGPM_ERR_ARG);
     GemmPlan pl;
     bool ok = count > 1;
     int n_pad_max = 0;
@@ -1454,28 +1471,25 @@ inline GemmPlan plan_group(const ggpm_gemm_call& c) {
     if (!ok) {
         // every member on the scalar-load kernel (ggpm_gemm sends a product there, unsplit, whenever one of its operands
         // does not allow 16-byte loads): the same tiles in one launch
-        bool scalar = count > 1;
-        for (int i = 0; i < count; ++i) scalar = scalar && !((pl.vec_a >> i & 1) && (pl.vec_b >> i & 1));
-        if (!scalar) { pl.kernel = GGPM_GEMM_KERNEL_SEQUENCE; return pl; }
-        pl.kernel = GGPM_GEMM_KERNEL_GROUP; pl.lds = LDS_SCALAR;
-        pl.grid[0] = ggpm_ceil_div(n_pad_max, BN); pl.grid[1] = ggpm_ceil_div(M, BM); pl.grid[2] = count;
+        if (!all_scalar(pl, count)) { pl.kernel = GGPM_GEMM_KERNEL_SEQUENCE; return pl; }
+        plan_tiles_64(pl, GGPM_GEMM_KERNEL_GROUP, LDS_SCALAR, n_pad_max, M, count);
         return pl;
     }
     if (small_launch(M, N, count)) { plan_small(pl, n_pad_max, M, count, 1); return pl; }
-    pl.kernel = GGPM_GEMM_KERNEL_GROUP_V2; pl.lds = LDS_V2;
-    pl.grid[0] = ggpm_ceil_div(n_pad_max, BN); pl.grid[1] = ggpm_ceil_div(M, BM); pl.grid[2] = count;
+    plan_tiles_64(pl, GGPM_GEMM_KERNEL_GROUP_V2, LDS_V2, n_pad_max, M, count);
     return pl;
 }
 
-// ggpm_gemm_grouped_masked
+// ggpm_gemm_grouped_masked.  Its two kinds of refusal are made member by member, so the one that wins is the first
+// member's that has any: stopped_at tells the entry point how far the walk came.
 inline GemmPlan plan_group_masked(const ggpm_gemm_call& c) {
     const int M = c.M, N = c.N, K = c.K[0], count = c.count;
-    if (count <= 0 || count > GGPM_GEMM_MAX_GROUP || M <= 0 || N <= 0 || K <= 0) return plan_refuse(GGPM_ERR_ARG);
+    if (!group_size_ok(count) || M <= 0 || N <= 0 || K <= 0) return plan_refuse(GGPM_ERR_ARG);
     int n_pad_max = 0;
     for (int i = 0; i < count; ++i) {
-        if (c.n_pad[i] < N || c.n_pad[i] > c.ldc[i]) return plan_refuse(GGPM_ERR_ARG);
+        if (c.n_pad[i] < N || c.n_pad[i] > c.ldc[i]) return plan_refuse(GGPM_ERR_ARG, i);
         if (!v2_operands_ok(c.lda[i], c.base_a[i], c.trans_a ? K : M, c.ldb[i], c.base_b[i], c.trans_b ? N : K))
-            return plan_refuse(GGPM_ERR_UNSUPPORTED);
+            return plan_refuse(GGPM_ERR_UNSUPPORTED, i);
         n_pad_max = max(n_pad_max, c.n_pad[i]);
     }
     if (!small_launch(M, N, count)) return plan_refuse(GGPM_ERR_UNSUPPORTED);
@@ -1487,16 +1501,16 @@ inline GemmPlan plan_group_masked(const ggpm_gemm_call& c) {
 }
 
 inline size_t group_splitk_bytes(int M, int N, int K, int count) {
-    if (M <= 0 || N <= 0 || K <= 0 || count <= 0 || count > GGPM_GEMM_MAX_GROUP || !small_launch(M, N, count)) return 0;
+    if (M <= 0 || N <= 0 || K <= 0 || !group_size_ok(count) || !small_launch(M, N, count)) return 0;
     int kc;
     const int sp = small_splits(M, N, K, count, &kc);
     return sp > 1 ? (size_t)sp * count * M * N * sizeof(float) : 0;
 }
 
-// ggpm_gemm_grouped_splitk
+// ggpm_gemm_grouped_splitk: the plan of ggpm_gemm_grouped when there is nothing to split or no room for the slabs
 inline GemmPlan plan_group_splitk(const ggpm_gemm_call& c) {
     const int M = c.M, N = c.N, K = c.K[0], count = c.count;
-    if (count <= 0 || count > GGPM_GEMM_MAX_GROUP || M <= 0 || N <= 0 || K <= 0) return plan_refuse(GGPM_ERR_ARG);
+    if (!group_size_ok(count) || M <= 0 || N <= 0 || K <= 0) return plan_refuse(GGPM_ERR_ARG);
     const size_t need = group_splitk_bytes(M, N, K, count);
     bool ok = need > 0 && c.has_ws && c.ws_bytes >= need;
     int n_pad_max = 0;
@@ -1510,16 +1524,14 @@ inline GemmPlan plan_group_splitk(const ggpm_gemm_call& c) {
     pl.vec_a = pl.vec_b = (1 << count) - 1;
     const int sp = small_splits(M, N, K, count, &pl.k_chunk[0]);
     plan_small(pl, N, M, count, sp);
-    pl.reduce = GGPM_GEMM_REDUCE_SPLITK_GROUP;
-    pl.ws_used = need;
+    plan_splitk_reduce(pl, GGPM_GEMM_REDUCE_SPLITK_GROUP, M, N, n_pad_max, count);
     return pl;
 }
 
 // ggpm_gemm_ksegments (c.count: nseg; K, lda, ldb, base_a, base_b per segment; ldc[0], n_pad[0])
 inline GemmPlan plan_segments(const ggpm_gemm_call& c) {
     const int M = c.M, N = c.N, nseg = c.count;
-    if (nseg <= 0 || nseg > GGPM_GEMM_MAX_GROUP || M <= 0 || N <= 0 || c.n_pad[0] < N || c.n_pad[0] > c.ldc[0])
-        return plan_refuse(GGPM_ERR_ARG);
+    if (!group_size_ok(nseg) || M <= 0 || N <= 0 || c.n_pad[0] < N || c.n_pad[0] > c.ldc[0]) return plan_refuse(GGPM_ERR_ARG);
     GemmPlan pl;
     bool ok = nseg > 1;
     for (int i = 0; i < nseg; ++i) {
@@ -1531,55 +1543,28 @@ inline GemmPlan plan_segments(const ggpm_gemm_call& c) {
     if (!ok) {
         // every segment on the scalar-load kernel (where ggpm_gemm sends a product, unsplit, whenever one of its operands
         // does not allow 16-byte loads): the chain of calls in ONE launch that rounds where the chain rounds (gemm_tile_64)
-        bool scalar = nseg > 1;
-        for (int i = 0; i < nseg; ++i) scalar = scalar && !((pl.vec_a >> i & 1) && (pl.vec_b >> i & 1));
-        if (!scalar) { pl.kernel = GGPM_GEMM_KERNEL_SEQUENCE; return pl; }
-        pl.kernel = GGPM_GEMM_KERNEL_SEGS; pl.lds = LDS_SCALAR;
-        pl.grid[0] = ggpm_ceil_div(c.n_pad[0], BN); pl.grid[1] = ggpm_ceil_div(M, BM); pl.grid[2] = 1;
+        if (!all_scalar(pl, nseg)) { pl.kernel = GGPM_GEMM_KERNEL_SEQUENCE; return pl; }
+        plan_tiles_64(pl, GGPM_GEMM_KERNEL_SEGS, LDS_SCALAR, c.n_pad[0], M, 1);
         return pl;
     }
     if (small_launch(M, N, 1)) { plan_small(pl, c.n_pad[0], M, 1, 1); return pl; }
-    pl.kernel = GGPM_GEMM_KERNEL_V2; pl.lds = LDS_V2;
-    pl.grid[0] = ggpm_ceil_div(c.n_pad[0], BN); pl.grid[1] = ggpm_ceil_div(M, BM); pl.grid[2] = 1;
+    plan_tiles_64(pl, GGPM_GEMM_KERNEL_V2, LDS_V2, c.n_pad[0], M, 1);
     return pl;
 }
-
-inline void call_set_member(ggpm_gemm_call& c, int i, const GgpmGemmProblem& p) {
-    c.lda[i] = p.lda; c.ldb[i] = p.ldb; c.ldc[i] = p.ldc; c.n_pad[i] = p.n_pad; c.base_a[i] = low4(p.A); c.base_b[i] = low4(p.B);
-}
-inline ggpm_gemm_call call_of_group(int entry, int trans_a, int trans_b, int M, int N, int K, int count, const GgpmGemmProblem* p,
-                                    bool has_ws, size_t ws_bytes) {
-    ggpm_gemm_call c{};
-    c.entry = entry; c.trans_a = trans_a; c.trans_b = trans_b; c.M = M; c.N = N; c.count = count; c.K[0] = K;
-    c.has_ws = has_ws; c.ws_bytes = ws_bytes;
-    for (int i = 0; i < count && i < GGPM_GEMM_MAX_GROUP; ++i) call_set_member(c, i, p[i]);
-    return c;
-}
-inline dim3 plan_grid(const GemmPlan& pl) { return dim3(pl.grid[0], pl.grid[1], pl.grid[2]); }
 }  // namespace
 
 extern "C" int ggpm_gemm_form_query(const ggpm_gemm_call* call, ggpm_gemm_form* out) {
     if (!call || !out) return GGPM_ERR_ARG;
-    const ggpm_gemm_call& c = *call;
     GemmPlan pl;
-    switch (c.entry) {
-        case GGPM_GEMM_ENTRY_GEMM:
-            pl = plan_gemm(c.trans_a, c.trans_b, c.M, c.N, c.K[0], c.lda[0], c.base_a[0], c.ldb[0], c.base_b[0], c.ldc[0], c.n_pad[0],
-                           c.has_ws != 0, c.ws_bytes);
-            break;
-        case GGPM_GEMM_ENTRY_GROUPED: pl = plan_group(c); break;
-        case GGPM_GEMM_ENTRY_GROUPED_SPLITK: pl = plan_group_splitk(c); break;
-        case GGPM_GEMM_ENTRY_GROUPED_MASKED: pl = plan_group_masked(c); break;
-        case GGPM_GEMM_ENTRY_KSEGMENTS: pl = plan_segments(c); break;
-        case GGPM_GEMM_ENTRY_TALL_GROUPED: pl = plan_tall_group(c); break;
-        case GGPM_GEMM_ENTRY_PAIR_GROUPED: pl = plan_pairs(c); break;
-        case GGPM_GEMM_ENTRY_TN_BF16: {      // ggpm_gemm_tn_bf16: one member, n_pad = N, operands rounded to bf16
-            if (!c.has_ws || c.M <= 0 || c.N <= 0 || c.K[0] <= 0 || c.ldc[0] < c.N) { pl = plan_refuse(GGPM_ERR_ARG); break; }
-            ggpm_gemm_call t = c;
-            t.count = 1; t.mode = 1; t.n_pad[0] = c.N;
-            pl = plan_tall_group(t);
-            break;
-        }
+    switch (call->entry) {
+        case GGPM_GEMM_ENTRY_GEMM: pl = plan_gemm(*call); break;
+        case GGPM_GEMM_ENTRY_GROUPED: pl = plan_group(*call); break;
+        case GGPM_GEMM_ENTRY_GROUPED_SPLITK: pl = plan_group_splitk(*call); break;
+        case GGPM_GEMM_ENTRY_GROUPED_MASKED: pl = plan_group_masked(*call); break;
+        case GGPM_GEMM_ENTRY_KSEGMENTS: pl = plan_segments(*call); break;
+        case GGPM_GEMM_ENTRY_TALL_GROUPED: pl = plan_tall_group(*call); break;
+        case GGPM_GEMM_ENTRY_PAIR_GROUPED: pl = plan_pairs(*call); break;
+        case GGPM_GEMM_ENTRY_TN_BF16: pl = plan_tn_bf16(*call); break;
         default: return GGPM_ERR_ARG;
     }
     *out = ggpm_gemm_form{};
@@ -1602,97 +1587,168 @@ extern "C" size_t ggpm_gemm_workspace_bytes(int M, int N, int K) {
     return bytes;
 }
 
+extern "C" size_t ggpm_gemm_grouped_splitk_workspace_bytes(int M, int N, int K, int count) {
+    return group_splitk_bytes(M, N, K, count);
+}
+
+bool ggpm_bf16_storage_applies(int E1, int H) { return gemm_use_tall() && E1 >= 6144 && tall_shape(H, H, E1); }
+extern "C" int ggpm_level_bf16_storage(int E1, int H) { return ggpm_bf16_storage_applies(E1, H) ? 1 : 0; }
+
+extern "C" int ggpm_gemm_tn_bf16_applies(int M, int N, int K) {
+    return gemm_use_tall() && M > 0 && N > 0 && K > 0 && tall_shape(M, N, K) ? 1 : 0;
+}
+
+bool ggpm_gemm_prefers_grouped(int M, int N, int K, int count) {
+    return ggpm_gemm_workspace_bytes(M, N, K) == 0 || (small_launch(M, N, count) && K <= 8192);
+}
+
+// ---- from a plan to launches: one filler, one executor ------------------------------------------------------------------
+namespace {
+// The description of a call over `count` members that share K (the entries with K per member / segment set c.K themselves).
+// Members beyond the group's limit are left out: the plan refuses such a call.
+inline ggpm_gemm_call call_of_group(int entry, int trans_a, int trans_b, int M, int N, int K, int count, const GgpmGemmProblem* p,
+                                    bool has_ws, size_t ws_bytes) {
+    ggpm_gemm_call c{};
+    c.entry = entry; c.trans_a = trans_a; c.trans_b = trans_b; c.M = M; c.N = N; c.count = count; c.K[0] = K;
+    c.has_ws = has_ws; c.ws_bytes = ws_bytes;
+    for (int i = 0; i < count && i < GGPM_GEMM_MAX_GROUP; ++i) {
+        c.K[i] = K; c.lda[i] = p[i].lda; c.ldb[i] = p[i].ldb; c.ldc[i] = p[i].ldc; c.n_pad[i] = p[i].n_pad;
+        c.base_a[i] = low4(p[i].A); c.base_b[i] = low4(p[i].B);
+    }
+    return c;
+}
+inline bool has_null_operand(const GgpmGemmProblem* p, int count) {
+    for (int i = 0; i < count && i < GGPM_GEMM_MAX_GROUP; ++i)
+        if (!p[i].A || !p[i].B || !p[i].C) return true;
+    return false;
+}
+
+// The kernel arguments of `count` members (member i: M x N x c.K[i] on p[i]): vecA / vecB, k_chunk and the slab base in `ws`
+// come from the plan and from nowhere else; `extra(g, i)` adds what only one entry point has (K segments, epilogue options);
+// the slots behind the last member repeat member 0.
+inline void no_extra(GemmArgs&, int) {}
+template <class Extra>
+inline void fill_group(GemmGroupArgs& gg, const GemmPlan& pl, const ggpm_gemm_call& c, int count, const GgpmGemmProblem* p, float* ws,
+                       Extra extra) {
+    for (int i = 0; i < count; ++i) {
+        GemmArgs& g = gg.p[i];
+        g = GemmArgs{};
+        g.M = c.M; g.N = c.N; g.K = c.K[i]; g.A = p[i].A; g.lda = p[i].lda; g.B = p[i].B; g.ldb = p[i].ldb; g.C = p[i].C; g.ldc = p[i].ldc;
+        g.n_pad = p[i].n_pad; g.bias = p[i].bias; g.accumulate = p[i].accumulate; g.act = p[i].act; g.zero_row0 = p[i].zero_row0;
+        g.vecA = pl.vec_a >> i & 1; g.vecB = pl.vec_b >> i & 1;
+        g.k_chunk = pl.k_chunk[i] ? pl.k_chunk[i] : pl.k_chunk[0];
+        g.ws = pl.ws_used ? ws + i * pl.ws_stride : nullptr;
+        extra(g, i);
+    }
+    for (int i = count; i < GGPM_GEMM_MAX_GROUP; ++i) gg.p[i] = gg.p[0];
+}
+
+// the (trans_a, trans_b) instantiation of a kernel template, launched on the plan's grid
+#define GGPM_LAUNCH_TT(KERNEL, ...)                                                                \
+    do {                                                                                           \
+        if (!trans_a && !trans_b) KERNEL<false, false><<<grid, pl.block, 0, s>>>(__VA_ARGS__);     \
+        else if (!trans_a && trans_b) KERNEL<false, true><<<grid, pl.block, 0, s>>>(__VA_ARGS__);  \
+        else if (trans_a && !trans_b) KERNEL<true, false><<<grid, pl.block, 0, s>>>(__VA_ARGS__);  \
+        else KERNEL<true, true><<<grid, pl.block, 0, s>>>(__VA_ARGS__);                            \
+    } while (0)
+
+// gemm_tn_tall; under GGPM_GEMM_DEBUG (dev variant) a single product also reports the loop stamps of its workgroup 0
+inline void launch_tall(const GemmPlan& pl, GemmGroupArgs& gg, dim3 grid, hipStream_t s) {
+    static unsigned long long* dbg = [] {
+        unsigned long long* p = nullptr;
+        if (ggpm_dev_env("GGPM_GEMM_DEBUG")) (void)hipMalloc(&p, 64);
+        return p;
+    }();
+    const bool stamps = dbg && pl.grid[2] == pl.splits;
+    if (stamps) gg.p[0].dbg = dbg;
+    gemm_tn_tall<<<grid, pl.block, 0, s>>>(gg, pl.splits);
+    if (stamps) {
+        const GemmArgs& g = gg.p[0];
+        unsigned long long h[6];
+        (void)hipStreamSynchronize(s);
+        (void)hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost);
+        const int steps = ggpm_ceil_div(g.k_chunk, 2 * TK) * 2;
+        fprintf(stderr, "[gemm_tn_tall %dx%dx%d grid %dx%dx%d] prologue %.2f us, loop %.2f us = %d steps x %.0f cycles, "
+                "shader clock %.2f GHz\n", g.M, g.N, g.K, grid.x, grid.y, grid.z, (h[3] - h[1]) * 0.01, (h[5] - h[3]) * 0.01,
+                steps, (double)(h[4] - h[2]) / steps, (double)(h[4] - h[2]) / ((h[5] - h[3]) * 10.0));
+    }
+}
+
+// Launches pl.kernel on the filled arguments, then the reduce the plan names.  (The kernels over one problem take gg.p[0].)
+inline int run_plan(const GemmPlan& pl, int trans_a, int trans_b, GemmGroupArgs& gg, ggpm_stream_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]);
+    switch (pl.kernel) {
+        case GGPM_GEMM_KERNEL_SMALL_V3: GGPM_LAUNCH_TT(gemm_small_v3, gg, pl.splits); break;
+        case GGPM_GEMM_KERNEL_V2: GGPM_LAUNCH_TT(gemm_kernel_v2, gg.p[0]); break;
+        case GGPM_GEMM_KERNEL_SCALAR: GGPM_LAUNCH_TT(gemm_kernel, gg.p[0]); break;
+        case GGPM_GEMM_KERNEL_TALL_BF16_IN16: gemm_tn_tall_bf16<true><<<grid, pl.block, 0, s>>>(gg, pl.splits); break;
+        case GGPM_GEMM_KERNEL_TALL_BF16: gemm_tn_tall_bf16<false><<<grid, pl.block, 0, s>>>(gg, pl.splits); break;
+        case GGPM_GEMM_KERNEL_GROUP: GGPM_LAUNCH_TT(gemm_kernel_group, gg); break;
+        case GGPM_GEMM_KERNEL_GROUP_V2: GGPM_LAUNCH_TT(gemm_group_v2, gg); break;
+        case GGPM_GEMM_KERNEL_SEGS:      // (A is never transposed)
+            if (trans_b) gemm_kernel_segs<true><<<grid, pl.block, 0, s>>>(gg.p[0]);
+            else gemm_kernel_segs<false><<<grid, pl.block, 0, s>>>(gg.p[0]);
+            break;
+        case GGPM_GEMM_KERNEL_TALL: launch_tall(pl, gg, grid, s); break;
+        case GGPM_GEMM_KERNEL_TALL_SPLIT:
+            ggpm_set_lds(gemm_tn_tall_split, pl.lds);
+            gemm_tn_tall_split<<<grid, pl.block, pl.lds, s>>>(gg, pl.splits);
+            break;
+        default: return GGPM_ERR_ARG;      // (NONE, SEQUENCE: nothing to launch; the entry points do not come here with them)
+    }
+    const dim3 rgrid(pl.reduce_grid[0], pl.reduce_grid[1], pl.reduce_grid[2]);
+    switch (pl.reduce) {
+        case GGPM_GEMM_REDUCE_SPLITK: splitk_reduce<<<rgrid, 256, 0, s>>>(gg.p[0], pl.splits); break;
+        case GGPM_GEMM_REDUCE_SPLITK_GROUP: splitk_reduce_group<<<rgrid, 256, 0, s>>>(gg, pl.splits); break;
+        case GGPM_GEMM_REDUCE_TALL: tall_reduce<<<rgrid, 256, 0, s>>>(gg, pl.splits, pl.grid[0], pl.grid[0] * pl.grid[1]); break;
+        default: break;
+    }
+    GGPM_CHECK_LAUNCH();
+    return GGPM_OK;
+}
+#undef GGPM_LAUNCH_TT
+
+// ggpm_gemm_grouped and ggpm_gemm_grouped_splitk behind their plans
+inline int run_group(const ggpm_gemm_call& c, const GemmPlan& pl, const GgpmGemmProblem* p, float* ws, ggpm_stream_t stream) {
+    if (pl.rc) return pl.rc;
+    if (pl.kernel == GGPM_GEMM_KERNEL_SEQUENCE) {
+        for (int i = 0; i < c.count; ++i) {
+            const int rc = ggpm_gemm(c.trans_a, c.trans_b, c.M, c.N, c.K[0], p[i].A, p[i].lda, p[i].B, p[i].ldb, p[i].C, p[i].ldc,
+                                     p[i].n_pad, p[i].bias, p[i].accumulate, p[i].act, p[i].zero_row0, nullptr, 0, stream);
+            if (rc) return rc;
+        }
+        return GGPM_OK;
+    }
+    GemmGroupArgs gg;
+    fill_group(gg, pl, c, c.count, p, ws, no_extra);
+    return run_plan(pl, c.trans_a, c.trans_b, gg, stream);
+}
+}  // namespace
+
+// ---- the entry points: pointer checks, the call's description, its plan, then the SEQUENCE fallback or fill + run ----------
 extern "C" int ggpm_gemm(int trans_a, int trans_b, int M, int N, int K, const float* A, int lda,
                          const float* B, int ldb, float* C, int ldc, int n_pad, const float* bias,
                          int accumulate, int act, int zero_row0, float* splitk_ws, size_t splitk_ws_bytes,
                          ggpm_stream_t stream) {
     GGPM_CLEAR_STALE_ERROR();
     if (!A || !B || !C) return GGPM_ERR_ARG;
-    const GemmPlan pl = plan_gemm(trans_a, trans_b, M, N, K, lda, low4(A), ldb, low4(B), ldc, n_pad, splitk_ws != nullptr, splitk_ws_bytes);
+    const GgpmGemmProblem p = {A, lda, B, ldb, C, ldc, n_pad, bias, accumulate, act, zero_row0};
+    const ggpm_gemm_call c = call_of_group(GGPM_GEMM_ENTRY_GEMM, trans_a, trans_b, M, N, K, 1, &p, splitk_ws != nullptr, splitk_ws_bytes);
+    const GemmPlan pl = plan_gemm(c);
     if (pl.rc) return pl.rc;
-    hipStream_t s = (hipStream_t)stream;
-    GemmArgs g{};
-    g.M = M; g.N = N; g.K = K; g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc;
-    g.n_pad = n_pad; g.bias = bias; g.accumulate = accumulate; g.act = act; g.zero_row0 = zero_row0;
-    g.vecA = pl.vec_a; g.vecB = pl.vec_b;
-    g.k_chunk = pl.k_chunk[0];
-    g.ws = pl.ws_used ? splitk_ws : nullptr;
-    const int splits = pl.splits;
-    const dim3 grid = plan_grid(pl);
-    if (pl.kernel == GGPM_GEMM_KERNEL_TALL_SPLIT) {
-        const int tiles_n = grid.x, tiles_m = grid.y;
-        GemmGroupArgs gg;
-        for (int i = 0; i < GGPM_GEMM_MAX_GROUP; ++i) gg.p[i] = g;
-        launch_tall_split(gg, grid, splits, s);
-        tall_reduce<<<tiles_n * tiles_m * 100, 256, 0, s>>>(gg, splits, tiles_n, tiles_n * tiles_m);
-        GGPM_CHECK_LAUNCH();
-        return GGPM_OK;
-    }
-    if (pl.kernel == GGPM_GEMM_KERNEL_TALL) {
-        const int tiles_n = grid.x, tiles_m = grid.y;
-        static unsigned long long* dbg = [] {
-            unsigned long long* p = nullptr;
-            if (ggpm_dev_env("GGPM_GEMM_DEBUG")) (void)hipMalloc(&p, 64);
-            return p;
-        }();
-        g.dbg = dbg;
-        GemmGroupArgs gg;
-        for (int i = 0; i < GGPM_GEMM_MAX_GROUP; ++i) gg.p[i] = g;
-        gemm_tn_tall<<<grid, 256, 0, s>>>(gg, splits);
-        if (dbg) {
-            unsigned long long h[6];
-            (void)hipStreamSynchronize(s);
-            (void)hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost);
-            const int steps = ggpm_ceil_div(g.k_chunk, 2 * TK) * 2;
-            fprintf(stderr, "[gemm_tn_tall %dx%dx%d grid %dx%dx%d] prologue %.2f us, loop %.2f us = %d steps x %.0f cycles, "
-                    "shader clock %.2f GHz\n", M, N, K, grid.x, grid.y, grid.z, (h[3] - h[1]) * 0.01, (h[5] - h[3]) * 0.01,
-                    steps, (double)(h[4] - h[2]) / steps, (double)(h[4] - h[2]) / ((h[5] - h[3]) * 10.0));
-        }
-        if (splits > 1) tall_reduce<<<tiles_n * tiles_m * 100, 256, 0, s>>>(gg, splits, tiles_n, tiles_n * tiles_m);
-        GGPM_CHECK_LAUNCH();
-        return GGPM_OK;
-    }
-    if (pl.kernel == GGPM_GEMM_KERNEL_SMALL_V3) {
-        GemmGroupArgs gg;
-        for (int i = 0; i < GGPM_GEMM_MAX_GROUP; ++i) gg.p[i] = g;
-        launch_small(trans_a, trans_b, gg, grid, 1, s);
-        GGPM_CHECK_LAUNCH();
-        return GGPM_OK;
-    }
-    if (pl.kernel == GGPM_GEMM_KERNEL_V2) {
-        if (!trans_a && !trans_b) gemm_kernel_v2<false, false><<<grid, 256, 0, s>>>(g);
-        else if (!trans_a && trans_b) gemm_kernel_v2<false, true><<<grid, 256, 0, s>>>(g);
-        else if (trans_a && !trans_b) gemm_kernel_v2<true, false><<<grid, 256, 0, s>>>(g);
-        else gemm_kernel_v2<true, true><<<grid, 256, 0, s>>>(g);
-    } else if (!trans_a && !trans_b) gemm_kernel<false, false><<<grid, 256, 0, s>>>(g);
-    else if (!trans_a && trans_b) gemm_kernel<false, true><<<grid, 256, 0, s>>>(g);
-    else if (trans_a && !trans_b) gemm_kernel<true, false><<<grid, 256, 0, s>>>(g);
-    else gemm_kernel<true, true><<<grid, 256, 0, s>>>(g);
-    if (splits > 1) {
-        dim3 rg(ggpm_ceil_div(n_pad, 256), M);
-        splitk_reduce<<<rg, 256, 0, s>>>(g, splits);
-    }
-    GGPM_CHECK_LAUNCH();
-    return GGPM_OK;
+    GemmGroupArgs gg;
+    fill_group(gg, pl, c, 1, &p, splitk_ws, no_extra);
+    return run_plan(pl, trans_a, trans_b, gg, stream);
 }
 
-namespace {
-inline void fill_args(GemmArgs& g, int M, int N, int K, const GgpmGemmProblem& p) {
-    g = GemmArgs{};
-    g.M = M; g.N = N; g.K = K; g.A = p.A; g.lda = p.lda; g.B = p.B; g.ldb = p.ldb; g.C = p.C; g.ldc = p.ldc;
-    g.n_pad = p.n_pad; g.bias = p.bias; g.accumulate = p.accumulate; g.act = p.act; g.zero_row0 = p.zero_row0;
-    g.vecA = g.vecB = 1;
-    g.k_chunk = ggpm_round_up(K, BK);
-}
-}  // namespace
-
-int ggpm_gemm_tall_grouped(int M, int N, int count, const GgpmGemmProblem* p, const int* K, float* ws, size_t ws_bytes,
-                           ggpm_stream_t stream, int bf16) {
+extern "C" int ggpm_gemm_tn_tall_grouped(int M, int N, int count, const ggpm_gemm_problem* p, const int* K, float* ws,
+                                         size_t ws_bytes, int mode, ggpm_stream_t stream) {
     GGPM_CLEAR_STALE_ERROR();
-    if (count <= 0 || count > GGPM_GEMM_MAX_GROUP || !p || !K || M <= 0 || N <= 0) return GGPM_ERR_ARG;
+    if (!p || !K || mode < 0 || mode > 2) return GGPM_ERR_ARG;
     ggpm_gemm_call c = call_of_group(GGPM_GEMM_ENTRY_TALL_GROUPED, 1, 0, M, N, 0, count, p, ws != nullptr, ws_bytes);
-    for (int i = 0; i < count; ++i) c.K[i] = K[i];
-    c.mode = bf16;
+    for (int i = 0; i < count && i < GGPM_GEMM_MAX_GROUP; ++i) c.K[i] = K[i];
+    c.mode = mode;
     const GemmPlan pl = plan_tall_group(c);
     if (pl.rc) return pl.rc;
     if (pl.kernel == GGPM_GEMM_KERNEL_SEQUENCE) {
@@ -1703,43 +1759,36 @@ int ggpm_gemm_tall_grouped(int M, int N, int count, const GgpmGemmProblem* p, co
         }
         return GGPM_OK;
     }
-    const int splits = pl.splits;
-    const size_t slab = tall_slab_bytes(M, N);
     GemmGroupArgs gg;
-    for (int i = 0; i < count; ++i) {
-        fill_args(gg.p[i], M, N, K[i], p[i]);
-        gg.p[i].k_chunk = pl.k_chunk[i];
-        gg.p[i].ws = ws + (size_t)i * splits * (slab / sizeof(float));
-    }
-    for (int i = count; i < GGPM_GEMM_MAX_GROUP; ++i) gg.p[i] = gg.p[0];
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid = plan_grid(pl);
-    const int tiles_n = grid.x, tiles_m = grid.y;
-    if (pl.kernel == GGPM_GEMM_KERNEL_TALL_BF16_IN16) gemm_tn_tall_bf16<true><<<grid, 256, 0, s>>>(gg, splits);
-    else if (pl.kernel == GGPM_GEMM_KERNEL_TALL_BF16) gemm_tn_tall_bf16<false><<<grid, 256, 0, s>>>(gg, splits);
-    else if (pl.kernel == GGPM_GEMM_KERNEL_TALL_SPLIT) launch_tall_split(gg, grid, splits, s);
-    else gemm_tn_tall<<<grid, 256, 0, s>>>(gg, splits);
-    tall_reduce<<<dim3(tiles_n * tiles_m * 100, count), 256, 0, s>>>(gg, splits, tiles_n, tiles_n * tiles_m);
-    GGPM_CHECK_LAUNCH();
-    return GGPM_OK;
+    fill_group(gg, pl, c, count, p, ws, no_extra);
+    return run_plan(pl, 1, 0, gg, stream);
+}
+
+extern "C" int ggpm_gemm_tn_bf16(int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
+                                 float* ws, size_t ws_bytes, ggpm_stream_t stream) {
+    if (!A || !B || !C || !ws) return GGPM_ERR_ARG;
+    const GgpmGemmProblem p = {A, lda, B, ldb, C, ldc, N, nullptr, 0, GGPM_ACT_NONE, 0};      // (n_pad = N: ldc < N is refused)
+    return ggpm_gemm_tn_tall_grouped(M, N, 1, &p, &K, ws, ws_bytes, 1, stream);
 }
 
 // C_i = hi_i^T B_i + lo_i^T B_i = [hi_i; lo_i]^T [B_i; B_i] for `count` members in ONE launch of the small-product kernel:
 // each member is one accumulator chain over two K segments of `rows` rows (no split-K, no reduce launch).  Shapes with
 // more output tiles than that kernel is for run as two products per member, the second one accumulating.
-int ggpm_gemm_tn_pair_grouped(int M, int N, int rows, int ld, int count, const ggpm_pair_problem* p, ggpm_stream_t stream) {
+extern "C" int ggpm_gemm_tn_pair_grouped_c(int M, int N, int rows, int ld, int count, const ggpm_pair_problem* p,
+                                           ggpm_stream_t stream) {
     GGPM_CLEAR_STALE_ERROR();
-    if (count <= 0 || count > GGPM_GEMM_MAX_GROUP || !p || M <= 0 || N <= 0 || rows <= 0 || ld < M || ld < N) return GGPM_ERR_ARG;
+    if (!p) return GGPM_ERR_ARG;
     ggpm_gemm_call c{};
     c.entry = GGPM_GEMM_ENTRY_PAIR_GROUPED; c.trans_a = 1; c.M = M; c.N = N; c.count = count; c.K[0] = rows; c.lda[0] = c.ldb[0] = ld;
-    for (int i = 0; i < count; ++i) {
-        if (!p[i].hi || !p[i].lo || !p[i].B || !p[i].C || p[i].ldc < N) return GGPM_ERR_ARG;
-        c.ldc[i] = p[i].ldc; c.base_a[i] = low4(p[i].hi); c.base_lo[i] = low4(p[i].lo); c.base_b[i] = low4(p[i].B);
+    GgpmGemmProblem q[GGPM_GEMM_MAX_GROUP];
+    for (int i = 0; i < count && i < GGPM_GEMM_MAX_GROUP; ++i) {
+        if (!p[i].hi || !p[i].lo || !p[i].B || !p[i].C) return GGPM_ERR_ARG;
+        c.K[i] = rows; c.ldc[i] = p[i].ldc; c.base_a[i] = low4(p[i].hi); c.base_lo[i] = low4(p[i].lo); c.base_b[i] = low4(p[i].B);
+        q[i] = {p[i].hi, ld, p[i].B, ld, p[i].C, p[i].ldc, N, nullptr, 0, GGPM_ACT_NONE, 0};
     }
     const GemmPlan pl = plan_pairs(c);
     if (pl.rc) return pl.rc;
-    const bool ok = pl.kernel != GGPM_GEMM_KERNEL_SEQUENCE;
-    if (!ok) {
+    if (pl.kernel == GGPM_GEMM_KERNEL_SEQUENCE) {
         for (int i = 0; i < count; ++i) {
             int rc = ggpm_gemm(1, 0, M, N, rows, p[i].hi, ld, p[i].B, ld, p[i].C, p[i].ldc, N, nullptr, 0, GGPM_ACT_NONE, 0,
                                nullptr, 0, stream);
@@ -1751,80 +1800,28 @@ int ggpm_gemm_tn_pair_grouped(int M, int N, int rows, int ld, int count, const g
         return GGPM_OK;
     }
     GemmGroupArgs gg;
-    for (int i = 0; i < count; ++i) {
-        const GgpmGemmProblem q = {p[i].hi, ld, p[i].B, ld, p[i].C, p[i].ldc, N, nullptr, 0, GGPM_ACT_NONE, 0};
-        GemmArgs& g = gg.p[i];
-        fill_args(g, M, N, rows, q);
+    fill_group(gg, pl, c, count, q, nullptr, [&](GemmArgs& g, int i) {
         g.nseg = 2;
         g.segA[0] = p[i].hi; g.segA[1] = p[i].lo;
         for (int sg = 0; sg < 2; ++sg) { g.segB[sg] = p[i].B; g.seg_lda[sg] = g.seg_ldb[sg] = ld; g.segK[sg] = rows; }
-    }
-    for (int i = count; i < GGPM_GEMM_MAX_GROUP; ++i) gg.p[i] = gg.p[0];
-    launch_small(1, 0, gg, plan_grid(pl), 1, (hipStream_t)stream);
-    GGPM_CHECK_LAUNCH();
-    return GGPM_OK;
-}
-
-bool ggpm_bf16_storage_applies(int E1, int H) {
-    static const int use_tall = [] { const char* e = ggpm_dev_env("GGPM_GEMM_TALL"); return e ? atoi(e) : 1; }();
-    return use_tall && E1 >= 6144 && tall_shape(H, H, E1);
-}
-extern "C" int ggpm_level_bf16_storage(int E1, int H) { return ggpm_bf16_storage_applies(E1, H) ? 1 : 0; }
-
-extern "C" int ggpm_gemm_tn_bf16_applies(int M, int N, int K) {
-    static const int use_tall = [] { const char* e = ggpm_dev_env("GGPM_GEMM_TALL"); return e ? atoi(e) : 1; }();
-    return use_tall && M > 0 && N > 0 && K > 0 && tall_shape(M, N, K) ? 1 : 0;
-}
-
-extern "C" int ggpm_gemm_tn_bf16(int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
-                                 float* ws, size_t ws_bytes, ggpm_stream_t stream) {
-    if (!A || !B || !C || !ws || M <= 0 || N <= 0 || K <= 0 || ldc < N) return GGPM_ERR_ARG;
-    const GgpmGemmProblem p = {A, lda, B, ldb, C, ldc, N, nullptr, 0, GGPM_ACT_NONE, 0};
-    return ggpm_gemm_tall_grouped(M, N, 1, &p, &K, ws, ws_bytes, stream, 1);
-}
-
-bool ggpm_gemm_prefers_grouped(int M, int N, int K, int count) {
-    return ggpm_gemm_workspace_bytes(M, N, K) == 0 || (small_launch(M, N, count) && K <= 8192);
+    });
+    return run_plan(pl, 1, 0, gg, stream);
 }
 
 extern "C" int ggpm_gemm_grouped(int trans_a, int trans_b, int M, int N, int K, int count, const ggpm_gemm_problem* p,
                                  ggpm_stream_t stream) {
     GGPM_CLEAR_STALE_ERROR();
-    if (count <= 0 || count > GGPM_GEMM_MAX_GROUP || !p || M <= 0 || N <= 0 || K <= 0) return GGPM_ERR_ARG;
-    for (int i = 0; i < count; ++i)
-        if (!p[i].A || !p[i].B || !p[i].C || p[i].n_pad < N || p[i].n_pad > p[i].ldc) return GGPM_ERR_ARG;
-    const GemmPlan pl = plan_group(call_of_group(GGPM_GEMM_ENTRY_GROUPED, trans_a, trans_b, M, N, K, count, p, false, 0));
-    if (pl.rc) return pl.rc;
-    if (pl.kernel == GGPM_GEMM_KERNEL_SEQUENCE) {
-        for (int i = 0; i < count; ++i) {
-            const int rc = ggpm_gemm(trans_a, trans_b, M, N, K, p[i].A, p[i].lda, p[i].B, p[i].ldb, p[i].C, p[i].ldc,
-                                     p[i].n_pad, p[i].bias, p[i].accumulate, p[i].act, p[i].zero_row0, nullptr, 0, stream);
-            if (rc) return rc;
-        }
-        return GGPM_OK;
-    }
-    GemmGroupArgs gg;
-    for (int i = 0; i < count; ++i) {
-        fill_args(gg.p[i], M, N, K, p[i]);
-        gg.p[i].vecA = pl.vec_a >> i & 1;
-        gg.p[i].vecB = pl.vec_b >> i & 1;
-    }
-    for (int i = count; i < GGPM_GEMM_MAX_GROUP; ++i) gg.p[i] = gg.p[0];
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid = plan_grid(pl);
-    if (pl.kernel == GGPM_GEMM_KERNEL_GROUP) {
-        if (!trans_a && !trans_b) gemm_kernel_group<false, false><<<grid, 256, 0, s>>>(gg);
-        else if (!trans_a && trans_b) gemm_kernel_group<false, true><<<grid, 256, 0, s>>>(gg);
-        else if (trans_a && !trans_b) gemm_kernel_group<true, false><<<grid, 256, 0, s>>>(gg);
-        else gemm_kernel_group<true, true><<<grid, 256, 0, s>>>(gg);
-    } else if (pl.kernel == GGPM_GEMM_KERNEL_SMALL_V3) {
-        launch_small(trans_a, trans_b, gg, grid, 1, s);
-    } else if (!trans_a && !trans_b) gemm_group_v2<false, false><<<grid, 256, 0, s>>>(gg);
-    else if (!trans_a && trans_b) gemm_group_v2<false, true><<<grid, 256, 0, s>>>(gg);
-    else if (trans_a && !trans_b) gemm_group_v2<true, false><<<grid, 256, 0, s>>>(gg);
-    else gemm_group_v2<true, true><<<grid, 256, 0, s>>>(gg);
-    GGPM_CHECK_LAUNCH();
-    return GGPM_OK;
+    if (!p || has_null_operand(p, count)) return GGPM_ERR_ARG;
+    const ggpm_gemm_call c = call_of_group(GGPM_GEMM_ENTRY_GROUPED, trans_a, trans_b, M, N, K, count, p, false, 0);
+    return run_group(c, plan_group(c), p, nullptr, stream);
+}
+
+extern "C" int ggpm_gemm_grouped_splitk(int trans_a, int trans_b, int M, int N, int K, int count, const ggpm_gemm_problem* p,
+                                        float* ws, size_t ws_bytes, ggpm_stream_t stream) {
+    GGPM_CLEAR_STALE_ERROR();
+    if (!p || has_null_operand(p, count)) return GGPM_ERR_ARG;
+    const ggpm_gemm_call c = call_of_group(GGPM_GEMM_ENTRY_GROUPED_SPLITK, trans_a, trans_b, M, N, K, count, p, ws != nullptr, ws_bytes);
+    return run_group(c, plan_group_splitk(c), p, ws, stream);
 }
 
 // ggpm_gemm_grouped on gemm_small_v3 with per-problem epilogue options (`e[i]`; common.h).  GGPM_ERR_UNSUPPORTED when the
@@ -1832,71 +1829,34 @@ extern "C" int ggpm_gemm_grouped(int trans_a, int trans_b, int M, int N, int K, 
 extern "C" int ggpm_gemm_grouped_masked(int trans_a, int trans_b, int M, int N, int K, int count, const ggpm_gemm_problem* p,
                                         const ggpm_gemm_epilogue* e, ggpm_stream_t stream) {
     GGPM_CLEAR_STALE_ERROR();
-    if (count <= 0 || count > GGPM_GEMM_MAX_GROUP || !p || !e || M <= 0 || N <= 0 || K <= 0) return GGPM_ERR_ARG;
-    for (int i = 0; i < count; ++i) {
-        if (!p[i].A || !p[i].B || !p[i].C || p[i].n_pad < N || p[i].n_pad > p[i].ldc) return GGPM_ERR_ARG;
+    if (!p || !e) return GGPM_ERR_ARG;
+    const ggpm_gemm_call c = call_of_group(GGPM_GEMM_ENTRY_GROUPED_MASKED, trans_a, trans_b, M, N, K, count, p, false, 0);
+    const GemmPlan pl = plan_group_masked(c);
+    // a member's pointers are checked ahead of its alignment, and member by member: up to the one the plan stopped at
+    for (int i = 0; i < count && i < GGPM_GEMM_MAX_GROUP && i <= pl.stopped_at; ++i) {
+        if (!p[i].A || !p[i].B || !p[i].C) return GGPM_ERR_ARG;
         if (e[i].addend && e[i].ld_addend < N) return GGPM_ERR_ARG;
         if (e[i].mask_out && (!e[i].mask_y || e[i].ld_mask < N)) return GGPM_ERR_ARG;
-        if (!v2_operands_ok(p[i].lda, low4(p[i].A), trans_a ? K : M, p[i].ldb, low4(p[i].B), trans_b ? N : K)) return GGPM_ERR_UNSUPPORTED;
     }
-    const GemmPlan pl = plan_group_masked(call_of_group(GGPM_GEMM_ENTRY_GROUPED_MASKED, trans_a, trans_b, M, N, K, count, p, false, 0));
     if (pl.rc) return pl.rc;
     GemmGroupArgs gg;
-    for (int i = 0; i < count; ++i) {
-        fill_args(gg.p[i], M, N, K, p[i]);
-        gg.p[i].addend = e[i].addend; gg.p[i].ld_addend = e[i].ld_addend;
-        gg.p[i].mask_y = e[i].mask_y; gg.p[i].mask_out = e[i].mask_out; gg.p[i].ld_mask = e[i].ld_mask;
-        gg.p[i].mask_act = e[i].mask_act; gg.p[i].mask_zero_row0 = e[i].mask_zero_row0;
-    }
-    for (int i = count; i < GGPM_GEMM_MAX_GROUP; ++i) gg.p[i] = gg.p[0];
-    launch_small(trans_a, trans_b, gg, plan_grid(pl), 1, (hipStream_t)stream);
-    GGPM_CHECK_LAUNCH();
-    return GGPM_OK;
-}
-
-extern "C" size_t ggpm_gemm_grouped_splitk_workspace_bytes(int M, int N, int K, int count) {
-    return group_splitk_bytes(M, N, K, count);
-}
-
-extern "C" int ggpm_gemm_grouped_splitk(int trans_a, int trans_b, int M, int N, int K, int count, const ggpm_gemm_problem* p,
-                                        float* ws, size_t ws_bytes, ggpm_stream_t stream) {
-    GGPM_CLEAR_STALE_ERROR();
-    if (count <= 0 || count > GGPM_GEMM_MAX_GROUP || !p || M <= 0 || N <= 0 || K <= 0) return GGPM_ERR_ARG;
-    const size_t need = group_splitk_bytes(M, N, K, count);
-    bool ok = need > 0 && ws && ws_bytes >= need;
-    for (int i = 0; i < count && ok; ++i)
-        if (!p[i].A || !p[i].B || !p[i].C || p[i].n_pad < N || p[i].n_pad > p[i].ldc) return GGPM_ERR_ARG;
-    const GemmPlan pl = plan_group_splitk(call_of_group(GGPM_GEMM_ENTRY_GROUPED_SPLITK, trans_a, trans_b, M, N, K, count, p, ws != nullptr, ws_bytes));
-    if (pl.rc) return pl.rc;
-    if (pl.reduce != GGPM_GEMM_REDUCE_SPLITK_GROUP) return ggpm_gemm_grouped(trans_a, trans_b, M, N, K, count, p, stream);
-    const int kc = pl.k_chunk[0], sp = pl.splits;
-    int n_pad_max = 0;
-    for (int i = 0; i < count; ++i) n_pad_max = max(n_pad_max, p[i].n_pad);
-    GemmGroupArgs gg;
-    for (int i = 0; i < count; ++i) {
-        fill_args(gg.p[i], M, N, K, p[i]);
-        gg.p[i].k_chunk = kc;
-        gg.p[i].ws = ws + (size_t)i * sp * M * N;
-    }
-    for (int i = count; i < GGPM_GEMM_MAX_GROUP; ++i) gg.p[i] = gg.p[0];
-    hipStream_t s = (hipStream_t)stream;
-    launch_small(trans_a, trans_b, gg, plan_grid(pl), sp, s);
-    splitk_reduce_group<<<dim3(ggpm_ceil_div(n_pad_max, 256), M, count), 256, 0, s>>>(gg, sp);
-    GGPM_CHECK_LAUNCH();
-    return GGPM_OK;
+    fill_group(gg, pl, c, count, p, nullptr, [&](GemmArgs& g, int i) {
+        g.addend = e[i].addend; g.ld_addend = e[i].ld_addend;
+        g.mask_y = e[i].mask_y; g.mask_out = e[i].mask_out; g.ld_mask = e[i].ld_mask;
+        g.mask_act = e[i].mask_act; g.mask_zero_row0 = e[i].mask_zero_row0;
+    });
+    return run_plan(pl, trans_a, trans_b, gg, stream);
 }
 
 extern "C" int ggpm_gemm_ksegments(int trans_b, int M, int N, int nseg, const float* const* A, const int* lda, const float* const* B,
                         const int* ldb, const int* K, float* C, int ldc, int n_pad, const float* bias, int accumulate,
                         int act, int zero_row0, ggpm_stream_t stream) {
     GGPM_CLEAR_STALE_ERROR();
-    if (nseg <= 0 || nseg > GGPM_GEMM_MAX_GROUP || !A || !lda || !B || !ldb || !K || !C || M <= 0 || N <= 0 || n_pad < N ||
-        n_pad > ldc)
-        return GGPM_ERR_ARG;
+    if (!A || !lda || !B || !ldb || !K || !C) return GGPM_ERR_ARG;
     ggpm_gemm_call c{};
     c.entry = GGPM_GEMM_ENTRY_KSEGMENTS; c.trans_b = trans_b; c.M = M; c.N = N; c.count = nseg; c.ldc[0] = ldc; c.n_pad[0] = n_pad;
-    for (int i = 0; i < nseg; ++i) {
-        if (!A[i] || !B[i] || K[i] <= 0) return GGPM_ERR_ARG;
+    for (int i = 0; i < nseg && i < GGPM_GEMM_MAX_GROUP; ++i) {
+        if (!A[i] || !B[i]) return GGPM_ERR_ARG;
         c.K[i] = K[i]; c.lda[i] = lda[i]; c.ldb[i] = ldb[i]; c.base_a[i] = low4(A[i]); c.base_b[i] = low4(B[i]);
     }
     const GemmPlan pl = plan_segments(c);
@@ -1911,77 +1871,39 @@ extern "C" int ggpm_gemm_ksegments(int trans_b, int M, int N, int nseg, const fl
         }
         return GGPM_OK;
     }
-    GemmArgs g{};
-    g.M = M; g.N = N; g.K = K[0]; g.C = C; g.ldc = ldc; g.n_pad = n_pad;
-    g.bias = bias; g.accumulate = accumulate; g.act = act; g.zero_row0 = zero_row0;
-    g.k_chunk = pl.k_chunk[0];
-    g.nseg = nseg;
-    for (int i = 0; i < nseg; ++i) { g.segA[i] = A[i]; g.segB[i] = B[i]; g.seg_lda[i] = lda[i]; g.seg_ldb[i] = ldb[i]; g.segK[i] = K[i]; }
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid = plan_grid(pl);
-    if (pl.kernel == GGPM_GEMM_KERNEL_SEGS) {
-        for (int i = 0; i < nseg; ++i) g.seg_vec |= (pl.vec_a >> i & 1) << (2 * i) | (pl.vec_b >> i & 1) << (2 * i + 1);
-        if (trans_b) gemm_kernel_segs<true><<<grid, 256, 0, s>>>(g);
-        else gemm_kernel_segs<false><<<grid, 256, 0, s>>>(g);
-        GGPM_CHECK_LAUNCH();
-        return GGPM_OK;
-    }
-    g.A = A[0]; g.lda = lda[0]; g.B = B[0]; g.ldb = ldb[0]; g.vecA = g.vecB = 1;
-    if (pl.kernel == GGPM_GEMM_KERNEL_SMALL_V3) {
-        GemmGroupArgs gg;
-        for (int i = 0; i < GGPM_GEMM_MAX_GROUP; ++i) gg.p[i] = g;
-        launch_small(0, trans_b, gg, grid, 1, s);
-        GGPM_CHECK_LAUNCH();
-        return GGPM_OK;
-    }
-    if (trans_b) gemm_kernel_v2<false, true><<<grid, 256, 0, s>>>(g);
-    else gemm_kernel_v2<false, false><<<grid, 256, 0, s>>>(g);
-    GGPM_CHECK_LAUNCH();
-    return GGPM_OK;
+    // one problem (its plain operands: segment 0) whose K runs over the segments
+    const GgpmGemmProblem p = {A[0], lda[0], B[0], ldb[0], C, ldc, n_pad, bias, accumulate, act, zero_row0};
+    GemmGroupArgs gg;
+    fill_group(gg, pl, c, 1, &p, nullptr, [&](GemmArgs& g, int) {
+        g.nseg = nseg;
+        for (int i = 0; i < nseg; ++i) {
+            g.segA[i] = A[i]; g.segB[i] = B[i]; g.seg_lda[i] = lda[i]; g.seg_ldb[i] = ldb[i]; g.segK[i] = K[i];
+            g.seg_vec |= (pl.vec_a >> i & 1) << (2 * i) | (pl.vec_b >> i & 1) << (2 * i + 1);
+        }
+    });
+    return run_plan(pl, 0, trans_b, gg, stream);
 }
 
-// the internal entry points under C linkage (include/ggpm_hip.h), as the level weight gradients call them
-extern "C" int ggpm_gemm_tn_tall_grouped(int M, int N, int count, const ggpm_gemm_problem* problems, const int* K, float* ws,
-                                         size_t ws_bytes, int mode, ggpm_stream_t stream) {
-    if (mode < 0 || mode > 2) return GGPM_ERR_ARG;
-    return ggpm_gemm_tall_grouped(M, N, count, problems, K, ws, ws_bytes, stream, mode);
-}
-extern "C" int ggpm_gemm_tn_pair_grouped_c(int M, int N, int rows, int ld, int count, const ggpm_pair_problem* problems,
-                                           ggpm_stream_t stream) {
-    return ggpm_gemm_tn_pair_grouped(M, N, rows, ld, count, problems, stream);
-}
+// column sums of an fp32 or (a_bf16; lda in elements) bf16 matrix
 extern "C" int ggpm_colsum_dtype(const float* A, int lda, int M, int N, float* out, float* ws, int a_bf16, ggpm_stream_t stream) {
-    return ggpm_colsum_any(A, lda, M, N, out, ws, a_bf16 != 0, stream);
-}
-
-extern "C" int ggpm_colsum(const float* A, int lda, int M, int N, float* out, float* ws, ggpm_stream_t stream) {
-    return ggpm_colsum_any(A, lda, M, N, out, ws, false, stream);
-}
-
-int ggpm_colsum_any(const float* A, int lda, int M, int N, float* out, float* ws, bool a_bf16, ggpm_stream_t stream) {
     GGPM_CLEAR_STALE_ERROR();
     if (!A || !out || !ws || M <= 0 || N <= 0) return GGPM_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    if (a_bf16) {                                // (large stashes only: always the two-stage form)
-        int chunks = ggpm_ceil_div(M, 128);
-        if (chunks > CS_ROWS) chunks = CS_ROWS;
-        colsum_stage1<true><<<dim3(ggpm_ceil_div(N, 64), chunks), 256, 0, s>>>(A, lda, M, N, ws);
-        colsum_stage2<<<ggpm_ceil_div(N, 64), 256, 0, s>>>(ws, N, chunks, out);
-        GGPM_CHECK_LAUNCH();
-        return GGPM_OK;
+    const int col_blocks = ggpm_ceil_div(N, 64);
+    if (!a_bf16 && M <= CS_ONE_MAX) {            // (bf16: large stashes only, always the two-stage form)
+        colsum_one<<<col_blocks, 1024, 0, s>>>(A, lda, M, N, out);
+    } else {
+        const int chunks = min(ggpm_ceil_div(M, 128), CS_ROWS);      // >= 128 rows per chunk, at most CS_ROWS chunks
+        if (a_bf16) colsum_stage1<true><<<dim3(col_blocks, chunks), 256, 0, s>>>(A, lda, M, N, ws);
+        else colsum_stage1<false><<<dim3(col_blocks, chunks), 256, 0, s>>>(A, lda, M, N, ws);
+        colsum_stage2<<<col_blocks, 256, 0, s>>>(ws, N, chunks, out);
     }
-    if (M <= CS_ONE_MAX) {
-        colsum_one<<<ggpm_ceil_div(N, 64), 1024, 0, s>>>(A, lda, M, N, out);
-        GGPM_CHECK_LAUNCH();
-        return GGPM_OK;
-    }
-    int chunks = ggpm_ceil_div(M, 128);          // >= 128 rows per chunk, at most CS_ROWS chunks
-    if (chunks > CS_ROWS) chunks = CS_ROWS;
-    dim3 g1(ggpm_ceil_div(N, 64), chunks);
-    colsum_stage1<false><<<g1, 256, 0, s>>>(A, lda, M, N, ws);
-    colsum_stage2<<<ggpm_ceil_div(N, 64), 256, 0, s>>>(ws, N, chunks, out);
     GGPM_CHECK_LAUNCH();
     return GGPM_OK;
+}
+
+extern "C" int ggpm_colsum(const float* A, int lda, int M, int N, float* out, float* ws, ggpm_stream_t stream) {
+    return ggpm_colsum_dtype(A, lda, M, N, out, ws, 0, stream);
 }
 
 extern "C" int ggpm_act_backward(const float* dy, const float* y, int rows, int cols, int ld, int act,

@@ -224,13 +224,13 @@ inline int tall_weight_grads(int H, int Hp, int n_gate, const WgradTerm* gate, i
     int rc;
     if (KQ > 0) {
         if (dbu) {
-            rc = ggpm_colsum_any(q.D, Hp, KQ, H, dbu, csws, st16, stream);
+            rc = ggpm_colsum_dtype(q.D, Hp, KQ, H, dbu, csws, st16, stream);
             if (rc) return rc;
         }
-        rc = ggpm_gemm_tall_grouped(H, H, n_gate + 1, gp, Ks, skws, skbytes, stream, tall_mode);
+        rc = ggpm_gemm_tn_tall_grouped(H, H, n_gate + 1, gp, Ks, skws, skbytes, tall_mode, stream);
         if (rc) return rc;
     } else {
-        rc = ggpm_gemm_tall_grouped(H, H, n_gate, gp, Ks, skws, skbytes, stream, tall_mode);
+        rc = ggpm_gemm_tn_tall_grouped(H, H, n_gate, gp, Ks, skws, skbytes, tall_mode, stream);
         if (rc) return rc;
         for (int r = 0; r < H; ++r) (void)hipMemsetAsync(q.dW + (size_t)r * q.ld, 0, H * sizeof(float), (hipStream_t)stream);
         if (dbu) (void)hipMemsetAsync(dbu, 0, H * sizeof(float), (hipStream_t)stream);
@@ -281,7 +281,7 @@ inline int level_weight_grads(int E1, int H, int depth, int lo, bool with_slot0,
             for (int r = 0; r < H; ++r) (void)hipMemsetAsync(q.dW + (size_t)r * q.ld, 0, H * sizeof(float), (hipStream_t)stream);
             if (dbu) (void)hipMemsetAsync(dbu, 0, H * sizeof(float), (hipStream_t)stream);
         }
-        rc = ggpm_gemm_tn_pair_grouped(H, H, E1, Hp, n, pp, stream);
+        rc = ggpm_gemm_tn_pair_grouped_c(H, H, E1, Hp, n, pp, stream);
         if (rc) return rc;
         GGPM_CHECK_LAUNCH();
         return GGPM_OK;

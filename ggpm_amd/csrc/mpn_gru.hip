@@ -1541,7 +1541,7 @@ int ggpm_gru_bias_u_grad(int E1, int H, int depth, int lo, float* work, float* d
         return GGPM_OK;
     }
     const bool st16 = ggpm_opts_or_default(opts).gate_dtype == 1 && ggpm_bf16_storage_applies(E1, H);
-    return ggpm_colsum_any(ggpm_slot_ptr(DQ, lo, slot, st16), Hp, (depth - lo) * E1, H, dbu, csws, st16, stream);
+    return ggpm_colsum_dtype(ggpm_slot_ptr(DQ, lo, slot, st16), Hp, (depth - lo) * E1, H, dbu, csws, st16, stream);
 }
 
 namespace {

@@ -169,8 +169,10 @@ int ggpm_gemm_tn_pair_grouped_c(int M, int N, int rows, int ld, int count, const
 int ggpm_colsum_dtype(const float* A, int lda, int M, int N, float* out, float* ws, int a_bf16, ggpm_stream_t stream);
 
 /* Which kernel a product runs on.  Host only: no HIP call, nothing launched.  The entry points above and this query decide
- * through the same functions (csrc/gemm.hip: plan_gemm, plan_tall_group, plan_group, plan_group_splitk, plan_segments,
- * plan_pairs), so what it reports is what a call does; DESIGN.md ("The GEMM forms") lists the thresholds.
+ * through the same functions (csrc/gemm.hip: plan_gemm, plan_group, plan_group_splitk, plan_group_masked, plan_segments,
+ * plan_tall_group, plan_tn_bf16, plan_pairs, one per GGPM_GEMM_ENTRY_* in that order), and an entry point fills its kernel
+ * arguments and launches from the plan alone (fill_group, run_plan), so what the query reports is what a call does;
+ * DESIGN.md ("The GEMM forms") lists the thresholds.
  * `call` describes what the dispatchers look at; pointers appear as the low four bits of their address only.
  *   entry   -- GGPM_GEMM_ENTRY_*: the entry point; count: members (grouped entries) or segments (ksegments), 1 for gemm
  *   K[i]    -- per member (tall_grouped) or per segment (ksegments); the other entries read K[0] (pair_grouped: rows)
