@@ -137,6 +137,10 @@ SIGNATURES = {
     "ggpm_latent_decomp": (I, [P, P, P, I, I, I, c_double, P, P, P, P, P]),
     "ggpm_latent_decomp_backward": (I, [P, P, P, P, P, P, I, I, I, P, P, P, P]),
     "ggpm_latent_decomp_accumulate": (I, [P, P, I, I, I, P, P]),
+    # the mixture-of-Gaussians prior (csrc/latent_prior.hip)
+    "ggpm_mixture_logp": (I, [P, P, P, P, I, I, I, P, P, P, P, P, P]),
+    "ggpm_mixture_logp_backward": (I, [P, P, P, P, P, P, P, I, I, I, I, P, P, P, P, P]),
+    "ggpm_sample_mixture": (I, [P, P, P, I, P, I, I, I, P, ctypes.c_uint, ctypes.c_uint, P, P]),
     "ggpm_dropout": (I, [P, I, I, I, ctypes.c_float,ctypes.c_uint, ctypes.c_uint, I, P]),
     # property heads / latent search (csrc/property.hip): heads are ggpm_prop_head*, grads ggpm_prop_head_grads*
     "ggpm_property_heads_workspace_bytes": (c_size_t, [I, I, P, P]),

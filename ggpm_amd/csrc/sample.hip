@@ -2,23 +2,9 @@
 // Stateless and counter-based, as ggpm_dropout's masks are: every random word is a function of
 // (seed_lo, seed_hi, site, sample id, step, slot) alone -- not of the row's position in the launch, of the other rows or of
 // the batch size.  Plain stores, no atomics, no LDS: the three kernels are a few hundred lanes of work each.
-#include "common.h"
+#include "sample_stream.h"
 
 namespace {
-__device__ __forceinline__ unsigned int fmix32(unsigned int h) {
-    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-    return h;
-}
-
-// the 24-bit uniform m of (seed, site, id, step, slot)
-__device__ __forceinline__ unsigned int sample_m(unsigned int seed_lo, unsigned int seed_hi, unsigned int site,
-                                                 unsigned int id, unsigned int step, unsigned int slot) {
-    const unsigned int base = fmix32(fmix32(id * 0x9E3779B1u + seed_lo) ^ (seed_hi + site * 0x7F4A7C15u));
-    return fmix32(base + (step * 64u + slot) * 0x9E3779B1u) >> 8;
-}
-
-constexpr float TWO_M24 = 5.9604644775390625e-08f;       // 2^-24
-
 // draw[i] = m 2^-24 < p[i]: both sides are exact fp32 values, so p = 0 never draws 1 and p = 1 always does
 __global__ void __launch_bounds__(256) sample_topo_k(const float* __restrict__ p, const int32_t* __restrict__ bidx,
                                                      const int32_t* __restrict__ ids, int n, unsigned int step,
@@ -51,15 +37,6 @@ __global__ void __launch_bounds__(64) sample_order_k(const int32_t* __restrict__
         rank += (kj > key || (kj == key && j < q)) ? 1 : 0;
     }
     if (q < k) order[(size_t)r * k + rank] = q;
-}
-
-// Box-Muller from two words per element: sqrt(-2 log u1) cos(2 pi u2), u1 = (m0 + 1) 2^-24 in (0, 1], u2 = m1 2^-24
-__device__ __forceinline__ float sample_gauss(unsigned int seed_lo, unsigned int seed_hi, unsigned int site,
-                                              unsigned int id, unsigned int counter) {
-    const unsigned int m0 = sample_m(seed_lo, seed_hi, site, id, counter, 0u);
-    const unsigned int m1 = sample_m(seed_lo, seed_hi, site, id, counter, 1u);
-    const float u1 = (float)(m0 + 1u) * TWO_M24, u2 = (float)m1 * TWO_M24;
-    return sqrtf(-2.f * logf(u1)) * cospif(2.f * u2);
 }
 
 __global__ void __launch_bounds__(256) sample_normal_k(float* __restrict__ out, int rows, int cols, int ld,

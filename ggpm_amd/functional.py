@@ -418,6 +418,99 @@ def latent_decomp_accumulate(comps: torch.Tensor, dwkl_dim: torch.Tensor, acc: t
     return acc
 
 
+MIXTURE_MAX_C = 4096            # include/ggpm_hip.h GGPM_MIXTURE_MAX_C
+
+
+def _mixture_args(what: str, logits: torch.Tensor, means: torch.Tensor, log_vars: torch.Tensor, z: Optional[torch.Tensor] = None):
+    """the checks the entries of the mixture prior share (no device needed for the ValueErrors) -> C, L and, with z, R"""
+    _fp32(what, logits=logits, means=means, log_vars=log_vars, z=z)
+    if means.dim() != 2 or means.numel() == 0 or log_vars.shape != means.shape or logits.shape != means.shape[:1]:
+        raise ValueError("%s: logits %s / means %s / log_vars %s must be [C], [C, L] and [C, L]"
+                         % (what, tuple(logits.shape), tuple(means.shape), tuple(log_vars.shape)))
+    C, L = means.shape
+    if C > MIXTURE_MAX_C or L > FREE_BITS_MAX_L:
+        raise ValueError("%s: %d components over %d latent columns (at most %d and %d)" % (what, C, L, MIXTURE_MAX_C, FREE_BITS_MAX_L))
+    if z is None:
+        return C, L
+    if z.dim() != 2 or z.shape[0] == 0 or z.shape[1] != L:
+        raise ValueError("%s: z %s must be [R, %d]" % (what, tuple(z.shape), L))
+    R = z.shape[0]
+    if R * L >= 1 << 31 or R * C >= 1 << 31:
+        raise ValueError("%s: %d rows of %d columns and %d components (fewer than 2^31 elements each way)" % (what, R, L, C))
+    return C, L, R
+
+
+def mixture_logp(z: torch.Tensor, logits: torch.Tensor, means: torch.Tensor, log_vars: torch.Tensor, want_resp: bool = False,
+                 want_stash: bool = True):
+    """z [R, L], the mixture's logits [C], means and log_vars [C, L] -> (logp fp32 [R]: the log-density of every row, ratio
+    fp32 [R]: logp minus the standard normal's log-density, resp fp32 [R, C] or None: the responsibilities, comp_stash fp64
+    [R, C] and logp_stash fp64 [R] or None: what the backward reads) (csrc/latent_prior.hip)"""
+    what = "mixture_logp"
+    C, L, R = _mixture_args(what, logits, means, log_vars, z)
+    _need_gpu(z, logits, means, log_vars)
+    z, logits, means, log_vars = z.contiguous(), logits.contiguous(), means.contiguous(), log_vars.contiguous()
+    dev = z.device
+    logp, ratio = torch.empty(R, dtype=torch.float32, device=dev), torch.empty(R, dtype=torch.float32, device=dev)
+    resp = torch.empty(R, C, dtype=torch.float32, device=dev) if want_resp else None
+    comp_stash = torch.empty(R, C, dtype=torch.float64, device=dev) if want_stash else None
+    logp_stash = torch.empty(R, dtype=torch.float64, device=dev) if want_stash else None
+    _lib.check(_lib.load().ggpm_mixture_logp(_p(z), _p(logits), _p(means), _p(log_vars), R, C, L, _p(logp), _p(ratio), _p(resp),
+                                             _p(comp_stash), _p(logp_stash), _stream()), what)
+    return logp, ratio, resp, comp_stash, logp_stash
+
+
+def mixture_logp_backward(z: torch.Tensor, logits: torch.Tensor, means: torch.Tensor, log_vars: torch.Tensor,
+                          comp_stash: torch.Tensor, logp_stash: torch.Tensor, g: torch.Tensor, on_logp: bool,
+                          want_dz: bool = True, want_params: bool = True):
+    """The gradient of sum_r g[r] ratio[r] (``on_logp``: of sum_r g[r] logp[r]) of ``mixture_logp``; the stashes are the
+    forward's, of the same inputs, ``g`` fp32 [R] -> (dz [R, L] or None, dmeans [C, L], dlog_vars [C, L], dlogits [C] or three
+    None): one launch for dz, one for the parameters' three (csrc/latent_prior.hip)"""
+    what = "mixture_logp_backward"
+    C, L, R = _mixture_args(what, logits, means, log_vars, z)
+    _fp32(what, g=g)
+    if g.shape != (R,):
+        raise ValueError("%s: g %s for %d rows (fp32 [R])" % (what, tuple(g.shape), R))
+    for name, t, shape in (("comp_stash", comp_stash, (R, C)), ("logp_stash", logp_stash, (R,))):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.shape != shape or not t.is_contiguous():
+            raise ValueError("%s: %s must be the forward's contiguous fp64 %s tensor" % (what, name, list(shape)))
+    if not want_dz and not want_params:
+        raise ValueError("%s: neither dz nor the parameters' gradients are asked for" % what)
+    _need_gpu(z, logits, means, log_vars, comp_stash, logp_stash, g)
+    z, logits, means, log_vars, g = z.contiguous(), logits.contiguous(), means.contiguous(), log_vars.contiguous(), g.contiguous()
+    dz = torch.empty_like(z) if want_dz else None
+    dm, ds, da = (torch.empty_like(means), torch.empty_like(log_vars), torch.empty_like(logits)) if want_params else (None,) * 3
+    _lib.check(_lib.load().ggpm_mixture_logp_backward(_p(z), _p(logits), _p(means), _p(log_vars), _p(comp_stash), _p(logp_stash),
+                                                      _p(g), int(bool(on_logp)), R, C, L, _p(dz), _p(dm), _p(ds), _p(da),
+                                                      _stream()), what)
+    return dz, dm, ds, da
+
+
+def sample_mixture(logits: torch.Tensor, means: torch.Tensor, log_vars: torch.Tensor, rows: int, seed_lo: int, seed_hi: int,
+                   ids=None, want_components: bool = False):
+    """[rows, L] draws from the mixture on the seeded stream (csrc/latent_prior.hip): row r, keyed by ``ids[r]`` (default
+    ``arange``), takes its component from one uniform of site PRIOR_COMP and then m + exp(s / 2) n with ``sample_normal``'s
+    n for the same seed and id -> (out, the int32 [rows] components or None)"""
+    what = "sample_mixture"
+    C, L = _mixture_args(what, logits, means, log_vars)
+    rows = int(rows)
+    if rows < 1 or rows * L >= 1 << 31 or rows * C >= 1 << 31:
+        raise ValueError("%s: %d rows of %d columns and %d components (at least one row, fewer than 2^31 elements each way)"
+                         % (what, rows, L, C))
+    ids = torch.arange(rows, dtype=torch.int32) if ids is None else torch.as_tensor(ids).to(torch.int64).bitwise_and(
+        0xFFFFFFFF).to(torch.int32)
+    if ids.shape != (rows,):
+        raise ValueError("%s: %d ids for %d rows" % (what, ids.numel(), rows))
+    _need_gpu(logits, means, log_vars)
+    logits, means, log_vars = logits.contiguous(), means.contiguous(), log_vars.contiguous()
+    dev = means.device
+    out = torch.empty(rows, L, dtype=torch.float32, device=dev)
+    comp = torch.empty(rows, dtype=torch.int32, device=dev) if want_components else None
+    ids = ids.to(dev)
+    _lib.check(_lib.load().ggpm_sample_mixture(_p(logits), _p(means), _p(log_vars), C, _p(out), rows, L, L, _p(ids),
+                                               seed_lo & 0xFFFFFFFF, seed_hi & 0xFFFFFFFF, _p(comp), _stream()), what)
+    return out, comp
+
+
 def padded_hidden(H: int) -> int:
     return (H + 15) // 16 * 16
 

@@ -9,6 +9,7 @@ from . import functional as F_
 from .decoder_heads import check_no_dropout
 from .latent_heads import Plain, _LatentTerms, _encode_heads
 from .nnutils import make_cuda
+from .prior import check_prior
 
 
 MolLikelihood = namedtuple("MolLikelihood", ["parts", "kl", "elbo", "iwae", "z", "stats"])
@@ -65,6 +66,46 @@ class DecompositionObjective(_ExtendedObjective):
     ``beta``, ``gamma`` (the floats that weighed them) and ``dataset_size`` (the int used)."""
 
     _EXTRAS = ("mi", "tc", "dwkl", "alpha", "beta", "gamma", "dataset_size")
+
+
+class PriorObjective(_ExtendedObjective):
+    """The second value of ``bound_loss(prior=...)``: :class:`MolObjective`'s seven fields -- ``kl``, ``elbo`` and ``iwae`` under
+    the prior used -- and two attributes, ``log_prior_ratio`` (fp32 [K, B] on the device, detached: log p(z_k) - log N(z_k; 0, I)
+    of every draw) and ``kl_standard`` (fp32 [B]: the analytic KL to the standard normal, ``kl`` of the call without a
+    prior)."""
+
+    _EXTRAS = ("log_prior_ratio", "kl_standard")
+
+
+class PriorEstimatorObjective(EstimatorObjective):
+    """:class:`EstimatorObjective` of a call with ``prior=``: its attributes and :class:`PriorObjective`'s two."""
+
+    _EXTRAS = EstimatorObjective._EXTRAS + PriorObjective._EXTRAS
+
+
+class PriorLikelihood(MolLikelihood):
+    """What ``log_likelihood(prior=...)`` returns: :class:`MolLikelihood`'s six fields -- ``kl``, ``elbo`` and ``iwae`` under
+    the prior used -- and :class:`PriorObjective`'s two attributes."""
+
+    def __new__(cls, *fields, log_prior_ratio, kl_standard):
+        self = super().__new__(cls, *fields)
+        self.log_prior_ratio, self.kl_standard = log_prior_ratio, kl_standard
+        return self
+
+
+def _prior_terms(prior, z, kl, logpq, stats):
+    """What a prior changes in the latent terms (*A learned prior*): ratio [K, B] = log p(z) - log N(z; 0, I) from
+    ONE call on all K draws -> (ratio, logpq + ratio, kl - mean_k ratio: the analytic standard-normal KL corrected by a Monte
+    Carlo estimate of E_q[log p - log N]; detached).  ``stats`` gains 'prior_launches', which the backward adds to."""
+    stats["prior_launches"] = 0
+
+    def count(n):
+        stats["prior_launches"] += n
+
+    ratio = prior.log_ratio(z, count=count)
+    with torch.no_grad():
+        kl_eff = kl.detach() - ratio.detach().mean(dim=0)
+    return ratio, logpq + ratio, kl_eff
 
 
 ESTIMATORS = ("reparam", "stl", "dreg")
@@ -184,7 +225,8 @@ def _likelihood_atom_level(model, what, tensors, schedule, record_grad):
     return tensors, atom, dict(encoder_calls=1, atom_level_calls=int(atom is not None), decoder_passes=0)
 
 
-def log_likelihood(model, batch, n_samples=1, seed=None, sample_ids=None, eps=None, max_cls_size=None, schedule=None):
+def log_likelihood(model, batch, n_samples=1, seed=None, sample_ids=None, eps=None, max_cls_size=None, schedule=None,
+                   prior=None):
     """``log_likelihood`` of the four VAEs (*Per-molecule ELBO and the importance-weighted bound*).
 
     The encoder, ``R_mean`` / ``R_var`` and -- for the hierarchical decoder -- the atom level run once: under teacher
@@ -194,10 +236,14 @@ def log_likelihood(model, batch, n_samples=1, seed=None, sample_ids=None, eps=No
     ``k * L + column``: a molecule's draws do not depend on its batch, and the first K draws of a larger call are the
     K-sample call's.  ``eps=`` (a fp32 [K, B, L] tensor on the model's device, ``n_samples`` = K) replaces the stream; all
     zeros with K = 1 is the ``perturb_z=False`` latent.  ``max_cls_size``: see ``molecule_losses`` -- None is the training
-    convention (the parts then add up to the training loss x B), an int makes numbers comparable across batches."""
+    convention (the parts then add up to the training loss x B), an int makes numbers comparable across batches.
+    ``prior`` (None: the standard normal, or a :class:`~ggpm_amd.prior.MixturePrior` of the latent's width on the model's
+    device; DESIGN.md, *A learned prior*): ``kl``, ``elbo`` and ``iwae`` are then under that prior, and the result is a
+    :class:`PriorLikelihood`, which adds ``log_prior_ratio`` [K, B] and ``kl_standard`` [B]; one more launch."""
     from .greedy_decode import split_seed
     name, dec, dev, K, B, L, schedule, C = _likelihood_args(model, "log_likelihood", batch, n_samples, sample_ids, eps,
                                                             max_cls_size, schedule)
+    prior = check_prior("%s.log_likelihood" % name, prior, L, dev)
     mols, graphs, tensors, orders = batch[0], batch[1], batch[2], batch[3]
     with torch.no_grad():
         tensors, atom, stats = _likelihood_atom_level(model, "log_likelihood", tensors, schedule, record_grad=False)
@@ -212,8 +258,12 @@ def log_likelihood(model, batch, n_samples=1, seed=None, sample_ids=None, eps=No
             dec.molecule_losses(mols, (zk, zk, zk), graphs, tensors, orders, schedule=schedule, max_cls_size=C, atom=atom,
                                 out=parts[k])
             stats["decoder_passes"] += 1
-        elbo, iwae = F_.iwae_finish(parts, logpq, kl)
-    return MolLikelihood(parts, kl, elbo, iwae, z, stats)
+        if prior is None:
+            elbo, iwae = F_.iwae_finish(parts, logpq, kl)
+            return MolLikelihood(parts, kl, elbo, iwae, z, stats)
+        ratio, logpq_eff, kl_eff = _prior_terms(prior, z, kl, logpq, stats)
+        elbo, iwae = F_.iwae_finish(parts, logpq_eff, kl_eff)
+    return PriorLikelihood(parts, kl_eff, elbo, iwae, z, stats, log_prior_ratio=ratio, kl_standard=kl)
 
 
 class _Bound(Plain):
@@ -223,7 +273,7 @@ class _Bound(Plain):
     set before), forms the loss from the K decoder passes and wraps the seven common fields in its result type; ``extras`` in
     the last two are the further outputs of its node."""
 
-    def __init__(self, name, B, L, objective, beta, alpha, gamma, dataset_size, free_bits):
+    def __init__(self, name, B, L, objective, beta, alpha, gamma, dataset_size, free_bits, prior=None):
         if alpha is not None or gamma is not None or dataset_size is not None:
             raise ValueError("%s.bound_loss: alpha, gamma and dataset_size weigh the split KL of objective \"tcvae\"; objective %r "
                              "has none" % (name, objective))
@@ -233,6 +283,9 @@ class _Bound(Plain):
         if free_bits is not None:
             if objective != "elbo":
                 raise ValueError("%s.bound_loss: free_bits holds the KL of the ELBO; objective %r has none to hold" % (name, objective))
+            if prior is not None:
+                raise ValueError("%s.bound_loss: free_bits holds the per-column KL to the standard normal, which a prior= "
+                                 "replaces; a mixture's KL has no per-column form" % name)
             self.free_bits = float(free_bits)
             if not (0.0 <= self.free_bits < float("inf")):
                 raise ValueError("%s.bound_loss: free_bits %r (None, or a finite value >= 0)" % (name, self.free_bits))
@@ -283,9 +336,12 @@ class _TCVAE(_Bound):
     independent; its dz joins the decoder's before ggpm_latent_terms_backward -- the existing rsample chain -- and its
     dmean / dpre_var are added behind it, so the heads and their deferred weight gradients run once."""
 
-    def __init__(self, name, B, L, objective, beta, alpha, gamma, dataset_size, free_bits):
+    def __init__(self, name, B, L, objective, beta, alpha, gamma, dataset_size, free_bits, prior=None):
         if free_bits is not None:
             raise ValueError("%s.bound_loss: free_bits holds the KL of the ELBO; objective \"tcvae\" splits it instead" % name)
+        if prior is not None:
+            raise ValueError("%s.bound_loss: objective \"tcvae\" splits the KL to the standard normal (its dimension-wise part "
+                             "is against N(0, 1) column by column), which a prior= replaces" % name)
         if dataset_size is None:
             raise ValueError("%s.bound_loss: objective \"tcvae\" needs dataset_size, the number of molecules of the data set"
                              % name)
@@ -337,12 +393,12 @@ class _Path(_Bound):
 
     ESTIMATOR, DREG = "stl", False
 
-    def __init__(self, name, B, L, objective, beta, alpha, gamma, dataset_size, free_bits):
+    def __init__(self, name, B, L, objective, beta, alpha, gamma, dataset_size, free_bits, prior=None):
         if objective != "iwae":
             raise ValueError("%s.bound_loss: estimator %r changes the gradient of the importance-weighted bound; objective %r "
                              "has an analytic KL and no score term to remove (free_bits included)"
                              % (name, self.ESTIMATOR, objective))
-        super().__init__(name, B, L, objective, beta, alpha, gamma, dataset_size, free_bits)
+        super().__init__(name, B, L, objective, beta, alpha, gamma, dataset_size, free_bits, prior)
         self.s, self.ess, self.spent = None, None, False
 
     def backward(self, dz, dkl, dlogpq, dextras, mean, pv, eps, saved):
@@ -369,7 +425,8 @@ VARIANTS = {"plain": _Bound, "free_bits": _FreeBits, "tcvae": _TCVAE, "stl": _Pa
 
 
 def bound_loss(model, batch, n_samples=1, objective="elbo", beta=1.0, mol_weights=None, seed=None, sample_ids=None, eps=None,
-               max_cls_size=None, schedule=None, estimator="reparam", alpha=None, gamma=None, dataset_size=None, free_bits=None):
+               max_cls_size=None, schedule=None, estimator="reparam", prior=None, alpha=None, gamma=None, dataset_size=None,
+               free_bits=None):
     """``bound_loss`` of the four VAEs (*Training on the bound*) -> (loss, :class:`MolObjective`).
 
     With ``nll``, ``kl``, ``logpq`` and ``iwae`` as ``log_likelihood`` forms them, w the molecule weights and K = n_samples:
@@ -407,17 +464,28 @@ def bound_loss(model, batch, n_samples=1, objective="elbo", beta=1.0, mol_weight
     gradient by its normalised importance weight once more and is unbiased.  Both need ``objective="iwae"`` (the analytic
     KL of the ELBO has no score term to remove, so ``free_bits`` is excluded too); loss, ``info``'s seven fields and the
     decoder's gradients are those of ``"reparam"``, and the second value is an :class:`EstimatorObjective`, which adds
-    ``estimator``, ``sample_weights`` ([K, B]) and ``ess`` ([B])."""
+    ``estimator``, ``sample_weights`` ([K, B]) and ``ess`` ([B]).
+
+    ``prior`` (*A learned prior*): None is the standard normal, the call as it is without the argument.  A
+    :class:`~ggpm_amd.prior.MixturePrior` of the latent's width on the model's device replaces it: with
+    ratio[k, i] = log p(z_k) - log N(z_k; 0, I) from one call on all K draws,
+      logpq_eff = logpq + ratio          kl_eff[i] = kl[i] - (1/K) sum_k ratio[k, i]
+    stand where logpq and kl stand above, and the gradient also reaches the prior's three parameters and, through z, the
+    encoder (under "stl" / "dreg" as part of the path term, not of the log q held fixed).  ``free_bits`` and
+    ``objective="tcvae"`` are defined against the standard normal and raise with a prior.  The second value is then a
+    :class:`PriorObjective` (:class:`PriorEstimatorObjective` under "stl" / "dreg"), which adds ``log_prior_ratio`` ([K, B])
+    and ``kl_standard`` ([B]); ``stats`` gains 'prior_launches', 1 after the forward and at most 3 after the backward."""
     from .greedy_decode import split_seed
     name, dec, dev, K, B, L, schedule, C = _likelihood_args(model, "bound_loss", batch, n_samples, sample_ids, eps,
                                                             max_cls_size, schedule)
+    prior = check_prior("%s.bound_loss" % name, prior, L, dev)
     if objective not in F_.BOUND_OBJECTIVES and objective != "tcvae":
         raise ValueError("%s.bound_loss: objective %r (one of %s)" % (name, objective, sorted(F_.BOUND_OBJECTIVES) + ["tcvae"]))
     if estimator not in ESTIMATORS:
         raise ValueError("%s.bound_loss: estimator %r (one of %s)" % (name, estimator, ", ".join(ESTIMATORS)))
     reparam = "tcvae" if objective == "tcvae" else "plain" if free_bits is None else "free_bits"
     variant = VARIANTS[estimator if estimator != "reparam" else reparam](name, B, L, objective, beta, alpha, gamma, dataset_size,
-                                                                       free_bits)
+                                                                       free_bits, prior)
     w = None
     if mol_weights is not None:
         if isinstance(mol_weights, torch.Tensor):
@@ -445,11 +513,27 @@ def bound_loss(model, batch, n_samples=1, objective="elbo", beta=1.0, mol_weight
                                              atom=atom))
             stats["decoder_passes"] += 1
         parts = torch.stack(parts, dim=0)
-        loss = variant.loss(parts, logpq, kl, extras, tuple(model.parameters()))
+        if prior is None:
+            loss = variant.loss(parts, logpq, kl, extras, tuple(model.parameters()))
+            kl_eff = kl.detach()
+        else:
+            ratio, logpq, kl_eff = _prior_terms(prior, z, kl, logpq, stats)
+            # the ELBO's KL is beta kl_eff: the objective's beta kl and one weighted sum of ratio (formed before the objective,
+            # which stays the first node of the pass); the importance-weighted bound reads ratio inside logpq_eff
+            term = None
+            if objective == "elbo":
+                cw = (torch.ones(B, dtype=torch.float64, device=dev) if w is None else w.double()) * (-variant.beta / float(B * K))
+                term = (ratio.double() * cw[None, :]).sum().to(torch.float32)
+            loss = variant.loss(parts, logpq, kl, extras, tuple(model.parameters()))
+            loss = loss if term is None else loss + term
     with torch.no_grad():
-        elbo, iwae = F_.iwae_finish(parts.detach(), logpq.detach(), kl.detach())
+        elbo, iwae = F_.iwae_finish(parts.detach(), logpq.detach(), kl_eff)
     ones = w if w is not None else torch.ones(B, dtype=torch.float32, device=dev)
-    return loss, variant.info((parts.detach(), kl.detach(), elbo, iwae, z.detach(), ones, stats), extras)
+    info = variant.info((parts.detach(), kl_eff, elbo, iwae, z.detach(), ones, stats), extras)
+    if prior is not None:
+        cls = PriorEstimatorObjective if isinstance(info, EstimatorObjective) else PriorObjective
+        info = cls(*info, log_prior_ratio=ratio.detach(), kl_standard=kl.detach(), **getattr(info, "__dict__", {}))
+    return loss, info
 
 
 def _update_heads(model, what, batch):

@@ -18,7 +18,8 @@ from .latent_heads import _KLHead, _LatentTerms, _latent_heads, rsample  # noqa:
 from .nnutils import make_cuda
 from .objectives import (ESTIMATORS, DecompositionObjective, EstimatorObjective, FreeBitsObjective,  # noqa: F401
                          LatentAccumulator, LatentDecomposition, LatentDecompositionAccumulator, LatentStats, MolLikelihood,
-                         MolObjective, bound_loss, log_likelihood)
+                         MolObjective, PriorEstimatorObjective, PriorLikelihood, PriorObjective, bound_loss, log_likelihood)
+from .prior import MixturePrior, check_prior  # noqa: F401
 
 
 class HierEncoderVAE(nn.Module):
@@ -255,26 +256,29 @@ class _VAE(nn.Module):
     def rsample(self, z_vecs, perturb=True):
         return rsample(z_vecs, self.R_mean, self.R_var, perturb)
 
-    def sample(self, batch_size, greedy=True, seed=None, max_decode_step=150, beam=5, graph_batch_factory=None):
+    def sample(self, batch_size, greedy=True, seed=None, max_decode_step=150, beam=5, graph_batch_factory=None, prior=None):
         """New molecules from the prior (what reference ggpm/property_vae.py:35-37 intends): seeded standard-normal latents
-        drawn on the device, then ``decode`` or, with ``greedy=False``, ``decode_sampled`` at the same seed ->
-        (results, molecules)."""
-        return _sample(self, batch_size, greedy, seed, max_decode_step, beam, graph_batch_factory)
+        drawn on the device -- with ``prior`` (a :class:`MixturePrior`) its ``sample(batch_size, seed=seed)`` instead --,
+        then ``decode`` or, with ``greedy=False``, ``decode_sampled`` at the same seed -> (results, molecules)."""
+        return _sample(self, batch_size, greedy, seed, max_decode_step, beam, graph_batch_factory, prior)
 
-    def log_likelihood(self, batch, n_samples=1, seed=None, sample_ids=None, eps=None, max_cls_size=None, schedule=None):
+    def log_likelihood(self, batch, n_samples=1, seed=None, sample_ids=None, eps=None, max_cls_size=None, schedule=None,
+                       prior=None):
         """Per-molecule reconstruction terms, KL, ELBO and the ``n_samples``-sample importance-weighted bound of ``batch``
-        (the tuple ``self(*batch)`` takes) -> :class:`MolLikelihood`; forward only, see :func:`log_likelihood`."""
-        return log_likelihood(self, batch, n_samples, seed, sample_ids, eps, max_cls_size, schedule)
+        (the tuple ``self(*batch)`` takes), under the standard normal or ``prior`` -> :class:`MolLikelihood`; forward only,
+        see :func:`log_likelihood`."""
+        return log_likelihood(self, batch, n_samples, seed, sample_ids, eps, max_cls_size, schedule, prior)
 
     def bound_loss(self, batch, n_samples=1, objective="elbo", beta=1.0, mol_weights=None, seed=None, sample_ids=None,
-                   eps=None, max_cls_size=None, schedule=None, estimator="reparam", alpha=None, gamma=None, dataset_size=None,
-                   free_bits=None):
+                   eps=None, max_cls_size=None, schedule=None, estimator="reparam", prior=None, alpha=None, gamma=None,
+                   dataset_size=None, free_bits=None):
         """The ``n_samples``-sample ELBO (``objective="elbo"``), importance-weighted bound (``"iwae"``) or beta-TCVAE loss
         (``"tcvae"``, with ``alpha``, ``gamma`` and ``dataset_size``) of ``batch`` as a loss to train on, with optional
         per-molecule weights, for the ELBO a free-bits KL and for the importance-weighted bound a choice of gradient
-        estimator -> (loss, :class:`MolObjective`); see :func:`bound_loss`."""
+        estimator, and for the ELBO and the importance-weighted bound a learned ``prior`` -> (loss, :class:`MolObjective`);
+        see :func:`bound_loss`."""
         return bound_loss(self, batch, n_samples, objective, beta, mol_weights, seed, sample_ids, eps, max_cls_size, schedule,
-                          estimator, alpha, gamma, dataset_size, free_bits)
+                          estimator, prior, alpha, gamma, dataset_size, free_bits)
 
     def latent_decomposition_accumulator(self, dataset_size, n_samples=1, seed=None):
         """A :class:`LatentDecompositionAccumulator` of this model: the split of the KL into mutual information, total
@@ -408,11 +412,14 @@ class HierPropOptVAE(_PropOptVAE):
         self._build(args, HierMPNEncoder, HierMPNDecoder)
 
 
-def _sample(model, batch_size, greedy, seed, max_decode_step, beam, graph_batch_factory):
+def _sample(model, batch_size, greedy, seed, max_decode_step, beam, graph_batch_factory, prior=None):
     """``sample`` of the four VAEs: [batch_size, decoder.latent_size] latents -- the width ``reconstruct`` hands to
-    ``decode`` -- from ``functional.sample_normal`` (sample ids ``arange``), used as all three source vectors."""
+    ``decode`` -- from ``functional.sample_normal`` or, with a prior, from its ``sample`` (sample ids ``arange``), used as all
+    three source vectors."""
     from .greedy_decode import split_seed
     dec = model.decoder
+    dev = next(dec.parameters()).device
+    prior = check_prior("%s.sample" % type(model).__name__, prior, dec.latent_size, dev)
     factory = graph_batch_factory
     if factory is None:
         factory = _graph_batch_factory(model, getattr(model, "args", None))
@@ -421,7 +428,8 @@ def _sample(model, batch_size, greedy, seed, max_decode_step, beam, graph_batch_
         raise ValueError("%s.sample: batch_size %d" % (type(model).__name__, batch_size))
     lo, hi = split_seed(seed)
     with torch.no_grad():
-        z = F_.sample_normal(int(batch_size), dec.latent_size, lo, hi, device=next(dec.parameters()).device)
+        z = F_.sample_normal(int(batch_size), dec.latent_size, lo, hi, device=dev) if prior is None else \
+            prior.sample(int(batch_size), seed=lo | hi << 32)
         if greedy:
             return dec.decode(None, (z, z, z), greedy=True, max_decode_step=max_decode_step, beam=beam,
                               graph_batch_factory=factory)

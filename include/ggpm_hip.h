@@ -1067,6 +1067,48 @@ int ggpm_latent_decomp_backward(const float* z, const float* mean, const float* 
 int ggpm_latent_decomp_accumulate(const float* comps, const float* dwkl_dim, int K, int B, int L, double* acc,
                                   ggpm_stream_t stream);
 
+/* A learnable mixture-of-Gaussians prior (prior.MixturePrior and the prior= of log_likelihood, bound_loss and sample of the four
+ * VAEs; csrc/latent_prior.hip): p(z) = sum_c pi_c N(z; m_c, diag(exp(s_c))), pi = softmax(a), with logits a [C], means m
+ * [C x L] and log_vars s [C x L]; z [R x L] (R = K B for the objectives: one call covers all K draws); everything fp32 and
+ * dense.  The conventions of ggpm_latent_decomp: EVERYTHING below is formed in fp64 from the fp32 inputs (exp / log on
+ * double); fixed reduction orders, no atomics, bitwise reproducible; one rounding where a fp32 value is stored.
+ *     comp[r,c] = (a_c - logsumexp a) - 0.5 sum_j (log 2pi + s[c,j] + (z[r,j] - m[c,j])^2 exp(-s[c,j]))
+ *     lp[r]     = logsumexp_c comp[r,c]                logn[r] = -0.5 sum_j (log 2pi + z[r,j]^2)
+ * ggpm_mixture_logp (one launch, one workgroup of 4 waves per row: wave w takes the components w, w + 4, ... with its lanes
+ * striding j; comp[r, 0:C] stays in LDS):
+ *     logp[r] = lp      ratio[r] = lp - logn   (the difference formed in fp64)      resp[r,c] = exp(comp - lp)   (nullable)
+ *     comp_stash[r,c] = comp,  logp_stash[r] = lp   (double; both nullable for a forward-only call)
+ * ggpm_mixture_logp_backward (at most two launches): with g[r] the gradient that reached ratio[r] (on_logp = 0) or logp[r]
+ * (on_logp = 1), gamma[r,c] = exp(comp_stash - logp_stash), d = z[r,j] - m[c,j], iv = exp(-s[c,j]):
+ *     dz[r,j] = g_r (sum_c gamma (-d iv) + [on_logp = 0] z[r,j])        (row pass: one workgroup per row, gamma[r, 0:C] in LDS,
+ *                                                                        wave w takes the columns w, w + 4, ..., lanes stride c)
+ *     dmeans[c,j]    = sum_r g_r gamma d iv                             (column pass: one workgroup per component and 64
+ *     dlog_vars[c,j] = sum_r g_r gamma 0.5 (d^2 iv - 1)                  columns; wave w takes the rows w, w + 4, ... in that
+ *     dlogits[c]     = sum_r g_r (gamma - pi_c)                          order, the waves' partials are added in wave order)
+ * WRITTEN (not added).  dz is nullable (no row pass); dmeans, dlog_vars and dlogits are nullable as a group (all three or none:
+ * no column pass, for a frozen prior); all four null is refused.  The stashes are the forward's, of the same inputs.
+ * ggpm_sample_mixture (one launch, one wave per row): with u = m(PRIOR_COMP, ids[r], 0, 0) 2^-24 (the seeded stream of
+ * ggpm_sample_normal) and e_c = exp(a_c - max a), comp[r] (int32, nullable) = the smallest c whose prefix sum e_0 + ... + e_c,
+ * taken in index order, exceeds u * sum_c e_c -- the last component with e_c > 0 if rounding leaves none -- and
+ *     out[r, j] = fmaf(expf(0.5f s[c,j]), n[r,j], m[c,j]),  j < cols = L            (fp32)
+ * with n[r,j] exactly ggpm_sample_normal's value for (seed, ids[r], j); columns cols..ld of a row are left alone.  A draw
+ * depends on the seed, the id and the column only.
+ * 1 <= C <= GGPM_MIXTURE_MAX_C: the workgroup of each of the three keeps one fp64 value per component in LDS (comp, gamma,
+ * e: 32 KiB at the limit, half of what a workgroup may declare statically).  1 <= L <= GGPM_FREE_BITS_MAX_L, R >= 1,
+ * R * L < 2^31 and R * C < 2^31 (rows for R and cols for L in ggpm_sample_mixture, ld >= cols).  A null required pointer, a size
+ * outside these limits, on_logp other than 0 / 1 or a partly given gradient group returns GGPM_ERR_ARG; nothing is launched
+ * then. */
+#define GGPM_SITE_SAMPLE_PRIOR_COMP 260
+#define GGPM_MIXTURE_MAX_C 4096
+int ggpm_mixture_logp(const float* z, const float* logits, const float* means, const float* log_vars, int R, int C, int L,
+                      float* logp, float* ratio, float* resp, double* comp_stash, double* logp_stash, ggpm_stream_t stream);
+int ggpm_mixture_logp_backward(const float* z, const float* logits, const float* means, const float* log_vars,
+                               const double* comp_stash, const double* logp_stash, const float* g, int on_logp, int R, int C,
+                               int L, float* dz, float* dmeans, float* dlog_vars, float* dlogits, ggpm_stream_t stream);
+int ggpm_sample_mixture(const float* logits, const float* means, const float* log_vars, int C, float* out, int rows, int cols,
+                        int ld, const int32_t* ids, unsigned int seed_lo, unsigned int seed_hi, int32_t* comp,
+                        ggpm_stream_t stream);
+
 /* ------------------------------------------------------------------ whole-encoder drivers
  * HierMPNEncoder.forward (ggpm/encoder.py:140-157, with embed_graph/inter/tree/root :96-138) and its backward as ONE
  * call each: the same kernels the op-by-op host path issues, sequenced from C++ (GRU or LSTM message function).
