@@ -764,8 +764,6 @@ class HierMPNDecoder(ScoreHeads):
     # launches share the GPU instead of queueing behind each other; autograd runs a node's backward on the stream of its
     # forward, so the backward overlaps the encoder's backward the same way.  The caller passes the handle it gets to
     # ``forward(atom=)``: nothing is kept on the decoder.  _dev.ATOM_AHEAD = False switches it off.
-    _ATOM_STREAMS = {}
-
     def start_atom_level(self, schedule, tensors) -> Optional["AtomAhead"]:
         """-> the handle ``forward(..., schedule=schedule, atom=)`` joins, or None where the level is not issued ahead."""
         if schedule is None or not (_dev.ATOM_AHEAD and _dev.ATOM_DECODE and _dev.DECODER_BATCHED):
@@ -779,12 +777,9 @@ class HierMPNDecoder(ScoreHeads):
             return None
         D = schedule.to_device(dev)._dev
         main = torch.cuda.current_stream(dev)
-        side = self._ATOM_STREAMS.get(dev.index)
-        if side is None:
-            # high priority: this chain of small dependent launches is the step's critical path, the encoder beside it
-            # has slack -- where both have a kernel waiting for CUs, this one goes first (_dev.ATOM_PRIORITY = False: default priority)
-            prio = -1 if _dev.ATOM_PRIORITY else 0
-            side = self._ATOM_STREAMS[dev.index] = torch.cuda.Stream(device=dev, priority=prio)
+        # high priority: this chain of small dependent launches is the step's critical path, the encoder beside it
+        # has slack -- where both have a kernel waiting for CUs, this one goes first (_dev.ATOM_PRIORITY = False: default priority)
+        side = F_.helper_stream(dev, "atom", priority=-1 if _dev.ATOM_PRIORITY else 0)
         side.wait_stream(main)
         with torch.cuda.stream(side):       # issued now; the compact form's autograd node is created at the join, behind the encoder's
             return AtomAhead(schedule, self._atom_level(schedule, D, graph_tensors), side)

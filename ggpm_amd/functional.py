@@ -939,22 +939,12 @@ class _Linear(torch.autograd.Function):
 
         wref, bias = ctx.weight_ref, ctx.bias_ref
         leaf = (ctx.needs_input_grad[0] and (bias is None or ctx.needs_input_grad[1]) and can_publish(wref, bias))
-        if leaf and defer_wgrads_enabled():       # one contraction per parameter at the end of the pass (see _DEFER)
+        if leaf and defer_wgrads_enabled():       # one contraction per parameter at the end of the pass (see _DeferredGrads)
             _defer_linear(wref, bias, dpre, list(xs), Ks)
             return (None, None, None, None, None, None, *dxs)
         use_side = side_stream_enabled() and leaf
         if use_side:      # weight / bias gradients: second stream, straight into param.grad (as the level functions do)
-            main = torch.cuda.current_stream()
-            side = _side_stream(weight.device)
-            side.wait_stream(main)
-            for tns in (dpre, *xs):
-                tns.record_stream(side)
-            with torch.cuda.stream(side):
-                dW, db = param_grads()
-                _accumulate_grad(wref, dW, main)
-                if db is not None:
-                    _accumulate_grad(bias, db, main)
-            _join_later(main, side)
+            publish_aside(weight.device, (dpre, *xs), (wref, bias), param_grads)
             return (None, None, None, None, None, None, *dxs)
         dW, db = param_grads()
         return (dW, db, None, None, None, None, *dxs)
@@ -1077,7 +1067,7 @@ def embed_graph(fnode: torch.Tensor, fmess: torch.Tensor, atom_size: int, bond_t
 # both users go through these ops).  A stock torch op on the same leaf would have autograd's AccumulateGrad add to
 # ``.grad`` on the main stream while the second stream may still be writing it -- route such a use through
 # GGPM_SIDE_STREAM=0, which keeps every gradient on the main stream and inside autograd.
-_SIDE = {}
+_HELPER_STREAMS = {}        # (device index, kind in "second", "atom") -> every helper stream that writes gradients
 
 
 def side_stream_enabled() -> bool:
@@ -1085,26 +1075,26 @@ def side_stream_enabled() -> bool:
     return os.environ.get("GGPM_SIDE_STREAM", "1") != "0"
 
 
+def helper_stream(device, kind: str, priority: int = 0) -> torch.cuda.Stream:
+    """The package's one stream of `kind` on `device`: "second" (weight gradients, index transposes) or "atom" (the
+    decoder's atom level, decoder.start_atom_level).  Created on first use, with the priority of that first request
+    (ROCm offers priorities 0 and -1 only: nothing below normal)."""
+    assert kind in ("second", "atom"), kind
+    key = (device.index if device.index is not None else torch.cuda.current_device(), kind)
+    if key not in _HELPER_STREAMS:
+        _HELPER_STREAMS[key] = torch.cuda.Stream(device=device, priority=priority)
+    return _HELPER_STREAMS[key]
+
+
 def _side_stream(device) -> torch.cuda.Stream:
-    key = (device.index if device.index is not None else torch.cuda.current_device())
-    if key not in _SIDE:
-        _SIDE[key] = torch.cuda.Stream(device=device)      # (ROCm offers priorities 0 and -1 only: nothing below normal)
-    return _SIDE[key]
+    return helper_stream(device, "second")
 
 
 def writer_streams(device) -> list:
-    """Every helper stream of the package on `device` that writes parameter gradients: the second stream and the decoder's
-    atom-level stream (parallel.FlatGradSync._join_writers)."""
-    key = (device.index if device.index is not None else torch.cuda.current_device())
-    out = [_SIDE[key]] if key in _SIDE else []
-    try:
-        from .decoder import HierMPNDecoder
-        s = HierMPNDecoder._ATOM_STREAMS.get(key)
-        if s is not None:
-            out.append(s)
-    except Exception:
-        pass
-    return out
+    """Every helper stream of the package in use on `device` (parallel.FlatGradSync._join_writers orders its collective
+    behind each of them)."""
+    index = device.index if device.index is not None else torch.cuda.current_device()
+    return [_HELPER_STREAMS[index, kind] for kind in ("second", "atom") if (index, kind) in _HELPER_STREAMS]
 
 
 # A gradient tensor computed on a helper stream (second stream, atom-level stream) and then read on the main stream
@@ -1130,9 +1120,9 @@ def second_backward(node: str) -> RuntimeError:
 
 
 def _accumulate_grad(param: torch.Tensor, g: torch.Tensor, main: torch.cuda.Stream) -> None:
-    """param.grad (+)= g on the CURRENT (side) stream."""
+    """param.grad (+)= g on the CURRENT stream; `main` is the stream the gradient is consumed on (hand_to)."""
+    hand_to(g, main)
     if param.grad is None:
-        hand_to(g, main)
         param.grad = g
     else:
         param.grad.add_(g)
@@ -1140,6 +1130,24 @@ def _accumulate_grad(param: torch.Tensor, g: torch.Tensor, main: torch.cuda.Stre
 
 def _join_later(main: torch.cuda.Stream, side: torch.cuda.Stream) -> None:
     torch.autograd.Variable._execution_engine.queue_callback(lambda: main.wait_stream(side))
+
+
+def publish_aside(device, reads, params, grads_fn) -> None:
+    """Form parameter gradients on the second stream and add them into ``.grad`` there, from inside a backward node: the
+    second stream waits for what the current stream has been given so far, `reads` (the tensors `grads_fn` reads, allocated
+    on the current stream) are marked for it, `grads_fn()` -> one gradient or None per entry of `params` runs on it, and
+    the current stream re-joins at the end of the backward pass.  The caller decides whether its parameters are eligible
+    (side_stream_enabled, can_publish) and returns None for them to autograd."""
+    main = torch.cuda.current_stream()
+    side = _side_stream(device)
+    side.wait_stream(main)
+    for t in reads:
+        t.record_stream(side)
+    with torch.cuda.stream(side):
+        for param, g in zip(params, grads_fn()):
+            if g is not None:
+                _accumulate_grad(param, g, main)
+    _join_later(main, side)
 
 
 # ----------------------------------------------------------------------------- phase marks (dev instrumentation)
@@ -1163,7 +1171,8 @@ def mark(name: str) -> None:
 # backward pass ends (autograd engine callback) every parameter gets ONE contraction over the stacked rows of all its
 # visits -- dW = [dpre_1; dpre_2; ...]^T [x_1; x_2; ...], the same sum in a different order -- and other per-visit
 # parameter gradients (the message functions', the embedding tables') are summed by one stacked reduction each.
-_DEFER = {"linear": {}, "sum": {}, "gather": {}, "task": None, "stream": None, "early": None, "pending": []}
+# The queue is the one _DeferredGrads instance (_DEFERRED): nodes queue through _defer_linear / _defer_gather / _defer_sum;
+# only its end-of-backward flush moves queued gradients into ``.grad``, on the stream they were queued on.
 
 
 def defer_wgrads_enabled() -> bool:
@@ -1201,162 +1210,175 @@ def can_publish(*params) -> bool:
                                for p in params)
 
 
-def _defer_register() -> None:
-    """Queue the end-of-backward flush once per backward pass.  A pass is identified by the autograd engine's graph
-    task id: a pass that RAISED never ran its callbacks, so whatever it left queued is dropped when the next pass
-    registers (nothing sticky survives a failed backward)."""
-    task = torch._C._current_graph_task_id()
-    if _DEFER["task"] != task or task < 0:
-        _DEFER["linear"].clear()
-        _DEFER["sum"].clear()
-        _DEFER["gather"].clear()
-        _DEFER["pending"], _DEFER["early"] = [], None
-        _DEFER["task"] = task
-        _DEFER["stream"] = torch.cuda.current_stream()
-        torch.autograd.Variable._execution_engine.queue_callback(_defer_flush)
-
-
-def _defer_linear(weight, bias, dpre, xs, Ks) -> None:
-    _defer_register()
-    # keyed by the parameter AND the column split it was visited with: a Linear used with two different K splits in one
-    # pass gets one contraction per split (both land in the same .grad)
-    key = (id(weight), tuple(Ks), id(bias) if bias is not None else 0)
-    _DEFER["linear"].setdefault(key, (weight, bias, tuple(Ks), []))[3].append((dpre, xs))
-
-
-def _defer_gather(table, width, dout, idx) -> None:
-    _defer_register()
-    _DEFER["gather"].setdefault((id(table), int(width)), (table, width, []))[2].append((dout, idx))
-
-
-def _defer_sum(param, grad) -> None:
-    """param.grad += grad, summed with the pass's other contributions to the same parameter by ONE reduction at the end."""
-    if grad is None:
-        return
-    _defer_register()
-    _DEFER["sum"].setdefault(id(param), (param, []))[1].append(grad)
-
-
-def _add_to_grad(param, g) -> None:
-    if param.grad is None:
-        param.grad = g
-    else:
-        param.grad.add_(g)
-
-
-def _defer_flush(side: Optional[torch.cuda.Stream] = None) -> None:
-    """Form the queued parameter gradients.  ``side`` = None: the end-of-backward callback, on the stream the entries
-    were queued on.  ``side`` given (flush_deferred_early): on that stream, ordered behind everything the queueing
-    stream has been given so far; the queueing stream re-joins at the end of the backward pass."""
-    lin, sums, gath = dict(_DEFER["linear"]), dict(_DEFER["sum"]), dict(_DEFER["gather"])
-    _DEFER["linear"].clear()
-    _DEFER["sum"].clear()
-    _DEFER["gather"].clear()
-    main = _DEFER["stream"]
-    if side is None:
-        _DEFER["task"] = None
-        mark("bwd: end-of-pass flush starts")
-        if main is not None and _DEFER["early"] is not None:
-            # what the early flush computed on the second stream is handed to .grad HERE, on the queueing stream, once
-            # that stream is ordered behind it: every mutation of .grad stays on one stream, whatever order the engine
-            # ran the nodes in (autograd's own AccumulateGrad for tied / shared parameters included)
-            main.wait_stream(_DEFER["early"])
-            _DEFER["early"] = None
-            with torch.cuda.stream(main):
-                for param, g in _DEFER["pending"]:
-                    _add_to_grad(param, g)
-        _DEFER["pending"] = []
-    if not (lin or sums or gath) or main is None:
-        return
-    stream = main
-    if side is not None:
-        side.wait_stream(main)
-        stream = side
-        _DEFER["early"] = side
-
-    def use(t):                            # queued on one stream, read on another: keep the allocator from recycling it early
-        if side is not None and isinstance(t, torch.Tensor) and t.is_cuda:
-            t.record_stream(stream)
-        return t
-
-    def publish(param, g):
-        if side is not None:               # computed early: published by the end-of-backward flush (see above)
-            hand_to(g, main)
-            _DEFER["pending"].append((param, g))
+def _linear_grads(entries, use, target):
+    """Every queued Linear's weight gradient (one contraction per K segment) and bias gradient in ONE library call
+    (ggpm_linear_wgrads_batch: the same launches in the same order as ~60 separate gemm / colsum calls)."""
+    items, keep, out, n_max, ws_max = [], [], [], 0, 0
+    lib = _lib.load()
+    for weight, bias, Ks, visits in entries:
+        N = weight.shape[0]
+        if len(visits) == 1:
+            dpre, xs = use(visits[0][0]), [use(x) for x in visits[0][1]]
         else:
-            _add_to_grad(param, g)
-
-    def target(param):
-        """Where a parameter's gradient is formed: its slice of the flat gradient buffer (parallel.FlatGradSync) when it has one
-        and nothing has been written there in this pass -- the optimizer / all-reduce side then finds it in place (no pack copy:
-        one multi-tensor launch right in front of the optimizer, and ~35 `.grad` re-pointings, less per step) -- else a fresh
-        tensor.  The first contribution of a pass writes, later ones are added (`_add_to_grad`)."""
-        v = grad_view(param)
-        if v is not None and id(param) not in taken:
-            taken.add(id(param))
-            return v
-        return torch.empty_like(param)
-
-    taken = set(id(q) for q, _ in _DEFER["pending"])
-    with torch.cuda.stream(stream):
-        # every Linear's weight gradient (one contraction per K segment) and bias gradient in ONE library call
-        # (ggpm_linear_wgrads_batch: the same launches in the same order as ~60 separate gemm / colsum calls)
-        items, keep, out, n_max, ws_max = [], [], [], 0, 0
-        lib = _lib.load()
-        for weight, bias, Ks, visits in lin.values():
-            N = weight.shape[0]
-            if len(visits) == 1:
-                dpre, xs = use(visits[0][0]), [use(x) for x in visits[0][1]]
-            else:
-                dpre = torch.cat([use(v[0]) for v in visits], dim=0)
-                xs = [torch.cat([use(v[1][i])[:, :K] for v in visits], dim=0) for i, K in enumerate(Ks)]
-            M = dpre.shape[0]
-            dW = target(weight)
-            db = target(bias) if bias is not None else None
-            o = 0
-            for i, (x, K) in enumerate(zip(xs, Ks)):
-                items.append((dpre.data_ptr(), _ld(dpre), x.data_ptr(), _ld(x), dW.data_ptr() + 4 * o, dW.stride(0),
-                              db.data_ptr() if (db is not None and i == 0) else 0, M, N, K))
-                ws_max = max(ws_max, int(lib.ggpm_gemm_workspace_bytes(N, K, M)))
-                o += K
-            n_max = max(n_max, N)
-            keep.append((dpre, xs, dW, db))
-            out.append((weight, dW))
-            if db is not None:
-                out.append((bias, db))
-        if items:
-            arr = _lib.array_type(WgradItem, len(items))(*[WgradItem(*it) for it in items])
-            dev = keep[0][0].device
-            ws = torch.empty(ws_max // 4, dtype=torch.float32, device=dev) if ws_max else None
-            csws = torch.empty(256 * n_max, dtype=torch.float32, device=dev)
-            _lib.check(lib.ggpm_linear_wgrads_batch(len(items), ctypes.addressof(arr), _p(ws), ws_max, _p(csws),
-                                                    _stream()), "linear_wgrads_batch")
-        # published only now, behind the launch that writes them: an add into an existing .grad (gradient accumulation,
-        # zero_grad(set_to_none=False), a Linear queued under two K splits) is enqueued after dW / db hold their values
-        for param, g in out:
-            publish(param, g)
-        for param, grads in sums.values():
-            publish(param, use(grads[0]) if len(grads) == 1 else torch.stack([use(g) for g in grads], dim=0).sum(dim=0))
-        for table, width, visits in gath.values():       # embedding tables: d(table)[id] = sum of the rows that used id
-            dout = use(visits[0][0]) if len(visits) == 1 else torch.cat([use(v[0]) for v in visits], dim=0)
-            idx = use(visits[0][1]) if len(visits) == 1 else torch.cat([use(v[1]).reshape(-1) for v in visits], dim=0)
-            csrT = csr_from_index(idx.reshape(-1), ncols=table.shape[0]).T
-            dtable = target(table)
-            _segment_sum_raw(dout, csrT, width, dtable)
-            publish(table, dtable)
+            dpre = torch.cat([use(v[0]) for v in visits], dim=0)
+            xs = [torch.cat([use(v[1][i])[:, :K] for v in visits], dim=0) for i, K in enumerate(Ks)]
+        M = dpre.shape[0]
+        dW = target(weight)
+        db = target(bias) if bias is not None else None
+        o = 0
+        for i, (x, K) in enumerate(zip(xs, Ks)):
+            items.append((dpre.data_ptr(), _ld(dpre), x.data_ptr(), _ld(x), dW.data_ptr() + 4 * o, dW.stride(0),
+                          db.data_ptr() if (db is not None and i == 0) else 0, M, N, K))
+            ws_max = max(ws_max, int(lib.ggpm_gemm_workspace_bytes(N, K, M)))
+            o += K
+        n_max = max(n_max, N)
+        keep.append((dpre, xs, dW, db))
+        out.append((weight, dW))
+        if db is not None:
+            out.append((bias, db))
+    if items:
+        arr = _lib.array_type(WgradItem, len(items))(*[WgradItem(*it) for it in items])
+        dev = keep[0][0].device
+        ws = torch.empty(ws_max // 4, dtype=torch.float32, device=dev) if ws_max else None
+        csws = torch.empty(256 * n_max, dtype=torch.float32, device=dev)
+        _lib.check(lib.ggpm_linear_wgrads_batch(len(items), ctypes.addressof(arr), _p(ws), ws_max, _p(csws),
+                                                _stream()), "linear_wgrads_batch")
+    # handed out only now, behind the launch that writes them: an add into an existing .grad (gradient accumulation,
+    # zero_grad(set_to_none=False), a Linear queued under two K splits) is enqueued after dW / db hold their values
+    return out
 
 
-def flush_deferred_early() -> None:
-    """Called from inside a backward pass at a point after which only nodes WITHOUT deferred gradients have much left to
-    do (the decoder's atom level and the encoder, once the heads and the tree-side levels have run): the queued
-    contractions start now on the second stream, beside that work, instead of behind it.  Whatever is queued later still
-    goes through the end-of-backward flush.  _dev.DEFER_EARLY = False switches it off."""
-    if not _dev.DEFER_EARLY or not side_stream_enabled():
-        return
-    main = _DEFER["stream"]
-    if main is None or _DEFER["task"] is None or _DEFER["task"] != torch._C._current_graph_task_id():
-        return
-    _defer_flush(side=_side_stream(main.device))       # (the end-of-backward callback stays registered: it publishes)
+def _sum_grads(entries, use, target):
+    """One stacked reduction per parameter over its per-visit gradients (lazily: each is published before the next is formed)."""
+    for param, grads in entries:
+        yield param, use(grads[0]) if len(grads) == 1 else torch.stack([use(g) for g in grads], dim=0).sum(dim=0)
+
+
+def _gather_grads(entries, use, target):
+    """Embedding tables: d(table)[id] = sum of the rows that used id, one scatter per table (one at a time, as the sums)."""
+    for table, width, visits in entries:
+        dout = use(visits[0][0]) if len(visits) == 1 else torch.cat([use(v[0]) for v in visits], dim=0)
+        idx = use(visits[0][1]) if len(visits) == 1 else torch.cat([use(v[1]).reshape(-1) for v in visits], dim=0)
+        csrT = csr_from_index(idx.reshape(-1), ncols=table.shape[0]).T
+        dtable = target(table)
+        _segment_sum_raw(dout, csrT, width, dtable)
+        yield table, dtable
+
+
+class _DeferredGrads:
+    """The deferred parameter gradients of ONE backward pass.  ``linear`` / ``sum`` / ``gather``: what is queued, by key;
+    ``task``: the pass (autograd graph-task id) the end-of-backward flush is registered for, ``stream``: the stream its
+    entries are queued on; ``early``: the other stream that wrote entries or formed ``pending``, the (param, grad) pairs
+    of an early flush that wait for the end of the pass."""
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self) -> None:
+        """The one place the per-pass state is cleared."""
+        self.linear, self.sum, self.gather = {}, {}, {}
+        self.task = self.stream = self.early = None
+        self.pending = []
+
+    def _begin(self) -> None:
+        """Queue the end-of-backward flush once per backward pass.  A pass is identified by the autograd engine's graph
+        task id: a pass that RAISED never ran its callbacks, so whatever it left queued is dropped when the next pass
+        registers (nothing sticky survives a failed backward)."""
+        task = torch._C._current_graph_task_id()
+        if self.task != task or task < 0:
+            self.reset()
+            self.task = task
+            self.stream = torch.cuda.current_stream()
+            torch.autograd.Variable._execution_engine.queue_callback(self.flush)
+
+    def add_linear(self, weight, bias, dpre, xs, Ks) -> None:
+        self._begin()
+        # keyed by the parameter AND the column split it was visited with: a Linear used with two different K splits in one
+        # pass gets one contraction per split (both land in the same .grad)
+        key = (id(weight), tuple(Ks), id(bias) if bias is not None else 0)
+        self.linear.setdefault(key, (weight, bias, tuple(Ks), []))[3].append((dpre, xs))
+
+    def add_gather(self, table, width, dout, idx) -> None:
+        self._begin()
+        self.gather.setdefault((id(table), int(width)), (table, width, []))[2].append((dout, idx))
+
+    def add_sum(self, param, grad) -> None:
+        """param.grad += grad, summed with the pass's other contributions to the same parameter by ONE reduction at the end."""
+        if grad is None:
+            return
+        self._begin()
+        self.sum.setdefault(id(param), (param, []))[1].append(grad)
+
+    def written_on(self, side: torch.cuda.Stream) -> None:
+        """The entries queued so far were produced on `side`: the end-of-pass flush waits for it before it reads them."""
+        self.early = side
+
+    def flush(self, side: Optional[torch.cuda.Stream] = None) -> None:
+        """Form the queued parameter gradients.  ``side`` = None: the end-of-backward callback, on the stream the entries
+        were queued on.  ``side`` given (flush_early): on that stream, ordered behind everything the queueing stream has
+        been given so far; the queueing stream re-joins at the end of the backward pass."""
+        queues, main = (self.linear, self.sum, self.gather), self.stream
+        if side is None:
+            early, pending = self.early, self.pending
+            self.reset()
+            mark("bwd: end-of-pass flush starts")
+            if main is not None and early is not None:
+                # what the early flush computed on the second stream is handed to .grad HERE, on the queueing stream, once
+                # that stream is ordered behind it: every mutation of .grad stays on one stream, whatever order the engine
+                # ran the nodes in (autograd's own AccumulateGrad for tied / shared parameters included)
+                main.wait_stream(early)
+                with torch.cuda.stream(main):
+                    for param, g in pending:
+                        _accumulate_grad(param, g, main)
+        else:
+            self.linear, self.sum, self.gather = {}, {}, {}
+        if not any(queues) or main is None:
+            return
+        stream = main
+        if side is not None:
+            side.wait_stream(main)
+            stream = self.early = side
+
+        def use(t):                        # queued on one stream, read on another: keep the allocator from recycling it early
+            if side is not None and isinstance(t, torch.Tensor) and t.is_cuda:
+                t.record_stream(stream)
+            return t
+
+        def target(param):
+            """Where a parameter's gradient is formed: its slice of the flat gradient buffer (parallel.FlatGradSync) when it has
+            one and nothing has been written there in this pass -- the optimizer / all-reduce side then finds it in place (no
+            pack copy: one multi-tensor launch right in front of the optimizer, and ~35 `.grad` re-pointings, less per step) --
+            else a fresh tensor.  The first contribution of a pass writes, later ones are added (`_accumulate_grad`)."""
+            v = grad_view(param)
+            if v is not None and id(param) not in taken:
+                taken.add(id(param))
+                return v
+            return torch.empty_like(param)
+
+        taken = set(id(q) for q, _ in self.pending)
+        with torch.cuda.stream(stream):
+            for step, queue in zip((_linear_grads, _sum_grads, _gather_grads), queues):
+                for param, g in step(queue.values(), use, target):
+                    if side is not None:   # computed early: published by the end-of-backward flush (see above)
+                        self.pending.append((param, g))
+                    else:
+                        _accumulate_grad(param, g, main)
+
+    def flush_early(self) -> None:
+        """Called from inside a backward pass at a point after which only nodes WITHOUT deferred gradients have much left to
+        do (the decoder's atom level and the encoder, once the heads and the tree-side levels have run): the queued
+        contractions start now on the second stream, beside that work, instead of behind it.  Whatever is queued later still
+        goes through the end-of-backward flush.  _dev.DEFER_EARLY = False switches it off."""
+        if not _dev.DEFER_EARLY or not side_stream_enabled():
+            return
+        if self.stream is None or self.task is None or self.task != torch._C._current_graph_task_id():
+            return
+        self.flush(side=_side_stream(self.stream.device))   # (the end-of-backward callback stays registered: it publishes)
+
+
+_DEFERRED = _DeferredGrads()
+_defer_linear, _defer_gather, _defer_sum = _DEFERRED.add_linear, _DEFERRED.add_gather, _DEFERRED.add_sum
+flush_deferred_early = _DEFERRED.flush_early
 
 
 # ----------------------------------------------------------------------------- GRU / LSTM cell adapters
@@ -1641,15 +1663,7 @@ def _level_backward(ctx, dHD, name: str):
         return cell.grads(bufs, hid, cell.input_half_grads(dX, x, _ld(x), E1, bufs))
 
     if use_side:
-        main = torch.cuda.current_stream()
-        side = _side_stream(x.device)
-        side.wait_stream(main)
-        for tns in (work, dX, Hs, St, x, *bufs, *hid):
-            tns.record_stream(side)
-        with torch.cuda.stream(side):
-            for prm, g in zip(cell.params, weight_grads()):
-                _accumulate_grad(prm, g, main)
-        _join_later(main, side)
+        publish_aside(x.device, (work, dX, Hs, St, x, *bufs, *hid), cell.params, weight_grads)
         return (dx,) + (None,) * (5 + len(cell.params))
     return (dx, None, None, None, None, None, *weight_grads())
 
@@ -1776,7 +1790,7 @@ def _sparse_backward(ctx, dH, dC, want_dx: bool, name: str):
     pgrads = cell.grads(bufs, hid, cell.input_half_grads(dXs, x_sub, _ld(x_sub), ms, bufs))
     dx = cell.input_grad(dXs, x_sub, ms) if want_dx else None
     if defer_wgrads_enabled() and can_publish(*cell.params):
-        for q, g in zip(cell.params, pgrads):         # summed once per parameter at the end of the pass (see _DEFER)
+        for q, g in zip(cell.params, pgrads):         # summed once per parameter at the end of the pass (see _DeferredGrads)
             _defer_sum(q, g)
         pgrads = (None,) * len(pgrads)
     return dHin[:, :H], (dCin[:, :H] if lstm else None), dx, pgrads

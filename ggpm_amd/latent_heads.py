@@ -74,15 +74,7 @@ def _latent_heads_backward(ctx, z_vecs, Wm, Wv, dmean, dpv):
         return dWm, F_.colsum(dmean, B, L), dWv, F_.colsum(dpv, B, L)
 
     if F_.side_stream_enabled() and F_.can_publish(*ctx.params) and all(ctx.needs_input_grad[1:5]):
-        main = torch.cuda.current_stream()
-        side = F_._side_stream(z_vecs.device)
-        side.wait_stream(main)
-        for t in (dmean, dpv, z_vecs):
-            t.record_stream(side)
-        with torch.cuda.stream(side):
-            for q, g in zip(ctx.params, param_grads()):
-                F_._accumulate_grad(q, g, main)
-        F_._join_later(main, side)
+        F_.publish_aside(z_vecs.device, (dmean, dpv, z_vecs), ctx.params, param_grads)
         return dx, None, None, None, None
     dWm, dbm, dWv, dbv = param_grads()
     return dx, dWm, dbm, dWv, dbv

@@ -118,7 +118,7 @@ class FlatGradSync:
         # there and ggpm_amd.optim.FlatAdam reads it as the gradient of its single flat parameter
         self.keep_flat = keep_flat
         self._early_work = None
-        # gradients this package forms itself (functional._defer_flush) are written straight into their slice of the
+        # gradients this package forms itself (functional._DeferredGrads.flush) are written straight into their slice of the
         # buffer: pack() then has nothing to copy for them
         # (not the encoder's: the C++ backward driver OVERWRITES its slices -- a tied embedding's decoder-side contribution
         # must be ADDED behind it, which the fresh-tensor path does).  A sync built later over the same parameters replaces

@@ -354,7 +354,7 @@ class _TreeLevelNative(torch.autograd.Function):
         work = torch.empty((wb + 3) // 4, **f32)
         # the level's parameter gradients on the second stream (csrc/tree_level.hip): what flows on -- d_lower, on the
         # attachment level the input of the atom level's 2.8 ms backward chain -- is then not queued behind ~145 us of
-        # contractions per level.  The deferred-gradient queue (functional._DEFER) sums them: on that same stream when it is
+        # contractions per level.  The deferred-gradient queue (functional._DEFERRED) sums them: on that same stream when it is
         # flushed early, on the main stream once it has waited for this one ("early") at the end of the pass.
         side = F_._side_stream(dev) if (F_.side_stream_enabled() and _dev.TREE_WGRADS_ASIDE) else None
         _lib.check(lib.ggpm_tree_level_backward(ctypes.byref(L), ctypes.byref(V), F_._p(d_node), F_._p(d_hid), ctypes.byref(g),
@@ -367,7 +367,7 @@ class _TreeLevelNative(torch.autograd.Function):
         for q, gr in zip(rp, cell.grads(dgw, (None, dUr, None, dbu), dgb)):
             F_._defer_sum(q, gr)
         if side is not None:
-            F_._DEFER["early"] = side      # the end-of-pass flush waits for the second stream before it reads what was queued
+            F_._DEFERRED.written_on(side)  # the end-of-pass flush waits for the second stream before it reads what was queued
         if W is not None:
             F_._defer_linear(W, b, dpre_w, [finput, lower], (He, H))
         F_._defer_linear(Wo, bo, dpre_o, [hnode, nei], (H, H))

@@ -130,7 +130,7 @@ class _FlushEarly(torch.autograd.Function):
     def backward(ctx, dx):
         from ggpm_amd import functional as F_
         F_.flush_deferred_early()
-        _FlushEarly.seen.append(F_._DEFER["early"] is not None)
+        _FlushEarly.seen.append(F_._DEFERRED.early is not None)
         return dx
 
 

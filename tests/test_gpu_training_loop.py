@@ -292,7 +292,7 @@ def test_a_failed_backward_does_not_poison_the_next_steps(monkeypatch):
         scale = float(w.abs().max()) + 1e-12
         assert float((f - w).abs().max()) <= 1e-5 * scale
         assert torch.equal(a, f) and torch.equal(t3, f)            # nothing lost, nothing doubled
-    assert not F_._DEFER["linear"] and not F_._DEFER["gather"] and not F_._DEFER["sum"]
+    assert not F_._DEFERRED.linear and not F_._DEFERRED.gather and not F_._DEFERRED.sum
 
 
 def test_a_parameter_with_a_hook_gets_its_gradient_through_autograd():

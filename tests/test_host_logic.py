@@ -48,10 +48,19 @@ def test_tree_chain_length_is_bounded_by_the_motif_count():
 
 
 class _FakeStream:
+    """Stands in for a HIP stream: remembers what it was created with and what it was told to wait for; ``log`` (shared)
+    keeps the order of the waits among whatever else a test appends."""
     device = torch.device("cpu")
+    log = []
+
+    def __init__(self, name="main", device=None, priority=0):
+        self.name, self.priority, self.waited = name, priority, []
+        if device is not None:
+            self.device = device
 
     def wait_stream(self, other):
-        pass
+        self.waited.append(other)
+        _FakeStream.log.append(("wait", self, other))
 
 
 class _Visit(torch.autograd.Function):
@@ -74,15 +83,13 @@ class _Visit(torch.autograd.Function):
 
 @pytest.fixture
 def fake_streams(monkeypatch):
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: _FakeStream())
+    main = _FakeStream()
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: main)
     monkeypatch.setattr(torch.cuda, "stream", lambda s: contextlib.nullcontext())
-    for k in ("linear", "sum", "gather"):
-        F_._DEFER[k].clear()
-    F_._DEFER.update(task=None, stream=None, early=None, pending=[])
-    yield
-    for k in ("linear", "sum", "gather"):
-        F_._DEFER[k].clear()
-    F_._DEFER.update(task=None, stream=None, early=None, pending=[])
+    del _FakeStream.log[:]
+    F_._DEFERRED.reset()
+    yield main
+    F_._DEFERRED.reset()
 
 
 def test_deferred_gradients_survive_a_failed_backward(fake_streams):
@@ -98,15 +105,15 @@ def test_deferred_gradients_survive_a_failed_backward(fake_streams):
 
     step(False)
     want = p.grad.clone()
-    assert want.abs().sum() > 0 and not F_._DEFER["sum"] and F_._DEFER["task"] is None
+    assert want.abs().sum() > 0 and not F_._DEFERRED.sum and F_._DEFERRED.task is None
     with pytest.raises(RuntimeError, match="injected"):
         step(True)
-    assert F_._DEFER["sum"], "the failed pass left its visit queued (the engine skipped the callback)"
-    leftovers = F_._DEFER["task"]
+    assert F_._DEFERRED.sum, "the failed pass left its visit queued (the engine skipped the callback)"
+    leftovers = F_._DEFERRED.task
     assert leftovers is not None
     step(False)                                                    # a normal step after the failure
     assert torch.equal(p.grad, want), (p.grad, want)               # not doubled by the failed pass's leftovers, not missing
-    assert not F_._DEFER["sum"] and F_._DEFER["task"] is None
+    assert not F_._DEFERRED.sum and F_._DEFERRED.task is None
     step(False)
     assert torch.equal(p.grad, want)
 
@@ -156,14 +163,124 @@ def test_deferred_linear_is_keyed_by_its_column_split(fake_streams):
             F_._defer_linear(w, None, torch.ones(3, 2), [torch.ones(3, 6)], (6,))
             F_._defer_linear(w, None, torch.ones(3, 2), [torch.ones(3, 2), torch.ones(3, 4)], (2, 4))
             F_._defer_linear(w, None, torch.ones(5, 2), [torch.ones(5, 6)], (6,))
-            keys = sorted(k[1] for k in F_._DEFER["linear"])
+            keys = sorted(k[1] for k in F_._DEFERRED.linear)
             assert keys == [(2, 4), (6,)]
-            assert sorted(len(v[3]) for v in F_._DEFER["linear"].values()) == [1, 2]
-            F_._DEFER["linear"].clear()                           # (the flush would need the GPU GEMM)
+            assert sorted(len(v[3]) for v in F_._DEFERRED.linear.values()) == [1, 2]
+            F_._DEFERRED.linear.clear()                           # (the flush would need the GPU GEMM)
             return g
 
     x = torch.ones(2, requires_grad=True)
     _Q.apply(x).sum().backward()
+
+
+def test_publish_aside_forms_on_the_second_stream_and_joins_at_the_end_of_the_pass(fake_streams, monkeypatch):
+    """functional.publish_aside: the second stream waits for the current one BEFORE the gradients are formed, every tensor
+    they are formed from is marked for it, a parameter without a gradient gets the very tensor, one with a gradient is
+    added to in place, and the current stream's re-join is queued for the end of the pass -- once, not run yet."""
+    class Engine:
+        callbacks = []
+
+        def queue_callback(self, fn):
+            self.callbacks.append(fn)
+
+    class Read:
+        def __init__(self):
+            self.marks = []
+
+        def record_stream(self, stream):
+            self.marks.append(stream)
+
+    main, side = fake_streams, _FakeStream("second")
+    monkeypatch.setattr(torch.autograd.Variable, "_execution_engine", Engine())
+    monkeypatch.setattr(F_, "_HELPER_STREAMS", {(0, "second"): side})
+    reads = [Read(), Read(), Read()]
+    fresh, kept = torch.nn.Parameter(torch.zeros(3)), torch.nn.Parameter(torch.zeros(3))
+    kept.grad = torch.ones(3)
+    ptr = kept.grad.data_ptr()
+    made = [torch.full((3,), 2.0), torch.full((3,), 5.0), None]
+
+    def grads_fn():
+        _FakeStream.log.append(("grads",))
+        return made
+
+    F_.publish_aside(torch.device("cuda", 0), reads, (fresh, kept, None), grads_fn)
+    assert _FakeStream.log == [("wait", side, main), ("grads",)]
+    assert all(r.marks == [side] for r in reads)
+    assert fresh.grad is made[0]
+    assert kept.grad.data_ptr() == ptr and torch.equal(kept.grad, torch.full((3,), 6.0))
+    assert len(Engine.callbacks) == 1 and main.waited == []        # queued, not run
+    Engine.callbacks[0]()
+    assert main.waited == [side]
+
+
+class _Step(torch.autograd.Function):
+    """Identity whose backward calls ``fn`` (a node that queues a gradient, or flushes the queue early)."""
+
+    @staticmethod
+    def forward(ctx, x, fn):
+        ctx.fn = fn
+        return x.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        ctx.fn()
+        return g, None
+
+
+def _backward_through(*fns):
+    """One backward pass whose nodes call ``fns`` in that order."""
+    y = torch.ones(2, requires_grad=True)
+    for fn in reversed(fns):
+        y = _Step.apply(y, fn)
+    y.sum().backward()
+
+
+def test_early_flush_is_published_by_the_end_of_pass_flush(fake_streams):
+    """A contribution queued before an early flush and one queued after it, for the same parameter (sums: no GEMM): the
+    early result waits in ``pending`` with ``.grad`` untouched, the end-of-pass flush waits for the second stream once and
+    adds both; ``written_on`` makes the end-of-pass flush wait the same way."""
+    main, side, Q = fake_streams, _FakeStream("second"), F_._DEFERRED
+    a, b, g0 = torch.tensor([1.0, 2.0, 3.0]), torch.tensor([10.0, 20.0, 30.0]), torch.tensor([100.0, 200.0, 300.0])
+    p = torch.nn.Parameter(torch.zeros(3))
+    p.grad = g0.clone()
+    ptr, seen = p.grad.data_ptr(), {}
+
+    def flush_early():
+        Q.flush(side=side)
+        seen.update(grad=p.grad.clone(), ptr=p.grad.data_ptr(), pending=[(q, g.clone()) for q, g in Q.pending],
+                    early=Q.early, log=list(_FakeStream.log))
+
+    _backward_through(lambda: F_._defer_sum(p, a.clone()), flush_early, lambda: F_._defer_sum(p, b.clone()))
+    assert torch.equal(seen["grad"], g0) and seen["ptr"] == ptr                     # untouched until the pass ends
+    assert len(seen["pending"]) == 1 and seen["pending"][0][0] is p and torch.equal(seen["pending"][0][1], a)
+    assert seen["early"] is side
+    assert seen["log"] == [("wait", side, main)]                   # the early flush is ordered behind the queueing stream
+    assert torch.equal(p.grad, g0 + a + b) and p.grad.data_ptr() == ptr
+    assert Q.pending == [] and Q.early is None and Q.task is None
+    assert main.waited == [side]                                   # exactly once
+
+    del main.waited[:]
+    p.grad = None
+    _backward_through(lambda: (F_._defer_sum(p, a.clone()), Q.written_on(side)))
+    assert main.waited == [side] and torch.equal(p.grad, a)
+    assert Q.pending == [] and Q.early is None and Q.task is None
+
+
+def test_helper_streams_come_from_one_table(monkeypatch):
+    """functional.helper_stream: one stream per (device, kind), created on first request with that request's priority;
+    writer_streams lists exactly the streams that exist."""
+    monkeypatch.setattr(torch.cuda, "Stream", lambda device=None, priority=0: _FakeStream("made", device, priority))
+    monkeypatch.setattr(F_, "_HELPER_STREAMS", {})
+    dev = torch.device("cuda", 0)
+    assert F_.writer_streams(dev) == []
+    second = F_._side_stream(dev)
+    assert F_.writer_streams(dev) == [second]
+    atom = F_.helper_stream(dev, "atom", priority=-1)
+    assert atom is not second and F_.writer_streams(dev) == [second, atom]
+    assert F_._side_stream(dev) is second and F_.helper_stream(dev, "second") is second
+    assert F_.helper_stream(dev, "atom") is atom and F_.helper_stream(dev, "atom", priority=-1) is atom
+    assert (second.priority, atom.priority) == (0, -1) and atom.device == dev
+    assert F_.writer_streams(torch.device("cuda", 1)) == []
 
 
 @pytest.mark.parametrize("name", ["vae_lstm_s41", "vae_gru_s42"])
