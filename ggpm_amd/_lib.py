@@ -54,6 +54,9 @@ SIGNATURES = {
     "ggpm_flat_sqnorm_partials": (I, [P, c_size_t, P, c_size_t, P]),
     "ggpm_flat_norm_finish": (I, [P, I, c_float, P, P]),
     "ggpm_adam_step_groups": (I, [P, P, P, P, c_size_t, P, I, P, I, P, I, c_float, P, I, P]),
+    # ... with the non-finite guard, the skipped-step counter pair and the EMA stream; and the in-place exchange
+    "ggpm_adam_step_ex": (I, [P, P, P, P, c_size_t, P, I, P, I, P, I, c_float, I, P, c_float, I, I, P, P, P, P]),
+    "ggpm_flat_swap": (I, [P, P, c_size_t, P]),
     "ggpm_onehot": (I, [P, I, I, P, I, I, I, P]),
     "ggpm_embed_graph": (I, [P, I, P, I, I, I, I, P, I, P, I, P]),
     "ggpm_level_bf16_storage": (I, [I, I]),

@@ -399,6 +399,110 @@ __global__ void __launch_bounds__(256) adam_groups_k(float* __restrict__ p, floa
         ggpm_st4(p + 4 * i, pp); ggpm_st4(m + 4 * i, mm); ggpm_st4(v + 4 * i, vv);
     }
 }
+
+// ---------------------------------------------------------------- guarded step, effective step count, EMA (FlatAdam)
+struct AdamExArgs {                                        // by value: row k of `hp` is group k
+    float hp[GGPM_ADAM_MAX_GROUPS][8];                     // b1, b2, eps, wd, step_size, inv_bc2_sqrt, lr, 0
+};
+
+__device__ __forceinline__ double pow_int(double b, int e) {       // b^e, e >= 1, by squaring: one fixed order for every e
+    double r = 1.0;
+    for (; e > 0; e >>= 1, b *= b)
+        if (e & 1) r *= b;
+    return r;
+}
+
+// adam_groups_k's arithmetic (the same expressions: until a step has been skipped, the same bits) with three additions, all
+// decided by every workgroup for itself from values that crossed a kernel boundary:
+//   * the whole launch leaves p, m, v, ema and g alone when skip_nonfinite is set and the norm is not finite;
+//   * the step count of the bias corrections is step - *skipped_in; once that differs from `step`, threads 0..n_groups-1
+//     re-form step_size and inv_bc2_sqrt from it in fp64;
+//   * ema += (1 - d) (p_new - ema) behind the parameter update.
+// Block 0, thread 0 writes status and *skipped_out (a location no thread of this launch reads).  n % 64 == 0.
+__global__ void __launch_bounds__(256) adam_ex_k(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                 float* __restrict__ v, size_t n, const uint8_t* __restrict__ tile_group,
+                                                 int n_groups, AdamExArgs args, int step, const double* __restrict__ partials,
+                                                 int n_partials, float max_norm, int write_clipped, float* __restrict__ ema,
+                                                 float ema_decay, int ema_warmup, int skip_nonfinite,
+                                                 const int* __restrict__ skipped_in, int* __restrict__ skipped_out,
+                                                 float* __restrict__ status) {
+    __shared__ double staged[NORM_MAX_PARTIALS];
+    __shared__ __attribute__((aligned(16))) float hp[GGPM_ADAM_MAX_GROUPS][8];
+    if (threadIdx.x < GGPM_ADAM_MAX_GROUPS * 8) (&hp[0][0])[threadIdx.x] = (&args.hp[0][0])[threadIdx.x];
+    if (partials && (int)threadIdx.x < n_partials) staged[threadIdx.x] = partials[threadIdx.x];
+    const int skipped = skipped_in ? *skipped_in : 0;
+    const int t_eff = step - skipped > 1 ? step - skipped : 1;
+    __syncthreads();
+    float norm = 0.0f, coef = 1.0f;
+    if (partials) {
+        norm_and_coef(staged, n_partials, max_norm, norm, coef);
+        if (!(max_norm > 0.f)) coef = 1.0f;                // guard without a clip
+    }
+    // Inf or NaN (exponent all ones); tested on the bits, so no floating-point mode can fold it away
+    const bool skip = skip_nonfinite != 0 && (__float_as_uint(norm) & 0x7f800000u) == 0x7f800000u;
+    if (skipped > 0 && (int)threadIdx.x < n_groups) {
+        float* h = hp[threadIdx.x];
+        const double bc1 = 1.0 - pow_int((double)h[0], t_eff), bc2 = 1.0 - pow_int((double)h[1], t_eff);
+        h[4] = (float)((double)h[6] / bc1); h[5] = (float)(1.0 / sqrt(bc2));
+    }
+    __syncthreads();
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (skipped_out) *skipped_out = skipped + (skip ? 1 : 0);
+        if (status) {
+            if (partials) { status[0] = norm; status[1] = coef; }
+            status[2] = skip ? 1.0f : 0.0f; status[3] = (float)t_eff;
+        }
+    }
+    if (skip) return;
+    const bool scale = partials != nullptr && max_norm > 0.f, store_g = scale && write_clipped != 0;
+    float one_minus_d = 1.f - ema_decay;
+    if (ema && ema_warmup) {
+        const float w = (float)(1 + t_eff) / (float)(10 + t_eff);
+        one_minus_d = 1.f - (w < ema_decay ? w : ema_decay);
+    }
+    const size_t n4 = n >> 2;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+        const int grp = tile_group ? (tile_group[i >> 4] & (GGPM_ADAM_MAX_GROUPS - 1)) : 0;
+        const float4 h0 = *reinterpret_cast<const float4*>(&hp[grp][0]);
+        const float b1 = h0.x, b2 = h0.y, eps = h0.z, wd = h0.w, step_size = hp[grp][4], inv_bc2_sqrt = hp[grp][5];
+        float4 pp = ggpm_ld4(p + 4 * i), gg = ggpm_ld4(g + 4 * i), mm = ggpm_ld4(m + 4 * i), vv = ggpm_ld4(v + 4 * i);
+        float* P = &pp.x; float* G = &gg.x; float* M = &mm.x; float* V = &vv.x;
+        if (scale) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) G[k] *= coef;
+            if (store_g) ggpm_st4(g + 4 * i, gg);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float gr = wd != 0.f ? G[k] + wd * P[k] : G[k];
+            M[k] = M[k] + (1.f - b1) * (gr - M[k]);
+            V[k] = b2 * V[k] + (1.f - b2) * gr * gr;
+            P[k] -= step_size * M[k] / (sqrtf(V[k]) * inv_bc2_sqrt + eps);
+        }
+        ggpm_st4(p + 4 * i, pp); ggpm_st4(m + 4 * i, mm); ggpm_st4(v + 4 * i, vv);
+        if (ema) {
+            float4 ee = ggpm_ld4(ema + 4 * i);
+            float* E = &ee.x;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) E[k] = E[k] + one_minus_d * (P[k] - E[k]);
+            ggpm_st4(ema + 4 * i, ee);
+        }
+    }
+}
+
+// a <-> b in place, 16 B per lane, grid-stride
+__global__ void __launch_bounds__(256) flat_swap_k(float* __restrict__ a, float* __restrict__ b, size_t n) {
+    const size_t n4 = n >> 2;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+        const float4 x = ggpm_ld4(a + 4 * i), y = ggpm_ld4(b + 4 * i);
+        ggpm_st4(a + 4 * i, y); ggpm_st4(b + 4 * i, x);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {          // tail of up to three elements
+        const size_t i = (n4 << 2) + threadIdx.x;
+        const float x = a[i], y = b[i];
+        a[i] = y; b[i] = x;
+    }
+}
 }  // namespace
 
 extern "C" size_t ggpm_flat_sqnorm_workspace_bytes(size_t n) { return (size_t)norm_grid(n) * sizeof(double); }
@@ -447,6 +551,50 @@ extern "C" int ggpm_adam_step_groups(float* p, float* g, float* m, float* v, siz
     if (blocks > 2048) blocks = 2048;
     adam_groups_k<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(p, g, m, v, n, tile_group, args, partials, n_partials,
                                                                    max_norm, clip_out, write_clipped);
+    GGPM_CHECK_LAUNCH();
+    return GGPM_OK;
+}
+
+extern "C" int ggpm_adam_step_ex(float* p, float* g, float* m, float* v, size_t n, const uint8_t* tile_group, int n_groups,
+                                 const ggpm_adam_group* groups, int step, const double* partials, int n_partials,
+                                 float max_norm, int write_clipped, float* ema, float ema_decay, int ema_warmup,
+                                 int skip_nonfinite, const int* skipped_in, int* skipped_out, float* status,
+                                 ggpm_stream_t stream) {
+    GGPM_CLEAR_STALE_ERROR();
+    if (!p || !g || !m || !v || !groups || n == 0 || n % 64 != 0 || step < 1) return GGPM_ERR_ARG;
+    if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) != 0) return GGPM_ERR_ARG;
+    if (n_groups < 1 || n_groups > GGPM_ADAM_MAX_GROUPS || (!tile_group && n_groups > 1)) return GGPM_ERR_ARG;
+    if (!(max_norm >= 0.f)) return GGPM_ERR_ARG;                                        // negative or NaN
+    if (partials && (n_partials < 1 || n_partials > NORM_MAX_PARTIALS || ((uintptr_t)partials & 7) != 0)) return GGPM_ERR_ARG;
+    if (!partials && (max_norm > 0.f || skip_nonfinite != 0)) return GGPM_ERR_ARG;      // a clip or the guard needs the norm
+    if (ema && (!(ema_decay >= 0.f) || !(ema_decay < 1.f) || ema == p || ema == g || ema == m || ema == v)) return GGPM_ERR_ARG;
+    if ((skipped_in == nullptr) != (skipped_out == nullptr) || (skipped_in && skipped_in == skipped_out)) return GGPM_ERR_ARG;
+    if ((((uintptr_t)skipped_in | (uintptr_t)skipped_out | (uintptr_t)status) & 3) != 0) return GGPM_ERR_ARG;
+    AdamExArgs args = {};
+    for (int k = 0; k < n_groups; ++k) {
+        const ggpm_adam_group& q = groups[k];
+        const double bc1 = 1.0 - pow((double)q.beta1, step), bc2 = 1.0 - pow((double)q.beta2, step);
+        float* h = args.hp[k];
+        h[0] = q.beta1; h[1] = q.beta2; h[2] = q.eps; h[3] = q.weight_decay;
+        h[4] = (float)((double)q.lr / bc1); h[5] = (float)(1.0 / sqrt(bc2)); h[6] = q.lr;
+    }
+    size_t blocks = ((n >> 2) + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    adam_ex_k<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(p, g, m, v, n, tile_group, n_groups, args, step, partials,
+                                                               n_partials, max_norm, write_clipped, ema, ema_decay, ema_warmup,
+                                                               skip_nonfinite, skipped_in, skipped_out, status);
+    GGPM_CHECK_LAUNCH();
+    return GGPM_OK;
+}
+
+extern "C" int ggpm_flat_swap(float* a, float* b, size_t n, ggpm_stream_t stream) {
+    GGPM_CLEAR_STALE_ERROR();
+    if (!a || !b || n == 0 || ((((uintptr_t)a | (uintptr_t)b) & 15) != 0)) return GGPM_ERR_ARG;
+    if ((a <= b ? (size_t)(b - a) : (size_t)(a - b)) < n) return GGPM_ERR_ARG;          // the same buffer, or overlapping
+    size_t blocks = ((n >> 2) + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    if (blocks < 1) blocks = 1;
+    flat_swap_k<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(a, b, n);
     GGPM_CHECK_LAUNCH();
     return GGPM_OK;
 }

@@ -338,6 +338,30 @@ typedef struct ggpm_adam_group { float lr, beta1, beta2, eps, weight_decay; } gg
 int ggpm_adam_step_groups(float* p, float* g, float* m, float* v, size_t n, const uint8_t* tile_group, int n_groups,
                           const ggpm_adam_group* groups, int step, const double* partials, int n_partials, float max_norm,
                           float* clip_out, int write_clipped, ggpm_stream_t stream);
+/* ggpm_adam_step_groups with a non-finite guard, a step count that leaves skipped steps out, and an exponential moving
+ * average of the parameters, in the same single launch.  Everything up to `write_clipped` is as above, except:
+ *   partials   required with max_norm > 0 or skip_nonfinite; with partials and max_norm == 0 the guard runs without a clip
+ *              (coefficient exactly 1, no multiply issued).  max_norm < 0 or NaN is refused.
+ *   guard      skip_nonfinite != 0 and the fp32 norm (status[0], the value clip_out[0] above would hold) not finite: the
+ *              step is SKIPPED: no byte of p, m, v, ema or g changes, with write_clipped too.  This covers an Inf or a NaN
+ *              anywhere in g, and also an all-finite g whose 2-norm overflows fp32 (above 3.4e38).
+ *   counter    skipped_in / skipped_out: two DIFFERENT device ints (both or neither); *skipped_out = *skipped_in + 1 on a
+ *              skipped step, = *skipped_in on an applied one.  The caller alternates the two call by call, so no workgroup
+ *              reads what another writes in the same launch.  `step` stays the caller's call count; the bias corrections
+ *              use t_eff = step - *skipped_in, as torch.optim.Adam does when optimizer.step() is simply not called.
+ *              While *skipped_in is 0 (or NULL) the corrections are the host-formed values of ggpm_adam_step_groups and
+ *              p, m, v are its bits; afterwards the device forms lr / (1 - b1^t_eff) and 1 / sqrt(1 - b2^t_eff) in fp64 with
+ *              the power by repeated squaring, which may differ from a host-formed value in the last fp32 bit.
+ *   ema        NULL, or n floats, 16-byte aligned, no alias of p, g, m, v; on an applied step, behind the update,
+ *              ema += (1 - d)(p_new - ema) in fp32, d = ema_decay in [0, 1), or with ema_warmup != 0
+ *              d = min(ema_decay, (1 + t_eff) / (10 + t_eff)) (one correctly rounded fp32 division; t_eff < 2^24).
+ *   status     NULL or device float[4] = {norm, coef, skipped (0 / 1), t_eff}; the first two only with partials. */
+int ggpm_adam_step_ex(float* p, float* g, float* m, float* v, size_t n, const uint8_t* tile_group, int n_groups,
+                      const ggpm_adam_group* groups, int step, const double* partials, int n_partials, float max_norm,
+                      int write_clipped, float* ema, float ema_decay, int ema_warmup, int skip_nonfinite,
+                      const int* skipped_in, int* skipped_out, float* status, ggpm_stream_t stream);
+/* a[i] <-> b[i] for i < n in place (16 B per lane, nothing allocated); a, b 16-byte aligned and not overlapping. */
+int ggpm_flat_swap(float* a, float* b, size_t n, ggpm_stream_t stream);
 int ggpm_onehot(const int32_t* idx, int rows, int classes, float* out, int ld_out, int col_off, int zero_to,
                 ggpm_stream_t stream);
 /* embed_graph (ggpm/encoder.py:119-126) in one launch: hnode[N1, ld_n] = onehot(fnode), hmess[E1, ld_m] =

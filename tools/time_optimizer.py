@@ -6,7 +6,7 @@ gradients (no forward pass): median host-issue ms and median device ms (HIP even
 Legs: (a) torch's clip_grad_norm_(model.parameters(), 20.0) + torch.optim.Adam(model.parameters(), fused=True).step();
 (b) FlatAdam.step(clip_norm=20.0); (c) FlatAdam.step(), the launch bench.py times; (d) (b) with four parameter groups (the
 split of vae_fine_tune_indv_opt.py by name: 'decoder', the rest, and -- this model has no property heads -- 'R_mean' and 'R_var'
-in their place).  Last line: FlatAdam.param_norm() + grad_norm() against the scripts' per-parameter .item() loops, both read
+in their place); (e) (b) with the non-finite guard; (f) (e) with the EMA of the parameters in the same launch.  Last line: FlatAdam.param_norm() + grad_norm() against the scripts' per-parameter .item() loops, both read
 on the host.
 """
 import argparse
@@ -41,7 +41,7 @@ def _model():
     return HierPropertyVAE(a).to(DEV)
 
 
-def _flat(groups: bool):
+def _flat(groups: bool, **features):
     model = _model()
     sync = FlatGradSync(model.parameters(), keep_flat=True)
     pg = None
@@ -50,7 +50,7 @@ def _flat(groups: bool):
         keys = ("decoder", "R_mean", "R_var")
         pg = [{"params": [p for k, p in named if not any(key in k for key in keys)], "lr": 1e-3}]
         pg += [{"params": [p for k, p in named if key in k], "lr": lr} for key, lr in zip(keys, (5e-4, 2e-3, 3e-3))]
-    opt = FlatAdam(sync, lr=1e-3, param_groups=pg)
+    opt = FlatAdam(sync, lr=1e-3, param_groups=pg, **features)
     gen = torch.Generator(device=DEV).manual_seed(1)
     for v in sync.views:                                 # random gradients; the padding between parameters stays zero
         v.normal_(generator=gen)
@@ -103,6 +103,14 @@ def main():
     base["flat_floats"] = sync.flat.numel()
     print(json.dumps(dict(base, leg="b: FlatAdam.step(clip_norm)", **_time(lambda: opt.step(clip_norm=CLIP), a.reps, a.warmup))))
     print(json.dumps(dict(base, leg="c: FlatAdam.step()", **_time(opt.step, a.reps, a.warmup))))
+    # the guarded step and the guarded, averaging step: each still the partials launch and ONE update launch
+    _, _, opt_g = _flat(groups=False, skip_nonfinite=True)
+    print(json.dumps(dict(base, leg="e: FlatAdam(skip_nonfinite).step(clip_norm)",
+                          **_time(lambda: opt_g.step(clip_norm=CLIP), a.reps, a.warmup))))
+    _, _, opt_e = _flat(groups=False, skip_nonfinite=True, ema_decay=0.999, ema_warmup=True)
+    print(json.dumps(dict(base, leg="f: FlatAdam(skip_nonfinite, ema_decay).step(clip_norm)",
+                          **_time(lambda: opt_e.step(clip_norm=CLIP), a.reps, a.warmup))))
+    assert opt_g.skipped_steps == 0 and opt_e.skipped_steps == 0
     _, sync4, opt4 = _flat(groups=True)
     print(json.dumps(dict(base, leg="d: FlatAdam.step(clip_norm), four groups",
                           **_time(lambda: opt4.step(clip_norm=CLIP), a.reps, a.warmup))))
