@@ -253,27 +253,55 @@ def index_scatter(sub: Tensor, full: Tensor, index: Tensor) -> Tensor:
     return full * mask.unsqueeze(-1) + buf
 
 
+# ``gate_dtype`` "bf16" / "bf16w" of the two functions below: the sparse kernels (mpn_gru.hip / mpn_lstm.hip with a `frozen`
+# mask) are the dense depth kernels over ALL rows of the level, so the rounding points are those of gru_cell_bf16 /
+# lstm_cell_bf16, applied to the full state:
+#   * the per-message product q^t = U_r h^t + b_u (LSTM: qf^t = W_f[:, I:] h^t) is formed for EVERY row of the level at every
+#     step, t = 0 (the q^0 launch on the caller's state) included, frozen rows too: rne(h^t) rne(U_r)^T; its gradient reaches
+#     the product summed over the uses of the row at step t + 1 and is rounded there, once per step (the DQ stash slot t);
+#     what it sends on to a frozen row's state is that row's share of the incoming-state gradient;
+#   * the gate products of the recomputed rows round s, g (LSTM: s) and the hidden halves of the gate weights, and in the
+#     backward the gate gradients d(pre-activation) and the weights again; a frozen row keeps h' = h (c' = c) bit for bit
+#     and its gate stashes are zero, so nothing of it passes a rounding but q;
+#   * "bf16w": the weight-gradient contractions (over the depth x E1 rows of the stashes, dq^0 included) on rounded
+#     operands as well -- where depth * E1 qualifies for the bf16 tall kernel, as for a dense level;
+#   * a sparse call never stores bf16 (ggpm_level_bf16_storage is for dense training levels): "bf16s" is refused.
+# Input halves, gate math and the state stay in the working dtype.
+def _sparse_gate_dtype(gate_dtype: str) -> str:
+    if gate_dtype not in ("f32", "bf16", "bf16w"):
+        raise ValueError("gate_dtype of a sparse level: " + gate_dtype)
+    return gate_dtype
+
+
 def gru_sparse_forward(p: Params, pre: str, h: Tensor, fmess: Tensor, submess: Tensor, bgraph: Tensor,
-                       depth: int) -> Tensor:
-    """GRU.sparse_forward -- ggpm/rnn.py:52-59."""
+                       depth: int, gate_dtype: str = "f32") -> Tensor:
+    """GRU.sparse_forward -- ggpm/rnn.py:52-59.  ``gate_dtype``: "f32", or "bf16" / "bf16w" (rounding points above)."""
+    gate_dtype = _sparse_gate_dtype(gate_dtype)
     mask = torch.ones(h.shape[0], dtype=h.dtype, device=h.device)
     mask[submess] = 0
     h = h * mask.unsqueeze(1)
     for _ in range(depth):
-        sub_h = gru_cell(p, pre, fmess, gather_rows(h, bgraph))
+        if gate_dtype == "f32":
+            sub_h = gru_cell(p, pre, fmess, gather_rows(h, bgraph))
+        else:
+            sub_h = gru_cell_bf16(p, pre, fmess, h, bgraph, gate_dtype)
         h = index_scatter(sub_h, h, submess)
     return h
 
 
 def lstm_sparse_forward(p: Params, pre: str, h: Tensor, c: Tensor, fmess: Tensor, submess: Tensor, bgraph: Tensor,
-                        depth: int) -> Tuple[Tensor, Tensor]:
-    """LSTM.sparse_forward -- ggpm/rnn.py:110-121."""
+                        depth: int, gate_dtype: str = "f32") -> Tuple[Tensor, Tensor]:
+    """LSTM.sparse_forward -- ggpm/rnn.py:110-121.  ``gate_dtype``: as gru_sparse_forward."""
+    gate_dtype = _sparse_gate_dtype(gate_dtype)
     mask = torch.ones(h.shape[0], dtype=h.dtype, device=h.device)
     mask[submess] = 0
     h = h * mask.unsqueeze(1)
     c = c * mask.unsqueeze(1)
     for _ in range(depth):
-        sub_h, sub_c = lstm_cell(p, pre, fmess, gather_rows(h, bgraph), gather_rows(c, bgraph))
+        if gate_dtype == "f32":
+            sub_h, sub_c = lstm_cell(p, pre, fmess, gather_rows(h, bgraph), gather_rows(c, bgraph))
+        else:
+            sub_h, sub_c = lstm_cell_bf16(p, pre, fmess, h, c, bgraph, gate_dtype)
         h = index_scatter(sub_h, h, submess)
         c = index_scatter(sub_c, c, submess)
     return h, c

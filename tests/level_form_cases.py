@@ -6,6 +6,10 @@ fwd_step, bwd_step over the cell descriptions of csrc/mpn_gru.hip and csrc/mpn_l
 form the table expects it to take, reduced to ``(tg, groups, gate_mode, rt2, fuse_fwd, fuse_bwd)``:
 tests/test_level_forms_cpu.py holds the table to the lattice the query spans (every reachable form has a case; every case
 has the form it states), tests/test_gpu_level_forms.py runs every case against the fp64 oracle.
+
+``OPT_DENSE`` / ``OPT_SPARSE`` hold the forms a call reaches only through ``ggpm_level_opts.gate_dtype`` and
+``prefer_narrow``; their forms carry ``st16`` as a seventh entry (``reduced_opt``), and
+tests/test_gpu_level_option_forms.py runs them.
 """
 from collections import namedtuple
 
@@ -14,8 +18,9 @@ import numpy as np
 I, K = 20, 4          # input width and predecessor slots of every case
 HIDDEN = (250, 300, 600)        # the hidden sizes of the shipped configurations
 
-# form: (tg, groups, gate_mode, rt2, fuse_fwd, fuse_bwd); E1 counts the pad row; ms: recomputed rows of a sparse call
-Case = namedtuple("Case", "cell H E1 depth form sparse ms")
+# form: (tg, groups, gate_mode, rt2, fuse_fwd, fuse_bwd); E1 counts the pad row; ms: recomputed rows of a sparse call;
+# gate_dtype (0 .. 3), prefer_narrow (0 / 1): the call's ggpm_level_opts (the option cases; their form ends in st16)
+Case = namedtuple("Case", "cell H E1 depth form sparse ms gate_dtype prefer_narrow", defaults=(0, 0))
 
 
 def _dense(cell, H, E1, form, depth=2):
@@ -77,9 +82,70 @@ LIMIT_DENSE = [_dense("GRU", 1264, 40, _groups(4, 20)), _dense("GRU", 1264, 673,
                _dense("LSTM", 848, 2049, (53, 1, 0, 0, 1, 0))]
 LIMIT_SPARSE = [_sparse("LSTM", 848, 450, _groups(7, 8))]
 
+# ---- the forms only options reach (training calls; DESIGN.md 5.1 counts them): one case per form, at the lower end of its
+# class -- the smallest E1 that takes it, 40 for the first class, 6144 for bf16 storage, 8177 for the two-row-tile forms a
+# call takes by its size -- and at the depth _GROUPED gives the class.  (gate_dtype, prefer_narrow) is the setting a
+# product path uses where several reach the form: the module attribute for the gate dtype, prefer_narrow for two row tiles.
+_TILES = {250: 16, 300: 19, 600: 38}
+# H -> [(E1, (tg, groups), depth)] of every class: the grouped ones from their lower end, then the single group
+_CLASSES = {H: [g for g in _GROUPED[H] if g[0] != 2048] + [(2049, (_TILES[H], 1), 2)] for H in HIDDEN}
+# what a single-group call fuses under gate modes 0 and 1 (forward, backward); a column-grouped call fuses nothing
+_SINGLE_FUSE = {("GRU", 250): (1, 1), ("GRU", 300): (1, 1), ("GRU", 600): (1, 0),
+                ("LSTM", 250): (1, 1), ("LSTM", 300): (1, 1), ("LSTM", 600): (1, 0)}
+# the hidden sizes at which a cell has two-row-tile kernels that fit the LDS / split images that fit beside its tiles
+_RT2_H = {"GRU": (250, 300, 600), "LSTM": (250, 300)}
+_SPLIT_H = {"GRU": (250, 300, 600), "LSTM": (250, 300)}
+STORAGE_H, STORAGE_E1, RT2_E1 = (300, 600), 6144, 8177      # bf16 storage: E1 >= 6144 at these H; 511 * 16 + 1 rows
+
+
+def _opt(cell, H, E1, depth, form, gate_dtype, prefer_narrow):
+    return Case(cell, H, E1, depth, form, False, 0, gate_dtype, prefer_narrow)
+
+
+OPT_DENSE = []
+for _cell in ("GRU", "LSTM"):
+    for _H in HIDDEN:
+        _ff, _fb = _SINGLE_FUSE[_cell, _H]
+        for _E1, (_tg, _g), _d in _CLASSES[_H]:
+            _one = _g == 1
+            _fuse = (_ff, _fb) if _one else (0, 0)
+            # bf16 operands, one row tile, fp32 storage (module.gate_dtype = "bf16")
+            OPT_DENSE.append(_opt(_cell, _H, _E1, _d, (_tg, _g, 1, 0) + _fuse + (0,), 1, 0))
+            if _H in _RT2_H[_cell]:
+                # fp32 MFMA on two row tiles, forced (prefer_narrow).  The GRU's single group: a default call takes this form
+                # from 8177 rows, where DENSE holds it at H = 300 only -- H = 250 / 600 stand here, at 2049 rows.
+                if not (_cell == "GRU" and _one and _H == 300):
+                    OPT_DENSE.append(_opt(_cell, _H, _E1, _d, (_tg, _g, 0, 1, 0, 0, 0), 0, 1))
+                # bf16 operands on two row tiles (GRU only), forced -- but the single group of H = 250, which a GRU level of
+                # 8177 rows takes by itself (no bf16 storage at that size)
+                if _cell == "GRU" and not (_one and _H not in STORAGE_H):
+                    OPT_DENSE.append(_opt(_cell, _H, _E1, _d, (_tg, _g, 1, 1, 0, 0, 0), 1, 1))
+            if _one and (_cell, _H) != ("LSTM", 600):
+                # fp32 MFMA where the default splits (gate_dtype 2); the LSTM at H = 600 has no room to split anyway
+                OPT_DENSE.append(_opt(_cell, _H, _E1, _d, (_tg, 1, 0, 0) + _fuse + (0,), 2, 0))
+            if not _one and _H in _SPLIT_H[_cell]:
+                # split operands on a column-grouped form (gate_dtype 3)
+                OPT_DENSE.append(_opt(_cell, _H, _E1, _d, (_tg, _g, 2, 0, 0, 0, 0), 3, 0))
+        if _H in STORAGE_H:      # bf16 operands + bf16 storage
+            OPT_DENSE.append(_opt(_cell, _H, STORAGE_E1, 2, (_TILES[_H], 1, 1, 0, _ff, _fb, 1), 1, 0))
+        if _cell == "GRU":       # the natural two-row-tile form under bf16: with bf16 storage where the level has it
+            OPT_DENSE.append(_opt(_cell, _H, RT2_E1, 2, (_TILES[_H], 1, 1, 1, 0, 0, int(_H in STORAGE_H)), 1, 0))
+
+# sparse calls under gate_dtype 1 and 3, on the three classes of SPARSE_E1 (a sparse call never takes two row tiles and
+# never stores bf16).  gate_dtype 3: the single group fuses what the dense default does on split operands; the LSTM at
+# H = 600 has no room for the images and keeps the default form, which SPARSE holds.
+OPT_SPARSE = []
+for _c in SPARSE:
+    _tg, _g, _, _, _ff, _fb = _c.form
+    OPT_SPARSE.append(_c._replace(form=(_tg, _g, 1, 0, _ff, _fb, 0), gate_dtype=1))
+    _split = _SINGLE_DENSE[_c.cell, _c.H] if _g == 1 else (_tg, _g, 2, 0, 0, 0)
+    if _split[2] == 2 and _c.H in _SPLIT_H[_c.cell]:
+        OPT_SPARSE.append(_c._replace(form=_split + (0,), gate_dtype=3))
+
 
 def case_id(c):
-    return "%s-H%d-E%d-d%d%s" % (c.cell, c.H, c.E1, c.depth, "-sparse" if c.sparse else "")
+    return "%s-H%d-E%d-d%d%s%s%s" % (c.cell, c.H, c.E1, c.depth, "-sparse" if c.sparse else "",
+                                     "-dt%d" % c.gate_dtype if c.gate_dtype else "", "-narrow" if c.prefer_narrow else "")
 
 
 def reduced(form):
@@ -87,10 +153,23 @@ def reduced(form):
     return (form.tg, form.groups, form.gate_mode, form.rt2, form.fuse_fwd, form.fuse_bwd)
 
 
-def query(case, training=True):
-    """-> the LevelForm of the case's call under default options (None: refused)"""
+def reduced_opt(form):
+    """... with st16: what the option tables state"""
+    return reduced(form) + (form.st16,)
+
+
+def level_opts(case, **fields):
+    """-> the functional.LevelOpts of the case's call (None: all defaults)"""
     from ggpm_amd import functional as F_
-    return F_.level_form(case.cell == "LSTM", case.E1, case.H, sparse=case.sparse, training=training)
+    if not (case.gate_dtype or case.prefer_narrow or fields):
+        return None
+    return F_.LevelOpts(gate_dtype=case.gate_dtype, prefer_narrow=case.prefer_narrow, **fields)
+
+
+def query(case, training=True):
+    """-> the LevelForm of the case's call under its options (None: refused)"""
+    from ggpm_amd import functional as F_
+    return F_.level_form(case.cell == "LSTM", case.E1, case.H, sparse=case.sparse, training=training, opts=level_opts(case))
 
 
 def _seed(case):

@@ -12,46 +12,11 @@ import pytest
 import torch
 
 import level_form_cases as C
-from golden_utils import rel_err
+# (the comparison helpers are shared with tests/test_gpu_level_option_forms.py; TOL and the two bars live with them)
+from level_form_checks import TOL, check as _check, dense_oracle as _dense_oracle, dev as _dev, module as _module, \
+    sparse_oracle as _sparse_oracle  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-TOL = 1e-4   # BASELINE.json: outputs / losses within 1e-4 fp32 relative
-
-
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _module(case, sd):
-    from ggpm_amd import rnn as R
-    mod = (R.GRU if case.cell == "GRU" else R.LSTM)(C.I, case.H, case.depth).to(_dev())
-    mod.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
-    return mod
-
-
-def _check(case, form, got, want64, want32, t0):
-    """Both bars on every tensor; prints the case's worst distances (HIP vs fp64, the oracle's fp32 run vs fp64, and the
-    largest share of the second bar any tensor used)."""
-    assert sorted(got) == sorted(want64) == sorted(want32)
-    hip = {k: rel_err(got[k], want64[k]) for k in got}
-    o32 = {k: rel_err(want32[k], want64[k]) for k in got}
-    share = {k: hip[k] / (3.0 * o32[k] + 1e-6) for k in got}
-    kh, ko, ks = (max(d, key=d.get) for d in (hip, o32, share))
-    print("level form %-26s form %-22s HIP-fp64 %.2e (%s)  oracle32-fp64 %.2e (%s)  share of 3x+1e-6 %.2f (%s)  %.2f s"
-          % (C.case_id(case), C.reduced(form), hip[kh], kh, o32[ko], ko, share[ks], ks, time.perf_counter() - t0))
-    for k in got:
-        assert hip[k] < TOL, (k, hip[k])
-        assert hip[k] <= 3.0 * o32[k] + 1e-6, (k, hip[k], o32[k])
-
-
-def _dense_oracle(case, sd, x, bgraph, w, dtype):
-    from oracle import ref_encoder as ref
-    p = {k: torch.from_numpy(v).to(dtype).requires_grad_(True) for k, v in sd.items()}
-    xr = torch.from_numpy(x).to(dtype).requires_grad_(True)
-    href = ref.rnn_forward(p, "", case.cell, xr, torch.from_numpy(bgraph), case.depth)
-    (href * torch.from_numpy(w).to(dtype)).sum().backward()
-    return dict({k: v.grad.numpy() for k, v in p.items()}, h=href.detach().numpy(), dx=xr.grad.numpy())
 
 
 def _dense_hip(case, sd, x, bgraph, w):
@@ -100,27 +65,6 @@ def test_dense_level_at_the_accepted_hidden_sizes_matches_fp64(case):
     """... and at the largest hidden sizes the entry points accept (up to five tiles per wave; every launch within a few
     hundred bytes of the LDS), and on both sides of the last fused single-group GRU forward"""
     _run_dense(case)
-
-
-def _sparse_oracle(case, sd, inputs, dtype):
-    from oracle import ref_encoder as ref
-    h, c, submess, x, bg, coef = inputs
-    p = {"rnn." + k: torch.from_numpy(v).to(dtype).requires_grad_(True) for k, v in sd.items()}
-    hr, cr, xr = (torch.from_numpy(a).to(dtype).requires_grad_(True) for a in (h, c, x))
-    cf = torch.from_numpy(coef).to(dtype)
-    sm, bgt = torch.from_numpy(submess), torch.from_numpy(bg)
-    if case.cell == "GRU":
-        ro = ref.gru_sparse_forward(p, "rnn.", hr, xr, sm, bgt, case.depth)
-        (cf[0] * ro).sum().backward()
-        res = {}
-    else:
-        ro, rc = ref.lstm_sparse_forward(p, "rnn.", hr, cr, xr, sm, bgt, case.depth)
-        ((cf[0] * ro).sum() + (cf[1] * rc).sum()).backward()
-        res = {"c": rc.detach().numpy(), "dc_in": cr.grad.numpy()[1:]}
-    # (row 0 of the incoming-state gradients: the pad row, see test_sparse_forward_matches_reference_golden)
-    res.update({k[4:]: v.grad.numpy() for k, v in p.items()}, h=ro.detach().numpy(), dh_in=hr.grad.numpy()[1:],
-               dx=xr.grad.numpy())
-    return res
 
 
 def _run_sparse(case):

@@ -1004,7 +1004,7 @@ def test_dropout_in_the_drivers_matches_oracle_with_the_same_masks(name):
 
 
 BF16_TOL = 2e-3      # HIP bf16 path vs the oracle with the SAME operand roundings (norm-wise, every tensor)
-BF16_STEP_TOL = 1e-3 # ... parameter gradients of one level over 2-3 depth steps (flipped roundings included, not yet amplified)
+from level_form_checks import BF16_STEP_TOL, bf16_oracle_mode, check_bf16_level  # noqa: E402  (one level, 2-3 depth steps)
 
 
 def _seeded_encoder_case(rnn, H, depth, specs, n_motif=60, n_attach=180, latent=32):
@@ -1130,40 +1130,15 @@ def test_bf16_level_kernels_match_the_bf16_oracle(rnn, E, I, H, depth):
         got[dt] = dict({k: v.grad.cpu().numpy() for k, v in mod.named_parameters()}, h=h.detach().cpu().numpy(),
                        dx=xg.grad.cpu().numpy())
     lib = _lib.load(build_if_missing=False)
-    mode = "bf16w" if lib.ggpm_gemm_tn_bf16_applies(H, H, (depth - 1) * (E + 1)) else "bf16"
-    if lib.ggpm_level_bf16_storage(E + 1, H):      # bf16 storage of the depth loop's arrays (tile_mma.h)
-        mode = "bf16s"
+    # "bf16w" / "bf16" by the shortest contraction; "bf16s": bf16 storage of the depth loop's arrays (tile_mma.h)
+    mode = bf16_oracle_mode(lib, H, (depth - 1) * (E + 1), lib.ggpm_level_bf16_storage(E + 1, H))
     p = {k: torch.from_numpy(v.copy()).requires_grad_(True) for k, v in sd.items()}
     xr = torch.from_numpy(x).requires_grad_(True)
     href = ref.rnn_forward(p, "", rnn, xr, torch.from_numpy(bgraph), depth, gate_dtype=mode)
     (href * w).sum().backward()
     want = dict({k: v.grad.numpy() for k, v in p.items()}, h=href.detach().numpy(), dx=xr.grad.numpy())
-    shift = {k: rel_err(got["bf16"][k], got["f32"][k]) for k in want}
-    assert shift["h"] > 1e-5                 # the bf16 path really ran
-    report = []
-    for k in ("h", "dx"):                    # row-wise: unflipped rows agree to fp32 noise
-        scale = np.abs(want[k]).max()
-        row = np.abs(got["bf16"][k] - want[k]).max(axis=1) / scale
-        med, frac, worst = float(np.median(row)), float((row <= 2e-5).mean()), float(row.max())
-        report.append("%s rows: median %.1e, %.1f%% within 2e-5, worst %.1e" % (k, med, 100 * frac, worst))
-        # (a flipped row reaches its predecessors through the backward gather: more dx rows than h rows are touched)
-        # (bf16 storage: what a flip moves is a STORED value, by one bf16 ulp of itself, i.e. up to 2^-8 of the tensor's scale)
-        # and every stored array is one more rounding point per element and depth step: more rows meet a flip)
-        worst_tol = 6e-3 if mode == "bf16s" else 2e-3
-        frac_min = {"h": 0.9, "dx": 0.7} if mode != "bf16s" else {"h": 0.75, "dx": 0.5}
-        med_tol = 5e-6 if mode == "bf16s" else 2e-6      # (measured: <= 2.6e-6 at H = 600, 0.0 for the state at every size)
-        assert med <= med_tol and frac >= frac_min[k] and worst <= worst_tol, (k, med, frac, worst)
-        # What the relaxed row fractions above still pin: a wrong rounding point, rounding mode, operand
-        # order or accumulation moves EVERY row.  Under bf16 storage a state row without a flipped rounding is BIT-EQUAL to
-        # the oracle (both round the same fp32 value to the same bf16), so the median row distance is exactly zero -- asserted.
-        if mode == "bf16s" and k == "h":
-            assert med == 0.0, ("bf16 storage: the median state row must be bit-equal to the oracle", med)
-    errs = {k: rel_err(got["bf16"][k], want[k]) for k in sd}
-    worst_k = max(errs, key=errs.get)
-    print("bf16 level %s E=%d H=%d depth=%d (weight-gradient operands %s): %s; parameter gradients worst %.2e (%s) at a "
-          "bf16 -> fp32 distance of %.2e" % (rnn, E, H, depth, mode, "; ".join(report), errs[worst_k], worst_k, shift[worst_k]))
-    for k, e in errs.items():
-        assert e <= BF16_STEP_TOL and e <= max(shift[k] / 3.0, 2e-5), (k, e, shift[k])
+    # (the criteria stated above: tests/level_form_checks.py, shared with tests/test_gpu_level_option_forms.py)
+    check_bf16_level("%s E=%d H=%d depth=%d" % (rnn, E, H, depth), got["bf16"], got["f32"], want, mode, list(sd))
 
 
 @pytest.mark.parametrize("case", ["tiny_gru_s1", "cfg_gru_s0", "cfg_lstm_s2", "polymer_lstm_h600_d30", "polymer_gru_h600_d10",

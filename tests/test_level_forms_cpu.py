@@ -70,6 +70,118 @@ def test_every_sparse_form_of_the_tested_classes_has_a_case():
                 assert form in table[cell, H], "no sparse case covers (cell, H, E1, form) = %r" % ((cell, H, E1, form),)
 
 
+# ---- the forms only options reach (C.OPT_DENSE, C.OPT_SPARSE; tests/test_gpu_level_option_forms.py runs them)
+SWEEP_E1 = tuple(range(2, 4097)) + (6143, 6144, 6145, 8177, 8192, 8193, 12289)
+SWEEP_OPTS = tuple((dt, pn) for dt in range(4) for pn in (0, 1))
+
+
+def _with_st16(c):
+    """a case's form as reduced_opt states it (a default case never stores bf16)"""
+    return c.form if len(c.form) == 7 else c.form + (0,)
+
+
+def _table_opt(cases):
+    forms = {}
+    for c in cases:
+        forms.setdefault((c.cell, c.H), set()).add(_with_st16(c))
+    return forms
+
+
+def _forward_form(form7):
+    """a reduced_opt form without fuse_bwd: what a forward call can tell apart"""
+    return form7[:5] + form7[6:]
+
+
+def _sweep(sparse, training=True, h_out=False):
+    """-> (cell, H, E1, gate_dtype, prefer_narrow, reduced_opt form) over the option sweep"""
+    import ctypes
+    for cell, H, (dt, pn) in itertools.product(("GRU", "LSTM"), C.HIDDEN, SWEEP_OPTS):
+        o = F_.LevelOpts(gate_dtype=dt, prefer_narrow=pn)
+        if h_out:
+            o.h_out = ctypes.c_void_p(256)      # host only: an address that is never read
+        for E1 in SWEEP_E1:
+            yield cell, H, E1, dt, pn, C.reduced_opt(F_.level_form(cell == "LSTM", E1, H, sparse=sparse, training=training,
+                                                                   opts=o))
+
+
+def _sparse_classes():
+    return {(cell, H): {C.reduced(F_.level_form(cell == "LSTM", E1, H, sparse=True))[:2] for E1 in C.SPARSE_E1}
+            for cell, H in itertools.product(("GRU", "LSTM"), C.HIDDEN)}
+
+
+def test_every_option_case_takes_the_form_the_table_states():
+    """... including st16, under the case's own gate_dtype / prefer_narrow; and the table is minimal: no two option cases
+    state the same form, none states a form a default case already holds, so deleting any one of them leaves its form
+    without a case and fails one of the coverage tests below."""
+    seen = {(c.cell, c.H, c.sparse, _with_st16(c)) for c in C.DENSE + C.SPARSE}
+    for c in C.OPT_DENSE + C.OPT_SPARSE:
+        f = C.query(c)
+        assert f is not None and len(c.form) == 7 and C.reduced_opt(f) == c.form, (C.case_id(c), f and C.reduced_opt(f), c.form)
+        assert c.gate_dtype or c.prefer_narrow, C.case_id(c)
+        key = (c.cell, c.H, c.sparse, c.form)
+        assert key not in seen, "two cases for one form: %s" % C.case_id(c)
+        seen.add(key)
+    ids = [C.case_id(c) for c in C.DENSE + C.SPARSE + C.OPT_DENSE + C.OPT_SPARSE]
+    assert len(set(ids)) == len(ids)
+    assert all(not c.sparse and c.depth == (3 if (c.H, c.form[:2]) == (600, (19, 2)) else 2) for c in C.OPT_DENSE)
+    assert all(c.sparse and c.E1 in C.SPARSE_E1 and abs(4 * c.ms - c.E1) < 4 and not c.prefer_narrow for c in C.OPT_SPARSE)
+
+
+def test_every_option_case_sits_at_the_lower_end_of_its_class():
+    """the smallest E1 of the sweep that takes the form under the case's options; 40 for the first class"""
+    for c in C.OPT_DENSE:
+        o = C.level_opts(c)
+        first = next(E1 for E1 in SWEEP_E1 if C.reduced_opt(F_.level_form(c.cell == "LSTM", E1, c.H, opts=o)) == c.form)
+        assert c.E1 == (40 if first == 2 else first), (C.case_id(c), first)
+
+
+def test_every_dense_form_the_options_reach_has_a_case():
+    """cell x H in {250, 300, 600} x E1 = 2 .. 4096 and the sizes around bf16 storage and the natural two row tiles x
+    gate_dtype 0 .. 3 x prefer_narrow 0 / 1, dense training call"""
+    table = _table_opt(C.DENSE + C.OPT_DENSE)
+    reached = set()
+    for cell, H, E1, dt, pn, form in _sweep(sparse=False):
+        assert form in table[cell, H], "no dense case covers (cell, H, E1, gate_dtype, prefer_narrow, form) = %r" % (
+            (cell, H, E1, dt, pn, form),)
+        reached.add((cell, H, form))
+    # ... and the lattice reaches every case of the table: 73 + 38 forms only options reach
+    assert {(c.cell, c.H, c.form) for c in C.OPT_DENSE} <= reached
+    # (two more GRU cases: the two-row-tile single groups a DEFAULT call takes from 8177 rows at H = 250 / 600 -- DENSE
+    # holds the one of H = 300 -- stand in OPT_DENSE at 2049 rows through prefer_narrow)
+    extra = [c for c in C.OPT_DENSE if c.cell == "GRU" and c.form in ((16, 1, 0, 1, 0, 0, 0), (38, 1, 0, 1, 0, 0, 0))]
+    assert sorted((c.H, c.E1, c.prefer_narrow) for c in extra) == [(250, 2049, 1), (600, 2049, 1)]
+    assert [sum(c.cell == cell for c in C.OPT_DENSE if c not in extra) for cell in ("GRU", "LSTM")] == [73, 38]
+
+
+def test_every_sparse_form_the_options_reach_in_the_tested_classes_has_a_case():
+    """the same sweep for sparse calls, over the three (tg, groups) classes the sparse cases stand in: 33 forms"""
+    table, classes = _table_opt(C.SPARSE + C.OPT_SPARSE), _sparse_classes()
+    reached = set()
+    for cell, H, E1, dt, pn, form in _sweep(sparse=True):
+        if form[:2] in classes[cell, H]:
+            assert form in table[cell, H], "no sparse case covers (cell, H, E1, gate_dtype, prefer_narrow, form) = %r" % (
+                (cell, H, E1, dt, pn, form),)
+            reached.add((cell, H, form))
+    assert {(c.cell, c.H, c.form) for c in C.OPT_SPARSE} <= reached and len(C.OPT_SPARSE) == 33
+
+
+@pytest.mark.parametrize("sparse", [False, True])
+def test_a_forward_only_call_takes_no_forward_form_of_its_own(sparse):
+    """training = 0, with and without ggpm_level_opts.h_out (which keeps bf16 storage): every forward form -- the form
+    without fuse_bwd -- is the forward form of a training case, so the GPU tests check forward-only calls by bit
+    equality with the training forward alone."""
+    cases = C.SPARSE + C.OPT_SPARSE if sparse else C.DENSE + C.OPT_DENSE
+    table = {k: {_forward_form(f) for f in v} for k, v in _table_opt(cases).items()}
+    classes = _sparse_classes()
+    for h_out in (False, True):
+        for cell, H, E1, dt, pn, form in _sweep(sparse=sparse, training=False, h_out=h_out):
+            assert form[5] == 0        # no backward, nothing fused into it
+            if sparse and form[:2] not in classes[cell, H]:
+                continue
+            assert _forward_form(form) in table[cell, H], \
+                "a forward-only form without a training case: %r" % ((cell, H, E1, dt, pn, h_out, form),)
+
+
 def _accepted_hp(lstm):
     return [hp for hp in range(16, 2049, 16) if F_.level_form(lstm, 40, hp) is not None]
 

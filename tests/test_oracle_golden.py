@@ -145,6 +145,56 @@ def test_oracle_sparse_forward_matches_reference(name):
         assert rel_err(v.grad.numpy(), z["grad/" + k]) <= 5e-5, k
 
 
+def _sparse_oracle_run(name, gate_dtype=None, dtype=torch.float32):
+    """-> (meta, fixtures, {tensor: numpy}) of the sparse oracle on a committed case; gate_dtype None: the call as it was
+    before the argument existed"""
+    from ggpm_amd.params import rnn_param_shapes, seeded_state_dict
+    z, rnn, (E1, I, H, depth, ms, K, seed) = _sparse_case(name)
+    h, c, submess, x, bg, coef = sparse_inputs(E1, I, H, ms, K, seed)
+    p = {k: torch.from_numpy(v).to(dtype).requires_grad_(True)
+         for k, v in seeded_state_dict(rnn_param_shapes(rnn, I, H), seed).items()}
+    ht, ct, xt = (torch.from_numpy(a).to(dtype).requires_grad_(True) for a in (h, c, x))
+    sm, bgt, cf = torch.from_numpy(submess), torch.from_numpy(bg), torch.from_numpy(coef).to(dtype)
+    kw = {} if gate_dtype is None else {"gate_dtype": gate_dtype}
+    if rnn == "GRU":
+        ho = ref.gru_sparse_forward(p, "", ht, xt, sm, bgt, depth, **kw)
+        (cf[0] * ho).sum().backward()
+        out = {}
+    else:
+        ho, co = ref.lstm_sparse_forward(p, "", ht, ct, xt, sm, bgt, depth, **kw)
+        ((cf[0] * ho).sum() + (cf[1] * co).sum()).backward()
+        out = {"c_out": co.detach().numpy(), "dc_in": ct.grad.numpy()}
+    out.update({"grad/" + k: v.grad.numpy() for k, v in p.items()}, h_out=ho.detach().numpy(), dh_in=ht.grad.numpy(),
+               dx=xt.grad.numpy())
+    return rnn, z, out
+
+
+@pytest.mark.parametrize("name", ["sparse_gru_s5", "sparse_lstm_s6", "sparse_gru_s7", "sparse_lstm_s8"])
+def test_bf16_sparse_cells_of_the_oracle_are_the_reference_cells_up_to_the_rounding(name, monkeypatch):
+    """``gate_dtype`` of ref.gru_sparse_forward / lstm_sparse_forward, the dense restatement's pin repeated: "f32" returns
+    the bits the functions returned without the argument; with the rounding replaced by the identity the bf16 restatement
+    (per-message products over the full state, hidden halves split off) reproduces the reference's sparse_forward
+    fixtures like the plain oracle does; with the rounding on it moves the result by a bf16-sized amount, no more; and
+    bf16 storage, which no sparse call has, is refused."""
+    rnn, z, plain = _sparse_oracle_run(name)
+    _, _, f32 = _sparse_oracle_run(name, "f32")
+    assert sorted(plain) == sorted(f32)
+    for k in plain:
+        assert np.array_equal(plain[k], f32[k]), k
+    monkeypatch.setattr(ref, "rne_bf16", lambda t: t)
+    for mode in ("bf16", "bf16w"):
+        _, _, got = _sparse_oracle_run(name, mode)
+        for k, v in got.items():
+            assert rel_err(v, z[k]) <= (2e-5 if k in ("h_out", "c_out") else 5e-5), (mode, k)
+    monkeypatch.undo()
+    for mode in ("bf16", "bf16w"):
+        _, _, got = _sparse_oracle_run(name, mode)
+        shift = max(rel_err(got[k], z[k]) for k in ("h_out", "c_out") if k in got)
+        assert 1e-6 < shift < 2e-2, (mode, shift)
+    with pytest.raises(ValueError):
+        _sparse_oracle_run(name, "bf16s")
+
+
 # ---------------------------------------------------------------- incremental encoders (SURVEY.md 8f row N1)
 @pytest.mark.parametrize("name", inc_case_names())
 def test_oracle_incremental_encoder_matches_reference(name):
