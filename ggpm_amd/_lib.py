@@ -144,6 +144,10 @@ SIGNATURES = {
     "ggpm_mixture_logp": (I, [P, P, P, P, I, I, I, P, P, P, P, P, P]),
     "ggpm_mixture_logp_backward": (I, [P, P, P, P, P, P, P, I, I, I, I, P, P, P, P, P]),
     "ggpm_sample_mixture": (I, [P, P, P, I, P, I, I, I, P, ctypes.c_uint, ctypes.c_uint, P, P]),
+    # the guided latent search (csrc/latent_search.hip): heads are ggpm_prop_head*
+    "ggpm_latent_search_guided": (I, [I, I, P, I, I, P, P, P, P, P, P, P, P, P, I, c_float, c_float, I, c_float, c_float,
+                                      c_float, c_float, c_float, P, P, P, P, P, P]),
+    "ggpm_latent_search_select": (I, [P, P, P, P, I, I, I, P, P, P, P, P]),
     "ggpm_dropout": (I, [P, I, I, I, ctypes.c_float,ctypes.c_uint, ctypes.c_uint, I, P]),
     # property heads / latent search (csrc/property.hip): heads are ggpm_prop_head*, grads ggpm_prop_head_grads*
     "ggpm_property_heads_workspace_bytes": (c_size_t, [I, I, P, P]),

@@ -12,8 +12,8 @@ import sys
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libggpm_hip.so")
-SOURCES = ["capi.hip", "graph.hip", "gemm.hip", "gather.hip", "mpn_gru.hip", "mpn_lstm.hip", "encoder.hip", "losses.hip", "decode.hip", "tree_level.hip", "schedule.hip", "property.hip", "motif_assm.hip", "motif_decode.hip", "hier_decode.hip", "sample.hip", "mol_loss.hip", "latent_dims.hip", "latent_decomp.hip", "latent_prior.hip"]
-HEADERS = ["common.h", "wave_f64.h", "sample_stream.h", "tile_mma.h", "level_host.h", "level_call.h", os.path.join("..", "..", "include", "ggpm_hip.h")]
+SOURCES = ["capi.hip", "graph.hip", "gemm.hip", "gather.hip", "mpn_gru.hip", "mpn_lstm.hip", "encoder.hip", "losses.hip", "decode.hip", "tree_level.hip", "schedule.hip", "property.hip", "motif_assm.hip", "motif_decode.hip", "hier_decode.hip", "sample.hip", "mol_loss.hip", "latent_dims.hip", "latent_decomp.hip", "latent_prior.hip", "latent_search.hip"]
+HEADERS = ["common.h", "wave_f64.h", "head_walk.h", "sample_stream.h", "tile_mma.h", "level_host.h", "level_call.h", os.path.join("..", "..", "include", "ggpm_hip.h")]
 ARCH = "gfx950"
 
 

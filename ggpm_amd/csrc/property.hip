@@ -13,28 +13,16 @@
 // Floating point: contraction is off in this file, so `a * b + c` is two roundings as in the reference's torch ops; the
 // dot products use explicit fma.  The patience ratio |loss - prev| / prev is an IEEE division (prev == 0 gives inf or
 // NaN, as torch does) and every comparison is an ordinary IEEE comparison (NaN compares false).
-#include "common.h"
+#include "head_walk.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int PROP_MAX_LINEAR = GGPM_PROP_MAX_LINEAR;
-constexpr int PROP_MAX_IN = 256;
-constexpr int PROP_MAX_W = 512;
 constexpr int PROP_MAX_B = 1024;            // heads forward / backward (one workgroup per head walks every row)
 constexpr int PROP_MAX_SEARCH_B = 1 << 20;  // latent search (one workgroup per row)
 constexpr int HEAD_THREADS = 512;
 constexpr int HEAD_RB = 8;                  // rows per chunk of the heads forward (LDS ping-pong of HEAD_RB x 512 floats)
-constexpr int SEARCH_THREADS = 256;         // two halves of 128 lanes: homo head, lumo head
-constexpr size_t SEARCH_LDS_MAX = 160 * 1024;
-
-struct HeadK {
-    int n;                                   // number of Linear layers
-    int w[PROP_MAX_LINEAR + 1];              // w[0] input, w[n] = 1
-    const float* W[PROP_MAX_LINEAR];
-    const float* b[PROP_MAX_LINEAR];
-};
 
 struct GradK {
     float* dW[PROP_MAX_LINEAR];
@@ -53,12 +41,6 @@ __device__ __forceinline__ bool keep_elem(unsigned int idx, unsigned int thresh,
     unsigned int h = fmix32(idx * 0x9E3779B1u + seed_lo);
     h = fmix32(h ^ (seed_hi + site * 0x7F4A7C15u));
     return (h >> 8) >= thresh;
-}
-
-__device__ __forceinline__ float wave_sum_fixed(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
 }
 
 // ------------------------------------------------------------------ heads forward
@@ -207,76 +189,27 @@ __global__ void __launch_bounds__(HEAD_THREADS) prop_heads_bwd_k(HeadsBwdArgs a)
 
 // ------------------------------------------------------------------ latent search
 struct SearchArgs {
-    HeadK head[2];
-    int mode, B, ld, half, steps, max_steps, in_lds;
+    HeadWalk w;                              // the heads and their LDS plan (head_walk.h)
+    int mode, B, ld, half, steps, max_steps;
     const float* z;
     const float* t[2];
     float lr, delta, patience, threshold, norm;
-    int woff[2][PROP_MAX_LINEAR], boff[2][PROP_MAX_LINEAR];   // LDS offsets of the weights (in_lds)
-    int wld[2][PROP_MAX_LINEAR];                                // row stride of W[l] as read (LDS: odd, conflict-free)
-    int aoff[2][PROP_MAX_LINEAR];                               // LDS offsets of the inputs of every Linear
-    int goff[2][2];                                             // LDS gradient ping-pong
-    int ooff;                                                   // LDS: the two head outputs
     float* z_out;
     float* pred;
     int32_t* steps_taken;
     int32_t* status;
 };
 
-// forward of both heads on the resident row: fills act[h][1..n-1] and o[h]
-__device__ __forceinline__ void search_forward(const SearchArgs& a, float* lds, float* const* Wp, float* const* bp, int h,
-                                               int lt, int maxn) {
-    const HeadK& H = a.head[h];
-    for (int l = 0; l < maxn; ++l) {
-        if (l < H.n) {
-            const int win = H.w[l], wout = H.w[l + 1];
-            const float* W = Wp[l];
-            const float* bias = bp[l];
-            const float* x = lds + a.aoff[h][l];
-            if (l < H.n - 1) {
-                float* y = lds + a.aoff[h][l + 1];
-                for (int j = lt; j < wout; j += 128) {
-                    const float* wr = W + (size_t)j * a.wld[h][l];
-                    float s = 0.f;
-                    for (int k = 0; k < win; ++k) s = __builtin_fmaf(wr[k], x[k], s);
-                    s = s + bias[j];
-                    y[j] = s > 0.f ? s : 0.f;
-                }
-            } else if (lt < 64) {           // Linear(w, 1): one full wave, lane-strided partials + fixed butterfly
-                float s = 0.f;
-                for (int k = lt; k < win; k += 64) s = __builtin_fmaf(W[k], x[k], s);
-                s = wave_sum_fixed(s);
-                if (lt == 0) lds[a.ooff + h] = s + bias[0];
-            }
-        }
-        __syncthreads();
-    }
-}
-
 __global__ void __launch_bounds__(SEARCH_THREADS) prop_search_k(SearchArgs a) {
     extern __shared__ float lds[];
     const int r = blockIdx.x;
     const int tid = threadIdx.x, lt = tid & 127;
     const int h = __builtin_amdgcn_readfirstlane(tid >> 7);     // wave-uniform: the halves are two whole waves each
-    const HeadK& H = a.head[h];
-    const int maxn = max(a.head[0].n, a.head[1].n);
+    const int maxn = max(a.w.head[0].n, a.w.head[1].n);
     float* Wp[PROP_MAX_LINEAR];
     float* bp[PROP_MAX_LINEAR];
-    for (int l = 0; l < PROP_MAX_LINEAR; ++l) {
-        Wp[l] = bp[l] = nullptr;
-        if (l < H.n) {
-            Wp[l] = a.in_lds ? lds + a.woff[h][l] : const_cast<float*>(H.W[l]);
-            bp[l] = a.in_lds ? lds + a.boff[h][l] : const_cast<float*>(H.b[l]);
-        }
-    }
-    if (a.in_lds) {
-        for (int l = 0; l < H.n; ++l) {
-            const int win = H.w[l], nw = win * H.w[l + 1], nb = H.w[l + 1], ldw = a.wld[h][l];
-            for (int i = lt; i < nw; i += 128) Wp[l][(i / win) * ldw + i % win] = H.W[l][i];
-            for (int i = lt; i < nb; i += 128) bp[l][i] = H.b[l][i];
-        }
-    }
-    float* v = lds + a.aoff[h][0];
+    head_walk_weights(a.w, lds, h, lt, Wp, bp);
+    float* v = lds + a.w.aoff[h][0];
     const float* zr = a.z + (size_t)r * a.ld + h * a.half;
     for (int k = lt; k < a.half; k += 128) v[k] = zr[k];
     __syncthreads();
@@ -288,8 +221,8 @@ __global__ void __launch_bounds__(SEARCH_THREADS) prop_search_k(SearchArgs a) {
     int n = 0;
     bool stopped = false;                    // soft mode's delta exit
     while (n < limit && (fixed || pat > 0.f)) {
-        search_forward(a, lds, Wp, bp, h, lt, maxn);
-        const float oh = lds[a.ooff], ol = lds[a.ooff + 1];
+        head_walk_forward(a.w, lds, Wp, bp, h, lt, maxn);
+        const float oh = lds[a.w.ooff], ol = lds[a.w.ooff + 1];
         ++n;
         if (!fixed) {
             const float dh = oh - th, dl = ol - tl;
@@ -301,83 +234,31 @@ __global__ void __launch_bounds__(SEARCH_THREADS) prop_search_k(SearchArgs a) {
         }
         // d loss / d v of this head: g = norm (o - t), back through Linear(w, 1), then every hidden layer
         const float o = h == 0 ? oh : ol;
-        const float g = a.norm * (o - tx);
-        {
-            const int l = H.n - 1, win = H.w[l];
-            float* gin = lds + a.goff[h][0];
-            for (int k = lt; k < win; k += 128) gin[k] = g * Wp[l][k];
-        }
-        __syncthreads();
-        int cur = 0;
-        for (int s = 1; s < maxn; ++s) {
-            const int l = H.n - 1 - s;      // Linear l: input w[l], output w[l + 1] (its output went through ReLU)
-            if (l >= 0) {
-                const int win = H.w[l], wout = H.w[l + 1];
-                const float* gout = lds + a.goff[h][cur];
-                const float* act = lds + a.aoff[h][l + 1];
-                float* gin = lds + a.goff[h][cur ^ 1];
-                const float* W = Wp[l];
-                for (int k = lt; k < win; k += 128) {
-                    float acc = 0.f;
-                    for (int j = 0; j < wout; ++j)
-                        acc = __builtin_fmaf(act[j] > 0.f ? gout[j] : 0.f, W[(size_t)j * a.wld[h][l] + k], acc);
-                    gin[k] = acc;
-                }
-            }
-            __syncthreads();
-            if (l >= 0) cur ^= 1;
-        }
+        const int cur = head_walk_backward(a.w, lds, Wp, h, lt, maxn, a.norm * (o - tx));
         // the reference's signed update, both heads every body: v - s lr g, s = -1 if o < t else +1
         const float step = (o < tx ? -1.f : 1.f) * a.lr;
-        const float* gin = lds + a.goff[h][cur];
+        const float* gin = lds + a.w.goff[h][cur];
         for (int k = lt; k < a.half; k += 128) v[k] = v[k] - step * gin[k];
         __syncthreads();
     }
     // final predictions on the final latent (the reference's predict() after the search)
-    search_forward(a, lds, Wp, bp, h, lt, maxn);
+    head_walk_forward(a.w, lds, Wp, bp, h, lt, maxn);
     float* zo = a.z_out + (size_t)r * a.ld;
     for (int k = lt; k < a.half; k += 128) zo[h * a.half + k] = v[k];
     if (tid == 0) {
         for (int k = 2 * a.half; k < a.ld; ++k) zo[k] = a.z[(size_t)r * a.ld + k];
-        a.pred[r] = lds[a.ooff];
-        a.pred[(size_t)a.B + r] = lds[a.ooff + 1];
+        a.pred[r] = lds[a.w.ooff];
+        a.pred[(size_t)a.B + r] = lds[a.w.ooff + 1];
         a.steps_taken[r] = n;
         const bool capped = fixed ? a.steps > a.max_steps : (!stopped && pat > 0.f && n >= a.max_steps);
         a.status[r] = capped ? GGPM_PROP_CAPPED : GGPM_PROP_DONE;
     }
 }
 
-int head_from(const ggpm_prop_head* in, int half, HeadK& out) {
-    if (!in) return GGPM_ERR_ARG;
-    const int n = in->n_linear;
-    if (n < 2 || n > PROP_MAX_LINEAR) return GGPM_ERR_UNSUPPORTED;
-    if (in->width[0] != half || in->width[n] != 1) return GGPM_ERR_ARG;
-    if (half < 1 || half > PROP_MAX_IN) return GGPM_ERR_UNSUPPORTED;
-    out = HeadK{};
-    out.n = n;
-    for (int l = 0; l <= n; ++l) {
-        if (in->width[l] < 1) return GGPM_ERR_ARG;
-        if (l > 0 && l < n && in->width[l] > PROP_MAX_W) return GGPM_ERR_UNSUPPORTED;
-        out.w[l] = in->width[l];
-    }
-    for (int l = 0; l < n; ++l) {
-        if (!in->W[l] || !in->b[l]) return GGPM_ERR_ARG;
-        out.W[l] = in->W[l];
-        out.b[l] = in->b[l];
-    }
-    return GGPM_OK;
-}
-
 size_t head_stash_floats(const HeadK& H, int B) {
     size_t f = 0;
     for (int l = 1; l < H.n; ++l) f += (size_t)B * H.w[l];
     return f;
-}
-
-int head_max_width(const HeadK& H) {
-    int m = 1;
-    for (int l = 0; l < H.n; ++l) m = max(m, H.w[l]);
-    return m;
 }
 
 size_t align_floats(size_t f) { return (f + 63) & ~(size_t)63; }     // 256-byte aligned sub-buffers
@@ -473,45 +354,14 @@ extern "C" int ggpm_property_latent_search(int mode, int B, const float* z, int 
     GGPM_CLEAR_STALE_ERROR();
     SearchArgs a{};
     int e;
-    if ((e = head_from(homo, half, a.head[0])) != GGPM_OK || (e = head_from(lumo, half, a.head[1])) != GGPM_OK) return e;
+    if ((e = head_from(homo, half, a.w.head[0])) != GGPM_OK || (e = head_from(lumo, half, a.w.head[1])) != GGPM_OK) return e;
     if (mode != GGPM_PROP_SEARCH_FIXED && mode != GGPM_PROP_SEARCH_SOFT && mode != GGPM_PROP_SEARCH_PATIENCE)
         return GGPM_ERR_ARG;
     if (!z || !t_homo || !t_lumo || !z_out || !pred_out || !steps_taken || !status || B < 1 || ld < 2 * half ||
         max_steps < 1 || (mode == GGPM_PROP_SEARCH_FIXED && steps < 0))
         return GGPM_ERR_ARG;
     if (B > PROP_MAX_SEARCH_B) return GGPM_ERR_UNSUPPORTED;
-    // LDS: [weights of both heads, if they fit] [inputs of every Linear] [gradient ping-pong] [two outputs]
-    size_t off = 0;
-    for (int h = 0; h < 2; ++h)
-        for (int l = 0; l < a.head[h].n; ++l) {
-            // rows of W in LDS at an odd stride: the forward's lanes (one row each) then hit distinct banks
-            a.wld[h][l] = a.head[h].w[l] | 1;
-            a.woff[h][l] = (int)off; off += (size_t)a.wld[h][l] * a.head[h].w[l + 1];
-            a.boff[h][l] = (int)off; off += (size_t)a.head[h].w[l + 1];
-        }
-    const size_t weight_floats = off;
-    size_t rest = 0;
-    int aoff[2][PROP_MAX_LINEAR] = {}, goff[2][2] = {};
-    for (int h = 0; h < 2; ++h) {
-        for (int l = 0; l < a.head[h].n; ++l) { aoff[h][l] = (int)rest; rest += (size_t)a.head[h].w[l]; }
-        const int wm = head_max_width(a.head[h]);
-        goff[h][0] = (int)rest; rest += wm;
-        goff[h][1] = (int)rest; rest += wm;
-    }
-    const int ooff = (int)rest;
-    rest += 2;
-    a.in_lds = (weight_floats + rest) * sizeof(float) <= SEARCH_LDS_MAX;
-    if (!a.in_lds)
-        for (int h = 0; h < 2; ++h)
-            for (int l = 0; l < a.head[h].n; ++l) a.wld[h][l] = a.head[h].w[l];
-    const size_t base = a.in_lds ? weight_floats : 0;
-    for (int h = 0; h < 2; ++h) {
-        for (int l = 0; l < PROP_MAX_LINEAR; ++l) a.aoff[h][l] = (int)base + aoff[h][l];
-        a.goff[h][0] = (int)base + goff[h][0];
-        a.goff[h][1] = (int)base + goff[h][1];
-    }
-    a.ooff = (int)base + ooff;
-    const size_t lds_bytes = (base + rest) * sizeof(float);
+    const size_t lds_bytes = head_walk_plan(a.w, 0, nullptr);
     if (lds_bytes > SEARCH_LDS_MAX) return GGPM_ERR_UNSUPPORTED;
     a.mode = mode; a.B = B; a.ld = ld; a.half = half; a.steps = steps; a.max_steps = max_steps;
     a.z = z; a.t[0] = t_homo; a.t[1] = t_lumo;

@@ -1133,6 +1133,48 @@ int ggpm_sample_mixture(const float* logits, const float* means, const float* lo
                         int ld, const int32_t* ids, unsigned int seed_lo, unsigned int seed_hi, int32_t* comp,
                         ggpm_stream_t stream);
 
+/* The guided latent search (PropertyVAEOptimizer.search; csrc/latent_search.hip): R = K B trajectories, row r
+ * of z0 [R x ld] belonging to molecule b = r mod B (the layout of z [K, B, L]), L = 2 half, v = the row's first L columns:
+ *     prop(v)   = w_h (f_homo(v[0:half]) - t_homo[b])^2 + w_l (f_lumo(v[half:L]) - t_lumo[b])^2
+ *     anchor(v) = 0.5 sum_j (v_j - mu[b,j])^2 exp(-lv[b,j])
+ *     prior(v)  = -log p(v): 0.5 sum_j (log 2pi + v_j^2) with the mixture pointers null, else -lp of ggpm_mixture_logp
+ *     J(v)      = prop + anchor_weight anchor + prior_weight prior
+ * ggpm_latent_search_guided (ONE launch for all rows and every step; one workgroup of 256 threads per row, the heads walked
+ * as ggpm_property_latent_search walks them; heads in eval form, no dropout):
+ *     m = 0; n = 0
+ *     repeat `steps` times:
+ *       o_x = f_x(v_x); prop = w_h (o_h - t_h)^2 + w_l (o_l - t_l)^2
+ *       if delta >= 0 and prop <= delta: stop (no update)
+ *       g = 2 w_x (o_x - t_x) df_x/dv  [+ anchor_weight (v - mu) exp(-lv)]  [+ prior_weight d prior/dv]
+ *       m = momentum m + g;  v = v - lr m;  n += 1
+ * (a term whose weight is exactly 0 is not evaluated inside the loop), then the heads and the three terms on the final v:
+ *     z_out [R x ld] (columns past L copied from z0), pred[2][R] (homo row, then lumo row), terms [R x 3] = prop, anchor,
+ *     prior (unweighted), J [R] = (prop + anchor_weight anchor) + prior_weight prior, steps_taken [R] = n.
+ * Arithmetic: heads, anchor gradient, standard-normal gradient (v) and the update are fp32 with contraction off (every
+ * product and sum above is one rounding, in the order written; exp(-lv) is expf, formed once); the dot products are fma
+ * chains as in ggpm_property_latent_search.  The mixture's gradient sum_c gamma_c (v_j - m[c,j]) exp(-s[c,j]) -- comp, the
+ * logsumexp and gamma included -- is fp64 from the fp32 inputs in a fixed order and rounded once to fp32 before it is weighed.
+ * The reported anchor and prior are summed in fp64 from the fp32 v, mu and expf(-lv) and rounded once; prop and J are fp32.
+ * No atomics: the same inputs give the same bits, and a row's results do not depend on B, K or the other rows.
+ * LDS: the heads' plan of ggpm_property_latent_search plus 4 L floats (momentum, mu, exp(-lv), the mixture gradient) and
+ * C + 1 doubles.  The weights of both heads stay in LDS when all of it fits in 160 KiB, otherwise they are read from global
+ * memory; if even that does not fit, GGPM_ERR_UNSUPPORTED.
+ * K, B >= 1, K B <= 2^20, ld >= L, steps >= 0; logits [C], means [C x L], log_vars [C x L] all null or all given with
+ * 1 <= C <= GGPM_MIXTURE_MAX_C; delta < 0 (or NaN) disables the exit.  A null required pointer, a bad size or a partly given
+ * mixture returns GGPM_ERR_ARG; heads outside the envelope above (2 <= n_linear <= GGPM_PROP_MAX_LINEAR, half <= 256, hidden
+ * widths <= 512) or K B > 2^20 return GGPM_ERR_UNSUPPORTED; nothing is launched then.
+ * ggpm_latent_search_select (one launch, one thread per molecule): best_k[b] (int32) = the k in 0..K-1 with the smallest
+ * J[k B + b]; ties go to the lowest k; a NaN ranks behind every number (+-inf included); all K NaN gives 0.  With
+ * r = best_k[b] B + b: z_best[b, 0:ld] = z[r, 0:ld], pred_best[2][B] = pred[.][r], terms_best[b, 0:3] = terms[r, 0:3].
+ * Every pointer required, K, B, ld >= 1, K B <= 2^20, else GGPM_ERR_ARG. */
+int ggpm_latent_search_guided(int K, int B, const float* z0, int ld, int half, const float* mu, const float* lv,
+                              const ggpm_prop_head* homo, const ggpm_prop_head* lumo, const float* t_homo, const float* t_lumo,
+                              const float* logits, const float* means, const float* log_vars, int C, float lr, float momentum,
+                              int steps, float delta, float w_h, float w_l, float anchor_weight, float prior_weight,
+                              float* z_out, float* pred, float* terms, float* J, int32_t* steps_taken, ggpm_stream_t stream);
+int ggpm_latent_search_select(const float* J, const float* z, const float* pred, const float* terms, int K, int B, int ld,
+                              int32_t* best_k, float* z_best, float* pred_best, float* terms_best, ggpm_stream_t stream);
+
 /* ------------------------------------------------------------------ whole-encoder drivers
  * HierMPNEncoder.forward (ggpm/encoder.py:140-157, with embed_graph/inter/tree/root :96-138) and its backward as ONE
  * call each: the same kernels the op-by-op host path issues, sequenced from C++ (GRU or LSTM message function).
